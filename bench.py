@@ -2,6 +2,8 @@
 """Headline benchmark: pooled nodes/sec of Reduce + Connect on batched graphs (BASELINE.json).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full         # + windows, rooflines, CPU baseline, secondaries
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as .npy
     python bench.py --gpus 8 ...                       # starts 8 ranks itself (child processes, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -11,18 +13,24 @@ K = 128, F = 64 (fp32, the precision the reference computes in).  Select and the
 excluded; inputs are resident in HBM when the timed region starts.  With N > 1 every rank pools its
 own B graphs (weak scaling, seed = rank) and the pooled outputs are all-gathered over RCCL inside the timed region.
 
-Rank 0 prints one JSON line per secondary workload as it is measured (short keys, no prose) and, as the LAST stdout
-line, the headline (< 4 KB: contract fields, windows, roofline, whole_step, cpu_baseline); everything, prose included,
-also goes to gpurun_out/bench_detail.json ($TGP_BENCH_DETAIL).  The headline line:
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs if given, and rank 0 prints ONE JSON line,
+the contract fields.  `--dump-outputs DIR` writes what the last timed step returned (x_pool, adj_pool for c2) as
+DIR/<name>.npy, float32 or float64, at most 64 MB in all (a fixed sample of each array beyond that); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+With --full, rank 0 prints one JSON line per secondary workload as it is measured (short keys, no prose) and, as the
+LAST stdout line, the headline (< 4 KB: contract fields, windows, roofline, whole_step, cpu_baseline); everything, prose
+included, also goes to the detail file (write_detail: $TGP_BENCH_DETAIL or its default path).  The headline line:
   contract fields  `value` / `ms_per_step` come from ONE window of EXACTLY --steps steps after --warmup warm-up steps
                    (+ "settle_steps" more untimed steps: ~50 ms of the same workload, so that the window does not sit
                    on the device's clock ramp), bracketed by barrier + device synchronise on both sides, MAX over ranks;
+                   a plain run prints these alone;
   "windows"        the same step re-timed as the median of 5 windows of >= 200 steps (tens of ms per window);
   "roofline"       fp32-MFMA roofline of the dominant kernel (U = A S, 2*B*N*N*K flop per launch), timed live with HIP
                    events on the launch stream;
   "cpu_baseline"   the CPU oracle (port of the reference algorithm) on a bounded sample of the same workload on this
                    box's host cores (rank 0, N = 1 only);
-Secondary lines ({"secondary": name, ...}): the other north_star workloads, each with its own median-window timing and roofline:
+Secondary lines (--full; {"secondary": name, ...}): the other north_star workloads, each with its own median-window timing and roofline:
                    c5 (N=8192,K=512,F=128: fp32 MFMA), topk1m (TopK scatter-reduce: HBM), topk_connect (TopK subgraph
                    Connect: HBM), c4_graclus (Reduce + coalesce Connect, both rooflines: HBM), c3 (MinCut small graphs:
                    HBM), c4_ndp (NDP-shaped Reduce), topk_batch / graclus_batch (batched sparse Reduce + Connect; with
@@ -126,22 +134,24 @@ class Ctx:
         return float(t)
 
 
-def timed_window(ctx: Ctx, step, steps: int, drain=None) -> float:
-    """EXACTLY `steps` steps bracketed by barrier + device synchronise on both sides; MAX over ranks (seconds)."""
+def timed_window(ctx: Ctx, step, steps: int, drain=None):
+    """EXACTLY `steps` (>= 1) steps bracketed by barrier + device synchronise on both sides: (MAX over ranks of the
+    seconds, what the last step returned)."""
     ctx.barrier()
     ctx.sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    last = step()  # only the last step's outputs are held (the others are freed as they would be without this)
     if drain is not None:
         drain()  # e.g. the last, partly filled all-gather bucket: it belongs to the timed region
     ctx.sync()
     ctx.barrier()
-    return ctx.max_over_ranks(time.perf_counter() - t0)
+    return ctx.max_over_ranks(time.perf_counter() - t0), last
 
 
 def median_windows(ctx: Ctx, step, drain=None, steps=WINDOW_STEPS, windows=WINDOWS) -> dict:
-    ms = [timed_window(ctx, step, steps, drain) / steps * 1e3 for _ in range(windows)]
+    ms = [timed_window(ctx, step, steps, drain)[0] / steps * 1e3 for _ in range(windows)]
     return {"steps_per_window": steps, "windows": windows, "ms_per_step_median": round(statistics.median(ms), 5),
             "ms_per_step_min": round(min(ms), 5), "ms_per_step_max": round(max(ms), 5)}
 
@@ -212,15 +222,21 @@ def dense_inputs(B, N, K, F, seed, dev):
 
 
 class Workload:
-    """name, step(), drain() (or None), nodes per step on this rank, rooflines() -> dict or list, extra config."""
+    """name, step() -> what the timed path hands its caller, drain() (or None), nodes per step on this rank,
+    rooflines() -> dict or list, extra config; `output_names` label the tuple step() returns (--dump-outputs)."""
     name = ""
     nodes = 0
     shards = False
     drain = None
     extra = None
+    output_names = ()
 
     def step(self):
         raise NotImplementedError
+
+    def outputs(self, res) -> dict:
+        """{name: tensor or None} of what one step returned."""
+        return dict(zip(self.output_names, res))
 
     def rooflines(self, dev):
         raise NotImplementedError
@@ -229,6 +245,7 @@ class Workload:
 class DenseDiffPool(Workload):
     """C2 / C5: fused A3 + A7 + A8 with DiffPool defaults (diffpool.py:98-115)."""
     shards = True
+    output_names = ("x_pool", "adj_pool")
 
     def __init__(self, which, ctx, unfused=False, force_collective=False):
         from tgp.connect import DenseConnect
@@ -282,6 +299,7 @@ class DenseDiffPool(Workload):
                 # asynchronous on RCCL's stream: overlaps the next steps' kernels (one collective in flight)
                 self.gather.start([x_pool, adj_pool])
                 self.gather.take_ready()  # a consumer would use these; the bench only must not accumulate them
+        return x_pool, adj_pool
 
     def cpu_pass(self):
         """reference base_reduce.py:158-161 + dense_conn.py:111-122 + ops.py:282-335 on the first graphs of THIS batch."""
@@ -322,6 +340,7 @@ class DenseDiffPool(Workload):
 class SmallGraphsMinCut(Workload):
     """C3: MinCut order on the PROTEINS-shape padded batch: x_pool, raw S^T A S, post-processed A' (one launch)."""
     shards = True
+    output_names = ("x_pool", "adj_raw", "adj_pool")
 
     def __init__(self, ctx, unfused=False):
         from tgp.connect import DenseConnect
@@ -351,11 +370,10 @@ class SmallGraphsMinCut(Workload):
         from tgp.utils.ops import postprocess_adj_pool_dense
         with torch.no_grad():
             if self.unfused:
-                self.red(self.X, self.so)
+                x_pool, _ = self.red(self.X, self.so)
                 raw = self.conn.dense_connect(adj=self.A, s=self.S)  # MinCut order: raw -> (loss) -> post-process
-                postprocess_adj_pool_dense(raw, True, True, True, False)
-            else:
-                self.pool.reduce_connect(self.X, self.A, self.so, want_raw=True)
+                return x_pool, raw, postprocess_adj_pool_dense(raw, True, True, True, False)
+            return self.pool.reduce_connect(self.X, self.A, self.so, want_raw=True)
 
     def cpu_pass(self):
         """MinCut order on the CPU: S^T X, raw S^T A S, post-processing (mincut.py:220-237 over the dense operators)."""
@@ -444,6 +462,12 @@ class PoolerForward(Workload):
         with torch.no_grad():
             return self.pooler(x=self.x, adj=self.ei, batch=self.batch)
 
+    def outputs(self, res):
+        out = {"x": res.x, "edge_index": res.edge_index, "edge_weight": res.edge_weight, "batch": res.batch,
+               "mask": res.mask}
+        out.update({f"loss_{k}": v for k, v in (res.loss or {}).items()})
+        return out
+
     def rooflines(self, dev):
         B, N, K, F = self.B, self.N, self.K, self.F
         ms = event_time_ms(self.step, 50, dev)
@@ -522,6 +546,12 @@ class PoolerTrainStep(Workload):
         loss.backward()
         return loss
 
+    def outputs(self, res):
+        """The loss and the gradients the step's backward left (read before any later step clears them)."""
+        out = {"loss": res, "x_grad": self.x.grad}
+        out.update({f"grad_{n}": p.grad for n, p in self.pooler.named_parameters()})
+        return out
+
     def rooflines(self, dev):
         B, N, K, F = self.B, self.N, self.K, self.F
         ms = event_time_ms(self.step, 50, dev)
@@ -591,6 +621,7 @@ class TopkBatch(Workload):
     the variable-size pooled outputs are all-gathered over RCCL inside the timed region (counts, then padded
     payloads, then node-id / graph-id offsets: the merge rule of tgp/data/collate.py:144-153)."""
     shards = True
+    output_names = ("x_pool", "edge_index_pool", "edge_weight_pool", "batch_pool")
 
     FRESH_COPIES = 24  # more distinct tensor objects than any per-tensor memo of the package holds (16)
 
@@ -774,6 +805,7 @@ def _big_graph(dev, g, sort_rows=True):
 
 class SparseReduceOnly(Workload):
     """topk1m / c4_ndp: the sparse Reduce (A1 + A2) with a one-to-one assignment (TopK, NDP)."""
+    output_names = ("x_pool", "batch_pool")
 
     def __init__(self, which, ctx):
         from tgp.reduce import BaseReduce
@@ -805,7 +837,7 @@ class SparseReduceOnly(Workload):
         so = self.so
         so._drop_caches()
         so._set_one_to_one_index()  # what TopkSelect / NDPSelect attach: one node per supernode, no sort
-        self.red(self.x, so, batch=self.batch)
+        return self.red(self.x, so, batch=self.batch)
 
     def cpu_pass(self):
         """reference base_reduce.py:14-53,141-155 (gather x weight, scatter-add, reduce_batch) on the measured inputs."""
@@ -833,6 +865,7 @@ class SparseReduceOnly(Workload):
 
 class TopkConnect(Workload):
     """A5 + A6: TopK subgraph Connect on N = 1M, E = 10M, ratio 0.5 (count, one sync, fill)."""
+    output_names = ("edge_index_pool", "edge_weight_pool")
 
     def __init__(self, ctx):
         from tgp.connect import SparseConnect
@@ -892,6 +925,7 @@ class TopkConnect(Workload):
 
 class GraclusC4(Workload):
     """C4: Graclus-shaped many-to-one S on one N=1M E=10M graph: Reduce (A1+A2) + coalesce Connect (A4+A6)."""
+    output_names = ("x_pool", "batch_pool", "edge_index_pool", "edge_weight_pool")
 
     def __init__(self, ctx, unsorted_edges=False):
         from tgp.connect import SparseConnect
@@ -923,7 +957,7 @@ class GraclusC4(Workload):
         so = self.so
         so._drop_caches()  # rebuild the inverted index every step (no cross-step caching)
         xp, bp = self.red(self.x, so, batch=self.batch)
-        return self.conn(self.ei, so, edge_weight=self.ew, batch_pooled=bp)
+        return (xp, bp) + tuple(self.conn(self.ei, so, edge_weight=self.ew, batch_pooled=bp))
 
     def cpu_pass(self):
         """reference base_reduce.py:14-53,141-155 + base_conn.py:83-89 (relabel + coalesce) + ops.py:338-419."""
@@ -1105,7 +1139,8 @@ def headline_text(line):
     """The LAST stdout line: the contract fields + windows, roofline, whole_step, cpu_baseline; < HEADLINE_LIMIT."""
     out = {k: line[k] for k in HEADLINE_KEYS if k in line}
     out["config"] = _slim(line["config"])
-    out["roofline"] = _slim(line["roofline"], _ROOF_KEYS)
+    if "roofline" in line:  # (--full)
+        out["roofline"] = _slim(line["roofline"], _ROOF_KEYS)
     if "cpu_baseline" in line:
         out["cpu_baseline"] = _slim(line["cpu_baseline"], _CPU_KEYS)
     text = json.dumps(out)
@@ -1154,6 +1189,37 @@ def write_detail(line, secondary):
         return None
 
 
+DUMP_LIMIT = 60_000_000  # bytes of array data written by --dump-outputs, all files together (< 64 MB with headers)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """`arrays` ({name: tensor or None}: what one step returned) -> `path`/<name>.npy.  Floating types of up to 32 bits,
+    bool and small integers are written as float32, everything else (int64 indices, float64) as float64, so that
+    indices stay exact.  Above `limit` bytes in all, every array is cut to the same fraction of its elements: a
+    sample fixed by seed 0 and the array's size, flattened, in index order, identical from run to run."""
+    import numpy as np
+    items = []
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = (t if isinstance(t, torch.Tensor) else torch.as_tensor(t)).detach()
+        narrow = t.dtype == torch.bool or t.element_size() <= (4 if t.is_floating_point() else 2)
+        items.append((name.replace("/", "_"), t.to(torch.float32 if narrow else torch.float64)))
+    if not items:
+        raise SystemExit("--dump-outputs: the workload's step returned no arrays")
+    total = sum(t.numel() * t.element_size() for _, t in items)
+    frac = limit / total if total > limit else 1.0
+    os.makedirs(path, exist_ok=True)
+    for name, t in items:
+        if frac < 1.0:
+            flat = t.reshape(-1)
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))
+            pick = pick[: int(flat.numel() * frac)].sort().values
+            t = flat[pick.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    return {"dir": path, "arrays": len(items), "sampled": frac < 1.0}
+
+
 # ------------------------------------------------------------------------------------------------ main
 ALL = ["c2", "c2_f64", "c5", "c3", "c4_graclus", "c4_ndp", "topk1m", "topk_connect", "topk_batch", "graclus_batch",
        "topk_batch_fresh", "graclus_batch_fresh", "e2e_diff_c2", "e2e_mincut_c3", "e2e_train_mincut_c3",
@@ -1168,12 +1234,17 @@ SHARDED = ("c5", "c2_f64", "c3", "topk_batch", "graclus_batch", "topk_batch_fres
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c2", choices=ALL)
+    ap.add_argument("--full", action="store_true",
+                    help="also the median windows, rooflines, CPU baseline, secondary workloads and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0's outputs)")
     ap.add_argument("--secondary", default=None,
-                    help="comma-separated secondary workloads ('none' to skip); default: all of them on the c2 line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: comma-separated secondary workloads ('none' to skip); default: all of them on "
+                         "the c2 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--unfused", action="store_true",
                     help="dense workloads: call the Reduce and Connect operators one after the other")
     ap.add_argument("--unsorted-edges", action="store_true",
@@ -1189,6 +1260,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and args.secondary not in (None, "none"):
+        raise SystemExit("--secondary runs with --full only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))  # no GPU call has been made in this process
 
@@ -1250,25 +1325,35 @@ def main():
         ctx.sync()
     if wl.drain is not None:
         wl.drain()  # warm-up ends with an empty gather bucket, its collective done (communicator set-up is not a step)
-    dt = timed_window(ctx, wl.step, args.steps, wl.drain)  # THE contract window: exactly --steps steps
-    win = median_windows(ctx, wl.step, wl.drain, steps=max(WINDOW_STEPS if args.workload != "c5" else 50, 1))
-    roofs = wl.rooflines(dev)
-    roofs = roofs if isinstance(roofs, list) else [roofs]
+    dt, last = timed_window(ctx, wl.step, args.steps, wl.drain)  # THE contract window: exactly --steps steps
     value = wl.nodes * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        info = dump_outputs(args.dump_outputs, wl.outputs(last))
+        print(f"bench.py: {info['arrays']} arrays of the last timed step in {info['dir']}"
+              + (" (a fixed sample of each)" if info["sampled"] else ""), file=sys.stderr)
+    del last
 
-    if args.secondary is None:
-        sec = SECONDARY_DEFAULT if args.workload == "c2" else []
-    else:
-        sec = [s for s in args.secondary.split(",") if s and s != "none"]
-    if world > 1:
-        sec = [s for s in sec if s in SHARDED]  # the graph-sharded ones
+    # --full: everything beyond the contract window (a plain run prints the contract fields only)
+    cpu_job = None  # host copies of the measured inputs now; the CPU passes run after the GPU work of the line
+    if args.full:
+        win = median_windows(ctx, wl.step, wl.drain, steps=max(WINDOW_STEPS if args.workload != "c5" else 50, 1))
+        roofs = wl.rooflines(dev)
+        roofs = roofs if isinstance(roofs, list) else [roofs]
+        if world == 1 and rank == 0 and not args.no_cpu_baseline and hasattr(wl, "cpu_pass"):
+            cpu_job = wl.cpu_pass()
     headline_cfg = dict(workload=wl.name, **(wl.extra or {}), parallelism=f"graph-sharded x{world}")
     dims = (wl.B, wl.N, wl.K, wl.F) if isinstance(wl, DenseDiffPool) else None
-    cpu_job = None  # host copies of the measured inputs now; the CPU passes run after the GPU work of the line
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and hasattr(wl, "cpu_pass"):
-        cpu_job = wl.cpu_pass()
     del wl
     torch.cuda.empty_cache()
+
+    sec = []
+    if args.full:
+        if args.secondary is None:
+            sec = SECONDARY_DEFAULT if args.workload == "c2" else []
+        else:
+            sec = [s for s in args.secondary.split(",") if s and s != "none"]
+        if world > 1:
+            sec = [s for s in sec if s in SHARDED]  # the graph-sharded ones
     secondary = []
     for s in sec:
         try:
@@ -1284,20 +1369,21 @@ def main():
             "metric": METRIC, "value": round(value, 1), "unit": "nodes/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "settle_steps": settle_steps, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": headline_cfg,
-            "windows": win, "roofline": roofs[0],
         }
-        if len(roofs) > 1:
-            line["roofline_other"] = roofs[1:]
-        if dims is not None:
-            fl = roofs[0]["whole_step_flops"]
-            ms = win["ms_per_step_median"]
-            line["whole_step"] = {"flops": fl, "tflops": round(fl / (ms * 1e-3) / 1e12, 2),
-                                  "frac_of_fp32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)}
-        if cpu_job is not None:
-            line["cpu_baseline"] = cpu_baseline(*cpu_job)
-        detail = write_detail(line, secondary)
-        if detail:
-            line["detail"] = detail
+        if args.full:
+            line["windows"], line["roofline"] = win, roofs[0]
+            if len(roofs) > 1:
+                line["roofline_other"] = roofs[1:]
+            if dims is not None:
+                fl = roofs[0]["whole_step_flops"]
+                ms = win["ms_per_step_median"]
+                line["whole_step"] = {"flops": fl, "tflops": round(fl / (ms * 1e-3) / 1e12, 2),
+                                      "frac_of_fp32_mfma_peak": round(fl / (ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)}
+            if cpu_job is not None:
+                line["cpu_baseline"] = cpu_baseline(*cpu_job)
+            detail = write_detail(line, secondary)
+            if detail:
+                line["detail"] = detail
         print(headline_text(line), flush=True)  # the LAST stdout line: what the driver parses
     if dist is not None:
         dist.barrier()

@@ -71,3 +71,42 @@ def test_headline_is_the_last_line_and_small():
         assert one["secondary"] == sec["workload"]
         if "error" not in sec:
             assert one["roofline"]["frac"] == sec["roofline"]["frac"] and one["ms_per_step"] == sec["ms_per_step"]
+
+
+def test_plain_headline_carries_the_contract_fields():
+    """A plain run (no --full) has no windows, roofline or CPU baseline: its line must still build and parse."""
+    import json
+    bench = _load_bench()
+    line = {"metric": bench.METRIC, "value": 1.0e8, "unit": "nodes/s", "n_gpus": 1, "steps": 20, "warmup": 5,
+            "settle_steps": 700, "ms_per_step": 0.09, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic", "config": {"workload": "DiffPool", "step": "prose " * 100}}
+    parsed = json.loads(bench.headline_text(line))
+    assert {k: parsed[k] for k in line if k != "config"} == {k: v for k, v in line.items() if k != "config"}
+    assert parsed["config"] == {"workload": "DiffPool"} and "roofline" not in parsed
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 for narrow types, float64 for int64 indices (exact), None entries skipped; above the
+    byte budget every array keeps the same fraction of its elements, the same ones in every run, in index order."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(3, 4, generator=g)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"x": x, "ei": torch.arange(10).view(2, 5), "none": None,
+                                                   "mask": torch.tensor([True, False])})
+    assert info == {"dir": str(tmp_path / "a"), "arrays": 3, "sampled": False}
+    assert sorted(os.listdir(tmp_path / "a")) == ["ei.npy", "mask.npy", "x.npy"]
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    ei = np.load(tmp_path / "a" / "ei.npy")
+    assert ei.dtype == np.float64 and np.array_equal(ei, np.arange(10).reshape(2, 5))
+    assert np.load(tmp_path / "a" / "mask.npy").tolist() == [1.0, 0.0]
+
+    big = {"a": torch.arange(1000, dtype=torch.float32), "b": torch.arange(500)}  # 4000 + 4000 bytes
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), big, limit=2000)["sampled"]
+    a1, a2 = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s2" / "a.npy")
+    assert a1.shape == (250,) and np.load(tmp_path / "s1" / "b.npy").shape == (125,)
+    assert np.array_equal(a1, a2) and (np.diff(a1) > 0).all()
+    assert bench.DUMP_LIMIT <= 64_000_000

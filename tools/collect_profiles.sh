@@ -15,20 +15,20 @@ pmc() {  # name, counter, command...
   rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/pmc_${name}_$ctr -o run -- "$@" > /dev/null 2> $out/pmc_${name}_$ctr.err
   cp $(find $out/pmc_${name}_$ctr -name "*counter_collection.csv" | head -1) $out/pmc_${name}_$ctr.csv 2>/dev/null
 }
-( time python3 bench.py > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default_time.txt
-python3 bench.py --steps 20 --warmup 5 > $out/bench_line.json 2> $out/bench_line.err
-TGP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29617 python3 bench.py --workload topk_batch --secondary none --no-cpu-baseline --steps 50 2> $out/bench_topk_batch_rccl.err | grep '^{' > $out/bench_topk_batch_rccl.json
-TGP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29618 python3 bench.py --workload c2 --secondary none --no-cpu-baseline --steps 50 2> $out/bench_c2_rccl.err | grep '^{' > $out/bench_c2_rccl.json
+( time python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default_time.txt
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_line.json 2> $out/bench_line.err
+TGP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29617 python3 bench.py --full --workload topk_batch --secondary none --no-cpu-baseline --steps 50 2> $out/bench_topk_batch_rccl.err | grep '^{' > $out/bench_topk_batch_rccl.json
+TGP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29618 python3 bench.py --full --workload c2 --secondary none --no-cpu-baseline --steps 50 2> $out/bench_c2_rccl.err | grep '^{' > $out/bench_c2_rccl.json
 python3 tools/bench_graclus_hubs.py 2>&1 | grep -v -i 'warn\|amdgpu.ids' > $out/graclus_hubs.txt
 python3 tools/bench_ndp_hubs.py 2>&1 | grep -v -i 'warn\|amdgpu.ids' > $out/ndp_hubs_after.txt
-stats bench python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+stats bench python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 # the headline alone: the secondaries (training steps) launch the same GEMM instantiation on other shapes, so only this
 # run's average for gemm_f32_mfma_kernel<false,true,128,64,0,2> is the headline kernel's duration
-stats bench_headline python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --secondary none
-stats c4_graclus_sorted python3 bench.py --workload c4_graclus --secondary none --no-cpu-baseline --steps 50
-stats c4_graclus_unsorted python3 bench.py --workload c4_graclus --unsorted-edges --secondary none --no-cpu-baseline --steps 50
-stats topk_connect python3 bench.py --workload topk_connect --secondary none --no-cpu-baseline --steps 50
-stats c2_f64 python3 bench.py --workload c2_f64 --secondary none --no-cpu-baseline --steps 20
+stats bench_headline python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --secondary none
+stats c4_graclus_sorted python3 bench.py --full --workload c4_graclus --secondary none --no-cpu-baseline --steps 50
+stats c4_graclus_unsorted python3 bench.py --full --workload c4_graclus --unsorted-edges --secondary none --no-cpu-baseline --steps 50
+stats topk_connect python3 bench.py --full --workload topk_connect --secondary none --no-cpu-baseline --steps 50
+stats c2_f64 python3 bench.py --full --workload c2_f64 --secondary none --no-cpu-baseline --steps 20
 python3 tools/bench_f64.py 2>&1 | grep -v -i "warn\|amdgpu.ids" > $out/fp64_dense.txt
 python3 tools/fresh_profile.py topk_c3 graclus_c3 mincut_c3 2>&1 | grep -E "^==|us  |GPU-busy" > $out/fresh_profile_kernels.txt
 stats kron python3 tools/bench_kron.py --no-reference
