@@ -475,7 +475,7 @@ def orthogonality_loss(s):  # losses.py:59-70
     sts = torch.matmul(s.transpose(-2, -1), s)
     sts = sts / torch.norm(sts, dim=(-2, -1), keepdim=True)
     k = s.size(-1)
-    eye = torch.eye(k) / math.sqrt(k)
+    eye = torch.eye(k, dtype=s.dtype) / math.sqrt(k)  # in S's dtype, as the reference builds it
     return torch.norm(sts - eye, dim=(-2, -1)).mean()
 
 
@@ -506,7 +506,7 @@ def unbatched_orthogonality_loss(s, batch):  # losses.py:204-240
     n, k = s.shape
     if batch is None:
         batch = torch.zeros(n, dtype=torch.long)
-    eye = torch.eye(k) / math.sqrt(k)
+    eye = torch.eye(k, dtype=s.dtype) / math.sqrt(k)  # in S's dtype, as the reference builds it
     vals = []
     for g in range(int(batch.max()) + 1):
         sg = s[batch == g]
