@@ -341,9 +341,9 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
     g.M = static_cast<int>(N); g.Kd = static_cast<int>(N);
     g.rhs[0] = GemmRhs{S, U, static_cast<int>(K), K, ldu, N * K, N * ldu, 0};
     g.splits = 1; g.k_per_split = static_cast<int>((N + BK - 1) / BK * BK);
-    
-    if (flags & TGP_ADJ_TRANSPOSED) launch_gemm<true>(g, static_cast<int>(B), stream);
-    else launch_gemm<false>(g, static_cast<int>(B), stream);
+    // (A is an adjacency: the chunks of it that are mostly zeros skip the MFMAs, see launch_gemm_skip_zeros)
+    if (flags & TGP_ADJ_TRANSPOSED) launch_gemm_skip_zeros<true>(g, static_cast<int>(B), stream);
+    else launch_gemm_skip_zeros<false>(g, static_cast<int>(B), stream);
   }
   if (want_a || want_x) {
     // aslab[b][s] = S[b]^T U[b], xslab[b][s] = S[b]^T X[b] over the s-th slice of N: one grid

@@ -44,6 +44,21 @@ constexpr int BK = 32;
 
 constexpr int LDA_ROWMAJOR = BK + 1;
 
+// MODE 3 (U = A S of the dense poolers, see launch_gemm_skip_zeros): a k-step whose A chunk (128 x BK, as 1024 groups
+// of 4 consecutive values) has at most this many groups holding a nonzero, and whose S rows are all finite, skips its
+// MFMAs and accumulates over the nonzeros alone.  Set from the density sweep of tools/c2_density_sweep.py (DESIGN.md
+// section 4): from about 6 % nonzeros (1 - 0.94^4 = 22 % of the groups) the MFMAs win at C2.
+#ifndef TGP_SPARSE_CHUNK_GROUPS
+#define TGP_SPARSE_CHUNK_GROUPS 224
+#endif
+// ... and after this many dense k-steps in a row the workgroup runs the rest of its k-loop in the plain MODE 0 form: no
+// more records and decisions (they cost a dense input ~12 % of the launch when taken at every step).  Measured on
+// uniformly random A only: a row panel that meets two dense chunks early (a dense diagonal block of community-ordered
+// nodes, say) multiplies the rest of its k-range in full -- the results are the same, the skipping is lost there.
+#ifndef TGP_DENSE_RUN
+#define TGP_DENSE_RUN 2
+#endif
+
 // One right-hand side / output pair.  A launch may carry up to three (column tiles >= tiles_n0 use the
 // second, those >= tiles_n1 the third), which lets S^T [U | X] -- and, for the training step, S^T [U | X | S] --
 // run as a single grid.
@@ -121,7 +136,7 @@ __device__ __forceinline__ float4 ld4_guarded(const float* p, bool ok) {
 // ALIGNED: buffer-descriptor path, all traffic is 16-byte vectors with one predicate per vector; bases and
 // leading dimensions need dword alignment only (see gemm_aligned).  Otherwise: scalar guarded path (matrices too
 // large for 32-bit descriptor offsets).
-// MODE 0: C = op(A) Bm (MODE 2: the same + GemmArgs.colsum).  MODE 1 (link-prediction residual, utils/losses.py:644-708): Bm is stored
+// MODE 0: C = op(A) Bm (MODE 2: the same + GemmArgs.colsum; MODE 3: the same, skipping the MFMAs of sparse A chunks).  MODE 1 (link-prediction residual, utils/losses.py:644-708): Bm is stored
 // [Nc][Kd] (n-major, i.e. the product is A Bm^T), and instead of storing C the epilogue accumulates
 // sum((resid - C)^2) over the tile, so S S^T never exists in memory.
 template <bool A_KMAJOR, bool ALIGNED, int BM, int BN, int MODE, int WN = 2>
@@ -135,6 +150,20 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   constexpr int A_VECS = BM * BK / 4 / THREADS;     // float4 per thread per stage (= 2)
   constexpr int B_VECS = BN * BK / 4 / THREADS;     // 2 (512 threads) or 4 (256 threads)
   constexpr int AK_LANES = BM / 4;                  // lanes per k-row of a k-major A tile
+  // MODE 3: C = op(A) Bm where A is mostly zeros (an adjacency).  After each A chunk is staged the workgroup counts its
+  // 4-value groups that hold a nonzero (and checks the chunk's Bm rows for Inf / NaN: 0 * Inf must stay NaN); a chunk
+  // at or below TGP_SPARSE_CHUNK_GROUPS skips its MFMAs and each wave walks the nonzeros of the rows it owns (rows
+  // wave + NW j) with v_fma_f32 into a register accumulator [S_ROWS][S_COLS per lane], merged into the MFMA accumulator
+  // once at the end.  Skipping A_ij * S_jk is exact for A_ij = +-0 and finite S_jk, so both forms compute the same sums.
+  constexpr bool SKIP = MODE == 3;
+  constexpr int NW = THREADS / 64;                  // waves
+  constexpr int S_ROWS = BM / NW, S_COLS = BN / 64;  // MODE 3: rows a wave owns, columns a lane owns
+  static_assert(!SKIP || (ALIGNED && S_ROWS % 2 == 0 && (S_COLS == 1 || S_COLS == 2) && NW <= 16 && BM * BN <= 2 * STAGE_FLOATS),
+                "MODE 3: aligned tiles, two rows per ballot, one or two columns per lane");
+  // k-major A tile: row stride in LDS (MODE 3 pads it so that the sparse walk's reads down a column of A spread
+  // over the banks; [BK][BM + 4] is exactly the size of the row-major [BM][BK + 1] tile)
+  constexpr int LDA_KM = SKIP ? BM + 4 : BM;
+  static_assert(BK * LDA_KM <= A_TILE_FLOATS, "k-major A tile exceeds its LDS slot");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -313,7 +342,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       float* d = As + tile_row((tid >> 3) + i * (THREADS / 8)) * LDA_ROWMAJOR + (tid & 7) * 4;
       d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
     } else {
-      *reinterpret_cast<float4*>(As + (tid / AK_LANES + i * (THREADS / AK_LANES)) * BM + (tid % AK_LANES) * 4) = v;
+      *reinterpret_cast<float4*>(As + (tid / AK_LANES + i * (THREADS / AK_LANES)) * LDA_KM + (tid % AK_LANES) * 4) = v;
     }
   };
   auto store_b = [&](int i, const float4& v, float* Bs) {
@@ -389,8 +418,8 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       }
     }
   }
-  const int a_off = A_KMAJOR ? lk * BM + wm * 32 + lm : (wm * 32 + lm) * LDA_ROWMAJOR + lk;
-  const int a_step = A_KMAJOR ? 2 * BM : 2;
+  const int a_off = A_KMAJOR ? lk * LDA_KM + wm * 32 + lm : (wm * 32 + lm) * LDA_ROWMAJOR + lk;
+  const int a_step = A_KMAJOR ? 2 * LDA_KM : 2;
   const int b_off = MODE == 1 ? (wn * (BN / WN) + lm) * LDA_ROWMAJOR + lk : lk * BN + wn * (BN / WN) + lm;
   constexpr int b_step = MODE == 1 ? 2 : 2 * BN;               // one k-pair
   constexpr int b_tile = MODE == 1 ? 32 * LDA_ROWMAJOR : 32;   // next 32 output columns
@@ -410,6 +439,72 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_r[p % (PD + 1)], b_r[p % (PD + 1)][j], acc[j], 0, 0, 0);
   };
 
+  // MODE 3: per-wave chunk records in LDS behind the two stages, [2 parities][16 words, NW used]: the count of nonzero
+  // groups in the part of the A chunk the wave staged, + 2^16 if its Bm values hold an Inf or NaN.  Written before the
+  // stage's barrier, summed by every wave after it.
+  [[maybe_unused]] unsigned* chunk_rec = reinterpret_cast<unsigned*>(smem + 2 * STAGE_FLOATS);
+  [[maybe_unused]] float sacc[SKIP ? S_ROWS : 1][S_COLS];
+  [[maybe_unused]] bool any_sparse = false;
+  if constexpr (SKIP) {
+#pragma unroll
+    for (int j = 0; j < S_ROWS; ++j)
+#pragma unroll
+      for (int c = 0; c < S_COLS; ++c) sacc[j][c] = 0.f;
+  }
+  // (on the bits: a group holds a nonzero when some value has a bit below the sign -- +-0 are zeros, a NaN of A is a
+  // nonzero and is kept; a value is not finite when its magnitude bits reach those of Inf)
+  auto record_chunk = [&](auto par, const auto& va, const auto& vb) {  // (generic: no code outside MODE 3)
+    unsigned n = 0;
+#pragma unroll
+    for (int i = 0; i < A_VECS; ++i)
+      n += __popcll(__ballot(((__float_as_uint(va[i].x) | __float_as_uint(va[i].y) | __float_as_uint(va[i].z) |
+                               __float_as_uint(va[i].w)) << 1) != 0u));
+    unsigned mag = 0;
+#pragma unroll
+    for (int i = 0; i < B_VECS; ++i)
+      mag = max(max(mag, max(__float_as_uint(vb[i].x) & 0x7fffffffu, __float_as_uint(vb[i].y) & 0x7fffffffu)),
+                max(__float_as_uint(vb[i].z) & 0x7fffffffu, __float_as_uint(vb[i].w) & 0x7fffffffu));
+    if (__ballot(mag >= 0x7f800000u)) n += 1u << 16;
+    if (lane == 0) chunk_rec[par * 16 + wave] = n;
+  };
+  auto chunk_is_sparse = [&](auto par) -> bool {
+    const uint4* r = reinterpret_cast<const uint4*>(chunk_rec + par * 16);
+    unsigned n = 0;
+#pragma unroll
+    for (int q = 0; q < NW / 4; ++q) {
+      const uint4 v = r[q];
+      n += v.x + v.y + v.z + v.w;
+    }
+    return __builtin_amdgcn_readfirstlane(n) <= TGP_SPARSE_CHUNK_GROUPS;
+  };
+  // sacc[j][c] += sum over the chunk's nonzeros A[wave + NW j][k] * Bm[k][S_COLS lane + c]: two rows per ballot (lanes
+  // 0-31 read row wave + NW 2i, lanes 32-63 row wave + NW (2i + 1)), then the set bits of each half, one k per
+  // iteration, the A value taken from its lane (uniform k: v_readlane), the Bm row from LDS (one read per lane).
+  // Each output element has one owner lane: no atomics, a fixed order.
+  auto sparse_chunk = [&](auto As, auto Bs) {
+#pragma unroll
+    for (int i = 0; i < S_ROWS / 2; ++i) {
+      const int row = wave + NW * (2 * i + (lane >> 5)), k = lane & 31;
+      const float v = A_KMAJOR ? As[k * LDA_KM + row] : As[row * LDA_ROWMAJOR + k];
+      const unsigned long long nz = __ballot(v != 0.f);
+      const int vbits = __float_as_int(v);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        for (unsigned m = static_cast<unsigned>(nz >> (32 * h)); m; m &= m - 1) {
+          const int kk = __builtin_ctz(m);
+          const float a = __int_as_float(__builtin_amdgcn_readlane(vbits, kk + 32 * h));
+          if constexpr (S_COLS == 2) {
+            const float2 b = *reinterpret_cast<const float2*>(Bs + kk * BN + 2 * lane);
+            sacc[2 * i + h][0] = fmaf(a, b.x, sacc[2 * i + h][0]);
+            sacc[2 * i + h][S_COLS - 1] = fmaf(a, b.y, sacc[2 * i + h][S_COLS - 1]);
+          } else {
+            sacc[2 * i + h][0] = fmaf(a, Bs[kk * BN + lane], sacc[2 * i + h][0]);
+          }
+        }
+      }
+    }
+  };
+
   // Stage schedule.  Per-wave time stamps (tools/gemm_stamps.py) showed that a wave loses most of a k-step not
   // in the MFMAs but queueing behind the other 15 waves of the CU whenever all of them issue their global loads
   // or their LDS stores at the same point of the step (the texture-address path takes 16 clk per 1 KB load and a
@@ -427,9 +522,13 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   // compiler must assume the loads into a register set are still pending when the next stage overwrites it, and it
   // put an `s_waitcnt vmcnt(0)` in front of the B tile's load -- right behind the two A loads of the same stage, so
   // every wave sat out a full memory round trip per k-step -- plus ~25 branches per step.
-  auto stage = [&](auto par_c, auto steady_c, int t) {
+  // SK (MODE 3): the stage decides between the MFMAs and the sparse walk, and records the chunk it stores
+  [[maybe_unused]] int dense_run = 0;       // MODE 3: dense k-steps in a row (workgroup-uniform)
+  [[maybe_unused]] bool dense_rest = false; // MODE 3: TGP_DENSE_RUN reached: plain stages from here on
+  auto stage = [&](auto par_c, auto steady_c, auto sk_c, int t) {
     constexpr int PAR = decltype(par_c)::value;
     constexpr bool STEADY = decltype(steady_c)::value;
+    constexpr bool SK = decltype(sk_c)::value;
     const float* As = PAR ? L1 : L0;
     const float* Bs = As + A_TILE_FLOATS;
     float* An = PAR ? L0 : L1;
@@ -446,8 +545,51 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
 #define TGP_PHASE(i) do {} while (0)
 #endif
     TGP_PHASE(0);
+    bool sparse = false;  // (workgroup-uniform)
+    if constexpr (SK) {
+      // the dense form's first operand reads go out together with the reads of the chunk records, so the stage waits
+      // for one LDS round trip before its first MFMA, as without the records (the empty asm keeps the compiler from
+      // sinking the operand reads behind the branch)
 #pragma unroll
-    for (int p = 0; p < PD; ++p) fetch_pair(As, Bs, p);
+      for (int p = 0; p < PD; ++p) fetch_pair(As, Bs, p);
+      sparse = chunk_is_sparse(PAR);
+#pragma unroll
+      for (int p = 0; p < PD; ++p) {
+        asm volatile("" ::"v"(a_r[p % (PD + 1)]));
+#pragma unroll
+        for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(b_r[p % (PD + 1)][j]));
+      }
+      any_sparse = any_sparse || sparse;
+      dense_run = sparse ? 0 : dense_run + 1;
+      dense_rest = dense_run >= TGP_DENSE_RUN;
+      if (sparse) {
+      // the stage's memory work in one block: tile t+2 is requested first, tile t+1 goes to LDS after the walk
+#pragma unroll
+      for (int v = 0; v < A_VECS + B_VECS; ++v)
+        if (do_load) {
+          if (v < A_VECS) ra[PAR][v] = load_a(v, k2, tail);
+          else rb[PAR][v - A_VECS] = load_b(v - A_VECS, k2, tail);
+        }
+      sparse_chunk(As, Bs);
+#pragma unroll
+      for (int v = 0; v < A_VECS + B_VECS; ++v)
+        if (do_store) {
+          if (v < A_VECS) store_a(v, ra[1 - PAR][v], An);
+          else store_b(v - A_VECS, rb[1 - PAR][v - A_VECS], Bn);
+        }
+      if (do_store) record_chunk(1 - PAR, ra[1 - PAR], rb[1 - PAR]);
+      // (the accumulator passes this branch in the registers the MFMAs use: without this the compiler gave the loop
+      // two homes for it and copied it back after every dense stage, behind the last MFMA's full latency)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) asm volatile("" : "+v"(acc[j]));
+      }
+    }
+    // (the sparse block above exists only in deciding stages: every other stage is the MODE 0 stage as it was)
+    if (!SK || !sparse) {
+    if constexpr (!SK) {
+#pragma unroll
+      for (int p = 0; p < PD; ++p) fetch_pair(As, Bs, p);
+    }
 #pragma unroll
     for (int p = 0; p < BK / 2; ++p) {
       if (p + PD < BK / 2) fetch_pair(As, Bs, p + PD);
@@ -470,9 +612,15 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
           else store_b(v - A_VECS, rb[1 - PAR][v - A_VECS], Bn);
         }
       }
+      // MODE 3: tile t+1's record right behind its last LDS store, between MFMAs (at the end of the stage it held up
+      // every wave's arrival at the barrier)
+      if constexpr (SK) {
+        if (p == STORE_AT + (SPREAD ? A_VECS + B_VECS : 1) && do_store) record_chunk(1 - PAR, ra[1 - PAR], rb[1 - PAR]);
+      }
       __builtin_amdgcn_sched_barrier(0);
       if (p == STORE_AT) TGP_PHASE(2);
       if (p == LOAD_AT) TGP_PHASE(4);
+    }
     }
     TGP_PHASE(5);
     __syncthreads();
@@ -495,11 +643,15 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     for (int i = 0; i < A_VECS; ++i) store_a(i, ra[0][i], L0);
 #pragma unroll
     for (int i = 0; i < B_VECS; ++i) store_b(i, rb[0][i], L0 + A_TILE_FLOATS);
+    if constexpr (SKIP) record_chunk(0, ra[0], rb[0]);
   }
   __syncthreads();
   TGP_STAMP(1);
   int t = 0;
   using std::integral_constant;
+  using FALSE_C = integral_constant<bool, false>;
+  using TRUE_C = integral_constant<bool, true>;
+  if constexpr (!SKIP) {
   if constexpr (ALIGNED && TGP_STEADY_LOOP) {
     // pairs of stages whose loaded tiles (t + 2 and t + 3) exist and are full
     for (; t + 3 < nk && kof(t + 3) + BK <= k_end; t += 2) {
@@ -507,8 +659,8 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       if (t == (nk / 2 & ~1)) TGP_STAMP(6);
       if (t == ((3 * nk) / 4 & ~1)) TGP_STAMP(7);
 #endif
-      stage(integral_constant<int, 0>{}, integral_constant<bool, true>{}, t);
-      stage(integral_constant<int, 1>{}, integral_constant<bool, true>{}, t + 1);
+      stage(integral_constant<int, 0>{}, TRUE_C{}, FALSE_C{}, t);
+      stage(integral_constant<int, 1>{}, TRUE_C{}, FALSE_C{}, t + 1);
     }
   }
   for (; t < nk; t += 2) {
@@ -516,10 +668,46 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     if (t == (nk / 2 & ~1)) TGP_STAMP(6);
     if (t == ((3 * nk) / 4 & ~1)) TGP_STAMP(7);
 #endif
-    stage(integral_constant<int, 0>{}, integral_constant<bool, false>{}, t);
-    if (t + 1 < nk) stage(integral_constant<int, 1>{}, integral_constant<bool, false>{}, t + 1);
+    stage(integral_constant<int, 0>{}, FALSE_C{}, FALSE_C{}, t);
+    if (t + 1 < nk) stage(integral_constant<int, 1>{}, FALSE_C{}, FALSE_C{}, t + 1);
+  }
+  } else {
+    // MODE 3: deciding stages until TGP_DENSE_RUN dense k-steps in a row, then the MODE 0 loop (pairs of full stages);
+    // the tail stages decide as long as the workgroup has not switched
+    for (; t + 3 < nk && kof(t + 3) + BK <= k_end && !dense_rest; t += 2) {
+      stage(integral_constant<int, 0>{}, TRUE_C{}, TRUE_C{}, t);
+      stage(integral_constant<int, 1>{}, TRUE_C{}, TRUE_C{}, t + 1);
+    }
+    for (; t + 3 < nk && kof(t + 3) + BK <= k_end; t += 2) {
+      stage(integral_constant<int, 0>{}, TRUE_C{}, FALSE_C{}, t);
+      stage(integral_constant<int, 1>{}, TRUE_C{}, FALSE_C{}, t + 1);
+    }
+    auto tail_stage = [&](auto par_c, int t) {
+      if (dense_rest) stage(par_c, FALSE_C{}, FALSE_C{}, t);
+      else stage(par_c, FALSE_C{}, TRUE_C{}, t);
+    };
+    for (; t < nk; t += 2) {
+      tail_stage(integral_constant<int, 0>{}, t);
+      if (t + 1 < nk) tail_stage(integral_constant<int, 1>{}, t + 1);
+    }
   }
   TGP_STAMP(2);
+  if constexpr (SKIP) {
+    if (any_sparse) {  // (workgroup-uniform; the k-loop's last barrier has passed: the LDS is free)
+#pragma unroll
+      for (int j = 0; j < S_ROWS; ++j)
+#pragma unroll
+        for (int c = 0; c < S_COLS; ++c) smem[(wave + NW * j) * BN + S_COLS * lane + c] = sacc[j][c];
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          acc[j][r] = __fadd_rn(acc[j][r],
+                                smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * BN + wn * (BN / WN) + j * 32 + lm]);
+      __syncthreads();  // (the epilogue's LDS patches may reuse these words)
+    }
+  }
 
   // ---- epilogue: C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) -----------
   if constexpr (MODE == 1) {
@@ -717,6 +905,31 @@ static bool launch_gemm(GemmArgs g, int batches, hipStream_t stream, int* tiles_
   else if (t.bn == 64) launch_gemm_cfg<A_KMAJOR, 128, 64>(g, batches, stream);
   else launch_gemm_cfg<A_KMAJOR, 128, 128, 0, 4>(g, batches, stream);  // 16 waves (4 x 4), one 32x32 tile each
   return false;
+}
+
+// U = A S of the dense poolers (MODE 3): A is an adjacency, mostly zeros, and the k-steps whose A chunk is sparse skip
+// their MFMAs (see gemm_f32_mfma_kernel).  128 x 128 tiles, 16 waves: at K <= 128 one column tile, so every A panel is
+// read from HBM once.  Grids of fewer than 256 such tiles (fewer graphs than C2's 32 at N = 1024) would leave CUs
+// idle and keep pick_tile's tiles; so does what MODE 3 does not cover (split / accumulating / multi-rhs launches,
+// operands past the 32-bit descriptor range).
+template <bool A_KMAJOR>
+static void launch_gemm_skip_zeros(GemmArgs g, int batches, hipStream_t stream) {
+  if (g.splits != 1 || g.accumulate || g.rhs[1].Bm || g.colsum || g.m_ptr || g.k_ptr || !gemm_aligned(g, A_KMAJOR)) {
+    launch_gemm<A_KMAJOR>(g, batches, stream);
+    return;
+  }
+  constexpr int BM = 128, BN = 128, WN = 4;
+  const int tiles_m = cdiv(g.M, BM), tiles_n = cdiv(g.rhs[0].Nc, BN);
+  const int nwg = batches * tiles_m * tiles_n;
+  if (nwg < 256) {  // a 128 x 128 grid would leave CUs idle: pick_tile's smaller tiles and the MODE 0 kernel
+    launch_gemm<A_KMAJOR>(g, batches, stream);
+    return;
+  }
+  g.tiles_m = tiles_m;
+  g.tiles_n0 = g.tiles_n = tiles_n;
+  g.tiles_n1 = 0;
+  const size_t lds = 2 * (BM * LDA_ROWMAJOR + BK * BN) * sizeof(float) + 2 * 16 * sizeof(unsigned);
+  hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 3, WN>), dim3(nwg), dim3(BM * 2 * WN), lds, stream, g);
 }
 
 // MODE 1 launch: sum((resid - A Bm^T)^2) per tile into g.partial; returns tiles per batch element.
