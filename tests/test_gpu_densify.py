@@ -155,11 +155,11 @@ def test_one_launch_batch_facts_equal_the_general_route(dev, monkeypatch):
     }
     for name, b in cases.items():
         bd = b.to(dev)
-        ops._BATCH_INFO.clear()
+        ops._INFO_OF_BATCH.clear()
         monkeypatch.setattr(ops, "_BATCH_FACTS_ONE_LAUNCH", True)
         a = ops.batch_info(bd, topk_ratio=0.5)
         assert a.is_sorted and a.memo.get(("topk", 0.5)) is not None, name
-        ops._BATCH_INFO.clear()
+        ops._INFO_OF_BATCH.clear()
         monkeypatch.setattr(ops, "_BATCH_FACTS_ONE_LAUNCH", False)
         r = ops.batch_info(bd, topk_ratio=0.5)
         sizes = torch.bincount(b)
@@ -174,16 +174,16 @@ def test_one_launch_batch_facts_equal_the_general_route(dev, monkeypatch):
         assert torch.equal(koff.cpu(), torch.cat([torch.zeros(1, dtype=torch.long), want_k.cumsum(0)])), name
     monkeypatch.setattr(ops, "_BATCH_FACTS_ONE_LAUNCH", True)
     for name, b in {"unsorted": torch.tensor([0, 0, 2, 1, 2]), "long_gap": torch.tensor([0] * 10 + [500] * 10)}.items():
-        ops._BATCH_INFO.clear()
+        ops._INFO_OF_BATCH.clear()
         info = ops.batch_info(b.to(dev))
         sizes = torch.bincount(b)
         assert torch.equal(info.sizes.cpu(), sizes), name      # the general route took it
         assert info.is_sorted == (name != "unsorted")
     # back-to-back calls on one stream: the ticket / flag words are left clean by every call, also by a refused one
-    ops._BATCH_INFO.clear()
+    ops._INFO_OF_BATCH.clear()
     for _ in range(3):
         for b in (cases["proteins"], torch.tensor([3, 2, 1]), cases["with_empty_ids"]):
-            ops._BATCH_INFO.clear()
+            ops._INFO_OF_BATCH.clear()
             info = ops.batch_info(b.to(dev))
             assert torch.equal(info.sizes.cpu(), torch.bincount(b))
 

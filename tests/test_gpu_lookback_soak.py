@@ -43,7 +43,7 @@ def _soak(calls_small, steps_big):
                 out = wl.pool.reduce_connect(wl.x, wl.ei, wl.ew, wl.so, wl.batch)
             if out is None:
                 declined += 1
-                kernels._SPS_DECLINED.clear()
+                kernels._DECLINED_LISTS.clear()
             elif i % 500 == 0:
                 xp, bp, ei, ew = out
                 if not (torch.equal(xp, ref[0]) and torch.equal(ei, ref[1]) and torch.equal(ew, ref[2])):

@@ -214,10 +214,10 @@ def test_one_launch_pooling_rechecks_the_offsets_it_is_handed(dev, alias):
         first = pooler(x=x, adj=ei2, edge_weight=ew, batch=batch)   # searches for its ranges, leaves them in the memo
     assert not kernels.sparse_pool_small_declined(ei2)
     assert torch.equal(first.edge_index, good.edge_index) and torch.equal(first.x, good.x)
-    hit = kernels._EDGE_PTR.get(id(ei2))
-    assert hit is not None and hit[0]() is ei2, "the first call must have remembered the ranges it searched for"
-    table = hit[4]
-    gp = hit[3]()                        # the batch vector's CSR offsets the table belongs to
+    gp = kernels._EDGE_RANGES.other(ei2)  # the batch vector's CSR offsets the table belongs to
+    assert gp is not None, "the first call must have remembered the ranges it searched for"
+    table = kernels._edge_ptr_memo(ei2, gp)
+    assert table is not None
     assert torch.equal(table, torch.searchsorted(ei2[0].contiguous(), gp))  # = lower bounds of graph_ptr in the row array
     table[table.numel() // 2] += 1       # still ascending, still 0 .. E: one edge now sits in the wrong graph's range
     with torch.no_grad():
@@ -297,7 +297,7 @@ def test_new_edge_lists_need_no_lower_bounds_launch(dev):
         e1 = ei.clone()
         with torch.no_grad():
             first = pooler(x=x, adj=e1, edge_weight=ew, batch=batch)
-            assert kernels._edge_ptr_memo(e1, kernels._EDGE_PTR[id(e1)][3]()) is not None
+            assert kernels._edge_ptr_memo(e1, kernels._EDGE_RANGES.other(e1)) is not None
             second = pooler(x=x, adj=e1, edge_weight=ew, batch=batch, so=first.so)
             staged_x, staged_b = pooler.reducer(x, first.so, batch=batch)
             staged_e, staged_w = pooler.connector(e1, first.so, edge_weight=ew, batch_pooled=staged_b)

@@ -31,4 +31,4 @@ for hubs, deg in ((0, 0), (10, 100_000), (100, 10_000)):
             return pooler(x=x, adj=ei, edge_weight=ew)
     out = fwd()
     print(f"    whole graclus forward {wall(fwd, 5):.3f} ms, pooled edges {out.edge_index.size(1)}, "
-          f"hub kernels {'on' if id(ei) in K._HUB_ROWS else 'off'}", flush=True)
+          f"hub kernels {'on' if K._HUB_LISTS.get(ei) is not None else 'off'}", flush=True)

@@ -16,7 +16,7 @@ for which in ("topk_batch", "graclus_batch"):
             out = wl.pool.reduce_connect(wl.x, wl.ei, wl.ew, wl.so, wl.batch)
         if out is None:
             declined += 1
-            kernels._SPS_DECLINED.clear()
+            kernels._DECLINED_LISTS.clear()
     torch.cuda.synchronize()
     print(f"{which}: {n} calls, {declined} declined, {(time.perf_counter()-t0)/n*1e6:.1f} us per call", flush=True)
 # the big-graph look-back kernels

@@ -9,6 +9,8 @@ Neither torch_geometric nor torch_scatter is needed.
 import importlib
 import sys
 
+from ._memo import clear_memos  # noqa: F401  (weakref is all it imports)
+
 eps = 1e-8  # reference: tgp/__init__.py:6
 
 __version__ = "1.0.1+mi355x"

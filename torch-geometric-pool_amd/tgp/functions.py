@@ -12,6 +12,7 @@ import torch
 from torch import Tensor
 
 from . import kernels as K
+from ._memo import stamp, unchanged
 
 
 def _needs_grad(*ts) -> bool:
@@ -1251,16 +1252,14 @@ class ASProducts:
     (poolers/diffpool.py:208-218): five N^2 K products where two suffice.  The object is found again in the forward
     by the identity of the two live tensors and carried into the backward by the autograd contexts."""
 
-    __slots__ = ("s_ref", "adj_ref", "versions", "u", "v", "__weakref__")
+    __slots__ = ("s_stamp", "adj_stamp", "u", "v", "__weakref__")
 
     def __init__(self, s: Tensor, adj: Tensor):
-        import weakref
-        self.s_ref, self.adj_ref = weakref.ref(s), weakref.ref(adj)
-        self.versions = (s._version, adj._version)
+        self.s_stamp, self.adj_stamp = stamp(s), stamp(adj)
         self.u = self.v = None
 
     def matches(self, s: Tensor, adj: Tensor) -> bool:
-        return self.s_ref() is s and self.adj_ref() is adj and self.versions == (s._version, adj._version)
+        return unchanged(self.s_stamp, s) and unchanged(self.adj_stamp, adj)
 
     @staticmethod
     def _product(s: Tensor, adj: Tensor, transposed: bool) -> Tensor:

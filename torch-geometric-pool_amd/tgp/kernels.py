@@ -14,6 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _native as N
+from ._memo import TensorMemo
 
 
 _OPS_MODULE = None
@@ -183,7 +184,6 @@ def _edge_rows(edge_index: Tensor) -> Tuple[Tensor, Tensor]:
 
 # ------------------------------------------------------------------------- A1 + A2 + A4/A5 + A6, batches of small graphs
 _SPS_STATE: dict = {}  # (device index, stream handle) -> _SpsState
-_SPS_DECLINED: dict = {}
 _SPS_WORDS: dict = {}  # (graphs, mode) -> look-back words of the one-launch kernel (a native call otherwise)
 # r6: the exact-size outputs of the one-launch sparse pooling are carved out of ONE allocation of at most this many bytes
 # (what a retained x' can pin); TGP_SPS_ARENA=0: four allocations of their own, sized once the count has arrived
@@ -336,45 +336,21 @@ def _sps_state(dev: torch.device, stream: int, words: int) -> "_SpsState":
     return ent
 
 
+_DECLINED_LISTS = TensorMemo(16)
+
+
 def sparse_pool_small_declined(edge_index: Tensor) -> bool:
     """Did the one-launch kernel refuse this very edge list before (unsorted rows, an edge between two graphs, ...)?
-    Remembered per tensor object + version, like the row-order memo, so that a refusal costs one launch once."""
-    hit = _SPS_DECLINED.get(id(edge_index))
-    return hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version
-
-
-def _sps_remember_declined(edge_index: Tensor) -> None:
-    import weakref
-    if len(_SPS_DECLINED) >= 16:
-        for key in [k for k, v in _SPS_DECLINED.items() if v[0]() is None]:
-            del _SPS_DECLINED[key]
-        while len(_SPS_DECLINED) >= 16:
-            del _SPS_DECLINED[next(iter(_SPS_DECLINED))]
-    _SPS_DECLINED[id(edge_index)] = (weakref.ref(edge_index), edge_index._version)
+    Remembered per tensor object, like the row order, so that a refusal costs one launch once."""
+    return _DECLINED_LISTS.get(edge_index) is not None
 
 
 def sparse_pool_small_max_graph_nodes() -> int:
     return int(N.lib().tgp_sparse_pool_small_max_graph_nodes())
 
 
-_EDGE_PTR: dict = {}  # id(edge_index) -> (weakref, version, id(graph_ptr), weakref(graph_ptr), edge_ptr)
-
-
-def _edge_ptr_memo(edge_index: Tensor, graph_ptr: Tensor) -> Optional[Tensor]:
-    hit = _EDGE_PTR.get(id(edge_index))
-    if (hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version and hit[2] == id(graph_ptr)
-            and hit[3]() is graph_ptr):
-        return hit[4]
-    return None
-
-
-def _edge_ptr_remember(edge_index: Tensor, graph_ptr: Tensor, out: Tensor) -> None:
-    key = id(edge_index)
-    if key in _EDGE_PTR:
-        del _EDGE_PTR[key]  # (re-inserted at the young end)
-    elif len(_EDGE_PTR) >= 16:
-        del _EDGE_PTR[next(iter(_EDGE_PTR))]  # the oldest entry (dicts keep insertion order): no scan on the hot path
-    _EDGE_PTR[key] = (_weakref(edge_index), edge_index._version, id(graph_ptr), _weakref(graph_ptr), out)
+_EDGE_RANGES = TensorMemo(16)  # (edge_index, graph_ptr) -> the per-graph edge ranges of graph_edge_ptr
+_edge_ptr_memo = _EDGE_RANGES.get
 
 
 def graph_edge_ptr(edge_index: Tensor, graph_ptr: Tensor) -> Tensor:
@@ -391,7 +367,7 @@ def graph_edge_ptr(edge_index: Tensor, graph_ptr: Tensor) -> Tensor:
     N.check(N.lib().tgp_graph_lower_bounds_i64(N.ptr(row) if row.numel() else None, row.numel(), N.ptr(gp),
                                                gp.numel() - 1, N.ptr(out), N.stream_ptr(dev)),
             "tgp_graph_lower_bounds_i64")
-    _edge_ptr_remember(edge_index, graph_ptr, out)
+    _EDGE_RANGES.put(edge_index, out, graph_ptr)
     return out
 
 
@@ -519,7 +495,7 @@ def sparse_pool_small(x: Tensor, graph_ptr: Tensor, edge_index: Tensor, edge_wei
         x_pool = torch.as_strided(f32, (K, F), (F, 1), 0)
         batch_pool = torch.as_strided(buf, (K,), (1,), ob >> 3) if want_batch else None
     if eptr_out is not None:  # (forgotten again below if the kernel refuses the input)
-        _edge_ptr_remember(edge_index, graph_ptr, eptr_out)
+        _EDGE_RANGES.put(edge_index, eptr_out, graph_ptr)
     if arena:
         # the call's one host wait (the reference's .item() syncs) and the column move, in one native call (r6)
         N.check(L.tgp_result_wait_pack_cols(pinned_p, epoch, col_out, cap_p, st), "tgp_result_wait_pack_cols")
@@ -530,8 +506,8 @@ def sparse_pool_small(x: Tensor, graph_ptr: Tensor, edge_index: Tensor, edge_wei
         total = state.wait(epoch)
     if total & 0x80000000:
         if eptr_out is not None:
-            _EDGE_PTR.pop(id(edge_index), None)
-        _sps_remember_declined(edge_index)
+            _EDGE_RANGES.discard(edge_index)
+        _DECLINED_LISTS.put(edge_index, True)
         return None
     n_out = total & 0x7FFFFFFF
     if arena:
@@ -856,8 +832,7 @@ def coalesce_edges(edge_index: Tensor, edge_weight: Optional[Tensor], cluster_in
     if staged_ok:
         # a list known to hold hub rows (a supernode row beyond 1024 raw entries) asks for the huge-row kernels at once;
         # any other list finds out from the count (-5), once per edge_index object
-        hub = _HUB_ROWS.get(id(edge_index))
-        hub = hub is not None and hub[0]() is edge_index and hub[1] == edge_index._version
+        hub = _HUB_LISTS.get(edge_index) is not None
         published = _PUBLISH_COUNTS and not torch.cuda.is_current_stream_capturing()
         for attempt in range(2):
             fl = flags | (N.HUGE_ROWS if hub else 0)
@@ -889,7 +864,7 @@ def coalesce_edges(edge_index: Tensor, edge_weight: Optional[Tensor], cluster_in
             if n_out != -5 or hub:
                 break
             hub = True
-            _remember_hub_rows(edge_index)
+            _HUB_LISTS.put(edge_index, True)
             del ws
         if n_out >= 0:
             out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
@@ -1171,50 +1146,23 @@ def edge_facts_finish(handle, edge_index: Tensor, graph_ptr: Tensor) -> bool:
         _remember_rows_sorted(edge_index, False)
         return False
     _remember_rows_sorted(edge_index, True)
-    _edge_ptr_remember(edge_index, graph_ptr, buf[: graph_ptr.numel()])
+    _EDGE_RANGES.put(edge_index, buf[: graph_ptr.numel()], graph_ptr)
     return True
 
 
-_COALESCED: dict = {}  # id(edge_index) -> (weakref, version, num_nodes): the list is strictly row-major sorted (no duplicates)
+_STRICTLY_SORTED = TensorMemo(16)  # edge lists known to be strictly row-major sorted (no duplicates) for a node count
 
 
 def coalesced_memo(edge_index: Tensor, num_nodes: int) -> bool:
-    hit = _COALESCED.get(id(edge_index))
-    return bool(hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version and hit[2] == num_nodes)
+    return _STRICTLY_SORTED.get(edge_index, extra=num_nodes) is not None
 
 
 def remember_coalesced(edge_index: Tensor, num_nodes: int) -> None:
-    import weakref
-    if len(_COALESCED) >= 16:
-        for key in [k for k, v in _COALESCED.items() if v[0]() is None]:
-            del _COALESCED[key]
-        while len(_COALESCED) >= 16:
-            del _COALESCED[next(iter(_COALESCED))]
-    _COALESCED[id(edge_index)] = (weakref.ref(edge_index), edge_index._version, num_nodes)
+    _STRICTLY_SORTED.put(edge_index, True, extra=num_nodes)
 
 
-_ADJ_SYMMETRIC: dict = {}  # id(edge_index) -> (weakref, version, weakref of the weights or None, its version, flag)
-
-
-def _adj_symmetric_memo(edge_index: Tensor, edge_weight: Optional[Tensor]) -> Optional[bool]:
-    hit = _ADJ_SYMMETRIC.get(id(edge_index))
-    if (hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version
-            and ((hit[2] is None and edge_weight is None)
-                 or (hit[2] is not None and hit[2]() is edge_weight and hit[3] == edge_weight._version))):
-        return hit[4]
-    return None
-
-
-def _remember_adj_symmetric(edge_index: Tensor, edge_weight: Optional[Tensor], flag: bool) -> None:
-    import weakref
-    if len(_ADJ_SYMMETRIC) >= 16:
-        for key in [k for k, v in _ADJ_SYMMETRIC.items() if v[0]() is None]:
-            del _ADJ_SYMMETRIC[key]
-        while len(_ADJ_SYMMETRIC) >= 16:
-            del _ADJ_SYMMETRIC[next(iter(_ADJ_SYMMETRIC))]
-    _ADJ_SYMMETRIC[id(edge_index)] = (weakref.ref(edge_index), edge_index._version,
-                                      None if edge_weight is None else weakref.ref(edge_weight),
-                                      None if edge_weight is None else edge_weight._version, flag)
+_SYMMETRIC_ADJ = TensorMemo(16)  # (edge_index, edge_weight or None) -> is the adjacency symmetric?
+_adj_symmetric_memo = _SYMMETRIC_ADJ.get
 
 
 class AdjSymmetry:
@@ -1227,9 +1175,8 @@ class AdjSymmetry:
     __slots__ = ("state", "tag", "answer", "ei", "ew")
 
     def __init__(self, edge_index: Tensor, edge_weight: Optional[Tensor], adj: Tensor, batch: Tensor, ptr: Tensor):
-        import weakref
         self.state = self.tag = None
-        self.ei, self.ew = weakref.ref(edge_index), (None if edge_weight is None else weakref.ref(edge_weight))
+        self.ei, self.ew = _weakref(edge_index), (None if edge_weight is None else _weakref(edge_weight))
         self.answer = _adj_symmetric_memo(edge_index, edge_weight)
         if self.answer is not None:
             return
@@ -1251,10 +1198,9 @@ class AdjSymmetry:
     def of_dense(cls, adj: Tensor) -> "AdjSymmetry":
         """The same question for a dense [B,N,N] float32 adjacency the caller holds (tgp_dense_symmetry_f32: one pass over
         the matrix); remembered for this tensor object + version, so a fixed dense graph pooled every epoch pays it once."""
-        import weakref
         self = cls.__new__(cls)
         self.state = self.tag = None
-        self.ei, self.ew = weakref.ref(adj), None
+        self.ei, self.ew = _weakref(adj), None
         self.answer = _adj_symmetric_memo(adj, None)
         if self.answer is not None:
             return self
@@ -1275,10 +1221,9 @@ class AdjSymmetry:
                      edge_weight: Optional[Tensor], row_ptr: Tensor, num_nodes: int) -> "AdjSymmetry":
         """The same question for a COALESCED row-sorted list with its CSR offsets (tgp_edge_symmetry_f32: every entry must
         have a mirror entry of equal weight); remembered for the (key_index, key_weight) objects the caller holds."""
-        import weakref
         self = cls.__new__(cls)
         self.state = self.tag = None
-        self.ei, self.ew = weakref.ref(key_index), (None if key_weight is None else weakref.ref(key_weight))
+        self.ei, self.ew = _weakref(key_index), (None if key_weight is None else _weakref(key_weight))
         self.answer = _adj_symmetric_memo(key_index, key_weight)
         if self.answer is not None:
             return self
@@ -1304,7 +1249,7 @@ class AdjSymmetry:
             if flags is not None:
                 ei, ew = self.ei(), (None if self.ew is None else self.ew())
                 if ei is not None and (self.ew is None or ew is not None):
-                    _remember_adj_symmetric(ei, ew, self.answer)
+                    _SYMMETRIC_ADJ.put(ei, self.answer, ew)
         return bool(self.answer)
 
 
@@ -1910,48 +1855,20 @@ def topk_select(score: Tensor, batch: Optional[Tensor], num_graphs: int, ptr: Te
     return out + ((AssignIndex(lift_ptr, None, k_total, n),) if with_lift else ())
 
 
-_ROWS_SORTED: dict = {}
-_HUB_ROWS: dict = {}  # edge lists on which the row-local coalesce met a supernode row beyond its LDS sort
-
-
-def _remember_hub_rows(edge_index: Tensor) -> None:
-    import weakref
-    if len(_HUB_ROWS) >= 16:
-        for key in [k for k, v in _HUB_ROWS.items() if v[0]() is None]:
-            del _HUB_ROWS[key]
-        while len(_HUB_ROWS) >= 16:
-            del _HUB_ROWS[next(iter(_HUB_ROWS))]
-    _HUB_ROWS[id(edge_index)] = (weakref.ref(edge_index), edge_index._version)
-
-
-def _rows_sorted_memo(edge_index: Tensor) -> Optional[bool]:
-    """What is already known about this tensor object: True / False, or None when it has not been looked at."""
-    hit = _ROWS_SORTED.get(id(edge_index))
-    if hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version:
-        return hit[2]
-    return None
+_HUB_LISTS = TensorMemo(16)  # edge lists on which the row-local coalesce met a supernode row beyond its LDS sort
+_SORTED_ROWS = TensorMemo(16)  # edge_index -> are its rows ascending?  (None: it has not been looked at)
+_rows_sorted_memo = _SORTED_ROWS.get
+_remember_rows_sorted = _SORTED_ROWS.put
 
 
 def _rows_sorted(edge_index: Tensor, row: Tensor) -> bool:
-    """Is the list grouped by ascending source node?  Memoised per tensor object (weak reference + version counter,
-    like utils.ops.batch_info), so an unchanged edge_index costs one host round trip in total, not one per call."""
-    import weakref
-    hit = _ROWS_SORTED.get(id(edge_index))
-    if hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version:
-        return hit[2]
-    flag = bool((row[1:] >= row[:-1]).all())
-    _remember_rows_sorted(edge_index, flag)
+    """Is the list grouped by ascending source node?  Remembered per tensor object, so an unchanged edge_index costs one
+    host round trip in total, not one per call."""
+    flag = _rows_sorted_memo(edge_index)
+    if flag is None:
+        flag = bool((row[1:] >= row[:-1]).all())
+        _remember_rows_sorted(edge_index, flag)
     return flag
-
-
-def _remember_rows_sorted(edge_index: Tensor, flag: bool) -> None:
-    import weakref
-    if len(_ROWS_SORTED) >= 16:
-        for key in [k for k, v in _ROWS_SORTED.items() if v[0]() is None]:
-            del _ROWS_SORTED[key]
-        while len(_ROWS_SORTED) >= 16:
-            del _ROWS_SORTED[next(iter(_ROWS_SORTED))]
-    _ROWS_SORTED[id(edge_index)] = (weakref.ref(edge_index), edge_index._version, flag)
 
 
 def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: int,
@@ -2390,25 +2307,20 @@ def spmm_sorted_csr(edge_index: Tensor, edge_weight: Optional[Tensor], num_rows:
     return out, row_ptr
 
 
-_CSR_OFFSETS: dict = {}  # id(edge_index) -> (weakref, version, num_rows, row_ptr)
+_ROW_OFFSETS = TensorMemo(16)
 
 
 def csr_offsets(edge_index: Tensor, num_rows: int) -> Tensor:
     """int32 [num_rows+1] CSR offsets of a row-sorted list: one launch for a new list, remembered per tensor object +
     version (full-batch training pools the same ``edge_index`` every step), like the per-graph edge ranges."""
-    key = id(edge_index)
-    hit = _CSR_OFFSETS.get(key)
-    if hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version and hit[2] == num_rows:
-        return hit[3]
+    hit = _ROW_OFFSETS.get(edge_index, extra=num_rows)
+    if hit is not None:
+        return hit
     row, _ = _edge_rows(edge_index)
     out = torch.empty(num_rows + 1, dtype=torch.int32, device=edge_index.device)
     rowptr_from_sorted(row, num_rows, out)
     if not torch.cuda.is_current_stream_capturing():
-        if key in _CSR_OFFSETS:
-            del _CSR_OFFSETS[key]
-        elif len(_CSR_OFFSETS) >= 16:
-            del _CSR_OFFSETS[next(iter(_CSR_OFFSETS))]
-        _CSR_OFFSETS[key] = (_weakref(edge_index), edge_index._version, num_rows, out)
+        _ROW_OFFSETS.put(edge_index, out, extra=num_rows)
     return out
 
 

@@ -16,6 +16,7 @@ import torch
 from torch import Tensor
 
 from .. import functions as Fn
+from .._memo import TensorMemo, stamp, unchanged
 from ..imports import is_sparsetensor
 from ..utils.ops import (
     connectivity_to_edge_index,
@@ -258,14 +259,14 @@ class SelectOutput:
             self._assign_index = kernels.build_assign_index(self.cluster_index, self.num_supernodes)
         return self._assign_index
 
-    _edge_csr = None  # (weakref to an edge_index tensor, its version, int32 CSR offsets): set by GraclusSelect
+    _edge_csr = None  # (stamp of an edge_index tensor, its int32 CSR offsets): set by GraclusSelect
 
     def edge_csr_for(self, edge_index) -> Optional[Tensor]:
         """CSR offsets a selector attached for exactly this edge_index tensor (same object, unmodified), else None."""
         hit = self._edge_csr
-        if (hit is not None and isinstance(edge_index, Tensor) and hit[0]() is edge_index
-                and hit[1] == edge_index._version and hit[2].device == edge_index.device):
-            return hit[2]
+        if (hit is not None and isinstance(edge_index, Tensor) and unchanged(hit[0], edge_index)
+                and hit[1].device == edge_index.device):
+            return hit[1]
         return None
 
     def __getstate__(self):
@@ -763,9 +764,8 @@ class GraclusSelect(Select):
             so._assign_index = assign
             if row_ptr is not None:
                 # CSR offsets of the (row-sorted) list the matcher walked: SparseConnect skips its own pass over the
-                # row array when it is handed this very edge_index object, unchanged (identity + version counter)
-                import weakref
-                so._edge_csr = (weakref.ref(edge_index), edge_index._version, row_ptr)
+                # row array when it is handed this very edge_index object, unchanged
+                so._edge_csr = (stamp(edge_index), row_ptr)
             return so
         pair = graclus_cluster(edge_index[0], edge_index[1], edge_weight, num_nodes)
         ids, assignment = torch.unique(pair, sorted=True, return_inverse=True)
@@ -792,38 +792,9 @@ def _ndp_side_stream(dev):
     return st
 
 
-_NDP_PREP: dict = {}  # id(edge_index) -> (weakref, version, weakref(edge_weight) | None, its version, n, indptr, w_sym)
-
-
-def _ndp_prep_memo(edge_index: Tensor, edge_weight: Optional[Tensor], n: int):
-    """(indptr, symmetrised weights) of an edge list NDPSelect has already recognised as row-sorted, duplicate-free,
-    loop-free and pattern-symmetric -- per tensor OBJECT and version (an in-place edit bumps the version), like the other
-    per-list memos of the package; the outputs are never written to by their consumers."""
-    hit = _NDP_PREP.get(id(edge_index))
-    if hit is None or hit[0]() is not edge_index or hit[1] != edge_index._version or hit[4] != n:
-        return None
-    if edge_weight is None:
-        if hit[2] is not None:
-            return None
-    elif hit[2] is None or hit[2]() is not edge_weight or hit[3] != edge_weight._version:
-        return None
-    return hit[5], hit[6]
-
-
-def _ndp_prep_remember(edge_index: Tensor, edge_weight: Optional[Tensor], n: int, indptr: Tensor, w_sym: Tensor) -> None:
-    import weakref
-    if edge_index.size(1) > (1 << 22):
-        return  # (the memo would pin > 16 MB per list; at that size the two launches it saves are noise)
-    for dead in [k for k, v in _NDP_PREP.items() if v[0]() is None]:
-        del _NDP_PREP[dead]  # a list that is gone must not keep its offsets and weights alive
-    key = id(edge_index)
-    if key in _NDP_PREP:
-        del _NDP_PREP[key]
-    elif len(_NDP_PREP) >= 8:
-        del _NDP_PREP[next(iter(_NDP_PREP))]  # the oldest entry
-    _NDP_PREP[key] = (weakref.ref(edge_index), edge_index._version,
-                      None if edge_weight is None else weakref.ref(edge_weight),
-                      0 if edge_weight is None else edge_weight._version, n, indptr, w_sym)
+# (edge_index, edge_weight or None, n) -> (indptr, symmetrised weights) of an edge list NDPSelect has already recognised
+# as row-sorted, duplicate-free, loop-free and pattern-symmetric; the outputs are never written to by their consumers
+_NDP_INPUTS = TensorMemo(8)
 
 
 class NDPSelect(Select):
@@ -958,7 +929,7 @@ class NDPSelect(Select):
         # A list that already is that (the usual PyG dataset of undirected graphs) is recognised by one kernel and used
         # as it is (r3: the two coalesce calls were two dozen launches and two host read-backs of the NDP forward).
         ei2 = None
-        prep = _ndp_prep_memo(edge_index, edge_weight, n)
+        prep = _NDP_INPUTS.get(edge_index, edge_weight, n)
         if prep is not None:  # this very list (object + version) was recognised as clean before: its CSR offsets and
             indptr, w_sym = prep  # symmetrised weights are reused -- two launches and a host read less per call (r6)
             ei2, w2 = edge_index, w_sym
@@ -969,7 +940,8 @@ class NDPSelect(Select):
                 w_sym, flag = K.ndp_symmetric_max(edge_index, w0, n, indptr)
                 if int(flag.item()) == 0:
                     ei2, w2 = edge_index, w_sym
-                    _ndp_prep_remember(edge_index, edge_weight, n, indptr, w_sym)
+                    if edge_index.size(1) <= (1 << 22):  # (above: > 16 MB pinned per list, two launches are noise)
+                        _NDP_INPUTS.put(edge_index, (indptr, w_sym), edge_weight, n)
         if ei2 is None:
             ident = torch.arange(n, device=dev)
             if w0 is None:

@@ -13,6 +13,7 @@ from torch import Tensor
 
 from .. import eps
 from .. import kernels as K
+from .._memo import TensorMemo
 from ..imports import HAS_TORCH_SPARSE, is_sparsetensor
 
 
@@ -55,11 +56,9 @@ def like_input_dtype(out, like):
 class BatchInfo:
     """Host-side facts about a batch vector (number of graphs, graph sizes, CSR offsets, longest graph).
     Reading them costs two device round trips; one pooler call asks for them in half a dozen places (dense
-    preprocessing, Reduce, Connect, Lift, the losses), so they are memoised per tensor OBJECT: the entry is
-    valid only while the weak reference still resolves to the very same tensor and its version counter has
-    not moved (an in-place write bumps it), which rules out stale hits from recycled memory."""
+    preprocessing, Reduce, Connect, Lift, the losses), so they are remembered per tensor OBJECT (a TensorMemo)."""
 
-    __slots__ = ("ref", "version", "num_graphs", "sizes", "_sizes_host", "ptr", "max_nodes", "distinct", "is_sorted",
+    __slots__ = ("num_graphs", "sizes", "_sizes_host", "ptr", "max_nodes", "distinct", "is_sorted",
                  "memo")  # memo: facts derived from the sizes by a caller (e.g. TopkSelect's per-graph k for a ratio)
 
     @property
@@ -71,7 +70,7 @@ class BatchInfo:
         return self._sizes_host
 
 
-_BATCH_INFO: dict = {}
+_INFO_OF_BATCH = TensorMemo(16)
 _BATCH_FACTS_ONE_LAUNCH = __import__("os").environ.get("TGP_BATCH_FACTS_ONE_LAUNCH", "1") != "0"  # A/B switch
 
 
@@ -97,7 +96,7 @@ def _batch_facts_device(batch: Tensor, info: "BatchInfo", topk_ratio: float = 0.
     return True
 
 
-_FACTS_PENDING: dict = {}  # id(batch) -> (weakref, version, ratio, launched call) of prefetch_batch_info
+_PREFETCHED_FACTS = TensorMemo(8)  # batch -> (ratio, launched call) of prefetch_batch_info; an abandoned one is forgotten
 
 
 def prefetch_batch_info(batch: Optional[Tensor], topk_ratio: float = 0.0) -> None:
@@ -105,19 +104,13 @@ def prefetch_batch_info(batch: Optional[Tensor], topk_ratio: float = 0.0) -> Non
     score pass over x) puts that work between this launch and the ``batch_info`` call that polls for the result, so the
     host wait covers the facts kernel only and the rest runs while the host goes on.  A no-op when the facts are
     memoised, the vector is not eligible, or a prefetch is already pending."""
-    import weakref
     if (batch is None or not _BATCH_FACTS_ONE_LAUNCH or not batch.is_cuda or batch.dtype != torch.long
             or not batch.is_contiguous() or batch.numel() == 0 or batch.numel() > (1 << 24)):
         return
-    hit = _BATCH_INFO.get(id(batch))
-    if hit is not None and hit.ref() is batch and hit.version == batch._version:
+    if (_INFO_OF_BATCH.get(batch) is not None or _PREFETCHED_FACTS.get(batch) is not None
+            or torch.cuda.is_current_stream_capturing()):
         return
-    if id(batch) in _FACTS_PENDING or torch.cuda.is_current_stream_capturing():
-        return
-    if len(_FACTS_PENDING) >= 8:
-        _FACTS_PENDING.clear()  # (abandoned prefetches: their launches complete on their own)
-    _FACTS_PENDING[id(batch)] = (weakref.ref(batch), batch._version, float(topk_ratio or 0.0),
-                                 _facts_sorted_launch(batch, topk_ratio))
+    _PREFETCHED_FACTS.put(batch, (float(topk_ratio or 0.0), _facts_sorted_launch(batch, topk_ratio)))
 
 
 def _facts_sorted_launch(batch: Tensor, topk_ratio: float):
@@ -151,16 +144,17 @@ def _batch_facts_sorted(batch: Tensor, info: "BatchInfo", topk_ratio: float = 0.
     long runs of ids without nodes) -- the general route below takes it."""
     if torch.cuda.is_current_stream_capturing():
         return False
-    pend = _FACTS_PENDING.pop(id(batch), None)
+    pend = _PREFETCHED_FACTS.pop(batch)
     launched = None
-    if pend is not None and pend[0]() is batch and pend[1] == batch._version:
+    if pend is not None:
         # a prefetch whose pinned slot (eight rotate: tag & 7) has been handed to a later launch is not waited for -- its
         # words are gone and the wait would spin into its bound (ADVICE r5): the facts are launched again
-        fresh = pend[3][0].facts_tag - pend[3][1] < 8
-        if fresh and (pend[2] == float(topk_ratio or 0.0) or pend[2] > 0):
-            launched = pend[3]
-            if pend[2] > 0 and not (topk_ratio and topk_ratio > 0):
-                topk_ratio = pend[2]  # (the prefetch also made a TopK plan: kept)
+        ratio, call = pend
+        fresh = call[0].facts_tag - call[1] < 8
+        if fresh and (ratio == float(topk_ratio or 0.0) or ratio > 0):
+            launched = call
+            if ratio > 0 and not (topk_ratio and topk_ratio > 0):
+                topk_ratio = ratio  # (the prefetch also made a TopK plan: kept)
     if launched is None:
         launched = _facts_sorted_launch(batch, topk_ratio)
     state, tag, buf, n, want_plan = launched
@@ -182,12 +176,11 @@ def _batch_facts_sorted(batch: Tensor, info: "BatchInfo", topk_ratio: float = 0.
 
 def batch_info(batch: Tensor, topk_ratio: float = 0.0) -> BatchInfo:
     """``topk_ratio``: a TopK selector asking first also gets its total number of kept nodes from the same read-back."""
-    import weakref
-    hit = _BATCH_INFO.get(id(batch))
-    if hit is not None and hit.ref() is batch and hit.version == batch._version:
+    hit = _INFO_OF_BATCH.get(batch)
+    if hit is not None:
         return hit
     info = BatchInfo()
-    info.ref, info.version, info.memo = weakref.ref(batch), batch._version, {}
+    info.memo = {}
     info._sizes_host = None
     info.ptr = None
     if batch.numel() == 0:
@@ -211,12 +204,7 @@ def batch_info(batch: Tensor, topk_ratio: float = 0.0) -> BatchInfo:
         info.ptr = torch.zeros(info.num_graphs + 1, dtype=torch.long, device=batch.device)
         if info.num_graphs:
             torch.cumsum(info.sizes, 0, out=info.ptr[1:])
-    if len(_BATCH_INFO) >= 16:  # a handful of live batch vectors at most; drop dead and old entries
-        for key in [k for k, v in _BATCH_INFO.items() if v.ref() is None]:
-            del _BATCH_INFO[key]
-        while len(_BATCH_INFO) >= 16:
-            del _BATCH_INFO[next(iter(_BATCH_INFO))]
-    _BATCH_INFO[id(batch)] = info
+    _INFO_OF_BATCH.put(batch, info)
     return info
 
 
