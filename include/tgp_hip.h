@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10042 /* 1.0.1 of the reference, ABI revision 41 (r6: tgp_mask_index_*, node_rank on tgp_kron_batched_count / _fill; the dense poolers' training step at C2 scale: tgp_dense_pool_train_*, tgp_mincut_terms_fused_f32, tgp_softmax_bwd_ex_f32, tgp_copy_cols2_f32; tgp_result_wait_pack_cols; tgp_spmm_csr_stats_f32 / _entropy_f32; tgp_segment_gemm_tn3_post_f32) */
+#define TGP_ABI_VERSION 10043 /* 1.0.1 of the reference, ABI revision 42 (DMoN: tgp_dmon_dense_terms_f32, tgp_dmon_edge_degrees_f32, tgp_dmon_node_terms_f32, tgp_dmon_loss_terms_f32 / _bwd_f32, tgp_dmon_ds_f32; revision 41, r6: tgp_mask_index_*, node_rank on tgp_kron_batched_count / _fill; the dense poolers' training step at C2 scale: tgp_dense_pool_train_*, tgp_mincut_terms_fused_f32, tgp_softmax_bwd_ex_f32, tgp_copy_cols2_f32; tgp_result_wait_pack_cols; tgp_spmm_csr_stats_f32 / _entropy_f32; tgp_segment_gemm_tn3_post_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -630,6 +630,49 @@ int tgp_mincut_loss_terms_f32(const float* raw, const float* den, const float* g
  * dS = S (W + W^T)). */
 int tgp_mincut_loss_terms_bwd_f32(const float* raw, const float* den, const float* gram, const float* g_terms, int64_t B,
                                   int64_t K, float eps, float* g_raw, float* c1, float* W, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DMoN's auxiliary losses (poolers/dmon.py, utils/losses.py:435-473, 1083-1265):
+ *   spectral[b] = -(trace(S^T A S) - ||ca_b||^2 / 2m_b) / 2m_b,  ca_b = S_b^T d_b,  2m_b = sum_i d_{b,i}
+ *   cluster[b]  = ||cs_b|| sqrt(K) / n_b - 1,                      cs_b = S_b^T 1
+ *   ortho[b]    = || G_b / ||G_b||_F - I / sqrt(K) ||_F,           G = S^T S
+ * The K-vectors are reduced in two stages: ``part`` [B][nsplit][2K+2] holds, per block of 64 rows of a graph,
+ * (ca | cs | sum of d | node count); the loss tail adds the blocks of a graph in a fixed order.
+ *
+ * tgp_dmon_dense_terms_f32: padded batch, S [B,N,K], nsplit = ceil(N / 64).  With A [B,N,N]: deg[b,i] = sum_j A[b,i,j]
+ *   on real rows (graph_sizes [B] and mask [B,N] (bytes) both optional), else 0, written to deg; one pass over A.  A NULL:
+ *   deg [B,N] is read as the degrees (e.g. from tgp_dmon_edge_degrees_f32), NULL = none (cluster loss only).  The node
+ *   count n_b is the mask's true entries (N without a mask).  One pass over S.
+ * tgp_dmon_edge_degrees_f32: deg [B,N] (padded) of a row-sorted edge list with node offsets node_ptr [B+1] and edge
+ *   offsets edge_ptr [B+1]: deg[b,j] = sum of w (NULL: 1) over the graph's edges whose key is node node_ptr[b] + j; key =
+ *   the rows (out-degrees) or the columns (in-degrees: the row sums of the densified A^T).  N <= 1024.
+ * tgp_dmon_node_terms_f32: un-padded batch, S [Ntot,K], deg [Ntot] (NULL: cluster loss only), ptr [B+1] node offsets,
+ *   nsplit = ceil(largest graph / 64).  n_b = ptr[b+1] - ptr[b].
+ * tgp_dmon_loss_terms_f32: out [3,B] = (c_spec spectral, c_clu cluster, c_ort ortho) per graph (the pooler's loss
+ *   coefficients; 1 for the bare losses); trace(S^T A S) from the diagonal of raw
+ *   [B,K,K], else from tr [B], else 0; gram [B,K,K] NULL: ortho = 0.  sqrt_k multiplies the cluster term.  clamp_m = 0:
+ *   a graph with m = 0 has spectral 0 (batched form); 1: m is clamped to eps (unbatched form).  Writes ca, cs [B,K] and
+ *   stats [B,4] = (2m as used or 0 | n_b | ||cs_b|| | trace) for the backward.
+ * tgp_dmon_loss_terms_bwd_f32: from the upstream gradients g_terms [3,B] (times the same coefficients): g_raw [B,K,K] = -(g_spec / 2m) I (NULL: not
+ *   written), g_tr [B] = -g_spec / 2m (NULL: not written), coef [B,2] = (2 g_spec / (2m)^2, g_clu sqrt(K) / (n_b ||cs||)),
+ *   and with gram W [B,K,K] = d ortho / d G (dS = S (W + W^T)).
+ * tgp_dmon_ds_f32: ds[r,k] (+)= coef[b,0] deg[r] ca[b,k] + coef[b,1] cs[b,k] over rows r of S; b = batch[r] when batch
+ *   is given (un-padded), else r / N (padded).  deg NULL: only the cluster part.  accumulate != 0: adds into ds.
+ * ---------------------------------------------------------------------------------- */
+int tgp_dmon_dense_terms_f32(const float* A, const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes,
+                             const uint8_t* mask, int64_t nsplit, float* deg, float* part, void* stream);
+int tgp_dmon_edge_degrees_f32(const int64_t* key, const float* w, int64_t E, const int64_t* node_ptr,
+                              const int64_t* edge_ptr, int64_t B, int64_t N, float* deg, void* stream);
+int tgp_dmon_node_terms_f32(const float* S, const float* deg, const int64_t* ptr, int64_t B, int64_t K, int64_t nsplit,
+                            float* part, void* stream);
+int tgp_dmon_loss_terms_f32(const float* part, int64_t nsplit, const float* raw, const float* tr, const float* gram,
+                            int64_t B, int64_t K, float sqrt_k, int clamp_m, float eps, float c_spec, float c_clu,
+                            float c_ort, float* out, float* ca, float* cs, float* stats, void* stream);
+int tgp_dmon_loss_terms_bwd_f32(const float* g_terms, const float* stats, const float* gram, int64_t B, int64_t K,
+                                float sqrt_k, float c_spec, float c_clu, float c_ort, float* g_raw, float* g_tr,
+                                float* coef, float* W, void* stream);
+int tgp_dmon_ds_f32(const float* deg, const float* ca, const float* cs, const float* coef, int64_t rows, int64_t N,
+                    const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * N1 (r6)  The dense poolers' TRAINING step for graphs beyond the one-wave / one-workgroup kernels (C2: B = 32,

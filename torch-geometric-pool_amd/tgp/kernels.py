@@ -1758,6 +1758,140 @@ def mincut_loss_terms_bwd(raw: Tensor, den: Tensor, gram: Tensor, g_terms: Tenso
     return g_raw, c1, W
 
 
+_DMON_ROWS = 64  # rows of one graph per workgroup of the DMoN partial pass (csrc/dmon.hip)
+
+
+def _mask_bytes(mask: Optional[Tensor], B: int, Nn: int) -> Optional[Tensor]:
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (B, Nn):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the batch ({B}, {Nn})")
+    m = mask if mask.dtype == torch.bool else mask != 0
+    return m.contiguous().view(torch.uint8)
+
+
+def dmon_dense_terms(adj: Optional[Tensor], s: Tensor, mask: Optional[Tensor] = None,
+                     graph_sizes: Optional[Tensor] = None, deg: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
+    """(deg [B,N] or None, part [B,ceil(N/64),2K+2]) of a padded batch: degrees d = row sums of adj on real rows (one pass
+    over adj) and the per-block partial sums (S^T d | S^T 1 | sum d | node count) of DMoN's losses
+    (utils/losses.py:1083-1148, 1216-1265).  ``adj`` None: the degrees ``deg`` [B,N] given (:func:`dmon_edge_degrees`),
+    or none (the cluster loss alone)."""
+    dev = N.require_device(adj, s, mask, deg)
+    s = N.f32c(s)
+    B, Nn, Kc = s.shape
+    a = None
+    if adj is not None:
+        a = N.f32c(adj)
+        if a.shape != (B, Nn, Nn):
+            raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
+    nsplit = max(1, -(-Nn // _DMON_ROWS))
+    if a is not None:
+        deg = torch.empty(B, Nn, dtype=torch.float32, device=dev)
+    elif deg is not None:
+        deg = N.f32c(deg)
+        if deg.shape != (B, Nn):
+            raise ValueError(f"deg {tuple(deg.shape)} does not match s {tuple(s.shape)}")
+    part = torch.empty(B, nsplit, 2 * Kc + 2, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_dmon_dense_terms_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+                                             N.ptr(_mask_bytes(mask, B, Nn)), nsplit, N.ptr(deg), N.ptr(part),
+                                             N.stream_ptr(dev)), "tgp_dmon_dense_terms_f32")
+    return deg, part
+
+
+def dmon_edge_degrees(edge_index: Tensor, edge_weight: Optional[Tensor], node_ptr: Tensor, edge_ptr: Tensor,
+                      max_nodes: int, in_degrees: bool) -> Tensor:
+    """deg [B,max_nodes] (padded) of a row-sorted edge list with per-graph node / edge offsets: the row sums of the
+    densified adjacency (``in_degrees``: of its transpose, what the batched poolers densify when adj_transpose), one
+    launch, summed in edge order."""
+    dev = N.require_device(edge_index, edge_weight, node_ptr, edge_ptr)
+    row, col = _edge_rows(edge_index)
+    key = col if in_degrees else row
+    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    B = node_ptr.numel() - 1
+    deg = torch.empty(B, int(max_nodes), dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_dmon_edge_degrees_f32(N.ptr(key) if key.numel() else None, N.ptr(w), key.numel(),
+                                              N.ptr(N.i64c(node_ptr)), N.ptr(N.i64c(edge_ptr)), B, int(max_nodes),
+                                              N.ptr(deg), N.stream_ptr(dev)), "tgp_dmon_edge_degrees_f32")
+    return deg
+
+
+def dmon_node_terms(s: Tensor, deg: Optional[Tensor], ptr: Tensor, max_nodes: int) -> Tensor:
+    """part [B,ceil(max_nodes/64),2K+2] of :func:`dmon_dense_terms` for an un-padded batch: s [Ntot,K], deg [Ntot] (None:
+    the cluster loss alone), ptr [B+1] node offsets of the sorted batch, ``max_nodes`` its largest graph."""
+    dev = N.require_device(s, deg, ptr)
+    s, ptr = N.f32c(s), N.i64c(ptr)
+    d = None if deg is None else N.f32c(deg.reshape(-1))
+    if d is not None and d.numel() != s.size(0):
+        raise ValueError("dmon_node_terms: deg must hold one value per row of s")
+    B, Kc = ptr.numel() - 1, s.size(1)
+    nsplit = max(1, -(-int(max_nodes) // _DMON_ROWS))
+    part = torch.empty(B, nsplit, 2 * Kc + 2, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_dmon_node_terms_f32(N.ptr(s), N.ptr(d), N.ptr(ptr), B, Kc, nsplit, N.ptr(part), N.stream_ptr(dev)),
+            "tgp_dmon_node_terms_f32")
+    return part
+
+
+def dmon_loss_terms(part: Tensor, raw: Optional[Tensor], tr: Optional[Tensor], gram: Optional[Tensor], sqrt_k: float,
+                    clamp_m: bool, coeffs=(1.0, 1.0, 1.0)):
+    """(out [3,B], ca [B,K], cs [B,K], stats [B,4]): DMoN's per-graph spectral, cluster and orthogonality terms, each
+    times its coefficient in ``coeffs``, in one launch from the partial sums of :func:`dmon_dense_terms` /
+    :func:`dmon_node_terms`; trace(S^T A S) from the diagonal of ``raw`` or from ``tr`` [B]; ``gram`` None: the
+    orthogonality row is 0."""
+    dev = N.require_device(part, raw, tr, gram)
+    part = N.f32c(part)
+    B, nsplit, P = part.shape
+    Kc = (P - 2) // 2
+    raw = None if raw is None else N.f32c(raw)
+    tr = None if tr is None else N.f32c(tr.reshape(-1))
+    gram = None if gram is None else N.f32c(gram)
+    for t, shape in ((raw, (B, Kc, Kc)), (gram, (B, Kc, Kc)), (tr, (B,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"dmon_loss_terms: operand {tuple(t.shape)}, expected {shape}")
+    out = torch.empty(3, B, dtype=torch.float32, device=dev)
+    ca = torch.empty(B, Kc, dtype=torch.float32, device=dev)
+    cs = torch.empty(B, Kc, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_dmon_loss_terms_f32(N.ptr(part), nsplit, N.ptr(raw), N.ptr(tr), N.ptr(gram), B, Kc, float(sqrt_k),
+                                            1 if clamp_m else 0, losses_eps(), *(float(c) for c in coeffs), N.ptr(out),
+                                            N.ptr(ca), N.ptr(cs), N.ptr(stats), N.stream_ptr(dev)),
+            "tgp_dmon_loss_terms_f32")
+    return out, ca, cs, stats
+
+
+def dmon_loss_terms_bwd(g_terms: Tensor, stats: Tensor, gram: Optional[Tensor], Kc: int, sqrt_k: float, want_raw: bool,
+                        want_tr: bool, coeffs=(1.0, 1.0, 1.0)):
+    """(g_raw [B,K,K] or None, g_tr [B] or None, coef [B,2], W [B,K,K] or None): the gradients of
+    :func:`dmon_loss_terms` (same ``coeffs``) from the upstream gradients [3,B], one launch (see
+    tgp_dmon_loss_terms_bwd_f32)."""
+    dev = N.require_device(g_terms, stats, gram)
+    g_terms, stats = N.f32c(g_terms), N.f32c(stats)
+    gram = None if gram is None else N.f32c(gram)
+    B = stats.size(0)
+    g_raw = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if want_raw else None
+    g_tr = torch.empty(B, dtype=torch.float32, device=dev) if want_tr else None
+    W = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if gram is not None else None
+    coef = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_dmon_loss_terms_bwd_f32(N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(sqrt_k),
+                                                *(float(c) for c in coeffs), N.ptr(g_raw), N.ptr(g_tr), N.ptr(coef), N.ptr(W), N.stream_ptr(dev)),
+            "tgp_dmon_loss_terms_bwd_f32")
+    return g_raw, g_tr, coef, W
+
+
+def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: int, nodes_per_graph: int,
+            batch: Optional[Tensor], out: Tensor, accumulate: bool) -> Tensor:
+    """out[r,k] (+)= coef[b,0] deg[r] ca[b,k] + coef[b,1] cs[b,k] over the ``rows`` rows of S: the spectral and cluster
+    parts of DMoN's dS, one elementwise pass.  Graph of a row: batch[r] (un-padded) or r // nodes_per_graph."""
+    dev = N.require_device(deg, ca, cs, coef, batch, out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * ca.size(1):
+        raise ValueError("dmon_ds: out must be a contiguous float32 tensor of rows x K values")
+    d = None if deg is None else N.f32c(deg.reshape(-1))
+    b = None if batch is None else N.i64c(batch)
+    N.check(N.lib().tgp_dmon_ds_f32(N.ptr(d), N.ptr(N.f32c(ca)), N.ptr(N.f32c(cs)), N.ptr(N.f32c(coef)), rows,
+                                    nodes_per_graph, N.ptr(b), ca.size(0), ca.size(1), 1 if accumulate else 0, out.data_ptr(),
+                                    N.stream_ptr(dev)), "tgp_dmon_ds_f32")
+    return out
+
+
 def topk_minscore(score: Tensor, ptr: Tensor, min_score: float, tol: float = 1e-7) -> Tuple[Tensor, Tensor]:
     """(prob [N], node_index [k]): per-graph softmax of ``score`` and the nodes above the min_score threshold, ascending
     (select/topk_select.py:186-194 with PyG's softmax / topk); ``ptr`` = node offsets of the sorted batch."""

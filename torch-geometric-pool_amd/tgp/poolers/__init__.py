@@ -1,9 +1,10 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon}.py).
 
-Only the five poolers named by the hot path are built: ``topk``, ``graclus``, ``ndp``, ``diff``,
+``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
-``ValueError("Unknown pooler_name=...")`` an unknown name does.
+``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling`` is built and exported as a class;
+its ``dmon`` alias is not registered yet.
 """
 from __future__ import annotations
 
@@ -24,6 +25,9 @@ from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPoo
 from ..utils.ops import batch_info, is_dense_adj
 from ..utils.losses import (
     _MinCutTermsFn,
+    _dmon_native,
+    cluster_loss,
+    dmon_loss_terms,
     entropy_loss,
     link_pred_loss,
     mincut_loss,
@@ -31,6 +35,9 @@ from ..utils.losses import (
     orthogonality_loss,
     sparse_link_pred_loss,
     sparse_mincut_loss,
+    sparse_spectral_loss,
+    spectral_loss,
+    unbatched_cluster_loss,
     unbatched_entropy_loss,
     unbatched_orthogonality_loss,
 )
@@ -224,7 +231,18 @@ class _DenseMLPPooling(DenseSRCPooling):
     def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
         raise NotImplementedError
 
-    _loss_needs_raw = False  # MinCut's cut loss reads the raw S^T A S
+    # which auxiliary losses the pooler computes: "diff" (link + entropy), "mincut" (cut + ortho: their per-graph
+    # terms come out of the pooling kernels), "dmon" (spectral + cluster + ortho from the raw S^T A S and their own
+    # loss kernels; the one-node training paths and the rows route decline it)
+    _loss_kind = "diff"
+
+    @property
+    def _mincut_terms(self) -> bool:
+        return self._loss_kind == "mincut"
+
+    @property
+    def _wants_raw(self) -> bool:
+        return self._loss_kind in ("mincut", "dmon")
 
     def _fused_diff_scales(self, adj, mask, adj_numel=None):
         """(link_scale, ent_scale) when the pooler's two losses can ride on the fused training call (DiffPool).
@@ -261,11 +279,11 @@ class _DenseMLPPooling(DenseSRCPooling):
         diff_scales = self._fused_diff_scales(adj, mask)
         out = K.dense_pool_select(
             x, adj, last.weight.detach(), None if last.bias is None else last.bias.detach(), mask, flags,
-            want_raw=self._loss_needs_raw, mincut_terms=self._loss_needs_raw, want_batch=want_batch,
+            want_raw=self._wants_raw, mincut_terms=self._mincut_terms, want_batch=want_batch,
             diff_stats=diff_scales is not None)
         s, x_pool, raw, adj_pool, terms = out[:5]
         so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw, adj_pool) + ((terms,) if self._loss_needs_raw else ())
+        fused = (x_pool, raw, adj_pool) + ((terms,) if self._mincut_terms else ())
         if diff_scales is not None:  # DiffPool (r6): both losses from the launch's per-graph records, one tail launch
             fused = fused + (K.diffpool_stats_tail(terms, diff_scales[0], diff_scales[1]),)
         return so, fused, (out[5] if want_batch else None)
@@ -294,6 +312,8 @@ class _DenseMLPPooling(DenseSRCPooling):
             return None  # (the edge weights get no gradient from the fused backward)
         training = torch.is_grad_enabled() and (x.requires_grad or last.weight.requires_grad
                                                 or (last.bias is not None and last.bias.requires_grad))
+        if training and self._loss_kind == "dmon":
+            return None  # (DMoN trains on the operator route)
         # (a pooler whose losses need the dense adjacency -- DiffPool's link loss -- gets it as a side output of the launch)
         if training and not (_FOLD_TRAINING and not c.edge_weight_norm
                              and K.mlp_select_bwd_fits(last.weight.size(0), x.size(1))):
@@ -325,7 +345,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         if training:  # one autograd node; the padded tensors the backward reads are side outputs of the same launch
             from .. import functions as Fn
             diff_scales = None
-            if not self._loss_needs_raw:
+            if not self._mincut_terms:
                 self._known_nodes = x.size(0)
                 diff_scales = self._fused_diff_scales(None, None, info.num_graphs * info.max_nodes * info.max_nodes)
                 if diff_scales is None:
@@ -334,12 +354,19 @@ class _DenseMLPPooling(DenseSRCPooling):
                     return None
             s, mask, x_pool, raw, adj_pool, terms, bp = Fn.select_pool_sparse(
                 x, last.weight, last.bias, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs,
-                info.max_nodes, flags, self.adj_transpose, self._loss_needs_raw, diff_scales, info.sizes)
-        elif self._loss_needs_raw:
+                info.max_nodes, flags, self.adj_transpose, self._mincut_terms, diff_scales, info.sizes)
+        elif self._mincut_terms:
             s, mask, x_pool, raw, adj_pool, terms, bp = K.dense_pool_select_sparse(
                 x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
                 last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
                 want_raw=True, mincut_terms=True)
+        elif self._loss_kind == "dmon":  # raw from the launch, degrees from the edge list: no dense adjacency either
+            s, mask, x_pool, raw, adj_pool, _, bp = K.dense_pool_select_sparse(
+                x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
+                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
+                want_raw=True, mincut_terms=False)
+            deg = K.dmon_edge_degrees(edge_index, edge_weight, info.ptr, edge_ptr, info.max_nodes, self.adj_transpose)
+            terms = self._dmon_means(s, raw, mask, info.sizes, deg=deg)
         else:  # DiffPool, inference (r6): both losses from per-graph records of the same launch -- no dense adjacency
             s, mask, x_pool, raw, adj_pool, terms, bp, dstats = K.dense_pool_select_sparse(
                 x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
@@ -352,7 +379,7 @@ class _DenseMLPPooling(DenseSRCPooling):
             return None  # rows not sorted: what the kernel computed on clamped ranges is dropped
         so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
         so._graph_sizes = info.sizes
-        if not self._loss_needs_raw:
+        if self._loss_kind == "diff":
             # (both losses came with the fused call: a LossPair -- training -- or a [2] tensor in the slot of `diff`)
             return so, (x_pool, None, adj_pool, None, terms), bp, None
         return so, (x_pool, raw, adj_pool, terms, None), bp, None
@@ -365,7 +392,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         from .. import functions as Fn, kernels as K
         sel, c = self.selector, self.connector
         lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        if (type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
+        if (self._loss_kind == "dmon"
+                or type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
                 or type(self.reducer) is not BaseReduce or not (isinstance(x, Tensor) and isinstance(adj, Tensor))
                 or x.dim() != 3 or adj.dim() != 3 or not x.is_cuda or x.dtype != torch.float32
                 or adj.dtype != torch.float32 or (mask is not None and mask.dtype != torch.bool)
@@ -379,11 +407,11 @@ class _DenseMLPPooling(DenseSRCPooling):
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
         diff_scales = self._fused_diff_scales(adj, mask)
         s, x_pool, raw, adj_pool, pair, bp = Fn.select_pool_small(
-            x, adj, last.weight, last.bias, mask, flags, self._loss_needs_raw, self._loss_needs_raw, diff_scales,
+            x, adj, last.weight, last.bias, mask, flags, self._mincut_terms, self._mincut_terms, diff_scales,
             graph_sizes, want_batch)
         so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw if self._loss_needs_raw else None, adj_pool)
-        if self._loss_needs_raw:
+        fused = (x_pool, raw if self._mincut_terms else None, adj_pool)
+        if self._mincut_terms:
             fused = fused + (pair,)
         if diff_scales is not None:
             fused = fused + (pair,)
@@ -396,7 +424,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         ran 65-71).  Returns ``(SelectOutput, fused, None)`` like :meth:`_select_reduce_connect_train`, or None."""
         from .. import functions as Fn, kernels as K
         sel, c = self.selector, self.connector
-        if (not _FOLD_TRAINING or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
+        if (not _FOLD_TRAINING or self._loss_kind == "dmon" or type(c) is not DenseConnect
+                or type(self.reducer) is not BaseReduce
                 or not (isinstance(x, Tensor) and isinstance(adj, Tensor)) or x.dim() != 3 or adj.dim() != 3
                 or not x.is_cuda or x.dtype != torch.float32 or adj.dtype != torch.float32
                 or (mask is not None and mask.dtype != torch.bool) or not torch.is_grad_enabled()
@@ -421,8 +450,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         if k == 0 or k > 4096 or K.dense_pool_is_small(x.size(0), x.size(1), k, x.size(2)):
             return None
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
-        mode, scales = (1, (0.0, 0.0)) if self._loss_needs_raw else (0, (0.0, 0.0))
-        if not self._loss_needs_raw:
+        mode, scales = (1, (0.0, 0.0)) if self._mincut_terms else (0, (0.0, 0.0))
+        if not self._mincut_terms:
             diff_scales = self._fused_diff_scales(adj, mask)
             if diff_scales is None:
                 return None
@@ -431,7 +460,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                                                            symmetry() if callable(symmetry) else symmetry)
         if so is None:
             so = SelectOutput(s=s_out, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw if self._loss_needs_raw else None, adj_pool, pair)
+        fused = (x_pool, raw if self._mincut_terms else None, adj_pool, pair)
         return so, fused, None
 
     @staticmethod
@@ -468,7 +497,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         from .. import kernels as K
         from .. import functions as Fn
         c, sel = self.connector, self.selector
-        if (type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
+        if (self._loss_kind == "dmon" or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
                 or (self.sparse_output and not batched_out)
                 or not (isinstance(x, Tensor) and isinstance(edge_index, Tensor))
                 or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32
@@ -546,7 +575,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         transposed = bool(batched_out and self.adj_transpose)
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose if batched_out else False,
                               c.edge_weight_norm)
-        mincut = self._loss_needs_raw
+        mincut = self._mincut_terms
         sw2, scales = 0.0, (0.0, 0.0)
         if not mincut:  # DiffPool: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
             # (batched form, losses.py:644-652: the dense A has the duplicates summed -- the same list after coalescing)
@@ -697,7 +726,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                 self._sizes_hint = (weakref.ref(adj), graph_sizes)  # valid for exactly this adjacency tensor
             diff_scales = self._fused_diff_scales(adj, mask)
             fused = folded[1] if folded is not None else self.reduce_connect(
-                x, adj, so, want_raw=self._loss_needs_raw, want_mincut_terms=self._loss_needs_raw,
+                x, adj, so, want_raw=self._wants_raw, want_mincut_terms=self._mincut_terms,
                 want_diff_losses=diff_scales)
             if fused is None and _FOLD_TRAINING:  # a selector with hidden layers made S: the pooling step is one node still
                 big = self._select_reduce_connect_large(x, adj, mask, graph_sizes, so=so, symmetry=symmetry)
@@ -709,7 +738,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                     batch_pool = folded[2]
                 else:
                     batch_pool = self.reducer.reduce_batch(so, batch if batch is not None else so.batch)
-                terms = fused[3] if self._loss_needs_raw else None
+                terms = fused[3] if self._mincut_terms else None
                 diff = fused[-1] if diff_scales is not None else None
                 loss = self._loss_from_fused(adj, so, mask, raw, terms, diff)
             else:
@@ -819,7 +848,7 @@ class MinCutPooling(_DenseMLPPooling):
                                               edge_weight_norm=c.edge_weight_norm)
         return adj_pool, loss
 
-    _loss_needs_raw = True
+    _loss_kind = "mincut"
 
     def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
         if terms is not None and so.s.dtype == torch.float32:
@@ -860,8 +889,73 @@ class MinCutPooling(_DenseMLPPooling):
                 "ortho_loss_coeff": self.ortho_loss_coeff}
 
 
+class DMoNPooling(_DenseMLPPooling):
+    r"""DMoN pooling: MinCut's Select / Reduce / Connect with the spectral (modularity), cluster and orthogonality losses
+    on the *raw* S^T A S (reference poolers/dmon.py:23-333).  Batched: the losses read the densified adjacency (A^T when
+    ``adj_transpose``: in-degrees), padded nodes excluded by the mask; unbatched: out-degrees of the edge list."""
+
+    _loss_kind = "dmon"
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, act: str = None, dropout: float = 0.0,
+                 spectral_loss_coeff: float = 1.0, cluster_loss_coeff: float = 1.0, ortho_loss_coeff: float = 0.0,
+                 remove_self_loops: bool = True, degree_norm: bool = True, edge_weight_norm: bool = False,
+                 adj_transpose: bool = True, lift: str = "precomputed", s_inv_op: str = "transpose",
+                 batched: bool = True, sparse_output: bool = False, cache_preprocessing: bool = False):
+        super().__init__(in_channels, k, act, dropout, remove_self_loops, degree_norm, edge_weight_norm,
+                         adj_transpose, lift, s_inv_op, batched, sparse_output, cache_preprocessing)
+        self.spectral_loss_coeff = spectral_loss_coeff
+        self.ortho_loss_coeff = ortho_loss_coeff
+        self.cluster_loss_coeff = cluster_loss_coeff
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
+        c = self.connector
+        raw = c.dense_connect(adj=adj, s=so.s)
+        loss = self.compute_loss(adj, so.s, raw, mask)
+        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
+                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
+                                              edge_weight_norm=c.edge_weight_norm)
+        return adj_pool, loss
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+        if terms is not None:  # the one-launch sparse route: the three batch means, coefficients applied
+            return {"spectral_loss": terms[0], "cluster_loss": terms[1], "ortho_loss": terms[2]}
+        return self.compute_loss(adj, so.s, raw, mask)
+
+    def _dmon_means(self, S, raw, mask, graph_sizes, adj=None, deg=None) -> Tensor:
+        """[3]: the batch means of the three terms (coefficients applied) from one pass over adj or the given degrees,
+        one over S, S^T S and one tail launch."""
+        coeffs = (self.spectral_loss_coeff, self.cluster_loss_coeff, self.ortho_loss_coeff)
+        return dmon_loss_terms(adj, S, raw, mask, graph_sizes, coeffs, deg=deg).mean(dim=1)
+
+    def _scaled(self, spectral, cluster, ortho) -> dict:
+        return {"spectral_loss": spectral if self.spectral_loss_coeff == 1 else spectral * self.spectral_loss_coeff,
+                "cluster_loss": cluster if self.cluster_loss_coeff == 1 else cluster * self.cluster_loss_coeff,
+                "ortho_loss": ortho if self.ortho_loss_coeff == 1 else ortho * self.ortho_loss_coeff}
+
+    def compute_loss(self, adj: Tensor, S: Tensor, adj_pooled: Tensor, mask: Optional[Tensor]) -> dict:
+        if (_dmon_native(adj, S, adj_pooled) and S.dim() == 3 and adj.dim() == 3 and adj_pooled.dim() == 3
+                and not adj.requires_grad):
+            # the three per-graph tails from one pass over adj, one over S, S^T S and one tail launch (native backward)
+            three = self._dmon_means(S, adj_pooled, mask, self._sizes_for(adj), adj=adj)
+            return {"spectral_loss": three[0], "cluster_loss": three[1], "ortho_loss": three[2]}
+        return self._scaled(spectral_loss(adj, S, adj_pooled, mask, batch_reduction="mean"),
+                            cluster_loss(S, mask=mask, batch_reduction="mean"),
+                            orthogonality_loss(S, batch_reduction="mean"))
+
+    def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
+        ei, ew = connectivity_to_edge_index(edge_index, edge_weight)
+        return self._scaled(sparse_spectral_loss(ei, S, ew, batch, batch_reduction="mean"),
+                            unbatched_cluster_loss(S, batch, batch_reduction="mean"),
+                            unbatched_orthogonality_loss(S, batch, batch_reduction="mean"))
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched, "spectral_loss_coeff": self.spectral_loss_coeff,
+                "cluster_loss_coeff": self.cluster_loss_coeff, "ortho_loss_coeff": self.ortho_loss_coeff}
+
+
 # =============================================================================== factory
-pooler_classes = ["DiffPool", "GraclusPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon" is not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["DMoNPooling", "DiffPool", "GraclusPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

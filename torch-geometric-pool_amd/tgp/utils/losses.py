@@ -1,5 +1,5 @@
-"""Auxiliary losses DiffPool / MinCut compute between Reduce and Connect
-(reference: tgp/utils/losses.py:39-123, 476-483, 644-708).
+"""Auxiliary losses DiffPool / MinCut / DMoN compute between Reduce and Connect
+(reference: tgp/utils/losses.py:39-123, 435-483, 644-708, 1083-1265).
 
 The batched dense losses run on native kernels: the link-prediction residual is
 reduced inside the GEMM epilogue so S S^T [B,N,N] is never materialised, the entropy and the
@@ -253,3 +253,142 @@ def sparse_link_pred_loss(S: Tensor, edge_index: Tensor, edge_weight: Optional[T
         return loss / (n * n) if n > 0 else loss
     sizes, _ = graph_ptr(batch, nb)
     return loss / (sizes * sizes).sum().clamp(min=1)  # stays on the device: no host round trip
+
+
+# ------------------------------------------------------------------------------------------------ DMoN
+class _DMoNTermsFn(torch.autograd.Function):
+    """[3,B] per-graph spectral, cluster and orthogonality terms of DMoN (utils/losses.py:1083-1265 and :59-70) with a
+    native backward.  Forward: the partial pass over S (behind one pass over adj for the degrees, ``layout`` "dense"),
+    S^T S when ``want_ortho``, one tail launch.  Backward: one launch for the per-graph coefficients and W, the product
+    S (W + W^T), one elementwise pass for dS = alpha_b d ca_b + beta_b cs_b; the gradient of raw is -(g_spec / 2m) I,
+    that of ``tr`` -g_spec / 2m.  Neither the adjacency nor the degrees get a gradient here.
+
+    ``layout``: ("dense", mask, graph_sizes[, deg [B,N]]) with ``source`` = adj [B,N,N] or None (then the degrees given,
+    or none), or ("flat", ptr, batch, max_nodes) with ``source`` = deg [Ntot] or None.  ``coeffs``: the three rows come out times these (the pooler's loss
+    coefficients: no separate scaling launch)."""
+
+    @staticmethod
+    def forward(ctx, S, raw, tr, source, layout, want_ortho, sqrt_k, clamp_m, coeffs):
+        if layout[0] == "dense":
+            deg, part = K.dmon_dense_terms(source, S, layout[1], layout[2], deg=layout[3] if len(layout) > 3 else None)
+            gram = K.dense_pool(S, None, S, graph_sizes=layout[2])[0] if want_ortho else None
+        else:
+            deg = source
+            part = K.dmon_node_terms(S, deg, layout[1], layout[3])
+            gram = None
+        out, ca, cs, stats = K.dmon_loss_terms(part, raw, tr, gram, sqrt_k, clamp_m, coeffs)
+        ctx.save_for_backward(S, deg, ca, cs, stats, gram)
+        ctx.layout, ctx.sqrt_k, ctx.coeffs = layout, sqrt_k, coeffs
+        ctx.has_raw, ctx.has_tr = raw is not None, tr is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S, deg, ca, cs, stats, gram = ctx.saved_tensors
+        g_raw, g_tr, coef, W = K.dmon_loss_terms_bwd(g, stats, gram, S.size(-1), ctx.sqrt_k,
+                                                     ctx.has_raw and ctx.needs_input_grad[1],
+                                                     ctx.has_tr and ctx.needs_input_grad[2], ctx.coeffs)
+        g_s = None
+        if ctx.needs_input_grad[0]:
+            acc = W is not None
+            g_s = K.bmm(S, W + W.transpose(1, 2)) if acc else torch.empty(S.shape, dtype=torch.float32, device=S.device)
+            if ctx.layout[0] == "dense":
+                K.dmon_ds(deg, ca, cs, coef, S.size(0) * S.size(1), S.size(1), None, g_s, acc)
+            else:
+                K.dmon_ds(deg, ca, cs, coef, S.size(0), max(S.size(0), 1), ctx.layout[2], g_s, acc)
+            g_s = g_s.to(S.dtype)
+        return g_s, g_raw, g_tr, None, None, None, None, None, None
+
+
+_ONES3 = (1.0, 1.0, 1.0)
+
+
+def _dmon_native(*ts) -> bool:
+    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
+    forms below."""
+    return not any(t is not None and t.dtype == torch.float64 for t in ts)
+
+
+def dmon_loss_terms(adj: Optional[Tensor], S: Tensor, adj_pooled: Tensor, mask: Optional[Tensor] = None,
+                    graph_sizes: Optional[Tensor] = None, coeffs=(1.0, 1.0, 1.0), deg: Optional[Tensor] = None) -> Tensor:
+    """[3,B]: per-graph values of :func:`spectral_loss`, :func:`cluster_loss` and :func:`orthogonality_loss` (before the
+    batch reduction) of a padded batch, each times its coefficient in ``coeffs``, float32 device operands: one pass over
+    adj (or ``adj`` None and the degrees ``deg`` [B,N] given), one over S, S^T S, one tail launch.  ``graph_sizes`` (this
+    build only): real nodes per graph of a zero-padded batch, lets the passes skip the padding."""
+    return _DMoNTermsFn.apply(S, adj_pooled, None, adj, ("dense", mask, graph_sizes, deg), True,
+                              math.sqrt(S.size(-1)), False, tuple(float(c) for c in coeffs))
+
+
+def spectral_loss(adj: Tensor, S: Tensor, adj_pooled: Tensor, mask: Optional[Tensor] = None,
+                  num_supernodes: Optional[int] = None, batch_reduction: str = "mean") -> Tensor:
+    """DMoN's spectral (modularity) loss -(trace(S^T A S) - ||S^T d||^2 / 2m) / 2m per graph, d the (masked) row sums of
+    ``adj``, 0 for a graph without edges (reference utils/losses.py:1083-1148)."""
+    if _dmon_native(adj, S, adj_pooled) and S.dim() == 3 and not adj.requires_grad:
+        terms = _DMoNTermsFn.apply(S, adj_pooled, None, adj, ("dense", mask, None), False, 1.0, False, _ONES3)
+        return _reduce(terms[0], batch_reduction)
+    if mask is None:
+        mask = torch.ones(S.size(0), S.size(1), dtype=torch.bool, device=S.device)
+    deg = adj.sum(-1) * mask
+    m = deg.sum(-1) / 2
+    safe_m = torch.where(m > 0, m, torch.ones_like(m))
+    ca = torch.einsum("bnk,bn->bk", S, deg)
+    tr = torch.diagonal(adj_pooled, dim1=-2, dim2=-1).sum(-1)
+    loss = -(tr - (ca * ca).sum(-1) / (2 * safe_m)) / (2 * safe_m)
+    return _reduce(torch.where(m > 0, loss, torch.zeros_like(loss)), batch_reduction)
+
+
+def cluster_loss(S: Tensor, mask: Optional[Tensor] = None, num_supernodes: Optional[int] = None,
+                 batch_reduction: str = "mean") -> Tensor:
+    """DMoN's cluster loss ||S^T 1|| sqrt(K) / n - 1 per graph, n = mask.sum(1) (N without a mask)
+    (reference utils/losses.py:1216-1265)."""
+    k = S.size(-1) if num_supernodes is None else num_supernodes
+    if _dmon_native(S) and S.dim() == 3:
+        terms = _DMoNTermsFn.apply(S, None, None, None, ("dense", mask, None), False, math.sqrt(k), False, _ONES3)
+        return _reduce(terms[1], batch_reduction)
+    n = S.size(1) if mask is None else mask.sum(dim=1)
+    return _reduce(torch.norm(S.sum(1), dim=1) / n * math.sqrt(k) - 1, batch_reduction)
+
+
+def _flat_layout(S: Tensor, batch: Optional[Tensor]):
+    """("flat", ptr, batch, max_nodes) of a sorted batch vector, or None when the batch is not sorted."""
+    n = S.size(0)
+    if batch is None:
+        return ("flat", Fn._whole_range(n, S.device), None, n)
+    from .ops import batch_info
+    info = batch_info(batch)
+    if not info.is_sorted:
+        return None
+    return ("flat", info.ptr, batch, info.max_nodes)
+
+
+def sparse_spectral_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Tensor] = None,
+                         batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The spectral loss of an edge list (reference utils/losses.py:1151-1213): out-degrees scatter(w, edge_index[0]),
+    trace(S_g^T A_g S_g) = sum over the graph's edges of w (S_src . S_dst), m_g clamped to eps."""
+    n = S.size(0)
+    w = _edge_weights(edge_index, edge_weight, S)
+    nb = num_graphs_of(batch)
+    bvec = _batch_or_zeros(batch, n, S.device)
+    src = edge_index[0]
+    deg = _seg_sum(w, src, n)
+    layout = _flat_layout(S, batch) if _dmon_native(S, w) and S.dim() == 2 and n > 0 else None
+    if layout is not None and not w.requires_grad:
+        tr = _seg_sum(w * Fn.edge_dot(S, edge_index), bvec[src], nb)
+        return _reduce(_DMoNTermsFn.apply(S, None, tr, deg, layout, False, 1.0, True, _ONES3)[0], batch_reduction)
+    tr = _seg_sum(w * (S[src] * S[edge_index[1]]).sum(-1), bvec[src], nb)
+    m = (_seg_sum(w, bvec[src], nb) / 2).clamp(min=eps)
+    ca = _seg_sum(S * deg.unsqueeze(-1), bvec, nb)
+    return _reduce(-(tr - (ca * ca).sum(-1) / (2 * m)) / (2 * m), batch_reduction)
+
+
+def unbatched_cluster_loss(S: Tensor, batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The cluster loss of an un-padded batch (reference utils/losses.py:435-473): ||S_g^T 1|| sqrt(K) / n_g - 1."""
+    n, k = S.shape
+    layout = _flat_layout(S, batch) if _dmon_native(S) and n > 0 else None
+    if layout is not None:
+        terms = _DMoNTermsFn.apply(S, None, None, None, layout, False, math.sqrt(k), True, _ONES3)
+        return _reduce(terms[1], batch_reduction)
+    nb = num_graphs_of(batch)
+    bvec = _batch_or_zeros(batch, n, S.device)
+    sizes = torch.bincount(bvec, minlength=nb)[:nb].to(S.dtype)
+    return _reduce(torch.norm(_seg_sum(S, bvec, nb), dim=1) / sizes * math.sqrt(k) - 1, batch_reduction)
