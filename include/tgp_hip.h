@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10043 /* 1.0.1 of the reference, ABI revision 42 (DMoN: tgp_dmon_dense_terms_f32, tgp_dmon_edge_degrees_f32, tgp_dmon_node_terms_f32, tgp_dmon_loss_terms_f32 / _bwd_f32, tgp_dmon_ds_f32; revision 41, r6: tgp_mask_index_*, node_rank on tgp_kron_batched_count / _fill; the dense poolers' training step at C2 scale: tgp_dense_pool_train_*, tgp_mincut_terms_fused_f32, tgp_softmax_bwd_ex_f32, tgp_copy_cols2_f32; tgp_result_wait_pack_cols; tgp_spmm_csr_stats_f32 / _entropy_f32; tgp_segment_gemm_tn3_post_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -552,6 +552,46 @@ int tgp_graclus_relabel_i64(const int64_t* label, int64_t num_nodes, void* ws, s
                                                     label is shared by at most two nodes -- a matching */,
                             float* ones /* optional [N]: filled with 1.0f, the values of the assignment matrix */,
                             void* stream);
+
+/* k-MIS selection (select/kmis_select.py; csrc/kmis_select.hip).  A node's priority is the 64-bit key (prio << 32) | node,
+ * smaller first: prio = the node's rank in a caller's permutation, or its updated score's bits in descending order, so ties
+ * go to the lower node index.  Every entry writes label [N] int64 = the MIS node that owns each node (an MIS node owns
+ * itself); tgp_graclus_relabel_i64 turns the owners into consecutive ids in ascending owner order.
+ *
+ * tgp_kmis_graphs: a sorted batch (graph_ptr [B + 1]) whose longest graph has at most max_graph_nodes <=
+ * tgp_kmis_max_graph_nodes() nodes, one workgroup per graph, all rounds in LDS, one launch.  mode 0: rank [N] int32;
+ * 1: score [N] compared as it is; 2: score / (A^T + I)^k 1 ("greedy", integer counts), also written to updated [N].
+ * words[0] != 0: declined (bit 0: an edge list that is not grouped by graph, an edge between two graphs, a graph longer
+ * than declared; bit 1: the round bound) -- the caller runs the device-wide entries instead.
+ *
+ * Device-wide: tgp_kmis_rounds_start (keys from rank, or from updated when rank is null; ws of
+ * tgp_kmis_workspace_bytes(N)), then tgp_kmis_rounds any number of times (round_base = rounds launched so far;
+ * open_flags[j] = 1 when round j still met an unmasked node, so the first 0 says the set is maximal; 2 * order_k launches
+ * per round), then tgp_kmis_clusters (rounds_done = rounds launched in all).
+ *
+ * tgp_kmis_greedy_f32: updated = score / (A^T + I)^k 1 device-wide (uses the same workspace, before the rounds).
+ * tgp_kmis_wsum_f32: out[c] = in[c] + sum of in[row[e]] over the edges e into c in the order of the by-destination index
+ * (grp_ptr [N + 1], grp_perm [E] of tgp_assign_index_build over col: edge-list order inside a group); with score,
+ * out[c] = score[c] / that sum ("w-greedy": one call per hop, score on the last).  tgp_kmis_degree_f32: the weighted
+ * in-degree in the same order (w null: the edge count).  tgp_kmis_mis_index_i64: mis[id] = owner of cluster id. */
+int tgp_kmis_max_graph_nodes(void);
+size_t tgp_kmis_workspace_bytes(int64_t num_nodes);
+int tgp_kmis_graphs(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes, const int64_t* graph_ptr,
+                    int64_t num_graphs, int max_graph_nodes, int order_k, int mode, const float* score,
+                    const int32_t* rank, float* updated, int64_t* label, int32_t* words, void* stream);
+int tgp_kmis_rounds_start(const int32_t* rank, const float* updated, int64_t num_nodes, void* ws, size_t ws_bytes,
+                          void* stream);
+int tgp_kmis_rounds(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes, int order_k, void* ws,
+                    int64_t round_base, int rounds, int32_t* open_flags, void* stream);
+int tgp_kmis_clusters(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes, int order_k, void* ws,
+                      int64_t rounds_done, int64_t* label, void* stream);
+int tgp_kmis_greedy_f32(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes, int order_k,
+                        const float* score, void* ws, size_t ws_bytes, float* updated, void* stream);
+int tgp_kmis_wsum_f32(const int64_t* row, const int32_t* grp_ptr, const int32_t* grp_perm, const float* in,
+                      const float* score, int64_t num_nodes, float* out, void* stream);
+int tgp_kmis_degree_f32(const int32_t* grp_ptr, const int32_t* grp_perm, const float* w, int64_t num_nodes, float* out,
+                        void* stream);
+int tgp_kmis_mis_index_i64(const int64_t* label, const int64_t* index, int64_t num_nodes, int64_t* mis, void* stream);
 
 /* TopkSelect scoring (select/topk_select.py:176, score = (x * w).sum(-1)): out[i] = <x[i,:], w>, one pass over
  * x [N,F] (row stride ldx); and the matching weight gradient out[f] = sum_i g[i] x[i,f] (fixed-order two-level

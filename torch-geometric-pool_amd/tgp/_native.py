@@ -139,6 +139,17 @@ SIGNATURES = {
     "tgp_graclus_match_graphs_fused": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
                                                 _c_p, _c_p, _c_p, _c_i64, _c_p, ctypes.c_uint32, _c_p]),
     "tgp_graclus_match_graphs": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_kmis_max_graph_nodes": (_c_int, []),
+    "tgp_kmis_workspace_bytes": (_c_sz, [_c_i64]),
+    "tgp_kmis_graphs": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p,
+                                 _c_p, _c_p]),
+    "tgp_kmis_rounds_start": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_sz, _c_p]),
+    "tgp_kmis_rounds": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_kmis_clusters": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_kmis_greedy_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p, _c_p]),
+    "tgp_kmis_wsum_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_kmis_degree_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_kmis_mis_index_i64": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tgp_graclus_match_rounds": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_p]),
     "tgp_batch_facts_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p]),
     "tgp_batch_facts_sorted_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p, _c_p, _c_p, _c_p,

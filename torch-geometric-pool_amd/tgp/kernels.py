@@ -2161,6 +2161,176 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
     return finish()
 
 
+# ------------------------------------------------------------------------- k-MIS selection (csrc/kmis_select.hip)
+def _dest_groups(edge_index: Tensor, num_nodes: int) -> AssignIndex:
+    """Edge positions grouped by destination, edge-list order inside a group: the summation order of every float sum of
+    the k-MIS selector."""
+    _, col = _edge_rows(edge_index)
+    return build_assign_index(col, num_nodes)
+
+
+def kmis_degree(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: int) -> Tensor:
+    """Weighted in-degree (select/kmis_select.py:21-32): deg[c] = sum of the weights of the edges into c, added in
+    edge-list order (no float atomics: the same bits on every call)."""
+    dev = N.require_device(edge_index, edge_weight)
+    out = torch.zeros(num_nodes, dtype=torch.float32, device=dev)
+    if num_nodes == 0 or edge_index.size(1) == 0:
+        return out
+    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    grp = _dest_groups(edge_index, num_nodes)
+    N.check(N.lib().tgp_kmis_degree_f32(N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(w), num_nodes, N.ptr(out),
+                                        N.stream_ptr(dev)), "tgp_kmis_degree_f32")
+    return out
+
+
+def kmis_updated_score(score: Tensor, edge_index: Tensor, order_k: int, heuristic: Optional[str]) -> Tensor:
+    """score / (A^T + I)^k 1 ("greedy") or score / (A^T + I)^k score ("w-greedy") (select/kmis_select.py:264-282), the
+    device-wide kernels.  "greedy" counts in integers; "w-greedy" adds every destination's terms in edge-list order
+    starting from the node's own value."""
+    dev = N.require_device(score, edge_index)
+    score = N.f32c(score.reshape(-1))
+    n = score.numel()
+    if heuristic is None or n == 0:
+        return score
+    row, col = _edge_rows(edge_index)
+    E, L, st = row.numel(), N.lib(), N.stream_ptr(dev)
+    out = torch.empty_like(score)
+    if heuristic == "greedy":
+        ws = N.workspace(L.tgp_kmis_workspace_bytes(n), dev)
+        N.check(L.tgp_kmis_greedy_f32(N.ptr(row), N.ptr(col), E, n, int(order_k), N.ptr(score), N.ptr(ws), ws.numel(),
+                                      N.ptr(out), st), "tgp_kmis_greedy_f32")
+        return out
+    if heuristic != "w-greedy":
+        raise ValueError(f"Unrecognized `score_heuristic` value: {heuristic}")
+    if order_k <= 0 or E == 0:
+        return score / score
+    grp = _dest_groups(edge_index, n)
+    cur, spare = score, [torch.empty_like(score), torch.empty_like(score)] if order_k > 1 else []
+    for h in range(order_k):
+        last = h == order_k - 1
+        dst = out if last else spare[h % 2]
+        N.check(L.tgp_kmis_wsum_f32(N.ptr(row), N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(cur),
+                                    N.ptr(score) if last else None, n, N.ptr(dst), st), "tgp_kmis_wsum_f32")
+        cur = dst
+    return out
+
+
+class KMISResult:
+    """What one k-MIS selection leaves: ``index`` [2, N] (row 0 = 0..N-1, row 1 = cluster id), ``k`` clusters, ``mis``
+    [k] (the MIS nodes, ascending = the node of every cluster id), ``updated`` (the score the priorities came from, or
+    None for an explicit permutation), ``route`` ("graphs" / "rounds") and ``rounds`` launched on the device-wide route."""
+    __slots__ = ("index", "k", "mis", "updated", "route", "rounds")
+
+
+def kmis_route(num_nodes: int, num_edges: int, graph_ptr: Optional[Tensor], max_graph_nodes: Optional[int]) -> str:
+    """The route a selection takes, from what the host already knows: "graphs" (one workgroup per graph) for a sorted
+    batch whose longest graph fits one workgroup, "rounds" (device-wide launches per hop) for everything else."""
+    if (graph_ptr is not None and max_graph_nodes is not None and graph_ptr.numel() >= 2 and num_nodes > 0
+            and 0 < max_graph_nodes <= N.lib().tgp_kmis_max_graph_nodes()):
+        return "graphs"
+    return "rounds"
+
+
+def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Optional[Tensor] = None,
+                heuristic: Optional[str] = None, perm: Optional[Tensor] = None, graph_ptr: Optional[Tensor] = None,
+                max_graph_nodes: Optional[int] = None, route: Optional[str] = None) -> KMISResult:
+    """Maximal k-independent set + clusters (select/kmis_select.py:35-170) by node priority: ``perm`` (a permutation,
+    first = highest priority), else descending ``heuristic``-updated ``score`` with ties to the lower node index, else
+    the node order.  ``graph_ptr`` / ``max_graph_nodes``: offsets and longest graph of a sorted batch.  ``route``: None
+    picks (``kmis_route``); "rounds" forces the device-wide kernels (tests run both on one input); a "graphs" call the
+    kernel declines (an edge between two graphs, a list not grouped by graph) goes on device-wide.  One host wait per
+    call on the per-graph route (status + cluster count); one per batch of rounds device-wide."""
+    dev = N.require_device(edge_index, score, perm)
+    row, col = _edge_rows(edge_index)
+    E, n, k = row.numel(), int(num_nodes), int(order_k)
+    if k < 1:
+        raise ValueError(f"order_k must be at least 1, got {order_k}")
+    L, st = N.lib(), N.stream_ptr(dev)
+    res = KMISResult()
+    res.updated, res.rounds = None, 0
+    if n == 0:
+        res.index = torch.empty(2, 0, dtype=torch.int64, device=dev)
+        res.k, res.mis, res.route = 0, torch.empty(0, dtype=torch.int64, device=dev), "rounds"
+        return res
+    if n > L.tgp_graclus_relabel_max_nodes():
+        raise N.TgpNativeError(f"kmis_select: {n} nodes exceed the relabelling kernels' "
+                               f"{L.tgp_graclus_relabel_max_nodes()}")
+    rank = None
+    if perm is not None:
+        if perm.numel() != n:
+            raise ValueError(f"perm must have one entry per node ({n}), got {perm.numel()}")
+        rank = torch.empty(n, dtype=torch.int32, device=dev)
+        rank[perm.reshape(-1)] = torch.arange(n, dtype=torch.int32, device=dev)
+    elif score is None:
+        rank = torch.arange(n, dtype=torch.int32, device=dev)
+    else:
+        score = N.f32c(score.reshape(-1))
+        if score.numel() != n:
+            raise ValueError(f"score must have one entry per node ({n}), got {score.numel()}")
+        if heuristic not in (None, "greedy", "w-greedy"):
+            raise ValueError(f"Unrecognized `score_heuristic` value: {heuristic}")
+    want = kmis_route(n, E, graph_ptr, max_graph_nodes)
+    if route is not None:
+        if route not in ("graphs", "rounds"):
+            raise ValueError(f"route must be 'graphs' or 'rounds', got {route!r}")
+        if route == "graphs" and want != "graphs":
+            raise ValueError("the per-graph route needs a sorted batch whose longest graph fits one workgroup")
+        want = route
+    label = torch.empty(n, dtype=torch.int64, device=dev)
+    index = torch.empty(2, n, dtype=torch.int64, device=dev)
+    mis = torch.empty(n, dtype=torch.int64, device=dev)
+    words = torch.empty(4, dtype=torch.int32, device=dev)  # [status, -, K (int64)]
+    rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
+
+    def relabel():
+        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
+                                          None, None, None, st), "tgp_graclus_relabel_i64")
+        N.check(L.tgp_kmis_mis_index_i64(N.ptr(label), N.ptr(index), n, N.ptr(mis), st), "tgp_kmis_mis_index_i64")
+
+    updated = None
+    if want == "graphs":
+        mode = 0 if rank is not None else (2 if heuristic == "greedy" else 1)
+        if rank is None:
+            updated = kmis_updated_score(score, edge_index, k, heuristic) if heuristic == "w-greedy" else score
+            if mode == 2:
+                updated = torch.empty_like(score)
+        gp = N.i64c(graph_ptr)
+        N.check(L.tgp_kmis_graphs(N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1, int(max_graph_nodes), k, mode,
+                                  N.ptr(score if mode == 2 else updated), N.ptr(rank), N.ptr(updated) if mode == 2 else None,
+                                  N.ptr(label), N.ptr(words), st), "tgp_kmis_graphs")
+        relabel()
+        got = words.tolist()  # the one host wait: status and K together
+        if got[0] == 0:
+            res.index, res.k, res.mis, res.updated, res.route = index, int(got[2]), mis[:int(got[2])], updated, "graphs"
+            return res
+        if got[0] & 2:
+            raise N.TgpNativeError("tgp_kmis_graphs: a graph did not finish within its round bound")
+        if route == "graphs":
+            raise N.TgpNativeError("tgp_kmis_graphs declined: the edge list is not grouped by graph or an edge joins "
+                                   "two graphs")
+        if mode == 2:
+            updated = None  # (graphs that declined left theirs unwritten)
+    if rank is None and updated is None:
+        updated = kmis_updated_score(score, edge_index, k, heuristic)
+    ws = N.workspace(L.tgp_kmis_workspace_bytes(n), dev)
+    N.check(L.tgp_kmis_rounds_start(N.ptr(rank), N.ptr(updated), n, N.ptr(ws), ws.numel(), st), "tgp_kmis_rounds_start")
+    done, step, finished = 0, 4, False
+    while not finished:
+        if done >= n + 4:  # a round adds a node while an unmasked one exists: n rounds is a hard cap
+            raise N.TgpNativeError("tgp_kmis_rounds: the set is not maximal after num_nodes rounds")
+        flags = torch.empty(step, dtype=torch.int32, device=dev)
+        N.check(L.tgp_kmis_rounds(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, step, N.ptr(flags), st),
+                "tgp_kmis_rounds")
+        done += step
+        finished = 0 in flags.tolist()  # one host wait per batch of rounds
+        step = min(2 * step, 256)  # a long tail means chain-like structure: more rounds per host wait
+    N.check(L.tgp_kmis_clusters(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, N.ptr(label), st), "tgp_kmis_clusters")
+    relabel()
+    kk = int(words.tolist()[2])
+    res.index, res.k, res.mis, res.updated, res.route, res.rounds = index, kk, mis[:kk], updated, "rounds", done
+    return res
+
+
 def _rows_f32(x: Tensor) -> Tensor:
     x = x.to(torch.float32) if x.dtype != torch.float32 else x
     return x if x.stride(1) == 1 else x.contiguous()

@@ -20,7 +20,7 @@ from .. import kernels as K
 from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
-from ..select import GraclusSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
+from ..select import GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
 from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling
 from ..utils.ops import batch_info, is_dense_adj
 from ..utils.losses import (
@@ -200,6 +200,58 @@ class NDPPooling(BasePrecoarseningMixin, SRCPooling):
         x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch)
         # batch: the Kron reduction is taken per graph (block-batched kernel); the reference's connector ignores it
         ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch)
+        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
+
+    def extra_repr_args(self) -> dict:
+        return {"cached": self.cached}
+
+
+class KMISPooling(BasePrecoarseningMixin, SRCPooling):
+    r"""k-MIS pooling (Bacciu et al., AAAI 2023; reference poolers/kmis.py:15-246): a maximal k-independent set chosen by
+    node score becomes the supernodes, every node joins the member that reaches it within ``order_k`` hops, features are
+    summed per supernode weighted by the scores (``reduce_red_op=None``: the members' own rows times their scores),
+    edges are coalesced.  ``KMISSelect`` + ``BaseReduce`` + ``SparseConnect`` + ``BaseLift``.
+
+    Ties between equal scores go to the lower node index and the selection is a pure function of the inputs (see
+    ``KMISSelect``); ``scorer="canonical"`` yields float32 scores (``so.s`` is float32 where the reference's is int64)
+    and is refused together with ``score_heuristic="w-greedy"``.  Callable scorers and ``"first"`` / ``"last"`` are
+    rejected by the selector's assertion, as in the reference.  ``cached=True`` needs a scorer without parameters."""
+
+    def __init__(self, in_channels: Optional[int] = None, order_k: int = 1, scorer: str = "linear",
+                 score_heuristic: Optional[str] = "greedy", force_undirected: bool = False, lift: str = "precomputed",
+                 s_inv_op: str = "transpose", reduce_red_op: Optional[str] = "sum", connect_red_op: str = "sum",
+                 lift_red_op: str = "sum", remove_self_loops: bool = True, degree_norm: bool = False,
+                 edge_weight_norm: bool = False, cached: bool = False):
+        super().__init__(
+            selector=KMISSelect(in_channels=in_channels, order_k=order_k, scorer=scorer,
+                                score_heuristic=score_heuristic, force_undirected=force_undirected, s_inv_op=s_inv_op),
+            reducer=BaseReduce(),
+            lifter=BaseLift(matrix_op=lift, reduce_op=lift_red_op),
+            connector=SparseConnect(reduce_op=connect_red_op, remove_self_loops=remove_self_loops,
+                                    degree_norm=degree_norm, edge_weight_norm=edge_weight_norm),
+            cached=cached)
+        self.reduce_red_op = reduce_red_op
+        self.cached = cached
+        self.precoarsenable = scorer in ["random", "constant", "canonical", "degree"]
+        if cached and scorer == "linear" or callable(scorer):
+            raise Exception("Caching should be disabled when using a linear scorer or a callable scorer.")
+
+    def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None,
+                so: Optional[SelectOutput] = None, batch: Optional[Tensor] = None, lifting: bool = False,
+                **kwargs):
+        if lifting:
+            return self.lift(x_pool=x, so=so)
+        so = self.select(x=x, edge_index=adj, edge_weight=edge_weight, batch=batch)
+        if self.reduce_red_op is None:
+            x_pool = torch.index_select(x, index=so.mis, dim=-2) * so.weight[so.mis].view(-1, 1)
+            batch_pool = None if batch is None else batch[so.mis]
+        else:
+            fused = self.reduce_connect(x, adj, edge_weight, so, batch)  # batches of small graphs: ONE launch
+            if fused is not None:
+                x_pool, batch_pool, ei, ew = fused
+                return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
+            x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch)
+        ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch_pooled=batch_pool)
         return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
 
     def extra_repr_args(self) -> dict:
@@ -954,8 +1006,8 @@ class DMoNPooling(_DenseMLPPooling):
 
 
 # =============================================================================== factory
-# ("dmon" is not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["DMoNPooling", "DiffPool", "GraclusPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon" and "kmis" are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["DMoNPooling", "DiffPool", "GraclusPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

@@ -777,6 +777,160 @@ class GraclusSelect(Select):
         return f"{self.__class__.__name__}(s_inv_op={self.s_inv_op})"
 
 
+# =============================================================================== k-MIS
+def _kmis_batch_facts(batch, num_nodes: int):
+    """(graph offsets, longest graph) of a sorted device batch vector, else (None, None): what picks the route."""
+    if isinstance(batch, Tensor) and batch.is_cuda and batch.numel() == num_nodes and num_nodes > 0:
+        from ..utils.ops import batch_info
+        info = batch_info(batch)  # (memoised per batch vector)
+        if info.is_sorted:
+            return info.ptr, info.max_nodes
+    return None, None
+
+
+def degree_scorer(edge_index, edge_weight: Optional[Tensor] = None, num_nodes: Optional[int] = None,
+                  dim: int = 1) -> Tensor:
+    """Weighted degree of every node over ``edge_index[dim]`` (in-degree for the default ``dim=1``), float32 [N]
+    (reference select/kmis_select.py:21-32).  Each node's weights are added in edge-list order: no float atomics, the
+    same bits on every call."""
+    from .. import kernels
+    num_nodes = maybe_num_nodes(edge_index, num_nodes)
+    edge_index, edge_weight = connectivity_to_edge_index(edge_index, edge_weight)
+    if dim not in (0, 1):
+        raise ValueError(f"dim must be 0 or 1, got {dim}")
+    if dim == 0:
+        edge_index = edge_index.flip(0)
+    return kernels.kmis_degree(edge_index, edge_weight, num_nodes)
+
+
+def _kmis_explicit(edge_index: Tensor, order_k: int, perm: Optional[Tensor], num_nodes: Optional[int], batch=None):
+    from .. import kernels
+    n = num_nodes if num_nodes is not None else maybe_num_nodes(edge_index)
+    gptr, gmax = _kmis_batch_facts(batch, n)
+    return n, kernels.kmis_select(edge_index, n, order_k, perm=perm, graph_ptr=gptr, max_graph_nodes=gmax)
+
+
+def maximal_independent_set(edge_index: Tensor, order_k: int = 1, perm: Optional[Tensor] = None,
+                            num_nodes: Optional[int] = None) -> Tensor:
+    """bool [N]: a maximal k-independent set (no two members within ``order_k`` hops, every node within ``order_k``
+    hops of a member), chosen greedily in the order of ``perm`` (node order when None); messages travel row -> col
+    (reference select/kmis_select.py:35-118)."""
+    n, res = _kmis_explicit(edge_index, order_k, perm, num_nodes)
+    mis = torch.zeros(n, dtype=torch.bool, device=edge_index.device)
+    mis[res.mis] = True
+    return mis
+
+
+def maximal_independent_set_cluster(edge_index: Tensor, order_k: int = 1, perm: Optional[Tensor] = None,
+                                    num_nodes: Optional[int] = None):
+    """``(mis bool [N], cluster int64 [N])``: the set of ``maximal_independent_set`` and, for every node, the index
+    (among the members in ascending node order) of the member whose priority reached it within ``order_k`` hops
+    (reference select/kmis_select.py:121-170)."""
+    n, res = _kmis_explicit(edge_index, order_k, perm, num_nodes)
+    mis = torch.zeros(n, dtype=torch.bool, device=edge_index.device)
+    mis[res.mis] = True
+    return mis, res.index[1]
+
+
+class KMISSelect(Select):
+    r"""Maximal k-independent-set selection (Bacciu et al., "Generalizing Downsampling from Regular Data to Graphs",
+    AAAI 2023; reference select/kmis_select.py:173-388): score the nodes, pick a maximal set of nodes that are pairwise
+    more than ``order_k`` hops apart greedily by descending score, assign every node to the member that reaches it.
+
+    ``scorer``: ``"linear"`` (sigmoid of a learnt projection of ``x``; needs ``in_channels``), ``"random"``,
+    ``"constant"``, ``"canonical"`` (node ``i`` scores ``-i``) or ``"degree"`` (weighted in-degree).
+    ``score_heuristic``: None, ``"greedy"`` (score / (A^T + I)^k 1) or ``"w-greedy"`` (score / (A^T + I)^k score).
+    ``force_undirected`` symmetrises the edges first (duplicates keep the larger weight).
+
+    What this port fixes where the reference leaves it open:
+
+    * **Ties go to the lower node index** (a stable descending sort).  The reference's ``argsort`` is stable only up to
+      16 elements on the host and arbitrary on a device; wherever its order is tie-free the results are the same, indices
+      bit for bit.
+    * The result is a pure function of the inputs: the float sums of ``"w-greedy"`` and of the ``"degree"`` scorer add
+      each node's terms in edge-list order starting from its own value (no float atomics), ``"greedy"`` counts in
+      integers, the division is correctly rounded.
+    * ``scorer="canonical"`` hands its scores out as float32 (the reference's are int64, so only ``so.s.dtype``
+      differs); it is refused above 2^24 nodes, where ``-i`` is no longer exact, and with ``"w-greedy"`` (which would
+      divide by sums that are zero or negative): ``ValueError``.
+    * Device tensors only: host inputs raise ``TgpNativeError`` (no CPU fallback).
+    """
+
+    _heuristics = {None, "greedy", "w-greedy"}
+    _scorers = {"linear", "degree", "random", "constant", "canonical"}
+
+    def __init__(self, in_channels: Optional[int] = None, order_k: int = 1, scorer: str = "linear",
+                 score_heuristic: Optional[str] = "greedy", force_undirected: bool = False,
+                 s_inv_op: str = "transpose"):
+        super().__init__()
+        assert score_heuristic in self._heuristics, f"Unrecognized `score_heuristic` value: {score_heuristic}"
+        assert scorer in self._scorers, f"Unrecognized `scorer` value: {scorer}"
+        if scorer == "canonical" and score_heuristic == "w-greedy":
+            raise ValueError("scorer='canonical' cannot be combined with score_heuristic='w-greedy': the sums it "
+                             "divides by are zero or negative")
+        self.order_k = order_k
+        self.scorer = scorer
+        self.score_heuristic = score_heuristic
+        self.force_undirected = force_undirected
+        self.s_inv_op = s_inv_op
+        if scorer == "linear":
+            if isinstance(in_channels, list):
+                in_channels = in_channels[0]
+            self.lin = torch.nn.Linear(in_channels, 1)
+
+    def reset_parameters(self):
+        if self.scorer == "linear":
+            self.lin.reset_parameters()
+
+    def _score(self, edge_index: Tensor, edge_weight: Optional[Tensor], x: Optional[Tensor], num_nodes: int) -> Tensor:
+        dev = edge_index.device
+        if self.scorer == "linear":
+            assert x is not None, "x must be provided when scorer is 'linear'"
+            return self.lin(x).sigmoid().view(-1)  # one small GEMV that must stay differentiable: torch
+        if self.scorer == "random":
+            return torch.rand(num_nodes, device=dev)
+        if self.scorer == "constant":
+            return torch.ones(num_nodes, device=dev)
+        if self.scorer == "canonical":
+            if num_nodes > (1 << 24):
+                raise ValueError("scorer='canonical' is exact in float32 only up to 2^24 nodes")
+            return -torch.arange(num_nodes, device=dev, dtype=torch.float32)
+        return degree_scorer(edge_index, edge_weight, num_nodes)
+
+    def forward(self, *, edge_index=None, edge_weight: Optional[Tensor] = None, x: Optional[Tensor] = None,
+                batch: Optional[Tensor] = None, num_nodes: Optional[int] = None, **kwargs) -> SelectOutput:
+        from .. import kernels, _native as N
+        size_x = x.size(0) if x is not None else None
+        num_nodes = num_nodes if num_nodes is not None else maybe_num_nodes(edge_index, size_x)
+        edge_index, edge_weight = connectivity_to_edge_index(edge_index, edge_weight)
+        N.require_device(edge_index, x)  # host tensors: no CPU fallback
+        if self.force_undirected:
+            both = torch.cat([edge_index, edge_index.flip(0)], dim=1)
+            w2 = None if edge_weight is None else torch.cat([edge_weight.reshape(-1), edge_weight.reshape(-1)])
+            edge_index, edge_weight = Fn.coalesce_edges(both, w2, torch.arange(num_nodes, device=both.device),
+                                                        num_nodes, reduce_op="max", remove_self_loops=False)
+        score = self._score(edge_index, edge_weight, x, num_nodes)
+        gptr, gmax = _kmis_batch_facts(batch, num_nodes)
+        with torch.no_grad():
+            res = kernels.kmis_select(edge_index, num_nodes, self.order_k, score=score.detach(),
+                                      heuristic=self.score_heuristic, graph_ptr=gptr, max_graph_nodes=gmax)
+        values = score if score.dtype == torch.float32 else score.to(torch.float32)
+        s = torch.sparse_coo_tensor(res.index, values, size=(num_nodes, res.k), is_coalesced=True)
+        so = SelectOutput(s=s, s_inv_op=self.s_inv_op, mis=res.mis)
+        so._hold_values(values)
+        so.__dict__["_identity_nodes"] = True  # row 0 of the indices is 0..N-1
+        so.__dict__["_no_empty_cluster"] = True  # every id is the rank of an MIS node, which belongs to its own cluster
+        so.__dict__["_kmis_route"] = res.route
+        so.__dict__["_kmis_rounds"] = res.rounds
+        so.__dict__["_kmis_updated"] = res.updated
+        return so
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__}(order_k={self.order_k}, scorer={self.scorer}, "
+                f"score_heuristic={self.score_heuristic}, force_undirected={self.force_undirected}, "
+                f"s_inv_op={self.s_inv_op})")
+
+
 # =============================================================================== NDP
 import os as _os
 
@@ -1071,4 +1225,5 @@ class NDPSelect(Select):
 
 
 __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
-           "topk", "graclus_cluster"]
+           "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
+           "degree_scorer"]
