@@ -7,6 +7,7 @@ on the CPU and nothing falls back to ATen kernels.
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 from typing import Optional, Sequence, Tuple
 from weakref import ref as _weakref
 
@@ -253,13 +254,14 @@ class _SpsState:
     workgroup stores {epoch, refused, total} into -- the host polls it instead of paying a device-to-host copy kernel
     and a stream synchronise for eight bytes (``tgp_count_publish`` gives every count -> fill pair the same read)."""
 
-    __slots__ = ("status", "epoch", "pinned", "host", "ticket", "facts_pinned", "facts_host", "facts_tag")
+    __slots__ = ("status", "epoch", "pinned", "host", "words", "ticket", "facts_pinned", "facts_host", "facts_tag")
 
     def __init__(self, dev, words):
         self.status = torch.zeros(max(int(words), 4096), dtype=torch.int64, device=dev)
         self.epoch = 0
         self.pinned = torch.zeros(8, dtype=torch.int64).pin_memory()
         self.host = self.pinned.numpy()  # the same memory
+        self.words = (self.status.data_ptr(), self.status.numel(), self.pinned.data_ptr())  # what every call is handed
         # the one-launch batch facts (utils.ops._batch_facts_sorted): arrival ticket + flag word (zero between calls) and
         # the pinned words {tag, B - 1, flags, longest graph, non-empty graphs, sum of TopK keep counts}
         self.ticket = torch.zeros(8, dtype=torch.int32, device=dev)  # words 0-1 batch facts, 2-3 edge facts / symmetry,
@@ -277,30 +279,33 @@ class _SpsState:
         words are not overwritten by the calls enqueued behind it)."""
         return self.facts_pinned.data_ptr() + 64 * (tag & 7)
 
-    def wait_facts(self, tag: int):
-        host, spins, o = self.facts_host, 0, 8 * (tag & 7)
-        while int(host[o]) != tag:
+    def _spin(self, host, at: int, arrived, error: str) -> int:
+        """The pinned word ``host[at]`` once ``arrived(word)`` holds.  Spins on it; after 4 000 000 looks the device is
+        synchronised (which surfaces a device fault, if that is what happened), the word is read once more and, still not
+        there, ``error`` is raised: a stuck device becomes an error instead of a hang."""
+        spins = 0
+        while True:
+            word = int(host[at])
+            if arrived(word):
+                return word
             spins += 1
             if spins > 4_000_000:
                 torch.cuda.synchronize(self.status.device)
-                if int(host[o]) != tag:
-                    raise N.TgpNativeError("tgp_batch_facts_sorted_i64 finished without storing its result word")
+                word = int(host[at])
+                if arrived(word):
+                    return word
+                raise N.TgpNativeError(error)
+
+    def wait_facts(self, tag: int):
+        host, o = self.facts_host, 8 * (tag & 7)
+        self._spin(host, o, lambda have: have == tag, "tgp_batch_facts_sorted_i64 finished without storing its result word")
         return int(host[o + 1]), int(host[o + 2]), int(host[o + 3]), int(host[o + 4]), int(host[o + 5])
 
     def peek_facts(self, tag: int):
         """The flag word of call ``tag``, or None when its slot has been reused by a later call (eight slots rotate)."""
-        host, spins, o = self.facts_host, 0, 8 * (tag & 7)
-        while True:
-            have = int(host[o])
-            if have == tag:
-                return int(host[o + 2])
-            if have > tag:
-                return None
-            spins += 1
-            if spins > 4_000_000:
-                torch.cuda.synchronize(self.status.device)
-                if int(host[o]) < tag:
-                    raise N.TgpNativeError("a facts launch finished without storing its result word")
+        host, o = self.facts_host, 8 * (tag & 7)
+        have = self._spin(host, o, lambda have: have >= tag, "a facts launch finished without storing its result word")
+        return int(host[o + 2]) if have == tag else None
 
     def next_epoch(self) -> int:
         self.epoch += 1
@@ -313,18 +318,40 @@ class _SpsState:
 
     def wait(self, epoch: int) -> int:
         """The result word of call ``epoch`` (spins on the pinned word; a stuck device is turned into an error)."""
-        host, spins = self.host, 0
-        while True:
-            word = int(host[0])
-            if (word >> 34) == epoch:
-                return word
-            spins += 1
-            if spins > 4_000_000:
-                torch.cuda.synchronize(self.status.device)  # surfaces a device fault, if that is what happened
-                word = int(host[0])
-                if (word >> 34) == epoch:
-                    return word
-                raise N.TgpNativeError("a kernel that hands its count over in a pinned host word finished without storing it")
+        return self._spin(self.host, 0, lambda word: (word >> 34) == epoch,
+                          "a kernel that hands its count over in a pinned host word finished without storing it")
+
+    def open_call(self) -> "_PublishedCall":
+        """Advance the epoch: the handle of the one call that may now store the pinned result word."""
+        return _PublishedCall(self)
+
+
+class _PublishedCall:
+    """One call's claim on the pinned result word of an :class:`_SpsState`: what the kernel is handed -- ``lookback``
+    (status words, their count, pinned word, epoch) for the look-back kernels, ``publish`` (pinned word, epoch) for
+    ``tgp_count_publish`` / ``tgp_mask_index_count`` -- and the wait for, and the decoding of, the word it stores."""
+
+    __slots__ = ("state", "epoch", "publish", "lookback")
+
+    def __init__(self, state: _SpsState):
+        self.state, self.epoch = state, state.next_epoch()
+        self.lookback = state.words + (self.epoch,)
+        self.publish = self.lookback[2:]
+
+    def total(self) -> Optional[int]:
+        """The one-launch kernels' word {refused: bit 31, total: bits 0..30}: the total, or None when the kernel refused
+        its input."""
+        word = self.state.wait(self.epoch)
+        return None if word & 0x80000000 else word & 0x7FFFFFFF
+
+    def count(self) -> int:
+        """The signed 34-bit count of a count kernel's word (decline codes are negative)."""
+        return _decode_count(self.state.wait(self.epoch))
+
+    def refused_for_ids(self) -> bool:
+        """After a refusal: did a chunk of this call meet an id outside its table?  It says so in word [1] of the status
+        buffer, tagged with the call's epoch (one device read, on the error path only)."""
+        return (int(self.state.status[1]) & 0xFFFFFFFF) == self.epoch
 
 
 def _sps_state(dev: torch.device, stream: int, words: int) -> "_SpsState":
@@ -465,6 +492,8 @@ def sparse_pool_small(x: Tensor, graph_ptr: Tensor, edge_index: Tensor, edge_wei
         if len(_SPS_WORDS) > 256:
             _SPS_WORDS.clear()
         words = _SPS_WORDS[(B, mode)] = int(L.tgp_sparse_pool_small_status_words(B, mode))
+    # (the handshake is written out here and not taken from `open_call`: no handle object and no tuples in front of a
+    #  ~10 us kernel, as long as nobody has measured that they cost nothing)
     state = _sps_state(dev, st, words)
     epoch = state.next_epoch()
     flags = (N.REMOVE_SELF_LOOPS if remove_self_loops else 0) | (N.EPS_FILTER if w is not None else 0)
@@ -542,16 +571,48 @@ def _read_count(d_count: Tensor) -> int:
     if _PUBLISH_COUNTS and not torch.cuda.is_current_stream_capturing():
         dev = d_count.device
         st = N.stream_ptr(dev)
-        state = _sps_state(dev, st, 0)
-        epoch = state.next_epoch()
-        N.check(N.lib().tgp_count_publish(N.ptr(d_count), state.pinned.data_ptr(), epoch, st), "tgp_count_publish")
-        n = _decode_count(state.wait(epoch))
+        call = _sps_state(dev, st, 0).open_call()
+        N.check(N.lib().tgp_count_publish(N.ptr(d_count), *call.publish, st), "tgp_count_publish")
+        n = call.count()
     else:
         n = int(d_count.item())
     if n == -2:  # refusal code of the count kernels: an endpoint (or cluster id) outside its table
         raise IndexError("edge_index holds node ids outside [0, num_nodes) (or cluster ids outside [0, num_supernodes)): "
                          "the reference's index ops raise for these inputs too")
     return n
+
+
+def _checked(fn, *args) -> None:
+    """Call a C-ABI entry point; a non-zero status is reported under the symbol that was called."""
+    N.check(fn(*args), fn.__name__)
+
+
+def _count_fill(dev, nbytes: int, count, fill, w_dtype=None, edge_id: bool = False,
+                call: Optional[_PublishedCall] = None, rows: int = 2, declines: bool = False):
+    """A count -> fill pair: size the workspace, launch ``count(workspace, its bytes, count word)``, read the count on
+    the host (the call's single wait: ``call``'s published word when the count kernel stores one, else `_read_count`),
+    allocate the exact-size outputs -- index ``[rows, n]``, weight ``[n]`` of ``w_dtype`` or None, with ``edge_id`` an
+    int64 ``[n]`` -- and launch ``fill(workspace, n, row' .. , weight', [edge_id'])`` on their pointers.
+    Returns the outputs, or -- for a pair that ``declines`` -- the count itself when it is negative: what a decline code
+    means is the caller's business.
+    (Known difference, kept: only `_read_count` raises for the code -2; a published count hands it back like any other
+    decline, and the sort-based route that then runs raises for the same input.)"""
+    ws = N.workspace(nbytes, dev)
+    d_count = torch.empty(1, dtype=torch.int64, device=dev)
+    count(N.ptr(ws), ws.numel(), N.ptr(d_count))
+    n = _read_count(d_count) if call is None else call.count()
+    if n < 0 and declines:
+        return n
+    index = torch.empty(rows, n, dtype=torch.int64, device=dev)
+    out = (index, None if w_dtype is None else torch.empty(n, dtype=w_dtype, device=dev))
+    if edge_id:
+        out += (torch.empty(n, dtype=torch.int64, device=dev),)
+    if n:
+        ptrs = [index.data_ptr() + 8 * n * r for r in range(rows)] + [N.ptr(t) for t in out[1:]]
+    else:  # an empty tensor has no device pointer to hand over
+        ptrs = [None] * (rows + len(out) - 1)
+    fill(N.ptr(ws), n, *ptrs)
+    return out
 
 
 def member_directory_for(assign: Optional["AssignIndex"], node_index: Optional[Tensor]) -> Optional[Tensor]:
@@ -622,21 +683,13 @@ def filter_edges(edge_index: Tensor, edge_weight: Optional[Tensor], node_index: 
         keep = w2.abs() > eps
         ei2, w2, eid = ei2[:, keep].contiguous(), w2[keep], eid[keep]
         return (ei2, w2, eid) if want_edge_id else (ei2, w2)
-    ws = N.workspace(L.tgp_connect_subgraph_workspace_bytes(E, num_nodes), dev)
-    d_count = torch.empty(1, dtype=torch.int64, device=dev)
-    N.check(L.tgp_connect_subgraph_count(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(ni),
-                                         0 if ni is None else ni.numel(), num_nodes, flags, eps, N.ptr(ws),
-                                         ws.numel(), N.ptr(d_count), st), "tgp_connect_subgraph_count")
-    n_out = _read_count(d_count)
-    out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-    out_w = None if w is None else torch.empty(n_out, dtype=torch.float32, device=dev)
-    out_id = torch.empty(n_out, dtype=torch.int64, device=dev) if want_edge_id else None
-    N.check(L.tgp_connect_subgraph_fill(N.ptr(row), N.ptr(col), N.ptr(w), E, num_nodes, flags, eps, N.ptr(ws), n_out,
-                                        N.ptr(out_ei[0]) if n_out else None,
-                                        N.ptr(out_ei[1]) if n_out else None, N.ptr(out_w),
-                                        N.ptr(out_id) if n_out else None, st),
-            "tgp_connect_subgraph_fill")
-    return (out_ei, out_w, out_id) if want_edge_id else (out_ei, out_w)
+    return _count_fill(
+        dev, L.tgp_connect_subgraph_workspace_bytes(E, num_nodes),
+        lambda ws, ws_bytes, cnt: _checked(L.tgp_connect_subgraph_count, N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(ni),
+                                           0 if ni is None else ni.numel(), num_nodes, flags, eps, ws, ws_bytes, cnt, st),
+        lambda ws, n_out, r, c, ow, oid=None: _checked(L.tgp_connect_subgraph_fill, N.ptr(row), N.ptr(col), N.ptr(w), E,
+                                                       num_nodes, flags, eps, ws, n_out, r, c, ow, oid, st),
+        None if w is None else torch.float32, edge_id=want_edge_id)
 
 
 def _filter_edges_single(L, dev, st, row, col, w, E, ni, num_nodes, flags, eps, want_edge_id, views=False, md=None):
@@ -646,29 +699,23 @@ def _filter_edges_single(L, dev, st, row, col, w, E, ni, num_nodes, flags, eps, 
     cap = torch.empty(2, E, dtype=torch.int64, device=dev)
     cap_w = None if w is None else torch.empty(E, dtype=w.dtype, device=dev)
     cap_id = torch.empty(E, dtype=torch.int64, device=dev) if want_edge_id else None
-    state = _sps_state(dev, st, L.tgp_connect_subgraph_single_status_words(E))
-    epoch = state.next_epoch()
+    call = _sps_state(dev, st, L.tgp_connect_subgraph_single_status_words(E)).open_call()
     cap_p = cap.data_ptr()
     entry = (L.tgp_connect_subgraph_single_f64 if (w is not None and w.dtype == torch.float64)
              else L.tgp_connect_subgraph_single)
     nblk = 0 if md is None else md.numel() // 5
-    N.check(entry(row.data_ptr(), col.data_ptr(), N.ptr(w), E, N.ptr(ni),
-                                          0 if ni is None else ni.numel(), num_nodes, flags, eps, ws.data_ptr(),
-                                          ws.numel(), cap_p, cap_p + 8 * E, N.ptr(cap_w), N.ptr(cap_id),
-                                          None if md is None else md.data_ptr(),
-                                          None if md is None else md.data_ptr() + 16 * nblk,
-                                          state.status.data_ptr(), state.status.numel(), state.pinned.data_ptr(), epoch,
-                                          st), "tgp_connect_subgraph_single")
-    total = state.wait(epoch)
-    if total & 0x80000000:
-        # refused: node ids outside [0, num_nodes) -- the reference's index ops raise for these inputs too; a chunk that
-        # met one says so in word [1] of the status buffer, tagged with this call's epoch -- or a look-back spin bound
-        word = int(state.status[1])
-        if (word & 0xFFFFFFFF) == epoch:
+    _checked(entry, row.data_ptr(), col.data_ptr(), N.ptr(w), E, N.ptr(ni), 0 if ni is None else ni.numel(), num_nodes,
+             flags, eps, ws.data_ptr(), ws.numel(), cap_p, cap_p + 8 * E, N.ptr(cap_w), N.ptr(cap_id),
+             None if md is None else md.data_ptr(), None if md is None else md.data_ptr() + 16 * nblk,
+             *call.lookback, st)
+    n_out = call.total()
+    if n_out is None:
+        # refused: node ids outside [0, num_nodes) -- the reference's index ops raise for these inputs too -- or a
+        # look-back spin bound
+        if call.refused_for_ids():
             raise IndexError("edge_index holds node ids outside [0, num_nodes) (or cluster ids outside "
                              "[0, num_supernodes)): the reference's index ops raise for these inputs too")
         return None
-    n_out = total & 0x7FFFFFFF
     if not views:  # exact-size outputs (the default): one launch moves the survivors out of the capacity buffers
         out_ei, out_w, out_id = _compact_edges(L, st, dev, cap_p, cap_p + 8 * E, N.ptr(cap_w),
                                                None if cap_w is None else cap_w.dtype, N.ptr(cap_id), n_out)
@@ -689,6 +736,87 @@ FUSED_MAX_SUPERNODES = 32 * 1024  # 1024 tiles of 32 supernode rows
 FUSED_MAX_AVG_ROW = 16
 
 
+def _coalesce_fused(q):
+    """Row-local route as ONE kernel (``tgp_connect_coalesce_fused_*``; float32 only): survivors written at their final
+    offsets through a decoupled look-back, the weights into a capacity-E buffer.  Declines with -3 (more tiles than one
+    launch wave holds) or -1 (unsorted rows, or a supernode row too long for it)."""
+    L, (E, _, _) = q.L, q.sizes
+    cap_w = None if q.w is None else torch.empty(max(E, 1), dtype=torch.float32, device=q.dev)
+    got = _count_fill(
+        q.dev, L.tgp_connect_coalesce_fused_workspace_bytes(*q.sizes),
+        lambda ws, ws_bytes, cnt: _checked(L.tgp_connect_coalesce_fused_count, *q.rc, q.cptr, q.ccol, *q.rest,
+                                           N.ptr(q.index.row_ptr), N.ptr(q.index.perm), q.op, q.flags, q.eps,
+                                           N.ptr(cap_w), ws, ws_bytes, cnt, q.st),
+        lambda ws, n, r, c, _: _checked(L.tgp_connect_coalesce_fused_fill, ws, *q.sizes, n, r, c, q.st),
+        declines=True)
+    if q.w is None or isinstance(got, int):
+        return got
+    n_out = got[0].size(1)  # the kernel wrote the weights at their final offsets of the capacity-E buffer
+    return got[0], cap_w[:n_out] if 2 * n_out >= E else cap_w[:n_out].clone()
+
+
+def _coalesce_rows(q):
+    """Row-local route as the staged pipeline (``tgp_connect_coalesce_rows_*``: any member count per supernode).
+    Declines with -1 (unsorted rows) or -5 (a hub row: a supernode row beyond 1024 raw entries).  float32 answers -5 by
+    one more attempt with the huge-row kernels and remembers the list in ``_HUB_LISTS``, so that later calls ask for them
+    at once; the float64 library has no huge-row form and reads no such memo."""
+    L, f64 = q.L, q.f64
+    hub = not f64 and _HUB_LISTS.get(q.edge_index) is not None
+    # float32: the published count is an A/B switch and is not capturable; float64 has the published entry only (its
+    # preconditions exclude capture)
+    published = f64 or (_PUBLISH_COUNTS and not torch.cuda.is_current_stream_capturing())
+    while True:
+        fl = q.flags | (N.HUGE_ROWS if hub else 0)
+        nbytes = (L.tgp_connect_coalesce_rows_huge_workspace_bytes if hub else
+                  q.entry("tgp_connect_coalesce_rows_workspace_bytes"))(*q.sizes)
+        members = (N.ptr(q.index.row_ptr), N.ptr(q.index.perm), q.cptr, q.op, fl, q.eps)
+        call = None
+        if published:
+            # the survivor scan is one look-back launch whose last workgroup stores the count into a pinned host word: no
+            # scan pair, no copy kernel, no stream synchronise; int32 columns when Select's CSR holds them (float32)
+            call = _sps_state(q.dev, q.st, L.tgp_connect_coalesce_rows_count_status_words(q.sizes[2], q.sizes[1])).open_call()
+            count = lambda ws, ws_bytes, cnt: _checked(  # noqa: E731
+                q.entry("tgp_connect_coalesce_rows_count_published"), *q.rc, q.ccol, *q.rest, *members, ws, ws_bytes,
+                cnt, *call.lookback, q.st)
+        else:
+            count = lambda ws, ws_bytes, cnt: _checked(  # noqa: E731
+                L.tgp_connect_coalesce_rows_count, *q.rc, *q.rest, *members, ws, ws_bytes, cnt, q.st)
+        # fill mode (float32 only): bit 0 = weights, bit 1 = huge rows
+        mode = () if f64 else ((0 if q.w is None else 1) | (2 if hub else 0),)
+        got = _count_fill(q.dev, nbytes, count,
+                          lambda ws, n, r, c, w: _checked(q.entry("tgp_connect_coalesce_rows_fill"), ws, *q.sizes, *mode,
+                                                          n, r, c, w, q.st),
+                          q.w_dtype, call=call, declines=True)
+        if got != -5 or hub or f64:  # (outputs, another decline, or no huge-row form to try)
+            return got
+        hub = True
+        _HUB_LISTS.put(q.edge_index, True)
+
+
+def _coalesce_grouped(q):
+    """Sort by supernode row only (half the radix passes of the general route: for more than 32 bits of (row, col) key)
+    and order the short rows in LDS; float32 only.  Declines (-1) when a supernode row is too long for that."""
+    L = q.L
+    return _count_fill(
+        q.dev, L.tgp_connect_coalesce_grouped_workspace_bytes(*q.sizes),
+        lambda ws, ws_bytes, cnt: _checked(L.tgp_connect_coalesce_grouped_count, *q.rc, *q.rest, q.op, q.flags, q.eps, ws,
+                                           ws_bytes, cnt, q.st),
+        lambda ws, n, r, c, w: _checked(L.tgp_connect_coalesce_rows_fill, ws, *q.sizes, 0 if q.w is None else 1, n, r, c,
+                                        w, q.st),
+        q.w_dtype, declines=True)
+
+
+def _coalesce_general(q):
+    """Device-wide sort by the whole (row, col) key: takes every list and never declines."""
+    return _count_fill(
+        q.dev, q.entry("tgp_connect_coalesce_workspace_bytes")(*q.sizes),
+        lambda ws, ws_bytes, cnt: _checked(q.entry("tgp_connect_coalesce_count"), *q.rc, *q.rest, q.op, q.flags, q.eps,
+                                           ws, ws_bytes, cnt, q.st),
+        lambda ws, n, r, c, w: _checked(q.entry("tgp_connect_coalesce_fill"), ws, *q.sizes, 0 if q.w is None else 1,
+                                        q.flags, n, r, c, w, q.st),
+        q.w_dtype)
+
+
 def coalesce_edges(edge_index: Tensor, edge_weight: Optional[Tensor], cluster_index: Tensor,
                    num_supernodes: int, reduce_op: str, remove_self_loops: bool,
                    eps_filter: bool = True, assign_index: Optional[AssignIndex] = None,
@@ -701,6 +829,8 @@ def coalesce_edges(edge_index: Tensor, edge_weight: Optional[Tensor], cluster_in
     path is tried first; it declines (count = -1) for unsorted rows or very long supernode rows.
     The row-local path is first tried as ONE fused kernel (``tgp_connect_coalesce_fused_*``: survivors written at
     their final offsets through a decoupled look-back), then as the staged pipeline (any member count per supernode).
+    float64 weights are merged in float64 (the reference's coalesce / scatter do), by the staged row-local pipeline or
+    the general route.
     ``csr`` = (row_ptr int32 [N+1], col int32 [E] or None) of exactly this row-sorted edge list (GraclusSelect builds
     the offsets): the pass over the row array is skipped; the fused kernel can also stream the 4-byte columns.
     ``route`` ("fused" / "staged" / "rows" / "grouped" / "general"; tests): take exactly that route, raise if it
@@ -710,215 +840,80 @@ def coalesce_edges(edge_index: Tensor, edge_weight: Optional[Tensor], cluster_in
     if reduce_op not in N.REDUCE_OPS:
         raise ValueError(f"unknown reduce_op '{reduce_op}', expected one of {sorted(N.REDUCE_OPS)}")
     dev = N.require_device(edge_index, edge_weight, cluster_index)
+    f64 = edge_weight is not None and edge_weight.dtype == torch.float64
+    if f64 and route not in (None, "general", "staged", "rows"):
+        raise RuntimeError("float64 edge weights take the staged row-local or the general coalesce route")
     row, col = _edge_rows(edge_index)
     E = row.numel()
-    if edge_weight is not None and edge_weight.dtype == torch.float64:
-        # fp64 weights are merged in fp64 (the reference's coalesce / scatter do).  r5: row-sorted input with the
-        # assignment's member index at hand takes the row-local pipeline in double (no device-wide sort); anything else
-        # (unsorted rows, a hub row, stream capture) the sort-based route, in double too
-        if route not in (None, "general", "staged", "rows"):
-            raise RuntimeError("float64 edge weights take the staged row-local or the general coalesce route")
-        w = N.f64c(edge_weight.reshape(-1))
-        cl = N.i64c(cluster_index)
-        flags = (N.REMOVE_SELF_LOOPS if remove_self_loops else 0) | (N.EPS_FILTER if eps_filter else 0)
-        L = N.lib()
-        rowish = route in ("staged", "rows")
-        if rowish and assign_index is None:
-            assign_index = build_assign_index(cl, num_supernodes)
-        if csr is not None and (csr[0].dtype != torch.int32 or csr[0].numel() != cl.numel() + 1
-                                or not csr[0].is_contiguous()):
-            raise ValueError("csr must be (int32 [N+1], int32 [E] or None) contiguous tensors of this edge list")
-        rows_ok = (route != "general" and assign_index is not None and assign_index.nnz == cl.numel()
-                   and assign_index.num_targets == num_supernodes and num_supernodes < (1 << 26) and E > 0
-                   and not torch.cuda.is_current_stream_capturing()
-                   and (rowish or csr is not None or _rows_sorted_memo(edge_index) is not False))
-        if rows_ok:
-            st = N.stream_ptr(dev)
-            ws = N.workspace(L.tgp_connect_coalesce_rows_workspace_bytes_f64(E, cl.numel(), num_supernodes), dev)
-            d_count = torch.empty(1, dtype=torch.int64, device=dev)
-            state = _sps_state(dev, st, L.tgp_connect_coalesce_rows_count_status_words(num_supernodes, cl.numel()))
-            epoch = state.next_epoch()
-            N.check(L.tgp_connect_coalesce_rows_count_published_f64(
-                N.ptr(row), N.ptr(col), None, N.ptr(w), E, N.ptr(cl), cl.numel(), num_supernodes,
-                N.ptr(assign_index.row_ptr), N.ptr(assign_index.perm), N.ptr(csr[0]) if csr is not None else None,
-                N.REDUCE_OPS[reduce_op], flags, ops_eps(), N.ptr(ws), ws.numel(), N.ptr(d_count),
-                state.status.data_ptr(), state.status.numel(), state.pinned.data_ptr(), epoch, st),
-                "tgp_connect_coalesce_rows_count_published_f64")
-            n_out = _decode_count(state.wait(epoch))
-            if n_out >= 0:
-                out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-                out_w = torch.empty(n_out, dtype=torch.float64, device=dev)
-                N.check(L.tgp_connect_coalesce_rows_fill_f64(N.ptr(ws), E, cl.numel(), num_supernodes, n_out,
-                                                             N.ptr(out_ei[0]) if n_out else None,
-                                                             N.ptr(out_ei[1]) if n_out else None,
-                                                             N.ptr(out_w) if n_out else None, st),
-                        "tgp_connect_coalesce_rows_fill_f64")
-                return out_ei, out_w
-            del ws
-            if rowish:
-                raise RuntimeError("row-local coalesce route declined (unsorted rows or a supernode row too long)")
-            if n_out == -1 and csr is None and _rows_sorted_memo(edge_index) is None:
-                _rows_sorted(edge_index, row)  # remember an unsorted list: later calls skip the attempt
-        elif rowish:
-            raise RuntimeError("row-local coalesce route not applicable")
-        ws = N.workspace(L.tgp_connect_coalesce_workspace_bytes_f64(E, cl.numel(), num_supernodes), dev)
-        d_count = torch.empty(1, dtype=torch.int64, device=dev)
-        st = N.stream_ptr(dev)
-        N.check(L.tgp_connect_coalesce_count_f64(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(cl), cl.numel(),
-                                                 num_supernodes, N.REDUCE_OPS[reduce_op], flags, ops_eps(), N.ptr(ws),
-                                                 ws.numel(), N.ptr(d_count), st), "tgp_connect_coalesce_count_f64")
-        n_out = _read_count(d_count)
-        out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-        out_w = torch.empty(n_out, dtype=torch.float64, device=dev)
-        N.check(L.tgp_connect_coalesce_fill_f64(N.ptr(ws), E, cl.numel(), num_supernodes, 1, flags, n_out,
-                                                N.ptr(out_ei[0]) if n_out else None,
-                                                N.ptr(out_ei[1]) if n_out else None, N.ptr(out_w) if n_out else None, st),
-                "tgp_connect_coalesce_fill_f64")
-        return out_ei, out_w
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = None if edge_weight is None else (N.f64c if f64 else N.f32c)(edge_weight.reshape(-1))
     cl = N.i64c(cluster_index)
-    flags = (N.REMOVE_SELF_LOOPS if remove_self_loops else 0) | (N.EPS_FILTER if (w is not None and eps_filter) else 0)
-    L = N.lib()
-    eps = ops_eps()
     if csr is not None:
         cptr, ccol = csr
         if (cptr.dtype != torch.int32 or cptr.numel() != cl.numel() + 1 or not cptr.is_contiguous()
-                or (ccol is not None and (ccol.dtype != torch.int32 or ccol.numel() != E or not ccol.is_contiguous()))):
+                or (ccol is not None and not f64 and (ccol.dtype != torch.int32 or ccol.numel() != E
+                                                      or not ccol.is_contiguous()))):  # (float64 reads no columns of it)
             raise ValueError("csr must be (int32 [N+1], int32 [E] or None) contiguous tensors of this edge list")
+    # (float64 used to build the index of a forced row-local route before it looked at `csr`; a malformed `csr` now
+    #  raises the same ValueError without that launch, as float32 always did)
     rowish = route in ("fused", "staged", "rows")
     if rowish and assign_index is None:
         assign_index = build_assign_index(cl, num_supernodes)
-    rows_ok = (route is None or rowish) and assign_index is not None and assign_index.nnz == cl.numel() \
-        and assign_index.num_targets == num_supernodes and num_supernodes < (1 << 26) \
-        and (rowish or csr is not None or _rows_sorted_memo(edge_index) is not False)
-    staged_ok = rows_ok
+    L = N.lib()
+    # what every route function is handed.  The tuples are the runs of positional arguments the native entry points share:
+    #   rc    = (row, col)                            the edge list's two rows
+    #   rest  = (w, E, cluster, N, num_supernodes)    what follows them in every count entry (w: None without weights)
+    #   sizes = (E, N, num_supernodes)                what every *_workspace_bytes and every fill entry takes
+    #   cptr, ccol = the caller's CSR offsets / int32 columns (None: not given; float64 reads no columns)
+    #   entry(name) = the symbol of this value type (`name` or `name_f64`); index = the supernode -> member AssignIndex
+    q = SimpleNamespace(
+        L=L, dev=dev, st=N.stream_ptr(dev), f64=f64, edge_index=edge_index, w=w, w_dtype=None if w is None else w.dtype,
+        entry=lambda name: getattr(L, name + "_f64" if f64 else name), index=assign_index,
+        sizes=(E, cl.numel(), num_supernodes), rc=(N.ptr(row), N.ptr(col)),
+        rest=(N.ptr(w), E, N.ptr(cl), cl.numel(), num_supernodes), op=N.REDUCE_OPS[reduce_op], eps=ops_eps(),
+        flags=(N.REMOVE_SELF_LOOPS if remove_self_loops else 0) | (N.EPS_FILTER if (w is not None and eps_filter) else 0),
+        cptr=None if csr is None else N.ptr(csr[0]), ccol=None if (csr is None or f64) else N.ptr(csr[1]))
+
+    # ---- the ladder: fused -> rows (staged) -> grouped -> general; float64 has the rows and the general route only.
+    # A route hands back its outputs or its negative decline code; a forced route that declines raises.
+    rows_ok = ((route is None or rowish) and assign_index is not None and assign_index.nnz == cl.numel()
+               and assign_index.num_targets == num_supernodes and num_supernodes < (1 << 26)
+               and (rowish or csr is not None or _rows_sorted_memo(edge_index) is not False)
+               and not (f64 and (E == 0 or torch.cuda.is_current_stream_capturing())))
     # the fused kernel's workgroups wait for their predecessors: it is used while all tiles are resident at once
     # (<= 1024 of them: one launch wave), i.e. for batches of small graphs, where the staged pipeline's ten launches
     # dominate; large lists take the staged pipeline, whose kernels never wait for each other
-    fused_ok = rows_ok and (route == "fused" or (num_supernodes <= FUSED_MAX_SUPERNODES
-                                                  and E <= FUSED_MAX_AVG_ROW * num_supernodes))
-    if fused_ok and route != "staged":
-        ws = N.workspace(L.tgp_connect_coalesce_fused_workspace_bytes(E, cl.numel(), num_supernodes), dev)
-        d_count = torch.empty(1, dtype=torch.int64, device=dev)
-        cap_w = None if w is None else torch.empty(max(E, 1), dtype=torch.float32, device=dev)
-        st = N.stream_ptr(dev)
-        cptr = ccol = None
-        if csr is not None:
-            cptr, ccol = csr
-        N.check(L.tgp_connect_coalesce_fused_count(N.ptr(row), N.ptr(col), N.ptr(cptr), N.ptr(ccol), N.ptr(w), E,
-                                                   N.ptr(cl), cl.numel(), num_supernodes,
-                                                   N.ptr(assign_index.row_ptr), N.ptr(assign_index.perm),
-                                                   N.REDUCE_OPS[reduce_op], flags, eps, N.ptr(cap_w), N.ptr(ws),
-                                                   ws.numel(), N.ptr(d_count), st), "tgp_connect_coalesce_fused_count")
-        n_out = _read_count(d_count)
-        if n_out >= 0:
-            out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-            N.check(L.tgp_connect_coalesce_fused_fill(N.ptr(ws), E, cl.numel(), num_supernodes, n_out,
-                                                      N.ptr(out_ei[0]) if n_out else None,
-                                                      N.ptr(out_ei[1]) if n_out else None, st),
-                    "tgp_connect_coalesce_fused_fill")
-            out_w = None
-            if w is not None:  # the kernel wrote the weights at their final offsets of the capacity-E buffer
-                out_w = cap_w[:n_out] if 2 * n_out >= E else cap_w[:n_out].clone()
-            return out_ei, out_w
-        del ws, cap_w
+    if rows_ok and not f64 and route != "staged" and (route == "fused" or (
+            num_supernodes <= FUSED_MAX_SUPERNODES and E <= FUSED_MAX_AVG_ROW * num_supernodes)):
+        got = _coalesce_fused(q)
+        if not isinstance(got, int):
+            return got
         if route == "fused":
-            raise RuntimeError(f"fused coalesce route declined (code {n_out})")
+            raise RuntimeError(f"fused coalesce route declined (code {got})")
         # -3: only the fused kernel's tile limit; -1 on a list whose rows ARE sorted: a supernode row too long for the
         # fused kernel -- the staged pipeline takes both (it sorts hub rows device-wide)
-        if n_out != -3 and E > 1 and csr is None and _rows_sorted_memo(edge_index) is None:
+        if got != -3 and E > 1 and csr is None and _rows_sorted_memo(edge_index) is None:
             _rows_sorted(edge_index, row)
-        staged_ok = n_out == -3 or (n_out == -1 and (csr is not None or _rows_sorted_memo(edge_index) is True))
-    if staged_ok:
-        # a list known to hold hub rows (a supernode row beyond 1024 raw entries) asks for the huge-row kernels at once;
-        # any other list finds out from the count (-5), once per edge_index object
-        hub = _HUB_LISTS.get(edge_index) is not None
-        published = _PUBLISH_COUNTS and not torch.cuda.is_current_stream_capturing()
-        for attempt in range(2):
-            fl = flags | (N.HUGE_ROWS if hub else 0)
-            nbytes = (L.tgp_connect_coalesce_rows_huge_workspace_bytes if hub else
-                      L.tgp_connect_coalesce_rows_workspace_bytes)(E, cl.numel(), num_supernodes)
-            ws = N.workspace(nbytes, dev)
-            st = N.stream_ptr(dev)
-            d_count = torch.empty(1, dtype=torch.int64, device=dev)
-            if published:
-                # r4: the survivor scan is one look-back launch whose last workgroup stores the count into a pinned host
-                # word: no scan pair, no copy kernel, no stream synchronise; int32 columns when Select's CSR holds them
-                state = _sps_state(dev, st, L.tgp_connect_coalesce_rows_count_status_words(num_supernodes, cl.numel()))
-                epoch = state.next_epoch()
-                N.check(L.tgp_connect_coalesce_rows_count_published(
-                    N.ptr(row), N.ptr(col), N.ptr(csr[1]) if csr is not None else None, N.ptr(w), E, N.ptr(cl),
-                    cl.numel(), num_supernodes, N.ptr(assign_index.row_ptr), N.ptr(assign_index.perm),
-                    N.ptr(csr[0]) if csr is not None else None, N.REDUCE_OPS[reduce_op], fl, eps, N.ptr(ws),
-                    ws.numel(), N.ptr(d_count), state.status.data_ptr(), state.status.numel(),
-                    state.pinned.data_ptr(), epoch, st), "tgp_connect_coalesce_rows_count_published")
-                n_out = _decode_count(state.wait(epoch))
-            else:
-                N.check(L.tgp_connect_coalesce_rows_count(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(cl), cl.numel(),
-                                                          num_supernodes, N.ptr(assign_index.row_ptr),
-                                                          N.ptr(assign_index.perm),
-                                                          N.ptr(csr[0]) if csr is not None else None,
-                                                          N.REDUCE_OPS[reduce_op], fl, eps, N.ptr(ws),
-                                                          ws.numel(), N.ptr(d_count), st), "tgp_connect_coalesce_rows_count")
-                n_out = _read_count(d_count)
-            if n_out != -5 or hub:
-                break
-            hub = True
-            _HUB_LISTS.put(edge_index, True)
-            del ws
-        if n_out >= 0:
-            out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-            out_w = None if w is None else torch.empty(n_out, dtype=torch.float32, device=dev)
-            N.check(L.tgp_connect_coalesce_rows_fill(N.ptr(ws), E, cl.numel(), num_supernodes,
-                                                     (0 if w is None else 1) | (2 if hub else 0),
-                                                     n_out, N.ptr(out_ei[0]) if n_out else None,
-                                                     N.ptr(out_ei[1]) if n_out else None, N.ptr(out_w), st),
-                    "tgp_connect_coalesce_rows_fill")
-            return out_ei, out_w
-        del ws  # declined: fall through to the sort-based path
+        rows_ok = got == -3 or (got == -1 and (csr is not None or _rows_sorted_memo(edge_index) is True))
+    if rows_ok:
+        got = _coalesce_rows(q)
+        if not isinstance(got, int):
+            return got
         if rowish:
             raise RuntimeError("row-local coalesce route declined (unsorted rows or a supernode row too long)")
-        if E > 1 and _rows_sorted_memo(edge_index) is None:
-            # remember WHY for this tensor object (one comparison pass, once): an unsorted list skips the row-local
-            # attempt (~50 us + a host round trip) on every later call
+        # remember WHY for this tensor object (one comparison pass, once): an unsorted list skips the row-local attempt
+        # (~50 us + a host round trip) on every later call
+        if (got == -1 and csr is None if f64 else E > 1) and _rows_sorted_memo(edge_index) is None:
             _rows_sorted(edge_index, row)
     if rowish:
-        raise RuntimeError("row-local coalesce route declined or not applicable")
-    if route == "grouped" or (route is None and 65536 < num_supernodes < (1 << 26)):
-        # more than 32 bits of (row, col) key: sort by supernode row only (half the radix passes) and order the short
-        # rows in LDS; declines (count = -1) when a supernode row is too long for that
-        ws = N.workspace(L.tgp_connect_coalesce_grouped_workspace_bytes(E, cl.numel(), num_supernodes), dev)
-        d_count = torch.empty(1, dtype=torch.int64, device=dev)
-        st = N.stream_ptr(dev)
-        N.check(L.tgp_connect_coalesce_grouped_count(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(cl), cl.numel(),
-                                                     num_supernodes, N.REDUCE_OPS[reduce_op], flags, eps, N.ptr(ws),
-                                                     ws.numel(), N.ptr(d_count), st), "tgp_connect_coalesce_grouped_count")
-        n_out = _read_count(d_count)
-        if n_out >= 0:
-            out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-            out_w = None if w is None else torch.empty(n_out, dtype=torch.float32, device=dev)
-            N.check(L.tgp_connect_coalesce_rows_fill(N.ptr(ws), E, cl.numel(), num_supernodes, 0 if w is None else 1,
-                                                     n_out, N.ptr(out_ei[0]) if n_out else None,
-                                                     N.ptr(out_ei[1]) if n_out else None, N.ptr(out_w), st),
-                    "tgp_connect_coalesce_rows_fill")
-            return out_ei, out_w
-        del ws
+        raise RuntimeError("row-local coalesce route not applicable" if f64 else
+                           "row-local coalesce route declined or not applicable")
+    if not f64 and (route == "grouped" or (route is None and 65536 < num_supernodes < (1 << 26))):
+        got = _coalesce_grouped(q)
+        if not isinstance(got, int):
+            return got
         if route == "grouped":
             raise RuntimeError("grouped coalesce route declined (a supernode row too long for the in-LDS sort)")
-    ws = N.workspace(L.tgp_connect_coalesce_workspace_bytes(E, cl.numel(), num_supernodes), dev)
-    d_count = torch.empty(1, dtype=torch.int64, device=dev)
-    st = N.stream_ptr(dev)
-    N.check(L.tgp_connect_coalesce_count(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(cl), cl.numel(),
-                                         num_supernodes, N.REDUCE_OPS[reduce_op], flags, eps, N.ptr(ws), ws.numel(),
-                                         N.ptr(d_count), st), "tgp_connect_coalesce_count")
-    n_out = _read_count(d_count)
-    out_ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-    out_w = None if w is None else torch.empty(n_out, dtype=torch.float32, device=dev)
-    N.check(L.tgp_connect_coalesce_fill(N.ptr(ws), E, cl.numel(), num_supernodes, 0 if w is None else 1, flags, n_out,
-                                        N.ptr(out_ei[0]) if n_out else None,
-                                        N.ptr(out_ei[1]) if n_out else None, N.ptr(out_w), st),
-            "tgp_connect_coalesce_fill")
-    return out_ei, out_w
+    return _coalesce_general(q)
 
 
 def normalize_edges_(edge_index: Tensor, edge_weight: Tensor, num_nodes: int, degree_norm: bool,
@@ -1900,16 +1895,13 @@ def topk_minscore(score: Tensor, ptr: Tensor, min_score: float, tol: float = 1e-
     n, B = score.numel(), ptr.numel() - 1
     prob = torch.empty(n, dtype=torch.float32, device=dev)
     L = N.lib()
-    ws = N.workspace(L.tgp_topk_minscore_workspace_bytes(n, B), dev)
-    d_count = torch.empty(1, dtype=torch.int64, device=dev)
     st = N.stream_ptr(dev)
-    N.check(L.tgp_topk_minscore_count(N.ptr(score), N.ptr(ptr), n, B, float(min_score), float(tol), N.ptr(prob),
-                                      N.ptr(ws), ws.numel(), N.ptr(d_count), st), "tgp_topk_minscore_count")
-    k = _read_count(d_count)
-    node_index = torch.empty(k, dtype=torch.int64, device=dev)
-    N.check(L.tgp_topk_minscore_fill(N.ptr(ws), N.ptr(ptr), n, B, k, N.ptr(node_index) if k else None, st),
-            "tgp_topk_minscore_fill")
-    return prob, node_index
+    node_index, _ = _count_fill(
+        dev, L.tgp_topk_minscore_workspace_bytes(n, B),
+        lambda ws, ws_bytes, cnt: _checked(L.tgp_topk_minscore_count, N.ptr(score), N.ptr(ptr), n, B, float(min_score),
+                                           float(tol), N.ptr(prob), ws, ws_bytes, cnt, st),
+        lambda ws, k, out, _: _checked(L.tgp_topk_minscore_fill, ws, N.ptr(ptr), n, B, k, out, st), rows=1)
+    return prob, node_index[0]
 
 
 def topk_plan(sizes: Tensor, ratio: float) -> Tuple[Tensor, Tensor]:
@@ -2033,8 +2025,7 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         # (no CSR); the kernel validates row order itself, so a list nobody has looked at yet needs no check pass
         gp = N.i64c(graph_ptr)
         B = gp.numel() - 1
-        state = _sps_state(dev, st, L.tgp_graclus_match_graphs_fused_status_words(B))
-        epoch = state.next_epoch()
+        call = _sps_state(dev, st, L.tgp_graclus_match_graphs_fused_status_words(B)).open_call()
         # one allocation for the four outputs (a batch of small graphs: a few hundred KB); the typed views are made
         # behind the launch, while the kernel runs
         o_idx = 0
@@ -2048,16 +2039,14 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         N.check(L.tgp_graclus_match_graphs_fused(N.ptr(row), N.ptr(col), N.ptr(w), num_nodes, E, N.ptr(gp), B,
                                                  N.ptr(eptr), None,
                                                  base + o_idx, base + o_ptr, base + o_perm, base + o_ones,
-                                                 state.status.data_ptr(), state.status.numel(),
-                                                 state.pinned.data_ptr(), epoch, st), "tgp_graclus_match_graphs_fused")
+                                                 *call.lookback, st), "tgp_graclus_match_graphs_fused")
         i64, i32, f32 = buf.view(torch.int64), buf.view(torch.int32), buf.view(torch.float32)
         index = torch.as_strided(i64, (2, num_nodes), (num_nodes, 1), o_idx >> 3)
         a_ptr = torch.as_strided(i32, (num_nodes + 1,), (1,), o_ptr >> 2)
         a_perm = torch.as_strided(i32, (num_nodes,), (1,), o_perm >> 2)
         ones = torch.as_strided(f32, (num_nodes,), (1,), o_ones >> 2)
-        word = state.wait(epoch)
-        if not word & 0x80000000:
-            k = word & 0x7FFFFFFF
+        k = call.total()
+        if k is not None:
             if E > 1 and _rows_sorted_memo(edge_index) is None:
                 _remember_rows_sorted(edge_index, True)  # (the kernel refuses lists whose rows are not ascending)
             out = (index, k, AssignIndex(a_ptr[:k + 1], a_perm, num_nodes, k), ones)
@@ -2984,11 +2973,10 @@ def mask_index(mask: Tensor, declined: Optional[Tensor] = None, want_rank: bool 
     if scratch is None or scratch.numel() < words:
         scratch = torch.zeros(max(words, 1024), dtype=torch.int32, device=dev)
         _MASK_INDEX_SCRATCH[key] = scratch
-    state = _sps_state(dev, st, 0)
-    epoch = state.next_epoch()
-    N.check(L.tgp_mask_index_count(N.ptr(mask), n, N.ptr(declined), N.ptr(scratch), state.pinned.data_ptr(), epoch, st),
+    call = _sps_state(dev, st, 0).open_call()
+    N.check(L.tgp_mask_index_count(N.ptr(mask), n, N.ptr(declined), N.ptr(scratch), *call.publish, st),
             "tgp_mask_index_count")
-    k = _decode_count(state.wait(epoch))
+    k = call.count()
     if k < 0:
         return None
     rows = 2 if want_rank else 1
@@ -3119,27 +3107,18 @@ def kron_batched(indptr: Tensor, col: Tensor, val: Optional[Tensor], perm: Optio
     if node_rank is not None and not (node_rank.dtype == torch.int32 and node_rank.numel() == num_nodes + 1
                                       and node_rank.is_contiguous() and node_rank.device == dev):
         node_rank = None  # (not the table of THIS batch: the call builds its own)
-    ws = N.workspace(L.tgp_kron_batched_workspace_bytes(num_nodes, B, max_graph_nodes, cap_dense, cap_big), dev)
-    d_count = torch.empty(1, dtype=torch.int64, device=dev)
     st = N.stream_ptr(dev)
-    N.check(L.tgp_kron_batched_count(N.ptr(indptr.contiguous()), N.ptr(col), N.ptr(v32), N.ptr(v64),
-                                     N.ptr(None if perm is None else perm.contiguous()),
-                                     (1 if from_adjacency else 0) | (2 if skip_oversize else 0),
-                                     num_nodes, col.numel(), N.ptr(graph_ptr), B, max_graph_nodes, cap_dense, cap_big,
-                                     num_big, N.ptr(node_index),
-                                     node_index.numel(), float(threshold), N.ptr(node_rank), N.ptr(ws), ws.numel(),
-                                     N.ptr(d_count), st),
-            "tgp_kron_batched_count")
-    n_out = _read_count(d_count)
-    if n_out < 0:
-        return None
-    ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-    ew = torch.empty(n_out, dtype=torch.float32, device=dev)
-    N.check(L.tgp_kron_batched_fill(N.ptr(ws), num_nodes, B, max_graph_nodes, cap_dense, cap_big, num_big,
-                                    N.ptr(graph_ptr), n_out,
-                                    N.ptr(ei[0]) if n_out else None, N.ptr(ei[1]) if n_out else None,
-                                    N.ptr(ew) if n_out else None, N.ptr(node_rank), st), "tgp_kron_batched_fill")
-    return ei, ew
+    got = _count_fill(
+        dev, L.tgp_kron_batched_workspace_bytes(num_nodes, B, max_graph_nodes, cap_dense, cap_big),
+        lambda ws, ws_bytes, cnt: _checked(
+            L.tgp_kron_batched_count, N.ptr(indptr.contiguous()), N.ptr(col), N.ptr(v32), N.ptr(v64),
+            N.ptr(None if perm is None else perm.contiguous()), (1 if from_adjacency else 0) | (2 if skip_oversize else 0),
+            num_nodes, col.numel(), N.ptr(graph_ptr), B, max_graph_nodes, cap_dense, cap_big, num_big, N.ptr(node_index),
+            node_index.numel(), float(threshold), N.ptr(node_rank), ws, ws_bytes, cnt, st),
+        lambda ws, n_out, r, c, w: _checked(L.tgp_kron_batched_fill, ws, num_nodes, B, max_graph_nodes, cap_dense, cap_big,
+                                            num_big, N.ptr(graph_ptr), n_out, r, c, w, N.ptr(node_rank), st),
+        torch.float32, declines=True)
+    return None if isinstance(got, int) else got
 
 
 # ------------------------------------------------------------------------- A10
@@ -3154,21 +3133,14 @@ def block_diag_edges(adj_pool: Tensor, relabel: Optional[Tensor] = None,
     rl = None if relabel is None else N.i64c(relabel)
     flags = N.REMOVE_SELF_LOOPS if remove_self_loops else 0
     L = N.lib()
-    ws = N.workspace(L.tgp_block_diag_workspace_bytes(B, K), dev)
-    d_count = torch.empty(1, dtype=torch.int64, device=dev)
     st = N.stream_ptr(dev)
     eps = ops_eps()
     count, fill = ((L.tgp_block_diag_count_f64, L.tgp_block_diag_fill_f64) if f64 else
                    (L.tgp_block_diag_count, L.tgp_block_diag_fill))
-    N.check(count(N.ptr(a), B, K, N.ptr(rl), flags, eps, N.ptr(ws), ws.numel(), N.ptr(d_count), st),
-            "tgp_block_diag_count")
-    n_out = _read_count(d_count)
-    ei = torch.empty(2, n_out, dtype=torch.int64, device=dev)
-    ew = torch.empty(n_out, dtype=a.dtype, device=dev)
-    N.check(fill(N.ptr(a), B, K, N.ptr(rl), flags, eps, N.ptr(ws), n_out,
-                                  N.ptr(ei[0]) if n_out else None, N.ptr(ei[1]) if n_out else None,
-                                  N.ptr(ew) if n_out else None, st), "tgp_block_diag_fill")
-    return ei, ew
+    return _count_fill(
+        dev, L.tgp_block_diag_workspace_bytes(B, K),
+        lambda ws, ws_bytes, cnt: _checked(count, N.ptr(a), B, K, N.ptr(rl), flags, eps, ws, ws_bytes, cnt, st),
+        lambda ws, n_out, r, c, w: _checked(fill, N.ptr(a), B, K, N.ptr(rl), flags, eps, ws, n_out, r, c, w, st), a.dtype)
 
 
 # ------------------------------------------------------------------------- A11
