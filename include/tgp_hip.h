@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -713,6 +713,60 @@ int tgp_dmon_loss_terms_bwd_f32(const float* g_terms, const float* stats, const 
                                 float* coef, float* W, void* stream);
 int tgp_dmon_ds_f32(const float* deg, const float* ca, const float* cs, const float* coef, int64_t rows, int64_t N,
                     const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * AsymCheegerCut's auxiliary losses (poolers/asym_cheeger_cut.py, utils/losses.py:503-550, 780-1010):
+ *   totvar[b]  = sum_ij a_ij ||s_i - s_j||_1 / (2 E_b),  E_b clamped to >= 1
+ *   balance[b] = (n (k-1) - sum_ik rho(s_ik - q_k)) / (n (k-1)),  q_k the idx-th largest entry of column k among the n
+ *                real nodes, idx = min(floor(n / k), n - 1), rho(d) = (k-1) d for d >= 0 and -d for d < 0
+ * No float atomics: every sum has a fixed order.  Graph b owns rows b N .. of S in the padded layout (ptr NULL; its real
+ * rows: the first graph_sizes[b] (NULL: N) of them whose mask byte (NULL: all) is set) or rows ptr[b] .. ptr[b+1] in the
+ * un-padded one.
+ *
+ * tgp_acc_small_graph_nodes: the largest graph the counting select takes (128).
+ * tgp_acc_tv_dense_f32: A [B,N,N], S [B,N,K], nrb = ceil(N / 16): part [B,nrb] = per block of 16 rows the sum of
+ *   a_ij ||s_i - s_j||_1 over its nonzero a_ij, cnt [B,nrb] (int32) = its nonzeros.  A wave skips 64-column chunks of A
+ *   that hold no nonzero.  Rows and columns beyond graph_sizes[b] are not read.
+ * tgp_acc_tv_dense_bwd_f32: dS [B,N,K] = g_terms[b] c_tv / (2 ecnt[b]) sum_j (a_ij + a_ji) sign(s_i - s_j), sign(0) = 0;
+ *   every row is written.  g_terms [B], ecnt [B] (int32, >= 1) from tgp_acc_loss_terms_f32.
+ * tgp_acc_tv_edge_f32: S [nodes,K], col [E] destinations, w [E] (NULL: ones), (src_ptr [nodes+1], src_perm [E]) (int32)
+ *   the edges grouped by source in edge-list order (tgp_assign_index_build over the sources): node_tv[i] = sum over the
+ *   out-edges of i of w_e ||s_i - s_dst||_1.
+ * tgp_acc_tv_edge_bwd_f32: dS [nodes,K] from the out-edges and the in-edges (dst_ptr, dst_perm: grouped by destination)
+ *   of every node; an edge belongs to the graph batch[source] (batch NULL: graph 0).
+ * tgp_acc_quantile_f32: per (graph, column) q [B,K] = the quantile, qnode [B,K] (int32) = the LOWEST row, relative to the
+ *   graph's first, that holds it (-1: none), colsum [B,K] = sum_i rho(s_ik - q_k), cge [B,K] (int32) = rows with
+ *   s_ik >= q_k; nreal [B] (int32) = real rows.  kq = the k of the loss.  max_nodes = the largest graph (N when padded).
+ *   route 0: the counting select when max_nodes <= tgp_acc_small_graph_nodes(), else the radix select; 1 / 2 force one.
+ *   Exact: the bits of the entry a descending sort has at position idx (-0 and +0 are one value, NaN the largest).
+ * tgp_acc_loss_terms_f32: out [2,B] = (c_tv totvar, c_bal balance), ecnt [B] (int32) = E_b clamped.  tv NULL: row 0 is 0;
+ *   dense form: tv = part, cnt, nrb; edge form: tv = node_tv, src_ptr, ptr (E_b = the edges whose source lies in graph
+ *   b).  colsum NULL: row 1 is 0.
+ * tgp_acc_asym_bwd_f32: dS[r,k] (+)= -g_bal[b] c_bal rho'(s - q_k) / (n (k-1)) on real rows, plus
+ *   g_bal[b] c_bal sum_i rho'(d_ik) / (n (k-1)) on the quantile node; rho'(d) = k-1 for d >= 0, -1 otherwise.  Graph of a
+ *   row: r / N (padded), batch[r] (un-padded; batch NULL: 0).
+ * ---------------------------------------------------------------------------------- */
+int tgp_acc_small_graph_nodes(void);
+int tgp_acc_tv_dense_f32(const float* A, const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes,
+                         int64_t nrb, float* part, int* cnt, void* stream);
+int tgp_acc_tv_dense_bwd_f32(const float* A, const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes,
+                             const float* g_terms, const int* ecnt, float c_tv, float* dS, void* stream);
+int tgp_acc_tv_edge_f32(const float* S, int64_t nodes, int64_t K, const int64_t* col, const float* w, int64_t E,
+                        const int* src_ptr, const int* src_perm, float* node_tv, void* stream);
+int tgp_acc_tv_edge_bwd_f32(const float* S, int64_t nodes, int64_t K, const int64_t* row, const int64_t* col,
+                            const float* w, int64_t E, const int* src_ptr, const int* src_perm, const int* dst_ptr,
+                            const int* dst_perm, const int64_t* batch, const float* g_terms, const int* ecnt, float c_tv,
+                            int64_t B, float* dS, void* stream);
+int tgp_acc_quantile_f32(const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes, const uint8_t* mask,
+                         const int64_t* ptr, int64_t max_nodes, int64_t kq, int route, float* q, int* qnode, float* colsum,
+                         int* cge, int* nreal, void* stream);
+int tgp_acc_loss_terms_f32(const float* tv, const int* cnt, const int* src_ptr, const int64_t* ptr, int64_t nrb,
+                           const float* colsum, const int* nreal, int64_t B, int64_t K, int64_t kq, float c_tv, float c_bal,
+                           float* out, int* ecnt, void* stream);
+int tgp_acc_asym_bwd_f32(const float* S, int64_t rows, int64_t N, int64_t K, const int64_t* batch, const int64_t* ptr,
+                         const int64_t* graph_sizes, const uint8_t* mask, const float* q, const int* qnode, const int* cge,
+                         const int* nreal, const float* g_bal, float c_bal, int64_t kq, int64_t B, int accumulate, float* dS,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * N1 (r6)  The dense poolers' TRAINING step for graphs beyond the one-wave / one-workgroup kernels (C2: B = 32,

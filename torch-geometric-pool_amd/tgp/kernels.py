@@ -1887,6 +1887,164 @@ def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: i
     return out
 
 
+_ACC_TV_ROWS = 16  # rows of the adjacency per workgroup of the dense total-variation pass (csrc/asym_cheeger.hip)
+ACC_ROUTES = ("auto", "count", "radix")
+
+
+def acc_small_graph_nodes() -> int:
+    """The largest graph the counting quantile select takes (its columns sit in LDS); larger ones take the radix select."""
+    return int(N.lib().tgp_acc_small_graph_nodes())
+
+
+def acc_tv_dense(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(part [B,ceil(N/16)] float32, cnt [B,ceil(N/16)] int32): per block of 16 rows of a padded batch the sum of
+    a_ij ||s_i - s_j||_1 over its nonzero entries, and their number (utils/losses.py:780-862).  One pass over ``adj``;
+    64-column chunks without a nonzero cost nothing more than their load."""
+    dev = N.require_device(adj, s)
+    a, s = N.f32c(adj), N.f32c(s)
+    if s.dim() != 3 or a.shape != (s.size(0), s.size(1), s.size(1)):
+        raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
+    B, Nn, Kc = s.shape
+    nrb = max(1, -(-Nn // _ACC_TV_ROWS))
+    part = torch.empty(B, nrb, dtype=torch.float32, device=dev)
+    cnt = torch.empty(B, nrb, dtype=torch.int32, device=dev)
+    N.check(N.lib().tgp_acc_tv_dense_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)), nrb,
+                                         N.ptr(part), N.ptr(cnt), N.stream_ptr(dev)), "tgp_acc_tv_dense_f32")
+    return part, cnt
+
+
+def acc_tv_dense_bwd(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor], g_tv: Tensor, ecnt: Tensor,
+                     c_tv: float) -> Tensor:
+    """dS [B,N,K] of the dense total variation: g_b c_tv / (2 E_b) sum_j (a_ij + a_ji) sign(s_i - s_j), every row
+    written; row i and column i of ``adj`` are both read (the column through a transposed LDS tile)."""
+    dev = N.require_device(adj, s, g_tv, ecnt)
+    a, s = N.f32c(adj), N.f32c(s)
+    B, Nn, Kc = s.shape
+    ds = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_acc_tv_dense_bwd_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+                                             N.ptr(N.f32c(g_tv)), N.ptr(ecnt), float(c_tv), N.ptr(ds),
+                                             N.stream_ptr(dev)), "tgp_acc_tv_dense_bwd_f32")
+    return ds
+
+
+def acc_edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = False) -> AssignIndex:
+    """The edge positions grouped by source (the forward's order) or by destination (needed by the backward only),
+    edge-list order inside a group: the summation order of the edge-form total variation."""
+    row, col = _edge_rows(edge_index)
+    return build_assign_index(col if by_destination else row, num_nodes)
+
+
+def acc_tv_edge(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], by_src: AssignIndex) -> Tensor:
+    """node_tv [N]: per node the sum over its out-edges of w_e ||s_i - s_dst||_1 (utils/losses.py:865-917), one wave per
+    node, added in edge-list order."""
+    dev = N.require_device(s, edge_index, edge_weight)
+    s = N.f32c(s)
+    _, col = _edge_rows(edge_index)
+    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    n, Kc, E = s.size(0), s.size(1), col.numel()
+    if w is not None and w.numel() != E:
+        raise ValueError("acc_tv_edge: one weight per edge")
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_acc_tv_edge_f32(N.ptr(s), n, Kc, N.ptr(col) if E else None, N.ptr(w), E, N.ptr(by_src.row_ptr),
+                                        N.ptr(by_src.perm), N.ptr(out), N.stream_ptr(dev)), "tgp_acc_tv_edge_f32")
+    return out
+
+
+def acc_tv_edge_bwd(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], by_src: AssignIndex,
+                    by_dst: AssignIndex, batch: Optional[Tensor], g_tv: Tensor, ecnt: Tensor, c_tv: float) -> Tensor:
+    """dS [N,K] of the edge-form total variation: every node adds over its out-edges and its in-edges (no scatter)."""
+    dev = N.require_device(s, edge_index, edge_weight, batch, g_tv, ecnt)
+    s = N.f32c(s)
+    row, col = _edge_rows(edge_index)
+    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    n, Kc, E = s.size(0), s.size(1), col.numel()
+    ds = torch.empty(n, Kc, dtype=torch.float32, device=dev)
+    b = None if batch is None else N.i64c(batch)
+    N.check(N.lib().tgp_acc_tv_edge_bwd_f32(N.ptr(s), n, Kc, N.ptr(row) if E else None, N.ptr(col) if E else None,
+                                            N.ptr(w), E, N.ptr(by_src.row_ptr), N.ptr(by_src.perm),
+                                            N.ptr(by_dst.row_ptr), N.ptr(by_dst.perm), N.ptr(b), N.ptr(N.f32c(g_tv)),
+                                            N.ptr(ecnt), float(c_tv), ecnt.numel(), N.ptr(ds), N.stream_ptr(dev)),
+            "tgp_acc_tv_edge_bwd_f32")
+    return ds
+
+
+def acc_quantile(s: Tensor, k: int, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None,
+                 ptr: Optional[Tensor] = None, max_nodes: Optional[int] = None, route: str = "auto"):
+    """(q [B,K], qnode [B,K] int32, colsum [B,K], cge [B,K] int32, nreal [B] int32, route taken): per graph and column
+    of ``s`` the entry a descending sort has at position min(floor(n / k), n - 1) among the graph's n real rows -- exact,
+    without sorting -- the LOWEST row (relative to the graph's first) that holds it, the asymmetric-norm sum
+    sum_i rho(s_ik - q_k) and the number of rows with s_ik >= q_k (utils/losses.py:503-550, 920-1010).  Padded layout:
+    s [B,N,K] with ``mask`` / ``graph_sizes``; un-padded: s [Ntot,K] with node offsets ``ptr`` [B+1] and ``max_nodes``.
+    ``route``: "count" (graphs of at most :func:`acc_small_graph_nodes` rows, ranked by counting in LDS), "radix"
+    (8-bit radix select) or "auto"."""
+    dev = N.require_device(s, mask, graph_sizes, ptr)
+    s = N.f32c(s)
+    if ptr is None:
+        if s.dim() != 3:
+            raise ValueError("acc_quantile: the padded layout takes s [B,N,K]")
+        B, Nn, Kc = s.shape
+        mx, p = Nn, None
+        m, gs = _mask_bytes(mask, B, Nn), _sizes_arg(graph_sizes, B, dev)
+    else:
+        if s.dim() != 2 or mask is not None or graph_sizes is not None or max_nodes is None:
+            raise ValueError("acc_quantile: the un-padded layout takes s [Ntot,K], ptr and max_nodes")
+        p = N.i64c(ptr)
+        B, Nn, Kc, mx, m, gs = p.numel() - 1, 0, s.size(1), int(max_nodes), None, None
+    code = ACC_ROUTES.index(route)
+    taken = "count" if code == 1 or (code == 0 and mx <= acc_small_graph_nodes()) else "radix"
+    q = torch.empty(B, Kc, dtype=torch.float32, device=dev)
+    colsum = torch.empty(B, Kc, dtype=torch.float32, device=dev)
+    qnode = torch.empty(B, Kc, dtype=torch.int32, device=dev)
+    cge = torch.empty(B, Kc, dtype=torch.int32, device=dev)
+    nreal = torch.empty(B, dtype=torch.int32, device=dev)
+    N.check(N.lib().tgp_acc_quantile_f32(N.ptr(s), B, Nn, Kc, N.ptr(gs), N.ptr(m), N.ptr(p), mx, int(k), code, N.ptr(q),
+                                         N.ptr(qnode), N.ptr(colsum), N.ptr(cge), N.ptr(nreal), N.stream_ptr(dev)),
+            "tgp_acc_quantile_f32")
+    return q, qnode, colsum, cge, nreal, taken
+
+
+def acc_tail(B: int, Kc: int, k: int, dev, tv=None, colsum: Optional[Tensor] = None,
+                   nreal: Optional[Tensor] = None, coeffs=(1.0, 1.0)) -> Tuple[Tensor, Tensor]:
+    """(out [2,B], ecnt [B] int32): the per-graph total-variation and balance terms times ``coeffs`` in one launch, the
+    partial sums added in a fixed order.  ``tv``: None, ("dense", part, cnt) of :func:`acc_tv_dense` or
+    ("edge", node_tv, by_src, ptr) of :func:`acc_tv_edge`; ``colsum`` / ``nreal`` of :func:`acc_quantile` or None."""
+    out = torch.empty(2, B, dtype=torch.float32, device=dev)
+    ecnt = torch.empty(B, dtype=torch.int32, device=dev)
+    vals = cnt = src_ptr = ptr = None
+    nrb = 0
+    if tv is not None and tv[0] == "dense":
+        vals, cnt = tv[1], tv[2]
+        nrb = vals.size(1)
+    elif tv is not None:
+        vals, src_ptr, ptr = tv[1], tv[2].row_ptr, N.i64c(tv[3])
+    N.check(N.lib().tgp_acc_loss_terms_f32(N.ptr(vals), N.ptr(cnt), N.ptr(src_ptr), N.ptr(ptr), nrb, N.ptr(colsum),
+                                           N.ptr(nreal), B, Kc, int(k), float(coeffs[0]), float(coeffs[1]), N.ptr(out),
+                                           N.ptr(ecnt), N.stream_ptr(dev)), "tgp_acc_loss_terms_f32")
+    return out, ecnt
+
+
+def acc_asym_bwd(s: Tensor, k: int, q: Tensor, qnode: Tensor, cge: Tensor, nreal: Tensor, g_bal: Tensor, c_bal: float,
+                 out: Tensor, accumulate: bool, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None,
+                 ptr: Optional[Tensor] = None, batch: Optional[Tensor] = None) -> Tensor:
+    """out (+)= dS of the balance term: one elementwise pass, the column's total added on the quantile node."""
+    dev = N.require_device(s, q, qnode, cge, nreal, g_bal, out, mask, graph_sizes, ptr, batch)
+    s = N.f32c(s)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != s.shape:
+        raise ValueError("acc_asym_bwd: out must be a contiguous float32 tensor shaped like s")
+    B, Kc = q.shape
+    if ptr is None:
+        rows, Nn = s.size(0) * s.size(1), s.size(1)
+        m, gs, p, b = _mask_bytes(mask, B, Nn), _sizes_arg(graph_sizes, B, dev), None, None
+    else:
+        rows, Nn, m, gs, p = s.size(0), 0, None, None, N.i64c(ptr)
+        b = None if batch is None else N.i64c(batch)
+    N.check(N.lib().tgp_acc_asym_bwd_f32(N.ptr(s), rows, Nn, Kc, N.ptr(b), N.ptr(p), N.ptr(gs), N.ptr(m), N.ptr(q),
+                                         N.ptr(qnode), N.ptr(cge), N.ptr(nreal), N.ptr(N.f32c(g_bal)), float(c_bal), int(k),
+                                         B, 1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev)),
+            "tgp_acc_asym_bwd_f32")
+    return out
+
+
 def topk_minscore(score: Tensor, ptr: Tensor, min_score: float, tol: float = 1e-7) -> Tuple[Tensor, Tensor]:
     """(prob [N], node_index [k]): per-graph softmax of ``score`` and the nodes above the min_score threshold, ascending
     (select/topk_select.py:186-194 with PyG's softmax / topk); ``ptr`` = node offsets of the sorted batch."""

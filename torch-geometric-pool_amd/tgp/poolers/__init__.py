@@ -1,10 +1,10 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
-``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling`` is built and exported as a class;
-its ``dmon`` alias is not registered yet.
+``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling`` and ``AsymCheegerCutPooling`` are built and
+exported as classes; their ``dmon`` / ``acc`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -25,7 +25,11 @@ from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPoo
 from ..utils.ops import batch_info, is_dense_adj
 from ..utils.losses import (
     _MinCutTermsFn,
+    _acc_native,
     _dmon_native,
+    acc_loss_terms,
+    acc_sparse_loss_terms,
+    asym_norm_loss,
     cluster_loss,
     dmon_loss_terms,
     entropy_loss,
@@ -36,7 +40,10 @@ from ..utils.losses import (
     sparse_link_pred_loss,
     sparse_mincut_loss,
     sparse_spectral_loss,
+    sparse_totvar_loss,
     spectral_loss,
+    totvar_loss,
+    unbatched_asym_norm_loss,
     unbatched_cluster_loss,
     unbatched_entropy_loss,
     unbatched_orthogonality_loss,
@@ -285,8 +292,23 @@ class _DenseMLPPooling(DenseSRCPooling):
 
     # which auxiliary losses the pooler computes: "diff" (link + entropy), "mincut" (cut + ortho: their per-graph
     # terms come out of the pooling kernels), "dmon" (spectral + cluster + ortho from the raw S^T A S and their own
-    # loss kernels; the one-node training paths and the rows route decline it)
+    # loss kernels), "acc" (total variation + balance from the adjacency and S alone, their own loss kernels)
     _loss_kind = "diff"
+    # kinds whose losses come from loss kernels of their own behind the operator route: the one-node training paths
+    # (_SelectPoolSmallFn, _PoolLargeFn, _PoolUnbatchedFn, the sparse training node) and the rows route decline them
+    _LOSS_ONLY_KINDS = ("dmon", "acc")
+
+    # kinds whose losses walk the dense adjacency itself (ACC's total variation counts its nonzero entries): they also
+    # decline the one-launch sparse kernel, which never forms that adjacency in memory
+    _DENSE_ADJ_LOSS_KINDS = ("acc",)
+
+    @property
+    def _loss_only(self) -> bool:
+        return self._loss_kind in self._LOSS_ONLY_KINDS
+
+    @property
+    def _loss_reads_dense_adj(self) -> bool:
+        return self._loss_kind in self._DENSE_ADJ_LOSS_KINDS
 
     @property
     def _mincut_terms(self) -> bool:
@@ -359,13 +381,15 @@ class _DenseMLPPooling(DenseSRCPooling):
                 or batch is None or batch.dtype != torch.long or batch.numel() != x.size(0) or x.size(0) == 0
                 or (edge_weight is not None and (edge_weight.dim() != 1 or edge_weight.dtype != torch.float32))):
             return None
+        if self._loss_reads_dense_adj:
+            return None  # (the batch is densified, as the reference does)
         last = lins[0]
         if torch.is_grad_enabled() and edge_weight is not None and edge_weight.requires_grad:
             return None  # (the edge weights get no gradient from the fused backward)
         training = torch.is_grad_enabled() and (x.requires_grad or last.weight.requires_grad
                                                 or (last.bias is not None and last.bias.requires_grad))
-        if training and self._loss_kind == "dmon":
-            return None  # (DMoN trains on the operator route)
+        if training and self._loss_only:
+            return None  # (the loss-only kinds train on the operator route)
         # (a pooler whose losses need the dense adjacency -- DiffPool's link loss -- gets it as a side output of the launch)
         if training and not (_FOLD_TRAINING and not c.edge_weight_norm
                              and K.mlp_select_bwd_fits(last.weight.size(0), x.size(1))):
@@ -444,7 +468,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         from .. import functions as Fn, kernels as K
         sel, c = self.selector, self.connector
         lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        if (self._loss_kind == "dmon"
+        if (self._loss_only
                 or type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
                 or type(self.reducer) is not BaseReduce or not (isinstance(x, Tensor) and isinstance(adj, Tensor))
                 or x.dim() != 3 or adj.dim() != 3 or not x.is_cuda or x.dtype != torch.float32
@@ -476,7 +500,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         ran 65-71).  Returns ``(SelectOutput, fused, None)`` like :meth:`_select_reduce_connect_train`, or None."""
         from .. import functions as Fn, kernels as K
         sel, c = self.selector, self.connector
-        if (not _FOLD_TRAINING or self._loss_kind == "dmon" or type(c) is not DenseConnect
+        if (not _FOLD_TRAINING or self._loss_only or type(c) is not DenseConnect
                 or type(self.reducer) is not BaseReduce
                 or not (isinstance(x, Tensor) and isinstance(adj, Tensor)) or x.dim() != 3 or adj.dim() != 3
                 or not x.is_cuda or x.dtype != torch.float32 or adj.dtype != torch.float32
@@ -549,7 +573,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         from .. import kernels as K
         from .. import functions as Fn
         c, sel = self.connector, self.selector
-        if (self._loss_kind == "dmon" or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
+        if (self._loss_only or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
                 or (self.sparse_output and not batched_out)
                 or not (isinstance(x, Tensor) and isinstance(edge_index, Tensor))
                 or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32
@@ -1005,9 +1029,71 @@ class DMoNPooling(_DenseMLPPooling):
                 "cluster_loss_coeff": self.cluster_loss_coeff, "ortho_loss_coeff": self.ortho_loss_coeff}
 
 
+class AsymCheegerCutPooling(_DenseMLPPooling):
+    r"""Asymmetric Cheeger cut pooling ("Total Variation Graph Neural Networks", Hansen & Bianchi, ICML 2023; reference
+    poolers/asym_cheeger_cut.py:22-321): MinCut's Select / Reduce / Connect with the total-variation loss
+    sum_ij a_ij ||s_i - s_j||_1 / (2 E) and the balance (asymmetric norm) loss around each column's quantile.  Batched:
+    the losses read the densified adjacency (its nonzero entries are the edges) and the mask; unbatched: the edge list
+    (every edge counts, zero-weight ones included).
+
+    Ties: where several nodes of a graph hold a column's quantile value, the quantile's gradient goes to the LOWEST node
+    index among them (the reference sorts unstably and leaves that open)."""
+
+    _loss_kind = "acc"
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, act: str = None, dropout: float = 0.0,
+                 totvar_coeff: float = 1.0, balance_coeff: float = 1.0, remove_self_loops: bool = True,
+                 degree_norm: bool = True, edge_weight_norm: bool = False, adj_transpose: bool = True,
+                 lift: str = "precomputed", s_inv_op: str = "transpose", batched: bool = True,
+                 sparse_output: bool = False, cache_preprocessing: bool = False):
+        super().__init__(in_channels, k, act, dropout, remove_self_loops, degree_norm, edge_weight_norm,
+                         adj_transpose, lift, s_inv_op, batched, sparse_output, cache_preprocessing)
+        self.k = k
+        self.totvar_coeff = totvar_coeff
+        self.balance_coeff = balance_coeff
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
+        c = self.connector
+        raw = c.dense_connect(adj=adj, s=so.s)
+        loss = self.compute_loss(adj, so.s, mask)
+        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
+                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
+                                              edge_weight_norm=c.edge_weight_norm)
+        return adj_pool, loss
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+        return self.compute_loss(adj, so.s, mask)
+
+    def _scaled(self, tv, bal) -> dict:
+        return {"total_variation_loss": tv if self.totvar_coeff == 1 else tv * self.totvar_coeff,
+                "balance_loss": bal if self.balance_coeff == 1 else bal * self.balance_coeff}
+
+    def compute_loss(self, adj: Tensor, S: Tensor, mask: Optional[Tensor] = None) -> dict:
+        if _acc_native(adj, S) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
+            # both per-graph terms, coefficients applied: the pass over adj's nonzeros, the quantile select, one tail
+            # launch (native backward)
+            both = acc_loss_terms(adj, S, self.k, mask, self._sizes_for(adj),
+                                  (self.totvar_coeff, self.balance_coeff)).mean(dim=1)
+            return {"total_variation_loss": both[0], "balance_loss": both[1]}
+        return self._scaled(totvar_loss(S, adj, batch_reduction="mean"),
+                            asym_norm_loss(S, self.k, mask=mask, batch_reduction="mean"))
+
+    def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
+        ei, ew = connectivity_to_edge_index(edge_index, edge_weight)
+        both = acc_sparse_loss_terms(ei, ew, S, self.k, batch, (self.totvar_coeff, self.balance_coeff))
+        if both is not None:  # one Function, one tail launch, coefficients applied (as the dense route)
+            both = both.mean(dim=1)
+            return {"total_variation_loss": both[0], "balance_loss": both[1]}
+        return self._scaled(sparse_totvar_loss(ei, S, ew, batch, batch_reduction="mean"),
+                            unbatched_asym_norm_loss(S, self.k, batch, batch_reduction="mean"))
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched, "totvar_coeff": self.totvar_coeff, "balance_coeff": self.balance_coeff}
+
+
 # =============================================================================== factory
-# ("dmon" and "kmis" are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["DMoNPooling", "DiffPool", "GraclusPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis" and "acc" are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "DMoNPooling", "DiffPool", "GraclusPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

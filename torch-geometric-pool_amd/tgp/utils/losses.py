@@ -392,3 +392,185 @@ def unbatched_cluster_loss(S: Tensor, batch: Optional[Tensor] = None, batch_redu
     bvec = _batch_or_zeros(batch, n, S.device)
     sizes = torch.bincount(bvec, minlength=nb)[:nb].to(S.dtype)
     return _reduce(torch.norm(_seg_sum(S, bvec, nb), dim=1) / sizes * math.sqrt(k) - 1, batch_reduction)
+
+
+# ------------------------------------------------------------------------------------------------ AsymCheegerCut
+class _ACCTermsFn(torch.autograd.Function):
+    """[2,B] per-graph total-variation and balance (asymmetric norm) terms of AsymCheegerCut pooling
+    (utils/losses.py:503-550, 780-1010), each times its coefficient in ``coeffs``, with a native backward.
+
+    Forward: the pass over the nonzeros of the adjacency (``layout`` "dense") or over every node's out-edges ("flat"),
+    the quantile select with the asymmetric-norm column sums, one tail launch.  Backward: dS of the total variation
+    (row i and column i of the adjacency; out- and in-edges of node i), then one elementwise pass that adds dS of the
+    balance term.  Neither the adjacency nor the edge weights get a gradient here.
+
+    ``layout``: ("dense", mask, graph_sizes) with ``source`` = adj [B,N,N] or None (no total variation), or
+    ("flat", ptr, batch, max_nodes) with ``source`` = (edge_index, edge_weight or None) or None.  ``k`` <= 1: no
+    balance term (0).  Ties: where several nodes of a graph hold a column's quantile value, the LOWEST node index
+    receives the quantile's gradient (the reference's unstable sort leaves that open)."""
+
+    @staticmethod
+    def forward(ctx, S, source, layout, k, coeffs):
+        dense = layout[0] == "dense"
+        dev = K.N.require_device(S)
+        tv = groups = sel = None
+        if dense:
+            B, Kc = S.size(0), S.size(2)
+            if source is not None:
+                tv = ("dense",) + K.acc_tv_dense(source, S, layout[2])
+            if k > 1:
+                sel = K.acc_quantile(S, k, mask=layout[1], graph_sizes=layout[2])
+        else:
+            B, Kc = layout[1].numel() - 1, S.size(1)
+            if source is not None:
+                groups = K.acc_edge_group(source[0], S.size(0))  # (by source; by destination: in the backward)
+                tv = ("edge", K.acc_tv_edge(S, source[0], source[1], groups), groups, layout[1])
+            if k > 1:
+                sel = K.acc_quantile(S, k, ptr=layout[1], max_nodes=layout[3])
+        out, ecnt = K.acc_tail(B, Kc, k, dev, tv, None if sel is None else sel[2], None if sel is None else sel[4],
+                                     coeffs)
+        ctx.save_for_backward(S, ecnt, *(sel[:2] + sel[3:5] if sel is not None else ()))
+        ctx.source, ctx.layout, ctx.k, ctx.coeffs, ctx.groups = source, layout, k, coeffs, groups
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S, ecnt, *sel = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g = g.to(torch.float32).contiguous()
+        layout, source, dense = ctx.layout, ctx.source, ctx.layout[0] == "dense"
+        ds = None
+        if source is not None and dense:
+            ds = K.acc_tv_dense_bwd(source, S, layout[2], g[0], ecnt, ctx.coeffs[0])
+        elif source is not None:
+            by_dst = K.acc_edge_group(source[0], S.size(0), by_destination=True)
+            ds = K.acc_tv_edge_bwd(S, source[0], source[1], ctx.groups, by_dst, layout[2], g[0], ecnt, ctx.coeffs[0])
+        if sel:
+            acc = ds is not None
+            if not acc:
+                ds = torch.empty(S.shape, dtype=torch.float32, device=S.device)
+            q, qnode, cge, nreal = sel
+            if dense:
+                K.acc_asym_bwd(S, ctx.k, q, qnode, cge, nreal, g[1], ctx.coeffs[1], ds, acc, mask=layout[1],
+                               graph_sizes=layout[2])
+            else:
+                K.acc_asym_bwd(S, ctx.k, q, qnode, cge, nreal, g[1], ctx.coeffs[1], ds, acc, ptr=layout[1],
+                               batch=layout[2])
+        if ds is None:
+            ds = torch.zeros(S.shape, dtype=torch.float32, device=S.device)
+        return ds.view(S.shape).to(S.dtype), None, None, None, None
+
+
+_ONES2 = (1.0, 1.0)
+
+
+def _acc_native(*ts) -> bool:
+    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
+    forms below."""
+    return not any(t is not None and t.dtype == torch.float64 for t in ts)
+
+
+def acc_loss_terms(adj: Optional[Tensor], S: Tensor, k: int, mask: Optional[Tensor] = None,
+                   graph_sizes: Optional[Tensor] = None, coeffs=(1.0, 1.0)) -> Tensor:
+    """[2,B]: per-graph values of :func:`totvar_loss` and :func:`asym_norm_loss` (before the batch reduction) of a padded
+    batch, each times its coefficient in ``coeffs``; float32 device operands.  ``graph_sizes`` (this build only): real
+    nodes per graph of a zero-padded batch, lets the passes skip the padding."""
+    return _ACCTermsFn.apply(S, adj, ("dense", mask, graph_sizes), int(k), tuple(float(c) for c in coeffs))
+
+
+def acc_sparse_loss_terms(edge_index: Tensor, edge_weight: Optional[Tensor], S: Tensor, k: int,
+                          batch: Optional[Tensor] = None, coeffs=(1.0, 1.0)) -> Optional[Tensor]:
+    """[2,B]: per-graph values of :func:`sparse_totvar_loss` and :func:`unbatched_asym_norm_loss` of an un-padded batch,
+    each times its coefficient, from ONE Function (one tail launch); None when the operands take the composed forms
+    (float64, edge weights that require grad, an unsorted batch, no nodes)."""
+    w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
+    if not (_acc_native(S, w) and S.dim() == 2 and S.size(0) > 0) or (w is not None and w.requires_grad):
+        return None
+    K.N.require_device(S, edge_index, w, batch)
+    layout = _flat_layout(S, batch)
+    if layout is None:
+        return None
+    return _ACCTermsFn.apply(S, (edge_index, w), layout, int(k), tuple(float(c) for c in coeffs))
+
+
+def totvar_loss(S: Tensor, adj: Tensor, batch_reduction: str = "mean") -> Tensor:
+    """The total-variation loss sum_ij a_ij ||s_i - s_j||_1 / (2 E) per graph, E = the nonzero entries of ``adj[b]``
+    clamped to >= 1 (reference utils/losses.py:780-862).  Padded rows are zero and add nothing; no mask is read."""
+    if _acc_native(S, adj) and S.dim() == 3 and not adj.requires_grad:
+        return _reduce(_ACCTermsFn.apply(S, adj, ("dense", None, None), 0, _ONES2)[0], batch_reduction)
+    b, i, j = adj.nonzero(as_tuple=True)  # (row-major: a fixed summation order)
+    dist = (S[b, i] - S[b, j]).abs().sum(-1)
+    tv = _seg_sum(adj[b, i, j] * dist, b, S.size(0))
+    edges = torch.bincount(b, minlength=S.size(0)).clamp(min=1)
+    return _reduce(tv / (2 * edges), batch_reduction)
+
+
+def sparse_totvar_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Tensor] = None,
+                       batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The total-variation loss of an edge list (reference utils/losses.py:865-917): E counts every edge whose source
+    lies in the graph, zero-weight ones included (the dense form counts nonzero entries)."""
+    n = S.size(0)
+    w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
+    if _acc_native(S, w) and S.dim() == 2 and not (w is not None and w.requires_grad):
+        K.N.require_device(S, edge_index, w, batch)
+        layout = _flat_layout(S, batch) if n > 0 else None
+        if layout is not None:
+            return _reduce(_ACCTermsFn.apply(S, (edge_index, w), layout, 0, _ONES2)[0], batch_reduction)
+    nb = num_graphs_of(batch)
+    src, dst = edge_index[0], edge_index[1]
+    graph = _batch_or_zeros(batch, n, S.device)[src]
+    dist = (S[src] - S[dst]).abs().sum(-1)
+    tv = _seg_sum(dist if w is None else w.to(S.dtype) * dist, graph, nb)
+    edges = torch.bincount(graph, minlength=nb)[:nb].clamp(min=1)
+    return _reduce(tv / (2 * edges), batch_reduction)
+
+
+def _asym_norm_composed(S: Tensor, k: int, graph: Tensor, nb: int) -> Tensor:
+    """[nb] balance terms of the rows of S [Ntot,K] grouped by ``graph``, as torch ops (any dtype, any row order)."""
+    out = []
+    for b in range(nb):
+        rows = S[graph == b]
+        n = rows.size(0)
+        beta = n * (k - 1)
+        if beta == 0:
+            out.append(S.new_zeros(()))
+            continue
+        q = rows.sort(dim=0, descending=True)[0][min(n // k, n - 1)]
+        d = rows - q
+        out.append((beta - torch.where(d >= 0, (k - 1) * d, -d).sum()) / beta)
+    return torch.stack(out) if out else S.new_zeros(0)
+
+
+def asym_norm_loss(S: Tensor, k: int, mask: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The asymmetric-norm (balance) loss (n (k-1) - sum_ik rho(s_ik - q_k)) / (n (k-1)) per graph: q_k the entry at position
+    min(floor(n / k), n - 1) of column k sorted in descending order, n the graph's real nodes (``mask``; N without one),
+    rho(d) = (k-1) d for d >= 0 and -d below; 0 when k <= 1 or n (k-1) == 0 (reference utils/losses.py:920-1010).
+
+    The quantile is differentiable: its gradient lands on the node that supplied it, and where several nodes tie at the
+    quantile value, on the LOWEST node index among them (the reference's unstable sort leaves that open)."""
+    B, n = S.size(0), S.size(1)
+    if k <= 1 or n == 0:
+        return _reduce(S.new_zeros(B), batch_reduction)
+    if _acc_native(S) and S.dim() == 3:
+        return _reduce(_ACCTermsFn.apply(S, None, ("dense", mask, None), int(k), _ONES2)[1], batch_reduction)
+    if mask is None:
+        mask = torch.ones(B, n, dtype=torch.bool, device=S.device)
+    graph = torch.arange(B, device=S.device).unsqueeze(1).expand(B, n)[mask]
+    # (every graph of the batch has a term, 0 for one without real nodes, as the kernels have it; the reference drops
+    #  trailing graphs whose mask is empty from the mean)
+    return _reduce(_asym_norm_composed(S[mask], k, graph, B), batch_reduction)
+
+
+def unbatched_asym_norm_loss(S: Tensor, k: int, batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The balance loss of an un-padded batch (reference utils/losses.py:503-550); ties as :func:`asym_norm_loss`."""
+    n = S.size(0)
+    if k <= 1:
+        return S.new_zeros(())
+    if _acc_native(S) and S.dim() == 2:
+        K.N.require_device(S, batch)
+        layout = _flat_layout(S, batch) if n > 0 else None
+        if layout is not None:
+            return _reduce(_ACCTermsFn.apply(S, None, layout, int(k), _ONES2)[1], batch_reduction)
+    graph = _batch_or_zeros(batch, n, S.device)
+    return _reduce(_asym_norm_composed(S, k, graph, int(graph.max()) + 1 if n else 0), batch_reduction)
