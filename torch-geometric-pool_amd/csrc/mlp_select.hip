@@ -628,7 +628,9 @@ extern "C" int tgp_softmax_bwd_ex_f32(const float* s, const float* ds, const flo
               "tgp_softmax_bwd_ex_f32: null pointer");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int k = static_cast<int>(K);
-  if (K <= 16)
+  // the lane-group width switches where tgp_softmax_bwd_f32's does: without an optional term the two kernels then make
+  // the same adds in the same order (bit-identical results)
+  if (K <= 32)
     hipLaunchKernelGGL(softmax_bwd_ex_kernel<16>, dim3(cdiv(M, 16)), dim3(256), 0, stream, s, ds, extra, c1, deg,
                        static_cast<long>(rows_per_graph), ent_g, ent_scale, ent_eps, dy, static_cast<long>(ld_dy),
                        static_cast<long>(M), k, batch);
