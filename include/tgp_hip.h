@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -713,6 +713,56 @@ int tgp_dmon_loss_terms_bwd_f32(const float* g_terms, const float* stats, const 
                                 float* coef, float* W, void* stream);
 int tgp_dmon_ds_f32(const float* deg, const float* ca, const float* cs, const float* coef, int64_t rows, int64_t N,
                     const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * HOSC pooling's auxiliary losses (poolers/hosc.py, utils/losses.py:218-316, 392-432, 597-641), motif adjacency
+ * M = A A A never formed:
+ *   cut[b]    = -trace(S^T A S) / (den1 + eps),   den1 = sum_i d1_i |S_i|^2,  d1 = A 1
+ *   ho_cut[b] = -num / (den3 + eps),  num = sum S (.) Z,  Z = A (A (A S)),  den3 = sum_i d3_i |S_i|^2,  d3 = A (A (A 1))
+ *   out[0,b]  = (1 - alpha) cut inv_k + alpha ho_cut inv_k          (a part whose weight is 0 is not evaluated)
+ *   out[1,b]  = mu || G / ||G||_F - I / sqrt(K) ||_F  (gram given)  or, hosc_ortho,
+ *               mu (sqrt(K) - sum_j ||S_*j|| / sqrt(n_b)) / (sqrt(K) - 1), 0 when K <= 1;  0 when mu = 0
+ * ``part`` [B][nsplit][tgp_hosc_record_floats(K)] holds, per block of 64 rows of a graph, the K column square sums, per
+ * block of 64 columns (num | den3 | num1 = sum S (.) (A S) | den1), and the node count; the tail adds the blocks of a graph
+ * in a fixed order.
+ *
+ * tgp_hosc_matvec_f32: y[b,i] = sum_j A[b,i,j] v[b,j] (v NULL: ones) on the rows below graph_sizes[b] (NULL: all), 0 on
+ *   the others; A [B,N,N], v and y [B,N]; one streaming pass over A.  The columns are not cut.
+ * tgp_hosc_node_terms_f32: S [rows,K]; Z, Z1 with row stride ldz, d3, d1 with element stride ldd (each NULL: its sums are
+ *   0).  Padded (ptr NULL): graph b owns rows b N .. b N + graph_sizes[b] (NULL: N), nsplit = ceil(N / 64), n_b = the
+ *   mask's (bytes, [B,N]) true entries (NULL: N).  Un-padded: rows ptr[b] .. ptr[b+1], nsplit = ceil(largest graph / 64),
+ *   n_b = the graph's rows.
+ * tgp_hosc_small_f32: padded batch with N, K <= tgp_hosc_small_graph_nodes() (64): d1, d3 [B,N], Z [B,N,K] and part
+ *   (nsplit = 1) in ONE launch, one workgroup per graph with A[b] and two [N,K] buffers in LDS.
+ * tgp_hosc_loss_terms_f32: out [2,B]; trace(S^T A S) from the diagonal of raw [B,K,K], else from the num1 partials.
+ *   Writes cn [B,K] = ||S_*k|| and stats [B,6] = (num | den3 + eps | n_b | trace | den1 + eps | sum_k cn_k).
+ * tgp_hosc_loss_terms_bwd_f32: from the upstream gradients g_terms [2,B]: coef [B,5] = (c_num = -g0 alpha inv_k / D3,
+ *   c_den = g0 alpha inv_k num / D3^2, c_ortho = -g1 mu / (sqrt(n_b) (sqrt(K) - 1)) (hosc_ortho, else 0),
+ *   c_den1 = g0 (1 - alpha) inv_k trace / D1^2, c_num1 = -g0 (1 - alpha) inv_k / D1), g_raw [B,K,K] = c_num1 I (NULL: not
+ *   written) and, with gram, W [B,K,K] = d out[1] / d G (dS = S (W + W^T)).
+ * tgp_hosc_ds_f32: ds[r,k] (+)= c_num (Z + Zt) + 2 c_den d3_r S + c_ortho S / cn[b,k] + 2 c_den1 d1_r S
+ *   + c_num1 (Z1 + Z1t); Zt = A^T (A^T (A^T S)), Z1t = A^T S with row stride ldzt, NULL: A = A^T, the forward's product
+ *   counts twice.  b = batch[r] when given (un-padded), else r / N.  A column of norm 0 gets no c_ortho term.
+ * ---------------------------------------------------------------------------------- */
+int tgp_hosc_small_graph_nodes(void);
+int64_t tgp_hosc_record_floats(int64_t K);
+int tgp_hosc_matvec_f32(const float* A, const float* v, int64_t B, int64_t N, const int64_t* graph_sizes, float* y,
+                        void* stream);
+int tgp_hosc_node_terms_f32(const float* S, const float* Z, const float* Z1, int64_t ldz, const float* d3,
+                            const float* d1, int64_t ldd, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes,
+                            const uint8_t* mask, const int64_t* ptr, int64_t nsplit, float* part, void* stream);
+int tgp_hosc_small_f32(const float* A, const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes,
+                       const uint8_t* mask, float* Z, float* d1, float* d3, float* part, void* stream);
+int tgp_hosc_loss_terms_f32(const float* part, int64_t nsplit, const float* raw, const float* gram, int64_t B, int64_t K,
+                            float alpha, float mu, float inv_k, int hosc_ortho, float eps, float* out, float* cn,
+                            float* stats, void* stream);
+int tgp_hosc_loss_terms_bwd_f32(const float* g_terms, const float* stats, const float* gram, int64_t B, int64_t K,
+                                float alpha, float mu, float inv_k, int hosc_ortho, float* g_raw, float* coef, float* W,
+                                void* stream);
+int tgp_hosc_ds_f32(const float* S, const float* Z, const float* Zt, const float* Z1, const float* Z1t, int64_t ldz,
+                    int64_t ldzt, const float* d3, const float* d1, int64_t ldd, const float* cn, const float* coef,
+                    int64_t rows, int64_t N, const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------
  * AsymCheegerCut's auxiliary losses (poolers/asym_cheeger_cut.py, utils/losses.py:503-550, 780-1010):

@@ -215,6 +215,18 @@ SIGNATURES = {
     "tgp_dmon_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p,
                                              _c_p, _c_p]),
     "tgp_dmon_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_hosc_small_graph_nodes": (_c_int, []),
+    "tgp_hosc_record_floats": (_c_i64, [_c_i64]),
+    "tgp_hosc_matvec_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_hosc_node_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
+                                         _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_hosc_small_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_hosc_loss_terms_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p,
+                                         _c_p, _c_p, _c_p]),
+    "tgp_hosc_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_int, _c_p, _c_p, _c_p,
+                                             _c_p]),
+    "tgp_hosc_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64,
+                                 _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
     "tgp_acc_small_graph_nodes": (_c_int, []),
     "tgp_acc_tv_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tgp_acc_tv_dense_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p]),

@@ -1887,6 +1887,176 @@ def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: i
     return out
 
 
+_HOSC_ROWS = 64  # rows of one graph per workgroup of the HOSC partial pass (csrc/hosc.hip)
+
+
+def hosc_small_graph_nodes() -> int:
+    """The largest graph (and cluster count) the one-launch HOSC forward takes (A[b] and two [N,K] buffers in LDS)."""
+    return int(N.lib().tgp_hosc_small_graph_nodes())
+
+
+def hosc_matvec(adj: Tensor, v: Optional[Tensor], graph_sizes: Optional[Tensor] = None) -> Tensor:
+    """y [B,N] = adj [B,N,N] @ v [B,N] (``v`` None: ones), 0 on the rows beyond ``graph_sizes``: one streaming pass over
+    adj; three of them give the motif degrees d3 = A (A (A 1)) without A A A (utils/losses.py:218-316)."""
+    dev = N.require_device(adj, v)
+    a = N.f32c(adj)
+    if a.dim() != 3 or a.size(1) != a.size(2):
+        raise ValueError(f"hosc_matvec: adj {tuple(adj.shape)} is not [B,N,N]")
+    B, Nn = a.size(0), a.size(1)
+    if v is not None:
+        v = N.f32c(v)
+        if tuple(v.shape) != (B, Nn):
+            raise ValueError(f"hosc_matvec: v {tuple(v.shape)} does not match adj {tuple(adj.shape)}")
+    y = torch.empty(B, Nn, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_hosc_matvec_f32(N.ptr(a), N.ptr(v), B, Nn, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(y),
+                                        N.stream_ptr(dev)), "tgp_hosc_matvec_f32")
+    return y
+
+
+def _hosc_rows(t: Optional[Tensor], rows: int, width: int):
+    """(float32 tensor, row stride in elements) of an optional operand of ``rows`` x ``width`` values: contiguous, or a
+    column block of a wider row-major buffer (2-D with unit column stride; 1-D with any stride when ``width`` is 1)."""
+    if t is None:
+        return None, 0
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if t.numel() != rows * width:
+        raise ValueError(f"operand {tuple(t.shape)} does not hold {rows} x {width} values")
+    if t.is_contiguous():
+        return t, width
+    if t.dim() == 1 and width == 1:
+        return t, t.stride(0)
+    if t.dim() == 2 and t.stride(1) == 1:
+        return t, t.stride(0)
+    return t.contiguous(), width
+
+
+def _hosc_ld(pairs, what: str) -> int:
+    lds = {ld for t, ld in pairs if t is not None}
+    if len(lds) > 1:
+        raise ValueError(f"{what}: operands of one kind must share their row stride")
+    return lds.pop() if lds else 0
+
+
+def hosc_node_terms(s: Tensor, z: Optional[Tensor], z1: Optional[Tensor], d3: Optional[Tensor], d1: Optional[Tensor],
+                    mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None, ptr: Optional[Tensor] = None,
+                    max_nodes: Optional[int] = None) -> Tensor:
+    """part [B,nsplit,record]: per block of 64 rows of a graph the column square sums of S, num = sum S (.) Z,
+    den3 = sum d3_i |S_i|^2, num1 = sum S (.) Z1, den1 = sum d1_i |S_i|^2 and the node count, in one pass.  Padded batch
+    (s [B,N,K], ``mask`` / ``graph_sizes``) or un-padded (s [Ntot,K] with ``ptr`` [B+1] and ``max_nodes``); z / z1 and
+    d3 / d1 may be column blocks of wider buffers (e.g. the K+1 columns of a CSR product on [S | 1])."""
+    dev = N.require_device(s, z, z1, d3, d1, mask, ptr)
+    s = N.f32c(s)
+    if ptr is None:
+        B, Nn, Kc = s.shape
+        rows, nsplit = B * Nn, max(1, -(-Nn // _HOSC_ROWS))
+        p = None
+    else:
+        p = N.i64c(ptr)
+        B, Nn, Kc = p.numel() - 1, 0, s.size(1)
+        rows, nsplit = s.size(0), max(1, -(-int(max_nodes) // _HOSC_ROWS))
+    zs = [_hosc_rows(t, rows, Kc) for t in (z, z1)]
+    ds_ = [_hosc_rows(t, rows, 1) for t in (d3, d1)]
+    L = N.lib()
+    part = torch.empty(B, nsplit, int(L.tgp_hosc_record_floats(Kc)), dtype=torch.float32, device=dev)
+    N.check(L.tgp_hosc_node_terms_f32(N.ptr(s), N.ptr(zs[0][0]), N.ptr(zs[1][0]), _hosc_ld(zs, "hosc_node_terms"),
+                                      N.ptr(ds_[0][0]), N.ptr(ds_[1][0]), _hosc_ld(ds_, "hosc_node_terms"), B, Nn, Kc,
+                                      N.ptr(_sizes_arg(graph_sizes, B, dev) if ptr is None else None),
+                                      N.ptr(_mask_bytes(mask, B, Nn) if ptr is None else None), N.ptr(p), nsplit,
+                                      N.ptr(part), N.stream_ptr(dev)), "tgp_hosc_node_terms_f32")
+    return part
+
+
+def hosc_is_small(Nn: int, Kc: int) -> bool:
+    """Does a padded batch of ``Nn`` nodes per graph and ``Kc`` clusters take the one-launch forward (:func:`hosc_small`)?"""
+    return bool(1 <= Nn <= hosc_small_graph_nodes() and 1 <= Kc <= hosc_small_graph_nodes())
+
+
+def hosc_small(adj: Tensor, s: Tensor, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None):
+    """(z [B,N,K], d1 [B,N], d3 [B,N], part [B,1,record]) of a padded batch of small graphs (N, K <= 64) in ONE launch:
+    what three :func:`hosc_matvec`, three products and :func:`hosc_node_terms` give on the general route."""
+    dev = N.require_device(adj, s, mask)
+    a, s = N.f32c(adj), N.f32c(s)
+    B, Nn, Kc = s.shape
+    if a.shape != (B, Nn, Nn):
+        raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
+    L = N.lib()
+    z = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
+    d = torch.empty(2, B, Nn, dtype=torch.float32, device=dev)
+    part = torch.empty(B, 1, int(L.tgp_hosc_record_floats(Kc)), dtype=torch.float32, device=dev)
+    N.check(L.tgp_hosc_small_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+                                 N.ptr(_mask_bytes(mask, B, Nn)), N.ptr(z), N.ptr(d[0]), N.ptr(d[1]), N.ptr(part),
+                                 N.stream_ptr(dev)), "tgp_hosc_small_f32")
+    return z, d[0], d[1], part
+
+
+def hosc_loss_terms(part: Tensor, Kc: int, raw: Optional[Tensor], gram: Optional[Tensor], alpha: float, mu: float,
+                    inv_k: float, hosc_ortho: bool):
+    """(out [2,B], cn [B,K], stats [B,6]): HOSC's per-graph terms ((1 - alpha) cut + alpha ho_cut) * inv_k and mu * ortho
+    in one launch from the partial records; trace(S^T A S) from the diagonal of ``raw``, else from the records' num1;
+    ``gram`` given: MinCut's orthogonality term, else (``hosc_ortho``) the column-norm form."""
+    dev = N.require_device(part, raw, gram)
+    part = N.f32c(part)
+    B, nsplit = part.size(0), part.size(1)
+    raw = None if raw is None else N.f32c(raw)
+    gram = None if gram is None else N.f32c(gram)
+    for t in (raw, gram):
+        if t is not None and tuple(t.shape) != (B, Kc, Kc):
+            raise ValueError(f"hosc_loss_terms: operand {tuple(t.shape)}, expected {(B, Kc, Kc)}")
+    if part.size(2) != int(N.lib().tgp_hosc_record_floats(Kc)):
+        raise ValueError("hosc_loss_terms: part does not hold records of K clusters")
+    out = torch.empty(2, B, dtype=torch.float32, device=dev)
+    cn = torch.empty(B, Kc, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 6, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_hosc_loss_terms_f32(N.ptr(part), nsplit, N.ptr(raw), N.ptr(gram), B, Kc, float(alpha), float(mu),
+                                            float(inv_k), 1 if hosc_ortho else 0, losses_eps(), N.ptr(out), N.ptr(cn),
+                                            N.ptr(stats), N.stream_ptr(dev)), "tgp_hosc_loss_terms_f32")
+    return out, cn, stats
+
+
+def hosc_loss_terms_bwd(g_terms: Tensor, stats: Tensor, gram: Optional[Tensor], Kc: int, alpha: float, mu: float,
+                        inv_k: float, hosc_ortho: bool, want_raw: bool):
+    """(g_raw [B,K,K] or None, coef [B,5], W [B,K,K] or None): the gradients of :func:`hosc_loss_terms` from the upstream
+    gradients [2,B], one launch (see tgp_hosc_loss_terms_bwd_f32)."""
+    dev = N.require_device(g_terms, stats, gram)
+    g_terms, stats = N.f32c(g_terms), N.f32c(stats)
+    gram = None if gram is None else N.f32c(gram)
+    B = stats.size(0)
+    g_raw = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if want_raw else None
+    W = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if gram is not None else None
+    coef = torch.empty(B, 5, dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_hosc_loss_terms_bwd_f32(N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(alpha), float(mu),
+                                                float(inv_k), 1 if hosc_ortho else 0, N.ptr(g_raw), N.ptr(coef), N.ptr(W),
+                                                N.stream_ptr(dev)), "tgp_hosc_loss_terms_bwd_f32")
+    return g_raw, coef, W
+
+
+def hosc_ds(s: Tensor, z: Optional[Tensor], zt: Optional[Tensor], z1: Optional[Tensor], z1t: Optional[Tensor],
+            d3: Optional[Tensor], d1: Optional[Tensor], cn: Optional[Tensor], coef: Tensor, nodes_per_graph: int,
+            batch: Optional[Tensor], out: Tensor, accumulate: bool) -> Tensor:
+    """out (+)= c_num (Z + Zt) + 2 c_den d3 S + c_ortho S / cn + 2 c_den1 d1 S + c_num1 (Z1 + Z1t) over the rows of S: the
+    elementwise part of HOSC's dS, one launch.  ``zt`` / ``z1t`` None: A = A^T, the forward's product counts twice.
+    Graph of a row: batch[r] (un-padded) or r // nodes_per_graph."""
+    dev = N.require_device(s, z, zt, z1, z1t, d3, d1, cn, coef, batch, out)
+    s = N.f32c(s)
+    Kc = s.size(-1)
+    rows = s.numel() // Kc
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * Kc:
+        raise ValueError("hosc_ds: out must be a contiguous float32 tensor of rows x K values")
+    zs = [_hosc_rows(t, rows, Kc) for t in (z, z1)]
+    zts = [_hosc_rows(t, rows, Kc) for t in (zt, z1t)]
+    ds_ = [_hosc_rows(t, rows, 1) for t in (d3, d1)]
+    b = None if batch is None else N.i64c(batch)
+    c = None if cn is None else N.f32c(cn)
+    coef = N.f32c(coef)
+    N.check(N.lib().tgp_hosc_ds_f32(N.ptr(s), N.ptr(zs[0][0]), N.ptr(zts[0][0]), N.ptr(zs[1][0]), N.ptr(zts[1][0]),
+                                    _hosc_ld(zs, "hosc_ds"), _hosc_ld(zts, "hosc_ds"), N.ptr(ds_[0][0]), N.ptr(ds_[1][0]),
+                                    _hosc_ld(ds_, "hosc_ds"), N.ptr(c), N.ptr(coef), rows, int(nodes_per_graph), N.ptr(b),
+                                    coef.size(0), Kc, 1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev)),
+            "tgp_hosc_ds_f32")
+    return out
+
+
 _ACC_TV_ROWS = 16  # rows of the adjacency per workgroup of the dense total-variation pass (csrc/asym_cheeger.hip)
 ACC_ROUTES = ("auto", "count", "radix")
 

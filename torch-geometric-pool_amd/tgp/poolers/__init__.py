@@ -1,10 +1,10 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
-``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling`` and ``AsymCheegerCutPooling`` are built and
-exported as classes; their ``dmon`` / ``acc`` aliases are not registered yet.
+``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling`` and
+``HOSCPooling`` are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -31,6 +31,13 @@ from ..utils.losses import (
     acc_sparse_loss_terms,
     asym_norm_loss,
     cluster_loss,
+    _hosc_native,
+    _ho_cut_composed_dense,
+    hosc_loss_terms,
+    hosc_orthogonality_loss,
+    hosc_sparse_loss_terms,
+    sparse_ho_mincut_loss,
+    unbatched_hosc_orthogonality_loss,
     dmon_loss_terms,
     entropy_loss,
     link_pred_loss,
@@ -292,15 +299,17 @@ class _DenseMLPPooling(DenseSRCPooling):
 
     # which auxiliary losses the pooler computes: "diff" (link + entropy), "mincut" (cut + ortho: their per-graph
     # terms come out of the pooling kernels), "dmon" (spectral + cluster + ortho from the raw S^T A S and their own
-    # loss kernels), "acc" (total variation + balance from the adjacency and S alone, their own loss kernels)
+    # loss kernels), "acc" (total variation + balance from the adjacency and S alone, their own loss kernels), "hosc"
+    # (first-order + motif cut and an orthogonality term: the raw S^T A S, the adjacency and S, their own loss kernels)
     _loss_kind = "diff"
     # kinds whose losses come from loss kernels of their own behind the operator route: the one-node training paths
     # (_SelectPoolSmallFn, _PoolLargeFn, _PoolUnbatchedFn, the sparse training node) and the rows route decline them
-    _LOSS_ONLY_KINDS = ("dmon", "acc")
+    _LOSS_ONLY_KINDS = ("dmon", "acc", "hosc")
 
-    # kinds whose losses walk the dense adjacency itself (ACC's total variation counts its nonzero entries): they also
-    # decline the one-launch sparse kernel, which never forms that adjacency in memory
-    _DENSE_ADJ_LOSS_KINDS = ("acc",)
+    # kinds whose losses walk the dense adjacency itself (ACC's total variation counts its nonzero entries, HOSC's motif
+    # chain multiplies by it three times): they also decline the one-launch sparse kernel, which never forms that
+    # adjacency in memory
+    _DENSE_ADJ_LOSS_KINDS = ("acc", "hosc")
 
     @property
     def _loss_only(self) -> bool:
@@ -316,7 +325,7 @@ class _DenseMLPPooling(DenseSRCPooling):
 
     @property
     def _wants_raw(self) -> bool:
-        return self._loss_kind in ("mincut", "dmon")
+        return self._loss_kind in ("mincut", "dmon", "hosc")
 
     def _fused_diff_scales(self, adj, mask, adj_numel=None):
         """(link_scale, ent_scale) when the pooler's two losses can ride on the fused training call (DiffPool).
@@ -1091,9 +1100,94 @@ class AsymCheegerCutPooling(_DenseMLPPooling):
         return {"batched": self.batched, "totvar_coeff": self.totvar_coeff, "balance_coeff": self.balance_coeff}
 
 
+class HOSCPooling(_DenseMLPPooling):
+    r"""Higher-order spectral clustering pooling ("Higher-order clustering and pooling for Graph Neural Networks", Duval &
+    Malliaros, CIKM 2022; reference poolers/hosc.py:25-384): MinCut's Select / Reduce / Connect with the loss
+    ``hosc_loss`` = ((1 - alpha) cut + alpha ho_cut) / k -- cut MinCut's first-order cut on the raw S^T A S, ho_cut the
+    same cut of the motif adjacency M = A A A -- and ``ortho_loss`` = mu x MinCut's orthogonality term or, with
+    ``hosc_ortho``, mu (sqrt(K) - sum_j ||S_*j|| / sqrt(n)) / (sqrt(K) - 1).
+
+    M is never formed: trace(S^T M S) = sum S (.) A (A (A S)) and M 1 = A (A (A 1)) (the reference's batched mode
+    multiplies A A A out; its unbatched function already uses the chain).  Batched: the losses read the densified
+    adjacency (A^T when ``adj_transpose``: in-degrees); unbatched: the edge list (out-degrees), so the two modes
+    disagree on a directed graph, as in the reference.  A disabled term (``mu = 0``, ``K <= 1``) is a float32 0-dim zero
+    on the inputs' device, where the reference hands out an int64 host zero."""
+
+    _loss_kind = "hosc"
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, act: str = None, dropout: float = 0.0,
+                 mu: float = 0.1, alpha: float = 0.5, hosc_ortho: bool = False, remove_self_loops: bool = True,
+                 degree_norm: bool = True, edge_weight_norm: bool = False, adj_transpose: bool = True,
+                 lift: str = "precomputed", s_inv_op: str = "transpose", batched: bool = True,
+                 sparse_output: bool = False, cache_preprocessing: bool = False):
+        super().__init__(in_channels, k, act, dropout, remove_self_loops, degree_norm, edge_weight_norm,
+                         adj_transpose, lift, s_inv_op, batched, sparse_output, cache_preprocessing)
+        self.k = k
+        self.mu = mu
+        self.alpha = alpha
+        self.hosc_ortho = hosc_ortho
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
+        c = self.connector
+        raw = c.dense_connect(adj=adj, s=so.s)
+        loss = self.compute_loss(adj, so.s, raw, mask)
+        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
+                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
+                                              edge_weight_norm=c.edge_weight_norm)
+        return adj_pool, loss
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+        return self.compute_loss(adj, so.s, raw, mask)
+
+    def compute_loss(self, adj: Tensor, S: Tensor, adj_pool: Tensor, mask: Optional[Tensor] = None) -> dict:
+        if (_hosc_native(adj, S, adj_pool) and S.dim() == 3 and adj.dim() == 3 and adj_pool.dim() == 3
+                and not adj.requires_grad):
+            # both per-graph rows, alpha, mu and 1 / k applied: the motif chain, one pass over S, one tail launch
+            both = hosc_loss_terms(adj, S, adj_pool, mask, self._sizes_for(adj), self.alpha, self.mu, self.k,
+                                   self.hosc_ortho).mean(dim=1)
+            return {"hosc_loss": both[0], "ortho_loss": both[1]}
+        cut = ho_cut = 0.0
+        if self.alpha < 1:
+            cut = mincut_loss(adj, S, adj_pool, batch_reduction="mean") / self.k
+        if self.alpha > 0:
+            ho_cut = _ho_cut_composed_dense(adj, S).mean() / self.k
+        if self.mu == 0:
+            ortho = S.new_zeros(())
+        elif self.hosc_ortho:
+            # (the reference's pooler always holds a mask -- all true for dense inputs given without one -- and takes
+            #  the square root of its integer row sums in float32)
+            full = mask if mask is not None else torch.ones(S.shape[:2], dtype=torch.bool, device=S.device)
+            ortho = hosc_orthogonality_loss(S, full, batch_reduction="mean")
+        else:
+            ortho = orthogonality_loss(S, batch_reduction="mean")
+        return {"hosc_loss": (1 - self.alpha) * cut + self.alpha * ho_cut, "ortho_loss": self.mu * ortho}
+
+    def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
+        ei, ew = connectivity_to_edge_index(edge_index, edge_weight)
+        both = hosc_sparse_loss_terms(ei, ew, S, batch, self.alpha, self.mu, self.k, self.hosc_ortho)
+        if both is not None:  # one Function, one tail launch, alpha, mu and 1 / k applied (as the dense route)
+            both = both.mean(dim=1)
+            return {"hosc_loss": both[0], "ortho_loss": both[1]}
+        cut = ho_cut = S.new_zeros(())
+        if self.alpha < 1:
+            cut = sparse_mincut_loss(ei, S, ew, batch, batch_reduction="mean") / self.k
+        if self.alpha > 0:
+            ho_cut = sparse_ho_mincut_loss(ei, S, ew, batch, batch_reduction="mean") / self.k
+        if self.mu == 0:
+            ortho = S.new_zeros(())
+        elif self.hosc_ortho:
+            ortho = unbatched_hosc_orthogonality_loss(S, batch, batch_reduction="mean")
+        else:
+            ortho = unbatched_orthogonality_loss(S, batch, batch_reduction="mean")
+        return {"hosc_loss": (1 - self.alpha) * cut + self.alpha * ho_cut, "ortho_loss": self.mu * ortho}
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched, "mu": self.mu, "alpha": self.alpha, "hosc_ortho": self.hosc_ortho}
+
+
 # =============================================================================== factory
-# ("dmon", "kmis" and "acc" are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "DMoNPooling", "DiffPool", "GraclusPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc" and "hosc" are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "DMoNPooling", "DiffPool", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

@@ -1,5 +1,5 @@
-"""Auxiliary losses DiffPool / MinCut / DMoN compute between Reduce and Connect
-(reference: tgp/utils/losses.py:39-123, 435-483, 644-708, 1083-1265).
+"""Auxiliary losses DiffPool / MinCut / DMoN / AsymCheegerCut / HOSC compute between Reduce and Connect
+(reference: tgp/utils/losses.py:39-123, 218-316, 392-483, 503-550, 597-708, 780-1010, 1083-1265).
 
 The batched dense losses run on native kernels: the link-prediction residual is
 reduced inside the GEMM epilogue so S S^T [B,N,N] is never materialised, the entropy and the
@@ -574,3 +574,262 @@ def unbatched_asym_norm_loss(S: Tensor, k: int, batch: Optional[Tensor] = None, 
             return _reduce(_ACCTermsFn.apply(S, None, layout, int(k), _ONES2)[1], batch_reduction)
     graph = _batch_or_zeros(batch, n, S.device)
     return _reduce(_asym_norm_composed(S, k, graph, int(graph.max()) + 1 if n else 0), batch_reduction)
+
+
+# ------------------------------------------------------------------------------------------------ HOSC
+def _hosc_native(*ts) -> bool:
+    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
+    forms below."""
+    return not any(t is not None and t.dtype == torch.float64 for t in ts)
+
+
+def _hosc_csr(edge_index: Tensor, w: Optional[Tensor], n: int):
+    """(edge_index, weights or None, int32 row offsets) of the row-sorted, duplicate-summed list: the CSR form of the A
+    the reference's ``sparse_coo_tensor(...).coalesce()`` builds (rows = sources)."""
+    ones = w is None
+    if ones and K.coalesced_memo(edge_index, n):
+        ei, w2 = edge_index, None
+    else:
+        ei, w2 = Fn.coalesce_sum(edge_index, torch.ones(edge_index.size(1), device=edge_index.device) if ones
+                                 else w.detach(), n)
+    if ones and ei is edge_index:
+        w2 = None  # (nothing merged: the weights are still all one)
+    return ei, w2, K.csr_offsets(ei, n)
+
+
+def _hosc_chain_csr(csr, S: Tensor, n: int, rounds: int):
+    """[T1, ..] with T1 = A [S | 1], T2 = A T1, T3 = A T2 for the first ``rounds`` of them: Z and the degree vector ride
+    together, K + 1 columns padded with zeros to a multiple of four (rows of 16-byte vectors for the CSR product)."""
+    ei, w, row_ptr = csr
+    kc = S.size(1)
+    t = torch.nn.functional.pad(S.detach().to(torch.float32), (0, -(-(kc + 1) // 4) * 4 - kc))
+    t[:, kc] = 1.0
+    out = []
+    for _ in range(rounds):
+        t = K.spmm_csr(row_ptr, ei, w, n, t)
+        out.append(t)
+    return out
+
+
+class _HOSCTermsFn(torch.autograd.Function):
+    """[2,B] per-graph terms of HOSC pooling (reference poolers/hosc.py:269-376, utils/losses.py:218-316, 392-432,
+    597-641): row 0 = ((1 - alpha) cut + alpha ho_cut) / k, row 1 = mu x orthogonality, with a native backward.  The motif
+    adjacency A A A is never formed: ho_cut = -sum S (.) A (A (A S)) / (sum_i d_i |S_i|^2 + eps), d = A (A (A 1)).
+
+    Forward, ``layout`` ("dense", mask, graph_sizes) with ``source`` = adj [B,N,N] or None (orthogonality only): three
+    matrix-vector passes over adj, three products on the matrix cores, one pass over S / Z / d, S^T S for MinCut's
+    orthogonality, one tail launch -- or, for N, K <= 64, ONE launch in front of the tail.  ``layout`` ("flat", ptr, batch,
+    max_nodes) with ``source`` = (edge_index, weights or None, row offsets) of the coalesced list: three CSR products on
+    [S | 1], the pass, the tail.  With alpha = 0 the chain is not run, with alpha = 1 the first-order cut is not evaluated.
+
+    Backward: one launch for the per-graph coefficients (and W, g_raw), Zt = A^T (A^T (A^T S)) -- skipped when the
+    adjacency is known to be symmetric -- and one elementwise launch for dS.  The adjacency gets no gradient here.
+    ``cfg`` = (alpha, mu, 1 / k, hosc_ortho).  ``raw`` [B,K,K] (dense layout) supplies trace(S^T A S) of the first-order
+    cut; without it, the first product A S does."""
+
+    @staticmethod
+    def forward(ctx, S, raw, source, layout, cfg):
+        alpha, mu, inv_k, hosc_ortho = cfg
+        dense = layout[0] == "dense"
+        kc = S.size(-1)
+        want_cut = source is not None and alpha < 1
+        want_ho = source is not None and alpha > 0
+        z = z1 = d1 = d3 = gram = sym = None
+        needs_grad = ctx.needs_input_grad[0]
+        if dense:
+            mask, sizes = layout[1], layout[2]
+            n = S.size(1)
+            if want_ho and K.hosc_is_small(n, kc):
+                z, d1, d3, part = K.hosc_small(source, S, mask, sizes)
+                if want_cut and raw is None:
+                    z1 = K.bmm(source, S)
+                    part = K.hosc_node_terms(S, z, z1, d3, d1, mask, sizes)
+            else:
+                if want_cut or want_ho:
+                    d1 = K.hosc_matvec(source, None, sizes)
+                if want_cut and raw is None:
+                    z1 = K.bmm(source, S)
+                if want_ho:
+                    d3 = K.hosc_matvec(source, K.hosc_matvec(source, d1, sizes), sizes)
+                    z = K.bmm(source, K.bmm(source, z1 if z1 is not None else K.bmm(source, S)))
+                part = K.hosc_node_terms(S, z, z1, d3, d1 if want_cut else None, mask, sizes)
+            if not want_cut:
+                d1 = None
+            if mu != 0 and not hosc_ortho:
+                gram = K.dense_pool(S, None, S, graph_sizes=sizes)[0]
+            if needs_grad and want_ho and source.dtype == torch.float32 and source.is_contiguous():
+                sym = K.AdjSymmetry.of_dense(source)
+        else:
+            n = S.size(0)
+            if want_cut or want_ho:
+                ts = _hosc_chain_csr(source, S, n, 3 if want_ho else 1)
+                if want_cut:
+                    z1, d1 = ts[0][:, :kc], ts[0][:, kc]
+                if want_ho:
+                    z, d3 = ts[2][:, :kc], ts[2][:, kc]
+                if needs_grad:
+                    sym = K.AdjSymmetry.of_edge_list(source[0], source[1], source[0], source[1], source[2], n)
+            part = K.hosc_node_terms(S, z, z1, d3, d1, ptr=layout[1], max_nodes=layout[3])
+        out, cn, stats = K.hosc_loss_terms(part, kc, raw if want_cut else None, gram, alpha, mu, inv_k, hosc_ortho)
+        adj = source if dense and (z is not None or z1 is not None) else None  # (the backward's A^T products read it)
+        ctx.save_for_backward(S, stats, cn if (hosc_ortho and mu != 0 and kc > 1) else None, gram, z, z1, d3, d1, adj)
+        ctx.layout, ctx.cfg, ctx.sym = layout, cfg, sym
+        ctx.csr = source if not dense else None
+        ctx.has_raw = raw is not None and want_cut
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S, stats, cn, gram, z, z1, d3, d1, adj = ctx.saved_tensors
+        alpha, mu, inv_k, hosc_ortho = ctx.cfg
+        kc = S.size(-1)
+        g_raw, coef, W = K.hosc_loss_terms_bwd(g, stats, gram, kc, alpha, mu, inv_k, hosc_ortho,
+                                               ctx.has_raw and ctx.needs_input_grad[1])
+        g_s = None
+        if ctx.needs_input_grad[0]:
+            acc = W is not None
+            g_s = K.bmm(S, W + W.transpose(1, 2)) if acc else torch.empty(S.shape, dtype=torch.float32, device=S.device)
+            zt = z1t = None
+            if (z is not None or z1 is not None) and not (ctx.sym is not None and ctx.sym.get()):
+                if ctx.layout[0] == "dense":
+                    u = K.bmm(adj, S, trans_a=True)
+                    z1t = u if z1 is not None else None
+                    if z is not None:
+                        zt = K.bmm(adj, K.bmm(adj, u, trans_a=True), trans_a=True)
+                else:  # the by-destination CSR (A^T), built here only
+                    ei, w, _ = ctx.csr
+                    n = S.size(0)
+                    csr_t = _hosc_csr(ei.flip(0), w, n)
+                    u = S.detach().to(torch.float32)
+                    ts = []
+                    for _ in range(3 if z is not None else 1):
+                        u = K.spmm_csr(csr_t[2], csr_t[0], csr_t[1], n, u)
+                        ts.append(u)
+                    z1t = ts[0] if z1 is not None else None
+                    zt = ts[2] if z is not None else None
+            if ctx.layout[0] == "dense":
+                K.hosc_ds(S, z, zt, z1, z1t, d3, d1, cn, coef, S.size(1), None, g_s, acc)
+            else:
+                K.hosc_ds(S, z, zt, z1, z1t, d3, d1, cn, coef, max(S.size(0), 1), ctx.layout[2], g_s, acc)
+            g_s = g_s.view(S.shape).to(S.dtype)
+        return g_s, g_raw, None, None, None
+
+
+def _hosc_cfg(alpha, mu, k, hosc_ortho):
+    return (float(alpha), float(mu), 1.0 / k, bool(hosc_ortho))
+
+
+def _hosc_ortho_composed(S: Tensor, n) -> Tensor:
+    """(sqrt(K) - sum_j ||S_*j|| / sqrt(n)) / (sqrt(K) - 1) per graph of S [B,N,K] as torch ops; n: a number or the
+    integer tensor mask.sum(1), whose square root the reference takes in float32 whatever S's dtype (losses.py:638)."""
+    sqrt_k = math.sqrt(S.size(-1))
+    sqrt_n = n.sqrt() if isinstance(n, Tensor) else math.sqrt(n)
+    return (sqrt_k - torch.norm(S, dim=-2).sum(-1) / sqrt_n) / (sqrt_k - 1)
+
+
+def _ho_cut_composed_dense(adj: Tensor, S: Tensor) -> Tensor:
+    """-sum S (.) A (A (A S)) / (sum_i d_i |S_i|^2 + eps), d = A (A (A 1)), per graph, in the chain form (never A A A)."""
+    zd = torch.cat([S, S.new_ones(S.shape[:-1] + (1,))], -1)
+    for _ in range(3):
+        zd = adj @ zd
+    num = (S * zd[..., :-1]).sum(dim=(-2, -1))
+    den = (zd[..., -1] * (S * S).sum(-1)).sum(-1)
+    return -(num / (den + eps))
+
+
+def hosc_loss_terms(adj: Optional[Tensor], S: Tensor, adj_pooled: Optional[Tensor], mask: Optional[Tensor] = None,
+                    graph_sizes: Optional[Tensor] = None, alpha: float = 0.5, mu: float = 0.1, k: Optional[int] = None,
+                    hosc_ortho: bool = False) -> Tensor:
+    """[2,B]: per-graph ((1 - alpha) cut + alpha ho_cut) / k and mu x orthogonality of a padded batch (the values
+    :class:`~tgp.poolers.HOSCPooling` averages), float32 device operands, the adjacency without a gradient.  ``k``: the
+    pooler's cluster count (S's last dimension by default).  ``graph_sizes`` (this build only): real nodes per graph of a
+    zero-padded batch, lets the passes skip the padding."""
+    k = S.size(-1) if k is None else k
+    return _HOSCTermsFn.apply(S, adj_pooled, adj, ("dense", mask, graph_sizes), _hosc_cfg(alpha, mu, k, hosc_ortho))
+
+
+def hosc_sparse_loss_terms(edge_index: Tensor, edge_weight: Optional[Tensor], S: Tensor, batch: Optional[Tensor] = None,
+                           alpha: float = 0.5, mu: float = 0.1, k: Optional[int] = None,
+                           hosc_ortho: bool = False) -> Optional[Tensor]:
+    """[2,B]: the same two rows for an un-padded batch (first-order cut with out-degrees, as
+    :func:`sparse_mincut_loss`); None when the operands take the composed forms (float64, edge weights that require grad,
+    an unsorted batch, no nodes or no edges).  MinCut's orthogonality row (``hosc_ortho`` False) is formed per graph from
+    the segment product S_g^T S_g beside the Function."""
+    w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
+    if (not (_hosc_native(S, w) and S.dim() == 2 and S.size(0) > 0 and edge_index.size(1) > 0)
+            or (w is not None and w.requires_grad)):
+        return None
+    K.N.require_device(S, edge_index, w, batch)
+    layout = _flat_layout(S, batch)
+    if layout is None:
+        return None
+    k = S.size(1) if k is None else k
+    n = S.size(0)
+    native_ortho = hosc_ortho or mu == 0
+    source = _hosc_csr(edge_index, w, n)
+    terms = _HOSCTermsFn.apply(S, None, source, layout, _hosc_cfg(alpha, mu if native_ortho else 0.0, k, hosc_ortho))
+    if native_ortho:
+        return terms
+    nb = layout[1].numel() - 1
+    gram = _per_graph_gram(S, batch, nb)
+    gram = gram / torch.norm(gram, dim=(-2, -1), keepdim=True)
+    target = torch.eye(S.size(1), device=S.device, dtype=S.dtype) / math.sqrt(S.size(1))
+    return torch.stack([terms[0], mu * torch.norm(gram - target, dim=(-2, -1))])
+
+
+def hosc_orthogonality_loss(S: Tensor, mask: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """HOSC's orthogonality loss (sqrt(K) - sum_j ||S_*j|| / sqrt(n)) / (sqrt(K) - 1) per graph, n = mask.sum(1) (N without
+    a mask); 0 for K <= 1 (reference utils/losses.py:597-641)."""
+    if S.size(-1) <= 1:
+        return _reduce(S.new_zeros(S.size(0)), batch_reduction)
+    if _hosc_native(S) and S.dim() == 3:
+        terms = _HOSCTermsFn.apply(S, None, None, ("dense", mask, None), (0.0, 1.0, 1.0, True))
+        return _reduce(terms[1], batch_reduction)
+    return _reduce(_hosc_ortho_composed(S, S.size(1) if mask is None else mask.sum(1)), batch_reduction)
+
+
+def unbatched_hosc_orthogonality_loss(S: Tensor, batch: Optional[Tensor] = None,
+                                      batch_reduction: str = "mean") -> Tensor:
+    """HOSC's orthogonality loss of an un-padded batch (reference utils/losses.py:392-432): n = the graph's node count; a
+    0-dim zero for K <= 1."""
+    n, k = S.shape
+    if k <= 1:
+        return S.new_zeros(())
+    layout = _flat_layout(S, batch) if _hosc_native(S) and n > 0 else None
+    if layout is not None:
+        terms = _HOSCTermsFn.apply(S, None, None, layout, (0.0, 1.0, 1.0, True))
+        return _reduce(terms[1], batch_reduction)
+    nb = num_graphs_of(batch)
+    bvec = _batch_or_zeros(batch, n, S.device)
+    sizes = torch.bincount(bvec, minlength=nb)[:nb].to(S.dtype)
+    norms = torch.stack([torch.norm(S[bvec == g], dim=0).sum() for g in range(nb)]) if nb else S.new_zeros(0)
+    sqrt_k = math.sqrt(k)
+    return _reduce((sqrt_k - norms / sizes.sqrt()) / (sqrt_k - 1), batch_reduction)
+
+
+def sparse_ho_mincut_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Tensor] = None,
+                          batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """The higher-order (motif) cut -trace(S_g^T M_g S_g) / (trace(S_g^T D_g S_g) + eps), M = A A A, D = diag(M 1), of an
+    edge list, in the chain form M S = A (A (A S)), M 1 = A (A (A 1)) (reference utils/losses.py:218-316).  As there: a
+    single graph gives a 0-dim value whatever the reduction, an empty edge list zeros."""
+    n = S.size(0)
+    nb = num_graphs_of(batch)
+    w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
+    if edge_index.numel() == 0:
+        return S.new_zeros(()) if nb == 1 else _reduce(S.new_zeros(nb), batch_reduction)
+    if _hosc_native(S, w) and S.dim() == 2 and n > 0 and not (w is not None and w.requires_grad):
+        K.N.require_device(S, edge_index, w, batch)
+        layout = _flat_layout(S, batch)
+        if layout is not None:
+            ho = _HOSCTermsFn.apply(S, None, _hosc_csr(edge_index, w, n), layout, (1.0, 0.0, 1.0, False))[0]
+            return ho[0] if nb == 1 else _reduce(ho, batch_reduction)
+    bvec = _batch_or_zeros(batch, n, S.device)
+    wv = torch.ones(edge_index.size(1), device=S.device, dtype=S.dtype) if w is None else w.to(S.dtype)
+    src, dst = edge_index[0], edge_index[1]
+    zd = torch.cat([S, S.new_ones(n, 1)], 1)
+    for _ in range(3):  # A x as a gather and an index_add over the edges (duplicates add up, as coalescing does)
+        zd = _seg_sum(wv.unsqueeze(-1) * zd[dst], src, n)
+    num = _seg_sum((S * zd[:, :-1]).sum(-1), bvec, nb)
+    den = _seg_sum(zd[:, -1] * (S * S).sum(-1), bvec, nb)
+    ho = -(num / (den + eps))
+    return ho[0] if nb == 1 else _reduce(ho, batch_reduction)
