@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -763,6 +763,29 @@ int tgp_hosc_ds_f32(const float* S, const float* Z, const float* Zt, const float
                     int64_t ldzt, const float* d3, const float* d1, int64_t ldd, const float* cn, const float* coef,
                     int64_t rows, int64_t N, const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * BN-Pool's reconstruction loss (poolers/bnpool.py:359-447, utils/losses.py:1268-1356), logits L = T S^T, T = S K,
+ * never written to memory.  Per graph b, m the node mask (bytes [B,N], NULL: all ones), n = sum m,
+ * e = #{(i,j): a_ij != 0, m_i m_j}, c = max(n^2 - e, 1) / max(e, 1), bce(l, a) = max(l, 0) - l a + log1p(exp(-|l|)):
+ *   rec[b] = (c sum_{a != 0} bce + sum_{a == 0} bce) / n^2,   both sums over m_i m_j = 1
+ * T, S [B,N,K] and A [B,N,N] contiguous float32; 1 <= K <= tgp_bnpool_max_clusters() (256), N >= 1.
+ *
+ * tgp_bnpool_rec_fwd_f32: one launch over the 32x32 tiles of L (exact-fp32 MFMA, T's rows and S's fragment on chip) that
+ *   reads each tile of A once and writes one record (sum a != 0 | sum a == 0 | count, int bits | 0) per (graph, block
+ *   of 32 columns) into ``part`` (``part_floats`` >= tgp_bnpool_part_floats(B, N) floats), then one tail launch that
+ *   adds a graph's records in a fixed order: rec [B], stats [B,2] = (c | n^2).  Bit-reproducible.
+ * tgp_bnpool_rec_bwd_f32: with G_ij = g[b] w_ij (sigmoid(l_ij) - a_ij) m_i m_j / n^2, w = c where a != 0, else 1
+ *   (stats from the forward), P = G S and Q = G^T T, both [B,N,K], from two launches that recompute the logit tiles
+ *   and keep G on chip (the second reads A's tiles transposed through LDS); no float atomics.  The caller forms
+ *   dS = P K^T + Q and dK = sum_b S^T P.  A gets no gradient.
+ * ---------------------------------------------------------------------------------- */
+int tgp_bnpool_max_clusters(void);
+int64_t tgp_bnpool_part_floats(int64_t B, int64_t N);
+int tgp_bnpool_rec_fwd_f32(const float* T, const float* S, const float* A, const uint8_t* mask, int64_t B, int64_t N,
+                           int64_t K, float* part, int64_t part_floats, float* rec, float* stats, void* stream);
+int tgp_bnpool_rec_bwd_f32(const float* T, const float* S, const float* A, const uint8_t* mask, const float* g,
+                           const float* stats, int64_t B, int64_t N, int64_t K, float* P, float* Q, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * AsymCheegerCut's auxiliary losses (poolers/asym_cheeger_cut.py, utils/losses.py:503-550, 780-1010):

@@ -227,6 +227,10 @@ SIGNATURES = {
                                              _c_p]),
     "tgp_hosc_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64,
                                  _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_bnpool_max_clusters": (_c_int, []),
+    "tgp_bnpool_part_floats": (_c_i64, [_c_i64, _c_i64]),
+    "tgp_bnpool_rec_fwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_bnpool_rec_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
     "tgp_acc_small_graph_nodes": (_c_int, []),
     "tgp_acc_tv_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tgp_acc_tv_dense_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p]),

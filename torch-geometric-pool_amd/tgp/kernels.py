@@ -2057,6 +2057,60 @@ def hosc_ds(s: Tensor, z: Optional[Tensor], zt: Optional[Tensor], z1: Optional[T
     return out
 
 
+def bnpool_max_clusters() -> int:
+    """The largest K the BN-Pool reconstruction kernels take (S's fragment sits in registers, a 32-row tile in LDS)."""
+    return int(N.lib().tgp_bnpool_max_clusters())
+
+
+def _bnpool_operands(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor], what: str):
+    dev = N.require_device(t, s, adj, mask)
+    t, s, a = N.f32c(t), N.f32c(s), N.f32c(adj)
+    if s.dim() != 3 or t.shape != s.shape or a.shape != (s.size(0), s.size(1), s.size(1)):
+        raise ValueError(f"{what}: T {tuple(t.shape)}, S {tuple(s.shape)}, adj {tuple(adj.shape)} are not "
+                         "[B,N,K], [B,N,K], [B,N,N]")
+    m = None
+    if mask is not None:
+        if mask.shape != s.shape[:2]:
+            raise ValueError(f"{what}: mask {tuple(mask.shape)} does not match S {tuple(s.shape)}")
+        m = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    return dev, t, s, a, m
+
+
+def bnpool_rec_fwd(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(rec [B], stats [B,2] = (c | n^2)): BN-Pool's per-graph class-balanced BCE between the logits T S^T (T = S K) and
+    ``adj``, divided by n^2 (utils/losses.py:1268-1356 as poolers/bnpool.py:400-416 calls it).  One launch over the
+    32x32 logit tiles (exact-fp32 MFMA) that reads ``adj`` once, one tail launch; the logits are never written."""
+    dev, t, s, a, m = _bnpool_operands(t, s, adj, mask, "bnpool_rec_fwd")
+    B, Nn, Kc = s.shape
+    rec = torch.empty(B, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    if B == 0:
+        return rec, stats
+    nfl = int(N.lib().tgp_bnpool_part_floats(B, Nn))
+    part = torch.empty(max(nfl, 1), dtype=torch.float32, device=dev)
+    N.check(N.lib().tgp_bnpool_rec_fwd_f32(N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), B, Nn, Kc, N.ptr(part), part.numel(),
+                                           N.ptr(rec), N.ptr(stats), N.stream_ptr(dev)), "tgp_bnpool_rec_fwd_f32")
+    return rec, stats
+
+
+def bnpool_rec_bwd(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor], g: Tensor,
+                   stats: Tensor) -> Tuple[Tensor, Tensor]:
+    """(P, Q) = (G S, G^T T), both [B,N,K], for G = d sum_b g_b rec_b / d logits: two launches that recompute the logit
+    tiles and keep G on chip (no float atomics)."""
+    dev, t, s, a, m = _bnpool_operands(t, s, adj, mask, "bnpool_rec_bwd")
+    N.require_device(g, stats)
+    B, Nn, Kc = s.shape
+    g, stats = N.f32c(g), N.f32c(stats)
+    if g.numel() != B or stats.shape != (B, 2):
+        raise ValueError(f"bnpool_rec_bwd: g {tuple(g.shape)} / stats {tuple(stats.shape)} do not match B = {B}")
+    p = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
+    q = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
+    if B > 0:
+        N.check(N.lib().tgp_bnpool_rec_bwd_f32(N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), N.ptr(g), N.ptr(stats), B, Nn, Kc,
+                                               N.ptr(p), N.ptr(q), N.stream_ptr(dev)), "tgp_bnpool_rec_bwd_f32")
+    return p, q
+
+
 _ACC_TV_ROWS = 16  # rows of the adjacency per workgroup of the dense total-variation pass (csrc/asym_cheeger.hip)
 ACC_ROUTES = ("auto", "count", "radix")
 

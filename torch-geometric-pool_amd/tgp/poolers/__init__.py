@@ -1,10 +1,11 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
-``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling`` and
-``HOSCPooling`` are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` aliases are not registered yet.
+``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
+``HOSCPooling`` and ``BNPool`` are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` aliases
+are not registered yet.
 """
 from __future__ import annotations
 
@@ -20,9 +21,9 @@ from .. import kernels as K
 from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
-from ..select import GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
+from ..select import DPSelect, GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
 from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling
-from ..utils.ops import batch_info, is_dense_adj
+from ..utils.ops import batch_info, batched_negative_edge_sampling, is_dense_adj, negative_edge_sampling
 from ..utils.losses import (
     _MinCutTermsFn,
     _acc_native,
@@ -31,6 +32,12 @@ from ..utils.losses import (
     acc_sparse_loss_terms,
     asym_norm_loss,
     cluster_loss,
+    _bnpool_native,
+    bnpool_rec_loss_terms,
+    cluster_connectivity_prior_loss,
+    kl_loss,
+    sparse_bce_reconstruction_loss,
+    weighted_bce_reconstruction_loss,
     _hosc_native,
     _ho_cut_composed_dense,
     hosc_loss_terms,
@@ -300,16 +307,17 @@ class _DenseMLPPooling(DenseSRCPooling):
     # which auxiliary losses the pooler computes: "diff" (link + entropy), "mincut" (cut + ortho: their per-graph
     # terms come out of the pooling kernels), "dmon" (spectral + cluster + ortho from the raw S^T A S and their own
     # loss kernels), "acc" (total variation + balance from the adjacency and S alone, their own loss kernels), "hosc"
-    # (first-order + motif cut and an orthogonality term: the raw S^T A S, the adjacency and S, their own loss kernels)
+    # (first-order + motif cut and an orthogonality term: the raw S^T A S, the adjacency and S, their own loss kernels),
+    # "bnpool" (reconstruction of the adjacency from S K S^T, its own tile kernels; a KL and a prior term as torch ops)
     _loss_kind = "diff"
     # kinds whose losses come from loss kernels of their own behind the operator route: the one-node training paths
     # (_SelectPoolSmallFn, _PoolLargeFn, _PoolUnbatchedFn, the sparse training node) and the rows route decline them
-    _LOSS_ONLY_KINDS = ("dmon", "acc", "hosc")
+    _LOSS_ONLY_KINDS = ("dmon", "acc", "hosc", "bnpool")
 
     # kinds whose losses walk the dense adjacency itself (ACC's total variation counts its nonzero entries, HOSC's motif
-    # chain multiplies by it three times): they also decline the one-launch sparse kernel, which never forms that
-    # adjacency in memory
-    _DENSE_ADJ_LOSS_KINDS = ("acc", "hosc")
+    # chain multiplies by it three times, BN-Pool's reconstruction loss meets every entry of it): they also decline the
+    # one-launch sparse kernel, which never forms that adjacency in memory
+    _DENSE_ADJ_LOSS_KINDS = ("acc", "hosc", "bnpool")
 
     @property
     def _loss_only(self) -> bool:
@@ -1185,9 +1193,153 @@ class HOSCPooling(_DenseMLPPooling):
         return {"batched": self.batched, "mu": self.mu, "alpha": self.alpha, "hosc_ortho": self.hosc_ortho}
 
 
+class BNPool(_DenseMLPPooling):
+    r"""BN-Pool ("BN-Pool: Bayesian Nonparametric Graph Pooling", Castellana & Bianchi 2025; reference
+    poolers/bnpool.py:27-556): the assignment comes from a truncated stick-breaking process (:class:`~tgp.select.DPSelect`),
+    Reduce and Connect are MinCut's, and three losses train it: ``quality``, the class-balanced binary cross entropy between
+    the logits S K S^T and the adjacency divided by n^2 (K a learnable k x k matrix); ``kl`` = eta x the KL divergence of
+    the sticks' Beta posteriors from the Beta(1, alpha_DP) prior; ``K_prior``, a Gaussian prior on K.
+
+    Batched: the reconstruction loss reads the preprocessed dense adjacency (A^T when ``adj_transpose``) and the mask;
+    float32 device tensors take the native route (utils.losses.bnpool_rec_loss_terms: the [B,N,N] logits are never
+    formed, forward or backward), float64 the composed one.  Unbatched: the reference's sampled-edge loss over the edge
+    list and the pairs :meth:`sample_negative_edges` draws (the project's own sampler, utils.ops); the per-graph
+    sampled-edge count normalises ``kl`` and ``K_prior``.
+
+    With ``train_K=False`` ``K_prior`` is a float32 0-dim zero on the inputs' device (the reference hands out a host
+    tensor)."""
+
+    _loss_kind = "bnpool"
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, alpha_DP=1.0, K_var=1.0, K_mu=10.0, K_init=1.0,
+                 eta=1.0, train_K=True, act: str = None, dropout: float = 0.0, remove_self_loops: bool = True,
+                 degree_norm: bool = True, edge_weight_norm: bool = False, adj_transpose: bool = True,
+                 lift: str = "precomputed", s_inv_op: str = "transpose", batched: bool = True,
+                 sparse_output: bool = False, cache_preprocessing: bool = False,
+                 num_neg_samples: Optional[int] = None):
+        if alpha_DP <= 0:
+            raise ValueError("alpha_DP must be positive")
+        if K_var <= 0:
+            raise ValueError("K_var must be positive")
+        if eta <= 0:
+            raise ValueError("eta must be positive")
+        if k <= 0:
+            raise ValueError("max_k must be positive")
+        super().__init__(in_channels, k, act, dropout, remove_self_loops, degree_norm, edge_weight_norm,
+                         adj_transpose, lift, s_inv_op, batched, sparse_output, cache_preprocessing)
+        self.selector = DPSelect(in_channels, k, batched_representation=batched, act=act, dropout=dropout,
+                                 s_inv_op=s_inv_op)
+        self.k = k
+        self.K_init_val = K_init
+        self.alpha_DP = alpha_DP
+        self.K_var_val = K_var
+        self.K_mu_val = K_mu
+        self.train_K = train_K
+        self.eta = eta
+        self.num_neg_samples = num_neg_samples
+        # prior of the stick-breaking process, prior of the cluster-cluster matrix, the matrix itself
+        self.register_buffer("alpha_prior", torch.ones(self.k - 1))
+        self.register_buffer("beta_prior", torch.ones(self.k - 1) * alpha_DP)
+        self.register_buffer("K_var", torch.tensor(K_var))
+        eye = torch.eye(self.k, self.k)
+        self.register_buffer("K_mu", K_mu * eye - K_mu * (1 - eye))
+        self.K = torch.nn.Parameter(K_init * eye - K_init * (1 - eye), requires_grad=train_K)
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        eye = torch.eye(self.k, self.k, device=self.K.device)
+        self.K.data = self.K_init_val * eye - self.K_init_val * (1 - eye)
+
+    def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None, so: Optional[SelectOutput] = None,
+                batch: Optional[Tensor] = None, batch_pooled: Optional[Tensor] = None, lifting: bool = False,
+                mask: Optional[Tensor] = None, **kwargs):
+        if lifting or self.batched:
+            return super().forward(x, adj, edge_weight, so=so, mask=mask, batch=batch, batch_pooled=batch_pooled,
+                                   lifting=lifting, **kwargs)
+        # unbatched: S [N,K], the sampled-edge loss, sparse Reduce and Connect
+        so = self.select(x=x, batch=batch)
+        loss = self.compute_sparse_loss(adj, batch, so)
+        x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch, return_batched=not self.sparse_output)
+        ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch, batch_pooled=batch_pool)
+        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so, loss=loss)
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
+        adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
+                                   batch_pooled=batch_pooled)
+        return adj_pool, self.compute_loss(adj, mask, so)
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+        return self.compute_loss(adj, mask, so)
+
+    def _prior_terms(self, q_z, norm_const, like: Tensor, **where) -> dict:
+        """``kl`` and ``K_prior`` (composed torch ops, element-wise over [.., k-1] and [k,k])."""
+        prior = torch.distributions.Beta(self.get_buffer("alpha_prior"), self.get_buffer("beta_prior"))
+        kl = kl_loss(q_z, prior, normalizing_const=norm_const, batch_reduction="mean", **where)
+        if self.train_K:
+            k_prior = cluster_connectivity_prior_loss(self.K, self.get_buffer("K_mu"), self.get_buffer("K_var"),
+                                                      normalizing_const=norm_const, batch_reduction="mean")
+        else:
+            k_prior = torch.zeros((), dtype=torch.float32, device=like.device)
+        return {"kl": self.eta * kl, "K_prior": k_prior}
+
+    def compute_loss(self, adj: Tensor, mask: Optional[Tensor], so: SelectOutput) -> dict:
+        s, q_z = so.s, so.q_z
+        n = mask.sum(-1) if mask is not None else torch.tensor(adj.shape[-1], device=adj.device)
+        n_squared = n ** 2
+        if _bnpool_native(s, self.K, adj) and s.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
+            # per-graph terms, already divided by n^2: T = S K, one launch over the logit tiles, one tail launch
+            rec = bnpool_rec_loss_terms(s, self.K, adj, mask).mean()
+        else:
+            rec = weighted_bce_reconstruction_loss(self.get_rec_adj(s), adj, mask, balance_links=True,
+                                                   normalizing_const=n_squared, batch_reduction="mean")
+        out = {"quality": rec}
+        out.update(self._prior_terms(q_z, n_squared, s, mask=mask))
+        return out
+
+    def sample_negative_edges(self, edge_index: Tensor, batch: Optional[Tensor]) -> Tensor:
+        """The non-edges the unbatched loss scores next to the edge list: undirected pairs, at most ``num_neg_samples`` per
+        graph (None: as many as the graph has edges)."""
+        if batch is None:
+            return negative_edge_sampling(edge_index, num_neg_samples=self.num_neg_samples, force_undirected=True)
+        return batched_negative_edge_sampling(edge_index, batch, num_neg_samples=self.num_neg_samples,
+                                              force_undirected=True)
+
+    def get_sparse_rec_loss(self, node_assignment: Tensor, adj, batch: Optional[Tensor], batch_size: int):
+        """(loss, sampled-edge count per graph) over the edge list and the sampled non-edges."""
+        edge_index, _ = connectivity_to_edge_index(adj)
+        neg_edge_index = self.sample_negative_edges(edge_index, batch)
+        all_edges = torch.cat([edge_index, neg_edge_index], dim=1)
+        logits = self.get_prob_link_logit(node_assignment, all_edges)
+        y = torch.cat([logits.new_ones(edge_index.size(1)), logits.new_zeros(neg_edge_index.size(1))], dim=0)
+        return sparse_bce_reconstruction_loss(logits, y, edges_batch_id=None if batch is None else batch[all_edges[0]],
+                                              batch_size=batch_size)
+
+    def compute_sparse_loss(self, adj, batch: Optional[Tensor], so: SelectOutput) -> dict:
+        from ..utils.ops import num_graphs_of
+        batch_size = num_graphs_of(batch) if batch is not None else 1
+        rec, norm_const = self.get_sparse_rec_loss(so.s, adj, batch, batch_size)
+        out = {"quality": rec}
+        where = dict(batch=batch, batch_size=batch_size) if batch is not None else {}
+        out.update(self._prior_terms(so.q_z, norm_const, so.s, **where))
+        return out
+
+    def get_rec_adj(self, S: Tensor) -> Tensor:
+        """The reconstructed adjacency's logits S K S^T (composed route and inspection; the native loss never forms it)."""
+        return S @ self.K @ S.transpose(-1, -2)
+
+    def get_prob_link_logit(self, node_assignment: Tensor, edges_list: Tensor) -> Tensor:
+        """Logits (S[u] K) . S[v] of the node pairs ``edges_list`` [2,E]."""
+        return ((node_assignment[edges_list[0]] @ self.K) * node_assignment[edges_list[1]]).sum(-1)
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched, "alpha_DP": self.alpha_DP, "k_prior_variance": self.K_var_val,
+                "k_prior_mean": self.K_mu_val, "k_init_value": self.K_init_val, "eta": self.eta, "train_K": self.train_K,
+                "num_neg_samples": self.num_neg_samples}
+
+
 # =============================================================================== factory
-# ("dmon", "kmis", "acc" and "hosc" are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "DMoNPooling", "DiffPool", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc" and "bnpool" are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

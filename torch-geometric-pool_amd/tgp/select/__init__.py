@@ -676,6 +676,55 @@ class MLPSelect(Select):
                 f"dropout={self.dropout}, s_inv_op={self.s_inv_op})")
 
 
+class DPSelect(MLPSelect):
+    r"""Dirichlet-process selector of BN-Pool (reference select/dp_select.py:13-176): the MLP has 2 (k - 1) outputs,
+    ``softplus`` and a clamp to [1e-3, 1e3] turn them into the parameters of ``q_z = Beta(alpha, beta)``, the sticks
+    ``z = self.sample_sticks(q_z)`` give pi_k = z_k prod_{j<k} (1 - z_j) (pi_K the rest of the stick) through a cumulative
+    sum in log space, and S = pi, zeroed on padded rows.  The ``SelectOutput`` carries ``q_z`` for the KL term.
+
+    Everything here is element-wise over [B,N,k-1] and stays a PyTorch op on the inputs' device (the device's gamma
+    sampler, ``softplus``, ``cumsum``); the MLP's Linear layers are the project's.
+
+    ``sample_sticks`` is the one random step; override it to inject a draw (host and device random streams differ).
+
+    Divergence from the reference: S takes the dtype of ``z``, so a float64 selector works; the reference allocates pi
+    as float32 whatever the input."""
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, batched_representation: bool = True,
+                 act: str = None, dropout: float = 0.0, s_inv_op: str = "transpose"):
+        super().__init__(in_channels=in_channels, k=2 * (k - 1), batched_representation=batched_representation,
+                         act=act, dropout=dropout, s_inv_op=s_inv_op)
+        self.k = k
+
+    def sample_sticks(self, q_z) -> Tensor:
+        """The stick fractions, one reparameterised draw of ``q_z``."""
+        return q_z.rsample()
+
+    @staticmethod
+    def _compute_pi_given_sticks(stick_fractions: Tensor) -> Tensor:
+        """[..., k-1] stick fractions in (0, 1) -> [..., k] assignment probabilities, products taken in log space."""
+        pad = stick_fractions.new_zeros(stick_fractions.shape[:-1] + (1,))
+        log_pi = torch.cat([torch.log(stick_fractions), pad], dim=-1)
+        log_pi = log_pi + torch.cat([pad, torch.cumsum(torch.log(1 - stick_fractions), dim=-1)], dim=-1)
+        return torch.exp(log_pi)
+
+    def forward(self, x: Tensor, mask: Optional[Tensor] = None, batch: Optional[Tensor] = None,
+                **kwargs) -> SelectOutput:
+        if self.batched_representation:
+            x = x.unsqueeze(0) if x.dim() == 2 else x
+        else:
+            assert x.dim() == 2, "x must be of shape [N, F] for unbatched mode"
+        out = torch.clamp(torch.nn.functional.softplus(self.mlp(x)), min=1e-3, max=1e3)
+        q_v_alpha, q_v_beta = torch.split(out, self.k - 1, dim=-1)
+        q_z = torch.distributions.Beta(q_v_alpha, q_v_beta)
+        s = self._compute_pi_given_sticks(self.sample_sticks(q_z))
+        if self.batched_representation:
+            if mask is not None:
+                s = s * mask.unsqueeze(-1)
+            return SelectOutput(s=s, s_inv_op=self.s_inv_op, in_mask=mask, q_z=q_z)
+        return SelectOutput(s=s, s_inv_op=self.s_inv_op, batch=batch, q_z=q_z)
+
+
 # =============================================================================== Graclus
 def graclus_cluster(row: Tensor, col: Tensor, weight: Optional[Tensor] = None,
                     num_nodes: Optional[int] = None, max_rounds: Optional[int] = None) -> Tensor:
@@ -1224,6 +1273,6 @@ class NDPSelect(Select):
         return f"{self.__class__.__name__}(s_inv_op={self.s_inv_op})"
 
 
-__all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
+__all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
            "degree_scorer"]

@@ -1,5 +1,5 @@
-"""Auxiliary losses DiffPool / MinCut / DMoN / AsymCheegerCut / HOSC compute between Reduce and Connect
-(reference: tgp/utils/losses.py:39-123, 218-316, 392-483, 503-550, 597-708, 780-1010, 1083-1265).
+"""Auxiliary losses DiffPool / MinCut / DMoN / AsymCheegerCut / HOSC / BN-Pool compute between Reduce and Connect
+(reference: tgp/utils/losses.py:39-123, 218-316, 392-483, 503-550, 597-708, 780-1010, 1083-1562).
 
 The batched dense losses run on native kernels: the link-prediction residual is
 reduced inside the GEMM epilogue so S S^T [B,N,N] is never materialised, the entropy and the
@@ -833,3 +833,137 @@ def sparse_ho_mincut_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[T
     den = _seg_sum(zd[:, -1] * (S * S).sum(-1), bvec, nb)
     ho = -(num / (den + eps))
     return ho[0] if nb == 1 else _reduce(ho, batch_reduction)
+
+
+# ------------------------------------------------------------------------------------------------ BN-Pool
+def _weighted_bce_terms(rec_adj: Tensor, adj: Tensor, mask: Optional[Tensor], balance_links: bool) -> Tensor:
+    """Per-graph sums of :func:`weighted_bce_reconstruction_loss` (before normalisation and batch reduction)."""
+    loss = torch.nn.functional.binary_cross_entropy_with_logits(rec_adj, adj, reduction="none")
+    if balance_links:
+        edge_mask = adj != 0
+        if mask is not None:
+            n = mask.sum(-1)
+            edge_mask = edge_mask & mask.unsqueeze(-1) & mask.unsqueeze(-2)
+        else:
+            n = adj.shape[-1]
+        n_edges = edge_mask.sum((-1, -2))
+        n_not_edges = torch.clamp(n ** 2 - n_edges, min=1)
+        # (integer / integer: a float32 quotient whatever the dtype of the logits, as in the reference)
+        balance = (n_not_edges / torch.clamp(n_edges, min=1)).to(loss.dtype)
+        # torch.where on the weight instead of the reference's loss[edge_mask] *= repeat_interleave(balance, n_edges),
+        # which waits on the host for the counts
+        loss = loss * torch.where(edge_mask, balance[..., None, None], loss.new_ones(()))
+    if mask is not None:
+        loss = loss * mask.unsqueeze(-1) * mask.unsqueeze(-2)
+    return loss.sum((-1, -2))
+
+
+def weighted_bce_reconstruction_loss(rec_adj: Tensor, adj: Tensor, mask: Optional[Tensor] = None,
+                                     balance_links: bool = True, normalizing_const: Optional[Tensor] = None,
+                                     batch_reduction: str = "mean") -> Tensor:
+    """Binary cross entropy between the logits ``rec_adj`` [B,N,N] and the targets ``adj`` (any real value), over the
+    entries whose row and column are in ``mask``; with ``balance_links`` the entries with ``adj != 0`` weigh
+    max(n^2 - e, 1) / max(e, 1), e their number; per graph divided by ``normalizing_const`` (reference
+    utils/losses.py:1268-1356).  Composed torch ops on logits that already exist: the fallback and the fp32 oracle of
+    :func:`bnpool_rec_loss_terms`, which never forms them."""
+    loss = _weighted_bce_terms(rec_adj, adj, mask, balance_links)
+    if normalizing_const is not None:
+        loss = loss / normalizing_const
+    return _reduce(loss, batch_reduction)
+
+
+def kl_loss(q, p, mask: Optional[Tensor] = None, batch: Optional[Tensor] = None, batch_size: int = None,
+            normalizing_const: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    """KL(q || p) summed over the last axis and over the nodes of each graph (``mask`` [B,N] for a padded batch, ``batch``
+    and ``batch_size`` for an un-padded one), divided by ``normalizing_const`` (reference utils/losses.py:1359-1443)."""
+    if mask is not None and batch is not None:
+        raise ValueError("Cannot specify both mask and batch")
+    if batch is not None and batch_size is None:
+        raise ValueError("Batch size must be specified if batch is specified")
+    loss = torch.distributions.kl_divergence(q, p).sum(-1)
+    if mask is not None:
+        loss = (loss * mask).sum(-1)
+    elif batch is not None:
+        loss = _seg_sum(loss, batch, batch_size)
+    else:
+        loss = loss.sum(-1)
+    if normalizing_const is not None:
+        loss = loss / normalizing_const
+    return _reduce(loss, batch_reduction)
+
+
+def cluster_connectivity_prior_loss(K: Tensor, K_mu: Tensor, K_var: Tensor, normalizing_const: Optional[Tensor] = None,
+                                    batch_reduction: str = "mean") -> Tensor:
+    """Gaussian prior on BN-Pool's cluster connectivity matrix: sum (K - K_mu)^2 / (2 K_var), shared among the graphs of
+    ``normalizing_const`` and divided by it (reference utils/losses.py:1446-1517)."""
+    prior_loss = (0.5 * (K - K_mu) ** 2 / K_var).sum()
+    if normalizing_const is not None:
+        bs = normalizing_const.shape[0] if normalizing_const.dim() > 0 else 1
+        prior_loss = prior_loss / bs / normalizing_const
+    return _reduce(prior_loss, batch_reduction)
+
+
+def sparse_bce_reconstruction_loss(link_prob_loigit, true_y, edges_batch_id: Optional[Tensor] = None, batch_size=None,
+                                   batch_reduction: str = "mean"):
+    """(loss, sampled-edge count): binary cross entropy over sampled edges, averaged per graph of ``edges_batch_id``
+    (reference utils/losses.py:1520-1562)."""
+    rec_loss = torch.nn.functional.binary_cross_entropy_with_logits(link_prob_loigit, true_y, reduction="none")
+    if edges_batch_id is None:
+        count = torch.tensor(rec_loss.size(0), device=rec_loss.device, dtype=rec_loss.dtype)
+        return rec_loss.mean(), count
+    summed_loss = _seg_sum(rec_loss, edges_batch_id, batch_size)
+    summed_count = torch.clamp(_seg_sum(torch.ones_like(rec_loss), edges_batch_id, batch_size), min=1)
+    return _reduce(summed_loss / summed_count, batch_reduction), summed_count
+
+
+class _BNPoolRecFn(torch.autograd.Function):
+    """[B] per-graph reconstruction loss of BN-Pool, rec_b = (c sum_{a != 0} bce + sum_{a == 0} bce) / n^2 over the
+    logits L = S K S^T, with a native backward; neither L nor any other [B,N,N] tensor is formed.
+
+    Forward: T = S K (torch.matmul, K / N of the work), one launch over the 32x32 logit tiles that reads the adjacency
+    once, one tail launch.  Backward: two launches recompute the tiles and give P = G S and Q = G^T T for
+    G = d loss / d L (the class weight c is a constant of the counts, saved from the forward); then dS = P K^T + Q and
+    dK = sum_b S^T P as small products.  No float atomics: forward and backward are reproducible bit for bit.  The
+    adjacency and the mask get no gradient."""
+
+    @staticmethod
+    def forward(ctx, S, Kmat, adj, mask):
+        T = torch.matmul(S, Kmat)
+        rec, stats = K.bnpool_rec_fwd(T, S, adj, mask)
+        ctx.save_for_backward(S, Kmat, adj, stats)
+        ctx.mask = mask
+        return rec
+
+    @staticmethod
+    def backward(ctx, g):
+        S, Kmat, adj, stats = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        Kc = S.size(-1)
+        P, Q = K.bnpool_rec_bwd(torch.matmul(S, Kmat), S, adj, ctx.mask, g.to(torch.float32).contiguous(), stats)
+        dS = dK = None
+        if ctx.needs_input_grad[0]:
+            dS = torch.addmm(Q.view(-1, Kc), P.view(-1, Kc), Kmat.t()).view(S.shape)
+        if ctx.needs_input_grad[1]:
+            dK = torch.matmul(S.reshape(-1, Kc).t(), P.view(-1, Kc))
+        return dS, dK, None, None
+
+
+def _bnpool_native(*ts) -> bool:
+    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
+    forms."""
+    return not any(t is not None and t.dtype == torch.float64 for t in ts)
+
+
+def bnpool_rec_loss_terms(S: Tensor, K_: Tensor, adj: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """[B]: BN-Pool's reconstruction loss per graph, ``weighted_bce_reconstruction_loss(S K S^T, adj, mask,
+    balance_links=True, normalizing_const=n^2, ...)`` before the batch reduction.  float32 device operands (``adj``
+    without a gradient, K at most 256 clusters) run on the native route, which never forms the logits; float64 operands,
+    a differentiable ``adj`` and wider K take the composed form.  float32 host tensors raise: there is no CPU fallback."""
+    if (_bnpool_native(S, K_, adj) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad):
+        K.N.require_device(S, K_, adj, mask)
+        if S.size(-1) <= K.bnpool_max_clusters():
+            return _BNPoolRecFn.apply(S, K_, adj, mask)
+    rec_adj = S @ K_ @ S.transpose(-1, -2)
+    n = mask.sum(-1) if mask is not None else torch.tensor(adj.shape[-1], device=adj.device)
+    return _weighted_bce_terms(rec_adj, adj, mask, True) / n ** 2

@@ -610,3 +610,111 @@ def get_assignments(kept_node_indices, edge_index: Optional[Tensor] = None, max_
     out = out[:, out[0].argsort()]
     out[1] = torch.unique(out[1], return_inverse=True)[1]
     return out
+
+
+# ----------------------------------------------------------------------------- negative edge sampling (BN-Pool, unbatched)
+# Pairs enumerated outright while the whole batch has at most this many (sum_g n_g^2); above it candidates are drawn.
+_NEG_DENSE_PAIRS = 1 << 22
+
+
+def _sampler_host_read(t: Tensor) -> list:
+    """The sampler's only way to the host: every wait of a call goes through here (the tests count them)."""
+    return t.tolist()
+
+
+def batched_negative_edge_sampling(edge_index: Tensor, batch, num_neg_samples: Optional[int] = None,
+                                   method: str = "auto", force_undirected: bool = False) -> Tensor:
+    """Node pairs that are not edges, drawn independently inside every graph of a batch (reference utils/ops.py:768-859;
+    this sampler is the project's own and does not reproduce the reference's draws).  ``batch`` is a sorted batch vector.
+
+    Every returned pair lies inside one graph, is no self-loop and is no edge of ``edge_index``; no pair is returned
+    twice.  Per graph at most ``num_neg_samples`` pairs come back -- ``None``: ``min(E_g, N_g^2 - E_g)`` -- and with
+    ``force_undirected`` every pair comes in both directions (neither of which is an edge), the cap rounded down to
+    even.  A graph with no room for negatives returns none.
+
+    The whole batch is handled by tensor ops at once: all ``sum_g N_g^2`` pairs are enumerated while there are at most
+    2^22 of them (or ``method="dense"``), otherwise three candidates per wanted pair are drawn and the duplicates, edges
+    and self-loops among them dropped (fewer than the cap may then come back); a random priority picks the pairs that
+    stay.  Three host waits per call at the most, whatever the number of graphs (and the batch facts of a batch vector
+    that is seen for the first time)."""
+    if method not in ("sparse", "dense", "auto"):
+        raise AssertionError(f"method must be 'sparse', 'dense' or 'auto', got {method!r}")
+    if not isinstance(batch, Tensor):
+        raise NotImplementedError("bipartite negative sampling is not implemented")
+    dev = edge_index.device
+    src, dst = edge_index[0], edge_index[1]
+    if batch.numel() == 0:
+        return edge_index.new_zeros((2, 0))
+    info = batch_info(batch)  # (memoised per batch vector: graph sizes and offsets)
+    B, n_g, ptr = info.num_graphs, info.sizes, info.ptr
+    g_e = batch[src]
+    e_g = torch.zeros(B, dtype=torch.long, device=dev).scatter_add_(0, g_e, torch.ones_like(g_e))
+    n2 = n_g * n_g
+    off2 = torch.zeros(B + 1, dtype=torch.long, device=dev)
+    torch.cumsum(n2, 0, out=off2[1:])
+    if num_neg_samples is None:
+        cap = torch.minimum(e_g, n2 - e_g).clamp_(min=0)
+    else:
+        cap = torch.full_like(n_g, max(int(num_neg_samples), 0))
+    if force_undirected:
+        cap = cap // 2
+    draws = torch.where(n_g > 0, 3 * cap + 8, torch.zeros_like(cap))
+    total_pairs, total_draws = _sampler_host_read(torch.stack([off2[-1], draws.sum()]))
+    edge_key = off2[g_e] + (src - ptr[g_e]) * n_g[g_e] + (dst - ptr[g_e])
+
+    dense = method == "dense" or (method == "auto" and total_pairs <= _NEG_DENSE_PAIRS)
+    graphs = torch.arange(B, device=dev)
+    if dense:
+        g_c = torch.repeat_interleave(graphs, n2, output_size=total_pairs)
+        local = torch.arange(total_pairs, device=dev) - off2[g_c]
+        u, v = local // n_g[g_c].clamp(min=1), local % n_g[g_c].clamp(min=1)
+        key = off2[g_c] + local
+    else:
+        g_c = torch.repeat_interleave(graphs, draws, output_size=total_draws)
+        nn_c = n_g[g_c]
+        r = torch.rand(2, total_draws, device=dev, dtype=torch.float64)
+        u = (r[0] * nn_c).long().minimum(nn_c - 1)
+        v = (r[1] * nn_c).long().minimum(nn_c - 1)
+        if force_undirected:
+            u, v = torch.minimum(u, v), torch.maximum(u, v)
+        key = torch.unique(off2[g_c] + u * nn_c + v)  # (sorted; its length is data dependent: a wait)
+        g_c = torch.searchsorted(off2[1:], key, right=True)
+        local = key - off2[g_c]
+        u, v = local // n_g[g_c].clamp(min=1), local % n_g[g_c].clamp(min=1)
+    ok = (u < v) if force_undirected else (u != v)
+    ok &= n_g[g_c] > 0
+    edge_sorted = torch.sort(edge_key).values
+
+    def is_edge(k):
+        if edge_sorted.numel() == 0:
+            return torch.zeros_like(k, dtype=torch.bool)
+        pos = torch.searchsorted(edge_sorted, k).clamp_(max=edge_sorted.numel() - 1)
+        return edge_sorted[pos] == k
+
+    ok &= ~is_edge(key)
+    if force_undirected:
+        ok &= ~is_edge(off2[g_c] + v * n_g[g_c] + u)
+    # a random order inside every graph, the pairs that cannot be used last; the first cap_g of a graph stay
+    prio = torch.where(ok, torch.rand(key.numel(), device=dev, dtype=torch.float64),
+                       torch.full((), 1.5, device=dev, dtype=torch.float64))
+    order = torch.argsort(g_c.to(torch.float64) * 2 + prio)
+    g_s = g_c[order]
+    first = torch.searchsorted(g_s, graphs)  # where each graph's run starts in the sorted order
+    rank = torch.arange(key.numel(), device=dev) - first[g_s]
+    keep = ok[order] & (rank < cap[g_s])
+    sel = order[keep]  # (boolean indexing: the last wait)
+    row, col = u[sel] + ptr[g_c[sel]], v[sel] + ptr[g_c[sel]]
+    if force_undirected:
+        row, col = torch.cat([row, col]), torch.cat([col, row])
+    return torch.stack([row, col], dim=0)
+
+
+def negative_edge_sampling(edge_index: Tensor, num_nodes=None, num_neg_samples: Optional[int] = None,
+                           method: str = "auto", force_undirected: bool = False) -> Tensor:
+    """:func:`batched_negative_edge_sampling` for ONE graph of ``num_nodes`` nodes (``None``: the largest index + 1;
+    reference utils/ops.py:636-765).  A ``(num_src, num_dst)`` tuple, a bipartite graph, is not implemented."""
+    if isinstance(num_nodes, (tuple, list)):
+        raise NotImplementedError("bipartite negative sampling is not implemented")
+    n = maybe_num_nodes(edge_index, num_nodes)
+    batch = torch.zeros(n, dtype=torch.long, device=edge_index.device)
+    return batched_negative_edge_sampling(edge_index, batch, num_neg_samples, method, force_undirected)
