@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -592,6 +592,56 @@ int tgp_kmis_wsum_f32(const int64_t* row, const int32_t* grp_ptr, const int32_t*
 int tgp_kmis_degree_f32(const int32_t* grp_ptr, const int32_t* grp_perm, const float* w, int64_t num_nodes, float* out,
                         void* stream);
 int tgp_kmis_mis_index_i64(const int64_t* label, const int64_t* index, int64_t num_nodes, int64_t* mis, void* stream);
+
+/* Edge-contraction selection (select/edge_contraction_select.py; csrc/edge_contract.hip; appended under ABI 10044).
+ *
+ * Scores.  tgp_edge_contract_project_f32: p [2 N] with p[i] = <x[i,:], w[:F]> and p[N + i] = <x[i,:], w[F:]>, w [2 F] the
+ * weight row of Linear(2 F, 1), one pass over x [N, F] (row stride ldx).  tgp_edge_contract_raw_f32: raw[e] = p[row[e]] +
+ * p[N + col[e]] + bias[0] (bias on the device, null = 0; an entry with an endpoint outside [0, N) gets 0) -- the
+ * reference's lin(cat(x[row], x[col])) without the E x 2F matrix.  tgp_edge_contract_normalize_f32: out[e] = f(raw)[e] +
+ * add, method 0 = softmax over the entries that share col[e], 1 = tanh, 2 = sigmoid.  The softmax walks the
+ * by-destination index (grp_ptr [N + 1], grp_perm [E] of tgp_assign_index_build over col) in a fixed order without float
+ * atomics, so a target with one incoming entry scores exactly 1 + add; seg [2 N] fp32, 8-byte aligned (each target's
+ * {maximum, sum} pair on return) and hubs [hub_cap + 1] int32, hub_cap >= E / tgp_edge_contract_hub_degree(), are scratch (targets with more
+ * incoming entries than that degree take a workgroup each).  raw and out are different arrays.
+ *
+ * Matching (maximal_matching, `:14-73`).  An entry's priority is the 64-bit key (prio << 32) | position, smaller first:
+ * prio = rank [E] int32 (the entry's rank in a caller's permutation) or, rank null, the bits of score [E] in descending
+ * order, so ties go to the lower position.  E < 2^32 (TGP_ERR_RANGE otherwise).  Outputs: match [E] bytes (1 = matched),
+ * label [N] int64 (label[col[m]] = row[m] for a matched entry m, label[i] = i otherwise: tgp_graclus_relabel_i64 turns it
+ * into consecutive ids), medge [N] int64 (the matched entry of a node, -1 for a singleton).
+ * tgp_edge_contract_graphs: a sorted batch (graph_ptr [B + 1]) whose longest graph has at most max_graph_nodes <=
+ * tgp_edge_contract_max_graph_nodes() nodes, one workgroup per graph, all rounds in LDS (the first
+ * tgp_edge_contract_edge_cache() entries of a graph too), one launch.  words [2] int32: words[0] != 0: declined (bit 0: a
+ * list that is not grouped by graph, an entry between two graphs, a graph longer than declared; bit 1: the round bound)
+ * -- the caller runs the device-wide entries instead; words[1] = rounds of the slowest graph.
+ * Device-wide: tgp_edge_contract_rounds_start (ws of tgp_edge_contract_workspace_bytes(N); clears match, label, medge),
+ * then tgp_edge_contract_rounds any number of times (round_base = rounds launched so far; open_flags[j] = 1 when round j
+ * still met a live entry, so the first 0 says the matching is maximal; two launches per round, and the rounds of a call
+ * behind such a 0 leave without reading the edge list).
+ * tgp_edge_contract_weights_f32: weight[i] = score[medge[i]], 1 for a singleton. */
+int tgp_edge_contract_max_graph_nodes(void);
+int tgp_edge_contract_edge_cache(void);
+int tgp_edge_contract_hub_degree(void);
+size_t tgp_edge_contract_workspace_bytes(int64_t num_nodes);
+int tgp_edge_contract_project_f32(const float* x, int64_t N, int64_t F, int64_t ldx, const float* w, float* p,
+                                  void* stream);
+int tgp_edge_contract_raw_f32(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes, const float* p,
+                              const float* bias, float* raw, void* stream);
+int tgp_edge_contract_normalize_f32(const float* raw, const int64_t* col, int64_t num_edges, int64_t num_nodes, int method,
+                                    float add, const int32_t* grp_ptr, const int32_t* grp_perm, float* seg, int32_t* hubs,
+                                    int64_t hub_cap, float* out, void* stream);
+int tgp_edge_contract_graphs(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes,
+                             const int64_t* graph_ptr, int64_t num_graphs, int max_graph_nodes, const float* score,
+                             const int32_t* rank, uint8_t* match, int64_t* label, int64_t* medge, int32_t* words,
+                             void* stream);
+int tgp_edge_contract_rounds_start(int64_t num_nodes, int64_t num_edges, void* ws, size_t ws_bytes, uint8_t* match,
+                                   int64_t* label, int64_t* medge, void* stream);
+int tgp_edge_contract_rounds(const int64_t* row, const int64_t* col, int64_t num_edges, int64_t num_nodes,
+                             const float* score, const int32_t* rank, void* ws, int64_t round_base, int rounds,
+                             int32_t* open_flags, uint8_t* match, int64_t* label, int64_t* medge, void* stream);
+int tgp_edge_contract_weights_f32(const int64_t* medge, const float* score, int64_t num_nodes, int64_t num_edges,
+                                  float* weight, void* stream);
 
 /* TopkSelect scoring (select/topk_select.py:176, score = (x * w).sum(-1)): out[i] = <x[i,:], w>, one pass over
  * x [N,F] (row stride ldx); and the matching weight gradient out[f] = sum_i g[i] x[i,f] (fixed-order two-level

@@ -150,6 +150,20 @@ SIGNATURES = {
     "tgp_kmis_wsum_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tgp_kmis_degree_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "tgp_kmis_mis_index_i64": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_edge_contract_max_graph_nodes": (_c_int, []),
+    "tgp_edge_contract_edge_cache": (_c_int, []),
+    "tgp_edge_contract_hub_degree": (_c_int, []),
+    "tgp_edge_contract_workspace_bytes": (_c_sz, [_c_i64]),
+    "tgp_edge_contract_project_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_edge_contract_raw_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_edge_contract_normalize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p,
+                                                 _c_i64, _c_p, _c_p]),
+    "tgp_edge_contract_graphs": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                          _c_p, _c_p]),
+    "tgp_edge_contract_rounds_start": (_c_int, [_c_i64, _c_i64, _c_p, _c_sz, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_edge_contract_rounds": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p,
+                                          _c_p, _c_p]),
+    "tgp_edge_contract_weights_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "tgp_graclus_match_rounds": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_p]),
     "tgp_batch_facts_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p]),
     "tgp_batch_facts_sorted_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p, _c_p, _c_p, _c_p,

@@ -2702,6 +2702,203 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
     return res
 
 
+# ------------------------------------------------------------------------- edge contraction (csrc/edge_contract.hip)
+EC_METHODS = {"softmax": 0, "tanh": 1, "sigmoid": 2}
+
+
+def edge_contract_raw(x: Tensor, edge_index: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """raw[e] = x[row[e]].w[:F] + x[col[e]].w[F:] + b, float32 [E]: the reference's ``lin(cat([x[row], x[col]]))``
+    (select/edge_contraction_select.py:217-218) as two per-node projections from one pass over ``x`` plus two gathered
+    scalars per entry; the E x 2F matrix is never formed.  ``weight``: the 2F weights of ``Linear(2F, 1)``."""
+    dev = N.require_device(x, edge_index, weight, bias)
+    if x.dim() != 2:
+        raise ValueError(f"edge_contract_raw expects x of shape [N, F], got {tuple(x.shape)}")
+    x, w = _rows_f32(x), N.f32c(weight.reshape(-1))
+    n, F = x.size(0), x.size(1)
+    if w.numel() != 2 * F:
+        raise ValueError(f"weight must have 2 * F = {2 * F} entries, got {w.numel()}")
+    b = None if bias is None else N.f32c(bias.reshape(-1))
+    row, col = _edge_rows(edge_index)
+    E, L, st = row.numel(), N.lib(), N.stream_ptr(dev)
+    p = torch.empty(2 * max(n, 1), dtype=torch.float32, device=dev)
+    raw = torch.empty(E, dtype=torch.float32, device=dev)
+    N.check(L.tgp_edge_contract_project_f32(N.ptr(x), n, F, x.stride(0) if n else F, N.ptr(w), N.ptr(p), st),
+            "tgp_edge_contract_project_f32")
+    N.check(L.tgp_edge_contract_raw_f32(N.ptr(row), N.ptr(col), E, n, N.ptr(p), N.ptr(b), N.ptr(raw), st),
+            "tgp_edge_contract_raw_f32")
+    return raw
+
+
+def edge_contract_normalize(raw: Tensor, edge_index: Optional[Tensor], num_nodes: Optional[int],
+                            method: str = "softmax", add_to_edge_score: float = 0.0) -> Tensor:
+    """f(raw) + add_to_edge_score, float32 [E]; f = "softmax" over the entries that share ``col[e]``, "tanh" or
+    "sigmoid" (select/edge_contraction_select.py:175-200, :221; the last two need neither ``edge_index`` nor
+    ``num_nodes``).  The softmax takes each target's maximum and sum in the order of the by-destination index, without
+    float atomics: the same bits on every call, and exactly ``1 + add_to_edge_score`` on a target with one incoming
+    entry."""
+    dev = N.require_device(raw, edge_index)
+    if method not in EC_METHODS:
+        raise ValueError(f"method must be one of {sorted(EC_METHODS)}, got {method!r}")
+    raw = N.f32c(raw.reshape(-1))
+    E, L, st = raw.numel(), N.lib(), N.stream_ptr(dev)
+    out = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return out
+    n, col, grp, seg, hubs, cap = 0, None, None, None, None, 0
+    if method == "softmax":
+        n = int(num_nodes)
+        _, col = _edge_rows(edge_index)
+        if col.numel() != E:
+            raise ValueError(f"raw must have one entry per edge ({col.numel()}), got {E}")
+        grp = _dest_groups(edge_index, n)
+        seg = torch.empty(2 * max(n, 1), dtype=torch.float32, device=dev)
+        cap = E // int(L.tgp_edge_contract_hub_degree()) + 1
+        hubs = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+    N.check(L.tgp_edge_contract_normalize_f32(N.ptr(raw), N.ptr(col), E, n, EC_METHODS[method], float(add_to_edge_score),
+                                              N.ptr(grp.row_ptr) if grp else None, N.ptr(grp.perm) if grp else None,
+                                              N.ptr(seg), N.ptr(hubs), cap, N.ptr(out), st),
+            "tgp_edge_contract_normalize_f32")
+    return out
+
+
+def edge_contract_scores(x: Tensor, edge_index: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
+                         method: str = "softmax", add_to_edge_score: float = 0.5) -> Tensor:
+    """The edge scores of EdgeContractionSelect without dropout (select/edge_contraction_select.py:217-221):
+    :func:`edge_contract_raw` then :func:`edge_contract_normalize`."""
+    raw = edge_contract_raw(x, edge_index, weight, bias)
+    return edge_contract_normalize(raw, edge_index, x.size(0), method, add_to_edge_score)
+
+
+class EdgeContractResult:
+    """What one edge-contraction selection leaves: ``index`` [2, N] (row 0 = 0..N-1, row 1 = cluster id), ``k`` clusters,
+    ``match`` (positions of the matched entries, ascending; compacted on first access), ``matched`` uint8 [E] (its flags),
+    ``medge`` [N] (the matched entry of every node, -1 for a singleton), ``weight`` [N] (the matched entry's score for
+    both members, 1 for a singleton; None for an explicit permutation), ``route`` ("graphs" / "rounds") and ``rounds``
+    (rounds that still met a live entry)."""
+    __slots__ = ("index", "k", "matched", "medge", "weight", "route", "rounds", "_match")
+
+    @property
+    def match(self) -> Tensor:
+        if self._match is None:
+            m = self.matched
+            got = mask_index(m) if 0 < m.numel() < (1 << 31) else None
+            self._match = got[0][0] if got is not None else m.nonzero().view(-1)
+        return self._match
+
+
+def edge_contract_route(num_nodes: int, num_edges: int, graph_ptr: Optional[Tensor],
+                        max_graph_nodes: Optional[int]) -> str:
+    """The route a matching takes, from what the host already knows: "graphs" (one workgroup per graph) for a sorted
+    batch whose longest graph fits one workgroup, "rounds" (device-wide launches per round) for everything else."""
+    if (graph_ptr is not None and max_graph_nodes is not None and graph_ptr.numel() >= 2 and num_nodes > 0
+            and num_edges > 0 and 0 < max_graph_nodes <= N.lib().tgp_edge_contract_max_graph_nodes()):
+        return "graphs"
+    return "rounds"
+
+
+def edge_contract_select(edge_index: Tensor, num_nodes: int, score: Optional[Tensor] = None,
+                         graph_ptr: Optional[Tensor] = None, max_graph_nodes: Optional[int] = None,
+                         route: Optional[str] = None, perm: Optional[Tensor] = None) -> EdgeContractResult:
+    """Maximal matching + clusters (select/edge_contraction_select.py:14-111, :223-236) by entry priority: ``perm`` (a
+    permutation of the entries, first = highest priority), else descending ``score`` with ties to the lower position, else
+    the list order.  Entries are directed and distinct: duplicates carry different ranks, a self-loop matches its node
+    with itself.  ``cluster[col[m]] = row[m]`` for a matched entry ``m`` (the source represents the pair), ids are the
+    rank of the representative among all representatives.  ``graph_ptr`` / ``max_graph_nodes``: offsets and longest graph
+    of a sorted batch.  ``route``: None picks (``edge_contract_route``); "rounds" forces the device-wide kernels; a
+    "graphs" call the kernel declines (an entry between two graphs, a list not grouped by graph) goes on device-wide.
+    One host wait per call on the per-graph route (status, rounds and cluster count together); one per batch of rounds
+    device-wide plus one for the count."""
+    dev = N.require_device(edge_index, score, perm)
+    row, col = _edge_rows(edge_index)
+    E, n = row.numel(), int(num_nodes)
+    L, st = N.lib(), N.stream_ptr(dev)
+    if E >= (1 << 32):
+        raise N.TgpNativeError(f"edge_contract_select: {E} entries exceed the 32-bit entry positions of the keys")
+    res = EdgeContractResult()
+    res.weight, res.rounds, res._match = None, 0, None
+    if n == 0:
+        res.index = torch.empty(2, 0, dtype=torch.int64, device=dev)
+        res.k, res.route = 0, "rounds"
+        res.matched = torch.zeros(E, dtype=torch.uint8, device=dev)
+        res.medge = torch.empty(0, dtype=torch.int64, device=dev)
+        res.weight = None if score is None else torch.empty(0, dtype=torch.float32, device=dev)
+        return res
+    if n > L.tgp_graclus_relabel_max_nodes():
+        raise N.TgpNativeError(f"edge_contract_select: {n} nodes exceed the relabelling kernels' "
+                               f"{L.tgp_graclus_relabel_max_nodes()}")
+    rank = None
+    if perm is not None:
+        if perm.numel() != E:
+            raise ValueError(f"perm must have one entry per edge ({E}), got {perm.numel()}")
+        rank = torch.empty(E, dtype=torch.int32, device=dev)
+        rank[perm.reshape(-1)] = torch.arange(E, dtype=torch.int32, device=dev)
+        score = None
+    elif score is None:
+        rank = torch.arange(E, dtype=torch.int32, device=dev)
+    else:
+        score = N.f32c(score.reshape(-1))
+        if score.numel() != E:
+            raise ValueError(f"score must have one entry per edge ({E}), got {score.numel()}")
+    want = edge_contract_route(n, E, graph_ptr, max_graph_nodes)
+    if route is not None:
+        if route not in ("graphs", "rounds"):
+            raise ValueError(f"route must be 'graphs' or 'rounds', got {route!r}")
+        if route == "graphs" and want != "graphs":
+            raise ValueError("the per-graph route needs a sorted batch whose longest graph fits one workgroup")
+        want = route
+    matched = torch.empty(E, dtype=torch.uint8, device=dev)
+    label = torch.empty(n, dtype=torch.int64, device=dev)
+    medge = torch.empty(n, dtype=torch.int64, device=dev)
+    index = torch.empty(2, n, dtype=torch.int64, device=dev)
+    weight = None if score is None else torch.empty(n, dtype=torch.float32, device=dev)
+    words = torch.empty(4, dtype=torch.int32, device=dev)  # [status, rounds, K (int64)]
+    rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
+
+    def finish():
+        # representatives (label[i] == i) -> consecutive ids: flags + exclusive scan, no sort, no torch.unique
+        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
+                                          None, None, None, st), "tgp_graclus_relabel_i64")
+        if weight is not None:
+            N.check(L.tgp_edge_contract_weights_f32(N.ptr(medge), N.ptr(score), n, E, N.ptr(weight), st),
+                    "tgp_edge_contract_weights_f32")
+
+    res.index, res.matched, res.medge, res.weight = index, matched, medge, weight
+    if want == "graphs":
+        gp = N.i64c(graph_ptr)
+        N.check(L.tgp_edge_contract_graphs(N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1, int(max_graph_nodes),
+                                           N.ptr(score), N.ptr(rank), N.ptr(matched), N.ptr(label), N.ptr(medge),
+                                           N.ptr(words), st), "tgp_edge_contract_graphs")
+        finish()
+        got = words.tolist()  # the one host wait: status, rounds and K together
+        if got[0] == 0:
+            res.k, res.route, res.rounds = int(got[2]), "graphs", int(got[1])
+            return res
+        if got[0] & 2:
+            raise N.TgpNativeError("tgp_edge_contract_graphs: a graph did not finish within its round bound")
+        if route == "graphs":
+            raise N.TgpNativeError("tgp_edge_contract_graphs declined: the edge list is not grouped by graph or an "
+                                   "entry joins two graphs")
+    ws = N.workspace(L.tgp_edge_contract_workspace_bytes(n), dev)
+    N.check(L.tgp_edge_contract_rounds_start(n, E, N.ptr(ws), ws.numel(), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
+            "tgp_edge_contract_rounds_start")
+    done, step, live = 0, 4, None
+    while live is None:
+        if done >= n + 4:  # a round retires a node while a live entry exists: n rounds is a hard cap
+            raise N.TgpNativeError("tgp_edge_contract_rounds: the matching is not maximal after num_nodes rounds")
+        flags = torch.empty(step, dtype=torch.int32, device=dev)
+        N.check(L.tgp_edge_contract_rounds(N.ptr(row), N.ptr(col), E, n, N.ptr(score), N.ptr(rank), N.ptr(ws), done, step,
+                                           N.ptr(flags), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
+                "tgp_edge_contract_rounds")
+        got = flags.tolist()  # one host wait per batch of rounds
+        if 0 in got:
+            live = done + got.index(0)
+        done += step
+        step = min(2 * step, 256)  # a long tail means chain-like structure: more rounds per host wait
+    finish()
+    res.k, res.route, res.rounds = int(words.tolist()[2]), "rounds", live
+    return res
+
+
 def _rows_f32(x: Tensor) -> Tensor:
     x = x.to(torch.float32) if x.dtype != torch.float32 else x
     return x if x.stride(1) == 1 else x.contiguous()

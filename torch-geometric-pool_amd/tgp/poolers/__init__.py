@@ -1,11 +1,11 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
-``HOSCPooling`` and ``BNPool`` are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` aliases
-are not registered yet.
+``HOSCPooling``, ``BNPool`` and ``EdgeContractionPooling`` are built and exported as classes; their ``dmon`` / ``acc`` /
+``hosc`` / ``bnpool`` / ``edgepool`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from .. import kernels as K
 from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
-from ..select import DPSelect, GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
+from ..select import DPSelect, EdgeContractionSelect, GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
 from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling
 from ..utils.ops import batch_info, batched_negative_edge_sampling, is_dense_adj, negative_edge_sampling
 from ..utils.losses import (
@@ -277,6 +277,43 @@ class KMISPooling(BasePrecoarseningMixin, SRCPooling):
 
     def extra_repr_args(self) -> dict:
         return {"cached": self.cached}
+
+
+class EdgeContractionPooling(SRCPooling):
+    r"""Edge-contraction pooling (EdgePool: Diehl et al. 2019; Diehl 2019; Landolfi 2022; reference
+    poolers/edge_contraction.py:15-185): every directed edge entry is scored from its two endpoint features, a maximal
+    matching chosen greedily by descending score is contracted, features are summed per cluster weighted by the matched
+    entry's score, edges are coalesced.  ``EdgeContractionSelect`` + ``BaseReduce`` + ``SparseConnect`` + ``BaseLift``.
+
+    Ties between equal scores go to the lower edge position and the selection is a pure function of the inputs (see
+    ``EdgeContractionSelect``)."""
+
+    def __init__(self, in_channels: int, edge_score_method: Optional[Callable] = None, dropout: Optional[float] = 0.0,
+                 add_to_edge_score: float = 0.5, lift: str = "precomputed", s_inv_op: str = "transpose",
+                 connect_red_op: str = "sum", lift_red_op: str = "sum", remove_self_loops: bool = True,
+                 degree_norm: bool = False, edge_weight_norm: bool = False):
+        super().__init__(
+            selector=EdgeContractionSelect(in_channels=in_channels, edge_score_method=edge_score_method, dropout=dropout,
+                                           add_to_edge_score=add_to_edge_score, s_inv_op=s_inv_op),
+            reducer=BaseReduce(),
+            lifter=BaseLift(matrix_op=lift, reduce_op=lift_red_op),
+            connector=SparseConnect(reduce_op=connect_red_op, remove_self_loops=remove_self_loops,
+                                    degree_norm=degree_norm, edge_weight_norm=edge_weight_norm))
+
+    def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None,
+                so: Optional[SelectOutput] = None, batch: Optional[Tensor] = None, lifting: bool = False,
+                **kwargs):
+        if lifting:
+            return self.lift(x_pool=x, so=so)
+        edge_index, edge_weight = connectivity_to_edge_index(adj, edge_weight)
+        so = self.select(x=x, edge_index=edge_index, batch=batch)
+        fused = self.reduce_connect(x, edge_index, edge_weight, so, batch)  # batches of small graphs: ONE launch
+        if fused is not None:
+            x_pool, batch_pool, ei, ew = fused
+            return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
+        x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch)
+        ei, ew = self.connect(edge_index=edge_index, so=so, edge_weight=edge_weight, batch_pooled=batch_pool)
+        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
 
 
 # =============================================================================== dense poolers
@@ -1338,8 +1375,8 @@ class BNPool(_DenseMLPPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc" and "bnpool" are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool" and "edgepool" (EdgeContractionPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

@@ -980,6 +980,248 @@ class KMISSelect(Select):
                 f"s_inv_op={self.s_inv_op})")
 
 
+# =============================================================================== edge contraction
+def _ec_norm_backward(g: Tensor, e: Tensor, edge_index: Optional[Tensor], num_nodes: Optional[int], method: str,
+                      add: float) -> Tensor:
+    """Gradient of ``f(raw) + add`` with respect to ``raw`` from the forward's result ``e`` (torch ops on the device)."""
+    s = e - add if add != 0.0 else e
+    if method == "tanh":
+        return g * (1.0 - s * s)
+    if method == "sigmoid":
+        return g * s * (1.0 - s)
+    gs = g * s  # softmax: s * (g - sum over the target's segment of g * s)
+    col = edge_index[1]
+    seg = torch.zeros(num_nodes, dtype=gs.dtype, device=gs.device).index_add_(0, col, gs)
+    return gs - s * seg[col]
+
+
+def _ec_raw_backward(g_raw: Tensor, x: Tensor, weight: Tensor, edge_index: Tensor, needs):
+    """Gradients of ``raw[e] = x[row[e]].w1 + x[col[e]].w2 + b`` with respect to x, the weight row and the bias: the
+    per-node sums of ``g_raw`` by source and by target (torch ``index_add_``), then one outer product for x and the
+    project's ``weighted_colsum`` (one pass over x) per weight half."""
+    from .. import kernels
+    n, F = x.size(0), x.size(1)
+    row, col = edge_index[0], edge_index[1]
+    g1 = torch.zeros(n, dtype=torch.float32, device=x.device).index_add_(0, row, g_raw)
+    g2 = torch.zeros(n, dtype=torch.float32, device=x.device).index_add_(0, col, g_raw)
+    w = weight.reshape(-1).to(torch.float32)
+    gx = gw = gb = None
+    if needs[0]:
+        gx = (g1.view(-1, 1) * w[:F].view(1, -1)).addcmul_(g2.view(-1, 1), w[F:].view(1, -1)).to(x.dtype)
+    if needs[1]:
+        xf = x.detach()
+        gw = torch.cat([kernels.weighted_colsum(xf, g1), kernels.weighted_colsum(xf, g2)]).view_as(weight).to(weight.dtype)
+    if needs[2]:
+        gb = g_raw.sum().view(1)
+    return gx, gw, gb
+
+
+class _EdgeRawFn(torch.autograd.Function):
+    """raw edge scores: native forward (kernels.edge_contract_raw), composed backward (``_ec_raw_backward``)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, edge_index):
+        from .. import kernels
+        ctx.save_for_backward(x, weight, edge_index)
+        ctx.has_bias = bias is not None
+        return kernels.edge_contract_raw(x, edge_index, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, edge_index = ctx.saved_tensors
+        needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
+        gx, gw, gb = _ec_raw_backward(g.contiguous(), x, weight, edge_index, needs)
+        return gx, gw, gb, None
+
+
+class _EdgeNormFn(torch.autograd.Function):
+    """f(raw) + add for the three built-in methods: native forward, composed backward."""
+
+    @staticmethod
+    def forward(ctx, raw, edge_index, num_nodes, method, add):
+        from .. import kernels
+        e = kernels.edge_contract_normalize(raw, edge_index, num_nodes, method, add)
+        ctx.save_for_backward(e, edge_index)
+        ctx.args = (num_nodes, method, add)
+        return e
+
+    @staticmethod
+    def backward(ctx, g):
+        e, edge_index = ctx.saved_tensors
+        return _ec_norm_backward(g, e, edge_index, *ctx.args), None, None, None, None
+
+
+class _EdgeScoreFn(torch.autograd.Function):
+    """The whole edge score without dropout as ONE autograd node: native forward (projection, raw scores,
+    normalisation), backward to x, the weight row and the bias composed of torch ops and ``weighted_colsum``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, edge_index, method, add):
+        from .. import kernels
+        e = kernels.edge_contract_scores(x, edge_index, weight, bias, method, add)
+        ctx.save_for_backward(x, weight, edge_index, e)
+        ctx.has_bias = bias is not None
+        ctx.args = (x.size(0), method, add)
+        return e
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, edge_index, e = ctx.saved_tensors
+        g_raw = _ec_norm_backward(g, e, edge_index, *ctx.args)
+        needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
+        gx, gw, gb = _ec_raw_backward(g_raw, x, weight, edge_index, needs)
+        return gx, gw, gb, None, None, None
+
+
+class _EdgeWeightFn(torch.autograd.Function):
+    """weight[i] = e[medge[i]] (1 for a singleton), the values the native kernel already wrote; the backward hands each
+    matched entry the gradients of its two members and nothing to any other entry."""
+
+    @staticmethod
+    def forward(ctx, e, medge, weight):
+        ctx.save_for_backward(medge)
+        ctx.num_edges = e.numel()
+        return weight.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        medge, = ctx.saved_tensors
+        ge = torch.zeros(ctx.num_edges, dtype=g.dtype, device=g.device)
+        if ctx.num_edges:
+            ge.index_add_(0, medge.clamp(min=0), g * (medge >= 0).to(g.dtype))
+        return ge, None, None
+
+
+def _ec_explicit(edge_index, num_nodes: Optional[int], perm: Optional[Tensor]):
+    from .. import kernels
+    edge_index, _ = connectivity_to_edge_index(edge_index, None)
+    n = num_nodes if num_nodes is not None else maybe_num_nodes(edge_index)
+    return edge_index, n, kernels.edge_contract_select(edge_index, n, perm=perm)
+
+
+def maximal_matching(edge_index, num_nodes: Optional[int] = None, perm: Optional[Tensor] = None) -> Tensor:
+    """bool [E]: a maximal matching over the directed entries of ``edge_index`` (no two matched entries share a node,
+    every entry touches a matched node), chosen greedily in the order of ``perm`` (list order when None) by Blelloch's
+    rounds (reference select/edge_contraction_select.py:14-73)."""
+    _, _, res = _ec_explicit(edge_index, num_nodes, perm)
+    return res.matched.to(torch.bool)
+
+
+def maximal_matching_cluster(edge_index, num_nodes: Optional[int] = None, perm: Optional[Tensor] = None):
+    """``(match bool [E], cluster int64 [N])``: the matching of ``maximal_matching`` and the clustering in which a
+    matched entry's two nodes share a cluster represented by its SOURCE and every other node is alone; ids are the rank of
+    the representative among all representatives (reference select/edge_contraction_select.py:76-111)."""
+    _, _, res = _ec_explicit(edge_index, num_nodes, perm)
+    return res.matched.to(torch.bool), res.index[1]
+
+
+class EdgeContractionSelect(Select):
+    r"""Edge-contraction selection (Diehl et al. 2019; Diehl 2019; Landolfi 2022; reference
+    select/edge_contraction_select.py:114-249): score every directed edge entry with a linear layer on the two endpoint
+    features, normalise (softmax over the entries that share a target, tanh or sigmoid), add ``add_to_edge_score``,
+    contract a maximal matching chosen greedily by descending score.  The matched entry's score is the weight of both
+    members of its cluster; singletons weigh 1.
+
+    ``edge_score_method``: one of the three ``compute_edge_score_*`` static methods (native path), or any callable
+    ``f(raw, edge_index, num_nodes)``, which is called on the natively computed raw scores and feeds the native matching.
+
+    What this port fixes where the reference leaves it open:
+
+    * **Ties go to the lower edge position** (a stable descending sort; NaN first, ``-0`` ties with ``+0``).  The
+      reference's ``argsort`` is not stable; wherever its order is tie-free the results are the same, indices bit for bit.
+    * The scores are a pure function of the inputs (no float atomics); a target with one incoming entry scores exactly
+      ``1 + add_to_edge_score`` under softmax.
+    * Scores are float32 whatever ``x.dtype`` is.
+    * Device tensors only: host inputs raise ``TgpNativeError`` (no CPU fallback).
+    """
+
+    def __init__(self, in_channels: int, edge_score_method: Optional[Callable] = None, dropout: Optional[float] = 0.0,
+                 add_to_edge_score: float = 0.5, s_inv_op: str = "transpose"):
+        super().__init__()
+        self.in_channels = in_channels
+        self.s_inv_op = s_inv_op
+        if edge_score_method is None:
+            edge_score_method = self.compute_edge_score_softmax
+        self.compute_edge_score = edge_score_method
+        self.add_to_edge_score = add_to_edge_score
+        self.dropout = dropout
+        self.lin = torch.nn.Linear(2 * in_channels, 1)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.lin.reset_parameters()
+
+    @staticmethod
+    def _normalized(raw: Tensor, edge_index: Optional[Tensor], num_nodes: Optional[int], method: str) -> Tensor:
+        from .. import _native as N
+        N.require_device(raw, edge_index)  # host tensors: no CPU fallback
+        return _EdgeNormFn.apply(raw, edge_index, num_nodes, method, 0.0)
+
+    @staticmethod
+    def compute_edge_score_softmax(raw_edge_score: Tensor, edge_index: Tensor, num_nodes: int) -> Tensor:
+        """Softmax of the raw scores over the entries that share a target node."""
+        return EdgeContractionSelect._normalized(raw_edge_score, edge_index, num_nodes, "softmax")
+
+    @staticmethod
+    def compute_edge_score_tanh(raw_edge_score: Tensor, edge_index: Optional[Tensor] = None,
+                                num_nodes: Optional[int] = None) -> Tensor:
+        """tanh of the raw scores."""
+        return EdgeContractionSelect._normalized(raw_edge_score, edge_index, num_nodes, "tanh")
+
+    @staticmethod
+    def compute_edge_score_sigmoid(raw_edge_score: Tensor, edge_index: Optional[Tensor] = None,
+                                   num_nodes: Optional[int] = None) -> Tensor:
+        """Sigmoid of the raw scores."""
+        return EdgeContractionSelect._normalized(raw_edge_score, edge_index, num_nodes, "sigmoid")
+
+    def _builtin_method(self) -> Optional[str]:
+        f = self.compute_edge_score
+        for name in ("softmax", "tanh", "sigmoid"):
+            if f is getattr(EdgeContractionSelect, "compute_edge_score_" + name):
+                return name
+        return None
+
+    def edge_scores(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        """The normalised scores ``e`` of every entry, float32 [E] (reference :217-221)."""
+        n = x.size(0)
+        method = self._builtin_method()
+        add = float(self.add_to_edge_score)
+        drop = self.training and self.dropout is not None and self.dropout > 0
+        if method is not None and not drop:
+            return _EdgeScoreFn.apply(x, self.lin.weight, self.lin.bias, edge_index, method, add)
+        raw = _EdgeRawFn.apply(x, self.lin.weight, self.lin.bias, edge_index)
+        if drop:
+            raw = torch.nn.functional.dropout(raw, p=self.dropout, training=True)
+        if method is not None:
+            return _EdgeNormFn.apply(raw, edge_index, n, method, add)
+        return self.compute_edge_score(raw, edge_index, n) + self.add_to_edge_score
+
+    def forward(self, x: Tensor, edge_index=None, batch: Optional[Tensor] = None, **kwargs) -> SelectOutput:
+        from .. import kernels, _native as N
+        edge_index, _ = connectivity_to_edge_index(edge_index, None)
+        N.require_device(x, edge_index)  # host tensors: no CPU fallback
+        n = x.size(0)
+        e = self.edge_scores(x, edge_index)
+        gptr, gmax = _kmis_batch_facts(batch, n)
+        with torch.no_grad():
+            res = kernels.edge_contract_select(edge_index, n, e.detach(), graph_ptr=gptr, max_graph_nodes=gmax)
+        values = _EdgeWeightFn.apply(e, res.medge, res.weight) if e.requires_grad else res.weight
+        s = torch.sparse_coo_tensor(res.index, values, size=(n, res.k), is_coalesced=True)
+        so = SelectOutput(s=s, s_inv_op=self.s_inv_op)
+        so._hold_values(values)
+        so.__dict__["_identity_nodes"] = True  # row 0 of the indices is 0..N-1
+        so.__dict__["_no_empty_cluster"] = True  # every id is the rank of a representative, which is in its own cluster
+        so.__dict__["_ec_route"] = res.route
+        so.__dict__["_ec_rounds"] = res.rounds
+        so.__dict__["_ec_result"] = res
+        return so
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__}(in_channels={self.in_channels}, "
+                f"edge_score_method={self.compute_edge_score.__name__}, dropout={self.dropout}, "
+                f"add_to_edge_score={self.add_to_edge_score}, s_inv_op={self.s_inv_op})")
+
+
 # =============================================================================== NDP
 import os as _os
 
@@ -1275,4 +1517,5 @@ class NDPSelect(Select):
 
 __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
+           "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster",
            "degree_scorer"]
