@@ -11,7 +11,7 @@
 // otherwise) on unsigned keys whose order is the float order.  No float atomics: every sum has a fixed order, so two calls
 // on the same inputs return the same bits.  Where several nodes hold the quantile value, the LOWEST node index is the one
 // reported (and the one that receives the quantile's gradient).
-#include "common.h"
+#include "loss_common.h"
 
 namespace tgp {
 namespace {
@@ -21,7 +21,6 @@ constexpr int AC_COLS = 32;          // columns of S per pass / workgroup of the
 constexpr int AC_RG = 8;             // row groups of a 256-thread workgroup over AC_COLS columns
 constexpr int AC_TV_ROWS = 16;       // rows of A per workgroup of the dense forward (4 per wave)
 constexpr int AC_BWD_ROWS = 32;      // rows of dS per workgroup of the dense backward (8 per wave)
-typedef float ac_f32x4 __attribute__((ext_vector_type(4)));
 
 // unsigned key with the order of the floats: -0 and +0 are one value, NaN is the largest (as a descending sort has it)
 __device__ __forceinline__ uint32_t ac_key(float v) {
@@ -34,20 +33,7 @@ __device__ __forceinline__ float ac_unkey(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// rows of S that graph b owns: padded (ptr NULL: b N .. + graph size or N) or un-padded (ptr[b] .. ptr[b+1])
-__device__ __forceinline__ void ac_range(int b, int N, const int64_t* sizes, const int64_t* ptr, int64_t& start,
-                                         int& count) {
-  if (ptr) {
-    start = ptr[b];
-    count = static_cast<int>(ptr[b + 1] - start);
-  } else {
-    start = static_cast<int64_t>(b) * N;
-    int64_t c = sizes ? sizes[b] : N;
-    c = c < 0 ? 0 : (c > N ? N : c);
-    count = static_cast<int>(c);
-  }
-}
-
+// NOT block_sum<256> (loss_common.h): the waves are added (sh0 + sh1) + (sh2 + sh3), a different rounding
 __device__ __forceinline__ float ac_block_sum(float v, float* sh) {  // 256 threads, sh: 4 floats; fixed order
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(256) void acc_tv_dense_kernel(const float* __restri
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int64_t start;
   int count;
-  ac_range(b, N, sizes, nullptr, start, count);
+  graph_rows(b, N, sizes, nullptr, start, count);
   const float* Ab = A + static_cast<int64_t>(b) * N * N;
   const float* Sb = S + start * K;
   const int i0 = rb * AC_TV_ROWS + w * 4;
@@ -100,9 +86,9 @@ __global__ __launch_bounds__(256) void acc_tv_dense_kernel(const float* __restri
         const int i = i0 + r;
         if (VEC) {
           const int j = j0 + 4 * lane;
-          ac_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+          f32x4 v = {0.f, 0.f, 0.f, 0.f};
           if (i < count && j < count)  // (N % 4 == 0: the four columns are inside the row)
-            v = __builtin_nontemporal_load(reinterpret_cast<const ac_f32x4*>(Ab + static_cast<int64_t>(i) * N + j));
+            v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(Ab + static_cast<int64_t>(i) * N + j));
           a[r][0] = v.x;
           a[r][1] = j + 1 < count ? v.y : 0.f;
           a[r][2] = j + 2 < count ? v.z : 0.f;
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(256) void acc_tv_dense_bwd_kernel(const float* __re
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int64_t start;
   int count;
-  ac_range(b, N, sizes, nullptr, start, count);
+  graph_rows(b, N, sizes, nullptr, start, count);
   const float* Ab = A + static_cast<int64_t>(b) * N * N;
   const float* Sb = S + start * K;
   const int e = ecnt[b] > 1 ? ecnt[b] : 1;
@@ -340,7 +326,7 @@ __global__ __launch_bounds__(256) void acc_select_count_kernel(const float* __re
   const int c = threadIdx.x & (AC_COLS - 1), rg = threadIdx.x / AC_COLS;
   int64_t start;
   int count;
-  ac_range(b, N, sizes, ptr, start, count);
+  graph_rows(b, N, sizes, ptr, start, count);
   if (count > AC_SMALL_NODES) count = AC_SMALL_NODES;  // (the host checks; never index LDS beyond the tile)
   const int n = ac_real_rows(count, mask, start, &sh_n);
   if (threadIdx.x < AC_SMALL_NODES)
@@ -424,7 +410,7 @@ __global__ __launch_bounds__(256) void acc_select_radix_kernel(const float* __re
   const int k = blockIdx.x * AC_COLS + c;
   int64_t start;
   int count;
-  ac_range(b, N, sizes, ptr, start, count);
+  graph_rows(b, N, sizes, ptr, start, count);
   const int n = ac_real_rows(count, mask, start, &sh_n);
   if (threadIdx.x == 0 && blockIdx.x == 0) nreal[b] = n;
   const int64_t o = static_cast<int64_t>(b) * K + k;
@@ -580,7 +566,7 @@ __global__ __launch_bounds__(256) void acc_asym_bwd_kernel(const float* __restri
     if (b >= 0 && b < B && kq > 1 && nreal[b] > 0) {
       int64_t start;
       int count;
-      ac_range(static_cast<int>(b), N, sizes, ptr, start, count);
+      graph_rows(static_cast<int>(b), N, sizes, ptr, start, count);
       const int64_t i = row - start;
       if (i >= 0 && i < count && (!mask || mask[row])) {
         const float n = static_cast<float>(nreal[b]);

@@ -8,77 +8,10 @@
 // The per-graph K-vectors ca = S^T d and cs = S^T 1 are reduced in two stages: every workgroup of the partial pass
 // writes the sums over its 64 rows, the tail adds the partials of a graph in a fixed order (no float atomics).
 // trace(S^T A S) comes from the raw Connect product (or, for an edge list, from a per-graph vector).
-#include "common.h"
+#include "loss_common.h"
 
 namespace tgp {
 namespace {
-
-constexpr int DM_ROWS = 64;  // rows of one graph per workgroup of the partial pass
-typedef float dm_f32x4 __attribute__((ext_vector_type(4)));
-
-template <int T>
-__device__ __forceinline__ float dm_block_sum(float v, float* sh) {  // sh: T / 64 floats; fixed order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int w = 0; w < T / 64; ++w) t += sh[w];
-  __syncthreads();  // sh is reused by the next call
-  return t;
-}
-
-// NV sums behind ONE pair of barriers (sh: NV * T / 64 floats); each sum in the order dm_block_sum adds it
-template <int T, int NV>
-__device__ __forceinline__ void dm_block_sums(float (&v)[NV], float* sh) {
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) sh[q * (T / 64) + (threadIdx.x >> 6)] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) t += sh[q * (T / 64) + w];
-    v[q] = t;
-  }
-  __syncthreads();
-}
-
-// G lanes per node row: d_i = sum_j A[b,i,j] on real rows (mask, graph size), 0 elsewhere.  The pass over A is
-// cut_rows_kernel's (losses.hip) without the S row norms.
-template <int G>
-__global__ __launch_bounds__(256) void dmon_deg_kernel(const float* __restrict__ A, int64_t rows, int N,
-                                                       const int64_t* __restrict__ sizes,
-                                                       const uint8_t* __restrict__ mask, float* __restrict__ deg) {
-  const int sub = threadIdx.x % G;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * (256 / G) + threadIdx.x / G;
-  float d = 0.f;
-  const bool real = row < rows && (!sizes || row % N < sizes[row / N]) && (!mask || mask[row]);
-  if (real) {
-    const float* a = A + row * N;
-    if ((N & 3) == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0) {
-      const dm_f32x4* a4 = reinterpret_cast<const dm_f32x4*>(a);
-      for (int j = sub; j < N / 4; j += G) {
-        const dm_f32x4 v = __builtin_nontemporal_load(a4 + j);
-        d += (v.x + v.y) + (v.z + v.w);
-      }
-    } else {
-      for (int j = sub; j < N; j += G) d += a[j];
-    }
-  }
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-  if (row < rows && sub == 0) deg[row] = d;
-}
 
 // One workgroup per (64 columns, 64 rows, graph): part[b][split] = [ca (K) | cs (K) | sum of d | node count].
 // Graph b owns rows start .. start + count of S and deg: padded (ptr == NULL: start = b N, count = graph size or N)
@@ -94,18 +27,11 @@ __global__ __launch_bounds__(256) void dmon_part_kernel(const float* __restrict_
   const int kc = blockIdx.x, split = blockIdx.y, b = blockIdx.z;
   const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
   const int k = kc * 64 + c;
-  int64_t start, count, span;
-  if (ptr) {
-    start = ptr[b];
-    count = ptr[b + 1] - start;
-    span = count;
-  } else {
-    start = static_cast<int64_t>(b) * N;
-    count = sizes ? (sizes[b] < N ? sizes[b] : N) : N;
-    span = N;
-  }
-  const int64_t lo = static_cast<int64_t>(split) * DM_ROWS;
-  const int64_t hi = count < lo + DM_ROWS ? count : lo + DM_ROWS;
+  int64_t start, count;
+  graph_rows(b, N, sizes, ptr, start, count);
+  const int64_t span = ptr ? count : N;
+  const int64_t lo = static_cast<int64_t>(split) * PART_ROWS;
+  const int64_t hi = count < lo + PART_ROWS ? count : lo + PART_ROWS;
   float ca = 0.f, cs = 0.f;
   if (k < K) {
 #pragma unroll 4
@@ -126,13 +52,13 @@ __global__ __launch_bounds__(256) void dmon_part_kernel(const float* __restrict_
   }
   if (kc == 0) {  // (uniform over the workgroup)
     float dsum = 0.f, nr = 0.f;
-    if (threadIdx.x < DM_ROWS) {
+    if (threadIdx.x < PART_ROWS) {
       const int64_t i = lo + threadIdx.x;
       if (deg && i < hi) dsum = deg[start + i];
       if (i < span) nr = (ptr || !mask) ? 1.f : (mask[start + i] ? 1.f : 0.f);
     }
     float v[2] = {dsum, nr};
-    dm_block_sums<256, 2>(v, sh);
+    block_sums<256, 2>(v, sh);
     if (threadIdx.x == 0) {
       out[2 * K] = v[0];
       out[2 * K + 1] = v[1];
@@ -179,19 +105,9 @@ __global__ __launch_bounds__(T) void dmon_tail_kernel(const float* __restrict__ 
   if (gram)
     for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(gram[off + i], gram[off + i], sq);
   float v[6] = {casq, cssq, m2, nr, tr, sq};
-  dm_block_sums<T, 6>(v, sh);
+  block_sums<T, 6>(v, sh);
   casq = v[0], cssq = v[1], m2 = v[2], nr = v[3], tr = v[4], sq = v[5];
-  float ortho = 0.f;
-  if (gram) {  // mincut_tail_kernel's orthogonality term
-    const float n = sqrtf(sq);
-    const float t = 1.0f / sqrtf(static_cast<float>(K));
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = gram[off + i] / n - ((i / K == i % K) ? t : 0.f);
-      acc = fmaf(y, y, acc);
-    }
-    ortho = sqrtf(dm_block_sum<T>(acc, sh));
-  }
+  const float ortho = gram ? ortho_term<T>(gram + off, K, sq, sh) : 0.f;
   if (threadIdx.x == 0) {
     if (!raw) tr = tr_in ? tr_in[b] : 0.f;
     float m = 0.5f * m2;
@@ -216,7 +132,7 @@ __global__ __launch_bounds__(T) void dmon_tail_kernel(const float* __restrict__ 
 // Backward of the tail, one workgroup per graph, from the upstream gradients g [3,B] (times the coefficients):
 //   g_tr[b] = -g_spec / 2m          (gradient with respect to trace(S^T A S); g_raw = g_tr I)
 //   coef[b] = (alpha, beta) = (2 g_spec / (2m)^2, g_clu sqrt(K) / (n_b ||cs||))   dS_i += alpha d_i ca + beta cs
-//   W[b]    = d ortho / d G as mincut_tail_bwd_kernel (dS = S (W + W^T))
+//   W[b]    = d ortho / d G (ortho_term_bwd; dS = S (W + W^T))
 template <int T>
 __global__ __launch_bounds__(T) void dmon_tail_bwd_kernel(const float* __restrict__ g, const float* __restrict__ stats,
                                                           const float* __restrict__ gram, int K, float sqrt_k,
@@ -230,27 +146,7 @@ __global__ __launch_bounds__(T) void dmon_tail_bwd_kernel(const float* __restric
   const float den = st[0], nr = st[1], ncs = st[2];
   const float g_spec = g[b] * c_spec, g_clu = g[B + b] * c_clu, g_ort = g[2 * B + b] * c_ort;
   const float gt = den > 0.f ? -g_spec / den : 0.f;
-  if (W && gram) {
-    const float* G = gram + off;
-    float sq = 0.f;
-    for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(G[i], G[i], sq);
-    sq = dm_block_sum<T>(sq, sh);
-    const float n = sqrtf(sq);
-    const float t = 1.0f / sqrtf(static_cast<float>(K));
-    float v[2] = {0.f, 0.f};  // |Y|^2, <G, Y>
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-      v[0] = fmaf(y, y, v[0]);
-      v[1] = fmaf(G[i], y, v[1]);
-    }
-    dm_block_sums<T, 2>(v, sh);
-    const float ny = sqrtf(v[0]), gy = v[1];
-    const float cw = ny > 0.f ? g_ort / (ny * n) : 0.f;
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-      W[off + i] = cw * (y - G[i] * (gy / sq));
-    }
-  }
+  if (W && gram) ortho_term_bwd<T>(gram + off, K, g_ort, W + off, sh);
   if (g_raw)
     for (int i = threadIdx.x; i < K * K; i += T) g_raw[off + i] = (i / K == i % K) ? gt : 0.f;
   if (threadIdx.x == 0) {
@@ -329,21 +225,15 @@ extern "C" int tgp_dmon_dense_terms_f32(const float* A, const float* S, int64_t 
                                         float* part, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   TGP_REQUIRE(B >= 0 && N >= 0 && K >= 1, TGP_ERR_INVALID, "tgp_dmon_dense_terms_f32: bad shape");
-  TGP_REQUIRE(nsplit == cdiv(N, DM_ROWS) || (N == 0 && nsplit == 1), TGP_ERR_INVALID,
+  TGP_REQUIRE(nsplit == cdiv(N, PART_ROWS) || (N == 0 && nsplit == 1), TGP_ERR_INVALID,
               "tgp_dmon_dense_terms_f32: nsplit must be ceil(N / 64)");
   if (B == 0) return TGP_OK;
   TGP_REQUIRE(S && part && (!A || deg), TGP_ERR_INVALID, "tgp_dmon_dense_terms_f32: null pointer");
   TGP_REQUIRE(B < 65536 && N < (1ll << 31) && K < 32768 && B * N < (1ll << 33) && nsplit < 65536, TGP_ERR_RANGE,
               "tgp_dmon_dense_terms_f32: too large");
   const int64_t rows = B * N;
-  if (A && rows > 0) {
-    if (N <= 64)
-      hipLaunchKernelGGL(dmon_deg_kernel<16>, dim3(cdiv(rows, 16)), dim3(256), 0, stream, A, rows, static_cast<int>(N),
-                         graph_sizes, mask, deg);
-    else
-      hipLaunchKernelGGL(dmon_deg_kernel<64>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, A, rows, static_cast<int>(N),
-                         graph_sizes, mask, deg);
-  }
+  const float* ones = nullptr;  // deg = A 1
+  if (A && rows > 0) TGP_LAUNCH_A_ROWS(false, A, ones, rows, static_cast<int>(N), graph_sizes, mask, deg, stream);
   launch_part(S, deg, B, N, K, graph_sizes, mask, nullptr, nsplit, part, stream);
   return check_launch("tgp_dmon_dense_terms_f32");
 }
@@ -378,14 +268,8 @@ extern "C" int tgp_dmon_loss_terms_f32(const float* part, int64_t nsplit, const 
   TGP_REQUIRE(part && out && ca && cs && stats, TGP_ERR_INVALID, "tgp_dmon_loss_terms_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31) && nsplit < 65536, TGP_ERR_RANGE, "tgp_dmon_loss_terms_f32: too many graphs");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(dmon_tail_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, part,
-                       static_cast<int>(nsplit), raw, tr, gram, static_cast<int>(K), sqrt_k, clamp_m, eps, c_spec,
-                       c_clu, c_ort, static_cast<int>(B), out, ca, cs, stats);
-  else
-    hipLaunchKernelGGL(dmon_tail_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, part,
-                       static_cast<int>(nsplit), raw, tr, gram, static_cast<int>(K), sqrt_k, clamp_m, eps, c_spec,
-                       c_clu, c_ort, static_cast<int>(B), out, ca, cs, stats);
+  TGP_LAUNCH_PER_GRAPH(dmon_tail_kernel, B, K, stream, part, static_cast<int>(nsplit), raw, tr, gram, static_cast<int>(K),
+                       sqrt_k, clamp_m, eps, c_spec, c_clu, c_ort, static_cast<int>(B), out, ca, cs, stats);
   return check_launch("tgp_dmon_loss_terms_f32");
 }
 
@@ -397,14 +281,8 @@ extern "C" int tgp_dmon_loss_terms_bwd_f32(const float* g_terms, const float* st
   TGP_REQUIRE(g_terms && stats && coef && (!gram || W), TGP_ERR_INVALID, "tgp_dmon_loss_terms_bwd_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31), TGP_ERR_RANGE, "tgp_dmon_loss_terms_bwd_f32: too many graphs");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(dmon_tail_bwd_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, g_terms, stats,
-                       gram, static_cast<int>(K), sqrt_k, c_spec, c_clu, c_ort, static_cast<int>(B), g_raw, g_tr,
-                       coef, W);
-  else
-    hipLaunchKernelGGL(dmon_tail_bwd_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, g_terms, stats,
-                       gram, static_cast<int>(K), sqrt_k, c_spec, c_clu, c_ort, static_cast<int>(B), g_raw, g_tr,
-                       coef, W);
+  TGP_LAUNCH_PER_GRAPH(dmon_tail_bwd_kernel, B, K, stream, g_terms, stats, gram, static_cast<int>(K), sqrt_k, c_spec,
+                       c_clu, c_ort, static_cast<int>(B), g_raw, g_tr, coef, W);
   return check_launch("tgp_dmon_loss_terms_bwd_f32");
 }
 

@@ -6,84 +6,19 @@
 //   ortho[b]  = mu || G / ||G||_F - I / sqrt(K) ||_F   (G = S^T S, MinCut's)   or, hosc_ortho,
 //               mu (sqrt(K) - sum_j ||S_*j|| / sqrt(n_b)) / (sqrt(K) - 1)      (0 when K <= 1)
 //
-// The motif adjacency M = A A A is never formed: d3 is three matrix-vector passes over A (hosc_matvec_kernel), Z three
+// The motif adjacency M = A A A is never formed: d3 is three matrix-vector passes over A (a_rows_kernel), Z three
 // N^2 K products on the fp32-MFMA bmm (or three CSR SpMMs for an edge list), num / den / the column norms one pass over
 // S, Z and the degree vectors (hosc_part_kernel) reduced per graph in a fixed order by the tail (no float atomics).
 // Batches of small graphs (N, K <= 64) get d1, d3, Z and the partial record from ONE launch (hosc_small_kernel).
-#include "common.h"
+#include "loss_common.h"
 
 namespace tgp {
 namespace {
 
-constexpr int HS_ROWS = 64;         // rows of one graph per workgroup of the partial pass
 constexpr int HS_SMALL = 64;        // the small-graph kernel: at most this many nodes and clusters
 constexpr int HS_REC = 4;           // floats per 64-column block of a partial record: num | den3 | num1 | den1
-typedef float hs_f32x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int hs_record(int K) { return K + HS_REC * ((K + 63) / 64) + 1; }
-
-template <int T, int NV>
-__device__ __forceinline__ void hs_block_sums(float (&v)[NV], float* sh) {  // sh: NV * T / 64 floats; fixed order
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) sh[q * (T / 64) + (threadIdx.x >> 6)] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) t += sh[q * (T / 64) + w];
-    v[q] = t;
-  }
-  __syncthreads();
-}
-
-// G lanes per node row: y[b,i] = sum_j A[b,i,j] v[b,j] (v NULL: ones) on the rows of the graph (graph size), 0 elsewhere.
-// The pass over A is dmon_deg_kernel's (dmon.hip) with the vector's chunk multiplied in; v (4 N bytes per graph) stays in
-// cache.  The columns are not cut at the graph size: a zero-padded A adds nothing there, a caller's own padding counts as
-// it does in the reference's A A A.
-template <int G>
-__global__ __launch_bounds__(256) void hosc_matvec_kernel(const float* __restrict__ A, const float* __restrict__ v,
-                                                          int64_t rows, int N, const int64_t* __restrict__ sizes,
-                                                          float* __restrict__ y) {
-  const int sub = threadIdx.x % G;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * (256 / G) + threadIdx.x / G;
-  float d = 0.f;
-  const bool real = row < rows && (!sizes || row % N < sizes[row / N]);
-  if (real) {
-    const float* a = A + row * N;
-    const float* x = v ? v + (row / N) * N : nullptr;
-    if ((N & 3) == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(v) % 16 == 0) {
-      const hs_f32x4* a4 = reinterpret_cast<const hs_f32x4*>(a);
-      const hs_f32x4* x4 = reinterpret_cast<const hs_f32x4*>(x);
-      if (x) {
-        for (int j = sub; j < N / 4; j += G) {
-          const hs_f32x4 p = __builtin_nontemporal_load(a4 + j);
-          const hs_f32x4 q = x4[j];
-          d += (p.x * q.x + p.y * q.y) + (p.z * q.z + p.w * q.w);
-        }
-      } else {
-        for (int j = sub; j < N / 4; j += G) {
-          const hs_f32x4 p = __builtin_nontemporal_load(a4 + j);
-          d += (p.x + p.y) + (p.z + p.w);
-        }
-      }
-    } else if (x) {
-      for (int j = sub; j < N; j += G) d = fmaf(a[j], x[j], d);
-    } else {
-      for (int j = sub; j < N; j += G) d += a[j];
-    }
-  }
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-  if (row < rows && sub == 0) y[row] = d;
-}
 
 // One workgroup per (64 columns kc, 64 rows, graph): part[b][split] = [ sum_i S_ik^2 (K) | per kc: num = sum S Z,
 // den3 = sum d3_i S_ik^2, num1 = sum S Z1, den1 = sum d1_i S_ik^2 | node count ].  Z, Z1 have row stride ldz, d3 and d1
@@ -103,18 +38,11 @@ __global__ __launch_bounds__(256) void hosc_part_kernel(const float* __restrict_
   const int kc = blockIdx.x, split = blockIdx.y, b = blockIdx.z;
   const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
   const int k = kc * 64 + c;
-  int64_t start, count, span;
-  if (ptr) {
-    start = ptr[b];
-    count = ptr[b + 1] - start;
-    span = count;
-  } else {
-    start = static_cast<int64_t>(b) * N;
-    count = sizes ? (sizes[b] < N ? sizes[b] : N) : N;
-    span = N;
-  }
-  const int64_t lo = static_cast<int64_t>(split) * HS_ROWS;
-  const int64_t hi = count < lo + HS_ROWS ? count : lo + HS_ROWS;
+  int64_t start, count;
+  graph_rows(b, N, sizes, ptr, start, count);
+  const int64_t span = ptr ? count : N;
+  const int64_t lo = static_cast<int64_t>(split) * PART_ROWS;
+  const int64_t hi = count < lo + PART_ROWS ? count : lo + PART_ROWS;
   float sq = 0.f, num = 0.f, den3 = 0.f, num1 = 0.f, den1 = 0.f;
   if (k < K) {
 #pragma unroll 4
@@ -131,12 +59,12 @@ __global__ __launch_bounds__(256) void hosc_part_kernel(const float* __restrict_
   }
   sh_sq[r][c] = sq;
   float nr = 0.f;
-  if (kc == 0 && threadIdx.x < HS_ROWS) {
+  if (kc == 0 && threadIdx.x < PART_ROWS) {
     const int64_t i = lo + threadIdx.x;
     if (i < span) nr = (ptr || !mask) ? 1.f : (mask[start + i] ? 1.f : 0.f);
   }
   float v[5] = {num, den3, num1, den1, nr};
-  hs_block_sums<256, 5>(v, sh);  // (its barriers also publish sh_sq)
+  block_sums<256, 5>(v, sh);  // (its barriers also publish sh_sq)
   const int nkc = (K + 63) / 64;
   float* out = part + (static_cast<int64_t>(b) * nsplit + split) * hs_record(K);
   if (r == 0 && k < K) out[k] = (sh_sq[0][c] + sh_sq[1][c]) + (sh_sq[2][c] + sh_sq[3][c]);
@@ -242,7 +170,7 @@ __global__ __launch_bounds__(256) void hosc_small_kernel(const float* __restrict
   float nr = 0.f;
   if (threadIdx.x < N) nr = mask ? (mask[static_cast<int64_t>(b) * N + threadIdx.x] ? 1.f : 0.f) : 1.f;
   float v[5] = {num, den3, num1, den1, nr};
-  hs_block_sums<256, 5>(v, sh);  // (its barriers also publish sh_sq)
+  block_sums<256, 5>(v, sh);  // (its barriers also publish sh_sq)
   float* out = part + static_cast<int64_t>(b) * hs_record(K);
   if (static_cast<int>(threadIdx.x) < K) {  // column threadIdx.x: its 256 / KP row groups in a fixed order
     float c = 0.f;
@@ -295,22 +223,12 @@ __global__ __launch_bounds__(T) void hosc_tail_kernel(const float* __restrict__ 
   if (gram)
     for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(gram[off + i], gram[off + i], sq);
   float v[7] = {cnsum, num, den3, num1, den1, nr, tr};
-  hs_block_sums<T, 7>(v, sh);
+  block_sums<T, 7>(v, sh);
   cnsum = v[0], num = v[1], den3 = v[2], num1 = v[3], den1 = v[4], nr = v[5], tr = v[6];
   float ortho = 0.f;
-  if (gram) {  // mincut_tail_kernel's orthogonality term
-    float w[1] = {sq};
-    hs_block_sums<T, 1>(w, sh);
-    sq = w[0];
-    const float n = sqrtf(sq);
-    const float t = 1.0f / sqrtf(static_cast<float>(K));
-    float acc[1] = {0.f};
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = gram[off + i] / n - ((i / K == i % K) ? t : 0.f);
-      acc[0] = fmaf(y, y, acc[0]);
-    }
-    hs_block_sums<T, 1>(acc, sh);
-    ortho = sqrtf(acc[0]);
+  if (gram) {
+    sq = block_sum<T>(sq, sh);
+    ortho = ortho_term<T>(gram + off, K, sq, sh);
   } else if (hosc_ortho && K > 1) {
     const float sqrt_k = sqrtf(static_cast<float>(K));
     ortho = (sqrt_k - cnsum / sqrtf(nr)) / (sqrt_k - 1.0f);
@@ -334,7 +252,7 @@ __global__ __launch_bounds__(T) void hosc_tail_kernel(const float* __restrict__ 
 //     c_ortho = -g1 mu / (sqrt(n_b) (sqrt(K) - 1))    dS_ik += c_ortho S_ik / ||S_*k||     (hosc_ortho)
 //     c_den1 = +g0 (1 - alpha) trace / (k D1^2)       dS += 2 c_den1 d1_i S_i
 //     c_num1 = -g0 (1 - alpha) / (k D1)      g_raw = c_num1 I  (or, without raw, dS += c_num1 (Z1 + Z1t))
-//   W[b] = d (mu ortho) / d G as mincut_tail_bwd_kernel (dS = S (W + W^T)), with gram.
+//   W[b] = d (mu ortho) / d G (ortho_term_bwd; dS = S (W + W^T)), with gram.
 template <int T>
 __global__ __launch_bounds__(T) void hosc_tail_bwd_kernel(const float* __restrict__ g, const float* __restrict__ stats,
                                                           const float* __restrict__ gram, int K, float alpha, float mu,
@@ -350,28 +268,7 @@ __global__ __launch_bounds__(T) void hosc_tail_bwd_kernel(const float* __restric
   const float gc = alpha < 1.f ? g0 * (1.0f - alpha) * inv_k : 0.f;
   const float gh = alpha > 0.f ? g0 * alpha * inv_k : 0.f;
   const float c_num1 = -gc / D1;
-  if (W && gram) {
-    const float g_ort = g1 * mu;
-    const float* G = gram + off;
-    float sq[1] = {0.f};
-    for (int i = threadIdx.x; i < K * K; i += T) sq[0] = fmaf(G[i], G[i], sq[0]);
-    hs_block_sums<T, 1>(sq, sh);
-    const float n = sqrtf(sq[0]);
-    const float t = 1.0f / sqrtf(static_cast<float>(K));
-    float v[2] = {0.f, 0.f};  // |Y|^2, <G, Y>
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-      v[0] = fmaf(y, y, v[0]);
-      v[1] = fmaf(G[i], y, v[1]);
-    }
-    hs_block_sums<T, 2>(v, sh);
-    const float ny = sqrtf(v[0]), gy = v[1];
-    const float cw = ny > 0.f ? g_ort / (ny * n) : 0.f;
-    for (int i = threadIdx.x; i < K * K; i += T) {
-      const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-      W[off + i] = cw * (y - G[i] * (gy / sq[0]));
-    }
-  }
+  if (W && gram) ortho_term_bwd<T>(gram + off, K, g1 * mu, W + off, sh);
   if (g_raw)
     for (int i = threadIdx.x; i < K * K; i += T) g_raw[off + i] = (i / K == i % K) ? c_num1 : 0.f;
   if (threadIdx.x == 0) {
@@ -436,13 +333,8 @@ extern "C" int tgp_hosc_matvec_f32(const float* A, const float* v, int64_t B, in
   if (rows == 0) return TGP_OK;
   TGP_REQUIRE(A && y, TGP_ERR_INVALID, "tgp_hosc_matvec_f32: null pointer");
   TGP_REQUIRE(B < 65536 && N < (1ll << 31) && rows < (1ll << 33), TGP_ERR_RANGE, "tgp_hosc_matvec_f32: too large");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (N <= 64)
-    hipLaunchKernelGGL(hosc_matvec_kernel<16>, dim3(cdiv(rows, 16)), dim3(256), 0, stream, A, v, rows,
-                       static_cast<int>(N), graph_sizes, y);
-  else
-    hipLaunchKernelGGL(hosc_matvec_kernel<64>, dim3(cdiv(rows, 4)), dim3(256), 0, stream, A, v, rows,
-                       static_cast<int>(N), graph_sizes, y);
+  const uint8_t* mask = nullptr;
+  TGP_LAUNCH_A_ROWS(true, A, v, rows, static_cast<int>(N), graph_sizes, mask, y, static_cast<hipStream_t>(stream_));
   return check_launch("tgp_hosc_matvec_f32");
 }
 
@@ -456,7 +348,7 @@ extern "C" int tgp_hosc_node_terms_f32(const float* S, const float* Z, const flo
   TGP_REQUIRE(S && part, TGP_ERR_INVALID, "tgp_hosc_node_terms_f32: null pointer");
   TGP_REQUIRE((!Z && !Z1) || ldz >= K, TGP_ERR_INVALID, "tgp_hosc_node_terms_f32: ldz < K");
   TGP_REQUIRE((!d3 && !d1) || ldd >= 1, TGP_ERR_INVALID, "tgp_hosc_node_terms_f32: ldd < 1");
-  TGP_REQUIRE(ptr || nsplit == cdiv(N, HS_ROWS) || (N == 0 && nsplit == 1), TGP_ERR_INVALID,
+  TGP_REQUIRE(ptr || nsplit == cdiv(N, PART_ROWS) || (N == 0 && nsplit == 1), TGP_ERR_INVALID,
               "tgp_hosc_node_terms_f32: nsplit must be ceil(N / 64)");
   TGP_REQUIRE(B < 65536 && N < (1ll << 31) && K < 32768 && nsplit < 65536 && ldz < (1ll << 31) && ldd < (1ll << 31),
               TGP_ERR_RANGE, "tgp_hosc_node_terms_f32: too large");
@@ -496,14 +388,8 @@ extern "C" int tgp_hosc_loss_terms_f32(const float* part, int64_t nsplit, const 
   TGP_REQUIRE(part && out && cn && stats, TGP_ERR_INVALID, "tgp_hosc_loss_terms_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31) && nsplit < 65536, TGP_ERR_RANGE, "tgp_hosc_loss_terms_f32: too many graphs");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(hosc_tail_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, part,
-                       static_cast<int>(nsplit), raw, gram, static_cast<int>(K), alpha, mu, inv_k, hosc_ortho, eps,
-                       static_cast<int>(B), out, cn, stats);
-  else
-    hipLaunchKernelGGL(hosc_tail_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, part,
-                       static_cast<int>(nsplit), raw, gram, static_cast<int>(K), alpha, mu, inv_k, hosc_ortho, eps,
-                       static_cast<int>(B), out, cn, stats);
+  TGP_LAUNCH_PER_GRAPH(hosc_tail_kernel, B, K, stream, part, static_cast<int>(nsplit), raw, gram, static_cast<int>(K),
+                       alpha, mu, inv_k, hosc_ortho, eps, static_cast<int>(B), out, cn, stats);
   return check_launch("tgp_hosc_loss_terms_f32");
 }
 
@@ -515,12 +401,8 @@ extern "C" int tgp_hosc_loss_terms_bwd_f32(const float* g_terms, const float* st
   TGP_REQUIRE(g_terms && stats && coef && (!gram || W), TGP_ERR_INVALID, "tgp_hosc_loss_terms_bwd_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31), TGP_ERR_RANGE, "tgp_hosc_loss_terms_bwd_f32: too many graphs");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(hosc_tail_bwd_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, g_terms, stats,
-                       gram, static_cast<int>(K), alpha, mu, inv_k, hosc_ortho, static_cast<int>(B), g_raw, coef, W);
-  else
-    hipLaunchKernelGGL(hosc_tail_bwd_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, g_terms, stats,
-                       gram, static_cast<int>(K), alpha, mu, inv_k, hosc_ortho, static_cast<int>(B), g_raw, coef, W);
+  TGP_LAUNCH_PER_GRAPH(hosc_tail_bwd_kernel, B, K, stream, g_terms, stats, gram, static_cast<int>(K), alpha, mu, inv_k,
+                       hosc_ortho, static_cast<int>(B), g_raw, coef, W);
   return check_launch("tgp_hosc_loss_terms_bwd_f32");
 }
 

@@ -5,56 +5,11 @@
 //                                                        utils/losses.py:39-81 (MinCut)
 //
 // All HBM-bound: every input byte is read once, reductions run in a fixed order (no float atomics).
-#include "common.h"
+#include "loss_common.h"
 
 namespace tgp {
 
 constexpr int RED_BLOCKS = 1024;
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-template <int T>
-__device__ __forceinline__ float block_sum_t(float v, float* sh) {  // sh: T / 64 floats; fixed order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int w = 0; w < T / 64; ++w) t += sh[w];
-  return t;
-}
-
-// four sums behind ONE pair of barriers (sh: 4 * T / 64 floats); each sum in the order block_sum_t adds it
-template <int T>
-__device__ __forceinline__ void block_sum4_t(float (&v)[4], float* sh) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sh[q * (T / 64) + (threadIdx.x >> 6)] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) t += sh[q * (T / 64) + w];
-    v[q] = t;
-  }
-}
 
 __device__ __forceinline__ float ent_term(float s, float eps) { return -s * logf(s + eps); }
 
@@ -63,14 +18,14 @@ __global__ __launch_bounds__(256) void entropy_partial_kernel(const float* __res
   __shared__ float sh[4];
   float acc = 0.f;
   const int64_t n4 = (reinterpret_cast<uintptr_t>(S) % 16 == 0) ? n / 4 : 0;
-  const nt_f32x4* S4 = reinterpret_cast<const nt_f32x4*>(S);
+  const f32x4* S4 = reinterpret_cast<const f32x4*>(S);
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += 256ll * gridDim.x) {
-    const nt_f32x4 v = __builtin_nontemporal_load(S4 + i);
+    const f32x4 v = __builtin_nontemporal_load(S4 + i);
     acc += (ent_term(v.x, eps) + ent_term(v.y, eps)) + (ent_term(v.z, eps) + ent_term(v.w, eps));
   }
   for (int64_t i = n4 * 4 + static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += 256ll * gridDim.x)
     acc += ent_term(S[i], eps);
-  const float t = block_sum_256(acc, sh);
+  const float t = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -79,7 +34,7 @@ __global__ __launch_bounds__(256) void final_sum_kernel(const float* __restrict_
   __shared__ float sh[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  const float t = block_sum_256(acc, sh);
+  const float t = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) out[0] = t;
 }
 
@@ -99,9 +54,9 @@ __global__ __launch_bounds__(256) void cut_rows_kernel(const float* __restrict__
     const float* a = A + row * N;
     const float* s = S + row * K;
     if ((N & 3) == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0) {
-      const nt_f32x4* a4 = reinterpret_cast<const nt_f32x4*>(a);
+      const f32x4* a4 = reinterpret_cast<const f32x4*>(a);
       for (int j = sub; j < N / 4; j += G) {
-        const nt_f32x4 v = __builtin_nontemporal_load(a4 + j);
+        const f32x4 v = __builtin_nontemporal_load(a4 + j);
         d += (v.x + v.y) + (v.z + v.w);
       }
     } else {
@@ -127,7 +82,7 @@ __global__ __launch_bounds__(256) void cut_den_kernel(const float* __restrict__ 
   const float* qq = q + static_cast<int64_t>(blockIdx.x) * N;
   float acc = 0.f;
   for (int i = threadIdx.x; i < N; i += 256) acc = fmaf(d[i], qq[i], acc);
-  const float t = block_sum_256(acc, sh);
+  const float t = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) den[blockIdx.x] = t;
 }
 
@@ -147,19 +102,12 @@ __global__ __launch_bounds__(T) void mincut_tail_kernel(const float* __restrict_
   float tr = 0.f, sq = 0.f;
   for (int i = threadIdx.x; i < K; i += T) tr += R[static_cast<int64_t>(i) * K + i];
   for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(G[i], G[i], sq);
-  tr = block_sum_t<T>(tr, sh);
-  sq = block_sum_t<T>(sq, sh);
-  const float n = sqrtf(sq);
-  const float t = 1.0f / sqrtf(static_cast<float>(K));
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < K * K; i += T) {
-    const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-    acc = fmaf(y, y, acc);
-  }
-  acc = block_sum_t<T>(acc, sh);
+  tr = block_sum<T>(tr, sh);
+  sq = block_sum<T>(sq, sh);
+  const float ortho = ortho_term<T>(G, K, sq, sh);
   if (threadIdx.x == 0) {
     out[b] = -(tr / (den[b] + eps));
-    out[B + b] = sqrtf(acc);
+    out[B + b] = ortho;
   }
 }
 
@@ -173,37 +121,18 @@ __global__ __launch_bounds__(T) void mincut_tail_bwd_kernel(const float* __restr
                                                               const float* __restrict__ gram, const float* __restrict__ g,
                                                               int K, float eps, int B, float* __restrict__ g_raw,
                                                               float* __restrict__ c1, float* __restrict__ W) {
-  __shared__ float sh[T / 64];
+  __shared__ float sh[2 * (T / 64)];
   const int b = blockIdx.x;
   const int64_t off = static_cast<int64_t>(b) * K * K;
   const float* R = raw + off;
-  const float* G = gram + off;
-  float tr = 0.f, sq = 0.f;
+  float tr = 0.f;
   for (int i = threadIdx.x; i < K; i += T) tr += R[static_cast<int64_t>(i) * K + i];
-  for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(G[i], G[i], sq);
-  tr = block_sum_t<T>(tr, sh);
-  sq = block_sum_t<T>(sq, sh);
-  const float n = sqrtf(sq);
-  const float t = 1.0f / sqrtf(static_cast<float>(K));
-  float ny2 = 0.f, gy = 0.f;
-  for (int i = threadIdx.x; i < K * K; i += T) {
-    const float y = G[i] / n - ((i / K == i % K) ? t : 0.f);
-    ny2 = fmaf(y, y, ny2);
-    gy = fmaf(G[i], y, gy);
-  }
-  ny2 = block_sum_t<T>(ny2, sh);
-  gy = block_sum_t<T>(gy, sh);
-  const float ny = sqrtf(ny2);
+  tr = block_sum<T>(tr, sh);
   const float g_cut = g[b], g_ortho = g[B + b];
   const float dd = den[b] + eps;
   const float cdiag = -g_cut / dd;
-  const float coef = ny > 0.f ? g_ortho / (ny * n) : 0.f;
-  for (int i = threadIdx.x; i < K * K; i += T) {
-    const bool diag = i / K == i % K;
-    const float y = G[i] / n - (diag ? t : 0.f);
-    W[off + i] = coef * (y - G[i] * (gy / sq));
-    g_raw[off + i] = diag ? cdiag : 0.f;
-  }
+  ortho_term_bwd<T>(gram + off, K, g_ortho, W + off, sh);
+  for (int i = threadIdx.x; i < K * K; i += T) g_raw[off + i] = (i / K == i % K) ? cdiag : 0.f;
   if (threadIdx.x == 0) c1[b] = g_cut * tr / (dd * dd);
 }
 
@@ -219,8 +148,8 @@ __global__ __launch_bounds__(256) void diffpool_tail_kernel(const float* __restr
   float a = 0.f, e = 0.f;
   for (int i = threadIdx.x; i < B; i += 256) a += sq[i];
   for (int i = threadIdx.x; i < n_partial; i += 256) e += ent_partial[i];
-  a = block_sum_256(a, sh);
-  e = block_sum_256(e, sh);
+  a = block_sum<256>(a, sh);
+  e = block_sum<256>(e, sh);
   if (threadIdx.x == 0) {
     out[0] = sqrtf(a) * link_scale;
     out[1] = e * ent_scale;
@@ -386,12 +315,8 @@ extern "C" int tgp_mincut_loss_terms_f32(const float* raw, const float* den, con
   if (B == 0) return TGP_OK;
   TGP_REQUIRE(raw && den && gram && out, TGP_ERR_INVALID, "tgp_mincut_loss_terms_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31), TGP_ERR_RANGE, "tgp_mincut_loss_terms_f32: too many graphs");
-  if (K >= 64)
-    hipLaunchKernelGGL(mincut_tail_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0,
-                       static_cast<hipStream_t>(stream_), raw, den, gram, static_cast<int>(K), eps, static_cast<int>(B), out);
-  else
-    hipLaunchKernelGGL(mincut_tail_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), raw, den, gram, static_cast<int>(K), eps, static_cast<int>(B), out);
+  TGP_LAUNCH_PER_GRAPH(mincut_tail_kernel, B, K, static_cast<hipStream_t>(stream_), raw, den, gram, static_cast<int>(K), eps,
+                       static_cast<int>(B), out);
   return check_launch("tgp_mincut_loss_terms_f32");
 }
 
@@ -403,14 +328,8 @@ extern "C" int tgp_mincut_loss_terms_bwd_f32(const float* raw, const float* den,
   TGP_REQUIRE(raw && den && gram && g_terms && g_raw && c1 && W, TGP_ERR_INVALID,
               "tgp_mincut_loss_terms_bwd_f32: null pointer");
   TGP_REQUIRE(B < (1ll << 31), TGP_ERR_RANGE, "tgp_mincut_loss_terms_bwd_f32: too many graphs");
-  if (K >= 64)
-    hipLaunchKernelGGL(mincut_tail_bwd_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0,
-                       static_cast<hipStream_t>(stream_), raw, den, gram, g_terms, static_cast<int>(K), eps,
-                       static_cast<int>(B), g_raw, c1, W);
-  else
-    hipLaunchKernelGGL(mincut_tail_bwd_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), raw, den, gram, g_terms, static_cast<int>(K), eps,
-                       static_cast<int>(B), g_raw, c1, W);
+  TGP_LAUNCH_PER_GRAPH(mincut_tail_bwd_kernel, B, K, static_cast<hipStream_t>(stream_), raw, den, gram, g_terms,
+                       static_cast<int>(K), eps, static_cast<int>(B), g_raw, c1, W);
   return check_launch("tgp_mincut_loss_terms_bwd_f32");
 }
 
@@ -476,7 +395,7 @@ __global__ __launch_bounds__(T) void mincut_tail2_kernel(const float* __restrict
   }
   {
     float four[4] = {dn, tr, trg, sq};
-    block_sum4_t<T>(four, sh);
+    block_sums<T, 4>(four, sh);
     dn = four[0]; tr = four[1]; trg = four[2]; sq = four[3];
   }
   const float n = sqrtf(sq);
@@ -497,7 +416,7 @@ __global__ __launch_bounds__(T) void mincut_tail2_kernel(const float* __restrict
       acc = fmaf(y, y, acc);
     }
   }
-  acc = block_sum_t<T>(acc, sh);
+  acc = block_sum<T>(acc, sh);
   if (threadIdx.x == 0) {
     den[b] = dn;
     out[b] = -(tr / (dn + eps));
@@ -522,8 +441,8 @@ __global__ __launch_bounds__(T) void mincut_tail2_kernel(const float* __restrict
     a0 += __hip_atomic_load(out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     a1 += __hip_atomic_load(out + B + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  a0 = block_sum_t<T>(a0, sh);
-  a1 = block_sum_t<T>(a1, sh);
+  a0 = block_sum<T>(a0, sh);
+  a1 = block_sum<T>(a1, sh);
   if (threadIdx.x == 0) {
     means[0] = a0 / static_cast<float>(B);
     means[1] = a1 / static_cast<float>(B);
@@ -721,8 +640,8 @@ __global__ __launch_bounds__(T) void graph_trace_gsq_kernel(const float* __restr
   float tr = 0.f, sq = 0.f;
   for (int i = threadIdx.x; i < K; i += T) tr += R[static_cast<int64_t>(i) * K + i];
   for (int i = threadIdx.x; i < K * K; i += T) sq = fmaf(G[i], G[i], sq);
-  tr = block_sum_t<T>(tr, sh);
-  sq = block_sum_t<T>(sq, sh);
+  tr = block_sum<T>(tr, sh);
+  sq = block_sum<T>(sq, sh);
   if (threadIdx.x == 0) { stats[2 * b] = tr; stats[2 * b + 1] = sq; }
 }
 
@@ -735,9 +654,9 @@ __global__ __launch_bounds__(256) void diffpool_u_final_kernel(const float* __re
   float tr = 0.f, gs = 0.f, e = 0.f;
   for (int i = threadIdx.x; i < B; i += 256) { tr += stats[2 * i]; gs += stats[2 * i + 1]; }
   for (int i = threadIdx.x; i < n_partial; i += 256) e += ent_partial[i];
-  tr = block_sum_256(tr, sh);
-  gs = block_sum_256(gs, sh);
-  e = block_sum_256(e, sh);
+  tr = block_sum<256>(tr, sh);
+  gs = block_sum<256>(gs, sh);
+  e = block_sum<256>(e, sh);
   if (threadIdx.x == 0) {
     const float sw2 = sw2_dev ? sw2_dev[0] : sw2_host;
     out[0] = sqrtf(fmaxf((sw2 - 2.0f * tr) + gs, 0.f)) * link_scale;
@@ -758,10 +677,10 @@ __global__ __launch_bounds__(256) void diffpool_stats_tail_kernel(const float* _
     const float4 v = s4[i];
     a2 += v.x; tr += v.y; fro += v.z; ent += v.w;
   }
-  a2 = block_sum_256(a2, sh);
-  tr = block_sum_256(tr, sh);
-  fro = block_sum_256(fro, sh);
-  ent = block_sum_256(ent, sh);
+  a2 = block_sum<256>(a2, sh);
+  tr = block_sum<256>(tr, sh);
+  fro = block_sum<256>(fro, sh);
+  ent = block_sum<256>(ent, sh);
   if (threadIdx.x == 0) {
     out[0] = sqrtf(fmaxf((a2 - 2.0f * tr) + fro, 0.f)) * link_scale;
     out[1] = ent * ent_scale;
@@ -803,12 +722,7 @@ extern "C" int tgp_diffpool_unbatched_tail_f32(const float* raw, const float* gr
   TGP_REQUIRE(raw && gram && stats && out2 && (n_partial == 0 || ent_partial), TGP_ERR_INVALID,
               "tgp_diffpool_unbatched_tail_f32: null pointer");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(graph_trace_gsq_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, raw, gram,
-                       static_cast<int>(K), stats);
-  else
-    hipLaunchKernelGGL(graph_trace_gsq_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, raw, gram,
-                       static_cast<int>(K), stats);
+  TGP_LAUNCH_PER_GRAPH(graph_trace_gsq_kernel, B, K, stream, raw, gram, static_cast<int>(K), stats);
   hipLaunchKernelGGL(diffpool_u_final_kernel, dim3(1), dim3(256), 0, stream, stats, static_cast<int>(B), sw2_dev, sw2_host,
                      ent_partial, n_partial, link_scale, ent_scale, out2);
   return check_launch("tgp_diffpool_unbatched_tail_f32");
@@ -829,14 +743,8 @@ extern "C" int tgp_mincut_terms_fused_f32(const float* raw, const float* gram, c
   TGP_REQUIRE(B < (1ll << 31), TGP_ERR_RANGE, "tgp_mincut_terms_fused_f32: too many graphs");
   TGP_REQUIRE(!means || ticket, TGP_ERR_INVALID, "tgp_mincut_terms_fused_f32: means need a zeroed ticket word");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (K >= 64)
-    hipLaunchKernelGGL(mincut_tail2_kernel<1024>, dim3(static_cast<unsigned>(B)), dim3(1024), 0, stream, raw, gram, deg, q,
-                       static_cast<int>(N), static_cast<int>(K), eps, static_cast<int>(B), den, out, stats, ptr, ticket, means,
-                       edge_row_ptr, edge_col, edge_w);
-  else
-    hipLaunchKernelGGL(mincut_tail2_kernel<256>, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, raw, gram, deg, q,
-                       static_cast<int>(N), static_cast<int>(K), eps, static_cast<int>(B), den, out, stats, ptr, ticket,
-                       means, edge_row_ptr, edge_col, edge_w);
+  TGP_LAUNCH_PER_GRAPH(mincut_tail2_kernel, B, K, stream, raw, gram, deg, q, static_cast<int>(N), static_cast<int>(K), eps,
+                       static_cast<int>(B), den, out, stats, ptr, ticket, means, edge_row_ptr, edge_col, edge_w);
   return check_launch("tgp_mincut_terms_fused_f32");
 }
 

@@ -1753,7 +1753,7 @@ def mincut_loss_terms_bwd(raw: Tensor, den: Tensor, gram: Tensor, g_terms: Tenso
     return g_raw, c1, W
 
 
-_DMON_ROWS = 64  # rows of one graph per workgroup of the DMoN partial pass (csrc/dmon.hip)
+_PART_ROWS = 64  # rows of one graph per workgroup of the DMoN / HOSC partial passes (PART_ROWS, csrc/loss_common.h)
 
 
 def _mask_bytes(mask: Optional[Tensor], B: int, Nn: int) -> Optional[Tensor]:
@@ -1779,7 +1779,7 @@ def dmon_dense_terms(adj: Optional[Tensor], s: Tensor, mask: Optional[Tensor] = 
         a = N.f32c(adj)
         if a.shape != (B, Nn, Nn):
             raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
-    nsplit = max(1, -(-Nn // _DMON_ROWS))
+    nsplit = max(1, -(-Nn // _PART_ROWS))
     if a is not None:
         deg = torch.empty(B, Nn, dtype=torch.float32, device=dev)
     elif deg is not None:
@@ -1819,7 +1819,7 @@ def dmon_node_terms(s: Tensor, deg: Optional[Tensor], ptr: Tensor, max_nodes: in
     if d is not None and d.numel() != s.size(0):
         raise ValueError("dmon_node_terms: deg must hold one value per row of s")
     B, Kc = ptr.numel() - 1, s.size(1)
-    nsplit = max(1, -(-int(max_nodes) // _DMON_ROWS))
+    nsplit = max(1, -(-int(max_nodes) // _PART_ROWS))
     part = torch.empty(B, nsplit, 2 * Kc + 2, dtype=torch.float32, device=dev)
     N.check(N.lib().tgp_dmon_node_terms_f32(N.ptr(s), N.ptr(d), N.ptr(ptr), B, Kc, nsplit, N.ptr(part), N.stream_ptr(dev)),
             "tgp_dmon_node_terms_f32")
@@ -1887,9 +1887,6 @@ def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: i
     return out
 
 
-_HOSC_ROWS = 64  # rows of one graph per workgroup of the HOSC partial pass (csrc/hosc.hip)
-
-
 def hosc_small_graph_nodes() -> int:
     """The largest graph (and cluster count) the one-launch HOSC forward takes (A[b] and two [N,K] buffers in LDS)."""
     return int(N.lib().tgp_hosc_small_graph_nodes())
@@ -1949,12 +1946,12 @@ def hosc_node_terms(s: Tensor, z: Optional[Tensor], z1: Optional[Tensor], d3: Op
     s = N.f32c(s)
     if ptr is None:
         B, Nn, Kc = s.shape
-        rows, nsplit = B * Nn, max(1, -(-Nn // _HOSC_ROWS))
+        rows, nsplit = B * Nn, max(1, -(-Nn // _PART_ROWS))
         p = None
     else:
         p = N.i64c(ptr)
         B, Nn, Kc = p.numel() - 1, 0, s.size(1)
-        rows, nsplit = s.size(0), max(1, -(-int(max_nodes) // _HOSC_ROWS))
+        rows, nsplit = s.size(0), max(1, -(-int(max_nodes) // _PART_ROWS))
     zs = [_hosc_rows(t, rows, Kc) for t in (z, z1)]
     ds_ = [_hosc_rows(t, rows, 1) for t in (d3, d1)]
     L = N.lib()

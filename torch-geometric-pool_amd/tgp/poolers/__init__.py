@@ -26,19 +26,16 @@ from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPoo
 from ..utils.ops import batch_info, batched_negative_edge_sampling, is_dense_adj, negative_edge_sampling
 from ..utils.losses import (
     _MinCutTermsFn,
-    _acc_native,
-    _dmon_native,
+    _native_f32,
     acc_loss_terms,
     acc_sparse_loss_terms,
     asym_norm_loss,
     cluster_loss,
-    _bnpool_native,
     bnpool_rec_loss_terms,
     cluster_connectivity_prior_loss,
     kl_loss,
     sparse_bce_reconstruction_loss,
     weighted_bce_reconstruction_loss,
-    _hosc_native,
     _ho_cut_composed_dense,
     hosc_loss_terms,
     hosc_orthogonality_loss,
@@ -1063,7 +1060,7 @@ class DMoNPooling(_DenseMLPPooling):
                 "ortho_loss": ortho if self.ortho_loss_coeff == 1 else ortho * self.ortho_loss_coeff}
 
     def compute_loss(self, adj: Tensor, S: Tensor, adj_pooled: Tensor, mask: Optional[Tensor]) -> dict:
-        if (_dmon_native(adj, S, adj_pooled) and S.dim() == 3 and adj.dim() == 3 and adj_pooled.dim() == 3
+        if (_native_f32(adj, S, adj_pooled) and S.dim() == 3 and adj.dim() == 3 and adj_pooled.dim() == 3
                 and not adj.requires_grad):
             # the three per-graph tails from one pass over adj, one over S, S^T S and one tail launch (native backward)
             three = self._dmon_means(S, adj_pooled, mask, self._sizes_for(adj), adj=adj)
@@ -1123,7 +1120,7 @@ class AsymCheegerCutPooling(_DenseMLPPooling):
                 "balance_loss": bal if self.balance_coeff == 1 else bal * self.balance_coeff}
 
     def compute_loss(self, adj: Tensor, S: Tensor, mask: Optional[Tensor] = None) -> dict:
-        if _acc_native(adj, S) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
+        if _native_f32(adj, S) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
             # both per-graph terms, coefficients applied: the pass over adj's nonzeros, the quantile select, one tail
             # launch (native backward)
             both = acc_loss_terms(adj, S, self.k, mask, self._sizes_for(adj),
@@ -1185,7 +1182,7 @@ class HOSCPooling(_DenseMLPPooling):
         return self.compute_loss(adj, so.s, raw, mask)
 
     def compute_loss(self, adj: Tensor, S: Tensor, adj_pool: Tensor, mask: Optional[Tensor] = None) -> dict:
-        if (_hosc_native(adj, S, adj_pool) and S.dim() == 3 and adj.dim() == 3 and adj_pool.dim() == 3
+        if (_native_f32(adj, S, adj_pool) and S.dim() == 3 and adj.dim() == 3 and adj_pool.dim() == 3
                 and not adj.requires_grad):
             # both per-graph rows, alpha, mu and 1 / k applied: the motif chain, one pass over S, one tail launch
             both = hosc_loss_terms(adj, S, adj_pool, mask, self._sizes_for(adj), self.alpha, self.mu, self.k,
@@ -1323,7 +1320,7 @@ class BNPool(_DenseMLPPooling):
         s, q_z = so.s, so.q_z
         n = mask.sum(-1) if mask is not None else torch.tensor(adj.shape[-1], device=adj.device)
         n_squared = n ** 2
-        if _bnpool_native(s, self.K, adj) and s.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
+        if _native_f32(s, self.K, adj) and s.dim() == 3 and adj.dim() == 3 and not adj.requires_grad:
             # per-graph terms, already divided by n^2: T = S K, one launch over the logit tiles, one tail launch
             rec = bnpool_rec_loss_terms(s, self.K, adj, mask).mean()
         else:

@@ -28,6 +28,12 @@ def _reduce(loss: Tensor, how: str) -> Tensor:
     raise ValueError(f"Batch reduction {how} not allowed, must be one of ['mean', 'sum'].")
 
 
+def _native_f32(*ts) -> bool:
+    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
+    forms."""
+    return not any(t is not None and t.dtype == torch.float64 for t in ts)
+
+
 def _seg_sum(src: Tensor, index: Tensor, size: int) -> Tensor:
     return src.new_zeros((size,) + tuple(src.shape[1:])).index_add_(0, index, src)
 
@@ -303,12 +309,6 @@ class _DMoNTermsFn(torch.autograd.Function):
 _ONES3 = (1.0, 1.0, 1.0)
 
 
-def _dmon_native(*ts) -> bool:
-    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
-    forms below."""
-    return not any(t is not None and t.dtype == torch.float64 for t in ts)
-
-
 def dmon_loss_terms(adj: Optional[Tensor], S: Tensor, adj_pooled: Tensor, mask: Optional[Tensor] = None,
                     graph_sizes: Optional[Tensor] = None, coeffs=(1.0, 1.0, 1.0), deg: Optional[Tensor] = None) -> Tensor:
     """[3,B]: per-graph values of :func:`spectral_loss`, :func:`cluster_loss` and :func:`orthogonality_loss` (before the
@@ -323,7 +323,7 @@ def spectral_loss(adj: Tensor, S: Tensor, adj_pooled: Tensor, mask: Optional[Ten
                   num_supernodes: Optional[int] = None, batch_reduction: str = "mean") -> Tensor:
     """DMoN's spectral (modularity) loss -(trace(S^T A S) - ||S^T d||^2 / 2m) / 2m per graph, d the (masked) row sums of
     ``adj``, 0 for a graph without edges (reference utils/losses.py:1083-1148)."""
-    if _dmon_native(adj, S, adj_pooled) and S.dim() == 3 and not adj.requires_grad:
+    if _native_f32(adj, S, adj_pooled) and S.dim() == 3 and not adj.requires_grad:
         terms = _DMoNTermsFn.apply(S, adj_pooled, None, adj, ("dense", mask, None), False, 1.0, False, _ONES3)
         return _reduce(terms[0], batch_reduction)
     if mask is None:
@@ -342,7 +342,7 @@ def cluster_loss(S: Tensor, mask: Optional[Tensor] = None, num_supernodes: Optio
     """DMoN's cluster loss ||S^T 1|| sqrt(K) / n - 1 per graph, n = mask.sum(1) (N without a mask)
     (reference utils/losses.py:1216-1265)."""
     k = S.size(-1) if num_supernodes is None else num_supernodes
-    if _dmon_native(S) and S.dim() == 3:
+    if _native_f32(S) and S.dim() == 3:
         terms = _DMoNTermsFn.apply(S, None, None, None, ("dense", mask, None), False, math.sqrt(k), False, _ONES3)
         return _reduce(terms[1], batch_reduction)
     n = S.size(1) if mask is None else mask.sum(dim=1)
@@ -371,7 +371,7 @@ def sparse_spectral_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Te
     bvec = _batch_or_zeros(batch, n, S.device)
     src = edge_index[0]
     deg = _seg_sum(w, src, n)
-    layout = _flat_layout(S, batch) if _dmon_native(S, w) and S.dim() == 2 and n > 0 else None
+    layout = _flat_layout(S, batch) if _native_f32(S, w) and S.dim() == 2 and n > 0 else None
     if layout is not None and not w.requires_grad:
         tr = _seg_sum(w * Fn.edge_dot(S, edge_index), bvec[src], nb)
         return _reduce(_DMoNTermsFn.apply(S, None, tr, deg, layout, False, 1.0, True, _ONES3)[0], batch_reduction)
@@ -384,7 +384,7 @@ def sparse_spectral_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Te
 def unbatched_cluster_loss(S: Tensor, batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
     """The cluster loss of an un-padded batch (reference utils/losses.py:435-473): ||S_g^T 1|| sqrt(K) / n_g - 1."""
     n, k = S.shape
-    layout = _flat_layout(S, batch) if _dmon_native(S) and n > 0 else None
+    layout = _flat_layout(S, batch) if _native_f32(S) and n > 0 else None
     if layout is not None:
         terms = _DMoNTermsFn.apply(S, None, None, None, layout, False, math.sqrt(k), True, _ONES3)
         return _reduce(terms[1], batch_reduction)
@@ -465,12 +465,6 @@ class _ACCTermsFn(torch.autograd.Function):
 _ONES2 = (1.0, 1.0)
 
 
-def _acc_native(*ts) -> bool:
-    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
-    forms below."""
-    return not any(t is not None and t.dtype == torch.float64 for t in ts)
-
-
 def acc_loss_terms(adj: Optional[Tensor], S: Tensor, k: int, mask: Optional[Tensor] = None,
                    graph_sizes: Optional[Tensor] = None, coeffs=(1.0, 1.0)) -> Tensor:
     """[2,B]: per-graph values of :func:`totvar_loss` and :func:`asym_norm_loss` (before the batch reduction) of a padded
@@ -485,7 +479,7 @@ def acc_sparse_loss_terms(edge_index: Tensor, edge_weight: Optional[Tensor], S: 
     each times its coefficient, from ONE Function (one tail launch); None when the operands take the composed forms
     (float64, edge weights that require grad, an unsorted batch, no nodes)."""
     w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
-    if not (_acc_native(S, w) and S.dim() == 2 and S.size(0) > 0) or (w is not None and w.requires_grad):
+    if not (_native_f32(S, w) and S.dim() == 2 and S.size(0) > 0) or (w is not None and w.requires_grad):
         return None
     K.N.require_device(S, edge_index, w, batch)
     layout = _flat_layout(S, batch)
@@ -497,7 +491,7 @@ def acc_sparse_loss_terms(edge_index: Tensor, edge_weight: Optional[Tensor], S: 
 def totvar_loss(S: Tensor, adj: Tensor, batch_reduction: str = "mean") -> Tensor:
     """The total-variation loss sum_ij a_ij ||s_i - s_j||_1 / (2 E) per graph, E = the nonzero entries of ``adj[b]``
     clamped to >= 1 (reference utils/losses.py:780-862).  Padded rows are zero and add nothing; no mask is read."""
-    if _acc_native(S, adj) and S.dim() == 3 and not adj.requires_grad:
+    if _native_f32(S, adj) and S.dim() == 3 and not adj.requires_grad:
         return _reduce(_ACCTermsFn.apply(S, adj, ("dense", None, None), 0, _ONES2)[0], batch_reduction)
     b, i, j = adj.nonzero(as_tuple=True)  # (row-major: a fixed summation order)
     dist = (S[b, i] - S[b, j]).abs().sum(-1)
@@ -512,7 +506,7 @@ def sparse_totvar_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[Tens
     lies in the graph, zero-weight ones included (the dense form counts nonzero entries)."""
     n = S.size(0)
     w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
-    if _acc_native(S, w) and S.dim() == 2 and not (w is not None and w.requires_grad):
+    if _native_f32(S, w) and S.dim() == 2 and not (w is not None and w.requires_grad):
         K.N.require_device(S, edge_index, w, batch)
         layout = _flat_layout(S, batch) if n > 0 else None
         if layout is not None:
@@ -552,7 +546,7 @@ def asym_norm_loss(S: Tensor, k: int, mask: Optional[Tensor] = None, batch_reduc
     B, n = S.size(0), S.size(1)
     if k <= 1 or n == 0:
         return _reduce(S.new_zeros(B), batch_reduction)
-    if _acc_native(S) and S.dim() == 3:
+    if _native_f32(S) and S.dim() == 3:
         return _reduce(_ACCTermsFn.apply(S, None, ("dense", mask, None), int(k), _ONES2)[1], batch_reduction)
     if mask is None:
         mask = torch.ones(B, n, dtype=torch.bool, device=S.device)
@@ -567,7 +561,7 @@ def unbatched_asym_norm_loss(S: Tensor, k: int, batch: Optional[Tensor] = None, 
     n = S.size(0)
     if k <= 1:
         return S.new_zeros(())
-    if _acc_native(S) and S.dim() == 2:
+    if _native_f32(S) and S.dim() == 2:
         K.N.require_device(S, batch)
         layout = _flat_layout(S, batch) if n > 0 else None
         if layout is not None:
@@ -577,12 +571,6 @@ def unbatched_asym_norm_loss(S: Tensor, k: int, batch: Optional[Tensor] = None, 
 
 
 # ------------------------------------------------------------------------------------------------ HOSC
-def _hosc_native(*ts) -> bool:
-    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
-    forms below."""
-    return not any(t is not None and t.dtype == torch.float64 for t in ts)
-
-
 def _hosc_csr(edge_index: Tensor, w: Optional[Tensor], n: int):
     """(edge_index, weights or None, int32 row offsets) of the row-sorted, duplicate-summed list: the CSR form of the A
     the reference's ``sparse_coo_tensor(...).coalesce()`` builds (rows = sources)."""
@@ -756,7 +744,7 @@ def hosc_sparse_loss_terms(edge_index: Tensor, edge_weight: Optional[Tensor], S:
     an unsorted batch, no nodes or no edges).  MinCut's orthogonality row (``hosc_ortho`` False) is formed per graph from
     the segment product S_g^T S_g beside the Function."""
     w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
-    if (not (_hosc_native(S, w) and S.dim() == 2 and S.size(0) > 0 and edge_index.size(1) > 0)
+    if (not (_native_f32(S, w) and S.dim() == 2 and S.size(0) > 0 and edge_index.size(1) > 0)
             or (w is not None and w.requires_grad)):
         return None
     K.N.require_device(S, edge_index, w, batch)
@@ -782,7 +770,7 @@ def hosc_orthogonality_loss(S: Tensor, mask: Optional[Tensor] = None, batch_redu
     a mask); 0 for K <= 1 (reference utils/losses.py:597-641)."""
     if S.size(-1) <= 1:
         return _reduce(S.new_zeros(S.size(0)), batch_reduction)
-    if _hosc_native(S) and S.dim() == 3:
+    if _native_f32(S) and S.dim() == 3:
         terms = _HOSCTermsFn.apply(S, None, None, ("dense", mask, None), (0.0, 1.0, 1.0, True))
         return _reduce(terms[1], batch_reduction)
     return _reduce(_hosc_ortho_composed(S, S.size(1) if mask is None else mask.sum(1)), batch_reduction)
@@ -795,7 +783,7 @@ def unbatched_hosc_orthogonality_loss(S: Tensor, batch: Optional[Tensor] = None,
     n, k = S.shape
     if k <= 1:
         return S.new_zeros(())
-    layout = _flat_layout(S, batch) if _hosc_native(S) and n > 0 else None
+    layout = _flat_layout(S, batch) if _native_f32(S) and n > 0 else None
     if layout is not None:
         terms = _HOSCTermsFn.apply(S, None, None, layout, (0.0, 1.0, 1.0, True))
         return _reduce(terms[1], batch_reduction)
@@ -817,7 +805,7 @@ def sparse_ho_mincut_loss(edge_index: Tensor, S: Tensor, edge_weight: Optional[T
     w = None if edge_weight is None else check_and_filter_edge_weights(edge_weight).view(-1)
     if edge_index.numel() == 0:
         return S.new_zeros(()) if nb == 1 else _reduce(S.new_zeros(nb), batch_reduction)
-    if _hosc_native(S, w) and S.dim() == 2 and n > 0 and not (w is not None and w.requires_grad):
+    if _native_f32(S, w) and S.dim() == 2 and n > 0 and not (w is not None and w.requires_grad):
         K.N.require_device(S, edge_index, w, batch)
         layout = _flat_layout(S, batch)
         if layout is not None:
@@ -949,18 +937,12 @@ class _BNPoolRecFn(torch.autograd.Function):
         return dS, dK, None, None
 
 
-def _bnpool_native(*ts) -> bool:
-    """float32 operands take the kernels (host tensors raise there: no CPU fallback); float64 takes the composed torch
-    forms."""
-    return not any(t is not None and t.dtype == torch.float64 for t in ts)
-
-
 def bnpool_rec_loss_terms(S: Tensor, K_: Tensor, adj: Tensor, mask: Optional[Tensor] = None) -> Tensor:
     """[B]: BN-Pool's reconstruction loss per graph, ``weighted_bce_reconstruction_loss(S K S^T, adj, mask,
     balance_links=True, normalizing_const=n^2, ...)`` before the batch reduction.  float32 device operands (``adj``
     without a gradient, K at most 256 clusters) run on the native route, which never forms the logits; float64 operands,
     a differentiable ``adj`` and wider K take the composed form.  float32 host tensors raise: there is no CPU fallback."""
-    if (_bnpool_native(S, K_, adj) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad):
+    if (_native_f32(S, K_, adj) and S.dim() == 3 and adj.dim() == 3 and not adj.requires_grad):
         K.N.require_device(S, K_, adj, mask)
         if S.size(-1) <= K.bnpool_max_clusters():
             return _BNPoolRecFn.apply(S, K_, adj, mask)
