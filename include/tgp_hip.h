@@ -1403,6 +1403,54 @@ int tgp_gather_pack_bucket_f32(const void* const* ptrs, const int64_t* dims, int
 int tgp_gather_unpack_bucket_f32(const void* gathered, int64_t capacity, int64_t rank_stride, int world,
                                  int64_t max_words, int num_steps, void* const* ptrs, const int64_t* dims, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * LaPool's selector (reference select/lapool_select.py), csrc/lapool.hip.  fp32, no float atomics, the same bits on
+ * every call; no buffer of N_total x K_total elements.
+ * Layouts.  Padded batch: ptr NULL, rows = B N, graph b owns rows b N .. b N + N - 1, `mask` ([B N] bytes, NULL = every
+ * row real) marks the real ones.  Un-padded batch: ptr [B + 1] (int64 row offsets), no mask, `batch` [rows] names each
+ * row's graph (NULL only with B <= 1); rows of a graph are contiguous.
+ *   variation   v_i = || deg_i x_i - sum_j a_ij x_j ||_2, deg_i = sum_j a_ij.  dense: rows and columns of padded nodes
+ *               count as zero, v = 0 on padded rows, one pass over A (16-byte loads when N % 4 == 0 and A is 16-byte
+ *               aligned).  csr: an edge list grouped by source (row_ptr [n + 1], perm [E] edge positions or NULL =
+ *               identity, col [E] by edge position, w NULL = ones); self-loops are dropped, duplicates add, an endpoint
+ *               outside [0, n) is skipped.
+ *   flags       1 where v_i >= v_j for every neighbour j (dense: a_ij != 0 on real columns; csr: the entries left after
+ *               self-loop removal, explicit zeros included), 0 elsewhere and on padded rows.
+ *   columns     per graph: with fallback != 0 a graph that has a real row and no leader makes every real row a leader
+ *               (flags is rewritten); col_of [rows] = a leader's rank among its graph's leaders, -1 otherwise;
+ *               leaders [rows]: graph b's leader rows, ascending, stored from the graph's first row on; k [B];
+ *               *k_max = max_b k_b (device word, zeroed by the call).
+ *   assign      nrm [rows] = ||x_i||_2 and S [rows, K]: a padded row is 0, a leader row its one-hot column, every other
+ *               row softmax_c( x_i . x_l(c) / (|x_i| |x_l(c)| + eps) ) over its own graph's k_b leaders; columns >= k_b
+ *               are 0.  K >= max_b k_b.
+ *   assign_bwd  dX [rows, F] from dS: through the softmax and the cosine to the row itself and to the leaders it was
+ *               compared with; leader and padded rows of dS are not read.  g1, g2 [rows, K] and alpha [rows] are work
+ *               buffers of the caller.
+ * TGP_ERR_INVALID: a NULL output or input, a layout that contradicts itself; TGP_ERR_RANGE: rows, N, F, K or E beyond
+ * the int32 internals.  Both are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_lapool_variation_dense_f32(const float* A, const float* X, int64_t B, int64_t N, int64_t F,
+                                   const uint8_t* mask /* NULL ok */, float* v, void* stream);
+int tgp_lapool_variation_csr_f32(const int32_t* row_ptr, const int32_t* perm /* NULL ok */, const int64_t* col,
+                                 const float* w /* NULL ok */, const float* X, int64_t n, int64_t E, int64_t F, float* v,
+                                 void* stream);
+int tgp_lapool_flags_dense_f32(const float* A, const float* v, int64_t B, int64_t N, const uint8_t* mask /* NULL ok */,
+                               uint8_t* flags, void* stream);
+int tgp_lapool_flags_csr_f32(const int32_t* row_ptr, const int32_t* perm /* NULL ok */, const int64_t* col,
+                             const float* v, int64_t n, int64_t E, uint8_t* flags, void* stream);
+int tgp_lapool_columns(uint8_t* flags, int64_t rows, int64_t B, int64_t N, const uint8_t* mask /* NULL ok */,
+                       const int64_t* ptr /* NULL: padded */, int fallback, int32_t* col_of, int32_t* leaders, int32_t* k,
+                       int64_t* k_max, void* stream);
+int tgp_lapool_assign_f32(const float* X, int64_t rows, int64_t F, int64_t B, int64_t N, const uint8_t* mask /* NULL ok */,
+                          const int64_t* ptr /* NULL: padded */, const int64_t* batch /* NULL ok */,
+                          const int32_t* col_of, const int32_t* leaders, const int32_t* k, int64_t K, float eps,
+                          float* nrm, float* S, void* stream);
+int tgp_lapool_assign_bwd_f32(const float* X, const float* nrm, const float* S, const float* dS, int64_t rows, int64_t F,
+                              int64_t B, int64_t N, const uint8_t* mask /* NULL ok */,
+                              const int64_t* ptr /* NULL: padded */, const int64_t* batch /* NULL ok */,
+                              const int32_t* col_of, const int32_t* leaders, const int32_t* k, int64_t K, float eps,
+                              float* g1, float* g2, float* alpha, float* dX, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

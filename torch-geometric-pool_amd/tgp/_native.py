@@ -164,6 +164,15 @@ SIGNATURES = {
     "tgp_edge_contract_rounds": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p,
                                           _c_p, _c_p]),
     "tgp_edge_contract_weights_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_lapool_variation_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_lapool_variation_csr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_lapool_flags_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_lapool_flags_csr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_lapool_columns": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_lapool_assign_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
+                                       _c_f, _c_p, _c_p, _c_p]),
+    "tgp_lapool_assign_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p,
+                                           _c_p, _c_p, _c_i64, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tgp_graclus_match_rounds": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_p]),
     "tgp_batch_facts_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p]),
     "tgp_batch_facts_sorted_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p, _c_p, _c_p, _c_p,

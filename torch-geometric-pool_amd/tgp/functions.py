@@ -1291,3 +1291,26 @@ def shared_products(s: Tensor, adj: Tensor) -> ASProducts:
     fresh = ASProducts(s, adj)
     _PRODUCTS[key] = fresh
     return fresh
+
+
+# --------------------------------------------------------------------------------------- LaPool's assignment
+class _LaPoolAssignFn(torch.autograd.Function):
+    """S = per-graph softmax over the cosine similarities to the graph's leaders.  The leader set is discrete and carries
+    no gradient; dX comes from the native backward (two launches, no N_total x K_total buffer)."""
+
+    @staticmethod
+    def forward(ctx, x, lead):
+        s, nrm = K.lapool_assign(x, lead)
+        ctx.save_for_backward(x, nrm, s)
+        ctx.lead = lead
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        x, nrm, s = ctx.saved_tensors
+        dx = K.lapool_assign_bwd(x, nrm, s, g.contiguous(), ctx.lead)
+        return dx.to(x.dtype), None
+
+
+def lapool_assign(x: Tensor, lead) -> Tensor:
+    return _LaPoolAssignFn.apply(x, lead) if _needs_grad(x) else K.lapool_assign(x, lead)[0]

@@ -3804,3 +3804,194 @@ def to_dense_batch(x: Tensor, batch: Tensor, ptr: Tensor, num_graphs: int, max_n
     N.check(N.lib().tgp_to_dense_batch_f32(N.ptr(x2), x2.size(0), F, N.ptr(batch), N.ptr(ptr), num_graphs, max_nodes,
                                            N.ptr(out), N.ptr(mask), N.stream_ptr(dev)), "tgp_to_dense_batch_f32")
     return out.view((num_graphs, max_nodes) + tuple(x.shape[1:])), mask
+
+
+# ------------------------------------------------------------------------- LaPool's selector (csrc/lapool.hip)
+class LaPoolLeaders:
+    """The leaders of one batch: ``flags`` (bool, the batch's shape without the feature axis), ``col_of`` int32 [rows]
+    (a leader's column inside its graph, -1 otherwise), ``leaders`` int32 [rows] (graph b's leader rows, ascending,
+    stored from the graph's first row on), ``k`` int32 [B] and ``k_max`` = max_b k_b.  Reading ``k_max`` is the
+    selector's one host wait.  The layout rides along: padded (``ptr`` None, ``N`` rows per graph, ``mask`` bytes or
+    None) or un-padded (``ptr`` [B + 1], ``batch`` [rows] or None with one graph)."""
+    __slots__ = ("flags", "col_of", "leaders", "k", "_k_max_dev", "_k_max", "rows", "B", "N", "mask", "ptr", "batch")
+
+    @property
+    def k_max(self) -> int:
+        if self._k_max is None:
+            self._k_max = _read_count(self._k_max_dev)
+        return self._k_max
+
+
+def _lapool_dense_args(x: Tensor, adj: Optional[Tensor], mask: Optional[Tensor]):
+    if x.dim() != 3:
+        raise ValueError(f"x must be [B, N, F], got {tuple(x.shape)}")
+    B, Nn = x.size(0), x.size(1)
+    if adj is not None and tuple(adj.shape) != (B, Nn, Nn):
+        raise ValueError(f"adj {tuple(adj.shape)} does not match x {tuple(x.shape)}")
+    return B, Nn, _mask_bytes(mask, B, Nn)
+
+
+def lapool_edge_group(edge_index: Tensor, num_nodes: int) -> AssignIndex:
+    """The edge positions grouped by source, edge-list order inside a node: the order every sum of the edge form adds in
+    (an empty list has an index of zeros: nothing to build).  Two routes: a list whose sources ascend needs only its
+    CSR offsets (``perm`` None); any other list gets the by-source index, whose build sorts (a fixed 8 MB scratch).  A
+    stable sort by source keeps each node's order, so both routes add the same numbers in the same order."""
+    if edge_index.size(1) == 0:
+        dev = edge_index.device
+        return AssignIndex(torch.zeros(num_nodes + 1, dtype=torch.int32, device=dev),
+                           torch.zeros(1, dtype=torch.int32, device=dev), 0, num_nodes)
+    row, _ = _edge_rows(edge_index)
+    if _rows_sorted(edge_index, row):
+        # the usual layout: the offsets are the whole index (perm None = identity), one launch and no sort workspace
+        return AssignIndex(csr_offsets(edge_index, num_nodes), None, edge_index.size(1), num_nodes)
+    return acc_edge_group(edge_index, num_nodes)
+
+
+def _lapool_by_src(edge_index: Tensor, num_nodes: int, by_src: Optional[AssignIndex]) -> AssignIndex:
+    if by_src is None:
+        by_src = lapool_edge_group(edge_index, num_nodes)
+    if by_src.num_targets != num_nodes or by_src.nnz != edge_index.size(1):
+        raise ValueError("the by-source index does not belong to this edge list")
+    return by_src
+
+
+def lapool_variation(x: Tensor, adj: Optional[Tensor] = None, mask: Optional[Tensor] = None, *,
+                     edge_index: Optional[Tensor] = None, edge_weight: Optional[Tensor] = None,
+                     by_src: Optional[AssignIndex] = None) -> Tensor:
+    """v_i = ||deg_i x_i - sum_j a_ij x_j||_2 (select/lapool_select.py:229-233, 366-376).  Padded form: ``x`` [B,N,F],
+    ``adj`` [B,N,N], ``mask`` [B,N] -> [B,N], one pass over ``adj``, padded rows and columns count as zero.  Edge form:
+    ``x`` [n,F], ``edge_index`` [2,E] (+ ``edge_weight``, + its by-source index) -> [n]; self-loops are dropped and
+    duplicates add, in edge-list order."""
+    if (adj is None) == (edge_index is None):
+        raise ValueError("lapool_variation takes either a padded adjacency or an edge list")
+    dev = N.require_device(x, adj, mask, edge_index, edge_weight)
+    x, st = N.f32c(x), N.stream_ptr(dev)
+    if adj is not None:
+        B, Nn, mb = _lapool_dense_args(x, adj, mask)
+        a = N.f32c(adj)
+        v = torch.empty(B, Nn, dtype=torch.float32, device=dev)
+        _checked(N.lib().tgp_lapool_variation_dense_f32, N.ptr(a), N.ptr(x), B, Nn, x.size(2), N.ptr(mb), N.ptr(v), st)
+        return v
+    if x.dim() != 2:
+        raise ValueError(f"x must be [n, F], got {tuple(x.shape)}")
+    n, E = x.size(0), edge_index.size(1)
+    v = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return v
+    _, col = _edge_rows(edge_index)
+    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if w is not None and w.numel() != E:
+        raise ValueError("lapool_variation: one weight per edge")
+    grp = _lapool_by_src(edge_index, n, by_src)
+    _checked(N.lib().tgp_lapool_variation_csr_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(col) if E else None,
+             N.ptr(w), N.ptr(x), n, E, x.size(1), N.ptr(v), st)
+    return v
+
+
+def lapool_columns(flags: Tensor, mask: Optional[Tensor] = None, batch: Optional[Tensor] = None,
+                   ptr: Optional[Tensor] = None, fallback: bool = False) -> LaPoolLeaders:
+    """Columns for a given leader mask: ``flags`` [B,N] (padded, with ``mask``) or [n] (un-padded, with the sorted
+    ``batch`` and its offsets ``ptr``, both None for one graph).  ``fallback``: a graph with a real node and no leader
+    makes all its real nodes leaders.  Padded rows never lead."""
+    dev = N.require_device(flags, mask, batch, ptr)
+    f = (flags if flags.dtype == torch.bool else flags != 0).contiguous().clone().view(torch.uint8)
+    res = LaPoolLeaders()
+    if f.dim() == 2:
+        B, Nn = f.shape
+        res.mask, res.ptr, res.batch = _mask_bytes(mask, B, Nn), None, None
+    elif f.dim() == 1:
+        if mask is not None:
+            raise ValueError("a mask belongs to a padded batch")
+        if (batch is None) != (ptr is None):
+            raise ValueError("an un-padded batch gives its batch vector and its offsets together")
+        Nn = 0
+        if batch is None:
+            ptr = torch.tensor([0, f.numel()], dtype=torch.int64, device=dev)
+        elif batch.numel() != f.numel():
+            raise ValueError("one batch entry per node")
+        res.mask, res.ptr, res.batch = None, N.i64c(ptr), None if batch is None else N.i64c(batch)
+        B = res.ptr.numel() - 1
+    else:
+        raise ValueError(f"flags must be [B, N] or [n], got {tuple(flags.shape)}")
+    rows = f.numel()
+    res.rows, res.B, res.N, res._k_max = rows, B, Nn, None
+    res.col_of = torch.empty(rows, dtype=torch.int32, device=dev)
+    res.leaders = torch.empty(rows, dtype=torch.int32, device=dev)
+    res.k = torch.empty(B, dtype=torch.int32, device=dev)
+    res._k_max_dev = torch.empty(1, dtype=torch.int64, device=dev)
+    _checked(N.lib().tgp_lapool_columns, N.ptr(f) if rows else None, rows, B, Nn, N.ptr(res.mask), N.ptr(res.ptr),
+             int(bool(fallback)), N.ptr(res.col_of), N.ptr(res.leaders), N.ptr(res.k), N.ptr(res._k_max_dev),
+             N.stream_ptr(dev))
+    res.flags = f.view(torch.bool)
+    return res
+
+
+def lapool_leaders(v: Tensor, adj: Optional[Tensor] = None, mask: Optional[Tensor] = None, *,
+                   edge_index: Optional[Tensor] = None, by_src: Optional[AssignIndex] = None,
+                   batch: Optional[Tensor] = None, ptr: Optional[Tensor] = None) -> LaPoolLeaders:
+    """leader_i = v_i >= v_j for every neighbour j (select/lapool_select.py:235-242, 378-388), then the fall-back of a
+    graph without a leader and the leaders' columns, all on the device.  Padded form: a second pass over ``adj``,
+    neighbours are the nonzero entries on real columns.  Edge form: the entries left after self-loop removal, explicit
+    zero weights included.  (The reference's "every Laplacian weight is zero" branch needs no code: v is 0 everywhere
+    then and every comparison holds.)"""
+    if (adj is None) == (edge_index is None):
+        raise ValueError("lapool_leaders takes either a padded adjacency or an edge list")
+    dev = N.require_device(v, adj, mask, edge_index, batch, ptr)
+    v, st = N.f32c(v), N.stream_ptr(dev)
+    flags = torch.empty(v.shape, dtype=torch.uint8, device=dev)
+    if adj is not None:
+        if v.dim() != 2 or tuple(adj.shape) != (v.size(0), v.size(1), v.size(1)):
+            raise ValueError(f"adj {tuple(adj.shape)} does not match v {tuple(v.shape)}")
+        B, Nn = v.shape
+        _checked(N.lib().tgp_lapool_flags_dense_f32, N.ptr(N.f32c(adj)), N.ptr(v), B, Nn, N.ptr(_mask_bytes(mask, B, Nn)),
+                 N.ptr(flags), st)
+        return lapool_columns(flags, mask=mask, fallback=True)
+    if v.dim() != 1:
+        raise ValueError(f"v must be [n], got {tuple(v.shape)}")
+    n, E = v.numel(), edge_index.size(1)
+    if n:
+        _, col = _edge_rows(edge_index)
+        grp = _lapool_by_src(edge_index, n, by_src)
+        _checked(N.lib().tgp_lapool_flags_csr_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(col) if E else None,
+                 N.ptr(v), n, E, N.ptr(flags), st)
+    return lapool_columns(flags, batch=batch, ptr=ptr, fallback=True)
+
+
+def _lapool_rows(x: Tensor, lead: LaPoolLeaders) -> Tensor:
+    x = N.f32c(x)
+    if x.numel() // max(x.size(-1), 1) != lead.rows or (x.dim() == 3) != (lead.ptr is None):
+        raise ValueError(f"x {tuple(x.shape)} does not match the leaders' batch of {lead.rows} rows")
+    return x
+
+
+def lapool_assign(x: Tensor, lead: LaPoolLeaders) -> Tuple[Tensor, Tensor]:
+    """(S, row norms): per graph the softmax over the cosine similarities to that graph's own leaders
+    (select/lapool_select.py:26-76, 274-311), leader rows one-hot, padded rows and the columns from k_b on zero.
+    S is [B,N,K_max] for a padded batch and [n,K_max] otherwise; nothing of size N_total x K_total is formed."""
+    dev = N.require_device(x, lead.col_of)
+    x = _lapool_rows(x, lead)
+    Kc, F = lead.k_max, x.size(-1)
+    s = torch.empty(tuple(x.shape[:-1]) + (Kc,), dtype=torch.float32, device=dev)
+    nrm = torch.empty(lead.rows, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_lapool_assign_f32, N.ptr(x), lead.rows, F, lead.B, lead.N, N.ptr(lead.mask), N.ptr(lead.ptr),
+             N.ptr(lead.batch), N.ptr(lead.col_of), N.ptr(lead.leaders), N.ptr(lead.k), Kc, ops_eps(), N.ptr(nrm),
+             N.ptr(s) if s.numel() else None, N.stream_ptr(dev))
+    return s, nrm
+
+
+def lapool_assign_bwd(x: Tensor, nrm: Tensor, s: Tensor, ds: Tensor, lead: LaPoolLeaders) -> Tensor:
+    """dX of `lapool_assign`: through the softmax and the cosine, to a row itself and to the leaders it was compared
+    with; leader and padded rows of ``ds`` pass nothing.  Work buffers: two [rows, K_max] and one [rows]."""
+    dev = N.require_device(x, nrm, s, ds)
+    x, s, ds = _lapool_rows(x, lead), N.f32c(s), N.f32c(ds)
+    if s.shape != ds.shape or s.shape[:-1] != x.shape[:-1]:
+        raise ValueError(f"s {tuple(s.shape)}, ds {tuple(ds.shape)} and x {tuple(x.shape)} do not match")
+    Kc = s.size(-1)
+    dx = torch.empty_like(x)
+    g = torch.empty(2, lead.rows, max(Kc, 1), dtype=torch.float32, device=dev)
+    alpha = torch.empty(max(lead.rows, 1), dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_lapool_assign_bwd_f32, N.ptr(x), N.ptr(nrm), N.ptr(s) if Kc else None,
+             N.ptr(ds) if Kc else None, lead.rows, x.size(-1), lead.B, lead.N, N.ptr(lead.mask), N.ptr(lead.ptr),
+             N.ptr(lead.batch), N.ptr(lead.col_of), N.ptr(lead.leaders), N.ptr(lead.k), Kc, ops_eps(), N.ptr(g[0]),
+             N.ptr(g[1]), N.ptr(alpha), N.ptr(dx) if dx.numel() else None, N.stream_ptr(dev))
+    return dx

@@ -1,11 +1,11 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction}.py).
+(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction,lapool}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
-``HOSCPooling``, ``BNPool`` and ``EdgeContractionPooling`` are built and exported as classes; their ``dmon`` / ``acc`` /
-``hosc`` / ``bnpool`` / ``edgepool`` aliases are not registered yet.
+``HOSCPooling``, ``BNPool``, ``EdgeContractionPooling`` and ``LaPooling`` are built and exported as classes; their
+``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``edgepool`` / ``lap`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from .. import kernels as K
 from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
-from ..select import DPSelect, EdgeContractionSelect, GraclusSelect, KMISSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
+from ..select import DPSelect, EdgeContractionSelect, GraclusSelect, KMISSelect, LaPoolSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
 from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling
 from ..utils.ops import batch_info, batched_negative_edge_sampling, is_dense_adj, negative_edge_sampling
 from ..utils.losses import (
@@ -1371,9 +1371,59 @@ class BNPool(_DenseMLPPooling):
                 "num_neg_samples": self.num_neg_samples}
 
 
+class LaPooling(DenseSRCPooling):
+    r"""LaPool (Noutahi et al. 2019; reference poolers/lapool.py): :class:`~tgp.select.LaPoolSelect`,
+    :class:`~tgp.reduce.BaseReduce`, :class:`~tgp.connect.DenseConnect`, :class:`~tgp.lift.BaseLift`.  No learned
+    layer and no auxiliary loss.  Constructor arguments, defaults, the batched / unbatched control flow, the
+    ``sparse_output`` finalisation and lifting follow the reference.
+
+    Differences from the reference: ``shortest_path_reg=True`` raises ``NotImplementedError`` (scipy on the host there);
+    the ``"lap"`` alias of ``get_pooler`` is not registered yet; see :class:`~tgp.select.LaPoolSelect` for the
+    selector's."""
+
+    def __init__(self, shortest_path_reg: bool = False, remove_self_loops: bool = True, degree_norm: bool = True,
+                 edge_weight_norm: bool = False, lift: str = "precomputed", s_inv_op: str = "transpose",
+                 lift_red_op: str = "sum", batched: bool = True, sparse_output: bool = False):
+        super().__init__(
+            selector=LaPoolSelect(shortest_path_reg=shortest_path_reg, batched_representation=batched,
+                                  s_inv_op=s_inv_op),
+            reducer=BaseReduce(),
+            lifter=BaseLift(matrix_op=lift, reduce_op=lift_red_op),
+            connector=DenseConnect(remove_self_loops=remove_self_loops, degree_norm=degree_norm,
+                                   edge_weight_norm=edge_weight_norm, sparse_output=sparse_output),
+            batched=batched, sparse_output=sparse_output)
+
+    def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None,
+                so: Optional[SelectOutput] = None, batch: Optional[Tensor] = None,
+                batch_pooled: Optional[Tensor] = None, lifting: bool = False, mask: Optional[Tensor] = None,
+                **kwargs):
+        if lifting:
+            return self.lift(x_pool=x, so=so, batch=batch if batch is not None else so.batch,
+                             batch_pooled=batch_pooled)
+        if self.batched:
+            x, adj, mask = self._ensure_batched_inputs(x=x, edge_index=adj, edge_weight=edge_weight, batch=batch,
+                                                       mask=mask)
+            so = self.select(x=x, edge_index=adj, mask=mask)
+            x_pool, batch_pooled = self.reduce(x=x, so=so, batch=batch)
+            adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
+                                       batch_pooled=batch_pooled)
+            if not self.sparse_output:
+                return PoolingOutput(x=x_pool, edge_index=adj_pool, so=so)
+            x_pool, ei, ew, batch_pooled = self._finalize_sparse_output(x_pool=x_pool, adj_pool=adj_pool, batch=batch,
+                                                                        batch_pooled=batch_pooled, so=so)
+            return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pooled, so=so)
+        so = self.select(x=x, edge_index=adj, edge_weight=edge_weight, batch=batch, num_nodes=x.size(0))
+        x_pool, batch_pooled = self.reduce(x=x, so=so, batch=batch, return_batched=not self.sparse_output)
+        ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch, batch_pooled=batch_pooled)
+        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pooled, so=so)
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched}
+
+
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool" and "edgepool" (EdgeContractionPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "edgepool" (EdgeContractionPooling) and "lap" (LaPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

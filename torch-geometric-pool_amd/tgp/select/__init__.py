@@ -1222,6 +1222,103 @@ class EdgeContractionSelect(Select):
                 f"add_to_edge_score={self.add_to_edge_score}, s_inv_op={self.s_inv_op})")
 
 
+# =============================================================================== LaPool
+class LaPoolSelect(Select):
+    r"""LaPool's selector (Noutahi et al. 2019; reference select/lapool_select.py): the nodes whose Laplacian variation
+    :math:`\|(\mathbf{L}\mathbf{X})_i\|` is no smaller than any neighbour's lead, and every other node is assigned to
+    its own graph's leaders by a softmax over cosine similarities.  Dense ``S``: ``[B, N, K_max]`` in batched mode,
+    ``[N, K_max]`` otherwise, graph b's leaders in columns ``0 .. k_b - 1`` in node order, zero beyond.
+
+    Native path (csrc/lapool.hip): two streaming passes over the adjacency, one column kernel per batch, one
+    :math:`n_b \times k_b` product per graph; a multi-graph unbatched call is one pass over the whole batch.  One host
+    wait (``K_max``).  The leader set is discrete and carries no gradient; ``x`` gets its gradient through the
+    assignment.
+
+    Differences from the reference, all stated:
+
+    - ``shortest_path_reg=True`` (scipy on the host there) is not built: the constructor raises.
+    - Device tensors only; arithmetic in fp32 (``S`` carries the dtype of ``x``).
+    - The output carries one more field, ``leader_mask`` (bool, ``[B, N]`` or ``[N]``): the leaders themselves, which
+      ``S`` alone does not identify in a graph with a single leader.
+    - An unbatched multi-graph call wants a sorted ``batch`` (the reference's ``unbatch`` assumes one too) and treats an
+      edge between two graphs as any other edge; an endpoint outside ``[0, N)`` is ignored instead of raising.
+    """
+
+    is_dense: bool = True
+
+    def __init__(self, shortest_path_reg: bool = False, batched_representation: bool = True,
+                 s_inv_op: str = "transpose"):
+        super().__init__()
+        if shortest_path_reg:
+            raise NotImplementedError("LaPoolSelect(shortest_path_reg=True) is not built here: the reference computes "
+                                      "all-pairs shortest paths with scipy on the host.")
+        self.s_inv_op = s_inv_op
+        self.shortest_path_reg = shortest_path_reg
+        self.batched_representation = batched_representation
+
+    def forward(self, x: Tensor, edge_index=None, edge_weight: Optional[Tensor] = None,
+                batch: Optional[Tensor] = None, mask: Optional[Tensor] = None, num_nodes: Optional[int] = None,
+                **kwargs) -> SelectOutput:
+        from ..utils.ops import is_dense_adj
+        if self.batched_representation:
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            elif x.dim() != 3:
+                raise ValueError("x must have shape [B, N, F].")
+            if not is_dense_adj(edge_index):
+                raise ValueError("Batched LaPoolSelect expects a dense adjacency tensor.")
+            if edge_index.dim() == 2:
+                edge_index = edge_index.unsqueeze(0)
+            elif edge_index.dim() != 3:
+                raise ValueError("Batched LaPoolSelect expects a dense adjacency tensor of shape [B, N, N].")
+            m = mask
+            if m is not None and m.dim() == 1:
+                m = m.unsqueeze(0)
+            s, leaders = self._assign(x, adj=edge_index, mask=m)
+            return SelectOutput(s=s, s_inv_op=self.s_inv_op, in_mask=mask, leader_mask=leaders)
+        if x.dim() != 2:
+            raise ValueError("x must have shape [N, F].")
+        if mask is not None:
+            raise ValueError("mask is only supported for batched representations.")
+        if is_dense_adj(edge_index):
+            raise ValueError("Unbatched LaPoolSelect expects a sparse adjacency tensor.")
+        edge_index, edge_weight = connectivity_to_edge_index(edge_index, edge_weight)
+        s, leaders = self._assign(x, edge_index=edge_index, edge_weight=edge_weight, batch=batch)
+        return SelectOutput(s=s, s_inv_op=self.s_inv_op, batch=batch, leader_mask=leaders)
+
+    @staticmethod
+    def _assign(x: Tensor, adj: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                edge_index: Optional[Tensor] = None, edge_weight: Optional[Tensor] = None,
+                batch: Optional[Tensor] = None):
+        """(S, leader flags) of one batch, padded (``adj``, ``mask``) or un-padded (``edge_index``, ``batch``)."""
+        from .. import _native, kernels
+        _native.require_device(x, adj, mask, edge_index, edge_weight, batch)
+        x32 = x if x.dtype == torch.float32 else x.to(torch.float32)
+        with torch.no_grad():  # the leader set is discrete
+            if adj is not None:
+                v = kernels.lapool_variation(x32, adj, mask)
+                lead = kernels.lapool_leaders(v, adj, mask)
+            else:
+                ptr = None
+                if batch is not None and batch.numel():
+                    from ..utils.ops import batch_info
+                    if batch.numel() != x.size(0):
+                        raise ValueError(f"batch has {batch.numel()} entries for {x.size(0)} nodes")
+                    if not batch_info(batch).is_sorted:
+                        raise ValueError("Unbatched LaPoolSelect expects a sorted batch vector.")
+                    _, ptr = graph_ptr(batch)
+                else:
+                    batch = None
+                by_src = kernels.lapool_edge_group(edge_index, x.size(0))
+                v = kernels.lapool_variation(x32, edge_index=edge_index, edge_weight=edge_weight, by_src=by_src)
+                lead = kernels.lapool_leaders(v, edge_index=edge_index, by_src=by_src, batch=batch, ptr=ptr)
+        s = Fn.lapool_assign(x32, lead)
+        return (s if s.dtype == x.dtype else s.to(x.dtype)), lead.flags
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(s_inv_op={self.s_inv_op}, shortest_path_reg={self.shortest_path_reg})"
+
+
 # =============================================================================== NDP
 import os as _os
 
@@ -1517,5 +1614,5 @@ class NDPSelect(Select):
 
 __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
-           "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster",
+           "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster", "LaPoolSelect",
            "degree_scorer"]
