@@ -15,38 +15,24 @@
 // min), an entry that finds its own key at both endpoints is matched, its endpoints are marked.  Min is order-independent,
 // so the result is a pure function of the inputs.  Two routes, same bits:
 //  * ec_graphs_kernel: one workgroup per graph of a sorted batch, node minima / flags / the first entries in LDS,
-//    __syncthreads() between the phases of a round; it finds its entries by searching `row` and CHECKS that each lies
-//    inside its graph (the check of kmis_graphs_kernel): otherwise the call is declined through the status word.
+//    __syncthreads() between the phases of a round, behind the frame of graph_frame.h (which finds and CHECKS the
+//    graph's entries, or declines the call through the status word).
 //  * device-wide rounds: two launches per round (push; decide + reset of the other minima buffer), one lane per entry,
 //    "some entry is still live" is a flag per round that the host reads every few rounds.  No grid-wide barrier, no
 //    persistent kernel.
 // Both write match [E] (bytes), label [N] (cluster[col[m]] = row[m]: the SOURCE represents the pair) and medge [N] (the
 // matched entry of a node, -1 for a singleton); tgp_graclus_relabel_i64 turns the labels into consecutive ids (flags +
 // exclusive scan, no sort), ec_weight_kernel hands the matched entry's score to both members.
-#include "common.h"
-#include "lookback.h"
+#include "graph_frame.h"
 
 namespace tgp {
 
-constexpr int EC_GRAPH_MAX = 1024;       // nodes of a graph the per-graph route holds in LDS (local ids are 16-bit pairs)
-constexpr int EC_EDGE_CACHE_MAX = 4096;  // entries of a graph staged in LDS (packed pair + prio); the rest stay in L2
 constexpr int EC_GROUP = 8;              // lanes that share one target in the softmax statistics pass
 constexpr int EC_HUB_DEGREE = 512;       // targets with more incoming entries get a whole workgroup each
 constexpr int EC_HUB_BLOCKS = 256;       // workgroups of the hub pass (each walks the hub queue with this stride)
-constexpr unsigned long long EC_INF = ~0ull;
-
-// float -> uint32 whose ASCENDING unsigned order is DESCENDING float order; -0 ties with +0 and every NaN sorts first,
-// as torch's descending sort has them (the mapping of the k-MIS selector's node keys)
-__device__ __forceinline__ uint32_t ec_desc_bits(float v) {
-  if (v != v) return 0u;
-  if (v == 0.0f) v = 0.0f;
-  const uint32_t b = __float_as_uint(v);
-  const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ~asc;
-}
 
 __device__ __forceinline__ uint32_t ec_prio(const int32_t* __restrict__ rank, const float* __restrict__ score, int64_t e) {
-  return rank ? static_cast<uint32_t>(rank[e]) : ec_desc_bits(score[e]);
+  return rank ? static_cast<uint32_t>(rank[e]) : desc_bits(score[e]);
 }
 
 // ------------------------------------------------------------------------------------------------ scores
@@ -227,69 +213,28 @@ __global__ __launch_bounds__(1024) void ec_graphs_kernel(EcGraphArgs p) {
   uint32_t* s_edge = reinterpret_cast<uint32_t*>(s_min + p.nmax);
   uint32_t* s_prio = s_edge + p.ecap;
   uint8_t* s_m = reinterpret_cast<uint8_t*>(s_prio + p.ecap);
-  __shared__ int64_t s_range[2];
 
+  GraphFrame f;
+  if (!graph_frame_open(p.row, p.col, p.E, p.N, p.gptr, p.nmax, p.ecap, s_edge, p.words, f,
+                        [&](int64_t e, int64_t pos) { s_prio[e] = ec_prio(p.rank, p.score, pos); }))
+    return;  // (uniform)
   const int T = blockDim.x, tid = threadIdx.x;
-  const int g = blockIdx.x;
-  const int64_t n0 = p.gptr[g], n1 = p.gptr[g + 1];
-  const int64_t n64 = n1 - n0;
-  if (n64 <= 0) return;  // (uniform)
-  if (n64 > p.nmax || n0 < 0 || n1 > p.N) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
-  const int n = static_cast<int>(n64);
-  if (tid < 64) {
-    const int64_t* const arr[2] = {p.row, p.row};
-    const int64_t len[2] = {p.E, p.E}, key[2] = {n0, n1};
-    int64_t res[2];
-    wave_lower_bounds<2>(arr, len, key, res);
-    if (tid == 0) {
-      s_range[0] = res[0];
-      s_range[1] = res[1];
-    }
-  }
-  __syncthreads();
-  const int64_t lo = s_range[0];
-  const int64_t ne = s_range[1] - lo;
-  if (ne < 0 || lo < 0 || s_range[1] > p.E) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
-  // every entry of the range must lie inside this graph; the first `ecap` of them are kept as packed local pairs with
-  // their priority word
-  int bad = 0;
-  for (int64_t e = tid; e < ne; e += T) {
-    const int64_t r = p.row[lo + e] - n0, c = p.col[lo + e] - n0;
-    if (r < 0 || r >= n || c < 0 || c >= n) {
-      bad = 1;
-    } else if (e < p.ecap) {
-      s_edge[e] = (static_cast<uint32_t>(r) << 16) | static_cast<uint32_t>(c);
-      s_prio[e] = ec_prio(p.rank, p.score, lo + e);
-    }
-  }
+  const int n = f.n;
+  const int64_t n0 = f.n0, lo = f.lo, ne = f.ne;
+  // a graph that declined leaves label / medge unwritten: they are meaningless on a declined call, and
+  // tgp_edge_contract_rounds_start sets both again.  The first barrier of the round loop orders s_m before its reads.
   for (int i = tid; i < n; i += T) {
     s_m[i] = 0;
     p.label[n0 + i] = n0 + i;
     p.medge[n0 + i] = -1;
   }
-  if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
   auto entry_at = [&](int64_t e, int& r, int& c) -> unsigned long long {
-    uint32_t prio;
-    if (e < p.ecap) {
-      const uint32_t pk = s_edge[e];
-      r = static_cast<int>(pk >> 16);
-      c = static_cast<int>(pk & 0xFFFFu);
-      prio = s_prio[e];
-    } else {
-      r = static_cast<int>(p.row[lo + e] - n0);
-      c = static_cast<int>(p.col[lo + e] - n0);
-      prio = ec_prio(p.rank, p.score, lo + e);
+    if (f.cached(e)) {
+      f.cached_edge(e, r, c);
+      return make_key(s_prio[e], e);
     }
-    return (static_cast<unsigned long long>(prio) << 32) | static_cast<unsigned long long>(e);
+    f.listed_edge(e, r, c);
+    return make_key(ec_prio(p.rank, p.score, lo + e), e);
   };
 
   // ---- rounds: each matches at least one entry (the live entry with the smallest key) and thereby retires at least one
@@ -297,7 +242,7 @@ __global__ __launch_bounds__(1024) void ec_graphs_kernel(EcGraphArgs p) {
   bool finished = false;
   int round = 0;
   for (; round <= n; ++round) {
-    for (int i = tid; i < n; i += T) s_min[i] = EC_INF;
+    for (int i = tid; i < n; i += T) s_min[i] = KEY_INF;
     __syncthreads();
     int open = 0;
     for (int64_t e = tid; e < ne; e += T) {
@@ -354,8 +299,7 @@ __global__ __launch_bounds__(256) void ec_push_kernel(const int64_t* __restrict_
   if (static_cast<uint64_t>(r) >= static_cast<uint64_t>(n) || static_cast<uint64_t>(c) >= static_cast<uint64_t>(n)) return;
   if (matched[r] || matched[c]) return;
   *open_flag = 1;
-  const unsigned long long key =
-      (static_cast<unsigned long long>(ec_prio(rank, score, e)) << 32) | static_cast<unsigned long long>(e);
+  const unsigned long long key = make_key(ec_prio(rank, score, e), e);
   // a minimum only ever decreases during the launch: a key that is not below what a plain load sees cannot win
   if (key < __hip_atomic_load(&nmin[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&nmin[r], key);
   if (c != r && key < __hip_atomic_load(&nmin[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&nmin[c], key);
@@ -377,9 +321,8 @@ __global__ __launch_bounds__(256) void ec_decide_kernel(const int64_t* __restric
     const int64_t r = row[idx], c = col[idx];
     if (static_cast<uint64_t>(r) >= static_cast<uint64_t>(n) || static_cast<uint64_t>(c) >= static_cast<uint64_t>(n)) return;
     const unsigned long long vr = nmin[r];
-    if (vr == EC_INF || (vr & 0xFFFFFFFFull) != static_cast<unsigned long long>(idx)) return;  // (the low word names the entry)
-    const unsigned long long key =
-        (static_cast<unsigned long long>(ec_prio(rank, score, idx)) << 32) | static_cast<unsigned long long>(idx);
+    if (vr == KEY_INF || (vr & 0xFFFFFFFFull) != static_cast<unsigned long long>(idx)) return;  // (the low word names the entry)
+    const unsigned long long key = make_key(ec_prio(rank, score, idx), idx);
     if (vr == key && nmin[c] == key) {
       match[idx] = 1;
       matched[r] = 1;
@@ -389,7 +332,7 @@ __global__ __launch_bounds__(256) void ec_decide_kernel(const int64_t* __restric
       medge[c] = idx;
     }
   } else if (idx < E + n) {
-    next_min[idx - E] = EC_INF;
+    next_min[idx - E] = KEY_INF;
   }
 }
 
@@ -427,8 +370,8 @@ static bool ec_sizes_ok(int64_t N, int64_t E) { return N >= 0 && E >= 0 && N < (
 
 using namespace tgp;
 
-extern "C" int tgp_edge_contract_max_graph_nodes(void) { return EC_GRAPH_MAX; }
-extern "C" int tgp_edge_contract_edge_cache(void) { return EC_EDGE_CACHE_MAX; }
+extern "C" int tgp_edge_contract_max_graph_nodes(void) { return FRAME_GRAPH_MAX; }
+extern "C" int tgp_edge_contract_edge_cache(void) { return FRAME_EDGE_CACHE_MAX; }
 extern "C" int tgp_edge_contract_hub_degree(void) { return EC_HUB_DEGREE; }
 
 extern "C" size_t tgp_edge_contract_workspace_bytes(int64_t num_nodes) {
@@ -518,9 +461,9 @@ extern "C" int tgp_edge_contract_graphs(const int64_t* row, const int64_t* col, 
   TGP_REQUIRE(ec_sizes_ok(N, E) && B >= 0 && B < (1ll << 31), TGP_ERR_INVALID, "tgp_edge_contract_graphs: bad argument");
   TGP_REQUIRE(E < (1ll << 32), TGP_ERR_RANGE, "tgp_edge_contract_graphs: %lld entries exceed the 32-bit entry positions",
               static_cast<long long>(E));
-  TGP_REQUIRE(max_graph_nodes >= 1 && max_graph_nodes <= EC_GRAPH_MAX, TGP_ERR_RANGE,
+  TGP_REQUIRE(max_graph_nodes >= 1 && max_graph_nodes <= FRAME_GRAPH_MAX, TGP_ERR_RANGE,
               "tgp_edge_contract_graphs: a graph of %d nodes does not fit one workgroup (max %d)", max_graph_nodes,
-              EC_GRAPH_MAX);
+              FRAME_GRAPH_MAX);
   TGP_REQUIRE(words && graph_ptr && (N == 0 || (label && medge)) && (E == 0 || (row && col && match && (rank || score))),
               TGP_ERR_INVALID, "tgp_edge_contract_graphs: null pointer");
   (void)hipMemsetAsync(words, 0, 2 * sizeof(int32_t), stream);
@@ -529,12 +472,10 @@ extern "C" int tgp_edge_contract_graphs(const int64_t* row, const int64_t* col, 
   EcGraphArgs p;
   p.row = row; p.col = col; p.E = E; p.N = N; p.gptr = graph_ptr; p.score = score; p.rank = rank;
   p.match = match; p.label = label; p.medge = medge; p.words = words;
-  p.nmax = (max_graph_nodes + 63) / 64 * 64;
-  const int ecap = 16 * p.nmax;
-  p.ecap = ecap > EC_EDGE_CACHE_MAX ? EC_EDGE_CACHE_MAX : ecap;
-  const int threads = p.nmax <= 64 ? 64 : (p.nmax <= 256 ? 256 : 1024);
+  const FrameGeometry geo = graph_frame_geometry(max_graph_nodes);
+  p.nmax = geo.nmax; p.ecap = geo.ecap;
   const size_t lds = static_cast<size_t>(p.nmax) * (sizeof(unsigned long long) + 1) + static_cast<size_t>(p.ecap) * 8;
-  hipLaunchKernelGGL(ec_graphs_kernel, dim3(static_cast<unsigned>(B)), dim3(threads), lds, stream, p);
+  hipLaunchKernelGGL(ec_graphs_kernel, dim3(static_cast<unsigned>(B)), dim3(geo.threads), lds, stream, p);
   return check_launch("tgp_edge_contract_graphs");
 }
 

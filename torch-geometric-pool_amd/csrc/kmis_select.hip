@@ -12,32 +12,16 @@
 // leave the result a pure function of the inputs.
 //
 // Two routes, same results bit for bit:
-//  * kmis_graphs_kernel: one workgroup per graph of a sorted batch, everything in LDS, __syncthreads() between hops.
-//    It finds its edges by searching `row` for its node range and CHECKS that every edge it finds lies inside its
-//    graph; the ranges of consecutive graphs tile [0, E), so a list that is not grouped by graph, or has an edge between
-//    two graphs, fails that check in some workgroup and the call is declined (status word), never misread.
+//  * kmis_graphs_kernel: one workgroup per graph of a sorted batch, everything in LDS, __syncthreads() between hops,
+//    behind the frame of graph_frame.h: a list that is not grouped by graph, or has an edge between two graphs, is
+//    declined (status word), never misread.
 //  * device-wide rounds: one launch per hop, one lane per edge pushing with a 64-bit atomic min into the destination
 //    (a hub of degree 100 000 is 100 000 independent lanes, not one long row), three rotating buffers so that a hop
 //    reads X, writes Y and resets Z without a launch of its own.  "Some node is still unmasked" is a flag per round the
 //    host reads every few rounds.  No grid-wide barrier, no persistent kernel.
-#include "common.h"
-#include "lookback.h"
+#include "graph_frame.h"
 
 namespace tgp {
-
-constexpr int KM_GRAPH_MAX = 1024;  // nodes of a graph the per-graph route holds in LDS (local ids are 16-bit pairs)
-constexpr int KM_EDGE_CACHE_MAX = 4096;  // edges of a graph staged in LDS as packed local pairs; the rest stay in L2
-constexpr unsigned long long KM_INF = ~0ull;
-
-// float -> uint32 whose ASCENDING unsigned order is DESCENDING float order; -0 ties with +0 and every NaN sorts first,
-// as torch's descending sort has them
-__device__ __forceinline__ uint32_t km_desc_bits(float v) {
-  if (v != v) return 0u;
-  if (v == 0.0f) v = 0.0f;
-  const uint32_t b = __float_as_uint(v);
-  const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ~asc;
-}
 
 // ------------------------------------------------------------------------------------------------ per-graph route
 struct KmGraphArgs {
@@ -64,60 +48,13 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
   uint8_t* s_mask = s_mis + p.nmax;
   uint8_t* s_ma = s_mask + p.nmax;
   uint8_t* s_mb = s_ma + p.nmax;
-  __shared__ int64_t s_range[2];
 
+  GraphFrame f;
+  if (!graph_frame_open(p.row, p.col, p.E, p.N, p.gptr, p.nmax, p.ecap, s_edge, p.words, f, [](int64_t, int64_t) {}))
+    return;  // (uniform)
   const int T = blockDim.x, tid = threadIdx.x;
-  const int g = blockIdx.x;
-  const int64_t n0 = p.gptr[g], n1 = p.gptr[g + 1];
-  const int64_t n64 = n1 - n0;
-  if (n64 <= 0) return;  // (uniform)
-  if (n64 > p.nmax || n0 < 0 || n1 > p.N) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
-  const int n = static_cast<int>(n64);
-  if (tid < 64) {
-    const int64_t* const arr[2] = {p.row, p.row};
-    const int64_t len[2] = {p.E, p.E}, key[2] = {n0, n1};
-    int64_t res[2];
-    wave_lower_bounds<2>(arr, len, key, res);
-    if (tid == 0) {
-      s_range[0] = res[0];
-      s_range[1] = res[1];
-    }
-  }
-  __syncthreads();
-  const int64_t lo = s_range[0];
-  const int64_t ne64 = s_range[1] - lo;
-  if (ne64 < 0 || lo < 0 || s_range[1] > p.E) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
-  const int64_t ne = ne64;
-  // every edge of the range must lie inside this graph; the first `ecap` of them are kept as packed local pairs
-  int bad = 0;
-  for (int64_t e = tid; e < ne; e += T) {
-    const int64_t r = p.row[lo + e] - n0, c = p.col[lo + e] - n0;
-    if (r < 0 || r >= n || c < 0 || c >= n) {
-      bad = 1;
-    } else if (e < p.ecap) {
-      s_edge[e] = (static_cast<uint32_t>(r) << 16) | static_cast<uint32_t>(c);
-    }
-  }
-  if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.words, 1);
-    return;
-  }
-  auto edge_at = [&](int64_t e, int& r, int& c) {
-    if (e < p.ecap) {
-      const uint32_t pk = s_edge[e];
-      r = static_cast<int>(pk >> 16);
-      c = static_cast<int>(pk & 0xFFFFu);
-    } else {
-      r = static_cast<int>(p.row[lo + e] - n0);
-      c = static_cast<int>(p.col[lo + e] - n0);
-    }
-  };
+  const int n = f.n;
+  const int64_t n0 = f.n0, ne = f.ne;
 
   // ---- priorities
   if (p.mode == 2) {
@@ -129,7 +66,7 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
       __syncthreads();
       for (int64_t e = tid; e < ne; e += T) {
         int r, c;
-        edge_at(e, r, c);
+        f.edge_at(e, r, c);
         atomicAdd(&s_b[c], s_a[r]);
       }
       __syncthreads();
@@ -148,9 +85,9 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
         u = u / static_cast<float>(s_a[i]);
         p.updated[n0 + i] = u;
       }
-      prio = km_desc_bits(u);
+      prio = desc_bits(u);
     }
-    s_key[i] = (static_cast<unsigned long long>(prio) << 32) | static_cast<unsigned long long>(i);
+    s_key[i] = make_key(prio, i);
     s_mis[i] = 0;
     s_mask[i] = 0;
   }
@@ -164,7 +101,7 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
       int changed = 0;
       for (int64_t e = tid; e < ne; e += T) {
         int r, c;
-        edge_at(e, r, c);
+        f.edge_at(e, r, c);
         const unsigned long long v = s_a[r];
         if (v < s_a[c]) {  // (s_b[c] <= s_a[c]: anything not below s_a[c] cannot lower it)
           atomicMin(&s_b[c], v);
@@ -186,7 +123,7 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
     for (int i = tid; i < n; i += T) {
       const bool m = s_mask[i] != 0;
       open |= !m;
-      s_a[i] = m ? KM_INF : s_key[i];
+      s_a[i] = m ? KEY_INF : s_key[i];
     }
     if (!__syncthreads_or(open)) {
       finished = true;
@@ -204,7 +141,7 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
       int changed = 0;
       for (int64_t e = tid; e < ne; e += T) {
         int r, c;
-        edge_at(e, r, c);
+        f.edge_at(e, r, c);
         if (s_ma[r] && !s_ma[c]) {
           s_mb[c] = 1;
           changed = 1;
@@ -224,12 +161,12 @@ __global__ __launch_bounds__(1024) void kmis_graphs_kernel(KmGraphArgs p) {
     return;
   }
   // ---- clusters: the MIS keys travel k hops; the low word of what arrives names the owner
-  for (int i = tid; i < n; i += T) s_a[i] = s_mis[i] ? s_key[i] : KM_INF;
+  for (int i = tid; i < n; i += T) s_a[i] = s_mis[i] ? s_key[i] : KEY_INF;
   __syncthreads();
   min_hops();
   for (int i = tid; i < n; i += T) {
     const unsigned long long v = s_a[i];
-    p.label[n0 + i] = n0 + (v == KM_INF ? static_cast<int64_t>(i) : static_cast<int64_t>(v & 0xFFFFFFFFull));
+    p.label[n0 + i] = n0 + (v == KEY_INF ? static_cast<int64_t>(i) : static_cast<int64_t>(v & 0xFFFFFFFFull));
   }
 }
 
@@ -238,8 +175,8 @@ __global__ __launch_bounds__(256) void kmis_key_kernel(const int32_t* __restrict
                                                        int64_t n, unsigned long long* __restrict__ key) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint32_t prio = rank ? static_cast<uint32_t>(rank[i]) : km_desc_bits(upd[i]);
-  key[i] = (static_cast<unsigned long long>(prio) << 32) | static_cast<unsigned long long>(i);
+  const uint32_t prio = rank ? static_cast<uint32_t>(rank[i]) : desc_bits(upd[i]);
+  key[i] = make_key(prio, i);
 }
 
 // One hop of min.  Items [0, E) are edges (push src(row) into y[col]), items [E, E + N) are nodes (push the node's own
@@ -255,8 +192,8 @@ __global__ __launch_bounds__(256) void kmis_min_hop_kernel(const int64_t* __rest
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   auto src = [&](int64_t i) -> unsigned long long {
     if (SRC == 0) return x[i];
-    if (SRC == 1) return sel[i] ? KM_INF : key[i];
-    return sel[i] ? key[i] : KM_INF;
+    if (SRC == 1) return sel[i] ? KEY_INF : key[i];
+    return sel[i] ? key[i] : KEY_INF;
   };
   if (idx < E) {
     const int64_t r = row[idx], c = col[idx];
@@ -265,15 +202,15 @@ __global__ __launch_bounds__(256) void kmis_min_hop_kernel(const int64_t* __rest
       return;
     const unsigned long long v = src(r);
     // the destination only ever decreases during the hop: a value that is not below what a plain load sees cannot win
-    if (v != KM_INF && v < __hip_atomic_load(&y[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&y[c], v);
+    if (v != KEY_INF && v < __hip_atomic_load(&y[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&y[c], v);
   } else if (idx < E + n) {
     const int64_t i = idx - E;
     const unsigned long long v = src(i);
-    if (v != KM_INF) {
+    if (v != KEY_INF) {
       atomicMin(&y[i], v);
       if (SRC == 1) *open_flag = 1;
     }
-    z[i] = KM_INF;
+    z[i] = KEY_INF;
   }
 }
 
@@ -313,7 +250,7 @@ __global__ __launch_bounds__(256) void kmis_label_kernel(const unsigned long lon
   if (i >= n) return;
   const unsigned long long v = f[i];
   const int64_t o = static_cast<int64_t>(v & 0xFFFFFFFFull);
-  label[i] = (v == KM_INF || o >= n) ? i : o;
+  label[i] = (v == KEY_INF || o >= n) ? i : o;
 }
 
 // ---- "greedy": counts of (A^T + I)^k 1, device-wide, same three-buffer rotation (y and z start at zero)
@@ -401,7 +338,7 @@ static KmWs km_carve(void* ws, int64_t n) {
 
 using namespace tgp;
 
-extern "C" int tgp_kmis_max_graph_nodes(void) { return KM_GRAPH_MAX; }
+extern "C" int tgp_kmis_max_graph_nodes(void) { return FRAME_GRAPH_MAX; }
 
 extern "C" size_t tgp_kmis_workspace_bytes(int64_t num_nodes) {
   const size_t n = static_cast<size_t>(num_nodes > 0 ? num_nodes : 1);
@@ -422,8 +359,8 @@ extern "C" int tgp_kmis_graphs(const int64_t* row, const int64_t* col, int64_t E
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   TGP_REQUIRE(km_args_ok(N, E, order_k) && B >= 0 && B < (1ll << 31) && mode >= 0 && mode <= 2, TGP_ERR_INVALID,
               "tgp_kmis_graphs: bad argument");
-  TGP_REQUIRE(max_graph_nodes >= 1 && max_graph_nodes <= KM_GRAPH_MAX, TGP_ERR_RANGE,
-              "tgp_kmis_graphs: a graph of %d nodes does not fit one workgroup (max %d)", max_graph_nodes, KM_GRAPH_MAX);
+  TGP_REQUIRE(max_graph_nodes >= 1 && max_graph_nodes <= FRAME_GRAPH_MAX, TGP_ERR_RANGE,
+              "tgp_kmis_graphs: a graph of %d nodes does not fit one workgroup (max %d)", max_graph_nodes, FRAME_GRAPH_MAX);
   TGP_REQUIRE(words && graph_ptr && label && (E == 0 || (row && col)) && (mode == 0 ? rank != nullptr : score != nullptr) &&
                   (mode != 2 || updated),
               TGP_ERR_INVALID, "tgp_kmis_graphs: null pointer");
@@ -432,12 +369,10 @@ extern "C" int tgp_kmis_graphs(const int64_t* row, const int64_t* col, int64_t E
   KmGraphArgs p;
   p.row = row; p.col = col; p.E = E; p.N = N; p.gptr = graph_ptr; p.k = order_k; p.mode = mode;
   p.score = score; p.rank = rank; p.updated = updated; p.label = label; p.words = words;
-  p.nmax = (max_graph_nodes + 63) / 64 * 64;
-  int ecap = 16 * p.nmax;
-  p.ecap = ecap > KM_EDGE_CACHE_MAX ? KM_EDGE_CACHE_MAX : ecap;
-  const int threads = p.nmax <= 64 ? 64 : (p.nmax <= 256 ? 256 : 1024);
+  const FrameGeometry geo = graph_frame_geometry(max_graph_nodes);
+  p.nmax = geo.nmax; p.ecap = geo.ecap;
   const size_t lds = static_cast<size_t>(p.nmax) * (3 * sizeof(unsigned long long) + 4) + static_cast<size_t>(p.ecap) * 4;
-  hipLaunchKernelGGL(kmis_graphs_kernel, dim3(static_cast<unsigned>(B)), dim3(threads), lds, stream, p);
+  hipLaunchKernelGGL(kmis_graphs_kernel, dim3(static_cast<unsigned>(B)), dim3(geo.threads), lds, stream, p);
   return check_launch("tgp_kmis_graphs");
 }
 

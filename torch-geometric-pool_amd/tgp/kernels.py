@@ -2148,9 +2148,10 @@ def acc_tv_dense_bwd(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor], g_tv
     return ds
 
 
-def acc_edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = False) -> AssignIndex:
-    """The edge positions grouped by source (the forward's order) or by destination (needed by the backward only),
-    edge-list order inside a group: the summation order of the edge-form total variation."""
+def edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = False) -> AssignIndex:
+    """The edge positions grouped by source or by destination, edge-list order inside a group: the summation order of
+    every float sum that runs over a node's edges (the edge-form total variation and its backward, the k-MIS degrees and
+    "w-greedy" scores, the edge-contraction softmax, LaPool's by-source sums)."""
     row, col = _edge_rows(edge_index)
     return build_assign_index(col if by_destination else row, num_nodes)
 
@@ -2529,14 +2530,79 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
     return finish()
 
 
+# ------------------------------------------- what the k-MIS and edge-contraction selectors share (csrc/graph_frame.h)
+def _rank_of(count: int, perm: Optional[Tensor], what: str, dev) -> Tensor:
+    """int32 [count]: the rank ``perm`` gives every item (first = 0); the list order for None."""
+    if perm is None:
+        return torch.arange(count, dtype=torch.int32, device=dev)
+    if perm.numel() != count:
+        raise ValueError(f"perm must have one entry per {what} ({count}), got {perm.numel()}")
+    rank = torch.empty(count, dtype=torch.int32, device=dev)
+    rank[perm.reshape(-1)] = torch.arange(count, dtype=torch.int32, device=dev)
+    return rank
+
+
+def _frame_route(limit: str, need_edges: bool, num_nodes: int, num_edges: int, graph_ptr: Optional[Tensor],
+                 max_graph_nodes: Optional[int], route: Optional[str] = None) -> str:
+    """"graphs" (one workgroup per graph) for a sorted batch whose longest graph fits the frame (``limit``: the getter of
+    the selector's bound), "rounds" (device-wide launches) for everything else; ``route`` overrides, where it can."""
+    fits = (graph_ptr is not None and max_graph_nodes is not None and graph_ptr.numel() >= 2 and num_nodes > 0
+            and (num_edges > 0 or not need_edges) and 0 < max_graph_nodes <= getattr(N.lib(), limit)())
+    if route is None:
+        return "graphs" if fits else "rounds"
+    if route not in ("graphs", "rounds"):
+        raise ValueError(f"route must be 'graphs' or 'rounds', got {route!r}")
+    if route == "graphs" and not fits:
+        raise ValueError("the per-graph route needs a sorted batch whose longest graph fits one workgroup")
+    return route
+
+
+def _frame_done(status: int, name: str, route: Optional[str], what: str) -> bool:
+    """The status word of a per-graph launch: True = every graph done, False = declined (the device-wide route goes on)."""
+    if status == 0:
+        return True
+    if status & 2:
+        raise N.TgpNativeError(f"{name}: a graph did not finish within its round bound")
+    if route == "graphs":
+        raise N.TgpNativeError(f"{name} declined: the edge list is not grouped by graph or {what} joins two graphs")
+    return False
+
+
+def _run_rounds(launch, n: int, name: str, what: str, dev) -> Tuple[int, int]:
+    """Device-wide rounds in batches of 4, 8, ... 256, one host wait per batch: ``launch(done, step, flags)`` enqueues
+    rounds done .. done + step - 1, flags[j] = 0 for an idle one.  Returns (rounds launched, index of the first idle round)."""
+    done, step, idle = 0, 4, None
+    while idle is None:
+        if done >= n + 4:  # every round retires a node while anything is left: n rounds is a hard cap
+            raise N.TgpNativeError(f"{name}: {what} is not maximal after num_nodes rounds")
+        flags = torch.empty(step, dtype=torch.int32, device=dev)
+        launch(done, step, flags)
+        got = flags.tolist()  # one host wait per batch of rounds
+        if 0 in got:
+            idle = done + got.index(0)
+        done += step
+        step = min(2 * step, 256)  # a long tail means chain-like structure: more rounds per host wait
+    return done, idle
+
+
+def _owner_labels(n: int, name: str, dev, st):
+    """(label [n], index [2, n], words [4] int32, relabel): ``relabel()`` numbers the owners (label[i] == i) consecutively
+    into ``index`` (flags + exclusive scan, no sort, no torch.unique) and leaves their count in words[2:] as one int64."""
+    L = N.lib()
+    if n > L.tgp_graclus_relabel_max_nodes():
+        raise N.TgpNativeError(f"{name}: {n} nodes exceed the relabelling kernels' {L.tgp_graclus_relabel_max_nodes()}")
+    label = torch.empty(n, dtype=torch.int64, device=dev)
+    index = torch.empty(2, n, dtype=torch.int64, device=dev)
+    words = torch.empty(4, dtype=torch.int32, device=dev)
+    rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
+
+    def relabel():
+        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
+                                          None, None, None, st), "tgp_graclus_relabel_i64")
+    return label, index, words, relabel
+
+
 # ------------------------------------------------------------------------- k-MIS selection (csrc/kmis_select.hip)
-def _dest_groups(edge_index: Tensor, num_nodes: int) -> AssignIndex:
-    """Edge positions grouped by destination, edge-list order inside a group: the summation order of every float sum of
-    the k-MIS selector."""
-    _, col = _edge_rows(edge_index)
-    return build_assign_index(col, num_nodes)
-
-
 def kmis_degree(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: int) -> Tensor:
     """Weighted in-degree (select/kmis_select.py:21-32): deg[c] = sum of the weights of the edges into c, added in
     edge-list order (no float atomics: the same bits on every call)."""
@@ -2545,7 +2611,7 @@ def kmis_degree(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: in
     if num_nodes == 0 or edge_index.size(1) == 0:
         return out
     w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
-    grp = _dest_groups(edge_index, num_nodes)
+    grp = edge_group(edge_index, num_nodes, by_destination=True)
     N.check(N.lib().tgp_kmis_degree_f32(N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(w), num_nodes, N.ptr(out),
                                         N.stream_ptr(dev)), "tgp_kmis_degree_f32")
     return out
@@ -2572,7 +2638,7 @@ def kmis_updated_score(score: Tensor, edge_index: Tensor, order_k: int, heuristi
         raise ValueError(f"Unrecognized `score_heuristic` value: {heuristic}")
     if order_k <= 0 or E == 0:
         return score / score
-    grp = _dest_groups(edge_index, n)
+    grp = edge_group(edge_index, n, by_destination=True)
     cur, spare = score, [torch.empty_like(score), torch.empty_like(score)] if order_k > 1 else []
     for h in range(order_k):
         last = h == order_k - 1
@@ -2591,12 +2657,8 @@ class KMISResult:
 
 
 def kmis_route(num_nodes: int, num_edges: int, graph_ptr: Optional[Tensor], max_graph_nodes: Optional[int]) -> str:
-    """The route a selection takes, from what the host already knows: "graphs" (one workgroup per graph) for a sorted
-    batch whose longest graph fits one workgroup, "rounds" (device-wide launches per hop) for everything else."""
-    if (graph_ptr is not None and max_graph_nodes is not None and graph_ptr.numel() >= 2 and num_nodes > 0
-            and 0 < max_graph_nodes <= N.lib().tgp_kmis_max_graph_nodes()):
-        return "graphs"
-    return "rounds"
+    """The route a selection takes, from what the host already knows (:func:`_frame_route`)."""
+    return _frame_route("tgp_kmis_max_graph_nodes", False, num_nodes, num_edges, graph_ptr, max_graph_nodes)
 
 
 def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Optional[Tensor] = None,
@@ -2620,39 +2682,21 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
         res.index = torch.empty(2, 0, dtype=torch.int64, device=dev)
         res.k, res.mis, res.route = 0, torch.empty(0, dtype=torch.int64, device=dev), "rounds"
         return res
-    if n > L.tgp_graclus_relabel_max_nodes():
-        raise N.TgpNativeError(f"kmis_select: {n} nodes exceed the relabelling kernels' "
-                               f"{L.tgp_graclus_relabel_max_nodes()}")
     rank = None
-    if perm is not None:
-        if perm.numel() != n:
-            raise ValueError(f"perm must have one entry per node ({n}), got {perm.numel()}")
-        rank = torch.empty(n, dtype=torch.int32, device=dev)
-        rank[perm.reshape(-1)] = torch.arange(n, dtype=torch.int32, device=dev)
-    elif score is None:
-        rank = torch.arange(n, dtype=torch.int32, device=dev)
+    if perm is not None or score is None:
+        rank = _rank_of(n, perm, "node", dev)
     else:
         score = N.f32c(score.reshape(-1))
         if score.numel() != n:
             raise ValueError(f"score must have one entry per node ({n}), got {score.numel()}")
         if heuristic not in (None, "greedy", "w-greedy"):
             raise ValueError(f"Unrecognized `score_heuristic` value: {heuristic}")
-    want = kmis_route(n, E, graph_ptr, max_graph_nodes)
-    if route is not None:
-        if route not in ("graphs", "rounds"):
-            raise ValueError(f"route must be 'graphs' or 'rounds', got {route!r}")
-        if route == "graphs" and want != "graphs":
-            raise ValueError("the per-graph route needs a sorted batch whose longest graph fits one workgroup")
-        want = route
-    label = torch.empty(n, dtype=torch.int64, device=dev)
-    index = torch.empty(2, n, dtype=torch.int64, device=dev)
+    want = _frame_route("tgp_kmis_max_graph_nodes", False, n, E, graph_ptr, max_graph_nodes, route)
+    label, index, words, relabel_owners = _owner_labels(n, "kmis_select", dev, st)  # words: [status, -, K (int64)]
     mis = torch.empty(n, dtype=torch.int64, device=dev)
-    words = torch.empty(4, dtype=torch.int32, device=dev)  # [status, -, K (int64)]
-    rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
 
     def relabel():
-        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
-                                          None, None, None, st), "tgp_graclus_relabel_i64")
+        relabel_owners()
         N.check(L.tgp_kmis_mis_index_i64(N.ptr(label), N.ptr(index), n, N.ptr(mis), st), "tgp_kmis_mis_index_i64")
 
     updated = None
@@ -2668,30 +2712,20 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
                                   N.ptr(label), N.ptr(words), st), "tgp_kmis_graphs")
         relabel()
         got = words.tolist()  # the one host wait: status and K together
-        if got[0] == 0:
+        if _frame_done(got[0], "tgp_kmis_graphs", route, "an edge"):
             res.index, res.k, res.mis, res.updated, res.route = index, int(got[2]), mis[:int(got[2])], updated, "graphs"
             return res
-        if got[0] & 2:
-            raise N.TgpNativeError("tgp_kmis_graphs: a graph did not finish within its round bound")
-        if route == "graphs":
-            raise N.TgpNativeError("tgp_kmis_graphs declined: the edge list is not grouped by graph or an edge joins "
-                                   "two graphs")
         if mode == 2:
             updated = None  # (graphs that declined left theirs unwritten)
     if rank is None and updated is None:
         updated = kmis_updated_score(score, edge_index, k, heuristic)
     ws = N.workspace(L.tgp_kmis_workspace_bytes(n), dev)
     N.check(L.tgp_kmis_rounds_start(N.ptr(rank), N.ptr(updated), n, N.ptr(ws), ws.numel(), st), "tgp_kmis_rounds_start")
-    done, step, finished = 0, 4, False
-    while not finished:
-        if done >= n + 4:  # a round adds a node while an unmasked one exists: n rounds is a hard cap
-            raise N.TgpNativeError("tgp_kmis_rounds: the set is not maximal after num_nodes rounds")
-        flags = torch.empty(step, dtype=torch.int32, device=dev)
+
+    def launch(done, step, flags):
         N.check(L.tgp_kmis_rounds(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, step, N.ptr(flags), st),
                 "tgp_kmis_rounds")
-        done += step
-        finished = 0 in flags.tolist()  # one host wait per batch of rounds
-        step = min(2 * step, 256)  # a long tail means chain-like structure: more rounds per host wait
+    done, _ = _run_rounds(launch, n, "tgp_kmis_rounds", "the set", dev)
     N.check(L.tgp_kmis_clusters(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, N.ptr(label), st), "tgp_kmis_clusters")
     relabel()
     kk = int(words.tolist()[2])
@@ -2747,7 +2781,7 @@ def edge_contract_normalize(raw: Tensor, edge_index: Optional[Tensor], num_nodes
         _, col = _edge_rows(edge_index)
         if col.numel() != E:
             raise ValueError(f"raw must have one entry per edge ({col.numel()}), got {E}")
-        grp = _dest_groups(edge_index, n)
+        grp = edge_group(edge_index, n, by_destination=True)
         seg = torch.empty(2 * max(n, 1), dtype=torch.float32, device=dev)
         cap = E // int(L.tgp_edge_contract_hub_degree()) + 1
         hubs = torch.empty(cap + 1, dtype=torch.int32, device=dev)
@@ -2785,12 +2819,8 @@ class EdgeContractResult:
 
 def edge_contract_route(num_nodes: int, num_edges: int, graph_ptr: Optional[Tensor],
                         max_graph_nodes: Optional[int]) -> str:
-    """The route a matching takes, from what the host already knows: "graphs" (one workgroup per graph) for a sorted
-    batch whose longest graph fits one workgroup, "rounds" (device-wide launches per round) for everything else."""
-    if (graph_ptr is not None and max_graph_nodes is not None and graph_ptr.numel() >= 2 and num_nodes > 0
-            and num_edges > 0 and 0 < max_graph_nodes <= N.lib().tgp_edge_contract_max_graph_nodes()):
-        return "graphs"
-    return "rounds"
+    """The route a matching takes, from what the host already knows (:func:`_frame_route`; no entries: "rounds")."""
+    return _frame_route("tgp_edge_contract_max_graph_nodes", True, num_nodes, num_edges, graph_ptr, max_graph_nodes)
 
 
 def edge_contract_select(edge_index: Tensor, num_nodes: int, score: Optional[Tensor] = None,
@@ -2820,41 +2850,21 @@ def edge_contract_select(edge_index: Tensor, num_nodes: int, score: Optional[Ten
         res.medge = torch.empty(0, dtype=torch.int64, device=dev)
         res.weight = None if score is None else torch.empty(0, dtype=torch.float32, device=dev)
         return res
-    if n > L.tgp_graclus_relabel_max_nodes():
-        raise N.TgpNativeError(f"edge_contract_select: {n} nodes exceed the relabelling kernels' "
-                               f"{L.tgp_graclus_relabel_max_nodes()}")
     rank = None
-    if perm is not None:
-        if perm.numel() != E:
-            raise ValueError(f"perm must have one entry per edge ({E}), got {perm.numel()}")
-        rank = torch.empty(E, dtype=torch.int32, device=dev)
-        rank[perm.reshape(-1)] = torch.arange(E, dtype=torch.int32, device=dev)
-        score = None
-    elif score is None:
-        rank = torch.arange(E, dtype=torch.int32, device=dev)
+    if perm is not None or score is None:
+        rank, score = _rank_of(E, perm, "edge", dev), None
     else:
         score = N.f32c(score.reshape(-1))
         if score.numel() != E:
             raise ValueError(f"score must have one entry per edge ({E}), got {score.numel()}")
-    want = edge_contract_route(n, E, graph_ptr, max_graph_nodes)
-    if route is not None:
-        if route not in ("graphs", "rounds"):
-            raise ValueError(f"route must be 'graphs' or 'rounds', got {route!r}")
-        if route == "graphs" and want != "graphs":
-            raise ValueError("the per-graph route needs a sorted batch whose longest graph fits one workgroup")
-        want = route
+    want = _frame_route("tgp_edge_contract_max_graph_nodes", True, n, E, graph_ptr, max_graph_nodes, route)
+    label, index, words, relabel = _owner_labels(n, "edge_contract_select", dev, st)  # [status, rounds, K (int64)]
     matched = torch.empty(E, dtype=torch.uint8, device=dev)
-    label = torch.empty(n, dtype=torch.int64, device=dev)
     medge = torch.empty(n, dtype=torch.int64, device=dev)
-    index = torch.empty(2, n, dtype=torch.int64, device=dev)
     weight = None if score is None else torch.empty(n, dtype=torch.float32, device=dev)
-    words = torch.empty(4, dtype=torch.int32, device=dev)  # [status, rounds, K (int64)]
-    rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
 
     def finish():
-        # representatives (label[i] == i) -> consecutive ids: flags + exclusive scan, no sort, no torch.unique
-        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
-                                          None, None, None, st), "tgp_graclus_relabel_i64")
+        relabel()
         if weight is not None:
             N.check(L.tgp_edge_contract_weights_f32(N.ptr(medge), N.ptr(score), n, E, N.ptr(weight), st),
                     "tgp_edge_contract_weights_f32")
@@ -2867,30 +2877,18 @@ def edge_contract_select(edge_index: Tensor, num_nodes: int, score: Optional[Ten
                                            N.ptr(words), st), "tgp_edge_contract_graphs")
         finish()
         got = words.tolist()  # the one host wait: status, rounds and K together
-        if got[0] == 0:
+        if _frame_done(got[0], "tgp_edge_contract_graphs", route, "an entry"):
             res.k, res.route, res.rounds = int(got[2]), "graphs", int(got[1])
             return res
-        if got[0] & 2:
-            raise N.TgpNativeError("tgp_edge_contract_graphs: a graph did not finish within its round bound")
-        if route == "graphs":
-            raise N.TgpNativeError("tgp_edge_contract_graphs declined: the edge list is not grouped by graph or an "
-                                   "entry joins two graphs")
     ws = N.workspace(L.tgp_edge_contract_workspace_bytes(n), dev)
     N.check(L.tgp_edge_contract_rounds_start(n, E, N.ptr(ws), ws.numel(), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
             "tgp_edge_contract_rounds_start")
-    done, step, live = 0, 4, None
-    while live is None:
-        if done >= n + 4:  # a round retires a node while a live entry exists: n rounds is a hard cap
-            raise N.TgpNativeError("tgp_edge_contract_rounds: the matching is not maximal after num_nodes rounds")
-        flags = torch.empty(step, dtype=torch.int32, device=dev)
+
+    def launch(done, step, flags):
         N.check(L.tgp_edge_contract_rounds(N.ptr(row), N.ptr(col), E, n, N.ptr(score), N.ptr(rank), N.ptr(ws), done, step,
                                            N.ptr(flags), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
                 "tgp_edge_contract_rounds")
-        got = flags.tolist()  # one host wait per batch of rounds
-        if 0 in got:
-            live = done + got.index(0)
-        done += step
-        step = min(2 * step, 256)  # a long tail means chain-like structure: more rounds per host wait
+    _, live = _run_rounds(launch, n, "tgp_edge_contract_rounds", "the matching", dev)
     finish()
     res.k, res.route, res.rounds = int(words.tolist()[2]), "rounds", live
     return res
@@ -3844,7 +3842,7 @@ def lapool_edge_group(edge_index: Tensor, num_nodes: int) -> AssignIndex:
     if _rows_sorted(edge_index, row):
         # the usual layout: the offsets are the whole index (perm None = identity), one launch and no sort workspace
         return AssignIndex(csr_offsets(edge_index, num_nodes), None, edge_index.size(1), num_nodes)
-    return acc_edge_group(edge_index, num_nodes)
+    return edge_group(edge_index, num_nodes)
 
 
 def _lapool_by_src(edge_index: Tensor, num_nodes: int, by_src: Optional[AssignIndex]) -> AssignIndex:

@@ -771,6 +771,17 @@ def graclus_cluster(row: Tensor, col: Tensor, weight: Optional[Tensor] = None,
     return label
 
 
+def _sorted_batch_facts(batch, num_nodes: int):
+    """(graph offsets, longest graph) of a sorted device batch vector, else (None, None): what picks the
+    per-graph route of the Graclus, k-MIS and edge-contraction selectors."""
+    if isinstance(batch, Tensor) and batch.is_cuda and batch.numel() == num_nodes and num_nodes > 0:
+        from ..utils.ops import batch_info
+        info = batch_info(batch)  # (memoised per batch vector)
+        if info.is_sorted:
+            return info.ptr, info.max_nodes
+    return None, None
+
+
 class GraclusSelect(Select):
     r"""One-over-K hard assignment from a greedy matching, relabelled to consecutive ids
     (reference select/graclus_select.py:13-84)."""
@@ -786,13 +797,7 @@ class GraclusSelect(Select):
         if edge_index.is_cuda:
             # native matching + scan-based relabelling (no sort): representatives keep their relative order
             from .. import kernels, _native as N
-            gptr = gmax = None
-            batch = kwargs.get("batch")
-            if isinstance(batch, Tensor) and batch.is_cuda and batch.numel() == num_nodes and num_nodes > 0:
-                from ..utils.ops import batch_info
-                info = batch_info(batch)  # (memoised per batch vector)
-                if info.is_sorted:
-                    gptr, gmax = info.ptr, info.max_nodes
+            gptr, gmax = _sorted_batch_facts(kwargs.get("batch"), num_nodes)
             if num_nodes <= N.lib().tgp_graclus_relabel_max_nodes():
                 (index, k, assign, ones), row_ptr = kernels.graclus_match(edge_index, edge_weight, num_nodes,
                                                                           return_row_ptr=True, graph_ptr=gptr,
@@ -827,16 +832,6 @@ class GraclusSelect(Select):
 
 
 # =============================================================================== k-MIS
-def _kmis_batch_facts(batch, num_nodes: int):
-    """(graph offsets, longest graph) of a sorted device batch vector, else (None, None): what picks the route."""
-    if isinstance(batch, Tensor) and batch.is_cuda and batch.numel() == num_nodes and num_nodes > 0:
-        from ..utils.ops import batch_info
-        info = batch_info(batch)  # (memoised per batch vector)
-        if info.is_sorted:
-            return info.ptr, info.max_nodes
-    return None, None
-
-
 def degree_scorer(edge_index, edge_weight: Optional[Tensor] = None, num_nodes: Optional[int] = None,
                   dim: int = 1) -> Tensor:
     """Weighted degree of every node over ``edge_index[dim]`` (in-degree for the default ``dim=1``), float32 [N]
@@ -855,7 +850,7 @@ def degree_scorer(edge_index, edge_weight: Optional[Tensor] = None, num_nodes: O
 def _kmis_explicit(edge_index: Tensor, order_k: int, perm: Optional[Tensor], num_nodes: Optional[int], batch=None):
     from .. import kernels
     n = num_nodes if num_nodes is not None else maybe_num_nodes(edge_index)
-    gptr, gmax = _kmis_batch_facts(batch, n)
+    gptr, gmax = _sorted_batch_facts(batch, n)
     return n, kernels.kmis_select(edge_index, n, order_k, perm=perm, graph_ptr=gptr, max_graph_nodes=gmax)
 
 
@@ -959,7 +954,7 @@ class KMISSelect(Select):
             edge_index, edge_weight = Fn.coalesce_edges(both, w2, torch.arange(num_nodes, device=both.device),
                                                         num_nodes, reduce_op="max", remove_self_loops=False)
         score = self._score(edge_index, edge_weight, x, num_nodes)
-        gptr, gmax = _kmis_batch_facts(batch, num_nodes)
+        gptr, gmax = _sorted_batch_facts(batch, num_nodes)
         with torch.no_grad():
             res = kernels.kmis_select(edge_index, num_nodes, self.order_k, score=score.detach(),
                                       heuristic=self.score_heuristic, graph_ptr=gptr, max_graph_nodes=gmax)
@@ -1202,7 +1197,7 @@ class EdgeContractionSelect(Select):
         N.require_device(x, edge_index)  # host tensors: no CPU fallback
         n = x.size(0)
         e = self.edge_scores(x, edge_index)
-        gptr, gmax = _kmis_batch_facts(batch, n)
+        gptr, gmax = _sorted_batch_facts(batch, n)
         with torch.no_grad():
             res = kernels.edge_contract_select(edge_index, n, e.detach(), graph_ptr=gptr, max_graph_nodes=gmax)
         values = _EdgeWeightFn.apply(e, res.medge, res.weight) if e.requires_grad else res.weight

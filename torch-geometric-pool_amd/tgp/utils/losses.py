@@ -423,7 +423,7 @@ class _ACCTermsFn(torch.autograd.Function):
         else:
             B, Kc = layout[1].numel() - 1, S.size(1)
             if source is not None:
-                groups = K.acc_edge_group(source[0], S.size(0))  # (by source; by destination: in the backward)
+                groups = K.edge_group(source[0], S.size(0))  # (by source; by destination: in the backward)
                 tv = ("edge", K.acc_tv_edge(S, source[0], source[1], groups), groups, layout[1])
             if k > 1:
                 sel = K.acc_quantile(S, k, ptr=layout[1], max_nodes=layout[3])
@@ -444,7 +444,7 @@ class _ACCTermsFn(torch.autograd.Function):
         if source is not None and dense:
             ds = K.acc_tv_dense_bwd(source, S, layout[2], g[0], ecnt, ctx.coeffs[0])
         elif source is not None:
-            by_dst = K.acc_edge_group(source[0], S.size(0), by_destination=True)
+            by_dst = K.edge_group(source[0], S.size(0), by_destination=True)
             ds = K.acc_tv_edge_bwd(S, source[0], source[1], ctx.groups, by_dst, layout[2], g[0], ecnt, ctx.coeffs[0])
         if sel:
             acc = ds is not None
