@@ -1451,6 +1451,31 @@ int tgp_lapool_assign_bwd_f32(const float* X, const float* nrm, const float* S, 
                               const int32_t* col_of, const int32_t* leaders, const int32_t* k, int64_t K, float eps,
                               float* g1, float* g2, float* alpha, float* dX, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * SAGPooling's scorer (reference poolers/sag.py with PyG's GraphConv / SAGEConv at one output channel),
+ * csrc/sag_score.hip.  fp32, no float atomics, the same bits on every call; nothing of size E x F or N x F is formed.
+ *   row_project2  out0[i] = <x[i,:], w0>, out1[i] = <x[i,:], w1> from ONE pass over x (row stride ldx >= F; 16-byte
+ *                 loads when x is 16-byte aligned and ldx % 4 == 0, a row's last F % 4 columns by scalar loads).
+ *   aggregate     t[i] = (sum over group i of p[src[pos]] [/ max(size of group i, 1) when mean] + bias[0]) + q[i],
+ *                 a[i] = act(t[i]), act 0 = identity, 1 = tanh.  Group i = positions grp_perm[grp_ptr[i] .. grp_ptr[i+1])
+ *                 of the edge list (grp_perm NULL: the positions themselves, a list already grouped), added in that
+ *                 order.  A src outside [0, N) or a position outside [0, E) is skipped, never dereferenced (it still
+ *                 counts in the group's size).  With the by-destination index and src = the source row this is the
+ *                 forward; with the by-source index and src = the destination row it is the backward's g_p.
+ *   bwd_x         g_x[i,:] = g_q[i] w_root + g_p[i] w_rel (accumulate != 0: added to what g_x holds); g_x is [N,F]
+ *                 contiguous.
+ * TGP_ERR_INVALID: a NULL input or output, p given as an output, sizes below zero; TGP_ERR_RANGE: N or E beyond the int32
+ * index, F >= 2^31.  Both are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_row_project2_f32(const float* x, int64_t N, int64_t F, int64_t ldx, const float* w0, const float* w1, float* out0,
+                         float* out1, void* stream);
+int tgp_sag_aggregate_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL: list already grouped */,
+                          const int64_t* src, const float* p, const float* q /* NULL ok */,
+                          const float* bias /* NULL ok; one device float */, int64_t N, int64_t E, int mean, int act,
+                          float* t_out /* NULL ok */, float* a_out /* NULL ok, not both */, void* stream);
+int tgp_sag_score_bwd_x_f32(const float* g_q, const float* g_p, const float* w_root, const float* w_rel, int64_t N,
+                            int64_t F, int accumulate, float* g_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

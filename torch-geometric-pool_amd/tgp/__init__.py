@@ -15,7 +15,7 @@ eps = 1e-8  # reference: tgp/__init__.py:6
 
 __version__ = "1.0.1+mi355x"
 
-_submodules = ["poolers", "src", "select", "reduce", "lift", "connect", "utils", "kernels", "distributed"]
+_submodules = ["poolers", "src", "select", "reduce", "lift", "connect", "utils", "kernels", "distributed", "nn"]
 
 
 def freeze_gc() -> None:

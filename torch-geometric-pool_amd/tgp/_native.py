@@ -353,6 +353,10 @@ SIGNATURES = {
     "tgp_gather_unpack_bucket_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_p, _c_p, _c_p]),
     "tgp_debug_sort_workspace_bytes": (_c_sz, [_c_i64]),
     "tgp_debug_sort_pairs_u64": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "tgp_row_project2_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_sag_aggregate_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_p,
+                                       _c_p]),
+    "tgp_sag_score_bwd_x_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -634,6 +634,53 @@ def topk_score(x: Tensor, w: Tensor, use_tanh: bool) -> Tensor:
     return _TopkScoreFn.apply(x, w, use_tanh) if _needs_grad(x, w) else K.topk_score(x, w, use_tanh)
 
 
+# ------------------------------------------------------------- SAGPooling's scorer (one-channel GraphConv / SAGEConv)
+class _SagScoreFn(torch.autograd.Function):
+    """a = act((aggr_{j -> i} <x_j, w_rel> + b) + <x_i, w_root>), act = tanh or identity, aggr = sum or mean: one node of
+    the graph.  Forward: one pass over x (both projections) and E scalar gathers.  Backward from g_t = g (1 - a^2):
+    g_q = g_t, g_b = sum g_t, g_p[j] = sum_{e: src(e) = j} g_t[dst(e)] / (mean ? max(indeg, 1) : 1) -- the forward's
+    aggregate kernel over the by-source index -- then dx = g_q w_root^T + g_p w_rel^T in one pass and the two weight
+    gradients x^T g_q, x^T g_p (one pass over x each)."""
+
+    @staticmethod
+    def forward(ctx, x, edge_index, w_rel, w_root, bias, mean, use_tanh):
+        a = K.sag_score(x, edge_index, w_rel, w_root, bias, mean, use_tanh)
+        ctx.save_for_backward(x, edge_index, w_rel, w_root, a)
+        ctx.mean, ctx.use_tanh, ctx.has_bias = mean, use_tanh, bias is not None
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        x, edge_index, w_rel, w_root, a = ctx.saved_tensors
+        n = x.size(0)
+        gt = (torch.ops.aten.tanh_backward(g, a) if ctx.use_tanh else g).contiguous()
+        gs = gt
+        if ctx.mean:  # every message into i was divided by max(indeg_i, 1)
+            ptr = K.sag_edge_group(edge_index, n, by_destination=True).row_ptr
+            gs = gt / (ptr[1:] - ptr[:-1]).clamp_(min=1).to(gt.dtype)
+        _, col = K._edge_rows(edge_index)
+        gp = K.sag_aggregate(K.sag_edge_group(edge_index, n, by_destination=False), col, gs)
+        gx = g_rel = g_root = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = K.sag_score_bwd_x(gt if w_root is not None else torch.zeros_like(gt), gp,
+                                   w_root if w_root is not None else w_rel, w_rel)
+        if ctx.needs_input_grad[2]:
+            g_rel = K.weighted_colsum(x, gp).view_as(w_rel)
+        if w_root is not None and ctx.needs_input_grad[3]:
+            g_root = K.weighted_colsum(x, gt).view_as(w_root)
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            gb = gt.sum().reshape(1)
+        return gx, None, g_rel, g_root, gb, None, None
+
+
+def sag_score(x: Tensor, edge_index: Tensor, w_rel: Tensor, w_root: Optional[Tensor], bias: Optional[Tensor],
+              mean: bool, use_tanh: bool) -> Tensor:
+    """SAGPooling's score [N] on device float32 tensors (see :class:`_SagScoreFn`)."""
+    if _needs_grad(x, w_rel, w_root, bias):
+        return _SagScoreFn.apply(x, edge_index, w_rel, w_root, bias, mean, use_tanh)
+    return K.sag_score(x, edge_index, w_rel, w_root, bias, mean, use_tanh)
+
+
 class _TopkPoolTrainFn(torch.autograd.Function):
     """The ONE autograd node of TopK pooling's trained path (r5): x' = s_a x[i_a] and the kept scores s_a = act(x w /
     ||w||)[i_a] (the values of S) as functions of x and the projection w.  The forward values come from the caller --

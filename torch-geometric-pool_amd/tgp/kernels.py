@@ -3993,3 +3993,103 @@ def lapool_assign_bwd(x: Tensor, nrm: Tensor, s: Tensor, ds: Tensor, lead: LaPoo
              N.ptr(lead.batch), N.ptr(lead.col_of), N.ptr(lead.leaders), N.ptr(lead.k), Kc, ops_eps(), N.ptr(g[0]),
              N.ptr(g[1]), N.ptr(alpha), N.ptr(dx) if dx.numel() else None, N.stream_ptr(dev))
     return dx
+
+
+# ------------------------------------------------------------------------- SAGPooling's scorer (csrc/sag_score.hip)
+_SAG_GROUPS = TensorMemo(16)  # edge_index -> {(num_nodes, by_destination): AssignIndex}
+
+
+def row_project2(x: Tensor, w0: Tensor, w1: Tensor) -> Tuple[Tensor, Tensor]:
+    """(x w0, x w1): both dot products of every row from one pass over ``x`` [N,F] (any row stride)."""
+    dev = N.require_device(x, w0, w1)
+    x, w0, w1 = _row_major_f32(x), N.f32c(w0.reshape(-1)), N.f32c(w1.reshape(-1))
+    if w0.numel() != x.size(1) or w1.numel() != x.size(1):
+        raise ValueError(f"row_project2: x {tuple(x.shape)} against weights of {w0.numel()} and {w1.numel()} entries")
+    out = torch.empty(2, x.size(0), dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_row_project2_f32, N.ptr(x), x.size(0), x.size(1), x.stride(0), N.ptr(w0), N.ptr(w1),
+             N.ptr(out[0]), N.ptr(out[1]), N.stream_ptr(dev))
+    return out[0], out[1]
+
+
+def _row_major_f32(x: Tensor) -> Tensor:
+    """float32 [N,F] with unit column stride; a row stride of its own (a column slice) is kept."""
+    if x.dim() != 2:
+        raise ValueError(f"x must be [N, F], got {tuple(x.shape)}")
+    x = x if x.dtype == torch.float32 else x.to(torch.float32)
+    return x if (x.stride(1) == 1 and x.stride(0) >= x.size(1)) or x.numel() == 0 else x.contiguous()
+
+
+def sag_edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = True) -> AssignIndex:
+    """The index the scorer's sums run over: edge positions grouped by destination (forward) or by source (backward),
+    edge-list order inside a node.  A list that already ascends in that row needs only its CSR offsets (``perm`` None);
+    any other list gets the stable sort of :func:`edge_group`, so both routes add the same numbers in the same order.
+    Remembered per tensor object and version: full-batch training scores the same ``edge_index`` every step."""
+    key = (int(num_nodes), bool(by_destination))
+    memo = _SAG_GROUPS.get(edge_index)
+    if memo is not None and key in memo:
+        return memo[key]
+    dev, E = edge_index.device, edge_index.size(1)
+    if E == 0:
+        grp = AssignIndex(torch.zeros(num_nodes + 1, dtype=torch.int32, device=dev), None, 0, num_nodes)
+    else:
+        row, col = _edge_rows(edge_index)
+        tgt = col if by_destination else row
+        ascending = bool((col[1:] >= col[:-1]).all()) if by_destination else _rows_sorted(edge_index, row)
+        if ascending:
+            ptr = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev)
+            rowptr_from_sorted(tgt, num_nodes, ptr)
+            grp = AssignIndex(ptr, None, E, num_nodes)
+        else:
+            grp = edge_group(edge_index, num_nodes, by_destination=by_destination)
+    if not torch.cuda.is_current_stream_capturing():
+        if memo is None:
+            memo = {}
+            _SAG_GROUPS.put(edge_index, memo)
+        memo[key] = grp
+    return grp
+
+
+def sag_aggregate(grp: AssignIndex, src: Tensor, p: Tensor, q: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+                  mean: bool = False, tanh: bool = False, want_t: bool = False):
+    """a = act((sum over node i's group of p[src] [/ max(group size, 1)] + bias) + q_i), act = tanh or identity, the sum in
+    the order of ``grp`` (no float atomics).  ``want_t``: ``(t, a)`` with the pre-activation as well."""
+    dev = N.require_device(src, p, q, bias, grp.row_ptr)
+    p, src = N.f32c(p.reshape(-1)), N.i64c(src)
+    n, E = grp.num_targets, src.numel()
+    if p.numel() != n or grp.nnz != E or grp.row_ptr.numel() != n + 1 or (q is not None and q.numel() != n):
+        raise ValueError(f"sag_aggregate: {n} nodes and {grp.nnz} indexed edges against p {tuple(p.shape)}, "
+                         f"{E} edges" + ("" if q is None else f", q {tuple(q.shape)}"))
+    q = None if q is None else N.f32c(q.reshape(-1))
+    b = None if bias is None else N.f32c(bias.reshape(-1))
+    out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_sag_aggregate_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(p),
+             N.ptr(q), N.ptr(b), n, E, int(bool(mean)), int(bool(tanh)), N.ptr(out[0]) if want_t else None,
+             N.ptr(out[-1]), N.stream_ptr(dev))
+    return (out[0], out[1]) if want_t else out[0]
+
+
+def sag_score_bwd_x(g_q: Tensor, g_p: Tensor, w_root: Tensor, w_rel: Tensor, g_x: Optional[Tensor] = None) -> Tensor:
+    """dX = g_q (x) w_root + g_p (x) w_rel in one pass, added to ``g_x`` ([N,F] float32 contiguous, in place) when given."""
+    dev = N.require_device(g_q, g_p, w_root, w_rel, g_x)
+    g_q, g_p = N.f32c(g_q.reshape(-1)), N.f32c(g_p.reshape(-1))
+    w_root, w_rel = N.f32c(w_root.reshape(-1)), N.f32c(w_rel.reshape(-1))
+    n, F = g_q.numel(), w_root.numel()
+    if g_p.numel() != n or w_rel.numel() != F:
+        raise ValueError("sag_score_bwd_x: one g_q and g_p per node, one w_root and w_rel per column")
+    acc = g_x is not None
+    if acc and (g_x.dtype != torch.float32 or tuple(g_x.shape) != (n, F) or not g_x.is_contiguous()):
+        raise ValueError(f"sag_score_bwd_x: g_x must be a contiguous float32 [{n}, {F}]")
+    out = g_x if acc else torch.empty(n, F, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_sag_score_bwd_x_f32, N.ptr(g_q), N.ptr(g_p), N.ptr(w_root), N.ptr(w_rel), n, F, int(acc),
+             N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
+def sag_score(x: Tensor, edge_index: Tensor, w_rel: Tensor, w_root: Optional[Tensor], bias: Optional[Tensor],
+              mean: bool = False, tanh: bool = False, want_t: bool = False):
+    """The whole scorer, two launches: act(lin_rel(aggr_j x_j) + lin_root(x_i)) at one output channel as
+    project-then-aggregate.  ``w_root`` None (SAGEConv with ``root_weight=False``): no root term."""
+    p, q = row_project2(x, w_rel, w_rel if w_root is None else w_root)
+    row, _ = _edge_rows(edge_index)
+    grp = sag_edge_group(edge_index, x.size(0), by_destination=True)
+    return sag_aggregate(grp, row, p, None if w_root is None else q, bias, mean, tanh, want_t)

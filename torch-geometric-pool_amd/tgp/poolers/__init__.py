@@ -1,11 +1,11 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction,lapool}.py).
+(reference tgp/poolers/{__init__,topk,sag,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction,lapool}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
-``HOSCPooling``, ``BNPool``, ``EdgeContractionPooling`` and ``LaPooling`` are built and exported as classes; their
-``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``edgepool`` / ``lap`` aliases are not registered yet.
+``HOSCPooling``, ``BNPool``, ``EdgeContractionPooling``, ``LaPooling`` and ``SAGPooling`` are built and exported as
+classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``edgepool`` / ``lap`` / ``sag`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ from torch import Tensor
 
 from .. import functions as Fn
 from .. import kernels as K
+from .. import nn as _nn
 from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
@@ -158,6 +159,85 @@ class TopkPooling(SRCPooling):
             x_pool = self.multiplier * x_pool
         if fused is None:
             ei, ew = self.connect(so=so, edge_index=adj, edge_weight=edge_weight, batch_pooled=batch_pool)
+        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
+
+    def extra_repr_args(self) -> dict:
+        return {"multiplier": self.multiplier}
+
+
+class SAGPooling(SRCPooling):
+    r"""Self-attention graph pooling (Lee et al., ICML 2019; reference poolers/sag.py:17-228): the nodes are scored by a
+    one-channel graph convolution of ``attn`` (default: ``x``), the best ``ceil(ratio * n)`` of every graph are kept,
+    their features gated by the score, the induced subgraph kept.  ``TopkSelect`` (without a projection of its own) +
+    ``BaseReduce`` + ``SparseConnect`` + ``BaseLift``.  As in the reference, edge weights do not enter the score.
+
+    ``GNN``: None (:class:`tgp.nn.GraphConv`), :class:`tgp.nn.GraphConv` / :class:`tgp.nn.SAGEConv` or their names
+    ``"graphconv"`` / ``"sage"``; these score device float32 inputs natively (project, then aggregate: no ``E x F``
+    temporary), with the activation fused in ratio mode when it is tanh or linear.  Any other class is built as
+    ``GNN(in_channels, 1, **kwargs)`` and called as ``self.gnn(attn, adj)``, as the reference does.  ``kwargs`` the
+    class does not take are dropped.
+
+    The ``"sag"`` alias of ``get_pooler`` is not registered yet (the alias set is pinned to the five hot-path poolers)."""
+
+    _GNN_NAMES = {"graphconv": _nn.GraphConv, "sage": _nn.SAGEConv}
+
+    def __init__(self, in_channels: int, ratio: Union[float, int] = 0.5, GNN: Optional[torch.nn.Module] = None,
+                 min_score: Optional[float] = None, multiplier: float = 1.0,
+                 nonlinearity: Union[str, Callable] = "tanh", lift: str = "precomputed", s_inv_op: str = "transpose",
+                 connect_red_op: str = "sum", lift_red_op: str = "sum", remove_self_loops: bool = True,
+                 degree_norm: bool = False, edge_weight_norm: bool = False, **kwargs):
+        super().__init__(
+            selector=TopkSelect(ratio=ratio, min_score=min_score, act=nonlinearity, s_inv_op=s_inv_op),
+            reducer=BaseReduce(),
+            lifter=BaseLift(matrix_op=lift, reduce_op=lift_red_op),
+            connector=SparseConnect(reduce_op=connect_red_op, degree_norm=degree_norm,
+                                    edge_weight_norm=edge_weight_norm, remove_self_loops=remove_self_loops))
+        if isinstance(GNN, str):
+            if GNN.lower() not in self._GNN_NAMES:
+                raise ValueError(f"Unknown GNN='{GNN}'. Available names: {list(self._GNN_NAMES)}")
+            GNN = self._GNN_NAMES[GNN.lower()]
+        gnn_cls = GNN or _nn.GraphConv
+        # keep only the kwargs that are used in the GNN (signature works when __code__ is not available)
+        try:
+            params = set(inspect.signature(gnn_cls).parameters.keys())
+        except (ValueError, TypeError):
+            params = set()
+        self.gnn = gnn_cls(in_channels, 1, **{k: v for k, v in kwargs.items() if k in params})
+        self.multiplier = multiplier
+
+    def reset_parameters(self):
+        self.gnn.reset_parameters()
+        super().reset_parameters()
+
+    def _score_and_select(self, attn: Tensor, adj, batch: Optional[Tensor]) -> SelectOutput:
+        sel = self.selector
+        if (isinstance(self.gnn, (_nn.GraphConv, _nn.SAGEConv)) and type(sel) is TopkSelect and sel.min_score is None
+                and sel.ratio is not None and sel._fused_act is not None and self._so_cached is None):
+            # ratio mode, tanh or linear: the activation rides in the aggregate kernel and the score goes straight to the
+            # device selection (under autograd the scorer is one graph node; so.weight reaches it through take_unique)
+            score = self.gnn.score(attn, adj, sel._fused_act == "tanh")
+            if score is not None:
+                return sel._native_select(score, batch, attn.size(0))
+        return self.select(x=self.gnn(attn, adj), batch=batch)
+
+    def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None,
+                so: Optional[SelectOutput] = None, batch: Optional[Tensor] = None,
+                attn: Optional[Tensor] = None, lifting: bool = False, **kwargs):
+        if lifting:
+            return self.lift(x_pool=x, so=so)
+        attn = x if attn is None else attn
+        attn = attn.view(-1, 1) if attn.dim() == 1 else attn
+        so = self._score_and_select(attn, adj, batch)
+        fused = self.reduce_connect(x, adj, edge_weight, so, batch)  # batches of small graphs: ONE launch
+        if fused is not None:
+            x_pool, batch_pool, ei, ew = fused
+            if self.multiplier != 1:
+                x_pool = self.multiplier * x_pool
+            return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
+        x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch)
+        if self.multiplier != 1:
+            x_pool = self.multiplier * x_pool
+        ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch_pooled=batch_pool)
         return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so)
 
     def extra_repr_args(self) -> dict:
@@ -1422,8 +1502,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "edgepool" (EdgeContractionPooling) and "lap" (LaPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "edgepool" (EdgeContractionPooling), "lap" (LaPooling) and "sag" (SAGPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,
