@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -1475,6 +1475,48 @@ int tgp_sag_aggregate_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NUL
                           float* t_out /* NULL ok */, float* a_out /* NULL ok, not both */, void* stream);
 int tgp_sag_score_bwd_x_f32(const float* g_q, const float* g_p, const float* w_root, const float* w_rel, int64_t N,
                             int64_t F, int accumulate, float* g_x, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Segment readout (reference reduce/aggr_reduce.py, reduce/global_reduce.py over PyG's Sum / Mean / Max / Min /
+ * MultiAggregation), csrc/segment_aggr.hip.  fp32, no float atomics, the same bits on every call.
+ *   `ops` is a mask of (1 << TGP_SUM) | (1 << TGP_MEAN) | (1 << TGP_MIN) | (1 << TGP_MAX); ONE pass over x fills
+ *   out [G, n_ops * F], the requested operations side by side in enum order (sum, mean, min, max).  An empty group
+ *   gives 0 for every operation, the mean divides by max(count, 1), min / max are exact and NaN wins as in
+ *   torch.amax / amin.  Row source, exactly one of:
+ *     ptr [G + 1]      group g owns rows ptr[g] .. ptr[g + 1] - 1 of x (a sorted batch vector's offsets);
+ *     dense_nodes > 0  x is [G, dense_nodes, F] (num_rows = G * dense_nodes), `mask` ([num_rows] bytes, NULL = every
+ *                      row) names the rows that exist: the others are neither loaded nor counted;
+ *     node_index       gathered rows x[node_index[a], :] * weight[a] over the supernode -> assignment index of a
+ *                      sparse assignment (row_ptr [G + 1] and perm [nnz] of tgp_assign_index_build; row_ptr NULL: one
+ *                      assignment per group, perm [G] or NULL = identity; weight NULL = ones); the product is rounded
+ *                      before the add, as in tgp_reduce_sparse_f32.  A position, assignment or row outside its table
+ *                      is skipped, never dereferenced.
+ *   Every (group, feature) is added in ascending row order by one lane.  max_len is an upper bound of the longest
+ *   group (it only chooses the route, never the result's validity): beyond tgp_segment_aggr_chunk_rows() rows the
+ *   segments are cut into row chunks whose partial records (`ws`, tgp_segment_aggr_workspace_bytes; 0 = not needed)
+ *   a second kernel folds in a fixed order (runs of consecutive chunks, then the runs, both ascending).  16-byte
+ *   loads when F % 4 == 0, ldx % 4 == 0 and x / out / ties are 16-byte aligned; scalar loads otherwise.
+ *   ties (NULL ok) [G, n_mm * F] int32, min then max: the number of rows that attain the extreme; count (NULL ok) [G]
+ *   int32: the rows of each group.  The backward reads both.
+ *   bwd: dx [num_rows, F] (contiguous) = sum over the requested operations of g, g / max(count, 1) and
+ *   g [x == out] / ties, written once; g_out and out are [G, n_ops * F].  `batch` [num_rows] names every row's group
+ *   (NULL: the dense layout, or one group); rows of a group outside [0, G) and masked rows get 0.  The gathered
+ *   source has no native backward.
+ * TGP_ERR_INVALID: no or several row sources, an empty or unknown ops mask, a NULL input or output, sizes below
+ * zero; TGP_ERR_RANGE: G, num_rows * F or nnz beyond the int32 range.  Both are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_segment_aggr_chunk_rows(void);
+size_t tgp_segment_aggr_workspace_bytes(int64_t G, int64_t F, int ops, int64_t max_len);
+int tgp_segment_aggr_f32(const float* x, int64_t num_rows, int64_t F, int64_t ldx, const int64_t* ptr /* NULL ok */,
+                         int64_t dense_nodes, const uint8_t* mask /* NULL ok */, const int32_t* row_ptr /* NULL ok */,
+                         const int32_t* perm /* NULL ok */, const int64_t* node_index /* NULL ok */,
+                         const float* weight /* NULL ok */, int64_t nnz, int64_t G, int64_t max_len, int ops, float* out,
+                         int32_t* ties /* NULL ok */, int32_t* count /* NULL ok */, void* ws, size_t ws_bytes,
+                         void* stream);
+int tgp_segment_aggr_bwd_f32(const float* g_out, const float* x, int64_t num_rows, int64_t F, int64_t ldx,
+                             const int64_t* batch /* NULL ok */, int64_t dense_nodes, const uint8_t* mask /* NULL ok */,
+                             const float* out, const int32_t* ties, const int32_t* count, int64_t G, int ops, float* dx,
+                             void* stream);
 
 #ifdef __cplusplus
 }

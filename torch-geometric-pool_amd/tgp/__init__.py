@@ -1,8 +1,9 @@
 """tgp — MI355X-native drop-in for the SRC pooling hot path of torch-geometric-pool 1.0.1.
 
 Same import surface as the reference for the path it covers (``tgp.poolers.get_pooler``,
-``tgp.src.PoolingOutput``, ``tgp.select.SelectOutput``, ``tgp.reduce.BaseReduce``,
-``tgp.connect.{SparseConnect,DenseConnect,KronConnect}``, ``tgp.lift.BaseLift``); Reduce and
+``tgp.src.PoolingOutput``, ``tgp.select.SelectOutput``, ``tgp.reduce.{BaseReduce,AggrReduce,GlobalReduce,get_aggr}``
+with the ``Sum`` / ``Mean`` / ``Max`` / ``Min`` / ``MultiAggregation`` operators,
+``tgp.connect.{SparseConnect,DenseConnect,KronConnect}``, ``tgp.lift.BaseLift``); Reduce, the readout and
 Connect run as hand-written HIP kernels for gfx950 behind a C ABI (``include/tgp_hip.h``).
 Neither torch_geometric nor torch_scatter is needed.
 """

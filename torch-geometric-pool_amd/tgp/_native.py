@@ -357,6 +357,12 @@ SIGNATURES = {
     "tgp_sag_aggregate_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_p,
                                        _c_p]),
     "tgp_sag_score_bwd_x_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_segment_aggr_chunk_rows": (_c_int, []),
+    "tgp_segment_aggr_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int, _c_i64]),
+    "tgp_segment_aggr_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
+                                      _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "tgp_segment_aggr_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
+                                          _c_i64, _c_int, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

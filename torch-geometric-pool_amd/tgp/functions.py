@@ -1361,3 +1361,76 @@ class _LaPoolAssignFn(torch.autograd.Function):
 
 def lapool_assign(x: Tensor, lead) -> Tensor:
     return _LaPoolAssignFn.apply(x, lead) if _needs_grad(x) else K.lapool_assign(x, lead)[0]
+
+
+# --------------------------------------------------------------------------------------- segment readout
+def _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, want_aux):
+    """``src`` names the rows: ``("ptr", ptr, batch)``, ``("dense", nodes, mask)`` or ``("so", select_output)``."""
+    if src[0] == "ptr":
+        return K.segment_aggr(x, ops_mask, num_groups, max_len, ptr=src[1], want_aux=want_aux)
+    if src[0] == "dense":
+        return K.segment_aggr(x, ops_mask, num_groups, max_len, dense_nodes=src[1], mask=src[2], want_aux=want_aux)
+    so = src[1]
+    return K.segment_aggr(x, ops_mask, num_groups, max_len, index=so.assign_index(), node_index=K.N.i64c(so.node_index),
+                          weight=weight, want_aux=want_aux)
+
+
+class _SegmentAggrFn(torch.autograd.Function):
+    """out [G, n_ops * F] = the requested sum / mean / min / max of every group's rows, one pass (K.segment_aggr).
+    The contiguous and dense sources have a native backward (one launch writes dX once); the gathered source's d src and
+    d weight are torch ops over the saved outputs, scattered back to the node rows by the Lift kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, ops_mask, num_groups, max_len, src):
+        out, ties, count = _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, True)
+        ctx.save_for_backward(x, weight, out, ties, count)
+        ctx.ops_mask, ctx.num_groups, ctx.src = ops_mask, num_groups, src
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, out, ties, count = ctx.saved_tensors
+        src, ops_mask = ctx.src, ctx.ops_mask
+        g = g.contiguous()
+        if src[0] == "ptr":
+            return (K.segment_aggr_bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, batch=src[2]),
+                    None, None, None, None, None)
+        if src[0] == "dense":
+            return (K.segment_aggr_bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, dense_nodes=src[1],
+                                       mask=src[2]), None, None, None, None, None)
+        so = src[1]
+        ni, ci = so.node_index, so.cluster_index
+        rows = x[ni]
+        val = rows if weight is None else rows * weight.view(-1, 1)
+        F = x.size(1)
+        d = torch.zeros_like(val)
+        slot = mm = 0
+        for op in K.SEGMENT_OPS:
+            if not ops_mask & (1 << K.N.REDUCE_OPS[op]):
+                continue
+            gs = g[:, slot * F:(slot + 1) * F][ci]
+            if op == "sum":
+                d += gs
+            elif op == "mean":
+                d += gs / count.clamp(min=1).to(gs.dtype)[ci].view(-1, 1)
+            else:
+                hit = val == out[:, slot * F:(slot + 1) * F][ci]
+                share = gs / ties[:, mm * F:(mm + 1) * F][ci].clamp(min=1).to(gs.dtype)
+                d += torch.where(hit, share, torch.zeros_like(share))
+                mm += 1
+            slot += 1
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            from .lift import lift_index_of
+            own = torch.arange(ni.numel(), device=ni.device)
+            gx = K.reduce_sparse(d, own, weight, lift_index_of(so))
+        if ctx.needs_input_grad[1]:
+            gw = (d * rows).sum(-1).view_as(weight)
+        return gx, gw, None, None, None, None
+
+
+def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, src, weight: Optional[Tensor] = None) -> Tensor:
+    """``x`` [rows, F] float32 on the device -> [G, n_ops * F], column blocks in ``K.SEGMENT_OPS`` order."""
+    if _needs_grad(x, weight):
+        return _SegmentAggrFn.apply(x, weight, ops_mask, num_groups, max_len, src)
+    return _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, False)[0]

@@ -42,7 +42,7 @@ class AssignIndex:
     assignment order).  A function of the SelectOutput only, so SelectOutput caches it."""
 
     __slots__ = ("_row_ptr", "perm", "nnz", "num_targets", "_device", "pack", "pack_key", "member_directory",
-                 "member_directory_key")
+                 "member_directory_key", "_max_members")
 
     def __init__(self, row_ptr: Optional[Tensor], perm: Optional[Tensor], nnz: int, num_targets: int, device=None):
         # row_ptr None: exactly one assignment per target (TopK, NDP) -- the table is arange and the Reduce kernel
@@ -66,12 +66,21 @@ class AssignIndex:
         # SelectOutput whose S was replaced must not get a Connect relabelled by the stale selection)
         self.member_directory = None
         self.member_directory_key = None
+        self._max_members = 1 if row_ptr is None else None
         self._device = perm.device if perm is not None else (row_ptr.device if row_ptr is not None else
                                                               torch.device(device))
 
     @property
     def one_to_one(self) -> bool:
         return self._row_ptr is None
+
+    @property
+    def max_members(self) -> int:
+        """Assignments of the largest target (one host read, remembered): the segment readout picks its route by it."""
+        if self._max_members is None:
+            rp = self._row_ptr
+            self._max_members = int((rp[1:] - rp[:-1]).max()) if self.num_targets > 0 else 0
+        return self._max_members
 
     @property
     def row_ptr(self) -> Tensor:
@@ -4093,3 +4102,79 @@ def sag_score(x: Tensor, edge_index: Tensor, w_rel: Tensor, w_root: Optional[Ten
     row, _ = _edge_rows(edge_index)
     grp = sag_edge_group(edge_index, x.size(0), by_destination=True)
     return sag_aggregate(grp, row, p, None if w_root is None else q, bias, mean, tanh, want_t)
+
+
+# ------------------------------------------------------------------------- segment readout (csrc/segment_aggr.hip)
+SEGMENT_OPS = ("sum", "mean", "min", "max")  # the order of their enum values = the order of the output's column blocks
+
+
+def segment_ops_mask(ops: Sequence[str]) -> int:
+    mask = 0
+    for op in ops:
+        if op not in SEGMENT_OPS:
+            raise ValueError(f"segment readout: unknown operation {op!r}")
+        mask |= 1 << N.REDUCE_OPS[op]
+    if mask == 0:
+        raise ValueError("segment readout: no operation requested")
+    return mask
+
+
+def segment_aggr_chunk_rows() -> int:
+    """Rows of the longest segment the readout still adds in one chain; one more row takes the split route."""
+    return int(N.lib().tgp_segment_aggr_chunk_rows())
+
+
+def _rows_f32(x: Tensor) -> Tensor:
+    """[rows, F] float32 with unit inner stride and a row stride of at least F (a copy only when the view is not)."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"segment readout expects float32 x of shape [rows, F], got {x.dtype} {tuple(x.shape)}")
+    if (x.size(1) > 1 and x.stride(1) != 1) or (x.size(0) > 1 and x.stride(0) < x.size(1)):
+        x = x.contiguous()
+    return x
+
+
+def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, ptr: Optional[Tensor] = None,
+                 dense_nodes: int = 0, mask: Optional[Tensor] = None, index: Optional[AssignIndex] = None,
+                 node_index: Optional[Tensor] = None, weight: Optional[Tensor] = None, want_aux: bool = False):
+    """One pass over ``x`` [rows, F] -> out [G, n_ops * F] (column blocks in ``SEGMENT_OPS`` order), plus with
+    ``want_aux`` the tie counts of min / max and the group sizes the backward reads.  Row source: ``ptr`` [G + 1]
+    (contiguous segments), ``dense_nodes`` (+ ``mask`` [rows] bytes), or ``index`` + ``node_index`` (+ ``weight``):
+    the rows of a sparse assignment (reduce/aggr_reduce.py:99-103 without the [nnz, F] product)."""
+    dev = N.require_device(x, ptr, mask, node_index, weight)
+    x = _rows_f32(x)
+    ptr = None if ptr is None else N.i64c(ptr)
+    node_index = None if node_index is None else N.i64c(node_index)
+    weight = None if weight is None else N.f32c(weight.reshape(-1))
+    mask = None if mask is None else mask.reshape(-1).contiguous()
+    if index is not None and (node_index is None or node_index.numel() != index.nnz
+                              or (weight is not None and weight.numel() != index.nnz)):
+        raise ValueError("segment readout: node_index and weight hold one entry per assignment of the index")
+    rows, F = x.shape
+    n_ops = bin(ops_mask).count("1")
+    n_mm = bin(ops_mask & ((1 << N.REDUCE_OPS["min"]) | (1 << N.REDUCE_OPS["max"]))).count("1")
+    out = torch.empty(num_groups, n_ops * F, dtype=torch.float32, device=dev)
+    ties = torch.empty(num_groups, n_mm * F, dtype=torch.int32, device=dev) if want_aux and n_mm else None
+    count = torch.empty(num_groups, dtype=torch.int32, device=dev) if want_aux else None
+    L = N.lib()
+    wsb = L.tgp_segment_aggr_workspace_bytes(num_groups, F, ops_mask, max_len)
+    ws = N.workspace(wsb, dev) if wsb else None
+    gathered = index is not None
+    _checked(L.tgp_segment_aggr_f32, N.ptr(x), rows, F, x.stride(0) if rows > 1 else max(x.stride(0), F), N.ptr(ptr),
+             dense_nodes, N.ptr(mask), N.ptr(index._row_ptr) if gathered else None,
+             N.ptr(index.perm) if gathered else None, N.ptr(node_index), N.ptr(weight), index.nnz if gathered else 0,
+             num_groups, max_len, ops_mask, N.ptr(out), N.ptr(ties), N.ptr(count), N.ptr(ws), wsb, N.stream_ptr(dev))
+    return out, ties, count
+
+
+def segment_aggr_bwd(g_out: Tensor, x: Tensor, out: Tensor, ties: Optional[Tensor], count: Tensor, ops_mask: int,
+                     num_groups: int, batch: Optional[Tensor] = None, dense_nodes: int = 0,
+                     mask: Optional[Tensor] = None) -> Tensor:
+    """dX [rows, F] of :func:`segment_aggr` for the contiguous and the dense sources, one launch, written once."""
+    dev = N.require_device(g_out, x, out, batch, mask)
+    g_out, x = N.f32c(g_out), _rows_f32(x)
+    rows, F = x.shape
+    dx = torch.empty(rows, F, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_segment_aggr_bwd_f32, N.ptr(g_out), N.ptr(x), rows, F,
+             x.stride(0) if rows > 1 else max(x.stride(0), F), N.ptr(batch), dense_nodes, N.ptr(mask), N.ptr(out),
+             N.ptr(ties), N.ptr(count), num_groups, ops_mask, N.ptr(dx), N.stream_ptr(dev))
+    return dx
