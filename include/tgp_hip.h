@@ -765,6 +765,31 @@ int tgp_dmon_ds_f32(const float* deg, const float* ca, const float* cs, const fl
                     const int64_t* batch, int64_t B, int64_t K, int accumulate, float* ds, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Just Balance pooling's auxiliary loss (poolers/just_balance.py, utils/losses.py:553-594, 1013-1080;
+ * csrc/just_balance.hip).  Per graph b, with c_k = sum_i S_ik^2 over the graph's rows:
+ *   out[b] = -sum_k sqrt(c_k + eps) / denom_b * scale,  denom_b = sqrt(n_b * num_supernodes) when normalize, else 1
+ * (the diagonal of sqrt(S^T S + eps); S^T S is never formed).  No float atomics: every sum has a fixed order.
+ * tgp_jb_terms_f32: S [rows,K] fp32.  Padded (ptr NULL, max_rows = N): graph b owns rows b N .. b N + graph_sizes[b]
+ *   (NULL: all N); n_b = the true entries of mask[b] (bytes, [B,N]) when mask is given, else graph_sizes[b], else
+ *   num_nodes.  Un-padded: rows ptr[b] .. ptr[b+1] (ptr [B+1], sorted batch; neither graph_sizes nor mask), n_b = the
+ *   graph's rows, max_rows = the largest graph.  max_rows <= 64: ONE launch, part is not touched (NULL ok); beyond, a
+ *   partial pass into part [B, ceil(max_rows / 64), K] and a one-workgroup-per-graph tail.  Writes out [B] and
+ *   coef [B,K] = -scale / (sqrt(c_k + eps) denom_b) for the backward (NULL: not written).  mean (NULL ok): one more
+ *   launch leaves the batch mean of out there, summed in a fixed order.  16-byte loads when K % 4 == 0 and S, part,
+ *   coef are 16-byte aligned, element loads otherwise.
+ * tgp_jb_ds_f32: ds[r,k] = g_b coef[b,k] S[r,k] over rows r of S (a fresh ds, nothing is accumulated); b = batch[r]
+ *   when batch is given (un-padded), else r / N; g [B], or one value for every graph when g_bcast != 0.
+ * TGP_ERR_INVALID: a NULL input or output, K < 1, sizes below zero, a layout that contradicts itself, a misaligned
+ * pointer (int64 tables 8 bytes, floats 4); TGP_ERR_RANGE: B, N, K, max_rows or B x splits beyond the int32 internals,
+ * a mask over N >= 2^24.  Both are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_jb_terms_f32(const float* S, int64_t B, int64_t N, int64_t K, const int64_t* graph_sizes, const uint8_t* mask,
+                     const int64_t* ptr, int64_t max_rows, int normalize, float num_nodes, float num_supernodes,
+                     float eps, float scale, float* part, float* out, float* coef, float* mean, void* stream);
+int tgp_jb_ds_f32(const float* S, const float* coef, const float* g, int g_bcast, int64_t rows, int64_t N,
+                  const int64_t* batch, int64_t B, int64_t K, float* ds, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * HOSC pooling's auxiliary losses (poolers/hosc.py, utils/losses.py:218-316, 392-432, 597-641), motif adjacency
  * M = A A A never formed:
  *   cut[b]    = -trace(S^T A S) / (den1 + eps),   den1 = sum_i d1_i |S_i|^2,  d1 = A 1

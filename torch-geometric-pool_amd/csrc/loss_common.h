@@ -1,4 +1,4 @@
-// What the dense-loss kernels (losses.hip, dmon.hip, hosc.hip, asym_cheeger.hip) share: the fixed-order block sums, the
+// What the dense-loss kernels (losses.hip, dmon.hip, hosc.hip, asym_cheeger.hip, just_balance.hip) share: the fixed-order block sums, the
 // orthogonality term and its gradient, the rows a graph owns, the streaming row pass over a padded A, and the launch of a
 // one-workgroup-per-graph tail.  Templates, inline device functions and launch macros only: nothing lands in a code
 // object that does not use it, and no kernel instantiation is in two of them.
@@ -9,7 +9,7 @@ namespace tgp {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int PART_ROWS = 64;  // rows of one graph per workgroup of a partial pass (dmon_part_kernel, hosc_part_kernel)
+constexpr int PART_ROWS = 64;  // rows of one graph per workgroup of a partial pass (dmon_part_kernel, hosc_part_kernel, jb_part_kernel)
 
 // ---- block sums ---------------------------------------------------------------------------------------------------
 // NV sums over the T threads of a workgroup behind ONE pair of barriers (sh: NV * T / 64 floats); every thread gets

@@ -238,6 +238,9 @@ SIGNATURES = {
     "tgp_dmon_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p,
                                              _c_p, _c_p]),
     "tgp_dmon_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_jb_terms_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_f, _c_f, _c_f, _c_f,
+                                  _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_jb_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "tgp_hosc_small_graph_nodes": (_c_int, []),
     "tgp_hosc_record_floats": (_c_i64, [_c_i64]),
     "tgp_hosc_matvec_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),

@@ -1762,7 +1762,7 @@ def mincut_loss_terms_bwd(raw: Tensor, den: Tensor, gram: Tensor, g_terms: Tenso
     return g_raw, c1, W
 
 
-_PART_ROWS = 64  # rows of one graph per workgroup of the DMoN / HOSC partial passes (PART_ROWS, csrc/loss_common.h)
+_PART_ROWS = 64  # rows of one graph per workgroup of the DMoN / HOSC / Just Balance partial passes (PART_ROWS, csrc/loss_common.h)
 
 
 def _mask_bytes(mask: Optional[Tensor], B: int, Nn: int) -> Optional[Tensor]:
@@ -1893,6 +1893,66 @@ def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: i
     N.check(N.lib().tgp_dmon_ds_f32(N.ptr(d), N.ptr(N.f32c(ca)), N.ptr(N.f32c(cs)), N.ptr(N.f32c(coef)), rows,
                                     nodes_per_graph, N.ptr(b), ca.size(0), ca.size(1), 1 if accumulate else 0, out.data_ptr(),
                                     N.stream_ptr(dev)), "tgp_dmon_ds_f32")
+    return out
+
+
+def jb_terms(s: Tensor, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None,
+             ptr: Optional[Tensor] = None, max_nodes: Optional[int] = None, normalize: bool = True,
+             num_nodes: Optional[int] = None, num_supernodes: Optional[int] = None, scale: float = 1.0,
+             want_coef: bool = True, want_mean: bool = False):
+    """(out [B], coef [B,K]): Just Balance's per-graph loss -sum_k sqrt(sum_i S_ik^2 + eps) / sqrt(n_b K) times
+    ``scale`` (utils/losses.py:553-594, 1013-1080; only the diagonal of S^T S is computed) and the coefficients
+    -scale / (sqrt(c_k + eps) sqrt(n_b K)) of its backward.  Padded ``s`` [B,N,K]: every graph's rows below
+    ``graph_sizes`` (None: all N) are summed; n_b = the mask's true entries, else the graph's size, else ``num_nodes``
+    (None: N).  Un-padded ``s`` [Ntot,K] with ``ptr`` [B+1] of the sorted batch and ``max_nodes`` its largest graph:
+    n_b = the graph's rows.  One launch when no graph has more than 64 rows, a partial pass and a tail otherwise.
+    ``want_coef`` False (inference): coef is None and not written.  ``want_mean``: a third value, the 0-dim batch mean
+    of out, from one more launch of the same native call (a fixed order of additions)."""
+    dev = N.require_device(s, mask, graph_sizes, ptr)
+    s = N.f32c(s)
+    if ptr is None:
+        if s.dim() != 3:
+            raise ValueError(f"jb_terms: a padded batch is [B,N,K], got {tuple(s.shape)}")
+        B, Nn, Kc = s.shape
+        rows_max = Nn
+        sizes, m, p = _sizes_arg(graph_sizes, B, dev), _mask_bytes(mask, B, Nn), None
+    else:
+        if s.dim() != 2 or mask is not None or graph_sizes is not None or max_nodes is None:
+            raise ValueError("jb_terms: an un-padded batch is [Ntot,K] with ptr and max_nodes, without mask or sizes")
+        p = N.i64c(ptr)
+        B, Nn, Kc = p.numel() - 1, 0, s.size(1)
+        rows_max = int(max_nodes)
+        sizes = m = None
+    if Kc < 1:
+        raise ValueError("jb_terms: S needs at least one column")
+    nsplit = max(1, -(-rows_max // _PART_ROWS))
+    part = torch.empty(B, nsplit, Kc, dtype=torch.float32, device=dev) if nsplit > 1 else None
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    coef = torch.empty(B, Kc, dtype=torch.float32, device=dev) if want_coef else None
+    mean = torch.empty((), dtype=torch.float32, device=dev) if want_mean else None
+    N.check(N.lib().tgp_jb_terms_f32(N.ptr(s), B, Nn, Kc, N.ptr(sizes), N.ptr(m), N.ptr(p), rows_max,
+                                     1 if normalize else 0, float(Nn if num_nodes is None else num_nodes),
+                                     float(Kc if num_supernodes is None else num_supernodes), losses_eps(), float(scale),
+                                     N.ptr(part), N.ptr(out), N.ptr(coef), N.ptr(mean), N.stream_ptr(dev)),
+            "tgp_jb_terms_f32")
+    return (out, coef, mean) if want_mean else (out, coef)
+
+
+def jb_ds(s: Tensor, coef: Tensor, g: Tensor, batch: Optional[Tensor] = None) -> Tensor:
+    """dS = g_b coef[b,k] S of :func:`jb_terms` in one elementwise launch, into a fresh tensor of S's shape.  ``g`` [B]
+    upstream gradients (an expanded scalar, what a mean over the batch sends, is read as one value); the graph of a
+    row is batch[r] (un-padded ``s`` [Ntot,K]; None: one graph) or its first index (padded [B,N,K])."""
+    dev = N.require_device(s, coef, g, batch)
+    s, coef = N.f32c(s), N.f32c(coef)
+    B, Kc = coef.shape
+    g, bcast = _bcast_or_dense(g, (B,))
+    if s.dim() == 3:
+        rows, per, b = s.size(0) * s.size(1), max(s.size(1), 1), None
+    else:
+        rows, per, b = s.size(0), max(s.size(0), 1), None if batch is None else N.i64c(batch)
+    out = torch.empty_like(s)
+    N.check(N.lib().tgp_jb_ds_f32(N.ptr(s), N.ptr(coef), N.ptr(g), 1 if bcast else 0, rows, per, N.ptr(b), B, Kc,
+                                  N.ptr(out), N.stream_ptr(dev)), "tgp_jb_ds_f32")
     return out
 
 

@@ -1,11 +1,12 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,sag,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,edge_contraction,lapool}.py).
+(reference tgp/poolers/{__init__,topk,sag,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,just_balance,edge_contraction,lapool}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
-``HOSCPooling``, ``BNPool``, ``EdgeContractionPooling``, ``LaPooling`` and ``SAGPooling`` are built and exported as
-classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``edgepool`` / ``lap`` / ``sag`` aliases are not registered yet.
+``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling`` and ``SAGPooling`` are built
+and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` aliases
+are not registered yet.
 """
 from __future__ import annotations
 
@@ -45,6 +46,8 @@ from ..utils.losses import (
     unbatched_hosc_orthogonality_loss,
     dmon_loss_terms,
     entropy_loss,
+    _jb_native,
+    jb_loss_mean,
     link_pred_loss,
     mincut_loss,
     mincut_loss_terms,
@@ -418,15 +421,20 @@ class _DenseMLPPooling(DenseSRCPooling):
     def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
         raise NotImplementedError
 
+    def _sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
+        return self.compute_sparse_loss(edge_index, edge_weight, S, batch)
+
     # which auxiliary losses the pooler computes: "diff" (link + entropy), "mincut" (cut + ortho: their per-graph
     # terms come out of the pooling kernels), "dmon" (spectral + cluster + ortho from the raw S^T A S and their own
     # loss kernels), "acc" (total variation + balance from the adjacency and S alone, their own loss kernels), "hosc"
     # (first-order + motif cut and an orthogonality term: the raw S^T A S, the adjacency and S, their own loss kernels),
-    # "bnpool" (reconstruction of the adjacency from S K S^T, its own tile kernels; a KL and a prior term as torch ops)
+    # "bnpool" (reconstruction of the adjacency from S K S^T, its own tile kernels; a KL and a prior term as torch ops),
+    # "jb" (Just Balance: the column norms of S alone, its own loss kernel; neither the adjacency nor S^T A S is read)
     _loss_kind = "diff"
     # kinds whose losses come from loss kernels of their own behind the operator route: the one-node training paths
     # (_SelectPoolSmallFn, _PoolLargeFn, _PoolUnbatchedFn, the sparse training node) and the rows route decline them
-    _LOSS_ONLY_KINDS = ("dmon", "acc", "hosc", "bnpool")
+    # ("jb" declines the rows route only under autograd: in inference its loss kernel runs on the route's un-padded S)
+    _LOSS_ONLY_KINDS = ("dmon", "acc", "hosc", "bnpool", "jb")
 
     # kinds whose losses walk the dense adjacency itself (ACC's total variation counts its nonzero entries, HOSC's motif
     # chain multiplies by it three times, BN-Pool's reconstruction loss meets every entry of it): they also decline the
@@ -574,6 +582,12 @@ class _DenseMLPPooling(DenseSRCPooling):
                 want_raw=True, mincut_terms=False)
             deg = K.dmon_edge_degrees(edge_index, edge_weight, info.ptr, edge_ptr, info.max_nodes, self.adj_transpose)
             terms = self._dmon_means(s, raw, mask, info.sizes, deg=deg)
+        elif self._loss_kind == "jb":  # the launch writes S; the loss reads nothing else: no dense adjacency, no raw
+            s, mask, x_pool, raw, adj_pool, _, bp = K.dense_pool_select_sparse(
+                x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
+                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
+                want_raw=False, mincut_terms=False)
+            terms = self._jb_mean(s, mask, info.sizes)
         else:  # DiffPool, inference (r6): both losses from per-graph records of the same launch -- no dense adjacency
             s, mask, x_pool, raw, adj_pool, terms, bp, dstats = K.dense_pool_select_sparse(
                 x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
@@ -704,7 +718,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         from .. import kernels as K
         from .. import functions as Fn
         c, sel = self.connector, self.selector
-        if (self._loss_only or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
+        jb = self._loss_kind == "jb"  # (its loss reads S alone: the one loss-only kind this route serves, in inference)
+        if ((self._loss_only and not jb) or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
                 or (self.sparse_output and not batched_out)
                 or not (isinstance(x, Tensor) and isinstance(edge_index, Tensor))
                 or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32
@@ -717,6 +732,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         grad = torch.is_grad_enabled()
         if grad and edge_weight is not None and edge_weight.requires_grad:
             return None
+        if jb and (not batched_out or (grad and (x.requires_grad or any(p.requires_grad for p in sel.parameters())))):
+            return None  # (Just Balance trains, and runs its unbatched mode, on the operator route)
         n = x.size(0)
         info = None
         if batch is not None:
@@ -743,7 +760,7 @@ class _DenseMLPPooling(DenseSRCPooling):
         # inference with a single-Linear selector (r6, late): the selector rides in the ONE native call of the forward
         # (kernels.pool_rows_forward); the SelectOutput is built from the S it leaves
         fold_inference = (not grad and single and K._POOL_ROWS_ONE_CALL and x.dtype == torch.float32 and x.is_contiguous()
-                          and lins[0].weight.size(0) <= 256)
+                          and lins[0].weight.size(0) <= 256 and not jb)
         if fold_inference:
             weight, bias = lins[0].weight.detach(), None if lins[0].bias is None else lins[0].bias.detach()
             s, training = None, False
@@ -784,7 +801,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                               c.edge_weight_norm)
         mincut = self._mincut_terms
         sw2, scales = 0.0, (0.0, 0.0)
-        if not mincut:  # DiffPool: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
+        if not mincut and not jb:  # DiffPool: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
             # (batched form, losses.py:644-652: the dense A has the duplicates summed -- the same list after coalescing)
             if batched_out and not unit:
                 sw2 = torch.dot(w, w)
@@ -805,6 +822,8 @@ class _DenseMLPPooling(DenseSRCPooling):
                 transposed)
             s_flat = s_out
             both = pair
+        elif jb:  # (the staged operators below: the one-call entry's loss modes are MinCut's and DiffPool's)
+            one = None
         else:
             one = K.pool_rows_forward(x, weight if s is None else None, bias if s is None else None, s, row_ptr, ei, w_used,
                                       ptr, max_nodes, transposed, flags, 1 if mincut else 2, scales, sw2)
@@ -814,6 +833,12 @@ class _DenseMLPPooling(DenseSRCPooling):
         if not training and one is not None:
             s, raw, x_pool, adj_pool = one["s"], one["raw"], one["x_pool"], one["adj_pool"]
             both = one["both"] if mincut else one["lossv"]
+            s_flat = s
+        elif jb:  # T = A S, S^T [T | X] with the post-processing, the loss kernel on the un-padded S
+            t = K.spmm_csr(row_ptr, ei, w_used, n, s)
+            raw, x_pool, adj_pool = K.segment_gemm_tn3(s, [t, x], ptr, max_nodes, transpose0=transposed, post_flags=flags)
+            both = K.jb_terms(s, ptr=ptr, max_nodes=max_nodes, normalize=bool(self.normalize_loss),
+                              scale=float(self.loss_coeff), want_coef=False, want_mean=True)[2]
             s_flat = s
         elif not training:
             if mincut:  # out-degrees and |S_i|^2 ride along with T = A S
@@ -846,6 +871,8 @@ class _DenseMLPPooling(DenseSRCPooling):
         if mincut:
             loss = {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
                     "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
+        elif jb:
+            loss = {"balance_loss": both}
         else:
             loss = {"link_loss": both[0], "entropy_loss": both[1]}
         batch_pool = self.reducer.reduce_batch(so, batch if batch is not None else so.batch)
@@ -962,7 +989,7 @@ class _DenseMLPPooling(DenseSRCPooling):
             so, x_pool, adj_pool, batch_pool, loss = fused
             return PoolingOutput(x=x_pool, edge_index=adj_pool, edge_weight=None, batch=batch_pool, so=so, loss=loss)
         so = fused[0] if fused is not None else self.select(x=x, batch=batch)
-        loss = self.compute_sparse_loss(adj, edge_weight, so.s, batch)
+        loss = self._sparse_loss(adj, edge_weight, so.s, batch)
         x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch, return_batched=not self.sparse_output)
         ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
                               batch_pooled=batch_pool)
@@ -1158,6 +1185,73 @@ class DMoNPooling(_DenseMLPPooling):
     def extra_repr_args(self) -> dict:
         return {"batched": self.batched, "spectral_loss_coeff": self.spectral_loss_coeff,
                 "cluster_loss_coeff": self.cluster_loss_coeff, "ortho_loss_coeff": self.ortho_loss_coeff}
+
+
+class JustBalancePooling(_DenseMLPPooling):
+    r"""Just Balance pooling ("Simplifying Clustering with Graph Neural Networks", Bianchi, NLDL 2023; reference
+    poolers/just_balance.py:17-322): MinCut's Select / Reduce / Connect with the single balance loss
+    -trace(sqrt(S^T S + eps)), by default divided by sqrt(n K) per graph, times ``loss_coeff``.  The loss reads S alone
+    -- neither the adjacency nor S^T A S -- and only the diagonal of S^T S is ever computed.
+
+    A NaN loss raises ``ValueError("Loss is NaN")`` where the loss is composed of torch ops (float64, host tensors, an
+    unsorted batch vector); behind the loss kernel the check would be a wait for the device and is not made.
+    ``data_transforms()`` returns None: the reference's ``NormalizeAdj`` lives in its ``tgp.data``, which this project
+    does not have."""
+
+    _loss_kind = "jb"
+
+    def __init__(self, in_channels: Union[int, List[int]], k: int, act: str = None, dropout: float = 0.0,
+                 normalize_loss: bool = True, loss_coeff: float = 1.0, remove_self_loops: bool = True,
+                 degree_norm: bool = True, edge_weight_norm: bool = False, adj_transpose: bool = True,
+                 lift: str = "precomputed", s_inv_op: str = "transpose", batched: bool = True,
+                 sparse_output: bool = False, cache_preprocessing: bool = False):
+        super().__init__(in_channels, k, act, dropout, remove_self_loops, degree_norm, edge_weight_norm,
+                         adj_transpose, lift, s_inv_op, batched, sparse_output, cache_preprocessing)
+        self.normalize_loss = normalize_loss
+        self.loss_coeff = loss_coeff
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
+        adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
+                                   batch_pooled=batch_pooled)
+        return adj_pool, self._loss_of(so, mask, self._sizes_for(adj))
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+        if terms is not None:  # the one-launch sparse route: the batch mean, loss_coeff applied
+            return {"balance_loss": terms}
+        return self._loss_of(so, mask, self._sizes_for(adj))
+
+    def _loss_of(self, so, mask, graph_sizes) -> dict:
+        if graph_sizes is not None and _jb_native(so.s):
+            # (the selector zeroed the padded rows of its own S, so the pass over S stops at each graph's size)
+            return {"balance_loss": self._jb_mean(so.s, mask, graph_sizes)}
+        return self.compute_loss(so.s, mask, so.num_nodes, so.num_supernodes)
+
+    def _jb_mean(self, S, mask, graph_sizes) -> Tensor:
+        """The batch mean of the per-graph loss, ``loss_coeff`` applied by the loss kernel itself."""
+        return jb_loss_mean(S, mask, graph_sizes, None, self.normalize_loss, scale=self.loss_coeff)
+
+    def compute_loss(self, S: Tensor, mask: Optional[Tensor] = None, num_nodes: Optional[int] = None,
+                     num_supernodes: Optional[int] = None) -> dict:
+        loss = jb_loss_mean(S, mask, None, None, self.normalize_loss, num_nodes, num_supernodes, scale=self.loss_coeff)
+        if not _jb_native(S) and torch.isnan(loss):  # (behind the kernel the check would be a wait for the device)
+            raise ValueError("Loss is NaN")
+        return {"balance_loss": loss}
+
+    def compute_sparse_loss(self, S: Tensor, batch: Optional[Tensor]) -> dict:
+        loss = jb_loss_mean(S, batch=batch, normalize_loss=self.normalize_loss, scale=self.loss_coeff)
+        if not _jb_native(S, batch) and torch.isnan(loss):
+            raise ValueError("Loss is NaN")
+        return {"balance_loss": loss}
+
+    def _sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
+        return self.compute_sparse_loss(S, batch)
+
+    @staticmethod
+    def data_transforms():
+        return None
+
+    def extra_repr_args(self) -> dict:
+        return {"batched": self.batched, "loss_coeff": self.loss_coeff, "normalize_loss": self.normalize_loss}
 
 
 class AsymCheegerCutPooling(_DenseMLPPooling):
@@ -1502,8 +1596,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "edgepool" (EdgeContractionPooling), "lap" (LaPooling) and "sag" (SAGPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling) and "sag" (SAGPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

@@ -394,6 +394,111 @@ def unbatched_cluster_loss(S: Tensor, batch: Optional[Tensor] = None, batch_redu
     return _reduce(torch.norm(_seg_sum(S, bvec, nb), dim=1) / sizes * math.sqrt(k) - 1, batch_reduction)
 
 
+# ------------------------------------------------------------------------------------------------ Just Balance
+class _JBTermsFn(torch.autograd.Function):
+    """[B] per-graph values of Just Balance's loss -sum_k sqrt(sum_i S_ik^2 + eps) / sqrt(n_b K), times ``scale``
+    (utils/losses.py:553-594, 1013-1080), with a native backward.  Forward: one launch when no graph has more than 64
+    rows, else the partial pass over S and a tail; the tail leaves coef [B,K].  Backward: one elementwise launch
+    dS = g_b coef_bk S.
+
+    ``layout``: ("dense", mask, graph_sizes, num_nodes) for S [B,N,K] or ("flat", ptr, batch, max_nodes) for S [Ntot,K]
+    of a sorted batch."""
+
+    @staticmethod
+    def forward(ctx, S, layout, normalize, num_supernodes, scale):
+        if layout[0] == "dense":
+            out, coef = K.jb_terms(S, mask=layout[1], graph_sizes=layout[2], normalize=normalize, num_nodes=layout[3],
+                                   num_supernodes=num_supernodes, scale=scale)
+        else:
+            out, coef = K.jb_terms(S, ptr=layout[1], max_nodes=layout[3], normalize=normalize,
+                                   num_supernodes=num_supernodes, scale=scale)
+        ctx.save_for_backward(S, coef)
+        ctx.batch = None if layout[0] == "dense" else layout[2]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S, coef = ctx.saved_tensors
+        g_s = K.jb_ds(S, coef, g, ctx.batch).to(S.dtype) if ctx.needs_input_grad[0] else None
+        return g_s, None, None, None, None
+
+
+def _jb_native(S: Tensor, batch: Optional[Tensor] = None) -> bool:
+    """The kernels take a float32 device S (un-padded: of a sorted batch); float64, host tensors and an unsorted batch
+    vector take the composed torch form."""
+    if not (S.is_cuda and S.dtype == torch.float32 and S.numel() > 0):
+        return False
+    if S.dim() == 3 or batch is None:
+        return True
+    from .ops import batch_info
+    return batch_info(batch).is_sorted  # (memoised per batch vector)
+
+
+def jb_loss_terms(S: Tensor, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None,
+                  batch: Optional[Tensor] = None, normalize_loss: bool = True, num_nodes: Optional[int] = None,
+                  num_supernodes: Optional[int] = None, scale: float = 1.0) -> Tensor:
+    """[B]: per-graph values of :func:`just_balance_loss` (S [B,N,K], ``mask``; ``graph_sizes``, this build only: real
+    nodes per graph of a batch whose padded rows of S are zero, lets the pass skip them) or of
+    :func:`unbatched_just_balance_loss` (S [Ntot,K], ``batch``), before the batch reduction, times ``scale``.  Only the
+    diagonal of S^T S is computed.  float32 device S (and a sorted batch): the kernels; otherwise torch ops."""
+    k = S.size(-1) if num_supernodes is None else num_supernodes
+    if S.dim() == 3:
+        if _jb_native(S):
+            return _JBTermsFn.apply(S, ("dense", mask, graph_sizes, num_nodes), bool(normalize_loss), k, float(scale))
+        loss = -torch.sqrt((S * S).sum(dim=1) + eps).sum(dim=-1)
+        if normalize_loss:
+            if mask is None:
+                n = S.size(1) if num_nodes is None else num_nodes
+                loss = loss / torch.tensor(n * k, dtype=loss.dtype, device=loss.device).sqrt()
+            else:
+                loss = loss / (mask.sum(dim=1).to(loss.dtype) * float(k)).sqrt()
+        return loss if scale == 1 else loss * scale
+    n = S.size(0)
+    if _jb_native(S, batch):
+        return _JBTermsFn.apply(S, _flat_layout(S, batch), bool(normalize_loss), S.size(1), float(scale))
+    bvec = _batch_or_zeros(batch, n, S.device)
+    nb = num_graphs_of(batch)
+    loss = -torch.sqrt(_seg_sum(S * S, bvec, nb) + eps).sum(dim=-1)
+    if normalize_loss:
+        sizes = torch.bincount(bvec, minlength=nb)[:nb].to(loss.dtype)
+        loss = loss / (sizes * float(S.size(1))).sqrt()
+    return loss if scale == 1 else loss * scale
+
+
+def jb_loss_mean(S: Tensor, mask: Optional[Tensor] = None, graph_sizes: Optional[Tensor] = None,
+                 batch: Optional[Tensor] = None, normalize_loss: bool = True, num_nodes: Optional[int] = None,
+                 num_supernodes: Optional[int] = None, scale: float = 1.0) -> Tensor:
+    """The batch mean of :func:`jb_loss_terms` (what the pooler hands out).  Inference on the kernels' path is ONE native
+    call: no autograd node, no coefficients for a backward, the mean from a launch of the same call; with
+    ``graph_sizes`` they also give n_b, which the mask would only count again."""
+    if _jb_native(S, batch) and not (torch.is_grad_enabled() and S.requires_grad):
+        k = S.size(-1) if num_supernodes is None else num_supernodes
+        if S.dim() == 3:
+            return K.jb_terms(S, mask=None if graph_sizes is not None else mask, graph_sizes=graph_sizes,
+                              normalize=bool(normalize_loss), num_nodes=num_nodes, num_supernodes=k, scale=float(scale),
+                              want_coef=False, want_mean=True)[2]
+        layout = _flat_layout(S, batch)
+        return K.jb_terms(S, ptr=layout[1], max_nodes=layout[3], normalize=bool(normalize_loss), scale=float(scale),
+                          want_coef=False, want_mean=True)[2]
+    return jb_loss_terms(S, mask, graph_sizes, batch, normalize_loss, num_nodes, num_supernodes, scale).mean()
+
+
+def just_balance_loss(S: Tensor, mask: Optional[Tensor] = None, normalize_loss: bool = True,
+                      num_nodes: Optional[int] = None, num_supernodes: Optional[int] = None,
+                      batch_reduction: str = "mean") -> Tensor:
+    """Just Balance's loss -trace(sqrt(S^T S + eps)) per graph of a padded batch S [B,N,K], over ALL N rows of S (the
+    mask only counts n_b); ``normalize_loss``: divided by sqrt(n_b K), n_b = mask.sum(1), without a mask ``num_nodes``
+    (default N); K = ``num_supernodes`` (default the columns of S) (reference utils/losses.py:1013-1080)."""
+    return _reduce(jb_loss_terms(S, mask, None, None, normalize_loss, num_nodes, num_supernodes), batch_reduction)
+
+
+def unbatched_just_balance_loss(S: Tensor, batch: Optional[Tensor] = None, normalize_loss: bool = True,
+                                batch_reduction: str = "mean") -> Tensor:
+    """The same loss of an un-padded batch S [Ntot,K]: graph g owns the rows with batch == g (None: one graph),
+    n_g = their number (reference utils/losses.py:553-594)."""
+    return _reduce(jb_loss_terms(S, batch=batch, normalize_loss=normalize_loss), batch_reduction)
+
+
 # ------------------------------------------------------------------------------------------------ AsymCheegerCut
 class _ACCTermsFn(torch.autograd.Function):
     """[2,B] per-graph total-variation and balance (asymmetric norm) terms of AsymCheegerCut pooling
