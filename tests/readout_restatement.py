@@ -1,7 +1,13 @@
 """Plain-torch restatement of the aggregation readout (reference reduce/aggr_reduce.py + global_reduce.py over PyG's
 ``scatter``): what ``AggrReduce`` / ``GlobalReduce`` return for sum / mean / max / min and a ``multi`` of them, in any
 float dtype, on any device.  ``test_readout_restatement.py`` holds it against every case of ``golden_readout_v1.pt``;
-the GPU tests use it in float64 as the reference of shapes the fixture does not hold."""
+the GPU tests use it in float64 as the reference of shapes the fixture does not hold.
+
+Values are the reference's everywhere.  The BACKWARD of max / min differs from the reference's in one case: a group whose
+extreme is exactly 0.  The reference starts ``scatter_reduce`` from zeros, and ATen's backward counts that initial 0 as
+one more tied entry (each tied row gets 1 / (ties + 1)); here the extremes start from -inf / +inf and each tied row gets
+1 / ties, which is the derivative and what the kernels compute.  The fixture's gradients (of ``sum(out ** 2)``, zero
+wherever the output is) cannot tell the two apart."""
 import os
 
 import torch
@@ -27,8 +33,14 @@ def scatter(src, index, dim_size, op):
             count = src.new_zeros(dim_size).index_add(0, index, src.new_ones(index.numel())).clamp(min=1)
             out = out / count.view(-1, 1)
         return out
+    # (the extremes start from -inf / +inf, not from the zeros an empty group ends with: the backward of ATen's
+    #  scatter_reduce counts the initial value among the tied entries even with include_self=False, so a group whose
+    #  extreme is exactly 0 would hand its rows 1 / (ties + 1) of the gradient instead of 1 / ties)
     idx = index.view(-1, 1).expand_as(src)
-    return out.scatter_reduce(0, idx, src, reduce="amax" if op == "max" else "amin", include_self=False)
+    start = torch.full_like(out, float("-inf") if op == "max" else float("inf"))
+    ext = start.scatter_reduce(0, idx, src, reduce="amax" if op == "max" else "amin", include_self=False)
+    some = torch.zeros(dim_size, dtype=torch.bool, device=src.device).index_fill(0, index, True)
+    return torch.where(some.view((-1,) + (1,) * (src.dim() - 1)), ext, out)
 
 
 def aggregate(src, index, dim_size, ops):

@@ -1,0 +1,1094 @@
+"""Seeded differential sweep of the newer kernel families against the float64 restatements.
+
+Every test draws its inputs from tests/fuzz_inputs.py (16 seeds per family and layer: the smallest shapes at which a
+kernel changes behaviour, every layout its wrapper accepts), runs the ``tgp.kernels`` wrappers (operator layer: the
+forward and the native backward operator on the same upstream gradient) or the public functions and classes (public
+layer: values per graph, gradients one output at a time) and compares with tests/fuzz_refs.py by the rule of
+tests/fuzz_compare.py.  Integer outputs are compared with ``torch.equal``.  Each test asserts the route its draw was
+made to reach where the wrapper reports one.  On one seed in four the same call runs twice (equal bits, forward and
+backward) and the padded and the un-padded layout of the same batch are both held to the bound.
+
+Every comparison prints a ``FUZZ`` line with e_kernel / e_r32; the worst ratios of the last measured run are in
+profiles/fuzz_newer_families.txt.
+
+Families: Just Balance, DMoN's, HOSC's and AsymCheegerCut's losses, LaPool's selector, BN-Pool's reconstruction loss, the
+segment readout,
+the SAG scorer, the k-MIS selector, the edge-contraction selector.
+"""
+import zlib
+
+import pytest
+import torch
+
+import fuzz_inputs as FI
+import fuzz_refs as FR
+from fuzz_compare import factor_of, forward_errors, grad_path_errors, print_grad_report, print_report
+from test_gpu_grad_paths import _graph_names
+
+pytestmark = pytest.mark.gpu
+
+SEEDS = list(FI.SEEDS)
+F64, F32 = torch.float64, torch.float32
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def mv(t):
+    return None if t is None else t.to(dev())
+
+
+def limits():
+    return FI.library_limits()
+
+
+def offset_by_one_element(t):
+    """The same values in a contiguous view that starts 4 bytes into its buffer (rows not 16-byte aligned)."""
+    buf = torch.zeros(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:] = t.reshape(-1)
+    out = buf[1:].view(t.shape)
+    assert out.is_contiguous() and (t.numel() == 0 or out.data_ptr() % 16 == 4)
+    return out
+
+
+def upstream(case, *shape):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(zlib.crc32(case.encode())))
+
+
+def finish(case, fails, report, kind="forward"):
+    print_report(report, kind)
+    assert not fails, "\n".join(fails)
+
+
+def check_grads(case, kernel, oracle, leaves):
+    report = []
+    fails = grad_path_errors(case, kernel, oracle, leaves, report=report)
+    print_grad_report(case, report)
+    assert not fails, "\n".join(fails)
+    return report
+
+
+# ===================================================================================================== Just Balance
+def _jb_inputs(d, layout=None):
+    """(S on the device, the wrapper's keyword arguments, the batch vector of an un-padded S) for the drawn layout."""
+    lay = d["layout"] if layout is None else layout
+    if lay in ("ptr", "ptr_offset"):
+        s = mv(d["s_flat"])
+        if lay == "ptr_offset":
+            s = offset_by_one_element(s)
+        return s, dict(ptr=mv(d["ptr"]), max_nodes=max(d["sizes"])), mv(d["batch"])
+    if lay == "sizes":
+        return mv(d["s_padded"]), dict(graph_sizes=mv(torch.tensor(d["sizes"]))), None
+    if lay == "mask_prefix":
+        return mv(d["s_padded"]), dict(mask=mv(d["mask"])), None
+    return mv(d["s"]), dict(mask=mv(d["mask"])), None
+
+
+def _jb_view(d, layout):
+    """The draw as the other layout of the same batch sees it (padded rows of S are zero there)."""
+    v = dict(d)
+    v["padded"] = layout in ("sizes", "mask_prefix")
+    v["s"] = d["s_padded"] if v["padded"] else d["s_flat"]
+    return v
+
+
+def _jb_operator(d, case, layout, report, twice):
+    from tgp import kernels as K
+    v = _jb_view(d, layout) if "s_flat" in d else d
+    s, kw, batch = _jb_inputs(d, layout)
+    out, coef = K.jb_terms(s, **kw)
+    assert out.dtype == F32 and tuple(out.shape) == (d["B"],) and tuple(coef.shape) == (d["B"], d["K"])
+    fin = FR.jb_finite(v)
+    for b in range(d["B"]):
+        if b not in fin:
+            assert float(out[b]) == float("-inf"), (case, b, float(out[b]))  # no real node: as the composed form
+    r64, r32 = FR.jb_reference(v, F64)[0], FR.jb_reference(v, F32)[0]
+    fails = forward_errors(case, FR.jb_split(v, out), r64, r32, factor=factor_of("jb"), report=report)
+    # the native backward operator on the same upstream gradient, one graph at a time
+    g = upstream(case, d["B"])
+    g[[b for b in range(d["B"]) if b not in fin]] = 0
+    ds = K.jb_ds(s, coef, mv(g), batch)
+    assert ds.shape == s.shape
+
+    def ref_grads(dtype):
+        outs, lv = FR.jb_reference(v, dtype)
+        if not outs:
+            return {}
+        total = sum(g[b].to(dtype) * outs[f"term[{b}]"] for b in fin)
+        (gs,) = torch.autograd.grad(total, lv["s"])
+        return {f"dS[{b}]": FR.jb_rows(v, gs, b) for b in fin}
+    g64, g32 = ref_grads(F64), ref_grads(F32)
+    got = {f"dS[{b}]": FR.jb_rows(v, ds.cpu(), b) for b in fin}
+    fails += forward_errors(case, got, g64, g32, factor=factor_of("jb"), report=report)
+    for b in fin:
+        rows = got[f"dS[{b}]"]
+        if d["zero_col"]:
+            assert bool((rows[:, d["K"] // 2] == 0).all()), (case, b)  # c_k = 0: the coefficient stays finite
+        if v["padded"] and layout in ("sizes", "mask_prefix"):
+            assert bool((rows[d["sizes"][b]:] == 0).all()), (case, b)  # padded rows: exact zeros
+    if twice:
+        out2, coef2 = K.jb_terms(s, **kw)
+        assert torch.equal(out, out2) and torch.equal(coef, coef2)
+        # (equal_nan: the rows of a graph without a real node are 0 * inf)
+        torch.testing.assert_close(K.jb_ds(s, coef2, mv(g), batch), ds, rtol=0, atol=0, equal_nan=True)
+    return fails
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_jb_operators(seed):
+    d = FI.draw("jb", seed, limits())
+    case, report = f"jb-op-{seed}", []
+    fails = _jb_operator(d, case, d["layout"], report, seed % 4 == 0)
+    if seed % 4 == 0 and "s_flat" in d:  # the padded and the un-padded layout of the same batch, both within the bound
+        other = "ptr" if d["padded"] else "sizes"
+        fails += _jb_operator(d, f"{case}-as-{other}", other, report, False)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_jb_public(seed):
+    from tgp.utils.losses import jb_loss_terms, just_balance_loss, unbatched_just_balance_loss
+    d = FI.draw("jb", seed, limits())
+    case = f"jb-public-{seed}"
+    fin = FR.jb_finite(d)
+    keep = mv(FR.jb_row_mask(d))
+    seen = {}
+
+    def kernel():
+        s, kw, batch = _jb_inputs(d)
+        leaf = s.detach().clone().requires_grad_(True)
+        s_in = torch.where(keep, leaf, leaf.detach())  # rows of a graph without a real node carry 0 * inf in every form
+        if d["layout"] == "ptr_offset":
+            s_in = offset_by_one_element(s_in)
+        if d["padded"]:
+            terms = jb_loss_terms(s_in, kw.get("mask"), kw.get("graph_sizes"))
+        else:
+            terms = jb_loss_terms(s_in, batch=batch)
+        seen["terms"], seen["s"] = terms, s_in
+        return FR.jb_split(d, terms), {"s": leaf}
+
+    outs, _ = kernel()
+    assert "_JBTermsFnBackward" in _graph_names(seen["terms"].grad_fn)
+    report = []
+    r64, r32 = FR.jb_reference(d, F64)[0], FR.jb_reference(d, F32)[0]
+    fails = forward_errors(case, outs, r64, r32, factor=factor_of("jb"), report=report)
+    # the reduced forms the public names hand out: the same terms, reduced in float32
+    with torch.no_grad():
+        if d["padded"] and d["layout"] != "sizes":
+            total = just_balance_loss(seen["s"], mv(d["mask"]), batch_reduction="sum")
+        elif not d["padded"]:
+            total = unbatched_just_balance_loss(seen["s"], mv(d["batch"]), batch_reduction="sum")
+        else:
+            total = None
+    if total is not None and len(fin) == seen["terms"].numel():
+        want = {"sum": sum(r64.values())}
+        fails += forward_errors(case, {"sum": total}, want, {"sum": sum(r32.values())}, factor=factor_of("jb"),
+                                report=report)
+    finish(case, fails, report)
+    if fin:
+        check_grads(case, kernel, lambda dt: FR.jb_reference(d, dt), ["s"])
+    if seed % 4 == 0 and fin:  # the same public call twice: equal bits, forward and backward
+        runs = []
+        for _ in range(2):
+            o, lv = kernel()
+            total = sum(o.values())
+            runs.append((seen["terms"].detach().clone(), torch.autograd.grad(total, lv["s"])[0]))
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]), case
+
+
+# ============================================================================================================= DMoN
+def _per_graph(name, t, graphs=None):
+    return {f"{name}[{b}]": t[b] for b in (range(t.size(0)) if graphs is None else graphs)}
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_dmon_operators(seed):
+    """``dmon_dense_terms`` (degrees and the per-block partial sums), ``dmon_node_terms`` and ``dmon_edge_degrees`` on
+    the same batch un-padded, and the backward's elementwise ``dmon_ds``, each against its plain statement."""
+    from tgp import kernels as K
+    lim = limits()
+    d = FI.draw("dmon", seed, lim)
+    case, report, part_rows = f"dmon-op-{seed}", [], lim["part_rows"]
+    s, adj, mask, sizes = mv(d["s"]), mv(d["adj"]), mv(d["mask"]), mv(d["graph_sizes"])
+    deg, part = K.dmon_dense_terms(adj, s, mask, sizes)
+    B, N, Kc = d["s"].shape
+    assert tuple(part.shape) == (B, max(1, -(-N // part_rows)), 2 * Kc + 2)  # one block / the partial pass
+    (d64, p64), (d32, p32) = FR.dmon_partial_sums(d, F64, part_rows), FR.dmon_partial_sums(d, F32, part_rows)
+    ref64 = {**_per_graph("deg", d64), **_per_graph("part", p64)}
+    ref32 = {**_per_graph("deg", d32), **_per_graph("part", p32)}
+    zeros = {f"deg[{b}]": ~d["real"][b] for b in range(B)}
+    fails = forward_errors(case, {**_per_graph("deg", deg), **_per_graph("part", part)}, ref64, ref32, zeros=zeros,
+                           factor=factor_of("dmon"), report=report)
+    assert torch.equal(part[:, :, 2 * Kc + 1].sum(1).cpu(), torch.tensor(d["n_b"], dtype=F32)), case  # the node counts
+    if seed % 4 == 0:
+        deg2, part2 = K.dmon_dense_terms(adj, s, mask, sizes)
+        assert torch.equal(deg, deg2) and torch.equal(part, part2)
+    if d["prefix"]:  # the un-padded layout of the same batch: both within the bound
+        longest = max(d["n_b"])
+        ptr = mv(d["ptr"])
+        for in_deg in (False, True):
+            de = K.dmon_edge_degrees(mv(d["edge_index"]), mv(d["edge_weight"]), ptr, mv(d["edge_ptr"]), longest, in_deg)
+            want64 = (d["adj"].double().sum(1) if in_deg else d64)[:, :longest]
+            want32 = (d["adj"].sum(1) if in_deg else d32)[:, :longest]
+            fails += forward_errors(f"{case}-edge-degrees-{'in' if in_deg else 'out'}", _per_graph("deg", de),
+                                    _per_graph("deg", want64), _per_graph("deg", want32),
+                                    zeros={f"deg[{b}]": ~d["real"][b, :longest] for b in range(B)},
+                                    factor=factor_of("dmon"), report=report)
+        deg_flat = torch.cat([deg[b, :c] for b, c in enumerate(d["n_b"])])
+        part_f = K.dmon_node_terms(mv(d["s_flat"]), deg_flat, ptr, longest)
+        f64, f32 = FR.dmon_partial_sums(d, F64, part_rows, flat=True)[1], FR.dmon_partial_sums(d, F32, part_rows, flat=True)[1]
+        assert tuple(part_f.shape) == tuple(f64.shape)
+        fails += forward_errors(f"{case}-flat", _per_graph("part", part_f), _per_graph("part", f64),
+                                _per_graph("part", f32), factor=factor_of("dmon"), report=report)
+    # dS (+)= coef_0 deg ca + coef_1 cs: the backward's elementwise pass, padded and (prefix draws) un-padded
+    ca, cs, coef = upstream(case + "ca", B, Kc), upstream(case + "cs", B, Kc), upstream(case + "coef", B, 2)
+    old = upstream(case + "old", B, N, Kc) if seed % 2 else None
+    out = mv(old).clone() if old is not None else torch.empty(B, N, Kc, device=dev())
+    K.dmon_ds(deg, mv(ca), mv(cs), mv(coef), B * N, N, None, out, old is not None)
+
+    def ds_ref(dtype):
+        r = FR.dmon_ds_reference(deg.cpu(), ca, cs, coef, dtype)
+        return r if old is None else r + old.to(dtype)
+    fails += forward_errors(f"{case}-ds", _per_graph("dS", out), _per_graph("dS", ds_ref(F64)), _per_graph("dS", ds_ref(F32)),
+                            factor=factor_of("dmon"), report=report)
+    if d["prefix"]:
+        rows = int(d["ptr"][-1])
+        out_f = torch.empty(rows, Kc, device=dev())
+        K.dmon_ds(deg_flat, mv(ca), mv(cs), mv(coef), rows, max(rows, 1), mv(d["batch"]), out_f, False)
+        pick = lambda t: torch.cat([t[b, :c] for b, c in enumerate(d["n_b"])])  # noqa: E731
+        fails += forward_errors(f"{case}-ds-flat", {"dS": out_f}, {"dS": pick(FR.dmon_ds_reference(deg.cpu(), ca, cs, coef, F64))},
+                                {"dS": pick(FR.dmon_ds_reference(deg.cpu(), ca, cs, coef, F32))},
+                                factor=factor_of("dmon"), report=report)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_dmon_public(seed):
+    from tgp.utils.losses import dmon_loss_terms
+    d = FI.draw("dmon", seed, limits())
+    case, report = f"dmon-public-{seed}", []
+    fin = FR.dmon_finite(d)
+    names = ("spectral", "cluster", "ortho")
+
+    def run(graphs):
+        s = mv(d["s"][graphs]).requires_grad_(True)
+        adj = mv(d["adj"][graphs])
+        raw = torch.matmul(torch.matmul(s.detach().transpose(1, 2), adj), s.detach()).requires_grad_(True)
+        terms = dmon_loss_terms(adj, s, raw, None if d["mask"] is None else mv(d["mask"][graphs]),
+                                None if d["graph_sizes"] is None else mv(d["graph_sizes"][graphs]))
+        assert tuple(terms.shape) == (3, len(graphs)) and "_DMoNTermsFnBackward" in _graph_names(terms.grad_fn)
+        return terms, s, raw
+    every = list(range(d["B"]))
+    terms, _, raw_all = run(every)  # values: the whole batch, the graph without a node in its place
+    raw_all = raw_all.detach().cpu()
+    got = {f"{n}[{b}]": terms[i, b] for i, n in enumerate(names) for b in fin}
+    with torch.no_grad():
+        fails = forward_errors(case, got, FR.dmon_reference(d, F64, raw_all)[0], FR.dmon_reference(d, F32, raw_all)[0],
+                               factor=factor_of("dmon"), report=report)
+    finish(case, fails, report)
+    if not fin:
+        return
+    wanted = set(FR.dmon_reference(d, F64, raw_all, grads=True)[0])
+
+    def kernel():  # gradients: the graphs with a real node (the others are 0 / 0 in every form)
+        t, s, raw = run(fin)
+        outs = {f"{n}[{b}]": t[i, j] for i, n in enumerate(names) for j, b in enumerate(fin)}
+        return {n: v for n, v in outs.items() if n in wanted}, {"s": s, "raw": raw}
+    check_grads(case, kernel, lambda dt: FR.dmon_reference(d, dt, raw_all, grads=True), ["s", "raw"])
+    if seed % 4 == 0:
+        runs = []
+        for _ in range(2):
+            t, s, raw = run(fin)
+            runs.append([t.detach()] + list(torch.autograd.grad(t.sum(), [s, raw])))
+        assert all(torch.equal(u, v) for u, v in zip(*runs)), case
+
+
+# =========================================================================================================== LaPool
+def _lapool_x(d):
+    x = mv(d["x"])
+    return offset_by_one_element(x) if d["layout"] == "edges_offset" else x
+
+
+def _lapool_lead(d, v):
+    """``K.lapool_leaders`` on the variations ``v`` (device) in the drawn layout."""
+    from tgp import kernels as K
+    if d["padded"]:
+        return K.lapool_leaders(v, mv(d["adj"]), mv(d["mask"]))
+    return K.lapool_leaders(v, edge_index=mv(d["edge_index"]), batch=mv(d["batch"]), ptr=mv(d["ptr"]))
+
+
+def _lapool_check_leaders(case, d, lead, v_host):
+    """Leader flags, columns and counts for the float32 variations as given: exact."""
+    flags = FR.lapool_leaders(d, v_host)
+    want = {"flags": flags.reshape(-1), **FR.lapool_columns(d, flags)}
+    real = d["real"].reshape(-1) if d["padded"] else torch.ones(flags.numel(), dtype=torch.bool)
+    got = {"flags": lead.flags.reshape(-1).cpu() & real, "col_of": torch.where(real, lead.col_of.cpu().long(), -1),
+           "k": lead.k.cpu()}
+    want["col_of"] = torch.where(real, want["col_of"], -1)
+    assert lead.k_max == int(want["k"].max()), case
+    return forward_errors(case, got, want, want, exact=set(want)), flags
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_lapool_operators(seed):
+    """``lapool_variation`` against float64; ``lapool_leaders`` (flags, columns, counts: exact) on the kernel's own
+    variations and on integer-valued ones full of ties; ``lapool_assign`` and its native backward for those leaders."""
+    from tgp import kernels as K
+    d = FI.draw("lapool", seed, limits())
+    case, report = f"lapool-op-{seed}", []
+    x = _lapool_x(d)
+    B = len(d["n_b"])
+    if d["padded"]:
+        v = K.lapool_variation(x, mv(d["adj"]), mv(d["mask"]))
+    else:
+        ei = mv(d["edge_index"])
+        by_src = K.lapool_edge_group(ei, d["n"])
+        ascending = bool((d["edge_index"][0, 1:] >= d["edge_index"][0, :-1]).all())
+        assert (by_src.perm is None) == (ascending and ei.size(1) > 0), case  # sorted sources: the CSR offsets alone
+        v = K.lapool_variation(x, edge_index=ei, edge_weight=mv(d["edge_weight"]), by_src=by_src)
+    rows = lambda t, b: FR.lapool_graph_rows(d, t, b)  # noqa: E731
+    every = range(B)
+    fails = forward_errors(case, {f"v[{b}]": rows(v, b) for b in every},
+                           {f"v[{b}]": rows(FR.lapool_variation(d, F64), b) for b in every},
+                           {f"v[{b}]": rows(FR.lapool_variation(d, F32), b) for b in every},
+                           zeros={f"v[{b}]": ~d["real"][b] for b in every} if d["padded"] else None,
+                           factor=factor_of("lapool"), report=report)
+    more, _ = _lapool_check_leaders(f"{case}-tied", d, _lapool_lead(d, mv(d["v_tied"])), d["v_tied"])
+    fails += more
+    lead = _lapool_lead(d, v)
+    more, flags = _lapool_check_leaders(f"{case}-own", d, lead, v.cpu())
+    fails += more
+    s, nrm = K.lapool_assign(x, lead)
+    r64, r32 = FR.lapool_reference(d, F64, flags)[0], FR.lapool_reference(d, F32, flags)[0]
+    kmax = lead.k_max
+    ks = FR.lapool_columns(d, flags)["k"]
+    zeros = {}
+    for b in every:  # padded rows and the columns from k_b on: exact zeros
+        z = torch.zeros(rows(s, b).shape, dtype=torch.bool)
+        z[:, int(ks[b]):] = True
+        if d["padded"]:
+            z[~d["real"][b]] = True
+        zeros[f"S[{b}]"] = z
+    with torch.no_grad():
+        fails += forward_errors(f"{case}-assign", {f"S[{b}]": rows(s, b) for b in every}, r64, r32, zeros=zeros,
+                                factor=factor_of("lapool"), report=report)
+    nrm64 = d["x"].double().norm(dim=-1).reshape(-1)
+    real = d["real"].reshape(-1) if d["padded"] else torch.ones(nrm64.numel(), dtype=torch.bool)
+    fails += forward_errors(f"{case}-assign", {"nrm": nrm.cpu()[real]}, {"nrm": nrm64[real]},
+                            {"nrm": d["x"].norm(dim=-1).reshape(-1)[real]}, factor=factor_of("lapool"), report=report)
+    if kmax > 0:  # the native backward operator on one upstream gradient
+        ds = upstream(case, *s.shape)
+        dx = K.lapool_assign_bwd(x, nrm, s, mv(ds), lead)
+
+        def ref_dx(dtype):
+            outs, lv = FR.lapool_reference(d, dtype, flags)
+            total = sum((outs[f"S[{b}]"] * rows(ds, b).to(dtype)).sum() for b in every)
+            (gx,) = torch.autograd.grad(total, lv["x"])
+            return {f"dx[{b}]": rows(gx, b) for b in every}
+        zx = {f"dx[{b}]": (~d["real"][b]).unsqueeze(-1).expand(-1, d["F"]) for b in every} if d["padded"] else None
+        fails += forward_errors(f"{case}-bwd", {f"dx[{b}]": rows(dx, b) for b in every}, ref_dx(F64), ref_dx(F32),
+                                zeros=zx, factor=factor_of("lapool"), report=report)
+        if seed % 4 == 0:
+            s2, nrm2 = K.lapool_assign(x, lead)
+            assert torch.equal(s, s2) and torch.equal(nrm, nrm2)
+            assert torch.equal(K.lapool_assign_bwd(x, nrm, s, mv(ds), lead), dx), case
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_lapool_public(seed):
+    """``functions.lapool_assign`` (one autograd node, the native backward) per graph, gradients to x one graph at a
+    time, for the leaders of the integer-valued variations (fixed, exact: no float decides the leader set)."""
+    from tgp import functions as Fn
+    d = FI.draw("lapool", seed, limits())
+    case, report = f"lapool-public-{seed}", []
+    lead = _lapool_lead(d, mv(d["v_tied"]))
+    flags = FR.lapool_leaders(d, d["v_tied"])
+    assert torch.equal(lead.k.cpu().long(), FR.lapool_columns(d, flags)["k"]), case
+    B = len(d["n_b"])
+
+    def kernel():
+        x = _lapool_x(d).detach().requires_grad_(True)
+        s = Fn.lapool_assign(x, lead)
+        assert "_LaPoolAssignFnBackward" in _graph_names(s.grad_fn)
+        return {f"S[{b}]": FR.lapool_graph_rows(d, s, b) for b in range(B)}, {"x": x}
+    outs, _ = kernel()
+    with torch.no_grad():
+        fails = forward_errors(case, outs, FR.lapool_reference(d, F64, flags)[0], FR.lapool_reference(d, F32, flags)[0],
+                               factor=factor_of("lapool"), report=report)
+    finish(case, fails, report)
+    if lead.k_max > 0:
+        check_grads(case, kernel, lambda dt: FR.lapool_reference(d, dt, flags), ["x"])
+
+
+# =================================================================================================== AsymCheegerCut
+def _acc_quantile_checks(case, d, got, want, graphs, small, route, fails, report, colsum_of):
+    """One ``acc_quantile`` result against the exact selection (value, LOWEST row that holds it, rows >= it, real rows)
+    on the graphs with a real node, its route, and the asymmetric-norm column sums."""
+    q, qnode, colsum, cge, nreal, taken = got
+    assert taken == ("count" if route == "count" or (route == "auto" and small) else "radix"), (case, route, taken)
+    have = {"q": q.cpu()[graphs], "qnode": qnode.cpu()[graphs], "cge": cge.cpu()[graphs], "nreal": nreal.cpu()}
+    ref = {n: (v if n == "nreal" else v[graphs]) for n, v in want.items()}
+    fails += forward_errors(f"{case}-{route}", have, ref, ref, exact=set(ref))
+    fails += forward_errors(f"{case}-{route}", {"colsum": colsum.cpu()[graphs]}, {"colsum": colsum_of(F64)[graphs]},
+                            {"colsum": colsum_of(F32)[graphs]}, factor=factor_of("acc"), report=report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_acc_operators(seed):
+    """The total variation (dense blocks of 16 rows; per node over the listed edges), the quantile select on both routes
+    where the size permits, the tail, and the three native backward operators on one upstream gradient each -- padded
+    and, where the real rows are a prefix, un-padded with its hub."""
+    from tgp import kernels as K
+    lim = limits()
+    d = FI.draw("acc", seed, lim)
+    case, report = f"acc-op-{seed}", []
+    s, adj, mask, sizes = mv(d["s"]), mv(d["adj"]), mv(d["mask"]), mv(d["graph_sizes"])
+    B, N, Kc = d["s"].shape
+    k, fin = d["loss_k"], FR.dmon_finite(d)
+    every = list(range(B))
+    # ---- padded: forward
+    part, cnt = K.acc_tv_dense(adj, s, sizes)
+    (p64, c64), (p32, _) = FR.acc_tv_blocks(d, F64, lim["acc_tv_rows"]), FR.acc_tv_blocks(d, F32, lim["acc_tv_rows"])
+    assert tuple(part.shape) == tuple(p64.shape) and torch.equal(cnt.cpu().long(), c64), case
+    fails = forward_errors(f"{case}-tv", _per_graph("part", part), _per_graph("part", p64), _per_graph("part", p32),
+                           factor=factor_of("acc"), report=report)
+    small = N <= lim["acc_small_graph_nodes"]
+    assert small == (N <= K.acc_small_graph_nodes())
+    want = FR.acc_quantile_exact(d)
+    colsum_of = lambda dt: FR.acc_colsum(d, dt, want["q"])  # noqa: E731
+    sel = None  # (k <= 1: no balance term -- the select and its backward are not run, as the loss Function has it)
+    for route in (["auto"] + (["count", "radix"] if small else [])) if k > 1 else []:  # (auto beyond the limit: radix)
+        got = K.acc_quantile(s, k, mask=mask, graph_sizes=sizes, route=route)
+        _acc_quantile_checks(case, d, got, want, fin, small, route, fails, report, colsum_of)
+        sel = got if sel is None else sel
+    q, qnode, colsum, cge, nreal, _ = sel if sel is not None else (None,) * 6
+    out, ecnt = K.acc_tail(B, Kc, k, dev(), ("dense", part, cnt), colsum, nreal)
+    assert torch.equal(ecnt.cpu().long().clamp(min=1), c64.sum(1).clamp(min=1)), case
+    r64, r32 = FR.acc_reference(d, F64)[0], FR.acc_reference(d, F32)[0]
+    with torch.no_grad():
+        fails += forward_errors(f"{case}-tail", {**_per_graph("tv", out[0]), **_per_graph("balance", out[1])}, r64, r32,
+                                factor=factor_of("acc"), report=report)
+    # ---- padded: the native backward operators
+    g = upstream(case, 2, B)
+    old = upstream(case + "old", B, N, Kc) if seed % 2 else None
+    d_tv = K.acc_tv_dense_bwd(adj, s, sizes, mv(g[0]), ecnt, 1.0)
+    d_bal = mv(old).clone() if old is not None else torch.zeros(B, N, Kc, device=dev())
+    if k > 1:
+        K.acc_asym_bwd(s, k, q, qnode, cge, nreal, mv(g[1]), 1.0, d_bal, old is not None, mask=mask, graph_sizes=sizes)
+
+    def ref_grads(dtype, reference=FR.acc_reference, rows=lambda t, b: t[b], graphs=every, prior=old):
+        outs, lv = reference(d, dtype)
+        res = {}
+        for i, name in enumerate(("tv", "balance")):
+            total = sum(g[i, b].to(dtype) * outs[f"{name}[{b}]"] for b in graphs)
+            gs = torch.autograd.grad(total, lv["s"], allow_unused=True)[0] if total.requires_grad else None
+            gs = torch.zeros_like(lv["s"]) if gs is None else gs
+            if name == "balance" and prior is not None:
+                gs = gs + prior.to(dtype)
+            res.update({f"d_{name}[{b}]": rows(gs, b) for b in graphs})
+        return res
+    got = {**_per_graph("d_tv", d_tv), **_per_graph("d_balance", d_bal)}
+    zeros = None if old is not None else {f"d_balance[{b}]": (~d["real"][b]).unsqueeze(-1).expand(-1, Kc) for b in every}
+    fails += forward_errors(f"{case}-bwd", got, ref_grads(F64), ref_grads(F32), zeros=zeros, factor=factor_of("acc"),
+                            report=report)
+    if seed % 4 == 0:
+        assert all(torch.equal(u, v) for u, v in zip(K.acc_tv_dense(adj, s, sizes), (part, cnt)))
+        if k > 1:
+            assert all(torch.equal(u, v) for u, v in zip(K.acc_quantile(s, k, mask=mask, graph_sizes=sizes)[:5], sel[:5]))
+        assert torch.equal(K.acc_tv_dense_bwd(adj, s, sizes, mv(g[0]), ecnt, 1.0), d_tv)
+    # ---- un-padded: the same batch as rows with ptr and an edge list (duplicates, the hub)
+    if d["prefix"]:
+        sf, ei, w = mv(d["s_flat"]), mv(d["edge_index"]), mv(d["edge_weight"])
+        ptr, batch, n = mv(d["ptr"]), mv(d["batch"]), d["n"]
+        by_src, by_dst = K.edge_group(ei, n), K.edge_group(ei, n, by_destination=True)
+        node_tv = K.acc_tv_edge(sf, ei, w, by_src)
+        fails += forward_errors(f"{case}-edge-tv", {"node_tv": node_tv}, {"node_tv": FR.acc_node_tv(d, F64)},
+                                {"node_tv": FR.acc_node_tv(d, F32)}, factor=factor_of("acc"), report=report)
+        longest = max(d["n_b"])
+        fsmall = longest <= lim["acc_small_graph_nodes"]
+        fsel = None
+        for route in (["auto"] + (["count", "radix"] if fsmall else [])) if k > 1 else []:
+            got = K.acc_quantile(sf, k, ptr=ptr, max_nodes=longest, route=route)
+            _acc_quantile_checks(f"{case}-flat", d, got, want, fin, fsmall, route, fails, report, colsum_of)
+            fsel = got if fsel is None else fsel
+        fsel = fsel if fsel is not None else (None,) * 6
+        fout, fecnt = K.acc_tail(B, Kc, k, dev(), ("edge", node_tv, by_src, ptr), fsel[2], fsel[4])
+        edges = torch.bincount(d["batch"][d["edge_index"][0]], minlength=B)
+        assert torch.equal(fecnt.cpu().long().clamp(min=1), edges.clamp(min=1)), case
+        f64, f32 = FR.acc_flat_reference(d, F64)[0], FR.acc_flat_reference(d, F32)[0]
+        with torch.no_grad():
+            fails += forward_errors(f"{case}-flat-tail", {**_per_graph("tv", fout[0]), **_per_graph("balance", fout[1])},
+                                    f64, f32, factor=factor_of("acc"), report=report)
+        e_tv = K.acc_tv_edge_bwd(sf, ei, w, by_src, by_dst, batch, mv(g[0]), fecnt, 1.0)
+        e_bal = torch.zeros(n, Kc, device=dev())
+        if k > 1:
+            K.acc_asym_bwd(sf, k, fsel[0], fsel[1], fsel[3], fsel[4], mv(g[1]), 1.0, e_bal, False, ptr=ptr, batch=batch)
+        seg = lambda t, b: t[int(d["ptr"][b]):int(d["ptr"][b + 1])]  # noqa: E731
+        got = {f"d_tv[{b}]": seg(e_tv, b) for b in every}
+        got.update({f"d_balance[{b}]": seg(e_bal, b) for b in every})
+        flat = dict(reference=FR.acc_flat_reference, rows=seg, prior=None)
+        # (a hub's edges cross the rows of its graph only: every graph's rows still depend on its own term alone)
+        fails += forward_errors(f"{case}-flat-bwd", got, ref_grads(F64, **flat), ref_grads(F32, **flat),
+                                factor=factor_of("acc"), report=report)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_acc_public(seed):
+    from tgp.utils.losses import acc_loss_terms, acc_sparse_loss_terms
+    d = FI.draw("acc", seed, limits())
+    case, report = f"acc-public-{seed}", []
+    B, k = d["B"], d["loss_k"]
+    adj, mask, sizes = mv(d["adj"]), mv(d["mask"]), mv(d["graph_sizes"])
+
+    def kernel():
+        s = mv(d["s"]).requires_grad_(True)
+        terms = acc_loss_terms(adj, s, k, mask, sizes)
+        assert tuple(terms.shape) == (2, B) and "_ACCTermsFnBackward" in _graph_names(terms.grad_fn)
+        return {**_per_graph("tv", terms[0]), **_per_graph("balance", terms[1])}, {"s": s}
+    outs, _ = kernel()
+    with torch.no_grad():
+        fails = forward_errors(case, outs, FR.acc_reference(d, F64)[0], FR.acc_reference(d, F32)[0],
+                               factor=factor_of("acc"), report=report)
+    runs = [(kernel, lambda dt: FR.acc_reference(d, dt), case)]
+    if d["prefix"]:  # the un-padded public form of the same batch (graphs up to the last one with a node)
+        ei, w, batch = mv(d["edge_index"]), mv(d["edge_weight"]), mv(d["batch"])
+        nb = int(d["batch"].max()) + 1
+
+        def trimmed(dt):
+            o, lv = FR.acc_flat_reference(d, dt)
+            return {n: v for n, v in o.items() if int(n[n.index("[") + 1:-1]) < nb}, lv
+
+        def kernel_flat():
+            s = mv(d["s_flat"]).requires_grad_(True)
+            terms = acc_sparse_loss_terms(ei, w, s, k, batch)
+            assert terms is not None and tuple(terms.shape) == (2, nb)
+            assert "_ACCTermsFnBackward" in _graph_names(terms.grad_fn)
+            return {**_per_graph("tv", terms[0]), **_per_graph("balance", terms[1])}, {"s": s}
+        flat_outs = kernel_flat()[0]
+        with torch.no_grad():
+            fails += forward_errors(f"{case}-flat", flat_outs, trimmed(F64)[0], trimmed(F32)[0],
+                                    factor=factor_of("acc"), report=report)
+        runs.append((kernel_flat, trimmed, f"{case}-flat"))
+    finish(case, fails, report)
+    for run, oracle, name in runs:
+        check_grads(name, run, oracle, ["s"])
+        if seed % 4 == 0:
+            twice = []
+            for _ in range(2):
+                o, lv = run()
+                twice.append([torch.stack(list(o.values())).detach(), torch.autograd.grad(sum(o.values()), lv["s"])[0]])
+            assert all(torch.equal(u, v) for u, v in zip(*twice)), name
+
+
+# ============================================================================================================= HOSC
+@pytest.mark.parametrize("seed", SEEDS)
+def test_hosc_operators(seed):
+    """The motif chain without A A A: three ``hosc_matvec`` passes and three products (general route) and, where the
+    batch fits it, the one-launch ``hosc_small``: d1 = A 1, d3 = A A A 1, z = A A A S against the explicit cube."""
+    from tgp import kernels as K
+    lim = limits()
+    d = FI.draw("hosc", seed, lim)
+    case, report = f"hosc-op-{seed}", []
+    s, adj, mask, sizes = mv(d["s"]), mv(d["adj"]), mv(d["mask"]), mv(d["graph_sizes"])
+    B, N, Kc = d["s"].shape
+    small = K.hosc_is_small(N, Kc)
+    assert small == (N <= lim["hosc_small_graph_nodes"] and Kc <= lim["hosc_small_graph_nodes"]), case
+    names = ("d1", "d3", "z")
+    r64 = {f"{n}[{b}]": t[b] for n, t in zip(names, FR.hosc_chain(d, F64)) for b in range(B)}
+    r32 = {f"{n}[{b}]": t[b] for n, t in zip(names, FR.hosc_chain(d, F32)) for b in range(B)}
+    zeros = {f"{n}[{b}]": (~d["real"][b]).unsqueeze(-1).expand(-1, Kc) if n == "z" else ~d["real"][b]
+             for n in names for b in range(B)}
+    d1 = K.hosc_matvec(adj, None, sizes)
+    d3 = K.hosc_matvec(adj, K.hosc_matvec(adj, d1, sizes), sizes)
+    z = K.bmm(adj, K.bmm(adj, K.bmm(adj, s)))
+    got = {f"{n}[{b}]": t[b] for n, t in zip(names, (d1, d3, z)) for b in range(B)}
+    fails = forward_errors(f"{case}-chain", got, r64, r32, zeros=zeros, factor=factor_of("hosc"), report=report)
+    if small:
+        zs, d1s, d3s, part = K.hosc_small(adj, s, mask, sizes)
+        assert tuple(part.shape) == (B, 1, int(K.N.lib().tgp_hosc_record_floats(Kc)))
+        got = {f"{n}[{b}]": t[b] for n, t in zip(names, (d1s, d3s, zs)) for b in range(B)}
+        fails += forward_errors(f"{case}-small", got, r64, r32, zeros=zeros, factor=factor_of("hosc"), report=report)
+        if seed % 4 == 0:
+            again = K.hosc_small(adj, s, mask, sizes)
+            assert all(torch.equal(u, v) for u, v in zip((zs, d1s, d3s, part), again)), case
+        # the one-launch record (its num1 = sum S (.) A S comes from the first round) and hosc_node_terms on the general
+        # route's operands, with and without that first product: the same records
+        z1 = K.bmm(adj, s)
+
+        def chain_record(dt, with_z1):
+            c1, c3, cz = FR.hosc_chain(d, dt)
+            cz1 = d["adj"].to(dt) @ d["s"].to(dt) if with_z1 else torch.zeros_like(cz)
+            return FR.hosc_records(d, dt, cz, cz1, c3, c1, lim["part_rows"])
+        for name, have, with_z1 in (("small", part, True), ("general", K.hosc_node_terms(s, z, None, d3, d1, mask, sizes), False),
+                                    ("general-z1", K.hosc_node_terms(s, z, z1, d3, d1, mask, sizes), True)):
+            fails += forward_errors(f"{case}-record-{name}", _per_graph("part", have),
+                                    _per_graph("part", chain_record(F64, with_z1)),
+                                    _per_graph("part", chain_record(F32, with_z1)), factor=factor_of("hosc"), report=report)
+    # hosc_node_terms and the backward's elementwise hosc_ds on operands of their own, every term switched on
+    zr, z1r, ztr, z1tr = (upstream(case + n, B, N, Kc) for n in ("z", "z1", "zt", "z1t"))
+    d3r, d1r = upstream(case + "d3", B, N).abs(), upstream(case + "d1", B, N).abs()
+    part_r = K.hosc_node_terms(s, mv(zr), mv(z1r), mv(d3r), mv(d1r), mask, sizes)
+    assert tuple(part_r.shape) == (B, max(1, -(-N // lim["part_rows"])), int(K.N.lib().tgp_hosc_record_floats(Kc)))
+    rec = lambda dt: FR.hosc_records(d, dt, zr, z1r, d3r, d1r, lim["part_rows"])  # noqa: E731
+    fails += forward_errors(f"{case}-node-terms", _per_graph("part", part_r), _per_graph("part", rec(F64)),
+                            _per_graph("part", rec(F32)), factor=factor_of("hosc"), report=report)
+    cn, coef = upstream(case + "cn", B, Kc).abs() + 0.5, upstream(case + "coef", B, 5)
+    old = upstream(case + "old", B, N, Kc) if seed % 2 else None
+    out = mv(old).clone() if old is not None else torch.empty(B, N, Kc, device=dev())
+    K.hosc_ds(s, mv(zr), mv(ztr), mv(z1r), mv(z1tr), mv(d3r), mv(d1r), mv(cn), mv(coef), N, None, out, old is not None)
+
+    def ds_ref(dt):
+        r = FR.hosc_ds_reference(d, dt, zr, ztr, z1r, z1tr, d3r, d1r, cn, coef)
+        return r if old is None else r + old.to(dt)
+    fails += forward_errors(f"{case}-ds", _per_graph("dS", out), _per_graph("dS", ds_ref(F64)), _per_graph("dS", ds_ref(F32)),
+                            factor=factor_of("hosc"), report=report)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_hosc_public(seed):
+    from tgp import kernels as K
+    from tgp.utils.losses import hosc_loss_terms
+    lim = limits()
+    d = FI.draw("hosc", seed, lim)
+    case, report = f"hosc-public-{seed}", []
+    fin = FR.dmon_finite(d)
+    small = d["N"] <= lim["hosc_small_graph_nodes"] and d["K"] <= lim["hosc_small_graph_nodes"]
+    assert K.hosc_is_small(d["N"], d["K"]) == small, case  # the route the draw was made to reach
+    use_raw = d["with_raw"] and d["alpha"] < 1
+
+    def run(graphs):
+        s = mv(d["s"][graphs]).requires_grad_(True)
+        adj = mv(d["adj"][graphs])
+        raw = None
+        if d["with_raw"]:
+            raw = torch.matmul(torch.matmul(s.detach().transpose(1, 2), adj), s.detach()).requires_grad_(True)
+        terms = hosc_loss_terms(adj, s, raw, None if d["mask"] is None else mv(d["mask"][graphs]),
+                                None if d["graph_sizes"] is None else mv(d["graph_sizes"][graphs]),
+                                alpha=d["alpha"], mu=d["mu"], hosc_ortho=d["hosc_ortho"])
+        assert tuple(terms.shape) == (2, len(graphs)) and "_HOSCTermsFnBackward" in _graph_names(terms.grad_fn)
+        return terms, s, raw
+    terms, _, raw_all = run(list(range(d["B"])))  # values: the whole batch, the graph without a node in its place
+    raw_all = raw_all.detach().cpu() if use_raw else None
+    got = {f"{n}[{b}]": terms[i, b] for i, n in enumerate(("hosc", "ortho")) for b in fin}
+    with torch.no_grad():
+        fails = forward_errors(case, got, FR.hosc_reference(d, F64, raw_all)[0], FR.hosc_reference(d, F32, raw_all)[0],
+                               factor=factor_of("hosc"), report=report)
+    finish(case, fails, report)
+    if not fin:
+        return
+    wanted = set(FR.hosc_reference(d, F64, raw_all, grads=True)[0])
+
+    def kernel():  # gradients: the graphs with a real node (the others are 0 / 0 in every form)
+        t, s, raw = run(fin)
+        outs = {f"{n}[{b}]": t[i, j] for i, n in enumerate(("hosc", "ortho")) for j, b in enumerate(fin)}
+        return {n: v for n, v in outs.items() if n in wanted}, {"s": s, "raw": raw if use_raw else None}
+    check_grads(case, kernel, lambda dt: FR.hosc_reference(d, dt, raw_all, grads=True), ["s", "raw"])
+    if seed % 4 == 0:
+        runs = []
+        for _ in range(2):
+            t, s, _ = run(fin)
+            runs.append([t.detach(), torch.autograd.grad(t.sum(), s)[0]])
+        assert all(torch.equal(u, v) for u, v in zip(*runs)), case
+
+
+# ========================================================================================================== BN-Pool
+def _bnpool_rows(d, t):
+    """Per graph with a real node: the rows of a [B,N,K] tensor; the rows outside the mask must be exact zeros."""
+    return {b: t[b] for b in FR.bnpool_finite(d)}
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_bnpool_operators(seed):
+    from tgp import kernels as K
+    d = FI.draw("bnpool", seed, limits())
+    case, report = f"bnpool-op-{seed}", []
+    assert d["K"] <= K.bnpool_max_clusters()
+    s, adj, mask = mv(d["s"]), mv(d["adj"]), mv(d["mask"])
+    t = torch.matmul(s, mv(d["k_mat"]))
+    rec, stats = K.bnpool_rec_fwd(t, s, adj, mask)
+    assert rec.dtype == F32 and tuple(rec.shape) == (d["B"],) and tuple(stats.shape) == (d["B"], 2)
+    fin = FR.bnpool_finite(d)
+
+    def reference(dtype):  # (T as the device formed it: the operators are judged on their own inputs)
+        return FR.bnpool_operator_reference(d, dtype, t=t.cpu())
+    r64, r32 = reference(F64)[0], reference(F32)[0]
+    fails = forward_errors(case, {f"rec[{b}]": rec[b] for b in fin}, r64, r32, factor=factor_of("bnpool"), report=report)
+    n2 = torch.tensor([float(n * n) for n in d["n_b"]])
+    assert torch.equal(stats[:, 1].cpu(), n2), case
+    g = upstream(case, d["B"])
+    g[[b for b in range(d["B"]) if b not in fin]] = 0
+    p, q = K.bnpool_rec_bwd(t, s, adj, mask, mv(g), stats)
+
+    def ref_grads(dtype):
+        outs, lv = reference(dtype)
+        if not outs:
+            return {}
+        total = sum(g[b].to(dtype) * outs[f"rec[{b}]"] for b in fin)
+        gt, gs = torch.autograd.grad(total, [lv["t"], lv["s"]])
+        out = {f"P[{b}]": gt[i] for i, b in enumerate(fin)}
+        out.update({f"Q[{b}]": gs[i] for i, b in enumerate(fin)})
+        return out
+    got = {f"P[{b}]": p[b] for b in fin}
+    got.update({f"Q[{b}]": q[b] for b in fin})
+    outside = ~FR.bnpool_row_mask(d)
+    zeros = {f"{w}[{b}]": outside[b].expand(-1, d["K"]) for w in "PQ" for b in fin}
+    fails += forward_errors(case, got, ref_grads(F64), ref_grads(F32), zeros=zeros, factor=factor_of("bnpool"),
+                            report=report)
+    if seed % 4 == 0:
+        rec2, stats2 = K.bnpool_rec_fwd(t, s, adj, mask)
+        p2, q2 = K.bnpool_rec_bwd(t, s, adj, mask, mv(g), stats2)
+        assert torch.equal(rec[fin], rec2[fin]) and torch.equal(stats, stats2)
+        assert all(torch.equal(p[b], p2[b]) and torch.equal(q[b], q2[b]) for b in fin)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_bnpool_public(seed):
+    from tgp.utils.losses import bnpool_rec_loss_terms
+    d = FI.draw("bnpool", seed, limits())
+    case, report = f"bnpool-public-{seed}", []
+    fin = FR.bnpool_finite(d)
+    adj, mask = mv(d["adj"]), mv(d["mask"])
+
+    def kernel(graphs=fin):
+        """The public call on ``graphs`` (gradients: those with a real node; a graph without one is 0 / 0 in every
+        form and would put NaN into the shared cluster matrix's gradient)."""
+        s, k_mat = mv(d["s"][graphs]).requires_grad_(True), mv(d["k_mat"]).requires_grad_(True)
+        rec = bnpool_rec_loss_terms(s, k_mat, adj[graphs], None if mask is None else mask[graphs])
+        assert "_BNPoolRecFnBackward" in _graph_names(rec.grad_fn)  # the native route, never the composed form
+        return {f"rec[{b}]": rec[i] for i, b in enumerate(graphs) if b in fin}, {"s": s, "k_mat": k_mat}
+    outs, _ = kernel(list(range(d["B"])))  # values: the whole batch, the graph without a node in its place
+    with torch.no_grad():
+        fails = forward_errors(case, outs, FR.bnpool_reference(d, F64)[0], FR.bnpool_reference(d, F32)[0],
+                               factor=factor_of("bnpool"), report=report)
+    finish(case, fails, report)
+    if fin:
+        check_grads(case, kernel, lambda dt: FR.bnpool_reference(d, dt), ["s", "k_mat"])
+    if seed % 4 == 0 and fin:  # the same public call twice: equal bits, forward and backward
+        twice = []
+        for _ in range(2):
+            o, lv = kernel()
+            twice.append([torch.stack(list(o.values())).detach()]
+                         + list(torch.autograd.grad(sum(o.values()), [lv["s"], lv["k_mat"]])))
+        assert all(torch.equal(u, v) for u, v in zip(*twice)), case
+
+
+# ========================================================================================================== readout
+def _readout_call(d, x, want_aux=True):
+    """K.segment_aggr on the drawn row source: (out, ties, count, what the backward operator needs or None)."""
+    from tgp import kernels as K
+    ops_mask = K.segment_ops_mask(d["ops"])
+    lay, g = d["layout"], d["groups"]
+    if lay.startswith("ptr"):
+        out = K.segment_aggr(x, ops_mask, g, d["max_len"], ptr=mv(d["ptr"]), want_aux=want_aux)
+        return out, dict(batch=mv(d["batch"]))
+    if lay.startswith("dense"):
+        m = None if d["mask"] is None else mv(d["mask"]).reshape(-1).contiguous().view(torch.uint8)
+        out = K.segment_aggr(x.reshape(-1, d["F"]), ops_mask, g, d["max_len"], dense_nodes=d["N"], mask=m,
+                             want_aux=want_aux)
+        return out, dict(dense_nodes=d["N"], mask=m)
+    index = K.build_assign_index(mv(d["cluster_index"]), g)
+    assert index.max_members == d["max_len"]
+    out = K.segment_aggr(x, ops_mask, g, index.max_members, index=index, node_index=mv(d["node_index"]),
+                         weight=mv(d["weight"]), want_aux=want_aux)
+    return out, None
+
+
+def _readout_x(d):
+    if d["layout"] == "ptr_sliced":
+        x = mv(d["x_base"])[:, d["first"]:d["first"] + d["F"]]
+        assert x.stride(0) == d["F"] + 7
+        return x
+    x = mv(d["x"])
+    if d["layout"].startswith("dense") and d["mask"] is not None:  # a masked row is never read
+        x = torch.where(mv(d["mask"]).unsqueeze(-1), x, torch.full_like(x, float("nan")))
+    return x
+
+
+def _blocks(d, t, ops=None):
+    ops = d["ops"] if ops is None else ops
+    f = t.size(1) // len(ops)
+    return {op: t[:, i * f:(i + 1) * f] for i, op in enumerate(ops)}
+
+
+def _readout_exact_names(d):
+    """max / min are selections among float32 values; integer-valued rows make every sum (and the one division of the
+    mean) exact in float32: compared with ``torch.equal`` against the float32 restatement."""
+    return set(d["ops"]) if d["integer"] else {op for op in d["ops"] if op in ("min", "max")}
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_readout_operators(seed):
+    from tgp import kernels as K
+    lim = limits()
+    d = FI.draw("readout", seed, lim)
+    case, report = f"readout-op-{seed}", []
+    x = _readout_x(d)
+    ops_mask = K.segment_ops_mask(d["ops"])
+    # the route: a segment longer than one chunk sends the batch to the split route, which alone needs a workspace
+    split = d["max_len"] > K.segment_aggr_chunk_rows()
+    wsb = K.N.lib().tgp_segment_aggr_workspace_bytes(d["groups"], d["F"], ops_mask, d["max_len"])
+    assert (wsb > 0) == split and split == (d["max_len"] > lim["segment_chunk_rows"]), (case, wsb, d["max_len"])
+    (out, ties, count), bwd = _readout_call(d, x)
+    r64, r32 = FR.readout_reference(d, F64)[0], FR.readout_reference(d, F32)[0]
+    with torch.no_grad():
+        fails = forward_errors(case, _blocks(d, out), r64, r32, exact=_readout_exact_names(d), exact_ref=r32,
+                               factor=factor_of("readout"), report=report)
+    want = FR.readout_exact(d)
+    assert torch.equal(count.cpu().long(), want["count"]), case
+    some = want["count"] > 0  # (the tie count of a group without rows is never read)
+    mm = [op for op in d["ops"] if op in ("min", "max")]
+    for op, blk in (_blocks(d, ties, mm).items() if mm else ()):
+        assert torch.equal(blk.cpu().long()[some], want[f"ties_{op}"][some]), (case, op)
+    assert bool((out[~mv(some)] == 0).all()), case  # groups without rows give 0 for every operation
+    out_plain = _readout_call(d, x, want_aux=False)[0][0]
+    assert torch.equal(out_plain, out)
+    if bwd is not None:  # the native backward operator (contiguous and dense sources) on one upstream gradient
+        g = upstream(case, *out.shape)
+        x2 = x.reshape(-1, d["F"])
+        dx = K.segment_aggr_bwd(mv(g), x2, out, ties, count, ops_mask, d["groups"], **bwd)
+
+        def ref_grad(dtype):
+            outs, lv = FR.readout_reference(d, dtype)
+            y = torch.cat([outs[op] for op in d["ops"]], -1)
+            return {"dx": torch.autograd.grad(y, lv["x"], g.to(dtype))[0].reshape(-1, d["F"])}
+        zeros = None
+        if d["layout"].startswith("dense") and d["mask"] is not None:
+            zeros = {"dx": ~d["mask"].reshape(-1, 1).expand(-1, d["F"])}
+        fails += forward_errors(case, {"dx": dx}, ref_grad(F64), ref_grad(F32), zeros=zeros,
+                                factor=factor_of("readout"), report=report)
+        if seed % 4 == 0:
+            assert torch.equal(dx, K.segment_aggr_bwd(mv(g), x2, out, ties, count, ops_mask, d["groups"], **bwd))
+    if seed % 4 == 0:
+        again = _readout_call(d, x)[0]
+        assert torch.equal(out, again[0]) and torch.equal(count, again[2])
+        assert ties is None or torch.equal(ties, again[1])
+        # the same groups through all three row sources (contiguous, dense with a mask, gathered): each within the bound
+        for name, got in _readout_three_sources(d).items():
+            with torch.no_grad():
+                fails += forward_errors(f"{case}-as-{name}", _blocks(d, got), r64, r32, exact=_readout_exact_names(d),
+                                        exact_ref=r32, factor=factor_of("readout"), report=report)
+    finish(case, fails, report)
+
+
+def _readout_three_sources(d):
+    """The draw's groups (its float32 rows, weighted where it has weights) handed to ``K.segment_aggr`` as contiguous
+    segments, as a padded batch with a prefix mask and as a gathered assignment: {source: out}."""
+    from tgp import kernels as K
+    rows = FR.readout_rows(d, d["x"], d.get("weight"))
+    index, g, f = d["index"], d["groups"], d["F"]
+    ops_mask = K.segment_ops_mask(d["ops"])
+    order = torch.argsort(index, stable=True)
+    counts = torch.bincount(index, minlength=g)
+    ptr = torch.zeros(g + 1, dtype=torch.long)
+    ptr[1:] = counts.cumsum(0)
+    longest = int(counts.max())
+    out = {"ptr": K.segment_aggr(mv(rows[order].contiguous()), ops_mask, g, longest, ptr=mv(ptr))[0]}
+    width = max(longest, 1)
+    padded = torch.full((g, width, f), float("nan"))  # (a masked row is never read)
+    mask = torch.arange(width).view(1, -1) < counts.view(-1, 1)
+    padded[mask] = rows[order]
+    out["dense"] = K.segment_aggr(mv(padded.reshape(-1, f)), ops_mask, g, width, dense_nodes=width,
+                                  mask=mv(mask).reshape(-1).contiguous().view(torch.uint8))[0]
+    assign = K.build_assign_index(mv(index), g)
+    out["gather"] = K.segment_aggr(mv(rows.contiguous()), ops_mask, g, assign.max_members, index=assign,
+                                   node_index=mv(torch.arange(rows.size(0))))[0]
+    return out
+
+
+def _readout_public(d, x, weight=None):
+    from tgp.reduce import AggrReduce, GlobalReduce, get_aggr
+    from tgp.select import SelectOutput
+    ops = list(d["ops"])
+    op, kw = ("multi", {"aggrs": ops}) if len(ops) > 1 else (ops[0], {})
+    lay = d["layout"]
+    if lay.startswith("ptr"):
+        return GlobalReduce(op, **kw)(x, batch=mv(d["batch"]), size=d["groups"])
+    if lay.startswith("dense"):
+        return GlobalReduce(op, **kw)(x, mask=mv(d["mask"]))
+    so = SelectOutput(node_index=mv(d["node_index"]), cluster_index=mv(d["cluster_index"]),
+                      weight=None if weight is None else weight.detach(), num_nodes=d["num_nodes"],
+                      num_supernodes=d["groups"])
+    if weight is not None:
+        so._hold_values(weight)
+    return AggrReduce(get_aggr(op, **kw))(x, so)[0]
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_readout_public(seed):
+    d = FI.draw("readout", seed, limits())
+    case, report = f"readout-public-{seed}", []
+
+    def kernel():
+        x = _readout_x(d).detach().requires_grad_(True)  # (a column slice stays a view with its own row stride)
+        w = None if d.get("weight") is None else mv(d["weight"]).requires_grad_(True)
+        out = _readout_public(d, x, w)
+        assert out.dtype == F32 and "_SegmentAggrFnBackward" in _graph_names(out.grad_fn)
+        return _blocks(d, out), {"x": x, "weight": w}
+
+    outs, _ = kernel()
+    r64, r32 = FR.readout_reference(d, F64)[0], FR.readout_reference(d, F32)[0]
+    with torch.no_grad():
+        fails = forward_errors(case, outs, r64, r32, exact=_readout_exact_names(d), exact_ref=r32,
+                               factor=factor_of("readout"), report=report)
+    finish(case, fails, report)
+    nan_rows = d["layout"].startswith("dense") and d["mask"] is not None
+    if not nan_rows:
+        check_grads(case, kernel, lambda dt: FR.readout_reference(d, dt), ["x", "weight"])
+    else:  # the same, with finite values on the masked rows (their gradient must be exact zeros)
+        def kernel_finite():
+            x = mv(d["x"]).requires_grad_(True)
+            return _blocks(d, _readout_public(d, x)), {"x": x}
+        check_grads(case, kernel_finite, lambda dt: FR.readout_reference(d, dt), ["x"])
+        x = mv(d["x"]).requires_grad_(True)
+        (gx,) = torch.autograd.grad(_readout_public(d, x).sum(), x)
+        assert bool((gx[~mv(d["mask"])] == 0).all()), case
+
+
+# ============================================================================================================== SAG
+def _sag_x(d):
+    if d["layout"] == "sliced":
+        x = mv(d["x_base"])[:, d["first"]:d["first"] + d["F"]]
+        assert x.stride(0) == d["F"] + 5
+        return x
+    return offset_by_one_element(mv(d["x"])) if d["layout"] == "offset" else mv(d["x"])
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_sag_operators(seed):
+    from tgp import kernels as K
+    d = FI.draw("sag", seed, limits())
+    case, report = f"sag-op-{seed}", []
+    x, ei, n = _sag_x(d), mv(d["edge_index"]), d["n"]
+    w_rel, w_root, b = mv(d["w_rel"]), mv(d["w_root"]), mv(d["b"])
+    p, q = K.row_project2(x, w_rel, w_rel if w_root is None else w_root)
+    grp = K.sag_edge_group(ei, n, by_destination=True)
+    ascending = bool((d["edge_index"][1, 1:] >= d["edge_index"][1, :-1]).all())
+    assert ascending or d["order"] == "shuffled"
+    assert (grp.perm is None) == ascending, case  # a list that ascends in its destinations needs only its CSR offsets
+    t, a = K.sag_aggregate(grp, ei[0], p, None if w_root is None else q, b, mean=d["mean"], tanh=True, want_t=True)
+    t2, a2 = K.sag_score(x, ei, w_rel, w_root, b, mean=d["mean"], tanh=True, want_t=True)
+    assert torch.equal(t, t2) and torch.equal(a, a2), case
+    assert torch.equal(K.sag_score(x, ei, w_rel, w_root, b, mean=d["mean"], tanh=False), t), case
+    r64, r32 = FR.sag_reference(d, F64)[0], FR.sag_reference(d, F32)[0]
+    with torch.no_grad():
+        fails = forward_errors(case, {"p": p, "q": q, "t": t, "a": a}, r64, r32, factor=factor_of("sag"), report=report)
+    # the native backward operator: dX = g_q (x) w_root + g_p (x) w_rel, alone and added to a gradient already there
+    g_q, g_p = upstream(case + "q", n), upstream(case + "p", n)
+    old = upstream(case + "old", n, d["F"]) if seed % 2 else None
+    dx = K.sag_score_bwd_x(mv(g_q), mv(g_p), w_rel if w_root is None else w_root, w_rel,
+                           None if old is None else mv(old).clone())
+
+    def ref_dx(dtype):
+        g = FR.sag_bwd_x_reference(d, dtype, g_q, g_p)
+        return {"dx": g if old is None else g + old.to(dtype)}
+    fails += forward_errors(case, {"dx": dx}, ref_dx(F64), ref_dx(F32), factor=factor_of("sag"), report=report)
+    if seed % 4 == 0:
+        again = K.sag_score(x, mv(d["edge_index"].clone()), w_rel, w_root, b, mean=d["mean"], tanh=True, want_t=True)
+        assert torch.equal(t, again[0]) and torch.equal(a, again[1])
+        by_src = K.sag_edge_group(ei, n, by_destination=False)
+        gt = mv(g_q)
+        assert torch.equal(K.sag_aggregate(by_src, ei[1], gt), K.sag_aggregate(by_src, ei[1], gt))
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_sag_public(seed):
+    from tgp import functions as Fn
+    d = FI.draw("sag", seed, limits())
+    case, report = f"sag-public-{seed}", []
+    ei = mv(d["edge_index"])
+
+    def kernel():
+        lv = {"x": _sag_x(d).detach().requires_grad_(True), "w_rel": mv(d["w_rel"]).requires_grad_(True),
+              "w_root": None if d["w_root"] is None else mv(d["w_root"]).requires_grad_(True),
+              "b": None if d["b"] is None else mv(d["b"]).requires_grad_(True)}
+        a = Fn.sag_score(lv["x"], ei, lv["w_rel"], lv["w_root"], lv["b"], d["mean"], True)
+        assert "_SagScoreFnBackward" in _graph_names(a.grad_fn)
+        return {"a": a}, lv
+
+    def oracle(dtype):
+        outs, lv = FR.sag_reference(d, dtype)
+        return {"a": outs["a"]}, lv
+    outs, _ = kernel()
+    with torch.no_grad():
+        fails = forward_errors(case, outs, oracle(F64)[0], oracle(F32)[0], factor=factor_of("sag"), report=report)
+    finish(case, fails, report)
+    check_grads(case, kernel, oracle, ["x", "w_rel", "w_root", "b"])
+    if seed % 4 == 0:
+        runs = []
+        for _ in range(2):
+            o, lv = kernel()
+            leaves = [t for t in lv.values() if t is not None]
+            runs.append([o["a"].detach()] + list(torch.autograd.grad(o["a"].sum(), leaves)))
+        assert all(torch.equal(u, v) for u, v in zip(*runs)), case
+
+
+# ======================================================================================================== selectors
+def _kmis_got(res, n):
+    assert torch.equal(res.index[0], torch.arange(n, device=res.index.device))
+    return {"k": torch.tensor(res.k), "mis": res.mis, "cluster": res.index[1]}
+
+
+def _ec_got(res, n):
+    assert torch.equal(res.index[0], torch.arange(n, device=res.index.device))
+    return {"k": torch.tensor(res.k), "matched": res.matched, "match": res.match, "cluster": res.index[1]}
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_kmis_select(seed):
+    from tgp import kernels as K
+    d = FI.draw("kmis", seed, limits())
+    case = f"kmis-{seed}"
+    ei, n, k = mv(d["edge_index"]), d["n"], d["order_k"]
+    ptr, gmax = mv(d["graph_ptr"]), d["max_graph_nodes"]
+    assert K.kmis_route(n, ei.size(1), ptr, gmax) == d["route"], case
+    fails = []
+    for what, pri, perm in (("perm", dict(perm=mv(d["perm"])), d["perm"]),
+                            ("score", dict(score=mv(d["score"]), heuristic=None), FR.tied_order(d["score"]))):
+        want = FR.kmis_exact(d, perm)
+        for route in (None, "rounds"):
+            res = K.kmis_select(ei, n, k, graph_ptr=ptr, max_graph_nodes=gmax, route=route, **pri)
+            assert res.route == (d["route"] if route is None else "rounds"), (case, what, route, res.route)
+            fails += forward_errors(f"{case}-{what}-{route or 'natural'}", _kmis_got(res, n), want, want, exact=set(want))
+            if seed % 4 == 0:
+                two = K.kmis_select(ei, n, k, graph_ptr=ptr, max_graph_nodes=gmax, route=route, **pri)
+                assert torch.equal(res.index, two.index) and torch.equal(res.mis, two.mis) and res.k == two.k
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_edge_contract_select(seed):
+    import edgepool_restatement as RE
+    from tgp import kernels as K
+    d = FI.draw("edge_contract", seed, limits())
+    case = f"edge_contract-{seed}"
+    ei, n = mv(d["edge_index"]), d["n"]
+    ptr, gmax = mv(d["graph_ptr"]), d["max_graph_nodes"]
+    assert K.edge_contract_route(n, ei.size(1), ptr, gmax) == d["route"], case
+    fails = []
+    for what, pri, perm in (("perm", dict(perm=mv(d["perm"])), d["perm"]),
+                            ("score", dict(score=mv(d["score"])), FR.tied_order(d["score"]))):
+        want = FR.edge_contract_exact(d, perm)
+        if what == "score":  # the matched entry's score for both members of a pair, 1 for a singleton: copies
+            want["weight"] = RE.weights(d["edge_index"], n, want["matched"].bool(), d["score"])
+        for route in (None, "rounds"):
+            res = K.edge_contract_select(ei, n, graph_ptr=ptr, max_graph_nodes=gmax, route=route, **pri)
+            assert res.route == (d["route"] if route is None else "rounds"), (case, what, route, res.route)
+            got = _ec_got(res, n)
+            if what == "score":
+                got["weight"] = res.weight
+            fails += forward_errors(f"{case}-{what}-{route or 'natural'}", got, want, want, exact=set(want))
+            m = want["matched"].bool()
+            medge = res.medge.cpu()
+            pairs = d["edge_index"][:, m]
+            assert bool((medge[pairs[0]] == m.nonzero().view(-1)).all()) and bool((medge[pairs[1]] == m.nonzero().view(-1)).all())
+            assert int((medge >= 0).sum()) == torch.unique(pairs).numel()
+            if seed % 4 == 0:
+                two = K.edge_contract_select(ei, n, graph_ptr=ptr, max_graph_nodes=gmax, route=route, **pri)
+                assert torch.equal(res.index, two.index) and torch.equal(res.matched, two.matched) and res.k == two.k
+    assert not fails, "\n".join(fails)

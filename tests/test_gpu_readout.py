@@ -345,6 +345,27 @@ def test_gradients_split_among_tied_rows(op):
         assert_grad(got[1], sum(p[1] for p in parts), (8 + 2 + n) * U * terms, f"{which} d weight")
 
 
+@pytest.mark.parametrize("op", ["max", "min"])
+def test_gradient_of_an_extreme_that_is_exactly_zero(op):
+    """Regression, found by the seeded family sweep (readout draws of one and two rows per group, integer-valued x): a
+    group whose max / min is exactly 0.  The kernel's backward splits the gradient among the tied rows; the composed
+    form (float64, unsorted batch vectors) and the restatement started ``scatter_reduce`` from zeros, whose backward
+    counts that initial 0 as one more tied entry: the rows received 1 / (ties + 1).  All three routes now agree."""
+    x = torch.tensor([[0.0, -1.0, 3.0], [0.0, 2.0, 3.0], [0.0, 5.0, -4.0]])
+    batch = torch.tensor([0, 0, 1])
+    first = [0.5, 0.0, 0.5] if op == "max" else [0.5, 1.0, 0.5]
+    want = torch.tensor([first, [0.5, 1.0 - first[1], 0.5], [1.0, 1.0, 1.0]])
+    order = torch.tensor([2, 0, 1])
+    for name, xs, bs, ws in (("kernel", x, batch, want), ("float64", x.double(), batch, want.double()),
+                             ("unsorted", x[order], batch[order], want[order])):
+        xd = mv(xs).requires_grad_(True)
+        out = GlobalReduce(op)(xd, batch=mv(bs), size=3)
+        assert torch.equal(out.cpu(), R.scatter(xs, bs, 3, op)), name
+        assert torch.equal(torch.autograd.grad(out.sum(), xd)[0].cpu(), ws), name
+    x64 = x.double().requires_grad_(True)
+    assert torch.equal(torch.autograd.grad(R.scatter(x64, batch, 3, op).sum(), x64)[0], want.double())
+
+
 # ------------------------------------------------------------------------------------------------ routing
 def test_dtype_and_order_routing():
     batch, size = segment_batch(40)

@@ -41,7 +41,10 @@ class Aggregation(nn.Module):
 
 
 def composed_aggregate(x: Tensor, index: Tensor, dim_size: int, op: str) -> Tensor:
-    """PyG's ``scatter(x, index, 0, dim_size, op)`` from torch ops, in the dtype and on the device of ``x``."""
+    """PyG's ``scatter(x, index, 0, dim_size, op)`` from torch ops, in the dtype and on the device of ``x``: the same
+    values.  The gradient of max / min departs from it in one case, on purpose: a group whose extreme is exactly 0 hands
+    each tied row 1 / ties, as the kernel's backward does, where ``scatter_reduce`` started from zeros hands out
+    1 / (ties + 1) (DESIGN.md, "Readout gradients at a zero extreme")."""
     out = x.new_zeros((dim_size,) + tuple(x.shape[1:]))
     if op in ("sum", "mean"):
         out.index_add_(0, index, x)
@@ -49,8 +52,15 @@ def composed_aggregate(x: Tensor, index: Tensor, dim_size: int, op: str) -> Tens
             count = x.new_zeros(dim_size).index_add_(0, index, x.new_ones(index.numel())).clamp(min=1)
             out = out / count.view((-1,) + (1,) * (x.dim() - 1))
         return out
-    idx = index.view((-1,) + (1,) * (x.dim() - 1)).expand_as(x)
-    return out.scatter_reduce_(0, idx, x, reduce="amax" if op == "max" else "amin", include_self=False)
+    # the extremes start from -inf / +inf: ATen's backward counts the initial value among the tied entries even with
+    # include_self=False, so from zeros a group whose extreme is exactly 0 would hand its rows 1 / (ties + 1) of the
+    # gradient, where the kernel's backward (and every other group) hands out 1 / ties
+    shape = (-1,) + (1,) * (x.dim() - 1)
+    idx = index.view(shape).expand_as(x)
+    start = torch.full_like(out, float("-inf") if op == "max" else float("inf"))
+    ext = start.scatter_reduce_(0, idx, x, reduce="amax" if op == "max" else "amin", include_self=False)
+    some = torch.zeros(dim_size, dtype=torch.bool, device=x.device).index_fill_(0, index, True)
+    return torch.where(some.view(shape), ext, out)
 
 
 def _columns(out: Tensor, computed: Sequence[str], wanted: Sequence[str]) -> Tensor:
