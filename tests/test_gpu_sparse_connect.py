@@ -18,25 +18,8 @@ def dev():
 
 
 # --------------------------------------------------------------------------- SparseConnect weight gradients
-def _dense_ref_coalesce(ei, w, cl, k, op, remove_self_loops, eps=1e-8):
-    """Differentiable torch restatement of cluster -> coalesce(reduce=op) -> filters, returning the pooled weights in
-    row-major order (what PyG's scatter-based coalesce + postprocess_adj_pool_sparse compute)."""
-    key = cl[ei[0]] * k + cl[ei[1]]
-    uniq, inv = torch.unique(key, return_inverse=True)
-    if op in ("sum", "mean"):
-        out = torch.zeros(uniq.numel(), dtype=w.dtype).index_add(0, inv, w)
-        if op == "mean":
-            out = out / torch.bincount(inv, minlength=uniq.numel()).to(w.dtype)
-    elif op == "mul":
-        out = torch.ones(uniq.numel(), dtype=w.dtype).scatter_reduce(0, inv, w, "prod", include_self=True)
-    else:
-        out = torch.zeros(uniq.numel(), dtype=w.dtype).scatter_reduce(0, inv, w, "amax" if op == "max" else "amin",
-                                                                     include_self=False)
-    r, c = uniq // k, uniq % k
-    keep = out.abs() > eps
-    if remove_self_loops:
-        keep = keep & (r != c)
-    return torch.stack([r[keep], c[keep]]), out[keep]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from warm_state import _dense_ref_coalesce  # noqa: E402  (shared with tests/test_gpu_warm_state.py)
 
 
 # ------------------------------------------------------------------------------ fused coalesce route (r3)

@@ -195,6 +195,7 @@ def _edge_rows(edge_index: Tensor) -> Tuple[Tensor, Tensor]:
 # ------------------------------------------------------------------------- A1 + A2 + A4/A5 + A6, batches of small graphs
 _SPS_STATE: dict = {}  # (device index, stream handle) -> _SpsState
 _SPS_WORDS: dict = {}  # (graphs, mode) -> look-back words of the one-launch kernel (a native call otherwise)
+_EPOCH_LIMIT = (1 << 29) - 1  # the epoch at which a state's status buffer is cleared and its epochs start over
 # r6: the exact-size outputs of the one-launch sparse pooling are carved out of ONE allocation of at most this many bytes
 # (what a retained x' can pin); TGP_SPS_ARENA=0: four allocations of their own, sized once the count has arrived
 _SPS_ARENA = os.environ.get("TGP_SPS_ARENA", "1") != "0"
@@ -318,7 +319,7 @@ class _SpsState:
 
     def next_epoch(self) -> int:
         self.epoch += 1
-        if self.epoch >= (1 << 29) - 1:  # epochs of a buffer never repeat: start over on a cleared buffer
+        if self.epoch >= _EPOCH_LIMIT:  # epochs of a buffer never repeat: start over on a cleared buffer
             torch.cuda.synchronize(self.status.device)
             self.status.zero_()
             self.host[0] = 0
@@ -391,8 +392,11 @@ _edge_ptr_memo = _EDGE_RANGES.get
 
 def graph_edge_ptr(edge_index: Tensor, graph_ptr: Tensor) -> Tensor:
     """First edge of every graph of a sorted batch in a row-sorted list ([B+1] int64: lower bounds of ``graph_ptr`` in the
-    row array), remembered per (edge list object + version, graph_ptr object): one tiny launch for a new pair, nothing
-    for a pair that is pooled again.  The consumers re-check what they read through it."""
+    row array), remembered per (edge list object + version, graph_ptr object + version): one tiny launch for a new pair,
+    nothing for a pair that is pooled again.  ``sparse_pool_small`` and the one-launch GraclusSelect re-check what they
+    read through it (a wrong table is a refusal); ``dense_pool_select_sparse`` clamps the ranges into [0, E] and
+    ``dmon_edge_degrees`` reads them as they are: both trust that the table belongs to the list ("What is
+    remembered between calls")."""
     hit = _edge_ptr_memo(edge_index, graph_ptr)
     if hit is not None:
         return hit

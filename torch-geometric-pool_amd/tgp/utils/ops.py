@@ -151,10 +151,13 @@ def _batch_facts_sorted(batch: Tensor, info: "BatchInfo", topk_ratio: float = 0.
         # words are gone and the wait would spin into its bound: the facts are launched again
         ratio, call = pend
         fresh = call[0].facts_tag - call[1] < 8
-        if fresh and (ratio == float(topk_ratio or 0.0) or ratio > 0):
+        asked = float(topk_ratio or 0.0)
+        # the prefetch's TopK plan belongs to ITS ratio: taken for that ratio, or kept next to facts asked for without
+        # one; a call with another ratio launches again (the plan of r1 must not be stored under the key of r2)
+        if fresh and (ratio == asked or (ratio > 0 and asked <= 0)):
             launched = call
-            if ratio > 0 and not (topk_ratio and topk_ratio > 0):
-                topk_ratio = ratio  # (the prefetch also made a TopK plan: kept)
+            if ratio > 0:
+                topk_ratio = ratio  # (the prefetch also made a TopK plan: kept, under the prefetch's own ratio)
     if launched is None:
         launched = _facts_sorted_launch(batch, topk_ratio)
     state, tag, buf, n, want_plan = launched
