@@ -33,29 +33,6 @@ __device__ __forceinline__ float ac_unkey(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// NOT block_sum<256> (loss_common.h): the waves are added (sh0 + sh1) + (sh2 + sh3), a different rounding
-__device__ __forceinline__ float ac_block_sum(float v, float* sh) {  // 256 threads, sh: 4 floats; fixed order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float t = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return t;
-}
-
-__device__ __forceinline__ long long ac_block_count(long long v, long long* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const long long t = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return t;
-}
-
 __device__ __forceinline__ float ac_sign(float d) { return static_cast<float>((d > 0.f) - (d < 0.f)); }
 
 // ------------------------------------------------------------------------------------------------ dense total variation
@@ -131,8 +108,8 @@ __global__ __launch_bounds__(256) void acc_tv_dense_kernel(const float* __restri
       }
     }
   }
-  const float total = ac_block_sum(acc, sh);
-  const long long c = ac_block_count(lane == 0 ? cnt : 0, shc);
+  const float total = block_fold_pair256<true>(acc, sh, op_add{});
+  const long long c = block_fold_seq<256, true>(lane == 0 ? cnt : 0, shc);
   if (threadIdx.x == 0) {
     part[static_cast<int64_t>(b) * nrb + rb] = total;
     cnt_out[static_cast<int64_t>(b) * nrb + rb] = static_cast<int>(c);
@@ -234,6 +211,7 @@ __global__ __launch_bounds__(256) void acc_tv_edge_kernel(const float* __restric
     const float* Sj = S + j * K;
     for (int k = lane; k < K; k += 64) acc = fmaf(we, fabsf(Si[k] - Sj[k]), acc);
   }
+  // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if (lane == 0) node_tv[i] = acc;
@@ -526,12 +504,12 @@ __global__ __launch_bounds__(256) void acc_tail_kernel(const float* __restrict__
       t += tv[i];
       if (cnt) e += cnt[i];
     }
-    t = ac_block_sum(t, sh);
-    e = src_ptr ? static_cast<long long>(src_ptr[hi]) - src_ptr[lo] : ac_block_count(e, shc);
+    t = block_fold_pair256<true>(t, sh, op_add{});
+    e = src_ptr ? static_cast<long long>(src_ptr[hi]) - src_ptr[lo] : block_fold_seq<256, true>(e, shc);
   }
   if (colsum) {
     for (int k = threadIdx.x; k < K; k += 256) a += colsum[static_cast<int64_t>(b) * K + k];
-    a = ac_block_sum(a, sh);
+    a = block_fold_pair256<true>(a, sh, op_add{});
   }
   if (threadIdx.x == 0) {
     const long long e1 = e > 1 ? e : 1;

@@ -188,6 +188,7 @@ __global__ __launch_bounds__(256, (KT <= 2 || (KT == 4 && MODE != 2)) ? 2 : 1) v
   }
 
   if (MODE == 0) {
+    // the order of wave_butterfly (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       pos += __shfl_xor(pos, off);
@@ -248,6 +249,7 @@ __global__ __launch_bounds__(64) void bnpool_tail_kernel(const float* __restrict
   if (mask) {
     for (int i = lane; i < N; i += 64) n += mask[static_cast<long>(b) * N + i] != 0 ? 1 : 0;
   }
+  // the order of wave_butterfly (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     pos += __shfl_xor(pos, off);

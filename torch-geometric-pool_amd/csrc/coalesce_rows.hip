@@ -378,12 +378,6 @@ __device__ __forceinline__ void cr_intra21(uint32_t (&k)[4]) {
   cr_ce(k[0], k[1]); cr_ce(k[2], k[3]);  // j = 1
 }
 
-// DPP move (row_shr:n = 0x110 + n, row_shl:n = 0x100 + n, inside a 16-lane row; lanes shifted in from outside read 0)
-template <int CTRL>
-__device__ __forceinline__ uint32_t cr_dpp(uint32_t v) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
-}
-
 template <int LPR, typename WT>
 __device__ __forceinline__ void cr_sort_rows(uint32_t* s_key, WT* s_val, uint32_t b, uint32_t T, bool mine,
                                              uint32_t row_id, bool has_w, int reduce_op, int flags, WT eps,
@@ -416,7 +410,7 @@ __device__ __forceinline__ void cr_sort_rows(uint32_t* s_key, WT* s_val, uint32_
     c[q] = k[q] >> PB;
     acc[q] = (valid[q] && has_w) ? s_val[b + (k[q] & PM)] : WT(0);
   }
-  const uint32_t pc = cr_dpp<0x111>(c[3]);  // row_shr:1; an earlier element of a valid one is valid
+  const uint32_t pc = dpp<0x111, true>(c[3]);  // row_shr:1; an earlier element of a valid one is valid
   head[0] = valid[0] && (l == 0 || pc != c[0]);
 #pragma unroll
   for (int q = 1; q < 4; ++q) head[q] = valid[q] && c[q] != c[q - 1];
@@ -434,20 +428,20 @@ __device__ __forceinline__ void cr_sort_rows(uint32_t* s_key, WT* s_val, uint32_
   bool long_run = false;
   if (any_fold) {  // a run of three or more equal columns anywhere in the wave?
     // (DPP reads 0 from lanes that are switched off: move first, with every lane on, then mask)
-    const uint32_t prev_nh = cr_dpp<0x111>(nonhead[3] ? 1u : 0u);
+    const uint32_t prev_nh = dpp<0x111, true>(nonhead[3] ? 1u : 0u);
     const bool prev_nonhead = (l > 0) & (prev_nh != 0u);
     long_run = __any((nonhead[0] && prev_nonhead) || (nonhead[1] && nonhead[0]) || (nonhead[2] && nonhead[1]) ||
                      (nonhead[3] && nonhead[2]));
   }
   if (any_fold && !long_run) {  // runs of two: the head takes its successor's weight, in registers
-    const uint32_t next_nh = cr_dpp<0x101>(nonhead[0] ? 1u : 0u);  // row_shl:1
+    const uint32_t next_nh = dpp<0x101, true>(nonhead[0] ? 1u : 0u);  // row_shl:1
     const bool next_nonhead = (l < LPR - 1) & (next_nh != 0u);
     WT next_acc;
     if constexpr (sizeof(WT) == 4) {
-      next_acc = __uint_as_float(cr_dpp<0x101>(__float_as_uint(acc[0])));
+      next_acc = __uint_as_float(dpp<0x101, true>(__float_as_uint(acc[0])));
     } else {  // a double travels as its two halves
       const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(acc[0]));
-      const uint32_t lo = cr_dpp<0x101>(static_cast<uint32_t>(bits)), hi = cr_dpp<0x101>(static_cast<uint32_t>(bits >> 32));
+      const uint32_t lo = dpp<0x101, true>(static_cast<uint32_t>(bits)), hi = dpp<0x101, true>(static_cast<uint32_t>(bits >> 32));
       next_acc = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
     }
 #pragma unroll
@@ -491,14 +485,14 @@ __device__ __forceinline__ void cr_sort_rows(uint32_t* s_key, WT* s_val, uint32_
   }
   uint32_t incl = cnt_lane;  // inclusive scan over the LPR lanes of the row
   {
-    uint32_t t = cr_dpp<0x111>(incl);  // row_shr:d inside the 16-lane row; the l >= d guard keeps it inside the LPR group
+    uint32_t t = dpp<0x111, true>(incl);  // row_shr:d inside the 16-lane row; the l >= d guard keeps it inside the LPR group
     if (l >= 1) incl += t;
-    t = cr_dpp<0x112>(incl);
+    t = dpp<0x112, true>(incl);
     if (l >= 2) incl += t;
-    t = cr_dpp<0x114>(incl);
+    t = dpp<0x114, true>(incl);
     if (l >= 4) incl += t;
     if constexpr (LPR == 16) {
-      t = cr_dpp<0x118>(incl);
+      t = dpp<0x118, true>(incl);
       if (l >= 8) incl += t;
     }
   }
@@ -1196,6 +1190,7 @@ __device__ __forceinline__ bool fz_lookback(const unsigned long long* __restrict
     const unsigned long long pre = __ballot((st >> 32) == 2);
     const int first = pre ? __builtin_ctzll(pre) : 64;  // nearest predecessor that already knows its prefix
     uint32_t v = lane <= first ? static_cast<uint32_t>(st) : 0u;
+    // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     excl += v;

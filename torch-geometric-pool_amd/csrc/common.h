@@ -66,3 +66,5 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace tgp
+
+#include "wave.h"  // the wave and block reductions (needs lane_id above)

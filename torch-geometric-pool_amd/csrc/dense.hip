@@ -523,6 +523,7 @@ __global__ __launch_bounds__(256) void slab_sum_split_kernel(const float* __rest
 #pragma unroll 4
       for (int sp = q; sp < slabs; sp += 8) v = __fadd_rn(v, src[static_cast<long>(sp) * K * W]);
     }
+    // the butterfly going UP, offsets 1, 2, 4 (not wave_fold<8>, which goes down): the eight slab groups of a column
     v = __fadd_rn(v, __shfl_xor(v, 1, 64));
     v = __fadd_rn(v, __shfl_xor(v, 2, 64));
     v = __fadd_rn(v, __shfl_xor(v, 4, 64));
@@ -616,6 +617,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
         }
       }
       if (!cols) {
+        // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
         for (int dd = 32; dd > 0; dd >>= 1) racc += __shfl_xor(racc, dd, WAVE);
         if (lane == 0) s_d[i] = racc;
@@ -655,6 +657,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
           cacc[jj] += gp;
         }
       }
+      // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
       for (int dd = 32; dd > 0; dd >>= 1) racc += __shfl_xor(racc, dd, WAVE);
       if (lane == 0) s_rowq[i] = racc;
@@ -715,6 +718,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
     for (int i = wave; i < K; i += NW) {
       float acc = 0.f;
       for (int j = lane; j < K; j += 64) acc += r1(i, j);
+      // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
       for (int dd = 32; dd > 0; dd >>= 1) acc += __shfl_xor(acc, dd, WAVE);
       if (lane == 0) s_d[i] = acc;
@@ -745,6 +749,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
   for (int i = wave; i < K; i += NW) {  // rowsum_i(G P)
     float acc = 0.f;
     for (int j = lane; j < K; j += 64) acc += gv(i, j) * pval(i, j);
+    // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int dd = 32; dd > 0; dd >>= 1) acc += __shfl_xor(acc, dd, WAVE);
     if (lane == 0) s_rowq[i] = acc;

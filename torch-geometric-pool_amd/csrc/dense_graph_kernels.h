@@ -64,37 +64,7 @@ struct SmallArgs {
   float* diff_stats;
 };
 
-__device__ __forceinline__ float sg_wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
 __device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
-// Reductions over the 32 lanes of a half-wave, the result in every lane: four DPP rotations inside the 16-lane rows
-// (register moves) and ONE ds_swizzle across the two rows (a __shfl_xor ladder is five trips through the LDS pipe: 320
-// of them per wave made the folded selector cost 20 us instead of 3)
-template <int CTRL>
-__device__ __forceinline__ float sg_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float sg_swz16(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x1F | (16 << 10)));
-}
-__device__ __forceinline__ float sg_half_sum(float v) {
-  v += sg_dpp<0x121>(v);  // row_ror:1
-  v += sg_dpp<0x122>(v);
-  v += sg_dpp<0x124>(v);
-  v += sg_dpp<0x128>(v);
-  return v + sg_swz16(v);
-}
-__device__ __forceinline__ float sg_half_max(float v) {
-  v = fmaxf(v, sg_dpp<0x121>(v));
-  v = fmaxf(v, sg_dpp<0x122>(v));
-  v = fmaxf(v, sg_dpp<0x124>(v));
-  v = fmaxf(v, sg_dpp<0x128>(v));
-  return fmaxf(v, sg_swz16(v));
-}
 // exp(x) for x <= 0 on v_exp_f32 with the rounding error of x * log2(e) carried along (as csrc/mlp_select.hip: relative
 // error ~2e-7; -inf and anything below 2^-150 give 0)
 __device__ __forceinline__ float sg_exp_neg(float x) {
@@ -285,11 +255,11 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
         //  four DPP moves and an LDS swizzle each)
         float mx[16], ex[16], sm[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mx[r] = sg_half_max(z[r]);
+        for (int r = 0; r < 16; ++r) mx[r] = wave_half_fold(z[r], op_max{});
 #pragma unroll
         for (int r = 0; r < 16; ++r) ex[r] = sg_exp_neg(z[r] - mx[r]);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sm[r] = sg_half_sum(ex[r]);
+        for (int r = 0; r < 16; ++r) sm[r] = wave_half_fold(ex[r], op_add{});
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int node = 32 * T + rho(r) + 4 * lk;
@@ -400,7 +370,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (rho(r) + 4 * lk == lm) tr += aa[r];
-        tr = sg_wave_sum(tr);
+        tr = wave_sum(tr);
         // degrees: lane i sums row i of the (logical) adjacency tile; rows / columns beyond N are zero
         float* s_deg = As + SG_N * SG_LDA;
         {
@@ -417,7 +387,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
           const int node = 32 * (q >> 4) + rho(q & 15) + 4 * lk;
           den = fmaf(s_deg[node], sr[q] * sr[q], den);
         }
-        den = sg_wave_sum(den);
+        den = wave_sum(den);
         f32x16 gg;  // S^T S: lane = column, register r = row rho(r) + 4 lk
 #pragma unroll
         for (int r = 0; r < 16; ++r) gg[r] = 0.f;
@@ -426,7 +396,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
         float fro = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) fro = fmaf(gg[r], gg[r], fro);
-        const float nrm = sqrtf(sg_wave_sum(fro));
+        const float nrm = sqrtf(wave_sum(fro));
         const float tdiag = 1.0f / sqrtf(static_cast<float>(K));
         float acc = 0.f;
 #pragma unroll
@@ -437,7 +407,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
             acc = fmaf(y, y, acc);
           }
         }
-        acc = sg_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) {
           p.mincut_terms[b] = -(tr / (den + p.loss_eps));
           p.mincut_terms[p.B + b] = sqrtf(acc);
@@ -448,14 +418,14 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (rho(r) + 4 * lk == lm) tr += aa[r];
-        tr = sg_wave_sum(tr);
+        tr = wave_sum(tr);
         float a2 = 0.f;  // lane i sweeps row i of the adjacency tile (rows / columns beyond N are zero)
         {
           const float* rowp = As + lane * SG_LDA;
 #pragma unroll 16
           for (int j = 0; j < SG_N; ++j) a2 = fmaf(rowp[j], rowp[j], a2);
         }
-        a2 = sg_wave_sum(a2);
+        a2 = wave_sum(a2);
         f32x16 gg;  // S^T S: lane = column, register r = row rho(r) + 4 lk
 #pragma unroll
         for (int r = 0; r < 16; ++r) gg[r] = 0.f;
@@ -464,11 +434,11 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
         float fro = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) fro = fmaf(gg[r], gg[r], fro);
-        fro = sg_wave_sum(fro);
+        fro = wave_sum(fro);
         float ent = 0.f;  // (padded nodes / columns hold S = 0: -0 log(eps) = 0)
 #pragma unroll
         for (int q = 0; q < 32; ++q) ent -= sr[q] * logf(sr[q] + p.loss_eps);
-        ent = sg_wave_sum(ent);
+        ent = wave_sum(ent);
         if (lane == 0) {
           float* o = p.diff_stats + static_cast<long>(b) * 4;
           o[0] = a2; o[1] = tr; o[2] = fro; o[3] = ent;
@@ -494,13 +464,14 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
             float s = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) s += aa[r];
-            s += __shfl_xor(s, 32, WAVE);
+            s = wave_sum<64, 32>(s);  // the two half-waves
             dcol = s;
           } else {                            // sum over columns (axis -1): reduce each row over lanes
             float mine = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               float s = aa[r];
+              // the order of wave_sum<32> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
               for (int d = 16; d > 0; d >>= 1) s += __shfl_xor(s, d, WAVE);
               // row (rho(r) + 4*lk) total now on every lane of this half-wave; hand it to lane = row
@@ -529,8 +500,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
 #pragma unroll
           for (int r = 0; r < 16; ++r)
             if (lm < K && rho(r) + 4 * lk < K) m = fmaxf(m, fabsf(aa[r]));
-#pragma unroll
-          for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, WAVE));
+          m = wave_max(m);
           if (m == 0.f) m = 1.f;
 #pragma unroll
           for (int r = 0; r < 16; ++r) aa[r] = aa[r] / m;
@@ -696,14 +666,14 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       if (rho(r) + 4 * lk == lm) tr += R[r];
-    tr = sg_wave_sum(tr);
+    tr = wave_sum(tr);
     float den = 0.f;
 #pragma unroll
     for (int q = 0; q < 32; ++q) {
       const int node = 32 * (q >> 4) + rho(q & 15) + 4 * lk;
       den = fmaf(s_deg[node], sr[q] * sr[q], den);
     }
-    den = sg_wave_sum(den) + p.loss_eps;
+    den = wave_sum(den) + p.loss_eps;
     cdiag = -gt_cut / den;
     c1 = 2.0f * gt_cut * tr / (den * den);
   }
@@ -717,7 +687,7 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
       float fro = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) fro = fmaf(gg[r], gg[r], fro);
-      const float ng2 = sg_wave_sum(fro), ng = sqrtf(ng2);
+      const float ng2 = wave_sum(fro), ng = sqrtf(ng2);
       const float tdiag = 1.0f / sqrtf(static_cast<float>(K));
       float y[16], ny2 = 0.f, gy = 0.f;
 #pragma unroll
@@ -727,8 +697,8 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
         ny2 = fmaf(y[r], y[r], ny2);
         gy = fmaf(gg[r], y[r], gy);
       }
-      ny2 = sg_wave_sum(ny2);
-      gy = sg_wave_sum(gy);
+      ny2 = wave_sum(ny2);
+      gy = wave_sum(gy);
       const float ny = sqrtf(ny2);
       const float coef = ny > 0.f ? 2.0f * gt_ortho / (ny * ng) : 0.f;  // (the factor 2: gG + gG^T, gG symmetric)
 #pragma unroll
@@ -780,13 +750,14 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
         float s = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s += r0[r];
-        s += __shfl_xor(s, 32, WAVE);
+        s += __shfl_xor(s, 32, WAVE);  // the two half-waves (wave_sum<64, 32>, written out)
         dcol = s;
       } else {
         float mine = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float s = r0[r];
+          // the order of wave_sum<32> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
           for (int d = 16; d > 0; d >>= 1) s += __shfl_xor(s, d, WAVE);
           if (lm == rho(r) + 4 * lk) mine = s;
@@ -810,12 +781,13 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
         qv[r] = gP[r] * pv;
         colq += qv[r];
         float s = qv[r];
+        // the order of wave_sum<32> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
         for (int dd = 16; dd > 0; dd >>= 1) s += __shfl_xor(s, dd, WAVE);
         if (lm == row) rowmine = s;
         gP[r] = gP[r] / (drow * d);
       }
-      colq += __shfl_xor(colq, 32, WAVE);
+      colq += __shfl_xor(colq, 32, WAVE);  // the two half-waves (wave_sum<64, 32>, written out)
       {
         const float other = __shfl_xor(rowmine, 32, WAVE);
         bool own = false;
@@ -1225,6 +1197,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void dense_pool_medium_kernel(Med
       const int i = e / KP, j = e % KP;
       if (j < K) m = fmaxf(m, fabsf(Rs[i * (KP + 1) + j]));
     }
+    // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, WAVE));
     __syncthreads();

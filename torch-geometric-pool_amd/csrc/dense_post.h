@@ -98,6 +98,7 @@ __global__ __launch_bounds__(1024) void post_degree_kernel(PostArgs p) {
       if (i >= K) break;
       float s = 0.f;
       for (int j = lane; j < K; j += 64) s = __fadd_rn(s, a[static_cast<long>(i) * K + j]);
+      // the shuffle-down ladder, distances 32 .. 1: lane 0 alone holds the result, and not in the rounding of wave_fold
 #pragma unroll
       for (int d = 32; d > 0; d >>= 1) s = __fadd_rn(s, __shfl_down(s, d, WAVE));
       if (lane == 0) p.dvec[static_cast<long>(b) * K + i] = sqrtf(fmaxf(s, p.eps));
@@ -130,6 +131,7 @@ __global__ __launch_bounds__(256) void post_scale_kernel(PostArgs p) {
     }
   }
   if (p.flags & TGP_EDGE_WEIGHT_NORM) {
+    // the shuffle-down ladder (as post_degree_kernel): lane 0 alone holds the maximum
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_down(mx, d, WAVE));
     if (lane_id() == 0) s_max[wave_id()] = mx;
@@ -209,6 +211,7 @@ __global__ __launch_bounds__(256) void post_small_kernel(PostArgs p, int B) {
     }
   }
   if (p.flags & TGP_EDGE_WEIGHT_NORM) {
+    // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, WAVE));
     if (m == 0.f) m = 1.f;
@@ -269,8 +272,7 @@ __global__ __launch_bounds__(256) void post_tiny_kernel(PostArgs p, int B) {
 #pragma unroll
     for (int j = 0; j < 32; ++j)
       if (!hi && ok && j < K) m = fmaxf(m, fabsf(t[j]));
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) m = fmaxf(m, __shfl_xor(m, sft, WAVE));
+    m = wave_max(m);
     if (m == 0.f) m = 1.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) t[j] = t[j] / m;
@@ -394,6 +396,7 @@ __global__ __launch_bounds__(1024) void post_lds_kernel(PostArgs p, int B, XComb
       for (int i = w; i < K; i += 16) {
         float sacc = 0.f;
         for (int j = lane; j < K; j += 64) sacc = __fadd_rn(sacc, m[i * K + j]);
+        // the shuffle-down ladder of post_degree_kernel (the same bits)
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) sacc = __fadd_rn(sacc, __shfl_down(sacc, d, WAVE));
         if (lane == 0) dv[i] = sqrtf(fmaxf(sacc, p.eps));
@@ -423,6 +426,7 @@ __global__ __launch_bounds__(1024) void post_lds_kernel(PostArgs p, int B, XComb
     }
   }
   if (!ewn) return;
+  // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, WAVE));
   if (lane == 0) s_max[w] = mx;

@@ -153,11 +153,7 @@ __global__ __launch_bounds__(256) void batch_facts_kernel(const int64_t* __restr
       atomicAdd(sizes + b, static_cast<unsigned long long>(end - lane));
     }
     long long mx = in ? b : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const long long t = __shfl_xor(mx, o, 64);
-      mx = t > mx ? t : mx;
-    }
+    mx = wave_max(mx);
     if (lane == 0) atomicMax(facts, static_cast<unsigned long long>(mx));
   }
 }
@@ -181,6 +177,7 @@ __global__ __launch_bounds__(256) void batch_facts_finish_kernel(const unsigned 
       }
     }
   }
+  // the order of wave_butterfly (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long t = __shfl_xor(mx, o, 64);
@@ -302,6 +299,7 @@ __global__ __launch_bounds__(256) void batch_facts_sorted_kernel(const int64_t* 
       keep += mine;
       if (koff) {  // exclusive prefix of k over the graphs, in graph order: thread-local, then over the workgroup
         long long inc = mine;
+        // the order of wave_incl_scan (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
           const long long o = __shfl_up(inc, off, WAVE);
@@ -329,6 +327,7 @@ __global__ __launch_bounds__(256) void batch_facts_sorted_kernel(const int64_t* 
     }
     if (koff && tid == 0) koff[B] = s_carry;
   }
+  // the order of wave_butterfly (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const long long t = __shfl_xor(mx, o, 64);

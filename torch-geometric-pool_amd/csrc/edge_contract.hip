@@ -71,7 +71,8 @@ __global__ __launch_bounds__(256) void ec_project_kernel(const float* __restrict
         }
       }
     }
-    for (int m = lpr >> 1; m >= 1; m >>= 1) {  // (uniform trip count: every lane of the wave takes part)
+    // the order of wave_butterfly at a run-time group width (uniform trip count: every lane of the wave takes part)
+    for (int m = lpr >> 1; m >= 1; m >>= 1) {
       a1 = a1 + __shfl_xor(a1, m);
       a2 = a2 + __shfl_xor(a2, m);
     }
@@ -125,12 +126,12 @@ __global__ __launch_bounds__(256) void ec_softmax_stats_kernel(const float* __re
   if (!hub) {
     for (int32_t j = b + sub + EC_GROUP; j < e; j += EC_GROUP) mx = fmaxf(mx, raw[grp_perm[j]]);
   }
-  for (int m = EC_GROUP >> 1; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+  mx = wave_max<EC_GROUP>(mx);
   if (first) sum = expf(v0 - mx);
   if (!hub) {
     for (int32_t j = b + sub + EC_GROUP; j < e; j += EC_GROUP) sum = sum + expf(raw[grp_perm[j]] - mx);
   }
-  for (int m = EC_GROUP >> 1; m >= 1; m >>= 1) sum = sum + __shfl_xor(sum, m);
+  sum = wave_sum<EC_GROUP>(sum);
   if (!live || sub != 0) return;
   if (hub) {
     const int q = atomicAdd(hubs, 1);

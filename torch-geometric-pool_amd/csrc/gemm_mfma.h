@@ -747,6 +747,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
         }
     }
     // fixed-order reduction: lanes (xor butterfly) -> waves (LDS, summed in wave order)
+    // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
     __syncthreads();
@@ -808,7 +809,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           cs = __fadd_rn(cs, (g.colsum_skip_diag && (r & 3) + 8 * (r >> 2) == dcol) ? 0.f : acc[j][r]);
-        cs = __fadd_rn(cs, __shfl_xor(cs, 32, 64));
+        cs = wave_fold<64, 32>(cs, op_fadd_rn{});  // the two half-waves
         if (lk == 0) smem[wm * BN + wn * (BN / WN) + j * 32 + lm] = cs;
       }
       __syncthreads();

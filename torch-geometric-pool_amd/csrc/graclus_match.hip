@@ -59,6 +59,7 @@ __global__ __launch_bounds__(256) void gm_csr_gather_kernel(const int64_t* __res
       term = i < j ? h : 0ull - h;
     }
   }
+  // the order of wave_sum on a 64-bit value, its halves shuffled apart (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const unsigned lo = __shfl_xor(static_cast<unsigned>(term), off, WAVE);
@@ -76,6 +77,7 @@ __global__ __launch_bounds__(1024) void gm_fingerprint_kernel(const unsigned lon
   __shared__ unsigned long long s_sum[16];
   unsigned long long t = 0;
   for (int b = threadIdx.x; b < nb; b += 1024) t += partial[b];
+  // the order of wave_sum on a 64-bit value, its halves shuffled apart (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const unsigned lo = __shfl_xor(static_cast<unsigned>(t), off, WAVE);
@@ -933,12 +935,7 @@ __global__ __launch_bounds__(256) void rl_paired_prefix_kernel(const uint32_t* _
   const int t = blockIdx.x * 8 + (threadIdx.x >> 5), q = threadIdx.x & 31;  // 32 lanes per tile, 8 tiles per workgroup
   if (t >= tiles) return;
   const uint32_t c = __popc(paired[static_cast<int64_t>(t) * 32 + q]);
-  uint32_t inc = c;
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) {
-    const uint32_t v = __shfl_up(inc, o, 32);
-    if (q >= o) inc += v;
-  }
+  const uint32_t inc = wave_incl_scan<32>(c);
   wprefix2[static_cast<int64_t>(t) * 32 + q] = inc - c;
   if (q == 31) tile_sum2[t] = inc;
 }

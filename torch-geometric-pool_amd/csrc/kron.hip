@@ -50,15 +50,6 @@ __global__ __launch_bounds__(256) void kron_flags_kernel(const int64_t* __restri
   if (j > 0 && node_index[j - 1] >= v) atomicOr(status, KRON_UNSORTED);
 }
 
-__device__ __forceinline__ int64_t wave_incl_scan64(int64_t v) {
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const int64_t t = __shfl_up(v, d, WAVE);
-    if (lane_id() >= d) v += t;
-  }
-  return v;
-}
-
 // what the multi-workgroup kernels need to know about one of their graphs: ONE 40-byte record read per workgroup
 // (graph_ptr -> rank -> big_off was a chain of three dependent global reads in front of every panel launch)
 struct BigDesc {
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(1024) void kron_plan_kernel(const int64_t* __restri
         }
       }
     }
-    const int64_t isq = wave_incl_scan64(sq), ibig = wave_incl_scan64(big);
+    const int64_t isq = wave_incl_scan(sq), ibig = wave_incl_scan(big);
     if (lane == WAVE - 1) { s_w[0][w] = isq; s_w[1][w] = ibig; }
     __syncthreads();
     int64_t osq = s_carry[0], obig = s_carry[1], tsq = 0, tbig = 0;
@@ -883,6 +874,7 @@ __global__ __launch_bounds__(256) void kron_big_fill_kernel(KronArgs a, const ui
   const float* d = a.dense + a.sq_off[q.g];
   uint32_t before = 0;  // survivors of the graph's rows in front of this block (per-row counts from the finish pass)
   for (int i = threadIdx.x; i < i0; i += 256) before += a.rowcnt[q.r0 + i];
+  // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
   if (lane == 0) s_w[w] = before;

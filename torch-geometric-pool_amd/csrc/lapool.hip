@@ -13,17 +13,6 @@
 namespace tgp {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-  return x;
-}
-
 __device__ __forceinline__ int graph_of(int64_t row, int N, const int64_t* ptr, const int64_t* batch) {
   return ptr ? (batch ? static_cast<int>(batch[row]) : 0) : static_cast<int>(row / N);
 }
@@ -117,7 +106,7 @@ __global__ __launch_bounds__(256) void lapool_var_csr_kernel(const int32_t* __re
       ss = fmaf(d, d, ss);
     }
   }
-  for (int o = G / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  for (int o = G / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);  // the order of wave_sum at a run-time group width
   if (row < n && sub == 0) v[row] = sqrtf(ss);
 }
 
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(256) void lapool_norm_kernel(const float* __restric
   float ss = 0.f;
   if (row < rows)
     for (int f = sub; f < F; f += G) ss = fmaf(X[row * F + f], X[row * F + f], ss);
-  for (int o = G / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  for (int o = G / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);  // the order of wave_sum at a run-time group width
   if (row < rows && sub == 0) nrm[row] = sqrtf(ss);
 }
 

@@ -55,11 +55,6 @@ __device__ __forceinline__ int sps_tile_id(unsigned long long* ticket_word, unsi
   return *s_tile;
 }
 
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
 // The look-back in two halves, so that the words' round trip (~1 us: they live behind the fabric) overlaps work that does
 // not depend on them: `issue` requests the 256 nearest predecessor words, `finish` consumes them (re-reading only those
 // that were not published yet) and walks further back if none of them held a prefix.
@@ -125,7 +120,7 @@ __device__ __forceinline__ void sps_lookback_finish(unsigned long long* status, 
       if (!done) {  // (uniform: `done` comes from ballots)
         const unsigned long long pre = __ballot(((lk.st[k] >> 32) & 3ull) == 2);
         const int first = pre ? __builtin_ctzll(pre) : 64;  // nearest predecessor that already knows its prefix
-        excl += wave_sum32(lane <= first ? static_cast<uint32_t>(lk.st[k]) & 0x7FFFFFFFu : 0u);
+        excl += wave_sum(lane <= first ? static_cast<uint32_t>(lk.st[k]) & 0x7FFFFFFFu : 0u);
         bad = bad || __any(lane <= first && ((lk.st[k] >> 31) & 1ull));
         done = pre != 0ull;
       }
@@ -151,28 +146,6 @@ __device__ __forceinline__ void sps_lookback(unsigned long long* status, int til
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Finding a sorted batch's per-graph ranges inside a kernel (sparse_pool_small.hip, the one-launch Graclus matching).
-__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, WAVE);
-  return v;
-}
-__device__ __forceinline__ int64_t wave_min64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int64_t t = __shfl_xor(v, o, WAVE);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int64_t wave_max64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int64_t t = __shfl_xor(v, o, WAVE);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 // NK lower bounds by ONE wave, together: 128 probes per round and key (two per lane), the loads of all keys in
 // flight at once -- three dependent rounds for 300 k entries instead of a log2 chain of nineteen.  On an array that is
 // not ascending the result is still a deterministic function of (array, key), which is all the tiling check of the

@@ -11,42 +11,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PART_ROWS = 64;  // rows of one graph per workgroup of a partial pass (dmon_part_kernel, hosc_part_kernel, jb_part_kernel)
 
-// ---- block sums ---------------------------------------------------------------------------------------------------
-// NV sums over the T threads of a workgroup behind ONE pair of barriers (sh: NV * T / 64 floats); every thread gets
-// every sum.  The order of the additions is what makes the losses reproducible (no float atomics), and it is this one:
-// within a wave __shfl_xor at offsets 32, 16, 8, 4, 2, 1; one float per wave in sh; then t = 0, t += sh[w] for
-// w = 0 .. T / 64 - 1.
-// Barriers: one before the write of sh, one before its reads, NONE behind them.  A second call may follow directly (its
-// first barrier comes after every thread's reads of this one); a caller that touches sh by other means between two calls
-// needs a barrier of its own.  Memory a caller wrote to LDS before the call is visible to every thread after it.
-template <int T, int NV>
-__device__ __forceinline__ void block_sums(float (&v)[NV], float* sh) {
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) sh[q * (T / 64) + (threadIdx.x >> 6)] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) t += sh[q * (T / 64) + w];
-    v[q] = t;
-  }
-}
-
-template <int T>
-__device__ __forceinline__ float block_sum(float v, float* sh) {  // sh: T / 64 floats
-  float one[1] = {v};
-  block_sums<T, 1>(one, sh);
-  return one[0];
-}
-
 // ---- the orthogonality term || G / ||G||_F - I / sqrt(K) ||_F of one graph (utils/losses.py:59-70) -----------------
 // T threads, G [K,K]; sq = ||G||_F^2, which the caller reduces beside its other sums.  sh: T / 64 floats.
 template <int T>
@@ -145,6 +109,7 @@ __global__ __launch_bounds__(256) void a_rows_kernel(const float* __restrict__ A
       for (int j = sub; j < N; j += G) d += a[j];
     }
   }
+  // the order of wave_sum<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
   if (row < rows && sub == 0) y[row] = d;

@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256) void cut_rows_kernel(const float* __restrict__
     }
     for (int k = sub; k < K; k += G) qq = fmaf(s[k], s[k], qq);
   }
+  // the order of wave_butterfly<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) {
     d += __shfl_xor(d, o, 64);
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(256) void edge_dot_kernel(const int64_t* __restrict
         for (int k = sub; k < K; k += G) acc = fmaf(a[k], b[k], acc);
       }
     }
+    // the order of wave_sum<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (e < E && sub == 0) out[e] = acc;
@@ -618,6 +620,7 @@ __global__ __launch_bounds__(256) void edge_row_stats_kernel(const int* __restri
     const float* s = S + i * K;
     for (int k = sub; k < K; k += G) qq = fmaf(s[k], s[k], qq);
   }
+  // the order of wave_butterfly<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) {
     d += __shfl_xor(d, o, 64);

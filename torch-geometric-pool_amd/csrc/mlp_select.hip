@@ -252,12 +252,10 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ y
   float* row = y + m * K;
   float mx = -INFINITY;
   for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k] + (bias ? bias[k] : 0.f));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   float sum = 0.f;
   for (int k = lane; k < K; k += 64) sum += expf(row[k] + (bias ? bias[k] : 0.f) - mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  sum = wave_sum(sum);
   const float keep = mask ? static_cast<float>(mask[m] != 0) : 1.f;
   for (int k = lane; k < K; k += 64) row[k] = expf(row[k] + (bias ? bias[k] : 0.f) - mx) / sum * keep;
 }
@@ -274,8 +272,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
   float dot = 0.f;
   if (ok)
     for (int k = sub; k < K; k += G) dot = fmaf(dr[k], sr[k], dot);
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+  dot = wave_sum<G>(dot);
   if (ok) {
     float* out = dy + m * K;
     for (int k = sub; k < K; k += G) out[k] = sr[k] * (dr[k] - dot);
@@ -316,8 +313,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_ex_kernel(const float* __rest
   float dot = 0.f;
   if (ok)
     for (int k = sub; k < K; k += G) dot = fmaf(eff(k), sr[k], dot);
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+  dot = wave_sum<G>(dot);
   if (ok) {
     float* out = dy + m * ld_dy;
     for (int k = sub; k < K; k += G) out[k] = sr[k] * (eff(k) - dot);

@@ -23,80 +23,6 @@ __device__ __forceinline__ uint32_t ndp_hash(uint64_t seed, uint64_t v) {
   return static_cast<uint32_t>(x);
 }
 
-// Sum over the 64 lanes of a wave, the same value in every lane: four rotate-and-add steps inside the 16-lane rows
-// (DPP row_ror: register moves, no trip through the LDS pipe that a shuffle takes), then the four row sums are read
-// through scalar registers.  The iteration below does a dozen of these per step, back to back.
-template <int CTRL>
-__device__ __forceinline__ double ndp_dpp_f64(double v) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(u), CTRL, 0xF, 0xF, false));
-  const unsigned hi =
-      static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(u >> 32), CTRL, 0xF, 0xF, false));
-  return __longlong_as_double((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-__device__ __forceinline__ double ndp_readlane_f64(double v, int lane) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(u), lane));
-  const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(u >> 32), lane));
-  return __longlong_as_double((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-__device__ __forceinline__ double ndp_wave_sum(double v) {
-  v += ndp_dpp_f64<0x121>(v);  // row_ror:1
-  v += ndp_dpp_f64<0x122>(v);  // row_ror:2
-  v += ndp_dpp_f64<0x124>(v);  // row_ror:4
-  v += ndp_dpp_f64<0x128>(v);  // row_ror:8 -> every lane holds its row's sum
-  return (ndp_readlane_f64(v, 0) + ndp_readlane_f64(v, 16)) + (ndp_readlane_f64(v, 32) + ndp_readlane_f64(v, 48));
-}
-
-template <int THREADS>
-__device__ __forceinline__ double ndp_block_sum(double v, double* s_red) {
-  v = ndp_wave_sum(v);
-  if constexpr (THREADS == 64) return v;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < THREADS / 64; ++w) t += s_red[w];
-  return t;
-}
-// K sums at once: the K wave reductions are independent instruction chains (they overlap), and a 256-thread
-// workgroup pays its two barriers once for all of them.  s_red: K * (THREADS / 64) doubles.
-template <int THREADS, int K>
-__device__ __forceinline__ void ndp_block_sums(double (&v)[K], double* s_red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ndp_wave_sum(v[k]);
-  if constexpr (THREADS == 64) return;
-  constexpr int NW = THREADS / 64;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_red[k * NW + (threadIdx.x >> 6)] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += s_red[k * NW + w];
-    v[k] = t;
-  }
-}
-
-template <int THREADS>
-__device__ __forceinline__ double ndp_block_max(double v, double* s_red) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, WAVE));
-  if constexpr (THREADS == 64) return v;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < THREADS / 64; ++w) t = fmax(t, s_red[w]);
-  return t;
-}
-
 // largest eigenpair of a symmetric 3 x 3 matrix (cyclic Jacobi, fixed sweeps; every thread runs it on the same numbers)
 __device__ __forceinline__ void ndp_eig3_largest(double a[3][3], int dim, double& theta, double c[3]) {
   double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -322,7 +248,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
     vol_part += d;
     x[i] = (static_cast<double>(ndp_hash(0x5EEDull, static_cast<uint64_t>(i) + 977ull * n) >> 8) / 8388608.0) - 1.0;
   }
-  const double vol = ndp_block_sum<THREADS>(vol_part, s_red);
+  const double vol = block_fold_seq<THREADS>(vol_part, s_red, fold_rows{});
   __syncthreads();
   if (cached) {
     for (int i = tid; i <= n; i += THREADS) mptr[i] = indptr[p0 + i] - e_lo;
@@ -364,7 +290,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
     // x <- x / |x|, ax = Ls x, lambda = x . ax
     double sq = 0.0;
     for (int i = tid; i < n; i += THREADS) sq += x[i] * x[i];
-    const double x2 = ndp_block_sum<THREADS>(sq, s_red);
+    const double x2 = block_fold_seq<THREADS>(sq, s_red, fold_rows{});
     __syncthreads();
     {
       const double ix0 = ndp_rsqrt(x2);
@@ -374,7 +300,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
     matvec(x, ax);
     double dt = 0.0;
     for (int i = tid; i < n; i += THREADS) dt += x[i] * ax[i];
-    double lam = ndp_block_sum<THREADS>(dt, s_red);
+    double lam = block_fold_seq<THREADS>(dt, s_red, fold_rows{});
     // One step = three rounds of reductions (the basis {x, w, p} is orthonormalised with coefficients that ride
     // along with sums needed anyway, and |x| = 1 is restored together with the new Rayleigh quotient):
     //   A: |r|^2, x.p, r.p            r = Ls x - lambda x, w = r / |r|, p' = p - (x.p) x - (w.p) w
@@ -390,7 +316,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
         sa[1] += x[i] * pv[i];
         sa[2] += r * pv[i];
       }
-      ndp_block_sums<THREADS, 3>(sa, s_red);
+      block_fold_seq<THREADS>(sa, s_red, fold_rows{});
       const double rn2 = sa[0];
       if (!(rn2 > tol * tol * lam * lam)) break;  // |Ls x - lambda x| <= tol * lambda: converged
       const double inv_r = ndp_rsqrt(rn2);
@@ -415,7 +341,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
         sb[4] += wv[i] * api;
         sb[5] += pi * api;
       }
-      ndp_block_sums<THREADS, 6>(sb, s_red);
+      block_fold_seq<THREADS>(sb, s_red, fold_rows{});
       const int dim = (has_p && sb[0] > 1e-24) ? 3 : 2;  // p was unit length: what is left of it outside span{x, w}
       const double ip = dim == 3 ? ndp_rsqrt(sb[0]) : 0.0;
       double h[3][3] = {{lam, sb[1], sb[3] * ip}, {sb[1], sb[2], sb[4] * ip}, {sb[3] * ip, sb[4] * ip, sb[5] * ip * ip}};
@@ -437,7 +363,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
         sc[0] += xn * xn;
         sc[1] += xn * axn;
       }
-      ndp_block_sums<THREADS, 2>(sc, s_red);
+      block_fold_seq<THREADS>(sc, s_red, fold_rows{});
       const double ix = ndp_rsqrt(sc[0]);
       for (int i = tid; i < n; i += THREADS) {
         x[i] *= ix;
@@ -460,7 +386,7 @@ __global__ __launch_bounds__(THREADS) void ndp_partition_kernel(const int32_t* _
         if ((x[c - p0] >= 0.0) != zi) cross += w ? static_cast<double>(w[e]) : 1.0;
       }
     }
-    const double cut = ndp_block_sum<THREADS>(cross, s_red) / vol;
+    const double cut = block_fold_seq<THREADS>(cross, s_red, fold_rows{}) / vol;
     if (cut < 0.5) random_part = true;  // ndp_select.py:250-252
   }
   for (int i = tid; i < n; i += THREADS) {
@@ -520,7 +446,7 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
   }
   const float my_dis = deg > 0.0 ? static_cast<float>(1.0 / sqrt(deg)) : 0.f;
   if (on) dis[lane] = my_dis;
-  const double vol = ndp_wave_sum(deg);
+  const double vol = wave_sum_rows(deg);
   __builtin_amdgcn_wave_barrier();
   if (cached && on) {
     for (int e = e_beg; e < e_end; ++e) {
@@ -576,7 +502,7 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
   double x = on ? (static_cast<double>(ndp_hash(0x5EEDull, static_cast<uint64_t>(lane) + 977ull * n) >> 8) / 8388608.0) - 1.0
                 : 0.0;
   if (!random_part) {
-    const double x2 = ndp_wave_sum(x * x);
+    const double x2 = wave_sum_rows(x * x);
     x *= ndp_rsqrt(x2);
     if (warm) {
       // ---- r6: Lanczos warm start.  A LOBPCG step is ~5 k cycles of reductions and Rayleigh-Ritz around a 150-cycle
@@ -595,9 +521,9 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
         const int mmax = n < warm ? n : warm;
         for (int j = 0; j < mmax; ++j) {
           double u = matvec(v);
-          const double a = ndp_wave_sum(u * v);
+          const double a = wave_sum_rows(u * v);
           u = (u - a * v) - bprev * vp;
-          const double b2 = ndp_wave_sum(u * u);
+          const double b2 = wave_sum_rows(u * u);
           if (lane == j) ta = a;
           m = j + 1;
           if (!(b2 > 1e-26)) break;  // an invariant subspace: T is exact
@@ -613,10 +539,10 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
         for (int pass = 0; pass < 6; ++pass) {  // 2 / 65^6 = 3e-11: with the two inverse iterations below, enough
           const double step = (hi - lo) * (1.0 / 65.0);
           const double sig = lo + step * (lane + 1);
-          double d0 = 1.0, d1 = sig - ndp_readlane_f64(ta, 0);
+          double d0 = 1.0, d1 = sig - readlane(ta, 0);
           bool ok = d1 > 0.0;
           for (int j = 1; j < m; ++j) {
-            const double aj = ndp_readlane_f64(ta, j), bb = ndp_readlane_f64(tb2, j - 1);
+            const double aj = readlane(ta, j), bb = readlane(tb2, j - 1);
             const double d2 = (sig - aj) * d1 - bb * d0;
             d0 = d1;
             d1 = d2;
@@ -636,36 +562,36 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
           // z_j = b_j + b_{j-1} z_{j-1} / delta_{j-1};  y_{m-1} = z_{m-1} / delta_{m-1}, y_j = (z_j + b_j y_{j+1}) / delta_j
           double dprev_inv = 0.0, zprev = 0.0;
           for (int j = 0; j < m; ++j) {
-            const double aj = ndp_readlane_f64(ta, j), bjm = j ? ndp_readlane_f64(tb, j - 1) : 0.0;
+            const double aj = readlane(ta, j), bjm = j ? readlane(tb, j - 1) : 0.0;
             double dj = (sig - aj) - bjm * bjm * dprev_inv;
             if (!(dj > 1e-20)) dj = 1e-20;
-            const double zj = ndp_readlane_f64(yl, j) + bjm * zprev * dprev_inv;
+            const double zj = readlane(yl, j) + bjm * zprev * dprev_inv;
             dprev_inv = ndp_rcp(dj);
             zprev = zj;
             if (lane == j) { dinv = dprev_inv; zl = zj; }
           }
           double ynext = 0.0;
           for (int j = m - 1; j >= 0; --j) {
-            const double bj = j + 1 < m ? ndp_readlane_f64(tb, j) : 0.0;
-            const double yj = (ndp_readlane_f64(zl, j) + bj * ynext) * ndp_readlane_f64(dinv, j);
+            const double bj = j + 1 < m ? readlane(tb, j) : 0.0;
+            const double yj = (readlane(zl, j) + bj * ynext) * readlane(dinv, j);
             ynext = yj;
             if (lane == j) yl = yj;
           }
-          const double y2 = ndp_wave_sum(lane < m ? yl * yl : 0.0);
+          const double y2 = wave_sum_rows(lane < m ? yl * yl : 0.0);
           yl = lane < m ? yl * ndp_rsqrt(y2) : 0.0;
         }
         double v = x0, vp = 0.0, bprev = 0.0, xn = 0.0;
         for (int j = 0; j < m; ++j) {
-          xn += ndp_readlane_f64(yl, j) * v;
+          xn += readlane(yl, j) * v;
           if (j + 1 == m) break;
           double u = matvec(v);
-          u = (u - ndp_readlane_f64(ta, j) * v) - bprev * vp;
+          u = (u - readlane(ta, j) * v) - bprev * vp;
           vp = v;
-          v = u * ndp_readlane_f64(tib, j);
-          bprev = ndp_readlane_f64(tb, j);
+          v = u * readlane(tib, j);
+          bprev = readlane(tb, j);
         }
         double sn[2] = {xn * xn, xn * x0};
-        ndp_block_sums<64, 2>(sn, nullptr);
+        block_fold_seq<64>(sn, static_cast<double*>(nullptr), fold_rows{});
         if (sn[0] > 1e-200 && sn[0] < 1e200) {  // (else: keep the start vector; the loop below does the work as before)
           const double sc = ndp_rsqrt(sn[0]);
           x = xn * (sn[1] < 0.0 ? -sc : sc);  // the start vector's side, as the LOBPCG iterates keep it (c0 >= 0)
@@ -673,12 +599,12 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
       }
     }
     double ax = matvec(x), pv = 0.0, ap = 0.0;
-    double lam = ndp_wave_sum(x * ax);
+    double lam = wave_sum_rows(x * ax);
     bool has_p = false;
     for (; it < max_iter; ++it) {
       const double r = ax - lam * x;
       double sa[3] = {r * r, x * pv, r * pv};
-      ndp_block_sums<64, 3>(sa, nullptr);
+      block_fold_seq<64>(sa, static_cast<double*>(nullptr), fold_rows{});
       const double rn2 = sa[0];
       if (!(rn2 > tol * tol * lam * lam)) break;  // |Ls x - lambda x| <= tol * lambda: converged
       const double inv_r = ndp_rsqrt(rn2);
@@ -693,7 +619,7 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
         ap = 0.0;
       }
       double sb[6] = {pv * pv, x * aw, wv * aw, x * ap, wv * ap, pv * ap};
-      ndp_block_sums<64, 6>(sb, nullptr);
+      block_fold_seq<64>(sb, static_cast<double*>(nullptr), fold_rows{});
       const int dim = (has_p && sb[0] > 1e-24) ? 3 : 2;
       const double ip = dim == 3 ? ndp_rsqrt(sb[0]) : 0.0;
       const double h[3][3] = {{lam, sb[1], sb[3] * ip}, {sb[1], sb[2], sb[4] * ip}, {sb[3] * ip, sb[4] * ip, sb[5] * ip * ip}};
@@ -708,7 +634,7 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
       pv = pn * sp;
       ap = apn * sp;
       double sc[2] = {xn * xn, xn * axn};
-      ndp_block_sums<64, 2>(sc, nullptr);
+      block_fold_seq<64>(sc, static_cast<double*>(nullptr), fold_rows{});
       const double ix = ndp_rsqrt(sc[0]);
       x = xn * ix;
       ax = axn * ix;
@@ -727,7 +653,7 @@ __global__ __launch_bounds__(64) void ndp_partition_wave_kernel(const int32_t* _
       if (c < p0 || c >= p1) continue;
       if ((xs[c - p0] >= 0.0) != zi) cross += w ? static_cast<double>(w[e]) : 1.0;
     }
-    const double cut = ndp_wave_sum(cross) / vol;
+    const double cut = wave_sum_rows(cross) / vol;
     if (cut < 0.5) random_part = true;  // ndp_select.py:250-252
   }
   if (on) {
@@ -847,14 +773,14 @@ __device__ __forceinline__ double nl_hub_row(const int64_t* __restrict__ col, co
   }
   double sv[1] = {acc};
   __syncthreads();  // s_red may still be read by the previous row's tree
-  ndp_block_sums<NL_THREADS, 1>(sv, s_red);
+  block_fold_seq<NL_THREADS>(sv, s_red, fold_rows{});
   return sv[0];
 }
 
 template <int K>
 __device__ __forceinline__ void nl_store_partials(double (&v)[K], double* __restrict__ partial) {
   __shared__ double s_red[K * (NL_THREADS / 64)];
-  ndp_block_sums<NL_THREADS, K>(v, s_red);
+  block_fold_seq<NL_THREADS>(v, s_red, fold_rows{});
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) partial[blockIdx.x * 8 + k] = v[k];
@@ -872,7 +798,7 @@ __device__ __forceinline__ void nl_reduce_partials(const double* __restrict__ pa
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] += partial[b * 8 + k];
   }
-  ndp_block_sums<NL_THREADS, K>(v, s_red);
+  block_fold_seq<NL_THREADS>(v, s_red, fold_rows{});
 #pragma unroll
   for (int k = 0; k < K; ++k) out[k] = v[k];
 }
@@ -881,7 +807,7 @@ __device__ __forceinline__ void nl_reduce_partials(const double* __restrict__ pa
 template <int K, int STRIDE>
 __device__ __forceinline__ void nl_store_slots(double (&v)[K], double* __restrict__ partial) {
   __shared__ double s_red[K * (NL_THREADS / 64)];
-  ndp_block_sums<NL_THREADS, K>(v, s_red);
+  block_fold_seq<NL_THREADS>(v, s_red, fold_rows{});
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) partial[blockIdx.x * STRIDE + k] = v[k];
@@ -898,7 +824,7 @@ __device__ __forceinline__ void nl_reduce_slots(const double* __restrict__ parti
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] += partial[b * STRIDE + k];
   }
-  ndp_block_sums<NL_THREADS, K>(v, s_red);
+  block_fold_seq<NL_THREADS>(v, s_red, fold_rows{});
 #pragma unroll
   for (int k = 0; k < K; ++k) out[k] = v[k];
 }
@@ -994,7 +920,7 @@ __global__ __launch_bounds__(NL_THREADS) void nl_hub_setup_kernel(const int32_t*
       double sv[1] = {0.0};
       for (int e = a + static_cast<int>(threadIdx.x); e < b; e += NL_THREADS) sv[0] += static_cast<double>(w[e]);
       __syncthreads();
-      ndp_block_sums<NL_THREADS, 1>(sv, s_red);
+      block_fold_seq<NL_THREADS>(sv, s_red, fold_rows{});
       d = sv[0];
     }
     if (threadIdx.x == 0) {
@@ -1021,7 +947,7 @@ __global__ __launch_bounds__(NL_THREADS) void nl_init_reduce_kernel(NlVecs v, in
       hv[1] += v.hub_part[2 * h + 1];
     }
     __syncthreads();
-    ndp_block_sums<NL_THREADS, 2>(hv, s_hub);
+    block_fold_seq<NL_THREADS>(hv, s_hub, fold_rows{});
     s[0] += hv[0];
     s[1] += hv[1];
   }
@@ -1247,6 +1173,7 @@ __global__ __launch_bounds__(NL_THREADS) void nl_matvec_kernel(const int32_t* __
 #pragma unroll
     for (int u = 0; u < NL_U; ++u) {
       double a = acc[u];
+      // the order of wave_sum<NL_G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
       for (int o = NL_G / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, WAVE);
       const int64_t i = i0 + u * ngroups;

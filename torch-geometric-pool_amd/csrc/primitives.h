@@ -7,15 +7,6 @@
 namespace tgp {
 
 // ------------------------------------------------------------------ wave / block scans
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    uint32_t t = __shfl_up(v, d, WAVE);
-    if (lane_id() >= d) v += t;
-  }
-  return v;
-}
-
 // Exclusive scan over the 256 threads of a workgroup.  s_w: 4 words of LDS.
 __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* s_w, uint32_t* total) {
   const uint32_t inc = wave_incl_scan(v);

@@ -78,6 +78,7 @@ __global__ __launch_bounds__(256) void row_project2_kernel(const float* __restri
         }
       }
     }
+    // the order of wave_butterfly<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) {
       acc0 += __shfl_xor(acc0, off);

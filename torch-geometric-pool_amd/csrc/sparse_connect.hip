@@ -682,8 +682,7 @@ __global__ __launch_bounds__(256) void degree_stitch_kernel(const int64_t* __res
     float part = 0.f;
     if (lane < first_stop) part = head[mine];
     else if (lane == first_stop) part = tail[mine];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part = __fadd_rn(part, __shfl_xor(part, off));
+    part = wave_fold(part, op_fadd_rn{});
     acc = __fadd_rn(part, acc);
     if (stop) break;
     t -= 64;
@@ -761,6 +760,7 @@ __global__ __launch_bounds__(256) void graph_max_kernel(const int64_t* __restric
   const int64_t g0 = __shfl(g_cur, 0);
   const bool wave_uniform = __all(g_cur == g0 || g_cur < 0);
   if (wave_uniform) {
+    // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const uint32_t o = __shfl_xor(m_cur, off);
@@ -997,6 +997,7 @@ __global__ __launch_bounds__(256) void spmm_rows_vec4_kernel(const int32_t* __re
       *reinterpret_cast<float4*>(T + i * K + f) = acc;
     }
     if constexpr (STATS == 1) {
+      // the order of wave_sum<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
       for (int o = G / 2; o > 0; o >>= 1) qsum += __shfl_xor(qsum, o, 64);
       if (g == 0) {
@@ -1007,6 +1008,7 @@ __global__ __launch_bounds__(256) void spmm_rows_vec4_kernel(const int32_t* __re
   }
   if constexpr (STATS == 2) {
     __shared__ float s_e[4];
+    // the order of wave_sum (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) esum += __shfl_xor(esum, o, 64);
     if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6] = esum;

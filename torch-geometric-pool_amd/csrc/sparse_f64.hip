@@ -163,6 +163,7 @@ __global__ __launch_bounds__(256) void f64_post_dense_kernel(const double* __res
         double acc = 0.0;
 #pragma unroll 4
         for (int64_t c = lane; c < K; c += 64) acc += at(i, c);
+        // the shuffle-down ladder, distances 32 .. 1: lane 0 alone holds the sum (not the rounding of wave_sum)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
         if (lane == 0) d[i] = sqrt(fmax(acc, eps));

@@ -244,8 +244,8 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_pool_small_kernel(SpsArgs p
     const int64_t cl = ci - a0;  // one supernode per kept node, numbered graph-major: a permutation of the slice
     const bool okc = !act || (cl >= 0 && cl < ka);
     if (__any(!okv || !okc)) bad = true;
-    M = wave_or64((act && okv) ? 1ull << (v - n0) : 0ull);
-    const unsigned long long CM = wave_or64((act && okc) ? 1ull << cl : 0ull);
+    M = wave_or((act && okv) ? 1ull << (v - n0) : 0ull);
+    const unsigned long long CM = wave_or((act && okc) ? 1ull << cl : 0ull);
     if (__popcll(CM) != ka) bad = true;
     SPS_STAMP(2);
     // A5 + A6, pass 1: survivors of the graph (the predicate of utils/ops.py:370-380 on the induced subgraph)
@@ -282,8 +282,8 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_pool_small_kernel(SpsArgs p
     wj = (nact && p.weight) ? p.weight[n0 + lane] : 1.0f;
     int64_t pc = (q0 + lane < q1) ? p.cluster_index[q0 + lane] : -1;
     if (__any(nact && ni != n0 + lane)) bad = true;  // every node assigned, in node order (base_select.py:58)
-    cmin = wave_min64(nact ? cj : INT64_MAX);
-    const int64_t cmax = wave_max64(nact ? cj : -1);
+    cmin = wave_min(nact ? cj : INT64_MAX);
+    const int64_t cmax = wave_max(nact ? cj : -1);
     if (n > 0) {
       if (cmin < 0 || cmax >= p.K || cmax - cmin + 1 > 64) bad = true;
       else kc = static_cast<int>(cmax - cmin + 1);
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_pool_small_kernel(SpsArgs p
             pc = (r0 + lane < r1) ? p.cluster_index[r0 + lane] : -1;
           }
         }
-        want = wave_max64(pc) + 1;
+        want = wave_max(pc) + 1;
       }
       if (cmin != want) bad = true;
       if (n1 == p.N && cmax != p.K - 1) bad = true;
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_pool_small_kernel(SpsArgs p
   bool tile_refused = false;
   if (wv == 0) {  // the tile's count goes out first: successors only need this word
     const uint32_t mine = lane < WAVES ? s_cnt[lane] : 0u;
-    tile_tot = wave_sum32(mine & 0x7FFFFFFFu);
+    tile_tot = wave_sum(mine & 0x7FFFFFFFu);
     tile_refused = __any((mine >> 31) != 0u);
     if (lane == 0)
       sps_store(p.status + 2 + tile_id, p.tag | (tile_id == 0 ? SPS_PRE : SPS_AGG) |

@@ -60,12 +60,6 @@ __global__ __launch_bounds__(256) void topk_rank_kernel(const uint64_t* __restri
 // a graph's order gets supernode koff[g] + q if q < k[g] -- exactly what topk_rank_kernel writes.
 constexpr int kSegSortMax = 2048;
 
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
-  const unsigned lo = __shfl_xor(static_cast<unsigned>(v), mask, WAVE);
-  const unsigned hi = __shfl_xor(static_cast<unsigned>(v >> 32), mask, WAVE);
-  return (static_cast<unsigned long long>(hi) << 32) | lo;
-}
-
 __global__ __launch_bounds__(256) void topk_segsort_wave_kernel(const float* __restrict__ score,
                                                                 const int64_t* __restrict__ ptr,
                                                                 const int64_t* __restrict__ k,
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void topk_segsort_wave_kernel(const float* __r
   for (int size = 2; size <= 64; size <<= 1) {
 #pragma unroll
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      const unsigned long long o = shfl_xor_u64(v, stride);
+      const unsigned long long o = __shfl_xor(v, stride, WAVE);
       const bool up = (lane & size) == 0;          // ascending block
       const bool lower = (lane & stride) == 0;     // this lane keeps the smaller of the pair in an ascending block
       const bool take_min = up == lower;
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void topk_segsort_wave_fill_kernel(
   for (int size = 2; size <= 64; size <<= 1) {
 #pragma unroll
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      const unsigned long long o = shfl_xor_u64(v, stride);
+      const unsigned long long o = __shfl_xor(v, stride, WAVE);
       const bool up = (lane & size) == 0;
       const bool lower = (lane & stride) == 0;
       const bool take_min = up == lower;
@@ -364,8 +358,7 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* __restrict__ 
     for (int k = (VEC ? sub * 4 : sub) + MAXC * STEP; k < F; k += STEP)
 #pragma unroll
       for (int j = 0; j < (VEC ? 4 : 1); ++j) sq = fmaf(w[k + j], w[k + j], sq);
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+    sq = wave_sum<G>(sq);
     nrm = sqrtf(sq);
   }
   for (int64_t base = wave * PER_WAVE; base < n; base += nwaves * PER_WAVE) {
@@ -390,6 +383,7 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* __restrict__ 
         for (int j = 0; j < (VEC ? 4 : 1); ++j) acc = fmaf(a[k + j], w[k + j], acc);
       }
     }
+    // the order of wave_sum<G> (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (post) {
@@ -519,8 +513,7 @@ __global__ __launch_bounds__(256) void topk_pool_bwd_kernel(TopkPoolBwdArgs p) {
     sq = fmaf(wr[j].x, wr[j].x, sq); sq = fmaf(wr[j].y, wr[j].y, sq);
     sq = fmaf(wr[j].z, wr[j].z, sq); sq = fmaf(wr[j].w, wr[j].w, sq);
   }
-#pragma unroll
-  for (int off = 4; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+  sq = wave_sum<8>(sq);
   const float inv = 1.f / sqrtf(sq);
   float4 acc[CPL];
 #pragma unroll
@@ -563,11 +556,10 @@ __global__ __launch_bounds__(256) void topk_pool_bwd_kernel(TopkPoolBwdArgs p) {
         d2 = fmaf(xr[u][j].x, wr[j].x, d2); d2 = fmaf(xr[u][j].y, wr[j].y, d2);
         d2 = fmaf(xr[u][j].z, wr[j].z, d2); d2 = fmaf(xr[u][j].w, wr[j].w, d2);
       }
-#pragma unroll
-      for (int off = 4; off > 0; off >>= 1) {
-        d1 += __shfl_xor(d1, off);
-        d2 += __shfl_xor(d2, off);
-      }
+      wave_butterfly<8>([&](auto peer) {
+        d1 += peer(d1);
+        d2 += peer(d2);
+      });
       const float gv = ge[u] + d1;
       const float gt = p.use_tanh ? gv * (1.f - sv[u] * sv[u]) : gv;
       const float gtn = ok[u] ? gt * inv : 0.f;
@@ -588,7 +580,8 @@ __global__ __launch_bounds__(256) void topk_pool_bwd_kernel(TopkPoolBwdArgs p) {
     }
   }
   if (!p.part) return;
-  // the wave's eight lane groups (lane bits 3..5), then the four waves in wave order
+  // the wave's eight lane groups (lane bits 3..5), then the four waves in wave order; the butterfly goes UP here, offsets
+  // 8, 16, 32 (not wave_butterfly, which goes down)
 #pragma unroll
   for (int off = 8; off < 64; off <<= 1) {
     accc += __shfl_xor(accc, off);
@@ -643,8 +636,7 @@ __global__ __launch_bounds__(512) void topk_pool_bwd_final_kernel(const float* _
   if (q == 0) {
     float sq = 0.f;
     for (int f = lane; f < F; f += 64) sq = fmaf(w[f], w[f], sq);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+    sq = wave_sum(sq);
     if (lane == 0) s_inv = 1.f / sqrtf(sq);
   }
   __syncthreads();
@@ -690,6 +682,7 @@ __global__ __launch_bounds__(1024) void topk_plan_kernel(const int64_t* __restri
       k[g] = v;
     }
     long long inc = v;  // inclusive scan over the wave
+    // the order of wave_incl_scan (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
       const long long o = __shfl_up(inc, off, WAVE);
@@ -744,23 +737,6 @@ static TopkLayout topk_layout(void* ws, int64_t n) {
 // in ascending node order (nonzero()).  One workgroup per graph of the sorted batch walks its nodes three times (max,
 // sum of exponentials, probabilities + keep flags; the scores stay in L2): batches of small graphs are one launch,
 // a single large graph is one workgroup's stream.  Sums are taken in a fixed order (strided partial sums, then waves).
-__device__ __forceinline__ float ms_block_max(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float ms_block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 __global__ __launch_bounds__(256) void topk_minscore_kernel(const float* __restrict__ score,
                                                             const int64_t* __restrict__ ptr, float min_score,
                                                             float tol, float* __restrict__ prob,
@@ -775,10 +751,10 @@ __global__ __launch_bounds__(256) void topk_minscore_kernel(const float* __restr
   }
   float mx = -INFINITY;
   for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) mx = fmaxf(mx, score[i]);
-  mx = ms_block_max(mx, sh);
+  mx = block_fold_pair256<false>(mx, sh, op_max{});
   float sum = 0.f;
   for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) sum += expf(score[i] - mx);
-  sum = ms_block_sum(sum, sh);
+  sum = block_fold_pair256<false>(sum, sh, op_add{});
   const float den = sum + 1e-16f;
   const float floor_ = fminf(1.0f / den - tol, min_score);  // max probability = exp(0) / den
   uint32_t mine = 0;
@@ -789,7 +765,7 @@ __global__ __launch_bounds__(256) void topk_minscore_kernel(const float* __restr
     keep[i] = k ? 1 : 0;
     mine += k ? 1u : 0u;
   }
-  const float total = ms_block_sum(static_cast<float>(mine), sh);  // (< 2^24 per graph: exact; larger graphs below)
+  const float total = block_fold_pair256<false>(static_cast<float>(mine), sh, op_add{});  // (< 2^24 per graph: exact; larger graphs below)
   if (p1 - p0 < (1 << 24)) {
     if (threadIdx.x == 0) counts[g] = static_cast<uint32_t>(total);
   } else {
