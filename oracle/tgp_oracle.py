@@ -93,7 +93,9 @@ def topk_perm(score: Tensor, ratio, batch: Tensor, min_score=None, tol=1e-7) -> 
         k = torch.minimum(torch.full_like(n_per, int(ratio)), n_per)
     else:
         k = (float(ratio) * n_per.to(score.dtype)).ceil().to(torch.long)
-    _, order = torch.sort(score.view(-1), descending=True)
+    # PyG sorts with stable=False, which leaves the order inside a tie (equal scores, several NaN) open; the stable
+    # order -- lower node id first -- is one of the outcomes it allows and the one the native selection defines
+    _, order = torch.sort(score.view(-1), descending=True, stable=True)
     b_sorted, b_perm = torch.sort(batch[order], stable=True)
     ptr = counts_to_ptr(n_per)
     rank_in_graph = torch.arange(score.numel()) - ptr[b_sorted]

@@ -328,3 +328,101 @@ def test_get_assignments_and_assign_all_nodes(golden):
     with pytest.raises(AssertionError):
         small.assign_all_nodes(adj=None)
     assert small.assign_all_nodes(adj=ei) is not small and out.assign_all_nodes(adj=ei) is out  # all kept: unchanged
+
+
+# --------------------------------------------------------------------- golden: non-finite inputs
+@pytest.fixture(scope="module")
+def golden_nonfinite():
+    """tests/golden/golden_nonfinite_v1.pt: the reference's own code on inputs that hold a NaN, an infinity or both
+    infinities in one reduction (tests/golden/make_golden_nonfinite.py)."""
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_nonfinite_v1.pt")
+    blob = torch.load(path, weights_only=True)
+    assert blob["tgp_version"] == "1.0.1" and len(blob["cases"]) == 12
+    return blob["cases"]
+
+
+def same(got, want, msg):
+    """Equal NaN masks, equal infinities with sign, the rest at this file's tolerance; integer tensors bit-exact."""
+    from nonfinite import assert_same_nonfinite
+    assert got.dtype == want.dtype, f"{msg}: {got.dtype} vs {want.dtype}"
+    assert_same_nonfinite(got, want, msg, rtol=RTOL, atol=ATOL)
+
+
+def test_golden_nonfinite_holds_what_it_is_for(golden_nonfinite):
+    """The fixture really contains the cases the kernels' tests lean on (a regenerated file that lost them fails)."""
+    g = golden_nonfinite
+    for op in ("min", "max"):  # a NaN merged with finite duplicates removes the edge (0, 1); the lone NaN removes (1, 0)
+        ei = g[f"connect_{op}"]["expected"]["plain_ei"]
+        assert not bool(((ei[0] == 0) & (ei[1] == 1)).any()) and not bool(((ei[0] == 1) & (ei[1] == 0)).any())
+    assert bool(torch.isinf(g["connect_sum"]["expected"]["plain_ew"]).any())
+    for name in ("mincut", "ortho", "link", "link_normalized", "entropy", "sparse_mincut", "unbatched_ortho",
+                 "sparse_link", "unbatched_entropy"):
+        assert bool(torch.isnan(g["losses_nan_in_s"]["expected"][name])), name
+    e = g["losses_inf_in_adj"]["expected"]
+    assert float(e["link"]) == float("inf") and float(e["sparse_link"]) == float("inf") and bool(torch.isfinite(e["ortho"]))
+    e = g["postprocess_dense"]["expected"]
+    assert bool(torch.isnan(e["rsl0_dn1_at0_ewn0"][1, 2]).all())       # the inf - inf row is NaN: clamp keeps a NaN
+    assert bool(torch.isnan(e["rsl0_dn0_at0_ewn1"][0]).all())          # a NaN entry makes its graph's maximum NaN
+    assert bool(torch.isfinite(e["rsl0_dn1_at0_ewn0"][2]).all())       # a negative row sum is clamped, nothing else
+    assert bool(torch.isnan(g["topk_ratio_half"]["expected"]["weight"]).any())
+
+
+@pytest.mark.parametrize("op", ["sum", "mean", "min", "max", "mul"])
+def test_golden_nonfinite_connect(golden_nonfinite, op):
+    c = golden_nonfinite[f"connect_{op}"]
+    i, e = c["inputs"], c["expected"]
+    for tag, flags in (("plain", (False, False, False)), ("flags", (True, True, True))):
+        rsl, dn, ewn = flags
+        ei, ew = O.sparse_connect(i["edge_index"], i["edge_weight"], torch.arange(8), i["cluster_index"], 8,
+                                  i["num_supernodes"], remove_self_loops=rsl, reduce_op=op, edge_weight_norm=ewn,
+                                  batch_pooled=i["batch_pooled"], degree_norm=dn)
+        exact(ei, e[tag + "_ei"], f"{op}.{tag}.edge_index")
+        same(ew, e[tag + "_ew"], f"{op}.{tag}.edge_weight")
+
+
+def test_golden_nonfinite_postprocess(golden_nonfinite):
+    c = golden_nonfinite["postprocess_dense"]
+    assert len(c["expected"]) == 16
+    for key, val in c["expected"].items():
+        f = {p[:-1]: bool(int(p[-1])) for p in key.split("_")}
+        same(O.postprocess_dense(c["inputs"]["adj_pool"], f["rsl"], f["dn"], f["at"], f["ewn"]), val, key)
+    c = golden_nonfinite["postprocess_sparse"]
+    i, e = c["inputs"], c["expected"]
+    keys = [k[:-3] for k in e if k.endswith("_ei")]
+    assert len(keys) == 8
+    for key in keys:
+        f = {p[:-1]: bool(int(p[-1])) for p in key.split("_")}
+        ei, ew = O.postprocess_sparse(i["edge_index"], i["edge_weight"], i["num_nodes"], f["rsl"], f["dn"], f["ewn"],
+                                      i["batch_pooled"])
+        exact(ei, e[key + "_ei"], key)
+        same(ew, e[key + "_ew"], key)
+
+
+@pytest.mark.parametrize("tag", ["nan_in_s", "inf_in_adj"])
+def test_golden_nonfinite_losses(golden_nonfinite, tag):
+    c = golden_nonfinite[f"losses_{tag}"]
+    i, e = c["inputs"], c["expected"]
+    s, a, ei, ew, batch = i["s"], i["adj"], i["edge_index"], i["edge_weight"], i["batch"]
+    sf = s.reshape(-1, s.size(-1))
+    got = {"mincut": O.mincut_loss(a, s, O.dense_connect(s, a)), "ortho": O.orthogonality_loss(s),
+           "link": O.link_pred_loss(s, a, False), "link_normalized": O.link_pred_loss(s, a, True),
+           "entropy": O.entropy_loss(s, sf.size(0)), "sparse_mincut": O.sparse_mincut_loss(ei, sf, ew, batch),
+           "unbatched_ortho": O.unbatched_orthogonality_loss(sf, batch),
+           "sparse_link": O.sparse_link_pred_loss(sf, ei, ew, batch, False),
+           "unbatched_entropy": O.entropy_loss(sf, sf.size(0))}
+    assert set(got) == set(e)
+    for name, val in e.items():
+        same(got[name], val, f"{tag}.{name}")
+
+
+@pytest.mark.parametrize("tag", ["ratio_half", "ratio_two", "min_score"])
+def test_golden_nonfinite_topk(golden_nonfinite, tag):
+    c = golden_nonfinite[f"topk_{tag}"]
+    i, e = c["inputs"], c["expected"]
+    ni, ci, w = O.topk_select(i["score"], None, c["cfg"].get("ratio", 0.5), i["batch"], c["cfg"].get("min_score"),
+                              act="linear")
+    assert ni.numel() == e["num_supernodes"]
+    exact(ni, e["node_index"], tag + ".node_index")
+    exact(ci, e["cluster_index"], tag + ".cluster_index")
+    same(w, e["weight"], tag + ".weight")

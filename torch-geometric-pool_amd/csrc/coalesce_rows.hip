@@ -296,8 +296,8 @@ __device__ __forceinline__ uint32_t xor_lane(uint32_t v) {
 
 __device__ __forceinline__ float cr_reduce(float acc, float v, int op) {
   switch (op) {
-    case TGP_MIN: return fminf(acc, v);
-    case TGP_MAX: return fmaxf(acc, v);
+    case TGP_MIN: return nan_min(acc, v);
+    case TGP_MAX: return nan_max(acc, v);
     case TGP_MUL: return __fmul_rn(acc, v);
     default: return __fadd_rn(acc, v);
   }
@@ -305,8 +305,8 @@ __device__ __forceinline__ float cr_reduce(float acc, float v, int op) {
 // float64 edge weights (r5): the row-local routes merge in double, as the reference's coalesce does for a double tensor
 __device__ __forceinline__ double cr_reduce(double acc, double v, int op) {
   switch (op) {
-    case TGP_MIN: return fmin(acc, v);
-    case TGP_MAX: return fmax(acc, v);
+    case TGP_MIN: return nan_min(acc, v);
+    case TGP_MAX: return nan_max(acc, v);
     case TGP_MUL: return __dmul_rn(acc, v);
     default: return __dadd_rn(acc, v);
   }

@@ -639,7 +639,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
         c = s_d[t];
       }
       s_gs[t] = c >= eps ? 1.f : 0.f;  // clamp(min = eps) passes the gradient where c >= eps
-      s_d[t] = sqrtf(fmaxf(c, eps));
+      s_d[t] = sqrtf(clamp_min(c, eps));
     }
     __syncthreads();
     cacc[0] = cacc[1] = 0.f;
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(IN_LDS ? 1024 : 256) void post_bwd_kernel(const flo
   for (int t = tid; t < K; t += T) {
     const float c = s_d[t];
     s_gs[t] = c >= eps ? 1.f : 0.f;  // clamp(min = eps) passes the gradient where c >= eps
-    s_d[t] = sqrtf(fmaxf(c, eps));
+    s_d[t] = sqrtf(clamp_min(c, eps));
   }
   __syncthreads();
   auto pdiv = [&](int i, int j) -> float {  // the forward's P_ij, same arithmetic

@@ -69,7 +69,7 @@ __device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 // error ~2e-7; -inf and anything below 2^-150 give 0)
 __device__ __forceinline__ float sg_exp_neg(float x) {
   const float L = 1.44269504088896341f, Llo = 1.92596299112661746e-8f;
-  x = fmaxf(x, -104.f);
+  x = nan_max(x, -104.f);  // (a NaN stays: torch.softmax gives a NaN row)
   const float y = x * L;
   float r = fmaf(x, L, -y);
   r = fmaf(x, Llo, r);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
         //  four DPP moves and an LDS swizzle each)
         float mx[16], ex[16], sm[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mx[r] = wave_half_fold(z[r], op_max{});
+        for (int r = 0; r < 16; ++r) mx[r] = wave_half_fold(z[r], op_max{});  // (a NaN logit reaches sm[] through sg_exp_neg)
 #pragma unroll
         for (int r = 0; r < 16; ++r) ex[r] = sg_exp_neg(z[r] - mx[r]);
 #pragma unroll
@@ -459,6 +459,11 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
             if (rho(r) + 4 * lk == lm) aa[r] = 0.f;
         }
         if (p.flags & TGP_DEGREE_NORM) {
+          // rows / columns beyond K are products with the zero padding of S: exact zeros, unless A S holds an infinity
+          // (0 * inf = NaN).  The degree sums below run over all 32: take the padding out by index.
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (lm >= K || rho(r) + 4 * lk >= K) aa[r] = 0.f;
           float dcol;  // degree of index `lm`, identical on both half-waves
           if (p.flags & TGP_SUM_AXIS_ROWS) {  // sum over rows (axis -2): per-lane column sum
             float s = 0.f;
@@ -485,7 +490,7 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
             for (int r = 0; r < 16; ++r) own |= (rho(r) + 4 * lk == lm);
             dcol = own ? mine : other;
           }
-          const float d = sqrtf(fmaxf(dcol, p.eps));  // d[lm]
+          const float d = sqrtf(clamp_min(dcol, p.eps));  // d[lm]
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int row = rho(r) + 4 * lk;
@@ -499,8 +504,8 @@ __global__ __launch_bounds__(64 * SG_WAVES, 2) void dense_pool_small_kernel(Smal
           float m = 0.f;
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (lm < K && rho(r) + 4 * lk < K) m = fmaxf(m, fabsf(aa[r]));
-          m = wave_max(m);
+            if (lm < K && rho(r) + 4 * lk < K) m = nan_max(m, fabsf(aa[r]));
+          m = wave_nanmax(m);
           if (m == 0.f) m = 1.f;
 #pragma unroll
           for (int r = 0; r < 16; ++r) aa[r] = aa[r] / m;
@@ -768,7 +773,7 @@ __global__ __launch_bounds__(64 * SG_WAVES) void dense_pool_small_bwd_kernel(Sma
         for (int r = 0; r < 16; ++r) own |= (rho(r) + 4 * lk == lm);
         dcol = own ? mine : other;
       }
-      const float d = sqrtf(fmaxf(dcol, p.eps));
+      const float d = sqrtf(clamp_min(dcol, p.eps));
       const bool pass = dcol >= p.eps;  // clamp(min = eps) lets the gradient through where the sum is not below eps
       float qv[16], colq = 0.f, rowmine = 0.f;
 #pragma unroll
@@ -1178,7 +1183,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void dense_pool_medium_kernel(Med
     if (tid < K) {
       float t = 0.f;
       for (int q = 0; q < K; ++q) t = __fadd_rn(t, rows ? Rs[q * (KP + 1) + tid] : Rs[tid * (KP + 1) + q]);
-      ds[tid] = sqrtf(fmaxf(t, p.eps));
+      ds[tid] = sqrtf(clamp_min(t, p.eps));
     }
     __syncthreads();
     for (int e = tid; e < K * KP; e += NT) {
@@ -1195,17 +1200,17 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void dense_pool_medium_kernel(Med
     float m = 0.f;
     for (int e = tid; e < K * KP; e += NT) {
       const int i = e / KP, j = e % KP;
-      if (j < K) m = fmaxf(m, fabsf(Rs[i * (KP + 1) + j]));
+      if (j < K) m = nan_max(m, fabsf(Rs[i * (KP + 1) + j]));
     }
-    // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
+    // the order of wave_nanmax (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, WAVE));
+    for (int d = 32; d > 0; d >>= 1) m = nan_max(m, __shfl_xor(m, d, WAVE));
     __syncthreads();
     if (lane == 0) ds[w] = m;
     __syncthreads();
     scale = 0.f;
 #pragma unroll
-    for (int q = 0; q < WAVES; ++q) scale = fmaxf(scale, ds[q]);
+    for (int q = 0; q < WAVES; ++q) scale = nan_max(scale, ds[q]);
     if (scale == 0.f) scale = 1.f;
   }
   for (int e = tid; e < K * KP; e += NT) {

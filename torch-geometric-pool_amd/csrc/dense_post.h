@@ -90,7 +90,7 @@ __global__ __launch_bounds__(1024) void post_degree_kernel(PostArgs p) {
       float t = 0.f;
 #pragma unroll
       for (int q = 0; q < 16; ++q) t = __fadd_rn(t, s_part[q][lane]);
-      p.dvec[static_cast<long>(b) * K + j] = sqrtf(fmaxf(t, p.eps));  // sqrt(clamp(d, eps)): ops.py:318
+      p.dvec[static_cast<long>(b) * K + j] = sqrtf(clamp_min(t, p.eps));  // sqrt(clamp(d, eps)): ops.py:318
     }
   } else {
     for (int r = w; r < 64; r += 16) {
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(1024) void post_degree_kernel(PostArgs p) {
       // the shuffle-down ladder, distances 32 .. 1: lane 0 alone holds the result, and not in the rounding of wave_fold
 #pragma unroll
       for (int d = 32; d > 0; d >>= 1) s = __fadd_rn(s, __shfl_down(s, d, WAVE));
-      if (lane == 0) p.dvec[static_cast<long>(b) * K + i] = sqrtf(fmaxf(s, p.eps));
+      if (lane == 0) p.dvec[static_cast<long>(b) * K + i] = sqrtf(clamp_min(s, p.eps));
     }
   }
 }
@@ -127,18 +127,18 @@ __global__ __launch_bounds__(256) void post_scale_kernel(PostArgs p) {
         v = by_cols ? (v / dj) / di : (v / di) / dj;
         row[j] = v;
       }
-      mx = fmaxf(mx, fabsf(v));
+      mx = nan_max(mx, fabsf(v));
     }
   }
   if (p.flags & TGP_EDGE_WEIGHT_NORM) {
     // the shuffle-down ladder (as post_degree_kernel): lane 0 alone holds the maximum
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_down(mx, d, WAVE));
+    for (int d = 32; d > 0; d >>= 1) mx = nan_max(mx, __shfl_down(mx, d, WAVE));
     if (lane_id() == 0) s_max[wave_id()] = mx;
     __syncthreads();
     if (tid == 0)
       p.maxpart[static_cast<long>(b) * POST_BLOCKS + blockIdx.x] =
-          fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+          nan_max(nan_max(s_max[0], s_max[1]), nan_max(s_max[2], s_max[3]));
   }
 }
 
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void post_maxnorm_kernel(PostArgs p) {
   const int b = blockIdx.y, K = p.K, tid = threadIdx.x;
   float m = 0.f;
 #pragma unroll
-  for (int q = 0; q < POST_BLOCKS; ++q) m = fmaxf(m, p.maxpart[static_cast<long>(b) * POST_BLOCKS + q]);
+  for (int q = 0; q < POST_BLOCKS; ++q) m = nan_max(m, p.maxpart[static_cast<long>(b) * POST_BLOCKS + q]);
   if (m == 0.f) m = 1.f;
   float* a = p.dst + static_cast<long>(b) * K * K;
   const long kk = static_cast<long>(K) * K;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void post_small_kernel(PostArgs p, int B) {
           mine = __fadd_rn(mine, t);
         }
     }
-    d = sqrtf(fmaxf(mine, p.eps));  // d[lane]
+    d = sqrtf(clamp_min(mine, p.eps));  // d[lane]
   }
   const bool by_cols = p.flags & TGP_SUM_AXIS_ROWS;
   float m = 0.f;
@@ -207,13 +207,13 @@ __global__ __launch_bounds__(256) void post_small_kernel(PostArgs p, int B) {
         t = by_cols ? (t / d) / di : (t / di) / d;
         dstb[i * K + lane] = t;
       }
-      m = fmaxf(m, fabsf(t));
+      m = nan_max(m, fabsf(t));
     }
   }
   if (p.flags & TGP_EDGE_WEIGHT_NORM) {
-    // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
+    // the order of wave_nanmax (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
-    for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, WAVE));
+    for (int s = 32; s > 0; s >>= 1) m = nan_max(m, __shfl_xor(m, s, WAVE));
     if (m == 0.f) m = 1.f;
     if (col_ok)
       for (int i = 0; i < K; ++i) dstb[i * K + lane] = dstb[i * K + lane] / m;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void post_tiny_kernel(PostArgs p, int B) {
 #pragma unroll
     for (int j = 0; j < 32; ++j) sum = __fadd_rn(sum, t[j]);  // lanes < 32: column sums; >= 32: row sums
     const bool by_cols = p.flags & TGP_SUM_AXIS_ROWS;
-    const float d = sqrtf(fmaxf(__shfl(sum, by_cols ? idx : 32 + idx, WAVE), p.eps));  // d[idx] on every lane
+    const float d = sqrtf(clamp_min(__shfl(sum, by_cols ? idx : 32 + idx, WAVE), p.eps));  // d[idx] on every lane
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
       const float dj = __shfl(d, j, WAVE);
@@ -271,8 +271,8 @@ __global__ __launch_bounds__(256) void post_tiny_kernel(PostArgs p, int B) {
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j)
-      if (!hi && ok && j < K) m = fmaxf(m, fabsf(t[j]));
-    m = wave_max(m);
+      if (!hi && ok && j < K) m = nan_max(m, fabsf(t[j]));
+    m = wave_nanmax(m);
     if (m == 0.f) m = 1.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) t[j] = t[j] / m;
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(1024) void post_lds_kernel(PostArgs p, int B, XComb
           float t = 0.f;
 #pragma unroll
           for (int q = 0; q < 16; ++q) t = __fadd_rn(t, s_part[q * 64 + lane]);
-          dv[j] = sqrtf(fmaxf(t, p.eps));
+          dv[j] = sqrtf(clamp_min(t, p.eps));
         }
         __syncthreads();
       }
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(1024) void post_lds_kernel(PostArgs p, int B, XComb
         // the shuffle-down ladder of post_degree_kernel (the same bits)
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) sacc = __fadd_rn(sacc, __shfl_down(sacc, d, WAVE));
-        if (lane == 0) dv[i] = sqrtf(fmaxf(sacc, p.eps));
+        if (lane == 0) dv[i] = sqrtf(clamp_min(sacc, p.eps));
       }
       __syncthreads();
     }
@@ -419,21 +419,21 @@ __global__ __launch_bounds__(1024) void post_lds_kernel(PostArgs p, int B, XComb
       }
     }
     if (ewn) {
-      mx = fmaxf(fmaxf(mx, fmaxf(fabsf(t.x), fabsf(t.y))), fmaxf(fabsf(t.z), fabsf(t.w)));
+      mx = nan_max(nan_max(mx, nan_max(fabsf(t.x), fabsf(t.y))), nan_max(fabsf(t.z), fabsf(t.w)));
       *reinterpret_cast<float4*>(m + e) = t;
     } else {
       *reinterpret_cast<float4*>(dstb + e) = t;
     }
   }
   if (!ewn) return;
-  // the order of wave_max (wave.h), written out: a call here changes the kernel's instruction stream
+  // the order of wave_nanmax (wave.h), written out: a call here changes the kernel's instruction stream
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, WAVE));
+  for (int d = 32; d > 0; d >>= 1) mx = nan_max(mx, __shfl_xor(mx, d, WAVE));
   if (lane == 0) s_max[w] = mx;
   __syncthreads();
   float gm = 0.f;
 #pragma unroll
-  for (int q = 0; q < 16; ++q) gm = fmaxf(gm, s_max[q]);
+  for (int q = 0; q < 16; ++q) gm = nan_max(gm, s_max[q]);
   if (gm == 0.f) gm = 1.f;
   for (int e = tid * 4; e < kk; e += 4096) {
     float4 t = *reinterpret_cast<const float4*>(m + e);
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(512) void post_rows_kernel(PostRowsArgs p) {
 #pragma unroll
       for (int qq = 0; qq < 2 * PR_MAX_SPLITS; ++qq)
         if (qq < parts) c = __fadd_rn(c, pv[qq]);
-      s_d[j] = sqrtf(fmaxf(c, p.eps));
+      s_d[j] = sqrtf(clamp_min(c, p.eps));
     }
   }
   __syncthreads();

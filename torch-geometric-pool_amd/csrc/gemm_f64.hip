@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void dense64_post_rows_kernel(const double* __
       const double* cp = colpart + static_cast<long>(b) * nb * K + j;
       double c = 0.0;
       for (int q = 0; q < nb; ++q) c += cp[static_cast<long>(q) * K];
-      s_d64[j] = sqrt(fmax(c, eps));
+      s_d64[j] = sqrt(clamp_min(c, eps));
     }
   }
   __syncthreads();

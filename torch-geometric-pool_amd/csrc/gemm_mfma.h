@@ -802,6 +802,16 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     // column sums of this tile (rows beyond M are zero: the operands were zero-filled): registers in order, the two
     // half-waves, then the row waves in order through LDS (the k-loop's last barrier has passed: smem is free)
     if (g.colsum && which == 0) {  // (workgroup-uniform)
+      // ... exact zeros unless the other operand holds an infinity: 0 * inf = NaN.  A tile that reaches beyond M (workgroup-
+      // uniform; C is stored by now) clears those rows first, so that a NaN of the padding stays out of the degrees
+      if (m0 + BM > M) {
+        const int rows_left = M - (m0 + wm * 32 + 4 * lk);  // row offset of the first row beyond M
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((r & 3) + 8 * (r >> 2) >= rows_left) acc[j][r] = 0.f;
+      }
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         float cs = 0.f;

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void gm_symmetrise_kernel(const int32_t* __res
     for (int32_t t = lo; t < hi; ++t)
       if (nbr[t] == i) { q = t; break; }
   if (q < 0) nbr[p] = -1;
-  else wt[p] = fmaxf(wt[p], wt[q]);
+  else wt[p] = fmaxf(wt[p], wt[q]);  // (fmaxf: Graclus's own rule, not torch's -- a NaN direction loses to a real weight)
 }
 
 constexpr int GM_LONG_ROW = 256;  // rows beyond this many entries are scanned by whole waves (see gm_best_neighbour_wave)
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(GF_WAVES * 64) void gm_graph_fused_kernel(GfArgs p)
           for (int t = lo; t < hi; ++t)
             if (L.nbr[t] == i) { q = t; break; }
         drop[k] = q < 0;
-        if (q >= 0) nw[k] = fmaxf(w, L.wt[q]);
+        if (q >= 0) nw[k] = fmaxf(w, L.wt[q]);  // (fmaxf: as gm_symmetrise_kernel, a NaN direction loses)
       }
     }
   }

@@ -648,6 +648,15 @@ __global__ __launch_bounds__(T) void graph_trace_gsq_kernel(const float* __restr
   if (threadIdx.x == 0) { stats[2 * b] = tr; stats[2 * b + 1] = sq; }
 }
 
+// |A - S S^T|_F^2 from its expansion a2 - 2 tr + gs (a2 = sum of A^2, tr = trace(S^T A S), gs = |S^T S|_F^2), clamped at 0
+// as Tensor.clamp does: a NaN (a NaN anywhere in S or A) falls through, where fmaxf(NaN, 0) made the loss 0.  An infinite
+// entry of A makes a2 AND tr infinite; the reference's residual holds an infinity and no NaN there, its norm is +inf
+// (utils/losses.py:644-652, and 661-708 for the sparse form), so the expansion's inf - inf is not formed.
+__device__ __forceinline__ float link_residual_sq(float a2, float tr, float gs) {
+  if (a2 == INFINITY && fabsf(gs) < INFINITY) return INFINITY;
+  return clamp_min((a2 - 2.0f * tr) + gs, 0.f);
+}
+
 // out[0] = sqrt(max(sw2 - 2 sum_b trace_b + sum_b gsq_b, 0)) * link_scale, out[1] = (sum of the entropy partials) * ent_scale
 __global__ __launch_bounds__(256) void diffpool_u_final_kernel(const float* __restrict__ stats, int B,
                                                                const float* __restrict__ sw2_dev, float sw2_host,
@@ -662,7 +671,7 @@ __global__ __launch_bounds__(256) void diffpool_u_final_kernel(const float* __re
   e = block_sum<256>(e, sh);
   if (threadIdx.x == 0) {
     const float sw2 = sw2_dev ? sw2_dev[0] : sw2_host;
-    out[0] = sqrtf(fmaxf((sw2 - 2.0f * tr) + gs, 0.f)) * link_scale;
+    out[0] = sqrtf(link_residual_sq(sw2, tr, gs)) * link_scale;
     out[1] = e * ent_scale;
   }
 }
@@ -685,7 +694,7 @@ __global__ __launch_bounds__(256) void diffpool_stats_tail_kernel(const float* _
   fro = block_sum<256>(fro, sh);
   ent = block_sum<256>(ent, sh);
   if (threadIdx.x == 0) {
-    out[0] = sqrtf(fmaxf((a2 - 2.0f * tr) + fro, 0.f)) * link_scale;
+    out[0] = sqrtf(link_residual_sq(a2, tr, fro)) * link_scale;
     out[1] = ent * ent_scale;
   }
 }

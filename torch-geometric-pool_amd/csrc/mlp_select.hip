@@ -48,7 +48,7 @@ __device__ __forceinline__ float half_swap(float v) { return __shfl_xor(v, 32, 6
 // 2^-126 come out as 0.
 __device__ __forceinline__ float exp_neg(float x) {
   const float L = 1.44269504088896341f, Llo = 1.92596299112661746e-8f;
-  x = fmaxf(x, -104.f);  // 2^-150 = 0 in fp32; keeps -inf (padded columns) out of the error term (inf - inf)
+  x = nan_max(x, -104.f);  // 2^-150 = 0 in fp32; keeps -inf (padded columns) out of the error term (inf - inf); a NaN stays
   const float y = x * L;
   float r = fmaf(x, L, -y);
   r = fmaf(x, Llo, r);
@@ -193,6 +193,8 @@ __global__ __launch_bounds__(64 * MS_WAVES, KT > 6 ? 1 : 2) void mlp_select_mfma
     }
 
     // ---- softmax over the row held by lanes (lm, h = 0/1): column n = 32 t + (i & 3) + 8 (i >> 2) + 4 h
+    // (fmaxf: no NaN is lost here -- a NaN logit reaches `sum` through exp_neg below and makes the row NaN, an infinite
+    //  maximum gives inf - inf; both as torch.softmax.  One v_max_f32 per logit, no compare masks.)
     float mx = -INFINITY;
 #pragma unroll
     for (int t = 0; t < KT; ++t)
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ y
   if (m >= M) return;
   const int lane = lane_id();
   float* row = y + m * K;
-  float mx = -INFINITY;
+  float mx = -INFINITY;  // (fmaxf: a NaN logit is not lost, expf carries it into `sum` and the whole row, as torch.softmax)
   for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k] + (bias ? bias[k] : 0.f));
   mx = wave_max(mx);
   float sum = 0.f;

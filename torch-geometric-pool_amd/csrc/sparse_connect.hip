@@ -473,8 +473,8 @@ __device__ __forceinline__ double vt_mul(double a, double b) { return __dmul_rn(
 template <typename VT>
 __device__ __forceinline__ VT vt_reduce(VT acc, VT v, int op) {
   switch (op) {
-    case TGP_MIN: return fmin(acc, v);
-    case TGP_MAX: return fmax(acc, v);
+    case TGP_MIN: return nan_min(acc, v);
+    case TGP_MAX: return nan_max(acc, v);
     case TGP_MUL: return vt_mul(acc, v);
     default: return vt_add(acc, v);
   }
@@ -707,13 +707,14 @@ __global__ __launch_bounds__(256) void degree_scale_kernel(const int64_t* __rest
   const int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (e < E) {
     // deg.clamp(min=eps).pow(-0.5); w * dis[row] * dis[col]  (ops.py:395-401)
-    const float dr = 1.0f / sqrtf(fmaxf(deg[row[e]], eps));
-    const float dc = 1.0f / sqrtf(fmaxf(deg[col[e]], eps));
+    const float dr = 1.0f / sqrtf(clamp_min(deg[row[e]], eps));
+    const float dc = 1.0f / sqrtf(clamp_min(deg[col[e]], eps));
     w[e] = __fmul_rn(__fmul_rn(w[e], dr), dc);
   }
 }
 
-// |w| is non-negative, so its IEEE bit pattern orders like an unsigned int: exact, order-free max.
+// |w| is non-negative, so its IEEE bit pattern orders like an unsigned int: exact, order-free max.  A NaN's pattern lies
+// above +inf's, so a NaN weight wins the maximum and the whole graph comes out NaN, as the reference's amax gives it.
 // A batch has few graphs, so one atomic per edge would serialise on a handful of addresses
 // (113 ms at E = 10M, 8 graphs).  Each thread instead walks a contiguous slice of the list keeping a
 // running (graph, max) pair -- rows are normally sorted, so the graph id changes a few times per

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void f64_degree_scale_kernel(const int64_t* __
                                                                int64_t E, const double* __restrict__ deg, double eps) {
   const int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (e < E) {  // deg.clamp(min=eps).pow(-0.5); w * dis[row] * dis[col]  (ops.py:395-401)
-    const double dr = 1.0 / sqrt(fmax(deg[row[e]], eps)), dc = 1.0 / sqrt(fmax(deg[col[e]], eps));
+    const double dr = 1.0 / sqrt(clamp_min(deg[row[e]], eps)), dc = 1.0 / sqrt(clamp_min(deg[col[e]], eps));
     w[e] = __dmul_rn(__dmul_rn(w[e], dr), dc);
   }
 }
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void f64_post_dense_kernel(const double* __res
         double acc = 0.0;
 #pragma unroll 8
         for (int64_t r = 0; r < K; ++r) acc += at(r, i);
-        d[i] = sqrt(fmax(acc, eps));
+        d[i] = sqrt(clamp_min(acc, eps));
       }
     } else {
       const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void f64_post_dense_kernel(const double* __res
         // the shuffle-down ladder, distances 32 .. 1: lane 0 alone holds the sum (not the rounding of wave_sum)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-        if (lane == 0) d[i] = sqrt(fmax(acc, eps));
+        if (lane == 0) d[i] = sqrt(clamp_min(acc, eps));
       }
     }
   }

@@ -70,8 +70,8 @@ struct SpsArgs {
 
 __device__ __forceinline__ float sps_reduce(float acc, float v, int op) {
   switch (op) {
-    case TGP_MIN: return fminf(acc, v);
-    case TGP_MAX: return fmaxf(acc, v);
+    case TGP_MIN: return nan_min(acc, v);
+    case TGP_MAX: return nan_max(acc, v);
     case TGP_MUL: return __fmul_rn(acc, v);
     default: return __fadd_rn(acc, v);
   }

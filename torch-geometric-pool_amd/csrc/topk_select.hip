@@ -750,13 +750,14 @@ __global__ __launch_bounds__(256) void topk_minscore_kernel(const float* __restr
     return;
   }
   float mx = -INFINITY;
-  for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) mx = fmaxf(mx, score[i]);
-  mx = block_fold_pair256<false>(mx, sh, op_max{});
+  for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) mx = nan_max(mx, score[i]);
+  mx = block_fold_pair256<false>(mx, sh, op_nanmax{});
   float sum = 0.f;
   for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) sum += expf(score[i] - mx);
   sum = block_fold_pair256<false>(sum, sh, op_add{});
   const float den = sum + 1e-16f;
-  const float floor_ = fminf(1.0f / den - tol, min_score);  // max probability = exp(0) / den
+  const float top = 1.0f / den - tol;                          // max probability = exp(0) / den
+  const float floor_ = top > min_score ? min_score : top;      // Tensor.clamp(max=min_score): a NaN falls through
   uint32_t mine = 0;
   for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) {
     const float pr = expf(score[i] - mx) / den;

@@ -36,7 +36,7 @@ struct op_or {
   template <typename T>
   __device__ __forceinline__ T operator()(T a, T b) const { return a | b; }
 };
-struct op_max {  // floats: fmaxf / fmax (a NaN loses); integers: the later value only where it is larger
+struct op_max {  // floats: fmaxf / fmax (a NaN loses: see op_nanmax); integers: the later value only where it is larger
   __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
   __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); }
   template <typename T>
@@ -45,6 +45,27 @@ struct op_max {  // floats: fmaxf / fmax (a NaN loses); integers: the later valu
 struct op_min {
   template <typename T>
   __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; }
+};
+
+// ---- the reference's NaN rule -------------------------------------------------------------------------------------
+// torch's max / amax / amin / clamp propagate a NaN; fmaxf / fminf return the other operand.  Wherever the reference
+// takes one of those over values a caller supplies, the kernels use these: a NaN operand is the result.  (IEEE 754-2019
+// maximum / minimum: v_maximum3_f32 / v_minimum3_f32 on gfx950, one instruction like v_max_f32; fp64 gets v_max_f64
+// and a select.)
+template <typename T>
+__device__ __forceinline__ T nan_max(T a, T b) { return __builtin_elementwise_maximum(a, b); }
+template <typename T>
+__device__ __forceinline__ T nan_min(T a, T b) { return __builtin_elementwise_minimum(a, b); }
+// Tensor.clamp(min=lo): a NaN falls through
+template <typename T>
+__device__ __forceinline__ T clamp_min(T d, T lo) { return d < lo ? lo : d; }
+struct op_nanmax {
+  template <typename T>
+  __device__ __forceinline__ T operator()(T a, T b) const { return nan_max(a, b); }
+};
+struct op_nanmin {
+  template <typename T>
+  __device__ __forceinline__ T operator()(T a, T b) const { return nan_min(a, b); }
 };
 
 // ---- xor butterfly ------------------------------------------------------------------------------------------------
@@ -69,6 +90,10 @@ template <int G = 64, typename T>
 __device__ __forceinline__ T wave_max(T v) { return wave_fold<G>(v, op_max{}); }
 template <int G = 64, typename T>
 __device__ __forceinline__ T wave_min(T v) { return wave_fold<G>(v, op_min{}); }
+template <int G = 64, typename T>
+__device__ __forceinline__ T wave_nanmax(T v) { return wave_fold<G>(v, op_nanmax{}); }  // a NaN in any lane wins
+template <int G = 64, typename T>
+__device__ __forceinline__ T wave_nanmin(T v) { return wave_fold<G>(v, op_nanmin{}); }
 template <int G = 64, typename T>
 __device__ __forceinline__ T wave_or(T v) { return wave_fold<G>(v, op_or{}); }
 
