@@ -24,7 +24,7 @@ from ..connect import DenseConnect, KronConnect, SparseConnect
 from ..lift import BaseLift
 from ..reduce import BaseReduce
 from ..select import DPSelect, EdgeContractionSelect, GraclusSelect, KMISSelect, LaPoolSelect, MLPSelect, NDPSelect, SelectOutput, TopkSelect
-from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling
+from ..src import BasePrecoarseningMixin, DenseSRCPooling, PoolingOutput, SRCPooling, _Pooled
 from ..utils.ops import batch_info, batched_negative_edge_sampling, is_dense_adj, negative_edge_sampling
 from ..utils.losses import (
     _MinCutTermsFn,
@@ -414,9 +414,23 @@ class _DenseMLPPooling(DenseSRCPooling):
             adj_transpose=adj_transpose, cache_preprocessing=cache_preprocessing, batched=batched,
             sparse_output=sparse_output)
 
-    # hooks filled in by the two poolers -------------------------------------------------
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        raise NotImplementedError
+    # hooks filled in by the poolers -----------------------------------------------------
+    # True: the operator route connects through self.connect (which caches, and records its own autograd graph); False:
+    # through dense_connect, the loss on the raw S^T A S, then the post-processing
+    _connects_through_operator = False
+
+    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled, known_nodes=None):
+        if self._connects_through_operator:
+            adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
+                                       batch_pooled=batch_pooled)
+            return adj_pool, self._loss_from_fused(adj, so, mask, None, known_nodes=known_nodes)
+        c = self.connector
+        raw = c.dense_connect(adj=adj, s=so.s)
+        loss = self._loss_from_fused(adj, so, mask, raw, known_nodes=known_nodes)
+        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
+                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
+                                              edge_weight_norm=c.edge_weight_norm)
+        return adj_pool, loss
 
     def compute_sparse_loss(self, edge_index, edge_weight, S, batch) -> dict:
         raise NotImplementedError
@@ -451,55 +465,106 @@ class _DenseMLPPooling(DenseSRCPooling):
 
     @property
     def _mincut_terms(self) -> bool:
-        return self._loss_kind == "mincut"
+        return self._loss_kind in ("mincut",)
 
     @property
     def _wants_raw(self) -> bool:
         return self._loss_kind in ("mincut", "dmon", "hosc")
 
-    def _fused_diff_scales(self, adj, mask, adj_numel=None):
-        """(link_scale, ent_scale) when the pooler's two losses can ride on the fused training call (DiffPool).
-        ``adj_numel``: B * N * N of the padded adjacency when ``adj`` is not that tensor (sparse inputs)."""
+    def _fused_diff_scales(self, adj, known_nodes, adj_numel=None):
+        """(link_scale, ent_scale) when the pooler's two losses can ride on the fused call (DiffPool, and only with the
+        real-node count ``known_nodes`` the host already has).  ``adj_numel``: B * N * N of the padded adjacency when
+        ``adj`` is not that tensor (sparse inputs), or a callable that gives it."""
         return None
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
+        """The loss dict from what a fused route left: ``terms`` / ``diff`` when the route produced them, else the
+        pooler's own loss on ``adj``, ``so`` and ``raw``."""
+        raise NotImplementedError
+
+    # the one-launch sparse kernel: what the pooler asks of the launch besides _wants_raw and _mincut_terms ...
+    _sparse_diff_stats = False
+
+    def _sparse_launch_loss(self, s, mask, raw, terms, stats, edges, info, num_nodes) -> dict:
+        """... and the loss dict it makes of what came back.  ``stats``: the [B,4] records when ``_sparse_diff_stats``;
+        ``edges`` = (edge_index, edge_weight, edge_ptr)."""
+        raise NotImplementedError
+
+    # the un-padded rows route: the loss mode of its native entries (1: MinCut's two terms, 2: DiffPool's two losses;
+    # 0: no mode of theirs -- the staged operators and _rows_staged_loss, inference of the batched mode only); None: the
+    # pooler does not take the route
+    _rows_mode = None
+
+    def _rows_staged_loss(self, s, ptr, max_nodes) -> dict:
+        raise NotImplementedError
+
+    def _pair_loss(self, both) -> dict:
+        """The loss dict from the pooler's two finished batch means."""
         raise NotImplementedError
 
     def _lift(self, x, so, batch, batch_pooled):
         return self.lift(x_pool=x, so=so, batch=batch, batch_pooled=batch_pooled)
 
-    def _select_reduce_connect(self, x, adj, mask, want_batch=False):
-        """Inference on a batch of small graphs with a single-Linear selector: Select + Reduce + Connect as ONE launch
-        (tgp_dense_pool_select_f32: S is formed in the pooling kernel's registers and written once).  Returns
-        ``(SelectOutput, (x_pool, raw, adj_pool[, terms]), pooled batch vector or None)`` or None when the case is not
-        that one."""
-        from .. import kernels as K
-        sel, c = self.selector, self.connector
-        lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        if (type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
-                or type(self.reducer) is not BaseReduce or not (isinstance(x, Tensor) and isinstance(adj, Tensor))
-                or x.dim() != 3 or adj.dim() != 3 or not x.is_cuda or x.dtype != torch.float32
-                or adj.dtype != torch.float32 or (mask is not None and mask.dtype != torch.bool)):
+    # the gates the routes share (they take the submodules the route has looked up: a Module attribute costs a search)
+    @staticmethod
+    def _mlp_lins(sel):
+        """The Linear layers of a selector that is exactly MLPSelect, else None."""
+        return getattr(getattr(sel, "mlp", None), "lins", None) if type(sel) is MLPSelect else None
+
+    @staticmethod
+    def _single_linear(lins):
+        """The only layer of ``_mlp_lins(sel)`` when there is exactly one and it is float32, else None."""
+        if lins is None or len(lins) != 1:
             return None
         last = lins[0]
-        if torch.is_grad_enabled() and (x.requires_grad or adj.requires_grad or last.weight.requires_grad
-                                        or (last.bias is not None and last.bias.requires_grad)):
+        return last if last.weight.dtype == torch.float32 else None
+
+    def _plain_wiring(self, c) -> bool:
+        return type(c) is DenseConnect and type(self.reducer) is BaseReduce
+
+    @staticmethod
+    def _padded_f32(x, adj, mask) -> bool:
+        """A padded float32 device batch x [B,N,F], adj [B,N,N] with a bool mask or none."""
+        return (isinstance(x, Tensor) and isinstance(adj, Tensor) and x.dim() == 3 and adj.dim() == 3 and x.is_cuda
+                and x.dtype == torch.float32 and adj.dtype == torch.float32
+                and (mask is None or mask.dtype == torch.bool) and adj.shape == (x.size(0), x.size(1), x.size(1)))
+
+    @staticmethod
+    def _flat_f32(x, edge_index, edge_weight, batch) -> bool:
+        """An un-padded float32 device batch x [N,F], N > 0, with an int64 edge list [2,E], float32 edge weights or
+        none, an int64 batch vector [N] or none."""
+        return (isinstance(x, Tensor) and isinstance(edge_index, Tensor) and x.dim() == 2 and x.is_cuda
+                and x.dtype == torch.float32 and x.size(0) > 0 and edge_index.dim() == 2 and edge_index.size(0) == 2
+                and edge_index.dtype == torch.long and edge_index.is_cuda
+                and (edge_weight is None or edge_weight.dtype == torch.float32)
+                and (batch is None or (batch.dtype == torch.long and batch.numel() == x.size(0))))
+
+    def _select_reduce_connect(self, x, adj, mask, want_batch=False, known_nodes=None):
+        """Inference on a batch of small graphs with a single-Linear selector: Select + Reduce + Connect as ONE launch
+        (tgp_dense_pool_select_f32: S is formed in the pooling kernel's registers and written once).  Returns a
+        ``_Pooled`` (``terms``: MinCut's per-graph terms, ``diff``: DiffPool's two losses, ``batch_pool`` when
+        ``want_batch``) or None when the case is not that one."""
+        sel, c = self.selector, self.connector
+        last = self._single_linear(self._mlp_lins(sel))
+        if last is None or not self._plain_wiring(c) or not self._padded_f32(x, adj, mask):
             return None
-        if (last.weight.dtype != torch.float32 or adj.shape != (x.size(0), x.size(1), x.size(1))
-                or not K.dense_pool_is_small(x.size(0), x.size(1), last.weight.size(0), x.size(2))):
+        weight, bias = last.weight, last.bias
+        if torch.is_grad_enabled() and (x.requires_grad or adj.requires_grad or weight.requires_grad
+                                        or (bias is not None and bias.requires_grad)):
+            return None
+        if not K.dense_pool_is_small(x.size(0), x.size(1), weight.size(0), x.size(2)):
             return None
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
-        diff_scales = self._fused_diff_scales(adj, mask)
-        out = K.dense_pool_select(
-            x, adj, last.weight.detach(), None if last.bias is None else last.bias.detach(), mask, flags,
-            want_raw=self._wants_raw, mincut_terms=self._mincut_terms, want_batch=want_batch,
-            diff_stats=diff_scales is not None)
-        s, x_pool, raw, adj_pool, terms = out[:5]
-        so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw, adj_pool) + ((terms,) if self._mincut_terms else ())
+        diff_scales = self._fused_diff_scales(adj, known_nodes)
+        mincut = self._mincut_terms
+        s, x_pool, raw, adj_pool, terms, *bp = K.dense_pool_select(
+            x, adj, weight.detach(), None if bias is None else bias.detach(), mask, flags,
+            want_raw=self._wants_raw, mincut_terms=mincut, want_batch=want_batch, diff_stats=diff_scales is not None)
+        diff = None
         if diff_scales is not None:  # DiffPool (r6): both losses from the launch's per-graph records, one tail launch
-            fused = fused + (K.diffpool_stats_tail(terms, diff_scales[0], diff_scales[1]),)
-        return so, fused, (out[5] if want_batch else None)
+            diff = K.diffpool_stats_tail(terms, diff_scales[0], diff_scales[1])
+        return _Pooled(SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask), x_pool, raw, adj_pool,
+                       terms if mincut else None, diff, bp[0] if want_batch else None)
 
     def _select_reduce_connect_sparse(self, x, edge_index, edge_weight, batch):
         """A sorted batch of small graphs that arrives as PyG hands it over (x [N,F], a row-sorted
@@ -507,31 +572,25 @@ class _DenseMLPPooling(DenseSRCPooling):
         (tgp_dense_pool_select_sparse_f32: every graph's adjacency tile is built in LDS from its edges) -- neither
         ``to_dense_batch`` nor ``to_dense_adj`` runs and no [B,N,N] tensor exists.  Training takes the same launch as one
         autograd node (functions._SelectPoolSparseFn: the padded tensors the backward kernels read are side outputs).  Only
-        for poolers whose losses come out of the kernel (MinCut); returns ``(SelectOutput, fused, pooled batch vector)``
-        or None."""
-        from .. import kernels as K
+        for poolers whose losses do not walk the dense adjacency; returns a ``_Pooled`` with the finished ``loss`` or
+        None."""
         sel, c = self.selector, self.connector
-        lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        if (not _FOLD_SPARSE_INPUTS or self.cache_preprocessing
-                or type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
-                or type(self.reducer) is not BaseReduce or not (isinstance(x, Tensor) and isinstance(edge_index, Tensor))
-                or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or edge_index.dim() != 2
-                or edge_index.size(0) != 2 or edge_index.dtype != torch.long or not edge_index.is_cuda
-                or batch is None or batch.dtype != torch.long or batch.numel() != x.size(0) or x.size(0) == 0
-                or (edge_weight is not None and (edge_weight.dim() != 1 or edge_weight.dtype != torch.float32))):
+        last = self._single_linear(self._mlp_lins(sel))
+        if (not _FOLD_SPARSE_INPUTS or self.cache_preprocessing or last is None or not self._plain_wiring(c)
+                or not self._flat_f32(x, edge_index, edge_weight, batch)
+                or batch is None  # (this route only: the kernel walks the graphs of a batch vector)
+                or (edge_weight is not None and edge_weight.dim() != 1)):  # (this route only: one weight per edge)
             return None
         if self._loss_reads_dense_adj:
             return None  # (the batch is densified, as the reference does)
-        last = lins[0]
-        if torch.is_grad_enabled() and edge_weight is not None and edge_weight.requires_grad:
+        weight, bias, grad = last.weight, last.bias, torch.is_grad_enabled()
+        if grad and edge_weight is not None and edge_weight.requires_grad:
             return None  # (the edge weights get no gradient from the fused backward)
-        training = torch.is_grad_enabled() and (x.requires_grad or last.weight.requires_grad
-                                                or (last.bias is not None and last.bias.requires_grad))
+        training = grad and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
         if training and self._loss_only:
             return None  # (the loss-only kinds train on the operator route)
         # (a pooler whose losses need the dense adjacency -- DiffPool's link loss -- gets it as a side output of the launch)
-        if training and not (_FOLD_TRAINING and not c.edge_weight_norm
-                             and K.mlp_select_bwd_fits(last.weight.size(0), x.size(1))):
+        if training and not (_FOLD_TRAINING and not c.edge_weight_norm and K.mlp_select_bwd_fits(weight.size(0), x.size(1))):
             return None
         # the one-launch kernel walks every graph's edge range: the list must be grouped by ascending source node (what
         # PyG's loaders produce).  Known per tensor object once it has been looked at; a NEW list gets its ranges and
@@ -549,116 +608,76 @@ class _DenseMLPPooling(DenseSRCPooling):
             if pending is None:
                 return None
         info = batch_info(batch)  # (memoised per batch vector)
-        if (not info.is_sorted or last.weight.dtype != torch.float32
-                or not K.dense_pool_is_small(info.num_graphs, info.max_nodes, last.weight.size(0), x.size(1))):
+        if (not info.is_sorted
+                or not K.dense_pool_is_small(info.num_graphs, info.max_nodes, weight.size(0), x.size(1))):
             if pending is not None:
                 K.edge_facts_finish(pending, edge_index, info.ptr)  # (the launch is out: keep what it found)
             return None
         edge_ptr = pending[2] if pending is not None else K.graph_edge_ptr(edge_index, info.ptr)
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
-        ad = None
+        mincut = self._mincut_terms
         if training:  # one autograd node; the padded tensors the backward reads are side outputs of the same launch
-            from .. import functions as Fn
             diff_scales = None
-            if not self._mincut_terms:
-                self._known_nodes = x.size(0)
-                diff_scales = self._fused_diff_scales(None, None, info.num_graphs * info.max_nodes * info.max_nodes)
+            if not mincut:
+                diff_scales = self._fused_diff_scales(None, x.size(0), info.num_graphs * info.max_nodes * info.max_nodes)
                 if diff_scales is None:
                     if pending is not None:
                         K.edge_facts_finish(pending, edge_index, info.ptr)
                     return None
-            s, mask, x_pool, raw, adj_pool, terms, bp = Fn.select_pool_sparse(
-                x, last.weight, last.bias, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs,
-                info.max_nodes, flags, self.adj_transpose, self._mincut_terms, diff_scales, info.sizes)
-        elif self._mincut_terms:
-            s, mask, x_pool, raw, adj_pool, terms, bp = K.dense_pool_select_sparse(
+            s, mask, x_pool, raw, adj_pool, pair, bp = Fn.select_pool_sparse(
+                x, weight, bias, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs,
+                info.max_nodes, flags, self.adj_transpose, mincut, diff_scales, info.sizes)
+            loss = self._pair_loss(pair)  # (both losses came with the fused call: a LossPair)
+        else:  # the pooler's losses from what the launch wrote: no dense adjacency
+            s, mask, x_pool, raw, adj_pool, terms, bp, *stats = K.dense_pool_select_sparse(
                 x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
-                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
-                want_raw=True, mincut_terms=True)
-        elif self._loss_kind == "dmon":  # raw from the launch, degrees from the edge list: no dense adjacency either
-            s, mask, x_pool, raw, adj_pool, _, bp = K.dense_pool_select_sparse(
-                x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
-                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
-                want_raw=True, mincut_terms=False)
-            deg = K.dmon_edge_degrees(edge_index, edge_weight, info.ptr, edge_ptr, info.max_nodes, self.adj_transpose)
-            terms = self._dmon_means(s, raw, mask, info.sizes, deg=deg)
-        elif self._loss_kind == "jb":  # the launch writes S; the loss reads nothing else: no dense adjacency, no raw
-            s, mask, x_pool, raw, adj_pool, _, bp = K.dense_pool_select_sparse(
-                x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
-                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
-                want_raw=False, mincut_terms=False)
-            terms = self._jb_mean(s, mask, info.sizes)
-        else:  # DiffPool, inference (r6): both losses from per-graph records of the same launch -- no dense adjacency
-            s, mask, x_pool, raw, adj_pool, terms, bp, dstats = K.dense_pool_select_sparse(
-                x, edge_index, edge_weight, batch, info.ptr, edge_ptr, info.num_graphs, info.max_nodes,
-                last.weight.detach(), None if last.bias is None else last.bias.detach(), flags, self.adj_transpose,
-                want_raw=False, mincut_terms=False, diff_stats=True)
-            numel = info.num_graphs * info.max_nodes * info.max_nodes  # adj.numel() of the padded batch (losses.py:651)
-            link_scale = self.link_loss_coeff / numel if self.normalize_loss is True else self.link_loss_coeff
-            terms = K.diffpool_stats_tail(dstats, float(link_scale), float(self.ent_loss_coeff) / x.size(0))
+                weight.detach(), None if bias is None else bias.detach(), flags, self.adj_transpose,
+                want_raw=self._wants_raw, mincut_terms=mincut, diff_stats=self._sparse_diff_stats)
+            loss = self._sparse_launch_loss(s, mask, raw, terms, stats[0] if stats else None,
+                                            (edge_index, edge_weight, edge_ptr), info, x.size(0))
         if pending is not None and not K.edge_facts_finish(pending, edge_index, info.ptr):
             return None  # rows not sorted: what the kernel computed on clamped ranges is dropped
         so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
         so._graph_sizes = info.sizes
-        if self._loss_kind == "diff":
-            # (both losses came with the fused call: a LossPair -- training -- or a [2] tensor in the slot of `diff`)
-            return so, (x_pool, None, adj_pool, None, terms), bp, None
-        return so, (x_pool, raw, adj_pool, terms, None), bp, None
+        return _Pooled(so, x_pool, raw if self._wants_raw else None, adj_pool, batch_pool=bp, loss=loss)
 
-    def _select_reduce_connect_train(self, x, adj, mask, graph_sizes, want_batch=False):
+    def _select_reduce_connect_train(self, x, adj, mask, graph_sizes, want_batch=False, known_nodes=None):
         """Training on a batch of small graphs with a single-Linear selector: Select + Reduce + Connect + loss tails as
         ONE autograd node (functions._SelectPoolSmallFn: one forward launch, two backward launches; the selector and the
         pooling were two nodes with eight + one backward launches and an accumulation of the two gradients of X).
-        Returns ``(SelectOutput, fused)`` like :meth:`_select_reduce_connect`, the losses as a ``LossPair``."""
-        from .. import functions as Fn, kernels as K
+        Returns a ``_Pooled`` like :meth:`_select_reduce_connect`, the losses as a ``LossPair``."""
         sel, c = self.selector, self.connector
-        lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        if (self._loss_only
-                or type(sel) is not MLPSelect or lins is None or len(lins) != 1 or type(c) is not DenseConnect
-                or type(self.reducer) is not BaseReduce or not (isinstance(x, Tensor) and isinstance(adj, Tensor))
-                or x.dim() != 3 or adj.dim() != 3 or not x.is_cuda or x.dtype != torch.float32
-                or adj.dtype != torch.float32 or (mask is not None and mask.dtype != torch.bool)
+        last = self._single_linear(self._mlp_lins(sel))
+        if (self._loss_only or last is None or not self._plain_wiring(c) or not self._padded_f32(x, adj, mask)
                 or not torch.is_grad_enabled() or adj.requires_grad or c.edge_weight_norm):
             return None
-        last = lins[0]
-        if (last.weight.dtype != torch.float32 or adj.shape != (x.size(0), x.size(1), x.size(1))
-                or not K.dense_pool_is_small(x.size(0), x.size(1), last.weight.size(0), x.size(2))
-                or not K.mlp_select_bwd_fits(last.weight.size(0), x.size(2))):
+        weight, mincut = last.weight, self._mincut_terms
+        if (not K.dense_pool_is_small(x.size(0), x.size(1), weight.size(0), x.size(2))
+                or not K.mlp_select_bwd_fits(weight.size(0), x.size(2))):
             return None
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
-        diff_scales = self._fused_diff_scales(adj, mask)
+        diff_scales = self._fused_diff_scales(adj, known_nodes)
         s, x_pool, raw, adj_pool, pair, bp = Fn.select_pool_small(
-            x, adj, last.weight, last.bias, mask, flags, self._mincut_terms, self._mincut_terms, diff_scales,
-            graph_sizes, want_batch)
-        so = SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw if self._mincut_terms else None, adj_pool)
-        if self._mincut_terms:
-            fused = fused + (pair,)
-        if diff_scales is not None:
-            fused = fused + (pair,)
-        return so, fused, bp
+            x, adj, weight, last.bias, mask, flags, mincut, mincut, diff_scales, graph_sizes, want_batch)
+        return _Pooled(SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask), x_pool, raw if mincut else None, adj_pool,
+                       pair if mincut else None, pair if diff_scales is not None else None, bp)
 
-    def _select_reduce_connect_large(self, x, adj, mask, graph_sizes, so=None, symmetry=None):
+    def _select_reduce_connect_large(self, x, adj, mask, graph_sizes, so=None, symmetry=None, known_nodes=None):
         """Training on a padded batch whose graphs are beyond the one-wave kernels (C2-sized), r6: Select (single-Linear
         selector; otherwise ``so`` holds S) + Reduce + Connect + post-processing + the pooler's two losses as ONE
         autograd node (functions._PoolLargeFn: ~10 forward and ~13 backward launches where the operator-by-operator graph
-        ran 65-71).  Returns ``(SelectOutput, fused, None)`` like :meth:`_select_reduce_connect_train`, or None."""
-        from .. import functions as Fn, kernels as K
+        ran 65-71).  Returns a ``_Pooled`` like :meth:`_select_reduce_connect_train`, or None."""
         sel, c = self.selector, self.connector
-        if (not _FOLD_TRAINING or self._loss_only or type(c) is not DenseConnect
-                or type(self.reducer) is not BaseReduce
-                or not (isinstance(x, Tensor) and isinstance(adj, Tensor)) or x.dim() != 3 or adj.dim() != 3
-                or not x.is_cuda or x.dtype != torch.float32 or adj.dtype != torch.float32
-                or (mask is not None and mask.dtype != torch.bool) or not torch.is_grad_enabled()
-                or adj.requires_grad or c.edge_weight_norm or adj.shape != (x.size(0), x.size(1), x.size(1))
-                or x.size(0) == 0 or x.size(1) == 0 or x.size(2) == 0):
+        if (not _FOLD_TRAINING or self._loss_only or not self._plain_wiring(c) or not self._padded_f32(x, adj, mask)
+                or not torch.is_grad_enabled() or adj.requires_grad or c.edge_weight_norm
+                or x.size(0) == 0 or x.size(1) == 0 or x.size(2) == 0):  # (this route only: its grids need every extent)
             return None
-        lins = getattr(getattr(sel, "mlp", None), "lins", None)
         weight = bias = s = None
         if so is None:
-            if type(sel) is not MLPSelect or lins is None or len(lins) != 1 or lins[0].weight.dtype != torch.float32:
+            last = self._single_linear(self._mlp_lins(sel))
+            if last is None:
                 return None
-            weight, bias = lins[0].weight, lins[0].bias
+            weight, bias = last.weight, last.bias
             k = weight.size(0)
             if not (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
                 return None
@@ -671,23 +690,23 @@ class _DenseMLPPooling(DenseSRCPooling):
         if k == 0 or k > 4096 or K.dense_pool_is_small(x.size(0), x.size(1), k, x.size(2)):
             return None
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
-        mode, scales = (1, (0.0, 0.0)) if self._mincut_terms else (0, (0.0, 0.0))
+        mode, scales = 1, (0.0, 0.0)  # (the loss modes of the native entries: 1 MinCut's terms, 2 DiffPool's losses)
         if not self._mincut_terms:
-            diff_scales = self._fused_diff_scales(adj, mask)
-            if diff_scales is None:
+            scales = self._fused_diff_scales(adj, known_nodes)
+            if scales is None:
                 return None
-            mode, scales = 2, diff_scales
+            mode = 2
         s_out, x_pool, raw, adj_pool, pair = Fn.pool_large(x, adj, weight, bias, mask, s, flags, mode, scales, graph_sizes,
                                                            symmetry() if callable(symmetry) else symmetry)
         if so is None:
             so = SelectOutput(s=s_out, s_inv_op=sel.s_inv_op, in_mask=mask)
-        fused = (x_pool, raw if self._mincut_terms else None, adj_pool, pair)
-        return so, fused, None
+        if mode == 1:
+            return _Pooled(so, x_pool, raw, adj_pool, terms=pair)
+        return _Pooled(so, x_pool, None, adj_pool, diff=pair)
 
     @staticmethod
     def _adj_symmetry(edge_index, edge_weight, dense_adj, batch):
         """kernels.AdjSymmetry for the adjacency forward() densified from this edge list, or None."""
-        from .. import kernels as K
         if not (isinstance(edge_index, Tensor) and edge_index.dim() == 2 and edge_index.size(0) == 2
                 and edge_index.dtype == torch.long and edge_index.is_cuda and batch is not None
                 and (edge_weight is None or isinstance(edge_weight, Tensor))):
@@ -713,27 +732,26 @@ class _DenseMLPPooling(DenseSRCPooling):
         S^T A^T S when adj_transpose (= the transpose of S^T (A S); MinCut's degrees are then in-degrees, sum_i (A q)_i),
         S handed out padded [B,Nmax,K] with its mask, losses normalised as the batched forms do.
 
-        Returns (SelectOutput, x_pool [B,K,F], adj_pool [B,K,K], pooled batch vector, losses); ``(SelectOutput,)`` when
-        only Select could be done here (unbatched mode); None when the case is not this one."""
-        from .. import kernels as K
-        from .. import functions as Fn
+        Returns a ``_Pooled`` with x_pool [B,K,F], adj_pool [B,K,K], the pooled batch vector and the finished ``loss``;
+        one with only ``so`` set when only Select could be done here (unbatched mode); None when the case is not this
+        one."""
         c, sel = self.connector, self.selector
-        jb = self._loss_kind == "jb"  # (its loss reads S alone: the one loss-only kind this route serves, in inference)
-        if ((self._loss_only and not jb) or type(c) is not DenseConnect or type(self.reducer) is not BaseReduce
-                or (self.sparse_output and not batched_out)
-                or not (isinstance(x, Tensor) and isinstance(edge_index, Tensor))
-                or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32
-                or edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.long
-                or not edge_index.is_cuda or edge_index.size(1) == 0 or x.size(0) == 0 or x.size(1) == 0
-                or (edge_weight is not None and (not isinstance(edge_weight, Tensor) or edge_weight.dtype != torch.float32
-                                                 or edge_weight.numel() != edge_index.size(1)))
-                or (batch is not None and (batch.dtype != torch.long or batch.numel() != x.size(0)))):
+        mode = self._rows_mode
+        staged = mode == 0  # (no loss mode in the native entries: the staged operators, see _rows_mode)
+        if (mode is None or not self._plain_wiring(c) or (self.sparse_output and not batched_out)
+                # (this route only: a non-tensor weight declines here instead of raising)
+                or (edge_weight is not None and not isinstance(edge_weight, Tensor))
+                or not self._flat_f32(x, edge_index, edge_weight, batch)
+                # (this route only: the CSR and the products need an edge and a feature; the weights may have any shape)
+                or edge_index.size(1) == 0 or x.size(1) == 0
+                or (edge_weight is not None and edge_weight.numel() != edge_index.size(1))):
             return None
         grad = torch.is_grad_enabled()
         if grad and edge_weight is not None and edge_weight.requires_grad:
             return None
-        if jb and (not batched_out or (grad and (x.requires_grad or any(p.requires_grad for p in sel.parameters())))):
-            return None  # (Just Balance trains, and runs its unbatched mode, on the operator route)
+        if staged and (not batched_out
+                       or (grad and (x.requires_grad or any(p.requires_grad for p in sel.parameters())))):
+            return None  # (such a pooler trains, and runs its unbatched mode, on the operator route)
         n = x.size(0)
         info = None
         if batch is not None:
@@ -743,37 +761,40 @@ class _DenseMLPPooling(DenseSRCPooling):
             ptr, max_nodes, nb = info.ptr, info.max_nodes, info.num_graphs
         else:
             ptr, max_nodes, nb = Fn._whole_range(n, x.device), n, 1
-        lins = getattr(getattr(sel, "mlp", None), "lins", None)
-        single = type(sel) is MLPSelect and lins is not None and len(lins) == 1 and lins[0].weight.dtype == torch.float32
+        lins = self._mlp_lins(sel)
+        last = self._single_linear(lins)
+        single = last is not None
         if batched_out:  # every check comes BEFORE Select here: a bail-out must leave the batched flow untouched
-            if (not _ROWS_ROUTE or self.cache_preprocessing or type(sel) is not MLPSelect or lins is None
-                    or lins[-1].weight.dtype != torch.float32
-                    or edge_index.size(1) > _rows_route_density(lins[-1].weight.size(0)) * float(n) * float(max_nodes)
-                    or K.dense_pool_is_small(nb, max_nodes, lins[-1].weight.size(0), x.size(1))):
+            w_out = None if lins is None else lins[-1].weight  # (K is the last layer's, however many there are)
+            if (not _ROWS_ROUTE or self.cache_preprocessing or w_out is None or w_out.dtype != torch.float32
+                    or edge_index.size(1) > _rows_route_density(w_out.size(0)) * float(n) * float(max_nodes)
+                    or K.dense_pool_is_small(nb, max_nodes, w_out.size(0), x.size(1))):
                 return None
-            k_out = lins[-1].weight.size(0)
+            k_out = w_out.size(0)
             will_train = grad and (x.requires_grad or any(p.requires_grad for p in sel.parameters()))
             if will_train and (not _FOLD_TRAINING or c.edge_weight_norm or k_out > 4096):
                 return None
         # the selector: folded into the training node when it is a single Linear, else run in front (its S handed over)
         so = weight = bias = None
+        if single:
+            weight, bias = last.weight, last.bias
         # inference with a single-Linear selector (r6, late): the selector rides in the ONE native call of the forward
         # (kernels.pool_rows_forward); the SelectOutput is built from the S it leaves
         fold_inference = (not grad and single and K._POOL_ROWS_ONE_CALL and x.dtype == torch.float32 and x.is_contiguous()
-                          and lins[0].weight.size(0) <= 256 and not jb)
+                          and weight.size(0) <= 256 and not staged)
         if fold_inference:
-            weight, bias = lins[0].weight.detach(), None if lins[0].bias is None else lins[0].bias.detach()
+            weight, bias = weight.detach(), None if bias is None else bias.detach()
             s, training = None, False
         elif not (grad and single and _FOLD_TRAINING):
+            weight = bias = None  # (the selector runs in front: its S is handed over)
             so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
             s = so.s
             if batched_out and isinstance(s, Tensor) and s.dim() == 3 and s.size(0) == 1:
                 s = s[0]  # (MLPSelect in its batched representation treats [N,F] as one padded graph)
             if not (isinstance(s, Tensor) and s.dim() == 2 and s.dtype == torch.float32 and s.size(0) == n):
-                return None if batched_out else (so,)  # (the caller goes on with this SelectOutput on the operator path)
+                return None if batched_out else _Pooled(so)  # (the caller goes on with it on the operator path)
             training = grad and (s.requires_grad or x.requires_grad)
         else:
-            weight, bias = lins[0].weight, lins[0].bias
             s = None
             training = x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)
             if not training:
@@ -785,7 +806,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                 return None
             if so is None:
                 so = self.select(x=x, batch=batch)
-            return (so,)
+            return _Pooled(so)
         w_in = None if edge_weight is None else edge_weight.reshape(-1)
         ones = w_in is None
         # sorted + duplicate-summed A (what the reference's per-graph `.coalesce()` does), T = A S, then one product grid
@@ -799,34 +820,28 @@ class _DenseMLPPooling(DenseSRCPooling):
         transposed = bool(batched_out and self.adj_transpose)
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose if batched_out else False,
                               c.edge_weight_norm)
-        mincut = self._mincut_terms
+        mincut = mode == 1
         sw2, scales = 0.0, (0.0, 0.0)
-        if not mincut and not jb:  # DiffPool: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
+        if mode == 2:  # the link loss: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
             # (batched form, losses.py:644-652: the dense A has the duplicates summed -- the same list after coalescing)
             if batched_out and not unit:
                 sw2 = torch.dot(w, w)
             else:
                 sw2 = float(edge_index.size(1)) if ones else torch.dot(w_in.detach(), w_in.detach())
-            link_scale = float(self.link_loss_coeff)
-            if self.normalize_loss is True:
-                if batched_out:  # adj.numel() of the padded batch (losses.py:651)
-                    denom = nb * max_nodes * max_nodes
-                else:
-                    denom = sum(v * v for v in info.sizes_host) if info is not None else n * n
-                link_scale = link_scale / max(denom, 1)
-            scales = (link_scale, float(self.ent_loss_coeff) / n)
+            # (the normaliser, asked only when the link loss is normalised: adj.numel() of the padded batch, losses.py:651)
+            scales = self._fused_diff_scales(None, n, (lambda: nb * max_nodes * max_nodes) if batched_out else (
+                lambda: sum(v * v for v in info.sizes_host) if info is not None else n * n))
         if training:
             sym = K.AdjSymmetry.of_edge_list(edge_index, edge_weight, ei, w_used, row_ptr, n)
             s_out, x_pool, raw, adj_pool, pair = Fn.pool_unbatched(
-                x, weight, bias, s, ei, w_used, row_ptr, ptr, batch, max_nodes, flags, 1 if mincut else 2, scales, sw2, sym,
-                transposed)
+                x, weight, bias, s, ei, w_used, row_ptr, ptr, batch, max_nodes, flags, mode, scales, sw2, sym, transposed)
             s_flat = s_out
             both = pair
-        elif jb:  # (the staged operators below: the one-call entry's loss modes are MinCut's and DiffPool's)
+        elif staged:  # (the staged operators below: the one-call entry's loss modes are MinCut's and DiffPool's)
             one = None
         else:
             one = K.pool_rows_forward(x, weight if s is None else None, bias if s is None else None, s, row_ptr, ei, w_used,
-                                      ptr, max_nodes, transposed, flags, 1 if mincut else 2, scales, sw2)
+                                      ptr, max_nodes, transposed, flags, mode, scales, sw2)
             if one is None and s is None:  # (not the one-call entry's case after all: the selector runs on its own)
                 so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
                 s = so.s[0] if (batched_out and so.s.dim() == 3) else so.s
@@ -834,16 +849,15 @@ class _DenseMLPPooling(DenseSRCPooling):
             s, raw, x_pool, adj_pool = one["s"], one["raw"], one["x_pool"], one["adj_pool"]
             both = one["both"] if mincut else one["lossv"]
             s_flat = s
-        elif jb:  # T = A S, S^T [T | X] with the post-processing, the loss kernel on the un-padded S
+        elif staged:  # T = A S, S^T [T | X] with the post-processing, the pooler's loss on the un-padded S
             t = K.spmm_csr(row_ptr, ei, w_used, n, s)
             raw, x_pool, adj_pool = K.segment_gemm_tn3(s, [t, x], ptr, max_nodes, transpose0=transposed, post_flags=flags)
-            both = K.jb_terms(s, ptr=ptr, max_nodes=max_nodes, normalize=bool(self.normalize_loss),
-                              scale=float(self.loss_coeff), want_coef=False, want_mean=True)[2]
+            loss = self._rows_staged_loss(s, ptr, max_nodes)
             s_flat = s
         elif not training:
             if mincut:  # out-degrees and |S_i|^2 ride along with T = A S
                 t, deg, q = K.spmm_csr(row_ptr, ei, w_used, n, s, want_stats=True)
-            else:       # DiffPool: the entropy sum over S rides along
+            else:       # mode 2: the entropy sum over S rides along
                 t, ent_part = K.spmm_csr(row_ptr, ei, w_used, n, s, want_stats="entropy")
             raw, x_pool, gram, adj_pool = K.segment_gemm_tn3(s, [t, x, s], ptr, max_nodes, transpose0=transposed,
                                                              post_flags=flags)
@@ -868,26 +882,30 @@ class _DenseMLPPooling(DenseSRCPooling):
                 so._graph_sizes = info.sizes
         elif so is None:
             so = SelectOutput(s=s_flat, s_inv_op=sel.s_inv_op, batch=batch)
-        if mincut:
-            loss = {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
-                    "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
-        elif jb:
-            loss = {"balance_loss": both}
-        else:
-            loss = {"link_loss": both[0], "entropy_loss": both[1]}
+        if not staged:
+            loss = self._pair_loss(both)
         batch_pool = self.reducer.reduce_batch(so, batch if batch is not None else so.batch)
-        return so, x_pool, adj_pool, batch_pool, loss
+        return _Pooled(so, x_pool, None, adj_pool, batch_pool=batch_pool, loss=loss)
 
     def _sizes_for(self, adj):
         """Real nodes per graph of the zero-padded batch ``adj`` belongs to, if forward() densified it itself."""
+        # (_sizes_hint stays on the module, unlike the per-call node count: the public compute_loss reads it with no
+        #  forward() in between, and it answers only for the very adjacency tensor it was noted for)
         hint = getattr(self, "_sizes_hint", None)
         return hint[1] if hint is not None and hint[0]() is adj else None
 
-    def _real_nodes(self, mask):
+    @staticmethod
+    def _real_nodes(known_nodes, mask):
         """Valid nodes of the padded batch: the host-side count when forward() had one, else a 0-dim device tensor
         (no host round trip either way)."""
-        known = getattr(self, "_known_nodes", None)
-        return known if known is not None else mask.sum()
+        return known_nodes if known_nodes is not None else mask.sum()
+
+    def _batched_output(self, x_pool, adj_pool, so, loss, batch, batch_pool) -> PoolingOutput:
+        if self.sparse_output:
+            x_pool, ei, ew, batch_pool = self._finalize_sparse_output(
+                x_pool=x_pool, adj_pool=adj_pool, batch=batch, batch_pooled=batch_pool, so=so)
+            return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so, loss=loss)
+        return PoolingOutput(x=x_pool, edge_index=adj_pool, so=so, loss=loss)
 
     def forward(self, x: Tensor, adj=None, edge_weight: Optional[Tensor] = None,
                 so: Optional[SelectOutput] = None, mask: Optional[Tensor] = None,
@@ -898,49 +916,35 @@ class _DenseMLPPooling(DenseSRCPooling):
         if self.batched:
             if so is None and mask is None and not is_dense_adj(adj):
                 self._sizes_hint = None
-                sparse = self._select_reduce_connect_sparse(x, adj, edge_weight, batch)
-                if sparse is not None:  # straight from the un-padded batch: no densification launches
-                    self._known_nodes = x.size(0)
-                    so, fused, batch_pool, dense_adj = sparse
-                    x_pool, raw, adj_pool, terms, diff = fused
-                    loss = self._loss_from_fused(dense_adj if dense_adj is not None else adj, so, None, raw, terms, diff)
-                    if self.sparse_output:
-                        x_pool, ei, ew, batch_pool = self._finalize_sparse_output(
-                            x_pool=x_pool, adj_pool=adj_pool, batch=batch, batch_pooled=batch_pool, so=so)
-                        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so,
-                                             loss=loss)
-                    return PoolingOutput(x=x_pool, edge_index=adj_pool, so=so, loss=loss)
-                rows = self._unbatched_fused(x, adj, edge_weight, batch, batched_out=True)
-                if rows is not None:  # large sparse graphs: the un-padded rows route, no dense adjacency (r6)
-                    so, x_pool, adj_pool, batch_pool, loss = rows
-                    if self.sparse_output:
-                        x_pool, ei, ew, batch_pool = self._finalize_sparse_output(
-                            x_pool=x_pool, adj_pool=adj_pool, batch=batch, batch_pooled=batch_pool, so=so)
-                        return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so,
-                                             loss=loss)
-                    return PoolingOutput(x=x_pool, edge_index=adj_pool, so=so, loss=loss)
+                # straight from the un-padded batch, no densification launches: small graphs in the one-launch kernel,
+                # large sparse ones on the un-padded rows route (r6)
+                pooled = self._select_reduce_connect_sparse(x, adj, edge_weight, batch)
+                if pooled is None:
+                    pooled = self._unbatched_fused(x, adj, edge_weight, batch, batched_out=True)
+                if pooled is not None:
+                    return self._batched_output(pooled.x_pool, pooled.adj_pool, pooled.so, pooled.loss, batch,
+                                                pooled.batch_pool)
             # number of real nodes behind the padded batch, when the host already knows it (a reduction over the mask
             # costs ~25 us on the device for any mask size)
-            self._known_nodes = None
+            known_nodes = None
             graph_sizes = None
             sparse_in = False
             if not is_dense_adj(adj) and isinstance(x, Tensor) and x.dim() == 2:
                 sparse_in = True
-                self._known_nodes = x.size(0)
+                known_nodes = x.size(0)
                 if batch is not None and batch.numel() > 0 and x.is_cuda:
                     graph_sizes = batch_info(batch).sizes  # memoised: the densification below asks for it anyway
             elif mask is None and isinstance(x, Tensor) and x.dim() == 3:
-                self._known_nodes = x.size(0) * x.size(1)
+                known_nodes = x.size(0) * x.size(1)
             sparse_edges = (adj, edge_weight) if sparse_in else None
             x, adj, mask = self._ensure_batched_inputs(x=x, edge_index=adj, edge_weight=edge_weight, batch=batch,
                                                        mask=mask)
             # (the folded kernels also write the pooled batch vector: arange(B).repeat_interleave(K) of the B graphs)
             want_bp = sparse_in and batch is not None and batch.dtype == torch.long and batch.numel() > 0
-            folded = self._select_reduce_connect(x, adj, mask, want_bp)
-            if folded is None and _FOLD_TRAINING:
-                folded = self._select_reduce_connect_train(x, adj, mask, graph_sizes, want_bp)
+            pooled = self._select_reduce_connect(x, adj, mask, want_bp, known_nodes)
+            if pooled is None and _FOLD_TRAINING:
+                pooled = self._select_reduce_connect_train(x, adj, mask, graph_sizes, want_bp, known_nodes)
             symmetry = None
-            from .. import kernels as K_
             if sparse_in and _FOLD_TRAINING and torch.is_grad_enabled() and isinstance(adj, Tensor) and adj.dim() == 3:
                 # (asked only when the one-node path takes the call: a launch over the entries, answered in its backward)
                 dense_adj, ei_in, ew_in = adj, sparse_edges[0], sparse_edges[1]
@@ -950,45 +954,37 @@ class _DenseMLPPooling(DenseSRCPooling):
                 # a dense adjacency the caller holds (e.g. one fixed graph pooled every epoch): one pass over it, once
                 # per tensor object, tells whether A = A^T (the backward then forms one N^2 K product less)
                 held = adj
-                symmetry = lambda: K_.AdjSymmetry.of_dense(held)  # noqa: E731
-            if folded is None and _FOLD_TRAINING:  # graphs beyond the one-wave kernels: one autograd node as well (r6)
-                folded = self._select_reduce_connect_large(x, adj, mask, graph_sizes, symmetry=symmetry)
-            so = folded[0] if folded is not None else self.select(x=x, mask=mask)
+                symmetry = lambda: K.AdjSymmetry.of_dense(held)  # noqa: E731
+            if pooled is None and _FOLD_TRAINING:  # graphs beyond the one-wave kernels: one autograd node as well (r6)
+                pooled = self._select_reduce_connect_large(x, adj, mask, graph_sizes, symmetry=symmetry,
+                                                           known_nodes=known_nodes)
+            so = pooled.so if pooled is not None else self.select(x=x, mask=mask)
             self._sizes_hint = None
             if graph_sizes is not None and graph_sizes.numel() == x.size(0):
                 so._graph_sizes = graph_sizes
                 self._sizes_hint = (weakref.ref(adj), graph_sizes)  # valid for exactly this adjacency tensor
-            diff_scales = self._fused_diff_scales(adj, mask)
-            fused = folded[1] if folded is not None else self.reduce_connect(
-                x, adj, so, want_raw=self._wants_raw, want_mincut_terms=self._mincut_terms,
-                want_diff_losses=diff_scales)
-            if fused is None and _FOLD_TRAINING:  # a selector with hidden layers made S: the pooling step is one node still
-                big = self._select_reduce_connect_large(x, adj, mask, graph_sizes, so=so, symmetry=symmetry)
-                if big is not None:
-                    fused = big[1]
-            if fused is not None:  # Reduce + Connect in one native call (training: batches of small graphs only)
-                x_pool, raw, adj_pool = fused[:3]
-                if folded is not None and folded[2] is not None:
-                    batch_pool = folded[2]
-                else:
+            if pooled is None:  # Reduce + Connect in one native call (training: batches of small graphs only)
+                pooled = self._reduce_connect_pooled(x, adj, so, self._wants_raw, self._mincut_terms,
+                                                     self._fused_diff_scales(adj, known_nodes))
+                if pooled is None and _FOLD_TRAINING:  # a selector with hidden layers made S: the pooling step is one node still
+                    pooled = self._select_reduce_connect_large(x, adj, mask, graph_sizes, so=so, symmetry=symmetry,
+                                                               known_nodes=known_nodes)
+            if pooled is not None:
+                x_pool, adj_pool, batch_pool = pooled.x_pool, pooled.adj_pool, pooled.batch_pool
+                if batch_pool is None:
                     batch_pool = self.reducer.reduce_batch(so, batch if batch is not None else so.batch)
-                terms = fused[3] if self._mincut_terms else None
-                diff = fused[-1] if diff_scales is not None else None
-                loss = self._loss_from_fused(adj, so, mask, raw, terms, diff)
+                loss = self._loss_from_fused(adj, so, mask, pooled.raw, pooled.terms, pooled.diff, known_nodes)
             else:
                 x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch)
-                adj_pool, loss = self._batched_connect_and_loss(x, adj, so, mask, edge_weight, batch, batch_pool)
-            if self.sparse_output:
-                x_pool, ei, ew, batch_pool = self._finalize_sparse_output(
-                    x_pool=x_pool, adj_pool=adj_pool, batch=batch, batch_pooled=batch_pool, so=so)
-                return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so, loss=loss)
-            return PoolingOutput(x=x_pool, edge_index=adj_pool, so=so, loss=loss)
+                adj_pool, loss = self._batched_connect_and_loss(x, adj, so, mask, edge_weight, batch, batch_pool,
+                                                                known_nodes)
+            return self._batched_output(x_pool, adj_pool, so, loss, batch, batch_pool)
         # unbatched: S [N,K], sparse A, sparse losses
-        fused = self._unbatched_fused(x, adj, edge_weight, batch)
-        if fused is not None and len(fused) == 5:  # the losses from the products the Connect forms anyway (r6)
-            so, x_pool, adj_pool, batch_pool, loss = fused
-            return PoolingOutput(x=x_pool, edge_index=adj_pool, edge_weight=None, batch=batch_pool, so=so, loss=loss)
-        so = fused[0] if fused is not None else self.select(x=x, batch=batch)
+        pooled = self._unbatched_fused(x, adj, edge_weight, batch)
+        if pooled is not None and pooled.x_pool is not None:  # the losses from the products the Connect forms anyway (r6)
+            return PoolingOutput(x=pooled.x_pool, edge_index=pooled.adj_pool, edge_weight=None, batch=pooled.batch_pool,
+                                 so=pooled.so, loss=pooled.loss)
+        so = pooled.so if pooled is not None else self.select(x=x, batch=batch)
         loss = self._sparse_loss(adj, edge_weight, so.s, batch)
         x_pool, batch_pool = self.reduce(x=x, so=so, batch=batch, return_batched=not self.sparse_output)
         ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
@@ -1011,24 +1007,35 @@ class DiffPool(_DenseMLPPooling):
         self.ent_loss_coeff = ent_loss_coeff
         self.normalize_loss = normalize_loss
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
-                                   batch_pooled=batch_pooled)
-        loss = self.compute_loss(adj=adj, S=so.s, num_nodes=self._real_nodes(mask))
-        return adj_pool, loss
+    _connects_through_operator = True
+    _sparse_diff_stats = True
+    _rows_mode = 2
 
-    def _fused_diff_scales(self, adj, mask, adj_numel=None):
-        num_nodes = self._real_nodes(mask)
-        if not (isinstance(num_nodes, int) and num_nodes > 0):
-            return None
-        numel = adj.numel() if adj_numel is None else adj_numel
-        link_scale = self.link_loss_coeff / numel if self.normalize_loss is True else self.link_loss_coeff
+    def _loss_scales(self, adj_numel, num_nodes):
+        """(link_scale, ent_scale): the coefficients with the two normalisations folded in (``adj_numel``: adj.numel()
+        of the padded batch, losses.py:651, or a callable asked only when the link loss is normalised)."""
+        link_scale = self.link_loss_coeff
+        if self.normalize_loss is True:
+            link_scale = link_scale / (adj_numel() if callable(adj_numel) else adj_numel)
         return (float(link_scale), float(self.ent_loss_coeff) / num_nodes)
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
-        if diff is not None:  # both losses came with the fused training call (and are differentiated by its backward)
-            return {"link_loss": diff[0], "entropy_loss": diff[1]}
-        return self.compute_loss(adj=adj, S=so.s, num_nodes=self._real_nodes(mask))
+    def _fused_diff_scales(self, adj, known_nodes, adj_numel=None):
+        if not (isinstance(known_nodes, int) and known_nodes > 0):
+            return None
+        return self._loss_scales(adj.numel() if adj_numel is None else adj_numel, known_nodes)
+
+    def _sparse_launch_loss(self, s, mask, raw, terms, stats, edges, info, num_nodes) -> dict:
+        # inference (r6): both losses from per-graph records of the same launch -- no dense adjacency
+        scales = self._loss_scales(info.num_graphs * info.max_nodes * info.max_nodes, num_nodes)
+        return self._pair_loss(K.diffpool_stats_tail(stats, scales[0], scales[1]))
+
+    def _pair_loss(self, both) -> dict:
+        return {"link_loss": both[0], "entropy_loss": both[1]}
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
+        if diff is not None:  # both losses came with the fused call (and are differentiated by its backward)
+            return self._pair_loss(diff)
+        return self.compute_loss(adj=adj, S=so.s, num_nodes=self._real_nodes(known_nodes, mask))
 
     def compute_loss(self, adj: Tensor, S: Tensor, num_nodes: int) -> dict:
         if (S.is_cuda and S.dim() == 3 and S.dtype == torch.float32 and adj.dim() == 3 and adj.is_contiguous()
@@ -1036,10 +1043,8 @@ class DiffPool(_DenseMLPPooling):
                 and not (torch.is_grad_enabled() and (S.requires_grad or adj.requires_grad))):
             # inference: both losses from their native partial reductions and one tail launch (as torch ops behind
             # the kernels: sum, sqrt, a final-sum kernel, a division and two multiplications)
-            from .. import kernels as K
-            link_scale = self.link_loss_coeff / adj.numel() if self.normalize_loss is True else self.link_loss_coeff
-            both = K.diffpool_loss_tail(S, adj, self._sizes_for(adj), link_scale, self.ent_loss_coeff / num_nodes)
-            return {"link_loss": both[0], "entropy_loss": both[1]}
+            link_scale, ent_scale = self._loss_scales(adj.numel(), num_nodes)
+            return self._pair_loss(K.diffpool_loss_tail(S, adj, self._sizes_for(adj), link_scale, ent_scale))
         return {"link_loss": link_pred_loss(S, adj, normalize_loss=self.normalize_loss,
                                             graph_sizes=self._sizes_for(adj)) * self.link_loss_coeff,
                 "entropy_loss": entropy_loss(S, num_nodes) * self.ent_loss_coeff}
@@ -1073,24 +1078,21 @@ class MinCutPooling(_DenseMLPPooling):
         return self.lift(x_pool=x, so=so, batch=batch if batch is not None else so.batch,
                          batch_pooled=batch_pooled)
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        c = self.connector
-        raw = c.dense_connect(adj=adj, s=so.s)
-        loss = self.compute_loss(adj, so.s, raw)
-        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
-                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
-                                              edge_weight_norm=c.edge_weight_norm)
-        return adj_pool, loss
-
     _loss_kind = "mincut"
+    _rows_mode = 1
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+    def _pair_loss(self, both) -> dict:
+        return {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
+                "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
+
+    def _sparse_launch_loss(self, s, mask, raw, terms, stats, edges, info, num_nodes) -> dict:
+        return self._pair_loss(terms.mean(dim=1))
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
         if terms is not None and so.s.dtype == torch.float32:
             # both per-graph loss tails came out of the pooling kernel itself (batches of small graphs); under autograd
             # their batch means arrive as two 0-dim outputs of the fused Function (functions.LossPair)
-            both = terms if isinstance(terms, LossPair) else terms.mean(dim=1)
-            return {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
-                    "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
+            return self._pair_loss(terms if isinstance(terms, LossPair) else terms.mean(dim=1))
         return self.compute_loss(adj, so.s, raw)
 
     def compute_loss(self, adj: Tensor, S: Tensor, adj_pooled: Tensor) -> dict:
@@ -1098,15 +1100,11 @@ class MinCutPooling(_DenseMLPPooling):
                 and not (torch.is_grad_enabled() and (S.requires_grad or adj.requires_grad
                                                        or adj_pooled.requires_grad))):
             # inference: both losses' per-graph tails in one launch (as torch ops: ~14 launches of a few hundred bytes)
-            both = mincut_loss_terms(adj, S, adj_pooled, graph_sizes=self._sizes_for(adj)).mean(dim=1)
-            return {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
-                    "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
+            return self._pair_loss(mincut_loss_terms(adj, S, adj_pooled, graph_sizes=self._sizes_for(adj)).mean(dim=1))
         if (S.is_cuda and S.dim() == 3 and S.dtype == torch.float32 and adj.dim() == 3 and not adj.requires_grad
                 and adj_pooled.dtype == torch.float32 and adj_pooled.dim() == 3):
             # training: both losses as one Function with a native backward tail (the adjacency gets no gradient there)
-            both = _MinCutTermsFn.apply(adj, S, adj_pooled, self._sizes_for(adj)).mean(dim=1)
-            return {"cut_loss": both[0] if self.cut_loss_coeff == 1 else both[0] * self.cut_loss_coeff,
-                    "ortho_loss": both[1] if self.ortho_loss_coeff == 1 else both[1] * self.ortho_loss_coeff}
+            return self._pair_loss(_MinCutTermsFn.apply(adj, S, adj_pooled, self._sizes_for(adj)).mean(dim=1))
         return {"cut_loss": mincut_loss(adj, S, adj_pooled, batch_reduction="mean",
                                         graph_sizes=self._sizes_for(adj)) * self.cut_loss_coeff,
                 "ortho_loss": orthogonality_loss(S, batch_reduction="mean",
@@ -1141,25 +1139,21 @@ class DMoNPooling(_DenseMLPPooling):
         self.ortho_loss_coeff = ortho_loss_coeff
         self.cluster_loss_coeff = cluster_loss_coeff
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        c = self.connector
-        raw = c.dense_connect(adj=adj, s=so.s)
-        loss = self.compute_loss(adj, so.s, raw, mask)
-        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
-                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
-                                              edge_weight_norm=c.edge_weight_norm)
-        return adj_pool, loss
+    def _sparse_launch_loss(self, s, mask, raw, terms, stats, edges, info, num_nodes) -> dict:
+        # raw from the launch, degrees from the edge list: no dense adjacency either
+        edge_index, edge_weight, edge_ptr = edges
+        deg = K.dmon_edge_degrees(edge_index, edge_weight, info.ptr, edge_ptr, info.max_nodes, self.adj_transpose)
+        return self._dmon_means(s, raw, mask, info.sizes, deg=deg)
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
-        if terms is not None:  # the one-launch sparse route: the three batch means, coefficients applied
-            return {"spectral_loss": terms[0], "cluster_loss": terms[1], "ortho_loss": terms[2]}
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
         return self.compute_loss(adj, so.s, raw, mask)
 
-    def _dmon_means(self, S, raw, mask, graph_sizes, adj=None, deg=None) -> Tensor:
-        """[3]: the batch means of the three terms (coefficients applied) from one pass over adj or the given degrees,
-        one over S, S^T S and one tail launch."""
+    def _dmon_means(self, S, raw, mask, graph_sizes, adj=None, deg=None) -> dict:
+        """The batch means of the three terms (coefficients applied) from one pass over adj or the given degrees, one
+        over S, S^T S and one tail launch."""
         coeffs = (self.spectral_loss_coeff, self.cluster_loss_coeff, self.ortho_loss_coeff)
-        return dmon_loss_terms(adj, S, raw, mask, graph_sizes, coeffs, deg=deg).mean(dim=1)
+        three = dmon_loss_terms(adj, S, raw, mask, graph_sizes, coeffs, deg=deg).mean(dim=1)
+        return {"spectral_loss": three[0], "cluster_loss": three[1], "ortho_loss": three[2]}
 
     def _scaled(self, spectral, cluster, ortho) -> dict:
         return {"spectral_loss": spectral if self.spectral_loss_coeff == 1 else spectral * self.spectral_loss_coeff,
@@ -1170,8 +1164,7 @@ class DMoNPooling(_DenseMLPPooling):
         if (_native_f32(adj, S, adj_pooled) and S.dim() == 3 and adj.dim() == 3 and adj_pooled.dim() == 3
                 and not adj.requires_grad):
             # the three per-graph tails from one pass over adj, one over S, S^T S and one tail launch (native backward)
-            three = self._dmon_means(S, adj_pooled, mask, self._sizes_for(adj), adj=adj)
-            return {"spectral_loss": three[0], "cluster_loss": three[1], "ortho_loss": three[2]}
+            return self._dmon_means(S, adj_pooled, mask, self._sizes_for(adj), adj=adj)
         return self._scaled(spectral_loss(adj, S, adj_pooled, mask, batch_reduction="mean"),
                             cluster_loss(S, mask=mask, batch_reduction="mean"),
                             orthogonality_loss(S, batch_reduction="mean"))
@@ -1210,25 +1203,27 @@ class JustBalancePooling(_DenseMLPPooling):
         self.normalize_loss = normalize_loss
         self.loss_coeff = loss_coeff
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
-                                   batch_pooled=batch_pooled)
-        return adj_pool, self._loss_of(so, mask, self._sizes_for(adj))
+    _connects_through_operator = True
+    _rows_mode = 0
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
-        if terms is not None:  # the one-launch sparse route: the batch mean, loss_coeff applied
-            return {"balance_loss": terms}
-        return self._loss_of(so, mask, self._sizes_for(adj))
+    def _sparse_launch_loss(self, s, mask, raw, terms, stats, edges, info, num_nodes) -> dict:
+        # the launch writes S; the loss reads nothing else: no dense adjacency, no raw
+        return self._jb_mean(s, mask, info.sizes)
 
-    def _loss_of(self, so, mask, graph_sizes) -> dict:
+    def _rows_staged_loss(self, s, ptr, max_nodes) -> dict:
+        return {"balance_loss": K.jb_terms(s, ptr=ptr, max_nodes=max_nodes, normalize=bool(self.normalize_loss),
+                                           scale=float(self.loss_coeff), want_coef=False, want_mean=True)[2]}
+
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
+        graph_sizes = self._sizes_for(adj)
         if graph_sizes is not None and _jb_native(so.s):
             # (the selector zeroed the padded rows of its own S, so the pass over S stops at each graph's size)
-            return {"balance_loss": self._jb_mean(so.s, mask, graph_sizes)}
+            return self._jb_mean(so.s, mask, graph_sizes)
         return self.compute_loss(so.s, mask, so.num_nodes, so.num_supernodes)
 
-    def _jb_mean(self, S, mask, graph_sizes) -> Tensor:
+    def _jb_mean(self, S, mask, graph_sizes) -> dict:
         """The batch mean of the per-graph loss, ``loss_coeff`` applied by the loss kernel itself."""
-        return jb_loss_mean(S, mask, graph_sizes, None, self.normalize_loss, scale=self.loss_coeff)
+        return {"balance_loss": jb_loss_mean(S, mask, graph_sizes, None, self.normalize_loss, scale=self.loss_coeff)}
 
     def compute_loss(self, S: Tensor, mask: Optional[Tensor] = None, num_nodes: Optional[int] = None,
                      num_supernodes: Optional[int] = None) -> dict:
@@ -1277,16 +1272,7 @@ class AsymCheegerCutPooling(_DenseMLPPooling):
         self.totvar_coeff = totvar_coeff
         self.balance_coeff = balance_coeff
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        c = self.connector
-        raw = c.dense_connect(adj=adj, s=so.s)
-        loss = self.compute_loss(adj, so.s, mask)
-        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
-                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
-                                              edge_weight_norm=c.edge_weight_norm)
-        return adj_pool, loss
-
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
         return self.compute_loss(adj, so.s, mask)
 
     def _scaled(self, tv, bal) -> dict:
@@ -1343,16 +1329,7 @@ class HOSCPooling(_DenseMLPPooling):
         self.alpha = alpha
         self.hosc_ortho = hosc_ortho
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        c = self.connector
-        raw = c.dense_connect(adj=adj, s=so.s)
-        loss = self.compute_loss(adj, so.s, raw, mask)
-        adj_pool = postprocess_adj_pool_dense(raw, remove_self_loops=c.remove_self_loops,
-                                              degree_norm=c.degree_norm, adj_transpose=c.adj_transpose,
-                                              edge_weight_norm=c.edge_weight_norm)
-        return adj_pool, loss
-
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
         return self.compute_loss(adj, so.s, raw, mask)
 
     def compute_loss(self, adj: Tensor, S: Tensor, adj_pool: Tensor, mask: Optional[Tensor] = None) -> dict:
@@ -1471,12 +1448,9 @@ class BNPool(_DenseMLPPooling):
         ei, ew = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch, batch_pooled=batch_pool)
         return PoolingOutput(x=x_pool, edge_index=ei, edge_weight=ew, batch=batch_pool, so=so, loss=loss)
 
-    def _batched_connect_and_loss(self, x, adj, so, mask, edge_weight, batch, batch_pooled):
-        adj_pool, _ = self.connect(edge_index=adj, so=so, edge_weight=edge_weight, batch=batch,
-                                   batch_pooled=batch_pooled)
-        return adj_pool, self.compute_loss(adj, mask, so)
+    _connects_through_operator = True
 
-    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None) -> dict:
+    def _loss_from_fused(self, adj, so, mask, raw, terms=None, diff=None, known_nodes=None) -> dict:
         return self.compute_loss(adj, mask, so)
 
     def _prior_terms(self, q_z, norm_const, like: Tensor, **where) -> dict:

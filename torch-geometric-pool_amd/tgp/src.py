@@ -5,14 +5,14 @@ from __future__ import annotations
 import os as _os
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Dict, Iterator, List, Optional, Tuple, Union
+from typing import Dict, Iterator, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
 
 from . import functions as Fn
 from . import kernels as K
-from .connect import Connect, SparseConnect, _normalize_pooled_edges
+from .connect import Connect, DenseConnect, SparseConnect, _normalize_pooled_edges
 from .imports import HAS_PYG
 from .lift import Lift
 from .reduce import BaseReduce, Reduce, _SparseReduceFn
@@ -79,6 +79,22 @@ class PoolingOutput:
             from torch_geometric.data import Data
             return Data(**fields)
         return SimpleNamespace(**fields)
+
+
+class _Pooled(NamedTuple):
+    """What a fused route of the dense poolers hands back; a field the route did not produce is None.  ``terms``:
+    MinCut's per-graph terms [2,B], or the ``functions.LossPair`` of their batch means under autograd; ``diff``:
+    DiffPool's two losses; ``batch_pool``: the pooled batch vector when the route wrote it; ``loss``: the finished dict
+    when the route makes it (``terms`` and ``diff`` are then left unset).  Only ``so`` set: the route could do Select
+    alone."""
+    so: SelectOutput
+    x_pool: Optional[Tensor] = None
+    raw: Optional[Tensor] = None
+    adj_pool: Optional[Tensor] = None
+    terms: object = None
+    diff: object = None
+    batch_pool: Optional[Tensor] = None
+    loss: Optional[dict] = None
 
 
 class SRCPooling(torch.nn.Module):
@@ -393,17 +409,13 @@ class DenseSRCPooling(SRCPooling):
         self.preprocessing_cache = None
 
     def reduce_connect(self, x: Tensor, adj: Tensor, so: SelectOutput, want_raw: bool = False,
-                       out_x: Optional[Tensor] = None, out_adj: Optional[Tensor] = None,
-                       want_mincut_terms: bool = False, want_diff_losses=None):
+                       out_x: Optional[Tensor] = None, out_adj: Optional[Tensor] = None):
         """Reduce + Connect of a padded dense batch as ONE native call (fused A3 + A7 + A8):
         ``(x_pool [B,K,F], raw S^T A S or None, adj_pool [B,K,K])``.  ``U = A S`` is formed once and
         ``S^T [U | X]`` runs as a single grid (one wave per graph when the graphs fit in LDS), so S is read
         once for both products.  Used by the dense poolers' forward whenever no gradient is required; under
         autograd the separately differentiable ``reduce`` / ``connect`` operators are used instead and this
         returns None."""
-        from .connect import DenseConnect
-        from .reduce import BaseReduce
-        from . import kernels as K
         c = self.connector
         s = so.s
         if not (type(c) is DenseConnect and type(self.reducer) is BaseReduce and isinstance(s, Tensor)
@@ -420,39 +432,55 @@ class DenseSRCPooling(SRCPooling):
                     or s.dtype != torch.float32 or x.dtype != torch.float32 or adj.dtype != torch.float32
                     or not K.dense_pool_is_small(s.size(0), s.size(1), s.size(2), x.size(2))):
                 return None
-            # want_diff_losses = (link_scale, ent_scale): DiffPool's two losses ride along as a last value [2]
-            # (the auxiliary losses come as functions.LossPair: two 0-dim outputs of the fused Function)
-            x_pool, raw, adj_pool, terms, diff = Fn.dense_pool_small(
-                s, adj, x, flags, want_raw, want_mincut_terms, want_diff_losses, getattr(so, "_graph_sizes", None),
-                loss_scalars=True)
-            res = (x_pool, raw if want_raw else None, adj_pool)
-            if want_mincut_terms:
-                res = res + (terms,)
-            return res + (diff,) if want_diff_losses is not None else res
+            x_pool, raw, adj_pool, _, _ = Fn.dense_pool_small(
+                s, adj, x, flags, want_raw, False, None, getattr(so, "_graph_sizes", None), loss_scalars=True)
+            return x_pool, raw if want_raw else None, adj_pool
         # out_x / out_adj (optional, float32 [B,K,F] / [B,K,K]): the kernels write the pooled outputs straight into
         # caller memory, e.g. the next slot of distributed.PackedGather's send buffer (no pack copy before the RCCL call)
-        diff = None
-        if (want_diff_losses is not None and not want_mincut_terms and out_x is None and out_adj is None
-                and s.dtype == torch.float32 and x.dtype == torch.float32 and adj.dtype == torch.float32):
-            # DiffPool, inference, a batch of small graphs (r6): both losses from the pooling launch's per-graph records
-            # (stats is None when the batch takes another kernel: the caller's own tail computes them then)
-            out = K.dense_pool(s, adj, x, flags, want_raw=want_raw, want_post=True,
-                               graph_sizes=getattr(so, "_graph_sizes", None), diff_stats=True)
-            if out[3] is not None:
-                diff = K.diffpool_stats_tail(out[3], want_diff_losses[0], want_diff_losses[1])
-        else:
-            out = K.dense_pool(s, adj, x, flags, want_raw=want_raw, want_post=True,
-                               graph_sizes=getattr(so, "_graph_sizes", None), out_x=out_x, out_adj=out_adj,
-                               mincut_terms=want_mincut_terms)
-        x_pool, raw, adj_pool = out[:3]
+        x_pool, raw, adj_pool = K.dense_pool(s, adj, x, flags, want_raw=want_raw, want_post=True,
+                                             graph_sizes=getattr(so, "_graph_sizes", None), out_x=out_x, out_adj=out_adj)
         # fp32 arithmetic (fp64 when an operand is float64); results carry the dtypes the reference's ATen ops would return
-        res = (like_input_dtype(x_pool, x), like_input_dtype(raw, s), like_input_dtype(adj_pool, s))
-        # want_mincut_terms: a fourth value, the [2,B] loss tails from inside the pooling kernel (None when the batch
-        # does not take the one-wave-per-graph kernel); want_diff_losses: a last value, None on this (no-grad) path --
-        # the caller's own inference tail computes the two losses
-        if want_mincut_terms:
-            res = res + (out[3],)
-        return res + (diff,) if want_diff_losses is not None else res
+        return like_input_dtype(x_pool, x), like_input_dtype(raw, s), like_input_dtype(adj_pool, s)
+
+    def _reduce_connect_pooled(self, x: Tensor, adj: Tensor, so: SelectOutput, want_raw: bool, mincut_terms: bool,
+                               diff_scales) -> Optional[_Pooled]:
+        """:meth:`reduce_connect` as a :class:`_Pooled` record, for the poolers whose losses ride on the pooling call:
+        ``mincut_terms`` asks for MinCut's per-graph terms [2,B] (``terms``: None when the batch does not take the
+        one-wave-per-graph kernel; a ``functions.LossPair`` of the two batch means under autograd), ``diff_scales`` =
+        (link_scale, ent_scale) for DiffPool's two losses (``diff``: [2], or a ``LossPair`` under autograd; None when the
+        batch takes another kernel -- the caller's own tail computes them then).  A pooler that asks for neither gets
+        the public method's three values."""
+        if not mincut_terms and diff_scales is None:
+            res = self.reduce_connect(x, adj, so, want_raw)
+            return None if res is None else _Pooled(so, res[0], res[1], res[2])
+        c = self.connector
+        s = so.s
+        # (the public method's gate and its two branches, with the loss outputs switched on)
+        if not (type(c) is DenseConnect and type(self.reducer) is BaseReduce and isinstance(s, Tensor)
+                and not s.is_sparse and s.dim() == 3 and adj.dim() == 3 and x.dim() == 3 and s.is_cuda):
+            return None
+        if s.size(0) != adj.size(0):
+            raise ValueError("Assignment and adjacency batch sizes do not match: "
+                             f"got s.size(0)={s.size(0)} and adj.size(0)={adj.size(0)}.")
+        flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
+        sizes = getattr(so, "_graph_sizes", None)
+        if torch.is_grad_enabled() and (s.requires_grad or adj.requires_grad or x.requires_grad):
+            if (adj.requires_grad or c.edge_weight_norm
+                    or s.dtype != torch.float32 or x.dtype != torch.float32 or adj.dtype != torch.float32
+                    or not K.dense_pool_is_small(s.size(0), s.size(1), s.size(2), x.size(2))):
+                return None
+            x_pool, raw, adj_pool, terms, diff = Fn.dense_pool_small(s, adj, x, flags, want_raw, mincut_terms, diff_scales,
+                                                                     sizes, loss_scalars=True)
+            return _Pooled(so, x_pool, raw if want_raw else None, adj_pool, terms if mincut_terms else None,
+                          diff if diff_scales is not None else None)
+        # DiffPool, inference, a batch of small graphs (r6): both losses from the pooling launch's per-graph records
+        # (float32 only; the records are None when the batch takes another kernel)
+        stats = not mincut_terms and s.dtype == torch.float32 and x.dtype == torch.float32 and adj.dtype == torch.float32
+        x_pool, raw, adj_pool, *extra = K.dense_pool(s, adj, x, flags, want_raw=want_raw, want_post=True, graph_sizes=sizes,
+                                                     mincut_terms=mincut_terms, diff_stats=stats)
+        terms = extra[0] if mincut_terms else None
+        diff = K.diffpool_stats_tail(extra[0], diff_scales[0], diff_scales[1]) if stats and extra[0] is not None else None
+        return _Pooled(so, like_input_dtype(x_pool, x), like_input_dtype(raw, s), like_input_dtype(adj_pool, s), terms, diff)
 
     def _finalize_sparse_output(self, x_pool: Tensor, adj_pool: Tensor, batch: Optional[Tensor],
                                 batch_pooled: Optional[Tensor], so: SelectOutput):
