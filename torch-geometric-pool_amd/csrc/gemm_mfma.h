@@ -481,11 +481,21 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   // 0-31 read row wave + NW 2i, lanes 32-63 row wave + NW (2i + 1)), then the set bits of each half, one k per
   // iteration, the A value taken from its lane (uniform k: v_readlane), the Bm row from LDS (one read per lane).
   // Each output element has one owner lane: no atomics, a fixed order.
+  // The row reads of all ballots go out together, ahead of the first ballot.  Read one by one, each in front of its own
+  // ballot, they were S_ROWS / 2 LDS round trips in a row in every sparse k-step: 2 to 3 us of the C2 launch at every
+  // density below the threshold (profiles/adj_ring.md, which also has what did not pay: batching the Bm row reads).
   auto sparse_chunk = [&](auto As, auto Bs) {
+    float va[S_ROWS / 2];
 #pragma unroll
     for (int i = 0; i < S_ROWS / 2; ++i) {
       const int row = wave + NW * (2 * i + (lane >> 5)), k = lane & 31;
-      const float v = A_KMAJOR ? As[k * LDA_KM + row] : As[row * LDA_ROWMAJOR + k];
+      va[i] = A_KMAJOR ? As[k * LDA_KM + row] : As[row * LDA_ROWMAJOR + k];
+    }
+#pragma unroll
+    for (int i = 0; i < S_ROWS / 2; ++i) asm volatile("" : "+v"(va[i]));  // (keeps the reads from sinking to their ballots)
+#pragma unroll
+    for (int i = 0; i < S_ROWS / 2; ++i) {
+      const float v = va[i];
       const unsigned long long nz = __ballot(v != 0.f);
       const int vbits = __float_as_int(v);
 #pragma unroll
