@@ -1502,6 +1502,63 @@ int tgp_sag_score_bwd_x_f32(const float* g_q, const float* g_p, const float* w_r
                             int64_t F, int accumulate, float* g_x, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * ASAPooling's fitness (reference poolers/asap.py:205-237 with PyG's LEConv at one output channel), csrc/asap.hip.
+ * fp32, no float atomics, the same bits on every call; nothing of size E x F is formed and the F x F Linear is never
+ * applied to a row.  Every entry takes an edge group as the SAG aggregate does: group i = positions
+ * grp_perm[grp_ptr[i] .. grp_ptr[i+1]) of the edge list (grp_perm NULL: the positions themselves), src the endpoint
+ * gathered through a position.  A position outside [0, E) or an endpoint outside its range is skipped, never
+ * dereferenced.
+ *   query         sq[i] = <max over group i of x_pool[src,:], w_tilde> + c[0]; an empty group gives c[0]; a NaN among
+ *                 the candidates of a column gives NaN (torch's amax).  Rows of x_pool have stride ldx >= F; 16-byte
+ *                 loads under row_project2's rule.
+ *                 With argpos ([N,F] int32) it also writes the edge POSITION that gave each maximum: the lowest
+ *                 position among equal candidates, the lowest NaN position when a NaN wins, -1 for an empty group.
+ *                 Positions, not source ids: a by-source backward that matched ids would count a duplicate edge twice.
+ *   edge_softmax  alpha[pos] = exp(l - m_i) / (sum over group i of exp(l - m_i) + 1e-16), l = leaky_relu(sq[i] + sp[src]),
+ *                 written at the edge's own position (an edge whose endpoint is out of range gets 0).
+ *   attend        out[i,:] = sum over group i of val[pos] x[src,:] (val NULL: 1), out [N,F] contiguous, x [N_src,F] with
+ *                 row stride ldx; with w3 ([3,F] contiguous) also p[k*N + i] = <out[i,:], w3[k,:]>, k = 0, 1, 2, taken from
+ *                 the finished row in registers.  By destination with src = the source row it is x_new; by source with
+ *                 src = the destination row and x = a gradient of x_new it is that gradient's pull-back to x.
+ *   leconv        t[i] = ((p[2N+i] + b3) + sum_e w_e p[src_e]) + (b1 - p[N+i]) sum_e w_e over group i in its order
+ *                 (w_e = edge_weight[pos], or 1), a[i] = act(t[i]), act 0 = identity, 1 = tanh, 2 = sigmoid.
+ *   edge_dot      out[pos] = <g[i,:], x[src,:]> for every edge of group i (g [N,F] contiguous): the backward's g_alpha.
+ *   softmax_bwd   d = sum over group i of alpha g_alpha; g_l[pos] = alpha (g_alpha - d) * (sq[i] + sp[src] > 0 ? 1 :
+ *                 negative_slope); g_sq[i] = sum over group i of g_l.
+ *   query_bwd     out[j,f] = w_tilde[f] * sum over group j (BY SOURCE, dst the gathered endpoint) of g_sq[dst] where
+ *                 argpos[dst,f] is that edge's position: the master query's backward, out [N,F] contiguous.
+ * The orders of the sums are those of csrc/asap.hip's head comment.  One wave walks one group in query, edge_softmax and
+ * attend, whatever its length.
+ * TGP_ERR_INVALID: a NULL input or output, an input given as the output, sizes below zero, ldx < F, an unknown act;
+ * TGP_ERR_RANGE: N or E beyond the int32 index, F >= 2^31.  Both are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_asap_query_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL: list already grouped */,
+                       const int64_t* src, const float* x_pool, int64_t ldx, const float* w_tilde,
+                       const float* c /* one device float */, int64_t N, int64_t E, int64_t F, float* sq,
+                       int32_t* argpos /* NULL ok; [N,F] */, void* stream);
+int tgp_asap_edge_softmax_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                              const float* sq, const float* sp, int64_t N, int64_t E, float negative_slope, float* alpha,
+                              void* stream);
+int tgp_asap_attend_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                        const float* val /* NULL ok */, const float* x, int64_t ldx, const float* w3 /* NULL ok */,
+                        int64_t N, int64_t N_src, int64_t E, int64_t F, float* out, float* p /* NULL iff w3 is */,
+                        void* stream);
+int tgp_asap_leconv_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                        const float* edge_weight /* NULL ok */, const float* p, const float* b1 /* NULL ok */,
+                        const float* b3 /* NULL ok */, int64_t N, int64_t E, int act, float* t_out /* NULL ok */,
+                        float* a_out /* NULL ok, not both */, void* stream);
+
+int tgp_asap_edge_dot_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                          const float* g, const float* x, int64_t ldx, int64_t N, int64_t E, int64_t F, float* out,
+                          void* stream);
+int tgp_asap_softmax_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                             const float* alpha, const float* g_alpha, const float* sq, const float* sp, int64_t N,
+                             int64_t E, float negative_slope, float* g_l, float* g_sq, void* stream);
+int tgp_asap_query_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                           const int32_t* argpos, const float* g_sq, const float* w_tilde, int64_t N, int64_t E,
+                           int64_t F, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Segment readout (reference reduce/aggr_reduce.py, reduce/global_reduce.py over PyG's Sum / Mean / Max / Min /
  * MultiAggregation), csrc/segment_aggr.hip.  fp32, no float atomics, the same bits on every call.
  *   `ops` is a mask of (1 << TGP_SUM) | (1 << TGP_MEAN) | (1 << TGP_MIN) | (1 << TGP_MAX); ONE pass over x fills

@@ -356,6 +356,17 @@ SIGNATURES = {
     "tgp_gather_unpack_bucket_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_p, _c_p, _c_p]),
     "tgp_debug_sort_workspace_bytes": (_c_sz, [_c_i64]),
     "tgp_debug_sort_pairs_u64": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "tgp_asap_query_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
+                                    _c_p]),
+    "tgp_asap_edge_dot_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_asap_softmax_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p,
+                                          _c_p]),
+    "tgp_asap_query_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_asap_edge_softmax_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p]),
+    "tgp_asap_attend_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
+                                     _c_p, _c_p]),
+    "tgp_asap_leconv_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p,
+                                     _c_p]),
     "tgp_row_project2_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "tgp_sag_aggregate_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_p,
                                        _c_p]),

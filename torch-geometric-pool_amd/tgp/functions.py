@@ -681,6 +681,181 @@ def sag_score(x: Tensor, edge_index: Tensor, w_rel: Tensor, w_root: Optional[Ten
     return K.sag_score(x, edge_index, w_rel, w_root, bias, mean, use_tanh)
 
 
+# ------------------------------------------------------------- ASAPooling's fitness (attention + one-channel LEConv)
+def _asap_attention_fwd(x, x_pool, edge_index, lin_w, lin_b, att_w, att_b, negative_slope, mask, proj, want_arg):
+    n, F = x.shape
+    a = att_w.reshape(-1)
+    a1, a2 = a[:F], a[F:]
+    w_tilde = a1 @ lin_w  # [F] = W^T a1
+    c = (a1 @ lin_b if lin_b is not None else a1.new_zeros(())) + (att_b.reshape(()) if att_b is not None else 0.0)
+    sp, _ = K.row_project2(x_pool, a2, a2)
+    row, _ = K._edge_rows(edge_index)
+    grp = K.sag_edge_group(edge_index, n, by_destination=True)
+    got = K.asap_query(grp, row, x_pool, w_tilde, c, want_arg)
+    sq, arg = got if want_arg else (got, None)
+    alpha = K.asap_edge_softmax(grp, row, sq, sp, negative_slope)
+    alpha_m = alpha if mask is None else alpha * mask
+    x_new, p = K.asap_attend(grp, row, x, alpha_m, proj)
+    return alpha, alpha_m, x_new, p, sq, sp, arg, w_tilde
+
+
+class _AsapAttentionFn(torch.autograd.Function):
+    """(x, x_pool, lin, att) -> (x_new, alpha_m, p): ASAPooling's attention as ONE node.  The forward is the four kernels
+    of :func:`asap_attention`; it keeps alpha, sq, sp [E' / N floats] and the int32 arg-max edge positions [N,F] of the
+    master query.  Backward from g = d x_new (alpha_m and p leave the node without a gradient path: alpha_m is returned
+    for inspection, p is a hint for the LEConv node, which differentiates through x_new itself):
+      g_x       = sum over j's out-edges of alpha_m g[dst]             (the attend kernel over the by-source index)
+      g_alpha   = mask <g[dst], x[src]>                                 (edge_dot: the g row in registers)
+      g_l, g_sq = softmax and leaky backward per destination            (softmax_bwd)
+      g_sp[j]   = sum over j's out-edges of g_l                         (the LEConv aggregate kernel with p1 = 1)
+      g_x_pool  = g_sp (x) a2 + the master query's backward by source   (query_bwd, then one outer-product pass)
+    and N- or F-sized algebra as torch operators: g_a2 = x_pool^T g_sp, g_w~ = (max rows)^T g_sq, g_W = a1 (x) g_w~,
+    g_a1 = W g_w~ + b_lin sum g_sq, g_b_lin = a1 sum g_sq, g_b_att = sum g_sq."""
+
+    @staticmethod
+    def forward(ctx, x, x_pool, edge_index, lin_w, lin_b, att_w, att_b, negative_slope, mask, proj):
+        alpha, alpha_m, x_new, p, sq, sp, arg, w_tilde = _asap_attention_fwd(
+            x, x_pool, edge_index, lin_w, lin_b, att_w, att_b, negative_slope, mask, proj, True)
+        ctx.save_for_backward(x, x_pool, edge_index, lin_w, lin_b, att_w, mask, alpha, alpha_m, sq, sp, arg, w_tilde)
+        ctx.slope, ctx.same = float(negative_slope), x_pool is x
+        ctx.has_att_b = att_b is not None
+        if p is None:
+            p = x_new.new_empty(0)
+        ctx.mark_non_differentiable(alpha_m, p)
+        return x_new, alpha_m, p
+
+    @staticmethod
+    def backward(ctx, g, _ga, _gp):
+        x, x_pool, edge_index, lin_w, lin_b, att_w, mask, alpha, alpha_m, sq, sp, arg, w_tilde = ctx.saved_tensors
+        n, F = x.shape
+        g = g.contiguous()
+        row, col = K._edge_rows(edge_index)
+        by_dst = K.sag_edge_group(edge_index, n, by_destination=True)
+        by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+        need = ctx.needs_input_grad
+        gx = gxp = g_lin_w = g_lin_b = g_att_w = g_att_b = None
+        if need[0]:
+            gx, _ = K.asap_attend(by_src, col, g, alpha_m)
+        if any(need[i] for i in (1, 3, 4, 5, 6)) or (ctx.same and need[0]):
+            g_alpha = K.asap_edge_dot(by_dst, row, g, x)
+            if mask is not None:
+                g_alpha = g_alpha * mask
+            g_l, g_sq = K.asap_softmax_bwd(by_dst, row, alpha, g_alpha, sq, sp, ctx.slope)
+            ones = torch.zeros(3, n, dtype=torch.float32, device=x.device)
+            ones[0] = 1.0
+            g_sp = K.asap_leconv(by_src, col, ones, g_l)
+            a = att_w.reshape(-1)
+            a1, a2 = a[:F], a[F:]
+            if need[1] or (ctx.same and need[0]):
+                gxp = K.asap_query_bwd(by_src, col, arg, g_sq, w_tilde)
+                K.sag_score_bwd_x(g_sp, torch.zeros_like(g_sp), a2, a2, gxp)
+                if ctx.same:
+                    gx = gxp if gx is None else gx.add_(gxp)
+                    gxp = None
+            s = g_sq.sum()
+            if need[3] or need[5]:
+                src_of = row[arg.clamp(min=0).long()]  # [N,F]: the source row of every maximum
+                rows_max = x_pool.gather(0, src_of) * (arg >= 0)
+                g_wt = K.weighted_colsum(rows_max, g_sq)
+                if need[3]:
+                    g_lin_w = torch.outer(a1, g_wt)
+                if need[5]:
+                    g_a1 = lin_w @ g_wt + (lin_b * s if lin_b is not None else 0.0)
+                    g_att_w = torch.cat([g_a1, K.weighted_colsum(x_pool, g_sp)]).view_as(att_w)
+            if lin_b is not None and need[4]:
+                g_lin_b = a1 * s
+            if ctx.has_att_b and need[6]:
+                g_att_b = s.reshape(1)
+        # (when x_pool IS x its gradient went into gx and gxp is None)
+        return gx, gxp, None, g_lin_w, g_lin_b, g_att_w, g_att_b, None, None, None
+
+
+def asap_attention(x: Tensor, x_pool: Tensor, edge_index: Tensor, lin_w: Tensor, lin_b: Optional[Tensor], att_w: Tensor,
+                   att_b: Optional[Tensor], negative_slope: float, mask: Optional[Tensor] = None,
+                   proj: Optional[Tensor] = None):
+    """(alpha [E'], x_new [N,F], p [3,N] or None) of ASAPooling's attention on device float32 tensors, ``edge_index`` being
+    the list with its self-loops.  ``att = [a1 | a2]`` is linear, so the logit of edge j -> i is
+    ``leaky(sq[i] + sp[j])`` with ``sq = <x_q, W^T a1> + (<a1, b_lin> + b_att)`` and ``sp = <x_pool, a2>``: four
+    launches (project, master query, edge softmax, attend), one row gather per edge in two of them, nothing of size
+    ``E x F``.  ``mask`` [E'] multiplies alpha between the softmax and the attend kernel (the dropout of training; the
+    returned alpha carries it); ``proj`` [3,F] asks the attend kernel for the projections of the finished rows (LEConv's
+    p1, p2, p3; no gradient flows through them).  Under autograd the whole is one node (:class:`_AsapAttentionFn`)."""
+    if _needs_grad(x, x_pool, lin_w, lin_b, att_w, att_b):
+        x_new, alpha_m, p = _AsapAttentionFn.apply(x, x_pool, edge_index, lin_w, lin_b, att_w, att_b, negative_slope,
+                                                   mask, None if proj is None else proj.detach())
+        return alpha_m, x_new, (p if proj is not None else None)
+    _, alpha_m, x_new, p, _, _, _, _ = _asap_attention_fwd(x, x_pool, edge_index, lin_w, lin_b, att_w, att_b,
+                                                           negative_slope, mask, proj, False)
+    return alpha_m, x_new, p
+
+
+def _asap_projections(x, w3):
+    p12 = K.row_project2(x, w3[0], w3[1])
+    return torch.stack([p12[0], p12[1], K.row_project2(x, w3[2], w3[2])[0]])
+
+
+class _AsapLeconvFn(torch.autograd.Function):
+    """a = act(p3 + b3 + sum_e w_e p1[src_e] + (b1 - p2) W), p_k = <x, w_k>, W_i = the summed weight of i's in-edges: the
+    one-channel LEConv as one node.  Backward from g_t = g act'(a): g_p3 = g_t, g_p2 = -g_t W, g_p1[j] = sum over j's
+    out-edges of w_e g_t[dst] (the forward's aggregate kernel over the by-source index), g_b3 = sum g_t,
+    g_b1 = sum g_t W, g_x = sum_k g_pk (x) w_k (two outer-product passes), g_wk = x^T g_pk.  Edge weights get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, edge_index, edge_weight, w3, b1, b3, act, p):
+        n = x.size(0)
+        row, _ = K._edge_rows(edge_index)
+        grp = K.sag_edge_group(edge_index, n, by_destination=True)
+        if p is None:
+            p = _asap_projections(x, w3)
+        a = K.asap_leconv(grp, row, p, edge_weight, b1, b3, act)
+        ctx.save_for_backward(x, edge_index, edge_weight, w3, a)
+        ctx.act, ctx.has_b = act, (b1 is not None, b3 is not None)
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        x, edge_index, ew, w3, a = ctx.saved_tensors
+        n = x.size(0)
+        gt = (g * (1 - a * a) if ctx.act == "tanh" else g * a * (1 - a) if ctx.act == "sigmoid" else g).contiguous()
+        row, col = K._edge_rows(edge_index)
+        by_dst = K.sag_edge_group(edge_index, n, by_destination=True)
+        by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+        unit = torch.zeros(3, n, dtype=torch.float32, device=x.device)
+        unit[1] = -1.0
+        wsum = K.asap_leconv(by_dst, row, unit, ew)  # (0 - (-1)) W
+        gp = torch.zeros(3, n, dtype=torch.float32, device=x.device)
+        gp[0] = gt
+        g1 = K.asap_leconv(by_src, col, gp, ew)
+        g2 = -(gt * wsum)
+        gx = gw = gb1 = gb3 = None
+        if ctx.needs_input_grad[0]:
+            gx = K.sag_score_bwd_x(g1, g2, w3[0], w3[1])
+            K.sag_score_bwd_x(gt, torch.zeros_like(gt), w3[2], w3[2], gx)
+        if ctx.needs_input_grad[3]:
+            gw = torch.stack([K.weighted_colsum(x, g1), K.weighted_colsum(x, g2), K.weighted_colsum(x, gt)])
+        if ctx.has_b[0] and ctx.needs_input_grad[4]:
+            gb1 = (gt * wsum).sum().reshape(1)
+        if ctx.has_b[1] and ctx.needs_input_grad[5]:
+            gb3 = gt.sum().reshape(1)
+        return gx, None, None, gw, gb1, gb3, None, None
+
+
+def asap_leconv_score(x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], w3: Tensor, b1: Optional[Tensor],
+                      b3: Optional[Tensor], act: str = "identity", p: Optional[Tensor] = None) -> Tensor:
+    """act(LEConv(F, 1)(x, edge_index, edge_weight)) [N] on device float32 tensors as project-then-aggregate; ``w3`` is
+    [3,F] = (lin1, lin2, lin3), ``p`` [3,N] the projections of x on it when the caller has them (the attend kernel emits
+    them).  Under autograd one node (:class:`_AsapLeconvFn`); an ``edge_weight`` that requires grad is refused (the
+    composed form is the caller's route for it)."""
+    if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("asap_leconv_score gives edge weights no gradient: take LEConv's composed form")
+    if _needs_grad(x, w3, b1, b3):
+        return _AsapLeconvFn.apply(x, edge_index, edge_weight, w3, b1, b3, act, None if p is None else p.detach())
+    n = x.size(0)
+    row, _ = K._edge_rows(edge_index)
+    grp = K.sag_edge_group(edge_index, n, by_destination=True)
+    return K.asap_leconv(grp, row, _asap_projections(x, w3) if p is None else p, edge_weight, b1, b3, act)
+
+
 class _TopkPoolTrainFn(torch.autograd.Function):
     """The ONE autograd node of TopK pooling's trained path (r5): x' = s_a x[i_a] and the kept scores s_a = act(x w /
     ||w||)[i_a] (the values of S) as functions of x and the projection w.  The forward values come from the caller --

@@ -4168,8 +4168,140 @@ def sag_score(x: Tensor, edge_index: Tensor, w_rel: Tensor, w_root: Optional[Ten
     return sag_aggregate(grp, row, p, None if w_root is None else q, bias, mean, tanh, want_t)
 
 
+# ------------------------------------------------------------------------- ASAPooling's fitness (csrc/asap.hip)
+ASAP_ACTS = {"identity": 0, "tanh": 1, "sigmoid": 2}
+
+
+def _asap_group(name: str, grp: AssignIndex, src: Tensor) -> Tuple[Tensor, int, int]:
+    src = N.i64c(src)
+    n, E = grp.num_targets, src.numel()
+    if grp.nnz != E or grp.row_ptr.numel() != n + 1:
+        raise ValueError(f"{name}: an index of {grp.nnz} edges over {n} nodes against {E} edges")
+    return src, n, E
+
+
+def asap_query(grp: AssignIndex, src: Tensor, x_pool: Tensor, w_tilde: Tensor, c: Tensor, want_arg: bool = False):
+    """sq[i] = <max over node i's group of x_pool[src], w_tilde> + c (c: one device float).  A NaN among a column's
+    candidates gives NaN, as ``torch.amax`` does; a node without in-edges gives c.  ``want_arg``: ``(sq, argpos)`` with
+    the int32 [n, F] edge positions of the maxima (lowest position on a tie, -1 for a node without in-edges)."""
+    dev = N.require_device(src, x_pool, w_tilde, c, grp.row_ptr)
+    src, n, E = _asap_group("asap_query", grp, src)
+    x_pool, w_tilde, c = _row_major_f32(x_pool), N.f32c(w_tilde.reshape(-1)), N.f32c(c.reshape(-1))
+    if x_pool.size(0) != n or w_tilde.numel() != x_pool.size(1) or c.numel() != 1:
+        raise ValueError(f"asap_query: x_pool {tuple(x_pool.shape)} against {n} nodes, w_tilde of {w_tilde.numel()} and "
+                         f"c of {c.numel()} entries")
+    sq = torch.empty(n, dtype=torch.float32, device=dev)
+    arg = torch.empty(n, x_pool.size(1), dtype=torch.int32, device=dev) if want_arg else None
+    _checked(N.lib().tgp_asap_query_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(x_pool),
+             x_pool.stride(0) if n > 1 else max(x_pool.stride(0), x_pool.size(1)), N.ptr(w_tilde), N.ptr(c), n, E,
+             x_pool.size(1), N.ptr(sq), N.ptr(arg), N.stream_ptr(dev))
+    return (sq, arg) if want_arg else sq
+
+
+def asap_edge_dot(grp: AssignIndex, src: Tensor, g: Tensor, x: Tensor) -> Tensor:
+    """out[pos] = <g[i], x[src[pos]]> for every edge of node i's group: the gradient of the attend kernel's ``val``."""
+    dev = N.require_device(src, g, x, grp.row_ptr)
+    src, n, E = _asap_group("asap_edge_dot", grp, src)
+    g, x = N.f32c(g), _row_major_f32(x)
+    if g.dim() != 2 or g.size(0) != n or x.size(0) != n or g.size(1) != x.size(1):
+        raise ValueError(f"asap_edge_dot: g {tuple(g.shape)} and x {tuple(x.shape)} against {n} nodes")
+    out = torch.empty(E, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_edge_dot_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(g),
+             N.ptr(x), x.stride(0) if n > 1 else max(x.stride(0), x.size(1)), n, E, x.size(1),
+             N.ptr(out) if E else None, N.stream_ptr(dev))
+    return out
+
+
+def asap_softmax_bwd(grp: AssignIndex, src: Tensor, alpha: Tensor, g_alpha: Tensor, sq: Tensor, sp: Tensor,
+                     negative_slope: float) -> Tuple[Tensor, Tensor]:
+    """(g_l [E], g_sq [n]): the backward of :func:`asap_edge_softmax` through the softmax and the leaky ReLU."""
+    dev = N.require_device(src, alpha, g_alpha, sq, sp, grp.row_ptr)
+    src, n, E = _asap_group("asap_softmax_bwd", grp, src)
+    alpha, g_alpha = N.f32c(alpha.reshape(-1)), N.f32c(g_alpha.reshape(-1))
+    sq, sp = N.f32c(sq.reshape(-1)), N.f32c(sp.reshape(-1))
+    if alpha.numel() != E or g_alpha.numel() != E or sq.numel() != n or sp.numel() != n:
+        raise ValueError(f"asap_softmax_bwd: alpha and g_alpha per edge ({E}), sq and sp per node ({n})")
+    g_l = torch.empty(E, dtype=torch.float32, device=dev)
+    g_sq = torch.empty(n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_softmax_bwd_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None,
+             N.ptr(alpha) if E else None, N.ptr(g_alpha) if E else None, N.ptr(sq), N.ptr(sp), n, E,
+             float(negative_slope), N.ptr(g_l) if E else None, N.ptr(g_sq), N.stream_ptr(dev))
+    return g_l, g_sq
+
+
+def asap_query_bwd(by_src: AssignIndex, dst: Tensor, argpos: Tensor, g_sq: Tensor, w_tilde: Tensor) -> Tensor:
+    """g_x_pool [n, F] of :func:`asap_query`: row j collects ``g_sq[dst] * w_tilde[f]`` from the out-edges of j whose
+    position is the arg-max of (dst, f).  ``by_src`` is the by-source group, ``dst`` the destination row."""
+    dev = N.require_device(dst, argpos, g_sq, w_tilde, by_src.row_ptr)
+    dst, n, E = _asap_group("asap_query_bwd", by_src, dst)
+    g_sq, w_tilde = N.f32c(g_sq.reshape(-1)), N.f32c(w_tilde.reshape(-1))
+    F = w_tilde.numel()
+    if argpos.dtype != torch.int32 or tuple(argpos.shape) != (n, F) or not argpos.is_contiguous() or g_sq.numel() != n:
+        raise ValueError(f"asap_query_bwd: argpos must be a contiguous int32 [{n}, {F}], g_sq [{n}]")
+    out = torch.empty(n, F, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_query_bwd_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
+             N.ptr(argpos), N.ptr(g_sq), N.ptr(w_tilde), n, E, F, N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
+def asap_edge_softmax(grp: AssignIndex, src: Tensor, sq: Tensor, sp: Tensor, negative_slope: float) -> Tensor:
+    """alpha [E]: the softmax of leaky_relu(sq[dst] + sp[src]) over every node's group (``+ 1e-16`` in the denominator),
+    at the edges' own positions."""
+    dev = N.require_device(src, sq, sp, grp.row_ptr)
+    src, n, E = _asap_group("asap_edge_softmax", grp, src)
+    sq, sp = N.f32c(sq.reshape(-1)), N.f32c(sp.reshape(-1))
+    if sq.numel() != n or sp.numel() != n:
+        raise ValueError(f"asap_edge_softmax: one sq and one sp per node ({n}), got {sq.numel()} and {sp.numel()}")
+    alpha = torch.empty(E, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_edge_softmax_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None,
+             N.ptr(sq), N.ptr(sp), n, E, float(negative_slope), N.ptr(alpha) if E else None, N.stream_ptr(dev))
+    return alpha
+
+
+def asap_attend(grp: AssignIndex, src: Tensor, x: Tensor, val: Optional[Tensor] = None,
+                proj: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """(out [n, F], p [3, n] or None): out[i] = sum over node i's group of val[pos] x[src] (``val`` None: 1), one row
+    gather per edge; with ``proj`` [3, F] also the three projections of every finished row."""
+    dev = N.require_device(src, x, val, proj, grp.row_ptr)
+    src, n, E = _asap_group("asap_attend", grp, src)
+    x = _row_major_f32(x)
+    F = x.size(1)
+    val = None if val is None else N.f32c(val.reshape(-1))
+    proj = None if proj is None else N.f32c(proj)
+    if (val is not None and val.numel() != E) or (proj is not None and tuple(proj.shape) != (3, F)):
+        raise ValueError(f"asap_attend: one value per edge ({E}) and projections [3, {F}]")
+    out = torch.empty(n, F, dtype=torch.float32, device=dev)
+    p = None if proj is None else torch.empty(3, n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_attend_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(val),
+             N.ptr(x), x.stride(0) if x.size(0) > 1 else max(x.stride(0), F), N.ptr(proj), n, x.size(0), E, F,
+             N.ptr(out), N.ptr(p), N.stream_ptr(dev))
+    return out, p
+
+
+def asap_leconv(grp: AssignIndex, src: Tensor, p: Tensor, edge_weight: Optional[Tensor] = None,
+                b1: Optional[Tensor] = None, b3: Optional[Tensor] = None, act: str = "identity",
+                want_t: bool = False):
+    """a = act(((p3 + b3) + sum_e w_e p1[src_e]) + (b1 - p2) sum_e w_e) over every node's group in its order; ``p`` is
+    [3, n].  ``want_t``: ``(t, a)`` with the pre-activation as well."""
+    if act not in ASAP_ACTS:
+        raise ValueError(f"asap_leconv: act {act!r} is not one of {sorted(ASAP_ACTS)}")
+    dev = N.require_device(src, p, edge_weight, b1, b3, grp.row_ptr)
+    src, n, E = _asap_group("asap_leconv", grp, src)
+    p = N.f32c(p)
+    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if tuple(p.shape) != (3, n) or (ew is not None and ew.numel() != E):
+        raise ValueError(f"asap_leconv: p must be [3, {n}] and edge_weight [{E}]")
+    b1 = None if b1 is None else N.f32c(b1.reshape(-1))
+    b3 = None if b3 is None else N.f32c(b3.reshape(-1))
+    out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_asap_leconv_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(ew),
+             N.ptr(p), N.ptr(b1), N.ptr(b3), n, E, ASAP_ACTS[act], N.ptr(out[0]) if want_t else None, N.ptr(out[-1]),
+             N.stream_ptr(dev))
+    return (out[0], out[1]) if want_t else out[0]
+
+
 # ------------------------------------------------------------------------- segment readout (csrc/segment_aggr.hip)
-SEGMENT_OPS = ("sum", "mean", "min", "max")  # the order of their enum values = the order of the output's column blocks
+SEGMENT_OPS =("sum", "mean", "min", "max")  # the order of their enum values = the order of the output's column blocks
 
 
 def segment_ops_mask(ops: Sequence[str]) -> int:

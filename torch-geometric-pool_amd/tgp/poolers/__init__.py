@@ -1,12 +1,12 @@
 """Pooling layers of the north-star path and the ``get_pooler`` factory
-(reference tgp/poolers/{__init__,topk,sag,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,just_balance,edge_contraction,lapool}.py).
+(reference tgp/poolers/{__init__,topk,sag,asap,graclus,ndp,diffpool,mincut,dmon,asym_cheeger_cut,hosc,bnpool,just_balance,edge_contraction,lapool}.py).
 
 ``get_pooler`` knows the five poolers named by the hot path: ``topk``, ``graclus``, ``ndp``, ``diff``,
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
-``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling`` and ``SAGPooling`` are built
-and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` aliases
-are not registered yet.
+``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling``, ``SAGPooling`` and ``ASAPooling``
+(``tgp/poolers/asap.py``) are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` /
+``edgepool`` / ``lap`` / ``sag`` / ``asap`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -65,6 +65,7 @@ from ..utils.losses import (
 )
 from ..utils.ops import connectivity_to_edge_index, postprocess_adj_pool_dense
 from ..functions import LossPair
+from .asap import ASAPooling
 
 import os as _os
 
@@ -1570,8 +1571,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling) and "sag" (SAGPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling) and "asap" (ASAPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,

@@ -1,4 +1,5 @@
 from .ops import (
+    add_remaining_self_loops,
     apply_dense_node_mask,
     batched_negative_edge_sampling,
     build_pooled_batch,
@@ -21,7 +22,7 @@ from .ops import (
 from .signature import Signature, foo_signature
 
 __all__ = [
-    "apply_dense_node_mask", "batched_negative_edge_sampling", "build_pooled_batch", "check_and_filter_edge_weights",
+    "add_remaining_self_loops", "apply_dense_node_mask", "batched_negative_edge_sampling", "build_pooled_batch", "check_and_filter_edge_weights",
     "connectivity_to_edge_index", "connectivity_to_sparsetensor", "connectivity_to_torch_coo",
     "dense_to_block_diag", "expand_compacted_rows", "get_mask_from_dense_s", "is_dense_adj",
     "is_multi_graph_batch", "negative_edge_sampling", "postprocess_adj_pool_dense", "postprocess_adj_pool_sparse", "pseudo_inverse",

@@ -300,6 +300,61 @@ def connectivity_to_edge_index(edge_index, edge_weight: Optional[Tensor] = None)
     raise NotImplementedError()
 
 
+_LOOPED_EDGES = TensorMemo(16)  # edge_index (+ edge_weight, (N, fill)) -> (augmented edge_index, augmented weights)
+
+
+def _add_remaining_self_loops(edge_index: Tensor, edge_weight: Optional[Tensor], fill_value: float, n: int):
+    """PyG's ``add_remaining_self_loops``: the non-loop edges in their order, then one loop per node.  A node that had
+    loops keeps the weight of its LAST one (what PyG's indexed assignment leaves on the host; taken here as the maximum
+    position so that a device gives the same answer on every call)."""
+    row, col = edge_index[0], edge_index[1]
+    keep = row != col
+    loop = torch.arange(n, dtype=edge_index.dtype, device=edge_index.device)
+    out = torch.cat([edge_index[:, keep], loop.view(1, -1).expand(2, -1)], dim=1)
+    if edge_weight is None:
+        return out, None
+    loop_w = edge_weight.new_full((n,) + tuple(edge_weight.shape[1:]), fill_value)
+    at = (~keep).nonzero().view(-1)
+    if at.numel():
+        last = torch.full((n,), -1, dtype=torch.long, device=at.device).scatter_reduce(
+            0, row[at], at, reduce="amax", include_self=True)
+        has = last >= 0
+        loop_w = torch.where(has.view((-1,) + (1,) * (edge_weight.dim() - 1)), edge_weight[last.clamp(min=0)], loop_w)
+    return out, torch.cat([edge_weight[keep], loop_w], dim=0)
+
+
+def add_remaining_self_loops(edge_index, edge_weight: Optional[Tensor] = None, fill_value: float = 1.0,
+                             num_nodes: Optional[int] = None):
+    """A loop of weight ``fill_value`` on every node that has none; existing loops keep their weight and move to the end
+    (reference utils/ops.py:1000-1040).  ``[2, E]`` tensors give ``(edge_index, edge_weight)`` (``None`` weights stay
+    ``None``), a torch COO adjacency gives ``(coalesced COO, None)``.
+
+    The result for a ``[2, E]`` list is remembered per (``edge_index``, ``edge_weight``, ``N``, ``fill_value``) object and
+    version: full-batch training hands the same list in every step, and everything remembered per edge list downstream
+    (the edge groups of the ASAP and SAG kernels) keys on the augmented object.  An ``edge_weight`` that requires grad
+    is never remembered, nor is anything while a stream is capturing."""
+    if is_sparsetensor(edge_index):
+        if num_nodes is not None and num_nodes != edge_index.size(0):
+            edge_index = edge_index.sparse_resize((num_nodes, num_nodes))
+        return edge_index.fill_diag(fill_value), None
+    if isinstance(edge_index, Tensor) and edge_index.is_sparse:
+        indices, values = edge_index.indices(), edge_index.values()
+        n = maybe_num_nodes(indices, num_nodes)
+        li, lw = _add_remaining_self_loops(indices, values, fill_value, n)
+        return torch.sparse_coo_tensor(li, lw, size=(n, n), device=edge_index.device).coalesce(), None
+    n = maybe_num_nodes(edge_index, num_nodes)
+    extra = (int(n), float(fill_value))
+    remember = not (edge_weight is not None and edge_weight.requires_grad)
+    if remember:
+        hit = _LOOPED_EDGES.get(edge_index, edge_weight, extra)
+        if hit is not None:
+            return hit
+    out = _add_remaining_self_loops(edge_index, edge_weight, fill_value, n)
+    if remember and not (edge_index.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _LOOPED_EDGES.put(edge_index, out, edge_weight, extra)
+    return out
+
+
 def connectivity_to_torch_coo(edge_index, edge_weight: Optional[Tensor] = None,
                               num_nodes: Optional[int] = None) -> Tensor:
     if not isinstance(edge_index, Tensor) and not is_sparsetensor(edge_index):
