@@ -1600,6 +1600,55 @@ int tgp_segment_aggr_bwd_f32(const float* g_out, const float* x, int64_t num_row
                              const float* out, const int32_t* ties, const int32_t* count, int64_t G, int ops, float* dx,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * MaxCutPooling (reference select/maxcut_select.py, utils/ops.py delta_gcn_matrix and propagate_assignments_sparse,
+ * utils/losses.py maxcut_loss), csrc/maxcut.hip.  fp32, no float atomics, the same bits on every call.  grp_ptr [N + 1]
+ * and grp_perm [E] (NULL: the list is already grouped) are the edge positions by destination or by source, edge-list
+ * order inside a node; `other` is the row of the opposite endpoints.  One wave walks one group whatever its length.
+ *   degree:  over the by-source group, deg_i = the summed weight of i's out-edges that are not self-loops (weight NULL:
+ *            ones), dinv = deg^-1/2 with inf -> 0; then coef[e] = w_e dinv[src_e] and coef_t[e] = w_e dinv[dst_e]
+ *            (either NULL: not written).
+ *   layer:   h_i = act((1 - delta) [i < n_p] z_i + (delta dinv_i) sum over i's group, self-loops skipped, of
+ *            coef[e] z[other_e] + bias), z [N, C], C in 1 .. tgp_maxcut_max_width(); n_p one DEVICE word (NULL: N);
+ *            act 0 identity, 1 tanh, 2 relu.  h_out [N, C] (NULL ok) and, with w_next [C_next, C], z_next = h w_next^T
+ *            [N, C_next] (both NULL and C_next 0: no projection); at least one output.  A slot of the wave adds every
+ *            (64 / G)-th edge of the group in group order (G = C rounded up to a power of two), the slots fold at
+ *            offsets 32 .. G, the projection adds the channels in ascending order.
+ *   tail:    score_i = act(<mlp(h_i), w> + b): n_layers Linear + mlp_act (widths [n_layers], a HOST array, every width
+ *            in 1 .. tgp_maxcut_max_width()), then Linear(., 1).  params packs, per layer, W [out, in] and b [out], then
+ *            w and b; n_params must be exactly that count and at most tgp_maxcut_tail_max_params().
+ *   wgrad:   out [Ca, Cb] = a^T b for a [N, Ca], b [N, Cb]: partial sums of 1024 consecutive rows each (ws,
+ *            tgp_maxcut_wgrad_workspace_bytes), added in ascending chunk order.
+ *   cut:     az_i = sum over i's group of w_e s[other_e] (self-loops and duplicates included), cut_i = s_i az_i,
+ *            wsum_i = sum of w_e; any of the three outputs may be NULL, not all.
+ *   assign_round: one round of label propagation over the by-destination group.  Labels 1 .. K, 0 = none; a labelled
+ *            node keeps its label, another takes the label most of its labelled sources carry (duplicates counted, the
+ *            lowest label on a tie), or stays 0.  Reads label_in only.
+ * TGP_ERR_INVALID: a NULL input or output, an input given as an output, sizes below zero, a width outside its range, an
+ * unknown act, a parameter count that does not fit the widths; TGP_ERR_RANGE: N or E beyond the int32 index;
+ * TGP_ERR_WORKSPACE: ws_bytes below the query.  All are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_maxcut_max_width(void);
+int tgp_maxcut_tail_max_params(void);
+int tgp_maxcut_degree_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                          const int64_t* dst, const float* edge_weight /* NULL ok */, int64_t N, int64_t E, float* dinv,
+                          float* coef /* NULL ok */, float* coef_t /* NULL ok */, void* stream);
+int tgp_maxcut_layer_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* other,
+                         const float* coef, const float* dinv, const float* z, const float* bias /* NULL ok */, int64_t N,
+                         int64_t E, int64_t C, const int64_t* n_p /* NULL ok */, float delta, int act,
+                         float* h_out /* NULL ok */, const float* w_next /* NULL ok */, int64_t C_next,
+                         float* z_next /* NULL iff w_next is */, void* stream);
+int tgp_maxcut_tail_f32(const float* h, int64_t N, int64_t C, const int64_t* widths /* host */, int64_t n_layers,
+                        const float* params, int64_t n_params, int mlp_act, int act, float* score, void* stream);
+size_t tgp_maxcut_wgrad_workspace_bytes(int64_t N, int64_t Ca, int64_t Cb);
+int tgp_maxcut_wgrad_f32(const float* a, const float* b, int64_t N, int64_t Ca, int64_t Cb, float* out, void* ws,
+                         size_t ws_bytes, void* stream);
+int tgp_maxcut_cut_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* other,
+                       const float* edge_weight /* NULL ok */, const float* s, int64_t N, int64_t E,
+                       float* az /* NULL ok */, float* cut /* NULL ok */, float* wsum /* NULL ok */, void* stream);
+int tgp_maxcut_assign_round_i32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                                const int32_t* label_in, int64_t N, int64_t E, int32_t* label_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

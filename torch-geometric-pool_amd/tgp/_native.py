@@ -377,6 +377,16 @@ SIGNATURES = {
                                       _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     "tgp_segment_aggr_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
                                           _c_i64, _c_int, _c_p, _c_p]),
+    "tgp_maxcut_max_width": (_c_int, []),
+    "tgp_maxcut_tail_max_params": (_c_int, []),
+    "tgp_maxcut_degree_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_maxcut_layer_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_f,
+                                      _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "tgp_maxcut_tail_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_p]),
+    "tgp_maxcut_wgrad_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "tgp_maxcut_wgrad_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
+    "tgp_maxcut_cut_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_maxcut_assign_round_i32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -6,7 +6,7 @@ made of the same native kernels.  Every wrapper calls the kernel directly when n
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -1609,3 +1609,161 @@ def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, src, w
     if _needs_grad(x, weight):
         return _SegmentAggrFn.apply(x, weight, ops_mask, num_groups, max_len, src)
     return _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, False)[0]
+
+
+# ------------------------------------------------------------- MaxCutPooling: the delta-GCN score net and the cut loss
+_MAXCUT_TORCH_ACT = {"identity": lambda t: t, "tanh": torch.tanh, "relu": torch.relu}
+
+
+def _maxcut_first(x, init_w, init_b, w0):
+    """z of layer 0: ``initial_layer`` then layer 0's ``lin``, two dense GEMMs."""
+    return torch.nn.functional.linear(torch.nn.functional.linear(x, init_w, init_b), w0)
+
+
+def _maxcut_tail_torch(h, tail, mlp_act, act):
+    """The row MLP as torch operators (training: the backward differentiates exactly this)."""
+    lin = torch.nn.functional.linear
+    for w, b in zip(tail[0:-2:2], tail[1:-2:2]):
+        h = _MAXCUT_TORCH_ACT[mlp_act](lin(h, w, b))
+    return _MAXCUT_TORCH_ACT[act](lin(h, tail[-2], tail[-1])).view(-1)
+
+
+def _maxcut_layers(z, edge_index, edge_weight, conv_w, conv_b, delta, mp_act, keep):
+    """The message-passing stack on the projected rows ``z`` of layer 0: one launch per layer, each writing the next
+    layer's ``z``.  ``keep``: every layer's output is returned (the backward reads them), else only the last."""
+    n = z.size(0)
+    row, col = K._edge_rows(edge_index)
+    by_dst = K.sag_edge_group(edge_index, n, by_destination=True)
+    by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+    dinv, coef, coef_t = K.maxcut_degree(by_src, edge_index, edge_weight, want_coef=True, want_coef_t=keep)
+    n_p = K.maxcut_n_p(edge_index)
+    hs, last = [], len(conv_w) - 1
+    for l in range(len(conv_w)):
+        h, z = K.maxcut_layer(by_dst, row, coef, dinv, z, conv_b[l], n_p, delta, mp_act,
+                              conv_w[l + 1] if l < last else None, want_h=keep or l == last)
+        hs.append(h)
+    return hs, dinv, coef_t, n_p
+
+
+class _MaxCutScoreFn(torch.autograd.Function):
+    """MaxCutScoreNet as ONE node.  Forward: the first projection (torch GEMMs), one layer kernel per delta-GCN layer
+    (every h kept), the row MLP.  Backward, layers in reverse: g_t = g_h act'(h), g_b = column sums of g_t, g_z through the
+    by-source index (the layer kernel with w_e dinv[dst_e], no bias, no activation) which also emits g_h_prev = g_z W,
+    g_W = g_z^T h_prev as a two-stage column reduction.  The first projection and the row MLP are dense row operators:
+    their gradients come from torch on the recomputed expressions.  Edge weights get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, edge_index, edge_weight, delta, mp_act, mlp_act, act, n_conv, *params):
+        init_w, init_b = params[0], params[1]
+        conv_w, conv_b = params[2:2 + n_conv], params[2 + n_conv:2 + 2 * n_conv]
+        tail = params[2 + 2 * n_conv:]
+        z0 = _maxcut_first(x, init_w, init_b, conv_w[0])
+        hs, dinv, coef_t, n_p = _maxcut_layers(z0, edge_index, edge_weight, conv_w, conv_b, delta, mp_act, True)
+        score = _maxcut_tail_torch(hs[-1], tail, mlp_act, act)
+        ctx.save_for_backward(x, edge_index, dinv, coef_t, n_p, *hs, *params)
+        ctx.cfg = (float(delta), mp_act, mlp_act, act, n_conv)
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        delta, mp_act, mlp_act, act, n_conv = ctx.cfg
+        saved = ctx.saved_tensors
+        x, edge_index, dinv, coef_t, n_p = saved[:5]
+        hs, params = saved[5:5 + n_conv], saved[5 + n_conv:]
+        init_w, init_b = params[0], params[1]
+        conv_w, conv_b = params[2:2 + n_conv], params[2 + n_conv:2 + 2 * n_conv]
+        tail = params[2 + 2 * n_conv:]
+        need = ctx.needs_input_grad
+        n = x.size(0)
+        _, col = K._edge_rows(edge_index)
+        by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+        grads = [None] * len(params)
+        # the row MLP
+        with torch.enable_grad():
+            h_last = hs[-1].detach().requires_grad_(True)
+            leaves = [t.detach().requires_grad_(True) for t in tail]
+            out = _maxcut_tail_torch(h_last, leaves, mlp_act, act)
+        got = torch.autograd.grad(out, [h_last] + leaves, g.contiguous())
+        g_h = got[0]
+        grads[2 + 2 * n_conv:] = got[1:]
+        # the delta-GCN layers, last to first
+        g_z = None
+        for l in range(n_conv - 1, -1, -1):
+            h = hs[l]
+            g_t = (torch.ops.aten.tanh_backward(g_h, h) if mp_act == "tanh" else
+                   torch.ops.aten.threshold_backward(g_h, h, 0) if mp_act == "relu" else g_h).contiguous()
+            grads[2 + n_conv + l] = g_t.sum(0)
+            g_z, g_h = K.maxcut_layer(by_src, col, coef_t, dinv, g_t, None, n_p, delta, "identity",
+                                      conv_w[l].t().contiguous() if l > 0 else None, want_h=True)
+            if l > 0:
+                grads[2 + l] = K.maxcut_wgrad(g_z, hs[l - 1])
+        # the first projection
+        with torch.enable_grad():
+            xl = x.detach().requires_grad_(bool(need[0]))
+            leaves = [t.detach().requires_grad_(True) for t in (init_w, init_b, conv_w[0])]
+            z0 = _maxcut_first(xl, *leaves)
+        got = torch.autograd.grad(z0, ([xl] if need[0] else []) + leaves, g_z)
+        g_x = got[0] if need[0] else None
+        grads[0], grads[1], grads[2] = got[-3], got[-2], got[-1]
+        return (g_x, None, None, None, None, None, None, None) + tuple(
+            gr if need[8 + k] else None for k, gr in enumerate(grads))
+
+
+def maxcut_score(x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], init: Sequence[Tensor],
+                 conv_w: Sequence[Tensor], conv_b: Sequence[Tensor], tail: Sequence[Tensor], delta: float, mp_act: str,
+                 mlp_act: str, act: str) -> Tensor:
+    """MaxCutScoreNet's score [N] on device float32 tensors without the propagation matrix, an ``N + E`` list, a sort or
+    anything of size ``E x C``.  ``init`` = (weight, bias) of ``initial_layer``, ``conv_w`` / ``conv_b`` the layers'
+    ``lin.weight`` / ``bias``, ``tail`` = (W, b) of every mlp layer in order, then of ``final_layer``.  Under autograd one
+    node (:class:`_MaxCutScoreFn`); an ``edge_weight`` that requires grad is refused (the composed form is its route)."""
+    if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("maxcut_score gives edge weights no gradient: take MaxCutScoreNet's composed form")
+    params = tuple(init) + tuple(conv_w) + tuple(conv_b) + tuple(tail)
+    if _needs_grad(x, *params):
+        return _MaxCutScoreFn.apply(x, edge_index, edge_weight, float(delta), mp_act, mlp_act, act, len(conv_w), *params)
+    z0 = _maxcut_first(x, init[0], init[1], conv_w[0])
+    hs, _, _, _ = _maxcut_layers(z0, edge_index, edge_weight, conv_w, conv_b, float(delta), mp_act, False)
+    return K.maxcut_tail(hs[-1], tail[0::2], tail[1::2], mlp_act, act)
+
+
+def _maxcut_loss_fwd(s, edge_index, edge_weight, ptr, num_graphs, max_nodes):
+    n = s.numel()
+    _, col = K._edge_rows(edge_index)
+    by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+    az, cut, wsum = K.maxcut_cut(by_src, col, s, edge_weight)
+    sums = K.segment_aggr(torch.stack([cut, wsum], dim=1), 1 << K.N.REDUCE_OPS["sum"], num_graphs, max_nodes, ptr=ptr)[0]
+    vol = sums[:, 1]
+    vol = torch.where(vol == 0, torch.ones_like(vol), vol)
+    return (sums[:, 0] / vol).mean(), az, vol
+
+
+class _MaxCutLossFn(torch.autograd.Function):
+    """mean over the graphs of s^T A s / vol (vol = the graph's summed edge weight, 0 -> 1) on the raw list.  Backward:
+    g_s_i = g (az_i + (A^T s)_i) / (B vol_g), A^T s through the by-destination index.  Edge weights get no gradient."""
+
+    @staticmethod
+    def forward(ctx, s, edge_index, edge_weight, batch, ptr, num_graphs, max_nodes):
+        loss, az, vol = _maxcut_loss_fwd(s, edge_index, edge_weight, ptr, num_graphs, max_nodes)
+        ctx.save_for_backward(s, edge_index, edge_weight, batch, az, vol)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        s, edge_index, edge_weight, batch, az, vol = ctx.saved_tensors
+        row, _ = K._edge_rows(edge_index)
+        by_dst = K.sag_edge_group(edge_index, s.numel(), by_destination=True)
+        at = K.maxcut_cut(by_dst, row, s, edge_weight, want_cut=False, want_wsum=False)[0]
+        scale = g / (vol * vol.numel())
+        g_s = (az + at) * (scale[batch] if batch is not None else scale)
+        return g_s.view_as(s), None, None, None, None, None, None
+
+
+def maxcut_loss(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], batch: Optional[Tensor], ptr: Tensor,
+                num_graphs: int, max_nodes: int) -> Tensor:
+    """The cut loss (mean reduction) of device float32 scores [N]; ``ptr`` [B + 1] are the node offsets of the graphs of
+    a sorted ``batch`` (None: one graph).  One autograd node."""
+    if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("maxcut_loss's native node gives edge weights no gradient: take the composed form")
+    if _needs_grad(s):
+        return _MaxCutLossFn.apply(s, edge_index, edge_weight, batch, ptr, num_graphs, max_nodes)
+    return _maxcut_loss_fwd(s, edge_index, edge_weight, ptr, num_graphs, max_nodes)[0]

@@ -4374,3 +4374,206 @@ def segment_aggr_bwd(g_out: Tensor, x: Tensor, out: Tensor, ties: Optional[Tenso
              x.stride(0) if rows > 1 else max(x.stride(0), F), N.ptr(batch), dense_nodes, N.ptr(mask), N.ptr(out),
              N.ptr(ties), N.ptr(count), num_groups, ops_mask, N.ptr(dx), N.stream_ptr(dev))
     return dx
+
+
+# ------------------------------------------------------------------------- MaxCutPooling (csrc/maxcut.hip)
+MAXCUT_ACTS = {"identity": 0, "tanh": 1, "relu": 2}
+MAXCUT_ASSIGN_MAX_GROUP = 4096  # in-edges of one destination above which the assignment takes the composed rounds: one
+#                                  wave walks a group once per DISTINCT label among its sources (length x labels / 64 steps)
+MAXCUT_SCORE_MAX_GROUP = 4096  # the score net takes the composed form when the longest by-destination group exceeds this
+MAXCUT_SCORE_GROUP_SHARE = 256  # ... and E / this: one wave adds a group's rows in every layer
+_MAXCUT_NP = TensorMemo(16)  # edge_index -> one device int64: the list's largest endpoint + 1 (0 for an empty list)
+_MAXCUT_NP_HOST = TensorMemo(16)  # edge_index -> the same number on the host (read once, for a call without a batch vector)
+_MAXCUT_ONE_GRAPH_PTR: dict = {}  # (n, device) -> the offsets [0, n] of a single graph (the loss without a batch vector)
+
+
+def maxcut_max_width() -> int:
+    """The widest row the layer, tail and weight-gradient kernels take."""
+    return int(N.lib().tgp_maxcut_max_width())
+
+
+def maxcut_tail_max_params() -> int:
+    return int(N.lib().tgp_maxcut_tail_max_params())
+
+
+def maxcut_n_p(edge_index: Tensor) -> Tensor:
+    """``n_P`` of the delta-GCN matrix as one device word: the reference infers the size of ``P`` from the list
+    (``max(edge_index) + 1``), so nodes above every endpoint get no diagonal term.  One reduction, remembered per tensor
+    object and version; the host never reads it."""
+    got = _MAXCUT_NP.get(edge_index)
+    if got is None:
+        if edge_index.numel():
+            got = (edge_index.max() + 1).reshape(1).to(torch.int64)
+        else:
+            got = torch.zeros(1, dtype=torch.int64, device=edge_index.device)
+        if not torch.cuda.is_current_stream_capturing():
+            _MAXCUT_NP.put(edge_index, got)
+    return got
+
+
+def maxcut_n_p_host(edge_index: Tensor) -> int:
+    """:func:`maxcut_n_p` as a Python int: one host read per list, remembered like the device word."""
+    got = _MAXCUT_NP_HOST.get(edge_index)
+    if got is None:
+        got = (int(maxcut_n_p(edge_index)),)
+        if not torch.cuda.is_current_stream_capturing():
+            _MAXCUT_NP_HOST.put(edge_index, got)
+    return got[0]
+
+
+def maxcut_one_graph_ptr(n: int, device) -> Tensor:
+    """int64 [0, n] on ``device``: the node offsets of a single graph, kept for the last few sizes."""
+    key = (int(n), torch.device(device))
+    got = _MAXCUT_ONE_GRAPH_PTR.get(key)
+    if got is None:
+        if len(_MAXCUT_ONE_GRAPH_PTR) >= 8:
+            _MAXCUT_ONE_GRAPH_PTR.clear()
+        got = _MAXCUT_ONE_GRAPH_PTR[key] = torch.tensor([0, int(n)], dtype=torch.long, device=device)
+    return got
+
+
+def maxcut_score_has_hub(edge_index: Tensor, num_nodes: int) -> bool:
+    """Is the longest group (by destination or by source) too long for the layer kernel's one wave per group?  Measured on one MI355X
+    (profiles/maxcut_forward.txt): the wave adds about one row per 0.23 us and layer, the composed form costs about
+    2.2 ns per edge and layer stack of four, so the two meet near a group of E / 400 edges; the gate stands at
+    ``max(MAXCUT_SCORE_MAX_GROUP, E / MAXCUT_SCORE_GROUP_SHARE)``.  The longest group is remembered with the index (one
+    host read on a list's first sight)."""
+    longest = max(sag_edge_group(edge_index, num_nodes, by_destination=True).max_members,  # the forward's walks
+                  sag_edge_group(edge_index, num_nodes, by_destination=False).max_members)  # the backward's
+    return longest > max(MAXCUT_SCORE_MAX_GROUP, edge_index.size(1) // MAXCUT_SCORE_GROUP_SHARE)
+
+
+def maxcut_degree(by_src: AssignIndex, edge_index: Tensor, edge_weight: Optional[Tensor] = None, want_coef: bool = True,
+                  want_coef_t: bool = False):
+    """(dinv [N], coef [E] or None, coef_t [E] or None): ``dinv = deg^-1/2`` (inf -> 0) of the degrees by source without
+    self-loops, ``coef_e = w_e dinv[src_e]`` (the forward's per-edge factor), ``coef_t_e = w_e dinv[dst_e]`` (the
+    backward's)."""
+    dev = N.require_device(edge_index, edge_weight, by_src.row_ptr)
+    row, col = _edge_rows(edge_index)
+    n, E = by_src.num_targets, row.numel()
+    if by_src.nnz != E or by_src.row_ptr.numel() != n + 1:
+        raise ValueError(f"maxcut_degree: an index of {by_src.nnz} edges over {n} nodes against {E} edges")
+    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if ew is not None and ew.numel() != E:
+        raise ValueError(f"maxcut_degree: {ew.numel()} weights for {E} edges")
+    dinv = torch.empty(n, dtype=torch.float32, device=dev)
+    coef = torch.empty(E, dtype=torch.float32, device=dev) if want_coef else None
+    coef_t = torch.empty(E, dtype=torch.float32, device=dev) if want_coef_t else None
+    _checked(N.lib().tgp_maxcut_degree_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(row) if E else None,
+             N.ptr(col) if E else None, N.ptr(ew), n, E, N.ptr(dinv), N.ptr(coef) if E else None,
+             N.ptr(coef_t) if E else None, N.stream_ptr(dev))
+    return dinv, coef, coef_t
+
+
+def maxcut_layer(grp: AssignIndex, other: Tensor, coef: Optional[Tensor], dinv: Tensor, z: Tensor,
+                 bias: Optional[Tensor], n_p: Optional[Tensor], delta: float, act: str = "identity",
+                 w_next: Optional[Tensor] = None, want_h: bool = True):
+    """(h [N, C] or None, z_next [N, C_next] or None): one delta-GCN layer on the projected rows ``z``,
+    ``h_i = act((1 - delta) [i < n_p] z_i + delta dinv_i sum coef_e z[other_e] + bias)`` over node i's group without its
+    self-loops, and in the same launch ``z_next = h w_next^T``."""
+    if act not in MAXCUT_ACTS:
+        raise ValueError(f"maxcut_layer: act {act!r} is not one of {sorted(MAXCUT_ACTS)}")
+    dev = N.require_device(other, coef, dinv, z, bias, n_p, w_next, grp.row_ptr)
+    other, n, E = _asap_group("maxcut_layer", grp, other)
+    z, dinv = N.f32c(z), N.f32c(dinv.reshape(-1))
+    if z.dim() != 2 or z.size(0) != n or dinv.numel() != n or (E and (coef is None or coef.numel() != E)):
+        raise ValueError(f"maxcut_layer: z {tuple(z.shape)} and dinv [{dinv.numel()}] against {n} nodes, one coefficient "
+                         f"per edge ({E})")
+    C = z.size(1)
+    coef = None if coef is None else N.f32c(coef.reshape(-1))
+    bias = None if bias is None else N.f32c(bias.reshape(-1))
+    if bias is not None and bias.numel() != C:
+        raise ValueError(f"maxcut_layer: bias of {bias.numel()} entries for {C} channels")
+    if n_p is not None and (n_p.dtype != torch.int64 or n_p.numel() != 1):
+        raise ValueError("maxcut_layer: n_p is one device int64")
+    w_next = None if w_next is None else N.f32c(w_next)
+    if w_next is not None and (w_next.dim() != 2 or w_next.size(1) != C):
+        raise ValueError(f"maxcut_layer: w_next {tuple(w_next.shape)} against {C} channels")
+    if not want_h and w_next is None:
+        raise ValueError("maxcut_layer: no output asked for")
+    Cn = 0 if w_next is None else w_next.size(0)
+    h = torch.empty(n, C, dtype=torch.float32, device=dev) if want_h else None
+    zn = torch.empty(n, Cn, dtype=torch.float32, device=dev) if w_next is not None else None
+    _checked(N.lib().tgp_maxcut_layer_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(other) if E else None,
+             N.ptr(coef) if E else None, N.ptr(dinv), N.ptr(z), N.ptr(bias), n, E, C, N.ptr(n_p), float(delta),
+             MAXCUT_ACTS[act], N.ptr(h), N.ptr(w_next), Cn, N.ptr(zn), N.stream_ptr(dev))
+    return h, zn
+
+
+def maxcut_tail_fits(width: int, layers: Sequence) -> bool:
+    """Do the row MLP's widths and parameter count fit the tail kernel (``layers``: the Linear modules, final last)?"""
+    wmax = maxcut_max_width()
+    outs = [lin.weight.size(0) for lin in layers]
+    ins = [lin.weight.size(1) for lin in layers]
+    if len(layers) < 1 or len(layers) > 9 or outs[-1] != 1 or ins != [width] + outs[:-1]:
+        return False
+    if any(o < 1 or o > wmax for o in outs) or width > wmax or any(lin.bias is None for lin in layers):
+        return False
+    return sum(lin.weight.numel() + lin.bias.numel() for lin in layers) <= maxcut_tail_max_params()
+
+
+def maxcut_tail(h: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], mlp_act: str, act: str) -> Tensor:
+    """score [N] = act(final(mlp(h))): ``weights`` / ``biases`` of the mlp's Linear layers in order, the final
+    ``Linear(., 1)`` last; one pass over ``h`` [N, C], the parameters in LDS."""
+    if mlp_act not in MAXCUT_ACTS or act not in MAXCUT_ACTS:
+        raise ValueError(f"maxcut_tail: activations must be among {sorted(MAXCUT_ACTS)}")
+    dev = N.require_device(h, *weights, *biases)
+    h = N.f32c(h)
+    if h.dim() != 2 or len(weights) != len(biases) or not weights:
+        raise ValueError("maxcut_tail: h must be [N, C] and every Linear needs its weight and bias")
+    packed = torch.cat([t.detach().to(torch.float32).reshape(-1) for wb in zip(weights, biases) for t in wb])
+    widths = [w.size(0) for w in weights[:-1]]
+    arr = (N.ctypes.c_int64 * max(len(widths), 1))(*widths)
+    score = torch.empty(h.size(0), dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_maxcut_tail_f32, N.ptr(h), h.size(0), h.size(1), N.ctypes.addressof(arr), len(widths),
+             N.ptr(packed), packed.numel(), MAXCUT_ACTS[mlp_act], MAXCUT_ACTS[act], N.ptr(score), N.stream_ptr(dev))
+    return score
+
+
+def maxcut_wgrad(a: Tensor, b: Tensor) -> Tensor:
+    """``a^T b`` [Ca, Cb] of two [N, .] row blocks at widths up to :func:`maxcut_max_width`: partial sums of fixed row
+    chunks folded in ascending order, the same bits on every call."""
+    dev = N.require_device(a, b)
+    a, b = N.f32c(a), N.f32c(b)
+    if a.dim() != 2 or b.dim() != 2 or a.size(0) != b.size(0):
+        raise ValueError(f"maxcut_wgrad: a {tuple(a.shape)} and b {tuple(b.shape)} do not share their rows")
+    L = N.lib()
+    out = torch.empty(a.size(1), b.size(1), dtype=torch.float32, device=dev)
+    wsb = L.tgp_maxcut_wgrad_workspace_bytes(a.size(0), a.size(1), b.size(1))
+    ws = N.workspace(wsb, dev)
+    _checked(L.tgp_maxcut_wgrad_f32, N.ptr(a), N.ptr(b), a.size(0), a.size(1), b.size(1), N.ptr(out), N.ptr(ws), wsb,
+             N.stream_ptr(dev))
+    return out
+
+
+def maxcut_cut(grp: AssignIndex, other: Tensor, s: Tensor, edge_weight: Optional[Tensor] = None, want_cut: bool = True,
+               want_wsum: bool = True):
+    """(az, cut, wsum) [N] each (the unwanted ones None): ``az_i = sum over node i's group of w_e s[other_e]`` on the raw
+    list, ``cut_i = s_i az_i``, ``wsum_i = sum w_e``."""
+    dev = N.require_device(other, s, edge_weight, grp.row_ptr)
+    other, n, E = _asap_group("maxcut_cut", grp, other)
+    s = N.f32c(s.reshape(-1))
+    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if s.numel() != n or (ew is not None and ew.numel() != E):
+        raise ValueError(f"maxcut_cut: one score per node ({n}) and one weight per edge ({E})")
+    out = torch.empty(3, n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_maxcut_cut_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(other) if E else None, N.ptr(ew),
+             N.ptr(s), n, E, N.ptr(out[0]), N.ptr(out[1]) if want_cut else None, N.ptr(out[2]) if want_wsum else None,
+             N.stream_ptr(dev))
+    return out[0], out[1] if want_cut else None, out[2] if want_wsum else None
+
+
+def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, rounds: int) -> Tensor:
+    """``rounds`` rounds of the nearest-supernode label propagation on int32 labels [N] (1 .. K, 0 = none), launched back
+    to back on two buffers without a host wait; returns the labels after the last round."""
+    dev = N.require_device(src, labels, by_dst.row_ptr)
+    src, n, E = _asap_group("maxcut_assign_rounds", by_dst, src)
+    if labels.dtype != torch.int32 or labels.numel() != n or not labels.is_contiguous():
+        raise ValueError(f"maxcut_assign_rounds: labels must be a contiguous int32 [{n}]")
+    cur, nxt = labels, torch.empty_like(labels)
+    fn = N.lib().tgp_maxcut_assign_round_i32
+    for _ in range(int(rounds)):
+        _checked(fn, N.ptr(by_dst.row_ptr), N.ptr(by_dst.perm), N.ptr(src) if E else None, N.ptr(cur), n, E, N.ptr(nxt),
+                 N.stream_ptr(dev))
+        cur, nxt = nxt, cur
+    return cur

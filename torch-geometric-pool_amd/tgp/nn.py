@@ -6,6 +6,10 @@
 naming the argument.  With one output channel projection and aggregation commute, so device float32 tensors take the
 native project-then-aggregate scorer (``tgp.functions.sag_score``: one pass over x, E scalar gathers, no ``E x F`` or
 ``N x F`` temporary); host tensors and other dtypes take the composed form (gather, ``index_add_``, two ``Linear``s).
+
+``GCNConv`` (any width, ``normalize=False`` only, not in ``__all__``) is the layer of MaxCutPool's score net: it carries
+PyG's names (``lin.weight``, ``bias``) and initialisation, and its forward is the composed form of
+``tgp.poolers.MaxCutScoreNet``, whose native route reads the parameters directly (``tgp.functions.maxcut_score``).
 """
 from __future__ import annotations
 
@@ -111,4 +115,47 @@ class SAGEConv(_OneChannelConv):
         self.root_weight = bool(root_weight)
 
 
-__all__ = ["GraphConv", "SAGEConv"]
+class GCNConv(torch.nn.Module):
+    r"""PyG's ``GCNConv`` as :class:`~tgp.poolers.MaxCutScoreNet` uses it: ``normalize=False``, so
+    :math:`\mathbf{x}'_i = \sum_{j \to i} w_{ji} \mathbf{W} \mathbf{x}_j + \mathbf{b}` on the list as given (the caller
+    brings the propagation matrix).  Parameters ``lin.weight`` [out, in] (glorot) and ``bias`` [out] (zeros), PyG's names.
+    The score net's native route reads these parameters and never calls this forward; this is the composed form."""
+
+    def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False,
+                 add_self_loops: Optional[bool] = None, normalize: bool = True, bias: bool = True):
+        super().__init__()
+        if normalize:
+            raise NotImplementedError("GCNConv: normalize=True is not implemented (the MaxCut score net brings its own "
+                                      "propagation matrix)")
+        if improved or add_self_loops:
+            raise NotImplementedError("GCNConv: improved / add_self_loops are not implemented (they belong to "
+                                      "normalize=True)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.lin.weight)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None) -> Tensor:
+        if not isinstance(edge_index, Tensor) or edge_index.is_sparse:
+            from .utils.ops import connectivity_to_edge_index
+            edge_index, edge_weight = connectivity_to_edge_index(edge_index, edge_weight)
+        z = self.lin(x)
+        msg = z[edge_index[0]]
+        if edge_weight is not None:
+            msg = msg * edge_weight.view(-1, 1).to(msg.dtype)
+        out = torch.zeros_like(z).index_add_(0, edge_index[1], msg)
+        return out if self.bias is None else out + self.bias
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}"
+
+
+__all__ = ["GraphConv", "SAGEConv"]  # (SAGPooling's scorers; GCNConv is imported by name)

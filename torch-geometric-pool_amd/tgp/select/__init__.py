@@ -1610,4 +1610,12 @@ class NDPSelect(Select):
 __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
            "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster", "LaPoolSelect",
-           "degree_scorer"]
+           "degree_scorer", "MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling"]
+
+
+def __getattr__(name):
+    # MaxCutPool's selector and score net live next to their pooler (tgp/poolers/maxcut.py), which imports this module
+    if name in ("MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling"):
+        from ..poolers import maxcut
+        return getattr(maxcut, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

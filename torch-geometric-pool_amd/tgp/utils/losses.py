@@ -1054,3 +1054,57 @@ def bnpool_rec_loss_terms(S: Tensor, K_: Tensor, adj: Tensor, mask: Optional[Ten
     rec_adj = S @ K_ @ S.transpose(-1, -2)
     n = mask.sum(-1) if mask is not None else torch.tensor(adj.shape[-1], device=adj.device)
     return _weighted_bce_terms(rec_adj, adj, mask, True) / n ** 2
+
+
+# ------------------------------------------------------------------------------------------------ MaxCutPool's cut loss
+def maxcut_loss(scores: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None,
+                batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
+    r"""The auxiliary loss of :class:`~tgp.poolers.MaxCutPooling` (reference utils/losses.py maxcut_loss):
+    :math:`\mathbf{z}^\top \mathbf{A} \mathbf{z} / V` per graph with :math:`V` the graph's summed edge weight (0 -> 1),
+    on the list as given -- self-loops and duplicate edges count --, then the batch reduction.
+
+    Device float32 scores with an int64 ``[2, E]`` list, a sorted (or no) batch vector, the mean reduction and edge
+    weights that need no gradient take the native node (``tgp.functions.maxcut_loss``: one pass over the by-source
+    groups, no sparse tensor, no sort); everything else takes the composed form below."""
+    if scores.dim() == 2 and scores.size(1) == 1:
+        scores = scores.squeeze(-1)
+    elif scores.dim() != 1:
+        raise ValueError(f"Expected scores to have shape [N] or [N, 1], got {scores.shape}")
+    n = scores.size(0)
+    if edge_weight is not None and edge_weight.dim() > 1:
+        edge_weight = edge_weight.squeeze()
+    if maxcut_loss_native_case(scores, edge_index, edge_weight, batch, batch_reduction):
+        if batch is None:
+            return Fn.maxcut_loss(scores, edge_index, edge_weight, None, K.maxcut_one_graph_ptr(n, scores.device), 1, n)
+        from .ops import batch_info
+        info = batch_info(batch)
+        return Fn.maxcut_loss(scores, edge_index, edge_weight, batch, info.ptr, info.num_graphs, info.max_nodes)
+    if batch is None:
+        batch = torch.zeros(n, dtype=torch.long, device=scores.device)
+    w = torch.ones(edge_index.size(1), dtype=scores.dtype, device=scores.device) if edge_weight is None else edge_weight
+    src, dst = edge_index[0], edge_index[1]
+    az = _seg_sum(w * scores[dst], src, n)
+    nb = num_graphs_of(batch)
+    cut = _seg_sum(scores * az, batch, nb)
+    vol = _seg_sum(w, batch[src], nb)
+    vol = torch.where(vol == 0, torch.ones_like(vol), vol)
+    return _reduce(cut / vol, batch_reduction)
+
+
+def maxcut_loss_native_case(scores: Tensor, edge_index, edge_weight: Optional[Tensor], batch: Optional[Tensor],
+                            batch_reduction: str = "mean") -> bool:
+    """Does :func:`maxcut_loss` take its native node for these inputs?"""
+    if not (isinstance(edge_index, Tensor) and not edge_index.is_sparse and edge_index.dim() == 2
+            and edge_index.size(0) == 2 and edge_index.dtype == torch.int64 and edge_index.is_cuda
+            and scores.is_cuda and scores.dtype == torch.float32 and scores.numel() > 0 and batch_reduction == "mean"):
+        return False
+    if edge_weight is not None and (edge_weight.dtype != torch.float32 or edge_weight.numel() != edge_index.size(1)
+                                    or (edge_weight.requires_grad and torch.is_grad_enabled())):
+        return False
+    if batch is None:
+        return True
+    if not (batch.is_cuda and batch.dtype == torch.int64 and batch.numel() == scores.numel()):
+        return False
+    from .ops import batch_info
+    info = batch_info(batch)
+    return bool(info.is_sorted and info.num_graphs >= 1)

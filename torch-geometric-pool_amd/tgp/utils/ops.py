@@ -776,3 +776,38 @@ def negative_edge_sampling(edge_index: Tensor, num_nodes=None, num_neg_samples: 
     n = maybe_num_nodes(edge_index, num_nodes)
     batch = torch.zeros(n, dtype=torch.long, device=edge_index.device)
     return batched_negative_edge_sampling(edge_index, batch, num_neg_samples, method, force_undirected)
+
+
+# ----------------------------------------------------------------------------- MaxCutPool's propagation matrix
+def delta_gcn_matrix(edge_index, edge_weight: Optional[Tensor] = None, delta: float = 2.0,
+                     num_nodes: Optional[int] = None):
+    r"""The :math:`\delta`-GCN propagation matrix :math:`\mathbf{P} = \mathbf{I} - \delta \mathbf{L}_{sym}` of MaxCutPool
+    (reference utils/ops.py delta_gcn_matrix) in the format of the input: ``(edge_index, edge_weight)`` for an edge list,
+    ``(matrix, None)`` for a torch COO tensor or a ``SparseTensor``.  Input self-loops are dropped, the degrees are the
+    row sums by source, :math:`d^{-1/2}` is 0 for an isolated node, duplicates are summed by the final coalesce and the
+    diagonal carries :math:`1 - \delta`.  Without ``num_nodes`` the size is inferred from the list, so a node above
+    every endpoint has no row.  Without ``edge_weight`` the unit weights are float32, as the reference's are.
+
+    This is the composed form: :class:`~tgp.poolers.MaxCutScoreNet` calls it for host tensors, other dtypes and sparse
+    connectivity; its native route never forms the matrix."""
+    as_sparsetensor = is_sparsetensor(edge_index)
+    as_coo = isinstance(edge_index, Tensor) and edge_index.is_sparse
+    ei, ew = connectivity_to_edge_index(edge_index, edge_weight)
+    n = maybe_num_nodes(ei, num_nodes)
+    keep = ei[0] != ei[1]
+    ei = ei[:, keep]
+    ew = torch.ones(ei.size(1), device=ei.device) if ew is None else ew[keep]
+    row, col = ei[0], ei[1]
+    dis = torch.zeros(n, dtype=ew.dtype, device=ei.device).index_add_(0, row, ew).pow_(-0.5)
+    dis.masked_fill_(dis == float("inf"), 0)
+    loops = torch.arange(n, device=ei.device)
+    ones = torch.ones(n, dtype=ew.dtype, device=ei.device)
+    # -delta L_sym = delta D^-1/2 A D^-1/2 - delta I, then + I: the diagonal is summed by the coalesce as the reference's is
+    index = torch.cat([ei, torch.stack([loops, loops]), torch.stack([loops, loops])], dim=1)
+    value = torch.cat([-delta * -(dis[row] * ew * dis[col]), -delta * ones, ones])
+    p = torch.sparse_coo_tensor(index, value, size=(n, n)).coalesce()
+    if as_sparsetensor:
+        return connectivity_to_sparsetensor(p, None, n), None
+    if as_coo:
+        return p, None
+    return p.indices(), p.values()
