@@ -3,6 +3,9 @@ reference's fixtures by its own CPU test) called on a draw of tests/fuzz_inputs.
 
 ``reference(draw, dtype)`` -> (float outputs by name, leaves by name): the form ``grad_path_errors`` takes as its oracle.
 ``exact(draw)`` -> the integer outputs (selections, clusters, counts, tie counts), compared with ``torch.equal``.
+For ASAP and MaxCut the operator layer has every kernel's own plain definition on its own float32 inputs, the public
+layer the reference-shaped forms of tests/asap_restatement.py and tests/maxcut_restatement.py (not the collapsed
+algebra the kernels use), and the exact outputs are the edge-group index, the arg-max table and the labels.
 Host only."""
 import os
 import sys
@@ -13,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import acc_restatement as RA  # noqa: E402
+import asap_restatement as RAS  # noqa: E402
 import bnpool_restatement as RB  # noqa: E402
 import dmon_restatement as RD  # noqa: E402
 import edgepool_restatement as RE  # noqa: E402
@@ -20,6 +24,7 @@ import hosc_restatement as RH  # noqa: E402
 import jb_restatement as RJ  # noqa: E402
 import kmis_restatement as RK  # noqa: E402
 import lapool_restatement as RL  # noqa: E402
+import maxcut_restatement as RM  # noqa: E402
 import readout_restatement as RR  # noqa: E402
 import sag_restatement as RS  # noqa: E402
 
@@ -400,3 +405,235 @@ def tied_order(score, higher=False):
     n = score.numel()
     rev = torch.argsort(score.flip(0), descending=True, stable=True)
     return (n - 1) - rev
+
+
+# ------------------------------------------------------------------------------------- the shared edge-group index
+def edge_group_exact(edge_index, n, by_destination):
+    """What ``kernels.sag_edge_group`` must hold, from a stable host argsort of the same list: ``row_ptr`` [n + 1],
+    ``perm`` (the edge positions grouped by the row, list order inside a group; None when the list already ascends in
+    that row or is empty: offsets only) and the longest group."""
+    tgt = edge_index[1 if by_destination else 0]
+    counts = torch.bincount(tgt, minlength=n)
+    row_ptr = torch.zeros(n + 1, dtype=torch.long)
+    row_ptr[1:] = counts.cumsum(0)
+    ascending = tgt.numel() == 0 or bool((tgt[1:] >= tgt[:-1]).all())
+    return {"row_ptr": row_ptr, "perm": None if ascending else torch.argsort(tgt, stable=True),
+            "max_members": int(counts.max()) if n else 0}
+
+
+def regrouped_order(edge_index, by_destination):
+    """long [E]: the same list in the OTHER index form of that direction with every group's edges in the same order -- a
+    list that does not ascend in the grouped row is stably sorted by it (offsets only), one that does is interleaved
+    (every group's first edge, then every group's second ...: a permutation again)."""
+    tgt = edge_index[1 if by_destination else 0]
+    if tgt.numel() == 0 or not bool((tgt[1:] >= tgt[:-1]).all()):
+        return torch.argsort(tgt, stable=True)
+    first = torch.zeros(int(tgt.max()) + 2, dtype=torch.long)
+    first[1:] = torch.bincount(tgt).cumsum(0)
+    rank = torch.arange(tgt.numel()) - first[tgt]  # an edge's place inside its group
+    return torch.argsort(rank * (int(tgt.max()) + 1) + (int(tgt.max()) - tgt), stable=True)
+
+
+# ------------------------------------------------------------------------------------------------------------- ASAP
+def asap_params(d, dtype):
+    """(the restatement's parameters, the drawn ones as leaves by name); a bias that is off is a zero no gradient reaches."""
+    par, lv = {}, {}
+    for k, v in d["params"].items():
+        if v is None:
+            par[k] = torch.zeros(d["F"] if k == "lin.bias" else 1, dtype=dtype)
+        else:
+            par[k] = lv[k] = _leaf(v, dtype)
+    return par, lv
+
+
+def _asap_rows(d, dtype):
+    x = _leaf(d["x"], dtype)
+    return x, (x if d["same_pool"] else _leaf(d["x_pool"], dtype))
+
+
+def _asap_mask(d, dtype):
+    return None if d["alpha_mask"] is None else d["alpha_mask"].to(dtype)
+
+
+def _asap_weight(d, dtype):
+    return None if d["edge_weight"] is None else d["edge_weight"].to(dtype)
+
+
+def asap_reference(d, dtype):
+    """The public layer, reference-shaped (the F x F Linear on every max row, ``att`` on the concatenation, LEConv as
+    PyG's code): "alpha" [E] (masked where a mask is drawn), "x_new" [n, F], "score" [n] = act(fitness)."""
+    x, x_pool = _asap_rows(d, dtype)
+    par, lv = asap_params(d, dtype)
+    alpha, x_new, fit = RAS.fitness_reference_shaped(x, x_pool, d["edge_index"], _asap_weight(d, dtype), par,
+                                                     d["negative_slope"], _asap_mask(d, dtype))
+    # (alpha leaves the product's node without a gradient path: it is handed out for inspection, so it is a value here)
+    return {"alpha": alpha.detach(), "x_new": x_new, "score": RAS.activate(fit, d["act"])}, {"x": x, "x_pool": x_pool, **lv}
+
+
+def asap_operator_inputs(d):
+    """float32 inputs of the operators past the first, as the collapsed restatement hands them on in float32: w~ and c,
+    sq and sp, the (masked) alpha, LEConv's three weight rows, the projections p [3, n] and the two biases."""
+    with torch.no_grad():
+        par, _ = asap_params(d, torch.float32)
+        ei, n = d["edge_index"], d["n"]
+        wt, c, a2 = RAS.collapse(par)
+        sq = RAS.master_query(d["x_pool"], ei, n)[0] @ wt + c
+        sp = d["x_pool"] @ a2
+        val = RAS.softmax(torch.nn.functional.leaky_relu(sq[ei[1]] + sp[ei[0]], d["negative_slope"]), ei[1], n)
+        if d["alpha_mask"] is not None:
+            val = val * d["alpha_mask"]
+        x_new = torch.zeros_like(d["x"]).index_add(0, ei[1], d["x"][ei[0]] * val.view(-1, 1))
+        w3 = torch.cat([par[f"select_scorer.lin{k}.weight"] for k in (1, 2, 3)])
+        return {"w_tilde": wt, "c": c.reshape(1), "sq": sq, "sp": sp, "val": val, "w3": w3, "p": w3 @ x_new.t(),
+                "b1": par["select_scorer.lin1.bias"], "b3": par["select_scorer.lin3.bias"]}
+
+
+def asap_edge_softmax(logit, dst, n, drop_65th=False):
+    """PyG's edge softmax (``+ 1e-16``).  ``drop_65th``: the wrong form in which the 65th edge of a group (lane 0's second
+    trip of a 64-lane loop) never reaches the group's sum."""
+    mx = logit.new_zeros(n).scatter_reduce(0, dst, logit.detach(), reduce="amax", include_self=False)
+    ex = (logit - mx[dst]).exp()
+    add = ex
+    if drop_65th and dst.numel():
+        order = torch.argsort(dst, stable=True)
+        first = torch.zeros(n + 1, dtype=torch.long)
+        first[1:] = torch.bincount(dst, minlength=n).cumsum(0)
+        lost = order[(torch.arange(dst.numel()) - first[dst[order]]) == 64]
+        add = ex.clone()
+        add[lost] = 0
+    return ex / (logit.new_zeros(n).index_add(0, dst, add) + 1e-16)[dst]
+
+
+def asap_operator_reference(d, dtype, inp=None, drop_65th=False):
+    """Every operator's own plain definition on ITS inputs (``inp``, float32, default :func:`asap_operator_inputs`):
+    "sq" = <scatter-max of x_pool[src], w~> + c, "alpha" = the segment softmax of leaky(sq_in[dst] + sp_in[src]),
+    "out" = the weighted row sum of x[src] with "proj" = its three projections, "t" / "a" = LEConv's scalar form on p and
+    its activation.  Leaves x, x_pool, sq_in, sp_in, logit (per edge, an intermediate), val and p: the backward operators
+    are the gradients of sq, alpha and out to them."""
+    inp = asap_operator_inputs(d) if inp is None else inp
+    (src, dst), n = d["edge_index"], d["n"]
+    x, x_pool = _asap_rows(d, dtype)
+    lv = {"x": x, "x_pool": x_pool}
+    outs = {"sq": RAS.scatter_max(x_pool[src], dst, n) @ inp["w_tilde"].to(dtype) + inp["c"].to(dtype)}
+    sq_in, sp_in = _leaf(inp["sq"], dtype), _leaf(inp["sp"], dtype)
+    logit = sq_in[dst] + sp_in[src]
+    outs["alpha"] = asap_edge_softmax(torch.nn.functional.leaky_relu(logit, d["negative_slope"]), dst, n, drop_65th)
+    val = _leaf(inp["val"], dtype)
+    outs["out"] = torch.zeros_like(x).index_add(0, dst, x[src] * val.view(-1, 1))
+    outs["proj"] = inp["w3"].to(dtype) @ outs["out"].t()
+    p = _leaf(inp["p"], dtype)
+    w = torch.ones(src.numel(), dtype=dtype) if d["edge_weight"] is None else d["edge_weight"].to(dtype)
+    agg = torch.zeros(n, dtype=dtype).index_add(0, dst, w * p[0][src])
+    wsum = torch.zeros(n, dtype=dtype).index_add(0, dst, w)
+    outs["t"] = p[2] + inp["b3"].to(dtype) + agg + (inp["b1"].to(dtype) - p[1]) * wsum
+    outs["a"] = RAS.activate(outs["t"], d["act"])
+    lv.update(sq_in=sq_in, sp_in=sp_in, logit=logit, val=val if val.numel() else None, p=p)  # (no leaf without entries)
+    return outs, lv
+
+
+def asap_argmax_exact(d, x_pool=None, higher=False):
+    """"max" [n, F] (an entry of the float32 input; 0 for a node without in-edge) and "argpos" [n, F]: the LOWEST edge
+    position among the equal maxima of (node, column), -1 for an empty group.  ``higher``: the wrong rule."""
+    x_pool = d["x_pool"] if x_pool is None else x_pool
+    ei, n = d["edge_index"], d["n"]
+    E = ei.size(1)
+    mx, arg = RAS.master_query(x_pool, ei, n)
+    if higher and E:
+        flipped, pos = ei.flip(1), torch.arange(E - 1, -1, -1)  # the last position first: the lowest becomes the highest
+        arg_f = RAS.master_query(x_pool, flipped, n)[1]
+        arg = torch.where(arg_f < E, pos[arg_f.clamp(max=E - 1)], arg_f)
+    return {"max": mx, "argpos": torch.where(arg < E, arg, torch.full_like(arg, -1))}
+
+
+def asap_tied_sources(d):
+    """How many (node, column) maxima are held by two DIFFERENT source rows of the group (duplicates of one row aside)."""
+    ei, n = d["edge_index"], d["n"]
+    if ei.size(1) == 0:
+        return 0
+    uniq = torch.unique(ei, dim=1)
+    rows = d["x_pool"][uniq[0]]
+    hit = (rows == RAS.scatter_max(rows, uniq[1], n)[uniq[1]]).to(torch.long)
+    return int((torch.zeros(n, rows.size(1), dtype=torch.long).index_add(0, uniq[1], hit) > 1).sum())
+
+
+def asap_query_half_matters(d, nodes, loops=True):
+    """Does x_new of ``nodes`` depend on ``lin``, its bias and ``att``'s bias at all?  They reach a node only through its
+    sq_i, one shift of all of its group's logits, which the group's softmax does not see unless leaky ReLU treats its
+    members differently: some group of ``nodes`` must hold logits on both sides of 0 (decided in float64).  Where none
+    does, the gradient to those parameters is zero in exact arithmetic and rounding noise in any precision.
+    ``loops``: on the list with its remaining self-loops, as the pooler sees it."""
+    ei, n = d["edge_index"], d["n"]
+    if loops:
+        ei, _ = RAS.add_remaining_self_loops(ei, None, n)
+    with torch.no_grad():
+        wt, c, a2 = RAS.collapse(asap_params(d, torch.float64)[0])
+        rows = d["x_pool"].double()
+        t = (RAS.master_query(rows, ei, n)[0] @ wt + c)[ei[1]] + (rows @ a2)[ei[0]]
+    lo = torch.full((n,), float("inf"), dtype=torch.float64).scatter_reduce(0, ei[1], t, reduce="amin")
+    hi = torch.full((n,), float("-inf"), dtype=torch.float64).scatter_reduce(0, ei[1], t, reduce="amax")
+    return bool(((lo < 0) & (hi > 0))[nodes].any())
+
+
+def asap_pool_case(d):
+    """The draw as a fixture case of ``asap_restatement.pool_case`` (the whole pooler; the drawn biases all on)."""
+    return {"inputs": {"x": d["x"], "edge_index": d["edge_index"], "edge_weight": d["edge_weight"], "batch": d["batch"]},
+            "cfg": {"in_channels": d["F"], "ratio": 0.5, "negative_slope": d["negative_slope"], "nonlinearity": d["act"]},
+            "params": d["params"], "gnn": None}
+
+
+# ----------------------------------------------------------------------------------------------------------- MaxCut
+def maxcut_operator_inputs(d):
+    """float32 inputs of the operators past the first: the rows z [n, C_l] every drawn layer projects from, the rows the
+    tail reads, dinv as the float32 restatement gives it."""
+    g = torch.Generator().manual_seed(7_000_003 + d["seed"])
+    n = d["n"]
+    z = [torch.randn(n, c, generator=g) for c in d["widths"]]
+    w = RM._weights(d["edge_index"], d["edge_weight"], torch.float32)
+    return {"z": z, "h_tail": torch.randn(n, d["widths"][-1], generator=g), "dinv": RM.dinv_of(d["edge_index"], w, n)}
+
+
+def maxcut_operator_reference(d, dtype, inp=None, n_p=None):
+    """Every operator's own plain definition: "dinv", "coef" = w dinv[src], "coef_t" = w dinv[dst]; per drawn layer l
+    "h{l}" = ``layer_collapsed`` on z_l with its bias and ``mp_act``, "z_next{l}" = h_l W_{l+1}^T, "lin{l}" the same layer
+    without bias and activation (its gradient to z_l is the backward's use of the kernel over the by-source group);
+    "tail" = ``_tail`` where the tail fits; "az", "cut", "wsum" by source and "at" = A^T s by destination on the raw list.
+    ``n_p``: another diagonal limit than the list's (a wrong stand-in)."""
+    inp = maxcut_operator_inputs(d) if inp is None else inp
+    ei, n = d["edge_index"], d["n"]
+    n_p = d["n_p"] if n_p is None else n_p
+    w = RM._weights(ei, d["edge_weight"], dtype)
+    dinv = RM.dinv_of(ei, w, n)
+    outs = {"dinv": dinv, "coef": w * dinv[ei[0]], "coef_t": w * dinv[ei[1]]}
+    par = {k: v.to(dtype) for k, v in d["params"].items()}
+    dinv_in, lv = inp["dinv"].to(dtype), {}
+    for l in range(len(d["widths"])):
+        z = lv[f"z{l}"] = _leaf(inp["z"][l], dtype)
+        h = RM.layer_collapsed(z, ei, w, dinv_in, n_p, d["delta"], par[f"{RM.PRE}mp_convs.{l}.bias"], d["mp_act"])
+        outs[f"h{l}"] = h
+        if l + 1 < len(d["widths"]):
+            outs[f"z_next{l}"] = h @ par[f"{RM.PRE}mp_convs.{l + 1}.lin.weight"].t()
+        outs[f"lin{l}"] = RM.layer_collapsed(z, ei, w, dinv_in, n_p, d["delta"])
+    if d["tail"] != "unfit":
+        lv["h_tail"] = _leaf(inp["h_tail"], dtype)
+        outs["tail"] = RM._tail(lv["h_tail"], par, len(d["mlp_units"]), d["mlp_act"], d["act"])
+    s = lv["s"] = _leaf(d["s"], dtype)
+    outs["az"] = torch.zeros(n, dtype=dtype).index_add(0, ei[0], w * s[ei[1]])
+    outs["cut"] = s * outs["az"]
+    outs["wsum"] = torch.zeros(n, dtype=dtype).index_add(0, ei[0], w)
+    outs["at"] = torch.zeros(n, dtype=dtype).index_add(0, ei[1], w * s[ei[0]])
+    return outs, lv
+
+
+def maxcut_reference(d, dtype):
+    """The public layer, reference-shaped: "score" [n] of the net on the explicit delta-GCN matrix (leaves x and every
+    parameter) and "loss", the cut loss of the drawn scores s (leaf s)."""
+    x, s = _leaf(d["x"], dtype), _leaf(d["s"], dtype)
+    par = {k: _leaf(v, dtype) for k, v in d["params"].items()}
+    ew = None if d["edge_weight"] is None else d["edge_weight"].to(dtype)
+    score = RM.scores_reference_shaped(par, d["cfg"], x, d["edge_index"], ew)
+    return {"score": score, "loss": RM.cut_loss(s, d["edge_index"], ew, d["batch"])}, {"x": x, "s": s, **par}
+
+
+def maxcut_labels_exact(d):
+    """int64 [n]: the labels (1 .. K by position among the kept nodes, 0 = none) after ``max_iter`` rounds."""
+    return torch.tensor(RM.assign_rounds(d["kept"], d["edge_index"], d["n"], d["max_iter"]), dtype=torch.long)

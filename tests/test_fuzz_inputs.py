@@ -5,8 +5,10 @@
 * Every index is in range, every ``ptr`` monotone, every edge inside its graph.
 * Conditioning: the float32 restatement against the float64 one stays within CAP / FACTOR on every (family, seed), for
   the values and (through ``grad_path_errors``, which holds the cap itself) for the gradients.
-* The harness finds faults: with the float32 restatement standing in for the kernels every seed passes; three wrong
-  Python stand-ins are each flagged on at least one seed, by the name of the output.
+* The harness finds faults: with the float32 restatement standing in for the kernels every seed passes; wrong Python
+  stand-ins (a dropped row, ties resolved the wrong way, a scaled term; for ASAP an arg-max tie resolved to the higher
+  edge position and an edge softmax that loses a group's 65th edge, for MaxCut a diagonal term above n_P) are each
+  flagged on at least one seed, by the name of the output.
 """
 import pytest
 import torch
@@ -35,10 +37,19 @@ FLOAT_REFS = {"jb": FR.jb_reference, "readout": FR.readout_reference, "sag": FR.
               "acc": FR.acc_reference,
               "lapool": lambda d, dt: FR.lapool_reference(d, dt, FR.lapool_leaders(d, FR.lapool_variation(d, torch.float32))),
               "acc_flat": lambda d, dt: FR.acc_flat_reference(d, dt) if d["prefix"] else ({}, {}),
-              "hosc": lambda d, dt: FR.hosc_reference(d, dt, _dmon_raw(d) if d["with_raw"] else None, grads=True)}
+              "hosc": lambda d, dt: FR.hosc_reference(d, dt, _dmon_raw(d) if d["with_raw"] else None, grads=True),
+              "asap": FR.asap_reference, "asap_operators": FR.asap_operator_reference,
+              "maxcut": FR.maxcut_reference, "maxcut_operators": FR.maxcut_operator_reference}
+ASAP_PARAMS = ["lin.weight", "lin.bias", "att.weight", "att.bias", "select_scorer.lin1.weight", "select_scorer.lin1.bias",
+               "select_scorer.lin2.weight", "select_scorer.lin3.weight", "select_scorer.lin3.bias"]
+# (every name a drawn score net can have: 1 ... 4 layers, a tail of up to two Linear; a leaf a draw lacks is skipped)
+MAXCUT_PARAMS = [FR.RM.PRE + n + e for n in ["initial_layer", "final_layer", "mlp.0", "mlp.1"] for e in (".weight", ".bias")] \
+    + [f"{FR.RM.PRE}mp_convs.{l}{e}" for l in range(4) for e in (".lin.weight", ".bias")]
 LEAVES = {"jb": ["s"], "readout": ["x", "weight"], "sag": ["x", "w_rel", "w_root", "b"], "bnpool": ["s", "k_mat"],
           "bnpool_operators": ["t", "s"], "dmon": ["s", "raw"], "hosc": ["s", "raw"], "acc": ["s"],
-          "acc_flat": ["s"], "lapool": ["x"]}
+          "acc_flat": ["s"], "lapool": ["x"], "asap": ["x", "x_pool"] + ASAP_PARAMS,
+          "asap_operators": ["x", "x_pool", "sq_in", "sp_in", "val", "p"], "maxcut": ["x", "s"] + MAXCUT_PARAMS,
+          "maxcut_operators": ["z0", "z1", "z2", "z3", "h_tail", "s"]}
 
 
 def draws(family):
@@ -48,6 +59,10 @@ def draws(family):
 def _same(a, b):
     if isinstance(a, torch.Tensor):
         return isinstance(b, torch.Tensor) and a.dtype == b.dtype and torch.equal(a, b)
+    if isinstance(a, dict):  # (a draw's parameters by name)
+        return isinstance(b, dict) and set(a) == set(b) and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same(u, v) for u, v in zip(a, b))
     return a == b
 
 
@@ -135,6 +150,93 @@ def test_every_boundary_value_layout_and_route_is_drawn(family):
         assert {d["order"] for d in ds} == {"sorted", "shuffled"}
         assert {d["root"] for d in ds} == {True, False} and {d["bias"] for d in ds} == {True, False}
         assert any(64 < d["in_degree_max"] <= 256 for d in ds) and any(d["in_degree_max"] > 256 for d in ds)
+    if family in ("asap", "maxcut"):
+        assert {d["density"] for d in ds} == set(FI.DENSITIES) and {d["order"] for d in ds} == set(FI.EDGE_ORDERS)
+        assert {d["directed"] for d in ds} == {True, False} and {d["weighted"] for d in ds} == {True, False}
+        assert {d["hub"] for d in ds} == set(FI.EDGE_HUBS)
+        for d in ds:  # the hub is there: one node of the list has at least that many in-edges, exactly that many at 63 ... 65
+            indeg = torch.bincount(d["edge_index"][1], minlength=d["n"])
+            assert d["hub"] == 0 or d["hub"] in indeg.tolist(), (d["seed"], d["hub"])
+        # both index forms in both directions: offsets only (perm None) and a permutation, on lists that have edges
+        forms = {(by_dst, FR.edge_group_exact(d["edge_index"], d["n"], by_dst)["perm"] is None)
+                 for d in ds if d["edge_index"].size(1) > 1 for by_dst in (True, False)}
+        assert forms == {(True, True), (True, False), (False, True), (False, False)}
+        assert any(d["edge_weight"] is not None and bool((d["edge_weight"] == 0).any()) for d in ds)  # explicit zeros
+        assert any(bool((d["edge_index"][0] == d["edge_index"][1]).any()) for d in ds)  # self-loops
+        assert any(torch.unique(d["edge_index"], dim=1).size(1) < d["edge_index"].size(1) for d in ds)  # duplicates
+        sizes = lambda d: d.get("all_sizes", d["sizes"])  # noqa: E731
+        # a graph of 0 and of 1 nodes inside a batch; node ranges without an edge at the start and at the end of a batch;
+        # a list that does not reach N in a batch of several graphs
+        assert any(0 in sizes(d) and d["B"] > 1 for d in ds) and any(1 in sizes(d) and d["B"] > 1 for d in ds)
+        touched = [torch.bincount(d["edge_index"].reshape(-1), minlength=d["n"]) > 0 for d in ds]
+        assert any(t.any() and not t[0] for t in touched) and any(t.any() and not t[-1] for t in touched)
+        assert any(d["B"] > 1 and d["edge_index"].numel() and int(d["edge_index"].max()) + 1 < d["n"] for d in ds)
+    if family == "asap":
+        from tgp import kernels as K
+        assert set(FI.ASAP_ACT_NAMES) == set(K.ASAP_ACTS) and {d["act"] for d in ds} == set(FI.ASAP_ACT_NAMES)
+        assert sorted(d["F"] for d in ds) == sorted(FI.ASAP_FEATURES) and len(FI.ASAP_FEATURES) == len(FI.SEEDS)
+        for d in ds:  # the form and the lane count are the rule's, from F, stride and pointer
+            stride, first = FI.asap_row_geometry(d["F"], d["layout"])
+            vec = d["F"] >= 4 and stride % 4 == 0 and first % 16 == 0
+            assert d["form"] == ("vec16" if vec else "scalar")
+            units = -(-d["F"] // 4) if vec else d["F"]
+            assert d["lanes"] == min([g for g in FI.ASAP_LANES[d["form"]] if g >= units], default=64)
+        assert {d["form"] for d in ds} == {"vec16", "scalar"}
+        # (on draws whose list has edges in groups of several: a kernel that walks no edge shows nothing)
+        walked = [d for d in ds if d["in_degree_max"] > 2]
+        vec = {d["F"]: d["lanes"] for d in walked if d["form"] == "vec16"}
+        assert set(vec.values()) == set(FI.ASAP_LANES["vec16"])  # every G of the 16-byte form, 4 and 8 among them
+        assert 8 in vec and {12, 16} & set(vec) and 32 in vec and {257, 260} & set(vec)  # (257, 260: the second block)
+        assert {d["form"] for d in walked if d["F"] == 260} == {"scalar"}
+        assert {d["lanes"] for d in walked if d["form"] == "scalar"} == set(FI.ASAP_LANES["scalar"])
+        assert {d["negative_slope"] for d in ds} == {0.2, 0.0} and {d["bias"] for d in ds} == {True, False}
+        assert {d["same_pool"] for d in ds} == {True, False}
+        assert all((d["x_pool"] is d["x"]) == d["same_pool"] for d in ds)
+        assert {d["alpha_mask"] is not None for d in ds} == {True, False}
+        assert any(d["alpha_mask"] is not None and 0 < int((d["alpha_mask"] == 0).sum()) < d["alpha_mask"].numel() for d in ds)
+        tied = [d for d in ds if d["x_tied"] is not None]
+        assert tied and any(FR.asap_tied_sources(dict(d, x_pool=d["x_tied"])) > 0 for d in tied)
+    if family == "maxcut":
+        from tgp import kernels as K
+        assert set(FI.MAXCUT_ACT_NAMES) == set(K.MAXCUT_ACTS)
+        for name in ("mp_act", "mlp_act", "act"):
+            assert {d[name] for d in ds} == set(FI.MAXCUT_ACT_NAMES)
+        assert {w for d in ds for w in d["widths"]} == set(FI.MAXCUT_WIDTHS) and {d["F"] for d in ds} == set(FI.MAXCUT_WIDTHS[1:])
+        assert {len(d["widths"]) for d in ds} == {1, 2, 3, 4}
+        pairs = [(a, b) for d in ds for a, b in zip(d["widths"][:-1], d["widths"][1:])]
+        assert all(a != b for a, b in pairs)
+        cross = lambda a, b: FI.pow2_ceil(a) != FI.pow2_ceil(b)  # noqa: E731  (another lane count per row)
+        assert any(b > a and cross(a, b) for a, b in pairs) and any(b < a and cross(a, b) for a, b in pairs)
+        assert {d["delta"] for d in ds} == {0.5, 2.0} and {d["tail"] for d in ds} == set(FI.MAXCUT_TAILS)
+        wmax = limits()["maxcut_max_width"]
+        for d in ds:  # the tail that does not fit is wider than the widest row; every other tail is within it
+            assert (max(d["mlp_units"], default=0) > wmax) == (d["tail"] == "unfit")
+        assert {d["np_class"] for d in ds} == set(FI.NP_CLASSES)
+        for d in ds:
+            ei = d["edge_index"]
+            assert d["n_p"] == (int(ei.max()) + 1 if ei.numel() else 0)
+            assert {"full": d["n_p"] == d["n"], "below": 0 < d["n_p"] < d["n"] or d["n"] <= 2, "empty": ei.numel() == 0,
+                    "loops": ei.numel() > 0 and bool((ei[0] == ei[1]).all())}[d["np_class"]], (d["seed"], d["np_class"])
+            assert d["edge_weight"] is None or bool((d["edge_weight"] >= 0).all())
+        assert any(d["np_class"] == "below" and d["B"] > 1 and d["n_p"] < d["n"] for d in ds)
+        zero = [d for d in ds if d["zero_degree_node"] is not None]
+        assert zero  # a node with out-edges to other nodes whose degree is 0: dinv goes inf -> 0
+        for d in zero:
+            out = (d["edge_index"][0] == d["zero_degree_node"]) & (d["edge_index"][1] != d["zero_degree_node"])
+            assert bool(out.any()) and float(d["edge_weight"][out].sum()) == 0.0
+            assert float(FR.RM.dinv_of(d["edge_index"], d["edge_weight"], d["n"])[d["zero_degree_node"]]) == 0.0
+        assert {d["keep"] for d in ds} == set(FI.MAXCUT_KEEP) and {d["max_iter"] for d in ds} == {1, 5}
+        for d in ds:  # between 1 and all nodes of every graph with a node are kept
+            per = torch.bincount(d["batch"][d["kept"]], minlength=len(d["all_sizes"]))
+            assert all((0 < k <= c) if c else k == 0 for k, c in zip(per.tolist(), d["all_sizes"]))
+            assert bool((d["kept"][1:] > d["kept"][:-1]).all())
+        chains = [d for d in ds if d["chain"]]
+        assert chains
+        for d in chains:  # the path's tail is still unlabelled after max_iter rounds, and one more round would go on
+            label = FR.maxcut_labels_exact(d)
+            assert int(label[-1]) == 0 and int(label[d["n"] - d["all_sizes"][-1] + d["max_iter"]]) > 0
+        L = limits()["maxcut_wgrad_rows"]
+        assert all(d["wgrad_rows"] == [L - 1, L, L + 1, 2 * L + 1] for d in ds)
     if family in ("kmis", "edge_contract"):
         assert {d["density"] for d in ds} == set(FI.DENSITIES) and {d["directed"] for d in ds} == {True, False}
         assert {d["route"] for d in ds} == {"graphs", "rounds"}
@@ -175,6 +277,17 @@ def test_every_index_is_in_range(family):
             assert int(torch.bincount(d["index"], minlength=1).max()) <= d["max_len"]
         if family == "jb" and not d["padded"]:
             assert d["s"].size(0) == int(d["ptr"][-1]) == d["batch"].numel()
+        if family in ("asap", "maxcut"):
+            assert d["x"].shape == (d["n"], d["F"]) and d["batch"].numel() == d["n"] == int(d["ptr"][-1])
+            assert d["edge_weight"] is None or d["edge_weight"].shape == (d["edge_index"].size(1),)
+        if family == "asap":
+            # no maximum is held by two DIFFERENT source rows of a group: the kernel's rule (the lower position) and the
+            # even split of torch's amax backward then agree (duplicates of one row tie, and there they do)
+            assert FR.asap_tied_sources(d) == 0 and d["x_pool"].shape == d["x"].shape
+            assert d["alpha_mask"] is None or d["alpha_mask"].shape == (d["edge_index"].size(1),)
+        if family == "maxcut":
+            assert d["kept"].numel() > 0 and 0 <= int(d["kept"].min()) and int(d["kept"].max()) < d["n"]
+            assert d["s"].shape == (d["n"],) and bool((d["s"] > 0).all())
 
 
 @pytest.mark.parametrize("family", sorted(FLOAT_REFS))
@@ -187,7 +300,9 @@ def test_the_reference_alone_is_well_conditioned(family):
             r64, r32 = ref(d, torch.float64)[0], ref(d, torch.float32)[0]
         worst = conditioning(r64, r32)
         assert worst <= CAP / FACTOR, (family, d["seed"], worst)
-        case = f"{family}-{d['seed']}"
+        # (the upstream gradients are seeded by the case's name: the public layer of the two edge families is checked
+        # under the names the sweep uses, so this is the conditioning of exactly the gradients compared on the device)
+        case = f"{family}-public-{d['seed']}" if family in ("asap", "maxcut") else f"{family}-{d['seed']}"
         fails = forward_errors(case, r32, r64, r32)
         fails += grad_path_errors(case, lambda: ref(d, torch.float32), lambda dt: ref(d, dt), LEAVES[family])
         assert not fails, "\n".join(fails)
@@ -270,4 +385,79 @@ def test_one_loss_term_scaled_by_a_thousandth_is_flagged():
         gfails = grad_path_errors(case, faulty, lambda dt: FR.jb_reference(d, dt), ["s"])
         assert gfails and all(f"path {name}," in m for m in gfails), gfails
         hits += 1
+    assert hits >= 1
+
+
+# ------------------------------------------------------------------------------------------- ASAP and MaxCut stand-ins
+def test_the_exact_references_of_the_edge_families_pass_themselves():
+    """The index, the arg-max table and the labels are deterministic functions of the draw, and the two index forms of
+    one direction describe the same groups in the same order."""
+    for d in draws("asap")[::4] + draws("maxcut")[::4]:
+        ei, n = d["edge_index"], d["n"]
+        for by_dst in (True, False):
+            want = FR.edge_group_exact(ei, n, by_dst)
+            assert int(want["row_ptr"][-1]) == ei.size(1) and want["max_members"] == int(want["row_ptr"].diff().max())
+            order = FR.regrouped_order(ei, by_dst)
+            other = FR.edge_group_exact(ei[:, order], n, by_dst)
+            assert torch.equal(other["row_ptr"], want["row_ptr"])
+            pos = lambda g, m: torch.arange(m) if g["perm"] is None else g["perm"]  # noqa: E731
+            assert torch.equal(order[pos(other, ei.size(1))], pos(want, ei.size(1)))  # the same edges in the same order
+    for d in draws("asap")[::4]:
+        want = FR.asap_argmax_exact(d)
+        assert not forward_errors(f"asap-{d['seed']}", FR.asap_argmax_exact(d), want, want, exact=set(want))
+        if d["edge_index"].size(1):
+            src = d["edge_index"][0][want["argpos"].clamp(min=0)]
+            picked = torch.where(want["argpos"] >= 0, d["x_pool"][src, torch.arange(d["F"]).expand_as(src)], 0.0)
+            assert torch.equal(picked, want["max"])  # the maximum is the entry at the stored position
+    for d in draws("maxcut")[::4]:
+        label = FR.maxcut_labels_exact(d)
+        assert torch.equal(label[d["kept"]], torch.arange(1, d["kept"].numel() + 1))
+
+
+def test_an_argmax_tie_resolved_to_the_higher_position_is_flagged():
+    """A wrong stand-in for ASAP's master query: among equal maxima the HIGHER edge position is stored.  Duplicate edges
+    tie in every column, the tied rows of ``x_tied`` between different sources; the maximum itself is the same."""
+    hits = 0
+    for d in draws("asap"):
+        for rows in [d["x_pool"]] + ([d["x_tied"]] if d["x_tied"] is not None else []):
+            want, bad = FR.asap_argmax_exact(d, rows), FR.asap_argmax_exact(d, rows, higher=True)
+            fails = forward_errors(f"asap-{d['seed']}", bad, want, want, exact=set(want))
+            if fails:
+                assert _flagged(fails) == {"argpos"}, fails
+                hits += 1
+    assert hits >= 1
+
+
+def test_an_edge_softmax_that_loses_the_65th_edge_of_a_group_is_flagged():
+    """A wrong stand-in for ASAP's edge softmax: lane 0's second trip through a group never reaches the sum.  Flagged as
+    "alpha" on exactly the draws with a group of at least 65 edges."""
+    hits = 0
+    for d in draws("asap"):
+        inp = FR.asap_operator_inputs(d)
+        with torch.no_grad():
+            r64, r32 = (FR.asap_operator_reference(d, dt, inp)[0] for dt in (torch.float64, torch.float32))
+            bad = FR.asap_operator_reference(d, torch.float32, inp, drop_65th=True)[0]
+        fails = forward_errors(f"asap-{d['seed']}", bad, r64, r32)
+        assert _flagged(fails) == ({"alpha"} if d["in_degree_max"] >= 65 else set()), (d["seed"], fails)
+        hits += bool(fails)
+    assert hits >= 1
+
+
+def test_a_diagonal_term_at_or_above_n_p_is_flagged():
+    """A wrong stand-in for MaxCut's layer: every node gets (1 - delta) z_i, also those at or above n_P (which the
+    reference's matrix has no row for).  Flagged as the layers' outputs on exactly the draws whose list does not reach N."""
+    hits = 0
+    for d in draws("maxcut"):
+        inp = FR.maxcut_operator_inputs(d)
+        with torch.no_grad():
+            r64, r32 = (FR.maxcut_operator_reference(d, dt, inp)[0] for dt in (torch.float64, torch.float32))
+            bad = FR.maxcut_operator_reference(d, torch.float32, inp, n_p=d["n"])[0]
+        fails = forward_errors(f"maxcut-{d['seed']}", bad, r64, r32)
+        layers = {f"{name}{l}" for l in range(len(d["widths"])) for name in ("h", "lin")} \
+            | {f"z_next{l}" for l in range(len(d["widths"]) - 1)}
+        if d["n_p"] < d["n"]:
+            assert _flagged(fails) and _flagged(fails) <= layers and f"lin0" in _flagged(fails), (d["seed"], fails)
+            hits += 1
+        else:
+            assert not fails, (d["seed"], fails)
     assert hits >= 1

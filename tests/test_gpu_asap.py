@@ -701,3 +701,25 @@ def test_gradients_of_the_pooler_match_the_fixture(name):
         return {"sum_sq": (got["x_pool"] ** 2).sum()}, {"x": x, **par}
 
     check_grad_paths(name, kernel, oracle, ["x"] + names)
+
+
+# ------------------------------------------------------------------------------------------------ regressions of the sweep
+def test_a_list_without_edges_goes_through_the_backward():
+    """The sweep's (asap, seed 11, g_sq) and (asap, seed 12, g_sq): five graphs without a single edge (224 nodes,
+    F = 16).  With E = 0 every per-edge pointer of ``asap_softmax_bwd`` is NULL, and the entry took the two NULLs of
+    ``g_l`` and ``alpha`` for "an input given as an output": the backward of the attention raised; past it, the node
+    looked the maxima's source rows up in an empty ``row``.  The operator gives an empty g_l and g_sq = 0; the two nodes'
+    gradients are those of the float64 reference-shaped restatement (x_new = 0, every node's query is the bias row)."""
+    n, f = 224, 16
+    gen = torch.Generator().manual_seed(11)
+    ei = torch.zeros(2, 0, dtype=torch.long, device=dev())
+    grp = K.sag_edge_group(ei, n, by_destination=True)
+    none = torch.zeros(0, device=dev())
+    g_l, g_sq = K.asap_softmax_bwd(grp, ei[0], none, none, torch.randn(n, generator=gen).to(dev()),
+                                   torch.randn(n, generator=gen).to(dev()), 0.2)
+    assert g_l.shape == (0,) and torch.equal(g_sq, torch.zeros(n, device=dev()))
+    torch.manual_seed(11)
+    state = {k: v.clone() for k, v in ASAPooling(f).state_dict().items()}
+    x0 = torch.randn(n, f, generator=gen)
+    kernel, oracle, leaves = _fitness_paths(state, dict(in_channels=f), x0, ei.cpu(), None)
+    check_grad_paths("asap/no-edges", kernel, oracle, leaves)

@@ -13,7 +13,9 @@ profiles/fuzz_newer_families.txt.
 
 Families: Just Balance, DMoN's, HOSC's and AsymCheegerCut's losses, LaPool's selector, BN-Pool's reconstruction loss, the
 segment readout,
-the SAG scorer, the k-MIS selector, the edge-contraction selector.
+the SAG scorer, the k-MIS selector, the edge-contraction selector, ASAP's fitness (csrc/asap.hip) and MaxCut's score
+net, cut loss and assignment rounds (csrc/maxcut.hip).  The last two also compare the shared edge-group index
+(``kernels.sag_edge_group``, both directions, both forms) exactly with a stable host argsort of the same list.
 """
 import zlib
 
@@ -1092,3 +1094,524 @@ def test_edge_contract_select(seed):
                 two = K.edge_contract_select(ei, n, graph_ptr=ptr, max_graph_nodes=gmax, route=route, **pri)
                 assert torch.equal(res.index, two.index) and torch.equal(res.matched, two.matched) and res.k == two.k
     assert not fails, "\n".join(fails)
+
+
+# ============================================================================================= the edge-group index
+def _check_groups(case, ei_host, ei, n):
+    """``kernels.sag_edge_group`` in both directions against a stable host argsort of the same list: the offsets, the
+    positions (or their absence on a list that ascends in the grouped row) and the longest group, exactly."""
+    from tgp import kernels as K
+    fails, groups, E = [], {}, ei_host.size(1)
+    for by_dst in (True, False):
+        grp = K.sag_edge_group(ei, n, by_destination=by_dst)
+        want = FR.edge_group_exact(ei_host, n, by_dst)
+        where = f"{case}-{'by_dst' if by_dst else 'by_src'}"
+        assert (grp.perm is None) == (want["perm"] is None), where
+        assert grp.nnz == E and grp.num_targets == n and grp.max_members == want["max_members"], where
+        ref = {"row_ptr": want["row_ptr"]}
+        got = {"row_ptr": grp.row_ptr}
+        if want["perm"] is not None:
+            ref["perm"], got["perm"] = want["perm"], grp.perm[:E]
+        fails += forward_errors(where, got, ref, ref, exact=set(ref))
+        groups[by_dst] = grp
+    return fails, groups[True], groups[False]
+
+
+def _regrouped(d, by_dst):
+    """The draw with its list in the other index form of that direction, every group's edges in the same order."""
+    order = FR.regrouped_order(d["edge_index"], by_dst)
+    v = dict(d)
+    v["edge_index"] = d["edge_index"][:, order].contiguous()
+    for name in ("edge_weight", "alpha_mask"):
+        if d.get(name) is not None:
+            v[name] = d[name][order].contiguous()
+    return v, order
+
+
+def _by_graph(d, outs, names):
+    """``outs`` plus, for every listed per-node output, its rows graph by graph: no graph is judged through the batch."""
+    res = dict(outs)
+    for name in names:
+        for b, c in enumerate(d.get("all_sizes", d["sizes"])):
+            if c and name in outs:
+                res[f"{name}[{b}]"] = outs[name][int(d["ptr"][b]):int(d["ptr"][b + 1])]
+    return res
+
+
+def _grads(y, leaves, up):
+    """d<y, up> / d leaf for every leaf, zeros where the path does not reach it."""
+    live = [t for t in leaves if t is not None]
+    got = torch.autograd.grad(y, live, up.to(y.dtype), allow_unused=True, retain_graph=True) if y.requires_grad and live else ()
+    got = iter(got)
+    out = []
+    for t in leaves:
+        g = None if t is None else next(got, None)
+        out.append(torch.zeros_like(t) if (g is None and t is not None) else g)
+    return out
+
+
+# ============================================================================================================= ASAP
+def _rows_view(t, layout):
+    """Host rows [n, F] as the device view of the drawn layout (tests/test_gpu_asap.py ``rows``): a column slice one
+    float past a 16-byte boundary (row stride F + 3), a column slice that keeps the 16-byte loads (row stride the next
+    multiple of four above F + 3), or contiguous but 4 bytes into its buffer.  The columns outside a slice hold NaN."""
+    t = mv(t)
+    n, f = t.shape
+    if layout == "offset":
+        return offset_by_one_element(t)
+    if layout.startswith("sliced"):
+        width, first = (f + 3, 1) if layout == "sliced_unaligned" else ((f + 7) // 4 * 4, 0)
+        base = torch.full((n, width), float("nan"), device=t.device)
+        base[:, first:first + f] = t
+        view = base[:, first:first + f]
+        assert view.stride(0) == width and view.data_ptr() % 16 == 4 * first
+        return view
+    return t
+
+
+def _asap_form(x):
+    """The load form the row kernels take for ``x``: the library's rule restated from F, the row stride and the pointer."""
+    ld = x.stride(0) if x.size(0) > 1 else max(x.stride(0), x.size(1))
+    return "vec16" if x.size(1) >= 4 and ld % 4 == 0 and x.data_ptr() % 16 == 0 else "scalar"
+
+
+def _asap_operators(d, case, report, twice):
+    from tgp import kernels as K
+    fac = factor_of("asap")
+    n, F, E, slope = d["n"], d["F"], d["edge_index"].size(1), d["negative_slope"]
+    ei = mv(d["edge_index"])
+    src, dst = ei[0], ei[1]
+    fails, by_dst, by_src = _check_groups(case, d["edge_index"], ei, n)
+    x = _rows_view(d["x"], d["layout"])
+    x_pool = x if d["same_pool"] else _rows_view(d["x_pool"], d["layout"])
+    assert _asap_form(x) == d["form"] and _asap_form(x_pool) == d["form"], (case, d["layout"], F)
+    assert d["lanes"] == FI.asap_lanes(F, d["form"])
+    inp = FR.asap_operator_inputs(d)
+    wt, c, sq_in, sp_in, val, w3, p_in = (mv(inp[k]) for k in ("w_tilde", "c", "sq", "sp", "val", "w3", "p"))
+    b1, b3, ew = mv(d["params"]["select_scorer.lin1.bias"]), mv(d["params"]["select_scorer.lin3.bias"]), mv(d["edge_weight"])
+
+    def forward():
+        sq, arg = K.asap_query(by_dst, src, x_pool, wt, c, want_arg=True)
+        alpha = K.asap_edge_softmax(by_dst, src, sq_in, sp_in, slope)
+        out, proj = K.asap_attend(by_dst, src, x, val, w3)
+        t, a = K.asap_leconv(by_dst, src, p_in, ew, b1, b3, d["act"], want_t=True)
+        return {"sq": sq, "alpha": alpha, "out": out, "proj": proj, "t": t, "a": a, "argpos": arg}
+    got = forward()
+    # without the table (the inference route folds the slots another way): the same bits
+    same = {"sq without argpos": got["sq"]}
+    fails += forward_errors(case, {"sq without argpos": K.asap_query(by_dst, src, x_pool, wt, c)}, same, same, exact=set(same))
+    plain, none = K.asap_attend(by_dst, src, x, val)
+    assert none is None and torch.equal(plain, got["out"]), case
+    assert torch.equal(K.asap_leconv(by_dst, src, p_in, ew, b1, b3, d["act"]), got["a"]), case
+    with torch.no_grad():
+        r64, r32 = FR.asap_operator_reference(d, F64, inp)[0], FR.asap_operator_reference(d, F32, inp)[0]
+    fails += forward_errors(case, got, r64, r32, factor=fac, report=report)
+    # the arg-max table (the lowest position among equals, -1 for an empty group) and the maximum itself, exactly
+    exact = FR.asap_argmax_exact(d)
+    probe, zero = {"argpos": got["argpos"]}, torch.zeros(1, device=dev())
+    cols = sorted({0, F // 2, F - 1})
+    for f in cols:  # w~ = e_f, c = 0: sq is column f of the max row, an entry of the input
+        e_f = torch.zeros(F, device=dev())
+        e_f[f] = 1.0
+        probe[f"max[:,{f}]"] = K.asap_query(by_dst, src, x_pool, e_f, zero)
+        exact[f"max[:,{f}]"] = exact["max"][:, f]
+    del exact["max"]
+    fails += forward_errors(case, probe, exact, exact, exact=set(exact))
+    if d["x_tied"] is not None:  # maxima held by several DIFFERENT source rows: forward only, the positions exactly
+        tied = FR.asap_argmax_exact(d, d["x_tied"])
+        _, arg = K.asap_query(by_dst, src, _rows_view(d["x_tied"], d["layout"]), wt, c, want_arg=True)
+        fails += forward_errors(f"{case}-tied", {"argpos": arg}, {"argpos": tied["argpos"]}, tied, exact={"argpos"})
+    # the four backward operators on seeded upstream gradients, against the float64 autograd of the same definitions
+    g_out, g_alpha, g_sq = upstream(case + "g", n, F), upstream(case + "ga", E), upstream(case + "gsq", n)
+
+    def backward():
+        g_l, g_sq_out = K.asap_softmax_bwd(by_dst, src, got["alpha"], mv(g_alpha), sq_in, sp_in, slope)
+        return {"g_x": K.asap_attend(by_src, dst, mv(g_out), val)[0], "g_val": K.asap_edge_dot(by_dst, src, mv(g_out), x),
+                "g_l": g_l, "g_sq": g_sq_out, "g_x_pool": K.asap_query_bwd(by_src, dst, got["argpos"], mv(g_sq), wt)}
+
+    def ref_backward(dtype):
+        outs, lv = FR.asap_operator_reference(d, dtype, inp)
+        g_x, g_val = _grads(outs["out"], [lv["x"], lv["val"]], g_out)
+        g_l, g_sq_out = _grads(outs["alpha"], [lv["logit"], lv["sq_in"]], g_alpha)
+        (g_xp,) = _grads(outs["sq"], [lv["x_pool"]], g_sq)
+        return {"g_x": g_x, "g_val": torch.zeros(0, dtype=dtype) if g_val is None else g_val, "g_l": g_l,
+                "g_sq": g_sq_out, "g_x_pool": g_xp}
+    got_b = backward()
+    fails += forward_errors(f"{case}-bwd", got_b, ref_backward(F64), ref_backward(F32), factor=fac, report=report)
+    if twice:  # the same calls again: equal bits, forward and backward
+        for first, second in ((got, forward()), (got_b, backward())):
+            assert all(torch.equal(first[k], second[k]) for k in first), case
+    return fails
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_asap_operators(seed):
+    """Every ``tgp.kernels`` wrapper of csrc/asap.hip on the draw, one by one, each against its own plain definition:
+    the index in both directions, the master query with its arg-max table, the edge softmax, the attend kernel with its
+    projections, the LEConv aggregate, and the four backward operators."""
+    d = FI.draw("asap", seed, limits())
+    case, report = f"asap-op-{seed}", []
+    fails = _asap_operators(d, case, report, seed % 4 == 0)
+    if seed % 4 == 0:  # the same list in the other index form of its by-destination groups: within the bound as well
+        fails += _asap_operators(_regrouped(d, True)[0], f"{case}-regrouped", report, False)
+    finish(case, fails, report)
+
+
+class _Calls:
+    """Counts the calls of functions of a module while a block runs (which route a public class took)."""
+
+    def __init__(self, owner, *names):
+        self.owner, self.names, self.count = owner, names, {n: 0 for n in names}
+
+    def __enter__(self):
+        self._orig = {n: getattr(self.owner, n) for n in self.names}
+        for n in self.names:
+            def counted(*a, _n=n, **k):
+                self.count[_n] += 1
+                return self._orig[_n](*a, **k)
+            setattr(self.owner, n, counted)
+        return self
+
+    def __exit__(self, *exc):
+        for n, fn in self._orig.items():
+            setattr(self.owner, n, fn)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_asap_public(seed):
+    """``functions.asap_attention`` + ``asap_leconv_score`` (one autograd node each) against the REFERENCE-SHAPED
+    restatement: values graph by graph, gradients one output at a time to x, x_pool and every drawn parameter; the same
+    through ``ASAPooling.fitness`` and the whole pooler where the draw is one the class takes (every bias on, x_pool = x;
+    the pooler: no mask), what follows the selection on the product's own kept nodes."""
+    import asap_restatement as RAS
+    from tgp import functions as Fn
+    from tgp.poolers import ASAPooling
+    d = FI.draw("asap", seed, limits())
+    case, report, fac = f"asap-public-{seed}", [], factor_of("asap")
+    ei, ew, mask, slope = mv(d["edge_index"]), mv(d["edge_weight"]), mv(d["alpha_mask"]), d["negative_slope"]
+    names = [k for k, v in d["params"].items() if v is not None]
+
+    def leaves(view):
+        x = _rows_view(d["x"], view["layout"]).detach().requires_grad_(True)
+        x_pool = x if d["same_pool"] else _rows_view(d["x_pool"], view["layout"]).detach().requires_grad_(True)
+        return x, x_pool, {k: mv(d["params"][k]).requires_grad_(True) for k in names}
+
+    def run(x, x_pool, par, edges, weight, msk):
+        w3 = torch.cat([par[f"select_scorer.lin{k}.weight"] for k in (1, 2, 3)])
+        alpha, x_new, p = Fn.asap_attention(x, x_pool, edges, par["lin.weight"], par.get("lin.bias"), par["att.weight"],
+                                            par.get("att.bias"), slope, msk, w3)
+        score = Fn.asap_leconv_score(x_new, edges, weight, w3, par.get("select_scorer.lin1.bias"),
+                                     par.get("select_scorer.lin3.bias"), d["act"], p)
+        return {"alpha": alpha, "x_new": x_new, "score": score}
+
+    def kernel():
+        x, x_pool, par = leaves(d)
+        outs = run(x, x_pool, par, ei, ew, mask)
+        assert "_AsapAttentionFnBackward" in _graph_names(outs["x_new"].grad_fn), case
+        assert "_AsapLeconvFnBackward" in _graph_names(outs["score"].grad_fn) and not outs["alpha"].requires_grad, case
+        return outs, {"x": x, "x_pool": x_pool, **par}
+
+    def oracle(dtype):
+        return FR.asap_reference(d, dtype)
+    assert _asap_form(leaves(d)[0]) == d["form"], case
+    outs, _ = kernel()
+    rows = ("x_new", "score")
+    with torch.no_grad():
+        r64, r32 = _by_graph(d, oracle(F64)[0], rows), _by_graph(d, oracle(F32)[0], rows)
+        fails = forward_errors(case, _by_graph(d, outs, rows), r64, r32, factor=fac, report=report)
+        x, x_pool, par = leaves(d)  # without a graph: the inference route (no arg-max table), held to the same bound
+        plain = run(x.detach(), x_pool.detach(), {k: v.detach() for k, v in par.items()}, ei, ew, mask)
+        fails += forward_errors(f"{case}-no-grad", _by_graph(d, plain, rows), r64, r32, factor=fac, report=report)
+    finish(case, fails, report)
+    lv_names = ["x", "x_pool"] + names
+    check_grads(case, kernel, oracle, lv_names)
+    if seed % 4 == 0:
+        runs = []
+        for _ in range(2):  # the same public call twice: equal bits, forward and backward
+            o, lv = kernel()
+            wrt = [lv["x"]] + ([] if d["same_pool"] else [lv["x_pool"]]) + [lv[k] for k in names]
+            total = (o["x_new"] * o["score"].view(-1, 1)).sum()
+            runs.append([o["alpha"], o["x_new"].detach(), o["score"].detach()] + list(torch.autograd.grad(total, wrt)))
+        assert all(torch.equal(u, v) for u, v in zip(*runs)), case
+        v, order = _regrouped(d, True)  # the other index form of the same list: within the bound as well
+        x, x_pool, par = leaves(v)
+        with torch.no_grad():
+            other = run(x.detach(), x_pool.detach(), {k: t.detach() for k, t in par.items()}, mv(v["edge_index"]),
+                        mv(v["edge_weight"]), mv(v["alpha_mask"]))
+            want64, want32 = dict(r64, alpha=r64["alpha"][order]), dict(r32, alpha=r32["alpha"][order])
+            more = []
+            fails = forward_errors(f"{case}-regrouped", _by_graph(d, other, rows), want64, want32, factor=fac, report=more)
+        finish(case, fails, more)
+    if not (d["bias"] and d["same_pool"]):
+        return
+    # the public class on the draws it takes natively
+    pool = ASAPooling(d["F"], ratio=0.5, negative_slope=slope, nonlinearity=d["act"]).to(dev()).eval()
+    pool.load_state_dict({k: mv(t) for k, t in d["params"].items()})
+    par = dict(pool.named_parameters())
+    with _Calls(Fn, "asap_attention", "asap_leconv_score") as calls:
+        x = _rows_view(d["x"], d["layout"]).detach().requires_grad_(True)
+        alpha, x_new, score = pool.fitness(x, ei, ew, mask=mask, act=d["act"])
+    assert calls.count == {"asap_attention": 1, "asap_leconv_score": 1}, (case, calls.count)  # the native route
+    assert "_AsapAttentionFnBackward" in _graph_names(x_new.grad_fn) and "_AsapLeconvFnBackward" in _graph_names(score.grad_fn)
+    for name, t in (("alpha", alpha), ("x_new", x_new), ("score", score)):
+        assert torch.equal(t.detach(), outs[name].detach()), (case, name)  # the functions' own bits
+    if d["alpha_mask"] is not None:
+        return
+    # the whole pooler: Reduce on the PRODUCT's kept nodes (TopK's choice among float scores is not compared)
+    batch, kept = mv(d["batch"]), {}
+
+    def pooler():
+        x = _rows_view(d["x"], d["layout"]).detach().requires_grad_(True)
+        with _Calls(Fn, "asap_attention") as calls:
+            out = pool(x=x, adj=ei, edge_weight=ew, batch=batch)
+        assert calls.count["asap_attention"] == 1, case
+        perm = torch.empty_like(out.so.node_index)
+        perm[out.so.cluster_index] = out.so.node_index  # row c of the pooled features is the kept node of supernode c
+        kept["perm"] = perm.cpu()
+        return {"x_pool": out.x}, {"x": x, **par}
+    pooler()
+    fixture = FR.asap_pool_case(d)
+
+    def pooled(dtype):
+        x = d["x"].to(dtype).requires_grad_(True)
+        p = {k: t.to(dtype).requires_grad_(True) for k, t in d["params"].items()}
+        got = RAS.pool_case(fixture, dtype, collapsed=False, params=p, x=x, perm=kept["perm"])
+        return {"x_pool": got["x_pool"]}, {"x": x, **p}
+    more = []
+    with torch.no_grad():
+        fails = forward_errors(f"{case}-pooler", pooler()[0], pooled(F64)[0], pooled(F32)[0], factor=fac, report=more)
+    finish(case, fails, more)
+    # (where no kept node's group holds logits on both sides of 0, the pooled rows do not depend on the query half of
+    # the attention in exact arithmetic: its parameters are then no leaves of this path)
+    query_half = () if FR.asap_query_half_matters(d, kept["perm"]) else ("lin.weight", "lin.bias", "att.bias")
+    check_grads(f"{case}-pooler", pooler, pooled, ["x"] + [k for k in names if k not in query_half])
+
+
+# =========================================================================================================== MaxCut
+def _maxcut_lists(d):
+    """The score net's parameters of the draw as ``functions.maxcut_score`` takes them, by the reference's names."""
+    import maxcut_restatement as RM
+    pre, depth, n_mlp = RM.PRE, len(d["widths"]), len(d["mlp_units"])
+    tail = [f"{pre}mlp.{l}{e}" for l in range(n_mlp) for e in (".weight", ".bias")] \
+        + [pre + "final_layer.weight", pre + "final_layer.bias"]
+    return ([pre + "initial_layer.weight", pre + "initial_layer.bias"], [f"{pre}mp_convs.{l}.lin.weight" for l in range(depth)],
+            [f"{pre}mp_convs.{l}.bias" for l in range(depth)], tail)
+
+
+def _maxcut_operators(d, case, report, twice, inp=None, seeds=None):
+    """(failures, every output by name, the operators' float32 inputs) of the ``tgp.kernels`` wrappers of
+    csrc/maxcut.hip on the draw, one by one.  ``inp``: the inputs of another run (the same list in another order: the
+    host's own dinv would be summed in that other order); ``seeds``: that run's case, which names its upstream gradients."""
+    import types
+
+    import maxcut_restatement as RM
+    from tgp import kernels as K
+    fac = factor_of("maxcut")
+    n, E, delta, widths = d["n"], d["edge_index"].size(1), d["delta"], d["widths"]
+    ei = mv(d["edge_index"])
+    row, col = ei[0], ei[1]
+    fails, by_dst, by_src = _check_groups(case, d["edge_index"], ei, n)
+    ew, par = mv(d["edge_weight"]), {k: mv(v) for k, v in d["params"].items()}
+    inp = FR.maxcut_operator_inputs(d) if inp is None else inp
+    w32 = RM._weights(d["edge_index"], d["edge_weight"], F32)
+    dinv_in = mv(inp["dinv"])
+    coef_in, coef_t_in = mv(w32 * inp["dinv"][d["edge_index"][0]]), mv(w32 * inp["dinv"][d["edge_index"][1]])
+    n_p = K.maxcut_n_p(ei)
+    assert int(n_p) == d["n_p"], case
+    place = offset_by_one_element if d["layout"] == "offset" else (lambda t: t)
+    g_t = [upstream(f"{seeds or case}gt{l}", n, c) for l, c in enumerate(widths)]
+    _, conv_w, conv_b, tail = _maxcut_lists(d)
+    s = mv(d["s"])
+
+    def forward():
+        dinv, coef, coef_t = K.maxcut_degree(by_src, ei, ew, True, True)
+        got = {"dinv": dinv, "coef": coef, "coef_t": coef_t}
+        for l in range(len(widths)):
+            z = place(mv(inp["z"][l]))
+            w_next = par[conv_w[l + 1]] if l + 1 < len(widths) else None
+            h, zn = K.maxcut_layer(by_dst, row, coef_in, dinv_in, z, par[conv_b[l]], n_p, delta, d["mp_act"], w_next)
+            got[f"h{l}"] = h
+            if w_next is not None:
+                got[f"z_next{l}"] = zn
+                none, again = K.maxcut_layer(by_dst, row, coef_in, dinv_in, z, par[conv_b[l]], n_p, delta, d["mp_act"],
+                                             w_next, want_h=False)
+                assert none is None and torch.equal(again, zn), (case, l)  # without h: the same bits
+            got[f"lin{l}"] = K.maxcut_layer(by_dst, row, coef_in, dinv_in, z, None, n_p, delta, "identity")[0]
+            # the backward's use: the by-source group with w_e dinv[dst_e], no bias, no activation, g_h_prev = g_z W fused
+            back = par[conv_w[l]].t().contiguous() if l > 0 else None
+            got[f"g_z{l}"], g_h = K.maxcut_layer(by_src, col, coef_t_in, dinv_in, place(mv(g_t[l])), None, n_p, delta,
+                                                 "identity", back, want_h=True)
+            if l > 0:
+                got[f"g_h{l}"] = g_h
+        if d["tail"] != "unfit":
+            got["tail"] = K.maxcut_tail(mv(inp["h_tail"]), [par[k] for k in tail[0::2]], [par[k] for k in tail[1::2]],
+                                        d["mlp_act"], d["act"])
+        got["az"], got["cut"], got["wsum"] = K.maxcut_cut(by_src, col, s, ew)
+        at = K.maxcut_cut(by_dst, row, s, ew, want_cut=False, want_wsum=False)
+        assert at[1] is None and at[2] is None
+        got["at"] = at[0]
+        labels = torch.zeros(n, dtype=torch.int32, device=dev())
+        labels[mv(d["kept"])] = torch.arange(1, d["kept"].numel() + 1, dtype=torch.int32, device=dev())
+        got["labels"] = K.maxcut_assign_rounds(by_dst, row, labels, d["max_iter"])
+        return got
+
+    def reference(dtype):
+        outs, lv = FR.maxcut_operator_reference(d, dtype, inp)
+        for l in range(len(widths)):
+            (outs[f"g_z{l}"],) = _grads(outs[f"lin{l}"], [lv[f"z{l}"]], g_t[l])
+            if l > 0:
+                outs[f"g_h{l}"] = outs[f"g_z{l}"] @ d["params"][conv_w[l]].to(dtype)
+        return {k: v.detach() for k, v in outs.items()}
+    got = forward()
+    layers = [types.SimpleNamespace(weight=d["params"][w], bias=d["params"][b]) for w, b in zip(tail[0::2], tail[1::2])]
+    assert K.maxcut_tail_fits(widths[-1], layers) == (d["tail"] != "unfit"), case
+    if d["zero_degree_node"] is not None:  # its degree is 0 although it has edges: inf -> 0
+        assert float(got["dinv"][d["zero_degree_node"]]) == 0.0, case
+    r64, r32 = reference(F64), reference(F32)
+    exact = {"labels": FR.maxcut_labels_exact(d)}
+    fails += forward_errors(case, got, {**r64, **exact}, r32, exact={"labels"}, factor=fac, report=report)
+    # the weight gradient a^T b at the drawn N and around the rows of one partial sum
+    ca, cb = widths[-1], d["F"]
+    for rows in [n] + (d["wgrad_rows"] if not case.endswith("regrouped") else []):
+        a, b = upstream(f"{case}wa{rows}", rows, ca), upstream(f"{case}wb{rows}", rows, cb)
+        name = "wgrad" if rows == n else f"wgrad@{rows}"
+        got[name] = K.maxcut_wgrad(mv(a), mv(b))
+        fails += forward_errors(case, {name: got[name]}, {name: a.double().t() @ b.double()}, {name: a.t() @ b}, factor=fac,
+                                report=report)
+        if twice:
+            assert torch.equal(got[name], K.maxcut_wgrad(mv(a), mv(b))), (case, name)
+    if twice:
+        again = forward()
+        assert all(torch.equal(got[k], again[k]) for k in again), case
+    return fails, got, inp
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_maxcut_operators(seed):
+    """Every ``tgp.kernels`` wrapper of csrc/maxcut.hip on the draw: the index in both directions, the degrees with both
+    coefficient arrays, every drawn layer (h, the fused projection to the next layer's width, the form without h, the
+    backward's use over the by-source group), the tail, the weight gradient, the cut kernel in both directions and the
+    assignment rounds (exactly).  One seed in four: the same calls twice, and the list in the other index form of its
+    by-destination and of its by-source groups -- EQUAL bits in everything that is summed over those groups."""
+    d = FI.draw("maxcut", seed, limits())
+    case, report = f"maxcut-op-{seed}", []
+    fails, got, inp = _maxcut_operators(d, case, report, seed % 4 == 0)
+    if seed % 4 == 0:
+        depth = len(d["widths"])
+        sums = {True: [f"{n}{l}" for l in range(depth) for n in ("h", "lin")] + [f"z_next{l}" for l in range(depth - 1)]
+                + ["at", "labels"],
+                False: ["dinv", "az", "cut", "wsum"] + [f"g_z{l}" for l in range(depth)] + [f"g_h{l}" for l in range(1, depth)]}
+        for by_dst in (True, False):
+            v, order = _regrouped(d, by_dst)
+            more, other, _ = _maxcut_operators(v, f"{case}-{'dst' if by_dst else 'src'}-regrouped", report, False, inp, case)
+            fails += more
+            for name in sums[by_dst]:
+                assert torch.equal(got[name], other[name]), (case, by_dst, name)
+            if not by_dst:
+                for name in ("coef", "coef_t"):
+                    assert torch.equal(got[name][mv(order)], other[name]), (case, name)
+    finish(case, fails, report)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_maxcut_public(seed):
+    """``functions.maxcut_score`` and ``functions.maxcut_loss`` (one autograd node each) against the REFERENCE-SHAPED
+    score net (the explicit delta-GCN matrix) and ``cut_loss``: values (the scores graph by graph), gradients one output
+    at a time to x, s and every parameter; the same through ``MaxCutScoreNet`` and ``utils.maxcut_loss`` with their
+    routes -- a tail that does not fit the kernels takes the composed form --, and ``MaxCutSelect.assign`` on the drawn
+    kept nodes (the labelled nodes only: the draw for the others is not compared)."""
+    import maxcut_restatement as RM
+    from tgp import functions as Fn
+    from tgp import kernels as K
+    from tgp.poolers import MaxCutScoreNet, MaxCutSelect
+    from tgp.select import SelectOutput
+    from tgp.utils import maxcut_loss
+    d = FI.draw("maxcut", seed, limits())
+    case, report, fac = f"maxcut-public-{seed}", [], factor_of("maxcut")
+    fits, n, sizes = d["tail"] != "unfit", d["n"], d["all_sizes"]
+    ei, ew, batch = mv(d["edge_index"]), mv(d["edge_weight"]), mv(d["batch"])
+    names = sorted(d["params"])
+    init, conv_w, conv_b, tail = _maxcut_lists(d)
+    nb = int(d["batch"].max()) + 1  # (the graphs the batch vector shows: an empty graph at the end is not among them)
+    ptr, longest = mv(d["ptr"][:nb + 1]), max(sizes[:nb])
+    place = offset_by_one_element if d["layout"] == "offset" else (lambda t: t)
+
+    def leaves():
+        return place(mv(d["x"])).requires_grad_(True), mv(d["s"]).requires_grad_(True), \
+            {k: mv(d["params"][k]).requires_grad_(True) for k in names}
+
+    def score_of(x, par, edges, weight):
+        return Fn.maxcut_score(x, edges, weight, [par[k] for k in init], [par[k] for k in conv_w], [par[k] for k in conv_b],
+                               [par[k] for k in tail], d["delta"], d["mp_act"], d["mlp_act"], d["act"])
+
+    net = MaxCutScoreNet(d["F"], mp_units=d["widths"], mp_act=d["mp_act"], mlp_units=d["mlp_units"], mlp_act=d["mlp_act"],
+                         act=d["act"], delta=d["delta"]).to(dev())
+    net.load_state_dict({k[len(RM.PRE):]: mv(v) for k, v in d["params"].items()})
+    net_par = {RM.PRE + k: v for k, v in net.named_parameters()}
+    assert sorted(net_par) == names
+
+    def kernel():
+        x, s, par = leaves()
+        if fits:
+            score = score_of(x, par, ei, ew)
+            assert "_MaxCutScoreFnBackward" in _graph_names(score.grad_fn), case
+        else:  # the class is the only public form of a net the kernels do not take: the composed route
+            with _Calls(Fn, "maxcut_score") as calls:
+                score = net(x, ei, ew).view(-1)
+            assert calls.count["maxcut_score"] == 0 and "_MaxCutScoreFnBackward" not in _graph_names(score.grad_fn), case
+            par = net_par
+        loss = Fn.maxcut_loss(s, ei, ew, batch, ptr, nb, longest)
+        assert "_MaxCutLossFnBackward" in _graph_names(loss.grad_fn), case
+        return {"score": score, "loss": loss}, {"x": x, "s": s, **par}
+
+    def oracle(dtype):
+        return FR.maxcut_reference(d, dtype)
+    assert net.native_case(place(mv(d["x"])), ei, ew) == fits, case
+    outs, _ = kernel()
+    with torch.no_grad():
+        r64, r32 = _by_graph(d, oracle(F64)[0], ("score",)), _by_graph(d, oracle(F32)[0], ("score",))
+        fails = forward_errors(case, _by_graph(d, outs, ("score",)), r64, r32, factor=fac, report=report)
+        # without a graph: the inference route (only the last layer's h is written, the tail kernel scores the rows)
+        with _Calls(Fn, "maxcut_score", "maxcut_loss") as calls:
+            plain = {"score": net(place(mv(d["x"])), ei, ew).view(-1), "loss": maxcut_loss(mv(d["s"]), ei, ew, batch)}
+        assert calls.count == {"maxcut_score": int(fits), "maxcut_loss": 1}, (case, calls.count)
+        assert torch.equal(plain["loss"], outs["loss"].detach()), case
+        fails += forward_errors(f"{case}-no-grad", _by_graph(d, plain, ("score",)), r64, r32, factor=fac, report=report)
+    finish(case, fails, report)
+    check_grads(case, kernel, oracle, ["x", "s"] + names)
+    if fits:  # the class under autograd: the functions' node and its bits
+        x, _, _ = leaves()
+        with _Calls(Fn, "maxcut_score") as calls:
+            tracked = net(x, ei, ew).view(-1)
+        assert calls.count["maxcut_score"] == 1 and "_MaxCutScoreFnBackward" in _graph_names(tracked.grad_fn), case
+        assert torch.equal(tracked.detach(), outs["score"].detach()), case
+    if seed % 4 == 0 and fits:
+        runs = []
+        for _ in range(2):  # the same public call twice: equal bits, forward and backward
+            o, lv = kernel()
+            wrt = [lv["x"], lv["s"]] + [lv[k] for k in names]
+            runs.append([o["score"].detach(), o["loss"].detach()] + list(torch.autograd.grad(o["score"].sum() + o["loss"], wrt)))
+        assert all(torch.equal(u, v) for u, v in zip(*runs)), case
+        v, _ = _regrouped(d, True)  # the other index form of the by-destination groups: within the bound as well
+        with torch.no_grad():
+            x, s, par = leaves()
+            e2, w2 = mv(v["edge_index"]), mv(v["edge_weight"])
+            other = {"score": score_of(x.detach(), {k: t.detach() for k, t in par.items()}, e2, w2),
+                     "loss": Fn.maxcut_loss(s.detach(), e2, w2, batch, ptr, nb, longest)}
+            more = []
+            fails = forward_errors(f"{case}-regrouped", _by_graph(d, other, ("score",)), r64, r32, factor=fac, report=more)
+        finish(case, fails, more)
+    # the assignment through the selector: native rounds unless every node is kept; the labelled nodes exactly
+    kept = mv(d["kept"])
+    sel = MaxCutSelect(4, mp_units=[4], mlp_units=[])
+    so = SelectOutput(node_index=kept, num_nodes=n, cluster_index=torch.arange(kept.numel(), device=dev()),
+                      num_supernodes=kept.numel())
+    with _Calls(K, "maxcut_assign_rounds") as calls:
+        got = sel.assign(so, ei, None, batch, d["max_iter"])
+    assert calls.count["maxcut_assign_rounds"] == int(kept.numel() < n), (case, calls.count)
+    label = FR.maxcut_labels_exact(d)
+    reached = label > 0
+    assert got.num_supernodes == kept.numel() and got.num_nodes == n, case
+    assert torch.equal(got.cluster_index.cpu()[reached], label[reached] - 1), case
+    if d["chain"]:
+        assert int((~reached).sum()) > 0, case  # the path's tail is left to the draw inside its graph

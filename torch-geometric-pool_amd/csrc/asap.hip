@@ -559,7 +559,8 @@ extern "C" int tgp_asap_softmax_bwd_f32(const int32_t* grp_ptr, const int32_t* g
   if (N == 0) return TGP_OK;
   TGP_REQUIRE(grp_ptr && sq && sp && g_sq && (E == 0 || (src && alpha && g_alpha && g_l)), TGP_ERR_INVALID,
               "tgp_asap_softmax_bwd_f32: null pointer");
-  TGP_REQUIRE(g_l != alpha && g_l != g_alpha && g_sq != sq && g_sq != sp, TGP_ERR_INVALID,
+  // (a list without edges hands every per-edge pointer as NULL: only g_sq, all zeros, is written)
+  TGP_REQUIRE((E == 0 || (g_l != alpha && g_l != g_alpha)) && g_sq != sq && g_sq != sp, TGP_ERR_INVALID,
               "tgp_asap_softmax_bwd_f32: an input given as an output");
   hipLaunchKernelGGL(asap_softmax_bwd_kernel, dim3(cdiv(N, 4)), dim3(256), 0, stream, grp_ptr, grp_perm, src, alpha,
                      g_alpha, sq, sp, N, E, negative_slope, g_l, g_sq);

@@ -754,8 +754,11 @@ class _AsapAttentionFn(torch.autograd.Function):
                     gxp = None
             s = g_sq.sum()
             if need[3] or need[5]:
-                src_of = row[arg.clamp(min=0).long()]  # [N,F]: the source row of every maximum
-                rows_max = x_pool.gather(0, src_of) * (arg >= 0)
+                if row.numel():
+                    src_of = row[arg.clamp(min=0).long()]  # [N,F]: the source row of every maximum
+                    rows_max = x_pool.gather(0, src_of) * (arg >= 0)
+                else:  # a list without edges: every group is empty, every maximum the scatter's zero
+                    rows_max = torch.zeros_like(x_pool)
                 g_wt = K.weighted_colsum(rows_max, g_sq)
                 if need[3]:
                     g_lin_w = torch.outer(a1, g_wt)
