@@ -339,6 +339,10 @@ int tgp_postprocess_sparse_norm_f32(const int64_t* row, const int64_t* col, floa
  * graph_sizes (optional): graph b's real nodes are its first graph_sizes[b] rows and everything beyond them in
  * S, A, X is zero (the layout of to_dense_batch / to_dense_adj, src.py:434-450); kernels then stop at the real
  * size instead of the padded one.  NULL = every row may be non-zero.
+ * Graphs beyond the one-wave / one-workgroup kernels take U = A S, S^T [U | X] split over N into partial slabs, and a
+ * slab combine with the post-processing; where U = A S runs one 128-column tile (K <= 128, K and F multiples of 4,
+ * F <= 64, N <= 1024, at least 256 row tiles of 128) the second product is folded into the first launch: one partial
+ * slab per 128-row tile, U never in memory.  The workspace is sized for the larger slab count of the two routes.
  * ---------------------------------------------------------------------------------- */
 size_t tgp_dense_pool_workspace_bytes(int64_t B, int64_t N, int64_t K, int64_t F);
 int tgp_dense_pool_f32(const float* S, const float* A, const float* X, int64_t B, int64_t N, int64_t K,

@@ -69,10 +69,15 @@ static DensePlan dense_plan(int64_t B, int64_t N, int64_t K, int64_t F, bool wit
   p.splits = static_cast<int>(splits);
   p.k_per_split = static_cast<int>(kps);
   p.u_floats = static_cast<size_t>(B) * N * K;
-  p.aslab_floats = static_cast<size_t>(B) * splits * K * K;
-  p.xslab_floats = static_cast<size_t>(B) * splits * K * F;
+  // the folded route (dense_pool_tiled) leaves one slab and one row of column sums per 128-row tile of N: both slab sets
+  // and the degree partials are sized for the larger of the two counts
+  const int64_t fold = fold_tiles(N, K, F) <= PR_MAX_SPLITS ? fold_tiles(N, K, F) : 0;
+  const int64_t slabs = splits > fold ? splits : fold;
+  const int64_t parts = splits * ((K + 63) / 64) > fold ? splits * ((K + 63) / 64) : fold;
+  p.aslab_floats = static_cast<size_t>(B) * slabs * K * K;
+  p.xslab_floats = static_cast<size_t>(B) * slabs * K * F;
   p.post_floats = post_ws_floats(B, K);
-  p.colsum_floats = static_cast<size_t>(B) * splits * ((K + 63) / 64) * K;  // post_rows_kernel's degree partials
+  p.colsum_floats = static_cast<size_t>(B) * parts * K;  // post_rows_kernel's degree partials
   return p;
 }
 
@@ -102,7 +107,7 @@ static int dense_pool_impl(const float* S, const float* A, const float* X, int64
                            void* stream_);
 static int dense_pool_tiled(const float* S, const float* A, const float* X, int64_t B, int64_t N, int64_t K, int64_t F,
                             int flags, float eps, float* x_pool, float* adj_raw, float* adj_pool, float* U, int64_t ldu,
-                            float* gram, const DensePlan& p, Carver& cv, hipStream_t stream);
+                            float* gram, const DensePlan& p, Carver& cv, hipStream_t stream, bool keep_u = true);
 
 extern "C" int tgp_dense_pool_f32(const float* S, const float* A, const float* X, int64_t B, int64_t N,
                                   int64_t K, int64_t F, int flags, float eps, const int64_t* graph_sizes,
@@ -317,15 +322,19 @@ static int dense_pool_impl(const float* S, const float* A, const float* X, int64
   const DensePlan p = dense_plan(B, N, K, F);
   Carver cv(ws);
   float* U = cv.take<float>(p.u_floats);
-  return dense_pool_tiled(S, A, X, B, N, K, F, flags, eps, x_pool, adj_raw, adj_pool, U, K, nullptr, p, cv, stream);
+  return dense_pool_tiled(S, A, X, B, N, K, F, flags, eps, x_pool, adj_raw, adj_pool, U, K, nullptr, p, cv, stream,
+                          /*keep_u=*/false);
 }
 
 // The tiled path: U = A S (row stride ldu: the training step keeps U inside a wider buffer), S^T [U | X (| S)] split
 // over N into slabs, and the slab combine + post-processing.  `gram` (optional, [B,K,K]): S^T S rides along as a third
 // right-hand side of the second product (MinCut's orthogonality loss and DiffPool's link-loss gradient need it).
+// keep_u = false (the caller has no use for U; no gram): where the zero-skipping U = A S kernel would run one column tile
+// (K <= 128) the second product is folded into it -- each workgroup leaves S_r^T [U_r | X_r] over its own 128 rows as one
+// of N / 128 partial slabs (launch_gemm_fold), U is never written, and post_rows_kernel adds the slabs up: two launches.
 static int dense_pool_tiled(const float* S, const float* A, const float* X, int64_t B, int64_t N, int64_t K, int64_t F,
                             int flags, float eps, float* x_pool, float* adj_raw, float* adj_pool, float* U, int64_t ldu,
-                            float* gram, const DensePlan& p, Carver& cv, hipStream_t stream) {
+                            float* gram, const DensePlan& p, Carver& cv, hipStream_t stream, bool keep_u) {
   const bool want_x = X && x_pool && F > 0;
   const bool want_a = A && (adj_raw || adj_pool);
   float* aslab = cv.take<float>(p.aslab_floats);
@@ -334,6 +343,35 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
   float* colpart = cv.take<float>(p.colsum_floats);
   float* gslab = gram ? cv.take<float>(p.aslab_floats) : nullptr;
 
+  const int fold = (want_a && !keep_u && !gram) ? fold_tiles(N, K, F) : 0;  // (F as dense_plan sized the slabs for)
+  if (fold > 0 && fold <= PR_MAX_SPLITS && static_cast<size_t>(B) * fold * K * K <= p.aslab_floats &&
+      post_rows_ok(K, flags, aslab, adj_raw, adj_pool) &&
+      reinterpret_cast<uintptr_t>(xslab) % 16 == 0) {
+    GemmArgs g{};
+    g.A = A; g.lda = N; g.sA = N * N;
+    g.M = static_cast<int>(N); g.Kd = static_cast<int>(N);
+    g.rhs[0] = GemmRhs{S, aslab, static_cast<int>(K), K, K, N * K, static_cast<long>(fold) * K * K, K * K};
+    if (want_x) g.rhs[1] = GemmRhs{X, xslab, static_cast<int>(F), F, F, N * F, static_cast<long>(fold) * K * F, K * F};
+    g.splits = 1; g.k_per_split = static_cast<int>((N + BK - 1) / BK * BK);
+    g.colsum = colpart;
+    g.colsum_skip_diag = (flags & TGP_REMOVE_SELF_LOOPS) ? 1 : 0;
+    const bool folded = (flags & TGP_ADJ_TRANSPOSED) ? launch_gemm_fold<true>(g, static_cast<int>(B), stream)
+                                                     : launch_gemm_fold<false>(g, static_cast<int>(B), stream);
+    if (folded) {
+      PostRowsArgs r{};
+      r.slab = aslab; r.splits = fold; r.s_split = K * K; r.s_batch = static_cast<long>(fold) * K * K;
+      r.colsum = (flags & TGP_DEGREE_NORM) ? colpart : nullptr; r.tiles_m = 1;
+      r.K = static_cast<int>(K); r.flags = flags; r.eps = eps; r.raw = adj_raw; r.dst = adj_pool;
+      if (want_x) {
+        r.xslab = xslab; r.xs_split = K * F; r.xs_batch = static_cast<long>(fold) * K * F;
+        r.F = static_cast<int>(F); r.x_pool = x_pool;
+      }
+      const unsigned grid = static_cast<unsigned>(B * ((K + PR_ROWS - 1) / PR_ROWS));
+      r.main_blocks = static_cast<int>(grid);
+      hipLaunchKernelGGL(post_rows_kernel, dim3(grid), dim3(512), 0, stream, r);
+      return check_launch("tgp_dense_pool_f32");
+    }
+  }
   if (want_a) {
     // U[b] = A[b] S[b]     (M = N, Kd = N, Nc = K)
     GemmArgs g{};

@@ -18,6 +18,7 @@ namespace tgp {
 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;
 #ifndef TGP_OPERAND_PREFETCH
@@ -100,6 +101,9 @@ struct GemmArgs {
   // takes the residual of its mirror image -- sum((resid[J-rows][I-cols] - C^T)^2) -- and tiles with I > J do nothing:
   // 36 instead of 64 products per graph at N = 1024
   int symmetric;
+  // MODE 4 (MODE 3 + the second product folded in, see launch_gemm_fold): rhs[0].C is the slab set [batches][tiles_m]
+  // [Nc][Nc] of S_r^T U_r (row tile r of batch b at b * sC + r * sCsplit; U itself is not stored), rhs[1] (Bm optional) is
+  // X with its slab set [batches][tiles_m][Nc][rhs[1].Nc], colsum is [batches][tiles_m][Nc]
 };
 
 // Row of a [rows][BK+1] LDS tile served by slot t = 8*g + r (8 lanes per slot, slot = one 128-byte row segment).
@@ -136,7 +140,8 @@ __device__ __forceinline__ float4 ld4_guarded(const float* p, bool ok) {
 // ALIGNED: buffer-descriptor path, all traffic is 16-byte vectors with one predicate per vector; bases and
 // leading dimensions need dword alignment only (see gemm_aligned).  Otherwise: scalar guarded path (matrices too
 // large for 32-bit descriptor offsets).
-// MODE 0: C = op(A) Bm (MODE 2: the same + GemmArgs.colsum; MODE 3: the same, skipping the MFMAs of sparse A chunks).  MODE 1 (link-prediction residual, utils/losses.py:644-708): Bm is stored
+// MODE 0: C = op(A) Bm (MODE 2: the same + GemmArgs.colsum; MODE 3: the same, skipping the MFMAs of sparse A chunks;
+// MODE 4: MODE 3's k-loop, then Bm_r^T [C_r | X_r] over the tile's own rows instead of the store of C).  MODE 1 (link-prediction residual, utils/losses.py:644-708): Bm is stored
 // [Nc][Kd] (n-major, i.e. the product is A Bm^T), and instead of storing C the epilogue accumulates
 // sum((resid - C)^2) over the tile, so S S^T never exists in memory.
 template <bool A_KMAJOR, bool ALIGNED, int BM, int BN, int MODE, int WN = 2>
@@ -155,7 +160,9 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   // at or below TGP_SPARSE_CHUNK_GROUPS skips its MFMAs and each wave walks the nonzeros of the rows it owns (rows
   // wave + NW j) with v_fma_f32 into a register accumulator [S_ROWS][S_COLS per lane], merged into the MFMA accumulator
   // once at the end.  Skipping A_ij * S_jk is exact for A_ij = +-0 and finite S_jk, so both forms compute the same sums.
-  constexpr bool SKIP = MODE == 3;
+  constexpr bool FOLD = MODE == 4;
+  constexpr bool SKIP = MODE == 3 || FOLD;
+  static_assert(!FOLD || (BM == 128 && BN == 128 && WN == 4), "MODE 4: one 128 x 128 tile, 16 waves as 4 x 4");
   constexpr int NW = THREADS / 64;                  // waves
   constexpr int S_ROWS = BM / NW, S_COLS = BN / 64;  // MODE 3: rows a wave owns, columns a lane owns
   static_assert(!SKIP || (ALIGNED && S_ROWS % 2 == 0 && (S_COLS == 1 || S_COLS == 2) && NW <= 16 && BM * BN <= 2 * STAGE_FLOATS),
@@ -657,6 +664,24 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   }
   __syncthreads();
   TGP_STAMP(1);
+  // MODE 4: the tail's operands -- rows m0 .. m0 + 127 of Bm (S_r) and of X (X_r) -- pass through registers: per thread
+  // four vectors of S_r (its B-tile vector, 32 rows apart) and two of X_r (16 lanes per row of <= 64 values, 64 rows
+  // apart).  Rows beyond the matrices and columns beyond Nc / F come back as zeros from the descriptors' range check.
+  [[maybe_unused]] float4 fs[4], fx[2];
+  auto fold_load = [&]() {
+    if constexpr (FOLD) {
+      const GemmRhs& RX = g.rhs[1];
+      const int x_bytes = RX.Bm ? static_cast<int>(g.Kd) * static_cast<int>(RX.ldb) * 4 : 0;
+      const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(RX.Bm ? RX.Bm + static_cast<long>(batch) * RX.sB : Bm), 0, x_bytes, 0x00020000);
+      const int ldx4 = RX.Bm ? static_cast<int>(RX.ldb) * 4 : 0;
+      const int voff_x = (RX.Bm && (tid & 15) * 4 < RX.Nc) ? (tid >> 4) * ldx4 + (tid & 15) * 16 : OOB;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fs[i] = buf_ld4(rsrc_b, voff_b[0], (m0 + 32 * i) * static_cast<int>(ldb) * 4);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fx[i] = buf_ld4(rsrc_x, voff_x, (m0 + 64 * i) * ldx4);
+    }
+  };
   int t = 0;
   using std::integral_constant;
   using FALSE_C = integral_constant<bool, false>;
@@ -702,7 +727,8 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     }
   }
   TGP_STAMP(2);
-  if constexpr (SKIP) {
+  fold_load();  // (MODE 4: the tail's operands are requested as the k-loop ends)
+  if constexpr (SKIP && !FOLD) {  // (MODE 4 adds the walk's sums to U where the tail keeps it: in LDS, below)
     if (any_sparse) {  // (workgroup-uniform; the k-loop's last barrier has passed: the LDS is free)
 #pragma unroll
       for (int j = 0; j < S_ROWS; ++j)
@@ -717,6 +743,147 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
                                 smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * BN + wn * (BN / WN) + j * 32 + lm]);
       __syncthreads();  // (the epilogue's LDS patches may reuse these words)
     }
+  }
+
+  // ---- MODE 4 tail: P = S_r^T [U_r | X_r] over the tile's 128 rows, U_r taken from the accumulators -------------------
+  // The 128 x 192 result is 8 x 12 blocks of 16 x 16 (v_mfma_f32_16x16x4_f32: the same exact fp32 chains as the 32 x 32
+  // form), six per wave -- wave (wm, wn) owns rows 32 wm .. + 31 and columns 48 wn .. + 47 of [S^T U | S^T X] -- each over
+  // the full k range, so every element has one owner and one summation order (k ascending) and nothing is added across
+  // waves.  Both operands lie in LDS whole, S_r [128][128] and [U_r | X_r] [128][192]: exactly the 160 KB, so the rows
+  // are not padded but swizzled -- column c of row k sits at c ^ 16 (k & 3), which keeps 16-byte vectors whole and puts
+  // the four k rows of an operand read on different banks.  The result then goes to LDS as one tile [128][196] and
+  // leaves in 16-byte stores; its column sums are taken from there in row order (16-row partials by eight thread
+  // groups, added in order).
+  if constexpr (FOLD) {
+    constexpr int P_LD = 196;
+    float* Sf = smem;
+    float* UXf = smem + BM * BN;
+    const GemmRhs& RX = g.rhs[1];
+    const int F = RX.Bm ? RX.Nc : 0;
+    const int l15 = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = (tid >> 5) + 32 * i;
+      *reinterpret_cast<float4*>(Sf + k * BN + (((tid & 31) * 4) ^ ((k & 3) << 4))) = fs[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = (tid >> 4) + 64 * i;
+      *reinterpret_cast<float4*>(UXf + k * 192 + ((BN + (tid & 15) * 4) ^ ((k & 3) << 4))) = fx[i];
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {  // rows beyond M are zeros (0 * Inf of the k-loop is not)
+      const int rl = (r & 3) + 8 * (r >> 2) + 4 * lk;
+      UXf[(wm * 32 + rl) * 192 + ((wn * 32 + lm) ^ ((r & 3) << 4))] = m0 + wm * 32 + rl < M ? acc[0][r] : 0.f;
+    }
+    f32x4 d[2][3];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[i][j][r] = 0.f;
+    __syncthreads();
+    if (any_sparse) {  // (workgroup-uniform) U += the walk's sums, each element by the lane that owns it: acc + sacc as in MODE 3
+#pragma unroll
+      for (int j = 0; j < S_ROWS; ++j) {
+        const int row = wave + NW * j;
+        float2* u = reinterpret_cast<float2*>(UXf + row * 192 + ((2 * lane) ^ ((row & 3) << 4)));
+        float2 v = *u;
+        v.x = __fadd_rn(v.x, sacc[j][0]);
+        v.y = __fadd_rn(v.y, sacc[j][S_COLS - 1]);
+        *u = v;
+      }
+      __syncthreads();
+    }
+    TGP_STAMP(8);  // (stamps build: slots 8 .. 11 are the tail's phases)
+    {
+      // operands of k-group s + 1 are requested before the MFMAs of group s; no branch inside (column blocks beyond
+      // Nc / F -- X absent or F < 64, Nc < 128 -- are multiplied all the same and not written below: a wave-uniform
+      // `if` per block compiled to a branch and a full LDS wait per block, 0.8 us of the C2 launch)
+      int a_at[2], b_at[3];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a_at[i] = lq * BN + ((wm * 32 + 16 * i + l15) ^ (lq << 4));
+#pragma unroll
+      for (int j = 0; j < 3; ++j) b_at[j] = lq * 192 + ((wn * 48 + 16 * j + l15) ^ (lq << 4));
+      float a[2][2], b[2][3];
+      auto fetch = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[s & 1][i] = Sf[4 * s * BN + a_at[i]];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) b[s & 1][j] = UXf[4 * s * 192 + b_at[j]];
+      };
+      fetch(0);
+#pragma unroll
+      for (int s = 0; s < 32; ++s) {
+        if (s + 1 < 32) fetch(s + 1);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            d[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][j], d[i][j], 0, 0, 0);
+        if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);  // ds_reads of group s + 1
+        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);                   // 6 x MFMA
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    TGP_STAMP(9);
+    __syncthreads();  // (the result tile overwrites the operands)
+    bool used[3];  // (wave-uniform) column blocks beyond Nc and beyond F are not written
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int c0 = wn * 48 + 16 * j;
+      used[j] = c0 < BN ? c0 < Nc : c0 - BN < F;
+    }
+    float* P = smem;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (used[j]) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) P[(wm * 32 + 16 * i + 4 * lq + r) * P_LD + wn * 48 + 16 * j + l15] = d[i][j][r];
+        }
+    __syncthreads();
+    TGP_STAMP(10);
+    // the column sums first: they need LDS alone, and the launch then ends behind its stores
+    if (g.colsum) {  // (workgroup-uniform)
+      float* part = smem + BM * P_LD;  // [8][BN]
+      const int j = tid & (BN - 1), q = tid >> 7;
+      float cs = 0.f;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int row = 16 * q + u;
+        const float v = P[row * P_LD + j];
+        cs = __fadd_rn(cs, (row >= Nc || (g.colsum_skip_diag && row == j)) ? 0.f : v);
+      }
+      part[q * BN + j] = cs;
+      __syncthreads();
+      if (tid < Nc) {
+        float tot = 0.f;
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) tot = __fadd_rn(tot, part[qq * BN + tid]);
+        g.colsum[(static_cast<long>(batch) * g.tiles_m + tm) * Nc + tid] = tot;
+      }
+    }
+    TGP_STAMP(11);
+    // rows and columns < Nc of S^T U, columns < F of S^T X (rows >= Nc of P are 0 * U: not zeros when U holds a NaN)
+    float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
+    const int kq = Nc >> 2, fq = F >> 2;
+    for (int e = tid; e < Nc * kq; e += THREADS) {
+      const int row = e / kq, c4 = (e - row * kq) * 4;
+      *reinterpret_cast<float4*>(Ca + static_cast<long>(row) * R.ldc + c4) = *reinterpret_cast<const float4*>(P + row * P_LD + c4);
+    }
+    if (F) {
+      float* Cx = RX.C + static_cast<long>(batch) * RX.sC + static_cast<long>(tm) * RX.sCsplit;
+      for (int e = tid; e < Nc * fq; e += THREADS) {
+        const int row = e / fq, c4 = (e - row * fq) * 4;
+        *reinterpret_cast<float4*>(Cx + static_cast<long>(row) * RX.ldc + c4) =
+            *reinterpret_cast<const float4*>(P + row * P_LD + BN + c4);
+      }
+    }
+    TGP_STAMP(3);
+    return;
   }
 
   // ---- epilogue: C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) -----------
@@ -951,6 +1118,41 @@ static void launch_gemm_skip_zeros(GemmArgs g, int batches, hipStream_t stream) 
   g.tiles_n1 = 0;
   const size_t lds = 2 * (BM * LDA_ROWMAJOR + BK * BN) * sizeof(float) + 2 * 16 * sizeof(unsigned);
   hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 3, WN>), dim3(nwg), dim3(BM * 2 * WN), lds, stream, g);
+}
+
+// U = A S with S^T [U | X] folded in (MODE 4): where launch_gemm_skip_zeros takes MODE 3 with a single column tile, a
+// workgroup ends its k-loop holding complete rows of U, and S_r^T [U_r | X_r] over those rows is one of tiles_m partial
+// slabs of the second product -- no launch of its own, no U in memory, nothing shared between workgroups.  The caller
+// has checked the shape (fold_tiles) and the slabs' alignment; this returns false, having launched nothing, when MODE 3
+// would not be taken.  g.rhs[0].C / rhs[1] / colsum as described at GemmArgs.
+constexpr int FOLD_BM = 128, FOLD_MAX_F = 64;
+static int fold_tiles(int64_t N, int64_t K, int64_t F) {  // row tiles per graph, 0 = the shape does not fold
+  return (K <= 128 && K % 4 == 0 && F <= FOLD_MAX_F && F % 4 == 0) ? cdiv(N, FOLD_BM) : 0;
+}
+template <bool A_KMAJOR>
+static bool launch_gemm_fold(GemmArgs g, int batches, hipStream_t stream) {
+  constexpr int BM = FOLD_BM, BN = 128, WN = 4;
+  const GemmRhs x = g.rhs[1];
+  g.rhs[1] = GemmRhs{};  // (gemm_aligned looks at the first right-hand side only: X is checked here)
+  const long lim = (1l << 31) - 4096;
+  if (!gemm_aligned(g, A_KMAJOR) || g.rhs[0].Nc > BN ||
+      (x.Bm && (reinterpret_cast<uintptr_t>(x.Bm) % 4 != 0 || x.Nc > FOLD_MAX_F || (static_cast<long>(g.Kd) + BM) * x.ldb * 4 >= lim)))
+    return false;
+  g.rhs[1] = x;
+  g.tiles_m = cdiv(g.M, BM);
+  g.tiles_n0 = g.tiles_n = 1;
+  g.tiles_n1 = 0;
+  g.splits = 1;
+  const int nwg = batches * g.tiles_m;
+  if (nwg < 256) return false;
+  // the tail's operands S_r [128][128] and [U_r | X_r] [128][192] (the k-loop's stages and the result tile lie inside)
+  constexpr size_t lds = (BM * BN + BM * 192) * sizeof(float);  // = 160 KB: the whole LDS of a CU
+  static_assert(BM * BN + BM * 192 >= BM * 196 + 8 * BN && BM * 196 + 8 * BN >= 2 * (BM * LDA_ROWMAJOR + BK * BN) + 2 * 16,
+                "MODE 4: the tail's operands cover its result tile, which covers the k-loop's stages");
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 4, WN>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 4, WN>), dim3(nwg), dim3(BM * 2 * WN), lds, stream, g);
+  return true;
 }
 
 // MODE 1 launch: sum((resid - A Bm^T)^2) per tile into g.partial; returns tiles per batch element.
