@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -1652,6 +1652,51 @@ int tgp_maxcut_cut_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL o
                        float* az /* NULL ok */, float* cut /* NULL ok */, float* wsum /* NULL ok */, void* stream);
 int tgp_maxcut_assign_round_i32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
                                 const int32_t* label_in, int64_t N, int64_t E, int32_t* label_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * EigenPooling (reference select/eigenpool_select.py, reduce/eigenpool_reduce.py, lift/eigenpool_lift.py),
+ * csrc/eigenpool.hip.  The reference's pooling matrix Theta [n, K H] has at most H non-zeros per row; it is kept as
+ * theta_modes [N, H] (node i's entry in mode h of its own cluster) plus the inverted index of the groups, a group being
+ * a (graph, cluster) pair: theta_ptr [G + 1] and theta_perm [N] of tgp_assign_index_build over gid [N] (ascending node
+ * index inside a group).
+ *   modes:   one workgroup per group.  The induced sub-adjacency is gathered from the by-source edge index (grp_ptr
+ *            [N + 1], grp_perm [E] or NULL for a list that is grouped already; duplicates are added in edge-list order
+ *            in fp32), the reference's Laplacian is formed in float64 (degrees = column sums; normalized: plus the
+ *            smallest positive fp32 subnormal, L = I - D^-1/2 A D^-1/2; otherwise D - A) and solved by a cyclic Jacobi
+ *            iteration with a fixed round-robin rotation order.  Eigenpairs ascending, ties to the lower column; mode
+ *            h of a group of m nodes is eigenvector min(h, m - 1), negated when its first entry (the group's lowest
+ *            node) is negative; a one-node group gets its self-loop weight in all H modes; an empty group writes
+ *            nothing.  embed != 0 (needs normalized): every row is scaled by deg^-1/2 (1 for a node without induced
+ *            edges), the spectral embedding of the labeller.  deg [N] (NULL ok): the column sums.  One rounding to
+ *            fp32 at the end.  A group whose Laplacian has a NaN or an infinite entry gets NaN in all its modes (eigh
+ *            refuses such a matrix); the other groups are not touched by it.
+ *            max_m in 1 .. tgp_eigenpool_max_group_nodes() sizes the LDS frame (an upper bound of the largest group).
+ *            *status (one zeroed device word) collects: bit 0 an index outside its table (a member that is not a node
+ *            of its group, an unsorted member list, an edge position or endpoint out of range), bit 1 a group whose
+ *            induced adjacency is not symmetric, bit 2 a group of more than max_m nodes.  A flagged group is left
+ *            unwritten; nothing out of range is dereferenced.
+ *   reduce:  out [G, H F]: out[g, h F + f] = sum over the group's nodes, ascending, of theta[i, h] x[i, f].  A row of x
+ *            is read once for (up to 8) modes; one lane adds every (group, mode, feature): no float atomics, the same
+ *            bits on every call.  max_len is an upper bound of the longest group (it only chooses the route, never the
+ *            result's validity; 0 = short groups): beyond 128 rows 4, beyond 1024 rows 16 waves share a group, each
+ *            adding one run of consecutive rows, the runs folded in ascending order.  An empty group gives a zero
+ *            row; a member outside [0, N) is skipped.
+ *   lift:    out [N, F]: out[i, f] = sum_h theta[i, h] x_pool[gid[i], h F + f]; a node whose gid is outside [0, G) gets
+ *            zeros.  reduce and lift are each other's adjoint.
+ * TGP_ERR_INVALID: a NULL input or output, an input given as the output, sizes below zero, H < 1, ldx < F, max_m
+ * outside its range; TGP_ERR_RANGE: N, E, G or F beyond the int32 index.  All are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_eigenpool_max_group_nodes(void);
+int tgp_eigenpool_modes_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                            const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* theta_ptr,
+                            const int32_t* theta_perm, int64_t N, int64_t E, int64_t G, int64_t H, int64_t max_m,
+                            int normalized, int embed, float* theta_modes, float* deg /* NULL ok */, int32_t* status,
+                            void* stream);
+int tgp_eigenpool_reduce_f32(const float* theta_modes, const int32_t* theta_ptr, const int32_t* theta_perm,
+                             const float* x, int64_t ldx, int64_t N, int64_t G, int64_t H, int64_t F, int64_t max_len,
+                             float* out, void* stream);
+int tgp_eigenpool_lift_f32(const float* theta_modes, const int32_t* gid, const float* x_pool, int64_t N, int64_t G,
+                           int64_t H, int64_t F, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -387,6 +387,12 @@ SIGNATURES = {
     "tgp_maxcut_wgrad_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
     "tgp_maxcut_cut_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
     "tgp_maxcut_assign_round_i32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_eigenpool_max_group_nodes": (_c_int, []),
+    "tgp_eigenpool_modes_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                         _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_eigenpool_reduce_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
+                                          _c_p]),
+    "tgp_eigenpool_lift_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

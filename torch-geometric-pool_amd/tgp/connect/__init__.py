@@ -528,4 +528,12 @@ class KronConnect(Connect):
         return f"{self.__class__.__name__}(sparse_threshold={self.sparse_threshold})"
 
 
-__all__ = ["Connect", "SparseConnect", "DenseConnect", "KronConnect", "sparse_connect"]
+__all__ = ["Connect", "SparseConnect", "DenseConnect", "KronConnect", "sparse_connect", "EigenPoolConnect"]
+
+
+def __getattr__(name):
+    # EigenPool's Connect lives next to its pooler (tgp/poolers/eigenpool.py), which imports this module
+    if name == "EigenPoolConnect":
+        from ..poolers import eigenpool
+        return eigenpool.EigenPoolConnect
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

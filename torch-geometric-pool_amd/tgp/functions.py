@@ -1770,3 +1770,49 @@ def maxcut_loss(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], ba
     if _needs_grad(s):
         return _MaxCutLossFn.apply(s, edge_index, edge_weight, batch, ptr, num_graphs, max_nodes)
     return _maxcut_loss_fwd(s, edge_index, edge_weight, ptr, num_graphs, max_nodes)[0]
+
+
+# ------------------------------------------------------------------------------------------------ EigenPooling
+class _EigenReduceFn(torch.autograd.Function):
+    """X_pool = Theta^T X over the compact pooling matrix; dX is the Lift kernel.  Theta carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, theta_modes, groups, gid, max_len):
+        ctx.save_for_backward(theta_modes, gid)
+        ctx.num_groups = groups.num_targets
+        return K.eigenpool_reduce(theta_modes, groups, x, max_len)
+
+    @staticmethod
+    def backward(ctx, g):
+        theta_modes, gid = ctx.saved_tensors
+        return K.eigenpool_lift(theta_modes, gid, g.contiguous(), ctx.num_groups), None, None, None, None
+
+
+class _EigenLiftFn(torch.autograd.Function):
+    """X_lift = Theta X_pool; dX_pool is the Reduce kernel.  Theta carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x_pool, theta_modes, groups, gid, max_len):
+        ctx.save_for_backward(theta_modes)
+        ctx.groups, ctx.max_len = groups, max_len
+        return K.eigenpool_lift(theta_modes, gid, x_pool, groups.num_targets)
+
+    @staticmethod
+    def backward(ctx, g):
+        (theta_modes,) = ctx.saved_tensors
+        return K.eigenpool_reduce(theta_modes, ctx.groups, g.contiguous(), ctx.max_len), None, None, None, None
+
+
+def eigenpool_reduce(x: Tensor, theta_modes: Tensor, groups, gid: Tensor, max_len: int = 0) -> Tensor:
+    """[G, H F] pooled features of device float32 ``x`` [N, F]; one autograd node whose backward is the Lift kernel.
+    ``max_len``: an upper bound of the longest group (``kernels.eigenpool_reduce``)."""
+    if _needs_grad(x):
+        return _EigenReduceFn.apply(x, theta_modes, groups, gid, max_len)
+    return K.eigenpool_reduce(theta_modes, groups, x, max_len)
+
+
+def eigenpool_lift(x_pool: Tensor, theta_modes: Tensor, groups, gid: Tensor, max_len: int = 0) -> Tensor:
+    """[N, F] lifted features of device float32 ``x_pool`` [G, H F]; one autograd node whose backward is the Reduce."""
+    if _needs_grad(x_pool):
+        return _EigenLiftFn.apply(x_pool, theta_modes, groups, gid, max_len)
+    return K.eigenpool_lift(theta_modes, gid, x_pool, groups.num_targets)

@@ -4577,3 +4577,82 @@ def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, round
                  N.stream_ptr(dev))
         cur, nxt = nxt, cur
     return cur
+
+
+# ------------------------------------------------------------------------------------------------ EigenPooling
+EIG_BAD_INPUT, EIG_ASYMMETRIC, EIG_OVER_LIMIT = 1, 2, 4  # status bits of tgp_eigenpool_modes_f32
+
+
+def eigenpool_max_group_nodes() -> int:
+    """Nodes of the largest (graph, cluster) group the modes kernel solves in LDS; one more takes the composed route."""
+    return int(N.lib().tgp_eigenpool_max_group_nodes())
+
+
+def eigenpool_modes(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor, groups: AssignIndex,
+                    num_modes: int, max_group: int, normalized: bool = True, embed: bool = False,
+                    want_degree: bool = False):
+    """theta_modes [N, H] float32 of the groups named by ``gid`` [N] int32 (``groups``: its inverted index), and the
+    kernel's status word as a host int (bits ``EIG_*``; a flagged group is left at zero) -- plus, with ``want_degree``,
+    the induced degrees [N].  ``max_group`` bounds the largest group the launch has to hold (at most
+    :func:`eigenpool_max_group_nodes`; larger groups are flagged, not solved)."""
+    dev = N.require_device(dst, edge_weight, gid, by_src.row_ptr, groups.row_ptr)
+    dst, n, E = _asap_group("eigenpool_modes", by_src, dst)
+    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
+        raise ValueError(f"eigenpool_modes: gid must be a contiguous int32 [{n}]")
+    if groups.nnz != n or (ew is not None and ew.numel() != E):
+        raise ValueError(f"eigenpool_modes: one group per node ({n}) and one weight per edge ({E})")
+    H = int(num_modes)
+    theta = torch.zeros(n, max(H, 1), dtype=torch.float32, device=dev)
+    deg = torch.zeros(n, dtype=torch.float32, device=dev) if want_degree else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _checked(N.lib().tgp_eigenpool_modes_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
+             N.ptr(ew), N.ptr(gid), N.ptr(groups.row_ptr), N.ptr(groups.perm), n, E, groups.num_targets, H,
+             int(max_group), 1 if normalized else 0, 1 if embed else 0, N.ptr(theta), N.ptr(deg), N.ptr(status),
+             N.stream_ptr(dev))
+    st = int(status.item())
+    if st & EIG_BAD_INPUT:
+        raise N.TgpNativeError("tgp_eigenpool_modes_f32: an index outside its table (an edge endpoint, an edge position "
+                               "or a label out of range); nothing out of range was read")
+    return (theta, st, deg) if want_degree else (theta, st)
+
+
+def _eigenpool_rows(name: str, t: Tensor) -> Tensor:
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"{name} expects float32 [rows, cols], got {t.dtype} {tuple(t.shape)}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def eigenpool_reduce(theta_modes: Tensor, groups: AssignIndex, x: Tensor, max_len: int = 0) -> Tensor:
+    """X_pool [G, H F]: ``X_pool[g, h F + f] = sum_{i in group g} theta_modes[i, h] x[i, f]``, nodes ascending, one pass
+    over x, the same bits on every call.  ``max_len``: an upper bound of the longest group (0: short groups); it picks
+    how many waves share a group, never the result's validity."""
+    dev = N.require_device(theta_modes, x, groups.row_ptr)
+    theta_modes, x = _eigenpool_rows("eigenpool_reduce", theta_modes), _eigenpool_rows("eigenpool_reduce", x)
+    n, H = theta_modes.shape
+    if x.size(0) != n or groups.nnz != n or H < 1:
+        raise ValueError(f"eigenpool_reduce: theta_modes {tuple(theta_modes.shape)}, x {tuple(x.shape)} and an index of "
+                         f"{groups.nnz} nodes do not go together")
+    F, G = x.size(1), groups.num_targets
+    out = torch.empty(G, H * F, dtype=torch.float32, device=dev)
+    if G and F:
+        _checked(N.lib().tgp_eigenpool_reduce_f32, N.ptr(theta_modes), N.ptr(groups.row_ptr), N.ptr(groups.perm), N.ptr(x),
+                 F, n, G, H, F, int(max_len), N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
+def eigenpool_lift(theta_modes: Tensor, gid: Tensor, x_pool: Tensor, num_groups: int) -> Tensor:
+    """X_lift [N, F]: ``X_lift[i, f] = sum_h theta_modes[i, h] x_pool[gid[i], h F + f]`` (the adjoint of the Reduce)."""
+    dev = N.require_device(theta_modes, gid, x_pool)
+    theta_modes, x_pool = _eigenpool_rows("eigenpool_lift", theta_modes), _eigenpool_rows("eigenpool_lift", x_pool)
+    n, H = theta_modes.shape
+    if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
+        raise ValueError(f"eigenpool_lift: gid must be a contiguous int32 [{n}]")
+    if H < 1 or x_pool.size(0) != num_groups or x_pool.size(1) % H:
+        raise ValueError(f"eigenpool_lift: x_pool {tuple(x_pool.shape)} is not [{num_groups}, {H} F]")
+    F = x_pool.size(1) // H
+    out = torch.empty(n, F, dtype=torch.float32, device=dev)
+    if n and F:
+        _checked(N.lib().tgp_eigenpool_lift_f32, N.ptr(theta_modes), N.ptr(gid), N.ptr(x_pool), n, num_groups, H, F,
+                 N.ptr(out), N.stream_ptr(dev))
+    return out

@@ -136,4 +136,12 @@ class BaseLift(Lift):
         return f"{self.__class__.__name__}(matrix_op={self.matrix_op}, reduce_op={self.reduce_op})"
 
 
-__all__ = ["Lift", "BaseLift"]
+__all__ = ["Lift", "BaseLift", "EigenPoolLift"]
+
+
+def __getattr__(name):
+    # EigenPool's Lift lives next to its pooler (tgp/poolers/eigenpool.py), which imports this module
+    if name == "EigenPoolLift":
+        from ..poolers import eigenpool
+        return eigenpool.EigenPoolLift
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

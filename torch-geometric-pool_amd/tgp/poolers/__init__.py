@@ -5,9 +5,9 @@
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
 ``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling``, ``SAGPooling``, ``ASAPooling``
-(``tgp/poolers/asap.py``) and ``MaxCutPooling`` (``tgp/poolers/maxcut.py``) are built and exported as classes; their
-``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` / ``asap`` / ``maxcut`` aliases are
-not registered yet.
+(``tgp/poolers/asap.py``), ``MaxCutPooling`` (``tgp/poolers/maxcut.py``) and ``EigenPooling`` (``tgp/poolers/eigenpool.py``)
+are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` /
+``sag`` / ``asap`` / ``maxcut`` / ``eigen`` aliases are not registered yet.
 """
 from __future__ import annotations
 
@@ -68,6 +68,7 @@ from ..utils.ops import connectivity_to_edge_index, postprocess_adj_pool_dense
 from ..functions import LossPair
 from .asap import ASAPooling
 from .maxcut import MaxCutPooling, MaxCutScoreNet, MaxCutSelect
+from .eigenpool import EigenPoolConnect, EigenPoolLift, EigenPoolReduce, EigenPoolSelect, EigenPooling
 
 import os as _os
 
@@ -1573,8 +1574,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling) and "maxcut" (MaxCutPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling) and "eigen" (EigenPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,
@@ -1616,4 +1617,6 @@ def get_pooler(pooler_name: str, **kwargs):
     return cls(**init_kwargs)
 
 
-__all__ = ["get_pooler", "pooler_map", "pooler_classes"] + pooler_classes + ["MaxCutSelect", "MaxCutScoreNet"]
+__all__ = ["get_pooler", "pooler_map", "pooler_classes"] + pooler_classes + ["MaxCutSelect", "MaxCutScoreNet", "EigenPoolSelect",
+                                                                          "EigenPoolReduce", "EigenPoolConnect",
+                                                                          "EigenPoolLift"]

@@ -10,4 +10,12 @@ from .get_aggr import get_aggr, resolve_reduce_op
 from .global_reduce import GlobalReduce
 
 __all__ = ["Reduce", "BaseReduce", "AggrReduce", "GlobalReduce", "get_aggr", "resolve_reduce_op", "Aggregation",
-           "SumAggregation", "MeanAggregation", "MaxAggregation", "MinAggregation", "MultiAggregation"]
+           "SumAggregation", "MeanAggregation", "MaxAggregation", "MinAggregation", "MultiAggregation", "EigenPoolReduce"]
+
+
+def __getattr__(name):
+    # EigenPool's Reduce lives next to its pooler (tgp/poolers/eigenpool.py), which imports this package
+    if name == "EigenPoolReduce":
+        from ..poolers import eigenpool
+        return eigenpool.EigenPoolReduce
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

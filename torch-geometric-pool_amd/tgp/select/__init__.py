@@ -275,7 +275,8 @@ class SelectOutput:
         factory = state.pop("_L_factory", None)  # a closure over device tensors: the pickle carries the Laplacian itself
         if factory is not None and "L" not in state:
             state["L"] = factory()
-        for helper in ("_adj_device_csr", "_kron_csr", "_node_batch", "_partition_info", "_values_of", "_node_rank"):
+        for helper in ("_adj_device_csr", "_kron_csr", "_node_batch", "_partition_info", "_values_of", "_node_rank",
+                       "_eig_cache"):
             state.pop(helper, None)  # device-side shortcuts of this process; KronConnect rebuilds what it needs from L
         return state
 
@@ -1610,7 +1611,8 @@ class NDPSelect(Select):
 __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "GraclusSelect", "NDPSelect", "cluster_to_s",
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
            "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster", "LaPoolSelect",
-           "degree_scorer", "MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling"]
+           "degree_scorer", "MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling", "EigenPoolSelect", "eigenpool_select",
+           "eigenpool_theta"]
 
 
 def __getattr__(name):
@@ -1618,4 +1620,8 @@ def __getattr__(name):
     if name in ("MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling"):
         from ..poolers import maxcut
         return getattr(maxcut, name)
+    # EigenPool's operators live next to their pooler too (tgp/poolers/eigenpool.py)
+    if name in ("EigenPoolSelect", "eigenpool_select", "eigenpool_theta"):
+        from ..poolers import eigenpool
+        return getattr(eigenpool, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
