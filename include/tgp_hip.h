@@ -1698,6 +1698,50 @@ int tgp_eigenpool_reduce_f32(const float* theta_modes, const int32_t* theta_ptr,
 int tgp_eigenpool_lift_f32(const float* theta_modes, const int32_t* gid, const float* x_pool, int64_t N, int64_t G,
                            int64_t H, int64_t F, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * NMF pooling (reference select/nmf_select.py), csrc/nmf.hip: A ~ W H per graph by scikit-learn's coordinate descent
+ * (solver "cd", shuffle off, no regularisation), S = softmax(H^T).  One workgroup per graph; the graph's nodes come from
+ * the inverted index of gid [N] (graph_ptr [G + 1], graph_perm [N] of tgp_assign_index_build: ascending node index inside
+ * a graph, which is the node's LOCAL index), its edges from the by-source edge index (grp_ptr [N + 1], grp_perm [E] or
+ * NULL for a list that is grouped already).  Duplicate edges are added in edge-list order in fp32, the sum is clamped at
+ * 0.  With n nodes and ka = max(1, min(K, n)):  n > 1 and ka >= n gives the identity, ka == 1 a column of ones, both
+ * without a factorisation; otherwise W [n, ka] and H^T [n, ka] start from the explicit init (w0, h0t [N, K] node-major,
+ * columns >= ka ignored, both or neither) or from the default one, avg * 2u with avg = sqrt(mean(A) / ka) and u in (0, 1]
+ * a 32-bit hash of (seed, factor, local node index, component), and iteration it = 1 .. max_iter updates W, then H:
+ *     Gram = F^T F, P = A F (A^T F for H), F the other factor; per row i, t = 0 .. ka - 1 in order:
+ *     grad = -P[i,t] + sum_r Gram[t,r] U[i,r];  violation += |U[i,t] == 0 ? min(0, grad) : grad|;
+ *     if Gram[t,t] != 0: U[i,t] = max(U[i,t] - grad / Gram[t,t], 0)
+ * and stops when the first iteration's violation is 0 or violation / first violation <= tol (a NaN ratio runs to
+ * max_iter).  All sums are fp32 in ascending index order (the row violations: lane l of one wave adds rows l, l + 64, then
+ * an xor butterfly); no fused multiply-add, no float atomics: the same bits on every call.
+ *   factorize: s [N, out_cols] gets softmax over the ka columns and zeros behind them (out_cols >= ka of every graph).
+ *              Optional (NULL ok): w_out, ht_out [N, K] the raw factors (zeros behind column ka; not written for a
+ *              graph that is not factorised), iters [G] the iteration at which a factorised graph stopped,
+ *              violation_ratio [G] its last ratio (0 when the first violation is 0).
+ *   init:      w0, h0t [N, K] of the default init alone (rows of graphs that are not factorised are not written).
+ * max_n in 1 .. tgp_nmf_max_nodes() sizes the LDS frame (an upper bound of the largest graph).  *status (one zeroed
+ * device word) collects: bit 0 an index outside its table (a member that is not a node of its graph, an unsorted member
+ * list, an edge position or endpoint out of range, an edge whose endpoints lie in two graphs, out_cols < ka), bit 1 a NaN
+ * or infinite entry of a factorised graph's clamped adjacency, bit 2 a graph of more than max_n nodes or K >
+ * tgp_nmf_max_k().  A flagged graph is left unwritten; nothing out of range is dereferenced.
+ * TGP_ERR_INVALID: a NULL input or output, sizes below zero, K < 1, out_cols < 1, max_iter < 1, tol < 0 or NaN, max_n
+ * outside its range, one of w0 / h0t without the other; TGP_ERR_RANGE: a size beyond the int32 index.  All are found
+ * before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_nmf_max_nodes(void);
+int tgp_nmf_max_k(void);
+int tgp_nmf_init_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                     const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* graph_ptr,
+                     const int32_t* graph_perm, int64_t N, int64_t E, int64_t G, int64_t K, int64_t max_n, int64_t seed,
+                     float* w0, float* h0t, int32_t* status, void* stream);
+int tgp_nmf_factorize_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                          const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* graph_ptr,
+                          const int32_t* graph_perm, int64_t N, int64_t E, int64_t G, int64_t K, int64_t out_cols,
+                          int64_t max_n, int64_t seed, float tol, int64_t max_iter, const float* w0 /* NULL ok */,
+                          const float* h0t /* NULL ok */, float* s, float* w_out /* NULL ok */,
+                          float* ht_out /* NULL ok */, int32_t* iters /* NULL ok */, float* violation_ratio /* NULL ok */,
+                          int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

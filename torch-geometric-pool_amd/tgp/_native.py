@@ -393,6 +393,13 @@ SIGNATURES = {
     "tgp_eigenpool_reduce_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
                                           _c_p]),
     "tgp_eigenpool_lift_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
+    "tgp_nmf_max_nodes": (_c_int, []),
+    "tgp_nmf_max_k": (_c_int, []),
+    "tgp_nmf_init_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                  _c_p, _c_p, _c_p, _c_p]),
+    "tgp_nmf_factorize_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                       _c_i64, _c_i64, _c_f, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                       _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -4656,3 +4656,72 @@ def eigenpool_lift(theta_modes: Tensor, gid: Tensor, x_pool: Tensor, num_groups:
         _checked(N.lib().tgp_eigenpool_lift_f32, N.ptr(theta_modes), N.ptr(gid), N.ptr(x_pool), n, num_groups, H, F,
                  N.ptr(out), N.stream_ptr(dev))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ NMF pooling
+NMF_BAD_INPUT, NMF_NON_FINITE, NMF_OVER_LIMIT = 1, 2, 4  # status bits of tgp_nmf_factorize_f32 / tgp_nmf_init_f32
+
+
+def nmf_max_nodes() -> int:
+    """Nodes of the largest graph the NMF kernel factorises in LDS; one more takes the composed route."""
+    return int(N.lib().tgp_nmf_max_nodes())
+
+
+def nmf_max_k() -> int:
+    """The largest ``K`` the NMF kernel's LDS frame holds."""
+    return int(N.lib().tgp_nmf_max_k())
+
+
+def _nmf_args(name: str, by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor,
+              graphs: AssignIndex):
+    dst, n, E = _asap_group(name, by_src, dst)
+    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
+        raise ValueError(f"{name}: gid must be a contiguous int32 [{n}]")
+    if graphs.nnz != n or (ew is not None and ew.numel() != E):
+        raise ValueError(f"{name}: one graph per node ({n}) and one weight per edge ({E})")
+    return dst, ew, n, E
+
+
+def nmf_init(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor, graphs: AssignIndex, k: int,
+             max_n: int, seed: int = 0):
+    """(W0 [N, K], H0^T [N, K], status): the default init of the NMF kernel alone (zeros for the graphs that are not
+    factorised, and for a flagged graph)."""
+    dev = N.require_device(dst, edge_weight, gid, by_src.row_ptr, graphs.row_ptr)
+    dst, ew, n, E = _nmf_args("nmf_init", by_src, dst, edge_weight, gid, graphs)
+    w0 = torch.zeros(2, n, max(int(k), 1), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _checked(N.lib().tgp_nmf_init_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None, N.ptr(ew),
+             N.ptr(gid), N.ptr(graphs.row_ptr), N.ptr(graphs.perm), n, E, graphs.num_targets, int(k), int(max_n),
+             int(seed), N.ptr(w0[0]), N.ptr(w0[1]), N.ptr(status), N.stream_ptr(dev))
+    return w0[0], w0[1], int(status.item())
+
+
+def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor, graphs: AssignIndex,
+                  k: int, out_cols: int, max_n: int, seed: int = 0, tol: float = 1e-4, max_iter: int = 5000,
+                  init: Optional[Tuple[Tensor, Tensor]] = None, want_factors: bool = False) -> dict:
+    """One launch of the per-graph NMF kernel: ``s`` [N, out_cols] (softmax of H^T, zero columns behind ``ka``; zeros for
+    a flagged graph), ``status`` (a host int, bits ``NMF_*``: the call's one host wait), ``iters`` [G] int32 and
+    ``ratio`` [G], and with ``want_factors`` the raw ``w`` / ``ht`` [N, K].  ``init``: (W0, H0^T) [N, K] node-major."""
+    dev = N.require_device(dst, edge_weight, gid, by_src.row_ptr, graphs.row_ptr)
+    dst, ew, n, E = _nmf_args("nmf_factorize", by_src, dst, edge_weight, gid, graphs)
+    Kc, G = int(k), graphs.num_targets
+    w0 = h0t = None
+    if init is not None:
+        w0, h0t = N.f32c(init[0]), N.f32c(init[1])
+        if tuple(w0.shape) != (n, Kc) or tuple(h0t.shape) != (n, Kc):
+            raise ValueError(f"nmf_factorize: an explicit init is (W0, H0^T), both [{n}, {Kc}]")
+    s = torch.zeros(n, int(out_cols), dtype=torch.float32, device=dev)
+    fac = torch.zeros(2, n, max(Kc, 1), dtype=torch.float32, device=dev) if want_factors else None
+    iters = torch.zeros(G, dtype=torch.int32, device=dev)
+    ratio = torch.zeros(G, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _checked(N.lib().tgp_nmf_factorize_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
+             N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr), N.ptr(graphs.perm), n, E, G, Kc, int(out_cols), int(max_n),
+             int(seed), float(tol), int(max_iter), N.ptr(w0), N.ptr(h0t), N.ptr(s),
+             N.ptr(fac[0]) if want_factors else None, N.ptr(fac[1]) if want_factors else None, N.ptr(iters),
+             N.ptr(ratio), N.ptr(status), N.stream_ptr(dev))
+    out = {"s": s, "status": int(status.item()), "iters": iters, "ratio": ratio}
+    if want_factors:
+        out["w"], out["ht"] = fac[0], fac[1]
+    return out

@@ -5,9 +5,10 @@
 ``mincut`` (+ ``diff_u`` / ``mincut_u``).  Every other alias of the reference raises the same
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
 ``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling``, ``SAGPooling``, ``ASAPooling``
-(``tgp/poolers/asap.py``), ``MaxCutPooling`` (``tgp/poolers/maxcut.py``) and ``EigenPooling`` (``tgp/poolers/eigenpool.py``)
-are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` /
-``sag`` / ``asap`` / ``maxcut`` / ``eigen`` aliases are not registered yet.
+(``tgp/poolers/asap.py``), ``MaxCutPooling`` (``tgp/poolers/maxcut.py``), ``EigenPooling`` (``tgp/poolers/eigenpool.py``)
+and ``NMFPooling`` (``tgp/poolers/nmf.py``) are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` /
+``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` / ``asap`` / ``maxcut`` / ``eigen`` / ``nmf`` aliases are not
+registered yet.
 """
 from __future__ import annotations
 
@@ -69,6 +70,7 @@ from ..functions import LossPair
 from .asap import ASAPooling
 from .maxcut import MaxCutPooling, MaxCutScoreNet, MaxCutSelect
 from .eigenpool import EigenPoolConnect, EigenPoolLift, EigenPoolReduce, EigenPoolSelect, EigenPooling
+from .nmf import NMFPooling, NMFSelect
 
 import os as _os
 
@@ -1574,8 +1576,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling) and "eigen" (EigenPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling), "eigen" (EigenPooling) and "nmf" (NMFPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "NMFPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,
@@ -1619,4 +1621,4 @@ def get_pooler(pooler_name: str, **kwargs):
 
 __all__ = ["get_pooler", "pooler_map", "pooler_classes"] + pooler_classes + ["MaxCutSelect", "MaxCutScoreNet", "EigenPoolSelect",
                                                                           "EigenPoolReduce", "EigenPoolConnect",
-                                                                          "EigenPoolLift"]
+                                                                          "EigenPoolLift", "NMFSelect"]

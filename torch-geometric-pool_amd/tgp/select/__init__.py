@@ -1612,7 +1612,7 @@ __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "Gra
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
            "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster", "LaPoolSelect",
            "degree_scorer", "MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling", "EigenPoolSelect", "eigenpool_select",
-           "eigenpool_theta"]
+           "eigenpool_theta", "NMFSelect", "nmf_select"]
 
 
 def __getattr__(name):
@@ -1624,4 +1624,8 @@ def __getattr__(name):
     if name in ("EigenPoolSelect", "eigenpool_select", "eigenpool_theta"):
         from ..poolers import eigenpool
         return getattr(eigenpool, name)
+    # and so does NMF pooling's selector (tgp/poolers/nmf.py)
+    if name in ("NMFSelect", "nmf_select"):
+        from ..poolers import nmf
+        return getattr(nmf, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
