@@ -431,6 +431,13 @@ def check(status: int, what: str) -> None:
         raise TgpNativeError(f"{what} failed with status {status}: {msg}")
 
 
+def checked(fn, *args) -> None:
+    """Call a C-ABI entry point; a non-zero status is reported under the symbol that was called."""
+    status = fn(*args)
+    if status != 0:
+        check(status, fn.__name__)
+
+
 def require_device(*tensors: Optional[Tensor]) -> torch.device:
     """All given tensors must live on one ROCm device; returns it."""
     dev = None
@@ -490,3 +497,17 @@ def i64c(t: Tensor) -> Tensor:
     if t.dtype != torch.int64:
         t = t.to(torch.int64)
     return t if t.is_contiguous() else t.contiguous()
+
+
+# optional operands: None stays None (the kernel is handed a null pointer), a tensor goes through f32c / i64c
+def opt_f32(t: Optional[Tensor]) -> Optional[Tensor]:
+    return None if t is None else f32c(t)
+
+
+def opt_f32_flat(t: Optional[Tensor]) -> Optional[Tensor]:
+    """:func:`opt_f32` of the operand as one vector (edge weights, scores, biases: [n] or [n, 1])."""
+    return None if t is None else f32c(t.reshape(-1))
+
+
+def opt_i64(t: Optional[Tensor]) -> Optional[Tensor]:
+    return None if t is None else i64c(t)

@@ -382,8 +382,7 @@ class SparseGather:
             q = 7 * j
             dims[q], dims[q + 1], dims[q + 2], dims[q + 3] = (x2.stride(0) if K else F) * xw, K, E, inputs[4]
             dims[q + 4], dims[q + 5], dims[q + 6] = F * xw, ww, xw
-        N.check(N.lib().tgp_gather_pack_bucket_f32(ptrs, dims, n, cap, send.data_ptr(), N.stream_ptr(dev)),
-                "tgp_gather_pack_bucket_f32")
+        N.checked(N.lib().tgp_gather_pack_bucket_f32, ptrs, dims, n, cap, send.data_ptr(), N.stream_ptr(dev))
         return send
 
     @staticmethod
@@ -484,8 +483,7 @@ class SparseGather:
             dims[o], dims[o + 1], dims[o + 2], dims[o + 3], dims[o + 4], dims[o + 5] = k_cap, e_cap, tag, F * xw, ww, xw
             steps.append((slot, tag, out, plan[j]))
         # ONE launch for the whole bucket (grid z = step)
-        N.check(L.tgp_gather_unpack_bucket_f32(gbase, cap, n * cap, self.world, max_words, n, ptrs, dims, st),
-                "tgp_gather_unpack_bucket_f32")
+        N.checked(L.tgp_gather_unpack_bucket_f32, gbase, cap, n * cap, self.world, max_words, n, ptrs, dims, st)
         bucket["steps"] = steps
 
     def _poll(self, slot: int, tag: int, block: bool) -> bool:
@@ -562,7 +560,7 @@ class SparseGather:
                 src[n], dst[n], nbytes[n] = t.data_ptr(), new.data_ptr(), t.numel() * es
                 n += 1
             out[i] = new
-        N.check(N.lib().tgp_copy_arrays(src, dst, nbytes, n, N.stream_ptr(first.device)), "tgp_copy_arrays")
+        N.checked(N.lib().tgp_copy_arrays, src, dst, nbytes, n, N.stream_ptr(first.device))
         return out
 
     def _finalise_oldest(self, block: bool, allow_redo: bool = False) -> bool:

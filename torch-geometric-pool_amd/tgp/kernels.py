@@ -6,7 +6,9 @@ on the CPU and nothing falls back to ATen kernels.
 """
 from __future__ import annotations
 
+import ctypes
 import os
+import threading
 from types import SimpleNamespace
 from typing import Optional, Sequence, Tuple
 from weakref import ref as _weakref
@@ -88,6 +90,12 @@ class AssignIndex:
             self._row_ptr = torch.arange(self.num_targets + 1, dtype=torch.int32, device=self._device)
         return self._row_ptr
 
+    def walk(self, other: Optional[Tensor], E: int):
+        """The three pointers a kernel that walks the groups of an edge index is handed: the offsets, the positions
+        (None: the identity) and ``other``, the edge row at the far end of every position (no pointer for an empty
+        list)."""
+        return N.ptr(self.row_ptr), N.ptr(self.perm), N.ptr(other) if E else None
+
 
 def build_assign_index(target_index: Tensor, num_targets: int) -> AssignIndex:
     dev = N.require_device(target_index)
@@ -98,8 +106,8 @@ def build_assign_index(target_index: Tensor, num_targets: int) -> AssignIndex:
     L = N.lib()
     wsb = L.tgp_assign_index_workspace_bytes(nnz, num_targets)
     ws = N.workspace(wsb, dev)
-    N.check(L.tgp_assign_index_build(N.ptr(target_index), nnz, num_targets, N.ptr(row_ptr), N.ptr(perm),
-                                     N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "tgp_assign_index_build")
+    _checked(L.tgp_assign_index_build, N.ptr(target_index), nnz, num_targets, N.ptr(row_ptr), N.ptr(perm), N.ptr(ws),
+             ws.numel(), N.stream_ptr(dev))
     return AssignIndex(row_ptr, perm, nnz, num_targets)
 
 
@@ -121,31 +129,27 @@ def reduce_sparse(x: Tensor, source_index: Tensor, weight: Optional[Tensor], ind
         src64 = N.i64c(source_index)
         w64 = None if weight is None else N.f64c(weight.reshape(-1))
         out = torch.empty(index.num_targets, x2.size(1), dtype=torch.float64, device=dev)
-        N.check(N.lib().tgp_reduce_sparse_f64(N.ptr(x2), x2.size(0), x2.size(1), x2.stride(0), N.ptr(src64), N.ptr(w64),
-                                              N.ptr(index._row_ptr), N.ptr(index.perm), index.nnz, index.num_targets,
-                                              N.ptr(out), N.stream_ptr(dev)), "tgp_reduce_sparse_f64")
+        _checked(N.lib().tgp_reduce_sparse_f64, N.ptr(x2), x2.size(0), x2.size(1), x2.stride(0), N.ptr(src64),
+                 N.ptr(w64), N.ptr(index._row_ptr), N.ptr(index.perm), index.nnz, index.num_targets, N.ptr(out),
+                 N.stream_ptr(dev))
         return out.view(-1) if squeeze else out
     x2 = x2.to(torch.float32) if x2.dtype != torch.float32 else x2
     if x2.stride(1) != 1:
         x2 = x2.contiguous()
     source_index = N.i64c(source_index)
-    w = None if weight is None else N.f32c(weight.reshape(-1))
+    w = N.opt_f32_flat(weight)
     F = x2.size(1)
     out = torch.empty(index.num_targets, F, dtype=torch.float32, device=dev)
     if (index.pack is not None and index.pack_key == (source_index.data_ptr(), 0 if w is None else w.data_ptr())
             and F % 4 == 0 and F >= 32 and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0):
         # one node per target (TopK, NDP): the packed index, one streamed 8-byte load per pooled row
-        N.check(N.lib().tgp_reduce_one_to_one_f32(N.ptr(x2), x2.size(0), F, x2.stride(0), N.ptr(index.pack),
-                                                  0 if w is None else 1, index.num_targets, N.ptr(out),
-                                                  N.stream_ptr(dev)), "tgp_reduce_one_to_one_f32")
+        _checked(N.lib().tgp_reduce_one_to_one_f32, N.ptr(x2), x2.size(0), F, x2.stride(0), N.ptr(index.pack),
+                 0 if w is None else 1, index.num_targets, N.ptr(out), N.stream_ptr(dev))
         return out.view(-1) if squeeze else out
     fast = index._row_ptr is not None and index.nnz <= x2.size(0)
-    N.check(N.lib().tgp_reduce_sparse_f32(N.ptr(x2), x2.size(0), F, x2.stride(0),
-                                          None if (identity_source and fast) else N.ptr(source_index),
-                                          None if unit_weight else N.ptr(w),
-                                          N.ptr(index._row_ptr), N.ptr(index.perm), index.nnz,
-                                          index.num_targets, N.ptr(out), N.stream_ptr(dev)),
-            "tgp_reduce_sparse_f32")
+    _checked(N.lib().tgp_reduce_sparse_f32, N.ptr(x2), x2.size(0), F, x2.stride(0),
+             None if (identity_source and fast) else N.ptr(source_index), None if unit_weight else N.ptr(w),
+             N.ptr(index._row_ptr), N.ptr(index.perm), index.nnz, index.num_targets, N.ptr(out), N.stream_ptr(dev))
     return out.view(-1) if squeeze else out
 
 
@@ -155,12 +159,12 @@ def one_to_one_index(node_index: Tensor, cluster_index: Tensor, weight: Optional
     streams -- one launch, no sort (select/base_select.py:58 keeps the assignment node-sorted)."""
     dev = N.require_device(node_index, cluster_index, weight)
     ni, ci = N.i64c(node_index), N.i64c(cluster_index)
-    w = None if weight is None else N.f32c(weight.reshape(-1))
+    w = N.opt_f32_flat(weight)
     k = ci.numel()
     perm = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
     pack = torch.empty(max(k, 1), dtype=torch.int64, device=dev)
-    N.check(N.lib().tgp_one_to_one_index_build(N.ptr(ni), N.ptr(ci), N.ptr(w), k, N.ptr(perm), N.ptr(pack),
-                                               N.stream_ptr(dev)), "tgp_one_to_one_index_build")
+    _checked(N.lib().tgp_one_to_one_index_build, N.ptr(ni), N.ptr(ci), N.ptr(w), k, N.ptr(perm), N.ptr(pack),
+             N.stream_ptr(dev))
     index = AssignIndex(None, perm, k, k)
     index.pack, index.pack_key = pack, (ni.data_ptr(), 0 if w is None else w.data_ptr())
     return index
@@ -173,10 +177,8 @@ def reduce_batch_sparse(batch: Tensor, node_index: Tensor, cluster_index: Tensor
     dev = N.require_device(batch, node_index, cluster_index)
     batch, node_index, cluster_index = N.i64c(batch), N.i64c(node_index), N.i64c(cluster_index)
     out = torch.empty(num_supernodes, dtype=torch.int64, device=dev)
-    N.check(N.lib().tgp_reduce_batch_i64(N.ptr(batch), N.ptr(node_index), N.ptr(cluster_index),
-                                         node_index.numel(), num_supernodes, 1 if every_cluster_has_a_node else 0,
-                                         N.ptr(out), N.stream_ptr(dev)),
-            "tgp_reduce_batch_i64")
+    _checked(N.lib().tgp_reduce_batch_i64, N.ptr(batch), N.ptr(node_index), N.ptr(cluster_index), node_index.numel(),
+             num_supernodes, 1 if every_cluster_has_a_node else 0, N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -190,6 +192,23 @@ def _edge_rows(edge_index: Tensor) -> Tuple[Tensor, Tensor]:
     if not (ei.dim() == 2 and ei.size(0) == 2 and (ei.stride(1) == 1 or ei.size(1) <= 1)):
         ei = ei.contiguous()
     return ei[0], ei[1]
+
+
+def _row_operand(x: Tensor, who: str, convert: bool = False, packed: bool = False) -> Tuple[Tensor, int]:
+    """THE row operand of the wrappers: ``(x, ld)`` = ``x`` as float32 [rows, F] with unit column stride, and the row
+    stride its kernel is handed.  Another dtype is converted (``convert``) or refused under the caller's name ``who``.
+    A view keeps its row stride -- a column slice of a wider buffer is read where it lies -- and is copied only when its
+    columns are strided or its rows overlap; ``packed`` (a kernel that takes no row stride): whenever it is not
+    contiguous."""
+    if x.dim() != 2 or (x.dtype != torch.float32 and not convert):
+        raise ValueError(f"{who} expects {'' if convert else 'float32 '}x of shape [rows, F], got {x.dtype} "
+                         f"{tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    rows, F = x.shape
+    if (not x.is_contiguous()) if packed else ((F > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < F)):
+        x = x.contiguous()
+    return x, (x.stride(0) if rows > 1 else max(x.stride(0), F))
 
 
 # ------------------------------------------------------------------------- A1 + A2 + A4/A5 + A6, batches of small graphs
@@ -213,7 +232,7 @@ SPS_COMPACT_BYTES = 1 << 30  # capacity buffers above this are replaced by exact
 # r4 behaviour, ``edge_index`` a [2, E'] VIEW of the capacity buffer (row stride E, E-sized storage kept alive; no copy)
 # for callers that consume the pooled graph at once, e.g. straight into SparseGather or the next pooling level.
 _OUTPUT_VIEWS_DEFAULT = os.environ.get("TGP_OUTPUT_VIEWS", "0") == "1"
-_OUTPUT_VIEWS_LOCAL = __import__("threading").local()  # per thread: a `with output_views()` in one thread must not
+_OUTPUT_VIEWS_LOCAL = threading.local()  # per thread: a `with output_views()` in one thread must not
 #                                                        change the layout other threads (autograd workers) hand out
 
 
@@ -252,8 +271,8 @@ def _compact_edges(L, st, dev, row_p: int, col_p: int, w_p, w_dtype, id_p, n_out
     out_id = None if id_p is None else torch.empty(n_out, dtype=torch.int64, device=dev)
     if n_out:
         o = out_ei.data_ptr()
-        N.check(L.tgp_edges_compact(row_p, col_p, w_p, 0 if w_p is None else out_w.element_size(), id_p, n_out,
-                                    o, o + 8 * n_out, N.ptr(out_w), N.ptr(out_id), st), "tgp_edges_compact")
+        _checked(L.tgp_edges_compact, row_p, col_p, w_p, 0 if w_p is None else out_w.element_size(), id_p, n_out, o,
+                 o + 8 * n_out, N.ptr(out_w), N.ptr(out_id), st)
     return out_ei, out_w, out_id
 
 
@@ -404,9 +423,8 @@ def graph_edge_ptr(edge_index: Tensor, graph_ptr: Tensor) -> Tensor:
     gp = N.i64c(graph_ptr)
     out = torch.empty(gp.numel(), dtype=torch.int64, device=dev)
     row = edge_index[0]
-    N.check(N.lib().tgp_graph_lower_bounds_i64(N.ptr(row) if row.numel() else None, row.numel(), N.ptr(gp),
-                                               gp.numel() - 1, N.ptr(out), N.stream_ptr(dev)),
-            "tgp_graph_lower_bounds_i64")
+    _checked(N.lib().tgp_graph_lower_bounds_i64, N.ptr(row) if row.numel() else None, row.numel(), N.ptr(gp),
+             gp.numel() - 1, N.ptr(out), N.stream_ptr(dev))
     _EDGE_RANGES.put(edge_index, out, graph_ptr)
     return out
 
@@ -525,13 +543,10 @@ def sparse_pool_small(x: Tensor, graph_ptr: Tensor, edge_index: Tensor, edge_wei
         else:
             eptr = None  # (mode 0 needs both tables)
     pinned_p = state.pinned.data_ptr()
-    N.check(L.tgp_sparse_pool_small_f32(x.data_ptr(), n, F, x.stride(0), gp.data_ptr(), B, N.ptr(eptr), N.ptr(aptr),
-                                        N.ptr(eptr_out), row_p if E else None,
-                                        col_p if E else None, N.ptr(w), E, ni_p, ci_p, N.ptr(wt),
-                                        nnz, K, mode, N.REDUCE_OPS[reduce_op], flags, ops_eps(),
-                                        xp_p, bp_p, cap_p, col_out, cw_p,
-                                        state.status.data_ptr(), state.status.numel(), pinned_p, epoch,
-                                        st), "tgp_sparse_pool_small_f32")
+    _checked(L.tgp_sparse_pool_small_f32, x.data_ptr(), n, F, x.stride(0), gp.data_ptr(), B, N.ptr(eptr), N.ptr(aptr),
+             N.ptr(eptr_out), row_p if E else None, col_p if E else None, N.ptr(w), E, ni_p, ci_p, N.ptr(wt), nnz, K,
+             mode, N.REDUCE_OPS[reduce_op], flags, ops_eps(), xp_p, bp_p, cap_p, col_out, cw_p, state.status.data_ptr(),
+             state.status.numel(), pinned_p, epoch, st)
     if one or arena:  # (behind the launch: the kernel is running)
         f32 = buf.view(torch.float32)
         x_pool = torch.as_strided(f32, (K, F), (F, 1), 0)
@@ -540,7 +555,7 @@ def sparse_pool_small(x: Tensor, graph_ptr: Tensor, edge_index: Tensor, edge_wei
         _EDGE_RANGES.put(edge_index, eptr_out, graph_ptr)
     if arena:
         # the call's one host wait (the reference's .item() syncs) and the column move, in one native call (r6)
-        N.check(L.tgp_result_wait_pack_cols(pinned_p, epoch, col_out, cap_p, st), "tgp_result_wait_pack_cols")
+        _checked(L.tgp_result_wait_pack_cols, pinned_p, epoch, col_out, cap_p, st)
         total = int(state.host[0])
         if (total >> 34) != epoch:
             raise N.TgpNativeError("tgp_result_wait_pack_cols returned before the result word of its call was stored")
@@ -585,7 +600,7 @@ def _read_count(d_count: Tensor) -> int:
         dev = d_count.device
         st = N.stream_ptr(dev)
         call = _sps_state(dev, st, 0).open_call()
-        N.check(N.lib().tgp_count_publish(N.ptr(d_count), *call.publish, st), "tgp_count_publish")
+        _checked(N.lib().tgp_count_publish, N.ptr(d_count), *call.publish, st)
         n = call.count()
     else:
         n = int(d_count.item())
@@ -595,9 +610,7 @@ def _read_count(d_count: Tensor) -> int:
     return n
 
 
-def _checked(fn, *args) -> None:
-    """Call a C-ABI entry point; a non-zero status is reported under the symbol that was called."""
-    N.check(fn(*args), fn.__name__)
+_checked = N.checked  # every native call goes through it: a failure is reported under the symbol that was called
 
 
 def _count_fill(dev, nbytes: int, count, fill, w_dtype=None, edge_id: bool = False,
@@ -657,7 +670,7 @@ def filter_edges(edge_index: Tensor, edge_weight: Optional[Tensor], node_index: 
     E = row.numel()
     f64 = edge_weight is not None and edge_weight.dtype == torch.float64  # fp64 weights pass through as they are
     w = None if edge_weight is None else (N.f64c if f64 else N.f32c)(edge_weight.reshape(-1))
-    ni = None if node_index is None else N.i64c(node_index)
+    ni = N.opt_i64(node_index)
     flags = (N.REMOVE_SELF_LOOPS if remove_self_loops else 0) | (N.EPS_FILTER if w is not None else 0)
     if want_edge_id:
         flags |= N.WANT_EDGE_ID
@@ -719,8 +732,8 @@ def _filter_edges_single(L, dev, st, row, col, w, E, ni, num_nodes, flags, eps, 
     nblk = 0 if md is None else md.numel() // 5
     _checked(entry, row.data_ptr(), col.data_ptr(), N.ptr(w), E, N.ptr(ni), 0 if ni is None else ni.numel(), num_nodes,
              flags, eps, ws.data_ptr(), ws.numel(), cap_p, cap_p + 8 * E, N.ptr(cap_w), N.ptr(cap_id),
-             None if md is None else md.data_ptr(), None if md is None else md.data_ptr() + 16 * nblk,
-             *call.lookback, st)
+             None if md is None else md.data_ptr(), None if md is None else md.data_ptr() + 16 * nblk, *call.lookback,
+             st)
     n_out = call.total()
     if n_out is None:
         # refused: node ids outside [0, num_nodes) -- the reference's index ops raise for these inputs too -- or a
@@ -937,18 +950,13 @@ def normalize_edges_(edge_index: Tensor, edge_weight: Tensor, num_nodes: int, de
     flags = (N.DEGREE_NORM if degree_norm else 0) | (N.EDGE_WEIGHT_NORM if edge_weight_norm else 0)
     if flags == 0 or row.numel() == 0:
         return edge_weight
-    bp = None if batch_pooled is None else N.i64c(batch_pooled)
-    L = N.lib()
-    if edge_weight.dtype == torch.float64:
-        ws = N.workspace(L.tgp_postprocess_sparse_workspace_bytes_f64(row.numel(), num_nodes, num_graphs), dev)
-        N.check(L.tgp_postprocess_sparse_norm_f64(N.ptr(row), N.ptr(col), N.ptr(edge_weight), row.numel(), num_nodes,
-                                                  flags, ops_eps(), N.ptr(bp), num_graphs, N.ptr(ws), ws.numel(),
-                                                  N.stream_ptr(dev)), "tgp_postprocess_sparse_norm_f64")
-        return edge_weight
-    ws = N.workspace(L.tgp_postprocess_sparse_workspace_bytes(row.numel(), num_nodes, num_graphs), dev)
-    N.check(L.tgp_postprocess_sparse_norm_f32(N.ptr(row), N.ptr(col), N.ptr(edge_weight), row.numel(), num_nodes,
-                                              flags, ops_eps(), N.ptr(bp), num_graphs, N.ptr(ws), ws.numel(),
-                                              N.stream_ptr(dev)), "tgp_postprocess_sparse_norm_f32")
+    bp = N.opt_i64(batch_pooled)
+    L, f64 = N.lib(), edge_weight.dtype == torch.float64
+    ws = N.workspace((L.tgp_postprocess_sparse_workspace_bytes_f64 if f64 else L.tgp_postprocess_sparse_workspace_bytes)(
+        row.numel(), num_nodes, num_graphs), dev)
+    _checked(L.tgp_postprocess_sparse_norm_f64 if f64 else L.tgp_postprocess_sparse_norm_f32, N.ptr(row), N.ptr(col),
+             N.ptr(edge_weight), row.numel(), num_nodes, flags, ops_eps(), N.ptr(bp), num_graphs, N.ptr(ws), ws.numel(),
+             N.stream_ptr(dev))
     return edge_weight
 
 
@@ -986,37 +994,6 @@ def _out_buffer(out: Optional[Tensor], shape, dev, dtype: torch.dtype = torch.fl
     return out
 
 
-def _dense_pool_f64(s, adj, x, flags, want_raw, want_post, out_x, out_adj):
-    """float64 operands: the same fused A3 + A7 + A8 call on v_mfma_f64_16x16x4_f64 (tgp_dense_pool_f64)."""
-    dev = N.require_device(s, adj, x)
-    s = N.f64c(s)
-    B, Nn, K = s.shape
-    F = 0
-    x_pool = adj_raw = adj_pool = None
-    if x is not None:
-        x = N.f64c(x)
-        if x.shape[:2] != (B, Nn):
-            raise ValueError(f"x {tuple(x.shape)} does not match s {tuple(s.shape)}")
-        F = x.size(2)
-        x_pool = _out_buffer(out_x, (B, K, F), dev, torch.float64)
-    a = None
-    if adj is not None:
-        if adj.shape != (B, Nn, Nn):
-            raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
-        a, tflag = _dense_adj_layout(adj, torch.float64)
-        flags |= tflag
-        if want_raw:
-            adj_raw = torch.empty(B, K, K, dtype=torch.float64, device=dev)
-        if want_post:
-            adj_pool = _out_buffer(out_adj, (B, K, K), dev, torch.float64)
-    L = N.lib()
-    ws = N.workspace(L.tgp_dense_pool_workspace_bytes_f64(B, Nn, K, F), dev)
-    N.check(L.tgp_dense_pool_f64(N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(), N.ptr(x_pool),
-                                 N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
-            "tgp_dense_pool_f64")
-    return x_pool, adj_raw, adj_pool
-
-
 def dense_pool(s: Tensor, adj: Optional[Tensor], x: Optional[Tensor], flags: int = 0, want_raw: bool = False,
                want_post: bool = True, graph_sizes: Optional[Tensor] = None, out_x: Optional[Tensor] = None,
                out_adj: Optional[Tensor] = None, mincut_terms: bool = False, diff_stats: bool = False):
@@ -1025,32 +1002,37 @@ def dense_pool(s: Tensor, adj: Optional[Tensor], x: Optional[Tensor], flags: int
     (optional): real nodes per graph when they are the leading rows and the padding is zero (to_dense_batch layout).
     ``mincut_terms``: return a fourth value, the [2,B] per-graph tails of MinCut's losses taken inside the pooling
     kernel (batches of small graphs only; None when the batch takes another kernel).  float64 operands (any of the
-    three) run the fp64 form of the same call; ``graph_sizes`` is a speed hint the fp64 form does not use."""
-    if _any_f64(s, adj, x):
-        out = _dense_pool_f64(s, adj, x, flags, want_raw, want_post, out_x, out_adj)
-        return out + (None,) if mincut_terms else out
+    three) run the fp64 form of the same call (tgp_dense_pool_f64, on v_mfma_f64_16x16x4_f64): it has neither the loss
+    terms nor the records, and ``graph_sizes`` is a speed hint it does not use."""
+    f64 = _any_f64(s, adj, x)
+    conv, dt = (N.f64c, torch.float64) if f64 else (N.f32c, torch.float32)
     dev = N.require_device(s, adj, x)
-    s = N.f32c(s)
+    s = conv(s)
     B, Nn, K = s.shape
     F = 0
     x_pool = adj_raw = adj_pool = None
     if x is not None:
-        x = N.f32c(x)
+        x = conv(x)
         if x.shape[:2] != (B, Nn):
             raise ValueError(f"x {tuple(x.shape)} does not match s {tuple(s.shape)}")
         F = x.size(2)
-        x_pool = _out_buffer(out_x, (B, K, F), dev)  # caller-provided: e.g. a slot of an all-gather send buffer
+        x_pool = _out_buffer(out_x, (B, K, F), dev, dt)  # caller-provided: e.g. a slot of an all-gather send buffer
     a = None
     if adj is not None:
         if adj.shape != (B, Nn, Nn):
             raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
-        a, tflag = _dense_adj_layout(adj)
+        a, tflag = _dense_adj_layout(adj, dt)
         flags |= tflag
         if want_raw:
-            adj_raw = torch.empty(B, K, K, dtype=torch.float32, device=dev)
+            adj_raw = torch.empty(B, K, K, dtype=dt, device=dev)
         if want_post:
-            adj_pool = _out_buffer(out_adj, (B, K, K), dev)
+            adj_pool = _out_buffer(out_adj, (B, K, K), dev, dt)
     L = N.lib()
+    if f64:
+        ws = N.workspace(L.tgp_dense_pool_workspace_bytes_f64(B, Nn, K, F), dev)
+        _checked(L.tgp_dense_pool_f64, N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(), N.ptr(x_pool),
+                 N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
+        return (x_pool, adj_raw, adj_pool, None) if mincut_terms else (x_pool, adj_raw, adj_pool)
     if diff_stats:
         # (r6) a fourth value: DiffPool's per-graph records [B,4] from the one-wave-per-graph kernel (:func:`diffpool_stats_tail`),
         # or None when the batch does not take that kernel (the caller computes the losses from the adjacency)
@@ -1058,24 +1040,22 @@ def dense_pool(s: Tensor, adj: Optional[Tensor], x: Optional[Tensor], flags: int
                 or not L.tgp_dense_pool_is_small(B, Nn, K, F)):
             return dense_pool(s, adj, x, flags & ~N.ADJ_TRANSPOSED, want_raw, want_post, graph_sizes, out_x, out_adj) + (None,)
         stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        N.check(L.tgp_dense_pool_small_diff_f32(N.ptr(s), N.ptr(a), N.ptr(x), None, None, None, B, Nn, K, F, flags, ops_eps(),
-                                                losses_eps(), None, N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool),
-                                                N.ptr(stats), None, N.stream_ptr(dev)), "tgp_dense_pool_small_diff_f32")
+        _checked(L.tgp_dense_pool_small_diff_f32, N.ptr(s), N.ptr(a), N.ptr(x), None, None, None, B, Nn, K, F, flags,
+                 ops_eps(), losses_eps(), None, N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(stats), None,
+                 N.stream_ptr(dev))
         return x_pool, adj_raw, adj_pool, stats
     ws = N.workspace(L.tgp_dense_pool_workspace_bytes(B, Nn, K, F), dev)
     if mincut_terms:
         terms = None
         if a is not None and L.tgp_dense_pool_is_small(B, Nn, K, F):
             terms = torch.empty(2, B, dtype=torch.float32, device=dev)
-            N.check(L.tgp_dense_pool_mincut_f32(N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(),
-                                                losses_eps(), N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool),
-                                                N.ptr(terms), N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
-                    "tgp_dense_pool_mincut_f32")
+            _checked(L.tgp_dense_pool_mincut_f32, N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(),
+                     losses_eps(), N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(terms), N.ptr(ws), ws.numel(),
+                     N.stream_ptr(dev))
             return x_pool, adj_raw, adj_pool, terms
     gs = _sizes_arg(graph_sizes, B, dev)
-    N.check(L.tgp_dense_pool_f32(N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(), N.ptr(gs), N.ptr(x_pool),
-                                 N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
-            "tgp_dense_pool_f32")
+    _checked(L.tgp_dense_pool_f32, N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags, ops_eps(), N.ptr(gs),
+             N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return (x_pool, adj_raw, adj_pool, None) if mincut_terms else (x_pool, adj_raw, adj_pool)
 
 
@@ -1094,7 +1074,7 @@ def dense_pool_select(x: Tensor, adj: Tensor, weight: Tensor, bias: Optional[Ten
     if weight.shape != (K, F) or adj.shape != (B, Nn, Nn):
         raise ValueError(f"dense_pool_select: shapes x {tuple(x.shape)}, adj {tuple(adj.shape)}, weight {tuple(weight.shape)}")
     a, tflag = _dense_adj_layout(adj)
-    b = None if bias is None else N.f32c(bias)
+    b = N.opt_f32(bias)
     m = None
     if mask is not None:
         m = mask.to(torch.uint8) if mask.dtype != torch.uint8 and mask.dtype != torch.bool else mask
@@ -1109,16 +1089,13 @@ def dense_pool_select(x: Tensor, adj: Tensor, weight: Tensor, bias: Optional[Ten
     bp = torch.empty(B * K, dtype=torch.int64, device=dev) if want_batch else None
     if diff_stats:  # (r6) DiffPool: `terms` holds the per-graph records [B,4] of :func:`diffpool_stats_tail` instead
         terms = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        N.check(N.lib().tgp_dense_pool_small_diff_f32(None, N.ptr(a), N.ptr(x), N.ptr(weight), N.ptr(b), N.ptr(m), B, Nn, K,
-                                                      F, flags | tflag, ops_eps(), losses_eps(), N.ptr(s), N.ptr(x_pool),
-                                                      N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(terms), N.ptr(bp),
-                                                      N.stream_ptr(dev)), "tgp_dense_pool_small_diff_f32")
+        _checked(N.lib().tgp_dense_pool_small_diff_f32, None, N.ptr(a), N.ptr(x), N.ptr(weight), N.ptr(b), N.ptr(m), B,
+                 Nn, K, F, flags | tflag, ops_eps(), losses_eps(), N.ptr(s), N.ptr(x_pool), N.ptr(adj_raw),
+                 N.ptr(adj_pool), N.ptr(terms), N.ptr(bp), N.stream_ptr(dev))
         return (s, x_pool, adj_raw, adj_pool, terms, bp) if want_batch else (s, x_pool, adj_raw, adj_pool, terms)
-    N.check(N.lib().tgp_dense_pool_select_f32(N.ptr(x), N.ptr(a), N.ptr(weight), N.ptr(b), N.ptr(m), B, Nn, K, F,
-                                              flags | tflag, ops_eps(), losses_eps(), N.ptr(s), N.ptr(x_pool),
-                                              N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(terms), N.ptr(bp),
-                                              N.stream_ptr(dev)),
-            "tgp_dense_pool_select_f32")
+    _checked(N.lib().tgp_dense_pool_select_f32, N.ptr(x), N.ptr(a), N.ptr(weight), N.ptr(b), N.ptr(m), B, Nn, K, F,
+             flags | tflag, ops_eps(), losses_eps(), N.ptr(s), N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool),
+             N.ptr(terms), N.ptr(bp), N.stream_ptr(dev))
     if want_batch:
         return s, x_pool, adj_raw, adj_pool, terms, bp
     return s, x_pool, adj_raw, adj_pool, terms
@@ -1138,9 +1115,8 @@ def edge_facts_launch(edge_index: Tensor, batch: Tensor):
     state = _sps_state(dev, st, 0)
     buf = torch.empty(n + 2, dtype=torch.long, device=dev)
     tag = state.next_facts_tag()
-    N.check(N.lib().tgp_edge_facts_sorted_i64(N.ptr(row), E, N.ptr(N.i64c(batch)), n, N.ptr(buf),
-                                              state.ticket.data_ptr() + 8, state.facts_slot(tag), tag, st),
-            "tgp_edge_facts_sorted_i64")
+    _checked(N.lib().tgp_edge_facts_sorted_i64, N.ptr(row), E, N.ptr(N.i64c(batch)), n, N.ptr(buf),
+             state.ticket.data_ptr() + 8, state.facts_slot(tag), tag, st)
     return state, tag, buf
 
 
@@ -1198,9 +1174,9 @@ class AdjSymmetry:
         st = N.stream_ptr(dev)
         self.state = _sps_state(dev, st, 0)
         self.tag = self.state.next_facts_tag()
-        N.check(N.lib().tgp_adj_symmetry_f32(N.ptr(row), N.ptr(col), E, N.ptr(N.i64c(batch)), N.ptr(N.i64c(ptr)),
-                                             adj.size(1), N.ptr(adj), self.state.ticket.data_ptr() + 8,
-                                             self.state.facts_slot(self.tag), self.tag, st), "tgp_adj_symmetry_f32")
+        _checked(N.lib().tgp_adj_symmetry_f32, N.ptr(row), N.ptr(col), E, N.ptr(N.i64c(batch)), N.ptr(N.i64c(ptr)),
+                 adj.size(1), N.ptr(adj), self.state.ticket.data_ptr() + 8, self.state.facts_slot(self.tag), self.tag,
+                 st)
 
     @classmethod
     def of_dense(cls, adj: Tensor) -> "AdjSymmetry":
@@ -1220,8 +1196,8 @@ class AdjSymmetry:
         st = N.stream_ptr(dev)
         self.state = _sps_state(dev, st, 0)
         self.tag = self.state.next_facts_tag()
-        N.check(N.lib().tgp_dense_symmetry_f32(N.ptr(adj), adj.size(0), adj.size(1), self.state.ticket.data_ptr() + 8,
-                                               self.state.facts_slot(self.tag), self.tag, st), "tgp_dense_symmetry_f32")
+        _checked(N.lib().tgp_dense_symmetry_f32, N.ptr(adj), adj.size(0), adj.size(1), self.state.ticket.data_ptr() + 8,
+                 self.state.facts_slot(self.tag), self.tag, st)
         return self
 
     @classmethod
@@ -1244,10 +1220,9 @@ class AdjSymmetry:
         st = N.stream_ptr(dev)
         self.state = _sps_state(dev, st, 0)
         self.tag = self.state.next_facts_tag()
-        w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
-        N.check(N.lib().tgp_edge_symmetry_f32(N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(row_ptr), num_nodes,
-                                              self.state.ticket.data_ptr() + 8, self.state.facts_slot(self.tag), self.tag,
-                                              st), "tgp_edge_symmetry_f32")
+        w = N.opt_f32_flat(edge_weight)
+        _checked(N.lib().tgp_edge_symmetry_f32, N.ptr(row), N.ptr(col), N.ptr(w), E, N.ptr(row_ptr), num_nodes,
+                 self.state.ticket.data_ptr() + 8, self.state.facts_slot(self.tag), self.tag, st)
         return self
 
     def get(self) -> bool:
@@ -1278,8 +1253,8 @@ def dense_pool_select_sparse(x: Tensor, edge_index: Tensor, edge_weight: Optiona
         raise ValueError("dense_pool_select_sparse: inconsistent shapes")
     row, col = _edge_rows(edge_index)
     E = row.numel()
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
-    b = None if bias is None else N.f32c(bias)
+    w = N.opt_f32_flat(edge_weight)
+    b = N.opt_f32(bias)
     s = torch.empty(B, Nn, K, dtype=torch.float32, device=dev)
     mask = torch.empty(B, Nn, dtype=torch.bool, device=dev)
     x_pool = torch.empty(B, K, F, dtype=torch.float32, device=dev)
@@ -1294,12 +1269,11 @@ def dense_pool_select_sparse(x: Tensor, edge_index: Tensor, edge_weight: Optiona
     # diff_stats (r6): a LAST value [B,4] = per-graph (sum A^2, trace(S^T A S), |S^T S|_F^2, entropy sum): DiffPool's two
     # losses without the dense adjacency (:func:`diffpool_stats_tail`)
     dstats = torch.empty(B, 4, dtype=torch.float32, device=dev) if diff_stats else None
-    N.check(N.lib().tgp_dense_pool_select_sparse_f32(
-        N.ptr(x), x.size(0), N.ptr(row) if E else None, N.ptr(col) if E else None, N.ptr(w), E, N.ptr(N.i64c(batch)),
-        N.ptr(N.i64c(node_ptr)), N.ptr(N.i64c(edge_ptr)), N.ptr(weight), N.ptr(b), B, Nn, K, F, flags,
-        1 if adj_transpose else 0, ops_eps(), losses_eps(), N.ptr(s), mask.data_ptr(), N.ptr(x_pool), N.ptr(adj_raw),
-        N.ptr(adj_pool), N.ptr(terms), N.ptr(bp), N.ptr(xd), N.ptr(ad), N.ptr(dstats), N.stream_ptr(dev)),
-        "tgp_dense_pool_select_sparse_f32")
+    _checked(N.lib().tgp_dense_pool_select_sparse_f32, N.ptr(x), x.size(0), N.ptr(row) if E else None,
+             N.ptr(col) if E else None, N.ptr(w), E, N.ptr(N.i64c(batch)), N.ptr(N.i64c(node_ptr)),
+             N.ptr(N.i64c(edge_ptr)), N.ptr(weight), N.ptr(b), B, Nn, K, F, flags, 1 if adj_transpose else 0, ops_eps(),
+             losses_eps(), N.ptr(s), mask.data_ptr(), N.ptr(x_pool), N.ptr(adj_raw), N.ptr(adj_pool), N.ptr(terms),
+             N.ptr(bp), N.ptr(xd), N.ptr(ad), N.ptr(dstats), N.stream_ptr(dev))
     tail = (dstats,) if diff_stats else ()
     if want_dense:
         return (s, mask, x_pool, adj_raw, adj_pool, terms, bp, xd, ad) + tail
@@ -1312,8 +1286,8 @@ def diffpool_stats_tail(stats: Tensor, link_scale: float, ent_scale: float) -> T
     dev = N.require_device(stats)
     stats = N.f32c(stats)
     out = torch.empty(2, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_diffpool_stats_tail_f32(N.ptr(stats), stats.size(0), float(link_scale), float(ent_scale),
-                                                N.ptr(out), N.stream_ptr(dev)), "tgp_diffpool_stats_tail_f32")
+    _checked(N.lib().tgp_diffpool_stats_tail_f32, N.ptr(stats), stats.size(0), float(link_scale), float(ent_scale),
+             N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -1374,13 +1348,10 @@ def dense_pool_small_bwd(s: Tensor, adj: Tensor, x: Optional[Tensor], flags: int
     diff_losses = grad(diff_losses, (2,)) if (g_link is not None or g_ent is not None) else None
     gs = torch.empty(B, Nn, K, dtype=torch.float32, device=dev)
     gx = torch.empty(B, Nn, F, dtype=torch.float32, device=dev) if (want_gx and x is not None) else None
-    N.check(N.lib().tgp_dense_pool_small_bwd_f32(N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags | tflag, ops_eps(),
-                                                 losses_eps(), N.ptr(g_x_pool), N.ptr(g_adj_pool), N.ptr(g_adj_raw),
-                                                 N.ptr(g_terms), N.ptr(g_cut), N.ptr(g_ortho), N.ptr(g_link),
-                                                 N.ptr(g_ent), N.ptr(diff_losses), float(link_scale),
-                                                 float(ent_scale), losses_eps(), (1 if bx else 0) | (2 if ba else 0),
-                                                 N.ptr(gs), N.ptr(gx), N.stream_ptr(dev)),
-            "tgp_dense_pool_small_bwd_f32")
+    _checked(N.lib().tgp_dense_pool_small_bwd_f32, N.ptr(s), N.ptr(a), N.ptr(x), B, Nn, K, F, flags | tflag, ops_eps(),
+             losses_eps(), N.ptr(g_x_pool), N.ptr(g_adj_pool), N.ptr(g_adj_raw), N.ptr(g_terms), N.ptr(g_cut),
+             N.ptr(g_ortho), N.ptr(g_link), N.ptr(g_ent), N.ptr(diff_losses), float(link_scale), float(ent_scale),
+             losses_eps(), (1 if bx else 0) | (2 if ba else 0), N.ptr(gs), N.ptr(gx), N.stream_ptr(dev))
     return gs, gx
 
 
@@ -1417,31 +1388,24 @@ def mlp_select_bwd(s: Tensor, g_s: Tensor, x: Tensor, weight: Tensor, want_gx: b
     ws = None
     if gw is not None:
         ws = N.workspace(L.tgp_mlp_select_bwd_workspace_bytes(M, F, K), dev)
-    N.check(L.tgp_mlp_select_bwd_f32(N.ptr(s), N.ptr(g_s), N.ptr(x), N.ptr(weight), M, F, K, N.ptr(gx),
-                                     1 if gx_accumulate is not None else 0, N.ptr(gw), N.ptr(gb), N.ptr(ws),
-                                     0 if ws is None else ws.numel(), st), "tgp_mlp_select_bwd_f32")
+    _checked(L.tgp_mlp_select_bwd_f32, N.ptr(s), N.ptr(g_s), N.ptr(x), N.ptr(weight), M, F, K, N.ptr(gx),
+             1 if gx_accumulate is not None else 0, N.ptr(gw), N.ptr(gb), N.ptr(ws), 0 if ws is None else ws.numel(),
+             st)
     return gx, (gw if want_gw else None), gb
 
 
 def postprocess_dense(adj_pool: Tensor, flags: int, inplace: bool = False) -> Tensor:
     """utils/ops.py:282-335 on a [B,K,K] tensor."""
     dev = N.require_device(adj_pool)
-    if adj_pool.dtype == torch.float64:  # a float64 pooled adjacency is post-processed in fp64 (utils/ops.py:282-335)
-        src = N.f64c(adj_pool)
-        dst = src if inplace else torch.empty_like(src)
-        B, K = src.size(0), src.size(1)
-        L = N.lib()
-        ws = N.workspace(L.tgp_postprocess_dense_workspace_bytes_f64(B, K), dev)
-        N.check(L.tgp_postprocess_dense_f64(N.ptr(src), N.ptr(dst), B, K, flags, ops_eps(), N.ptr(ws), ws.numel(),
-                                            N.stream_ptr(dev)), "tgp_postprocess_dense_f64")
-        return dst
-    src = N.f32c(adj_pool)
+    f64 = adj_pool.dtype == torch.float64  # a float64 pooled adjacency is post-processed in fp64 (utils/ops.py:282-335)
+    src = (N.f64c if f64 else N.f32c)(adj_pool)
     dst = src if inplace else torch.empty_like(src)
     B, K = src.size(0), src.size(1)
     L = N.lib()
-    ws = N.workspace(L.tgp_postprocess_dense_workspace_bytes(B, K), dev)
-    N.check(L.tgp_postprocess_dense_f32(N.ptr(src), N.ptr(dst), B, K, flags, ops_eps(), N.ptr(ws), ws.numel(),
-                                        N.stream_ptr(dev)), "tgp_postprocess_dense_f32")
+    ws = N.workspace((L.tgp_postprocess_dense_workspace_bytes_f64 if f64 else L.tgp_postprocess_dense_workspace_bytes)(B, K),
+                     dev)
+    _checked(L.tgp_postprocess_dense_f64 if f64 else L.tgp_postprocess_dense_f32, N.ptr(src), N.ptr(dst), B, K, flags,
+             ops_eps(), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return dst
 
 
@@ -1456,8 +1420,8 @@ def postprocess_dense_bwd(raw: Tensor, g_post: Tensor, flags: int) -> Optional[T
     # an expanded scalar (the gradient of a plain `.sum()`) is handed over as one value: no [B,K,K] copy of it (r6)
     g_post, one = _bcast_or_dense(g_post, raw.shape)
     out = torch.empty_like(raw)
-    N.check(N.lib().tgp_postprocess_dense_bwd_f32(N.ptr(raw), N.ptr(g_post), B, K, flags | ((1 << 16) if one else 0),
-                                                  ops_eps(), N.ptr(out), N.stream_ptr(dev)), "tgp_postprocess_dense_bwd_f32")
+    _checked(N.lib().tgp_postprocess_dense_bwd_f32, N.ptr(raw), N.ptr(g_post), B, K, flags | ((1 << 16) if one else 0),
+             ops_eps(), N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -1466,8 +1430,8 @@ def entropy_bwd(s: Tensor, g: Tensor, scale: float = 1.0) -> Tensor:
     dev = N.require_device(s, g)
     s32 = N.f32c(s)
     out = torch.empty_like(s32)
-    N.check(N.lib().tgp_entropy_bwd_f32(N.ptr(s32), s32.numel(), losses_eps(), N.ptr(N.f32c(g.reshape(1))), float(scale),
-                                        N.ptr(out), N.stream_ptr(dev)), "tgp_entropy_bwd_f32")
+    _checked(N.lib().tgp_entropy_bwd_f32, N.ptr(s32), s32.numel(), losses_eps(), N.ptr(N.f32c(g.reshape(1))),
+             float(scale), N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -1495,9 +1459,19 @@ def link_loss_sq(s: Tensor, adj: Tensor, graph_sizes: Optional[Tensor] = None) -
     sq = torch.empty(B, dtype=torch.float32, device=dev)
     L = N.lib()
     ws = N.workspace(L.tgp_link_loss_workspace_bytes(B, Nn, K), dev)
-    N.check(L.tgp_link_loss_f32(N.ptr(s), N.ptr(adj), B, Nn, K, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(sq),
-                                N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "tgp_link_loss_f32")
+    _checked(L.tgp_link_loss_f32, N.ptr(s), N.ptr(adj), B, Nn, K, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(sq),
+             N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return sq
+
+
+def _entropy_partials(s: Tensor, dev, st) -> Tuple[Tensor, int]:
+    """(buffer, n): the per-workgroup shares of sum(-s log(s + eps)) that the DiffPool tails add up, and their number."""
+    s32, L = N.f32c(s), N.lib()
+    ws = N.workspace(L.tgp_entropy_sum_workspace_bytes(s32.numel()), dev)
+    n_partial = ctypes.c_int(0)
+    _checked(L.tgp_entropy_partials_f32, N.ptr(s32), s32.numel(), losses_eps(), N.ptr(ws), ws.numel(),
+             ctypes.addressof(n_partial), st)
+    return ws, n_partial.value
 
 
 def diffpool_loss_tail(s: Tensor, adj: Tensor, graph_sizes: Optional[Tensor], link_scale: float,
@@ -1507,17 +1481,11 @@ def diffpool_loss_tail(s: Tensor, adj: Tensor, graph_sizes: Optional[Tensor], li
     launch (outside autograd)."""
     dev = N.require_device(s, adj)
     sq = link_loss_sq(s, adj, graph_sizes)
-    s32 = N.f32c(s)
-    L = N.lib()
-    ws = N.workspace(L.tgp_entropy_sum_workspace_bytes(s32.numel()), dev)
-    import ctypes as _ct
-    n_partial = _ct.c_int(0)
     st = N.stream_ptr(dev)
-    N.check(L.tgp_entropy_partials_f32(N.ptr(s32), s32.numel(), losses_eps(), N.ptr(ws), ws.numel(),
-                                       _ct.addressof(n_partial), st), "tgp_entropy_partials_f32")
+    ws, n_partial = _entropy_partials(s, dev, st)
     out = torch.empty(2, dtype=torch.float32, device=dev)
-    N.check(L.tgp_diffpool_loss_tail_f32(N.ptr(sq), sq.numel(), N.ptr(ws), n_partial.value, float(link_scale),
-                                         float(ent_scale), N.ptr(out), st), "tgp_diffpool_loss_tail_f32")
+    _checked(N.lib().tgp_diffpool_loss_tail_f32, N.ptr(sq), sq.numel(), N.ptr(ws), n_partial, float(link_scale),
+             float(ent_scale), N.ptr(out), st)
     return out
 
 
@@ -1530,10 +1498,23 @@ def entropy_sum(s: Tensor) -> Tensor:
     out = torch.empty((), dtype=torch.float32, device=dev)
     L = N.lib()
     ws = N.workspace(L.tgp_entropy_sum_workspace_bytes(s.numel()), dev)
-    N.check(L.tgp_entropy_sum_f32(N.ptr(s), s.numel(), losses_eps(), N.ptr(out), N.ptr(ws), ws.numel(),
-                                  N.stream_ptr(dev)),
-            "tgp_entropy_sum_f32")
+    _checked(L.tgp_entropy_sum_f32, N.ptr(s), s.numel(), losses_eps(), N.ptr(out), N.ptr(ws), ws.numel(),
+             N.stream_ptr(dev))
     return out
+
+
+def _cut_terms_f32(dev, adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor], want_den: bool):
+    """(deg [B,N], q [B,N], den [B] or None) from one launch of ``tgp_cut_terms_f32``."""
+    adj, s = N.f32c(adj), N.f32c(s)
+    B, Nn, K = s.shape
+    if adj.shape != (B, Nn, Nn):
+        raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
+    deg = torch.empty(B, Nn, dtype=torch.float32, device=dev)
+    q = torch.empty(B, Nn, dtype=torch.float32, device=dev)
+    den = torch.empty(B, dtype=torch.float32, device=dev) if want_den else None
+    _checked(N.lib().tgp_cut_terms_f32, N.ptr(adj), N.ptr(s), B, Nn, K, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+             N.ptr(deg), N.ptr(q), N.ptr(den), N.stream_ptr(dev))
+    return deg, q, den
 
 
 def cut_terms(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
@@ -1544,31 +1525,13 @@ def cut_terms(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor] = None) -> T
         a64, s64 = adj.to(torch.float64), s.to(torch.float64)
         deg, q = a64.sum(-1), (s64 * s64).sum(-1)
         return deg, q, (deg * q).sum(-1)
-    adj, s = N.f32c(adj), N.f32c(s)
-    B, Nn, K = s.shape
-    if adj.shape != (B, Nn, Nn):
-        raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
-    deg = torch.empty(B, Nn, dtype=torch.float32, device=dev)
-    q = torch.empty(B, Nn, dtype=torch.float32, device=dev)
-    den = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_cut_terms_f32(N.ptr(adj), N.ptr(s), B, Nn, K, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(deg),
-                                      N.ptr(q), N.ptr(den), N.stream_ptr(dev)), "tgp_cut_terms_f32")
-    return deg, q, den
+    return _cut_terms_f32(dev, adj, s, graph_sizes, True)
 
 
 def cut_rows(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """(deg [B,N], q [B,N]) of :func:`cut_terms` without the per-graph dot product (one launch: the training step's fused
     loss tail forms den itself, :func:`mincut_terms_fused`)."""
-    dev = N.require_device(adj, s)
-    adj, s = N.f32c(adj), N.f32c(s)
-    B, Nn, K = s.shape
-    if adj.shape != (B, Nn, Nn):
-        raise ValueError(f"adj {tuple(adj.shape)} does not match s {tuple(s.shape)}")
-    deg = torch.empty(B, Nn, dtype=torch.float32, device=dev)
-    q = torch.empty(B, Nn, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_cut_terms_f32(N.ptr(adj), N.ptr(s), B, Nn, K, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(deg),
-                                      N.ptr(q), None, N.stream_ptr(dev)), "tgp_cut_terms_f32")
-    return deg, q
+    return _cut_terms_f32(N.require_device(adj, s), adj, s, graph_sizes, False)[:2]
 
 
 def mincut_terms_fused(raw: Tensor, gram: Tensor, deg: Optional[Tensor], q: Optional[Tensor],
@@ -1578,8 +1541,8 @@ def mincut_terms_fused(raw: Tensor, gram: Tensor, deg: Optional[Tensor], q: Opti
     backward's right-hand sides need; ``want_means``: also the batch means of the two terms (what the pooler hands out)."""
     dev = N.require_device(raw, gram, deg, q)
     raw, gram = N.f32c(raw), N.f32c(gram)
-    deg = None if deg is None else N.f32c(deg)
-    q = None if q is None else N.f32c(q)  # (None: deg already carries the factor, den = sum of deg)
+    deg = N.opt_f32(deg)
+    q = N.opt_f32(q)  # (None: deg already carries the factor, den = sum of deg)
     # edges = (row_ptr int32 [Ntot+1], edge_index, weights or None) of an un-padded batch: den = sum_e w_e q[col_e], the
     # in-degree form (S^T A^T S of the batched poolers on the rows route); deg is then not read
     e_rp = e_col = e_w = None
@@ -1588,7 +1551,7 @@ def mincut_terms_fused(raw: Tensor, gram: Tensor, deg: Optional[Tensor], q: Opti
             raise ValueError("mincut_terms_fused(edges=...) needs ptr and q")
         e_rp, e_ei, e_w = edges
         e_col = _edge_rows(e_ei)[1]
-        e_w = None if e_w is None else N.f32c(e_w.reshape(-1))
+        e_w = N.opt_f32_flat(e_w)
     B, Kc, Nn = raw.size(0), raw.size(-1), (deg if deg is not None else q).size(-1)
     den = torch.empty(B, dtype=torch.float32, device=dev)
     out = torch.empty(2, B, dtype=torch.float32, device=dev)
@@ -1601,11 +1564,9 @@ def mincut_terms_fused(raw: Tensor, gram: Tensor, deg: Optional[Tensor], q: Opti
         means = torch.empty(2, dtype=torch.float32, device=dev)
         ticket = _sps_state(dev, st, 0).ticket.data_ptr() + 16
     # ptr: deg / q belong to an un-padded batch (graph b owns entries ptr[b] .. ptr[b+1])
-    N.check(N.lib().tgp_mincut_terms_fused_f32(N.ptr(raw), N.ptr(gram), N.ptr(deg), N.ptr(q), B, Nn, Kc, losses_eps(),
-                                               N.ptr(den), N.ptr(out), N.ptr(stats),
-                                               N.ptr(None if ptr is None else N.i64c(ptr)), ticket, N.ptr(means),
-                                               N.ptr(e_rp), N.ptr(e_col), N.ptr(e_w), st),
-            "tgp_mincut_terms_fused_f32")
+    _checked(N.lib().tgp_mincut_terms_fused_f32, N.ptr(raw), N.ptr(gram), N.ptr(deg), N.ptr(q), B, Nn, Kc, losses_eps(),
+             N.ptr(den), N.ptr(out), N.ptr(stats), N.ptr(N.opt_i64(ptr)), ticket, N.ptr(means), N.ptr(e_rp),
+             N.ptr(e_col), N.ptr(e_w), st)
     if want_means:
         return den, out, stats, (means if means is not None else out.mean(dim=1))
     return den, out, stats
@@ -1630,9 +1591,9 @@ def dense_pool_train_fwd(s: Tensor, adj_mem: Tensor, x: Tensor, flags: int, acat
     gram = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if want_gram else None
     L = N.lib()
     ws = N.workspace(L.tgp_dense_pool_train_workspace_bytes(B, Nn, Kc, F), dev)
-    N.check(L.tgp_dense_pool_train_fwd_f32(N.ptr(s), N.ptr(adj_mem), N.ptr(x), B, Nn, Kc, F, flags, ops_eps(),
-                                           N.ptr(acat), ld, N.ptr(x_pool), N.ptr(raw), N.ptr(adj_pool), N.ptr(gram),
-                                           N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "tgp_dense_pool_train_fwd_f32")
+    _checked(L.tgp_dense_pool_train_fwd_f32, N.ptr(s), N.ptr(adj_mem), N.ptr(x), B, Nn, Kc, F, flags, ops_eps(),
+             N.ptr(acat), ld, N.ptr(x_pool), N.ptr(raw), N.ptr(adj_pool), N.ptr(gram), N.ptr(ws), ws.numel(),
+             N.stream_ptr(dev))
     return x_pool, raw, adj_pool, gram
 
 
@@ -1648,11 +1609,10 @@ def dense_pool_train_rhs(g_raw_a: Optional[Tensor], g_raw_b: Optional[Tensor], m
     c1 = torch.empty(B, dtype=torch.float32, device=dev) if mode == 1 else None
     gw = torch.empty(B, 2 * Kc, F, dtype=torch.float32, device=dev) if weight is not None else None
     w = None if weight is None else N.f32c(weight.detach())
-    N.check(N.lib().tgp_dense_pool_train_rhs_f32(N.ptr(g_raw_a), N.ptr(g_raw_b), mode, N.ptr(stats), N.ptr(den),
-                                                 N.ptr(gram), N.ptr(g_la), N.ptr(g_lb), float(scale), N.ptr(link_loss),
-                                                 float(link_scale), losses_eps(), N.ptr(g_x), 1 if gx_bcast else 0,
-                                                 int(symmetric), N.ptr(w), B, Kc, F, N.ptr(rcat), N.ptr(c1),
-                                                 N.ptr(gw), N.stream_ptr(dev)), "tgp_dense_pool_train_rhs_f32")
+    _checked(N.lib().tgp_dense_pool_train_rhs_f32, N.ptr(g_raw_a), N.ptr(g_raw_b), mode, N.ptr(stats), N.ptr(den),
+             N.ptr(gram), N.ptr(g_la), N.ptr(g_lb), float(scale), N.ptr(link_loss), float(link_scale), losses_eps(),
+             N.ptr(g_x), 1 if gx_bcast else 0, int(symmetric), N.ptr(w), B, Kc, F, N.ptr(rcat), N.ptr(c1), N.ptr(gw),
+             N.stream_ptr(dev))
     return rcat, c1, gw
 
 
@@ -1668,7 +1628,7 @@ def softmax_bwd_ex(s: Tensor, ds: Tensor, extra: Optional[Tensor] = None, c1: Op
     else:
         B, Nn, Kc = s.shape
     s2, d2 = N.f32c(s), N.f32c(ds)
-    ex = None if extra is None else N.f32c(extra)
+    ex = N.opt_f32(extra)
     if d2.numel() != s2.numel() or (ex is not None and ex.numel() != s2.numel()):
         raise ValueError("softmax_bwd_ex: gradient shapes do not match s")
     if out is None:
@@ -1676,12 +1636,9 @@ def softmax_bwd_ex(s: Tensor, ds: Tensor, extra: Optional[Tensor] = None, c1: Op
     elif (out.shape != s2.shape or out.dtype != torch.float32 or out.stride(-1) != 1
           or (out.dim() == 3 and out.stride(0) != Nn * out.stride(1))):
         raise ValueError("softmax_bwd_ex: out must be a float32 view of s's shape with a uniform row stride")
-    N.check(N.lib().tgp_softmax_bwd_ex_f32(N.ptr(s2), N.ptr(d2), N.ptr(ex), N.ptr(None if c1 is None else N.f32c(c1)),
-                                           N.ptr(None if deg is None else N.f32c(deg)), Nn,
-                                           N.ptr(None if ent_g is None else N.f32c(ent_g.reshape(1))), float(ent_scale),
-                                           losses_eps(), out.data_ptr(), out.stride(-2), B * Nn, Kc,
-                                           N.ptr(None if batch is None else N.i64c(batch)), N.stream_ptr(dev)),
-            "tgp_softmax_bwd_ex_f32")
+    _checked(N.lib().tgp_softmax_bwd_ex_f32, N.ptr(s2), N.ptr(d2), N.ptr(ex), N.ptr(N.opt_f32(c1)),
+             N.ptr(N.opt_f32(deg)), Nn, N.ptr(None if ent_g is None else N.f32c(ent_g.reshape(1))), float(ent_scale),
+             losses_eps(), out.data_ptr(), out.stride(-2), B * Nn, Kc, N.ptr(N.opt_i64(batch)), N.stream_ptr(dev))
     return out
 
 
@@ -1695,8 +1652,8 @@ def copy_cols2(a: Tensor, b: Tensor, dst: Tensor, col_a: int, col_b: int, one_co
     if not (a.is_contiguous() and b.is_contiguous() and dst.is_contiguous()) or a.size(0) != dst.size(0) \
             or b.size(0) != dst.size(0):
         raise ValueError("copy_cols2: operands must be contiguous with equal row counts")
-    N.check(N.lib().tgp_copy_cols2_f32(N.ptr(a), a.size(1), N.ptr(b), b.size(1), dst.size(0), N.ptr(dst), dst.size(1),
-                                       col_a, col_b, one_col, N.stream_ptr(dev)), "tgp_copy_cols2_f32")
+    _checked(N.lib().tgp_copy_cols2_f32, N.ptr(a), a.size(1), N.ptr(b), b.size(1), dst.size(0), N.ptr(dst), dst.size(1),
+             col_a, col_b, one_col, N.stream_ptr(dev))
 
 
 def copy_cols3(a: Tensor, b: Tensor, c: Tensor, dst: Tensor, col_a: int, col_b: int, col_c: int, one_col: int = -1) -> None:
@@ -1704,9 +1661,8 @@ def copy_cols3(a: Tensor, b: Tensor, c: Tensor, dst: Tensor, col_a: int, col_b: 
     dev = N.require_device(a, b, c, dst)
     if not all(t.is_contiguous() and t.size(0) == dst.size(0) for t in (a, b, c)) or not dst.is_contiguous():
         raise ValueError("copy_cols3: operands must be contiguous with equal row counts")
-    N.check(N.lib().tgp_copy_cols3_f32(N.ptr(a), a.size(1), N.ptr(b), b.size(1), N.ptr(c), c.size(1), dst.size(0),
-                                       N.ptr(dst), dst.size(1), col_a, col_b, col_c, one_col, N.stream_ptr(dev)),
-            "tgp_copy_cols3_f32")
+    _checked(N.lib().tgp_copy_cols3_f32, N.ptr(a), a.size(1), N.ptr(b), b.size(1), N.ptr(c), c.size(1), dst.size(0),
+             N.ptr(dst), dst.size(1), col_a, col_b, col_c, one_col, N.stream_ptr(dev))
 
 
 def slab_sum_split(part: Tensor, F: int, want_gw: bool = True, want_gb: bool = True):
@@ -1715,8 +1671,7 @@ def slab_sum_split(part: Tensor, F: int, want_gw: bool = True, want_gb: bool = T
     slabs, Kc, W = part.shape
     gw = torch.empty(Kc, F, dtype=torch.float32, device=dev) if want_gw else None
     gb = torch.empty(Kc, dtype=torch.float32, device=dev) if want_gb else None
-    N.check(N.lib().tgp_slab_sum_split_f32(N.ptr(part), slabs, Kc, F, W, N.ptr(gw), N.ptr(gb), N.stream_ptr(dev)),
-            "tgp_slab_sum_split_f32")
+    _checked(N.lib().tgp_slab_sum_split_f32, N.ptr(part), slabs, Kc, F, W, N.ptr(gw), N.ptr(gb), N.stream_ptr(dev))
     return gw, gb
 
 
@@ -1734,9 +1689,10 @@ def bmm_into(a: Tensor, b: Tensor, out: Tensor, trans_a: bool = False, accumulat
         raise ValueError(f"bmm_into: shapes {tuple(a.shape)} x {tuple(b.shape)} -> {tuple(out.shape)}")
     sA = 0 if a.size(0) == 1 else a.stride(0)
     sB = 0 if b.size(0) == 1 else b.stride(0)
-    fn = N.lib().tgp_bmm_accumulate_f32 if accumulate else N.lib().tgp_bmm_f32
-    N.check(fn(a.data_ptr(), b.data_ptr(), out.data_ptr(), G, M, Nc, Kd, 1 if trans_a else 0, a.stride(1), b.stride(1),
-               out.stride(1), sA, sB, out.stride(0), N.stream_ptr(dev)), "tgp_bmm_f32")
+    L = N.lib()
+    _checked(L.tgp_bmm_accumulate_f32 if accumulate else L.tgp_bmm_f32, a.data_ptr(), b.data_ptr(), out.data_ptr(), G,
+             M, Nc, Kd, 1 if trans_a else 0, a.stride(1), b.stride(1), out.stride(1), sA, sB, out.stride(0),
+             N.stream_ptr(dev))
     return out
 
 
@@ -1746,8 +1702,8 @@ def mincut_loss_terms(raw: Tensor, den: Tensor, gram: Tensor) -> Tensor:
     raw, den, gram = N.f32c(raw), N.f32c(den), N.f32c(gram)
     B, Kc = raw.size(0), raw.size(-1)
     out = torch.empty(2, B, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_mincut_loss_terms_f32(N.ptr(raw), N.ptr(den), N.ptr(gram), B, Kc, losses_eps(), N.ptr(out),
-                                              N.stream_ptr(dev)), "tgp_mincut_loss_terms_f32")
+    _checked(N.lib().tgp_mincut_loss_terms_f32, N.ptr(raw), N.ptr(den), N.ptr(gram), B, Kc, losses_eps(), N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
@@ -1760,9 +1716,8 @@ def mincut_loss_terms_bwd(raw: Tensor, den: Tensor, gram: Tensor, g_terms: Tenso
     g_raw = torch.empty_like(raw)
     W = torch.empty_like(raw)
     c1 = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_mincut_loss_terms_bwd_f32(N.ptr(raw), N.ptr(den), N.ptr(gram), N.ptr(g_terms), B, Kc, losses_eps(),
-                                                  N.ptr(g_raw), N.ptr(c1), N.ptr(W), N.stream_ptr(dev)),
-            "tgp_mincut_loss_terms_bwd_f32")
+    _checked(N.lib().tgp_mincut_loss_terms_bwd_f32, N.ptr(raw), N.ptr(den), N.ptr(gram), N.ptr(g_terms), B, Kc,
+             losses_eps(), N.ptr(g_raw), N.ptr(c1), N.ptr(W), N.stream_ptr(dev))
     return g_raw, c1, W
 
 
@@ -1800,9 +1755,8 @@ def dmon_dense_terms(adj: Optional[Tensor], s: Tensor, mask: Optional[Tensor] = 
         if deg.shape != (B, Nn):
             raise ValueError(f"deg {tuple(deg.shape)} does not match s {tuple(s.shape)}")
     part = torch.empty(B, nsplit, 2 * Kc + 2, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_dmon_dense_terms_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
-                                             N.ptr(_mask_bytes(mask, B, Nn)), nsplit, N.ptr(deg), N.ptr(part),
-                                             N.stream_ptr(dev)), "tgp_dmon_dense_terms_f32")
+    _checked(N.lib().tgp_dmon_dense_terms_f32, N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+             N.ptr(_mask_bytes(mask, B, Nn)), nsplit, N.ptr(deg), N.ptr(part), N.stream_ptr(dev))
     return deg, part
 
 
@@ -1814,12 +1768,11 @@ def dmon_edge_degrees(edge_index: Tensor, edge_weight: Optional[Tensor], node_pt
     dev = N.require_device(edge_index, edge_weight, node_ptr, edge_ptr)
     row, col = _edge_rows(edge_index)
     key = col if in_degrees else row
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     B = node_ptr.numel() - 1
     deg = torch.empty(B, int(max_nodes), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_dmon_edge_degrees_f32(N.ptr(key) if key.numel() else None, N.ptr(w), key.numel(),
-                                              N.ptr(N.i64c(node_ptr)), N.ptr(N.i64c(edge_ptr)), B, int(max_nodes),
-                                              N.ptr(deg), N.stream_ptr(dev)), "tgp_dmon_edge_degrees_f32")
+    _checked(N.lib().tgp_dmon_edge_degrees_f32, N.ptr(key) if key.numel() else None, N.ptr(w), key.numel(),
+             N.ptr(N.i64c(node_ptr)), N.ptr(N.i64c(edge_ptr)), B, int(max_nodes), N.ptr(deg), N.stream_ptr(dev))
     return deg
 
 
@@ -1828,14 +1781,14 @@ def dmon_node_terms(s: Tensor, deg: Optional[Tensor], ptr: Tensor, max_nodes: in
     the cluster loss alone), ptr [B+1] node offsets of the sorted batch, ``max_nodes`` its largest graph."""
     dev = N.require_device(s, deg, ptr)
     s, ptr = N.f32c(s), N.i64c(ptr)
-    d = None if deg is None else N.f32c(deg.reshape(-1))
+    d = N.opt_f32_flat(deg)
     if d is not None and d.numel() != s.size(0):
         raise ValueError("dmon_node_terms: deg must hold one value per row of s")
     B, Kc = ptr.numel() - 1, s.size(1)
     nsplit = max(1, -(-int(max_nodes) // _PART_ROWS))
     part = torch.empty(B, nsplit, 2 * Kc + 2, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_dmon_node_terms_f32(N.ptr(s), N.ptr(d), N.ptr(ptr), B, Kc, nsplit, N.ptr(part), N.stream_ptr(dev)),
-            "tgp_dmon_node_terms_f32")
+    _checked(N.lib().tgp_dmon_node_terms_f32, N.ptr(s), N.ptr(d), N.ptr(ptr), B, Kc, nsplit, N.ptr(part),
+             N.stream_ptr(dev))
     return part
 
 
@@ -1849,9 +1802,9 @@ def dmon_loss_terms(part: Tensor, raw: Optional[Tensor], tr: Optional[Tensor], g
     part = N.f32c(part)
     B, nsplit, P = part.shape
     Kc = (P - 2) // 2
-    raw = None if raw is None else N.f32c(raw)
-    tr = None if tr is None else N.f32c(tr.reshape(-1))
-    gram = None if gram is None else N.f32c(gram)
+    raw = N.opt_f32(raw)
+    tr = N.opt_f32_flat(tr)
+    gram = N.opt_f32(gram)
     for t, shape in ((raw, (B, Kc, Kc)), (gram, (B, Kc, Kc)), (tr, (B,))):
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"dmon_loss_terms: operand {tuple(t.shape)}, expected {shape}")
@@ -1859,10 +1812,9 @@ def dmon_loss_terms(part: Tensor, raw: Optional[Tensor], tr: Optional[Tensor], g
     ca = torch.empty(B, Kc, dtype=torch.float32, device=dev)
     cs = torch.empty(B, Kc, dtype=torch.float32, device=dev)
     stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_dmon_loss_terms_f32(N.ptr(part), nsplit, N.ptr(raw), N.ptr(tr), N.ptr(gram), B, Kc, float(sqrt_k),
-                                            1 if clamp_m else 0, losses_eps(), *(float(c) for c in coeffs), N.ptr(out),
-                                            N.ptr(ca), N.ptr(cs), N.ptr(stats), N.stream_ptr(dev)),
-            "tgp_dmon_loss_terms_f32")
+    _checked(N.lib().tgp_dmon_loss_terms_f32, N.ptr(part), nsplit, N.ptr(raw), N.ptr(tr), N.ptr(gram), B, Kc,
+             float(sqrt_k), 1 if clamp_m else 0, losses_eps(), *(float(c) for c in coeffs), N.ptr(out), N.ptr(ca),
+             N.ptr(cs), N.ptr(stats), N.stream_ptr(dev))
     return out, ca, cs, stats
 
 
@@ -1873,15 +1825,14 @@ def dmon_loss_terms_bwd(g_terms: Tensor, stats: Tensor, gram: Optional[Tensor], 
     tgp_dmon_loss_terms_bwd_f32)."""
     dev = N.require_device(g_terms, stats, gram)
     g_terms, stats = N.f32c(g_terms), N.f32c(stats)
-    gram = None if gram is None else N.f32c(gram)
+    gram = N.opt_f32(gram)
     B = stats.size(0)
     g_raw = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if want_raw else None
     g_tr = torch.empty(B, dtype=torch.float32, device=dev) if want_tr else None
     W = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if gram is not None else None
     coef = torch.empty(B, 2, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_dmon_loss_terms_bwd_f32(N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(sqrt_k),
-                                                *(float(c) for c in coeffs), N.ptr(g_raw), N.ptr(g_tr), N.ptr(coef), N.ptr(W), N.stream_ptr(dev)),
-            "tgp_dmon_loss_terms_bwd_f32")
+    _checked(N.lib().tgp_dmon_loss_terms_bwd_f32, N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(sqrt_k),
+             *(float(c) for c in coeffs), N.ptr(g_raw), N.ptr(g_tr), N.ptr(coef), N.ptr(W), N.stream_ptr(dev))
     return g_raw, g_tr, coef, W
 
 
@@ -1892,11 +1843,11 @@ def dmon_ds(deg: Optional[Tensor], ca: Tensor, cs: Tensor, coef: Tensor, rows: i
     dev = N.require_device(deg, ca, cs, coef, batch, out)
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * ca.size(1):
         raise ValueError("dmon_ds: out must be a contiguous float32 tensor of rows x K values")
-    d = None if deg is None else N.f32c(deg.reshape(-1))
-    b = None if batch is None else N.i64c(batch)
-    N.check(N.lib().tgp_dmon_ds_f32(N.ptr(d), N.ptr(N.f32c(ca)), N.ptr(N.f32c(cs)), N.ptr(N.f32c(coef)), rows,
-                                    nodes_per_graph, N.ptr(b), ca.size(0), ca.size(1), 1 if accumulate else 0, out.data_ptr(),
-                                    N.stream_ptr(dev)), "tgp_dmon_ds_f32")
+    d = N.opt_f32_flat(deg)
+    b = N.opt_i64(batch)
+    _checked(N.lib().tgp_dmon_ds_f32, N.ptr(d), N.ptr(N.f32c(ca)), N.ptr(N.f32c(cs)), N.ptr(N.f32c(coef)), rows,
+             nodes_per_graph, N.ptr(b), ca.size(0), ca.size(1), 1 if accumulate else 0, out.data_ptr(),
+             N.stream_ptr(dev))
     return out
 
 
@@ -1934,11 +1885,10 @@ def jb_terms(s: Tensor, mask: Optional[Tensor] = None, graph_sizes: Optional[Ten
     out = torch.empty(B, dtype=torch.float32, device=dev)
     coef = torch.empty(B, Kc, dtype=torch.float32, device=dev) if want_coef else None
     mean = torch.empty((), dtype=torch.float32, device=dev) if want_mean else None
-    N.check(N.lib().tgp_jb_terms_f32(N.ptr(s), B, Nn, Kc, N.ptr(sizes), N.ptr(m), N.ptr(p), rows_max,
-                                     1 if normalize else 0, float(Nn if num_nodes is None else num_nodes),
-                                     float(Kc if num_supernodes is None else num_supernodes), losses_eps(), float(scale),
-                                     N.ptr(part), N.ptr(out), N.ptr(coef), N.ptr(mean), N.stream_ptr(dev)),
-            "tgp_jb_terms_f32")
+    _checked(N.lib().tgp_jb_terms_f32, N.ptr(s), B, Nn, Kc, N.ptr(sizes), N.ptr(m), N.ptr(p), rows_max,
+             1 if normalize else 0, float(Nn if num_nodes is None else num_nodes),
+             float(Kc if num_supernodes is None else num_supernodes), losses_eps(), float(scale), N.ptr(part),
+             N.ptr(out), N.ptr(coef), N.ptr(mean), N.stream_ptr(dev))
     return (out, coef, mean) if want_mean else (out, coef)
 
 
@@ -1953,10 +1903,10 @@ def jb_ds(s: Tensor, coef: Tensor, g: Tensor, batch: Optional[Tensor] = None) ->
     if s.dim() == 3:
         rows, per, b = s.size(0) * s.size(1), max(s.size(1), 1), None
     else:
-        rows, per, b = s.size(0), max(s.size(0), 1), None if batch is None else N.i64c(batch)
+        rows, per, b = s.size(0), max(s.size(0), 1), N.opt_i64(batch)
     out = torch.empty_like(s)
-    N.check(N.lib().tgp_jb_ds_f32(N.ptr(s), N.ptr(coef), N.ptr(g), 1 if bcast else 0, rows, per, N.ptr(b), B, Kc,
-                                  N.ptr(out), N.stream_ptr(dev)), "tgp_jb_ds_f32")
+    _checked(N.lib().tgp_jb_ds_f32, N.ptr(s), N.ptr(coef), N.ptr(g), 1 if bcast else 0, rows, per, N.ptr(b), B, Kc,
+             N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -1978,8 +1928,8 @@ def hosc_matvec(adj: Tensor, v: Optional[Tensor], graph_sizes: Optional[Tensor] 
         if tuple(v.shape) != (B, Nn):
             raise ValueError(f"hosc_matvec: v {tuple(v.shape)} does not match adj {tuple(adj.shape)}")
     y = torch.empty(B, Nn, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_hosc_matvec_f32(N.ptr(a), N.ptr(v), B, Nn, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(y),
-                                        N.stream_ptr(dev)), "tgp_hosc_matvec_f32")
+    _checked(N.lib().tgp_hosc_matvec_f32, N.ptr(a), N.ptr(v), B, Nn, N.ptr(_sizes_arg(graph_sizes, B, dev)), N.ptr(y),
+             N.stream_ptr(dev))
     return y
 
 
@@ -2029,11 +1979,10 @@ def hosc_node_terms(s: Tensor, z: Optional[Tensor], z1: Optional[Tensor], d3: Op
     ds_ = [_hosc_rows(t, rows, 1) for t in (d3, d1)]
     L = N.lib()
     part = torch.empty(B, nsplit, int(L.tgp_hosc_record_floats(Kc)), dtype=torch.float32, device=dev)
-    N.check(L.tgp_hosc_node_terms_f32(N.ptr(s), N.ptr(zs[0][0]), N.ptr(zs[1][0]), _hosc_ld(zs, "hosc_node_terms"),
-                                      N.ptr(ds_[0][0]), N.ptr(ds_[1][0]), _hosc_ld(ds_, "hosc_node_terms"), B, Nn, Kc,
-                                      N.ptr(_sizes_arg(graph_sizes, B, dev) if ptr is None else None),
-                                      N.ptr(_mask_bytes(mask, B, Nn) if ptr is None else None), N.ptr(p), nsplit,
-                                      N.ptr(part), N.stream_ptr(dev)), "tgp_hosc_node_terms_f32")
+    _checked(L.tgp_hosc_node_terms_f32, N.ptr(s), N.ptr(zs[0][0]), N.ptr(zs[1][0]), _hosc_ld(zs, "hosc_node_terms"),
+             N.ptr(ds_[0][0]), N.ptr(ds_[1][0]), _hosc_ld(ds_, "hosc_node_terms"), B, Nn, Kc,
+             N.ptr(_sizes_arg(graph_sizes, B, dev) if ptr is None else None),
+             N.ptr(_mask_bytes(mask, B, Nn) if ptr is None else None), N.ptr(p), nsplit, N.ptr(part), N.stream_ptr(dev))
     return part
 
 
@@ -2054,9 +2003,8 @@ def hosc_small(adj: Tensor, s: Tensor, mask: Optional[Tensor] = None, graph_size
     z = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
     d = torch.empty(2, B, Nn, dtype=torch.float32, device=dev)
     part = torch.empty(B, 1, int(L.tgp_hosc_record_floats(Kc)), dtype=torch.float32, device=dev)
-    N.check(L.tgp_hosc_small_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
-                                 N.ptr(_mask_bytes(mask, B, Nn)), N.ptr(z), N.ptr(d[0]), N.ptr(d[1]), N.ptr(part),
-                                 N.stream_ptr(dev)), "tgp_hosc_small_f32")
+    _checked(L.tgp_hosc_small_f32, N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+             N.ptr(_mask_bytes(mask, B, Nn)), N.ptr(z), N.ptr(d[0]), N.ptr(d[1]), N.ptr(part), N.stream_ptr(dev))
     return z, d[0], d[1], part
 
 
@@ -2068,8 +2016,8 @@ def hosc_loss_terms(part: Tensor, Kc: int, raw: Optional[Tensor], gram: Optional
     dev = N.require_device(part, raw, gram)
     part = N.f32c(part)
     B, nsplit = part.size(0), part.size(1)
-    raw = None if raw is None else N.f32c(raw)
-    gram = None if gram is None else N.f32c(gram)
+    raw = N.opt_f32(raw)
+    gram = N.opt_f32(gram)
     for t in (raw, gram):
         if t is not None and tuple(t.shape) != (B, Kc, Kc):
             raise ValueError(f"hosc_loss_terms: operand {tuple(t.shape)}, expected {(B, Kc, Kc)}")
@@ -2078,9 +2026,9 @@ def hosc_loss_terms(part: Tensor, Kc: int, raw: Optional[Tensor], gram: Optional
     out = torch.empty(2, B, dtype=torch.float32, device=dev)
     cn = torch.empty(B, Kc, dtype=torch.float32, device=dev)
     stats = torch.empty(B, 6, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_hosc_loss_terms_f32(N.ptr(part), nsplit, N.ptr(raw), N.ptr(gram), B, Kc, float(alpha), float(mu),
-                                            float(inv_k), 1 if hosc_ortho else 0, losses_eps(), N.ptr(out), N.ptr(cn),
-                                            N.ptr(stats), N.stream_ptr(dev)), "tgp_hosc_loss_terms_f32")
+    _checked(N.lib().tgp_hosc_loss_terms_f32, N.ptr(part), nsplit, N.ptr(raw), N.ptr(gram), B, Kc, float(alpha),
+             float(mu), float(inv_k), 1 if hosc_ortho else 0, losses_eps(), N.ptr(out), N.ptr(cn), N.ptr(stats),
+             N.stream_ptr(dev))
     return out, cn, stats
 
 
@@ -2090,14 +2038,13 @@ def hosc_loss_terms_bwd(g_terms: Tensor, stats: Tensor, gram: Optional[Tensor], 
     gradients [2,B], one launch (see tgp_hosc_loss_terms_bwd_f32)."""
     dev = N.require_device(g_terms, stats, gram)
     g_terms, stats = N.f32c(g_terms), N.f32c(stats)
-    gram = None if gram is None else N.f32c(gram)
+    gram = N.opt_f32(gram)
     B = stats.size(0)
     g_raw = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if want_raw else None
     W = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev) if gram is not None else None
     coef = torch.empty(B, 5, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_hosc_loss_terms_bwd_f32(N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(alpha), float(mu),
-                                                float(inv_k), 1 if hosc_ortho else 0, N.ptr(g_raw), N.ptr(coef), N.ptr(W),
-                                                N.stream_ptr(dev)), "tgp_hosc_loss_terms_bwd_f32")
+    _checked(N.lib().tgp_hosc_loss_terms_bwd_f32, N.ptr(g_terms), N.ptr(stats), N.ptr(gram), B, Kc, float(alpha),
+             float(mu), float(inv_k), 1 if hosc_ortho else 0, N.ptr(g_raw), N.ptr(coef), N.ptr(W), N.stream_ptr(dev))
     return g_raw, coef, W
 
 
@@ -2116,14 +2063,13 @@ def hosc_ds(s: Tensor, z: Optional[Tensor], zt: Optional[Tensor], z1: Optional[T
     zs = [_hosc_rows(t, rows, Kc) for t in (z, z1)]
     zts = [_hosc_rows(t, rows, Kc) for t in (zt, z1t)]
     ds_ = [_hosc_rows(t, rows, 1) for t in (d3, d1)]
-    b = None if batch is None else N.i64c(batch)
-    c = None if cn is None else N.f32c(cn)
+    b = N.opt_i64(batch)
+    c = N.opt_f32(cn)
     coef = N.f32c(coef)
-    N.check(N.lib().tgp_hosc_ds_f32(N.ptr(s), N.ptr(zs[0][0]), N.ptr(zts[0][0]), N.ptr(zs[1][0]), N.ptr(zts[1][0]),
-                                    _hosc_ld(zs, "hosc_ds"), _hosc_ld(zts, "hosc_ds"), N.ptr(ds_[0][0]), N.ptr(ds_[1][0]),
-                                    _hosc_ld(ds_, "hosc_ds"), N.ptr(c), N.ptr(coef), rows, int(nodes_per_graph), N.ptr(b),
-                                    coef.size(0), Kc, 1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev)),
-            "tgp_hosc_ds_f32")
+    _checked(N.lib().tgp_hosc_ds_f32, N.ptr(s), N.ptr(zs[0][0]), N.ptr(zts[0][0]), N.ptr(zs[1][0]), N.ptr(zts[1][0]),
+             _hosc_ld(zs, "hosc_ds"), _hosc_ld(zts, "hosc_ds"), N.ptr(ds_[0][0]), N.ptr(ds_[1][0]),
+             _hosc_ld(ds_, "hosc_ds"), N.ptr(c), N.ptr(coef), rows, int(nodes_per_graph), N.ptr(b), coef.size(0), Kc,
+             1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev))
     return out
 
 
@@ -2158,8 +2104,8 @@ def bnpool_rec_fwd(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor] = N
         return rec, stats
     nfl = int(N.lib().tgp_bnpool_part_floats(B, Nn))
     part = torch.empty(max(nfl, 1), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_bnpool_rec_fwd_f32(N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), B, Nn, Kc, N.ptr(part), part.numel(),
-                                           N.ptr(rec), N.ptr(stats), N.stream_ptr(dev)), "tgp_bnpool_rec_fwd_f32")
+    _checked(N.lib().tgp_bnpool_rec_fwd_f32, N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), B, Nn, Kc, N.ptr(part),
+             part.numel(), N.ptr(rec), N.ptr(stats), N.stream_ptr(dev))
     return rec, stats
 
 
@@ -2176,8 +2122,8 @@ def bnpool_rec_bwd(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor], g:
     p = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
     q = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
     if B > 0:
-        N.check(N.lib().tgp_bnpool_rec_bwd_f32(N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), N.ptr(g), N.ptr(stats), B, Nn, Kc,
-                                               N.ptr(p), N.ptr(q), N.stream_ptr(dev)), "tgp_bnpool_rec_bwd_f32")
+        _checked(N.lib().tgp_bnpool_rec_bwd_f32, N.ptr(t), N.ptr(s), N.ptr(a), N.ptr(m), N.ptr(g), N.ptr(stats), B, Nn,
+                 Kc, N.ptr(p), N.ptr(q), N.stream_ptr(dev))
     return p, q
 
 
@@ -2202,8 +2148,8 @@ def acc_tv_dense(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor] = None) -
     nrb = max(1, -(-Nn // _ACC_TV_ROWS))
     part = torch.empty(B, nrb, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, nrb, dtype=torch.int32, device=dev)
-    N.check(N.lib().tgp_acc_tv_dense_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)), nrb,
-                                         N.ptr(part), N.ptr(cnt), N.stream_ptr(dev)), "tgp_acc_tv_dense_f32")
+    _checked(N.lib().tgp_acc_tv_dense_f32, N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)), nrb,
+             N.ptr(part), N.ptr(cnt), N.stream_ptr(dev))
     return part, cnt
 
 
@@ -2215,9 +2161,8 @@ def acc_tv_dense_bwd(adj: Tensor, s: Tensor, graph_sizes: Optional[Tensor], g_tv
     a, s = N.f32c(adj), N.f32c(s)
     B, Nn, Kc = s.shape
     ds = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_acc_tv_dense_bwd_f32(N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
-                                             N.ptr(N.f32c(g_tv)), N.ptr(ecnt), float(c_tv), N.ptr(ds),
-                                             N.stream_ptr(dev)), "tgp_acc_tv_dense_bwd_f32")
+    _checked(N.lib().tgp_acc_tv_dense_bwd_f32, N.ptr(a), N.ptr(s), B, Nn, Kc, N.ptr(_sizes_arg(graph_sizes, B, dev)),
+             N.ptr(N.f32c(g_tv)), N.ptr(ecnt), float(c_tv), N.ptr(ds), N.stream_ptr(dev))
     return ds
 
 
@@ -2235,13 +2180,14 @@ def acc_tv_edge(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], by
     dev = N.require_device(s, edge_index, edge_weight)
     s = N.f32c(s)
     _, col = _edge_rows(edge_index)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     n, Kc, E = s.size(0), s.size(1), col.numel()
     if w is not None and w.numel() != E:
         raise ValueError("acc_tv_edge: one weight per edge")
     out = torch.empty(n, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_acc_tv_edge_f32(N.ptr(s), n, Kc, N.ptr(col) if E else None, N.ptr(w), E, N.ptr(by_src.row_ptr),
-                                        N.ptr(by_src.perm), N.ptr(out), N.stream_ptr(dev)), "tgp_acc_tv_edge_f32")
+    src_ptr, src_perm, col_p = by_src.walk(col, E)
+    _checked(N.lib().tgp_acc_tv_edge_f32, N.ptr(s), n, Kc, col_p, N.ptr(w), E, src_ptr, src_perm, N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
@@ -2251,15 +2197,15 @@ def acc_tv_edge_bwd(s: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor]
     dev = N.require_device(s, edge_index, edge_weight, batch, g_tv, ecnt)
     s = N.f32c(s)
     row, col = _edge_rows(edge_index)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     n, Kc, E = s.size(0), s.size(1), col.numel()
     ds = torch.empty(n, Kc, dtype=torch.float32, device=dev)
-    b = None if batch is None else N.i64c(batch)
-    N.check(N.lib().tgp_acc_tv_edge_bwd_f32(N.ptr(s), n, Kc, N.ptr(row) if E else None, N.ptr(col) if E else None,
-                                            N.ptr(w), E, N.ptr(by_src.row_ptr), N.ptr(by_src.perm),
-                                            N.ptr(by_dst.row_ptr), N.ptr(by_dst.perm), N.ptr(b), N.ptr(N.f32c(g_tv)),
-                                            N.ptr(ecnt), float(c_tv), ecnt.numel(), N.ptr(ds), N.stream_ptr(dev)),
-            "tgp_acc_tv_edge_bwd_f32")
+    b = N.opt_i64(batch)
+    src_ptr, src_perm, col_p = by_src.walk(col, E)  # (out-edges: the far end is the destination; in-edges: the source)
+    dst_ptr, dst_perm, row_p = by_dst.walk(row, E)
+    _checked(N.lib().tgp_acc_tv_edge_bwd_f32, N.ptr(s), n, Kc, row_p, col_p, N.ptr(w), E, src_ptr, src_perm, dst_ptr,
+             dst_perm, N.ptr(b), N.ptr(N.f32c(g_tv)), N.ptr(ecnt), float(c_tv), ecnt.numel(), N.ptr(ds),
+             N.stream_ptr(dev))
     return ds
 
 
@@ -2292,9 +2238,8 @@ def acc_quantile(s: Tensor, k: int, mask: Optional[Tensor] = None, graph_sizes: 
     qnode = torch.empty(B, Kc, dtype=torch.int32, device=dev)
     cge = torch.empty(B, Kc, dtype=torch.int32, device=dev)
     nreal = torch.empty(B, dtype=torch.int32, device=dev)
-    N.check(N.lib().tgp_acc_quantile_f32(N.ptr(s), B, Nn, Kc, N.ptr(gs), N.ptr(m), N.ptr(p), mx, int(k), code, N.ptr(q),
-                                         N.ptr(qnode), N.ptr(colsum), N.ptr(cge), N.ptr(nreal), N.stream_ptr(dev)),
-            "tgp_acc_quantile_f32")
+    _checked(N.lib().tgp_acc_quantile_f32, N.ptr(s), B, Nn, Kc, N.ptr(gs), N.ptr(m), N.ptr(p), mx, int(k), code,
+             N.ptr(q), N.ptr(qnode), N.ptr(colsum), N.ptr(cge), N.ptr(nreal), N.stream_ptr(dev))
     return q, qnode, colsum, cge, nreal, taken
 
 
@@ -2312,9 +2257,9 @@ def acc_tail(B: int, Kc: int, k: int, dev, tv=None, colsum: Optional[Tensor] = N
         nrb = vals.size(1)
     elif tv is not None:
         vals, src_ptr, ptr = tv[1], tv[2].row_ptr, N.i64c(tv[3])
-    N.check(N.lib().tgp_acc_loss_terms_f32(N.ptr(vals), N.ptr(cnt), N.ptr(src_ptr), N.ptr(ptr), nrb, N.ptr(colsum),
-                                           N.ptr(nreal), B, Kc, int(k), float(coeffs[0]), float(coeffs[1]), N.ptr(out),
-                                           N.ptr(ecnt), N.stream_ptr(dev)), "tgp_acc_loss_terms_f32")
+    _checked(N.lib().tgp_acc_loss_terms_f32, N.ptr(vals), N.ptr(cnt), N.ptr(src_ptr), N.ptr(ptr), nrb, N.ptr(colsum),
+             N.ptr(nreal), B, Kc, int(k), float(coeffs[0]), float(coeffs[1]), N.ptr(out), N.ptr(ecnt),
+             N.stream_ptr(dev))
     return out, ecnt
 
 
@@ -2332,11 +2277,10 @@ def acc_asym_bwd(s: Tensor, k: int, q: Tensor, qnode: Tensor, cge: Tensor, nreal
         m, gs, p, b = _mask_bytes(mask, B, Nn), _sizes_arg(graph_sizes, B, dev), None, None
     else:
         rows, Nn, m, gs, p = s.size(0), 0, None, None, N.i64c(ptr)
-        b = None if batch is None else N.i64c(batch)
-    N.check(N.lib().tgp_acc_asym_bwd_f32(N.ptr(s), rows, Nn, Kc, N.ptr(b), N.ptr(p), N.ptr(gs), N.ptr(m), N.ptr(q),
-                                         N.ptr(qnode), N.ptr(cge), N.ptr(nreal), N.ptr(N.f32c(g_bal)), float(c_bal), int(k),
-                                         B, 1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev)),
-            "tgp_acc_asym_bwd_f32")
+        b = N.opt_i64(batch)
+    _checked(N.lib().tgp_acc_asym_bwd_f32, N.ptr(s), rows, Nn, Kc, N.ptr(b), N.ptr(p), N.ptr(gs), N.ptr(m), N.ptr(q),
+             N.ptr(qnode), N.ptr(cge), N.ptr(nreal), N.ptr(N.f32c(g_bal)), float(c_bal), int(k), B,
+             1 if accumulate else 0, out.data_ptr(), N.stream_ptr(dev))
     return out
 
 
@@ -2365,8 +2309,7 @@ def topk_plan(sizes: Tensor, ratio: float) -> Tuple[Tensor, Tensor]:
     B = sizes.numel()
     k = torch.empty(B, dtype=torch.int64, device=dev)
     koff = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    N.check(N.lib().tgp_topk_plan(N.ptr(sizes), B, float(ratio), N.ptr(k), N.ptr(koff), N.stream_ptr(dev)),
-            "tgp_topk_plan")
+    _checked(N.lib().tgp_topk_plan, N.ptr(sizes), B, float(ratio), N.ptr(k), N.ptr(koff), N.stream_ptr(dev))
     return k, koff
 
 
@@ -2404,19 +2347,16 @@ def topk_select(score: Tensor, batch: Optional[Tensor], num_graphs: int, ptr: Te
     # r5: graphs beyond the per-graph sort routes (the device-wide route) also get the kept-node bitmap and its rank
     # directory from the compaction pass -- what the subgraph Connect of this very selection starts from
     directory = None
-    import ctypes as _ct
-    wrote = _ct.c_int(0)
+    wrote = ctypes.c_int(0)
     if n > 0 and k_total > 0 and not (0 < segments_max_nodes <= 8192):
         nblk = int(L.tgp_topk_select_directory_blocks(n))
         directory = torch.empty(5 * nblk, dtype=torch.int32, device=dev)  # [4 nblk] bitmap words | [nblk] rank128
-    N.check(L.tgp_topk_select(N.ptr(score), N.ptr(None if batch is None else N.i64c(batch)), n, num_graphs,
-                              N.ptr(N.i64c(ptr)), N.ptr(N.i64c(k)), N.ptr(N.i64c(koff)), segments_max_nodes, N.ptr(ws),
-                              ws.numel(), idx_p, idx_p + 8 * k_total, perm_p, val_p,
-                              N.ptr(lift_ptr), pack_p,
-                              None if directory is None else directory.data_ptr(),
-                              None if directory is None else directory.data_ptr() + 16 * nblk,
-                              _ct.addressof(wrote) if directory is not None else None,
-                              N.stream_ptr(dev)), "tgp_topk_select")
+    _checked(L.tgp_topk_select, N.ptr(score), N.ptr(N.opt_i64(batch)), n, num_graphs, N.ptr(N.i64c(ptr)),
+             N.ptr(N.i64c(k)), N.ptr(N.i64c(koff)), segments_max_nodes, N.ptr(ws), ws.numel(), idx_p,
+             idx_p + 8 * k_total, perm_p, val_p, N.ptr(lift_ptr), pack_p,
+             None if directory is None else directory.data_ptr(),
+             None if directory is None else directory.data_ptr() + 16 * nblk,
+             ctypes.addressof(wrote) if directory is not None else None, N.stream_ptr(dev))
     if not wrote.value:
         directory = None
     if one:
@@ -2468,7 +2408,7 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
     dev = N.require_device(edge_index, edge_weight)
     row, col = _edge_rows(edge_index)
     E = row.numel()
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     L = N.lib()
     st = N.stream_ptr(dev)
     if (relabel and max_rounds is None and graph_ptr is not None and max_graph_nodes is not None and E > 0
@@ -2489,10 +2429,8 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         base = buf.data_ptr()
         # (a list pooled before brings its per-graph offsets along; a new one lets the kernel search: r5, no launch for them)
         eptr = _edge_ptr_memo(edge_index, graph_ptr) if _SPS_GIVE_PTRS else None
-        N.check(L.tgp_graclus_match_graphs_fused(N.ptr(row), N.ptr(col), N.ptr(w), num_nodes, E, N.ptr(gp), B,
-                                                 N.ptr(eptr), None,
-                                                 base + o_idx, base + o_ptr, base + o_perm, base + o_ones,
-                                                 *call.lookback, st), "tgp_graclus_match_graphs_fused")
+        _checked(L.tgp_graclus_match_graphs_fused, N.ptr(row), N.ptr(col), N.ptr(w), num_nodes, E, N.ptr(gp), B,
+                 N.ptr(eptr), None, base + o_idx, base + o_ptr, base + o_perm, base + o_ones, *call.lookback, st)
         i64, i32, f32 = buf.view(torch.int64), buf.view(torch.int32), buf.view(torch.float32)
         index = torch.as_strided(i64, (2, num_nodes), (num_nodes, 1), o_idx >> 3)
         a_ptr = torch.as_strided(i32, (num_nodes + 1,), (1,), o_ptr >> 2)
@@ -2519,11 +2457,9 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
     if optimistic or (E > 1 and _rows_sorted(edge_index, row)):
         row_ptr, perm = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev), None
         if optimistic:
-            N.check(L.tgp_rowptr_from_sorted_flag_i64(N.ptr(row), E, num_nodes, N.ptr(row_ptr), N.ptr(words[1:]), st),
-                    "tgp_rowptr_from_sorted_flag_i64")
+            _checked(L.tgp_rowptr_from_sorted_flag_i64, N.ptr(row), E, num_nodes, N.ptr(row_ptr), N.ptr(words[1:]), st)
         else:
-            N.check(L.tgp_rowptr_from_sorted_i64(N.ptr(row), E, num_nodes, N.ptr(row_ptr), st),
-                    "tgp_rowptr_from_sorted_i64")
+            _checked(L.tgp_rowptr_from_sorted_i64, N.ptr(row), E, num_nodes, N.ptr(row_ptr), st)
         sorted_ptr = row_ptr
     else:
         index = build_assign_index(row, num_nodes)
@@ -2541,9 +2477,8 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         pairs["row_ptr"] = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev)
         pairs["perm"] = torch.empty(max(num_nodes, 1), dtype=torch.int32, device=dev)
         pairs["ones"] = torch.empty(num_nodes, dtype=torch.float32, device=dev)  # the values of S, same launch
-        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), num_nodes, N.ptr(rws), rws.numel(), N.ptr(index),
-                                          N.ptr(words[2:]), N.ptr(pairs["row_ptr"]), N.ptr(pairs["perm"]),
-                                          N.ptr(pairs["ones"]), st), "tgp_graclus_relabel_i64")
+        _checked(L.tgp_graclus_relabel_i64, N.ptr(label), num_nodes, N.ptr(rws), rws.numel(), N.ptr(index),
+                 N.ptr(words[2:]), N.ptr(pairs["row_ptr"]), N.ptr(pairs["perm"]), N.ptr(pairs["ones"]), st)
         return index
 
     def finish(index=None, k=None):
@@ -2557,15 +2492,13 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         return (out, sorted_ptr) if return_row_ptr else out
 
     def start(init_state=1):
-        N.check(L.tgp_graclus_match_start(N.ptr(row), N.ptr(col), N.ptr(w), N.ptr(row_ptr), N.ptr(perm), num_nodes, E,
-                                          N.ptr(ws), ws.numel(), N.ptr(label), init_state, st),
-                "tgp_graclus_match_start")
+        _checked(L.tgp_graclus_match_start, N.ptr(row), N.ptr(col), N.ptr(w), N.ptr(row_ptr), N.ptr(perm), num_nodes, E,
+                 N.ptr(ws), ws.numel(), N.ptr(label), init_state, st)
     start(0 if (per_graph and not finished) else 1)  # (the one-launch route sets the labels itself)
     if not finished and per_graph:
         gp = N.i64c(graph_ptr)
-        N.check(L.tgp_graclus_match_graphs(N.ptr(row_ptr), num_nodes, E, N.ptr(ws), N.ptr(gp), gp.numel() - 1,
-                                           int(max_graph_nodes), N.ptr(label), N.ptr(words), st),
-                "tgp_graclus_match_graphs")
+        _checked(L.tgp_graclus_match_graphs, N.ptr(row_ptr), num_nodes, E, N.ptr(ws), N.ptr(gp), gp.numel() - 1,
+                 int(max_graph_nodes), N.ptr(label), N.ptr(words), st)
         index = relabelled() if relabel else None  # (optimistic: one round trip for the status word and the count)
         got = words.tolist()
         if optimistic:
@@ -2581,14 +2514,14 @@ def graclus_match(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: 
         if max_rounds is not None:
             step = min(step, max_rounds - done)
         matched = torch.empty(step + 1, dtype=torch.int32, device=dev)  # [round flags ..., tail status]
-        N.check(L.tgp_graclus_match_rounds(N.ptr(row_ptr), num_nodes, E, N.ptr(ws), step, N.ptr(matched),
-                                           N.ptr(label), st), "tgp_graclus_match_rounds")
+        _checked(L.tgp_graclus_match_rounds, N.ptr(row_ptr), num_nodes, E, N.ptr(ws), step, N.ptr(matched),
+                 N.ptr(label), st)
         done += step
         if max_rounds is None:
             # the few thousand nodes that are still free after these rounds: all their remaining rounds in one workgroup
             # (declines when there are more than that), read back with the round flags
-            N.check(L.tgp_graclus_match_tail(N.ptr(row_ptr), num_nodes, E, N.ptr(ws), N.ptr(label),
-                                             N.ptr(matched[step:]), st), "tgp_graclus_match_tail")
+            _checked(L.tgp_graclus_match_tail, N.ptr(row_ptr), num_nodes, E, N.ptr(ws), N.ptr(label),
+                     N.ptr(matched[step:]), st)
             last, tail = matched[step - 1:].tolist()
             finished = last == 0 or tail == 1
         else:
@@ -2670,8 +2603,8 @@ def _owner_labels(n: int, name: str, dev, st):
     rws = N.workspace(L.tgp_graclus_relabel_workspace_bytes(n), dev)
 
     def relabel():
-        N.check(L.tgp_graclus_relabel_i64(N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
-                                          None, None, None, st), "tgp_graclus_relabel_i64")
+        _checked(L.tgp_graclus_relabel_i64, N.ptr(label), n, N.ptr(rws), rws.numel(), N.ptr(index), N.ptr(words[2:]),
+                 None, None, None, st)
     return label, index, words, relabel
 
 
@@ -2683,10 +2616,10 @@ def kmis_degree(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: in
     out = torch.zeros(num_nodes, dtype=torch.float32, device=dev)
     if num_nodes == 0 or edge_index.size(1) == 0:
         return out
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     grp = edge_group(edge_index, num_nodes, by_destination=True)
-    N.check(N.lib().tgp_kmis_degree_f32(N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(w), num_nodes, N.ptr(out),
-                                        N.stream_ptr(dev)), "tgp_kmis_degree_f32")
+    _checked(N.lib().tgp_kmis_degree_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(w), num_nodes, N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
@@ -2704,8 +2637,8 @@ def kmis_updated_score(score: Tensor, edge_index: Tensor, order_k: int, heuristi
     out = torch.empty_like(score)
     if heuristic == "greedy":
         ws = N.workspace(L.tgp_kmis_workspace_bytes(n), dev)
-        N.check(L.tgp_kmis_greedy_f32(N.ptr(row), N.ptr(col), E, n, int(order_k), N.ptr(score), N.ptr(ws), ws.numel(),
-                                      N.ptr(out), st), "tgp_kmis_greedy_f32")
+        _checked(L.tgp_kmis_greedy_f32, N.ptr(row), N.ptr(col), E, n, int(order_k), N.ptr(score), N.ptr(ws), ws.numel(),
+                 N.ptr(out), st)
         return out
     if heuristic != "w-greedy":
         raise ValueError(f"Unrecognized `score_heuristic` value: {heuristic}")
@@ -2716,8 +2649,8 @@ def kmis_updated_score(score: Tensor, edge_index: Tensor, order_k: int, heuristi
     for h in range(order_k):
         last = h == order_k - 1
         dst = out if last else spare[h % 2]
-        N.check(L.tgp_kmis_wsum_f32(N.ptr(row), N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(cur),
-                                    N.ptr(score) if last else None, n, N.ptr(dst), st), "tgp_kmis_wsum_f32")
+        _checked(L.tgp_kmis_wsum_f32, N.ptr(row), N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(cur),
+                 N.ptr(score) if last else None, n, N.ptr(dst), st)
         cur = dst
     return out
 
@@ -2770,7 +2703,7 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
 
     def relabel():
         relabel_owners()
-        N.check(L.tgp_kmis_mis_index_i64(N.ptr(label), N.ptr(index), n, N.ptr(mis), st), "tgp_kmis_mis_index_i64")
+        _checked(L.tgp_kmis_mis_index_i64, N.ptr(label), N.ptr(index), n, N.ptr(mis), st)
 
     updated = None
     if want == "graphs":
@@ -2780,9 +2713,9 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
             if mode == 2:
                 updated = torch.empty_like(score)
         gp = N.i64c(graph_ptr)
-        N.check(L.tgp_kmis_graphs(N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1, int(max_graph_nodes), k, mode,
-                                  N.ptr(score if mode == 2 else updated), N.ptr(rank), N.ptr(updated) if mode == 2 else None,
-                                  N.ptr(label), N.ptr(words), st), "tgp_kmis_graphs")
+        _checked(L.tgp_kmis_graphs, N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1, int(max_graph_nodes), k,
+                 mode, N.ptr(score if mode == 2 else updated), N.ptr(rank), N.ptr(updated) if mode == 2 else None,
+                 N.ptr(label), N.ptr(words), st)
         relabel()
         got = words.tolist()  # the one host wait: status and K together
         if _frame_done(got[0], "tgp_kmis_graphs", route, "an edge"):
@@ -2793,13 +2726,12 @@ def kmis_select(edge_index: Tensor, num_nodes: int, order_k: int = 1, score: Opt
     if rank is None and updated is None:
         updated = kmis_updated_score(score, edge_index, k, heuristic)
     ws = N.workspace(L.tgp_kmis_workspace_bytes(n), dev)
-    N.check(L.tgp_kmis_rounds_start(N.ptr(rank), N.ptr(updated), n, N.ptr(ws), ws.numel(), st), "tgp_kmis_rounds_start")
+    _checked(L.tgp_kmis_rounds_start, N.ptr(rank), N.ptr(updated), n, N.ptr(ws), ws.numel(), st)
 
     def launch(done, step, flags):
-        N.check(L.tgp_kmis_rounds(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, step, N.ptr(flags), st),
-                "tgp_kmis_rounds")
+        _checked(L.tgp_kmis_rounds, N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, step, N.ptr(flags), st)
     done, _ = _run_rounds(launch, n, "tgp_kmis_rounds", "the set", dev)
-    N.check(L.tgp_kmis_clusters(N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, N.ptr(label), st), "tgp_kmis_clusters")
+    _checked(L.tgp_kmis_clusters, N.ptr(row), N.ptr(col), E, n, k, N.ptr(ws), done, N.ptr(label), st)
     relabel()
     kk = int(words.tolist()[2])
     res.index, res.k, res.mis, res.updated, res.route, res.rounds = index, kk, mis[:kk], updated, "rounds", done
@@ -2815,21 +2747,17 @@ def edge_contract_raw(x: Tensor, edge_index: Tensor, weight: Tensor, bias: Optio
     (select/edge_contraction_select.py:217-218) as two per-node projections from one pass over ``x`` plus two gathered
     scalars per entry; the E x 2F matrix is never formed.  ``weight``: the 2F weights of ``Linear(2F, 1)``."""
     dev = N.require_device(x, edge_index, weight, bias)
-    if x.dim() != 2:
-        raise ValueError(f"edge_contract_raw expects x of shape [N, F], got {tuple(x.shape)}")
-    x, w = _rows_f32(x), N.f32c(weight.reshape(-1))
+    (x, ld), w = _row_operand(x, "edge_contract_raw", convert=True), N.f32c(weight.reshape(-1))
     n, F = x.size(0), x.size(1)
     if w.numel() != 2 * F:
         raise ValueError(f"weight must have 2 * F = {2 * F} entries, got {w.numel()}")
-    b = None if bias is None else N.f32c(bias.reshape(-1))
+    b = N.opt_f32_flat(bias)
     row, col = _edge_rows(edge_index)
     E, L, st = row.numel(), N.lib(), N.stream_ptr(dev)
     p = torch.empty(2 * max(n, 1), dtype=torch.float32, device=dev)
     raw = torch.empty(E, dtype=torch.float32, device=dev)
-    N.check(L.tgp_edge_contract_project_f32(N.ptr(x), n, F, x.stride(0) if n else F, N.ptr(w), N.ptr(p), st),
-            "tgp_edge_contract_project_f32")
-    N.check(L.tgp_edge_contract_raw_f32(N.ptr(row), N.ptr(col), E, n, N.ptr(p), N.ptr(b), N.ptr(raw), st),
-            "tgp_edge_contract_raw_f32")
+    _checked(L.tgp_edge_contract_project_f32, N.ptr(x), n, F, ld, N.ptr(w), N.ptr(p), st)
+    _checked(L.tgp_edge_contract_raw_f32, N.ptr(row), N.ptr(col), E, n, N.ptr(p), N.ptr(b), N.ptr(raw), st)
     return raw
 
 
@@ -2858,10 +2786,9 @@ def edge_contract_normalize(raw: Tensor, edge_index: Optional[Tensor], num_nodes
         seg = torch.empty(2 * max(n, 1), dtype=torch.float32, device=dev)
         cap = E // int(L.tgp_edge_contract_hub_degree()) + 1
         hubs = torch.empty(cap + 1, dtype=torch.int32, device=dev)
-    N.check(L.tgp_edge_contract_normalize_f32(N.ptr(raw), N.ptr(col), E, n, EC_METHODS[method], float(add_to_edge_score),
-                                              N.ptr(grp.row_ptr) if grp else None, N.ptr(grp.perm) if grp else None,
-                                              N.ptr(seg), N.ptr(hubs), cap, N.ptr(out), st),
-            "tgp_edge_contract_normalize_f32")
+    _checked(L.tgp_edge_contract_normalize_f32, N.ptr(raw), N.ptr(col), E, n, EC_METHODS[method],
+             float(add_to_edge_score), N.ptr(grp.row_ptr) if grp else None, N.ptr(grp.perm) if grp else None,
+             N.ptr(seg), N.ptr(hubs), cap, N.ptr(out), st)
     return out
 
 
@@ -2939,46 +2866,38 @@ def edge_contract_select(edge_index: Tensor, num_nodes: int, score: Optional[Ten
     def finish():
         relabel()
         if weight is not None:
-            N.check(L.tgp_edge_contract_weights_f32(N.ptr(medge), N.ptr(score), n, E, N.ptr(weight), st),
-                    "tgp_edge_contract_weights_f32")
+            _checked(L.tgp_edge_contract_weights_f32, N.ptr(medge), N.ptr(score), n, E, N.ptr(weight), st)
 
     res.index, res.matched, res.medge, res.weight = index, matched, medge, weight
     if want == "graphs":
         gp = N.i64c(graph_ptr)
-        N.check(L.tgp_edge_contract_graphs(N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1, int(max_graph_nodes),
-                                           N.ptr(score), N.ptr(rank), N.ptr(matched), N.ptr(label), N.ptr(medge),
-                                           N.ptr(words), st), "tgp_edge_contract_graphs")
+        _checked(L.tgp_edge_contract_graphs, N.ptr(row), N.ptr(col), E, n, N.ptr(gp), gp.numel() - 1,
+                 int(max_graph_nodes), N.ptr(score), N.ptr(rank), N.ptr(matched), N.ptr(label), N.ptr(medge),
+                 N.ptr(words), st)
         finish()
         got = words.tolist()  # the one host wait: status, rounds and K together
         if _frame_done(got[0], "tgp_edge_contract_graphs", route, "an entry"):
             res.k, res.route, res.rounds = int(got[2]), "graphs", int(got[1])
             return res
     ws = N.workspace(L.tgp_edge_contract_workspace_bytes(n), dev)
-    N.check(L.tgp_edge_contract_rounds_start(n, E, N.ptr(ws), ws.numel(), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
-            "tgp_edge_contract_rounds_start")
+    _checked(L.tgp_edge_contract_rounds_start, n, E, N.ptr(ws), ws.numel(), N.ptr(matched), N.ptr(label), N.ptr(medge),
+             st)
 
     def launch(done, step, flags):
-        N.check(L.tgp_edge_contract_rounds(N.ptr(row), N.ptr(col), E, n, N.ptr(score), N.ptr(rank), N.ptr(ws), done, step,
-                                           N.ptr(flags), N.ptr(matched), N.ptr(label), N.ptr(medge), st),
-                "tgp_edge_contract_rounds")
+        _checked(L.tgp_edge_contract_rounds, N.ptr(row), N.ptr(col), E, n, N.ptr(score), N.ptr(rank), N.ptr(ws), done,
+                 step, N.ptr(flags), N.ptr(matched), N.ptr(label), N.ptr(medge), st)
     _, live = _run_rounds(launch, n, "tgp_edge_contract_rounds", "the matching", dev)
     finish()
     res.k, res.route, res.rounds = int(words.tolist()[2]), "rounds", live
     return res
 
 
-def _rows_f32(x: Tensor) -> Tensor:
-    x = x.to(torch.float32) if x.dtype != torch.float32 else x
-    return x if x.stride(1) == 1 else x.contiguous()
-
-
 def row_dot(x: Tensor, w: Tensor) -> Tensor:
     """out[i] = <x[i,:], w> (select/topk_select.py:176) in one pass over x."""
     dev = N.require_device(x, w)
-    x, w = _rows_f32(x), N.f32c(w.reshape(-1))
+    (x, ld), w = _row_operand(x, "row_dot", convert=True), N.f32c(w.reshape(-1))
     out = torch.empty(x.size(0), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_row_dot_f32(N.ptr(x), x.size(0), x.size(1), x.stride(0), N.ptr(w), N.ptr(out),
-                                    N.stream_ptr(dev)), "tgp_row_dot_f32")
+    _checked(N.lib().tgp_row_dot_f32, N.ptr(x), x.size(0), x.size(1), ld, N.ptr(w), N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -2986,22 +2905,22 @@ def topk_score(x: Tensor, w: Tensor, tanh: bool) -> Tensor:
     """act(x.w / ||w||_2), act = tanh or identity: TopkSelect's ratio-mode score (select/topk_select.py:176-184) in
     the one pass over x (no gradient: inference and detached inputs)."""
     dev = N.require_device(x, w)
-    x, w = _rows_f32(x), N.f32c(w.reshape(-1))
+    (x, ld), w = _row_operand(x, "topk_score", convert=True), N.f32c(w.reshape(-1))
     out = torch.empty(x.size(0), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_topk_score_f32(N.ptr(x), x.size(0), x.size(1), x.stride(0), N.ptr(w), 1 if tanh else 0,
-                                       N.ptr(out), N.stream_ptr(dev)), "tgp_topk_score_f32")
+    _checked(N.lib().tgp_topk_score_f32, N.ptr(x), x.size(0), x.size(1), ld, N.ptr(w), 1 if tanh else 0, N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
 def weighted_colsum(x: Tensor, g: Tensor) -> Tensor:
     """out[f] = sum_i g[i] x[i,f]: the weight gradient of :func:`row_dot`."""
     dev = N.require_device(x, g)
-    x, g = _rows_f32(x), N.f32c(g.reshape(-1))
+    (x, ld), g = _row_operand(x, "weighted_colsum", convert=True), N.f32c(g.reshape(-1))
     out = torch.empty(x.size(1), dtype=torch.float32, device=dev)
     L = N.lib()
     ws = N.workspace(L.tgp_weighted_colsum_workspace_bytes(x.size(1)), dev)
-    N.check(L.tgp_weighted_colsum_f32(N.ptr(x), x.size(0), x.size(1), x.stride(0), N.ptr(g), N.ptr(out), N.ptr(ws),
-                                      ws.numel(), N.stream_ptr(dev)), "tgp_weighted_colsum_f32")
+    _checked(L.tgp_weighted_colsum_f32, N.ptr(x), x.size(0), x.size(1), ld, N.ptr(g), N.ptr(out), N.ptr(ws), ws.numel(),
+             N.stream_ptr(dev))
     return out
 
 
@@ -3021,10 +2940,10 @@ def topk_pool_bwd(x: Tensor, node_index: Tensor, cluster_index: Optional[Tensor]
     n, F = x.size(0), x.size(1)
     k = node_index.numel()
     ni = N.i64c(node_index)
-    ci = None if cluster_index is None else N.i64c(cluster_index)
+    ci = N.opt_i64(cluster_index)
     vals = N.f32c(values.reshape(-1))
     gp = None if g_xpool is None else N.f32c(g_xpool.reshape(k, F))
-    gv = None if g_values is None else N.f32c(g_values.reshape(-1))
+    gv = N.opt_f32_flat(g_values)
     wc = N.f32c(w.reshape(-1))
     # 16-byte loads: an upstream gradient or a parameter that is a view at an odd offset of a larger buffer (a flattened
     # parameter bucket, a slice of a concatenation) is copied once
@@ -3036,9 +2955,9 @@ def topk_pool_bwd(x: Tensor, node_index: Tensor, cluster_index: Optional[Tensor]
     gw = torch.empty(F, dtype=torch.float32, device=dev) if want_gw else None
     L = N.lib()
     ws = N.workspace(L.tgp_topk_pool_bwd_workspace_bytes(F), dev) if want_gw else None
-    N.check(L.tgp_topk_pool_bwd_f32(x.data_ptr(), n, F, x.stride(0), N.ptr(ni), N.ptr(ci), N.ptr(vals), k, N.ptr(gp),
-                                    N.ptr(gv), N.ptr(wc), 1 if use_tanh else 0, N.ptr(gx), N.ptr(gw), N.ptr(ws),
-                                    ws.numel() if ws is not None else 0, N.stream_ptr(dev)), "tgp_topk_pool_bwd_f32")
+    _checked(L.tgp_topk_pool_bwd_f32, x.data_ptr(), n, F, x.stride(0), N.ptr(ni), N.ptr(ci), N.ptr(vals), k, N.ptr(gp),
+             N.ptr(gv), N.ptr(wc), 1 if use_tanh else 0, N.ptr(gx), N.ptr(gw), N.ptr(ws),
+             ws.numel() if ws is not None else 0, N.stream_ptr(dev))
     return gx, gw
 
 
@@ -3049,8 +2968,8 @@ def pair_dot(a: Tensor, ia: Tensor, b: Tensor, ib: Tensor) -> Tensor:
     if a.dim() != 2 or b.dim() != 2 or a.size(1) != b.size(1) or ia.numel() != ib.numel():
         raise ValueError(f"pair_dot: a {tuple(a.shape)}, b {tuple(b.shape)}, {ia.numel()} / {ib.numel()} indices")
     out = torch.empty(ia.numel(), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_pair_dot_f32(N.ptr(ia), N.ptr(ib), ia.numel(), N.ptr(a), N.ptr(b), a.size(1), N.ptr(out),
-                                     N.stream_ptr(dev)), "tgp_pair_dot_f32")
+    _checked(N.lib().tgp_pair_dot_f32, N.ptr(ia), N.ptr(ib), ia.numel(), N.ptr(a), N.ptr(b), a.size(1), N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
@@ -3062,8 +2981,8 @@ def edge_dot(s: Tensor, edge_index: Tensor) -> Tensor:
         return (s[row] * s[col]).sum(-1)
     s = N.f32c(s)
     out = torch.empty(row.numel(), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_edge_dot_f32(N.ptr(row), N.ptr(col), row.numel(), N.ptr(s), s.size(0), s.size(1), N.ptr(out),
-                                     N.stream_ptr(dev)), "tgp_edge_dot_f32")
+    _checked(N.lib().tgp_edge_dot_f32, N.ptr(row), N.ptr(col), row.numel(), N.ptr(s), s.size(0), s.size(1), N.ptr(out),
+             N.stream_ptr(dev))
     return out
 
 
@@ -3087,27 +3006,21 @@ def bmm(a: Tensor, b: Tensor, trans_a: bool = False, accumulate_into: Optional[T
     Nc = b3.size(2)
     sA = 0 if a3.size(0) == 1 else a3.stride(0)
     sB = 0 if b3.size(0) == 1 else b3.stride(0)
-    if accumulate_into is not None:
+    acc = accumulate_into is not None
+    if acc:
         out = accumulate_into
         if (out.dtype != dt or not out.is_contiguous() or out.numel() != G * M * Nc or out.device != dev):
             raise ValueError(f"bmm: accumulate_into must be a contiguous {dt} tensor of the product's shape")
-        if f64:
-            N.check(N.lib().tgp_bmm_f64(N.ptr(a3), N.ptr(b3), N.ptr(out), G, M, Nc, Kd, 1 if trans_a else 0,
-                                        a3.stride(1), b3.stride(1), Nc, sA, sB, M * Nc, 1, N.stream_ptr(dev)),
-                    "tgp_bmm_f64")
-            return out
-        N.check(N.lib().tgp_bmm_accumulate_f32(N.ptr(a3), N.ptr(b3), N.ptr(out), G, M, Nc, Kd, 1 if trans_a else 0,
-                                               a3.stride(1), b3.stride(1), Nc, sA, sB, M * Nc, N.stream_ptr(dev)),
-                "tgp_bmm_accumulate_f32")
-        return out
-    out = torch.empty(G, M, Nc, dtype=dt, device=dev)
-    if f64:
-        N.check(N.lib().tgp_bmm_f64(N.ptr(a3), N.ptr(b3), N.ptr(out), G, M, Nc, Kd, 1 if trans_a else 0, a3.stride(1),
-                                    b3.stride(1), Nc, sA, sB, M * Nc, 0, N.stream_ptr(dev)), "tgp_bmm_f64")
     else:
-        N.check(N.lib().tgp_bmm_f32(N.ptr(a3), N.ptr(b3), N.ptr(out), G, M, Nc, Kd, 1 if trans_a else 0, a3.stride(1),
-                                    b3.stride(1), Nc, sA, sB, M * Nc, N.stream_ptr(dev)), "tgp_bmm_f32")
-    return out if (a.dim() == 3 or b.dim() == 3) else out[0]
+        out = torch.empty(G, M, Nc, dtype=dt, device=dev)
+    L = N.lib()
+    args = (N.ptr(a3), N.ptr(b3), N.ptr(out), G, M, Nc, Kd, 1 if trans_a else 0, a3.stride(1), b3.stride(1), Nc, sA, sB,
+            M * Nc)
+    if f64:  # (one float64 entry: accumulation is a flag of it)
+        _checked(L.tgp_bmm_f64, *args, 1 if acc else 0, N.stream_ptr(dev))
+    else:
+        _checked(L.tgp_bmm_accumulate_f32 if acc else L.tgp_bmm_f32, *args, N.stream_ptr(dev))
+    return out if (acc or a.dim() == 3 or b.dim() == 3) else out[0]
 
 
 # ------------------------------------------------------------------------- A13
@@ -3117,7 +3030,7 @@ def mlp_select(x: Tensor, weight: Tensor, bias: Optional[Tensor], mask: Optional
     dev = N.require_device(x, weight)
     lead = x.shape[:-1]
     x2 = N.f32c(x).reshape(-1, x.size(-1))
-    w, b = N.f32c(weight), (None if bias is None else N.f32c(bias))
+    w, b = N.f32c(weight), N.opt_f32(bias)
     M, F, Kc = x2.size(0), x2.size(1), w.size(0)
     if w.size(1) != F:
         raise ValueError(f"mlp_select: weight {tuple(weight.shape)} does not match features {F}")
@@ -3133,11 +3046,10 @@ def mlp_select(x: Tensor, weight: Tensor, bias: Optional[Tensor], mask: Optional
     st = N.stream_ptr(dev)
     if Kc <= L.tgp_mlp_select_max_fused_k():
         out = torch.empty(M, Kc, dtype=torch.float32, device=dev)
-        N.check(L.tgp_mlp_select_f32(N.ptr(x2), N.ptr(w), N.ptr(b), N.ptr(m8), M, F, Kc, N.ptr(out), st),
-                "tgp_mlp_select_f32")
+        _checked(L.tgp_mlp_select_f32, N.ptr(x2), N.ptr(w), N.ptr(b), N.ptr(m8), M, F, Kc, N.ptr(out), st)
     else:  # wider than eight accumulator tiles: tiled GEMM for the logits, then bias + softmax + mask in place
         out = bmm(x2, w.t().contiguous())
-        N.check(L.tgp_softmax_rows_f32(N.ptr(out), N.ptr(b), N.ptr(m8), M, Kc, st), "tgp_softmax_rows_f32")
+        _checked(L.tgp_softmax_rows_f32, N.ptr(out), N.ptr(b), N.ptr(m8), M, Kc, st)
     return out.view(*lead, Kc)
 
 
@@ -3146,8 +3058,7 @@ def softmax_bwd(s: Tensor, ds: Tensor) -> Tensor:
     dev = N.require_device(s, ds)
     s2, d2 = N.f32c(s).reshape(-1, s.size(-1)), N.f32c(ds).reshape(-1, s.size(-1))
     out = torch.empty_like(s2)
-    N.check(N.lib().tgp_softmax_bwd_f32(N.ptr(s2), N.ptr(d2), N.ptr(out), s2.size(0), s2.size(1),
-                                        N.stream_ptr(dev)), "tgp_softmax_bwd_f32")
+    _checked(N.lib().tgp_softmax_bwd_f32, N.ptr(s2), N.ptr(d2), N.ptr(out), s2.size(0), s2.size(1), N.stream_ptr(dev))
     return out.view(s.shape)
 
 
@@ -3155,24 +3066,17 @@ def segment_gemm_tn(s: Tensor, y: Tensor, ptr: Tensor, max_nodes: int) -> Tensor
     """C[b] = S_b^T Y_b over node rows ptr[b]..ptr[b+1] (reduce/base_reduce.py:170-182,
     connect/dense_conn.py:195-206) in one launch."""
     dev = N.require_device(s, y, ptr)
-    if _any_f64(s, y):
-        s, y, ptr = N.f64c(s), N.f64c(y), N.i64c(ptr)
-        B = ptr.numel() - 1
-        K, F = s.size(1), y.size(1)
-        out = torch.empty(B, K, F, dtype=torch.float64, device=dev)
-        L = N.lib()
-        ws = N.workspace(L.tgp_segment_gemm_tn_workspace_bytes_f64(B, K, F, max_nodes), dev)
-        N.check(L.tgp_segment_gemm_tn_f64(N.ptr(s), N.ptr(y), N.ptr(ptr), N.ptr(out), B, s.size(0), K, F, max_nodes,
-                                          N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "tgp_segment_gemm_tn_f64")
-        return out
-    s, y, ptr = N.f32c(s), N.f32c(y), N.i64c(ptr)
+    f64 = _any_f64(s, y)
+    conv = N.f64c if f64 else N.f32c
+    s, y, ptr = conv(s), conv(y), N.i64c(ptr)
     B = ptr.numel() - 1
     K, F = s.size(1), y.size(1)
-    out = torch.empty(B, K, F, dtype=torch.float32, device=dev)
+    out = torch.empty(B, K, F, dtype=s.dtype, device=dev)
     L = N.lib()
-    ws = N.workspace(L.tgp_segment_gemm_tn_workspace_bytes(B, K, F, max_nodes), dev)
-    N.check(L.tgp_segment_gemm_tn_f32(N.ptr(s), N.ptr(y), N.ptr(ptr), N.ptr(out), B, s.size(0), K, F,
-                                      max_nodes, N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "tgp_segment_gemm_tn_f32")
+    ws = N.workspace((L.tgp_segment_gemm_tn_workspace_bytes_f64 if f64 else L.tgp_segment_gemm_tn_workspace_bytes)(
+        B, K, F, max_nodes), dev)
+    _checked(L.tgp_segment_gemm_tn_f64 if f64 else L.tgp_segment_gemm_tn_f32, N.ptr(s), N.ptr(y), N.ptr(ptr),
+             N.ptr(out), B, s.size(0), K, F, max_nodes, N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return out
 
 
@@ -3186,14 +3090,10 @@ def segment_gemm_nn(a: Tensor, bm: Tensor, ptr: Tensor, max_nodes: int) -> Tenso
     B = ptr.numel() - 1
     if bm.dim() != 3 or bm.size(0) != B or bm.size(1) != a.size(1):
         raise ValueError(f"segment_gemm_nn: a {tuple(a.shape)} x bm {tuple(bm.shape)} with {B} graphs")
-    if f64:
-        out = torch.empty(a.size(0), bm.size(2), dtype=torch.float64, device=dev)
-        N.check(N.lib().tgp_segment_gemm_nn_f64(N.ptr(a), N.ptr(bm), N.ptr(ptr), N.ptr(out), B, a.size(0), a.size(1),
-                                                bm.size(2), max_nodes, N.stream_ptr(dev)), "tgp_segment_gemm_nn_f64")
-        return out
-    out = torch.empty(a.size(0), bm.size(2), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_segment_gemm_nn_f32(N.ptr(a), N.ptr(bm), N.ptr(ptr), N.ptr(out), B, a.size(0), a.size(1),
-                                            bm.size(2), max_nodes, N.stream_ptr(dev)), "tgp_segment_gemm_nn_f32")
+    out = torch.empty(a.size(0), bm.size(2), dtype=a.dtype, device=dev)
+    L = N.lib()
+    _checked(L.tgp_segment_gemm_nn_f64 if f64 else L.tgp_segment_gemm_nn_f32, N.ptr(a), N.ptr(bm), N.ptr(ptr),
+             N.ptr(out), B, a.size(0), a.size(1), bm.size(2), max_nodes, N.stream_ptr(dev))
     return out
 
 
@@ -3201,50 +3101,36 @@ def rowptr_from_sorted(row: Tensor, num_rows: int, out: Tensor) -> Tensor:
     """CSR offsets (int32 [num_rows+1]) of an ascending int64 row vector."""
     dev = N.require_device(row, out)
     row = N.i64c(row)
-    N.check(N.lib().tgp_rowptr_from_sorted_i64(N.ptr(row), row.numel(), num_rows, N.ptr(out), N.stream_ptr(dev)),
-            "tgp_rowptr_from_sorted_i64")
+    _checked(N.lib().tgp_rowptr_from_sorted_i64, N.ptr(row), row.numel(), num_rows, N.ptr(out), N.stream_ptr(dev))
     return out
 
 
-def spmm_sorted(edge_index: Tensor, edge_weight: Optional[Tensor], num_rows: int, s: Tensor) -> Tensor:
-    """T = A S for a row-sorted (coalesced) edge list (connect/dense_conn.py:165,204)."""
+def _spmm_sorted(edge_index: Tensor, edge_weight: Optional[Tensor], num_rows: int, s: Tensor, f64: bool):
+    """(T, row_ptr int32 [num_rows+1]): T = A S for a row-sorted (coalesced) edge list and the CSR offsets built on the
+    way, the operands taken as float32 or -- ``f64`` -- as float64."""
     dev = N.require_device(edge_index, edge_weight, s)
     row, col = _edge_rows(edge_index)
-    f64 = _any_f64(s, edge_weight)
     conv = N.f64c if f64 else N.f32c
     s = conv(s)
     w = None if edge_weight is None else conv(edge_weight)
     L = N.lib()
     st = N.stream_ptr(dev)
     row_ptr = torch.empty(num_rows + 1, dtype=torch.int32, device=dev)
-    N.check(L.tgp_rowptr_from_sorted_i64(N.ptr(row), row.numel(), num_rows, N.ptr(row_ptr), st),
-            "tgp_rowptr_from_sorted_i64")
-    if f64:
-        out = torch.empty(num_rows, s.size(1), dtype=torch.float64, device=dev)
-        N.check(L.tgp_spmm_csr_f64(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, row.numel(), N.ptr(s), s.size(1),
-                                   N.ptr(out), st), "tgp_spmm_csr_f64")
-        return out
-    out = torch.empty(num_rows, s.size(1), dtype=torch.float32, device=dev)
-    N.check(L.tgp_spmm_csr_f32(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, row.numel(), N.ptr(s), s.size(1),
-                               N.ptr(out), st), "tgp_spmm_csr_f32")
-    return out
+    _checked(L.tgp_rowptr_from_sorted_i64, N.ptr(row), row.numel(), num_rows, N.ptr(row_ptr), st)
+    out = torch.empty(num_rows, s.size(1), dtype=s.dtype, device=dev)
+    _checked(L.tgp_spmm_csr_f64 if f64 else L.tgp_spmm_csr_f32, N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows,
+             row.numel(), N.ptr(s), s.size(1), N.ptr(out), st)
+    return out, row_ptr
 
 
 def spmm_sorted_csr(edge_index: Tensor, edge_weight: Optional[Tensor], num_rows: int, s: Tensor):
     """(T, row_ptr int32 [num_rows+1]): :func:`spmm_sorted` for float32 operands, handing the CSR offsets it built back."""
-    dev = N.require_device(edge_index, edge_weight, s)
-    row, col = _edge_rows(edge_index)
-    s = N.f32c(s)
-    w = None if edge_weight is None else N.f32c(edge_weight)
-    L = N.lib()
-    st = N.stream_ptr(dev)
-    row_ptr = torch.empty(num_rows + 1, dtype=torch.int32, device=dev)
-    N.check(L.tgp_rowptr_from_sorted_i64(N.ptr(row), row.numel(), num_rows, N.ptr(row_ptr), st),
-            "tgp_rowptr_from_sorted_i64")
-    out = torch.empty(num_rows, s.size(1), dtype=torch.float32, device=dev)
-    N.check(L.tgp_spmm_csr_f32(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, row.numel(), N.ptr(s), s.size(1),
-                               N.ptr(out), st), "tgp_spmm_csr_f32")
-    return out, row_ptr
+    return _spmm_sorted(edge_index, edge_weight, num_rows, s, False)
+
+
+def spmm_sorted(edge_index: Tensor, edge_weight: Optional[Tensor], num_rows: int, s: Tensor) -> Tensor:
+    """T = A S for a row-sorted (coalesced) edge list (connect/dense_conn.py:165,204), in float64 when S or a weight is."""
+    return _spmm_sorted(edge_index, edge_weight, num_rows, s, _any_f64(s, edge_weight))[0]
 
 
 _ROW_OFFSETS = TensorMemo(16)
@@ -3272,30 +3158,28 @@ def spmm_csr(row_ptr: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor],
     dev = N.require_device(edge_index, edge_weight, s, row_ptr)
     _, col = _edge_rows(edge_index)
     s = N.f32c(s)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     out = torch.empty(num_rows, s.size(1), dtype=torch.float32, device=dev)
     if want_stats == "entropy":
         # (T, partials or None): DiffPool's entropy sum over S rides along as per-workgroup shares (None: this shape does
         # not take the row kernel; diffpool_unbatched_tail then runs its own pass over S)
         if s.size(0) != num_rows:
             raise ValueError("spmm_csr(want_stats='entropy') needs a square A: one row of S per row of A")
-        import ctypes as _ct
         part = torch.empty(max(num_rows, 1), dtype=torch.float32, device=dev)
-        n_part = _ct.c_int(-1)
-        N.check(N.lib().tgp_spmm_csr_entropy_f32(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(), N.ptr(s),
-                                                  s.size(1), N.ptr(out), losses_eps(), N.ptr(part),
-                                                  _ct.addressof(n_part), N.stream_ptr(dev)), "tgp_spmm_csr_entropy_f32")
+        n_part = ctypes.c_int(-1)
+        _checked(N.lib().tgp_spmm_csr_entropy_f32, N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(),
+                 N.ptr(s), s.size(1), N.ptr(out), losses_eps(), N.ptr(part), ctypes.addressof(n_part),
+                 N.stream_ptr(dev))
         return out, (part[: n_part.value] if n_part.value >= 0 else None)
     if want_stats:
         if s.size(0) != num_rows:
             raise ValueError("spmm_csr(want_stats=True) needs a square A: one row of S per row of A")
         dq = torch.empty(2, num_rows, dtype=torch.float32, device=dev)
-        N.check(N.lib().tgp_spmm_csr_stats_f32(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(), N.ptr(s),
-                                               s.size(1), N.ptr(out), dq.data_ptr(), dq.data_ptr() + 4 * num_rows,
-                                               N.stream_ptr(dev)), "tgp_spmm_csr_stats_f32")
+        _checked(N.lib().tgp_spmm_csr_stats_f32, N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(), N.ptr(s),
+                 s.size(1), N.ptr(out), dq.data_ptr(), dq.data_ptr() + 4 * num_rows, N.stream_ptr(dev))
         return out, dq[0], dq[1]
-    N.check(N.lib().tgp_spmm_csr_f32(N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(), N.ptr(s), s.size(1),
-                                     N.ptr(out), N.stream_ptr(dev)), "tgp_spmm_csr_f32")
+    _checked(N.lib().tgp_spmm_csr_f32, N.ptr(row_ptr), N.ptr(col), N.ptr(w), num_rows, col.numel(), N.ptr(s), s.size(1),
+             N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -3305,11 +3189,11 @@ def edge_row_stats(row_ptr: Tensor, edge_weight: Optional[Tensor], s: Tensor) ->
     dev = N.require_device(row_ptr, edge_weight, s)
     s = N.f32c(s)
     n = s.size(0)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     deg = torch.empty(n, dtype=torch.float32, device=dev)
     q = torch.empty(n, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_edge_row_stats_f32(N.ptr(row_ptr), N.ptr(w), N.ptr(s), n, s.size(1), N.ptr(deg), N.ptr(q),
-                                           N.stream_ptr(dev)), "tgp_edge_row_stats_f32")
+    _checked(N.lib().tgp_edge_row_stats_f32, N.ptr(row_ptr), N.ptr(w), N.ptr(s), n, s.size(1), N.ptr(deg), N.ptr(q),
+             N.stream_ptr(dev))
     return deg, q
 
 
@@ -3336,16 +3220,14 @@ def segment_gemm_tn3(s: Tensor, ys, ptr: Tensor, max_nodes: int, transpose0: boo
             raise ValueError("segment_gemm_tn3(post_flags=...): the first right-hand side must be [Ntot,K]")
         adj_pool = torch.empty(B, Kc, Kc, dtype=torch.float32, device=dev)
         ws = N.workspace(L.tgp_segment_gemm_tn3_post_workspace_bytes(B, Kc, fs[1], fs[2], max_nodes), dev)
-        N.check(L.tgp_segment_gemm_tn3_post_f32(N.ptr(s), yp[0], yp[1], fs[1], yp[2], fs[2], N.ptr(ptr), op[0], op[1],
-                                                op[2], N.ptr(adj_pool), B, s.size(0), Kc, max_nodes,
-                                                1 if transpose0 else 0, int(post_flags), ops_eps(), N.ptr(ws),
-                                                ws.numel(), N.stream_ptr(dev)), "tgp_segment_gemm_tn3_post_f32")
+        _checked(L.tgp_segment_gemm_tn3_post_f32, N.ptr(s), yp[0], yp[1], fs[1], yp[2], fs[2], N.ptr(ptr), op[0], op[1],
+                 op[2], N.ptr(adj_pool), B, s.size(0), Kc, max_nodes, 1 if transpose0 else 0, int(post_flags),
+                 ops_eps(), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
         return outs + [adj_pool]
     ws = N.workspace(L.tgp_segment_gemm_tn3_workspace_bytes(B, Kc, fs[0], fs[1], fs[2], max_nodes), dev)
     # transpose0: the first result (K x K) leaves the combine launch transposed
-    N.check(L.tgp_segment_gemm_tn3_f32(N.ptr(s), yp[0], fs[0], yp[1], fs[1], yp[2], fs[2], N.ptr(ptr), op[0], op[1], op[2],
-                                       B, s.size(0), Kc, max_nodes, 1 if transpose0 else 0, N.ptr(ws), ws.numel(),
-                                       N.stream_ptr(dev)), "tgp_segment_gemm_tn3_f32")
+    _checked(L.tgp_segment_gemm_tn3_f32, N.ptr(s), yp[0], fs[0], yp[1], fs[1], yp[2], fs[2], N.ptr(ptr), op[0], op[1],
+             op[2], B, s.size(0), Kc, max_nodes, 1 if transpose0 else 0, N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return outs
 
 
@@ -3412,14 +3294,13 @@ def pool_rows_forward(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor
         dstats, out2 = torch.empty(B, 2, **f32), torch.empty(2, **f32)
         sw2_dev = N.f32c(sw2.reshape(1)) if isinstance(sw2, Tensor) else None
     ws = N.workspace(L.tgp_pool_rows_fwd_workspace_bytes(B, Kc, F, max_nodes, n), dev)
-    N.check(L.tgp_pool_rows_fwd_f32(
-        x.data_ptr(), n, F, N.ptr(weight) if selector else None, N.ptr(bias) if selector else None, s.data_ptr(),
-        row_ptr.data_ptr(), N.ptr(col), N.ptr(w), col.numel(), ptr.data_ptr(), B, Kc, max_nodes, 1 if transposed else 0,
-        int(flags), ops_eps(), losses_eps(), int(mode), N.ptr(sw2_dev),
-        0.0 if (sw2_dev is not None or mode != 2) else float(sw2), float(scales[0]), float(scales[1]), t.data_ptr(),
-        raw.data_ptr(), x_pool.data_ptr(), N.ptr(gram), adj_pool.data_ptr(), N.ptr(rowstat), N.ptr(den), N.ptr(terms),
-        N.ptr(stats), N.ptr(means), ticket, N.ptr(dstats), N.ptr(out2), ws.data_ptr(), ws.numel(), st),
-        "tgp_pool_rows_fwd_f32")
+    _checked(L.tgp_pool_rows_fwd_f32, x.data_ptr(), n, F, N.ptr(weight) if selector else None,
+             N.ptr(bias) if selector else None, s.data_ptr(), row_ptr.data_ptr(), N.ptr(col), N.ptr(w), col.numel(),
+             ptr.data_ptr(), B, Kc, max_nodes, 1 if transposed else 0, int(flags), ops_eps(), losses_eps(), int(mode),
+             N.ptr(sw2_dev), 0.0 if (sw2_dev is not None or mode != 2) else float(sw2), float(scales[0]),
+             float(scales[1]), t.data_ptr(), raw.data_ptr(), x_pool.data_ptr(), N.ptr(gram), adj_pool.data_ptr(),
+             N.ptr(rowstat), N.ptr(den), N.ptr(terms), N.ptr(stats), N.ptr(means), ticket, N.ptr(dstats), N.ptr(out2),
+             ws.data_ptr(), ws.numel(), st)
     out = dict(s=s, t=t, raw=raw, x_pool=x_pool, gram=gram, adj_pool=adj_pool)
     if mode == 1:
         out.update(deg=rowstat[0], q=rowstat[1], den=den, terms=terms, stats=stats,
@@ -3474,14 +3355,14 @@ def pool_rows_backward(s: Tensor, t: Tensor, x: Tensor, weight: Tensor, raw: Ten
     part = torch.empty(slabs, Kc, F + pad, **e) if (want_gw or want_gb) else None
     gw = torch.empty(Kc, F, **e) if want_gw else None
     gb = torch.empty(Kc, **e) if want_gb else None
-    N.check(N.lib().tgp_pool_rows_bwd_f32(
-        s.data_ptr(), t.data_ptr(), x.data_ptr(), weight.data_ptr(), raw.data_ptr(), N.ptr(gram), N.ptr(stats), N.ptr(den),
-        N.ptr(deg), N.ptr(lossv), ptr.data_ptr(), N.ptr(batch), slab_ptr.data_ptr(), slabs, n, B, Kc, F, max_nodes,
-        int(flags), ops_eps(), losses_eps(), int(mode), 1 if transposed else 0, 1.0 / B,
-        float(scales[0]) if mode == 2 else 0.0, float(scales[1]) if mode == 2 else 0.0, N.ptr(g_adj), 1 if ga_bc else 0,
-        N.ptr(g_raw), N.ptr(g_xp), 1 if gx_bc else 0, N.ptr(g_s), N.ptr(g_la), N.ptr(g_lb), N.ptr(ga), rcat.data_ptr(),
-        N.ptr(c1), N.ptr(gwcat), acat.data_ptr(), gs.data_ptr(), N.ptr(gx), N.ptr(part), N.ptr(gw), N.ptr(gb),
-        N.stream_ptr(dev)), "tgp_pool_rows_bwd_f32")
+    _checked(N.lib().tgp_pool_rows_bwd_f32, s.data_ptr(), t.data_ptr(), x.data_ptr(), weight.data_ptr(), raw.data_ptr(),
+             N.ptr(gram), N.ptr(stats), N.ptr(den), N.ptr(deg), N.ptr(lossv), ptr.data_ptr(), N.ptr(batch),
+             slab_ptr.data_ptr(), slabs, n, B, Kc, F, max_nodes, int(flags), ops_eps(), losses_eps(), int(mode),
+             1 if transposed else 0, 1.0 / B, float(scales[0]) if mode == 2 else 0.0,
+             float(scales[1]) if mode == 2 else 0.0, N.ptr(g_adj), 1 if ga_bc else 0, N.ptr(g_raw), N.ptr(g_xp),
+             1 if gx_bc else 0, N.ptr(g_s), N.ptr(g_la), N.ptr(g_lb), N.ptr(ga), rcat.data_ptr(), N.ptr(c1),
+             N.ptr(gwcat), acat.data_ptr(), gs.data_ptr(), N.ptr(gx), N.ptr(part), N.ptr(gw), N.ptr(gb),
+             N.stream_ptr(dev))
     return gx, gw, gb
 
 
@@ -3494,10 +3375,9 @@ def segment_gemm_nn_into(a: Tensor, bm: Tensor, ptr: Tensor, out: Tensor, max_no
             or any(t.dtype != torch.float32 for t in (a, bm, out))):
         raise ValueError(f"segment_gemm_nn_into: {tuple(a.shape)} x {tuple(bm.shape)} -> {tuple(out.shape)}")
     ptr = N.i64c(ptr)
-    N.check(N.lib().tgp_segment_gemm_nn_ld_f32(a.data_ptr(), a.stride(0), bm.data_ptr(), bm.stride(1), bm.stride(0),
-                                               N.ptr(ptr), out.data_ptr(), out.stride(0), ptr.numel() - 1, a.size(0),
-                                               a.size(1), bm.size(2), max_nodes, N.stream_ptr(dev)),
-            "tgp_segment_gemm_nn_ld_f32")
+    _checked(N.lib().tgp_segment_gemm_nn_ld_f32, a.data_ptr(), a.stride(0), bm.data_ptr(), bm.stride(1), bm.stride(0),
+             N.ptr(ptr), out.data_ptr(), out.stride(0), ptr.numel() - 1, a.size(0), a.size(1), bm.size(2), max_nodes,
+             N.stream_ptr(dev))
     return out
 
 
@@ -3511,9 +3391,8 @@ def segment_gemm_tn_into(a: Tensor, y: Tensor, ptr: Tensor) -> Tensor:
     ptr = N.i64c(ptr)
     B = ptr.numel() - 1
     out = torch.empty(B, a.size(1), y.size(1), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_segment_gemm_tn_ld_f32(a.data_ptr(), a.stride(0), y.data_ptr(), y.stride(0), N.ptr(ptr),
-                                               N.ptr(out), B, a.size(0), a.size(1), y.size(1), N.stream_ptr(dev)),
-            "tgp_segment_gemm_tn_ld_f32")
+    _checked(N.lib().tgp_segment_gemm_tn_ld_f32, a.data_ptr(), a.stride(0), y.data_ptr(), y.stride(0), N.ptr(ptr),
+             N.ptr(out), B, a.size(0), a.size(1), y.size(1), N.stream_ptr(dev))
     return out
 
 
@@ -3526,25 +3405,18 @@ def diffpool_unbatched_tail(raw: Tensor, gram: Tensor, s: Tensor, sw2, link_scal
     dev = N.require_device(raw, gram, s, ent_partials)
     raw, gram = N.f32c(raw), N.f32c(gram)
     B, Kc = raw.size(0), raw.size(-1)
-    L = N.lib()
     st = N.stream_ptr(dev)
-    import ctypes as _ct
-    n_partial = _ct.c_int(0)
     if ent_partials is not None:
         ws = N.f32c(ent_partials.reshape(-1))
-        n_partial.value = ws.numel()
+        n_partial = ws.numel()
     else:
-        s32 = N.f32c(s)
-        ws = N.workspace(L.tgp_entropy_sum_workspace_bytes(s32.numel()), dev)
-        N.check(L.tgp_entropy_partials_f32(N.ptr(s32), s32.numel(), losses_eps(), N.ptr(ws), ws.numel(),
-                                           _ct.addressof(n_partial), st), "tgp_entropy_partials_f32")
+        ws, n_partial = _entropy_partials(s, dev, st)
     stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
     sw2_dev = N.f32c(sw2.reshape(1)) if isinstance(sw2, Tensor) else None
-    N.check(L.tgp_diffpool_unbatched_tail_f32(N.ptr(raw), N.ptr(gram), B, Kc, N.ptr(sw2_dev),
-                                              0.0 if sw2_dev is not None else float(sw2), N.ptr(ws), n_partial.value,
-                                              float(link_scale), float(ent_scale), N.ptr(stats), N.ptr(out), st),
-            "tgp_diffpool_unbatched_tail_f32")
+    _checked(N.lib().tgp_diffpool_unbatched_tail_f32, N.ptr(raw), N.ptr(gram), B, Kc, N.ptr(sw2_dev),
+             0.0 if sw2_dev is not None else float(sw2), N.ptr(ws), n_partial, float(link_scale),
+             float(ent_scale), N.ptr(stats), N.ptr(out), st)
     return out
 
 
@@ -3559,11 +3431,11 @@ def ndp_symmetric_max(edge_index: Tensor, weight: Optional[Tensor], num_nodes: i
     flag = 1 when the list is anything else (ndp_select.py:198-202 then needs the general route)."""
     dev = N.require_device(edge_index, weight, indptr)
     row, col = _edge_rows(edge_index)
-    w = None if weight is None else N.f32c(weight.reshape(-1))
+    w = N.opt_f32_flat(weight)
     out = torch.empty(row.numel(), dtype=torch.float32, device=dev)
     flag = torch.empty(1, dtype=torch.int32, device=dev)
-    N.check(N.lib().tgp_ndp_symmetric_max_f32(N.ptr(row), N.ptr(col), N.ptr(w), row.numel(), num_nodes, N.ptr(indptr),
-                                              N.ptr(out), N.ptr(flag), N.stream_ptr(dev)), "tgp_ndp_symmetric_max_f32")
+    _checked(N.lib().tgp_ndp_symmetric_max_f32, N.ptr(row), N.ptr(col), N.ptr(w), row.numel(), num_nodes, N.ptr(indptr),
+             N.ptr(out), N.ptr(flag), N.stream_ptr(dev))
     return out, flag
 
 
@@ -3577,7 +3449,7 @@ def ndp_partition(indptr: Tensor, col: Tensor, weight: Optional[Tensor], num_nod
     if indptr.dtype != torch.int32:
         raise ValueError("ndp_partition: indptr must be int32")
     col, graph_ptr = N.i64c(col), N.i64c(graph_ptr)
-    w = None if weight is None else N.f32c(weight.reshape(-1))
+    w = N.opt_f32_flat(weight)
     B = graph_ptr.numel() - 1
     # status | info | keep in one allocation, laid out as tgp_ndp_partition clears them with a single memset (r6)
     b_pad, n_keep = (max(B, 1) + 3) // 4 * 4, max(num_nodes, 1)
@@ -3585,10 +3457,9 @@ def ndp_partition(indptr: Tensor, col: Tensor, weight: Optional[Tensor], num_nod
     status = buf[:4].view(torch.int32)
     info = buf[16:16 + 4 * b_pad].view(torch.int32)
     keep = buf[16 + 4 * b_pad:]
-    N.check(N.lib().tgp_ndp_partition(N.ptr(indptr.contiguous()), N.ptr(col), N.ptr(w), num_nodes, col.numel(),
-                                      N.ptr(graph_ptr), B, max_graph_nodes, int(seed) & ((1 << 64) - 1), max_iter,
-                                      float(tol), N.ptr(keep), N.ptr(info), N.ptr(status), N.stream_ptr(dev)),
-            "tgp_ndp_partition")
+    _checked(N.lib().tgp_ndp_partition, N.ptr(indptr.contiguous()), N.ptr(col), N.ptr(w), num_nodes, col.numel(),
+             N.ptr(graph_ptr), B, max_graph_nodes, int(seed) & ((1 << 64) - 1), max_iter, float(tol), N.ptr(keep),
+             N.ptr(info), N.ptr(status), N.stream_ptr(dev))
     return (keep[:num_nodes] if raw_keep else keep[:num_nodes].bool()), info[:B], status
 
 
@@ -3621,8 +3492,7 @@ def mask_index(mask: Tensor, declined: Optional[Tensor] = None, want_rank: bool 
         scratch = torch.zeros(max(words, 1024), dtype=torch.int32, device=dev)
         _MASK_INDEX_SCRATCH[key] = scratch
     call = _sps_state(dev, st, 0).open_call()
-    N.check(L.tgp_mask_index_count(N.ptr(mask), n, N.ptr(declined), N.ptr(scratch), *call.publish, st),
-            "tgp_mask_index_count")
+    _checked(L.tgp_mask_index_count, N.ptr(mask), n, N.ptr(declined), N.ptr(scratch), *call.publish, st)
     k = call.count()
     if k < 0:
         return None
@@ -3634,9 +3504,9 @@ def mask_index(mask: Tensor, declined: Optional[Tensor] = None, want_rank: bool 
     pack = torch.empty(k, dtype=torch.int64, device=dev) if assign else None
     node_rank = torch.empty(n + 1, dtype=torch.int32, device=dev) if want_node_rank and n else None
     if k or node_rank is not None:
-        N.check(L.tgp_mask_index_fill(N.ptr(mask), n, N.ptr(scratch), k, N.ptr(index) if k else None,
-                                      index.data_ptr() + 8 * k if want_rank and k else None, N.ptr(ones) if k else None,
-                                      N.ptr(perm), N.ptr(pack), N.ptr(node_rank), st), "tgp_mask_index_fill")
+        _checked(L.tgp_mask_index_fill, N.ptr(mask), n, N.ptr(scratch), k, N.ptr(index) if k else None,
+                 index.data_ptr() + 8 * k if want_rank and k else None, N.ptr(ones) if k else None, N.ptr(perm),
+                 N.ptr(pack), N.ptr(node_rank), st)
     out = (index, ones)
     if want_assign:
         a_index = None
@@ -3660,28 +3530,26 @@ def ndp_partition_large(indptr: Tensor, col: Tensor, weight: Optional[Tensor], p
     if indptr.dtype != torch.int32 or keep.dtype != torch.uint8 or status.dtype != torch.int32:
         raise ValueError("ndp_partition_large: indptr / status must be int32, keep uint8")
     col = N.i64c(col)
-    w = None if weight is None else N.f32c(weight.reshape(-1))
+    w = N.opt_f32_flat(weight)
     L = N.lib()
     n = p1 - p0
     ws = N.workspace(L.tgp_ndp_large_workspace_bytes(n), dev)
     st = N.stream_ptr(dev)
-    N.check(L.tgp_ndp_large_start(N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, max_iter, N.ptr(ws), ws.numel(),
-                                  N.ptr(status), st), "tgp_ndp_large_start")
+    _checked(L.tgp_ndp_large_start, N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, max_iter, N.ptr(ws), ws.numel(),
+             N.ptr(status), st)
     progress = torch.zeros(2, dtype=torch.int32, device=dev)
     done = False
     while not done:
-        N.check(L.tgp_ndp_large_steps(N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, steps_per_batch, float(tol),
-                                      N.ptr(ws), ws.numel(), N.ptr(progress), N.ptr(status), st),
-                "tgp_ndp_large_steps")
+        _checked(L.tgp_ndp_large_steps, N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, steps_per_batch, float(tol),
+                 N.ptr(ws), ws.numel(), N.ptr(progress), N.ptr(status), st)
         flag, it = progress.tolist()  # one round trip per batch of steps
         done = flag != 0 or it >= max_iter
     info = torch.zeros(1, dtype=torch.int32, device=dev)
-    N.check(L.tgp_ndp_large_finish(N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, int(seed) & ((1 << 64) - 1),
-                                   N.ptr(ws), ws.numel(), N.ptr(keep), N.ptr(info), st), "tgp_ndp_large_finish")
+    _checked(L.tgp_ndp_large_finish, N.ptr(indptr), N.ptr(col), N.ptr(w), p0, p1, int(seed) & ((1 << 64) - 1),
+             N.ptr(ws), ws.numel(), N.ptr(keep), N.ptr(info), st)
     if want_state:
-        import ctypes as _ct
-        out = (_ct.c_double * 5)()
-        N.check(L.tgp_ndp_large_state(N.ptr(ws), n, _ct.addressof(out), st), "tgp_ndp_large_state")
+        out = (ctypes.c_double * 5)()
+        _checked(L.tgp_ndp_large_state, N.ptr(ws), n, ctypes.addressof(out), st)
         return info, {"lambda": out[0], "residual_sq": out[1], "steps": int(out[2]), "random": bool(out[3]),
                       "cut": out[4]}
     return info
@@ -3777,7 +3645,7 @@ def block_diag_edges(adj_pool: Tensor, relabel: Optional[Tensor] = None,
     f64 = adj_pool.dtype == torch.float64
     a = (N.f64c if f64 else N.f32c)(adj_pool if adj_pool.dim() == 3 else adj_pool.unsqueeze(0))
     B, K = a.size(0), a.size(1)
-    rl = None if relabel is None else N.i64c(relabel)
+    rl = N.opt_i64(relabel)
     flags = N.REMOVE_SELF_LOOPS if remove_self_loops else 0
     L = N.lib()
     st = N.stream_ptr(dev)
@@ -3797,15 +3665,15 @@ def to_dense_adj(edge_index: Tensor, edge_weight: Optional[Tensor], batch: Tenso
     ``zeroed_out``: a zero-filled [B,Nmax,Nmax] buffer to add into (:func:`to_dense_batch` can zero it in its launch)."""
     dev = N.require_device(edge_index, edge_weight, batch, ptr)
     row, col = _edge_rows(edge_index)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     batch, ptr = N.i64c(batch), N.i64c(ptr)
     adj = zeroed_out if zeroed_out is not None else torch.empty(num_graphs, max_nodes, max_nodes, dtype=torch.float32,
                                                                 device=dev)
     if tuple(adj.shape) != (num_graphs, max_nodes, max_nodes) or adj.dtype != torch.float32 or not adj.is_contiguous():
         raise ValueError("to_dense_adj: zeroed_out must be a contiguous float32 [B,Nmax,Nmax] tensor")
-    N.check(N.lib().tgp_to_dense_adj_f32(N.ptr(row), N.ptr(col), N.ptr(w), row.numel(), N.ptr(batch), N.ptr(ptr),
-                                         num_graphs, max_nodes, 1 if transposed else 0, 1 if zeroed_out is not None else 0,
-                                         N.ptr(adj), N.stream_ptr(dev)), "tgp_to_dense_adj_f32")
+    _checked(N.lib().tgp_to_dense_adj_f32, N.ptr(row), N.ptr(col), N.ptr(w), row.numel(), N.ptr(batch), N.ptr(ptr),
+             num_graphs, max_nodes, 1 if transposed else 0, 1 if zeroed_out is not None else 0, N.ptr(adj),
+             N.stream_ptr(dev))
     return adj
 
 
@@ -3819,9 +3687,8 @@ def to_dense_adj_channels(edge_index: Tensor, edge_attr: Tensor, batch: Tensor, 
     C = a.size(1)
     batch, ptr = N.i64c(batch), N.i64c(ptr)
     adj = torch.empty(num_graphs, max_nodes, max_nodes, C, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_to_dense_adj_channels_f32(N.ptr(row), N.ptr(col), N.ptr(a), E, C, N.ptr(batch), N.ptr(ptr),
-                                                  num_graphs, max_nodes, 1 if transposed else 0, N.ptr(adj),
-                                                  N.stream_ptr(dev)), "tgp_to_dense_adj_channels_f32")
+    _checked(N.lib().tgp_to_dense_adj_channels_f32, N.ptr(row), N.ptr(col), N.ptr(a), E, C, N.ptr(batch), N.ptr(ptr),
+             num_graphs, max_nodes, 1 if transposed else 0, N.ptr(adj), N.stream_ptr(dev))
     return adj.view((num_graphs, max_nodes, max_nodes) + tuple(edge_attr.shape[1:]))
 
 
@@ -3833,9 +3700,8 @@ def from_dense_adj(grad_adj: Tensor, edge_index: Tensor, batch: Tensor, ptr: Ten
     g = N.f32c(grad_adj)
     batch, ptr = N.i64c(batch), N.i64c(ptr)
     out = torch.empty(row.numel(), dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_from_dense_adj_f32(N.ptr(g), N.ptr(row), N.ptr(col), row.numel(), N.ptr(batch), N.ptr(ptr),
-                                           g.size(0), max_nodes, 1 if transposed else 0, N.ptr(out),
-                                           N.stream_ptr(dev)), "tgp_from_dense_adj_f32")
+    _checked(N.lib().tgp_from_dense_adj_f32, N.ptr(g), N.ptr(row), N.ptr(col), row.numel(), N.ptr(batch), N.ptr(ptr),
+             g.size(0), max_nodes, 1 if transposed else 0, N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -3846,8 +3712,8 @@ def from_dense_batch(dense: Tensor, batch: Tensor, ptr: Tensor, max_nodes: int) 
     batch, ptr = N.i64c(batch), N.i64c(ptr)
     n, F = batch.numel(), d.size(2)
     out = torch.empty(n, F, dtype=torch.float32, device=dev)
-    N.check(N.lib().tgp_from_dense_batch_f32(N.ptr(d), n, F, N.ptr(batch), N.ptr(ptr), d.size(0), max_nodes, N.ptr(out),
-                                             N.stream_ptr(dev)), "tgp_from_dense_batch_f32")
+    _checked(N.lib().tgp_from_dense_batch_f32, N.ptr(d), n, F, N.ptr(batch), N.ptr(ptr), d.size(0), max_nodes,
+             N.ptr(out), N.stream_ptr(dev))
     return out.view((n,) + tuple(dense.shape[2:]))
 
 
@@ -3864,16 +3730,14 @@ def to_dense_batch(x: Tensor, batch: Tensor, ptr: Tensor, num_graphs: int, max_n
     from .utils.ops import batch_info
     if F > 0 and ptr.numel() == num_graphs + 1 and batch_info(batch).is_sorted:
         # sorted batch vector (memoised fact): one output-parallel kernel writes rows, padding and mask -- no memsets
-        N.check(N.lib().tgp_to_dense_batch_sorted_f32(N.ptr(x2), x2.size(0), F, N.ptr(ptr), num_graphs, max_nodes,
-                                                      N.ptr(out), N.ptr(mask), N.ptr(also_zero),
-                                                      also_zero.numel() if also_zero is not None else 0,
-                                                      N.stream_ptr(dev)),
-                "tgp_to_dense_batch_sorted_f32")
+        _checked(N.lib().tgp_to_dense_batch_sorted_f32, N.ptr(x2), x2.size(0), F, N.ptr(ptr), num_graphs, max_nodes,
+                 N.ptr(out), N.ptr(mask), N.ptr(also_zero), also_zero.numel() if also_zero is not None else 0,
+                 N.stream_ptr(dev))
         return out.view((num_graphs, max_nodes) + tuple(x.shape[1:])), mask
     if also_zero is not None:
         also_zero.zero_()
-    N.check(N.lib().tgp_to_dense_batch_f32(N.ptr(x2), x2.size(0), F, N.ptr(batch), N.ptr(ptr), num_graphs, max_nodes,
-                                           N.ptr(out), N.ptr(mask), N.stream_ptr(dev)), "tgp_to_dense_batch_f32")
+    _checked(N.lib().tgp_to_dense_batch_f32, N.ptr(x2), x2.size(0), F, N.ptr(batch), N.ptr(ptr), num_graphs, max_nodes,
+             N.ptr(out), N.ptr(mask), N.stream_ptr(dev))
     return out.view((num_graphs, max_nodes) + tuple(x.shape[1:])), mask
 
 
@@ -3950,12 +3814,11 @@ def lapool_variation(x: Tensor, adj: Optional[Tensor] = None, mask: Optional[Ten
     if n == 0:
         return v
     _, col = _edge_rows(edge_index)
-    w = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    w = N.opt_f32_flat(edge_weight)
     if w is not None and w.numel() != E:
         raise ValueError("lapool_variation: one weight per edge")
     grp = _lapool_by_src(edge_index, n, by_src)
-    _checked(N.lib().tgp_lapool_variation_csr_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(col) if E else None,
-             N.ptr(w), N.ptr(x), n, E, x.size(1), N.ptr(v), st)
+    _checked(N.lib().tgp_lapool_variation_csr_f32, *grp.walk(col, E), N.ptr(w), N.ptr(x), n, E, x.size(1), N.ptr(v), st)
     return v
 
 
@@ -3980,7 +3843,7 @@ def lapool_columns(flags: Tensor, mask: Optional[Tensor] = None, batch: Optional
             ptr = torch.tensor([0, f.numel()], dtype=torch.int64, device=dev)
         elif batch.numel() != f.numel():
             raise ValueError("one batch entry per node")
-        res.mask, res.ptr, res.batch = None, N.i64c(ptr), None if batch is None else N.i64c(batch)
+        res.mask, res.ptr, res.batch = None, N.i64c(ptr), N.opt_i64(batch)
         B = res.ptr.numel() - 1
     else:
         raise ValueError(f"flags must be [B, N] or [n], got {tuple(flags.shape)}")
@@ -4014,8 +3877,8 @@ def lapool_leaders(v: Tensor, adj: Optional[Tensor] = None, mask: Optional[Tenso
         if v.dim() != 2 or tuple(adj.shape) != (v.size(0), v.size(1), v.size(1)):
             raise ValueError(f"adj {tuple(adj.shape)} does not match v {tuple(v.shape)}")
         B, Nn = v.shape
-        _checked(N.lib().tgp_lapool_flags_dense_f32, N.ptr(N.f32c(adj)), N.ptr(v), B, Nn, N.ptr(_mask_bytes(mask, B, Nn)),
-                 N.ptr(flags), st)
+        _checked(N.lib().tgp_lapool_flags_dense_f32, N.ptr(N.f32c(adj)), N.ptr(v), B, Nn,
+                 N.ptr(_mask_bytes(mask, B, Nn)), N.ptr(flags), st)
         return lapool_columns(flags, mask=mask, fallback=True)
     if v.dim() != 1:
         raise ValueError(f"v must be [n], got {tuple(v.shape)}")
@@ -4023,8 +3886,7 @@ def lapool_leaders(v: Tensor, adj: Optional[Tensor] = None, mask: Optional[Tenso
     if n:
         _, col = _edge_rows(edge_index)
         grp = _lapool_by_src(edge_index, n, by_src)
-        _checked(N.lib().tgp_lapool_flags_csr_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(col) if E else None,
-                 N.ptr(v), n, E, N.ptr(flags), st)
+        _checked(N.lib().tgp_lapool_flags_csr_f32, *grp.walk(col, E), N.ptr(v), n, E, N.ptr(flags), st)
     return lapool_columns(flags, batch=batch, ptr=ptr, fallback=True)
 
 
@@ -4075,21 +3937,14 @@ _SAG_GROUPS = TensorMemo(16)  # edge_index -> {(num_nodes, by_destination): Assi
 def row_project2(x: Tensor, w0: Tensor, w1: Tensor) -> Tuple[Tensor, Tensor]:
     """(x w0, x w1): both dot products of every row from one pass over ``x`` [N,F] (any row stride)."""
     dev = N.require_device(x, w0, w1)
-    x, w0, w1 = _row_major_f32(x), N.f32c(w0.reshape(-1)), N.f32c(w1.reshape(-1))
+    x, ld = _row_operand(x, "row_project2", convert=True)
+    w0, w1 = N.f32c(w0.reshape(-1)), N.f32c(w1.reshape(-1))
     if w0.numel() != x.size(1) or w1.numel() != x.size(1):
         raise ValueError(f"row_project2: x {tuple(x.shape)} against weights of {w0.numel()} and {w1.numel()} entries")
     out = torch.empty(2, x.size(0), dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_row_project2_f32, N.ptr(x), x.size(0), x.size(1), x.stride(0), N.ptr(w0), N.ptr(w1),
-             N.ptr(out[0]), N.ptr(out[1]), N.stream_ptr(dev))
+    _checked(N.lib().tgp_row_project2_f32, N.ptr(x), x.size(0), x.size(1), ld, N.ptr(w0), N.ptr(w1), N.ptr(out[0]),
+             N.ptr(out[1]), N.stream_ptr(dev))
     return out[0], out[1]
-
-
-def _row_major_f32(x: Tensor) -> Tensor:
-    """float32 [N,F] with unit column stride; a row stride of its own (a column slice) is kept."""
-    if x.dim() != 2:
-        raise ValueError(f"x must be [N, F], got {tuple(x.shape)}")
-    x = x if x.dtype == torch.float32 else x.to(torch.float32)
-    return x if (x.stride(1) == 1 and x.stride(0) >= x.size(1)) or x.numel() == 0 else x.contiguous()
 
 
 def sag_edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = True) -> AssignIndex:
@@ -4132,12 +3987,11 @@ def sag_aggregate(grp: AssignIndex, src: Tensor, p: Tensor, q: Optional[Tensor] 
     if p.numel() != n or grp.nnz != E or grp.row_ptr.numel() != n + 1 or (q is not None and q.numel() != n):
         raise ValueError(f"sag_aggregate: {n} nodes and {grp.nnz} indexed edges against p {tuple(p.shape)}, "
                          f"{E} edges" + ("" if q is None else f", q {tuple(q.shape)}"))
-    q = None if q is None else N.f32c(q.reshape(-1))
-    b = None if bias is None else N.f32c(bias.reshape(-1))
+    q = N.opt_f32_flat(q)
+    b = N.opt_f32_flat(bias)
     out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_sag_aggregate_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(p),
-             N.ptr(q), N.ptr(b), n, E, int(bool(mean)), int(bool(tanh)), N.ptr(out[0]) if want_t else None,
-             N.ptr(out[-1]), N.stream_ptr(dev))
+    _checked(N.lib().tgp_sag_aggregate_f32, *grp.walk(src, E), N.ptr(p), N.ptr(q), N.ptr(b), n, E, int(bool(mean)),
+             int(bool(tanh)), N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.stream_ptr(dev))
     return (out[0], out[1]) if want_t else out[0]
 
 
@@ -4186,14 +4040,14 @@ def asap_query(grp: AssignIndex, src: Tensor, x_pool: Tensor, w_tilde: Tensor, c
     the int32 [n, F] edge positions of the maxima (lowest position on a tie, -1 for a node without in-edges)."""
     dev = N.require_device(src, x_pool, w_tilde, c, grp.row_ptr)
     src, n, E = _asap_group("asap_query", grp, src)
-    x_pool, w_tilde, c = _row_major_f32(x_pool), N.f32c(w_tilde.reshape(-1)), N.f32c(c.reshape(-1))
+    x_pool, ld = _row_operand(x_pool, "asap_query", convert=True)
+    w_tilde, c = N.f32c(w_tilde.reshape(-1)), N.f32c(c.reshape(-1))
     if x_pool.size(0) != n or w_tilde.numel() != x_pool.size(1) or c.numel() != 1:
         raise ValueError(f"asap_query: x_pool {tuple(x_pool.shape)} against {n} nodes, w_tilde of {w_tilde.numel()} and "
                          f"c of {c.numel()} entries")
     sq = torch.empty(n, dtype=torch.float32, device=dev)
     arg = torch.empty(n, x_pool.size(1), dtype=torch.int32, device=dev) if want_arg else None
-    _checked(N.lib().tgp_asap_query_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(x_pool),
-             x_pool.stride(0) if n > 1 else max(x_pool.stride(0), x_pool.size(1)), N.ptr(w_tilde), N.ptr(c), n, E,
+    _checked(N.lib().tgp_asap_query_f32, *grp.walk(src, E), N.ptr(x_pool), ld, N.ptr(w_tilde), N.ptr(c), n, E,
              x_pool.size(1), N.ptr(sq), N.ptr(arg), N.stream_ptr(dev))
     return (sq, arg) if want_arg else sq
 
@@ -4202,12 +4056,11 @@ def asap_edge_dot(grp: AssignIndex, src: Tensor, g: Tensor, x: Tensor) -> Tensor
     """out[pos] = <g[i], x[src[pos]]> for every edge of node i's group: the gradient of the attend kernel's ``val``."""
     dev = N.require_device(src, g, x, grp.row_ptr)
     src, n, E = _asap_group("asap_edge_dot", grp, src)
-    g, x = N.f32c(g), _row_major_f32(x)
+    g, (x, ld) = N.f32c(g), _row_operand(x, "asap_edge_dot", convert=True)
     if g.dim() != 2 or g.size(0) != n or x.size(0) != n or g.size(1) != x.size(1):
         raise ValueError(f"asap_edge_dot: g {tuple(g.shape)} and x {tuple(x.shape)} against {n} nodes")
     out = torch.empty(E, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_edge_dot_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(g),
-             N.ptr(x), x.stride(0) if n > 1 else max(x.stride(0), x.size(1)), n, E, x.size(1),
+    _checked(N.lib().tgp_asap_edge_dot_f32, *grp.walk(src, E), N.ptr(g), N.ptr(x), ld, n, E, x.size(1),
              N.ptr(out) if E else None, N.stream_ptr(dev))
     return out
 
@@ -4223,9 +4076,9 @@ def asap_softmax_bwd(grp: AssignIndex, src: Tensor, alpha: Tensor, g_alpha: Tens
         raise ValueError(f"asap_softmax_bwd: alpha and g_alpha per edge ({E}), sq and sp per node ({n})")
     g_l = torch.empty(E, dtype=torch.float32, device=dev)
     g_sq = torch.empty(n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_softmax_bwd_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None,
-             N.ptr(alpha) if E else None, N.ptr(g_alpha) if E else None, N.ptr(sq), N.ptr(sp), n, E,
-             float(negative_slope), N.ptr(g_l) if E else None, N.ptr(g_sq), N.stream_ptr(dev))
+    _checked(N.lib().tgp_asap_softmax_bwd_f32, *grp.walk(src, E), N.ptr(alpha) if E else None,
+             N.ptr(g_alpha) if E else None, N.ptr(sq), N.ptr(sp), n, E, float(negative_slope),
+             N.ptr(g_l) if E else None, N.ptr(g_sq), N.stream_ptr(dev))
     return g_l, g_sq
 
 
@@ -4239,8 +4092,8 @@ def asap_query_bwd(by_src: AssignIndex, dst: Tensor, argpos: Tensor, g_sq: Tenso
     if argpos.dtype != torch.int32 or tuple(argpos.shape) != (n, F) or not argpos.is_contiguous() or g_sq.numel() != n:
         raise ValueError(f"asap_query_bwd: argpos must be a contiguous int32 [{n}, {F}], g_sq [{n}]")
     out = torch.empty(n, F, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_query_bwd_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
-             N.ptr(argpos), N.ptr(g_sq), N.ptr(w_tilde), n, E, F, N.ptr(out), N.stream_ptr(dev))
+    _checked(N.lib().tgp_asap_query_bwd_f32, *by_src.walk(dst, E), N.ptr(argpos), N.ptr(g_sq), N.ptr(w_tilde), n, E, F,
+             N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -4253,8 +4106,8 @@ def asap_edge_softmax(grp: AssignIndex, src: Tensor, sq: Tensor, sp: Tensor, neg
     if sq.numel() != n or sp.numel() != n:
         raise ValueError(f"asap_edge_softmax: one sq and one sp per node ({n}), got {sq.numel()} and {sp.numel()}")
     alpha = torch.empty(E, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_edge_softmax_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None,
-             N.ptr(sq), N.ptr(sp), n, E, float(negative_slope), N.ptr(alpha) if E else None, N.stream_ptr(dev))
+    _checked(N.lib().tgp_asap_edge_softmax_f32, *grp.walk(src, E), N.ptr(sq), N.ptr(sp), n, E, float(negative_slope),
+             N.ptr(alpha) if E else None, N.stream_ptr(dev))
     return alpha
 
 
@@ -4264,16 +4117,15 @@ def asap_attend(grp: AssignIndex, src: Tensor, x: Tensor, val: Optional[Tensor] 
     gather per edge; with ``proj`` [3, F] also the three projections of every finished row."""
     dev = N.require_device(src, x, val, proj, grp.row_ptr)
     src, n, E = _asap_group("asap_attend", grp, src)
-    x = _row_major_f32(x)
+    x, ld = _row_operand(x, "asap_attend", convert=True)
     F = x.size(1)
-    val = None if val is None else N.f32c(val.reshape(-1))
-    proj = None if proj is None else N.f32c(proj)
+    val = N.opt_f32_flat(val)
+    proj = N.opt_f32(proj)
     if (val is not None and val.numel() != E) or (proj is not None and tuple(proj.shape) != (3, F)):
         raise ValueError(f"asap_attend: one value per edge ({E}) and projections [3, {F}]")
     out = torch.empty(n, F, dtype=torch.float32, device=dev)
     p = None if proj is None else torch.empty(3, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_attend_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(val),
-             N.ptr(x), x.stride(0) if x.size(0) > 1 else max(x.stride(0), F), N.ptr(proj), n, x.size(0), E, F,
+    _checked(N.lib().tgp_asap_attend_f32, *grp.walk(src, E), N.ptr(val), N.ptr(x), ld, N.ptr(proj), n, x.size(0), E, F,
              N.ptr(out), N.ptr(p), N.stream_ptr(dev))
     return out, p
 
@@ -4288,20 +4140,19 @@ def asap_leconv(grp: AssignIndex, src: Tensor, p: Tensor, edge_weight: Optional[
     dev = N.require_device(src, p, edge_weight, b1, b3, grp.row_ptr)
     src, n, E = _asap_group("asap_leconv", grp, src)
     p = N.f32c(p)
-    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    ew = N.opt_f32_flat(edge_weight)
     if tuple(p.shape) != (3, n) or (ew is not None and ew.numel() != E):
         raise ValueError(f"asap_leconv: p must be [3, {n}] and edge_weight [{E}]")
-    b1 = None if b1 is None else N.f32c(b1.reshape(-1))
-    b3 = None if b3 is None else N.f32c(b3.reshape(-1))
+    b1 = N.opt_f32_flat(b1)
+    b3 = N.opt_f32_flat(b3)
     out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_leconv_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(src) if E else None, N.ptr(ew),
-             N.ptr(p), N.ptr(b1), N.ptr(b3), n, E, ASAP_ACTS[act], N.ptr(out[0]) if want_t else None, N.ptr(out[-1]),
-             N.stream_ptr(dev))
+    _checked(N.lib().tgp_asap_leconv_f32, *grp.walk(src, E), N.ptr(ew), N.ptr(p), N.ptr(b1), N.ptr(b3), n, E,
+             ASAP_ACTS[act], N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.stream_ptr(dev))
     return (out[0], out[1]) if want_t else out[0]
 
 
 # ------------------------------------------------------------------------- segment readout (csrc/segment_aggr.hip)
-SEGMENT_OPS =("sum", "mean", "min", "max")  # the order of their enum values = the order of the output's column blocks
+SEGMENT_OPS = ("sum", "mean", "min", "max")  # the order of their enum values = the order of the output's column blocks
 
 
 def segment_ops_mask(ops: Sequence[str]) -> int:
@@ -4320,15 +4171,6 @@ def segment_aggr_chunk_rows() -> int:
     return int(N.lib().tgp_segment_aggr_chunk_rows())
 
 
-def _rows_f32(x: Tensor) -> Tensor:
-    """[rows, F] float32 with unit inner stride and a row stride of at least F (a copy only when the view is not)."""
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError(f"segment readout expects float32 x of shape [rows, F], got {x.dtype} {tuple(x.shape)}")
-    if (x.size(1) > 1 and x.stride(1) != 1) or (x.size(0) > 1 and x.stride(0) < x.size(1)):
-        x = x.contiguous()
-    return x
-
-
 def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, ptr: Optional[Tensor] = None,
                  dense_nodes: int = 0, mask: Optional[Tensor] = None, index: Optional[AssignIndex] = None,
                  node_index: Optional[Tensor] = None, weight: Optional[Tensor] = None, want_aux: bool = False):
@@ -4337,10 +4179,10 @@ def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, ptr: O
     (contiguous segments), ``dense_nodes`` (+ ``mask`` [rows] bytes), or ``index`` + ``node_index`` (+ ``weight``):
     the rows of a sparse assignment (reduce/aggr_reduce.py:99-103 without the [nnz, F] product)."""
     dev = N.require_device(x, ptr, mask, node_index, weight)
-    x = _rows_f32(x)
-    ptr = None if ptr is None else N.i64c(ptr)
-    node_index = None if node_index is None else N.i64c(node_index)
-    weight = None if weight is None else N.f32c(weight.reshape(-1))
+    x, ld = _row_operand(x, "segment readout")
+    ptr = N.opt_i64(ptr)
+    node_index = N.opt_i64(node_index)
+    weight = N.opt_f32_flat(weight)
     mask = None if mask is None else mask.reshape(-1).contiguous()
     if index is not None and (node_index is None or node_index.numel() != index.nnz
                               or (weight is not None and weight.numel() != index.nnz)):
@@ -4355,10 +4197,10 @@ def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, ptr: O
     wsb = L.tgp_segment_aggr_workspace_bytes(num_groups, F, ops_mask, max_len)
     ws = N.workspace(wsb, dev) if wsb else None
     gathered = index is not None
-    _checked(L.tgp_segment_aggr_f32, N.ptr(x), rows, F, x.stride(0) if rows > 1 else max(x.stride(0), F), N.ptr(ptr),
-             dense_nodes, N.ptr(mask), N.ptr(index._row_ptr) if gathered else None,
-             N.ptr(index.perm) if gathered else None, N.ptr(node_index), N.ptr(weight), index.nnz if gathered else 0,
-             num_groups, max_len, ops_mask, N.ptr(out), N.ptr(ties), N.ptr(count), N.ptr(ws), wsb, N.stream_ptr(dev))
+    _checked(L.tgp_segment_aggr_f32, N.ptr(x), rows, F, ld, N.ptr(ptr), dense_nodes, N.ptr(mask),
+             N.ptr(index._row_ptr) if gathered else None, N.ptr(index.perm) if gathered else None, N.ptr(node_index),
+             N.ptr(weight), index.nnz if gathered else 0, num_groups, max_len, ops_mask, N.ptr(out), N.ptr(ties),
+             N.ptr(count), N.ptr(ws), wsb, N.stream_ptr(dev))
     return out, ties, count
 
 
@@ -4367,12 +4209,11 @@ def segment_aggr_bwd(g_out: Tensor, x: Tensor, out: Tensor, ties: Optional[Tenso
                      mask: Optional[Tensor] = None) -> Tensor:
     """dX [rows, F] of :func:`segment_aggr` for the contiguous and the dense sources, one launch, written once."""
     dev = N.require_device(g_out, x, out, batch, mask)
-    g_out, x = N.f32c(g_out), _rows_f32(x)
+    g_out, (x, ld) = N.f32c(g_out), _row_operand(x, "segment readout")
     rows, F = x.shape
     dx = torch.empty(rows, F, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_segment_aggr_bwd_f32, N.ptr(g_out), N.ptr(x), rows, F,
-             x.stride(0) if rows > 1 else max(x.stride(0), F), N.ptr(batch), dense_nodes, N.ptr(mask), N.ptr(out),
-             N.ptr(ties), N.ptr(count), num_groups, ops_mask, N.ptr(dx), N.stream_ptr(dev))
+    _checked(N.lib().tgp_segment_aggr_bwd_f32, N.ptr(g_out), N.ptr(x), rows, F, ld, N.ptr(batch), dense_nodes,
+             N.ptr(mask), N.ptr(out), N.ptr(ties), N.ptr(count), num_groups, ops_mask, N.ptr(dx), N.stream_ptr(dev))
     return dx
 
 
@@ -4453,15 +4294,14 @@ def maxcut_degree(by_src: AssignIndex, edge_index: Tensor, edge_weight: Optional
     n, E = by_src.num_targets, row.numel()
     if by_src.nnz != E or by_src.row_ptr.numel() != n + 1:
         raise ValueError(f"maxcut_degree: an index of {by_src.nnz} edges over {n} nodes against {E} edges")
-    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    ew = N.opt_f32_flat(edge_weight)
     if ew is not None and ew.numel() != E:
         raise ValueError(f"maxcut_degree: {ew.numel()} weights for {E} edges")
     dinv = torch.empty(n, dtype=torch.float32, device=dev)
     coef = torch.empty(E, dtype=torch.float32, device=dev) if want_coef else None
     coef_t = torch.empty(E, dtype=torch.float32, device=dev) if want_coef_t else None
-    _checked(N.lib().tgp_maxcut_degree_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(row) if E else None,
-             N.ptr(col) if E else None, N.ptr(ew), n, E, N.ptr(dinv), N.ptr(coef) if E else None,
-             N.ptr(coef_t) if E else None, N.stream_ptr(dev))
+    _checked(N.lib().tgp_maxcut_degree_f32, *by_src.walk(row, E), N.ptr(col) if E else None, N.ptr(ew), n, E,
+             N.ptr(dinv), N.ptr(coef) if E else None, N.ptr(coef_t) if E else None, N.stream_ptr(dev))
     return dinv, coef, coef_t
 
 
@@ -4480,13 +4320,13 @@ def maxcut_layer(grp: AssignIndex, other: Tensor, coef: Optional[Tensor], dinv: 
         raise ValueError(f"maxcut_layer: z {tuple(z.shape)} and dinv [{dinv.numel()}] against {n} nodes, one coefficient "
                          f"per edge ({E})")
     C = z.size(1)
-    coef = None if coef is None else N.f32c(coef.reshape(-1))
-    bias = None if bias is None else N.f32c(bias.reshape(-1))
+    coef = N.opt_f32_flat(coef)
+    bias = N.opt_f32_flat(bias)
     if bias is not None and bias.numel() != C:
         raise ValueError(f"maxcut_layer: bias of {bias.numel()} entries for {C} channels")
     if n_p is not None and (n_p.dtype != torch.int64 or n_p.numel() != 1):
         raise ValueError("maxcut_layer: n_p is one device int64")
-    w_next = None if w_next is None else N.f32c(w_next)
+    w_next = N.opt_f32(w_next)
     if w_next is not None and (w_next.dim() != 2 or w_next.size(1) != C):
         raise ValueError(f"maxcut_layer: w_next {tuple(w_next.shape)} against {C} channels")
     if not want_h and w_next is None:
@@ -4494,9 +4334,9 @@ def maxcut_layer(grp: AssignIndex, other: Tensor, coef: Optional[Tensor], dinv: 
     Cn = 0 if w_next is None else w_next.size(0)
     h = torch.empty(n, C, dtype=torch.float32, device=dev) if want_h else None
     zn = torch.empty(n, Cn, dtype=torch.float32, device=dev) if w_next is not None else None
-    _checked(N.lib().tgp_maxcut_layer_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(other) if E else None,
-             N.ptr(coef) if E else None, N.ptr(dinv), N.ptr(z), N.ptr(bias), n, E, C, N.ptr(n_p), float(delta),
-             MAXCUT_ACTS[act], N.ptr(h), N.ptr(w_next), Cn, N.ptr(zn), N.stream_ptr(dev))
+    _checked(N.lib().tgp_maxcut_layer_f32, *grp.walk(other, E), N.ptr(coef) if E else None, N.ptr(dinv), N.ptr(z),
+             N.ptr(bias), n, E, C, N.ptr(n_p), float(delta), MAXCUT_ACTS[act], N.ptr(h), N.ptr(w_next), Cn, N.ptr(zn),
+             N.stream_ptr(dev))
     return h, zn
 
 
@@ -4523,9 +4363,9 @@ def maxcut_tail(h: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], 
         raise ValueError("maxcut_tail: h must be [N, C] and every Linear needs its weight and bias")
     packed = torch.cat([t.detach().to(torch.float32).reshape(-1) for wb in zip(weights, biases) for t in wb])
     widths = [w.size(0) for w in weights[:-1]]
-    arr = (N.ctypes.c_int64 * max(len(widths), 1))(*widths)
+    arr = (ctypes.c_int64 * max(len(widths), 1))(*widths)
     score = torch.empty(h.size(0), dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_maxcut_tail_f32, N.ptr(h), h.size(0), h.size(1), N.ctypes.addressof(arr), len(widths),
+    _checked(N.lib().tgp_maxcut_tail_f32, N.ptr(h), h.size(0), h.size(1), ctypes.addressof(arr), len(widths),
              N.ptr(packed), packed.numel(), MAXCUT_ACTS[mlp_act], MAXCUT_ACTS[act], N.ptr(score), N.stream_ptr(dev))
     return score
 
@@ -4553,13 +4393,12 @@ def maxcut_cut(grp: AssignIndex, other: Tensor, s: Tensor, edge_weight: Optional
     dev = N.require_device(other, s, edge_weight, grp.row_ptr)
     other, n, E = _asap_group("maxcut_cut", grp, other)
     s = N.f32c(s.reshape(-1))
-    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    ew = N.opt_f32_flat(edge_weight)
     if s.numel() != n or (ew is not None and ew.numel() != E):
         raise ValueError(f"maxcut_cut: one score per node ({n}) and one weight per edge ({E})")
     out = torch.empty(3, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_maxcut_cut_f32, N.ptr(grp.row_ptr), N.ptr(grp.perm), N.ptr(other) if E else None, N.ptr(ew),
-             N.ptr(s), n, E, N.ptr(out[0]), N.ptr(out[1]) if want_cut else None, N.ptr(out[2]) if want_wsum else None,
-             N.stream_ptr(dev))
+    _checked(N.lib().tgp_maxcut_cut_f32, *grp.walk(other, E), N.ptr(ew), N.ptr(s), n, E, N.ptr(out[0]),
+             N.ptr(out[1]) if want_cut else None, N.ptr(out[2]) if want_wsum else None, N.stream_ptr(dev))
     return out[0], out[1] if want_cut else None, out[2] if want_wsum else None
 
 
@@ -4573,8 +4412,7 @@ def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, round
     cur, nxt = labels, torch.empty_like(labels)
     fn = N.lib().tgp_maxcut_assign_round_i32
     for _ in range(int(rounds)):
-        _checked(fn, N.ptr(by_dst.row_ptr), N.ptr(by_dst.perm), N.ptr(src) if E else None, N.ptr(cur), n, E, N.ptr(nxt),
-                 N.stream_ptr(dev))
+        _checked(fn, *by_dst.walk(src, E), N.ptr(cur), n, E, N.ptr(nxt), N.stream_ptr(dev))
         cur, nxt = nxt, cur
     return cur
 
@@ -4597,7 +4435,7 @@ def eigenpool_modes(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tens
     :func:`eigenpool_max_group_nodes`; larger groups are flagged, not solved)."""
     dev = N.require_device(dst, edge_weight, gid, by_src.row_ptr, groups.row_ptr)
     dst, n, E = _asap_group("eigenpool_modes", by_src, dst)
-    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    ew = N.opt_f32_flat(edge_weight)
     if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
         raise ValueError(f"eigenpool_modes: gid must be a contiguous int32 [{n}]")
     if groups.nnz != n or (ew is not None and ew.numel() != E):
@@ -4606,10 +4444,9 @@ def eigenpool_modes(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tens
     theta = torch.zeros(n, max(H, 1), dtype=torch.float32, device=dev)
     deg = torch.zeros(n, dtype=torch.float32, device=dev) if want_degree else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _checked(N.lib().tgp_eigenpool_modes_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
-             N.ptr(ew), N.ptr(gid), N.ptr(groups.row_ptr), N.ptr(groups.perm), n, E, groups.num_targets, H,
-             int(max_group), 1 if normalized else 0, 1 if embed else 0, N.ptr(theta), N.ptr(deg), N.ptr(status),
-             N.stream_ptr(dev))
+    _checked(N.lib().tgp_eigenpool_modes_f32, *by_src.walk(dst, E), N.ptr(ew), N.ptr(gid), N.ptr(groups.row_ptr),
+             N.ptr(groups.perm), n, E, groups.num_targets, H, int(max_group), 1 if normalized else 0, 1 if embed else 0,
+             N.ptr(theta), N.ptr(deg), N.ptr(status), N.stream_ptr(dev))
     st = int(status.item())
     if st & EIG_BAD_INPUT:
         raise N.TgpNativeError("tgp_eigenpool_modes_f32: an index outside its table (an edge endpoint, an edge position "
@@ -4617,18 +4454,13 @@ def eigenpool_modes(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tens
     return (theta, st, deg) if want_degree else (theta, st)
 
 
-def _eigenpool_rows(name: str, t: Tensor) -> Tensor:
-    if t.dim() != 2 or t.dtype != torch.float32:
-        raise ValueError(f"{name} expects float32 [rows, cols], got {t.dtype} {tuple(t.shape)}")
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def eigenpool_reduce(theta_modes: Tensor, groups: AssignIndex, x: Tensor, max_len: int = 0) -> Tensor:
     """X_pool [G, H F]: ``X_pool[g, h F + f] = sum_{i in group g} theta_modes[i, h] x[i, f]``, nodes ascending, one pass
     over x, the same bits on every call.  ``max_len``: an upper bound of the longest group (0: short groups); it picks
     how many waves share a group, never the result's validity."""
     dev = N.require_device(theta_modes, x, groups.row_ptr)
-    theta_modes, x = _eigenpool_rows("eigenpool_reduce", theta_modes), _eigenpool_rows("eigenpool_reduce", x)
+    theta_modes, _ = _row_operand(theta_modes, "eigenpool_reduce", packed=True)
+    x, _ = _row_operand(x, "eigenpool_reduce", packed=True)
     n, H = theta_modes.shape
     if x.size(0) != n or groups.nnz != n or H < 1:
         raise ValueError(f"eigenpool_reduce: theta_modes {tuple(theta_modes.shape)}, x {tuple(x.shape)} and an index of "
@@ -4636,15 +4468,16 @@ def eigenpool_reduce(theta_modes: Tensor, groups: AssignIndex, x: Tensor, max_le
     F, G = x.size(1), groups.num_targets
     out = torch.empty(G, H * F, dtype=torch.float32, device=dev)
     if G and F:
-        _checked(N.lib().tgp_eigenpool_reduce_f32, N.ptr(theta_modes), N.ptr(groups.row_ptr), N.ptr(groups.perm), N.ptr(x),
-                 F, n, G, H, F, int(max_len), N.ptr(out), N.stream_ptr(dev))
+        _checked(N.lib().tgp_eigenpool_reduce_f32, N.ptr(theta_modes), N.ptr(groups.row_ptr), N.ptr(groups.perm),
+                 N.ptr(x), F, n, G, H, F, int(max_len), N.ptr(out), N.stream_ptr(dev))
     return out
 
 
 def eigenpool_lift(theta_modes: Tensor, gid: Tensor, x_pool: Tensor, num_groups: int) -> Tensor:
     """X_lift [N, F]: ``X_lift[i, f] = sum_h theta_modes[i, h] x_pool[gid[i], h F + f]`` (the adjoint of the Reduce)."""
     dev = N.require_device(theta_modes, gid, x_pool)
-    theta_modes, x_pool = _eigenpool_rows("eigenpool_lift", theta_modes), _eigenpool_rows("eigenpool_lift", x_pool)
+    theta_modes, _ = _row_operand(theta_modes, "eigenpool_lift", packed=True)
+    x_pool, _ = _row_operand(x_pool, "eigenpool_lift", packed=True)
     n, H = theta_modes.shape
     if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
         raise ValueError(f"eigenpool_lift: gid must be a contiguous int32 [{n}]")
@@ -4675,7 +4508,7 @@ def nmf_max_k() -> int:
 def _nmf_args(name: str, by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor,
               graphs: AssignIndex):
     dst, n, E = _asap_group(name, by_src, dst)
-    ew = None if edge_weight is None else N.f32c(edge_weight.reshape(-1))
+    ew = N.opt_f32_flat(edge_weight)
     if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
         raise ValueError(f"{name}: gid must be a contiguous int32 [{n}]")
     if graphs.nnz != n or (ew is not None and ew.numel() != E):
@@ -4691,9 +4524,9 @@ def nmf_init(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gi
     dst, ew, n, E = _nmf_args("nmf_init", by_src, dst, edge_weight, gid, graphs)
     w0 = torch.zeros(2, n, max(int(k), 1), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _checked(N.lib().tgp_nmf_init_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None, N.ptr(ew),
-             N.ptr(gid), N.ptr(graphs.row_ptr), N.ptr(graphs.perm), n, E, graphs.num_targets, int(k), int(max_n),
-             int(seed), N.ptr(w0[0]), N.ptr(w0[1]), N.ptr(status), N.stream_ptr(dev))
+    _checked(N.lib().tgp_nmf_init_f32, *by_src.walk(dst, E), N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr),
+             N.ptr(graphs.perm), n, E, graphs.num_targets, int(k), int(max_n), int(seed), N.ptr(w0[0]), N.ptr(w0[1]),
+             N.ptr(status), N.stream_ptr(dev))
     return w0[0], w0[1], int(status.item())
 
 
@@ -4716,11 +4549,10 @@ def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor
     iters = torch.zeros(G, dtype=torch.int32, device=dev)
     ratio = torch.zeros(G, dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _checked(N.lib().tgp_nmf_factorize_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(dst) if E else None,
-             N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr), N.ptr(graphs.perm), n, E, G, Kc, int(out_cols), int(max_n),
-             int(seed), float(tol), int(max_iter), N.ptr(w0), N.ptr(h0t), N.ptr(s),
-             N.ptr(fac[0]) if want_factors else None, N.ptr(fac[1]) if want_factors else None, N.ptr(iters),
-             N.ptr(ratio), N.ptr(status), N.stream_ptr(dev))
+    _checked(N.lib().tgp_nmf_factorize_f32, *by_src.walk(dst, E), N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr),
+             N.ptr(graphs.perm), n, E, G, Kc, int(out_cols), int(max_n), int(seed), float(tol), int(max_iter),
+             N.ptr(w0), N.ptr(h0t), N.ptr(s), N.ptr(fac[0]) if want_factors else None,
+             N.ptr(fac[1]) if want_factors else None, N.ptr(iters), N.ptr(ratio), N.ptr(status), N.stream_ptr(dev))
     out = {"s": s, "status": int(status.item()), "iters": iters, "ratio": ratio}
     if want_factors:
         out["w"], out["ht"] = fac[0], fac[1]

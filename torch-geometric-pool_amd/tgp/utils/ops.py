@@ -82,8 +82,8 @@ def _batch_facts_device(batch: Tensor, info: "BatchInfo", topk_ratio: float = 0.
     n = batch.numel()
     sizes = torch.empty(n + 1, dtype=torch.long, device=batch.device)
     facts = torch.empty(5, dtype=torch.long, device=batch.device)
-    N.check(N.lib().tgp_batch_facts_i64(N.ptr(batch), n, N.ptr(sizes), N.ptr(facts), float(topk_ratio or 0.0),
-                                        N.stream_ptr(batch.device)), "tgp_batch_facts_i64")
+    N.checked(N.lib().tgp_batch_facts_i64, N.ptr(batch), n, N.ptr(sizes), N.ptr(facts), float(topk_ratio or 0.0),
+              N.stream_ptr(batch.device))
     max_id, flags, longest, distinct, keep = facts.tolist()
     if flags & 2:
         return False
@@ -126,11 +126,9 @@ def _facts_sorted_launch(batch: Tensor, topk_ratio: float):
     base = buf.data_ptr()
     o_sizes, o_k, o_koff = n + 2, 2 * n + 3, 3 * n + 4
     tag = state.next_facts_tag()
-    N.check(N.lib().tgp_batch_facts_sorted_i64(batch.data_ptr(), n, base, base + 8 * o_sizes, float(topk_ratio or 0.0),
-                                               (base + 8 * o_k) if want_plan else None,
-                                               (base + 8 * o_koff) if want_plan else None,
-                                               state.ticket.data_ptr(), state.facts_slot(tag), tag, st),
-            "tgp_batch_facts_sorted_i64")
+    N.checked(N.lib().tgp_batch_facts_sorted_i64, batch.data_ptr(), n, base, base + 8 * o_sizes,
+              float(topk_ratio or 0.0), (base + 8 * o_k) if want_plan else None,
+              (base + 8 * o_koff) if want_plan else None, state.ticket.data_ptr(), state.facts_slot(tag), tag, st)
     return state, tag, buf, n, want_plan
 
 
