@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32; PAN: tgp_pan_max_graph_nodes, tgp_pan_met_workspace_bytes, tgp_pan_met_count, tgp_pan_met_fill_f32, tgp_pan_met_bwd_f32, tgp_pan_score_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -1741,6 +1741,53 @@ int tgp_nmf_factorize_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NUL
                           const float* h0t /* NULL ok */, float* s, float* w_out /* NULL ok */,
                           float* ht_out /* NULL ok */, int32_t* iters /* NULL ok */, float* violation_ratio /* NULL ok */,
                           int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * PAN convolution and pooling (reference poolers/pan.py over PyG's PANConv), csrc/pan.hip: the MET matrix
+ *     M = D^-1/2 (sum_{n=0..L} c_n A_t^n) D^-1/2,  A_t[dst, src] = multiplicity of the edge src -> dst,
+ *     tmp_0 = w_0 I, tmp_n = w_n (tmp_{n-1} A_t), S = sum_n tmp_n (c_n = w_0 ... w_n),
+ *     deg_i = stored entries of row i (a count), dinv = deg^-1/2, M_ij = (dinv_j S_ij) dinv_i.
+ * The pattern is structural: (i, j) is stored iff a walk of length <= L joins them, whatever the value; the diagonal is
+ * always stored.  One wave owns a row and keeps it in LDS over the n nodes of the row's graph; the graphs are the node
+ * ranges graph_ptr [G + 1] (nodes grouped by graph), gid [N] names every node's graph (NULL: one graph), the edges come
+ * through the by-source edge index (grp_ptr [N + 1], grp_perm [E] or NULL for a list that is grouped already) and are
+ * added in edge-list order: fp32, no fused multiply-add, no float atomics, the same bits on every call.
+ *   count: row_ptr [N + 1] int32 (the CSR offsets of M, row_ptr[N] = nnz), dinv [N], *d_count = nnz -- or -1 when the
+ *          status word is set (the fill must not run then).  Row i checks every edge that starts at node i, so the
+ *          status word of the count covers every edge of the list.  ws: tgp_pan_met_workspace_bytes(N).
+ *   fill:  (out_row, out_col, out_val) [nnz] row-major sorted, ascending columns inside a row: coalesced, no sort.
+ *   bwd:   part [N, L + 1], part[i, n] = sum over row i's stored entries e of (g_val[e] dinv[col[e]]) dinv[i]
+ *          (A_t^n)[i, col[e]]; the column sums over i are the gradient with respect to c.
+ * max_n in 1 .. tgp_pan_max_graph_nodes() sizes the LDS frame (an upper bound of the largest graph).  *status (one zeroed
+ * device word) collects: bit 0 an index outside its table (a node outside its graph's range, an edge position or endpoint
+ * out of range, offsets that are not those of this pattern), bit 1 an edge whose endpoints lie in two graphs, bit 2 a graph
+ * of more than max_n nodes.  A flagged row is left unwritten; nothing out of range is dereferenced.
+ *   score: score[i] = act(beta[0] <x[i,:], p> + beta[1] sum_{e in column group i} val[e]), act 0 = identity, 1 = tanh;
+ *          col_ptr [N + 1] / col_perm [nnz] (NULL: grouped already) index M's entries by column.  dot_out, colsum_out
+ *          [N] (NULL ok) receive the two terms.
+ * TGP_ERR_INVALID: a NULL input or output, sizes below zero, L outside 0 .. 64, max_n outside its range, an empty count;
+ * TGP_ERR_RANGE: a size (or N x max_n) beyond the int32 index; TGP_ERR_WORKSPACE: ws too small.  All are found before
+ * any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_pan_max_graph_nodes(void);
+size_t tgp_pan_met_workspace_bytes(int64_t N);
+int tgp_pan_met_count(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                      const int32_t* gid /* NULL ok */, const int32_t* graph_ptr, int64_t N, int64_t E, int64_t G,
+                      int64_t L, int64_t max_n, int32_t* row_ptr, float* dinv, void* ws, size_t ws_bytes,
+                      int32_t* status, int64_t* d_count, void* stream);
+int tgp_pan_met_fill_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                         const int32_t* gid /* NULL ok */, const int32_t* graph_ptr, int64_t N, int64_t E, int64_t G,
+                         int64_t L, int64_t max_n, const float* weight, const int32_t* row_ptr, const float* dinv,
+                         int64_t nnz, int64_t* out_row, int64_t* out_col, float* out_val, int32_t* status,
+                         void* stream);
+int tgp_pan_met_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                        const int32_t* gid /* NULL ok */, const int32_t* graph_ptr, int64_t N, int64_t E, int64_t G,
+                        int64_t L, int64_t max_n, const int32_t* row_ptr, const int64_t* col, const float* g_val,
+                        const float* dinv, int64_t nnz, float* part, int32_t* status, void* stream);
+int tgp_pan_score_f32(const float* x, int64_t N, int64_t F, int64_t ldx, const float* p, const float* beta,
+                      const int32_t* col_ptr, const int32_t* col_perm /* NULL ok */, const float* val, int64_t nnz,
+                      int act, float* score, float* dot_out /* NULL ok */, float* colsum_out /* NULL ok */,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -400,6 +400,16 @@ SIGNATURES = {
     "tgp_nmf_factorize_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
                                        _c_i64, _c_i64, _c_f, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                        _c_p]),
+    "tgp_pan_max_graph_nodes": (_c_int, []),
+    "tgp_pan_met_workspace_bytes": (_c_sz, [_c_i64]),
+    "tgp_pan_met_count": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p,
+                                   _c_sz, _c_p, _c_p, _c_p]),
+    "tgp_pan_met_fill_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
+                                      _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_pan_met_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
+                                     _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_pan_score_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p,
+                                   _c_p, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

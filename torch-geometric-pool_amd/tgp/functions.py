@@ -1816,3 +1816,103 @@ def eigenpool_lift(x_pool: Tensor, theta_modes: Tensor, groups, gid: Tensor, max
     if _needs_grad(x_pool):
         return _EigenLiftFn.apply(x_pool, theta_modes, groups, gid, max_len)
     return K.eigenpool_lift(theta_modes, gid, x_pool, groups.num_targets)
+
+
+# ------------------------------------------------------------------------------------ PAN: MET matrix, M x and the score
+class _PanMetValuesFn(torch.autograd.Function):
+    """The values of the MET matrix as a function of PANConv's ``weight`` [L + 1].  The forward is the count -> fill pair
+    that already ran (``met``); the backward recomputes the row powers (K.pan_met_bwd), adds the rows' shares to dL/dc
+    and goes from c = cumprod(weight) to weight through torch's own cumprod backward on L + 1 numbers (it handles zero
+    weights).  ``deg`` is a count: no gradient passes through ``dinv``."""
+
+    @staticmethod
+    def forward(ctx, weight, met):
+        ctx.save_for_backward(weight)
+        # (a copy without the values: the record is handed this node's output, and must not keep the node alive)
+        ctx.met = K.PanMet(met.index, None, met.row_ptr, met.num_nodes, met.dinv, met.frame)
+        return met.values
+
+    @staticmethod
+    def backward(ctx, g):
+        (weight,) = ctx.saved_tensors
+        gc = K.pan_met_bwd(ctx.met, g).sum(dim=0)
+        with torch.enable_grad():
+            w = weight.detach().requires_grad_(True)
+            (gw,) = torch.autograd.grad(torch.cumprod(w, dim=0), w, gc.to(w.dtype))
+        return gw, None
+
+
+def pan_met(edge_index: Tensor, weight: Tensor, num_nodes: int, gid: Optional[Tensor], graph_ptr: Tensor,
+            max_graph_nodes: int):
+    """K.pan_met with ``values`` tracked back to ``weight`` (None when the kernel declines)."""
+    met = K.pan_met(edge_index, weight, num_nodes, gid, graph_ptr, max_graph_nodes)
+    if met is not None and _needs_grad(weight):
+        met.values = _PanMetValuesFn.apply(weight, met)
+    return met
+
+
+class _PanSpmmFn(torch.autograd.Function):
+    """out = M x on M's row-sorted list with the CSR offsets its build left (K.spmm_csr).  dx = M^T g through the
+    by-column group of M (K.reduce_sparse: no transposed copy of M), dM_e = <g[row_e], x[col_e]> (K.pair_dot)."""
+
+    @staticmethod
+    def forward(ctx, values, x, met):
+        ctx.save_for_backward(values, x)
+        ctx.met = met
+        return K.spmm_csr(met.row_ptr, met.index, values, met.num_nodes, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        values, x = ctx.saved_tensors
+        met = ctx.met
+        g = g.contiguous()
+        gv = gx = None
+        if ctx.needs_input_grad[0]:
+            gv = K.pair_dot(g, met.index[0], x, met.index[1])
+        if ctx.needs_input_grad[1]:
+            gx = K.reduce_sparse(g, met.index[0], values, met.col_group)
+        return gv, gx, None
+
+
+def pan_spmm(met, x: Tensor) -> Tensor:
+    """``M x`` for the MET record ``met`` (device float32), differentiable in M's values and in ``x``."""
+    if _needs_grad(met.values, x):
+        return _PanSpmmFn.apply(met.values, x, met)
+    return K.spmm_csr(met.row_ptr, met.index, met.values, met.num_nodes, x)
+
+
+class _PanScoreFn(torch.autograd.Function):
+    """PAN pooling's score act(beta_0 <x_i, p> + beta_1 colsum_i(M)) as one node of the graph.  Backward from
+    g_t = g (1 - s^2) (tanh) or g:  dx = beta_0 g_t p^T,  dp = beta_0 x^T g_t,  dbeta = (<g_t, x p>, <g_t, colsum>),
+    dM_e = beta_1 g_t[col_e]."""
+
+    @staticmethod
+    def forward(ctx, x, p, beta, values, met, use_tanh):
+        s, dot, colsum = K.pan_score(x, p, beta, met.col_group, values, use_tanh, want_terms=True)
+        ctx.save_for_backward(x, p, beta, s, dot, colsum)
+        ctx.met, ctx.use_tanh = met, use_tanh
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        x, p, beta, s, dot, colsum = ctx.saved_tensors
+        gt = (torch.ops.aten.tanh_backward(g, s) if ctx.use_tanh else g).contiguous()
+        gx = gp = gb = gv = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g0 = (gt * beta[0]).contiguous()
+            if ctx.needs_input_grad[0]:
+                gx = g0.unsqueeze(1) * p.reshape(1, -1)
+            if ctx.needs_input_grad[1]:
+                gp = K.weighted_colsum(x, g0).view_as(p)
+        if ctx.needs_input_grad[2]:
+            gb = torch.stack([(gt * dot).sum(), (gt * colsum).sum()]).view_as(beta)
+        if ctx.needs_input_grad[3]:
+            gv = (gt * beta[1])[ctx.met.index[1]]
+        return gx, gp, gb, gv, None, None
+
+
+def pan_score(x: Tensor, p: Tensor, beta: Tensor, met, use_tanh: bool) -> Tensor:
+    """PAN pooling's score [N] on device float32 tensors (see :class:`_PanScoreFn`)."""
+    if _needs_grad(x, p, beta, met.values):
+        return _PanScoreFn.apply(x, p, beta, met.values, met, use_tanh)
+    return K.pan_score(x, p, beta, met.col_group, met.values, use_tanh)

@@ -4557,3 +4557,153 @@ def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor
     if want_factors:
         out["w"], out["ht"] = fac[0], fac[1]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ PAN (csrc/pan.hip)
+PAN_BAD_INPUT, PAN_CROSS_GRAPH, PAN_OVER_LIMIT = 1, 2, 4  # status bits of the tgp_pan_met_* entries
+PAN_MAX_FILTER = 64
+
+# edge lists the MET kernel declined before (an edge between two graphs), per graph offsets and node count: the same
+# list with other graphs (no batch vector: one graph) is tried again
+_PAN_DECLINED = TensorMemo(16)
+_PAN_MET = TensorMemo(16)       # the sparse M a PANConv returned -> its PanMet record (what PANPooling starts from)
+
+
+def pan_max_graph_nodes() -> int:
+    """Nodes of the largest graph whose MET rows the kernel keeps in LDS; one more takes the composed route."""
+    return int(N.lib().tgp_pan_max_graph_nodes())
+
+
+_PAN_ONE_GRAPH_PTR: dict = {}
+
+
+def pan_one_graph_ptr(n: int, device) -> Tensor:
+    """int32 [0, n] on ``device``: the node offsets of a single graph, kept for the last few sizes."""
+    key = (int(n), torch.device(device))
+    got = _PAN_ONE_GRAPH_PTR.get(key)
+    if got is None:
+        if len(_PAN_ONE_GRAPH_PTR) >= 8:
+            _PAN_ONE_GRAPH_PTR.clear()
+        got = _PAN_ONE_GRAPH_PTR[key] = torch.tensor([0, int(n)], dtype=torch.int32, device=device)
+    return got
+
+
+class PanMet:
+    """A MET matrix as the layers pass it on: ``index`` [2, nnz] (row-major sorted, coalesced), ``values`` [nnz] (the
+    tensor autograd tracks), ``row_ptr`` int32 [N + 1], and -- native route only -- ``dinv`` [N] and ``frame``, the
+    operands of the row walk that the backward repeats.  ``col_group`` is built on first use and kept."""
+
+    __slots__ = ("index", "values", "row_ptr", "dinv", "frame", "num_nodes", "_col_group", "__weakref__")
+
+    def __init__(self, index, values, row_ptr, num_nodes, dinv=None, frame=None):
+        self.index, self.values, self.row_ptr, self.num_nodes = index, values, row_ptr, int(num_nodes)
+        self.dinv, self.frame, self._col_group = dinv, frame, None
+
+    @property
+    def col_group(self) -> AssignIndex:
+        """M's entries grouped by column, row order inside a column: the order of the score's column sums and of
+        ``M^T g`` in the backward of ``M x``."""
+        if self._col_group is None:
+            self._col_group = edge_group(self.index, self.num_nodes, by_destination=True)
+        return self._col_group
+
+
+def pan_record(m: Tensor) -> Optional[PanMet]:
+    """The record :class:`tgp.nn.PANConv` left for the sparse matrix ``m`` it returned (None: not one of them)."""
+    return _PAN_MET.get(m)
+
+
+def pan_remember(m: Tensor, met: PanMet) -> None:
+    if not torch.cuda.is_current_stream_capturing():
+        _PAN_MET.put(m, met)
+
+
+def pan_route(edge_index: Tensor, weight: Tensor, num_nodes: int, graph_ptr: Optional[Tensor],
+              max_graph_nodes: Optional[int]) -> str:
+    """"native" for device tensors with float32 weights, nodes grouped by graph (``graph_ptr`` given) and a largest graph
+    within :func:`pan_max_graph_nodes`; "composed" for everything else, and for a list the kernel declined before."""
+    n, E = int(num_nodes), edge_index.size(1)
+    ok = (edge_index.is_cuda and weight.is_cuda and weight.dtype == torch.float32 and graph_ptr is not None
+          and max_graph_nodes is not None and n > 0 and 0 < int(max_graph_nodes) <= pan_max_graph_nodes()
+          and weight.numel() - 1 <= PAN_MAX_FILTER and E < 2 ** 31 and n * int(max_graph_nodes) < 2 ** 31
+          and _PAN_DECLINED.get(edge_index, other=graph_ptr, extra=n) is None)
+    return "native" if ok else "composed"
+
+
+def pan_met(edge_index: Tensor, weight: Tensor, num_nodes: int, gid: Optional[Tensor], graph_ptr: Tensor,
+            max_graph_nodes: int) -> Optional[PanMet]:
+    """The MET matrix of ``weight`` [L + 1] over the graphs ``graph_ptr`` (int32 [G + 1]; ``gid`` int32 [N] names every
+    node's graph, None for one graph): a count -> fill pair with its single host wait.  None when the kernel declines (an
+    edge whose endpoints lie in two graphs: remembered for this list and these graphs); an index outside its table
+    raises.  The count checks every edge of the list at its source node, so its verdict is complete before the fill."""
+    dev = N.require_device(edge_index, weight, gid, graph_ptr)
+    row, col = _edge_rows(edge_index)
+    n, E, G = int(num_nodes), row.numel(), graph_ptr.numel() - 1
+    w = N.f32c(weight.detach().reshape(-1))
+    if gid is not None and (gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous()):
+        raise ValueError(f"pan_met: gid must be a contiguous int32 [{n}]")
+    if graph_ptr.dtype != torch.int32 or G < 1 or not graph_ptr.is_contiguous() or w.numel() < 1:
+        raise ValueError("pan_met: graph_ptr must be a contiguous int32 [G + 1] and weight hold at least one entry")
+    by_src = sag_edge_group(edge_index, n, by_destination=False)  # (remembered per edge_index tensor)
+    L, st = N.lib(), N.stream_ptr(dev)
+    frame = (*by_src.walk(col, E), N.ptr(gid), N.ptr(graph_ptr), n, E, G, w.numel() - 1, int(max_graph_nodes))
+    keep = (by_src, col, gid, graph_ptr)  # what the pointers of `frame` point into
+    row_ptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    dinv = torch.empty(n, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def count(ws, nbytes, d_count):
+        _checked(L.tgp_pan_met_count, *frame, N.ptr(row_ptr), N.ptr(dinv), ws, nbytes, N.ptr(status), d_count, st)
+
+    def fill(ws, nnz, r, c, v):
+        _checked(L.tgp_pan_met_fill_f32, *frame, N.ptr(w), N.ptr(row_ptr), N.ptr(dinv), nnz, r, c, v, N.ptr(status), st)
+
+    out = _count_fill(dev, L.tgp_pan_met_workspace_bytes(n), count, fill, w_dtype=torch.float32, declines=True)
+    if isinstance(out, int):
+        bits = int(status.item())
+        if bits & PAN_BAD_INPUT:
+            raise IndexError("pan_met: an index outside its table (an edge endpoint or edge position out of range, a node "
+                             "outside its graph's range); nothing out of range was read")
+        if bits & PAN_OVER_LIMIT:
+            raise N.TgpNativeError(f"pan_met: a graph of more than max_graph_nodes = {max_graph_nodes} nodes")
+        if not torch.cuda.is_current_stream_capturing():
+            _PAN_DECLINED.put(edge_index, True, other=graph_ptr, extra=n)
+        return None
+    index, values = out
+    return PanMet(index, values, row_ptr, n, dinv, (frame, keep))
+
+
+def pan_met_bwd(met: PanMet, g_values: Tensor) -> Tensor:
+    """part [N, L + 1]: per row of ``met`` the gradient shares of the series coefficients ``c_n`` (their sum over the
+    rows is dL/dc), from the row powers recomputed in LDS."""
+    frame, _ = met.frame
+    dev = N.require_device(g_values, met.index, met.dinv)
+    g = N.f32c(g_values.reshape(-1))
+    nnz = met.index.size(1)
+    if g.numel() != nnz:
+        raise ValueError(f"pan_met_bwd: {g.numel()} gradient entries for {nnz} stored ones")
+    n, L = met.num_nodes, frame[8]
+    part = torch.zeros(n, L + 1, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _, col = _edge_rows(met.index)
+    _checked(N.lib().tgp_pan_met_bwd_f32, *frame, N.ptr(met.row_ptr), N.ptr(col) if nnz else None,
+             N.ptr(g) if nnz else None, N.ptr(met.dinv), nnz, N.ptr(part), N.ptr(status), N.stream_ptr(dev))
+    return part
+
+
+def pan_score(x: Tensor, p: Tensor, beta: Tensor, col_group: AssignIndex, values: Tensor, tanh: bool,
+              want_terms: bool = False):
+    """act(beta[0] <x_i, p> + beta[1] sum_{e: col(e) = i} values[e]) [N] in one launch, act = tanh or identity;
+    ``want_terms``: ``(score, dot, colsum)`` with the two terms as well (what the backward needs)."""
+    dev = N.require_device(x, p, beta, values, col_group.row_ptr)
+    x, ld = _row_operand(x, "pan_score")
+    p, beta, values = N.f32c(p.reshape(-1)), N.f32c(beta.reshape(-1)), N.f32c(values.reshape(-1))
+    n, F, nnz = x.size(0), x.size(1), values.numel()
+    if p.numel() != F or beta.numel() != 2 or col_group.num_targets != n or col_group.nnz != nnz:
+        raise ValueError(f"pan_score: x {tuple(x.shape)}, p of {p.numel()}, beta of {beta.numel()} entries and an index of "
+                         f"{col_group.nnz} entries over {col_group.num_targets} nodes against {nnz} values")
+    out = torch.empty(3 if want_terms else 1, n, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_pan_score_f32, N.ptr(x), n, F, ld, N.ptr(p), N.ptr(beta), N.ptr(col_group.row_ptr),
+             N.ptr(col_group.perm), N.ptr(values) if nnz else None, nnz, int(bool(tanh)), N.ptr(out[0]),
+             N.ptr(out[1]) if want_terms else None, N.ptr(out[2]) if want_terms else None, N.stream_ptr(dev))
+    return (out[0], out[1], out[2]) if want_terms else out[0]

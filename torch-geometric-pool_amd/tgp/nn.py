@@ -10,6 +10,9 @@ native project-then-aggregate scorer (``tgp.functions.sag_score``: one pass over
 ``GCNConv`` (any width, ``normalize=False`` only, not in ``__all__``) is the layer of MaxCutPool's score net: it carries
 PyG's names (``lin.weight``, ``bias``) and initialisation, and its forward is the composed form of
 ``tgp.poolers.MaxCutScoreNet``, whose native route reads the parameters directly (``tgp.functions.maxcut_score``).
+
+``PANConv`` (any width) is PyG's path-integral convolution, the layer in front of :class:`~tgp.poolers.PANPooling`: it
+returns ``(out, M)`` with ``M`` the maximal-entropy-transition matrix the pooler scores by.
 """
 from __future__ import annotations
 
@@ -158,4 +161,125 @@ class GCNConv(torch.nn.Module):
         return f"{self.in_channels}, {self.out_channels}"
 
 
-__all__ = ["GraphConv", "SAGEConv"]  # (SAGPooling's scorers; GCNConv is imported by name)
+def pan_met_composed(edge_index: Tensor, weight: Tensor, num_nodes: int):
+    """The MET matrix composed from torch operators, any device and float dtype: ``(index [2, nnz], values [nnz])``
+    row-major sorted and coalesced, the same pattern in the same order as the kernel's.  ``tmp_n`` is kept as a COO list;
+    the product with ``A_t`` expands every entry ``(r, k)`` by the edges ``j -> k`` (the by-destination group of ``k``)
+    and merges equal ``(r, j)``; the ``L + 1`` partial lists are then concatenated and merged once more -- PyG's scheme.
+    The pattern is structural (nothing is pruned by value), ``deg`` counts stored entries.  Differentiable in
+    ``weight`` through torch's own autograd."""
+    n, dev, dtype = int(num_nodes), edge_index.device, weight.dtype
+    src, dst = edge_index[0].long(), edge_index[1].long()
+    src_by_dst = src[torch.argsort(dst, stable=True)]
+    indeg = torch.bincount(dst, minlength=n)
+    first = torch.cumsum(indeg, 0) - indeg
+    ar = torch.arange(n, device=dev)
+    rows, cols, vals = ar, ar, weight[0].expand(n)
+    keys, terms = [ar * n + ar], [vals]
+    for step in range(1, weight.numel()):
+        cnt = indeg[cols]
+        rep = torch.repeat_interleave(torch.arange(cols.numel(), device=dev), cnt)
+        within = torch.arange(rep.numel(), device=dev) - (torch.cumsum(cnt, 0) - cnt)[rep]
+        key, inv = torch.unique(rows[rep] * n + src_by_dst[first[cols[rep]] + within], return_inverse=True)
+        vals = weight[step] * torch.zeros(key.numel(), dtype=dtype, device=dev).index_add(0, inv, vals[rep])
+        rows, cols = torch.div(key, n, rounding_mode="floor"), key % n
+        keys.append(key)
+        terms.append(vals)
+    key, inv = torch.unique(torch.cat(keys), return_inverse=True)
+    s = torch.zeros(key.numel(), dtype=dtype, device=dev).index_add(0, inv, torch.cat(terms))
+    rows, cols = torch.div(key, n, rounding_mode="floor"), key % n
+    dinv = torch.bincount(rows, minlength=n).to(dtype).pow(-0.5)
+    dinv = torch.where(torch.isinf(dinv), torch.zeros_like(dinv), dinv)
+    return torch.stack([rows, cols]), (dinv[cols] * s) * dinv[rows]
+
+
+class PANConv(torch.nn.Module):
+    r"""PyG's ``PANConv`` (Ma et al., NeurIPS 2020): :math:`\mathbf{X}' = \mathbf{M}\mathbf{X}\mathbf{W}` with the
+    maximal-entropy-transition matrix :math:`\mathbf{M} = \mathbf{D}^{-1/2} \sum_{n=0}^{L} c_n \mathbf{A}_t^n
+    \mathbf{D}^{-1/2}`, :math:`c_n = \prod_{i \le n}` ``weight[i]``.  Parameters ``lin.weight`` [out, in], ``lin.bias``
+    [out] and ``weight`` [L + 1] (reset to 0.5), PyG's names.
+
+    ``forward(x, edge_index, batch=None) -> (out, M)``.  ``A_t[dst, src]`` counts the occurrences of the edge ``src ->
+    dst`` (edge values are ignored, duplicates count, self-loops stay); a sparse ``edge_index`` is read as ``A_t`` itself
+    (row = target), as PyG reads an ``adj_t``.  The stored pattern of ``M`` is structural -- ``(i, j)`` is kept iff a
+    walk of at most ``L`` edges joins them, whatever the value -- and ``D`` counts the stored entries of a row.  ``M``
+    comes back as a coalesced torch sparse COO tensor ``[N, N]`` with row = target; it is a
+    ``torch_sparse.SparseTensor`` only when that package is importable and the input was one (this build does not
+    depend on it).
+
+    ``batch`` tells the native route where the graphs are; without it the whole input is one graph.  Device float32
+    inputs whose nodes are grouped by graph, with every edge inside one graph and no graph beyond
+    ``kernels.pan_max_graph_nodes()`` nodes, take the row kernels of ``csrc/pan.hip`` (no sparse-sparse product, no
+    sort); larger graphs, float64, edges between graphs and host tensors take :func:`pan_met_composed`."""
+
+    def __init__(self, in_channels: int, out_channels: int, filter_size: int, **kwargs):
+        super().__init__()
+        if kwargs.pop("aggr", "add") != "add" or kwargs:
+            raise NotImplementedError(f"PANConv: only aggr='add' and no further arguments are implemented, got {kwargs}")
+        if int(filter_size) < 0:
+            raise ValueError(f"PANConv: filter_size must not be negative, got {filter_size}")
+        self.in_channels, self.out_channels, self.filter_size = in_channels, out_channels, int(filter_size)
+        self.lin = torch.nn.Linear(in_channels, out_channels)
+        self.weight = torch.nn.Parameter(torch.empty(self.filter_size + 1))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.lin.reset_parameters()
+        self.weight.data.fill_(0.5)
+
+    def met(self, edge_index: Tensor, num_nodes: int, batch: Optional[Tensor] = None):
+        """The MET record of ``edge_index`` [2, E]: a ``kernels.PanMet`` (``index``, ``values`` tracked back to
+        ``weight``, ``row_ptr``) from the native route, or from the composed form (``frame`` None)."""
+        from . import kernels as K
+        from .utils.ops import batch_info
+        n, dev = int(num_nodes), edge_index.device
+        graph_ptr = gid = longest = None
+        if edge_index.is_cuda and self.weight.is_cuda and n > 0:
+            if batch is None:
+                graph_ptr, longest = K.pan_one_graph_ptr(n, dev), n
+            elif batch.numel() == n:
+                info = batch_info(batch)
+                if info.is_sorted:
+                    facts = info.memo.get("pan")
+                    if facts is None:
+                        facts = info.memo["pan"] = (info.ptr.to(torch.int32), batch.to(torch.int32))
+                    (graph_ptr, gid), longest = facts, info.max_nodes
+        if K.pan_route(edge_index, self.weight, n, graph_ptr, longest) == "native":
+            met = Fn.pan_met(edge_index, self.weight, n, gid, graph_ptr, longest)
+            if met is not None:
+                return met
+        index, values = pan_met_composed(edge_index, self.weight, n)
+        row_ptr = None
+        if index.is_cuda and values.dtype == torch.float32:
+            row_ptr = K.rowptr_from_sorted(index[0], n, torch.empty(n + 1, dtype=torch.int32, device=dev))
+        return K.PanMet(index, values, row_ptr, n)
+
+    def forward(self, x: Tensor, edge_index, batch: Optional[Tensor] = None):
+        from . import kernels as K
+        from .imports import is_sparsetensor
+        was_sparsetensor = is_sparsetensor(edge_index)
+        if not isinstance(edge_index, Tensor) or edge_index.layout != torch.strided:
+            from .utils.ops import connectivity_to_edge_index
+            if isinstance(edge_index, Tensor) and edge_index.layout != torch.sparse_coo:
+                edge_index = edge_index.to_sparse_coo()
+            edge_index, _ = connectivity_to_edge_index(edge_index, None)
+            edge_index = edge_index.flip(0)  # (a sparse input is A_t: its rows are the targets)
+        n = x.size(0)
+        met = self.met(edge_index, n, batch)
+        if met.row_ptr is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2:
+            out = Fn.linear(Fn.pan_spmm(met, x), self.lin.weight, self.lin.bias)
+        else:
+            out = self.lin(torch.zeros_like(x).index_add(0, met.index[0], met.values.view(-1, 1) * x[met.index[1]]))
+        m = torch.sparse_coo_tensor(met.index, met.values, (n, n), is_coalesced=True)
+        if met.row_ptr is not None:
+            K.pan_remember(m, met)
+        if was_sparsetensor:  # pragma: no cover  (torch_sparse is not a dependency of this build)
+            from torch_sparse import SparseTensor
+            m = SparseTensor(row=met.index[0], col=met.index[1], value=met.values, sparse_sizes=(n, n), is_sorted=True)
+        return out, m
+
+    def extra_repr(self) -> str:
+        return f"{self.in_channels}, {self.out_channels}, filter_size={self.filter_size}"
+
+
+__all__ = ["GraphConv", "SAGEConv"]  # (SAGPooling's scorers; GCNConv and PANConv are imported by name)

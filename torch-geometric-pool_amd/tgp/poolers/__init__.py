@@ -71,6 +71,7 @@ from .asap import ASAPooling
 from .maxcut import MaxCutPooling, MaxCutScoreNet, MaxCutSelect
 from .eigenpool import EigenPoolConnect, EigenPoolLift, EigenPoolReduce, EigenPoolSelect, EigenPooling
 from .nmf import NMFPooling, NMFSelect
+from .pan import PANPooling
 
 import os as _os
 
@@ -1576,8 +1577,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling), "eigen" (EigenPooling) and "nmf" (NMFPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "NMFPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling), "eigen" (EigenPooling), "nmf" (NMFPooling) and "pan" (PANPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "NMFPooling", "PANPooling", "SAGPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,
