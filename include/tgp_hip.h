@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32; PAN: tgp_pan_max_graph_nodes, tgp_pan_met_workspace_bytes, tgp_pan_met_count, tgp_pan_met_fill_f32, tgp_pan_met_bwd_f32, tgp_pan_score_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32; PAN: tgp_pan_max_graph_nodes, tgp_pan_met_workspace_bytes, tgp_pan_met_count, tgp_pan_met_fill_f32, tgp_pan_met_bwd_f32, tgp_pan_score_f32; GTVConv: tgp_gtv_edge_fwd_f32, tgp_gtv_edge_bwd_terms_f32, tgp_gtv_edge_bwd_nodes_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -1788,6 +1788,41 @@ int tgp_pan_score_f32(const float* x, int64_t N, int64_t F, int64_t ldx, const f
                       const int32_t* col_ptr, const int32_t* col_perm /* NULL ok */, const float* val, int64_t nnz,
                       int act, float* score, float* dot_out /* NULL ok */, float* colsum_out /* NULL ok */,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * GTVConv's propagation (reference mp/gtvconv.py), csrc/gtvconv.hip.  With h = x W [N, C] already projected:
+ *     out_i = act((h_i + delta sum_{e: row(e) = i, col(e) != i} gamma_e (h_col(e) - h_i) + bias) [* mask_i]),
+ *     d_e = ||h_row(e) - h_col(e)||_1,  gamma_e = w_e / max(d_e, eps)  (w NULL: 1).
+ * A group of 8, 16, 32 or 64 lanes owns a node and keeps h_i in registers; every h_col is loaded once per edge (twice
+ * beyond 512 channels) and nothing of size E x C is formed.  Sums over a node's edges run in the order of the by-source
+ * index (src_ptr [N + 1], src_perm [E] or NULL for a list that is grouped already) and, in the node gradient, of the
+ * by-destination index (dst_ptr, dst_perm) after it: edge-list order inside a node, no float atomics, the same bits on
+ * every call.  A self-loop, an edge with an endpoint outside [0, N) and an index position outside [0, E) are skipped and
+ * never dereferenced; their d, gw and t entries are left as the caller initialised them (zeros).
+ *   fwd:       act_code 0 identity, 1 relu, 2 elu (alpha 1); mask [N] bytes (NULL ok, 0 = the row becomes act(0));
+ *              d [E] (NULL ok up to 512 channels) receives the distances a backward needs.
+ *   bwd_terms: g [N, C] = g_out act'(out) mask; per edge s_e = delta <g_i, h_col - h_i>, gw_e = s_e / max(d_e, eps)
+ *              (gw NULL ok: the gradient of w), t_e = -s_e gamma_e / d_e where d_e >= eps, else 0.
+ *   bwd_nodes: dh_i = g_i (1 - delta sum_out gamma_e) + sum_out t_e sign(h_i - h_col)
+ *                   + sum_in (delta gamma_e g_row - t_e sign(h_row - h_i)),  sign(0) = 0.
+ * Vector loads are used when C % 4 == 0 and every row buffer is 16-byte aligned.  nodes == 0 returns TGP_OK.
+ * TGP_ERR_INVALID: a NULL input or output, sizes below zero, C < 1, an unknown act_code; TGP_ERR_RANGE: nodes or E >= 2^31
+ * or C >= 32768.  All are found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_gtv_edge_fwd_f32(const float* h, int64_t nodes, int64_t C, const int32_t* src_ptr,
+                         const int32_t* src_perm /* NULL ok */, const int64_t* col, const float* w /* NULL ok */,
+                         int64_t E, const float* bias /* NULL ok */, const uint8_t* mask /* NULL ok */, float delta,
+                         float eps, int act_code, float* out, float* d /* NULL ok */, void* stream);
+int tgp_gtv_edge_bwd_terms_f32(const float* h, const float* out, const float* g_out, int64_t nodes, int64_t C,
+                               const int32_t* src_ptr, const int32_t* src_perm /* NULL ok */, const int64_t* col,
+                               const float* w /* NULL ok */, int64_t E, const float* d, const uint8_t* mask /* NULL ok */,
+                               float delta, float eps, int act_code, float* g, float* gw /* NULL ok */, float* t,
+                               void* stream);
+int tgp_gtv_edge_bwd_nodes_f32(const float* h, const float* g, int64_t nodes, int64_t C, const int32_t* src_ptr,
+                               const int32_t* src_perm /* NULL ok */, const int32_t* dst_ptr,
+                               const int32_t* dst_perm /* NULL ok */, const int64_t* row, const int64_t* col,
+                               const float* w /* NULL ok */, int64_t E, const float* d, const float* t, float delta,
+                               float eps, float* dh, void* stream);
 
 #ifdef __cplusplus
 }

@@ -410,6 +410,12 @@ SIGNATURES = {
                                      _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "tgp_pan_score_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p,
                                    _c_p, _c_p, _c_p]),
+    "tgp_gtv_edge_fwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_f, _c_f, _c_int,
+                                      _c_p, _c_p, _c_p]),
+    "tgp_gtv_edge_bwd_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p,
+                                            _c_f, _c_f, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_gtv_edge_bwd_nodes_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
+                                            _c_p, _c_p, _c_f, _c_f, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1916,3 +1916,56 @@ def pan_score(x: Tensor, p: Tensor, beta: Tensor, met, use_tanh: bool) -> Tensor
     if _needs_grad(x, p, beta, met.values):
         return _PanScoreFn.apply(x, p, beta, met.values, met, use_tanh)
     return K.pan_score(x, p, beta, met.col_group, met.values, use_tanh)
+
+
+class _GtvPropagateFn(torch.autograd.Function):
+    """GTVConv's propagation of the projected rows as one node of the graph (csrc/gtvconv.hip): one launch forward; the
+    backward is the edge-terms launch (g, the weight gradient and the gradient of every distance) and the node launch
+    (dh over out-edges and in-edges, no scatter).  The bias gradient is ``g.sum(0)``."""
+
+    @staticmethod
+    def forward(ctx, h, edge_weight, bias, row, col, mask, delta, eps, act_code, by_src, dst_index):
+        need = any(ctx.needs_input_grad[:3])
+        out, d = K.gtv_edge_fwd(h, col, edge_weight, by_src, bias, mask, delta, eps, act_code, want_d=need)
+        if need:
+            ctx.save_for_backward(h, out, edge_weight, d, row, col, mask)
+            ctx.args = (delta, eps, act_code, by_src, dst_index)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        h, out, w, d, row, col, mask = ctx.saved_tensors
+        delta, eps, act_code, by_src, dst_index = ctx.args
+        g, gw, t = K.gtv_edge_bwd_terms(h, out, g_out, col, w, by_src, d, mask, delta, eps, act_code,
+                                        want_gw=ctx.needs_input_grad[1])
+        dh = gb = None
+        if ctx.needs_input_grad[0]:
+            dh = K.gtv_edge_bwd_nodes(h, g, row, col, w, by_src, dst_index(), d, t, delta, eps)
+        if ctx.needs_input_grad[2]:
+            gb = g.sum(0)
+        return dh, gw, gb, None, None, None, None, None, None, None, None
+
+
+def gtv_propagate(h: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], bias: Optional[Tensor],
+                  mask: Optional[Tensor], delta: float, eps: float, act_code: int, by_src=None) -> Tensor:
+    """act((h_i + delta sum_{e: row = i, col != i} w_e / max(||h_i - h_col||_1, eps) (h_col - h_i) + bias) [* mask_i])
+    on device float32 tensors: ``h`` [N, C] contiguous, ``edge_weight`` [E] or None, ``bias`` [C] or None, ``mask`` [N]
+    bool or None, ``act_code`` 0 identity / 1 relu / 2 elu.  Gradients for ``h``, ``edge_weight`` and ``bias``.  The sums
+    run over the by-source edge index (remembered per ``edge_index`` object; ``by_src``: the caller's own, for a list it
+    knows to be grouped) and, in the backward, the by-destination one.  Edges with an end outside [0, N) are taken out
+    first -- the result is that of the list without them -- and self-loops are skipped by the kernels."""
+    n = h.size(0)
+    if by_src is None:
+        keep = K.gtv_edges_in_range(edge_index, n)
+        if keep is not None:
+            # (a fresh list per call: its indexes are rebuilt; such input is an error case, not a workload)
+            edge_index = edge_index[:, keep].contiguous()
+            edge_weight = None if edge_weight is None else edge_weight[keep]
+        by_src = K.sag_edge_group(edge_index, n, by_destination=False)
+        dst_index = lambda: K.sag_edge_group(edge_index, n, by_destination=True)  # noqa: E731
+    else:
+        dst_index = lambda: K.edge_group(edge_index, n, by_destination=True)  # noqa: E731
+    row, col = K._edge_rows(edge_index)
+    if _needs_grad(h, edge_weight, bias):
+        return _GtvPropagateFn.apply(h, edge_weight, bias, row, col, mask, delta, eps, act_code, by_src, dst_index)
+    return K.gtv_edge_fwd(h, col, edge_weight, by_src, bias, mask, delta, eps, act_code)[0]

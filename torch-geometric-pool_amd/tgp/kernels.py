@@ -4707,3 +4707,151 @@ def pan_score(x: Tensor, p: Tensor, beta: Tensor, col_group: AssignIndex, values
              N.ptr(col_group.perm), N.ptr(values) if nnz else None, nnz, int(bool(tanh)), N.ptr(out[0]),
              N.ptr(out[1]) if want_terms else None, N.ptr(out[2]) if want_terms else None, N.stream_ptr(dev))
     return (out[0], out[1], out[2]) if want_terms else out[0]
+
+
+# ------------------------------------------------------------------------------------------ GTVConv (csrc/gtvconv.hip)
+GTV_ACT_CODES = {"identity": 0, "relu": 1, "elu": 2}  # the activations the forward kernel applies itself
+GTV_MAX_CHANNELS = 32767
+GTV_REGISTER_CHANNELS = 512  # wider rows take the chunked kernels, which need the distance buffer in the forward too
+
+# How the last call of :class:`tgp.mp.GTVConv` / ``tgp.mp.gtv_propagate`` was served, and how many calls each route took
+GTV_RECORD = {"route": None, "native": 0, "composed": 0}
+
+_GTV_VALID = TensorMemo(16)  # edge_index (+ node count) -> True, or the positions of the edges with both ends in range
+
+
+def gtv_record() -> dict:
+    """A copy of the route record: ``route`` ("native" / "composed") of the last call and the two counters."""
+    return dict(GTV_RECORD)
+
+
+def gtv_note(route: str) -> None:
+    GTV_RECORD["route"] = route
+    GTV_RECORD[route] += 1
+
+
+def gtv_edges_in_range(edge_index: Tensor, num_nodes: int):
+    """None when every endpoint lies in [0, num_nodes); otherwise the positions (int64, ascending) of the edges whose
+    ends both do.  One host wait per ``edge_index`` object, remembered: the edge indexes are built from the sources and
+    the destinations, so a list is only handed to them with every id in range."""
+    got = _GTV_VALID.get(edge_index, extra=int(num_nodes))
+    if got is None:
+        if edge_index.numel() == 0:
+            got = True
+        else:
+            ok = ((edge_index >= 0) & (edge_index < num_nodes)).all(dim=0)
+            got = True if bool(ok.all()) else ok.nonzero().view(-1)
+        if not torch.cuda.is_current_stream_capturing():
+            _GTV_VALID.put(edge_index, got, extra=int(num_nodes))
+    return None if got is True else got
+
+
+def _gtv_frame(who: str, h: Tensor, col: Tensor, edge_weight: Optional[Tensor], by_src: AssignIndex):
+    """Shapes of what every GTV entry shares, checked before any launch: (n, C, E, w)."""
+    if h.dim() != 2 or h.dtype != torch.float32 or not h.is_contiguous():
+        raise ValueError(f"{who}: h must be a contiguous float32 [N, C], got {h.dtype} {tuple(h.shape)}")
+    n, C = h.shape
+    if not 1 <= C <= GTV_MAX_CHANNELS:
+        raise ValueError(f"{who}: {C} channels (1 .. {GTV_MAX_CHANNELS})")
+    if col.dim() != 1 or col.dtype != torch.int64 or not col.is_contiguous():
+        raise ValueError(f"{who}: the edge rows must be contiguous int64 vectors")
+    E = col.numel()
+    if E >= 2 ** 31 or n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} nodes and {E} edges are beyond the int32 index")
+    if by_src.num_targets != n or by_src.nnz != E or by_src.row_ptr.numel() != n + 1 or (
+            by_src.perm is not None and E and by_src.perm.numel() < E):
+        raise ValueError(f"{who}: an index of {by_src.nnz} edges over {by_src.num_targets} nodes against {E} edges over "
+                         f"{n} nodes")
+    w = edge_weight
+    if w is not None and (w.dim() != 1 or w.numel() != E or w.dtype != torch.float32):
+        raise ValueError(f"{who}: edge_weight must be float32 [{E}], got {w.dtype} {tuple(w.shape)}")
+    return n, C, E, (None if w is None else N.f32c(w))
+
+
+def _gtv_mask(who: str, mask: Optional[Tensor], n: int) -> Optional[Tensor]:
+    if mask is None:
+        return None
+    if mask.numel() != n or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: mask must hold one bool per node ({n}), got {mask.dtype} {tuple(mask.shape)}")
+    return mask.reshape(-1).contiguous().view(torch.uint8)
+
+
+def _gtv_row_like(who: str, name: str, t: Tensor, h: Tensor) -> Tensor:
+    if t.shape != h.shape or t.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} {t.dtype} {tuple(t.shape)} does not match h {tuple(h.shape)}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def gtv_edge_fwd(h: Tensor, col: Tensor, edge_weight: Optional[Tensor], by_src: AssignIndex, bias: Optional[Tensor],
+                 mask: Optional[Tensor], delta: float, eps: float, act_code: int, want_d: bool = False):
+    """(out [N,C], d [E] or None): GTVConv's propagation of the projected rows ``h`` (mp/gtvconv.py:137-167),
+    out_i = act((h_i + delta sum over i's out-edges of w_e / max(d_e, eps) (h_col - h_i) + bias) [* mask_i]) with
+    d_e = ||h_i - h_col||_1, one pass over every node's out-edges in the order of ``by_src``; self-loops and edges with
+    an end out of range are skipped.  ``want_d``: the distances as well (what a backward needs; 0 at a skipped edge)."""
+    who = "gtv_edge_fwd"
+    n, C, E, w = _gtv_frame(who, h, col, edge_weight, by_src)
+    if act_code not in (0, 1, 2):
+        raise ValueError(f"{who}: act_code {act_code} (0 identity, 1 relu, 2 elu)")
+    b = None
+    if bias is not None:
+        if bias.numel() != C or bias.dtype != torch.float32:
+            raise ValueError(f"{who}: bias must be float32 [{C}], got {bias.dtype} {tuple(bias.shape)}")
+        b = N.f32c(bias.reshape(-1))
+    m = _gtv_mask(who, mask, n)
+    dev = N.require_device(h, col, w, b, m)
+    out = torch.empty_like(h)
+    d = torch.zeros(E, dtype=torch.float32, device=dev) if (want_d or C > GTV_REGISTER_CHANNELS) and E else None
+    src_ptr, src_perm, col_p = by_src.walk(col, E)
+    _checked(N.lib().tgp_gtv_edge_fwd_f32, N.ptr(h), n, C, src_ptr, src_perm, col_p, N.ptr(w), E, N.ptr(b), N.ptr(m),
+             float(delta), float(eps), int(act_code), N.ptr(out), N.ptr(d), N.stream_ptr(dev))
+    if want_d and d is None:
+        d = torch.zeros(0, dtype=torch.float32, device=dev)
+    return out, (d if want_d else None)
+
+
+def gtv_edge_bwd_terms(h: Tensor, out: Tensor, g_out: Tensor, col: Tensor, edge_weight: Optional[Tensor],
+                       by_src: AssignIndex, d: Tensor, mask: Optional[Tensor], delta: float, eps: float, act_code: int,
+                       want_gw: bool = False):
+    """(g [N,C], gw [E] or None, t [E]) of the propagation's backward: g = g_out act'(out) mask, per out-edge
+    s_e = delta <g_i, h_col - h_i>, gw_e = s_e / max(d_e, eps) (the gradient of the edge weight) and the gradient of
+    d_e, t_e = -s_e gamma_e / d_e where d_e >= eps and 0 where the clamp holds (zeros at a skipped edge)."""
+    who = "gtv_edge_bwd_terms"
+    n, C, E, w = _gtv_frame(who, h, col, edge_weight, by_src)
+    out, g_out = _gtv_row_like(who, "out", out, h), _gtv_row_like(who, "g_out", g_out, h)
+    if d.numel() != E or d.dtype != torch.float32 or act_code not in (0, 1, 2):
+        raise ValueError(f"{who}: d must be float32 [{E}] and act_code one of 0, 1, 2")
+    m = _gtv_mask(who, mask, n)
+    dev = N.require_device(h, out, g_out, col, w, d, m)
+    g = torch.empty_like(h)
+    terms = torch.zeros(2 if want_gw else 1, max(E, 1), dtype=torch.float32, device=dev)
+    src_ptr, src_perm, col_p = by_src.walk(col, E)
+    _checked(N.lib().tgp_gtv_edge_bwd_terms_f32, N.ptr(h), N.ptr(out), N.ptr(g_out), n, C, src_ptr, src_perm, col_p,
+             N.ptr(w), E, N.ptr(N.f32c(d)), N.ptr(m), float(delta), float(eps), int(act_code), N.ptr(g),
+             N.ptr(terms[1]) if want_gw else None, N.ptr(terms[0]), N.stream_ptr(dev))
+    return g, (terms[1, :E] if want_gw else None), terms[0, :E]
+
+
+def gtv_edge_bwd_nodes(h: Tensor, g: Tensor, row: Tensor, col: Tensor, edge_weight: Optional[Tensor],
+                       by_src: AssignIndex, by_dst: AssignIndex, d: Tensor, t: Tensor, delta: float,
+                       eps: float) -> Tensor:
+    """dh [N,C]: every node adds over its out-edges and then its in-edges (no scatter),
+    dh_i = g_i (1 - delta sum_out gamma_e) + sum_out t_e sign(h_i - h_col) + sum_in (delta gamma_e g_row - t_e
+    sign(h_row - h_i))."""
+    who = "gtv_edge_bwd_nodes"
+    n, C, E, w = _gtv_frame(who, h, col, edge_weight, by_src)
+    g = _gtv_row_like(who, "g", g, h)
+    if row.shape != col.shape or row.dtype != torch.int64 or not row.is_contiguous():
+        raise ValueError(f"{who}: the edge rows must be contiguous int64 vectors of one length")
+    if by_dst.num_targets != n or by_dst.nnz != E or by_dst.row_ptr.numel() != n + 1:
+        raise ValueError(f"{who}: a by-destination index of {by_dst.nnz} edges over {by_dst.num_targets} nodes against "
+                         f"{E} edges over {n} nodes")
+    if d.numel() != E or t.numel() != E or d.dtype != torch.float32 or t.dtype != torch.float32:
+        raise ValueError(f"{who}: d and t must be float32 [{E}]")
+    dev = N.require_device(h, g, row, col, w, d, t)
+    dh = torch.empty_like(h)
+    src_ptr, src_perm, col_p = by_src.walk(col, E)
+    dst_ptr, dst_perm, row_p = by_dst.walk(row, E)
+    _checked(N.lib().tgp_gtv_edge_bwd_nodes_f32, N.ptr(h), N.ptr(g), n, C, src_ptr, src_perm, dst_ptr, dst_perm, row_p,
+             col_p, N.ptr(w), E, N.ptr(N.f32c(d)), N.ptr(N.f32c(t)), float(delta), float(eps), N.ptr(dh),
+             N.stream_ptr(dev))
+    return dh

@@ -8,7 +8,8 @@
 (``tgp/poolers/asap.py``), ``MaxCutPooling`` (``tgp/poolers/maxcut.py``), ``EigenPooling`` (``tgp/poolers/eigenpool.py``)
 and ``NMFPooling`` (``tgp/poolers/nmf.py``) are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` /
 ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` / ``asap`` / ``maxcut`` / ``eigen`` / ``nmf`` aliases are not
-registered yet.
+registered yet.  The message-passing layer the TVGNN model puts in front of ``AsymCheegerCutPooling`` is ``tgp.mp.GTVConv``
+(reference tgp/mp/gtvconv.py).
 """
 from __future__ import annotations
 
