@@ -1824,6 +1824,33 @@ int tgp_gtv_edge_bwd_nodes_f32(const float* h, const float* g, int64_t nodes, in
                                const float* w /* NULL ok */, int64_t E, const float* d, const float* t, float delta,
                                float eps, float* dh, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * SEP pooling's selector (Wu et al., ICML 2022; reference select/sep_select.py with levels = 1; DESIGN 4.26;
+ * csrc/sep_select.hip): per graph a structural-entropy coding tree grown by greedy merging and compressed to height 2;
+ * every node is labelled with its depth-1 cluster.  One workgroup per graph, all graphs in one launch, then two small
+ * launches: the exclusive prefix of the per-graph counts and its addition to the labels.
+ *   src_ptr / src_perm, dst_ptr / dst_perm: the edge positions grouped by source and by destination, edge-list order
+ *   inside a node (perm NULL: the list is grouped already); src, dst [E] the two edge rows; edge_weight [E] or NULL (1).
+ *   gid [N] the graph of every node; graph_ptr [G + 1]: graph g owns the nodes graph_ptr[g] .. graph_ptr[g + 1] - 1 (a
+ *   sorted batch vector).  max_n in 1 .. tgp_sep_max_nodes() sizes the LDS frame (an upper bound of the largest graph
+ *   the kernel is to take); tgp_sep_max_nodes() is what fits the 160 KiB of a CU.
+ * Outputs: cluster_index [N] int64 (ids offset by the exclusive prefix of the counts, in graph order), counts [G],
+ * offsets [G], words [2] = {status, number of supernodes}; counts and words are zeroed by the call.  Status bits:
+ * 1 = an index outside its table (an edge position, endpoint or CSR offset out of range, a node whose gid is not its
+ * graph, an edge between two graphs), 2 = a non-finite or negative weight after duplicates are summed, 4 = a graph of
+ * more than max_n nodes.  A flagged graph is left unwritten (its count stays 0 and its cluster_index entries are not
+ * touched); nothing out of range is dereferenced.  Self-loops are dropped.  The same input gives the same bits, wherever
+ * the graph stands in the batch.  G == 0 or N == 0 returns TGP_OK.
+ * TGP_ERR_INVALID: a NULL pointer, a negative size, max_n outside its range; TGP_ERR_RANGE: N, E or G >= 2^31.  All are
+ * found before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+int tgp_sep_max_nodes(void);
+int tgp_sep_select_f32(const int32_t* src_ptr, const int32_t* src_perm /* NULL ok */, const int32_t* dst_ptr,
+                       const int32_t* dst_perm /* NULL ok */, const int64_t* src, const int64_t* dst,
+                       const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* graph_ptr, int64_t N,
+                       int64_t E, int64_t G, int64_t max_n, int64_t* cluster_index, int32_t* counts, int32_t* offsets,
+                       int32_t* words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

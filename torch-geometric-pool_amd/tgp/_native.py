@@ -416,6 +416,9 @@ SIGNATURES = {
                                             _c_f, _c_f, _c_int, _c_p, _c_p, _c_p, _c_p]),
     "tgp_gtv_edge_bwd_nodes_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
                                             _c_p, _c_p, _c_f, _c_f, _c_p, _c_p]),
+    "tgp_sep_max_nodes": (_c_int, []),
+    "tgp_sep_select_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
+                                    _c_p, _c_p, _c_p, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -4559,6 +4559,48 @@ def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor
     return out
 
 
+# ------------------------------------------------------------------------------------------------ SEP (csrc/sep_select.hip)
+SEP_BAD_INPUT, SEP_BAD_WEIGHT, SEP_OVER_LIMIT = 1, 2, 4  # status bits of tgp_sep_select_f32
+
+
+def sep_max_nodes() -> int:
+    """Nodes of the largest graph whose coding tree the SEP kernel grows in LDS; one more takes the host route."""
+    return int(N.lib().tgp_sep_max_nodes())
+
+
+def sep_select(edge_index: Tensor, edge_weight: Optional[Tensor], gid: Tensor, graph_ptr: Tensor, num_nodes: int,
+               max_n: int, cluster_index: Optional[Tensor] = None) -> dict:
+    """The per-graph SEP selector (three launches, one host wait): ``cluster_index`` [N] int64 (left as it was for a
+    flagged graph; ``cluster_index`` given: that tensor is written), ``counts`` / ``offsets`` [G] int32, ``status`` (a
+    host int, bits ``SEP_*``) and ``total``, the number of supernodes of the graphs that were written."""
+    dev = N.require_device(edge_index, edge_weight, gid, graph_ptr)
+    n, G = int(num_nodes), graph_ptr.numel() - 1
+    row, col = _edge_rows(edge_index)
+    E = row.numel()
+    ew = N.opt_f32_flat(edge_weight)
+    if gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
+        raise ValueError(f"sep_select: gid must be a contiguous int32 [{n}]")
+    if graph_ptr.dtype != torch.int32 or G < 0 or not graph_ptr.is_contiguous():
+        raise ValueError("sep_select: graph_ptr must be a contiguous int32 [G + 1]")
+    if ew is not None and ew.numel() != E:
+        raise ValueError(f"sep_select: {ew.numel()} weights for {E} edges")
+    by_src = sag_edge_group(edge_index, n, by_destination=False)  # (remembered per edge_index tensor)
+    by_dst = sag_edge_group(edge_index, n, by_destination=True)
+    if cluster_index is None:
+        cluster_index = torch.empty(n, dtype=torch.int64, device=dev)
+    elif cluster_index.dtype != torch.int64 or cluster_index.numel() != n or not cluster_index.is_contiguous():
+        raise ValueError(f"sep_select: cluster_index must be a contiguous int64 [{n}]")
+    counts = torch.empty(2, max(G, 1), dtype=torch.int32, device=dev)
+    words = torch.empty(2, dtype=torch.int32, device=dev)
+    _checked(N.lib().tgp_sep_select_f32, N.ptr(by_src.row_ptr), N.ptr(by_src.perm), N.ptr(by_dst.row_ptr),
+             N.ptr(by_dst.perm), N.ptr(row) if E else None, N.ptr(col) if E else None, N.ptr(ew), N.ptr(gid),
+             N.ptr(graph_ptr), n, E, G, int(max_n), N.ptr(cluster_index), N.ptr(counts[0]), N.ptr(counts[1]),
+             N.ptr(words), N.stream_ptr(dev))
+    status, total = words.tolist()  # the call's one host wait
+    return {"cluster_index": cluster_index, "counts": counts[0, :G], "offsets": counts[1, :G], "status": status,
+            "total": total}
+
+
 # ------------------------------------------------------------------------------------------------ PAN (csrc/pan.hip)
 PAN_BAD_INPUT, PAN_CROSS_GRAPH, PAN_OVER_LIMIT = 1, 2, 4  # status bits of the tgp_pan_met_* entries
 PAN_MAX_FILTER = 64

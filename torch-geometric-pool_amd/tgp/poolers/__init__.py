@@ -6,9 +6,9 @@
 ``ValueError("Unknown pooler_name=...")`` an unknown name does.  ``DMoNPooling``, ``AsymCheegerCutPooling``,
 ``HOSCPooling``, ``BNPool``, ``JustBalancePooling``, ``EdgeContractionPooling``, ``LaPooling``, ``SAGPooling``, ``ASAPooling``
 (``tgp/poolers/asap.py``), ``MaxCutPooling`` (``tgp/poolers/maxcut.py``), ``EigenPooling`` (``tgp/poolers/eigenpool.py``)
-and ``NMFPooling`` (``tgp/poolers/nmf.py``) are built and exported as classes; their ``dmon`` / ``acc`` / ``hosc`` /
-``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` / ``asap`` / ``maxcut`` / ``eigen`` / ``nmf`` aliases are not
-registered yet.  The message-passing layer the TVGNN model puts in front of ``AsymCheegerCutPooling`` is ``tgp.mp.GTVConv``
+``NMFPooling`` (``tgp/poolers/nmf.py``) and ``SEPPooling`` (``tgp/poolers/sep.py``) are built and exported as classes;
+their ``dmon`` / ``acc`` / ``hosc`` / ``bnpool`` / ``jb`` / ``edgepool`` / ``lap`` / ``sag`` / ``asap`` / ``maxcut`` /
+``eigen`` / ``nmf`` / ``sep`` aliases are not registered yet.  The message-passing layer the TVGNN model puts in front of ``AsymCheegerCutPooling`` is ``tgp.mp.GTVConv``
 (reference tgp/mp/gtvconv.py).
 """
 from __future__ import annotations
@@ -73,6 +73,7 @@ from .maxcut import MaxCutPooling, MaxCutScoreNet, MaxCutSelect
 from .eigenpool import EigenPoolConnect, EigenPoolLift, EigenPoolReduce, EigenPoolSelect, EigenPooling
 from .nmf import NMFPooling, NMFSelect
 from .pan import PANPooling
+from .sep import SEPPooling, SEPSelect
 
 import os as _os
 
@@ -1578,8 +1579,8 @@ class LaPooling(DenseSRCPooling):
 
 
 # =============================================================================== factory
-# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling), "eigen" (EigenPooling), "nmf" (NMFPooling) and "pan" (PANPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
-pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "NMFPooling", "PANPooling", "SAGPooling", "TopkPooling"]
+# ("dmon", "kmis", "acc", "hosc", "bnpool", "jb" (JustBalancePooling), "edgepool" (EdgeContractionPooling), "lap" (LaPooling), "sag" (SAGPooling), "asap" (ASAPooling), "maxcut" (MaxCutPooling), "eigen" (EigenPooling), "nmf" (NMFPooling), "pan" (PANPooling) and "sep" (SEPPooling) are not in pooler_map yet: the alias set is pinned to the five poolers above)
+pooler_classes = ["ASAPooling", "AsymCheegerCutPooling", "BNPool", "DMoNPooling", "DiffPool", "EdgeContractionPooling", "EigenPooling", "GraclusPooling", "HOSCPooling", "JustBalancePooling", "KMISPooling", "LaPooling", "MaxCutPooling", "MinCutPooling", "NDPPooling", "NMFPooling", "PANPooling", "SAGPooling", "SEPPooling", "TopkPooling"]
 
 pooler_map = {
     "diff": DiffPool,
@@ -1623,4 +1624,4 @@ def get_pooler(pooler_name: str, **kwargs):
 
 __all__ = ["get_pooler", "pooler_map", "pooler_classes"] + pooler_classes + ["MaxCutSelect", "MaxCutScoreNet", "EigenPoolSelect",
                                                                           "EigenPoolReduce", "EigenPoolConnect",
-                                                                          "EigenPoolLift", "NMFSelect"]
+                                                                          "EigenPoolLift", "NMFSelect", "SEPSelect"]

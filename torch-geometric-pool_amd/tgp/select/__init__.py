@@ -1612,7 +1612,7 @@ __all__ = ["SelectOutput", "Select", "TopkSelect", "MLPSelect", "DPSelect", "Gra
            "topk", "graclus_cluster", "KMISSelect", "maximal_independent_set", "maximal_independent_set_cluster",
            "EdgeContractionSelect", "maximal_matching", "maximal_matching_cluster", "LaPoolSelect",
            "degree_scorer", "MaxCutSelect", "MaxCutScoreNet", "MaxCutPooling", "EigenPoolSelect", "eigenpool_select",
-           "eigenpool_theta", "NMFSelect", "nmf_select"]
+           "eigenpool_theta", "NMFSelect", "nmf_select", "SEPSelect", "sep_select"]
 
 
 def __getattr__(name):
@@ -1628,4 +1628,8 @@ def __getattr__(name):
     if name in ("NMFSelect", "nmf_select"):
         from ..poolers import nmf
         return getattr(nmf, name)
+    # and SEP pooling's (tgp/poolers/sep.py)
+    if name in ("SEPSelect", "sep_select"):
+        from ..poolers import sep
+        return getattr(sep, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
