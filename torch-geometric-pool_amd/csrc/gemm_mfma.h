@@ -56,6 +56,13 @@ constexpr int LDA_ROWMAJOR = BK + 1;
 // more records and decisions (they cost a dense input ~12 % of the launch when taken at every step).  Measured on
 // uniformly random A only: a row panel that meets two dense chunks early (a dense diagonal block of community-ordered
 // nodes, say) multiplies the rest of its k-range in full -- the results are the same, the skipping is lost there.
+// With a row-major A the 16-wave 128 x 128 tile first takes its k-range in 128-column chunks (128 x 128, 4096 groups)
+// for as long as they are sparse -- the wide front-end in gemm_f32_mfma_kernel -- and the 32-column stages above run
+// from the first chunk that is not.  Same share of the groups as the narrow threshold (4 x 224), confirmed by the same
+// sweep (profiles/adj_front.md).
+#ifndef TGP_SPARSE_WIDE_GROUPS
+#define TGP_SPARSE_WIDE_GROUPS 896
+#endif
 #ifndef TGP_DENSE_RUN
 #define TGP_DENSE_RUN 2
 #endif
@@ -233,9 +240,10 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     k_lo = static_cast<int>(g.k_ptr[batch]);
     k_hi = static_cast<int>(g.k_ptr[batch + 1]);
   }
-  const int k_begin = k_lo + split * g.k_per_split;
+  // (not const: the wide sparse front-end of MODE 3 / MODE 4 moves the start of the k-loop behind the chunks it took)
+  int k_begin = k_lo + split * g.k_per_split;
   const int k_end = min(k_hi, k_begin + g.k_per_split);
-  const int nk = k_end > k_begin ? (k_end - k_begin + BK - 1) / BK : 0;
+  int nk = k_end > k_begin ? (k_end - k_begin + BK - 1) / BK : 0;
 
   // register staging, two sets: tile t+2 is being loaded into one while tile t+1 is written to LDS from the other
   float4 ra[2][A_VECS], rb[2][B_VECS];
@@ -643,6 +651,134 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
     __syncthreads();
     TGP_PHASE(6);
   };
+  // ---- MODE 3 / MODE 4, row-major A, the 16-wave 128 x 128 tile: the wide sparse front-end ---------------------------
+  // While the next WIDE_K = 128 columns of the k-range form a sparse chunk of A (128 x 128, as 4096 groups of 4 values:
+  // at most TGP_SPARSE_WIDE_GROUPS hold a nonzero, and the chunk's Bm rows are finite) the workgroup takes it here, in
+  // one stage instead of four.  A is never a shared LDS tile here: it is an MFMA operand only in a dense chunk.  Wave w
+  // loads the rows it owns in the walk (w + NW j) itself, two rows per 16-byte load (lanes 0-31 one row, lanes 32-63 the
+  // other, 512 contiguous bytes each), and turns each pair through 1 KB of LDS of its own -- no barrier, a wave's LDS
+  // operations complete in order -- into a lane per column, 64 columns per register: what the narrow walk reads from
+  // the A tile.  The walk is then the narrow one, out of registers: ballot, v_readlane, one ds_read_b64 of the Bm row
+  // and one taken branch per nonzero.  (Walked as loaded, four columns per lane, it needs a second level -- which of
+  // the lane's four values -- and those scalar branches cost more than the front-end saves; loaded a lane per column,
+  // sixteen dword loads per chunk, the loads do: profiles/adj_front.md.)  The Bm rows of the chunk lie in LDS as
+  // [128][BN], the layout the narrow walk reads, in two buffers.  Chunk t + 1 (A as loaded, Bm in staging registers) is
+  // requested before chunk t is walked, and turned, stored and recorded behind the walk: one barrier per chunk.  Per
+  // output element the nonzeros are added in ascending k, as the narrow walk adds them, so the sums are bitwise those
+  // of the 32-column stages wherever both walk.
+  // The first chunk that is not sparse -- too many groups, an Inf / NaN in its Bm rows -- or fewer than 128 columns
+  // left end the front-end for this workgroup: the register-staged loop below then starts at that k (its prologue,
+  // records, TGP_DENSE_RUN and tail stages as they are) and runs zero stages when nothing is left.
+  constexpr bool FRONT = SKIP && !A_KMAJOR && BM == 128 && BN == 128 && WN == 4;
+  if constexpr (FRONT) {
+    constexpr int WIDE_K = 128;
+    constexpr int W_FLOATS = WIDE_K * BN;               // one Bm chunk in LDS; two buffers, the records behind them
+    constexpr int W_VECS = WIDE_K * BN / 4 / THREADS;   // float4 of Bm per thread and chunk (= 4)
+    constexpr int W_PAIRS = S_ROWS / 2;                 // row pairs of A per wave and chunk, one 16-byte load each (= 4)
+    constexpr int W_REGS = S_ROWS * (WIDE_K / 64);      // A values per lane and chunk: row j, columns 64 p + lane (= 16)
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    unsigned* wide_rec = reinterpret_cast<unsigned*>(smem + 2 * W_FLOATS);  // [2 parities][16 words], as chunk_rec
+    unsigned* wide_turn = wide_rec + 2 * 16 + wave * 256;                   // the wave's own 1 KB: one row pair
+    u32x4 wr[W_PAIRS];   // the next chunk's rows as loaded
+    unsigned wa[W_REGS];  // this chunk's rows, a lane per column
+    float4 ws[W_VECS];
+    int voff_w[W_PAIRS];
+#pragma unroll
+    for (int i = 0; i < W_PAIRS; ++i) {
+      const int m = m0 + wave + NW * (2 * i + (lane >> 5));
+      voff_w[i] = m < M ? (m * static_cast<int>(lda) + 4 * (lane & 31)) * 4 : OOB;  // (rows beyond M: zeros)
+    }
+    auto wide_load = [&](int k0) {  // the chunk at k0: A rows as loaded, the Bm rows into the staging registers
+#pragma unroll
+      for (int i = 0; i < W_PAIRS; ++i) wr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, voff_w[i], k0 * 4, 0);
+#pragma unroll
+      for (int i = 0; i < W_VECS; ++i)
+        ws[i] = buf_ld4(rsrc_b, voff_b[0], (k0 + i * (THREADS / BN_LANES)) * static_cast<int>(ldb) * 4);
+    };
+    // the staged Bm rows to LDS buffer PAR, the A rows turned into the registers the walk reads, and the wave's record
+    // of that chunk: the groups of its own A registers that hold a nonzero (the bit test of record_chunk), + 2^16 if
+    // the Bm values it staged hold an Inf or NaN
+    auto wide_publish = [&](auto par_c) {
+      constexpr int PAR = decltype(par_c)::value;
+#pragma unroll
+      for (int i = 0; i < W_VECS; ++i) store_b(i, ws[i], smem + PAR * W_FLOATS);
+      unsigned n = 0;
+#pragma unroll
+      for (int i = 0; i < W_PAIRS; ++i) {
+        n += __popcll(__ballot(((wr[i].x | wr[i].y | wr[i].z | wr[i].w) << 1) != 0u));
+        // (the wave barriers only keep the compiler from moving the accesses across each other)
+        *reinterpret_cast<u32x4*>(wide_turn + 4 * lane) = wr[i];  // row 2i: words 0 .. 127, row 2i + 1: 128 .. 255
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wa[4 * i + q] = wide_turn[64 * q + lane];
+        __builtin_amdgcn_wave_barrier();
+      }
+      unsigned mag = 0;
+#pragma unroll
+      for (int i = 0; i < W_VECS; ++i)
+        mag = max(max(mag, max(__float_as_uint(ws[i].x) & 0x7fffffffu, __float_as_uint(ws[i].y) & 0x7fffffffu)),
+                  max(__float_as_uint(ws[i].z) & 0x7fffffffu, __float_as_uint(ws[i].w) & 0x7fffffffu));
+      if (__ballot(mag >= 0x7f800000u)) n += 1u << 16;
+      if (lane == 0) wide_rec[PAR * 16 + wave] = n;
+    };
+    auto wide_is_sparse = [&](auto par_c) -> bool {
+      const uint4* r = reinterpret_cast<const uint4*>(wide_rec + decltype(par_c)::value * 16);
+      unsigned n = 0;
+#pragma unroll
+      for (int q = 0; q < NW / 4; ++q) {
+        const uint4 v = r[q];
+        n += v.x + v.y + v.z + v.w;
+      }
+      return __builtin_amdgcn_readfirstlane(n) <= TGP_SPARSE_WIDE_GROUPS;
+    };
+    // sacc[j][c] += sum over the chunk's nonzeros A[wave + NW j][k] * Bm[k][2 lane + c], k ascending within each row:
+    // per register one ballot (a != 0.f: -0 is a zero, a NaN is not), then its set bits as the narrow walk takes them.
+    // One Bm row read at a time: requested one nonzero ahead of the adds it measured slower (profiles/adj_front.md).
+    auto wide_walk = [&](auto par_c) {
+      const float* Bs = smem + decltype(par_c)::value * W_FLOATS;
+#pragma unroll
+      for (int r = 0; r < W_REGS; ++r) {
+        constexpr int PARTS = WIDE_K / 64;
+        const int j = r / PARTS;
+        const float* Bp = Bs + 64 * (r % PARTS) * BN + 2 * lane;
+        const int vbits = static_cast<int>(wa[r]);
+        for (unsigned long long m = __ballot(__int_as_float(vbits) != 0.f); m; m &= m - 1) {
+          const int kk = __builtin_ctzll(m);
+          const float a = __int_as_float(__builtin_amdgcn_readlane(vbits, kk));
+          const float2 b = *reinterpret_cast<const float2*>(Bp + kk * BN);
+          sacc[j][0] = fmaf(a, b.x, sacc[j][0]);
+          sacc[j][1] = fmaf(a, b.y, sacc[j][1]);
+        }
+      }
+    };
+    int kw = k_begin;
+    if (k_end - kw >= WIDE_K) {
+      using P0 = std::integral_constant<int, 0>;
+      using P1 = std::integral_constant<int, 1>;
+      wide_load(kw);
+      wide_publish(P0{});
+      __syncthreads();
+      // one chunk: decide, request the next, walk, publish the next.  Returns whether another chunk was published.
+      auto wide_stage = [&](auto par_c) -> bool {
+        constexpr int PAR = decltype(par_c)::value;
+        // (not sparse: nothing of the wide buffers is read any more -- every walk lies behind a barrier -- and the loop
+        // below stores into them only behind this point)
+        if (!wide_is_sparse(par_c)) return false;
+        const bool more = k_end - kw >= 2 * WIDE_K;  // (workgroup-uniform)
+        if (more) wide_load(kw + WIDE_K);
+        wide_walk(par_c);
+        if (more) wide_publish(std::integral_constant<int, 1 - PAR>{});
+        any_sparse = true;
+        kw += WIDE_K;
+        __syncthreads();  // chunk t + 1 is published; chunk t's buffer and record are free (and, at the end, the LDS)
+        return more;
+      };
+      while (wide_stage(P0{}) && wide_stage(P1{})) {
+      }
+      k_begin = kw;
+      nk = k_end > k_begin ? (k_end - k_begin + BK - 1) / BK : 0;
+    }
+  }
   if (nk > 0) {
 #pragma unroll
     for (int i = 0; i < A_VECS; ++i) ra[0][i] = load_a(i, kof(0), kof(0) + BK > k_end);
@@ -1116,7 +1252,13 @@ static void launch_gemm_skip_zeros(GemmArgs g, int batches, hipStream_t stream) 
   g.tiles_m = tiles_m;
   g.tiles_n0 = g.tiles_n = tiles_n;
   g.tiles_n1 = 0;
-  const size_t lds = 2 * (BM * LDA_ROWMAJOR + BK * BN) * sizeof(float) + 2 * 16 * sizeof(unsigned);
+  // row-major A: the wide front-end's two Bm chunks [128][BN], its records and 1 KB per wave (the k-loop's stages lie inside)
+  constexpr size_t lds = A_KMAJOR ? 2 * (BM * LDA_ROWMAJOR + BK * BN) * sizeof(float) + 2 * 16 * sizeof(unsigned)
+                                  : 2 * 128 * BN * sizeof(float) + (2 * 16 + 16 * 256) * sizeof(unsigned);
+  static_assert(A_KMAJOR || 2 * 128 * BN >= 2 * (BM * LDA_ROWMAJOR + BK * BN) + 2 * 16, "MODE 3: the wide chunks cover the stages");
+  if constexpr (!A_KMAJOR)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 3, WN>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 3, WN>), dim3(nwg), dim3(BM * 2 * WN), lds, stream, g);
 }
 
@@ -1149,6 +1291,7 @@ static bool launch_gemm_fold(GemmArgs g, int batches, hipStream_t stream) {
   constexpr size_t lds = (BM * BN + BM * 192) * sizeof(float);  // = 160 KB: the whole LDS of a CU
   static_assert(BM * BN + BM * 192 >= BM * 196 + 8 * BN && BM * 196 + 8 * BN >= 2 * (BM * LDA_ROWMAJOR + BK * BN) + 2 * 16,
                 "MODE 4: the tail's operands cover its result tile, which covers the k-loop's stages");
+  static_assert(BM * BN + BM * 192 >= 2 * 128 * BN + 2 * 16 + 16 * 256, "MODE 4: ... and the wide front-end's two Bm chunks, records and turn areas");
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 4, WN>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_KMAJOR, true, BM, BN, 4, WN>), dim3(nwg), dim3(BM * 2 * WN), lds, stream, g);
