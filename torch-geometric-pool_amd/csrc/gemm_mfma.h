@@ -66,6 +66,15 @@ constexpr int LDA_ROWMAJOR = BK + 1;
 #ifndef TGP_DENSE_RUN
 #define TGP_DENSE_RUN 2
 #endif
+// MODE 4 tail, each measured on its own (profiles/c2_tail.md).  TGP_FOLD_SKIP_ACC: a workgroup that ran no MFMA in its
+// k-loop writes the walk's sums to the tail's U operand directly, without the accumulators' trip through LDS.
+// TGP_FOLD_SPLIT: the tail's MFMAs in two phases, S^T U first; its result is parked in LDS and stored under S^T X.
+#ifndef TGP_FOLD_SKIP_ACC
+#define TGP_FOLD_SKIP_ACC 1
+#endif
+#ifndef TGP_FOLD_SPLIT
+#define TGP_FOLD_SPLIT 1
+#endif
 
 // One right-hand side / output pair.  A launch may carry up to three (column tiles >= tiles_n0 use the
 // second, those >= tiles_n1 the third), which lets S^T [U | X] -- and, for the training step, S^T [U | X | S] --
@@ -550,6 +559,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   // SK (MODE 3): the stage decides between the MFMAs and the sparse walk, and records the chunk it stores
   [[maybe_unused]] int dense_run = 0;       // MODE 3: dense k-steps in a row (workgroup-uniform)
   [[maybe_unused]] bool dense_rest = false; // MODE 3: TGP_DENSE_RUN reached: plain stages from here on
+  [[maybe_unused]] bool any_dense = false;  // MODE 4: some stage ran its MFMAs, so acc may hold something (workgroup-uniform)
   auto stage = [&](auto par_c, auto steady_c, auto sk_c, int t) {
     constexpr int PAR = decltype(par_c)::value;
     constexpr bool STEADY = decltype(steady_c)::value;
@@ -587,6 +597,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       any_sparse = any_sparse || sparse;
       dense_run = sparse ? 0 : dense_run + 1;
       dense_rest = dense_run >= TGP_DENSE_RUN;
+      if constexpr (FOLD) any_dense = any_dense || !sparse || dense_rest;  // (plain stages run only behind dense_rest)
       if (sparse) {
       // the stage's memory work in one block: tile t+2 is requested first, tile t+1 goes to LDS after the walk
 #pragma unroll
@@ -889,7 +900,8 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
   // are not padded but swizzled -- column c of row k sits at c ^ 16 (k & 3), which keeps 16-byte vectors whole and puts
   // the four k rows of an operand read on different banks.  The result then goes to LDS as one tile [128][196] and
   // leaves in 16-byte stores; its column sums are taken from there in row order (16-row partials by eight thread
-  // groups, added in order).
+  // groups, added in order).  That is the one-phase form (TGP_FOLD_SPLIT = 0); the shipped one gives a wave other
+  // columns of the same rows and lets S^T U leave while S^T X is multiplied -- same blocks, same orders: see there.
   if constexpr (FOLD) {
     constexpr int P_LD = 196;
     float* Sf = smem;
@@ -907,10 +919,24 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       const int k = (tid >> 4) + 64 * i;
       *reinterpret_cast<float4*>(UXf + k * 192 + ((BN + (tid & 15) * 4) ^ ((k & 3) << 4))) = fx[i];
     }
+    // (workgroup-uniform) no MFMA ran in the k-loop: acc is +0 everywhere, so U = 0 + sacc goes to LDS directly, each
+    // element from the lane that owns it in the walk -- the same add as below (a -0 sum becomes +0 there too), without
+    // the accumulators' trip through LDS and its barrier.  Rows beyond M: their A rows are zeros from the descriptor
+    // and only finite S rows are walked, so their sums are +0.
+    const bool direct = TGP_FOLD_SKIP_ACC && !any_dense;
+    if (direct) {
+#pragma unroll
+      for (int j = 0; j < S_ROWS; ++j) {
+        const int row = wave + NW * j;
+        *reinterpret_cast<float2*>(UXf + row * 192 + ((2 * lane) ^ ((row & 3) << 4))) =
+            make_float2(__fadd_rn(0.f, sacc[j][0]), __fadd_rn(0.f, sacc[j][S_COLS - 1]));
+      }
+    } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {  // rows beyond M are zeros (0 * Inf of the k-loop is not)
       const int rl = (r & 3) + 8 * (r >> 2) + 4 * lk;
       UXf[(wm * 32 + rl) * 192 + ((wn * 32 + lm) ^ ((r & 3) << 4))] = m0 + wm * 32 + rl < M ? acc[0][r] : 0.f;
+    }
     }
     f32x4 d[2][3];
 #pragma unroll
@@ -920,7 +946,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) d[i][j][r] = 0.f;
     __syncthreads();
-    if (any_sparse) {  // (workgroup-uniform) U += the walk's sums, each element by the lane that owns it: acc + sacc as in MODE 3
+    if (any_sparse && !direct) {  // (workgroup-uniform) U += the walk's sums, each element by the lane that owns it: acc + sacc as in MODE 3
 #pragma unroll
       for (int j = 0; j < S_ROWS; ++j) {
         const int row = wave + NW * j;
@@ -933,6 +959,145 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       __syncthreads();
     }
     TGP_STAMP(8);  // (stamps build: slots 8 .. 11 are the tail's phases)
+    if constexpr (TGP_FOLD_SPLIT) {
+      // Two MFMA phases, the first one's result leaving under the second.  Wave (wm, wn) owns rows 32 wm .. + 31 of both
+      // parts, columns 32 wn .. + 31 of S^T U (four blocks, d[i][0 .. 1]) and 16 wn .. + 15 of S^T X (two, d[i][2]): six
+      // blocks and 192 MFMAs as in the one-phase form below, every block over the full k range in ascending k.
+      //   U-part, 32 k-groups of four MFMAs; the 16-row column-sum partials are taken from its accumulators;
+      //   X-part, 32 k-groups of two, with one memory instruction behind each pair:
+      //     groups 0 .. 3, then the barrier behind which no wave reads U_r any more;
+      //     groups 4 .. 11 with the sixteen ds_write_b32 that park S^T U in U_r's LDS words, then a barrier;
+      //     groups 12 .. 19 with the 16-byte reads of the parked tile and their slab stores, four of each per thread;
+      //     groups 20 .. 31.
+      // S^T X then leaves straight from the accumulators (16 lanes per 64-byte row segment), and behind a last barrier
+      // -- S_r is dead -- the partials go to LDS and are added in order.
+      // (4 / 8 against 1 / 16, 2 / 8, 4 / 4 and 8 / 8: profiles/c2_tail.md)
+      constexpr int G_FREE = 4, G_PARK = 8, PARK_PER = 16 / G_PARK;
+      int a_at[2], u_at[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a_at[i] = lq * BN + ((wm * 32 + 16 * i + l15) ^ (lq << 4));
+#pragma unroll
+      for (int j = 0; j < 2; ++j) u_at[j] = lq * 192 + ((wn * 32 + 16 * j + l15) ^ (lq << 4));
+      const int x_at = lq * 192 + ((BN + wn * 16 + l15) ^ (lq << 4));
+      float a[2][2], b[2][2];
+      auto fetch_u = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[s & 1][i] = Sf[4 * s * BN + a_at[i]];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) b[s & 1][j] = UXf[4 * s * 192 + u_at[j]];
+      };
+      auto fetch_x = [&](int s) {  // (b[.][0] holds the X operand)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[s & 1][i] = Sf[4 * s * BN + a_at[i]];
+        b[s & 1][0] = UXf[4 * s * 192 + x_at];
+      };
+      fetch_u(0);
+#pragma unroll
+      for (int s = 0; s < 32; ++s) {
+        if (s + 1 < 32) fetch_u(s + 1);
+        else fetch_x(0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            d[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][j], d[i][j], 0, 0, 0);
+        if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // ds_reads of the next group
+        else __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                   // 4 x MFMA
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      TGP_STAMP(9);
+      // column sums of S^T U, the 16-row partial of block row 2 wm + i: a lane holds rows 4 lq + r of its column, so the
+      // lanes lq = 0 add their four rows to 0 and hand the sum to lq = 1, and so on -- the sixteen adds in row order;
+      // the lanes lq = 3 end up with the partial (rows >= Nc and, under colsum_skip_diag, the diagonal count as 0)
+      float cpart[2][2];
+      if (g.colsum) {  // (workgroup-uniform)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int col = wn * 32 + 16 * j + l15;
+            float cs = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              if (q) cs = __shfl_up(cs, 16, 64);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int row = wm * 32 + 16 * i + 4 * lq + r;
+                cs = __fadd_rn(cs, (row >= Nc || (g.colsum_skip_diag && row == col)) ? 0.f : d[i][j][r]);
+              }
+            }
+            cpart[i][j] = cs;
+          }
+      }
+      float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
+      float* cp = Ca + static_cast<long>(tid >> 5) * R.ldc + (tid & 31) * 4;  // this thread's vector of slab row tid / 32
+      const long cp_step = 32 * R.ldc;
+      float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);  // (one vector of the parked tile on its way to the slab)
+#pragma unroll
+      for (int s = 0; s < 32; ++s) {
+        if (s == G_FREE) __syncthreads();  // (no wave reads U_r any more)
+        if (s == G_FREE + G_PARK) {
+          __syncthreads();  // (S^T U is parked)
+          TGP_STAMP(10);
+        }
+        if (s + 1 < 32) fetch_x(s + 1);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) d[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][0], d[i][2], 0, 0, 0);
+        if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // ds_reads of the next group
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                   // 2 x MFMA
+        if (s >= G_FREE && s < G_FREE + G_PARK) {
+          // S^T U to U_r's words [128][first 128 of 192], column c of row p at c ^ 16 ((p >> 2) & 1): the two lq of a
+          // half-wave land on different halves of the 32 banks, so the ds_write_b32 are conflict-free, and 16-byte
+          // vectors stay whole.  Two of the sixteen per group.
+#pragma unroll
+          for (int h = 0; h < PARK_PER; ++h) {
+            const int e = PARK_PER * (s - G_FREE) + h, i = e >> 3, j = (e >> 2) & 1, r = e & 3;
+            const int p = wm * 32 + 16 * i + 4 * lq + r;
+            UXf[p * 192 + ((wn * 32 + 16 * j + l15) ^ ((lq & 1) << 4))] = d[i][j][r];
+          }
+        }
+        if (s >= G_FREE + G_PARK && s < G_FREE + G_PARK + 8) {
+          // rows and columns < Nc of the parked tile to the slab: 32 lanes per 512-byte row, one read or one store per group
+          const int e = s - (G_FREE + G_PARK), q = e >> 1;
+          const int row = (tid >> 5) + 32 * q, c4 = (tid & 31) * 4;
+          if ((e & 1) == 0) pv = *reinterpret_cast<const float4*>(UXf + row * 192 + (c4 ^ (((row >> 2) & 1) << 4)));
+          else if (row < Nc && c4 < Nc) *reinterpret_cast<float4*>(cp + q * cp_step) = pv;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      TGP_STAMP(11);
+      if (F) {  // columns < F of S^T X, rows < Nc (rows >= Nc are 0 * X: not zeros when X holds a NaN)
+        float* Cx = RX.C + static_cast<long>(batch) * RX.sC + static_cast<long>(tm) * RX.sCsplit;
+        const int col = wn * 16 + l15;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = wm * 32 + 16 * i + 4 * lq + r;
+            if (row < Nc && col < F) Cx[static_cast<long>(row) * RX.ldc + col] = d[i][2][r];
+          }
+      }
+      if (g.colsum) {  // (workgroup-uniform)
+        __syncthreads();  // (S_r is dead: the eight partials per column lie there, [8][BN])
+        float* part = smem;
+        if (lq == 3) {
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) part[(2 * wm + i) * BN + wn * 32 + 16 * j + l15] = cpart[i][j];
+        }
+        __syncthreads();
+        if (tid < Nc) {
+          float tot = 0.f;
+#pragma unroll
+          for (int qq = 0; qq < 8; ++qq) tot = __fadd_rn(tot, part[qq * BN + tid]);
+          g.colsum[(static_cast<long>(batch) * g.tiles_m + tm) * Nc + tid] = tot;
+        }
+      }
+      TGP_STAMP(3);
+      return;
+    }
     {
       // operands of k-group s + 1 are requested before the MFMAs of group s; no branch inside (column blocks beyond
       // Nc / F -- X absent or F < 64, Nc < 128 -- are multiplied all the same and not written below: a wave-uniform
