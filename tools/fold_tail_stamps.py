@@ -12,6 +12,9 @@ tail's first MFMA (8), at three points of the tail (9, 10, 11) and at the end (3
   10     S^T U parked in LDS (12 k-groups of S^T X done)   P in LDS
   11     S^T X multiplied, S^T U stored                    column sums written
 
+With block-order slabs (TGP_FOLD_BLOCKS = 1, the shipped form) nothing is parked: slot 10 is the same point of the X-part
+(12 of its 32 k-groups done, the four S^T U block stores issued behind the first four) and slot 11 its end.
+
 The stamps slow the launch, so the figures are shares; median and p10..p90 over the workgroups, in us."""
 import ctypes
 import os

@@ -78,6 +78,11 @@ static DensePlan dense_plan(int64_t B, int64_t N, int64_t K, int64_t F, bool wit
   p.xslab_floats = static_cast<size_t>(B) * slabs * K * F;
   p.post_floats = post_ws_floats(B, K);
   p.colsum_floats = static_cast<size_t>(B) * parts * K;  // post_rows_kernel's degree partials
+  // (the folded route's slabs may be in block order: K and F rounded up to 16)
+  const size_t fold_a = static_cast<size_t>(B * fold * fold_slab_floats(K, K));
+  const size_t fold_x = static_cast<size_t>(B * fold * fold_slab_floats(K, F));
+  if (fold_a > p.aslab_floats) p.aslab_floats = fold_a;
+  if (fold_x > p.xslab_floats) p.xslab_floats = fold_x;
   return p;
 }
 
@@ -344,14 +349,16 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
   float* gslab = gram ? cv.take<float>(p.aslab_floats) : nullptr;
 
   const int fold = (want_a && !keep_u && !gram) ? fold_tiles(N, K, F) : 0;  // (F as dense_plan sized the slabs for)
-  if (fold > 0 && fold <= PR_MAX_SPLITS && static_cast<size_t>(B) * fold * K * K <= p.aslab_floats &&
+  const long a_slab = fold_slab_floats(K, K), x_slab = fold_slab_floats(K, F);  // (block order under TGP_FOLD_BLOCKS)
+  if (fold > 0 && fold <= PR_MAX_SPLITS && static_cast<size_t>(B) * fold * a_slab <= p.aslab_floats &&
+      static_cast<size_t>(B) * fold * x_slab <= p.xslab_floats &&
       post_rows_ok(K, flags, aslab, adj_raw, adj_pool) &&
       reinterpret_cast<uintptr_t>(xslab) % 16 == 0) {
     GemmArgs g{};
     g.A = A; g.lda = N; g.sA = N * N;
     g.M = static_cast<int>(N); g.Kd = static_cast<int>(N);
-    g.rhs[0] = GemmRhs{S, aslab, static_cast<int>(K), K, K, N * K, static_cast<long>(fold) * K * K, K * K};
-    if (want_x) g.rhs[1] = GemmRhs{X, xslab, static_cast<int>(F), F, F, N * F, static_cast<long>(fold) * K * F, K * F};
+    g.rhs[0] = GemmRhs{S, aslab, static_cast<int>(K), K, K, N * K, fold * a_slab, a_slab};
+    if (want_x) g.rhs[1] = GemmRhs{X, xslab, static_cast<int>(F), F, F, N * F, fold * x_slab, x_slab};
     g.splits = 1; g.k_per_split = static_cast<int>((N + BK - 1) / BK * BK);
     g.colsum = colpart;
     g.colsum_skip_diag = (flags & TGP_REMOVE_SELF_LOOPS) ? 1 : 0;
@@ -359,16 +366,16 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
                                                      : launch_gemm_fold<false>(g, static_cast<int>(B), stream);
     if (folded) {
       PostRowsArgs r{};
-      r.slab = aslab; r.splits = fold; r.s_split = K * K; r.s_batch = static_cast<long>(fold) * K * K;
+      r.slab = aslab; r.splits = fold; r.s_split = a_slab; r.s_batch = fold * a_slab;
       r.colsum = (flags & TGP_DEGREE_NORM) ? colpart : nullptr; r.tiles_m = 1;
       r.K = static_cast<int>(K); r.flags = flags; r.eps = eps; r.raw = adj_raw; r.dst = adj_pool;
       if (want_x) {
-        r.xslab = xslab; r.xs_split = K * F; r.xs_batch = static_cast<long>(fold) * K * F;
+        r.xslab = xslab; r.xs_split = x_slab; r.xs_batch = fold * x_slab;
         r.F = static_cast<int>(F); r.x_pool = x_pool;
       }
       const unsigned grid = static_cast<unsigned>(B * ((K + PR_ROWS - 1) / PR_ROWS));
       r.main_blocks = static_cast<int>(grid);
-      hipLaunchKernelGGL(post_rows_kernel, dim3(grid), dim3(512), 0, stream, r);
+      hipLaunchKernelGGL(post_rows_kernel<TGP_FOLD_BLOCKS != 0>, dim3(grid), dim3(512), 0, stream, r);
       return check_launch("tgp_dense_pool_f32");
     }
   }
@@ -421,7 +428,7 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
         r.gslab = gslab; r.gram = gram;
         grid *= 2;
       }
-      hipLaunchKernelGGL(post_rows_kernel, dim3(grid), dim3(512), 0, stream, r);
+      hipLaunchKernelGGL(post_rows_kernel<false>, dim3(grid), dim3(512), 0, stream, r);
       return check_launch("tgp_dense_pool_f32");
     }
   }

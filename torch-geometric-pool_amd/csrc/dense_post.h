@@ -464,8 +464,89 @@ struct PostRowsArgs {
 constexpr int PR_ROWS = 16;
 constexpr int PR_MAX_SPLITS = 8;  // node-range splits of the second product this kernel takes (x 2 row tiles for K <= 128...)
 
+// BLOCKS (the folded route under TGP_FOLD_BLOCKS): both slab sets are in block order (fold_slab_floats, gemm_mfma.h), so
+// the 16 rows of a workgroup are one contiguous run of K / 16 blocks per slab and thread t takes the float4 at word 4 t of
+// it: rows i0 + 4 lq .. + 3 of column 16 (t / 64) + t % 16, lq = (t % 64) / 16.  Same adds, diagonal and divisions per
+// element as below, in the same order; d_j is now shared by the four components and d_i differs.  K <= 128, F <= 64.
+template <bool BLOCKS>
 __global__ __launch_bounds__(512) void post_rows_kernel(PostRowsArgs p) {
   __shared__ float s_d[1024];
+  if constexpr (BLOCKS) {
+    const int K = p.K, tid = threadIdx.x, kb = (K + 15) >> 4;
+    const int b = blockIdx.x / kb, rb = blockIdx.x - b * kb, i0 = rb * PR_ROWS;
+    const bool rsl = p.flags & TGP_REMOVE_SELF_LOOPS, dn = (p.flags & TGP_DEGREE_NORM) && p.colsum;
+    const int bc = tid >> 6, lq = (tid >> 4) & 3;
+    const int c = 16 * bc + (tid & 15), r0 = i0 + 4 * lq;  // (K % 4 == 0: the four rows are in range together)
+    const float* sb = p.slab + static_cast<long>(b) * p.s_batch;
+    const bool mine = bc < kb && c < K && r0 < K;
+    float4 t;
+    {
+      // every slab's value is requested before the first add
+      float4 v[PR_MAX_SPLITS];
+      const float* q = sb + (mine ? static_cast<long>(rb) * kb * 256 + 4 * tid : 0);
+#pragma unroll
+      for (int sp = 0; sp < PR_MAX_SPLITS; ++sp)
+        v[sp] = *reinterpret_cast<const float4*>(q + (sp < p.splits ? sp * p.s_split : 0));
+      t = v[0];
+#pragma unroll
+      for (int sp = 1; sp < PR_MAX_SPLITS; ++sp)
+        if (sp < p.splits) {
+          t.x = __fadd_rn(t.x, v[sp].x); t.y = __fadd_rn(t.y, v[sp].y);
+          t.z = __fadd_rn(t.z, v[sp].z); t.w = __fadd_rn(t.w, v[sp].w);
+        }
+    }
+    // x_pool rows of the same block row, requested here as well
+    const int F = p.x_pool ? p.F : 0, fb = (F + 15) >> 4;
+    const bool xmine = bc < fb && c < F && r0 < K;
+    float4 xv[PR_MAX_SPLITS];
+    {
+      const float* xq = xmine ? p.xslab + static_cast<long>(b) * p.xs_batch + static_cast<long>(rb) * fb * 256 + 4 * tid : sb;
+#pragma unroll
+      for (int sp = 0; sp < PR_MAX_SPLITS; ++sp)
+        xv[sp] = *reinterpret_cast<const float4*>(xq + ((xmine && sp < p.splits) ? sp * p.xs_split : 0));
+    }
+    if (dn) {  // (one partial per tile and column: tiles_m = 1 on this route)
+      for (int j = tid; j < K; j += 512) {
+        const float* cs = p.colsum + static_cast<long>(b) * p.splits * K + j;
+        float pv[PR_MAX_SPLITS];
+#pragma unroll
+        for (int qq = 0; qq < PR_MAX_SPLITS; ++qq) pv[qq] = cs[qq < p.splits ? static_cast<long>(qq) * K : 0];
+        float cc = 0.f;  // (the partial sums already leave the diagonal out when the self loops are removed)
+#pragma unroll
+        for (int qq = 0; qq < PR_MAX_SPLITS; ++qq)
+          if (qq < p.splits) cc = __fadd_rn(cc, pv[qq]);
+        s_d[j] = sqrtf(clamp_min(cc, p.eps));
+      }
+    }
+    float* rawb = p.raw ? p.raw + static_cast<long>(b) * K * K : nullptr;
+    float* dstb = p.dst ? p.dst + static_cast<long>(b) * K * K : nullptr;
+    __syncthreads();
+    if (mine) {
+      float tv[4] = {t.x, t.y, t.z, t.w};
+      const float dj = dn ? s_d[c] : 1.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long off = static_cast<long>(r0 + r) * K + c;
+        if (rawb) rawb[off] = tv[r];
+        if (!dstb) continue;
+        if (rsl && r0 + r == c) tv[r] = 0.f;
+        if (dn) tv[r] = (tv[r] / dj) / s_d[r0 + r];  // (adj / d[1,K]) / d[K,1]
+        dstb[off] = tv[r];
+      }
+    }
+    if (xmine) {
+      float4 v = xv[0];
+#pragma unroll
+      for (int sp = 1; sp < PR_MAX_SPLITS; ++sp)
+        if (sp < p.splits) {
+          v.x = __fadd_rn(v.x, xv[sp].x); v.y = __fadd_rn(v.y, xv[sp].y);
+          v.z = __fadd_rn(v.z, xv[sp].z); v.w = __fadd_rn(v.w, xv[sp].w);
+        }
+      float* xo = p.x_pool + static_cast<long>(b) * K * F + static_cast<long>(r0) * F + c;
+      xo[0] = v.x; xo[F] = v.y; xo[2 * F] = v.z; xo[3 * F] = v.w;
+    }
+    return;
+  }
   const int K = p.K, tid = threadIdx.x;
   const int blocks_per_graph = (K + PR_ROWS - 1) / PR_ROWS;
   if (p.gram && static_cast<int>(blockIdx.x) >= p.main_blocks) {  // (workgroup-uniform) fixed-order slab sum of S^T S

@@ -75,6 +75,21 @@ constexpr int LDA_ROWMAJOR = BK + 1;
 #ifndef TGP_FOLD_SPLIT
 #define TGP_FOLD_SPLIT 1
 #endif
+// The two-phase tail's exits, each measured on its own (profiles/c2_slab_blocks.md).  TGP_FOLD_BLOCKS: both slab sets
+// leave in the accumulators' own block order (fold_slab_floats), one 16-byte store per lane and 16 x 16 block, with no
+// park in LDS and no barrier inside the X-part; post_rows_kernel<true> reads them through the inverse map.
+// TGP_FOLD_SLAB_WT (with TGP_FOLD_BLOCKS): those slab stores are write-through (sc1), so the slabs are on their way to
+// memory while the X-part still multiplies and the next launch does not wait for 25 MB of dirty lines.
+#ifndef TGP_FOLD_BLOCKS
+#define TGP_FOLD_BLOCKS 1
+#endif
+#ifndef TGP_FOLD_SLAB_WT
+#define TGP_FOLD_SLAB_WT 1
+#endif
+#if !TGP_FOLD_SPLIT
+#undef TGP_FOLD_BLOCKS
+#define TGP_FOLD_BLOCKS 0
+#endif
 
 // One right-hand side / output pair.  A launch may carry up to three (column tiles >= tiles_n0 use the
 // second, those >= tiles_n1 the third), which lets S^T [U | X] -- and, for the training step, S^T [U | X | S] --
@@ -119,7 +134,8 @@ struct GemmArgs {
   int symmetric;
   // MODE 4 (MODE 3 + the second product folded in, see launch_gemm_fold): rhs[0].C is the slab set [batches][tiles_m]
   // [Nc][Nc] of S_r^T U_r (row tile r of batch b at b * sC + r * sCsplit; U itself is not stored), rhs[1] (Bm optional) is
-  // X with its slab set [batches][tiles_m][Nc][rhs[1].Nc], colsum is [batches][tiles_m][Nc]
+  // X with its slab set [batches][tiles_m][Nc][rhs[1].Nc], colsum is [batches][tiles_m][Nc].  Under TGP_FOLD_BLOCKS a
+  // slab is in block order (fold_slab_floats) and ldc is not used
 };
 
 // Row of a [rows][BK+1] LDS tile served by slot t = 8*g + r (8 lanes per slot, slot = one 128-byte row segment).
@@ -972,6 +988,7 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       // S^T X then leaves straight from the accumulators (16 lanes per 64-byte row segment), and behind a last barrier
       // -- S_r is dead -- the partials go to LDS and are added in order.
       // (4 / 8 against 1 / 16, 2 / 8, 4 / 4 and 8 / 8: profiles/c2_tail.md)
+      // That X-part is the row-major form (TGP_FOLD_BLOCKS = 0); the shipped one stores the blocks as they are: see there.
       constexpr int G_FREE = 4, G_PARK = 8, PARK_PER = 16 / G_PARK;
       int a_at[2], u_at[2];
 #pragma unroll
@@ -1030,53 +1047,98 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
             cpart[i][j] = cs;
           }
       }
-      float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
-      float* cp = Ca + static_cast<long>(tid >> 5) * R.ldc + (tid & 31) * 4;  // this thread's vector of slab row tid / 32
-      const long cp_step = 32 * R.ldc;
-      float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);  // (one vector of the parked tile on its way to the slab)
-#pragma unroll
-      for (int s = 0; s < 32; ++s) {
-        if (s == G_FREE) __syncthreads();  // (no wave reads U_r any more)
-        if (s == G_FREE + G_PARK) {
-          __syncthreads();  // (S^T U is parked)
-          TGP_STAMP(10);
-        }
-        if (s + 1 < 32) fetch_x(s + 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) d[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][0], d[i][2], 0, 0, 0);
-        if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // ds_reads of the next group
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                   // 2 x MFMA
-        if (s >= G_FREE && s < G_FREE + G_PARK) {
-          // S^T U to U_r's words [128][first 128 of 192], column c of row p at c ^ 16 ((p >> 2) & 1): the two lq of a
-          // half-wave land on different halves of the 32 banks, so the ds_write_b32 are conflict-free, and 16-byte
-          // vectors stay whole.  Two of the sixteen per group.
-#pragma unroll
-          for (int h = 0; h < PARK_PER; ++h) {
-            const int e = PARK_PER * (s - G_FREE) + h, i = e >> 3, j = (e >> 2) & 1, r = e & 3;
-            const int p = wm * 32 + 16 * i + 4 * lq + r;
-            UXf[p * 192 + ((wn * 32 + 16 * j + l15) ^ ((lq & 1) << 4))] = d[i][j][r];
-          }
-        }
-        if (s >= G_FREE + G_PARK && s < G_FREE + G_PARK + 8) {
-          // rows and columns < Nc of the parked tile to the slab: 32 lanes per 512-byte row, one read or one store per group
-          const int e = s - (G_FREE + G_PARK), q = e >> 1;
-          const int row = (tid >> 5) + 32 * q, c4 = (tid & 31) * 4;
-          if ((e & 1) == 0) pv = *reinterpret_cast<const float4*>(UXf + row * 192 + (c4 ^ (((row >> 2) & 1) << 4)));
-          else if (row < Nc && c4 < Nc) *reinterpret_cast<float4*>(cp + q * cp_step) = pv;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      TGP_STAMP(11);
-      if (F) {  // columns < F of S^T X, rows < Nc (rows >= Nc are 0 * X: not zeros when X holds a NaN)
-        float* Cx = RX.C + static_cast<long>(batch) * RX.sC + static_cast<long>(tm) * RX.sCsplit;
-        const int col = wn * 16 + l15;
+      if constexpr (TGP_FOLD_BLOCKS) {
+        // Block-order slabs (fold_slab_floats): d[i][j] is block (2 wm + i, 2 wn + j) of S^T U and d[i][2] block
+        // (2 wm + i, wn) of S^T X exactly as the wave holds them, so each leaves as one 16-byte store per lane, 1 KB per
+        // wave.  Blocks wholly beyond Nc / F are not stored (their offset fails the descriptor's range check: no branch);
+        // the out-of-range words of a partial block may hold anything and post_rows_kernel<true> does not read them.
+        // The X-part runs its 32 k-groups with no barrier; the four S^T U stores go out behind its first four pairs.
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        constexpr int WT = TGP_FOLD_SLAB_WT ? 16 : 0;  // (aux bit 4: sc1)
+        const int kb = (Nc + 15) >> 4, fb = (F + 15) >> 4;
+        float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
+        const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(Ca, 0, kb * kb * 1024, 0x00020000);
+        int voff_c[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = wm * 32 + 16 * i + 4 * lq + r;
-            if (row < Nc && col < F) Cx[static_cast<long>(row) * RX.ldc + col] = d[i][2][r];
+          for (int j = 0; j < 2; ++j) {
+            const int br = 2 * wm + i, bc = 2 * wn + j;
+            voff_c[i][j] = (br < kb && bc < kb) ? (br * kb + bc) * 1024 + lane * 16 : OOB;
           }
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+          if (s == 12) TGP_STAMP(10);
+          if (s + 1 < 32) fetch_x(s + 1);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) d[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][0], d[i][2], 0, 0, 0);
+          if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // ds_reads of the next group
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                   // 2 x MFMA
+          if (s < 4)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, d[s >> 1][s & 1]), rsrc_c,
+                                                   voff_c[s >> 1][s & 1], 0, WT);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        TGP_STAMP(11);
+        if (F) {  // (workgroup-uniform)
+          float* Cx = RX.C + static_cast<long>(batch) * RX.sC + static_cast<long>(tm) * RX.sCsplit;
+          const __amdgpu_buffer_rsrc_t rsrc_cx = __builtin_amdgcn_make_buffer_rsrc(Cx, 0, kb * fb * 1024, 0x00020000);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int br = 2 * wm + i;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, d[i][2]), rsrc_cx,
+                                                   (br < kb && wn < fb) ? (br * fb + wn) * 1024 + lane * 16 : OOB, 0, WT);
+          }
+        }
+      } else {
+        float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
+        float* cp = Ca + static_cast<long>(tid >> 5) * R.ldc + (tid & 31) * 4;  // this thread's vector of slab row tid / 32
+        const long cp_step = 32 * R.ldc;
+        float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);  // (one vector of the parked tile on its way to the slab)
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+          if (s == G_FREE) __syncthreads();  // (no wave reads U_r any more)
+          if (s == G_FREE + G_PARK) {
+            __syncthreads();  // (S^T U is parked)
+            TGP_STAMP(10);
+          }
+          if (s + 1 < 32) fetch_x(s + 1);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) d[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][0], d[i][2], 0, 0, 0);
+          if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // ds_reads of the next group
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                   // 2 x MFMA
+          if (s >= G_FREE && s < G_FREE + G_PARK) {
+            // S^T U to U_r's words [128][first 128 of 192], column c of row p at c ^ 16 ((p >> 2) & 1): the two lq of a
+            // half-wave land on different halves of the 32 banks, so the ds_write_b32 are conflict-free, and 16-byte
+            // vectors stay whole.  Two of the sixteen per group.
+#pragma unroll
+            for (int h = 0; h < PARK_PER; ++h) {
+              const int e = PARK_PER * (s - G_FREE) + h, i = e >> 3, j = (e >> 2) & 1, r = e & 3;
+              const int p = wm * 32 + 16 * i + 4 * lq + r;
+              UXf[p * 192 + ((wn * 32 + 16 * j + l15) ^ ((lq & 1) << 4))] = d[i][j][r];
+            }
+          }
+          if (s >= G_FREE + G_PARK && s < G_FREE + G_PARK + 8) {
+            // rows and columns < Nc of the parked tile to the slab: 32 lanes per 512-byte row, one read or one store per group
+            const int e = s - (G_FREE + G_PARK), q = e >> 1;
+            const int row = (tid >> 5) + 32 * q, c4 = (tid & 31) * 4;
+            if ((e & 1) == 0) pv = *reinterpret_cast<const float4*>(UXf + row * 192 + (c4 ^ (((row >> 2) & 1) << 4)));
+            else if (row < Nc && c4 < Nc) *reinterpret_cast<float4*>(cp + q * cp_step) = pv;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        TGP_STAMP(11);
+        if (F) {  // columns < F of S^T X, rows < Nc (rows >= Nc are 0 * X: not zeros when X holds a NaN)
+          float* Cx = RX.C + static_cast<long>(batch) * RX.sC + static_cast<long>(tm) * RX.sCsplit;
+          const int col = wn * 16 + l15;
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = wm * 32 + 16 * i + 4 * lq + r;
+              if (row < Nc && col < F) Cx[static_cast<long>(row) * RX.ldc + col] = d[i][2][r];
+            }
+        }
       }
       if (g.colsum) {  // (workgroup-uniform)
         __syncthreads();  // (S_r is dead: the eight partials per column lie there, [8][BN])
@@ -1435,6 +1497,13 @@ static void launch_gemm_skip_zeros(GemmArgs g, int batches, hipStream_t stream) 
 constexpr int FOLD_BM = 128, FOLD_MAX_F = 64;
 static int fold_tiles(int64_t N, int64_t K, int64_t F) {  // row tiles per graph, 0 = the shape does not fold
   return (K <= 128 && K % 4 == 0 && F <= FOLD_MAX_F && F % 4 == 0) ? cdiv(N, FOLD_BM) : 0;
+}
+// Floats of one slab of the folded route, rows x cols of S^T U (K x K) or S^T X (K x F).  TGP_FOLD_BLOCKS: an array of
+// 16 x 16 blocks, block row major, 256 floats per block; element (p, c) lies in block (p / 16, c / 16) at word
+// 4 lane + r with lane = 16 ((p % 16) / 4) + c % 16 and r = p % 4 -- d[r] of that lane in v_mfma_f32_16x16x4_f32's
+// accumulator layout.  Blocks wholly beyond rows / cols do not exist; otherwise the slab is row-major.
+static int64_t fold_slab_floats(int64_t rows, int64_t cols) {
+  return TGP_FOLD_BLOCKS ? ((rows + 15) / 16) * ((cols + 15) / 16) * 256 : rows * cols;
 }
 template <bool A_KMAJOR>
 static bool launch_gemm_fold(GemmArgs g, int batches, hipStream_t stream) {
