@@ -12,14 +12,25 @@ input a kernel is documented to reject.
 Families: Just Balance ("jb"), DMoN's losses ("dmon"), HOSC's losses ("hosc"), AsymCheegerCut's losses ("acc"),
 BN-Pool's reconstruction loss ("bnpool"), LaPool's selector ("lapool"), the segment readout ("readout"), the SAG scorer
 ("sag"), the k-MIS selector ("kmis"), the edge-contraction selector ("edge_contract"), ASAP's fitness ("asap") and
-MaxCut's score net, cut loss and assignment rounds ("maxcut").  New families are APPENDED: ``_gen`` seeds from a
-family's position in ``FAMILIES``.
+MaxCut's score net, cut loss and assignment rounds ("maxcut"), GTVConv's propagation with its two backward operators
+("gtv"), PAN's MET matrix, its backward and the pooling score ("pan") and EigenPooling's modes, Reduce and Lift
+("eigenpool").  New families are APPENDED: ``_gen`` seeds from a family's position in ``FAMILIES``.
 """
+import os
 import random
+import sys
 
 import torch
 
-FAMILIES = ("jb", "readout", "sag", "kmis", "edge_contract", "bnpool", "dmon", "hosc", "acc", "lapool", "asap", "maxcut")
+# The draws of "gtv" and "pan" depend on the float64 restatements (tests/gtv_restatement.py, tests/pan_restatement.py):
+# their sub-seed walks ask the reference whether a candidate keeps its kinks or its top-k cut clear of rounding.  Those
+# modules are imported inside the draw functions, from this directory.
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+FAMILIES = ("jb", "readout", "sag", "kmis", "edge_contract", "bnpool", "dmon", "hosc", "acc", "lapool", "asap", "maxcut",
+            "gtv", "pan", "eigenpool")
 SEEDS = tuple(range(16))
 
 ROWS = (0, 1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200)
@@ -46,6 +57,47 @@ MAXCUT_TAILS = ((), (16, 16), (64,), "unfit")  # "unfit": one mlp layer wider th
 NP_CLASSES = ("full", "below", "empty", "loops")  # n_P = max(edge_index) + 1 against N; no edge; self-loops only
 MAXCUT_KEEP = ("one", "half", "all")  # kept nodes per graph handed to the assignment rounds
 FRAME_CACHE_ENTRIES = 4096  # a graph with more entries than this (and at most 1024 nodes) overflows the frame's LDS cache
+# GTVConv (csrc/gtvconv.hip, ``gtv_pick``): G = 8 | 16 | 32 | 64 lanes own a node at C <= 32 | 64 | 128 | more, a lane holds
+# R = 4 channels (8 above 256), a block of 256 threads holds 256 / G nodes, and above the library's register limit (512)
+# the chunked kernels take one wave per node (4 per block).  16-byte loads at C % 4 == 0 on aligned rows, scalar loads
+# otherwise: every switch has a width of either form on each side.  One value per seed.
+GTV_WIDTHS = (1, 3, 4, 5, 32, 33, 64, 65, 128, 129, 256, 257, 260, 512, 513, 516)
+GTV_LANE_GROUPS = ((32, 8, 4), (64, 16, 4), (128, 32, 4), (256, 64, 4))  # (widest C, G, R); wider rows: G = 64, R = 8
+GTV_BATCHES = (1, 2, 3, 4, 5)
+GTV_OUT_HUBS = (0, 1, 63, 64, 65)  # one node's out-degree (the forward's and the terms kernel's loop)
+GTV_IN_HUBS = (0, 1, 65, 257)      # another node's in-degree, its out-degree 1: the node kernel's in-edge loop is the long one
+GTV_ACT_NAMES = ("identity", "relu", "elu")  # (the keys of kernels.GTV_ACT_CODES)
+GTV_DELTAS = (1.0, 0.311)
+GTV_EPS = (1e-3, 0.5)  # the second clamps a share of the edges
+GTV_MARGIN = 1e-4      # how far every kink of the propagation stays from the data (see _draw_gtv)
+GTV_F_IN = 5           # input width of the public layer: h = x @ weight
+GTV_SUB_SEEDS = 200
+# PAN (csrc/pan.hip): the backward walks a row's stored entries 64 per step and a graph's columns 64 per step in a frame
+# of max_n floats per wave; graphs of up to the library's limit (1024) nodes.  ``pan_score_kernel`` splits a node over
+# G = 16 lanes (no query: the constant of that kernel), both for the F columns of x and for the node's column group.
+PAN_SIZES = (1, 2, 3, 63, 64, 65, 127, 128, 129)
+PAN_BATCHES = (1, 2, 5)
+PAN_FILTERS = (0, 1, 2, 3, 4)
+PAN_HUB_ENTRIES = (1, 63, 64, 65, 129)  # stored entries of one planted row
+PAN_WEIGHTS = ("plain", "zero", "negative")  # |w| in [0.4, 0.9]; one exact zero; one negative
+PAN_SCORE_LANES = 16
+PAN_SCORE_FEATURES = (1, 15, 16, 17, 33, 64)
+PAN_SCORE_GROUPS = (0, 1, 15, 16, 17, 33)  # entries of one node's column group
+PAN_F = 4              # channels of x and of the convolution's output
+PAN_GAP = 1e-4         # the kept and the dropped scores of every graph are at least this far apart
+PAN_SUB_SEEDS = 200
+# EigenPooling (csrc/eigenpool.hip).  The modes kernel solves groups of up to the library's limit (96) nodes; its rotation
+# schedule pads odd sizes.  The Reduce kernel has no query for its constants: one wave adds a group of up to
+# EIG_REDUCE_ONE_WAVE = 128 rows alone, 4 waves share longer ones up to EIG_REDUCE_FOUR_WAVES = 1024, 16 beyond (the host
+# picks by the ``max_len`` hint), rows unrolled by 4, EIG_MODE_CHUNK = 8 modes per pass.
+EIG_REDUCE_ONE_WAVE, EIG_REDUCE_FOUR_WAVES, EIG_MODE_CHUNK, EIG_ROW_UNROLL = 128, 1024, 8, 4
+EIG_MODES = (1, 5, 8, 9)                  # H of the modes kernel
+EIG_LONGEST = (127, 128, 129, 1023, 1024, 1025)  # rows of the Reduce's longest group
+EIG_OTHER_ROWS = (0, 1, 5, 13)            # rows of its other groups
+EIG_FEATURES = (1, 3, 63, 64, 65, 130)
+EIG_REDUCE_MODES = (1, 7, 8, 9, 17)
+EIG_K = 3                                 # clusters per graph of the modes draw
+EIG_GAP = 1e-3                            # the spectral gap and the sign entry below which a group keeps the invariants only
 
 # the limits each family reads from the library (name -> the rows drawn around it: L - 1, L, L + 1)
 LIMITS = {
@@ -62,10 +114,13 @@ LIMITS = {
     "lapool": (),
     "asap": (),
     "maxcut": (),
+    "gtv": (),  # (graph sizes follow the nodes of a block at the drawn width, see _plan_gtv)
+    "pan": ("pan_max_graph_nodes",),
+    "eigenpool": ("eigenpool_max_group_nodes",),
 }
 # limits a draw reads without drawing graph sizes around them (the rows per partial sum of MaxCut's weight gradient,
-# the widest row its kernels take)
-DRAW_LIMITS = {"maxcut": ("maxcut_wgrad_rows", "maxcut_max_width")}
+# the widest row its kernels take; the widest row GTVConv's register kernels take)
+DRAW_LIMITS = {"maxcut": ("maxcut_wgrad_rows", "maxcut_max_width"), "gtv": ("gtv_register_channels",)}
 CLUSTER_LIMITS = {"bnpool": "bnpool_max_clusters"}  # K also draws this limit and half of it
 LAYOUTS = {
     "jb": ("ptr", "ptr_offset", "sizes", "mask_prefix", "mask_holes", "mask_empty_row"),
@@ -84,6 +139,9 @@ LAYOUTS = {
     # 16-byte loads; contiguous but 4 bytes into its buffer
     "asap": ("plain", "sliced_unaligned", "sliced_aligned", "offset"),
     "maxcut": ("plain", "offset"),
+    "gtv": ("plain", "offset"),  # h contiguous; contiguous but 4 bytes into its buffer (no 16-byte load may touch it)
+    "pan": ("plain", "sliced"),  # the scorer's x: contiguous; a column slice (ldx > F)
+    "eigenpool": ("plain", "sliced"),  # the Reduce's x: contiguous; a column slice
 }
 READOUT_OPS = ("sum", "mean", "min", "max")
 READOUT_SUBSETS = tuple(tuple(op for i, op in enumerate(READOUT_OPS) if m >> i & 1) for m in range(1, 16))
@@ -165,6 +223,10 @@ def _complete(family, limits, cfgs):
         return any(max(c["sizes"]) == lim and c["K"] <= lim and c["alpha"] > 0 for c in cfgs)
     if family in ("asap", "maxcut"):
         return _complete_edges(family, cfgs)
+    if family == "gtv":
+        return _complete_gtv(limits, cfgs)
+    if family == "pan":
+        return _complete_pan(limits, cfgs)
     if family not in ("kmis", "edge_contract"):
         return True
     lim = int(limits[LIMITS[family][0]])
@@ -270,8 +332,155 @@ def _plan_edges(family, cfgs, rng):
                         seen.add(w)
 
 
+def gtv_layout_class(c, limits):
+    """(G, R) of the register kernels at width ``c`` by the library's rule restated, "chunked" above its register limit."""
+    if c > int(limits["gtv_register_channels"]):
+        return "chunked"
+    return next(((g, r) for top, g, r in GTV_LANE_GROUPS if c <= top), (64, 8))
+
+
+def gtv_block_nodes(c, limits):
+    """Nodes of one 256-thread block: 256 / G, one wave per node on the chunked kernels."""
+    cls = gtv_layout_class(c, limits)
+    return 4 if cls == "chunked" else 256 // cls[0]
+
+
+def gtv_load_form(c, layout):
+    """"vec16" (C % 4 == 0 on 16-byte aligned rows) or "scalar"; fresh outputs are aligned, so ``h`` decides."""
+    return "vec16" if c % 4 == 0 and layout == "plain" else "scalar"
+
+
+def _plan_gtv(limits, rng):
+    """One width per seed; graph sizes P - 1, P, P + 1 around the P nodes of a block at that width, 1 and 2 besides; the
+    widths that alone hold a lane group's 16-byte form keep aligned rows, 32 and 512 lose them."""
+    n = len(SEEDS)
+    cfgs = [{"family": "gtv", "seed": s, "C": c} for s, c in enumerate(_one_each(GTV_WIDTHS, rng))]
+    batches = _one_each(GTV_BATCHES, rng)
+    groups = {}
+    for cfg in cfgs:
+        cfg["block_nodes"] = gtv_block_nodes(cfg["C"], limits)
+        groups.setdefault(cfg["block_nodes"], []).append(cfg)
+    for p, group in sorted(groups.items()):
+        need = -(-3 // len(group))  # graphs per seed so that P - 1, P and P + 1 all fit the group's seeds
+        counts = [max(batches[c["seed"]], need) for c in group]
+        small = (1, 2) if p == min(groups) else ()
+        for cfg, b, sz in zip(group, counts, _spread((p - 1, p, p + 1) + small, counts, rng)):
+            cfg["B"], cfg["sizes"] = b, list(sz)
+    for cfg, out_hub, in_hub, order, loops, weighted, mask, lay, act, delta, eps, bias, dense in zip(
+            cfgs, _one_each(GTV_OUT_HUBS, rng), _one_each(GTV_IN_HUBS, rng), _one_each(EDGE_ORDERS, rng),
+            _one_each((True, False), rng), _one_each((True, False), rng), _one_each((True, False, False), rng),
+            _one_each(LAYOUTS["gtv"], rng), _one_each(GTV_ACT_NAMES, rng), _one_each(GTV_DELTAS, rng),
+            _one_each(GTV_EPS, rng), _one_each((True, True, True, False), rng), _one_each((True, True) + (False,) * 14, rng)):
+        cfg.update(out_hub=out_hub, in_hub=in_hub, order=order, dups_loops=loops, weighted=weighted, mask=mask,
+                   layout=lay, act=act, delta=delta, eps=eps, bias=bias, dense=dense, directed=rng.random() < 0.5)
+        if cfg["C"] in (4, 64, 128, 256, 260):
+            cfg["layout"] = "plain"
+        elif cfg["C"] in (32, 512):
+            cfg["layout"] = "offset"
+    assert len(cfgs) == n
+    return cfgs
+
+
+def _complete_gtv(limits, cfgs):
+    """Every graph-size value of every block size, a graph for the two hubs in every draw, every batch size, both load
+    forms in every layout class of the register kernels, both layouts, and the pairs the spreads do not guarantee: relu
+    with a mask and without, a long in-edge loop on either form of the by-destination index."""
+    if {c["B"] for c in cfgs} != set(GTV_BATCHES) or {c["layout"] for c in cfgs} != set(LAYOUTS["gtv"]):
+        return False
+    if any(max(c["sizes"]) < 3 for c in cfgs) or not {1, 2} <= {v for c in cfgs for v in c["sizes"]}:
+        return False
+    for p in {c["block_nodes"] for c in cfgs}:
+        if not {p - 1, p, p + 1} <= {v for c in cfgs if c["block_nodes"] == p for v in c["sizes"]}:
+            return False
+    forms = {(gtv_layout_class(c["C"], limits), gtv_load_form(c["C"], c["layout"])) for c in cfgs}
+    classes = {k for k, _ in forms if k != "chunked"}
+    if any((k, f) not in forms for k in classes for f in ("vec16", "scalar")):
+        return False
+    if {c["mask"] for c in cfgs if c["act"] == "relu"} != {True, False}:
+        return False
+    long_in = {c["order"] == "by_destination" for c in cfgs if c["in_hub"] >= 65}
+    return long_in == {True, False} and any(c["eps"] == 0.5 and c["weighted"] for c in cfgs)
+
+
+def _plan_pan(limits, rng):
+    """Graph sizes 1 .. 129 and L - 1, L, L + 1 of the node limit over batches of 1, 2 and 5; a draw with a graph at the
+    limit keeps filter_size <= 2 (and its big graphs a mean degree of 1.5); the planted row has one stored entry where
+    filter_size = 0 leaves no other."""
+    lim = int(limits["pan_max_graph_nodes"])
+    batches = _one_each(PAN_BATCHES, rng)
+    sizes = _spread(PAN_SIZES + (lim - 1, lim, lim + 1), batches, rng)
+    seen = set()
+    for sz in sizes:  # a size at the limit once over the seeds and alone in its draw: the random fill-ins become small ones
+        for i, v in enumerate(sz):
+            if v >= lim - 1 and (v in seen or any(u >= lim - 1 for u in sz[:i])):
+                sz[i] = rng.choice(PAN_SIZES)
+            elif v >= lim - 1:
+                seen.add(v)
+    cfgs = [{"family": "pan", "seed": s, "B": batches[s], "sizes": list(sizes[s])} for s in range(len(SEEDS))]
+    for cfg, L, hub, kind, directed, order, lay, f, grp, use_tanh in zip(
+            cfgs, _one_each(PAN_FILTERS * 3 + (2,), rng), _one_each(PAN_HUB_ENTRIES * 3 + (65,), rng), _one_each(PAN_WEIGHTS, rng),
+            _one_each((True, False), rng), _one_each(("by_source", "shuffled"), rng), _one_each(LAYOUTS["pan"], rng),
+            _one_each(PAN_SCORE_FEATURES, rng), _one_each(PAN_SCORE_GROUPS, rng), _one_each((True, False), rng)):
+        big = max(cfg["sizes"]) >= lim - 1
+        L = min(L, 2) if big else L
+        cfg.update(filter_size=L, hub=hub if L > 0 else 1, weights=kind if L > 0 else "plain", directed=directed,
+                   order=order, layout=lay, score_F=f, score_group=grp, use_tanh=use_tanh, at_limit=big)
+    return cfgs
+
+
+def _complete_pan(limits, cfgs):
+    lim = int(limits["pan_max_graph_nodes"])
+    if {c["hub"] for c in cfgs} != set(PAN_HUB_ENTRIES) or {c["filter_size"] for c in cfgs} != set(PAN_FILTERS):
+        return False
+    if {c["weights"] for c in cfgs} != set(PAN_WEIGHTS) or {c["B"] for c in cfgs} != set(PAN_BATCHES):
+        return False
+    # the three sizes at the limit in three draws (one reference of that size per draw); past a wave of stored entries
+    # with the longest series; both list orders on the native route
+    if not set(PAN_SIZES) | {lim - 1, lim, lim + 1} <= {v for c in cfgs for v in c["sizes"]}:
+        return False
+    if sum(c["at_limit"] for c in cfgs) != 3 or any(sum(v >= lim - 1 for v in c["sizes"]) > 1 for c in cfgs):
+        return False
+    if any(c["at_limit"] and c["filter_size"] == 0 for c in cfgs):  # (a series of one term shows nothing of a big graph)
+        return False
+    native = [c for c in cfgs if max(c["sizes"]) <= lim]
+    return any(c["hub"] >= 65 and c["filter_size"] >= 3 for c in native) and {c["order"] for c in native} == {"by_source", "shuffled"} \
+        and {c["directed"] for c in native} == {True, False}
+
+
+EIG_SIZE_CLASSES = ("1", "2", "3", "H-1", "H", "H+1", "even", "odd", "L-1", "L", "L+1")
+
+
+def _plan_eigenpool(limits, rng):
+    """Modes: four group sizes per seed by class (1, 2, 3; around the drawn H; an even and an odd size in 20 .. 40;
+    around the group limit), laid out as two graphs of EIG_K clusters -- [a, empty, b] and [c, d, 2].  Reduce and Lift:
+    the longest group, the feature and mode counts, the layout of x."""
+    lim = int(limits["eigenpool_max_group_nodes"])
+    n = len(SEEDS)
+    cfgs = []
+    for s, (h, classes) in enumerate(zip(_one_each(EIG_MODES, rng), _spread(EIG_SIZE_CLASSES, [4] * n, rng))):
+        size = {"1": 1, "2": 2, "3": 3, "H-1": max(h - 1, 1), "H": h, "H+1": h + 1, "even": 2 * rng.randrange(10, 21),
+                "odd": 2 * rng.randrange(10, 20) + 1, "L-1": lim - 1, "L": lim, "L+1": lim + 1}
+        a, b, c, e = (size[k] for k in classes)
+        cfgs.append({"family": "eigenpool", "seed": s, "H": h, "classes": tuple(classes), "B": 2,
+                     "sizes": [a + b, c + e + 2], "clusters": [[a, 0, b], [c, e, 2]]})
+    for cfg, norm, longest, f, h2, lay in zip(cfgs, _one_each((True, False), rng), _one_each(EIG_LONGEST, rng),
+                                              _one_each(EIG_FEATURES, rng), _one_each(EIG_REDUCE_MODES, rng),
+                                              _one_each(LAYOUTS["eigenpool"], rng)):
+        others = list(EIG_OTHER_ROWS) + [rng.choice(EIG_OTHER_ROWS), rng.choice(EIG_OTHER_ROWS)]
+        rng.shuffle(others)
+        cfg.update(normalized=norm, longest=longest, F=f, reduce_H=h2, layout=lay,
+                   rows=others[:3] + [longest] + others[3:], hints=cfg["seed"] % 4 == 0)
+    return cfgs
+
+
 def _plan(family, limits, rng):
     n = len(SEEDS)
+    if family == "gtv":
+        return _plan_gtv(limits, rng)
+    if family == "pan":
+        return _plan_pan(limits, rng)
+    if family == "eigenpool":
+        return _plan_eigenpool(limits, rng)
     batches = _one_each(BATCHES, rng)
     # B >= 3: one slot is kept for the graph of 0 rows; 0 is not handed to the smaller batches (a batch without any row)
     counts = [b - 1 if b >= 3 else b for b in batches]
@@ -857,7 +1066,230 @@ def _draw_maxcut(cfg, g, limits):
     return d
 
 
-_DRAW = {"asap": _draw_asap, "maxcut": _draw_maxcut, "jb": _draw_jb, "dmon": _draw_dmon, "hosc": _draw_dmon, "acc": _draw_acc, "bnpool": _draw_bnpool,
+def gtv_margins(h, edge_index, edge_weight, bias, mask, delta, eps, act):
+    """How far the propagation's kinks stay from float64 rows ``h``: (the smallest nonzero channel difference |h_ic -
+    h_jc| over the non-loop edges, the smallest |d_e - eps| / eps, for relu the smallest |pre-activation| over the rows
+    the mask keeps -- a masked row is an exact zero with slope x mask = 0 on both sides -- and inf otherwise)."""
+    import gtv_restatement as R
+    inf = float("inf")
+    diff, dist = R.distances(h, edge_index)
+    pos = diff[diff > 0]
+    gap = float(pos.min()) if pos.numel() else inf
+    near = float(((dist - eps).abs() / eps).min()) if dist.numel() else inf
+    pre = inf
+    if act == "relu":
+        z = R.propagate(h, edge_index, None if edge_weight is None else edge_weight.to(h.dtype),
+                        None if bias is None else bias.to(h.dtype), None, delta, eps, None)
+        z = z if mask is None else z[mask]
+        pre = float(z.abs().min()) if z.numel() else inf
+    return gap, near, pre
+
+
+def gtv_draw_margins(d):
+    """The three margins of a draw, the worse of its two layers: the operator layer's rows ``h`` (with the mask) and the
+    public layer's ``x @ weight`` (sparse mode takes no mask), both in float64."""
+    op = gtv_margins(d["h"].double(), d["edge_index"], d["edge_weight"], d["bias"], d["mask"], d["delta"], d["eps"], d["act"])
+    pub = gtv_margins(d["x"].double() @ d["weight"].double(), d["edge_index"], d["edge_weight"], d["bias"], None,
+                      d["delta"], d["eps"], d["act"])
+    return tuple(min(a, b) for a, b in zip(op, pub))
+
+
+def _gtv_candidate(cfg, g):
+    sizes, C = cfg["sizes"], cfg["C"]
+    d = dict(cfg)
+    ptr = _ptr(sizes)
+    n = int(ptr[-1])
+    parts = [_edges(c, min(0.3, 4.0 / max(c, 1)), cfg["directed"], g, self_loops=cfg["dups_loops"],
+                    duplicates=cfg["dups_loops"]) + int(ptr[i]) for i, c in enumerate(sizes)]
+    ei = torch.cat(parts, 1)
+    # the two hubs sit in the longest graph (at least 3 nodes): v takes in-edges only from, u sends out-edges only to,
+    # the nodes that are neither (repeats: duplicates), so that both degrees are exact
+    big = max(range(len(sizes)), key=lambda i: sizes[i])
+    lo, c = int(ptr[big]), sizes[big]
+    v, u = lo, lo + c // 2
+    rest = torch.tensor([i for i in range(lo, lo + c) if i not in (u, v)])
+    ei = ei[:, (ei[0] != u) & (ei[0] != v) & (ei[1] != v)]
+    pick = lambda k: rest[torch.randint(0, rest.numel(), (k,), generator=g)]  # noqa: E731
+    src, dst = pick(cfg["in_hub"]), pick(cfg["out_hub"])
+    ei = torch.cat([ei, torch.stack([src, torch.full_like(src, v)]), torch.stack([torch.full_like(dst, u), dst]),
+                    torch.stack([torch.tensor([v]), pick(1)])], 1)
+    if cfg["dups_loops"]:  # (skipped by the kernels: neither hub's degree counts them)
+        ei = torch.cat([ei, torch.tensor([[u, v], [u, v]])], 1)
+    ei = ei[:, torch.randperm(ei.size(1), generator=g)]
+    if cfg["order"] != "shuffled":
+        ei = ei[:, torch.argsort(ei[1 if cfg["order"] == "by_destination" else 0], stable=True)]
+    ei = ei.contiguous()
+    E = ei.size(1)
+    ew = None
+    if cfg["weighted"]:
+        ew = torch.rand(E, generator=g) + 0.25
+        ew[torch.rand(E, generator=g) < 0.1] = 0.0
+    # rows: N(0, 1); three joined pairs are made twins -- h_j = h_i except in at most two channels, which differ by
+    # 0.05 .. 0.12 (d_e in 0.05 .. 0.24: clamped at eps = 0.5, free at 1e-3; every other channel difference an exact 0)
+    # -- and under eps = 0.5 one pair is equal in every channel (d_e = 0; at eps = 1e-3 its gamma of 1000 w would
+    # drown every other term of dh)
+    h = torch.randn(n, C, generator=g)
+    x = torch.randn(n, GTV_F_IN, generator=g)
+    real = (ei[0] != ei[1]).nonzero().view(-1)
+    twins, used = [], set()
+    for e in real[torch.randperm(real.numel(), generator=g)].tolist():  # (pairs that share no node: none undoes another)
+        if len(twins) < 4 and not {int(ei[0, e]), int(ei[1, e])} & used:
+            twins.append(e)
+            used |= {int(ei[0, e]), int(ei[1, e])}
+    for k, e in enumerate(twins):
+        i, j = int(ei[0, e]), int(ei[1, e])
+        h[j] = h[i]
+        if k == 0 and cfg["eps"] == 0.5:
+            x[j] = x[i]
+            continue
+        ch = torch.randperm(C, generator=g)[:2]
+        step = 0.05 + 0.07 * torch.rand(ch.numel(), generator=g)
+        h[j, ch] += torch.where(torch.rand(ch.numel(), generator=g) < 0.5, -step, step)
+    d.update(edge_index=ei, edge_weight=ew, ptr=ptr, n=n, batch=_batch(sizes), h=h, x=x, twin_edges=twins,
+             weight=torch.randn(GTV_F_IN, C, generator=g) * (2.0 / GTV_F_IN) ** 0.5,
+             bias=torch.randn(C, generator=g) * 0.3 if cfg["bias"] else None,
+             mask=(torch.rand(n, generator=g) < 0.7) if cfg["mask"] else None, out_hub_node=u, in_hub_node=v)
+    d["form"] = gtv_load_form(C, cfg["layout"])
+    return d
+
+
+def _draw_gtv(cfg, g, limits):
+    """h [n, C] (the operator layer's rows), x [n, 5] and weight [5, C] (the public layer's: h = x @ weight), the list in
+    the drawn order with the two hubs, weights (a tenth exact zeros) or None, bias or None, a node mask or None.
+
+    The propagation has kinks: |h_ic - h_jc| at 0, max(d_e, eps) at d_e = eps, relu at 0.  A float32 product on the other
+    side of one differs from the float64 reference by a whole term, not by rounding, so -- the separation rule of
+    ``GradCase`` in tests/test_gpu_gtv.py -- sub-seeds are walked until, in float64 and for both layers, no edge has a
+    channel difference in (0, GTV_MARGIN), no distance lies within GTV_MARGIN eps of eps and, for relu, no pre-activation
+    of a kept row lies within GTV_MARGIN of 0.  No draw is given up: 200 sub-seeds that all fail raise."""
+    base = int(g.initial_seed())
+    for sub in range(GTV_SUB_SEEDS):
+        d = _gtv_candidate(cfg, torch.Generator().manual_seed(base * 1009 + sub))
+        gap, near, pre = gtv_draw_margins(d)
+        if gap >= GTV_MARGIN and near >= GTV_MARGIN and pre >= GTV_MARGIN:
+            d["sub_seed"] = sub
+            return d
+    raise RuntimeError(f"gtv seed {cfg['seed']}: {GTV_SUB_SEEDS} sub-seeds did not keep the kinks away")
+
+
+def pan_cut_gap(score, batch, sizes, ratio=0.5):
+    """The smallest distance between a kept and a dropped score over the graphs (top ceil(ratio n_b) of each): inf where
+    every node of every graph is kept."""
+    gap, lo = float("inf"), 0
+    for c in sizes:
+        k = -(-c * ratio // 1)
+        s = torch.sort(score[lo:lo + c], descending=True).values
+        if 0 < k < c:
+            gap = min(gap, float(s[int(k) - 1] - s[int(k)]))
+        lo += c
+    return gap
+
+
+def _draw_pan(cfg, g, limits):
+    """The list of a sorted batch (random endpoints: loops and multi-edges as they fall; mirrored unless directed; graphs
+    above 200 nodes at a mean degree of 1.5) plus one more graph, the hub: ``hub`` nodes that all reach its first node
+    within min(filter_size, 2) hops, so that this row of M stores exactly ``hub`` entries.  ``weight`` [L + 1] with |w|
+    in [0.4, 0.9], one exact zero or one negative entry where drawn (the pattern is structural: it must not change).
+    The public layer's x, ``lin``, ``p`` and ``beta`` are walked over sub-seeds until the float64 scores of every graph
+    keep PAN_GAP between the kept and the dropped nodes (the selection is a top-k: the kept SET is compared exactly).
+    The scorer's own inputs: x [n, score_F], p, beta, and a list of entries with values in which one node's column group
+    holds exactly ``score_group`` entries."""
+    import pan_restatement as R
+    d = dict(cfg)
+    L, k = cfg["filter_size"], cfg["hub"]
+    sizes = list(cfg["sizes"]) + [k]
+    ptr = _ptr(sizes)
+    n = int(ptr[-1])
+    parts = []
+    for i, c in enumerate(cfg["sizes"]):
+        m = int(c * (1.5 if c > 200 else (0.5, 1.5, 3.0)[i % 3])) if c > 1 else 0
+        e = torch.randint(0, c, (2, m), generator=g)
+        parts.append((e if cfg["directed"] else torch.cat([e, e.flip(0)], 1)) + int(ptr[i]))
+    direct = max(1, (k - 1) // 2) if L >= 2 else k - 1  # the hub: nodes 1 .. direct point at node 0, the rest at one of them
+    src = torch.arange(1, k)
+    dst = torch.where(src <= direct, torch.zeros_like(src), 1 + torch.randint(0, max(direct, 1), (k - 1,), generator=g))
+    parts.append(torch.stack([src, dst]) + int(ptr[-2]))
+    ei = torch.cat(parts, 1)
+    ei = ei[:, torch.randperm(ei.size(1), generator=g)]
+    if cfg["order"] == "by_source":
+        ei = ei[:, torch.argsort(ei[0], stable=True)]
+    w = 0.4 + 0.5 * torch.rand(L + 1, generator=g)
+    at = int(torch.randint(1, L + 1, (1,), generator=g)) if L > 0 else 0
+    if cfg["weights"] == "zero":
+        w[at] = 0.0
+    elif cfg["weights"] == "negative":
+        w[at] = -w[at]
+    batch = _batch(sizes)
+    d.update(all_sizes=sizes, ptr=ptr, n=n, batch=batch, edge_index=ei.contiguous(), weight=w, hub_row=int(ptr[-2]),
+             route="native" if max(sizes) <= int(limits["pan_max_graph_nodes"]) else "composed")
+    # the scorer's own inputs
+    f, t = cfg["score_F"], n // 2
+    idx = torch.randint(0, n, (2, 3 * n), generator=g)
+    idx = torch.cat([idx[:, idx[1] != t], torch.stack([torch.randint(0, n, (cfg["score_group"],), generator=g),
+                                                       torch.full((cfg["score_group"],), t)])], 1)
+    idx = idx[:, torch.argsort(idx[0] * n + idx[1], stable=True)].contiguous()
+    d.update(score_index=idx, score_values=torch.randn(idx.size(1), generator=g), score_node=t,
+             score_x=torch.randn(n, f, generator=g), score_p=torch.randn(f, generator=g) / f ** 0.5,
+             beta=torch.tensor([0.7, -1.3]))
+    index, values = R.met(d["edge_index"], w.double(), n, batch)
+    base = int(g.initial_seed())
+    for sub in range(PAN_SUB_SEEDS):
+        gen = torch.Generator().manual_seed(base * 1013 + sub)
+        x = torch.randn(n, PAN_F, generator=gen)
+        lin_w, lin_b = torch.randn(PAN_F, PAN_F, generator=gen) * 0.5, torch.randn(PAN_F, generator=gen) * 0.1
+        p = torch.randn(PAN_F, generator=gen)
+        p = p / p.norm()
+        h = torch.zeros(n, PAN_F, dtype=torch.float64).index_add(0, index[0], values.view(-1, 1) * x.double()[index[1]])
+        h = h @ lin_w.double().t() + lin_b.double()
+        score = torch.tanh(R.raw_score(h, index, values, p.double(), d["beta"].double()))
+        if pan_cut_gap(score, batch, sizes) >= PAN_GAP:
+            d.update(x=x, lin_w=lin_w, lin_b=lin_b, p=p, sub_seed=sub)
+            return d
+    raise RuntimeError(f"pan seed {cfg['seed']}: {PAN_SUB_SEEDS} sub-seeds left no gap at the cut")
+
+
+def _draw_eigenpool(cfg, g, limits):
+    """Modes and the public layer: two graphs of EIG_K clusters, the nodes of a graph's clusters interleaved (``labels``),
+    one cluster of the first graph empty; every group connected (a path through it) and dense (half of its pairs), with
+    distinct weights in [0.1, 1) that separate its spectrum; as many weighted edges between a graph's clusters again;
+    the list symmetric and shuffled; x [n, 3].  Reduce and Lift on inputs of their own: groups of ``rows`` rows (the
+    longest among short ones, which leave most of the 4 or 16 waves without a row) interleaved in node order, any
+    values for theta [rows, reduce_H], x [rows, F] and x_pool [G, reduce_H F]."""
+    d = dict(cfg)
+    sizes, k = cfg["sizes"], EIG_K
+    ptr = _ptr(sizes)
+    n = int(ptr[-1])
+    labels = torch.cat([torch.repeat_interleave(torch.arange(k), torch.tensor(c))[torch.randperm(sum(c), generator=g)]
+                        for c in cfg["clusters"]])
+    batch = _batch(sizes)
+    gid = batch * k + labels
+    a = torch.zeros(n, n)
+    for grp in gid.unique().tolist():
+        nodes = (gid == grp).nonzero().view(-1)
+        m = nodes.numel()
+        up = torch.triu(torch.rand(m, m, generator=g) < 0.5, 1)
+        if m > 1:
+            up |= torch.diag(torch.ones(m - 1, dtype=torch.bool), 1)
+        w = torch.triu(torch.rand(m, m, generator=g) * 0.9 + 0.1, 1) * up
+        a[nodes.view(-1, 1), nodes.view(1, -1)] = w + w.t()
+    across = (batch.view(-1, 1) == batch.view(1, -1)) & (gid.view(-1, 1) != gid.view(1, -1))
+    w = torch.triu((torch.rand(n, n, generator=g) < 4.0 / n) * (torch.rand(n, n, generator=g) * 0.9 + 0.1), 1) * across
+    a = a + w + w.t()
+    ei = a.nonzero().t()
+    order = torch.randperm(ei.size(1), generator=g)
+    ei = ei[:, order].contiguous()
+    d.update(n=n, ptr=ptr, batch=batch, labels=labels, gid=gid, edge_index=ei, edge_weight=a[ei[0], ei[1]].contiguous(),
+             x=torch.randn(n, 3, generator=g), width=k)
+    rows = cfg["rows"]
+    total, G = sum(rows), len(rows)
+    rgid = _batch(rows)[torch.randperm(total, generator=g)]
+    d.update(reduce_gid=rgid, reduce_groups=G, theta=torch.randn(total, cfg["reduce_H"], generator=g),
+             reduce_x=torch.randn(total, cfg["F"], generator=g),
+             reduce_y=torch.randn(G, cfg["reduce_H"] * cfg["F"], generator=g))
+    return d
+
+
+_DRAW = {"gtv": _draw_gtv, "pan": _draw_pan, "eigenpool": _draw_eigenpool, "asap": _draw_asap, "maxcut": _draw_maxcut, "jb": _draw_jb, "dmon": _draw_dmon, "hosc": _draw_dmon, "acc": _draw_acc, "bnpool": _draw_bnpool,
          "lapool": _draw_lapool, "readout": _draw_readout, "sag": _draw_sag, "kmis": _draw_selector,
          "edge_contract": _draw_selector}
 
@@ -885,4 +1317,6 @@ def library_limits():
             "edge_contract_max_graph_nodes": int(lib.tgp_edge_contract_max_graph_nodes()),
             "bnpool_max_clusters": int(K.bnpool_max_clusters()),
             "hosc_small_graph_nodes": int(K.hosc_small_graph_nodes()),
-            "acc_small_graph_nodes": int(K.acc_small_graph_nodes()), "acc_tv_rows": int(K._ACC_TV_ROWS)}
+            "acc_small_graph_nodes": int(K.acc_small_graph_nodes()), "acc_tv_rows": int(K._ACC_TV_ROWS),
+            "gtv_register_channels": int(K.GTV_REGISTER_CHANNELS), "pan_max_graph_nodes": int(K.pan_max_graph_nodes()),
+            "eigenpool_max_group_nodes": int(K.eigenpool_max_group_nodes())}

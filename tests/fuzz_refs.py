@@ -6,9 +6,19 @@ reference's fixtures by its own CPU test) called on a draw of tests/fuzz_inputs.
 For ASAP and MaxCut the operator layer has every kernel's own plain definition on its own float32 inputs, the public
 layer the reference-shaped forms of tests/asap_restatement.py and tests/maxcut_restatement.py (not the collapsed
 algebra the kernels use), and the exact outputs are the edge-group index, the arg-max table and the labels.
+For GTVConv the operator layer is tests/gtv_restatement.py's ``propagate`` on the drawn rows with autograd's gradients
+at the activation input, the edge weights and the rows (what the two backward operators return), the public layer its
+``layer`` in sparse and in dense mode; ``gtv_backward_by_hand`` restates the backward operators' formulas for the wrong
+stand-ins of tests/test_fuzz_inputs.py.
+For PAN the MET matrix is stated as the sum of c_n-weighted dense powers of A_t with the series coefficients c as the
+leaf (asserted equal to tests/pan_restatement.py's ``met`` in float64), which gives ``pan_met_bwd``'s per-row shares and
+their column sums; the public layer is that matrix through the restatement's ``pool`` on the float64 selection.
+For EigenPooling the modes are tests/eigenpool_restatement.py's ``cluster_modes`` group by group (entries compared where
+the float64 spectrum separates them), Reduce and Lift their sums written out, the public layer ``collapsed``.
 Host only."""
 import os
 import sys
+import zlib
 
 import torch
 
@@ -20,11 +30,14 @@ import asap_restatement as RAS  # noqa: E402
 import bnpool_restatement as RB  # noqa: E402
 import dmon_restatement as RD  # noqa: E402
 import edgepool_restatement as RE  # noqa: E402
+import eigenpool_restatement as REG  # noqa: E402
+import gtv_restatement as RG  # noqa: E402
 import hosc_restatement as RH  # noqa: E402
 import jb_restatement as RJ  # noqa: E402
 import kmis_restatement as RK  # noqa: E402
 import lapool_restatement as RL  # noqa: E402
 import maxcut_restatement as RM  # noqa: E402
+import pan_restatement as RP  # noqa: E402
 import readout_restatement as RR  # noqa: E402
 import sag_restatement as RS  # noqa: E402
 
@@ -637,3 +650,318 @@ def maxcut_reference(d, dtype):
 def maxcut_labels_exact(d):
     """int64 [n]: the labels (1 .. K by position among the kept nodes, 0 = none) after ``max_iter`` rounds."""
     return torch.tensor(RM.assign_rounds(d["kept"], d["edge_index"], d["n"], d["max_iter"]), dtype=torch.long)
+
+
+# ---------------------------------------------------------------------------------------------------------- GTVConv
+def upstream(case, *shape):
+    """The upstream gradient of ``case``: float32 values seeded from the name (what tests/test_gpu_fuzz_families.py
+    hands the backward operators)."""
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(zlib.crc32(case.encode())))
+
+
+def gtv_skipped(d):
+    """bool [E]: the edges the kernels skip (self-loops; every endpoint of a draw is in range)."""
+    return d["edge_index"][0] == d["edge_index"][1]
+
+
+def gtv_operator_reference(d, dtype, case=None):
+    """``gtv_restatement.propagate`` on the draw's rows ``h``: "out", the distances "d" [E] (0 at a skipped edge), and the
+    gradients of <out, upstream(case + "g")> by autograd -- "g" at the activation's input before the mask (the bias is
+    handed in as one leaf row per node, whose gradient that is), "gw" at the edge weights (ones for a list without) and
+    "dh" at h.  Leaves "h" and "edge_weight"."""
+    case = f"gtv-op-{d['seed']}" if case is None else case
+    ei, (n, C) = d["edge_index"], d["h"].shape
+    E = ei.size(1)
+    h = _leaf(d["h"], dtype)
+    w = _leaf(torch.ones(E) if d["edge_weight"] is None else d["edge_weight"], dtype)
+    rows = _leaf((torch.zeros(C) if d["bias"] is None else d["bias"]).expand(n, C), dtype)
+    with torch.enable_grad():  # (the backward operators' outputs are gradients: also under a caller's no_grad)
+        out = RG.propagate(h, ei, w, rows, d["mask"], d["delta"], d["eps"], RG.ACTS[d["act"]])
+        dist = torch.zeros(E, dtype=dtype).index_put((gtv_skipped(d).logical_not().nonzero().view(-1),),
+                                                     RG.distances(h, ei)[1])
+        grads = torch.autograd.grad(out, [rows, w, h], upstream(case + "g", n, C).to(dtype), retain_graph=True,
+                                    allow_unused=True)
+    g, gw, dh = (torch.zeros_like(t) if v is None else v for t, v in zip((rows, w, h), grads))
+    return {"out": out, "d": dist, "g": g, "gw": gw, "dh": dh}, {"h": h, "edge_weight": w}
+
+
+def gtv_reference(d, dtype):
+    """The public layer in sparse mode: ``gtv_restatement.layer`` on x, weight, bias and the list (no mask, as in the
+    reference); every parameter and input a leaf."""
+    lv = {"x": _leaf(d["x"], dtype), "weight": _leaf(d["weight"], dtype), "bias": _leaf(d["bias"], dtype),
+          "edge_weight": _leaf(d["edge_weight"], dtype)}
+    out = RG.layer(lv["x"], lv["weight"], lv["bias"], d["edge_index"], lv["edge_weight"], None, d["delta"], d["eps"], d["act"])
+    return {"out": out}, lv
+
+
+def gtv_dense_batch(d):
+    """The draw's batch in dense mode: (x [B, N, 5] zero-padded, adj [B, N, N] float32 with duplicate edges added up and
+    the loops on its diagonal, mask [B, N] of the real rows)."""
+    sizes, ptr, ei = d["sizes"], d["ptr"], d["edge_index"]
+    B, N = len(sizes), max(sizes)
+    w = torch.ones(ei.size(1)) if d["edge_weight"] is None else d["edge_weight"]
+    b = d["batch"][ei[0]]
+    adj = torch.zeros(B, N, N).index_put((b, ei[0] - ptr[b], ei[1] - ptr[b]), w, accumulate=True)
+    x = torch.zeros(B, N, d["x"].size(1))
+    for i, c in enumerate(sizes):
+        x[i, :c] = d["x"][int(ptr[i]):int(ptr[i + 1])]
+    return x, adj, torch.arange(N).view(1, -1) < torch.tensor(sizes).view(-1, 1)
+
+
+def gtv_dense_reference(d, dtype):
+    """The public layer in dense mode on ``gtv_dense_batch``: "out" [B, N, C]; leaves x, weight, bias."""
+    x, adj, mask = gtv_dense_batch(d)
+    lv = {"x": _leaf(x, dtype), "weight": _leaf(d["weight"], dtype), "bias": _leaf(d["bias"], dtype)}
+    out = RG.layer(lv["x"], lv["weight"], lv["bias"], adj.to(dtype), None, mask, d["delta"], d["eps"], d["act"])
+    return {"out": out}, lv
+
+
+def gtv_in_edge_rank(d):
+    """int64 [E]: an edge's place among the in-edges of its destination, in the order of the by-destination index (list
+    order inside a node, skipped edges counted: the kernel walks them too)."""
+    dst = d["edge_index"][1]
+    order = torch.argsort(dst, stable=True)
+    first = torch.zeros(d["n"] + 1, dtype=torch.long)
+    first[1:] = torch.bincount(dst, minlength=d["n"]).cumsum(0)
+    rank = torch.empty_like(dst)
+    rank[order] = torch.arange(dst.numel()) - first[dst[order]]
+    return rank
+
+
+def gtv_backward_by_hand(d, dtype, case=None, drop_in_edge=None, slope_from_next_row=False):
+    """"g" and "dh" of the operator layer from the kernels' own formulas, without autograd (csrc/gtvconv.hip):
+    g = upstream act'(out) mask, s_e = delta <g_i, h_col - h_i>, t_e = -s_e gamma_e / d_e where d_e >= eps, and
+    dh_i = g_i (1 - delta sum_out gamma_e) + sum_out t_e sign(h_i - h_col) + sum_in (delta gamma_e g_row - t_e sign(h_row -
+    h_i)).  Two wrong stand-ins: ``drop_in_edge`` = k leaves the k-th in-edge (from 1) of every node out of the last sum;
+    ``slope_from_next_row`` takes act' from row i + 1."""
+    case = f"gtv-op-{d['seed']}" if case is None else case
+    ei, (n, C) = d["edge_index"], d["h"].shape
+    h = d["h"].to(dtype)
+    w = (torch.ones(ei.size(1)) if d["edge_weight"] is None else d["edge_weight"]).to(dtype)
+    bias = None if d["bias"] is None else d["bias"].to(dtype)
+    out = RG.propagate(h, ei, w, bias, d["mask"], d["delta"], d["eps"], RG.ACTS[d["act"]])
+    slope = {"identity": torch.ones_like(out), "relu": (out > 0).to(dtype),
+             "elu": torch.where(out > 0, torch.ones_like(out), out + 1)}[d["act"]]
+    if slope_from_next_row:
+        slope = slope.roll(-1, 0)
+    g = upstream(case + "g", n, C).to(dtype) * slope
+    if d["mask"] is not None:
+        g = g * d["mask"].view(-1, 1).to(dtype)
+    keep = gtv_skipped(d).logical_not()
+    row, col, wk = ei[0, keep], ei[1, keep], w[keep]
+    diff = h[col] - h[row]
+    dist = diff.abs().sum(-1)
+    gamma = wk / dist.clamp(min=d["eps"])
+    s = d["delta"] * (g[row] * diff).sum(-1)
+    t = torch.where(dist >= d["eps"], -s * gamma / dist.clamp(min=1e-300), torch.zeros_like(s))
+    sign = torch.sign(-diff)  # sign(h_row - h_col)
+    inward = d["delta"] * gamma.view(-1, 1) * g[row] - t.view(-1, 1) * sign
+    if drop_in_edge is not None:
+        inward = inward * (gtv_in_edge_rank(d)[keep] != drop_in_edge - 1).view(-1, 1).to(dtype)
+    dh = g * (1 - d["delta"] * torch.zeros(n, dtype=dtype).index_add(0, row, gamma)).view(-1, 1) \
+        + torch.zeros_like(h).index_add(0, row, t.view(-1, 1) * sign) + torch.zeros_like(h).index_add(0, col, inward)
+    return {"g": g, "dh": dh, "t": torch.zeros(ei.size(1), dtype=dtype).index_put((keep.nonzero().view(-1),), t)}
+
+
+# -------------------------------------------------------------------------------------------------------------- PAN
+_PAN_POWERS = {}
+
+
+def pan_powers(d, dtype):
+    """Per graph of the draw (first node, the dense powers [A_t^0 .. A_t^L], the stored pattern, D^-1/2 of the counted
+    degrees) in ``dtype``: constants of the list, kept for the last few draws (the oracle is called once per path)."""
+    key = (d["seed"], d["n"], d["edge_index"].size(1), int(d["edge_index"].sum()), dtype)
+    if key not in _PAN_POWERS:
+        if len(_PAN_POWERS) >= 6:
+            _PAN_POWERS.clear()
+        ei, L, out = d["edge_index"], d["filter_size"], []
+        owner = d["batch"][ei[0]]
+        for b, size in enumerate(d["all_sizes"]):
+            lo = int(d["ptr"][b])
+            local = ei[:, owner == b] - lo
+            a = RP.transposed_adjacency(local, size, dtype)
+            powers = [torch.eye(size, dtype=dtype)]
+            for _ in range(L):
+                powers.append(powers[-1] @ a)
+            _, pattern, _, deg = RP.met_dense_one(local, torch.ones(L + 1, dtype=dtype), size)
+            dinv = deg.pow(-0.5)
+            out.append((lo, powers, pattern, torch.where(torch.isinf(dinv), torch.zeros_like(dinv), dinv)))
+        _PAN_POWERS[key] = out
+    return _PAN_POWERS[key]
+
+
+def pan_met_from_coefficients(d, dtype, c):
+    """(index [2, nnz] row-major, values [nnz]) of M = D^-1/2 (sum_n c_n A_t^n) D^-1/2 on the structural pattern, with the
+    series coefficients ``c`` [L + 1] (c_n = w_0 ... w_n) as the differentiable input."""
+    idx, val = [], []
+    for lo, powers, pattern, dinv in pan_powers(d, dtype):
+        s = sum(c[k] * p for k, p in enumerate(powers))
+        m = (dinv.view(1, -1) * s) * dinv.view(-1, 1)
+        at = pattern.nonzero().t()
+        idx.append(at + lo)
+        val.append(m[at[0], at[1]])
+    return torch.cat(idx, 1), torch.cat(val)
+
+
+def pan_part_reference(d, dtype, g_values, row_limit=None):
+    """part [n, L + 1]: part[i, k] = dinv_i sum_j g_ij dinv_j (A_t^k)_ij over the stored entries of row i -- the share of
+    row i in dL/dc_k.  ``row_limit``: a wrong stand-in that stops after that many stored entries of a row."""
+    rows, at = [], 0
+    for lo, powers, pattern, dinv in pan_powers(d, dtype):
+        pos = pattern.nonzero().t()
+        gm = torch.zeros(pattern.shape, dtype=dtype).index_put((pos[0], pos[1]), g_values[at:at + pos.size(1)].to(dtype))
+        if row_limit is not None:
+            gm = gm * (pattern.cumsum(1) <= row_limit).to(dtype)
+        at += pos.size(1)
+        rows.append(torch.stack([dinv * ((gm * dinv.view(1, -1)) * p).sum(1) for p in powers], 1))
+    return torch.cat(rows)
+
+
+def pan_operator_reference(d, dtype, case=None, row_limit=None):
+    """"values" of the MET matrix (from the coefficient form, which equals ``pan_restatement.met`` in float64 to 1e-12:
+    asserted), "part" of ``pan_met_bwd`` on upstream(case + "g") and "dc", autograd's gradient at the coefficients
+    (part's column sums); the scorer's "score", "dot" and "colsum" on its own drawn inputs.  Leaf "c"."""
+    case = f"pan-op-{d['seed']}" if case is None else case
+    w = d["weight"].to(dtype)
+    c = _leaf(torch.cumprod(w, 0), dtype)
+    with torch.enable_grad():
+        index, values = pan_met_from_coefficients(d, dtype, c)
+        g = upstream(case + "g", values.numel()).to(dtype)
+        (dc,) = torch.autograd.grad(values, [c], g, retain_graph=True)
+    if dtype == torch.float64:
+        idx, val = RP.met(d["edge_index"], w, d["n"], d["batch"])
+        assert torch.equal(idx, index) and float((val - values.detach()).abs().max()) <= 1e-12
+    x, p, beta = d["score_x"].to(dtype), d["score_p"].to(dtype), d["beta"].to(dtype)
+    dot = x @ p
+    colsum = torch.zeros(d["n"], dtype=dtype).index_add(0, d["score_index"][1], d["score_values"].to(dtype))
+    t = beta[0] * dot + beta[1] * colsum
+    return {"values": values, "part": pan_part_reference(d, dtype, g, row_limit), "dc": dc,
+            "score": torch.tanh(t) if d["use_tanh"] else t, "dot": dot, "colsum": colsum}, {"c": c}
+
+
+PAN_EPS = 1e-8  # reference tgp/__init__.py: the sparse Connect drops pooled entries with |value| <= eps
+
+
+def pan_exact(d):
+    """The integer outputs: M's "index" and "row_ptr", the "kept" nodes (ascending; the float64 selection, whose cut the
+    draw keeps clear of rounding) and the pooled matrix's "pooled_index".  ``pan_restatement.pool`` keeps every entry of
+    the induced submatrix; the reference's sparse Connect then drops those with |value| <= eps (a zero series weight
+    leaves exact zeros on the entries only longer walks reach): "pooled_stored" marks the survivors among
+    "pooled_all", the float64 values of the whole submatrix."""
+    with torch.no_grad():
+        index, values = pan_met_from_coefficients(d, torch.float64, torch.cumprod(d["weight"].double(), 0))
+        x = d["x"].double()
+        h = torch.zeros_like(x).index_add(0, index[0], values.view(-1, 1) * x[index[1]]) @ d["lin_w"].double().t() \
+            + d["lin_b"].double()
+        _, _, perm, _, _, _, _ = RP.pool(h, index, values, d["batch"], d["p"].double(), d["beta"].double())
+        kept = perm.sort().values
+        pooled = RP.pool(h, index, values, d["batch"], d["p"].double(), d["beta"].double(), perm=kept)
+    row_ptr = torch.zeros(d["n"] + 1, dtype=torch.long)
+    row_ptr[1:] = torch.bincount(index[0], minlength=d["n"]).cumsum(0)
+    stored = pooled[6].abs() > PAN_EPS
+    return {"index": index, "row_ptr": row_ptr, "kept": kept, "pooled_index": pooled[5][:, stored],
+            "pooled_stored": stored, "pooled_all": pooled[6]}
+
+
+def pan_reference(d, dtype, ex=None):
+    """PANConv -> PANPooling: "conv_out", "met_values", and on the kept nodes in ascending order (``ex``: ``pan_exact``
+    of the draw, the float64 selection) their "weight", "x_pool" and the "pooled_values" of the induced submatrix's
+    stored entries.  Every parameter a leaf."""
+    ex = pan_exact(d) if ex is None else ex
+    kept = ex["kept"]
+    lv = {"x": _leaf(d["x"], dtype), "weight": _leaf(d["weight"], dtype), "lin.weight": _leaf(d["lin_w"], dtype),
+          "lin.bias": _leaf(d["lin_b"], dtype), "p": _leaf(d["p"], dtype), "beta": _leaf(d["beta"], dtype)}
+    index, values = pan_met_from_coefficients(d, dtype, torch.cumprod(lv["weight"], 0))
+    h = torch.zeros_like(lv["x"]).index_add(0, index[0], values.view(-1, 1) * lv["x"][index[1]]) @ lv["lin.weight"].t() \
+        + lv["lin.bias"]
+    _, _, _, weight, x_pool, _, pooled = RP.pool(h, index, values, d["batch"], lv["p"], lv["beta"], perm=kept)
+    return {"conv_out": h, "met_values": values, "weight": weight, "x_pool": x_pool,
+            "pooled_values": pooled[ex["pooled_stored"]]}, lv
+
+
+# ------------------------------------------------------------------------------------------------------- EigenPooling
+def eigenpool_groups(d):
+    """[(group id, its nodes ascending)] of the non-empty (graph, cluster) groups of the modes draw."""
+    return [(g, (d["gid"] == g).nonzero().view(-1)) for g in d["gid"].unique().tolist()]
+
+
+def eigenpool_group_modes(d, dtype):
+    """{group id: (modes [m, H], ascending eigenvalues or None)}: ``eigenpool_restatement.cluster_modes`` on the group's
+    induced adjacency (``dense_adjacency`` of the whole list) in ``dtype``."""
+    a = REG.dense_adjacency(d["edge_index"], d["edge_weight"], 0, d["n"], dtype)
+    return {g: REG.cluster_modes(a[nodes][:, nodes], d["H"], d["normalized"]) for g, nodes in eigenpool_groups(d)}
+
+
+EIG_GAP = 1e-3  # (fuzz_inputs.EIG_GAP: tests/test_fuzz_inputs.py asserts the two agree)
+
+
+def eigenpool_compared_groups(d):
+    """The groups whose entries are held by the rule -- one node, or, in float64, gaps of at least EIG_GAP among the
+    used eigenvalues and a sign-fixing entry of at least EIG_GAP in every column, and a float32 restatement within
+    CAP / FACTOR of it -- and the others, which keep the invariants of ``check_group_invariants`` alone."""
+    from fuzz_compare import CAP, FACTOR
+    m64, m32 = eigenpool_group_modes(d, torch.float64), eigenpool_group_modes(d, torch.float32)
+    good, rest = [], []
+    for g, nodes in eigenpool_groups(d):
+        (want, lam), m = m64[g], nodes.numel()
+        ok = m == 1
+        if m > 1:
+            used = min(d["H"] + 1, m)
+            e32 = float(torch.linalg.vector_norm(m32[g][0].double() - want) / torch.linalg.vector_norm(want))
+            ok = float((lam[1:used] - lam[:used - 1]).min()) >= EIG_GAP and float(want[0].abs().min()) >= EIG_GAP \
+                and e32 <= CAP / FACTOR
+        (good if ok else rest).append(g)
+    return good, rest
+
+
+def eigenpool_row_rank(gid):
+    """int64 [n]: a row's place among the rows of its group, nodes ascending (the Reduce's order)."""
+    order = torch.argsort(gid, stable=True)
+    first = torch.zeros(int(gid.max()) + 2, dtype=torch.long)
+    first[1:] = torch.bincount(gid).cumsum(0)
+    rank = torch.empty_like(gid)
+    rank[order] = torch.arange(gid.numel()) - first[gid[order]]
+    return rank
+
+
+def eigenpool_operator_reference(d, dtype, drop_row=None, late_wave=None, swap_modes=False):
+    """"modes[g]" of every compared group, and on the Reduce's own inputs "pool" [G, H F] = sum over a group's rows of
+    theta[i, h] x[i, f] and "lift" [n, F] = sum_h theta[i, h] y[gid_i, h F + f].  Wrong stand-ins: ``drop_row`` = k leaves
+    the k-th row (from 1) of every group out of the Reduce; ``late_wave`` = W starts the second of W waves one row late
+    (row ceil(len / W) of a group is lost); ``swap_modes`` exchanges the first two columns of every group's modes."""
+    modes = eigenpool_group_modes(d, dtype)
+    outs = {f"modes[{g}]": modes[g][0] for g in eigenpool_compared_groups(d)[0]}
+    if swap_modes:
+        outs = {k: (v[:, [1, 0] + list(range(2, v.size(1)))] if v.size(1) > 1 else v) for k, v in outs.items()}
+    gid, G, H = d["reduce_gid"], d["reduce_groups"], d["reduce_H"]
+    theta, x, y = d["theta"].to(dtype), d["reduce_x"].to(dtype), d["reduce_y"].to(dtype)
+    keep = torch.ones(gid.numel(), dtype=dtype)
+    rank, length = eigenpool_row_rank(gid), torch.bincount(gid, minlength=G)[gid]
+    if drop_row is not None:
+        keep = keep * (rank != drop_row - 1).to(dtype)
+    if late_wave is not None:
+        keep = keep * (rank != -(-length // late_wave)).to(dtype)
+    terms = (theta * keep.view(-1, 1)).unsqueeze(2) * x.unsqueeze(1)
+    outs["pool"] = torch.zeros(G, H, x.size(1), dtype=dtype).index_add_(0, gid, terms).view(G, -1)
+    outs["lift"] = (theta.unsqueeze(2) * y.view(G, H, -1)[gid]).sum(1)
+    return outs, {}
+
+
+def eigenpool_reference(d, dtype):
+    """EigenPooling through ``labels=``: ``eigenpool_restatement.collapsed`` -- "x_pool" [groups, H F] and "lift" on the
+    compared groups and their nodes (the modes of the others are free up to a sign or a rotation), "adj" [B, K, K] with
+    the pooler's default post-processing.  Leaf x."""
+    x = _leaf(d["x"], dtype)
+    res = REG.collapsed(x, d["edge_index"], d["edge_weight"], d["batch"], d["labels"], d["width"], d["H"], d["normalized"],
+                        dtype=dtype)
+    good = torch.tensor(eigenpool_compared_groups(d)[0])
+    rows = torch.isin(d["gid"], good)
+    return {"x_pool": res["x_pool"].reshape(-1, res["x_pool"].size(-1))[good], "lift": res["lift"][rows],
+            "adj": res["adj"]}, {"x": x}
+
+
+def eigenpool_exact(d):
+    """theta_ptr and theta_perm of the compact pooling matrix, and S as one-hot labels."""
+    res = REG.collapsed(d["x"], d["edge_index"], d["edge_weight"], d["batch"], d["labels"], d["width"], 1, d["normalized"])
+    return {"theta_ptr": res["theta_ptr"], "theta_perm": res["theta_perm"],
+            "s": torch.nn.functional.one_hot(d["labels"], d["width"]).float()}

@@ -1835,7 +1835,9 @@ class _PanMetValuesFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (weight,) = ctx.saved_tensors
-        gc = K.pan_met_bwd(ctx.met, g).sum(dim=0)
+        # (the rows' shares carry the signs of g: their N-term column sums cancel, so they are added in float64 and
+        # rounded once -- a float32 sum loses up to sum|share| / |sum| times its rounding on L + 1 numbers that cost nothing)
+        gc = K.pan_met_bwd(ctx.met, g).sum(dim=0, dtype=torch.float64)
         with torch.enable_grad():
             w = weight.detach().requires_grad_(True)
             (gw,) = torch.autograd.grad(torch.cumprod(w, dim=0), w, gc.to(w.dtype))
