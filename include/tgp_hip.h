@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32; PAN: tgp_pan_max_graph_nodes, tgp_pan_met_workspace_bytes, tgp_pan_met_count, tgp_pan_met_fill_f32, tgp_pan_met_bwd_f32, tgp_pan_score_f32; GTVConv: tgp_gtv_edge_fwd_f32, tgp_gtv_edge_bwd_terms_f32, tgp_gtv_edge_bwd_nodes_f32) */
+#define TGP_ABI_VERSION 10044 /* 1.0.1 of the reference, ABI revision 43 (k-MIS selection: tgp_kmis_graphs, tgp_kmis_rounds_start, tgp_kmis_rounds, tgp_kmis_clusters, tgp_kmis_greedy_f32, tgp_kmis_wsum_f32, tgp_kmis_degree_f32, tgp_kmis_mis_index_i64; appended without a new revision, AsymCheegerCut's losses: tgp_acc_small_graph_nodes, tgp_acc_tv_dense_f32 / _bwd_f32, tgp_acc_tv_edge_f32 / _bwd_f32, tgp_acc_quantile_f32, tgp_acc_loss_terms_f32, tgp_acc_asym_bwd_f32; HOSC's losses: tgp_hosc_small_graph_nodes, tgp_hosc_record_floats, tgp_hosc_matvec_f32, tgp_hosc_node_terms_f32, tgp_hosc_small_f32, tgp_hosc_loss_terms_f32 / _bwd_f32, tgp_hosc_ds_f32; BN-Pool's reconstruction loss: tgp_bnpool_max_clusters, tgp_bnpool_part_floats, tgp_bnpool_rec_fwd_f32 / _bwd_f32; edge-contraction selection: tgp_edge_contract_max_graph_nodes, tgp_edge_contract_edge_cache, tgp_edge_contract_hub_degree, tgp_edge_contract_workspace_bytes, tgp_edge_contract_project_f32, tgp_edge_contract_raw_f32, tgp_edge_contract_normalize_f32, tgp_edge_contract_graphs, tgp_edge_contract_rounds_start, tgp_edge_contract_rounds, tgp_edge_contract_weights_f32; the segment readout: tgp_segment_aggr_chunk_rows, tgp_segment_aggr_workspace_bytes, tgp_segment_aggr_f32 / _bwd_f32; EigenPooling: tgp_eigenpool_max_group_nodes, tgp_eigenpool_modes_f32, tgp_eigenpool_reduce_f32, tgp_eigenpool_lift_f32; PAN: tgp_pan_max_graph_nodes, tgp_pan_met_workspace_bytes, tgp_pan_met_count, tgp_pan_met_fill_f32, tgp_pan_met_bwd_f32, tgp_pan_score_f32; GTVConv: tgp_gtv_edge_fwd_f32, tgp_gtv_edge_bwd_terms_f32, tgp_gtv_edge_bwd_nodes_f32; the dense poolers' adjacency gradient: tgp_dense_pool_adj_grad_f32, tgp_dense_pool_adj_grad_small_f32) */
 
 enum tgp_status {
   TGP_OK = 0,
@@ -1850,6 +1850,39 @@ int tgp_sep_select_f32(const int32_t* src_ptr, const int32_t* src_perm /* NULL o
                        const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* graph_ptr, int64_t N,
                        int64_t E, int64_t G, int64_t max_n, int64_t* cluster_index, int32_t* counts, int32_t* offsets,
                        int32_t* words, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The dense poolers' gradient with respect to a dense adjacency that was handed in (DiffPool, MinCut; padded batch,
+ * float32; what the reference gets from ATen autograd over connect/dense_conn.py:111-122, utils/losses.py:39-56 and
+ * :644-652).  Per graph b, with R = S^T A S and M = the total gradient of R (post-processing backward + upstream + the
+ * loss' diagonal term: -(g_cut / (den + eps)) I for MinCut, -c I for DiffPool):
+ *     dA_b = S_b M_b S_b^T + gamma_b q_b 1^T + c A_b,      q_i = |s_i|^2,
+ *     gamma_b = g_cut trace(R_b) / (den_b + eps)^2   (MinCut: the gradient of den_b = sum_i (A 1)_i q_i),
+ *     c = link_scale^2 *g_link / *link_loss          (DiffPool: ONE scalar for the batch; 0 when the loss is 0).
+ * dA [B,N,N] is written once, one writer per element, no atomics: the same bits on every call.  Every coefficient is a
+ * device value; nothing is read back.
+ *
+ * tgp_dense_pool_adj_grad_f32 (graphs beyond the one-wave kernels; any N, K): M [B][K][K] with row stride ldm and batch
+ *   stride sM (the RV block of tgp_dense_pool_train_rhs_f32's rcat), S with row stride lds and batch stride sS, gamma
+ *   [B] or NULL (the c1 of that call), q [B,N] or NULL (formed from S then), g_link / link_loss 0-dim or NULL (A is
+ *   read only then).  T [B,N,K] is scratch for S M (tgp_bmm_f32); the N^2 K product T S^T runs on the fp32 matrix cores
+ *   and its epilogue adds the other two terms while the tile is in registers.  Two launches.
+ * tgp_dense_pool_adj_grad_small_f32 (N <= 64, K <= 32: the batches tgp_dense_pool_is_small accepts), one wave per graph,
+ *   one launch behind tgp_dense_pool_small_bwd_f32: M = ga + g_raw - (g_b / (den_b + loss_eps) + c) I is formed here from
+ *   ga (tgp_postprocess_dense_bwd_f32's output) and g_raw (each [B,K,K] or NULL), g_b = g_terms[0,b] + *g_mean_cut / B
+ *   (each optional; raw [B,K,K] = the forward's S^T A S and A are needed with either), den_b from one pass over A.
+ * TGP_ERR_INVALID: a NULL required operand, sizes below zero, K < 1, a row stride below K, dA given as an operand, a
+ * coefficient without what it is formed from, (small) N > 64 or K > 32; TGP_ERR_RANGE: N, K or the grid beyond the int32
+ * internals.  All are found before any HIP call; B == 0 or N == 0 returns TGP_OK.
+ * ---------------------------------------------------------------------------------- */
+int tgp_dense_pool_adj_grad_f32(const float* S, int64_t lds, int64_t sS, const float* A, const float* M, int64_t ldm,
+                                int64_t sM, const float* gamma, const float* q, const float* g_link,
+                                const float* link_loss, float link_scale, int64_t B, int64_t N, int64_t K, float* T,
+                                float* dA, void* stream);
+int tgp_dense_pool_adj_grad_small_f32(const float* S, const float* A, const float* ga, const float* g_raw,
+                                      const float* raw, const float* g_terms, const float* g_mean_cut,
+                                      const float* g_link, const float* link_loss, float link_scale, float loss_eps,
+                                      int64_t B, int64_t N, int64_t K, float* dA, void* stream);
 
 #ifdef __cplusplus
 }

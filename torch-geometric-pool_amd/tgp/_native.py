@@ -217,6 +217,10 @@ SIGNATURES = {
     "tgp_dense_pool_train_rhs_f32": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f, _c_f,
                                               _c_p, _c_int, _c_int, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p,
                                               _c_p]),
+    "tgp_dense_pool_adj_grad_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_f,
+                                             _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "tgp_dense_pool_adj_grad_small_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f,
+                                                   _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
     "tgp_softmax_bwd_ex_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_f, _c_f, _c_p, _c_i64, _c_i64,
                                         _c_i64, _c_p, _c_p]),
     "tgp_segment_gemm_nn_ld_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,

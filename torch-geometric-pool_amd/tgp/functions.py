@@ -943,9 +943,10 @@ class _DensePoolSmallFn(torch.autograd.Function):
     def forward(ctx, s, adj, x, flags, want_raw, want_terms, diff_scales, graph_sizes, scalars=False):
         ctx.set_materialize_grads(False)
         sd, ad = s.detach(), adj.detach()
+        ctx.adj_grad = ctx.needs_input_grad[1]  # (its backward reads the raw S^T A S: the kernel writes it then)
         x_pool, raw, adj_pool, terms, diff, la, lb = _pool_small_forward(
-            sd, ad, x.detach(), flags, want_raw, want_terms, diff_scales, graph_sizes, scalars)
-        ctx.save_for_backward(s, adj, x, diff)
+            sd, ad, x.detach(), flags, want_raw or ctx.adj_grad, want_terms, diff_scales, graph_sizes, scalars)
+        ctx.save_for_backward(s, adj, x, diff, raw)
         ctx.flags = flags
         ctx.want_gx = x.requires_grad
         ctx.diff_scales = diff_scales
@@ -962,9 +963,10 @@ class _DensePoolSmallFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_x, g_raw, g_adj, g_terms, g_diff, g_la, g_lb):
         from . import kernels as K
-        s, adj, x, diff = ctx.saved_tensors
+        s, adj, x, diff, raw = ctx.saved_tensors
         gs, gx = _pool_small_backward(ctx, s, adj, x, diff, g_x, g_raw, g_adj, g_terms, g_diff, g_la, g_lb)
-        return gs.to(s.dtype), None, (gx.to(x.dtype) if gx is not None else None), None, None, None, None, None, None
+        ga = _pool_small_adj_grad(ctx, s, adj, raw, diff, g_raw, g_adj, g_terms, g_diff, g_la) if ctx.adj_grad else None
+        return gs.to(s.dtype), ga, (gx.to(x.dtype) if gx is not None else None), None, None, None, None, None, None
 
 
 def _pool_small_backward(ctx, s, adj, x, diff, g_x, g_raw, g_adj, g_terms, g_diff, g_la, g_lb):
@@ -988,10 +990,35 @@ def _pool_small_backward(ctx, s, adj, x, diff, g_x, g_raw, g_adj, g_terms, g_dif
                                   link_scale=ds[0], ent_scale=ds[1], g_mean_terms=mean_terms, g_diff_pair=diff_pair)
 
 
+def _pool_small_adj_grad(ctx, s, adj, raw, diff, g_raw, g_adj, g_terms, g_diff, g_la):
+    """dA of the two fused Functions above / below, a launch of its own behind their backward (csrc/dense_adj_grad.hip:
+    adj_grad_small_kernel; + the post-processing backward when the pooled adjacency has an upstream gradient), or None
+    when no upstream gradient reaches A.  ``adj``: the contiguous float32 adjacency the caller handed in."""
+    from . import kernels as K
+    if g_raw is not None and g_raw.numel() == 0:
+        g_raw = None
+    if g_terms is not None and g_terms.numel() == 0:
+        g_terms = None
+    ds = ctx.diff_scales
+    g_link = g_mean_cut = None
+    if ds is not None:
+        g_link = g_diff[0] if (g_diff is not None and g_diff.numel()) else g_la
+    else:
+        g_mean_cut = g_la
+    if g_adj is None and g_raw is None and g_terms is None and g_mean_cut is None and g_link is None:
+        return None  # (pooled features, orthogonality, entropy: A is not in them)
+    ga = None
+    if g_adj is not None:
+        ga = K.postprocess_dense_bwd(raw, g_adj, ctx.flags)
+    return K.dense_pool_adj_grad_small(s.detach(), adj.detach(), ga, g_raw, raw, g_terms, g_mean_cut, g_link,
+                                       diff[0:1] if g_link is not None else None, ds[0] if ds is not None else 0.0)
+
+
 def dense_pool_small(s: Tensor, adj: Tensor, x: Tensor, flags: int, want_raw: bool, want_terms: bool,
                      diff_scales=None, graph_sizes: Optional[Tensor] = None, loss_scalars: bool = False):
-    """Differentiable fused Reduce + Connect for batches ``kernels.dense_pool_is_small`` accepts (adj gets no gradient:
-    callers check ``adj.requires_grad`` first): (x_pool, raw, adj_pool, terms, diff).  ``diff_scales = (link_scale,
+    """Differentiable fused Reduce + Connect for batches ``kernels.dense_pool_is_small`` accepts (a contiguous float32
+    adj that requires a gradient gets it from a launch of its own, ``_pool_small_adj_grad``; callers check
+    ``edge_weight_norm`` first): (x_pool, raw, adj_pool, terms, diff).  ``diff_scales = (link_scale,
     ent_scale)``: also DiffPool's link and entropy losses [2], differentiated by the same backward launch.
     ``loss_scalars``: the auxiliary losses come as a :class:`LossPair` of 0-dim tensors instead -- in place of ``terms``
     the batch means of MinCut's two terms, in place of ``diff`` its two entries."""
@@ -1018,15 +1045,17 @@ class _SelectPoolSmallFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         xd, ad = x.detach(), adj.detach()
         dstats = diff_scales is not None and not want_terms  # DiffPool (r6): per-graph records instead of MinCut's terms
+        ctx.adj_grad = ctx.needs_input_grad[1]  # (its backward reads the raw S^T A S: the kernel writes it then)
+        k_raw = want_raw or ctx.adj_grad
         s, x_pool, raw, adj_pool, terms, bp = K.dense_pool_select(
-            xd, ad, weight.detach(), None if bias is None else bias.detach(), mask, flags, want_raw=want_raw,
+            xd, ad, weight.detach(), None if bias is None else bias.detach(), mask, flags, want_raw=k_raw,
             mincut_terms=not dstats, want_batch=True, diff_stats=dstats) if want_batch else K.dense_pool_select(
-            xd, ad, weight.detach(), None if bias is None else bias.detach(), mask, flags, want_raw=want_raw,
+            xd, ad, weight.detach(), None if bias is None else bias.detach(), mask, flags, want_raw=k_raw,
             mincut_terms=not dstats, diff_stats=dstats) + (torch.empty(0, dtype=torch.long, device=x.device),)
         pre = (x_pool, raw, adj_pool, s.new_empty(0), terms) if dstats else (x_pool, raw, adj_pool, terms)
         x_pool, raw, adj_pool, terms, diff, la, lb = _pool_small_forward(
             s, ad, xd, flags, want_raw, want_terms, diff_scales, graph_sizes, True, pre=pre)
-        ctx.save_for_backward(s, adj, x, diff, weight)
+        ctx.save_for_backward(s, adj, x, diff, weight, raw)
         ctx.flags = flags
         ctx.want_gx = x.requires_grad  # (node features that are data, not activations: neither backward forms dX)
         ctx.diff_scales = diff_scales
@@ -1040,14 +1069,15 @@ class _SelectPoolSmallFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_s, g_x, g_raw, g_adj, _g_terms, _g_diff, g_la, g_lb, _g_bp):
         from . import kernels as K
-        s, adj, x, diff, weight = ctx.saved_tensors
+        s, adj, x, diff, weight, raw = ctx.saved_tensors
         gs, gx = _pool_small_backward(ctx, s, adj, x, diff, g_x, g_raw, g_adj, None, None, g_la, g_lb)
+        ga = _pool_small_adj_grad(ctx, s, adj, raw, diff, g_raw, g_adj, None, None, g_la) if ctx.adj_grad else None
         if g_s is not None:  # S was used outside the pooler as well
             gs = gs + g_s
         need = ctx.needs_input_grad
         gx, gw, gb = K.mlp_select_bwd(s, gs, x, weight, want_gx=need[0], want_gw=need[2],
                                       want_gb=ctx.has_bias and need[3], gx_accumulate=gx if need[0] else None)
-        return ((gx.to(x.dtype) if need[0] else None), None, gw, (gb if ctx.has_bias else None), None, None, None, None,
+        return ((gx.to(x.dtype) if need[0] else None), ga, gw, (gb if ctx.has_bias else None), None, None, None, None,
                 None, None, None)
 
 
@@ -1147,7 +1177,13 @@ class _PoolLargeFn(torch.autograd.Function):
         selector form: dY = softmax backward of gS + 2 c1 D S (MinCut) - g_ent (log S + ...) (DiffPool) in one launch,
              written over the V block; gX = [S | dY] [g_x' ; W] (one product over acat's last two blocks),
              [gW | gb] = dY^T [X | 1] (one product over acat's X block and the column of ones behind it).
-    The adjacency gets no gradient (callers check); edge_weight_norm is not differentiated here (callers check)."""
+        dA (only when the adjacency handed in requires a gradient: ``ctx.needs_input_grad``; the general backward is
+             taken then, RV = gR is written): dA = S gR S^T + c1 q 1^T (MinCut: q = |s_i|^2 from the forward's cut_rows)
+             + c A (DiffPool) -- T = S gR, then the N^2 K product with both other terms in its epilogue, [B,N,N] written
+             once (tgp_dense_pool_adj_grad_f32; nothing is allocated or launched when A is data, or when no upstream
+             gradient reaches A).
+    The adjacency must then be float32 and contiguous (callers check); edge_weight_norm is not differentiated here
+    (callers check)."""
 
     @staticmethod
     def forward(ctx, x, adj, weight, bias, mask, s_given, flags, mode, scales, graph_sizes, sym):
@@ -1167,9 +1203,13 @@ class _PoolLargeFn(torch.autograd.Function):
         x_pool, raw, adj_pool, gram = K.dense_pool_train_fwd(s, mem, xd, flags | tflag, acat, want_gram=mode != 0)
         empty = s.new_empty(0)
         la, lb = s.new_empty(0), s.new_empty(0)  # (distinct objects: both are outputs of this node)
-        deg = den = lossv = stats = None
+        deg = den = lossv = stats = qrow = None
+        ctx.adj_grad = ctx.needs_input_grad[1]
+        if ctx.adj_grad and tflag:
+            raise RuntimeError("dense pooling: the adjacency gradient needs a contiguous adjacency")
         if mode == 1:
             deg, q = K.cut_rows(ad, s, graph_sizes)
+            qrow = q if ctx.adj_grad else None  # (|s_i|^2: the row factor of dA's denominator term)
             den, terms, stats, both = K.mincut_terms_fused(raw, gram, deg, q, want_means=True)
             la, lb = both[0], both[1]
         elif mode == 2:
@@ -1180,7 +1220,7 @@ class _PoolLargeFn(torch.autograd.Function):
             flat = mem.reshape(-1)
             lossv = K.diffpool_unbatched_tail(raw, gram, s, torch.dot(flat, flat), scales[0], scales[1])
             la, lb = lossv[0], lossv[1]
-        keep = [t if t is not None else empty for t in (gram, deg, den, lossv, stats)]
+        keep = [t if t is not None else empty for t in (gram, deg, den, lossv, stats, qrow)]
         ctx.save_for_backward(s, mem, xd, empty if weight is None else weight, acat, raw, *keep)
         ctx.flags, ctx.tflag, ctx.mode, ctx.scales, ctx.selector = flags, tflag, mode, scales, selector
         ctx.has_bias = bias is not None
@@ -1196,7 +1236,7 @@ class _PoolLargeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_s, g_xp, g_raw, g_adj, g_la, g_lb):
         from . import _native as N
-        s, mem, xd, weight, acat, raw, gram, deg, den, lossv, stats = ctx.saved_tensors
+        s, mem, xd, weight, acat, raw, gram, deg, den, lossv, stats, qrow = ctx.saved_tensors
         B, Nn, Kc = s.shape
         F = xd.size(2)
         mode, selector = ctx.mode, ctx.selector
@@ -1215,7 +1255,8 @@ class _PoolLargeFn(torch.autograd.Function):
         gb = None if g_raw is None else N.f32c(g_raw)
         gx_t, gx_bc = K._bcast_or_dense(g_xp, (B, Kc, F))
         link_loss = lossv[0:1] if mode == 2 else None
-        symmetric = ctx.sym is not None and ctx.sym.get()  # A = A^T: V = U, the second N^2 K product is not needed
+        # A = A^T: V = U, the second N^2 K product is not needed (not asked when A wants a gradient: dA reads RV = gR)
+        symmetric = not ctx.adj_grad and ctx.sym is not None and ctx.sym.get()
         POOL_LARGE_STATS["symmetric" if symmetric else "general"] += 1
         fold_gx = selector and want_gx  # gX = [S | dY] [g_x ; W] as one product over acat's last two blocks
         rcat, c1, gwcat = K.dense_pool_train_rhs(
@@ -1225,6 +1266,11 @@ class _PoolLargeFn(torch.autograd.Function):
         pad = K.TRAIN_PAD
         ld = 3 * Kc + F + pad
         c_x, c_one, c_s, c_v = Kc, Kc + F, Kc + F + pad, 2 * Kc + F + pad
+        g_adj_in = None
+        if ctx.adj_grad and (ga is not None or gb is not None or g_la is not None):  # (else: no path reaches A)
+            g_adj_in = K.dense_pool_adj_grad(s, mem, rcat[:, c_v:, :], gamma=c1 if mode == 1 else None,
+                                             q=qrow if mode == 1 else None, g_link=g_la if mode == 2 else None,
+                                             link_loss=link_loss, link_scale=ctx.scales[0] if mode == 2 else 0.0)
         vblock = acat[:, :, c_v:]
         if not symmetric:  # V = A^T S into its column block (mem holds A, or A^T when tflag)
             K.bmm_into(mem, s, vblock, trans_a=not ctx.tflag)
@@ -1241,7 +1287,7 @@ class _PoolLargeFn(torch.autograd.Function):
                 gs.addcmul_((2.0 * c1).view(-1, 1, 1) * deg.unsqueeze(-1), s)
             if ent_g is not None:
                 gs += K.entropy_bwd(s, ent_g, ctx.scales[1])
-            return (gxd, None, None, None, None, gs, None, None, None, None, None)
+            return (gxd, g_adj_in, None, None, None, gs, None, None, None, None, None)
         # the selector's backward: dY over the V block (no longer needed), then two products
         K.softmax_bwd_ex(s, gs, extra=g_s, c1=c1 if mode == 1 else None, deg=deg if mode == 1 else None,
                          ent_g=ent_g, ent_scale=ctx.scales[1] if mode == 2 else 0.0, out=vblock)
@@ -1262,7 +1308,7 @@ class _PoolLargeFn(torch.autograd.Function):
             flat = acat.view(slabs, rows // slabs, ld)
             K.bmm_into(flat[:, :, c_v:], flat[:, :, c_x:c_x + F + pad], part, trans_a=True)
             gw, gbias = K.slab_sum_split(part, F, want_gw, want_gb)  # two contiguous tensors, slabs added in order
-        return (gxd, None, gw, gbias, None, None, None, None, None, None, None)
+        return (gxd, g_adj_in, gw, gbias, None, None, None, None, None, None, None)
 
 
 def _slab_ptr(rows: int, device) -> Tensor:

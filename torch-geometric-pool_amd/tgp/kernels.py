@@ -1696,6 +1696,95 @@ def bmm_into(a: Tensor, b: Tensor, out: Tensor, trans_a: bool = False, accumulat
     return out
 
 
+def _adj_grad_operands(who: str, s: Tensor, adj: Optional[Tensor], **square):
+    """Shared checks of the two adjacency-gradient wrappers: s [B,N,K] float32 with unit last stride, adj [B,N,N]
+    contiguous float32 or None, every ``square`` operand [B,K,K] or None."""
+    if s.dim() != 3 or s.dtype != torch.float32 or s.stride(2) != 1 or s.size(2) < 1:
+        raise ValueError(f"{who}: s must be a float32 [B,N,K] tensor (K >= 1) with unit last stride, got "
+                         f"{tuple(s.shape)} {s.dtype}")
+    B, Nn, Kc = s.shape
+    if adj is not None and (adj.shape != (B, Nn, Nn) or adj.dtype != torch.float32 or not adj.is_contiguous()):
+        raise ValueError(f"{who}: adj must be a contiguous float32 {(B, Nn, Nn)} tensor, got {tuple(adj.shape)} {adj.dtype}")
+    for name, t in square.items():
+        if t is not None and (t.shape != (B, Kc, Kc) or t.dtype != torch.float32):
+            raise ValueError(f"{who}: {name} must be a float32 {(B, Kc, Kc)} tensor, got {tuple(t.shape)} {t.dtype}")
+    return B, Nn, Kc
+
+
+def _dev_scalar(who: str, name: str, t: Optional[Tensor]) -> Optional[Tensor]:
+    """A 0-dim / one-element float32 device value of a native call (never read on the host), or None."""
+    if t is None:
+        return None
+    if t.numel() != 1:
+        raise ValueError(f"{who}: {name} must hold one value, got {tuple(t.shape)}")
+    return N.f32c(t.reshape(1))
+
+
+def dense_pool_adj_grad(s: Tensor, adj: Optional[Tensor], m: Tensor, gamma: Optional[Tensor] = None,
+                        q: Optional[Tensor] = None, g_link: Optional[Tensor] = None,
+                        link_loss: Optional[Tensor] = None, link_scale: float = 0.0) -> Tensor:
+    """dA [B,N,N] = S M S^T + gamma_b q_i + c A of the dense poolers' training step (connect/dense_conn.py:111-122,
+    utils/losses.py:39-56, 644-652 under autograd), any N and K: ``m`` [B,K,K] = the total gradient of S^T A S (a view
+    with unit last stride: the RV block of :func:`dense_pool_train_rhs`), ``gamma`` [B] = its ``c1`` (MinCut) with
+    ``q`` [B,N] = |s_i|^2 (:func:`cut_rows`; None: formed in the kernel), ``g_link`` / ``link_loss`` = DiffPool's upstream
+    gradient and forward value (0-dim device tensors: c = link_scale^2 g_link / link_loss, ``adj`` is read only then).
+    T = S M (:func:`bmm_into`'s kernel) + one N^2 K launch on the fp32 matrix cores that writes dA once."""
+    who = "dense_pool_adj_grad"
+    dev = N.require_device(s, adj, m, gamma, q, g_link, link_loss)
+    B, Nn, Kc = _adj_grad_operands(who, s, adj)
+    if m.dim() != 3 or m.shape != (B, Kc, Kc) or m.dtype != torch.float32 or m.stride(2) != 1:
+        raise ValueError(f"{who}: m must be a float32 {(B, Kc, Kc)} view with unit last stride, got {tuple(m.shape)} {m.dtype}")
+    if gamma is not None:
+        gamma = N.f32c(gamma)
+        if gamma.shape != (B,):
+            raise ValueError(f"{who}: gamma must be [{B}], got {tuple(gamma.shape)}")
+    if q is not None:
+        q = N.f32c(q)
+        if q.shape != (B, Nn):
+            raise ValueError(f"{who}: q must be {(B, Nn)}, got {tuple(q.shape)}")
+    g_link, link_loss = _dev_scalar(who, "g_link", g_link), _dev_scalar(who, "link_loss", link_loss)
+    if g_link is not None and (link_loss is None or adj is None):
+        raise ValueError(f"{who}: g_link needs link_loss and adj")
+    out = torch.empty(B, Nn, Nn, dtype=torch.float32, device=dev)
+    t = torch.empty(B, Nn, Kc, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_dense_pool_adj_grad_f32, s.data_ptr(), s.stride(1), s.stride(0), N.ptr(adj), m.data_ptr(),
+             m.stride(1), m.stride(0), N.ptr(gamma), N.ptr(q), N.ptr(g_link), N.ptr(link_loss), float(link_scale), B, Nn,
+             Kc, N.ptr(t), N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
+def dense_pool_adj_grad_small(s: Tensor, adj: Tensor, ga: Optional[Tensor] = None, g_raw: Optional[Tensor] = None,
+                              raw: Optional[Tensor] = None, g_terms: Optional[Tensor] = None,
+                              g_mean_cut: Optional[Tensor] = None, g_link: Optional[Tensor] = None,
+                              link_loss: Optional[Tensor] = None, link_scale: float = 0.0) -> Tensor:
+    """:func:`dense_pool_adj_grad` for batches of small graphs (N <= 64, K <= 32: what ``dense_pool_is_small`` accepts),
+    one wave per graph, one launch behind :func:`dense_pool_small_bwd`.  M is formed in the kernel: ``ga`` (the output of
+    :func:`postprocess_dense_bwd`) + ``g_raw`` (each [B,K,K] or None) - (g_b / (den_b + eps) + c) I with g_b =
+    ``g_terms``[0,b] + ``g_mean_cut`` / B (each optional; they need ``raw`` = the forward's S^T A S)."""
+    who = "dense_pool_adj_grad_small"
+    dev = N.require_device(s, adj, ga, g_raw, raw, g_terms, g_mean_cut, g_link, link_loss)
+    s = N.f32c(s)
+    B, Nn, Kc = _adj_grad_operands(who, s, adj, ga=ga, g_raw=g_raw, raw=raw)
+    if Nn > 64 or Kc > 32:
+        raise ValueError(f"{who}: one wave per graph takes N <= 64 and K <= 32, got N = {Nn}, K = {Kc}")
+    ga, g_raw, raw = N.opt_f32(ga), N.opt_f32(g_raw), N.opt_f32(raw)
+    if g_terms is not None:
+        g_terms = N.f32c(g_terms)
+        if g_terms.shape != (2, B):
+            raise ValueError(f"{who}: g_terms must be {(2, B)}, got {tuple(g_terms.shape)}")
+    g_mean_cut = _dev_scalar(who, "g_mean_cut", g_mean_cut)
+    g_link, link_loss = _dev_scalar(who, "g_link", g_link), _dev_scalar(who, "link_loss", link_loss)
+    if (g_terms is not None or g_mean_cut is not None) and raw is None:
+        raise ValueError(f"{who}: the cut term needs raw")
+    if g_link is not None and link_loss is None:
+        raise ValueError(f"{who}: g_link needs link_loss")
+    out = torch.empty(B, Nn, Nn, dtype=torch.float32, device=dev)
+    _checked(N.lib().tgp_dense_pool_adj_grad_small_f32, N.ptr(s), N.ptr(adj), N.ptr(ga), N.ptr(g_raw), N.ptr(raw),
+             N.ptr(g_terms), N.ptr(g_mean_cut), N.ptr(g_link), N.ptr(link_loss), float(link_scale), losses_eps(), B, Nn,
+             Kc, N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
 def mincut_loss_terms(raw: Tensor, den: Tensor, gram: Tensor) -> Tensor:
     """[2,B]: per-graph -trace(raw)/(den + eps) and ||G/||G|| - I/sqrt(K)||_F (utils/losses.py:39-70), one launch."""
     dev = N.require_device(raw, den, gram)

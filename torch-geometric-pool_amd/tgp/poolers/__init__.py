@@ -94,6 +94,9 @@ def _rows_route_density(k: int) -> float:
 _FOLD_TRAINING = _os.environ.get("TGP_FOLD_TRAINING", "1") != "0"
 # ... 0 densifies sparse inputs (to_dense_batch + to_dense_adj) in front of the fused inference call as before
 _FOLD_SPARSE_INPUTS = _os.environ.get("TGP_FOLD_SPARSE_INPUTS", "1") != "0"
+# ... 0 sends a dense adjacency that requires a gradient (the second level of a stacked model) to the operator route as
+# before, instead of keeping it on the one-node training routes with the native dA (csrc/dense_adj_grad.hip)
+_ADJ_GRAD = _os.environ.get("TGP_ADJ_GRAD", "1") != "0"
 
 
 # =============================================================================== sparse poolers
@@ -539,6 +542,14 @@ class _DenseMLPPooling(DenseSRCPooling):
                 and (mask is None or mask.dtype == torch.bool) and adj.shape == (x.size(0), x.size(1), x.size(1)))
 
     @staticmethod
+    def _adj_grad_ok(adj, c, handed: bool) -> bool:
+        """May a one-node training route take this adjacency although it requires a gradient?  Only a dense adjacency
+        the caller HANDED to forward() (one densified from an edge list would need the gradient at its E entries: the
+        operator route), float32 and contiguous, without edge_weight_norm."""
+        return bool(_ADJ_GRAD and handed and isinstance(adj, Tensor) and adj.dtype == torch.float32
+                    and adj.is_contiguous() and not c.edge_weight_norm)
+
+    @staticmethod
     def _flat_f32(x, edge_index, edge_weight, batch) -> bool:
         """An un-padded float32 device batch x [N,F], N > 0, with an int64 edge list [2,E], float32 edge weights or
         none, an int64 batch vector [N] or none."""
@@ -650,15 +661,19 @@ class _DenseMLPPooling(DenseSRCPooling):
         so._graph_sizes = info.sizes
         return _Pooled(so, x_pool, raw if self._wants_raw else None, adj_pool, batch_pool=bp, loss=loss)
 
-    def _select_reduce_connect_train(self, x, adj, mask, graph_sizes, want_batch=False, known_nodes=None):
+    def _select_reduce_connect_train(self, x, adj, mask, graph_sizes, want_batch=False, known_nodes=None,
+                                     adj_handed=False):
         """Training on a batch of small graphs with a single-Linear selector: Select + Reduce + Connect + loss tails as
         ONE autograd node (functions._SelectPoolSmallFn: one forward launch, two backward launches; the selector and the
         pooling were two nodes with eight + one backward launches and an accumulation of the two gradients of X).
+        ``adj_handed``: forward() was given this dense adjacency; one that requires a gradient then stays here and gets
+        it from a launch behind the node's backward (:meth:`_adj_grad_ok`).
         Returns a ``_Pooled`` like :meth:`_select_reduce_connect`, the losses as a ``LossPair``."""
         sel, c = self.selector, self.connector
         last = self._single_linear(self._mlp_lins(sel))
         if (self._loss_only or last is None or not self._plain_wiring(c) or not self._padded_f32(x, adj, mask)
-                or not torch.is_grad_enabled() or adj.requires_grad or c.edge_weight_norm):
+                or not torch.is_grad_enabled() or c.edge_weight_norm
+                or (adj.requires_grad and not self._adj_grad_ok(adj, c, adj_handed))):
             return None
         weight, mincut = last.weight, self._mincut_terms
         if (not K.dense_pool_is_small(x.size(0), x.size(1), weight.size(0), x.size(2))
@@ -671,14 +686,18 @@ class _DenseMLPPooling(DenseSRCPooling):
         return _Pooled(SelectOutput(s=s, s_inv_op=sel.s_inv_op, in_mask=mask), x_pool, raw if mincut else None, adj_pool,
                        pair if mincut else None, pair if diff_scales is not None else None, bp)
 
-    def _select_reduce_connect_large(self, x, adj, mask, graph_sizes, so=None, symmetry=None, known_nodes=None):
+    def _select_reduce_connect_large(self, x, adj, mask, graph_sizes, so=None, symmetry=None, known_nodes=None,
+                                     adj_handed=False):
         """Training on a padded batch whose graphs are beyond the one-wave kernels (C2-sized), r6: Select (single-Linear
         selector; otherwise ``so`` holds S) + Reduce + Connect + post-processing + the pooler's two losses as ONE
         autograd node (functions._PoolLargeFn: ~10 forward and ~13 backward launches where the operator-by-operator graph
-        ran 65-71).  Returns a ``_Pooled`` like :meth:`_select_reduce_connect_train`, or None."""
+        ran 65-71).  ``adj_handed``: as in :meth:`_select_reduce_connect_train` (the node's backward then also forms dA:
+        one small product and one N^2 K launch).  Returns a ``_Pooled`` like :meth:`_select_reduce_connect_train`, or
+        None."""
         sel, c = self.selector, self.connector
         if (not _FOLD_TRAINING or self._loss_only or not self._plain_wiring(c) or not self._padded_f32(x, adj, mask)
-                or not torch.is_grad_enabled() or adj.requires_grad or c.edge_weight_norm
+                or not torch.is_grad_enabled() or c.edge_weight_norm
+                or (adj.requires_grad and not self._adj_grad_ok(adj, c, adj_handed))
                 or x.size(0) == 0 or x.size(1) == 0 or x.size(2) == 0):  # (this route only: its grids need every extent)
             return None
         weight = bias = s = None
@@ -946,27 +965,30 @@ class _DenseMLPPooling(DenseSRCPooling):
             elif mask is None and isinstance(x, Tensor) and x.dim() == 3:
                 known_nodes = x.size(0) * x.size(1)
             sparse_edges = (adj, edge_weight) if sparse_in else None
+            adj_handed = is_dense_adj(adj)  # (a dense adjacency of the caller's: it may get a gradient on the fused routes)
             x, adj, mask = self._ensure_batched_inputs(x=x, edge_index=adj, edge_weight=edge_weight, batch=batch,
                                                        mask=mask)
             # (the folded kernels also write the pooled batch vector: arange(B).repeat_interleave(K) of the B graphs)
             want_bp = sparse_in and batch is not None and batch.dtype == torch.long and batch.numel() > 0
             pooled = self._select_reduce_connect(x, adj, mask, want_bp, known_nodes)
             if pooled is None and _FOLD_TRAINING:
-                pooled = self._select_reduce_connect_train(x, adj, mask, graph_sizes, want_bp, known_nodes)
+                pooled = self._select_reduce_connect_train(x, adj, mask, graph_sizes, want_bp, known_nodes, adj_handed)
             symmetry = None
             if sparse_in and _FOLD_TRAINING and torch.is_grad_enabled() and isinstance(adj, Tensor) and adj.dim() == 3:
                 # (asked only when the one-node path takes the call: a launch over the entries, answered in its backward)
                 dense_adj, ei_in, ew_in = adj, sparse_edges[0], sparse_edges[1]
                 symmetry = lambda: self._adj_symmetry(ei_in, ew_in, dense_adj, batch)  # noqa: E731
             elif (not sparse_in and _FOLD_TRAINING and torch.is_grad_enabled() and isinstance(adj, Tensor)
-                  and adj.dim() == 3 and adj.is_contiguous()):
+                  and adj.dim() == 3 and adj.is_contiguous() and not adj.requires_grad):
                 # a dense adjacency the caller holds (e.g. one fixed graph pooled every epoch): one pass over it, once
-                # per tensor object, tells whether A = A^T (the backward then forms one N^2 K product less)
+                # per tensor object, tells whether A = A^T (the backward then forms one N^2 K product less).  Not for one
+                # that requires a gradient: an activation is a fresh tensor every step, the memo would never hit and
+                # cost a pass per step -- the general backward is taken
                 held = adj
                 symmetry = lambda: K.AdjSymmetry.of_dense(held)  # noqa: E731
             if pooled is None and _FOLD_TRAINING:  # graphs beyond the one-wave kernels: one autograd node as well (r6)
                 pooled = self._select_reduce_connect_large(x, adj, mask, graph_sizes, symmetry=symmetry,
-                                                           known_nodes=known_nodes)
+                                                           known_nodes=known_nodes, adj_handed=adj_handed)
             so = pooled.so if pooled is not None else self.select(x=x, mask=mask)
             self._sizes_hint = None
             if graph_sizes is not None and graph_sizes.numel() == x.size(0):
@@ -974,10 +996,12 @@ class _DenseMLPPooling(DenseSRCPooling):
                 self._sizes_hint = (weakref.ref(adj), graph_sizes)  # valid for exactly this adjacency tensor
             if pooled is None:  # Reduce + Connect in one native call (training: batches of small graphs only)
                 pooled = self._reduce_connect_pooled(x, adj, so, self._wants_raw, self._mincut_terms,
-                                                     self._fused_diff_scales(adj, known_nodes))
+                                                     self._fused_diff_scales(adj, known_nodes),
+                                                     adj_grad=(not self._loss_only
+                                                               and self._adj_grad_ok(adj, self.connector, adj_handed)))
                 if pooled is None and _FOLD_TRAINING:  # a selector with hidden layers made S: the pooling step is one node still
                     pooled = self._select_reduce_connect_large(x, adj, mask, graph_sizes, so=so, symmetry=symmetry,
-                                                               known_nodes=known_nodes)
+                                                               known_nodes=known_nodes, adj_handed=adj_handed)
             if pooled is not None:
                 x_pool, adj_pool, batch_pool = pooled.x_pool, pooled.adj_pool, pooled.batch_pool
                 if batch_pool is None:

@@ -443,13 +443,15 @@ class DenseSRCPooling(SRCPooling):
         return like_input_dtype(x_pool, x), like_input_dtype(raw, s), like_input_dtype(adj_pool, s)
 
     def _reduce_connect_pooled(self, x: Tensor, adj: Tensor, so: SelectOutput, want_raw: bool, mincut_terms: bool,
-                               diff_scales) -> Optional[_Pooled]:
+                               diff_scales, adj_grad: bool = False) -> Optional[_Pooled]:
         """:meth:`reduce_connect` as a :class:`_Pooled` record, for the poolers whose losses ride on the pooling call:
         ``mincut_terms`` asks for MinCut's per-graph terms [2,B] (``terms``: None when the batch does not take the
         one-wave-per-graph kernel; a ``functions.LossPair`` of the two batch means under autograd), ``diff_scales`` =
         (link_scale, ent_scale) for DiffPool's two losses (``diff``: [2], or a ``LossPair`` under autograd; None when the
         batch takes another kernel -- the caller's own tail computes them then).  A pooler that asks for neither gets
-        the public method's three values."""
+        the public method's three values.  ``adj_grad``: the caller vouches that ``adj`` is a contiguous float32 adjacency
+        it was handed; one that requires a gradient then keeps the fused node (functions._DensePoolSmallFn forms dA in a
+        launch behind its backward) instead of the operator path.  The public method never does."""
         if not mincut_terms and diff_scales is None:
             res = self.reduce_connect(x, adj, so, want_raw)
             return None if res is None else _Pooled(so, res[0], res[1], res[2])
@@ -465,7 +467,7 @@ class DenseSRCPooling(SRCPooling):
         flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose, c.edge_weight_norm)
         sizes = getattr(so, "_graph_sizes", None)
         if torch.is_grad_enabled() and (s.requires_grad or adj.requires_grad or x.requires_grad):
-            if (adj.requires_grad or c.edge_weight_norm
+            if ((adj.requires_grad and not adj_grad) or c.edge_weight_norm
                     or s.dtype != torch.float32 or x.dtype != torch.float32 or adj.dtype != torch.float32
                     or not K.dense_pool_is_small(s.size(0), s.size(1), s.size(2), x.size(2))):
                 return None
