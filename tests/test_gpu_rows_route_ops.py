@@ -288,7 +288,7 @@ def _pool_batch(sizes, f, seed):
 
 def _pool_runs(pooler, x, ei, batch, dev):
     """Inference outputs and one training step's gradients of a pooler call, as a dict of tensors."""
-    lin = pooler.selector.mlp.lins[0]
+    lins = pooler.selector.mlp.lins
     args = dict(adj=ei.to(dev), batch=batch.to(dev))
     out = {}
     pooler.eval()
@@ -306,17 +306,21 @@ def _pool_runs(pooler, x, ei, batch, dev):
     l1, l2 = list(o.loss.values())
     ((o.x * wx).sum() + (o.edge_index * wa).sum() + 0.7 * l1 + 1.3 * l2).backward()
     out.update(train_x=o.x.detach(), train_adj=o.edge_index.detach(), train_loss1=l1.detach(), train_loss2=l2.detach(),
-               dX=xg.grad.clone(), dW=lin.weight.grad.clone(), db=lin.bias.grad.clone())
+               dX=xg.grad.clone())
+    for i, lin in enumerate(lins):  # (every layer of the selector: one, or two with a hidden layer)
+        out.update({f"dW{i}": lin.weight.grad.clone(), f"db{i}": lin.bias.grad.clone()})
     torch.cuda.synchronize()
     return out
 
 
-ONE_CALL_CASES = [  # alias, graph sizes, K, F, rows-route density to force (batched poolers)
+ONE_CALL_CASES = [  # alias, graph sizes, K, F or [F, hidden width], rows-route density to force (batched poolers)
     ("mincut_u", [130, 97, 160], 40, 24, None),
     ("diff_u", [130, 97, 160], 40, 24, None),
     ("mincut_u", [700, 90], 80, 33, None),
     ("diff_u", [700, 90], 80, 33, None),
     ("mincut", [260, 199], 72, 16, 2.0),
+    ("mincut_u", [130, 97], 40, [24, 8], None),  # a hidden layer: S is handed to the native call and to the node
+    ("diff", [260, 199], 72, [16, 8], 2.0),
 ]
 
 
@@ -324,7 +328,8 @@ ONE_CALL_CASES = [  # alias, graph sizes, K, F, rows-route density to force (bat
 def test_one_native_call_equals_the_composed_operators(dev, monkeypatch, alias, sizes, k, f, density):
     """kernels.pool_rows_forward / pool_rows_backward make the launches of the operator-by-operator path
     (csrc/pool_rows.cpp): so.s, x, adj, both losses in inference and dX, dW, db of a training step are bit-identical with
-    ``_POOL_ROWS_ONE_CALL`` on and off.  The spies make sure the two runs really took the two paths."""
+    ``_POOL_ROWS_ONE_CALL`` on and off.  The spies make sure the two runs really took the two paths.  With a hidden layer
+    the selector runs in front and hands S over: the forward's one call takes it, the backward's is not asked."""
     import tgp.poolers as P
     from tgp import kernels as K
     from tgp.poolers import get_pooler
@@ -342,15 +347,48 @@ def test_one_native_call_equals_the_composed_operators(dev, monkeypatch, alias, 
 
     monkeypatch.setattr(K, "pool_rows_forward", spy("fwd", fwd))
     monkeypatch.setattr(K, "pool_rows_backward", spy("bwd", bwd))
-    x, ei, _, batch = _pool_batch(sizes, f, seed=sum(sizes) + k)
+    hidden = isinstance(f, list)
+    x, ei, _, batch = _pool_batch(sizes, f[0] if hidden else f, seed=sum(sizes) + k)
     pooler = get_pooler(alias, in_channels=f, k=k).to(dev)
+    want = {"fwd": 2, "bwd": 0 if hidden else 1}  # inference, training forward, training backward
     monkeypatch.setattr(K, "_POOL_ROWS_ONE_CALL", True)
     one = _pool_runs(pooler, x, ei, batch, dev)
-    assert took == {"fwd": 2, "bwd": 1}, took  # inference, training forward, training backward
+    assert took == want, took
     monkeypatch.setattr(K, "_POOL_ROWS_ONE_CALL", False)
     composed = _pool_runs(pooler, x, ei, batch, dev)
-    assert took == {"fwd": 2, "bwd": 1}, took  # (the composed run took none)
+    assert took == want, took  # (the composed run took none)
     differ = [f"{name} (max |diff| {float((one[name] - composed[name]).abs().max()):.3e})"
               for name in one if not _same_bits(one[name], composed[name])]
     print(f"one_call/{alias}-K{k}-F{f} | {len(one)} values compared bit for bit | differ: {differ or 'none'}")
+    assert not differ, differ
+
+
+_COMPOSED_SIZES, _COMPOSED_K, _COMPOSED_F = [30, 80, 50], 5, 7
+
+
+@pytest.mark.parametrize("selector", [False, True], ids=["s_given", "selector"])
+@pytest.mark.parametrize("transposed", [False, True], ids=["plain", "transposed"])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_composed_forward_equals_the_one_native_call(dev, mode, transposed, selector):
+    """kernels.pool_rows_forward_composed makes the launches of kernels.pool_rows_forward one operator at a time
+    (csrc/pool_rows.cpp: "the same launches"): the two dicts have the same keys and every value is bit-identical, for the
+    three loss modes, both orientations of the pooled adjacency, S handed in and S from the selector's Linear."""
+    from tgp import kernels as K
+    sizes, k, f = _COMPOSED_SIZES, _COMPOSED_K, _COMPOSED_F
+    from test_gpu_unbatched_dense import _batch
+    x, ei, ew, _ = _batch(sizes, f, 6.0, seed=17)  # row-sorted and duplicate-free, a random weight per direction
+    n = sum(sizes)
+    g = torch.Generator().manual_seed(23)
+    weight, bias = (0.5 * torch.randn(k, f, generator=g)).to(dev), (0.1 * torch.randn(k, generator=g)).to(dev)
+    xd, eid, w, ptr = x.to(dev), ei.to(dev), ew.to(dev), R.ptr_of(sizes).to(dev)
+    s = None if selector else torch.softmax(xd @ weight.t() + bias, -1)
+    args = (xd, weight if selector else None, bias if selector else None, s, K.csr_offsets(eid, n), eid, w, ptr, max(sizes),
+            transposed, K.dense_flags(True, True, transposed, False), mode, (1.0 / n, 0.5 / n), float(torch.dot(ew, ew)))
+    one, composed = K.pool_rows_forward(*args), K.pool_rows_forward_composed(*args)
+    torch.cuda.synchronize()
+    assert one is not None and set(one) == set(composed), (one and sorted(one), sorted(composed))
+    differ = [name for name in one if (one[name] is None) != (composed[name] is None)
+              or (one[name] is not None and not _same_bits(one[name], composed[name]))]
+    print(f"composed/mode{mode}-transposed{int(transposed)}-selector{int(selector)} | {len(one)} values compared bit for bit"
+          f" | differ: {differ or 'none'}")
     assert not differ, differ

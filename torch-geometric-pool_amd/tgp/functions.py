@@ -1157,6 +1157,49 @@ def select_pool_small(x: Tensor, adj: Tensor, weight: Tensor, bias: Optional[Ten
 POOL_LARGE_STATS = {"symmetric": 0, "general": 0}  # backward passes by route (diagnostics / tests)
 
 
+def _node_outputs(ctx, s, selector, mode, x_pool, raw, adj_pool, la, lb):
+    """What the two training nodes return: S (an empty stand-in when S was handed in), x_pool, raw, adj_pool and the two
+    losses (not differentiable in mode 0, which has none)."""
+    if mode == 0:
+        ctx.mark_non_differentiable(la, lb)
+    if not selector:
+        s = s.new_empty(0)
+        ctx.mark_non_differentiable(s)
+    return s, x_pool, raw, adj_pool, la, lb
+
+
+def _loss_grads(mode, g_s, g_xp, g_raw, g_adj, g_la, g_lb):
+    """(g_la, g_lb) as the two backwards read them (mode 0 has no losses), or None when no gradient arrived at all."""
+    if mode == 0:
+        g_la = g_lb = None
+    if g_s is None and g_xp is None and g_raw is None and g_adj is None and g_la is None and g_lb is None:
+        return None
+    return g_la, g_lb
+
+
+def _upstream_grads(ctx, raw, g_adj, g_raw, g_xp, F):
+    """(ga, gb, gx_t, gx_bc): the gradient of raw through the post-processing and the one handed in directly, the
+    gradient of x_pool dense or as its one broadcast row -- as the right-hand-side kernel reads them."""
+    from . import _native as N
+    ga = None
+    if g_adj is not None:
+        ga = K.postprocess_dense_bwd(raw, g_adj, ctx.flags)
+        if ga is None:
+            raise RuntimeError("dense pooling backward: K > 4096 is not supported by the post-processing backward")
+    gb = None if g_raw is None else N.f32c(g_raw)
+    return (ga, gb) + tuple(K._bcast_or_dense(g_xp, (raw.size(0), raw.size(1), F)))
+
+
+def _train_rhs(ctx, upstream, gram, den, stats, lossv, g_la, g_lb, sym_flags, weight, B, Kc, F, dev):
+    """kernels.dense_pool_train_rhs with what each loss mode hands it.  ``weight``: the selector's when gX is folded in."""
+    mode = ctx.mode
+    ga, gb, gx_t, gx_bc = upstream
+    return K.dense_pool_train_rhs(
+        ga, gb, mode, stats if mode == 1 else None, den if mode == 1 else None, gram if mode else None, g_la,
+        g_lb if mode == 1 else None, 1.0 / B, lossv[0:1] if mode == 2 else None, ctx.scales[0] if mode == 2 else 0.0,
+        gx_t, gx_bc, sym_flags, weight, B, Kc, F, dev)
+
+
 class _PoolLargeFn(torch.autograd.Function):
     """Select (optional) + Reduce + Connect + post-processing + the pooler's two auxiliary losses of a padded batch whose
     graphs are too large for the one-wave / one-workgroup kernels (C2: 32 x 1024 nodes, K = 128), as ONE autograd node
@@ -1199,7 +1242,7 @@ class _PoolLargeFn(torch.autograd.Function):
         Kc = s.size(-1)
         ad = adj.detach()
         mem, tflag = K._dense_adj_layout(ad)
-        acat = torch.empty(B, Nn, 3 * Kc + F + K.TRAIN_PAD, dtype=torch.float32, device=xd.device)
+        acat = torch.empty(B, Nn, K.train_columns(Kc, F).ld, dtype=torch.float32, device=xd.device)
         x_pool, raw, adj_pool, gram = K.dense_pool_train_fwd(s, mem, xd, flags | tflag, acat, want_gram=mode != 0)
         empty = s.new_empty(0)
         la, lb = s.new_empty(0), s.new_empty(0)  # (distinct objects: both are outputs of this node)
@@ -1225,47 +1268,30 @@ class _PoolLargeFn(torch.autograd.Function):
         ctx.flags, ctx.tflag, ctx.mode, ctx.scales, ctx.selector = flags, tflag, mode, scales, selector
         ctx.has_bias = bias is not None
         ctx.sym = sym
-        if mode == 0:
-            ctx.mark_non_differentiable(la, lb)
-        if selector:
-            return s, x_pool, raw, adj_pool, la, lb
-        no_s = s.new_empty(0)
-        ctx.mark_non_differentiable(no_s)
-        return no_s, x_pool, raw, adj_pool, la, lb
+        return _node_outputs(ctx, s, selector, mode, x_pool, raw, adj_pool, la, lb)
 
     @staticmethod
     def backward(ctx, g_s, g_xp, g_raw, g_adj, g_la, g_lb):
-        from . import _native as N
         s, mem, xd, weight, acat, raw, gram, deg, den, lossv, stats, qrow = ctx.saved_tensors
         B, Nn, Kc = s.shape
         F = xd.size(2)
         mode, selector = ctx.mode, ctx.selector
         dev = s.device
-        if mode == 0:
-            g_la = g_lb = None
+        loss_grads = _loss_grads(mode, g_s, g_xp, g_raw, g_adj, g_la, g_lb)
+        if loss_grads is None:
+            return (None,) * 11
+        g_la, g_lb = loss_grads
         want_gx = ctx.needs_input_grad[0]
-        nothing = (None,) * 11
-        if g_s is None and g_xp is None and g_raw is None and g_adj is None and g_la is None and g_lb is None:
-            return nothing
-        ga = None
-        if g_adj is not None:
-            ga = K.postprocess_dense_bwd(raw, g_adj, ctx.flags)
-            if ga is None:
-                raise RuntimeError("dense pooling backward: K > 4096 is not supported by the post-processing backward")
-        gb = None if g_raw is None else N.f32c(g_raw)
-        gx_t, gx_bc = K._bcast_or_dense(g_xp, (B, Kc, F))
+        upstream = ga, gb, gx_t, gx_bc = _upstream_grads(ctx, raw, g_adj, g_raw, g_xp, F)
         link_loss = lossv[0:1] if mode == 2 else None
         # A = A^T: V = U, the second N^2 K product is not needed (not asked when A wants a gradient: dA reads RV = gR)
         symmetric = not ctx.adj_grad and ctx.sym is not None and ctx.sym.get()
         POOL_LARGE_STATS["symmetric" if symmetric else "general"] += 1
         fold_gx = selector and want_gx  # gX = [S | dY] [g_x ; W] as one product over acat's last two blocks
-        rcat, c1, gwcat = K.dense_pool_train_rhs(
-            ga, gb, mode, stats if mode == 1 else None, den if mode == 1 else None, gram if mode else None, g_la,
-            g_lb if mode == 1 else None, 1.0 / B, link_loss, ctx.scales[0] if mode == 2 else 0.0, gx_t, gx_bc, symmetric,
-            weight if fold_gx else None, B, Kc, F, dev)
+        rcat, c1, gwcat = _train_rhs(ctx, upstream, gram, den, stats, lossv, g_la, g_lb, symmetric,
+                                     weight if fold_gx else None, B, Kc, F, dev)
         pad = K.TRAIN_PAD
-        ld = 3 * Kc + F + pad
-        c_x, c_one, c_s, c_v = Kc, Kc + F, Kc + F + pad, 2 * Kc + F + pad
+        ld, c_x, c_one, c_s, c_v = K.train_columns(Kc, F)
         g_adj_in = None
         if ctx.adj_grad and (ga is not None or gb is not None or g_la is not None):  # (else: no path reaches A)
             g_adj_in = K.dense_pool_adj_grad(s, mem, rcat[:, c_v:, :], gamma=c1 if mode == 1 else None,
@@ -1339,76 +1365,28 @@ class _PoolUnbatchedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, s_given, ei, ew, row_ptr, ptr, batch, max_nodes, flags, mode, scales, sw2, sym,
                 transposed=False):
-        # transposed: the pooled adjacency is S^T A^T S (what the BATCHED poolers compute from a sparse input with
-        # adj_transpose=True, src.py:442-443) = the transpose of S^T (A S); MinCut's degrees are then the in-degrees
+        # transposed: the pooled adjacency is S^T A^T S (kernels.pool_rows_forward_composed says what that means)
         from . import _native as N
         ctx.set_materialize_grads(False)
         xd = N.f32c(x.detach())
-        n, F = xd.shape
-        selector = s_given is None
-        one = K.pool_rows_forward(xd, None if weight is None else weight.detach(), None if bias is None else bias.detach(),
-                                  None if selector else N.f32c(s_given.detach()), row_ptr, ei, ew, ptr, max_nodes,
-                                  transposed, flags, mode, scales, sw2)
-        if one is not None:  # the whole forward as ONE native call (r6, late: same launches, no host work between them)
-            s, t, raw, x_pool, gram, adj_pool = (one[k] for k in ("s", "t", "raw", "x_pool", "gram", "adj_pool"))
-            empty = s.new_empty(0)
-            la, lb = s.new_empty(0), s.new_empty(0)
-            deg = den = lossv = stats = None
-            if mode == 1:
-                deg, den, stats, both = one["deg"], one["den"], one["stats"], one["both"]
-                la, lb = both[0], both[1]
-            elif mode == 2:
-                lossv = one["lossv"]
-                la, lb = lossv[0], lossv[1]
-            return _PoolUnbatchedFn._finish_forward(ctx, s, t, xd, weight, raw, ei, row_ptr, ptr, gram, deg, den, lossv,
-                                                    stats, ew, batch, flags, mode, scales, selector, max_nodes, bias, sym,
-                                                    transposed, x_pool, adj_pool, la, lb)
-        s = K.mlp_select(xd, weight.detach(), None if bias is None else bias.detach(), None) if selector \
-            else N.f32c(s_given.detach())
-        Kc = s.size(1)
-        B = ptr.numel() - 1
-        deg = q = ent_part = None
-        if mode == 1:  # MinCut: out-degrees and |S_i|^2 ride along with T = A S
-            t, deg, q = K.spmm_csr(row_ptr, ei, ew, n, s, want_stats=True)
-        elif mode == 2:  # DiffPool: the entropy sum over S rides along
-            t, ent_part = K.spmm_csr(row_ptr, ei, ew, n, s, want_stats="entropy")
-        else:
-            t = K.spmm_csr(row_ptr, ei, ew, n, s)
-        raw, x_pool, gram, adj_pool = K.segment_gemm_tn3(s, [t, xd, s], ptr, max_nodes, transpose0=transposed,
-                                                         post_flags=flags)
-        empty = s.new_empty(0)
-        la, lb = s.new_empty(0), s.new_empty(0)
-        den = lossv = stats = None
-        if mode == 1:
-            if transposed:  # den = sum_j indeg_j q_j = sum_e w_e q[col_e]: the tail walks the graph's entries itself
-                den, terms, stats, both = K.mincut_terms_fused(raw, gram, None, q, ptr=ptr, want_means=True,
-                                                               edges=(row_ptr, ei, ew))
-            else:
-                den, terms, stats, both = K.mincut_terms_fused(raw, gram, deg, q, ptr=ptr, want_means=True)
-            la, lb = both[0], both[1]
-        elif mode == 2:
-            lossv = K.diffpool_unbatched_tail(raw, gram, s, sw2, scales[0], scales[1], ent_partials=ent_part)
-            la, lb = lossv[0], lossv[1]
-        return _PoolUnbatchedFn._finish_forward(ctx, s, t, xd, weight, raw, ei, row_ptr, ptr, gram, deg, den, lossv, stats,
-                                                ew, batch, flags, mode, scales, selector, max_nodes, bias, sym, transposed,
-                                                x_pool, adj_pool, la, lb)
-
-    @staticmethod
-    def _finish_forward(ctx, s, t, xd, weight, raw, ei, row_ptr, ptr, gram, deg, den, lossv, stats, ew, batch, flags, mode,
-                        scales, selector, max_nodes, bias, sym, transposed, x_pool, adj_pool, la, lb):
-        empty = s.new_empty(0)
-        keep = [v if v is not None else empty for v in (gram, deg, den, lossv, stats, ew, batch)]
-        ctx.save_for_backward(s, t, xd, empty if weight is None else weight, raw, ei, row_ptr, ptr, *keep)
-        ctx.flags, ctx.mode, ctx.scales, ctx.selector, ctx.max_nodes = flags, mode, scales, selector, max_nodes
+        rec = K.pool_rows(xd, None if weight is None else weight.detach(), None if bias is None else bias.detach(),
+                          None if s_given is None else N.f32c(s_given.detach()), row_ptr, ei, ew, ptr, max_nodes,
+                          transposed, flags, mode, scales, sw2)
+        ctx.flags, ctx.mode, ctx.scales, ctx.selector, ctx.max_nodes = flags, mode, scales, s_given is None, max_nodes
         ctx.has_bias, ctx.sym, ctx.has_w, ctx.has_batch = bias is not None, sym, ew is not None, batch is not None
         ctx.transposed = transposed
-        if mode == 0:
-            ctx.mark_non_differentiable(la, lb)
-        if selector:
-            return s, x_pool, raw, adj_pool, la, lb
-        no_s = s.new_empty(0)
-        ctx.mark_non_differentiable(no_s)
-        return no_s, x_pool, raw, adj_pool, la, lb
+        return _PoolUnbatchedFn._finish_forward(ctx, rec, xd, weight, ei, row_ptr, ptr, ew, batch)
+
+    @staticmethod
+    def _finish_forward(ctx, rec, xd, weight, ei, row_ptr, ptr, ew, batch):
+        """Keep what the backward reads of the forward's record ``rec`` (kernels.pool_rows) and hand out the rest."""
+        s, raw, mode = rec["s"], rec["raw"], ctx.mode
+        empty = s.new_empty(0)
+        keep = [v if v is not None else empty
+                for v in (rec["gram"], rec.get("deg"), rec.get("den"), rec.get("lossv"), rec.get("stats"), ew, batch)]
+        ctx.save_for_backward(s, rec["t"], xd, empty if weight is None else weight, raw, ei, row_ptr, ptr, *keep)
+        pair = rec["both"] if mode == 1 else rec["lossv"] if mode == 2 else (s.new_empty(0), s.new_empty(0))
+        return _node_outputs(ctx, s, ctx.selector, mode, rec["x_pool"], raw, rec["adj_pool"], pair[0], pair[1])
 
     @staticmethod
     def backward(ctx, g_s, g_xp, g_raw, g_adj, g_la, g_lb):
@@ -1421,11 +1399,10 @@ class _PoolUnbatchedFn(torch.autograd.Function):
         B = ptr.numel() - 1
         mode, selector = ctx.mode, ctx.selector
         dev = s.device
-        if mode == 0:
-            g_la = g_lb = None
-        nothing = (None,) * 16
-        if g_s is None and g_xp is None and g_raw is None and g_adj is None and g_la is None and g_lb is None:
-            return nothing
+        loss_grads = _loss_grads(mode, g_s, g_xp, g_raw, g_adj, g_la, g_lb)
+        if loss_grads is None:
+            return (None,) * 16
+        g_la, g_lb = loss_grads
         want_gx = ctx.needs_input_grad[0]
         symmetric = ctx.sym is not None and ctx.sym.get()
         POOL_LARGE_STATS["symmetric" if symmetric else "general"] += 1
@@ -1440,24 +1417,15 @@ class _PoolUnbatchedFn(torch.autograd.Function):
                                        want_gb)
             if one is not None:
                 return (one[0], one[1], one[2]) + (None,) * 13
-        ga = None
-        if g_adj is not None:
-            ga = K.postprocess_dense_bwd(raw, g_adj, ctx.flags)
-            if ga is None:
-                raise RuntimeError("dense pooling backward: K > 4096 is not supported by the post-processing backward")
-        gb = None if g_raw is None else N.f32c(g_raw)
-        gx_t, gx_bc = K._bcast_or_dense(g_xp, (B, Kc, F))
+        upstream = _, _, gx_t, gx_bc = _upstream_grads(ctx, raw, g_adj, g_raw, g_xp, F)
         fold_gx = selector and want_gx
         # the operand buffer's first block holds T = A S.  With raw = S^T A S that is "U" (right-hand side gR^T) and
         # T' = A^T S is "V" (gR); for the transposed form raw = S^T A^T S the two trade places (flag bit 1).
         sym_flags = 1 if symmetric else (2 if ctx.transposed else 0)
-        rcat, c1, gwcat = K.dense_pool_train_rhs(
-            ga, gb, mode, stats if mode == 1 else None, den if mode == 1 else None, gram if mode else None, g_la,
-            g_lb if mode == 1 else None, 1.0 / B, lossv[0:1] if mode == 2 else None,
-            ctx.scales[0] if mode == 2 else 0.0, gx_t, gx_bc, sym_flags, weight if fold_gx else None, B, Kc, F, dev)
+        rcat, c1, gwcat = _train_rhs(ctx, upstream, gram, den, stats, lossv, g_la, g_lb, sym_flags,
+                                     weight if fold_gx else None, B, Kc, F, dev)
         pad = K.TRAIN_PAD
-        ld = 3 * Kc + F + pad
-        c_x, c_one, c_s, c_v = Kc, Kc + F, Kc + F + pad, 2 * Kc + F + pad
+        ld, c_x, c_one, c_s, c_v = K.train_columns(Kc, F)
         acat = torch.empty(n, ld, dtype=torch.float32, device=dev)
         K.copy_cols3(t, xd, s, acat, 0, c_x, c_s, one_col=c_one)  # [T | X | 1 0 0 0 | S | .]: one launch
         vblock = acat[:, c_v:]

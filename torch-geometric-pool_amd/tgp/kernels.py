@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+from collections import namedtuple
 from types import SimpleNamespace
 from typing import Optional, Sequence, Tuple
 from weakref import ref as _weakref
@@ -1605,7 +1606,7 @@ def dense_pool_train_rhs(g_raw_a: Optional[Tensor], g_raw_b: Optional[Tensor], m
     training step's backward GEMM and, with the selector's ``weight``, [g_x ; W] for gX = [S | dY] [g_x ; W]
     (see tgp_dense_pool_train_rhs_f32 in include/tgp_hip.h).  ``symmetric``: bool, or the flag word (bit 0: A = A^T,
     bit 1: the RU / RV slots trade places)."""
-    rcat = torch.empty(B, 3 * Kc + F + TRAIN_PAD, Kc, dtype=torch.float32, device=dev)
+    rcat = torch.empty(B, train_columns(Kc, F).ld, Kc, dtype=torch.float32, device=dev)
     c1 = torch.empty(B, dtype=torch.float32, device=dev) if mode == 1 else None
     gw = torch.empty(B, 2 * Kc, F, dtype=torch.float32, device=dev) if weight is not None else None
     w = None if weight is None else N.f32c(weight.detach())
@@ -1643,6 +1644,14 @@ def softmax_bwd_ex(s: Tensor, ds: Tensor, extra: Optional[Tensor] = None, c1: Op
 
 
 TRAIN_PAD = 4  # width of the [1 0 0 0] column block of the training step's operand buffer (csrc/losses.hip)
+
+
+# the training step's operand buffer [U | X | 1 0 0 0 | S | V]: its row length and where the blocks behind U begin
+TrainColumns = namedtuple("TrainColumns", "ld c_x c_one c_s c_v")
+
+
+def train_columns(Kc: int, F: int) -> TrainColumns:
+    return TrainColumns(3 * Kc + F + TRAIN_PAD, Kc, Kc + F, Kc + F + TRAIN_PAD, 2 * Kc + F + TRAIN_PAD)
 
 
 def copy_cols2(a: Tensor, b: Tensor, dst: Tensor, col_a: int, col_b: int, one_col: int = -1) -> None:
@@ -3399,6 +3408,39 @@ def pool_rows_forward(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor
     return out
 
 
+def pool_rows_forward_composed(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], s_given: Optional[Tensor],
+                               row_ptr: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], ptr: Tensor,
+                               max_nodes: int, transposed: bool, flags: int, mode: int, scales=(0.0, 0.0), sw2=0.0):
+    """:func:`pool_rows_forward` one operator at a time: the same launches, the same dict, for any case.
+    ``transposed``: the pooled adjacency is S^T A^T S (what the BATCHED poolers compute from a sparse input with
+    adj_transpose=True, src.py:442-443) = the transpose of S^T (A S); MinCut's degrees are then the in-degrees."""
+    n, out = x.size(0), {}
+    s = mlp_select(x, weight, bias, None) if s_given is None else s_given
+    if mode == 1:  # MinCut: out-degrees and |S_i|^2 ride along with T = A S
+        t, deg, q = spmm_csr(row_ptr, edge_index, edge_weight, n, s, want_stats=True)
+    elif mode == 2:  # DiffPool: the entropy sum over S rides along
+        t, ent_part = spmm_csr(row_ptr, edge_index, edge_weight, n, s, want_stats="entropy")
+    else:
+        t = spmm_csr(row_ptr, edge_index, edge_weight, n, s)
+    raw, x_pool, gram, adj_pool = segment_gemm_tn3(s, [t, x, s], ptr, max_nodes, transpose0=transposed, post_flags=flags)
+    if mode == 1:
+        # transposed: den = sum_j indeg_j q_j = sum_e w_e q[col_e], the tail walks the graph's entries itself
+        den, terms, stats, both = mincut_terms_fused(raw, gram, None if transposed else deg, q, ptr=ptr, want_means=True,
+                                                     edges=(row_ptr, edge_index, edge_weight) if transposed else None)
+        out.update(deg=deg, q=q, den=den, terms=terms, stats=stats, both=both)
+    elif mode == 2:
+        out.update(lossv=diffpool_unbatched_tail(raw, gram, s, sw2, scales[0], scales[1], ent_partials=ent_part))
+    out.update(s=s, t=t, raw=raw, x_pool=x_pool, gram=gram if mode else None, adj_pool=adj_pool)
+    return out
+
+
+def pool_rows(*args):
+    """The rows route's forward: :func:`pool_rows_forward` where the case is that entry's, else the composed operators
+    (same arguments, same dict)."""
+    out = pool_rows_forward(*args)
+    return out if out is not None else pool_rows_forward_composed(*args)
+
+
 def pool_rows_backward(s: Tensor, t: Tensor, x: Tensor, weight: Tensor, raw: Tensor, gram, stats, den, deg, lossv,
                        ptr: Tensor, batch, slab_ptr: Tensor, max_nodes: int, flags: int, mode: int, transposed: bool,
                        scales, g_adj, g_raw, g_xp, g_s, g_la, g_lb, want_gx: bool, want_gw: bool, want_gb: bool):
@@ -3430,8 +3472,7 @@ def pool_rows_backward(s: Tensor, t: Tensor, x: Tensor, weight: Tensor, raw: Ten
         if tuple(g_xp.shape) != (B, Kc, F) or g_xp.dtype != f32:
             return None
         g_xp, gx_bc = _bcast_or_dense(g_xp, (B, Kc, F))
-    pad = TRAIN_PAD
-    ld = 3 * Kc + F + pad
+    pad, ld = TRAIN_PAD, train_columns(Kc, F).ld
     e = dict(dtype=f32, device=dev)
     ga = torch.empty(B, Kc, Kc, **e) if g_adj is not None else None
     rcat = torch.empty(B, ld, Kc, **e)

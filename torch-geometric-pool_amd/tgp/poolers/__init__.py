@@ -765,6 +765,28 @@ class _DenseMLPPooling(DenseSRCPooling):
         one."""
         c, sel = self.connector, self.selector
         mode = self._rows_mode
+        grad = torch.is_grad_enabled()
+        gate = self._rows_gate(x, edge_index, edge_weight, batch, batched_out, c, sel, mode, grad)
+        if gate is None:
+            return None
+        info, ptr, max_nodes, nb, last = gate
+        plan = self._rows_selector_plan(x, batch, batched_out, c, last, mode, grad)
+        if plan is None or isinstance(plan, _Pooled):
+            return plan
+        ei, w_used, row_ptr, sw2, scales = self._rows_adjacency(x, edge_index, edge_weight, batched_out, mode, info, nb,
+                                                                max_nodes)
+        transposed = bool(batched_out and self.adj_transpose)
+        flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose if batched_out else False,
+                              c.edge_weight_norm)
+        so, s_flat, x_pool, adj_pool, both_or_loss = self._rows_execute(
+            x, edge_index, edge_weight, batch, batched_out, plan, mode,
+            (row_ptr, ei, w_used, ptr, max_nodes, transposed, flags, mode, scales, sw2))
+        return self._rows_hand_out(sel, so, s_flat, x_pool, adj_pool, both_or_loss, mode, batch, batched_out, info, nb,
+                                   max_nodes)
+
+    def _rows_gate(self, x, edge_index, edge_weight, batch, batched_out, c, sel, mode, grad):
+        """Everything the rows route decides before Select runs: (info, ptr, max_nodes, number of graphs, the selector's
+        single Linear or None), or None when the case is not this route's (nothing has been run or remembered then)."""
         staged = mode == 0  # (no loss mode in the native entries: the staged operators, see _rows_mode)
         if (mode is None or not self._plain_wiring(c) or (self.sparse_output and not batched_out)
                 # (this route only: a non-tensor weight declines here instead of raising)
@@ -774,7 +796,6 @@ class _DenseMLPPooling(DenseSRCPooling):
                 or edge_index.size(1) == 0 or x.size(1) == 0
                 or (edge_weight is not None and edge_weight.numel() != edge_index.size(1))):
             return None
-        grad = torch.is_grad_enabled()
         if grad and edge_weight is not None and edge_weight.requires_grad:
             return None
         if staged and (not batched_out
@@ -790,65 +811,67 @@ class _DenseMLPPooling(DenseSRCPooling):
         else:
             ptr, max_nodes, nb = Fn._whole_range(n, x.device), n, 1
         lins = self._mlp_lins(sel)
-        last = self._single_linear(lins)
-        single = last is not None
         if batched_out:  # every check comes BEFORE Select here: a bail-out must leave the batched flow untouched
             w_out = None if lins is None else lins[-1].weight  # (K is the last layer's, however many there are)
             if (not _ROWS_ROUTE or self.cache_preprocessing or w_out is None or w_out.dtype != torch.float32
                     or edge_index.size(1) > _rows_route_density(w_out.size(0)) * float(n) * float(max_nodes)
                     or K.dense_pool_is_small(nb, max_nodes, w_out.size(0), x.size(1))):
                 return None
-            k_out = w_out.size(0)
             will_train = grad and (x.requires_grad or any(p.requires_grad for p in sel.parameters()))
-            if will_train and (not _FOLD_TRAINING or c.edge_weight_norm or k_out > 4096):
+            if will_train and (not _FOLD_TRAINING or c.edge_weight_norm or w_out.size(0) > 4096):
                 return None
-        # the selector: folded into the training node when it is a single Linear, else run in front (its S handed over)
-        so = weight = bias = None
-        if single:
-            weight, bias = last.weight, last.bias
-        # inference with a single-Linear selector (r6, late): the selector rides in the ONE native call of the forward
-        # (kernels.pool_rows_forward); the SelectOutput is built from the S it leaves
-        fold_inference = (not grad and single and K._POOL_ROWS_ONE_CALL and x.dtype == torch.float32 and x.is_contiguous()
-                          and weight.size(0) <= 256 and not staged)
-        if fold_inference:
-            weight, bias = weight.detach(), None if bias is None else bias.detach()
-            s, training = None, False
-        elif not (grad and single and _FOLD_TRAINING):
-            weight = bias = None  # (the selector runs in front: its S is handed over)
-            so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
-            s = so.s
-            if batched_out and isinstance(s, Tensor) and s.dim() == 3 and s.size(0) == 1:
-                s = s[0]  # (MLPSelect in its batched representation treats [N,F] as one padded graph)
-            if not (isinstance(s, Tensor) and s.dim() == 2 and s.dtype == torch.float32 and s.size(0) == n):
+        return info, ptr, max_nodes, nb, self._single_linear(lins)
+
+    def _rows_select(self, x, batch, batched_out):
+        """(so, S [N,K]) of the selector run on its own on the un-padded rows."""
+        so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
+        s = so.s
+        if batched_out and isinstance(s, Tensor) and s.dim() == 3 and s.size(0) == 1:
+            s = s[0]  # (MLPSelect in its batched representation treats [N,F] as one padded graph)
+        return so, s
+
+    def _rows_selector_plan(self, x, batch, batched_out, c, last, mode, grad):
+        """What becomes of the selector: (weight, bias, s, so, training) -- ``weight`` / ``bias`` of its single Linear when
+        it is folded into the one native call of the inference or into the training node (``s`` and ``so`` are None
+        then), else the S and the SelectOutput of the selector run in front.  The route's own answer when it stops here:
+        None, or -- unbatched mode -- a ``_Pooled`` with only ``so`` (the caller goes on with it on the operator path)."""
+        so = s = weight = bias = None
+        w, b = (last.weight, last.bias) if last is not None else (None, None)
+        if (w is not None and not grad and K._POOL_ROWS_ONE_CALL and x.dtype == torch.float32 and x.is_contiguous()
+                and w.size(0) <= 256 and mode != 0):
+            # inference with a single-Linear selector (r6, late): the selector rides in the ONE native call of the forward
+            # (kernels.pool_rows_forward); the SelectOutput is built from the S it leaves
+            weight, bias, training = w.detach(), None if b is None else b.detach(), False
+        elif w is not None and grad and _FOLD_TRAINING:  # a single Linear: folded into the training node, if anything trains
+            training = x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)
+            if training:
+                weight, bias = w, b
+            else:
+                so, s = self._rows_select(x, batch, batched_out)
+        else:  # the selector runs in front: its S is handed over
+            so, s = self._rows_select(x, batch, batched_out)
+            if not (isinstance(s, Tensor) and s.dim() == 2 and s.dtype == torch.float32 and s.size(0) == x.size(0)):
                 return None if batched_out else _Pooled(so)  # (the caller goes on with it on the operator path)
             training = grad and (s.requires_grad or x.requires_grad)
-        else:
-            s = None
-            training = x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)
-            if not training:
-                so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
-                s = so.s[0] if (batched_out and so.s.dim() == 3) else so.s
         k = s.size(1) if s is not None else weight.size(0)
         if training and (not _FOLD_TRAINING or c.edge_weight_norm or k > 4096):
             if batched_out:
                 return None
-            if so is None:
-                so = self.select(x=x, batch=batch)
-            return _Pooled(so)
+            return _Pooled(so if so is not None else self._rows_select(x, batch, False)[0])
+        return weight, bias, s, so, training
+
+    def _rows_adjacency(self, x, edge_index, edge_weight, batched_out, mode, info, nb, max_nodes):
+        """(ei, weights or None when all are one, CSR offsets, sw2, scales): the sorted, duplicate-summed A (what the
+        reference's per-graph ``.coalesce()`` does) and, for DiffPool, sum_e w_e^2 with the two loss scales."""
+        n = x.size(0)
         w_in = None if edge_weight is None else edge_weight.reshape(-1)
         ones = w_in is None
-        # sorted + duplicate-summed A (what the reference's per-graph `.coalesce()` does), T = A S, then one product grid
         if ones and K.coalesced_memo(edge_index, n):  # (known to be coalesced: no vector of ones is made for the check)
             ei, w = edge_index, None
         else:
             ei, w = Fn.coalesce_sum(edge_index, torch.ones(edge_index.size(1), device=x.device) if ones else w_in.detach(), n)
         unit = ones and ei is edge_index  # (nothing merged: the weights are still all one)
-        w_used = None if unit else w
         row_ptr = K.csr_offsets(ei, n)
-        transposed = bool(batched_out and self.adj_transpose)
-        flags = K.dense_flags(c.remove_self_loops, c.degree_norm, c.adj_transpose if batched_out else False,
-                              c.edge_weight_norm)
-        mincut = mode == 1
         sw2, scales = 0.0, (0.0, 0.0)
         if mode == 2:  # the link loss: sum_e w_e^2 runs over the list as given (duplicates not merged, losses.py:680-690)
             # (batched form, losses.py:644-652: the dense A has the duplicates summed -- the same list after coalescing)
@@ -859,49 +882,36 @@ class _DenseMLPPooling(DenseSRCPooling):
             # (the normaliser, asked only when the link loss is normalised: adj.numel() of the padded batch, losses.py:651)
             scales = self._fused_diff_scales(None, n, (lambda: nb * max_nodes * max_nodes) if batched_out else (
                 lambda: sum(v * v for v in info.sizes_host) if info is not None else n * n))
+        return ei, None if unit else w, row_ptr, sw2, scales
+
+    def _rows_execute(self, x, edge_index, edge_weight, batch, batched_out, plan, mode, args):
+        """Reduce, Connect and the losses by exactly one of the training node, the staged operators (``mode`` 0) and the
+        native forward; ``args``: kernels.pool_rows_forward's behind S.  Returns (so, S [N,K], x_pool, adj_pool, the
+        pooler's two batch means -- the finished loss dict from the staged operators)."""
+        weight, bias, s, so, training = plan
+        row_ptr, ei, w_used, ptr, max_nodes, transposed, flags, _, scales, sw2 = args
         if training:
-            sym = K.AdjSymmetry.of_edge_list(edge_index, edge_weight, ei, w_used, row_ptr, n)
-            s_out, x_pool, raw, adj_pool, pair = Fn.pool_unbatched(
-                x, weight, bias, s, ei, w_used, row_ptr, ptr, batch, max_nodes, flags, mode, scales, sw2, sym, transposed)
-            s_flat = s_out
-            both = pair
-        elif staged:  # (the staged operators below: the one-call entry's loss modes are MinCut's and DiffPool's)
-            one = None
-        else:
-            one = K.pool_rows_forward(x, weight if s is None else None, bias if s is None else None, s, row_ptr, ei, w_used,
-                                      ptr, max_nodes, transposed, flags, mode, scales, sw2)
-            if one is None and s is None:  # (not the one-call entry's case after all: the selector runs on its own)
-                so = self.select(x=x, batch=batch) if not batched_out else self.select(x=x)
-                s = so.s[0] if (batched_out and so.s.dim() == 3) else so.s
-        if not training and one is not None:
-            s, raw, x_pool, adj_pool = one["s"], one["raw"], one["x_pool"], one["adj_pool"]
-            both = one["both"] if mincut else one["lossv"]
-            s_flat = s
-        elif staged:  # T = A S, S^T [T | X] with the post-processing, the pooler's loss on the un-padded S
-            t = K.spmm_csr(row_ptr, ei, w_used, n, s)
-            raw, x_pool, adj_pool = K.segment_gemm_tn3(s, [t, x], ptr, max_nodes, transpose0=transposed, post_flags=flags)
-            loss = self._rows_staged_loss(s, ptr, max_nodes)
-            s_flat = s
-        elif not training:
-            if mincut:  # out-degrees and |S_i|^2 ride along with T = A S
-                t, deg, q = K.spmm_csr(row_ptr, ei, w_used, n, s, want_stats=True)
-            else:       # mode 2: the entropy sum over S rides along
-                t, ent_part = K.spmm_csr(row_ptr, ei, w_used, n, s, want_stats="entropy")
-            raw, x_pool, gram, adj_pool = K.segment_gemm_tn3(s, [t, x, s], ptr, max_nodes, transpose0=transposed,
-                                                             post_flags=flags)
-            if mincut:
-                if transposed:  # in-degrees: sum_j indeg_j q_j = sum_e w_e q[col_e]
-                    both = K.mincut_terms_fused(raw, gram, None, q, ptr=ptr, want_means=True,
-                                                edges=(row_ptr, ei, w_used))[3]
-                else:
-                    both = K.mincut_terms_fused(raw, gram, deg, q, ptr=ptr, want_means=True)[3]
-            else:
-                both = K.diffpool_unbatched_tail(raw, gram, s, sw2, scales[0], scales[1], ent_partials=ent_part)
-            s_flat = s
+            sym = K.AdjSymmetry.of_edge_list(edge_index, edge_weight, ei, w_used, row_ptr, x.size(0))
+            s, x_pool, _, adj_pool, both = Fn.pool_unbatched(x, weight, bias, s, ei, w_used, row_ptr, ptr, batch, max_nodes,
+                                                             flags, mode, scales, sw2, sym, transposed)
+            return so, s, x_pool, adj_pool, both
+        if mode == 0:  # T = A S, S^T [T | X] with the post-processing, the pooler's loss on the un-padded S
+            t = K.spmm_csr(row_ptr, ei, w_used, x.size(0), s)
+            _, x_pool, adj_pool = K.segment_gemm_tn3(s, [t, x], ptr, max_nodes, transpose0=transposed, post_flags=flags)
+            return so, s, x_pool, adj_pool, self._rows_staged_loss(s, ptr, max_nodes)
+        out = K.pool_rows_forward(x, weight, bias, s, *args)
+        if out is None:  # kernels.pool_rows, with Select in front of the composed operators where it has not run yet
+            if s is None:  # (not the one-call entry's case after all: the selector runs on its own, as the module has it)
+                so, s = self._rows_select(x, batch, batched_out)
+            out = K.pool_rows_forward_composed(x, None, None, s, *args)
+        return so, out["s"], out["x_pool"], out["adj_pool"], out["both"] if mode == 1 else out["lossv"]
+
+    def _rows_hand_out(self, sel, so, s_flat, x_pool, adj_pool, both_or_loss, mode, batch, batched_out, info, nb, max_nodes):
+        """The route's ``_Pooled``: S as the mode hands it out, the loss dict, the pooled batch vector."""
         if batched_out:  # S as the batched mode hands it out: padded [B,Nmax,K] + the node mask (differentiable view of S)
-            if n == nb * max_nodes:  # graphs of one size: the padded form is a view, the mask a constant
-                s_pad = s_flat.view(nb, max_nodes, k)
-                mask = torch.ones(nb, max_nodes, dtype=torch.bool, device=x.device)  # (a tensor of the caller's own)
+            if s_flat.size(0) == nb * max_nodes:  # graphs of one size: the padded form is a view, the mask a constant
+                s_pad = s_flat.view(nb, max_nodes, s_flat.size(1))
+                mask = torch.ones(nb, max_nodes, dtype=torch.bool, device=s_flat.device)  # (a tensor of the caller's own)
             else:
                 from ..src import to_dense_batch
                 s_pad, mask = to_dense_batch(s_flat, batch, max_nodes, nb)
@@ -910,8 +920,7 @@ class _DenseMLPPooling(DenseSRCPooling):
                 so._graph_sizes = info.sizes
         elif so is None:
             so = SelectOutput(s=s_flat, s_inv_op=sel.s_inv_op, batch=batch)
-        if not staged:
-            loss = self._pair_loss(both)
+        loss = both_or_loss if mode == 0 else self._pair_loss(both_or_loss)
         batch_pool = self.reducer.reduce_batch(so, batch if batch is not None else so.batch)
         return _Pooled(so, x_pool, None, adj_pool, batch_pool=batch_pool, loss=loss)
 
