@@ -1,5 +1,6 @@
 # a build of the library with other GEMM schedule constants, for same-box A/B (tools/c2_ab.sh):
 #   bash tools/build_gemm_variant.sh NAME -DTGP_LOAD_AT=2 -DTGP_STORE_AT=10   ->  torch-geometric-pool_amd/lib/libtgp_hip_NAME.so
+#   bash tools/build_gemm_variant.sh xfold -DTGP_FOLD_X_LATE=0                ->  the folded tail with its X-part (S^T X slabs), as before profiles/c2_xpool.md
 set -e
 cd "$(dirname "$0")/../torch-geometric-pool_amd/csrc"
 name=$1; shift

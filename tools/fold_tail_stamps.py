@@ -15,6 +15,10 @@ tail's first MFMA (8), at three points of the tail (9, 10, 11) and at the end (3
 With block-order slabs (TGP_FOLD_BLOCKS = 1, the shipped form) nothing is parked: slot 10 is the same point of the X-part
 (12 of its 32 k-groups done, the four S^T U block stores issued behind the first four) and slot 11 its end.
 
+Without the X-part (TGP_FOLD_X_LATE = 1, the shipped form: S^T X is formed by post_rows_kernel<true>) slot 9 is the end
+of the tail's MFMAs, slot 10 the four S^T U block stores issued, slot 11 the column-sum partials added lane to lane, and
+the end follows the partials' one barrier and the ordered add.
+
 The stamps slow the launch, so the figures are shares; median and p10..p90 over the workgroups, in us."""
 import ctypes
 import os

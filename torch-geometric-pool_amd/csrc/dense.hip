@@ -335,8 +335,9 @@ static int dense_pool_impl(const float* S, const float* A, const float* X, int64
 // over N into slabs, and the slab combine + post-processing.  `gram` (optional, [B,K,K]): S^T S rides along as a third
 // right-hand side of the second product (MinCut's orthogonality loss and DiffPool's link-loss gradient need it).
 // keep_u = false (the caller has no use for U; no gram): where the zero-skipping U = A S kernel would run one column tile
-// (K <= 128) the second product is folded into it -- each workgroup leaves S_r^T [U_r | X_r] over its own 128 rows as one
-// of N / 128 partial slabs (launch_gemm_fold), U is never written, and post_rows_kernel adds the slabs up: two launches.
+// (K <= 128) the second product is folded into it -- each workgroup leaves S_r^T U_r over its own 128 rows as one of
+// N / 128 partial slabs (launch_gemm_fold), U is never written, and post_rows_kernel adds the slabs up and forms S^T X
+// from S and X (TGP_FOLD_X_LATE; off: S_r^T [U_r | X_r] and x slabs): two launches.
 static int dense_pool_tiled(const float* S, const float* A, const float* X, int64_t B, int64_t N, int64_t K, int64_t F,
                             int flags, float eps, float* x_pool, float* adj_raw, float* adj_pool, float* U, int64_t ldu,
                             float* gram, const DensePlan& p, Carver& cv, hipStream_t stream, bool keep_u) {
@@ -370,7 +371,12 @@ static int dense_pool_tiled(const float* S, const float* A, const float* X, int6
       r.colsum = (flags & TGP_DEGREE_NORM) ? colpart : nullptr; r.tiles_m = 1;
       r.K = static_cast<int>(K); r.flags = flags; r.eps = eps; r.raw = adj_raw; r.dst = adj_pool;
       if (want_x) {
+#if TGP_FOLD_X_LATE
+        // (no x slabs on this route: the post workgroups form S^T X from S and X, tile by tile)
+        r.xl_S = S; r.xl_X = X; r.xl_ldx = F; r.xl_sx = N * F; r.xl_N = static_cast<int>(N);
+#else
         r.xslab = xslab; r.xs_split = x_slab; r.xs_batch = fold * x_slab;
+#endif
         r.F = static_cast<int>(F); r.x_pool = x_pool;
       }
       const unsigned grid = static_cast<unsigned>(B * ((K + PR_ROWS - 1) / PR_ROWS));

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_mfma.h"  // TGP_FOLD_X_LATE
 
 namespace tgp {
 
@@ -459,6 +460,11 @@ struct PostRowsArgs {
   // r6 (training step): workgroups >= main_blocks add up a second slab set of the same shape (S^T S) into `gram`,
   // no post-processing
   int main_blocks; const float* gslab; float* gram;
+#if TGP_FOLD_X_LATE
+  // post_rows_kernel<true>: no x slabs; x_pool = S^T X is formed from S [B][N][K] and X [B][N][F] (xl_ldx, xl_sx: row and
+  // batch stride of X) in this launch
+  const float* xl_S; const float* xl_X; long xl_ldx, xl_sx; int xl_N;
+#endif
 };
 
 constexpr int PR_ROWS = 16;
@@ -472,6 +478,133 @@ template <bool BLOCKS>
 __global__ __launch_bounds__(512) void post_rows_kernel(PostRowsArgs p) {
   __shared__ float s_d[1024];
   if constexpr (BLOCKS) {
+#if TGP_FOLD_X_LATE
+    // x_pool rows i0 .. i0 + 15 = S[b][:, i0 .. i0 + 15]^T X[b] are formed here: the first launch multiplies S^T U only
+    // and leaves no x slabs.  The bits are those of its former X-part: per 128-row tile t of N and 16 x 16 block one chain
+    // of 32 v_mfma_f32_16x16x4_f32 from zero, S_t^T as A and X_t as B, k-group s = rows 128 t + 4 s .. + 3 (row
+    // 4 s + lane / 16 on the lane), s ascending; rows >= N and columns >= K / F are zeros (the descriptors' range
+    // check); the tiles' partials are then added in tile order, starting from tile 0's, by the thread that owns the
+    // element.  Wave t takes tile t (splits <= 8, the waves of a workgroup) in four chains.  Which column of the block a
+    // lane's B operand stands for is free, so a lane loads 16 bytes of its X row -- columns 4 (lane % 16) .. + 3 -- and
+    // chain q multiplies component q: block q is columns {4 j + q}, and a lane's four accumulators of a row are four
+    // consecutive columns of x_pool.  The A operand is one dword per lane and k-group (16 lanes: 64 contiguous bytes of
+    // an S row), shared by the four chains.  The loop is bound by what a CU can pull out of L2 (320 KB: all of X[b] and
+    // its 16 columns of S[b]), not by the pipe (3.4 us) or by latency: sixteen waves of two chains with twice the
+    // requests in flight ran 1.6 us longer (profiles/c2_xpool.md).  XD k-groups of operands are in flight per wave, requested together with the
+    // slab values and the degree partials -- through descriptors, whose range check stands in for `sp < splits`: one
+    // round trip for everything the workgroup reads, where the selects of the slab form compiled to a branch and a wait
+    // per slab (profiles/c2_xpool.md).  Same adds, diagonal and divisions per element of A' as the slab form.
+    __shared__ __attribute__((aligned(16))) float s_px[PR_MAX_SPLITS][PR_ROWS][64];
+    typedef float xf32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned int xu32x4 __attribute__((ext_vector_type(4)));
+    constexpr int XD = 10;
+    constexpr int XOOB = static_cast<int>(0x80000000u);  // fails every range check
+    const int K = p.K, tid = threadIdx.x, kb = (K + 15) >> 4;
+    // (the block rows of a graph all read X[b] and S[b]: on one XCD, the one whose first-launch workgroups wrote the slabs)
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = bid / kb, rb = bid - b * kb, i0 = rb * PR_ROWS;
+    const bool rsl = p.flags & TGP_REMOVE_SELF_LOOPS, dn = (p.flags & TGP_DEGREE_NORM) && p.colsum;
+    const int bc = tid >> 6, lq = (tid >> 4) & 3, l15 = tid & 15;
+    const int c = 16 * bc + l15, r0 = i0 + 4 * lq;  // (K % 4 == 0: the four rows are in range together)
+    const bool mine = bc < kb && c < K && r0 < K;
+    const int F = p.x_pool ? p.F : 0;
+    const float* sb = p.slab + static_cast<long>(b) * p.s_batch;
+    const int s_split4 = static_cast<int>(p.s_split) * 4;
+    const __amdgpu_buffer_rsrc_t rsrc_sl =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sb), 0, p.splits * s_split4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_cs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(dn ? p.colsum + static_cast<long>(b) * p.splits * K : sb), 0, dn ? p.splits * K * 4 : 0, 0x00020000);
+    const int x_ld4 = static_cast<int>(p.xl_ldx) * 4, s_ld4 = K * 4;
+    const __amdgpu_buffer_rsrc_t rsrc_xx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(F ? p.xl_X + static_cast<long>(b) * p.xl_sx : sb), 0, F ? p.xl_N * x_ld4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_xs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(F ? p.xl_S + static_cast<long>(b) * p.xl_N * K : sb), 0, F ? p.xl_N * s_ld4 : 0, 0x00020000);
+    const int xt = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's tile
+    const bool xwave = F > 0 && xt < p.splits;               // (wave-uniform)
+    const int voff_xx = 4 * l15 < F ? lq * x_ld4 + 16 * l15 : XOOB;
+    const int voff_xs = i0 + l15 < K ? lq * s_ld4 + (i0 + l15) * 4 : XOOB;
+    // slab s of this block row is one run of K / 16 blocks; thread t takes the float4 at word 4 t of it
+    const int voff_sl = mine ? (rb * kb * 256 + 4 * tid) * 4 : XOOB;
+    xu32x4 v[PR_MAX_SPLITS];
+#pragma unroll
+    for (int sp = 0; sp < PR_MAX_SPLITS; ++sp) v[sp] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_sl, voff_sl, sp * s_split4, 0);
+    float pv[PR_MAX_SPLITS];  // (one degree partial per tile and column: tiles_m = 1 on this route; K <= 128 columns)
+#pragma unroll
+    for (int qq = 0; qq < PR_MAX_SPLITS; ++qq)
+      pv[qq] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc_cs, tid < K ? tid * 4 : XOOB, qq * K * 4, 0));
+    [[maybe_unused]] xu32x4 xb[XD];
+    [[maybe_unused]] float xa[XD];
+    auto x_request = [&](int s) {
+      xb[s % XD] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_xx, voff_xx, (xt * 128 + 4 * s) * x_ld4, 0);
+      xa[s % XD] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc_xs, voff_xs, (xt * 128 + 4 * s) * s_ld4, 0));
+    };
+    // (every wave: a wave without a tile, or a call without X, asks beyond the descriptors' ranges and gets zeros; behind
+    // a branch the waits for the degree partials would have to assume these requests were the last ones made)
+#pragma unroll
+    for (int s = 0; s < XD; ++s) x_request(s);
+    __builtin_amdgcn_sched_barrier(0);
+    float tv[4] = {__uint_as_float(v[0].x), __uint_as_float(v[0].y), __uint_as_float(v[0].z), __uint_as_float(v[0].w)};
+#pragma unroll
+    for (int sp = 1; sp < PR_MAX_SPLITS; ++sp)
+      if (sp < p.splits) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tv[r] = __fadd_rn(tv[r], __uint_as_float(v[sp][r]));
+      }
+    if (dn && tid < K) {
+      float cc = 0.f;  // (the partial sums already leave the diagonal out when the self loops are removed)
+#pragma unroll
+      for (int qq = 0; qq < PR_MAX_SPLITS; ++qq)
+        if (qq < p.splits) cc = __fadd_rn(cc, pv[qq]);
+      s_d[tid] = sqrtf(clamp_min(cc, p.eps));
+    }
+    if (xwave) {
+      xf32x4 xd[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xd[q][r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 32; ++s) {
+        const float a = xa[s % XD];
+        const xu32x4 bv = xb[s % XD];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xd[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, __uint_as_float(bv[q]), xd[q], 0, 0, 0);
+        if (s + XD < 32) x_request(s + XD);
+        __builtin_amdgcn_sched_barrier(0);  // (left alone the scheduler sinks the requests to their use: two in flight)
+      }
+      // tile xt's partial, row-major: a lane holds rows 4 lq + r, columns 4 (lane % 16) + q
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        *reinterpret_cast<float4*>(&s_px[xt][4 * lq + r][4 * l15]) = make_float4(xd[0][r], xd[1][r], xd[2][r], xd[3][r]);
+    }
+    float* rawb = p.raw ? p.raw + static_cast<long>(b) * K * K : nullptr;
+    float* dstb = p.dst ? p.dst + static_cast<long>(b) * K * K : nullptr;
+    __syncthreads();
+    if (mine) {
+      const float dj = dn ? s_d[c] : 1.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long off = static_cast<long>(r0 + r) * K + c;
+        if (rawb) rawb[off] = tv[r];
+        if (!dstb) continue;
+        if (rsl && r0 + r == c) tv[r] = 0.f;
+        if (dn) tv[r] = (tv[r] / dj) / s_d[r0 + r];  // (adj / d[1,K]) / d[K,1]
+        dstb[off] = tv[r];
+      }
+    }
+    if (tid < 256) {  // 16 rows x 16 vectors of x_pool: the tiles' partials in tile order, starting from tile 0's
+      const int row = tid >> 4, c4 = l15 * 4;
+      if (i0 + row < K && c4 < F) {
+        float4 xs = *reinterpret_cast<const float4*>(&s_px[0][row][c4]);
+        for (int sp = 1; sp < p.splits; ++sp) {
+          const float4 u = *reinterpret_cast<const float4*>(&s_px[sp][row][c4]);
+          xs.x = __fadd_rn(xs.x, u.x); xs.y = __fadd_rn(xs.y, u.y); xs.z = __fadd_rn(xs.z, u.z); xs.w = __fadd_rn(xs.w, u.w);
+        }
+        *reinterpret_cast<float4*>(p.x_pool + static_cast<long>(b) * K * F + static_cast<long>(i0 + row) * F + c4) = xs;
+      }
+    }
+    return;
+#else
     const int K = p.K, tid = threadIdx.x, kb = (K + 15) >> 4;
     const int b = blockIdx.x / kb, rb = blockIdx.x - b * kb, i0 = rb * PR_ROWS;
     const bool rsl = p.flags & TGP_REMOVE_SELF_LOOPS, dn = (p.flags & TGP_DEGREE_NORM) && p.colsum;
@@ -546,6 +679,7 @@ __global__ __launch_bounds__(512) void post_rows_kernel(PostRowsArgs p) {
       xo[0] = v.x; xo[F] = v.y; xo[2 * F] = v.z; xo[3 * F] = v.w;
     }
     return;
+  #endif
   }
   const int K = p.K, tid = threadIdx.x;
   const int blocks_per_graph = (K + PR_ROWS - 1) / PR_ROWS;

@@ -90,6 +90,16 @@ constexpr int LDA_ROWMAJOR = BK + 1;
 #undef TGP_FOLD_BLOCKS
 #define TGP_FOLD_BLOCKS 0
 #endif
+// TGP_FOLD_X_LATE (with TGP_FOLD_BLOCKS; profiles/c2_xpool.md): the tail multiplies S_r^T U_r only.  X_r is not requested,
+// no S^T X slabs are written, and post_rows_kernel<true> forms x_pool = S^T X from S and X itself, in the blocks, chains
+// and tile order the X-part had here.
+#ifndef TGP_FOLD_X_LATE
+#define TGP_FOLD_X_LATE 1
+#endif
+#if !TGP_FOLD_BLOCKS
+#undef TGP_FOLD_X_LATE
+#define TGP_FOLD_X_LATE 0
+#endif
 
 // One right-hand side / output pair.  A launch may carry up to three (column tiles >= tiles_n0 use the
 // second, those >= tiles_n1 the third), which lets S^T [U | X] -- and, for the training step, S^T [U | X | S] --
@@ -135,7 +145,8 @@ struct GemmArgs {
   // MODE 4 (MODE 3 + the second product folded in, see launch_gemm_fold): rhs[0].C is the slab set [batches][tiles_m]
   // [Nc][Nc] of S_r^T U_r (row tile r of batch b at b * sC + r * sCsplit; U itself is not stored), rhs[1] (Bm optional) is
   // X with its slab set [batches][tiles_m][Nc][rhs[1].Nc], colsum is [batches][tiles_m][Nc].  Under TGP_FOLD_BLOCKS a
-  // slab is in block order (fold_slab_floats) and ldc is not used
+  // slab is in block order (fold_slab_floats) and ldc is not used.  Under TGP_FOLD_X_LATE the kernel reads nothing of rhs[1]
+  // and writes no X slabs (launch_gemm_fold still checks it: the route's conditions are the same)
 };
 
 // Row of a [rows][BK+1] LDS tile served by slot t = 8*g + r (8 lanes per slot, slot = one 128-byte row segment).
@@ -841,8 +852,10 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       const int voff_x = (RX.Bm && (tid & 15) * 4 < RX.Nc) ? (tid >> 4) * ldx4 + (tid & 15) * 16 : OOB;
 #pragma unroll
       for (int i = 0; i < 4; ++i) fs[i] = buf_ld4(rsrc_b, voff_b[0], (m0 + 32 * i) * static_cast<int>(ldb) * 4);
+      if constexpr (!TGP_FOLD_X_LATE) {  // (X_LATE: the second launch reads X itself)
 #pragma unroll
       for (int i = 0; i < 2; ++i) fx[i] = buf_ld4(rsrc_x, voff_x, (m0 + 64 * i) * ldx4);
+      }
     }
   };
   int t = 0;
@@ -930,10 +943,12 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
       const int k = (tid >> 5) + 32 * i;
       *reinterpret_cast<float4*>(Sf + k * BN + (((tid & 31) * 4) ^ ((k & 3) << 4))) = fs[i];
     }
+    if constexpr (!TGP_FOLD_X_LATE) {  // (X_LATE: columns 128 .. 191 of the [U_r | X_r] rows stay free for the whole tail)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int k = (tid >> 4) + 64 * i;
       *reinterpret_cast<float4*>(UXf + k * 192 + ((BN + (tid & 15) * 4) ^ ((k & 3) << 4))) = fx[i];
+    }
     }
     // (workgroup-uniform) no MFMA ran in the k-loop: acc is +0 everywhere, so U = 0 + sacc goes to LDS directly, each
     // element from the lane that owns it in the walk -- the same add as below (a -0 sum becomes +0 there too), without
@@ -1012,18 +1027,37 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
 #pragma unroll
       for (int s = 0; s < 32; ++s) {
         if (s + 1 < 32) fetch_u(s + 1);
-        else fetch_x(0);
+        else if constexpr (!TGP_FOLD_X_LATE) fetch_x(0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int i = 0; i < 2; ++i)
             d[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s & 1][i], b[s & 1][j], d[i][j], 0, 0, 0);
         if (s + 1 < 32) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // ds_reads of the next group
-        else __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+        else if constexpr (!TGP_FOLD_X_LATE) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                   // 4 x MFMA
         __builtin_amdgcn_sched_barrier(0);
       }
       TGP_STAMP(9);
+      if constexpr (TGP_FOLD_X_LATE) {
+        // No X-part: the four S^T U blocks leave at once, as the same write-through block stores (fold_slab_floats: block
+        // (2 wm + i, 2 wn + j), blocks wholly beyond Nc fail the descriptor's range check), with the partials' adds
+        // behind them.
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        constexpr int WT = TGP_FOLD_SLAB_WT ? 16 : 0;  // (aux bit 4: sc1)
+        const int kb = (Nc + 15) >> 4;
+        float* Ca = R.C + static_cast<long>(batch) * R.sC + static_cast<long>(tm) * R.sCsplit;
+        const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(Ca, 0, kb * kb * 1024, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int br = 2 * wm + i, bc = 2 * wn + j;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, d[i][j]), rsrc_c,
+                                                   (br < kb && bc < kb) ? (br * kb + bc) * 1024 + lane * 16 : OOB, 0, WT);
+          }
+        TGP_STAMP(10);
+      }
       // column sums of S^T U, the 16-row partial of block row 2 wm + i: a lane holds rows 4 lq + r of its column, so the
       // lanes lq = 0 add their four rows to 0 and hand the sum to lq = 1, and so on -- the sixteen adds in row order;
       // the lanes lq = 3 end up with the partial (rows >= Nc and, under colsum_skip_diag, the diagonal count as 0)
@@ -1046,6 +1080,30 @@ __global__ __launch_bounds__(BM * 2 * WN) void gemm_f32_mfma_kernel(GemmArgs g) 
             }
             cpart[i][j] = cs;
           }
+      }
+      if constexpr (TGP_FOLD_X_LATE) {
+        // The eight 16-row partials per column go to the words X_r had -- columns 128 .. 191 of the operand rows, which
+        // nothing reads or writes in this tail: partial q of column c at row 2 q + c / 64 -- so they do not wait for S_r
+        // to die: one barrier, then the same ordered add as behind the X-part.
+        TGP_STAMP(11);
+        if (g.colsum) {  // (workgroup-uniform)
+          auto part_at = [&](int q, int c) { return UXf + (2 * q + (c >> 6)) * 192 + BN + (c & 63); };
+          if (lq == 3) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+              for (int j = 0; j < 2; ++j) *part_at(2 * wm + i, wn * 32 + 16 * j + l15) = cpart[i][j];
+          }
+          __syncthreads();
+          if (tid < Nc) {
+            float tot = 0.f;
+#pragma unroll
+            for (int qq = 0; qq < 8; ++qq) tot = __fadd_rn(tot, *part_at(qq, tid));
+            g.colsum[(static_cast<long>(batch) * g.tiles_m + tm) * Nc + tid] = tot;
+          }
+        }
+        TGP_STAMP(3);
+        return;
       }
       if constexpr (TGP_FOLD_BLOCKS) {
         // Block-order slabs (fold_slab_floats): d[i][j] is block (2 wm + i, 2 wn + j) of S^T U and d[i][2] block
