@@ -1884,6 +1884,39 @@ int tgp_dense_pool_adj_grad_small_f32(const float* S, const float* A, const floa
                                       const float* g_link, const float* link_loss, float link_scale, float loss_eps,
                                       int64_t B, int64_t N, int64_t K, float* dA, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * NMF pooling past the LDS limit of tgp_nmf_factorize_f32, csrc/nmf_rows.hip: the same algorithm, special cases, default
+ * init, stopping rule and outputs (see there), one workgroup of 1024 threads per graph of graph_list [num_listed], and no
+ * dense adjacency.  A row of A is the node's by-source group (grp_ptr, grp_perm, dst), a row of A^T its by-destination
+ * group (dgrp_ptr [N + 1], dgrp_perm [E] or NULL, src [E]); an entry is max(w_e, 0).  That is the dense matrix only for a
+ * COALESCED list, which the workgroup checks first: every by-source group strictly ascending in destination, every
+ * by-destination group strictly ascending in source, and the graph's members (graph_perm) one run of consecutive node
+ * indices.  Otherwise it sets status bit 3 (8, "not coalesced") and leaves the graph unwritten: the caller takes another
+ * route for it.  Bits 0 and 1 are those of tgp_nmf_factorize_f32 (an entry of graph_list outside 0 .. G - 1, and a group
+ * entry whose near end is not its node, are bit 0; bit 1 is checked per entry); bit 2 is never set: there is no node
+ * limit below the int32 index.  Nothing out of range is dereferenced.
+ *   Sums: P[i, :] over the row's entries in ascending order, the gradient in ascending r, fp32, no fused multiply-add;
+ *   Gram = F^T F on the fp32 matrix cores, the 16 waves' contiguous row slices added in ascending wave order; the
+ *   violations a thread's rows (i = tid, tid + 1024, ..) ascending, an xor butterfly per wave, the waves ascending.  No
+ *   float atomics: the same bits on every call.
+ *   Home of the factors: LDS, with the frame (floats) Gram [32][32], four partial tiles [4][32][32], 16 fold words, 4
+ *   control words, then W and H^T [n][K | 1] each, when that fits 160 KiB: n <= tgp_nmfrows_lds_nodes(K) (0 for a K the
+ *   kernel does not take); else, or with home = 1, the graph's rows of w_out / ht_out themselves.  Both are therefore
+ *   REQUIRED here ([N, K]; written for factorised graphs only) and must not alias w0 / h0t.
+ * TGP_ERR_INVALID: a NULL input or output, sizes below zero, K < 1, K > tgp_nmf_max_k(), out_cols < 1, max_iter < 1, tol < 0
+ * or NaN, home outside {0, 1}, one of w0 / h0t without the other; TGP_ERR_RANGE: a size beyond the int32 index.  All are
+ * found before any HIP call; G, N or num_listed == 0 returns TGP_OK.
+ * ---------------------------------------------------------------------------------- */
+int tgp_nmfrows_lds_nodes(int64_t K);
+int tgp_nmfrows_factorize_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                              const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* graph_ptr,
+                              const int32_t* graph_perm, int64_t N, int64_t E, int64_t G, int64_t K, int64_t out_cols,
+                              int64_t seed, float tol, int64_t max_iter, const float* w0 /* NULL ok */,
+                              const float* h0t /* NULL ok */, float* s, float* w_out, float* ht_out,
+                              int32_t* iters /* NULL ok */, float* violation_ratio /* NULL ok */, int32_t* status,
+                              const int32_t* dgrp_ptr, const int32_t* dgrp_perm /* NULL ok */, const int64_t* src,
+                              const int32_t* graph_list, int64_t num_listed, int64_t home, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

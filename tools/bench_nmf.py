@@ -11,7 +11,10 @@ Workloads (F = 32):
   small  2048 graphs of 20-60 nodes: every graph fits the kernel.  ``--fixed-iters T`` runs ``tol=0, max_iter=T`` to
          price an iteration.  The composed form and scikit-learn are timed on the first ``--subset`` graphs only (they
          take a host wait per iteration and per graph) and reported per graph, next to the kernel's time per graph.
-  large  one graph of 512 nodes: past the kernel's node limit, so BOTH sides are the composed route
+  large  one graph of 512 nodes: past the LDS kernel's node limit, so ``select`` is the row-walking kernel
+         (csrc/nmf_rows.hip) next to the composed form and scikit-learn
+  mid    256 graphs of 200-600 nodes: the row-walking kernel, one workgroup per graph (use ``--k 8`` and ``--k 32``)
+  huge   one graph of 4096 nodes (use ``--k 32``): past ``nmf_rows_lds_nodes``, the factors live in HBM
 Prints one JSON line.
 """
 import argparse
@@ -26,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("small", "large"), default="small")
+    ap.add_argument("--workload", choices=("small", "large", "mid", "huge"), default="small")
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--fixed-iters", type=int, default=0)
     ap.add_argument("--subset", type=int, default=16)
@@ -45,7 +48,8 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     k, F = a.k, 32
-    sizes = torch.randint(20, 61, (2048,), generator=g).tolist() if a.workload == "small" else [512]
+    sizes = {"small": lambda: torch.randint(20, 61, (2048,), generator=g).tolist(), "large": lambda: [512],
+             "mid": lambda: torch.randint(200, 601, (256,), generator=g).tolist(), "huge": lambda: [4096]}[a.workload]()
     eis, ews, bs, off = [], [], [], 0
     for gi, n in enumerate(sizes):
         up = torch.triu(torch.rand(n, n, generator=g) < (4.0 if n < 100 else 8.0) / n, 1)
@@ -133,8 +137,10 @@ def main():
     limit = kernels.nmf_max_nodes()
     out = {"workload": a.workload, "num_graphs": len(sizes), "num_nodes": n, "num_edges": int(ei.size(1)), "k": k,
            "features": F, "tol": kw["tol"], "max_iter": kw["max_iter"], "node_limit": limit, "k_limit": kernels.nmf_max_k(),
-           "select_route": "composed (over the limit) on both sides" if max(sizes) > limit or k > kernels.nmf_max_k()
-           else "kernel", "iters_mean": round(float(iters.mean()), 2), "iters_max": int(iters.max()),
+           "rows_lds_nodes": kernels.nmf_rows_lds_nodes(k) if k <= kernels.nmf_max_k() else 0,
+           "select_route": "composed (K over the limit) on both sides" if k > kernels.nmf_max_k() else
+           "kernel" if max(sizes) <= limit else "row-walking kernel, factors in " +
+           ("LDS" if max(sizes) <= kernels.nmf_rows_lds_nodes(k) else "HBM for the largest graphs"), "iters_mean": round(float(iters.mean()), 2), "iters_max": int(iters.max()),
            "subset_graphs": sub, "windows": a.windows, "steps_per_window": a.steps,
            "native_vs_composed_max_abs_s": err}
     for name in runs:

@@ -423,6 +423,10 @@ SIGNATURES = {
     "tgp_sep_max_nodes": (_c_int, []),
     "tgp_sep_select_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
                                     _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "tgp_nmfrows_lds_nodes": (_c_int, [_c_i64]),
+    "tgp_nmfrows_factorize_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                           _c_i64, _c_f, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                           _c_p, _c_p, _c_i64, _c_i64, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -4662,10 +4662,13 @@ def nmf_init(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gi
 
 def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor], gid: Tensor, graphs: AssignIndex,
                   k: int, out_cols: int, max_n: int, seed: int = 0, tol: float = 1e-4, max_iter: int = 5000,
-                  init: Optional[Tuple[Tensor, Tensor]] = None, want_factors: bool = False) -> dict:
+                  init: Optional[Tuple[Tensor, Tensor]] = None, want_factors: bool = False,
+                  status: Optional[Tensor] = None) -> dict:
     """One launch of the per-graph NMF kernel: ``s`` [N, out_cols] (softmax of H^T, zero columns behind ``ka``; zeros for
     a flagged graph), ``status`` (a host int, bits ``NMF_*``: the call's one host wait), ``iters`` [G] int32 and
-    ``ratio`` [G], and with ``want_factors`` the raw ``w`` / ``ht`` [N, K].  ``init``: (W0, H0^T) [N, K] node-major."""
+    ``ratio`` [G], and with ``want_factors`` the raw ``w`` / ``ht`` [N, K].  ``init``: (W0, H0^T) [N, K] node-major.
+    ``status`` given (one zeroed int32 device word): it collects the bits, nothing is read back here and
+    ``out["status"]`` is that tensor -- a caller with a second launch behind this one waits once for both."""
     dev = N.require_device(dst, edge_weight, gid, by_src.row_ptr, graphs.row_ptr)
     dst, ew, n, E = _nmf_args("nmf_factorize", by_src, dst, edge_weight, gid, graphs)
     Kc, G = int(k), graphs.num_targets
@@ -4678,15 +4681,73 @@ def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor
     fac = torch.zeros(2, n, max(Kc, 1), dtype=torch.float32, device=dev) if want_factors else None
     iters = torch.zeros(G, dtype=torch.int32, device=dev)
     ratio = torch.zeros(G, dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
     _checked(N.lib().tgp_nmf_factorize_f32, *by_src.walk(dst, E), N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr),
              N.ptr(graphs.perm), n, E, G, Kc, int(out_cols), int(max_n), int(seed), float(tol), int(max_iter),
              N.ptr(w0), N.ptr(h0t), N.ptr(s), N.ptr(fac[0]) if want_factors else None,
              N.ptr(fac[1]) if want_factors else None, N.ptr(iters), N.ptr(ratio), N.ptr(status), N.stream_ptr(dev))
-    out = {"s": s, "status": int(status.item()), "iters": iters, "ratio": ratio}
+    out = {"s": s, "status": int(status.item()) if own_status else status, "iters": iters, "ratio": ratio}
     if want_factors:
         out["w"], out["ht"] = fac[0], fac[1]
     return out
+
+
+NMF_NOT_COALESCED = 8  # status bit of tgp_nmfrows_factorize_f32: the graph is declined, another route takes it
+_NMF_HOMES = {"auto": 0, "hbm": 1}
+
+
+def nmf_rows_lds_nodes(k: int) -> int:
+    """Nodes of the largest graph whose factors the row-walking NMF kernel keeps in LDS at this ``k``; a larger graph's
+    factors live in HBM."""
+    return int(N.lib().tgp_nmfrows_lds_nodes(int(k)))
+
+
+def nmf_rows_factorize(by_src: AssignIndex, by_dst: AssignIndex, src: Tensor, dst: Tensor, edge_weight: Optional[Tensor],
+                       gid: Tensor, graphs: AssignIndex, graph_list: Tensor, k: int, out_cols: int, seed: int = 0,
+                       tol: float = 1e-4, max_iter: int = 5000, init: Optional[Tuple[Tensor, Tensor]] = None, *,
+                       home: str = "auto", s: Optional[Tensor] = None, w: Optional[Tensor] = None,
+                       ht: Optional[Tensor] = None, iters: Optional[Tensor] = None, ratio: Optional[Tensor] = None,
+                       status: Optional[Tensor] = None) -> dict:
+    """One launch of the row-walking NMF kernel (csrc/nmf_rows.hip) over the graphs of ``graph_list`` (int32): no dense
+    adjacency, no node limit.  The result dict of :func:`nmf_factorize`, ``w`` / ``ht`` always among it (they are the
+    factors' home for a graph past :func:`nmf_rows_lds_nodes`, or with ``home="hbm"``).  ``s``, ``w``, ``ht``, ``iters``,
+    ``ratio``, ``status`` (float32 / int32, contiguous) are written into when given; with ``status`` given nothing is read
+    back here and ``out["status"]`` is that tensor: the caller owns the host wait.  A graph whose list is not coalesced
+    sets ``NMF_NOT_COALESCED`` and is left unwritten."""
+    dev = N.require_device(dst, src, edge_weight, gid, by_src.row_ptr, by_dst.row_ptr, graphs.row_ptr, graph_list)
+    dst, ew, n, E = _nmf_args("nmf_rows_factorize", by_src, dst, edge_weight, gid, graphs)
+    src, n2, E2 = _asap_group("nmf_rows_factorize", by_dst, src)
+    if home not in _NMF_HOMES:
+        raise ValueError(f"nmf_rows_factorize: home is 'auto' or 'hbm', got {home!r}")
+    if n2 != n or graph_list.dtype != torch.int32 or not graph_list.is_contiguous():
+        raise ValueError("nmf_rows_factorize: both edge groups over the same nodes and a contiguous int32 graph list")
+    Kc, G = int(k), graphs.num_targets
+    w0 = h0t = None
+    if init is not None:
+        w0, h0t = N.f32c(init[0]), N.f32c(init[1])
+        if tuple(w0.shape) != (n, Kc) or tuple(h0t.shape) != (n, Kc):
+            raise ValueError(f"nmf_rows_factorize: an explicit init is (W0, H0^T), both [{n}, {Kc}]")
+
+    def buf(t, shape, dtype):
+        if t is None:
+            return torch.zeros(*shape, dtype=dtype, device=dev)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"nmf_rows_factorize: an output given must be a contiguous {dtype} {list(shape)}")
+        return t
+
+    s = buf(s, (n, int(out_cols)), torch.float32)
+    w, ht = buf(w, (n, max(Kc, 1)), torch.float32), buf(ht, (n, max(Kc, 1)), torch.float32)
+    iters, ratio = buf(iters, (G,), torch.int32), buf(ratio, (G,), torch.float32)
+    own_status = status is None
+    status = buf(status, (1,), torch.int32)
+    _checked(N.lib().tgp_nmfrows_factorize_f32, *by_src.walk(dst, E), N.ptr(ew), N.ptr(gid), N.ptr(graphs.row_ptr),
+             N.ptr(graphs.perm), n, E, G, Kc, int(out_cols), int(seed), float(tol), int(max_iter), N.ptr(w0), N.ptr(h0t),
+             N.ptr(s), N.ptr(w), N.ptr(ht), N.ptr(iters), N.ptr(ratio), N.ptr(status), *by_dst.walk(src, E),
+             N.ptr(graph_list) if graph_list.numel() else None, graph_list.numel(), _NMF_HOMES[home], N.stream_ptr(dev))
+    return {"s": s, "status": int(status.item()) if own_status else status, "iters": iters, "ratio": ratio, "w": w,
+            "ht": ht}
 
 
 # ------------------------------------------------------------------------------------------------ SEP (csrc/sep_select.hip)

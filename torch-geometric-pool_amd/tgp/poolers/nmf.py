@@ -6,11 +6,14 @@ The reference loops over the graphs in Python, copies each adjacency to the host
 ``non_negative_factorization(adj, n_components=ka, init="random", max_iter=5000)``: the coordinate-descent solver
 (``shuffle=False``, ``tol=1e-4``, no regularisation).  Here the same iteration runs on the device.
 
-Routes.  Device float32 inputs whose graphs have at most ``kernels.nmf_max_nodes()`` nodes, with ``k`` at
-most ``kernels.nmf_max_k()``, take ``tgp_nmf_factorize_f32``: one workgroup per graph, all graphs in one launch, one host
-wait per call (the status word).  Graphs past the node limit, a ``k`` past its limit and float64 weights take the same
-algorithm composed from torch operators on the device, graph by graph, with the same init; a batch may mix both.  Host
-tensors are refused: there is no CPU fallback.
+Routes.  Device float32 inputs with ``k`` at most ``kernels.nmf_max_k()`` run natively, one workgroup per
+graph, one host wait per call (the status word both launches share).  Graphs of at most ``kernels.nmf_max_nodes()`` nodes
+take ``tgp_nmf_factorize_f32`` (the dense adjacency in LDS); larger ones take ``tgp_nmfrows_factorize_f32`` on the same
+stream, which walks the edge groups and never forms the adjacency (factors in LDS up to
+``kernels.nmf_rows_lds_nodes(k)`` nodes, in HBM past it).  That kernel declines a graph whose edge list is not coalesced;
+such a graph, a ``k`` past its limit and float64 weights take the same algorithm composed from torch operators on the
+device, graph by graph, with the same init; a batch may mix all routes.  Host tensors are refused: there is no CPU
+fallback.
 
 Init.  The reference's init is random and unseeded: its output differs from run to run and cannot be reproduced.  The
 rules that do not depend on chance are kept (no rows for an empty graph, the identity for ``n > 1 and ka >= n``, a
@@ -166,25 +169,36 @@ def nmf_select(edge_index, k: int, edge_weight: Optional[Tensor] = None, batch: 
     factorised = [g for g, m in enumerate(sizes) if 1 < Kc < m]
     native = not f64 and Kc <= max_k
     if native:
-        todo = [g for g in factorised if sizes[g] > max_n]
+        rows = [g for g in factorised if sizes[g] > max_n]  # past the LDS kernel: the row-walking kernel, same stream
         by_src = K.sag_edge_group(ei, n, by_destination=False)  # (remembered per edge_index tensor)
         gid = gb.to(torch.int32)
         # the inverted index of a sorted batch vector: its CSR offsets and the identity (what tgp_assign_index_build gives)
         graphs = K.AssignIndex(ptr32, torch.arange(n, dtype=torch.int32, device=dev), n, B)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)  # one word for both launches: ONE host wait
         out = K.nmf_factorize(by_src, ei[1], ew, gid, graphs, Kc, width, min(max(sizes), max_n), seed, tol, max_iter, init,
-                              return_factors)
-        st = out["status"]
+                              return_factors, status=status)
+        s = out["s"]
+        wf, htf = (out["w"], out["ht"]) if return_factors else (None, None)
+        iters, ratio = out["iters"], out["ratio"]
+        if rows:
+            by_dst = K.sag_edge_group(ei, n, by_destination=True)
+            listed = torch.tensor(rows, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            home = (wf, htf) if return_factors else torch.zeros(2, n, Kc, dtype=torch.float32, device=dev).unbind(0)
+            K.nmf_rows_factorize(by_src, by_dst, ei[0], ei[1], ew, gid, graphs, listed, Kc, width, seed, tol, max_iter,
+                                 init, s=s, w=home[0], ht=home[1], iters=iters, ratio=ratio, status=status)
+        st = int(status.item())
         if st & K.NMF_BAD_INPUT:
             raise ValueError("nmf_select: an index outside its table (an edge endpoint or edge position out of range, a "
                              "node outside its graph, or an edge whose endpoints lie in two graphs); nothing out of "
                              "range was read")
         if st & K.NMF_NON_FINITE:
             raise ValueError("nmf_select: the adjacency contains NaN or infinity")
-        s = out["s"]
-        wf, htf = (out["w"], out["ht"]) if return_factors else (None, None)
-        iters, ratio = out["iters"], out["ratio"]
+        todo = []
+        if st & K.NMF_NOT_COALESCED:  # a declined graph was left unwritten: its iteration count is still 0
+            stopped = iters.cpu()
+            todo = [g for g in rows if int(stopped[g]) == 0]
         # a graph past the node limit that needs no factorisation was flagged too: it is written below
-        special = [g for g, m in enumerate(sizes) if m > max_n and g not in todo]
+        special = [g for g, m in enumerate(sizes) if m > max_n and g not in rows]
     else:
         todo, special = factorised, [g for g in range(B) if g not in factorised]
         s = torch.zeros(n, width, dtype=out_dtype, device=dev)
