@@ -1686,6 +1686,11 @@ int tgp_maxcut_assign_round_i32(const int32_t* grp_ptr, const int32_t* grp_perm 
  * TGP_ERR_INVALID: a NULL input or output, an input given as the output, sizes below zero, H < 1, ldx < F, max_m
  * outside its range; TGP_ERR_RANGE: N, E, G or F beyond the int32 index.  All are found before any HIP call.
  * ---------------------------------------------------------------------------------- */
+enum tgp_eigenpool_status { /* bits of tgp_eigenpool_modes_f32's *status */
+  TGP_EIG_BAD_INPUT = 1,    /* an index outside its table */
+  TGP_EIG_ASYMMETRIC = 2,   /* a group whose induced adjacency is not symmetric: nothing written for it */
+  TGP_EIG_OVER_LIMIT = 4    /* a group larger than max_m: nothing written for it */
+};
 int tgp_eigenpool_max_group_nodes(void);
 int tgp_eigenpool_modes_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
                             const float* edge_weight /* NULL ok */, const int32_t* gid, const int32_t* theta_ptr,
@@ -1728,6 +1733,13 @@ int tgp_eigenpool_lift_f32(const float* theta_modes, const int32_t* gid, const f
  * outside its range, one of w0 / h0t without the other; TGP_ERR_RANGE: a size beyond the int32 index.  All are found
  * before any HIP call.
  * ---------------------------------------------------------------------------------- */
+enum tgp_nmf_status {        /* bits of *status of tgp_nmf_init_f32, tgp_nmf_factorize_f32 and tgp_nmfrows_factorize_f32 */
+  TGP_NMF_BAD_INPUT = 1,     /* an index outside its table, an edge across two graphs */
+  TGP_NMF_NON_FINITE = 2,    /* a NaN or infinite entry of the clamped adjacency */
+  TGP_NMF_OVER_LIMIT = 4,    /* a graph of more than max_n nodes, or K > tgp_nmf_max_k() */
+  TGP_NMF_NOT_COALESCED = 8  /* tgp_nmfrows_factorize_f32 alone: a group that does not strictly ascend, or members that
+                                are not one run; the graph is declined and the caller takes another route for it */
+};
 int tgp_nmf_max_nodes(void);
 int tgp_nmf_max_k(void);
 int tgp_nmf_init_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
@@ -1769,6 +1781,11 @@ int tgp_nmf_factorize_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NUL
  * TGP_ERR_RANGE: a size (or N x max_n) beyond the int32 index; TGP_ERR_WORKSPACE: ws too small.  All are found before
  * any HIP call.
  * ---------------------------------------------------------------------------------- */
+enum tgp_pan_status {      /* bits of *status of the tgp_pan_met_* entries */
+  TGP_PAN_BAD_INPUT = 1,   /* an index outside its table */
+  TGP_PAN_CROSS_GRAPH = 2, /* an edge whose endpoints lie in two graphs */
+  TGP_PAN_OVER_LIMIT = 4   /* a graph of more than max_n nodes */
+};
 int tgp_pan_max_graph_nodes(void);
 size_t tgp_pan_met_workspace_bytes(int64_t N);
 int tgp_pan_met_count(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
@@ -1844,6 +1861,11 @@ int tgp_gtv_edge_bwd_nodes_f32(const float* h, const float* g, int64_t nodes, in
  * TGP_ERR_INVALID: a NULL pointer, a negative size, max_n outside its range; TGP_ERR_RANGE: N, E or G >= 2^31.  All are
  * found before any HIP call.
  * ---------------------------------------------------------------------------------- */
+enum tgp_sep_status {     /* bits of words[0] of tgp_sep_select_f32 */
+  TGP_SEP_BAD_INPUT = 1,  /* an index outside its table, an edge across two graphs */
+  TGP_SEP_BAD_WEIGHT = 2, /* a non-finite or negative summed weight */
+  TGP_SEP_OVER_LIMIT = 4  /* a graph of more than max_n nodes */
+};
 int tgp_sep_max_nodes(void);
 int tgp_sep_select_f32(const int32_t* src_ptr, const int32_t* src_perm /* NULL ok */, const int32_t* dst_ptr,
                        const int32_t* dst_perm /* NULL ok */, const int64_t* src, const int64_t* dst,
@@ -1891,7 +1913,7 @@ int tgp_dense_pool_adj_grad_small_f32(const float* S, const float* A, const floa
  * group (dgrp_ptr [N + 1], dgrp_perm [E] or NULL, src [E]); an entry is max(w_e, 0).  That is the dense matrix only for a
  * COALESCED list, which the workgroup checks first: every by-source group strictly ascending in destination, every
  * by-destination group strictly ascending in source, and the graph's members (graph_perm) one run of consecutive node
- * indices.  Otherwise it sets status bit 3 (8, "not coalesced") and leaves the graph unwritten: the caller takes another
+ * indices.  Otherwise it sets status bit 3 (TGP_NMF_NOT_COALESCED) and leaves the graph unwritten: the caller takes another
  * route for it.  Bits 0 and 1 are those of tgp_nmf_factorize_f32 (an entry of graph_list outside 0 .. G - 1, and a group
  * entry whose near end is not its node, are bit 0; bit 1 is checked per entry); bit 2 is never set: there is no node
  * limit below the int32 index.  Nothing out of range is dereferenced.

@@ -23,10 +23,7 @@ constexpr int EIG_MODE_CHUNK = 8;    // modes one pass of the Reduce kernel keep
 constexpr int EIG_REDUCE_ONE_WAVE = 128;   // longest group one wave still adds alone; beyond it 4, beyond 1024 16 waves
 constexpr int EIG_REDUCE_FOUR_WAVES = 1024;
 
-// status bits of the modes kernel
-constexpr int EIG_BAD_INPUT = 1;     // an index outside its table
-constexpr int EIG_ASYMMETRIC = 2;    // a group whose induced adjacency is not symmetric: nothing written for it
-constexpr int EIG_OVER_LIMIT = 4;    // a group larger than max_m: nothing written for it
+// (the status bits of the modes kernel: enum tgp_eigenpool_status of tgp_hip.h)
 
 struct EigLds {
   int ld;
@@ -104,13 +101,13 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_modes_kernel(ModesArgs p) {
 
   const int t0 = p.theta_ptr[g], t1 = p.theta_ptr[g + 1];
   if (t0 < 0 || t1 < t0 || t1 > p.N) {  // (uniform)
-    if (tid == 0) atomicOr(p.status, EIG_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_BAD_INPUT);
     return;
   }
   const int m = t1 - t0;
   if (m == 0) return;
   if (m > p.max_m) {
-    if (tid == 0) atomicOr(p.status, EIG_OVER_LIMIT);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_OVER_LIMIT);
     return;
   }
   // the members, ascending; every one must be a node of this group
@@ -129,13 +126,13 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_modes_kernel(ModesArgs p) {
     V[i] = 0.0;
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, EIG_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_BAD_INPUT);
     return;
   }
   for (int a = tid + 1; a < m; a += T)
     if (mem[a - 1] >= mem[a]) bad = 1;
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, EIG_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_BAD_INPUT);
     return;
   }
   // induced sub-adjacency: row a is owned by one thread, which adds its node's edges in edge-list order (fp32, as the
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_modes_kernel(ModesArgs p) {
     }
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, EIG_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_BAD_INPUT);
     return;
   }
   if (m == 1) {  // a one-node group carries its own self-loop weight in every mode
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(EIG_THREADS) void eig_modes_kernel(ModesArgs p) {
     }
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, EIG_ASYMMETRIC);
+    if (tid == 0) atomicOr(p.status, TGP_EIG_ASYMMETRIC);
     return;
   }
   // degrees: column sums, ascending rows

@@ -24,9 +24,7 @@ constexpr int NMF_MAX_NODES = 128;  // 128 x 129 fp32 adjacency + three 128 x 33
 constexpr int NMF_MAX_K = 32;       // of the 160 KB LDS of a CU
 constexpr int NMF_SMALL_NODES = 64; // launches whose graphs all fit run 128 threads (a row update uses one thread per node)
 
-constexpr int NMF_BAD_INPUT = 1;    // an index outside its table, an edge across two graphs
-constexpr int NMF_NON_FINITE = 2;   // a NaN or infinite entry of the clamped adjacency
-constexpr int NMF_OVER_LIMIT = 4;   // a graph of more than max_n nodes, or K > NMF_MAX_K
+// (the status bits: enum tgp_nmf_status of tgp_hip.h)
 
 struct NmfLds {
   int lda, ldk;
@@ -154,18 +152,18 @@ __global__ __launch_bounds__(256) void nmf_factorize_kernel(NmfArgs p) {
   // ---- per-workgroup (uniform) decisions
   const int t0 = p.graph_ptr[g], t1 = p.graph_ptr[g + 1];
   if (t0 < 0 || t1 < t0 || t1 > p.N) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   const int n = t1 - t0;
   if (n == 0) return;
   if (n > p.max_n || p.K > NMF_MAX_K) {
-    if (tid == 0) atomicOr(p.status, NMF_OVER_LIMIT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_OVER_LIMIT);
     return;
   }
   const int ka = p.K < n ? p.K : n;  // (K >= 1, n >= 1)
   if (!p.init_only && ka > p.out_cols) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   // the members, ascending; every one must be a node of this graph
@@ -181,13 +179,13 @@ __global__ __launch_bounds__(256) void nmf_factorize_kernel(NmfArgs p) {
   }
   for (int i = tid; i < n * lda; i += T) A[i] = 0.0f;
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   for (int a = tid + 1; a < n; a += T)
     if (mem[a - 1] >= mem[a]) bad = 1;
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   // the adjacency: row a is owned by one thread, which adds its node's edges in edge-list order
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(256) void nmf_factorize_kernel(NmfArgs p) {
     }
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   // the reference's rules that need no factorisation (nmf_select.py:63-69)
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(256) void nmf_factorize_kernel(NmfArgs p) {
     rowbuf[a] = rs;
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, NMF_NON_FINITE);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_NON_FINITE);
     return;
   }
   // ---- init

@@ -5,8 +5,8 @@
 // One workgroup of 1024 threads per LISTED graph.  A row of A is the node's by-source edge group, a row of A^T its
 // by-destination group, an entry is clamp_min(w_e, 0).  That is the dense matrix only for a COALESCED list: every
 // by-source group strictly ascending in destination, every by-destination group strictly ascending in source, the graph's
-// nodes one run of consecutive indices.  The workgroup checks this first and declines (NMF_NOT_COALESCED, graph unwritten)
-// otherwise.  Then a row walk in ascending entry order adds the terms of the dense walk in the same order: the terms it
+// nodes one run of consecutive indices.  The workgroup checks this first and declines (TGP_NMF_NOT_COALESCED, graph
+// unwritten) otherwise.  Then a row walk in ascending entry order adds the terms of the dense walk in the same order: the terms it
 // skips are exact zeros.
 //   factors:     W and H^T [n, K] live in LDS (odd row stride) when 2 n (K | 1) floats fit behind the fixed part of the
 //                frame, else in the graph's rows of w_out / ht_out in HBM (one workgroup, __syncthreads(): workgroup-scope
@@ -45,9 +45,7 @@ constexpr int NR_RED = NR_SCRATCH + NR_SLOTS * NR_TILE * NR_TILE; // [NR_WAVES] 
 constexpr int NR_CTL = NR_RED + NR_WAVES;                         // 4 words
 constexpr int NR_FACTORS = NR_CTL + 4;
 
-constexpr int NMF_BAD_INPUT = 1;      // (the bits of csrc/nmf.hip)
-constexpr int NMF_NON_FINITE = 2;
-constexpr int NMF_NOT_COALESCED = 8;  // a group that does not strictly ascend, or members that are not one run
+// (the status bits: enum tgp_nmf_status of tgp_hip.h, shared with csrc/nmf.hip)
 
 inline int rows_lds_nodes(int K) { return (NR_LDS_BYTES / 4 - NR_FACTORS) / (2 * (K | 1)); }
 
@@ -98,25 +96,25 @@ __device__ __forceinline__ int rows_check_group(const int32_t* ptr, const int32_
                                                 const int64_t* own, const float* w, int node, int base, int n, int E,
                                                 float& sum) {
   const int e0 = ptr[node], e1 = ptr[node + 1];
-  if (e0 < 0 || e1 < e0 || e1 > E) return NMF_BAD_INPUT;
+  if (e0 < 0 || e1 < e0 || e1 > E) return TGP_NMF_BAD_INPUT;
   int flags = 0;
   int64_t prev = -1;
   for (int e = e0; e < e1; ++e) {
     const int pos = perm ? perm[e] : e;
     if (pos < 0 || pos >= E) {
-      flags |= NMF_BAD_INPUT;
+      flags |= TGP_NMF_BAD_INPUT;
       continue;
     }
     const int64_t j = other[pos];
     if (j < base || j >= static_cast<int64_t>(base) + n || own[pos] != node) {  // (an edge that leaves the graph)
-      flags |= NMF_BAD_INPUT;
+      flags |= TGP_NMF_BAD_INPUT;
       continue;
     }
-    if (j <= prev) flags |= NMF_NOT_COALESCED;
+    if (j <= prev) flags |= TGP_NMF_NOT_COALESCED;
     prev = j;
     if (SUM) {
       const float v = clamp_min(w ? w[pos] : 1.0f, 0.0f);
-      if (!(v <= FLT_MAX)) flags |= NMF_NON_FINITE;
+      if (!(v <= FLT_MAX)) flags |= TGP_NMF_NON_FINITE;
       sum += v;
     }
   }
@@ -336,19 +334,19 @@ __global__ __launch_bounds__(NR_THREADS) void nmf_rows_kernel(RowsArgs p) {
   // ---- per-workgroup (uniform) decisions
   const int g = p.list[blockIdx.x];
   if (g < 0 || g >= p.G) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   const int t0 = p.graph_ptr[g], t1 = p.graph_ptr[g + 1];
   if (t0 < 0 || t1 < t0 || t1 > p.N) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   const int n = t1 - t0;
   if (n == 0) return;
   const int ka = p.K < n ? p.K : n;
   if (ka > p.out_cols) {
-    if (tid == 0) atomicOr(p.status, NMF_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_NMF_BAD_INPUT);
     return;
   }
   // the members: nodes of this graph, and one run base, base + 1, ..
@@ -356,12 +354,12 @@ __global__ __launch_bounds__(NR_THREADS) void nmf_rows_kernel(RowsArgs p) {
   int flags = 0;
   for (int a = tid; a < n; a += NR_THREADS) {
     const int node = p.graph_perm[t0 + a];
-    if (node < 0 || node >= p.N || p.gid[node] != g) flags |= NMF_BAD_INPUT;
-    else if (static_cast<int64_t>(node) != static_cast<int64_t>(base) + a) flags |= NMF_NOT_COALESCED;
+    if (node < 0 || node >= p.N || p.gid[node] != g) flags |= TGP_NMF_BAD_INPUT;
+    else if (static_cast<int64_t>(node) != static_cast<int64_t>(base) + a) flags |= TGP_NMF_NOT_COALESCED;
   }
   flags = rows_block_or(flags, ctl);
   if (flags) {  // (an index outside its table first: a list with both is refused, not declined)
-    if (tid == 0) atomicOr(p.status, (flags & NMF_BAD_INPUT) ? NMF_BAD_INPUT : NMF_NOT_COALESCED);
+    if (tid == 0) atomicOr(p.status, (flags & TGP_NMF_BAD_INPUT) ? TGP_NMF_BAD_INPUT : TGP_NMF_NOT_COALESCED);
     return;
   }
   // every group of the graph, both directions; the clamped entries' sum on the way (a thread's rows ascending)
@@ -373,8 +371,8 @@ __global__ __launch_bounds__(NR_THREADS) void nmf_rows_kernel(RowsArgs p) {
     total += rs;
   }
   flags = rows_block_or(flags, ctl);
-  if (flags & (NMF_BAD_INPUT | NMF_NOT_COALESCED)) {
-    if (tid == 0) atomicOr(p.status, (flags & NMF_BAD_INPUT) ? NMF_BAD_INPUT : NMF_NOT_COALESCED);
+  if (flags & (TGP_NMF_BAD_INPUT | TGP_NMF_NOT_COALESCED)) {
+    if (tid == 0) atomicOr(p.status, (flags & TGP_NMF_BAD_INPUT) ? TGP_NMF_BAD_INPUT : TGP_NMF_NOT_COALESCED);
     return;
   }
   // the reference's rules that need no factorisation (nmf_select.py:63-69)
@@ -386,8 +384,8 @@ __global__ __launch_bounds__(NR_THREADS) void nmf_rows_kernel(RowsArgs p) {
     }
     return;
   }
-  if (flags & NMF_NON_FINITE) {
-    if (tid == 0) atomicOr(p.status, NMF_NON_FINITE);
+  if (flags & TGP_NMF_NON_FINITE) {
+    if (tid == 0) atomicOr(p.status, TGP_NMF_NON_FINITE);
     return;
   }
   total = block_fold_seq<NR_THREADS, true>(total, smem + NR_RED);

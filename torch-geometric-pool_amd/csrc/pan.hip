@@ -34,9 +34,7 @@ constexpr int PAN_MAX_NODES = 1024;
 constexpr int PAN_WAVES = 4;
 constexpr int PAN_MAX_FILTER = 64;  // (a power series that long has no use; the bound keeps L + 1 an int)
 
-constexpr int PAN_BAD_INPUT = 1;    // an index outside its table
-constexpr int PAN_CROSS_GRAPH = 2;  // an edge whose endpoints lie in two graphs
-constexpr int PAN_OVER_LIMIT = 4;   // a graph of more than max_n nodes
+// (the status bits: enum tgp_pan_status of tgp_hip.h)
 
 constexpr int64_t I32_MAX = 2147483647;
 
@@ -68,16 +66,16 @@ __device__ __forceinline__ void pan_wave_sync() {
 __device__ __forceinline__ bool pan_frame(const PanGraph& p, int i, int& base, int& n, int& bad) {
   const int g = p.gid ? p.gid[i] : 0;
   if (g < 0 || g >= p.G) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     return false;
   }
   const int t0 = p.graph_ptr[g], t1 = p.graph_ptr[g + 1];
   if (t0 < 0 || t1 > p.N || i < t0 || i >= t1) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     return false;
   }
   if (t1 - t0 > p.max_n) {
-    bad |= PAN_OVER_LIMIT;
+    bad |= TGP_PAN_OVER_LIMIT;
     return false;
   }
   base = t0;
@@ -90,7 +88,7 @@ __device__ __forceinline__ void pan_edge_range(const PanGraph& p, int v, int& e0
   e0 = p.grp_ptr[v];
   e1 = p.grp_ptr[v + 1];
   if (e0 < 0 || e1 < e0 || e1 > p.E) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     e0 = e1 = 0;
   }
 }
@@ -99,16 +97,16 @@ __device__ __forceinline__ void pan_edge_range(const PanGraph& p, int v, int& e0
 __device__ __forceinline__ int pan_far_end(const PanGraph& p, int e, int base, int n, int& bad) {
   const int pos = p.grp_perm ? p.grp_perm[e] : e;
   if (static_cast<unsigned>(pos) >= static_cast<unsigned>(p.E)) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     return -1;
   }
   const int64_t k = p.dst[pos];
   if (k < 0 || k >= p.N) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     return -1;
   }
   if (k < base || k >= static_cast<int64_t>(base) + n) {
-    bad |= PAN_CROSS_GRAPH;
+    bad |= TGP_PAN_CROSS_GRAPH;
     return -1;
   }
   return static_cast<int>(k - base);
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(PAN_WAVES * 64) void pan_fill_kernel(PanGraph p, co
   const int count = pan_reach(p, mask, base, n, self, lane, bad);
   const int64_t off = row_ptr[i], end = row_ptr[i + 1];
   if (off < 0 || end - off != count || end > nnz) {  // the offsets are not those of this pattern: write nothing
-    pan_flag(p.status, bad | PAN_BAD_INPUT, lane);
+    pan_flag(p.status, bad | TGP_PAN_BAD_INPUT, lane);
     return;
   }
   const float w0 = weight[0];
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(PAN_WAVES * 64) void pan_bwd_kernel(PanGraph p, con
   }
   int64_t off = row_ptr[i], end = row_ptr[i + 1];
   if (off < 0 || end < off || end > nnz) {
-    bad |= PAN_BAD_INPUT;
+    bad |= TGP_PAN_BAD_INPUT;
     off = end = 0;
   }
   // the row's pattern as M stores it: only these columns are read below, so only they are walked
@@ -297,7 +295,7 @@ __global__ __launch_bounds__(PAN_WAVES * 64) void pan_bwd_kernel(PanGraph p, con
   pan_wave_sync();
   for (int64_t e = off + lane; e < end; e += 64) {
     const int64_t c = col[e];
-    if (c < base || c >= static_cast<int64_t>(base) + n) bad |= PAN_BAD_INPUT;
+    if (c < base || c >= static_cast<int64_t>(base) + n) bad |= TGP_PAN_BAD_INPUT;
     else mask[c - base] = 1;
   }
   pan_wave_sync();

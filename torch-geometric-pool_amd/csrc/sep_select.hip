@@ -29,9 +29,7 @@ namespace {
 constexpr int SEP_THREADS = 256;
 constexpr size_t SEP_LDS_BYTES = 160 * 1024;
 
-constexpr int SEP_BAD_INPUT = 1;   // an index outside its table, an edge across two graphs
-constexpr int SEP_BAD_WEIGHT = 2;  // a non-finite or negative summed weight
-constexpr int SEP_OVER_LIMIT = 4;  // a graph of more than max_n nodes
+// (the status bits: enum tgp_sep_status of tgp_hip.h)
 
 struct SepLds {
   int ldc;
@@ -227,13 +225,13 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_select_kernel(SepArgs p) {
   // ---- per-workgroup (uniform) decisions
   const int t0 = p.graph_ptr[g], t1 = p.graph_ptr[g + 1];
   if (t0 < 0 || t1 < t0 || t1 > p.N) {
-    if (tid == 0) atomicOr(p.status, SEP_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_SEP_BAD_INPUT);
     return;
   }
   const int n = t1 - t0;
   if (n == 0) return;
   if (n > p.max_n) {
-    if (tid == 0) atomicOr(p.status, SEP_OVER_LIMIT);
+    if (tid == 0) atomicOr(p.status, TGP_SEP_OVER_LIMIT);
     return;
   }
   const bool has = tid < n;  // (n <= max_n <= 256 threads: thread x owns row x)
@@ -279,7 +277,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_select_kernel(SepArgs p) {
     }
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, SEP_BAD_INPUT);
+    if (tid == 0) atomicOr(p.status, TGP_SEP_BAD_INPUT);
     return;
   }
   // ---- weights finite and >= 0; the leaves' volumes: the fp32 entries in ascending column order into fp64
@@ -300,7 +298,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_select_kernel(SepArgs p) {
     f.label[tid] = tid;
   }
   if (__syncthreads_or(bad)) {
-    if (tid == 0) atomicOr(p.status, SEP_BAD_WEIGHT);
+    if (tid == 0) atomicOr(p.status, TGP_SEP_BAD_WEIGHT);
     return;
   }
   // ---- connected components: every node takes the smallest label among its neighbours' (and that label's label)

@@ -1,5 +1,9 @@
 """ctypes binding of the tgp HIP library (``include/tgp_hip.h``).
 
+The header is the only statement of the C ABI: the argument and return types of every entry point and the values of
+its enums are read from it when this module is imported (:func:`parse_header`), so a new entry point or constant is
+declared there and nowhere else.
+
 There is deliberately **no CPU or PyTorch fallback** behind these wrappers: if
 ``lib/libtgp_hip.so`` is missing, or an operator is handed tensors that do not live on a
 ROCm device, the call raises.  PyTorch is used for device memory (outputs and workspaces
@@ -9,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from typing import Optional
 
 import torch
@@ -17,423 +22,100 @@ from torch import Tensor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TGP_HIP_LIB: load another build of the same library (kernel experiments); never a different implementation
 LIB_PATH = os.environ.get("TGP_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libtgp_hip.so")
-
-# flag bits / enums, mirrored from include/tgp_hip.h
-REMOVE_SELF_LOOPS = 1
-DEGREE_NORM = 2
-EDGE_WEIGHT_NORM = 4
-SUM_AXIS_ROWS = 8
-EPS_FILTER = 16
-ADJ_TRANSPOSED = 32
-NODE_FILTER = 64
-WANT_EDGE_ID = 128
-HUGE_ROWS = 256
-REDUCE_OPS = {"sum": 0, "add": 0, "mean": 1, "min": 2, "max": 3, "mul": 4}
-
-_c_i64, _c_int, _c_sz, _c_p, _c_f = ctypes.c_int64, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_float
-
-# name -> (restype, argtypes); must list every symbol the header declares
-SIGNATURES = {
-    "tgp_version": (_c_int, []),
-    "tgp_last_error": (ctypes.c_char_p, []),
-    "tgp_device_cu_count": (_c_int, []),
-    "tgp_assign_index_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_assign_index_build": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_reduce_sparse_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                       _c_i64, _c_p, _c_p]),
-    "tgp_reduce_batch_i64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_connect_subgraph_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_connect_subgraph_count": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p,
-                                            _c_sz, _c_p, _c_p]),
-    "tgp_connect_subgraph_fill": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_i64, _c_p,
-                                           _c_p, _c_p, _c_p, _c_p]),
-    "tgp_connect_subgraph_single_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_connect_subgraph_single_status_words": (_c_i64, [_c_i64]),
-    "tgp_connect_subgraph_single": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_sz, _c_p,
-                                             _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_count": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_f,
-                                            _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_connect_coalesce_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _c_p, _c_p,
-                                           _c_p, _c_p]),
-    "tgp_connect_coalesce_rows_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_rows_huge_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_rows_count": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p,
-                                                 _c_int, _c_int, _c_f, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_count_publish": (_c_int, [_c_p, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_rows_count_status_words": (_c_i64, [_c_i64, _c_i64]),
-    "tgp_connect_coalesce_rows_count_published": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p,
-                                                           _c_p, _c_p, _c_int, _c_int, _c_f, _c_p, _c_sz, _c_p, _c_p,
-                                                           _c_i64, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_rows_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p,
-                                                _c_p]),
-    "tgp_connect_coalesce_rows_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_rows_count_published_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p,
-                                                               _c_p, _c_p, _c_int, _c_int, ctypes.c_double, _c_p, _c_sz,
-                                                               _c_p, _c_p, _c_i64, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_rows_fill_f64": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_connect_coalesce_fused_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_fused_count": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p,
-                                                  _c_p, _c_int, _c_int, _c_f, _c_p, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_connect_coalesce_fused_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_sparse_pool_small_max_graph_nodes": (_c_int, []),
-    "tgp_sparse_pool_small_status_words": (_c_i64, [_c_i64, _c_int]),
-    "tgp_graph_lower_bounds_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_sparse_pool_small_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p,
-                                           _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                           _c_p, _c_i64, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_grouped_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_grouped_count": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int,
-                                                    _c_f, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_postprocess_sparse_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_postprocess_sparse_norm_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_i64,
-                                                 _c_p, _c_sz, _c_p]),
-    "tgp_dense_pool_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_dense_pool_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_p, _c_p,
-                                    _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_dense_pool_is_small": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_dense_pool_mincut_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f, _c_f, _c_p,
-                                           _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_dense_pool_select_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f, _c_f,
-                                           _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_edge_facts_sorted_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, ctypes.c_uint64, _c_p]),
-    "tgp_dense_pool_select_sparse_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                                  _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_f, _c_f, _c_p, _c_p, _c_p,
-                                                  _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_diffpool_stats_tail_f32": (_c_int, [_c_p, _c_i64, _c_f, _c_f, _c_p, _c_p]),
-    "tgp_dense_pool_small_diff_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
-                                               _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_dense_pool_small_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f, _c_f, _c_p,
-                                              _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f, _c_f, _c_int,
-                                              _c_p, _c_p, _c_p]),
-    "tgp_postprocess_dense_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_postprocess_dense_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_p]),
-    "tgp_postprocess_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_sz, _c_p]),
-    "tgp_bmm_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64,
-                             _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_bmm_accumulate_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64,
-                                        _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_segment_gemm_tn_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_segment_gemm_tn_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                         _c_p, _c_sz, _c_p]),
-    "tgp_segment_gemm_nn_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_topk_plan": (_c_int, [_c_p, _c_i64, ctypes.c_double, _c_p, _c_p, _c_p]),
-    "tgp_topk_select_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_topk_select": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_sz, _c_p, _c_p, _c_p,
-                                 _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_topk_select_directory_blocks": (_c_i64, [_c_i64]),
-    "tgp_one_to_one_index_build": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_reduce_one_to_one_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_int, _c_i64, _c_p, _c_p]),
-    "tgp_topk_minscore_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_topk_minscore_count": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_p, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_topk_minscore_fill": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_graclus_match_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_graclus_match_start": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_sz, _c_p, _c_int, _c_p]),
-    "tgp_graclus_relabel_max_nodes": (_c_i64, []),
-    "tgp_graclus_relabel_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_graclus_relabel_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_sz, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_graclus_match_tail": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_graclus_match_max_graph_nodes": (_c_int, []),
-    "tgp_graclus_match_graphs_fused_max_graph_nodes": (_c_int, []),
-    "tgp_graclus_match_graphs_fused_status_words": (_c_i64, [_c_i64]),
-    "tgp_graclus_match_graphs_fused": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
-                                                _c_p, _c_p, _c_p, _c_i64, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_graclus_match_graphs": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_kmis_max_graph_nodes": (_c_int, []),
-    "tgp_kmis_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_kmis_graphs": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p,
-                                 _c_p, _c_p]),
-    "tgp_kmis_rounds_start": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_sz, _c_p]),
-    "tgp_kmis_rounds": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_kmis_clusters": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_kmis_greedy_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_kmis_wsum_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_kmis_degree_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_kmis_mis_index_i64": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_edge_contract_max_graph_nodes": (_c_int, []),
-    "tgp_edge_contract_edge_cache": (_c_int, []),
-    "tgp_edge_contract_hub_degree": (_c_int, []),
-    "tgp_edge_contract_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_edge_contract_project_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_edge_contract_raw_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_edge_contract_normalize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p,
-                                                 _c_i64, _c_p, _c_p]),
-    "tgp_edge_contract_graphs": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                          _c_p, _c_p]),
-    "tgp_edge_contract_rounds_start": (_c_int, [_c_i64, _c_i64, _c_p, _c_sz, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_edge_contract_rounds": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p,
-                                          _c_p, _c_p]),
-    "tgp_edge_contract_weights_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_lapool_variation_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_lapool_variation_csr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_lapool_flags_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_lapool_flags_csr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_lapool_columns": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_lapool_assign_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                       _c_f, _c_p, _c_p, _c_p]),
-    "tgp_lapool_assign_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p,
-                                           _c_p, _c_p, _c_i64, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_graclus_match_rounds": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_p]),
-    "tgp_batch_facts_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p]),
-    "tgp_batch_facts_sorted_i64": (_c_int, [_c_p, _c_i64, _c_p, _c_p, ctypes.c_double, _c_p, _c_p, _c_p, _c_p,
-                                            ctypes.c_uint64, _c_p]),
-    "tgp_topk_score_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p]),
-    "tgp_row_dot_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_weighted_colsum_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_weighted_colsum_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_topk_pool_bwd_fits": (_c_int, [_c_i64]),
-    "tgp_topk_pool_bwd_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_topk_pool_bwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_int,
-                                       _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_pair_dot_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_edge_dot_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_link_loss_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_link_loss_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_entropy_sum_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_entropy_bwd_f32": (_c_int, [_c_p, _c_i64, _c_f, _c_p, _c_f, _c_p, _c_p]),
-    "tgp_entropy_sum_f32": (_c_int, [_c_p, _c_i64, _c_f, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_cut_terms_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_mincut_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_dense_pool_train_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_dense_pool_train_fwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_f, _c_p, _c_i64,
-                                              _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_mincut_terms_fused_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_f, _c_p, _c_p, _c_p,
-                                            _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_segment_gemm_tn3_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_segment_gemm_tn3_post_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_pool_rows_fwd_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_pool_rows_bwd_f32": (_c_int, [_c_p] * 13 + [_c_i64] * 6 + [_c_int, _c_f, _c_f, _c_int, _c_int, _c_f, _c_f, _c_f, _c_p,
-                                       _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p] + [_c_p] * 10 + [_c_p]),
-    "tgp_pool_rows_fwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64,
-                                       _c_i64, _c_int, _c_int, _c_f, _c_f, _c_int, _c_p, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p,
-                                       _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_segment_gemm_tn3_post_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                               _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_f, _c_p, _c_sz, _c_p]),
-    "tgp_segment_gemm_tn3_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                          _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_sz, _c_p]),
-    "tgp_edge_row_stats_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_diffpool_unbatched_tail_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_f, _c_p, _c_int, _c_f, _c_f, _c_p,
-                                                 _c_p, _c_p]),
-    "tgp_dense_pool_train_rhs_f32": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f, _c_f,
-                                              _c_p, _c_int, _c_int, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p,
-                                              _c_p]),
-    "tgp_dense_pool_adj_grad_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_f,
-                                             _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_dense_pool_adj_grad_small_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f,
-                                                   _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_softmax_bwd_ex_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_f, _c_f, _c_p, _c_i64, _c_i64,
-                                        _c_i64, _c_p, _c_p]),
-    "tgp_segment_gemm_nn_ld_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
-                                            _c_i64, _c_i64, _c_p]),
-    "tgp_segment_gemm_tn_ld_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_dense_symmetry_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, ctypes.c_uint64, _c_p]),
-    "tgp_edge_symmetry_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, ctypes.c_uint64, _c_p]),
-    "tgp_slab_sum_split_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_adj_symmetry_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, ctypes.c_uint64, _c_p]),
-    "tgp_copy_cols2_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_copy_cols3_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
-                                    _c_i64, _c_p]),
-    "tgp_mincut_loss_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p]),
-    "tgp_dmon_dense_terms_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_dmon_edge_degrees_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_dmon_node_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_dmon_loss_terms_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_int, _c_f, _c_f, _c_f,
-                                         _c_f, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_dmon_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p,
-                                             _c_p, _c_p]),
-    "tgp_dmon_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_jb_terms_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_f, _c_f, _c_f, _c_f,
-                                  _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_jb_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_hosc_small_graph_nodes": (_c_int, []),
-    "tgp_hosc_record_floats": (_c_i64, [_c_i64]),
-    "tgp_hosc_matvec_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_hosc_node_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                         _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_hosc_small_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_hosc_loss_terms_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p,
-                                         _c_p, _c_p, _c_p]),
-    "tgp_hosc_loss_terms_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_f, _c_f, _c_int, _c_p, _c_p, _c_p,
-                                             _c_p]),
-    "tgp_hosc_ds_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64,
-                                 _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_bnpool_max_clusters": (_c_int, []),
-    "tgp_bnpool_part_floats": (_c_i64, [_c_i64, _c_i64]),
-    "tgp_bnpool_rec_fwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_bnpool_rec_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_acc_small_graph_nodes": (_c_int, []),
-    "tgp_acc_tv_dense_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_acc_tv_dense_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p]),
-    "tgp_acc_tv_edge_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_acc_tv_edge_bwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                         _c_p, _c_p, _c_f, _c_i64, _c_p, _c_p]),
-    "tgp_acc_quantile_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p,
-                                      _c_p, _c_p, _c_p, _c_p]),
-    "tgp_acc_loss_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_f, _c_f,
-                                        _c_p, _c_p, _c_p]),
-    "tgp_acc_asym_bwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                      _c_f, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_rowptr_from_sorted_flag_i64": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_rowptr_from_sorted_i64": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_spmm_csr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_spmm_csr_stats_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_spmm_csr_entropy_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_f, _c_p, _c_p, _c_p]),
-    "tgp_to_dense_adj_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_p]),
-    "tgp_to_dense_adj_channels_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p,
-                                               _c_p]),
-    "tgp_from_dense_adj_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_from_dense_batch_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_to_dense_batch_sorted_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "tgp_entropy_partials_f32": (_c_int, [_c_p, _c_i64, _c_f, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_diffpool_loss_tail_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_int, _c_f, _c_f, _c_p, _c_p]),
-    "tgp_to_dense_batch_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_block_diag_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_block_diag_count": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_f, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_block_diag_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, _c_f, _c_p, _c_i64, _c_p, _c_p, _c_p,
-                                     _c_p]),
-    "tgp_ndp_symmetric_max_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_ndp_max_graph_nodes": (_c_int, []),
-    "tgp_ndp_partition": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, ctypes.c_uint64, _c_int,
-                                   ctypes.c_double, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_ndp_large_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_ndp_large_start": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_ndp_large_steps": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_double, _c_p, _c_sz, _c_p,
-                                     _c_p, _c_p]),
-    "tgp_ndp_large_finish": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, ctypes.c_uint64, _c_p, _c_sz, _c_p, _c_p,
-                                      _c_p]),
-    "tgp_ndp_large_state": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
-    "tgp_kron_batched_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_kron_batched_max_graph_nodes": (_c_int, []),
-    "tgp_kron_batched_count": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_i64, _c_i64,
-                                        _c_i64, _c_i64, _c_i64, _c_p, _c_i64, ctypes.c_double, _c_p, _c_p, _c_sz, _c_p,
-                                        _c_p]),
-    "tgp_kron_batched_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p,
-                                       _c_p, _c_p, _c_p]),
-    "tgp_mlp_select_max_fused_k": (_c_int, []),
-    "tgp_mlp_select_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_softmax_rows_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p]),
-    "tgp_softmax_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p]),
-    "tgp_mlp_select_bwd_fits": (_c_int, [_c_i64, _c_i64]),
-    "tgp_mlp_select_bwd_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_mlp_select_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_p,
-                                        _c_sz, _c_p]),
-    "tgp_reduce_sparse_f64": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_connect_subgraph_single_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_double,
-                                                 _c_p, _c_sz, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p,
-                                                 ctypes.c_uint32, _c_p]),
-    "tgp_connect_coalesce_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_connect_coalesce_count_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int,
-                                                ctypes.c_double, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_connect_coalesce_fill_f64": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _c_p, _c_p, _c_p,
-                                               _c_p]),
-    "tgp_postprocess_sparse_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_postprocess_sparse_norm_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_double, _c_p, _c_i64,
-                                                 _c_p, _c_sz, _c_p]),
-    "tgp_block_diag_count_f64": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, ctypes.c_double, _c_p, _c_sz, _c_p, _c_p]),
-    "tgp_block_diag_fill_f64": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_int, ctypes.c_double, _c_p, _c_i64, _c_p, _c_p,
-                                         _c_p, _c_p]),
-    "tgp_postprocess_dense_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64]),
-    "tgp_postprocess_dense_f64": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_double, _c_p, _c_sz, _c_p]),
-    "tgp_edges_compact": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_copy_arrays": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p]),
-    "tgp_result_wait_pack_cols": (_c_int, [_c_p, ctypes.c_uint32, _c_p, _c_p, _c_p]),
-    "tgp_mask_index_scratch_words": (_c_i64, [_c_i64]),
-    "tgp_mask_index_count": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, ctypes.c_uint32, _c_p]),
-    "tgp_mask_index_fill": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_bmm_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_i64,
-                             _c_i64, _c_i64, _c_int, _c_p]),
-    "tgp_dense_pool_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_dense_pool_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, ctypes.c_double, _c_p, _c_p,
-                                    _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_segment_gemm_tn_workspace_bytes_f64": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
-    "tgp_segment_gemm_tn_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_sz,
-                                         _c_p]),
-    "tgp_segment_gemm_nn_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "tgp_spmm_csr_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_gather_pack_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
-    "tgp_gather_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
-                                     _c_i64, _c_p, _c_p]),
-    "tgp_gather_unpack_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_p,
-                                       _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_uint64, _c_p]),
-    "tgp_gather_max_bucket_steps": (_c_int, []),
-    "tgp_gather_pack_bucket_f32": (_c_int, [_c_p, _c_p, _c_int, _c_i64, _c_p, _c_p]),
-    "tgp_gather_unpack_bucket_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_p, _c_p, _c_p]),
-    "tgp_debug_sort_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_debug_sort_pairs_u64": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_asap_query_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                    _c_p]),
-    "tgp_asap_edge_dot_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_asap_softmax_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p,
-                                          _c_p]),
-    "tgp_asap_query_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_asap_edge_softmax_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_f, _c_p, _c_p]),
-    "tgp_asap_attend_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
-                                     _c_p, _c_p]),
-    "tgp_asap_leconv_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p,
-                                     _c_p]),
-    "tgp_row_project2_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_sag_aggregate_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_p,
-                                       _c_p]),
-    "tgp_sag_score_bwd_x_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_segment_aggr_chunk_rows": (_c_int, []),
-    "tgp_segment_aggr_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int, _c_i64]),
-    "tgp_segment_aggr_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                      _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_segment_aggr_bwd_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p,
-                                          _c_i64, _c_int, _c_p, _c_p]),
-    "tgp_maxcut_max_width": (_c_int, []),
-    "tgp_maxcut_tail_max_params": (_c_int, []),
-    "tgp_maxcut_degree_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_maxcut_layer_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_f,
-                                      _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p]),
-    "tgp_maxcut_tail_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_p]),
-    "tgp_maxcut_wgrad_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64]),
-    "tgp_maxcut_wgrad_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_sz, _c_p]),
-    "tgp_maxcut_cut_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_maxcut_assign_round_i32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_eigenpool_max_group_nodes": (_c_int, []),
-    "tgp_eigenpool_modes_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                         _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_eigenpool_reduce_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
-                                          _c_p]),
-    "tgp_eigenpool_lift_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "tgp_nmf_max_nodes": (_c_int, []),
-    "tgp_nmf_max_k": (_c_int, []),
-    "tgp_nmf_init_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                  _c_p, _c_p, _c_p, _c_p]),
-    "tgp_nmf_factorize_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                       _c_i64, _c_i64, _c_f, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                       _c_p]),
-    "tgp_pan_max_graph_nodes": (_c_int, []),
-    "tgp_pan_met_workspace_bytes": (_c_sz, [_c_i64]),
-    "tgp_pan_met_count": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p,
-                                   _c_sz, _c_p, _c_p, _c_p]),
-    "tgp_pan_met_fill_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                      _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_pan_met_bwd_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                     _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "tgp_pan_score_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p,
-                                   _c_p, _c_p, _c_p]),
-    "tgp_gtv_edge_fwd_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_f, _c_f, _c_int,
-                                      _c_p, _c_p, _c_p]),
-    "tgp_gtv_edge_bwd_terms_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p,
-                                            _c_f, _c_f, _c_int, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_gtv_edge_bwd_nodes_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                            _c_p, _c_p, _c_f, _c_f, _c_p, _c_p]),
-    "tgp_sep_max_nodes": (_c_int, []),
-    "tgp_sep_select_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
-                                    _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "tgp_nmfrows_lds_nodes": (_c_int, [_c_i64]),
-    "tgp_nmfrows_factorize_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                           _c_i64, _c_f, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
-                                           _c_p, _c_p, _c_i64, _c_i64, _c_p]),
-}
-
-_lib: Optional[ctypes.CDLL] = None
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "tgp_hip.h")
 
 
 class TgpNativeError(RuntimeError):
-    """Raised when the HIP library is missing or reports a non-zero status."""
+    """Raised when the HIP library is missing or reports a non-zero status, or its header cannot be bound."""
+
+
+# every kind of parameter and of return value the C ABI uses; a pointer of any type is a c_void_p
+_BY_VALUE = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+             "double": ctypes.c_double, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+_FUNCTION = re.compile(r"([\w\s*]+?)\b(tgp_\w+)\s*\(([^()]*)\)")  # return type, name, parameter list
+_ENUM = re.compile(r"enum\s+(\w+)\s*\{([^{}]*)\}")
+_ENUMERATOR = re.compile(r"(\w+)\s*=\s*(-?(?:0|[1-9]\d*))")  # an explicit decimal value
+_POINTER = re.compile(r"[\w\s*]*\*[\w\s*]*")  # const T* name, T* const* name, ...
+_VALUE = re.compile(r"(\w+)(?:\s+\w+)?")  # T or T name
+
+
+def parse_header(text: str):
+    """``(signatures, enums)`` of a C header written the way ``include/tgp_hip.h`` is: between comments and
+    preprocessor lines, nothing but ``enum name { A = 1, ... };`` and ``type tgp_name(parameters);``.
+    ``signatures``: name -> (restype, [argtypes]); ``enums``: enum name -> {enumerator: value}.  Anything else --
+    a by-value type outside ``_BY_VALUE`` / ``_RETURNS``, a function pointer, ``...``, an enumerator without an explicit
+    value, text that is no complete declaration -- raises :class:`TgpNativeError`; nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text, n_extern = re.subn(r'extern\s+"C"\s*\{', "", text)
+    *statements, rest = text.split(";")
+    signatures, enums = {}, {}
+    for statement in statements:
+        decl = " ".join(statement.split())
+        fn, enum = _FUNCTION.fullmatch(decl), _ENUM.fullmatch(decl)
+        if fn:
+            ret, name, params = fn.groups()
+            ret = re.sub(r"\s*\*", "*", ret.strip())
+            if ret not in _RETURNS:
+                raise TgpNativeError(f"C ABI header: {name} returns '{ret}', which is none of {sorted(_RETURNS)}")
+            if name in signatures:
+                raise TgpNativeError(f"C ABI header: {name} is declared twice")
+            argtypes = []
+            for param in [] if params.strip() == "void" else params.split(","):
+                value = _VALUE.fullmatch(param.strip())
+                if _POINTER.fullmatch(param):
+                    argtypes.append(ctypes.c_void_p)
+                elif value and value[1] in _BY_VALUE:
+                    argtypes.append(_BY_VALUE[value[1]])
+                else:
+                    raise TgpNativeError(f"C ABI header: {name} has the parameter '{param.strip()}', which is neither a "
+                                         f"pointer nor one of {sorted(_BY_VALUE)}")
+            signatures[name] = (_RETURNS[ret], argtypes)
+        elif enum:
+            values = {}
+            for item in enum[2].split(","):
+                enumerator = _ENUMERATOR.fullmatch(item.strip())
+                if not enumerator:
+                    raise TgpNativeError(f"C ABI header: enum {enum[1]} has the enumerator '{item.strip()}', which is not "
+                                         "'NAME = integer'")
+                values[enumerator[1]] = int(enumerator[2])
+            enums[enum[1]] = values
+        elif decl:
+            raise TgpNativeError(f"C ABI header: the declaration '{decl[:120]}' is not understood")
+    if rest.split() != ["}"] * n_extern:
+        raise TgpNativeError(f"C ABI header: '{' '.join(rest.split())[:120]}' after the last declaration is not understood")
+    return signatures, enums
+
+
+def read_header(path: str):
+    """:func:`parse_header` of the file at ``path``."""
+    try:
+        with open(path) as fh:
+            text = fh.read()
+    except OSError as err:
+        raise TgpNativeError(
+            f"C ABI header {path} cannot be read ({err.strerror}): the bindings are derived from it") from err
+    return parse_header(text)
+
+
+# SIGNATURES: name -> (restype, argtypes) of every symbol the header declares; ENUMS: its enums
+SIGNATURES, ENUMS = read_header(HEADER_PATH)
+
+_flags = ENUMS["tgp_flags"]
+REMOVE_SELF_LOOPS = _flags["TGP_REMOVE_SELF_LOOPS"]
+DEGREE_NORM = _flags["TGP_DEGREE_NORM"]
+EDGE_WEIGHT_NORM = _flags["TGP_EDGE_WEIGHT_NORM"]
+SUM_AXIS_ROWS = _flags["TGP_SUM_AXIS_ROWS"]
+EPS_FILTER = _flags["TGP_EPS_FILTER"]
+ADJ_TRANSPOSED = _flags["TGP_ADJ_TRANSPOSED"]
+NODE_FILTER = _flags["TGP_NODE_FILTER"]
+WANT_EDGE_ID = _flags["TGP_WANT_EDGE_ID"]
+HUGE_ROWS = _flags["TGP_HUGE_ROWS"]
+REDUCE_OPS = {name[len("TGP_"):].lower(): value for name, value in ENUMS["tgp_reduce_op"].items()}
+REDUCE_OPS["add"] = REDUCE_OPS["sum"]  # the reference accepts both names
+
+_lib: Optional[ctypes.CDLL] = None
 
 
 def lib() -> ctypes.CDLL:

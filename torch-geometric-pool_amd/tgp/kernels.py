@@ -4548,7 +4548,10 @@ def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, round
 
 
 # ------------------------------------------------------------------------------------------------ EigenPooling
-EIG_BAD_INPUT, EIG_ASYMMETRIC, EIG_OVER_LIMIT = 1, 2, 4  # status bits of tgp_eigenpool_modes_f32
+_EIG = N.ENUMS["tgp_eigenpool_status"]  # status bits of tgp_eigenpool_modes_f32
+EIG_BAD_INPUT = _EIG["TGP_EIG_BAD_INPUT"]
+EIG_ASYMMETRIC = _EIG["TGP_EIG_ASYMMETRIC"]
+EIG_OVER_LIMIT = _EIG["TGP_EIG_OVER_LIMIT"]
 
 
 def eigenpool_max_group_nodes() -> int:
@@ -4622,7 +4625,10 @@ def eigenpool_lift(theta_modes: Tensor, gid: Tensor, x_pool: Tensor, num_groups:
 
 
 # ------------------------------------------------------------------------------------------------ NMF pooling
-NMF_BAD_INPUT, NMF_NON_FINITE, NMF_OVER_LIMIT = 1, 2, 4  # status bits of tgp_nmf_factorize_f32 / tgp_nmf_init_f32
+_NMF = N.ENUMS["tgp_nmf_status"]  # status bits of tgp_nmf_factorize_f32 / tgp_nmf_init_f32
+NMF_BAD_INPUT = _NMF["TGP_NMF_BAD_INPUT"]
+NMF_NON_FINITE = _NMF["TGP_NMF_NON_FINITE"]
+NMF_OVER_LIMIT = _NMF["TGP_NMF_OVER_LIMIT"]
 
 
 def nmf_max_nodes() -> int:
@@ -4694,7 +4700,8 @@ def nmf_factorize(by_src: AssignIndex, dst: Tensor, edge_weight: Optional[Tensor
     return out
 
 
-NMF_NOT_COALESCED = 8  # status bit of tgp_nmfrows_factorize_f32: the graph is declined, another route takes it
+# status bit of tgp_nmfrows_factorize_f32: the graph is declined, another route takes it
+NMF_NOT_COALESCED = _NMF["TGP_NMF_NOT_COALESCED"]
 _NMF_HOMES = {"auto": 0, "hbm": 1}
 
 
@@ -4751,7 +4758,10 @@ def nmf_rows_factorize(by_src: AssignIndex, by_dst: AssignIndex, src: Tensor, ds
 
 
 # ------------------------------------------------------------------------------------------------ SEP (csrc/sep_select.hip)
-SEP_BAD_INPUT, SEP_BAD_WEIGHT, SEP_OVER_LIMIT = 1, 2, 4  # status bits of tgp_sep_select_f32
+_SEP = N.ENUMS["tgp_sep_status"]  # status bits of tgp_sep_select_f32
+SEP_BAD_INPUT = _SEP["TGP_SEP_BAD_INPUT"]
+SEP_BAD_WEIGHT = _SEP["TGP_SEP_BAD_WEIGHT"]
+SEP_OVER_LIMIT = _SEP["TGP_SEP_OVER_LIMIT"]
 
 
 def sep_max_nodes() -> int:
@@ -4793,7 +4803,10 @@ def sep_select(edge_index: Tensor, edge_weight: Optional[Tensor], gid: Tensor, g
 
 
 # ------------------------------------------------------------------------------------------------ PAN (csrc/pan.hip)
-PAN_BAD_INPUT, PAN_CROSS_GRAPH, PAN_OVER_LIMIT = 1, 2, 4  # status bits of the tgp_pan_met_* entries
+_PAN = N.ENUMS["tgp_pan_status"]  # status bits of the tgp_pan_met_* entries
+PAN_BAD_INPUT = _PAN["TGP_PAN_BAD_INPUT"]
+PAN_CROSS_GRAPH = _PAN["TGP_PAN_CROSS_GRAPH"]
+PAN_OVER_LIMIT = _PAN["TGP_PAN_OVER_LIMIT"]
 PAN_MAX_FILTER = 64
 
 # edge lists the MET kernel declined before (an edge between two graphs), per graph offsets and node count: the same
