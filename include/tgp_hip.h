@@ -1563,6 +1563,60 @@ int tgp_asap_query_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NU
                            int64_t F, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The hub route of the ASAP fitness and the SAG scorer, csrc/hub_walk.hip.  fp32, no float atomics, the same bits on
+ * every call.  The eight walks above give one group to one wave (the two scalar aggregates: to one lane); these entries
+ * serve the groups a host plan names as hubs, cut into chunks of tgp_hubwalk_chunk() entries with one wave per
+ * (hub, chunk).  They take the FULL index (grp_ptr, grp_perm, the gathered endpoint) and the plan:
+ *   hub_ids [H] int32 ascending, chunk_ptr [H + 1] int32, T = chunk_ptr[H]; chunk c of hub h covers entries
+ *   b + c C .. min(b + (c + 1) C, e) of its group [b, e): a function of the group alone.
+ * Every entry writes the outputs of the hub nodes (and of their edges) ONLY; the caller runs the one-wave entry on the
+ * light index (every hub group emptied) first and the hub entry after it on the same stream.  Chunks leave partial
+ * records in `ws` (tgp_hubwalk_workspace_bytes(T, F); F = 0 for the scalar, softmax and softmax_bwd entries) and a tail
+ * folds a hub's records in an order fixed by the group: see the head comment of csrc/hub_walk.hip.
+ *   scalar       leconv = 0: tgp_sag_aggregate_f32's t and a (q, bias, mean, act 0 / 1); leconv = 1: tgp_asap_leconv_f32's
+ *                (p is [3,N], bias = b3, b1, edge_weight, act 0 / 1 / 2).
+ *   the others   the values of the tgp_asap_* entry of the same name.  Maxima and argpos are exact; the sums have the hub
+ *                route's own order, so a hub's floats differ from the one-wave walk's in the last bits.
+ * TGP_ERR_INVALID: a NULL input, output, plan table or workspace, a workspace too small, an input given as the output,
+ * sizes below zero, ldx < F, an unknown act; TGP_ERR_RANGE: N, E, H or T beyond the int32 index, F >= 2^31.  Both are
+ * found before any HIP call.  The order of the checks: N, E, H, T and F against their ranges first; then H = 0, T = 0 or
+ * N = 0 (an empty plan) is TGP_OK whatever else is handed over, nothing launched or read; then everything else.
+ * ---------------------------------------------------------------------------------- */
+int tgp_hubwalk_chunk(void);
+size_t tgp_hubwalk_workspace_bytes(int64_t T, int64_t F);
+int tgp_hubwalk_scalar_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                           const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T,
+                           const float* edge_weight /* NULL ok */, const float* p, const float* q /* NULL ok */,
+                           const float* bias /* NULL ok */, const float* b1 /* NULL ok */, int64_t N, int64_t E,
+                           int leconv, int mean, int act, float* t_out /* NULL ok */,
+                           float* a_out /* NULL ok, not both */, void* ws, size_t ws_bytes, void* stream);
+int tgp_hubwalk_query_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                          const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T, const float* x_pool,
+                          int64_t ldx, const float* w_tilde, const float* c, int64_t N, int64_t E, int64_t F, float* sq,
+                          int32_t* argpos /* NULL ok */, void* ws, size_t ws_bytes, void* stream);
+int tgp_hubwalk_edge_softmax_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                                 const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T, const float* sq,
+                                 const float* sp, int64_t N, int64_t E, float negative_slope, float* alpha, void* ws,
+                                 size_t ws_bytes, void* stream);
+int tgp_hubwalk_attend_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                           const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T,
+                           const float* val /* NULL ok */, const float* x, int64_t ldx, const float* w3 /* NULL ok */,
+                           int64_t N, int64_t N_src, int64_t E, int64_t F, float* out, float* p /* NULL iff w3 is */,
+                           void* ws, size_t ws_bytes, void* stream);
+int tgp_hubwalk_edge_dot_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                             const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T, const float* g,
+                             const float* x, int64_t ldx, int64_t N, int64_t E, int64_t F, float* out, void* stream);
+int tgp_hubwalk_softmax_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                                const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T,
+                                const float* alpha, const float* g_alpha, const float* sq, const float* sp, int64_t N,
+                                int64_t E, float negative_slope, float* g_l, float* g_sq, void* ws, size_t ws_bytes,
+                                void* stream);
+int tgp_hubwalk_query_bwd_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* dst,
+                              const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T,
+                              const int32_t* argpos, const float* g_sq, const float* w_tilde, int64_t N, int64_t E,
+                              int64_t F, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Segment readout (reference reduce/aggr_reduce.py, reduce/global_reduce.py over PyG's Sum / Mean / Max / Min /
  * MultiAggregation), csrc/segment_aggr.hip.  fp32, no float atomics, the same bits on every call.
  *   `ops` is a mask of (1 << TGP_SUM) | (1 << TGP_MEAN) | (1 << TGP_MIN) | (1 << TGP_MAX); ONE pass over x fills

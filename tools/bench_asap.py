@@ -39,10 +39,15 @@ HBM_PEAK = 8.0e12  # bytes / s, MI355X
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("small", "large", "hub"), default="small")
+    ap.add_argument("--workload", choices=("small", "large", "hub", "hub_sweep"), default="small")
+    ap.add_argument("--degrees", type=int, nargs="*", default=[1024, 4096, 16384, 65536, 524293],
+                    help="hub_sweep: the in-degrees of the one hub, a JSON line each")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--hub-min-group", type=int, default=None,
+                    help="kernels.HUB_MIN_GROUP for this run; a value above every in-degree suppresses the hub plan, "
+                         "which times the one-wave kernels alone")
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "torch-geometric-pool_amd"))
     import torch
@@ -52,8 +57,12 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("bench_asap.py measures on the GPU: none found")
+    if a.hub_min_group is not None:
+        kernels.HUB_MIN_GROUP = a.hub_min_group
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if a.workload == "hub_sweep":
+        return hub_sweep(a, torch, kernels, ASAPooling, add_remaining_self_loops, dev)
     g = torch.Generator().manual_seed(0)
     batch = None
     if a.workload == "small":
@@ -161,6 +170,8 @@ def main():
     out = {"workload": a.workload, "num_nodes": n, "num_edges": int(ei.size(1)), "num_edges_with_loops": E,
            "features": F, "index_route": "offsets" if grp.perm is None else "permutation",
            "max_in_degree": int((grp.row_ptr[1:] - grp.row_ptr[:-1]).max()),
+           "hub_min_group": kernels.HUB_MIN_GROUP, "hubs": 0 if grp.hub is None else grp.hub.H,
+           "hub_chunks": 0 if grp.hub is None else grp.hub.chunks,
            "supernodes": int(forward().so.num_supernodes), "windows": a.windows, "steps_per_window": a.steps,
            "native_vs_composed_max_abs_diff": err}
     for name in runs:
@@ -178,6 +189,79 @@ def main():
         out[f"{name}_bytes_counted"] = b
         out[f"{name}_share_of_hbm_peak"] = round(b / (med[name] * 1e-3) / HBM_PEAK, 4)
     print(json.dumps(out))
+
+
+def hub_sweep(a, torch, kernels, ASAPooling, add_remaining_self_loops, dev):
+    """One JSON line per hub in-degree: 65536 nodes, 524288 random edges and ``degree`` more into node 7, F = 128.  The
+    same list as two tensor objects: the index of one is built with the plan suppressed (the one-wave kernels), the
+    index of the other with the threshold just below the degree (the hub route, whatever HUB_MIN_GROUP is), so one run
+    times one-wave, hub route and composed form in alternating windows."""
+    F, n, e = 128, 65536, 524288
+    asap = ASAPooling(in_channels=F).to(dev)
+    le = asap.select_scorer
+    for degree in a.degrees:
+        g = torch.Generator().manual_seed(0)
+        ei = torch.cat([torch.randint(0, n, (2, e), generator=g),
+                        torch.stack([torch.randint(0, n, (degree,), generator=g), torch.full((degree,), 7)])], 1).to(dev)
+        x = torch.randn(n, F, generator=g).to(dev)
+        lists = {"one_wave": ei, "hub_route": ei.clone()}
+        looped = {k: add_remaining_self_loops(v, None, num_nodes=n)[0] for k, v in lists.items()}
+
+        def fitness(ea):
+            with torch.no_grad():
+                return asap.fitness(x, ea, None, act="sigmoid")
+
+        def composed(ea, xg):
+            _, x_new = asap.attention(xg, xg, ea)
+            msg = le.lin1(x_new)[ea[0]] - le.lin2(x_new)[ea[1]]
+            return x_new, torch.sigmoid(msg.new_zeros(n, 1).index_add_(0, ea[1], msg) + le.lin3(x_new)).view(-1)
+
+        def train(route, ea):
+            asap.zero_grad(set_to_none=True)
+            xg = x.detach().requires_grad_(True)
+            x_new, s_ = asap.fitness(xg, ea, None, act="sigmoid")[1:] if route == "native" else composed(ea, xg)
+            ((x_new * s_.view(-1, 1)) ** 2).sum().backward()
+
+        def forward(adj):
+            with torch.no_grad():
+                return asap(x=x, adj=adj)
+
+        def step(adj):
+            asap.zero_grad(set_to_none=True)
+            (asap(x=x, adj=adj).x ** 2).sum().backward()
+
+        def composed_fitness():
+            with torch.no_grad():
+                return composed(looped["one_wave"], x)
+
+        runs = {"composed_fitness": composed_fitness, "composed_train": lambda: train("composed", looped["one_wave"])}
+        for k in lists:
+            runs.update({f"{k}_fitness": lambda k=k: fitness(looped[k]), f"{k}_train": lambda k=k: train("native", looped[k]),
+                         f"{k}_forward": lambda k=k: forward(lists[k]), f"{k}_train_step": lambda k=k: step(lists[k])})
+        keep = kernels.HUB_MIN_GROUP
+        for name, fn in runs.items():  # the first call builds the indices: with or without the plan
+            kernels.HUB_MIN_GROUP = degree - 1 if name.startswith("hub_route") else 1 << 40
+            for _ in range(max(1, a.warmup)):
+                fn()
+        kernels.HUB_MIN_GROUP = keep
+        plans = {k: kernels.sag_edge_group(v, n).hub for k, v in looped.items()}
+        assert plans["one_wave"] is None and plans["hub_route"] is not None and plans["hub_route"].H >= 1
+        ms = {name: [] for name in runs}
+        for _ in range(a.windows):
+            for name, fn in runs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) / a.steps * 1e3)
+        out = {"workload": "hub_sweep", "hub_in_degree": degree, "num_nodes": n, "features": F,
+               "chunk": kernels.hub_chunk(), "hubs": plans["hub_route"].H, "hub_chunks": plans["hub_route"].chunks,
+               "windows": a.windows, "steps_per_window": a.steps}
+        for name, v in ms.items():
+            out[f"{name}_ms"] = [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]  # median, min, max
+        print(json.dumps(out), flush=True)
+        kernels._SAG_GROUPS.clear()
 
 
 def _no_grad(torch, pooler, x, ei, batch):

@@ -42,7 +42,9 @@ def _sync():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("small", "large"), default="small")
+    ap.add_argument("--workload", choices=("small", "large", "hub_sweep"), default="small")
+    ap.add_argument("--degrees", type=int, nargs="*", default=[1024, 4096, 16384, 65536, 524293],
+                    help="hub_sweep: the in-degrees of the one hub, a JSON line each")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
@@ -56,6 +58,8 @@ def main():
         raise SystemExit("bench_sag.py measures on the GPU: none found")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if a.workload == "hub_sweep":
+        return hub_sweep(a, torch, kernels, SAGPooling, dev)
     g = torch.Generator().manual_seed(0)
     if a.workload == "small":
         F = 32
@@ -159,6 +163,68 @@ def main():
     out["aggregate_bytes_counted"] = aggregate_bytes
     out["aggregate_share_of_hbm_peak"] = round(aggregate_bytes / (med["native_aggregate"] * 1e-3) / HBM_PEAK, 4)
     print(json.dumps(out))
+
+
+def hub_sweep(a, torch, kernels, SAGPooling, dev):
+    """One JSON line per hub in-degree: 65536 nodes, 524288 random edges and ``degree`` more into node 7, F = 128.  The
+    same list as two tensor objects: the index of one is built with the plan suppressed (the lane-per-node aggregate),
+    the index of the other with the threshold just below the degree (the hub route), so one run times one-wave, hub
+    route and composed form in alternating windows."""
+    F, n, e = 128, 65536, 524288
+    sag = SAGPooling(in_channels=F).to(dev)
+    rel, root = sag.gnn.lin_rel, sag.gnn.lin_root
+    for degree in a.degrees:
+        g = torch.Generator().manual_seed(0)
+        ei = torch.cat([torch.randint(0, n, (2, e), generator=g),
+                        torch.stack([torch.randint(0, n, (degree,), generator=g), torch.full((degree,), 7)])], 1).to(dev)
+        x = torch.randn(n, F, generator=g).to(dev)
+        lists = {"one_wave": ei, "hub_route": ei.clone()}
+
+        def scorer(adj):
+            with torch.no_grad():
+                return sag.gnn.score(x, adj, True)
+
+        def composed_scorer():
+            with torch.no_grad():
+                agg = torch.zeros_like(x).index_add_(0, ei[1], x[ei[0]])
+                return torch.tanh(rel(agg) + root(x)).view(-1)
+
+        def forward(adj):
+            with torch.no_grad():
+                return sag(x=x, adj=adj)
+
+        def step(adj):
+            sag.zero_grad(set_to_none=True)
+            (sag(x=x, adj=adj).x ** 2).sum().backward()
+
+        runs = {"composed_scorer": composed_scorer}
+        for k in lists:
+            runs.update({f"{k}_scorer": lambda k=k: scorer(lists[k]), f"{k}_forward": lambda k=k: forward(lists[k]),
+                         f"{k}_train_step": lambda k=k: step(lists[k])})
+        keep = kernels.HUB_MIN_GROUP
+        for name, fn in runs.items():  # the first call builds the indices: with or without the plan
+            kernels.HUB_MIN_GROUP = degree - 1 if name.startswith("hub_route") else 1 << 40
+            for _ in range(max(1, a.warmup)):
+                fn()
+        kernels.HUB_MIN_GROUP = keep
+        plans = {k: kernels.sag_edge_group(v, n).hub for k, v in lists.items()}
+        assert plans["one_wave"] is None and plans["hub_route"] is not None and plans["hub_route"].H >= 1
+        ms = {name: [] for name in runs}
+        for _ in range(a.windows):
+            for name, fn in runs.items():
+                _sync()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                _sync()
+                ms[name].append((time.perf_counter() - t0) / a.steps * 1e3)
+        out = {"workload": "hub_sweep", "hub_in_degree": degree, "num_nodes": n, "features": F,
+               "chunk": kernels.hub_chunk(), "hubs": plans["hub_route"].H, "hub_chunks": plans["hub_route"].chunks,
+               "windows": a.windows, "steps_per_window": a.steps}
+        for name, v in ms.items():
+            out[f"{name}_ms"] = [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]  # median, min, max
+        print(json.dumps(out), flush=True)
+        kernels._SAG_GROUPS.clear()
 
 
 if __name__ == "__main__":

@@ -6,6 +6,8 @@
 // The sums run in edge-list order inside a node over a by-destination index (no float atomics: the score decides a
 // top-k, the same bits on every call).  The backward is the same aggregate over the by-source index plus one pass that
 // writes dX = g_q (x) w_root + g_p (x) w_rel (sag_score_bwd_x_kernel).
+// A node with very many in-edges would hold its one lane for the whole walk: the host gives such groups to the chunked
+// hub route (hub_walk.hip) and sag_aggregate_kernel the list without them.
 #include "common.h"
 
 namespace tgp {

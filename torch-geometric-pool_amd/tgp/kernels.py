@@ -45,7 +45,7 @@ class AssignIndex:
     assignment order).  A function of the SelectOutput only, so SelectOutput caches it."""
 
     __slots__ = ("_row_ptr", "perm", "nnz", "num_targets", "_device", "pack", "pack_key", "member_directory",
-                 "member_directory_key", "_max_members")
+                 "member_directory_key", "_max_members", "hub")
 
     def __init__(self, row_ptr: Optional[Tensor], perm: Optional[Tensor], nnz: int, num_targets: int, device=None):
         # row_ptr None: exactly one assignment per target (TopK, NDP) -- the table is arange and the Reduce kernel
@@ -70,6 +70,8 @@ class AssignIndex:
         self.member_directory = None
         self.member_directory_key = None
         self._max_members = 1 if row_ptr is None else None
+        # the hub plan of an edge-group index (:func:`build_hub_plan`), None when no group is long enough to have one
+        self.hub = None
         self._device = perm.device if perm is not None else (row_ptr.device if row_ptr is not None else
                                                               torch.device(device))
 
@@ -4099,12 +4101,77 @@ def sag_edge_group(edge_index: Tensor, num_nodes: int, by_destination: bool = Tr
             grp = AssignIndex(ptr, None, E, num_nodes)
         else:
             grp = edge_group(edge_index, num_nodes, by_destination=by_destination)
+    grp.hub = build_hub_plan(grp)  # with the index: warm calls read nothing
     if not torch.cuda.is_current_stream_capturing():
         if memo is None:
             memo = {}
             _SAG_GROUPS.put(edge_index, memo)
         memo[key] = grp
     return grp
+
+
+# ------------------------------------------------------------------------- the hub route (csrc/hub_walk.hip)
+HUB_MIN_GROUP = 4096  # a group with MORE entries than this is a hub: its chunks get a wave each
+
+
+def hub_chunk() -> int:
+    """Entries of one chunk of a hub group (a compile-time constant of csrc/hub_walk.hip)."""
+    return int(N.lib().tgp_hubwalk_chunk())
+
+
+class HubPlan:
+    """The hubs of an edge-group index: ``hub_ids`` int32 [H] ascending, ``chunk_ptr`` int32 [H + 1] (hub h owns chunks
+    chunk_ptr[h] .. chunk_ptr[h+1], chunk c the entries b + c C .. min(b + (c+1) C, e) of its group), ``chunks`` their
+    total and ``light``, the index over the same list with every hub group emptied (the surviving entries in order)."""
+
+    __slots__ = ("hub_ids", "chunk_ptr", "H", "chunks", "light")
+
+    def __init__(self, hub_ids: Tensor, chunk_ptr: Tensor, chunks: int, light: AssignIndex):
+        self.hub_ids, self.chunk_ptr, self.H, self.chunks, self.light = hub_ids, chunk_ptr, hub_ids.numel(), chunks, light
+
+    def args(self):
+        return N.ptr(self.hub_ids), N.ptr(self.chunk_ptr), self.H, self.chunks
+
+    def workspace(self, F: int, dev) -> Tensor:
+        return N.workspace(N.lib().tgp_hubwalk_workspace_bytes(self.chunks, F), dev)
+
+
+def build_hub_plan(grp: AssignIndex, min_group: Optional[int] = None, chunk: Optional[int] = None) -> Optional[HubPlan]:
+    """The :class:`HubPlan` of ``grp``, or None when no group has more than ``min_group`` (default ``HUB_MIN_GROUP``)
+    entries: the common case, found without a host read when the whole list is that short and with one otherwise.  Torch
+    operators on the index's own device; chunk boundaries depend on a group's length alone."""
+    mg = HUB_MIN_GROUP if min_group is None else int(min_group)
+    n = grp.num_targets
+    if grp.one_to_one or n == 0 or grp.nnz <= mg:
+        return None
+    rp = grp.row_ptr
+    lens = rp[1:] - rp[:-1]
+    if int(lens.max()) <= mg:  # the host read of the common case: one reduction, no hub
+        return None
+    hub = lens > mg
+    hub_ids = hub.nonzero().reshape(-1)
+    C = hub_chunk() if chunk is None else int(chunk)
+    chunk_ptr = torch.zeros(hub_ids.numel() + 1, dtype=torch.int32, device=rp.device)
+    chunk_ptr[1:] = torch.cumsum((lens[hub_ids] + (C - 1)) // C, 0)
+    light_ptr = torch.zeros(n + 1, dtype=torch.int32, device=rp.device)
+    light_ptr[1:] = torch.cumsum(lens.masked_fill(hub, 0), 0)
+    entry = torch.arange(grp.nnz, dtype=torch.int32, device=rp.device)
+    owner = torch.searchsorted(rp[1:].contiguous(), entry, right=True).clamp_(max=n - 1)  # the group of every entry
+    pos = entry if grp.perm is None else grp.perm[:grp.nnz]
+    light_perm = pos[~hub[owner]].to(torch.int32)
+    if light_perm.numel() == 0:
+        light_perm = torch.zeros(1, dtype=torch.int32, device=rp.device)
+    light = AssignIndex(light_ptr, light_perm.contiguous(), grp.nnz, n)
+    return HubPlan(hub_ids.to(torch.int32), chunk_ptr, int(chunk_ptr[-1]), light)
+
+
+def _hub_run(grp: AssignIndex, F: int, dev):
+    """(the index the one-wave entry runs on, the hub entry's leading arguments, its workspace: a tensor the caller
+    holds until the hub entry has been launched)."""
+    plan = grp.hub
+    if plan is None:
+        return grp, None, None
+    return plan.light, plan.args(), plan.workspace(F, dev)
 
 
 def sag_aggregate(grp: AssignIndex, src: Tensor, p: Tensor, q: Optional[Tensor] = None, bias: Optional[Tensor] = None,
@@ -4120,8 +4187,13 @@ def sag_aggregate(grp: AssignIndex, src: Tensor, p: Tensor, q: Optional[Tensor] 
     q = N.opt_f32_flat(q)
     b = N.opt_f32_flat(bias)
     out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_sag_aggregate_f32, *grp.walk(src, E), N.ptr(p), N.ptr(q), N.ptr(b), n, E, int(bool(mean)),
+    run, hub, ws = _hub_run(grp, 0, dev)
+    _checked(N.lib().tgp_sag_aggregate_f32, *run.walk(src, E), N.ptr(p), N.ptr(q), N.ptr(b), n, E, int(bool(mean)),
              int(bool(tanh)), N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_scalar_f32, *grp.walk(src, E), *hub, None, N.ptr(p), N.ptr(q), N.ptr(b), None, n, E,
+                 0, int(bool(mean)), int(bool(tanh)), N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.ptr(ws),
+                 ws.numel(), N.stream_ptr(dev))
     return (out[0], out[1]) if want_t else out[0]
 
 
@@ -4177,8 +4249,12 @@ def asap_query(grp: AssignIndex, src: Tensor, x_pool: Tensor, w_tilde: Tensor, c
                          f"c of {c.numel()} entries")
     sq = torch.empty(n, dtype=torch.float32, device=dev)
     arg = torch.empty(n, x_pool.size(1), dtype=torch.int32, device=dev) if want_arg else None
-    _checked(N.lib().tgp_asap_query_f32, *grp.walk(src, E), N.ptr(x_pool), ld, N.ptr(w_tilde), N.ptr(c), n, E,
+    run, hub, ws = _hub_run(grp, x_pool.size(1), dev)
+    _checked(N.lib().tgp_asap_query_f32, *run.walk(src, E), N.ptr(x_pool), ld, N.ptr(w_tilde), N.ptr(c), n, E,
              x_pool.size(1), N.ptr(sq), N.ptr(arg), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_query_f32, *grp.walk(src, E), *hub, N.ptr(x_pool), ld, N.ptr(w_tilde), N.ptr(c), n,
+                 E, x_pool.size(1), N.ptr(sq), N.ptr(arg), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return (sq, arg) if want_arg else sq
 
 
@@ -4190,8 +4266,12 @@ def asap_edge_dot(grp: AssignIndex, src: Tensor, g: Tensor, x: Tensor) -> Tensor
     if g.dim() != 2 or g.size(0) != n or x.size(0) != n or g.size(1) != x.size(1):
         raise ValueError(f"asap_edge_dot: g {tuple(g.shape)} and x {tuple(x.shape)} against {n} nodes")
     out = torch.empty(E, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_edge_dot_f32, *grp.walk(src, E), N.ptr(g), N.ptr(x), ld, n, E, x.size(1),
+    run, hub, _ = _hub_run(grp, 0, dev)
+    _checked(N.lib().tgp_asap_edge_dot_f32, *run.walk(src, E), N.ptr(g), N.ptr(x), ld, n, E, x.size(1),
              N.ptr(out) if E else None, N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_edge_dot_f32, *grp.walk(src, E), *hub, N.ptr(g), N.ptr(x), ld, n, E, x.size(1),
+                 N.ptr(out), N.stream_ptr(dev))
     return out
 
 
@@ -4206,9 +4286,13 @@ def asap_softmax_bwd(grp: AssignIndex, src: Tensor, alpha: Tensor, g_alpha: Tens
         raise ValueError(f"asap_softmax_bwd: alpha and g_alpha per edge ({E}), sq and sp per node ({n})")
     g_l = torch.empty(E, dtype=torch.float32, device=dev)
     g_sq = torch.empty(n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_softmax_bwd_f32, *grp.walk(src, E), N.ptr(alpha) if E else None,
+    run, hub, ws = _hub_run(grp, 0, dev)
+    _checked(N.lib().tgp_asap_softmax_bwd_f32, *run.walk(src, E), N.ptr(alpha) if E else None,
              N.ptr(g_alpha) if E else None, N.ptr(sq), N.ptr(sp), n, E, float(negative_slope),
              N.ptr(g_l) if E else None, N.ptr(g_sq), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_softmax_bwd_f32, *grp.walk(src, E), *hub, N.ptr(alpha), N.ptr(g_alpha), N.ptr(sq),
+                 N.ptr(sp), n, E, float(negative_slope), N.ptr(g_l), N.ptr(g_sq), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return g_l, g_sq
 
 
@@ -4222,8 +4306,12 @@ def asap_query_bwd(by_src: AssignIndex, dst: Tensor, argpos: Tensor, g_sq: Tenso
     if argpos.dtype != torch.int32 or tuple(argpos.shape) != (n, F) or not argpos.is_contiguous() or g_sq.numel() != n:
         raise ValueError(f"asap_query_bwd: argpos must be a contiguous int32 [{n}, {F}], g_sq [{n}]")
     out = torch.empty(n, F, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_query_bwd_f32, *by_src.walk(dst, E), N.ptr(argpos), N.ptr(g_sq), N.ptr(w_tilde), n, E, F,
+    run, hub, ws = _hub_run(by_src, F, dev)
+    _checked(N.lib().tgp_asap_query_bwd_f32, *run.walk(dst, E), N.ptr(argpos), N.ptr(g_sq), N.ptr(w_tilde), n, E, F,
              N.ptr(out), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_query_bwd_f32, *by_src.walk(dst, E), *hub, N.ptr(argpos), N.ptr(g_sq),
+                 N.ptr(w_tilde), n, E, F, N.ptr(out), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return out
 
 
@@ -4236,8 +4324,12 @@ def asap_edge_softmax(grp: AssignIndex, src: Tensor, sq: Tensor, sp: Tensor, neg
     if sq.numel() != n or sp.numel() != n:
         raise ValueError(f"asap_edge_softmax: one sq and one sp per node ({n}), got {sq.numel()} and {sp.numel()}")
     alpha = torch.empty(E, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_edge_softmax_f32, *grp.walk(src, E), N.ptr(sq), N.ptr(sp), n, E, float(negative_slope),
+    run, hub, ws = _hub_run(grp, 0, dev)
+    _checked(N.lib().tgp_asap_edge_softmax_f32, *run.walk(src, E), N.ptr(sq), N.ptr(sp), n, E, float(negative_slope),
              N.ptr(alpha) if E else None, N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_edge_softmax_f32, *grp.walk(src, E), *hub, N.ptr(sq), N.ptr(sp), n, E,
+                 float(negative_slope), N.ptr(alpha), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return alpha
 
 
@@ -4255,8 +4347,12 @@ def asap_attend(grp: AssignIndex, src: Tensor, x: Tensor, val: Optional[Tensor] 
         raise ValueError(f"asap_attend: one value per edge ({E}) and projections [3, {F}]")
     out = torch.empty(n, F, dtype=torch.float32, device=dev)
     p = None if proj is None else torch.empty(3, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_attend_f32, *grp.walk(src, E), N.ptr(val), N.ptr(x), ld, N.ptr(proj), n, x.size(0), E, F,
+    run, hub, ws = _hub_run(grp, F, dev)
+    _checked(N.lib().tgp_asap_attend_f32, *run.walk(src, E), N.ptr(val), N.ptr(x), ld, N.ptr(proj), n, x.size(0), E, F,
              N.ptr(out), N.ptr(p), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_attend_f32, *grp.walk(src, E), *hub, N.ptr(val), N.ptr(x), ld, N.ptr(proj), n,
+                 x.size(0), E, F, N.ptr(out), N.ptr(p), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return out, p
 
 
@@ -4276,8 +4372,12 @@ def asap_leconv(grp: AssignIndex, src: Tensor, p: Tensor, edge_weight: Optional[
     b1 = N.opt_f32_flat(b1)
     b3 = N.opt_f32_flat(b3)
     out = torch.empty(2 if want_t else 1, n, dtype=torch.float32, device=dev)
-    _checked(N.lib().tgp_asap_leconv_f32, *grp.walk(src, E), N.ptr(ew), N.ptr(p), N.ptr(b1), N.ptr(b3), n, E,
+    run, hub, ws = _hub_run(grp, 0, dev)
+    _checked(N.lib().tgp_asap_leconv_f32, *run.walk(src, E), N.ptr(ew), N.ptr(p), N.ptr(b1), N.ptr(b3), n, E,
              ASAP_ACTS[act], N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.stream_ptr(dev))
+    if hub is not None:
+        _checked(N.lib().tgp_hubwalk_scalar_f32, *grp.walk(src, E), *hub, N.ptr(ew), N.ptr(p), None, N.ptr(b3), N.ptr(b1),
+                 n, E, 1, 0, ASAP_ACTS[act], N.ptr(out[0]) if want_t else None, N.ptr(out[-1]), N.ptr(ws), ws.numel(), N.stream_ptr(dev))
     return (out[0], out[1]) if want_t else out[0]
 
 
