@@ -1708,6 +1708,38 @@ int tgp_maxcut_assign_round_i32(const int32_t* grp_ptr, const int32_t* grp_perm 
                                 const int32_t* label_in, int64_t N, int64_t E, int32_t* label_out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The hub route of MaxCutPooling's layer and assignment round, csrc/maxcut_hub.hip.  fp32 / int32, no float atomics, the
+ * same bits on every call.  As the tgp_hubwalk_* entries: they take the FULL index and the host plan (hub_ids [H] int32
+ * ascending, chunk_ptr [H + 1] int32, T = chunk_ptr[H], chunks of tgp_hubwalk_chunk() entries, one wave per (hub, chunk)),
+ * write the outputs of the hub nodes ONLY, and run after the one-wave entry on the light index on the same stream.
+ *   layer:        tgp_maxcut_layer_f32's h_out and z_next rows of the hubs.  A chunk leaves a partial row and an "any
+ *                 valid entry that is no self-loop" flag in ws (tgp_mchub_workspace_bytes(T, C)); per hub the records are
+ *                 folded slot s = records s, s + 16, .. ascending, then the sixteen slots in order, and the row is
+ *                 finished by the one-wave kernel's own epilogue.  The sums have this route's order, so a hub's floats
+ *                 differ from the one-wave walk's in the last bits.
+ *   assign_round: tgp_maxcut_assign_round_i32's label_out of the hubs, exactly.  K = the largest label; a label outside
+ *                 0 .. K counts nothing.  ws holds H x (K + 1) int32 counts (tgp_mchub_assign_workspace_bytes(H, K)) that
+ *                 the CALLER zeroes once; a round leaves them zero for the next one.  Integer atomics only.
+ * TGP_ERR_INVALID: a NULL input, output, plan table or workspace, an input given as the output, sizes below zero, a width
+ * outside 1 .. tgp_maxcut_max_width(), an unknown act; TGP_ERR_RANGE: N, E, H, T, C or K beyond the int32 index;
+ * TGP_ERR_WORKSPACE: ws_bytes below the query.  All are found before any HIP call.  The order of the checks: the sizes
+ * against their ranges first; then H = 0, T = 0 or N = 0 (an empty plan) is TGP_OK whatever else is handed over, nothing
+ * launched or read; then everything else.
+ * ---------------------------------------------------------------------------------- */
+size_t tgp_mchub_workspace_bytes(int64_t T, int64_t C);
+size_t tgp_mchub_assign_workspace_bytes(int64_t H, int64_t K);
+int tgp_mchub_layer_f32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* other,
+                        const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T, const float* coef,
+                        const float* dinv, const float* z, const float* bias /* NULL ok */, int64_t N, int64_t E,
+                        int64_t C, const int64_t* n_p /* NULL ok */, float delta, int act, float* h_out /* NULL ok */,
+                        const float* w_next /* NULL ok */, int64_t C_next, float* z_next /* NULL iff w_next is */,
+                        void* ws, size_t ws_bytes, void* stream);
+int tgp_mchub_assign_round_i32(const int32_t* grp_ptr, const int32_t* grp_perm /* NULL ok */, const int64_t* src,
+                               const int32_t* hub_ids, const int32_t* chunk_ptr, int64_t H, int64_t T,
+                               const int32_t* label_in, int64_t N, int64_t E, int64_t K, int32_t* label_out, void* ws,
+                               size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * EigenPooling (reference select/eigenpool_select.py, reduce/eigenpool_reduce.py, lift/eigenpool_lift.py),
  * csrc/eigenpool.hip.  The reference's pooling matrix Theta [n, K H] has at most H non-zeros per row; it is kept as
  * theta_modes [N, H] (node i's entry in mode h of its own cluster) plus the inverted index of the groups, a group being

@@ -15,47 +15,21 @@
 //   maxcut_assign_kernel     one label-propagation round: an unlabelled node takes the label most of its labelled
 //                            sources carry, duplicates counted, the lowest label on a tie
 // No float atomics; every sum has one order, fixed by the group (a slot adds its edges in group order).  One wave walks
-// a group whatever its length: there is no hub route.  A position outside [0, E) or an endpoint outside
+// a group whatever its length; the groups a host plan names as hubs are emptied from the index these kernels get and
+// served by maxcut_hub.hip (layer and assignment).  A position outside [0, E) or an endpoint outside
 // [0, N) is skipped and never dereferenced.
 #include <math.h>
 
 #include "common.h"
+#include "maxcut_row.h"  // kMaxWidth, group_of, endpoint_of, activate, the row epilogue (shared with maxcut_hub.hip)
 
 namespace tgp {
 namespace {
 
-constexpr int kMaxWidth = 64;        // widest row a layer or the tail takes
 constexpr int kTailMaxParams = 8192;  // floats of the tail's packed parameters (LDS)
 constexpr int kTailMaxLayers = 8;
 constexpr int kWgradRows = 1024;  // rows per partial sum of the weight gradient
 constexpr int kWgradTile = 16;
-
-struct Group {
-  int64_t b, e;
-};
-
-__device__ __forceinline__ Group group_of(const int32_t* __restrict__ grp_ptr, int64_t i, int64_t E) {
-  int64_t b = grp_ptr[i], e = grp_ptr[i + 1];
-  if (b < 0) b = 0;
-  if (e > E) e = E;
-  return {b, e};
-}
-
-// the other endpoint of group entry j, or -1 when the position or the endpoint is out of range
-__device__ __forceinline__ int64_t endpoint_of(const int32_t* __restrict__ grp_perm, const int64_t* __restrict__ other,
-                                                int64_t j, int64_t E, int64_t n, int64_t* pos_out) {
-  const int64_t pos = grp_perm ? static_cast<int64_t>(grp_perm[j]) : j;
-  *pos_out = pos;
-  if (static_cast<uint64_t>(pos) >= static_cast<uint64_t>(E)) return -1;
-  const int64_t r = other[pos];
-  return static_cast<uint64_t>(r) < static_cast<uint64_t>(n) ? r : -1;
-}
-
-__device__ __forceinline__ float activate(float t, int act) {
-  if (act == 1) return tanhf(t);
-  if (act == 2) return t < 0.0f ? 0.0f : t;  // a NaN stays a NaN, as torch.relu keeps it
-  return t;
-}
 
 // ---- degrees ------------------------------------------------------------------------------------------------------
 // One wave per node over the by-source group: lane l adds entries l, l + 64, ..; the lanes fold at offsets 32 .. 1.
@@ -107,16 +81,9 @@ __global__ __launch_bounds__(256) void maxcut_layer_kernel(const int32_t* __rest
                                                            int C_next, float* __restrict__ z_next) {
   constexpr int PER = 64 / G;
   __shared__ float wt[kMaxWidth * kMaxWidth];  // wt[c * C_next + o] = w_next[o * C + c]
-  if (w_next) {
-    for (int idx = threadIdx.x; idx < C * C_next; idx += 256) {
-      const int o = idx / C, c = idx - o * C;
-      wt[c * C_next + o] = w_next[idx];
-    }
-    __syncthreads();
-  }
+  stage_next_weight<256>(wt, w_next, C, C_next);
   const int lane = threadIdx.x & 63, sub = lane % G, slot = lane / G, wave = threadIdx.x >> 6;
-  const int64_t np = n_p ? n_p[0] : n;
-  const float diag = 1.0f - delta;
+  const LayerRow row{dinv, z, bias, C, n_p ? n_p[0] : n, delta, act, h_out, w_next ? wt : nullptr, C_next, z_next};
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 4 + wave; i < n; i += static_cast<int64_t>(gridDim.x) * 4) {
     const Group g = group_of(grp_ptr, i, E);
     float acc = 0.0f;
@@ -131,24 +98,7 @@ __global__ __launch_bounds__(256) void maxcut_layer_kernel(const int32_t* __rest
       }
     }
     acc = wave_sum<64, G>(acc);  // the slots: offsets 32 .. G
-    // a node without an edge has no off-diagonal entry at all: a non-finite dinv_i must not reach it through 0 * NaN
-    const bool has_edges = __ballot(any) != 0;
-    float h = 0.0f;
-    if (sub < C) {
-      float t = has_edges ? (delta * dinv[i]) * acc : 0.0f;
-      if (i < np) t = diag * z[i * C + sub] + t;
-      if (bias) t = t + bias[sub];
-      h = activate(t, act);
-      if (h_out && slot == 0) h_out[i * C + sub] = h;
-    }
-    if (w_next) {  // lane o: <h, w_next[o, :]> in channel order; channel c sits in lane c (slot 0)
-      float p = 0.0f;
-      for (int c = 0; c < C; ++c) {
-        const float hc = __shfl(h, c, 64);
-        if (lane < C_next) p = fmaf(hc, wt[c * C_next + lane], p);
-      }
-      if (lane < C_next) z_next[i * C_next + lane] = p;
-    }
+    finish_layer_row(row, i, acc, __ballot(any) != 0, lane, sub, slot);
   }
 }
 
@@ -323,13 +273,6 @@ __global__ __launch_bounds__(256) void maxcut_assign_kernel(const int32_t* __res
     cur = next;
   }
   if (lane == 0) label_out[i] = best;
-}
-
-inline int check_index_sizes(const char* what, int64_t N, int64_t E) {
-  TGP_REQUIRE(N >= 0 && E >= 0, TGP_ERR_INVALID, "%s: bad size", what);
-  TGP_REQUIRE(N < (1ll << 31) && E <= INT32_MAX, TGP_ERR_RANGE, "%s: N=%lld or E=%lld beyond the int32 index", what,
-              static_cast<long long>(N), static_cast<long long>(E));
-  return TGP_OK;
 }
 
 inline int row_blocks(int64_t n) {  // four rows per workgroup, at most 8192 workgroups (the kernels stride over the rest)

@@ -4453,6 +4453,9 @@ MAXCUT_ASSIGN_MAX_GROUP = 4096  # in-edges of one destination above which the as
 #                                  wave walks a group once per DISTINCT label among its sources (length x labels / 64 steps)
 MAXCUT_SCORE_MAX_GROUP = 4096  # the score net takes the composed form when the longest by-destination group exceeds this
 MAXCUT_SCORE_GROUP_SHARE = 256  # ... and E / this: one wave adds a group's rows in every layer
+# (both gates read the longest group ONE WAVE walks, maxcut_one_wave_group: a hub plan takes the longer ones away)
+MAXCUT_ASSIGN_HUB_WS_BYTES = 64 << 20  # 64 MiB: the hub rounds keep H x (K + 1) int32 counts, zeroed once per call and
+#                                        scanned once per round; above this the assignment takes the composed rounds
 _MAXCUT_NP = TensorMemo(16)  # edge_index -> one device int64: the list's largest endpoint + 1 (0 for an empty list)
 _MAXCUT_NP_HOST = TensorMemo(16)  # edge_index -> the same number on the host (read once, for a call without a batch vector)
 _MAXCUT_ONE_GRAPH_PTR: dict = {}  # (n, device) -> the offsets [0, n] of a single graph (the loss without a batch vector)
@@ -4508,10 +4511,24 @@ def maxcut_score_has_hub(edge_index: Tensor, num_nodes: int) -> bool:
     (profiles/maxcut_forward.txt): the wave adds about one row per 0.23 us and layer, the composed form costs about
     2.2 ns per edge and layer stack of four, so the two meet near a group of E / 400 edges; the gate stands at
     ``max(MAXCUT_SCORE_MAX_GROUP, E / MAXCUT_SCORE_GROUP_SHARE)``.  The longest group is remembered with the index (one
-    host read on a list's first sight)."""
-    longest = max(sag_edge_group(edge_index, num_nodes, by_destination=True).max_members,  # the forward's walks
-                  sag_edge_group(edge_index, num_nodes, by_destination=False).max_members)  # the backward's
+    host read on a list's first sight).  Groups above ``HUB_MIN_GROUP`` never reach that wave (the hub plan sends them to
+    csrc/maxcut_hub.hip, which wins at every measured length), so the gate reads :func:`maxcut_one_wave_group` and does
+    not fire at the shipped constants."""
+    longest = max(maxcut_one_wave_group(sag_edge_group(edge_index, num_nodes, by_destination=True)),  # the forward's walks
+                  maxcut_one_wave_group(sag_edge_group(edge_index, num_nodes, by_destination=False)))  # the backward's
     return longest > max(MAXCUT_SCORE_MAX_GROUP, edge_index.size(1) // MAXCUT_SCORE_GROUP_SHARE)
+
+
+def maxcut_one_wave_group(grp: AssignIndex) -> int:
+    """The longest group of ``grp`` that ONE wave still walks: with a hub plan the groups above ``HUB_MIN_GROUP`` go to
+    the chunked route (csrc/maxcut_hub.hip), so the one-wave kernels meet nothing longer than that."""
+    return grp.max_members if grp.hub is None else min(grp.max_members, HUB_MIN_GROUP)
+
+
+def maxcut_assign_hub_fits(by_dst: AssignIndex, num_labels: int) -> bool:
+    """Does the hub route's count table, ``H x (num_labels + 1)`` int32, stay within ``MAXCUT_ASSIGN_HUB_WS_BYTES``?"""
+    plan = by_dst.hub
+    return plan is None or plan.H * (int(num_labels) + 1) * 4 <= MAXCUT_ASSIGN_HUB_WS_BYTES
 
 
 def maxcut_degree(by_src: AssignIndex, edge_index: Tensor, edge_weight: Optional[Tensor] = None, want_coef: bool = True,
@@ -4564,9 +4581,15 @@ def maxcut_layer(grp: AssignIndex, other: Tensor, coef: Optional[Tensor], dinv: 
     Cn = 0 if w_next is None else w_next.size(0)
     h = torch.empty(n, C, dtype=torch.float32, device=dev) if want_h else None
     zn = torch.empty(n, Cn, dtype=torch.float32, device=dev) if w_next is not None else None
-    _checked(N.lib().tgp_maxcut_layer_f32, *grp.walk(other, E), N.ptr(coef) if E else None, N.ptr(dinv), N.ptr(z),
-             N.ptr(bias), n, E, C, N.ptr(n_p), float(delta), MAXCUT_ACTS[act], N.ptr(h), N.ptr(w_next), Cn, N.ptr(zn),
-             N.stream_ptr(dev))
+    plan = grp.hub
+    run = grp if plan is None else plan.light
+    row = (N.ptr(coef) if E else None, N.ptr(dinv), N.ptr(z), N.ptr(bias), n, E, C, N.ptr(n_p), float(delta),
+           MAXCUT_ACTS[act], N.ptr(h), N.ptr(w_next), Cn, N.ptr(zn))
+    _checked(N.lib().tgp_maxcut_layer_f32, *run.walk(other, E), *row, N.stream_ptr(dev))
+    if plan is not None:  # the hubs' rows, over what the run on the light index left there
+        ws = N.workspace(N.lib().tgp_mchub_workspace_bytes(plan.chunks, C), dev)
+        _checked(N.lib().tgp_mchub_layer_f32, *grp.walk(other, E), *plan.args(), *row, N.ptr(ws), ws.numel(),
+                 N.stream_ptr(dev))
     return h, zn
 
 
@@ -4632,17 +4655,28 @@ def maxcut_cut(grp: AssignIndex, other: Tensor, s: Tensor, edge_weight: Optional
     return out[0], out[1] if want_cut else None, out[2] if want_wsum else None
 
 
-def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, rounds: int) -> Tensor:
+def maxcut_assign_rounds(by_dst: AssignIndex, src: Tensor, labels: Tensor, rounds: int,
+                         num_labels: Optional[int] = None) -> Tensor:
     """``rounds`` rounds of the nearest-supernode label propagation on int32 labels [N] (1 .. K, 0 = none), launched back
-    to back on two buffers without a host wait; returns the labels after the last round."""
+    to back on two buffers without a host wait; returns the labels after the last round.  An index with a hub plan runs
+    every round twice, the one-wave kernel on the light index and the chunked one on the hubs; it needs ``num_labels``
+    = K for its count table (read from ``labels`` with one host wait when not given; see ``maxcut_assign_hub_fits``)."""
     dev = N.require_device(src, labels, by_dst.row_ptr)
     src, n, E = _asap_group("maxcut_assign_rounds", by_dst, src)
     if labels.dtype != torch.int32 or labels.numel() != n or not labels.is_contiguous():
         raise ValueError(f"maxcut_assign_rounds: labels must be a contiguous int32 [{n}]")
     cur, nxt = labels, torch.empty_like(labels)
-    fn = N.lib().tgp_maxcut_assign_round_i32
+    L, plan = N.lib(), by_dst.hub
+    run = by_dst if plan is None else plan.light
+    if plan is not None and int(rounds) > 0:
+        Kl = int(labels.max()) if num_labels is None else int(num_labels)
+        wsb = L.tgp_mchub_assign_workspace_bytes(plan.H, Kl)
+        counts = torch.zeros(max(wsb, 256), dtype=torch.uint8, device=dev)  # zeroed once: a round leaves them zero
     for _ in range(int(rounds)):
-        _checked(fn, *by_dst.walk(src, E), N.ptr(cur), n, E, N.ptr(nxt), N.stream_ptr(dev))
+        _checked(L.tgp_maxcut_assign_round_i32, *run.walk(src, E), N.ptr(cur), n, E, N.ptr(nxt), N.stream_ptr(dev))
+        if plan is not None:
+            _checked(L.tgp_mchub_assign_round_i32, *by_dst.walk(src, E), *plan.args(), N.ptr(cur), n, E, Kl, N.ptr(nxt),
+                     N.ptr(counts), counts.numel(), N.stream_ptr(dev))
         cur, nxt = nxt, cur
     return cur
 

@@ -14,8 +14,9 @@ row sums by source without self-loops and ``dinv = deg^-1/2`` (inf -> 0):
 Device float32 inputs with an int64 ``[2, E]`` list take the native route (``tgp.functions.maxcut_score`` /
 ``maxcut_loss``, ``MaxCutSelect.assign``), which forms neither ``P`` nor anything of size ``E x C``.  Host
 tensors, other dtypes, sparse connectivity, a width above the kernels' limit, an activation the kernels do not know, an
-``edge_weight`` that requires grad and a list with a hub (``kernels.maxcut_score_has_hub``) take the composed form with
-the same results.
+``edge_weight`` that requires grad and a list whose longest one-wave group passes ``kernels.maxcut_score_has_hub`` take
+the composed form with the same results.  A node with more than ``kernels.HUB_MIN_GROUP`` edges in a group is a hub:
+its group is cut into chunks with a wave each (csrc/maxcut_hub.hip), so a power-law graph stays on the native route.
 """
 from __future__ import annotations
 
@@ -91,7 +92,7 @@ class MaxCutScoreNet(torch.nn.Module):
             return False
         if not K.maxcut_tail_fits(self.mp_convs[-1].out_channels, list(self.mlp) + [self.final_layer]):
             return False
-        # a hub: one wave would add its whole group in every layer, the composed form's atomics spread it
+        # a group too long for one wave that no hub plan took away (none at the shipped constants)
         return not K.maxcut_score_has_hub(edge_index, x.size(0))
 
     def forward(self, x: Tensor, edge_index, edge_weight: Optional[Tensor] = None) -> Tensor:
@@ -143,8 +144,10 @@ class MaxCutSelect(TopkSelect):
         """``so.assign_all_nodes(adj=edge_index, weight=weight, max_iter=, batch=, closest_node_assignment=True)``.  A
         device int64 list runs the propagation rounds natively: int32 labels on two buffers, ``max_iter`` launches without
         a host wait in between (a round with nothing to do changes nothing), then one wait for "all assigned"; leftovers
-        take ``get_random_map_mask`` and the relabelling is the composed routine's.  A list with a destination of more
-        than ``kernels.MAXCUT_ASSIGN_MAX_GROUP`` in-edges takes the composed routine."""
+        take ``get_random_map_mask`` and the relabelling is the composed routine's.  Destinations with more than
+        ``kernels.HUB_MIN_GROUP`` in-edges run on the chunked hub route (csrc/maxcut_hub.hip).  A list whose longest
+        one-wave group exceeds ``kernels.MAXCUT_ASSIGN_MAX_GROUP``, or whose hubs' count table exceeds
+        ``kernels.MAXCUT_ASSIGN_HUB_WS_BYTES``, takes the composed routine."""
         max_iter = self.max_iter if max_iter is None else max_iter
         kept, n = so.node_index, so.num_nodes
         if not (isinstance(edge_index, Tensor) and not edge_index.is_sparse and edge_index.is_cuda
@@ -160,14 +163,15 @@ class MaxCutSelect(TopkSelect):
             raise ValueError(f"Weight tensor size ({weight.size(0)}) must match the number of nodes ({n})")
         dev = edge_index.device
         by_dst = K.sag_edge_group(edge_index, n, by_destination=True)
-        if by_dst.max_members > K.MAXCUT_ASSIGN_MAX_GROUP:
-            # a hub: the one wave of its group would walk it once per distinct label
+        if (K.maxcut_one_wave_group(by_dst) > K.MAXCUT_ASSIGN_MAX_GROUP
+                or not K.maxcut_assign_hub_fits(by_dst, kept.numel())):
+            # a group one wave would walk once per distinct label, or hubs whose count table is too large
             return so.assign_all_nodes(adj=edge_index, weight=weight, max_iter=max_iter, batch=batch,
                                        closest_node_assignment=True)
         labels = torch.zeros(n, dtype=torch.int32, device=dev)
         labels[kept] = torch.arange(1, kept.numel() + 1, dtype=torch.int32, device=dev)
         row, _ = K._edge_rows(edge_index)
-        labels = K.maxcut_assign_rounds(by_dst, row, labels, max_iter)
+        labels = K.maxcut_assign_rounds(by_dst, row, labels, max_iter, kept.numel())
         mask = labels > 0
         target = kept[(labels.to(torch.long) - 1).clamp_(min=0)]
         if not bool(mask.all()):  # the one wait
