@@ -867,6 +867,36 @@ int tgp_bnpool_rec_bwd_f32(const float* T, const float* S, const float* A, const
                            const float* stats, int64_t B, int64_t N, int64_t K, float* P, float* Q, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * BN-Pool's sampled-edge reconstruction loss (unbatched mode: poolers/bnpool.py get_sparse_rec_loss,
+ * utils/losses.py:1520-1562) over a positive list P and a negative list Q, each with its own edge-group index
+ * (offsets int32 [N + 1], positions int32 or NULL = the identity, as tgp_sag_aggregate_f32 takes them) and never
+ * concatenated.  S, T = S K [N,K] contiguous float32, 1 <= K <= tgp_bnpool_max_clusters().  For an edge e = (u, v):
+ *   l_e = <T[u], S[v]>,  bce_e = max(l, 0) - l y + log1p(exp(-|l|)),  y = 1 on P and 0 on Q,  d_e = sigmoid(l_e) - y
+ *
+ * tgp_bnedge_fwd_f32 (by-source indices, p_dst / q_dst the destination rows): node_loss[u] = sum of bce_e over u's
+ *   group in P and then its group in Q, each in the index's order; d_p [Ep] / d_q [En] (NULL: not wanted) get d_e at
+ *   the edge's own position.  One launch, nothing of size E x K, no float atomics.
+ * tgp_bnedge_bwd_f32: with c [num_graphs] and the graph of an edge = batch[its source] (batch NULL: graph 0),
+ *   dT[u] = sum_{e out of u} c d_e S[v_e] (by-source indices) and, unless dSv is NULL, dSv[v] = sum_{e into v} c d_e T[u_e]
+ *   (by-destination indices pd_* / qd_*, p_src / q_src the source rows), every row written once by its owner, the sums
+ *   in the indices' order, P's group first.  The caller forms dS = dSv + dT K^T and dK = S^T dT.
+ * status (one device word, cleared by the call): bit 0 (forward) / 1 (by source) / 2 (by destination) is set when an
+ *   edge position outside its list, an endpoint outside [0, N) or a graph id outside [0, num_graphs) was met; such an
+ *   edge contributes nothing and is never dereferenced.
+ * ---------------------------------------------------------------------------------- */
+int tgp_bnedge_fwd_f32(const float* S, const float* T, int64_t N, int64_t K, const int32_t* p_ptr,
+                       const int32_t* p_perm /* NULL ok */, const int64_t* p_dst, int64_t Ep, const int32_t* q_ptr,
+                       const int32_t* q_perm /* NULL ok */, const int64_t* q_dst, int64_t En, float* node_loss,
+                       float* d_p /* NULL ok */, float* d_q /* NULL ok */, uint32_t* status, void* stream);
+int tgp_bnedge_bwd_f32(const float* S, const float* T, int64_t N, int64_t K, const int64_t* batch /* NULL ok */,
+                       const float* c, int64_t num_graphs, const int32_t* p_ptr, const int32_t* p_perm /* NULL ok */,
+                       const int64_t* p_dst, int64_t Ep, const int32_t* q_ptr, const int32_t* q_perm /* NULL ok */,
+                       const int64_t* q_dst, int64_t En, const int32_t* pd_ptr, const int32_t* pd_perm /* NULL ok */,
+                       const int64_t* p_src, const int32_t* qd_ptr, const int32_t* qd_perm /* NULL ok */,
+                       const int64_t* q_src, const float* d_p, const float* d_q, float* dT, float* dSv /* NULL ok */,
+                       uint32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * AsymCheegerCut's auxiliary losses (poolers/asym_cheeger_cut.py, utils/losses.py:503-550, 780-1010):
  *   totvar[b]  = sum_ij a_ij ||s_i - s_j||_1 / (2 E_b),  E_b clamped to >= 1
  *   balance[b] = (n (k-1) - sum_ik rho(s_ik - q_k)) / (n (k-1)),  q_k the idx-th largest entry of column k among the n

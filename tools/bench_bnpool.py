@@ -6,11 +6,19 @@ composed form that multiplies them out: the same inputs, the same timing as benc
     python tools/bench_bnpool.py --pooler bnpool   --workload loss_c2       # the reconstruction loss alone, native
     python tools/bench_bnpool.py --pooler composed --workload loss_c2       # the same loss as fp32 torch ops on the device
     ... --backward                                                          # forward + backward to S and K
+    python tools/bench_bnpool.py --pooler bnpool --workload edge_small      # unbatched mode: native against composed
 
 Workloads:
   c2          dense padded inference, B = 32 graphs x N = 1024 nodes, K = 128, F = 64 (adjacency 1 % dense)
   loss_c2     the reconstruction loss alone on the c2 adjacency, S = stick-breaking of seeded sticks, asymmetric K
   loss_small  the same on 2048 graphs of 20-60 nodes densified to [2048,60,60] with their mask, K = 20
+  edge_small  the unbatched mode (sampled-edge loss, csrc/bnpool_edge.hip) on 2048 graphs of 20-60 nodes, K = 20, F = 32
+  edge_large  the same on one graph of N = 1 M nodes and E = 10 M edges, K = 32, F = 32, as many non-edges as edges
+  edge_sweep  the loss alone on 1, 2, 4, .. 256 graphs of 20-60 nodes: where the native route starts to pay
+              (utils.losses.BNPOOL_EDGE_MIN_EDGES comes from it)
+              edge_small and edge_large print four lines -- the loss alone (forward; forward + backward), the whole unbatched forward and the
+              training step -- each native against the composed expression in alternating windows of one process.  The
+              loss alone gets its non-edges as a NEW tensor object every step, so the native side pays their index.
 
 Prints one JSON line: the median time, the peak of allocated memory one step adds, and for the loss workloads the rate
 of the logit product (2 B N^2 K flop per product: one in the forward; the native backward forms four more, two logit
@@ -46,10 +54,107 @@ def _small_adjacency(torch, g, dev):
     return adj.to(dev), mask.to(dev)
 
 
+def _edge_inputs(torch, g, dev, large, graphs=2048):
+    if large:
+        n, K = 1 << 20, 32
+        ei = torch.randint(0, n, (2, 10_000_000), generator=g)
+        return ei.to(dev), None, n, K
+    sizes = torch.randint(20, 61, (graphs,), generator=g)
+    off = torch.cumsum(sizes, 0) - sizes
+    eis = []
+    for m, o in zip(sizes.tolist(), off.tolist()):
+        a = torch.triu(torch.rand(m, m, generator=g) < 4.0 / m, 1)
+        eis.append((a | a.t()).nonzero().t() + o)
+    return torch.cat(eis, 1).to(dev), torch.repeat_interleave(torch.arange(graphs), sizes).to(dev), int(sizes.sum()), 20
+
+
+def edge_workloads(a, torch, dev, graphs=2048):
+    """The four native-against-composed lines of the unbatched mode (``edge_sweep``: the two of the loss alone)."""
+    from tgp.poolers import BNPool
+    from tgp.utils import losses as L
+    g = torch.Generator().manual_seed(0)
+    ei, batch, n, K = _edge_inputs(torch, g, dev, a.workload == "edge_large", graphs)
+    F = 32
+    x = torch.randn(n, F, generator=g).to(dev)
+    S = torch.softmax(torch.randn(n, K, generator=g), -1).to(dev)
+    Km = torch.randn(K, K, generator=g).to(dev)
+    pooler = BNPool(in_channels=F, k=K, batched=False).to(dev)
+    neg = pooler.sample_negative_edges(ei, batch)
+    G = 1 if batch is None else graphs
+
+    def composed(S_, K_, pos, q, b, bs):
+        e = torch.cat([pos, q], dim=1)
+        logits = ((S_[e[0]] @ K_) * S_[e[1]]).sum(-1)
+        y = torch.cat([logits.new_ones(pos.size(1)), logits.new_zeros(q.size(1))], dim=0)
+        return L.sparse_bce_reconstruction_loss(logits, y, None if b is None else b[e[0]], bs)
+
+    def loss_step(fn, backward):
+        def step():
+            q = neg.view(2, -1)  # a new tensor object: the per-tensor memo misses, as it does for freshly drawn pairs
+            if not backward:
+                with torch.no_grad():
+                    return fn(S, Km, ei, q, batch, G)
+            s_, k_ = S.detach().requires_grad_(), Km.detach().requires_grad_()
+            fn(s_, k_, ei, q, batch, G)[0].backward()
+        return step
+
+    def pooler_step(native, train):
+        rec = (lambda s_, adj, b, bs: L.bnpool_sparse_rec_loss(s_, pooler.K, adj, pooler.sample_negative_edges(adj, b),
+                                                               b, bs)) if native else (
+            lambda s_, adj, b, bs: composed(s_, pooler.K, adj, pooler.sample_negative_edges(adj, b), b, bs))
+
+        def step():
+            pooler.get_sparse_rec_loss = rec
+            if not train:
+                with torch.no_grad():
+                    return pooler(x=x, adj=ei, batch=batch)
+            pooler.zero_grad(set_to_none=True)
+            out = pooler(x=x, adj=ei, batch=batch)
+            (out.x.sum() + sum(out.loss.values())).backward()
+        return step
+
+    lines = [("loss_forward", loss_step(L.bnpool_sparse_rec_loss, False), loss_step(composed, False)),
+             ("loss_forward_backward", loss_step(L.bnpool_sparse_rec_loss, True), loss_step(composed, True)),
+             ("pooler_forward", pooler_step(True, False), pooler_step(False, False)),
+             ("pooler_train_step", pooler_step(True, True), pooler_step(False, True))]
+    if a.workload == "edge_sweep":
+        L.BNPOOL_EDGE_MIN_EDGES = 0  # the sweep is where the threshold comes from: every size takes the native route
+        lines = lines[:2]
+    for name, native, comp in lines:
+        ms, peak = {"native": [], "composed": []}, {}
+        for tag, step in (("native", native), ("composed", comp)):
+            for _ in range(a.warmup):
+                step()
+            _sync()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step()
+            _sync()
+            peak[tag] = int(torch.cuda.max_memory_allocated() - base)
+        for _ in range(a.windows):
+            for tag, step in (("native", native), ("composed", comp)):
+                _sync()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step()
+                _sync()
+                ms[tag].append((time.perf_counter() - t0) / a.steps * 1e3)
+        med = {t: statistics.median(v) for t, v in ms.items()}
+        print(json.dumps({"workload": a.workload, "line": name, "nodes": n, "edges": ei.size(1), "non_edges": neg.size(1),
+                          "K": K, "native_ms_median": round(med["native"], 4),
+                          "composed_ms_median": round(med["composed"], 4),
+                          "composed_over_native": round(med["composed"] / med["native"], 3),
+                          "native_ms_windows": [round(v, 4) for v in ms["native"]],
+                          "composed_ms_windows": [round(v, 4) for v in ms["composed"]],
+                          "native_peak_bytes": peak["native"], "composed_peak_bytes": peak["composed"],
+                          "windows": a.windows, "steps_per_window": a.steps}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pooler", choices=("bnpool", "mincut", "composed"), required=True)
-    ap.add_argument("--workload", choices=("c2", "loss_c2", "loss_small"), default="c2")
+    ap.add_argument("--workload", choices=("c2", "loss_c2", "loss_small", "edge_small", "edge_large", "edge_sweep"),
+                    default="c2")
     ap.add_argument("--backward", action="store_true")
     ap.add_argument("--tree", default=ROOT, help="checkout whose tgp package is imported")
     ap.add_argument("--steps", type=int, default=100)
@@ -65,6 +170,12 @@ def main():
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(0)
     flop = None
+    if a.workload == "edge_sweep":  # the loss alone on 1, 2, 4, .. 256 graphs of 20-60 nodes (about 150 edges each)
+        for graphs in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+            edge_workloads(a, torch, dev, graphs)
+        return
+    if a.workload.startswith("edge_"):
+        return edge_workloads(a, torch, dev)
     if a.workload == "c2":
         B, N, K, F = 32, 1024, 128, 64
         adj = (torch.rand(B, N, N, generator=g) < 0.005)

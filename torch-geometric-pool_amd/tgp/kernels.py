@@ -2227,7 +2227,79 @@ def bnpool_rec_bwd(t: Tensor, s: Tensor, adj: Tensor, mask: Optional[Tensor], g:
     return p, q
 
 
-_ACC_TV_ROWS = 16  # rows of the adjacency per workgroup of the dense total-variation pass (csrc/asym_cheeger.hip)
+def _bnpool_edge_operands(s: Tensor, t: Tensor, lists, what: str):
+    """(device, S, T, [(edge_index rows, E)]) of the sampled-edge kernels; ``lists``: (edge_index, by-source index,
+    by-destination index or None) of the positive and of the negative list."""
+    dev = N.require_device(s, t, *(ei for ei, _, _ in lists))
+    s, t = N.f32c(s), N.f32c(t)
+    if s.dim() != 2 or t.shape != s.shape or not 1 <= s.size(1) <= bnpool_max_clusters():
+        raise ValueError(f"{what}: S {tuple(s.shape)} and T {tuple(t.shape)} are not two [N, K] with K <= "
+                         f"{bnpool_max_clusters()}")
+    rows = []
+    for ei, by_src, by_dst in lists:
+        row, col = _edge_rows(ei)
+        for grp in (by_src, by_dst):
+            if grp is not None and (grp.nnz != col.numel() or grp.num_targets != s.size(0)):
+                raise ValueError(f"{what}: an index of {grp.nnz} edges over {grp.num_targets} nodes against "
+                                 f"{col.numel()} edges and {s.size(0)} nodes")
+        rows.append((row, col, col.numel()))
+    return dev, s, t, rows
+
+
+def _bnpool_edge_status(status: Tensor, check: bool, what: str) -> Tensor:
+    if check and int(status):
+        raise ValueError(f"{what}: an edge position, an endpoint or a graph id out of range (status {int(status)})")
+    return status
+
+
+def bnpool_edge_fwd(s: Tensor, t: Tensor, pos, neg, want_d: bool = True, check: bool = False):
+    """(node_loss [N], d_p [Ep] or None, d_q [En] or None, status): BN-Pool's sampled-edge loss per source node, the
+    sum of bce(<T[u], S[v]>, y) over u's out-edges in the positive list (y = 1) and then in the negative one (y = 0),
+    and with ``want_d`` the per-edge sigmoid(l) - y the backward reads.  ``pos`` / ``neg``: (edge_index, its by-source
+    :func:`sag_edge_group`); the lists are never concatenated and nothing of size E x K is formed.  ``status``: one
+    device int32, nonzero when an out-of-range position or endpoint was skipped; ``check`` reads it and raises
+    ``ValueError`` (a host wait the hot path does not pay)."""
+    (pe, pg), (qe, qg) = pos, neg
+    dev, s, t, ((_, pcol, Ep), (_, qcol, En)) = _bnpool_edge_operands(s, t, ((pe, pg, None), (qe, qg, None)),
+                                                                       "bnpool_edge_fwd")
+    n = s.size(0)
+    node_loss = torch.empty(n, dtype=torch.float32, device=dev)
+    d_p = torch.empty(Ep, dtype=torch.float32, device=dev) if want_d else None
+    d_q = torch.empty(En, dtype=torch.float32, device=dev) if want_d else None
+    status = torch.empty((), dtype=torch.int32, device=dev)
+    _checked(N.lib().tgp_bnedge_fwd_f32, N.ptr(s), N.ptr(t), n, s.size(1), *pg.walk(pcol, Ep), Ep, *qg.walk(qcol, En),
+             En, N.ptr(node_loss), N.ptr(d_p) if Ep else None, N.ptr(d_q) if En else None, N.ptr(status),
+             N.stream_ptr(dev))
+    return node_loss, d_p, d_q, _bnpool_edge_status(status, check, "bnpool_edge_fwd")
+
+
+def bnpool_edge_bwd(s: Tensor, t: Tensor, pos, neg, d_p: Tensor, d_q: Tensor, c: Tensor,
+                    batch: Optional[Tensor] = None, want_dsv: bool = True, check: bool = False):
+    """(dT [N,K], dSv [N,K] or None, status): dT[u] = sum over u's out-edges of c d_e S[v_e] and dSv[v] = sum over v's
+    in-edges of c d_e T[u_e], c = ``c``[``batch``[source]] (``batch`` None: c[0]); every row is written once by its
+    owner, in the indices' order, the positive list first.  ``pos`` / ``neg``: (edge_index, by-source index,
+    by-destination index -- None without ``want_dsv``).  The caller forms dS = dSv + dT K^T and dK = S^T dT."""
+    (pe, pg, pgd), (qe, qg, qgd) = pos, neg
+    dev, s, t, ((prow, pcol, Ep), (qrow, qcol, En)) = _bnpool_edge_operands(s, t, (pos, neg), "bnpool_edge_bwd")
+    N.require_device(d_p, d_q, c, batch)
+    d_p, d_q, c, batch = N.f32c(d_p), N.f32c(d_q), N.f32c(c.reshape(-1)), N.opt_i64(batch)
+    n = s.size(0)
+    if d_p.numel() != Ep or d_q.numel() != En or c.numel() < 1 or (batch is not None and batch.numel() != n) or (
+            want_dsv and (pgd is None or qgd is None)):
+        raise ValueError(f"bnpool_edge_bwd: d_p [{Ep}], d_q [{En}], c [graphs], batch [{n}] and, for dSv, both "
+                         "by-destination indices")
+    d_t = torch.empty(n, s.size(1), dtype=torch.float32, device=dev)
+    d_sv = torch.empty(n, s.size(1), dtype=torch.float32, device=dev) if want_dsv else None
+    status = torch.empty((), dtype=torch.int32, device=dev)
+    none3 = (None, None, None)
+    _checked(N.lib().tgp_bnedge_bwd_f32, N.ptr(s), N.ptr(t), n, s.size(1), N.ptr(batch), N.ptr(c), c.numel(),
+             *pg.walk(pcol, Ep), Ep, *qg.walk(qcol, En), En, *(pgd.walk(prow, Ep) if want_dsv else none3),
+             *(qgd.walk(qrow, En) if want_dsv else none3), N.ptr(d_p) if Ep else None, N.ptr(d_q) if En else None,
+             N.ptr(d_t), N.ptr(d_sv), N.ptr(status), N.stream_ptr(dev))
+    return d_t, d_sv, _bnpool_edge_status(status, check, "bnpool_edge_bwd")
+
+
+_ACC_TV_ROWS = 16 # rows of the adjacency per workgroup of the dense total-variation pass (csrc/asym_cheeger.hip)
 ACC_ROUTES = ("auto", "count", "radix")
 
 

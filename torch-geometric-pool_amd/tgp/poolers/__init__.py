@@ -37,6 +37,7 @@ from ..utils.losses import (
     asym_norm_loss,
     cluster_loss,
     bnpool_rec_loss_terms,
+    bnpool_sparse_rec_loss,
     cluster_connectivity_prior_loss,
     kl_loss,
     sparse_bce_reconstruction_loss,
@@ -1430,8 +1431,9 @@ class BNPool(_DenseMLPPooling):
     Batched: the reconstruction loss reads the preprocessed dense adjacency (A^T when ``adj_transpose``) and the mask;
     float32 device tensors take the native route (utils.losses.bnpool_rec_loss_terms: the [B,N,N] logits are never
     formed, forward or backward), float64 the composed one.  Unbatched: the reference's sampled-edge loss over the edge
-    list and the pairs :meth:`sample_negative_edges` draws (the project's own sampler, utils.ops); the per-graph
-    sampled-edge count normalises ``kl`` and ``K_prior``.
+    list and the pairs :meth:`sample_negative_edges` draws (the project's own sampler, utils.ops); float32 device tensors
+    take the native route (utils.losses.bnpool_sparse_rec_loss: the two lists are walked where they lie, nothing of size
+    E x K is formed), float64 the composed one; the per-graph sampled-edge count normalises ``kl`` and ``K_prior``.
 
     With ``train_K=False`` ``K_prior`` is a float32 0-dim zero on the inputs' device (the reference hands out a host
     tensor)."""
@@ -1532,11 +1534,7 @@ class BNPool(_DenseMLPPooling):
         """(loss, sampled-edge count per graph) over the edge list and the sampled non-edges."""
         edge_index, _ = connectivity_to_edge_index(adj)
         neg_edge_index = self.sample_negative_edges(edge_index, batch)
-        all_edges = torch.cat([edge_index, neg_edge_index], dim=1)
-        logits = self.get_prob_link_logit(node_assignment, all_edges)
-        y = torch.cat([logits.new_ones(edge_index.size(1)), logits.new_zeros(neg_edge_index.size(1))], dim=0)
-        return sparse_bce_reconstruction_loss(logits, y, edges_batch_id=None if batch is None else batch[all_edges[0]],
-                                              batch_size=batch_size)
+        return bnpool_sparse_rec_loss(node_assignment, self.K, edge_index, neg_edge_index, batch, batch_size)
 
     def compute_sparse_loss(self, adj, batch: Optional[Tensor], so: SelectOutput) -> dict:
         from ..utils.ops import num_graphs_of

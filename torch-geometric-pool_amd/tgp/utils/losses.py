@@ -1056,6 +1056,102 @@ def bnpool_rec_loss_terms(S: Tensor, K_: Tensor, adj: Tensor, mask: Optional[Ten
     return _weighted_bce_terms(rec_adj, adj, mask, True) / n ** 2
 
 
+class _BNPoolEdgeRecFn(torch.autograd.Function):
+    """(loss, sampled-edge count) of BN-Pool's unbatched mode over the edge list and the sampled non-edges, one autograd
+    node; no tensor of size E x K is formed, forward or backward, and the two lists are never concatenated.
+
+    Forward: T = S K (torch.matmul), one launch that walks every source node's out-edges in both lists and leaves the
+    per-node loss sums and the per-edge sigmoid(l) - y, the segment readout for the per-graph sums, the counts from the
+    indices' row offsets.  Backward: dT by source and dSv by destination from one native call, then dS = dSv + dT K^T
+    and dK = S^T dT as small products.  No float atomics: the same input gives the same bits.
+
+    ``pos`` / ``neg``: (edge_index, by-source index, by-destination index or None); ``layout``: :func:`_flat_layout`."""
+
+    @staticmethod
+    def forward(ctx, S, Kmat, pos, neg, batch, layout):
+        _, gptr, _, max_nodes = layout
+        G = gptr.numel() - 1
+        T = torch.matmul(S, Kmat)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        node_loss, d_p, d_q, _ = K.bnpool_edge_fwd(S, T, pos[:2], neg[:2], want_d=need)
+        sums = K.segment_aggr(node_loss.view(-1, 1), K.segment_ops_mask(("sum",)), G, max_nodes, ptr=gptr)[0].view(-1)
+        if batch is None:
+            edges = pos[1].nnz + neg[1].nnz
+            count = torch.tensor(edges, device=S.device, dtype=S.dtype)
+            norm = count.view(1)
+            loss = (sums / norm).view(())
+        else:  # out-degree sums of each graph's nodes: the row offsets of both indices at the graphs' boundaries
+            off = pos[1].row_ptr[gptr] + neg[1].row_ptr[gptr]
+            count = norm = (off[1:] - off[:-1]).clamp_(min=1).to(S.dtype)
+            loss = (sums / norm).mean(dim=0)
+        if need:
+            ctx.save_for_backward(S, Kmat, d_p, d_q, norm)
+            ctx.pos, ctx.neg, ctx.batch = pos, neg, batch
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    def backward(ctx, g, _g_count):
+        S, Kmat, d_p, d_q, norm = ctx.saved_tensors
+        c = (g.to(torch.float32) / norm.numel()) / norm
+        want_ds = ctx.needs_input_grad[0]
+        d_t, d_sv, _ = K.bnpool_edge_bwd(S, torch.matmul(S, Kmat), ctx.pos, ctx.neg, d_p, d_q, c, ctx.batch,
+                                         want_dsv=want_ds)
+        dS = torch.addmm(d_sv, d_t, Kmat.t()) if want_ds else None
+        dK = torch.matmul(S.t(), d_t) if ctx.needs_input_grad[1] else None
+        return dS, dK, None, None, None, None
+
+
+def _bnpool_edge_lists(S: Tensor, edge_index: Tensor, neg_edge_index: Tensor, want_dst: bool):
+    """The two (edge_index, by-source index, by-destination index or None) of the native sampled-edge loss, or None when
+    a group of one of the indices is long enough to carry a hub plan (no chunked route for this loss yet)."""
+    out = []
+    for ei in (edge_index, neg_edge_index):
+        by_src = K.sag_edge_group(ei, S.size(0), by_destination=False)
+        by_dst = K.sag_edge_group(ei, S.size(0), by_destination=True) if want_dst else None
+        if by_src.hub is not None or (by_dst is not None and by_dst.hub is not None):
+            return None
+        out.append((ei, by_src, by_dst))
+    return out
+
+
+# Sampled edges (E' = edges + non-edges) from which the unbatched loss takes the native route.  Below it the call is
+# bound by launches and by the host reads of the non-edges' index, and the composed expression is ahead: measured on one
+# MI355X (tools/bench_bnpool.py --workload edge_sweep, profiles/bnpool_edge_forward.txt) the composed forward takes 0.14 ms
+# against 0.18 - 0.24 ms at every size up to E' = 78 736 and forward + backward is level there (0.57 against 0.54 ms); at
+# E' = 635 344 the native route is 3.1x ahead.  2^17 lies between the two, next to the interpolated crossing (1.6e5).
+BNPOOL_EDGE_MIN_EDGES = 1 << 17
+
+
+def bnpool_sparse_rec_loss(S: Tensor, K_: Tensor, edge_index: Tensor, neg_edge_index: Tensor,
+                           batch: Optional[Tensor] = None, batch_size: Optional[int] = None):
+    """(loss, sampled-edge count): BN-Pool's unbatched reconstruction loss, the binary cross entropy of the logits
+    (S[u] K) . S[v] over the edges (target 1) and the sampled non-edges (target 0), averaged per graph of the edge's
+    source and then over the graphs; the count is ``[G]`` with a batch vector and a 0-dim E' without one, as
+    :func:`sparse_bce_reconstruction_loss` hands it out.
+
+    float32 device operands with S [N,K], K at most ``kernels.bnpool_max_clusters()``, at least
+    ``BNPOOL_EDGE_MIN_EDGES`` sampled edges (and one), a sorted batch vector and no edge group beyond
+    ``kernels.HUB_MIN_GROUP`` run on the native route (:class:`_BNPoolEdgeRecFn`); everything else evaluates the
+    composed expression.  float32 host tensors raise: there is no CPU fallback."""
+    if S.dtype == torch.float32 and K_.dtype == torch.float32 and S.dim() == 2:
+        K.N.require_device(S, K_, edge_index, neg_edge_index, batch)
+        sampled = edge_index.size(1) + neg_edge_index.size(1)
+        native = sampled >= max(BNPOOL_EDGE_MIN_EDGES, 1) and 0 < S.size(1) <= K.bnpool_max_clusters() and S.size(0) > 0
+        layout = _flat_layout(S, batch) if native else None
+        if layout is not None and (batch_size is None or batch_size == layout[1].numel() - 1):
+            lists = _bnpool_edge_lists(S, edge_index, neg_edge_index, torch.is_grad_enabled() and S.requires_grad)
+            if lists is not None:
+                return _BNPoolEdgeRecFn.apply(S, K_, lists[0], lists[1], batch, layout)
+    all_edges = torch.cat([edge_index, neg_edge_index], dim=1)
+    logits = ((S[all_edges[0]] @ K_) * S[all_edges[1]]).sum(-1)
+    y = torch.cat([logits.new_ones(edge_index.size(1)), logits.new_zeros(neg_edge_index.size(1))], dim=0)
+    if batch is not None and batch_size is None:
+        batch_size = num_graphs_of(batch)
+    return sparse_bce_reconstruction_loss(logits, y, edges_batch_id=None if batch is None else batch[all_edges[0]],
+                                          batch_size=batch_size)
+
+
 # ------------------------------------------------------------------------------------------------ MaxCutPool's cut loss
 def maxcut_loss(scores: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None,
                 batch: Optional[Tensor] = None, batch_reduction: str = "mean") -> Tensor:
