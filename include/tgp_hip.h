@@ -107,6 +107,24 @@ int tgp_one_to_one_index_build(const int64_t* node_index, const int64_t* cluster
 int tgp_reduce_one_to_one_f32(const float* x, int64_t num_nodes, int64_t num_features, int64_t x_row_stride,
                               const uint64_t* pack, int has_weight, int64_t num_supernodes, float* x_pool, void* stream);
 
+/* 16-bit storage forms of A1 (csrc/sparse_half.hip): x and x_pool hold bfloat16 or float16 (`dtype`), the assignment
+ * weight stays fp32 (a 16-bit weight widens exactly).  Arithmetic is fp32 in the order of the fp32 entries -- widen after
+ * the load, product rounded before the add, ONE round-to-nearest-even at the store -- so the bytes are those of
+ * tgp_reduce_sparse_f32 / tgp_reduce_one_to_one_f32 on the widened x, rounded to `dtype`.  Every shape is taken: 16-byte
+ * loads of 8 features when F % 8 == 0, x_row_stride % 8 == 0 and x / x_pool are 16-byte aligned, one lane per feature
+ * otherwise.  A source row outside [0, num_nodes) is skipped.  The Lift is the same call with node and supernode swapped.
+ * TGP_ERR_INVALID: an unknown dtype, a NULL input or output, sizes below zero, a row stride below F; TGP_ERR_RANGE: nnz,
+ * K (or num_nodes of the packed form) >= 2^31.  All are found before any HIP call. */
+enum tgp_dtype { TGP_BF16 = 1, TGP_F16 = 2 };
+int tgp_reduce_sparse_h16(int dtype, const void* x, int64_t num_nodes, int64_t num_features, int64_t x_row_stride,
+                          const int64_t* node_index /* NULL = assignment i reads row i */,
+                          const float* weight /* may be NULL = ones */,
+                          const int32_t* row_ptr /* NULL = one assignment per supernode (nnz == K) */,
+                          const int32_t* perm /* NULL = identity */, int64_t nnz, int64_t num_supernodes,
+                          void* x_pool /* [K,F] contiguous */, void* stream);
+int tgp_reduce_one_to_one_h16(int dtype, const void* x, int64_t num_nodes, int64_t num_features, int64_t x_row_stride,
+                              const uint64_t* pack, int has_weight, int64_t num_supernodes, void* x_pool, void* stream);
+
 /* A2  Reduce.reduce_batch, sparse branch (reduce/base_reduce.py:37-41):
  *     out = arange(K); out[cluster_index[i]] = batch[node_index[i]]                      */
 int tgp_reduce_batch_i64(const int64_t* batch, const int64_t* node_index, const int64_t* cluster_index,
@@ -1686,6 +1704,23 @@ int tgp_segment_aggr_f32(const float* x, int64_t num_rows, int64_t F, int64_t ld
 int tgp_segment_aggr_bwd_f32(const float* g_out, const float* x, int64_t num_rows, int64_t F, int64_t ldx,
                              const int64_t* batch /* NULL ok */, int64_t dense_nodes, const uint8_t* mask /* NULL ok */,
                              const float* out, const int32_t* ties, const int32_t* count, int64_t G, int ops, float* dx,
+                             void* stream);
+
+/* The segment readout over 16-bit storage (csrc/sparse_half.hip): x, out, g_out and dx hold `dtype` (tgp_dtype), weight,
+ * ties and count are as above.  fp32 arithmetic in the fp32 entry's order, the same cut into row chunks (the workspace is
+ * tgp_segment_aggr_workspace_bytes: the partial records stay fp32, the fold is the fp32 fold) and one rounding at the
+ * last write: the bytes of tgp_segment_aggr_f32 / _bwd_f32 on the widened operands, rounded to `dtype`.  16-byte loads of
+ * 8 features when F % 8 == 0, ldx % 8 == 0 and the pointers are 16-byte aligned; one lane per feature otherwise.  Errors
+ * as above, plus TGP_ERR_INVALID for an unknown dtype and TGP_ERR_WORKSPACE for a workspace below the query. */
+int tgp_segment_aggr_h16(int dtype, const void* x, int64_t num_rows, int64_t F, int64_t ldx,
+                         const int64_t* ptr /* NULL ok */, int64_t dense_nodes, const uint8_t* mask /* NULL ok */,
+                         const int32_t* row_ptr /* NULL ok */, const int32_t* perm /* NULL ok */,
+                         const int64_t* node_index /* NULL ok */, const float* weight /* NULL ok */, int64_t nnz, int64_t G,
+                         int64_t max_len, int ops, void* out, int32_t* ties /* NULL ok */, int32_t* count /* NULL ok */,
+                         void* ws, size_t ws_bytes, void* stream);
+int tgp_segment_aggr_bwd_h16(int dtype, const void* g_out, const void* x, int64_t num_rows, int64_t F, int64_t ldx,
+                             const int64_t* batch /* NULL ok */, int64_t dense_nodes, const uint8_t* mask /* NULL ok */,
+                             const void* out, const int32_t* ties, const int32_t* count, int64_t G, int ops, void* dx,
                              void* stream);
 
 /* ------------------------------------------------------------------------------------

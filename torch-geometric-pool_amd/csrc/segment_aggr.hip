@@ -16,6 +16,7 @@
 // Min / max are exact, NaN wins as in torch.amax / amin, and the same pass counts the rows that attain the extreme
 // (`ties`), which is all the backward needs to split the gradient among them.
 #include "common.h"
+#include "segment_plan.h"
 
 namespace tgp {
 
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(256) void segment_aggr_kernel(SaSrc s, SaOut o, int
 // split route, second kernel: one workgroup per (group, 4 features).  SA_FOLD_PARTS threads per feature each fold a
 // contiguous run of the group's chunk records in ascending chunk order, then one thread folds the runs in ascending
 // order: a fixed order, whatever the launch.
-constexpr int SA_FOLD_PARTS = 64;
+// (SA_FOLD_PARTS: segment_plan.h)
 
 template <bool SUMS, bool MM>
 __device__ __forceinline__ void sa_fold_record(SaAcc<1>& a, float sum, float mn, int32_t cmn, float mx, int32_t cmx) {
@@ -389,7 +390,7 @@ static int sa_popcount(int v) { return __builtin_popcount(static_cast<unsigned>(
 // rows per chunk and chunks per segment; n_chunks == 1: no workspace, the items write the output themselves.  The split
 // route cuts finer than SA_CHUNK while the batch has fewer items than the device has lanes for (32 graphs of 1024 rows
 // would otherwise be 128 lane groups), down to SA_MIN_CHUNK rows, and coarser when SA_MAX_ITEMS bounds the records.
-static void sa_plan(int64_t G, int64_t F, int64_t max_len, int64_t* chunk, int64_t* n_chunks) {
+void tgp::sa_plan(int64_t G, int64_t F, int64_t max_len, int64_t* chunk, int64_t* n_chunks) {
   *chunk = max_len > 0 ? max_len : 1;
   *n_chunks = 1;
   if (max_len <= SA_CHUNK || G <= 0) return;

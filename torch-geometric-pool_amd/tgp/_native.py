@@ -115,6 +115,10 @@ HUGE_ROWS = _flags["TGP_HUGE_ROWS"]
 REDUCE_OPS = {name[len("TGP_"):].lower(): value for name, value in ENUMS["tgp_reduce_op"].items()}
 REDUCE_OPS["add"] = REDUCE_OPS["sum"]  # the reference accepts both names
 
+BF16 = ENUMS["tgp_dtype"]["TGP_BF16"]  # the storage types of the *_h16 entries
+F16 = ENUMS["tgp_dtype"]["TGP_F16"]
+H16_CODES = {torch.bfloat16: BF16, torch.float16: F16}
+
 _lib: Optional[ctypes.CDLL] = None
 
 

@@ -316,16 +316,16 @@ class _SparseLiftFn(torch.autograd.Function):
     def forward(ctx, x_pool, values, row, col, index, back_index_fn):
         ctx.save_for_backward(x_pool, values, row, col)
         ctx.back_index_fn = back_index_fn
-        return K.reduce_sparse(x_pool, col, values, index)
+        return K.reduce_rows(x_pool, col, values, index)
 
     @staticmethod
     def backward(ctx, g):
         x_pool, values, row, col = ctx.saved_tensors
         g = g.contiguous()
         gx = gv = None
-        if ctx.needs_input_grad[0]:
-            gx = K.reduce_sparse(g, row, values, ctx.back_index_fn())
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[0]:  # (half rows: the half Reduce of the half upstream gradient)
+            gx = K.reduce_rows(g, row, values, ctx.back_index_fn())
+        if ctx.needs_input_grad[1]:  # (pair_dot has no 16-bit form: half rows are widened for it)
             gv = K.pair_dot(g, row, x_pool, col) if g.dim() == 2 else (g[row] * x_pool[col]).sum(-1)
         return gx, gv, None, None, None, None
 
@@ -334,7 +334,7 @@ def sparse_lift(x_pool: Tensor, values: Tensor, row: Tensor, col: Tensor, index,
     """``index``: inverted index over ``row`` (output nodes); ``back_index_fn()``: the one over ``col``."""
     if _needs_grad(x_pool, values):
         return _SparseLiftFn.apply(x_pool, values, row, col, index, back_index_fn)
-    return K.reduce_sparse(x_pool, col, values, index)
+    return K.reduce_rows(x_pool, col, values, index)
 
 
 # ------------------------------------------------------------------------------- sparse -> padded dense
@@ -1558,13 +1558,14 @@ def lapool_assign(x: Tensor, lead) -> Tensor:
 # --------------------------------------------------------------------------------------- segment readout
 def _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, want_aux):
     """``src`` names the rows: ``("ptr", ptr, batch)``, ``("dense", nodes, mask)`` or ``("so", select_output)``."""
+    call = K.segment_aggr_h16 if K.is_half_rows(x) else K.segment_aggr  # half rows are read and written in 16 bits
     if src[0] == "ptr":
-        return K.segment_aggr(x, ops_mask, num_groups, max_len, ptr=src[1], want_aux=want_aux)
+        return call(x, ops_mask, num_groups, max_len, ptr=src[1], want_aux=want_aux)
     if src[0] == "dense":
-        return K.segment_aggr(x, ops_mask, num_groups, max_len, dense_nodes=src[1], mask=src[2], want_aux=want_aux)
+        return call(x, ops_mask, num_groups, max_len, dense_nodes=src[1], mask=src[2], want_aux=want_aux)
     so = src[1]
-    return K.segment_aggr(x, ops_mask, num_groups, max_len, index=so.assign_index(), node_index=K.N.i64c(so.node_index),
-                          weight=weight, want_aux=want_aux)
+    return call(x, ops_mask, num_groups, max_len, index=so.assign_index(), node_index=K.N.i64c(so.node_index),
+                weight=weight, want_aux=want_aux)
 
 
 class _SegmentAggrFn(torch.autograd.Function):
@@ -1584,12 +1585,12 @@ class _SegmentAggrFn(torch.autograd.Function):
         x, weight, out, ties, count = ctx.saved_tensors
         src, ops_mask = ctx.src, ctx.ops_mask
         g = g.contiguous()
+        bwd = K.segment_aggr_bwd_h16 if K.is_half_rows(x) else K.segment_aggr_bwd
         if src[0] == "ptr":
-            return (K.segment_aggr_bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, batch=src[2]),
-                    None, None, None, None, None)
+            return (bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, batch=src[2]), None, None, None, None, None)
         if src[0] == "dense":
-            return (K.segment_aggr_bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, dense_nodes=src[1],
-                                       mask=src[2]), None, None, None, None, None)
+            return (bwd(g, x, out, ties, count, ops_mask, ctx.num_groups, dense_nodes=src[1], mask=src[2]),
+                    None, None, None, None, None)
         so = src[1]
         ni, ci = so.node_index, so.cluster_index
         rows = x[ni]
@@ -1622,7 +1623,8 @@ class _SegmentAggrFn(torch.autograd.Function):
 
 
 def segment_aggr(x: Tensor, ops_mask: int, num_groups: int, max_len: int, src, weight: Optional[Tensor] = None) -> Tensor:
-    """``x`` [rows, F] float32 on the device -> [G, n_ops * F], column blocks in ``K.SEGMENT_OPS`` order."""
+    """``x`` [rows, F] on the device, float32 or half rows (``K.is_half_rows``; the gathered source of half rows has no
+    backward) -> [G, n_ops * F] in the dtype of ``x``, column blocks in ``K.SEGMENT_OPS`` order."""
     if _needs_grad(x, weight):
         return _SegmentAggrFn.apply(x, weight, ops_mask, num_groups, max_len, src)
     return _segment_aggr_call(x, weight, ops_mask, num_groups, max_len, src, False)[0]

@@ -156,6 +156,48 @@ def reduce_sparse(x: Tensor, source_index: Tensor, weight: Optional[Tensor], ind
     return out.view(-1) if squeeze else out
 
 
+def is_half_rows(x) -> bool:
+    """A [rows, F] bfloat16 / float16 device tensor whose rows are contiguous (a row-strided view included): what the
+    16-bit storage kernels (csrc/sparse_half.hip) read where it lies, without an fp32 copy."""
+    return (isinstance(x, Tensor) and x.is_cuda and not x.is_sparse and x.dim() == 2 and x.dtype in N.H16_CODES
+            and (x.size(1) <= 1 or x.stride(1) == 1) and (x.size(0) <= 1 or x.stride(0) >= x.size(1)))
+
+
+def _half_ld(x: Tensor) -> int:
+    return x.stride(0) if x.size(0) > 1 else max(x.stride(0), x.size(1))
+
+
+def reduce_sparse_h16(x: Tensor, source_index: Tensor, weight: Optional[Tensor], index: AssignIndex,
+                      identity_source: bool = False, unit_weight: bool = False) -> Tensor:
+    """:func:`reduce_sparse` of half rows (:func:`is_half_rows`), read and written in 16 bits: the bytes of
+    ``reduce_sparse(x.float(), ...).to(x.dtype)`` without the fp32 copy of ``x`` and the fp32 result.  ``weight`` is
+    handed over in fp32 (a 16-bit weight widens exactly)."""
+    dev = N.require_device(x, source_index, weight)
+    if not is_half_rows(x):
+        raise ValueError(f"reduce_sparse_h16 expects bfloat16 / float16 rows [N, F], got {x.dtype} {tuple(x.shape)}")
+    if weight is not None and weight.dtype == torch.float64:
+        raise ValueError("reduce_sparse_h16: float64 weights take the fp64 kernel (reduce_sparse)")
+    source_index = N.i64c(source_index)
+    w = N.opt_f32_flat(weight)
+    code, F = N.H16_CODES[x.dtype], x.size(1)
+    out = torch.empty(index.num_targets, F, dtype=x.dtype, device=dev)
+    if index.pack is not None and index.pack_key == (source_index.data_ptr(), 0 if w is None else w.data_ptr()):
+        _checked(N.lib().tgp_reduce_one_to_one_h16, code, N.ptr(x), x.size(0), F, _half_ld(x), N.ptr(index.pack),
+                 0 if w is None else 1, index.num_targets, N.ptr(out), N.stream_ptr(dev))
+        return out
+    fast = index._row_ptr is not None and index.nnz <= x.size(0)
+    _checked(N.lib().tgp_reduce_sparse_h16, code, N.ptr(x), x.size(0), F, _half_ld(x),
+             None if (identity_source and fast) else N.ptr(source_index), None if unit_weight else N.ptr(w),
+             N.ptr(index._row_ptr), N.ptr(index.perm), index.nnz, index.num_targets, N.ptr(out), N.stream_ptr(dev))
+    return out
+
+
+def reduce_rows(x: Tensor, source_index: Tensor, weight: Optional[Tensor], index: AssignIndex, **known) -> Tensor:
+    """The sparse Reduce / Lift in the storage type of ``x``: half rows stay 16-bit, everything else is
+    :func:`reduce_sparse`."""
+    return (reduce_sparse_h16 if is_half_rows(x) else reduce_sparse)(x, source_index, weight, index, **known)
+
+
 def one_to_one_index(node_index: Tensor, cluster_index: Tensor, weight: Optional[Tensor]) -> AssignIndex:
     """Inverted index of an assignment whose supernodes own exactly one node each (cluster_index a permutation of
     0..k-1: TopK, NDP): perm = the inverse permutation, plus the packed {source row, weight} form the Reduce kernel
@@ -4516,6 +4558,50 @@ def segment_aggr_bwd(g_out: Tensor, x: Tensor, out: Tensor, ties: Optional[Tenso
     dx = torch.empty(rows, F, dtype=torch.float32, device=dev)
     _checked(N.lib().tgp_segment_aggr_bwd_f32, N.ptr(g_out), N.ptr(x), rows, F, ld, N.ptr(batch), dense_nodes,
              N.ptr(mask), N.ptr(out), N.ptr(ties), N.ptr(count), num_groups, ops_mask, N.ptr(dx), N.stream_ptr(dev))
+    return dx
+
+
+def segment_aggr_h16(x: Tensor, ops_mask: int, num_groups: int, max_len: int, ptr: Optional[Tensor] = None,
+                     dense_nodes: int = 0, mask: Optional[Tensor] = None, index: Optional[AssignIndex] = None,
+                     node_index: Optional[Tensor] = None, weight: Optional[Tensor] = None, want_aux: bool = False):
+    """:func:`segment_aggr` of half rows (:func:`is_half_rows`): ``out`` has the dtype of ``x`` and the bytes of the
+    fp32 readout of ``x.float()`` rounded to it; the split route's partial records stay fp32."""
+    dev = N.require_device(x, ptr, mask, node_index, weight)
+    if not is_half_rows(x):
+        raise ValueError(f"segment readout (16-bit) expects bfloat16 / float16 rows, got {x.dtype} {tuple(x.shape)}")
+    ptr, node_index, weight = N.opt_i64(ptr), N.opt_i64(node_index), N.opt_f32_flat(weight)
+    mask = None if mask is None else mask.reshape(-1).contiguous()
+    if index is not None and (node_index is None or node_index.numel() != index.nnz
+                              or (weight is not None and weight.numel() != index.nnz)):
+        raise ValueError("segment readout: node_index and weight hold one entry per assignment of the index")
+    rows, F = x.shape
+    n_ops = bin(ops_mask).count("1")
+    n_mm = bin(ops_mask & ((1 << N.REDUCE_OPS["min"]) | (1 << N.REDUCE_OPS["max"]))).count("1")
+    out = torch.empty(num_groups, n_ops * F, dtype=x.dtype, device=dev)
+    ties = torch.empty(num_groups, n_mm * F, dtype=torch.int32, device=dev) if want_aux and n_mm else None
+    count = torch.empty(num_groups, dtype=torch.int32, device=dev) if want_aux else None
+    L = N.lib()
+    wsb = L.tgp_segment_aggr_workspace_bytes(num_groups, F, ops_mask, max_len)
+    ws = N.workspace(wsb, dev) if wsb else None
+    gathered = index is not None
+    _checked(L.tgp_segment_aggr_h16, N.H16_CODES[x.dtype], N.ptr(x), rows, F, _half_ld(x), N.ptr(ptr), dense_nodes,
+             N.ptr(mask), N.ptr(index._row_ptr) if gathered else None, N.ptr(index.perm) if gathered else None,
+             N.ptr(node_index), N.ptr(weight), index.nnz if gathered else 0, num_groups, max_len, ops_mask, N.ptr(out),
+             N.ptr(ties), N.ptr(count), N.ptr(ws), wsb, N.stream_ptr(dev))
+    return out, ties, count
+
+
+def segment_aggr_bwd_h16(g_out: Tensor, x: Tensor, out: Tensor, ties: Optional[Tensor], count: Tensor, ops_mask: int,
+                         num_groups: int, batch: Optional[Tensor] = None, dense_nodes: int = 0,
+                         mask: Optional[Tensor] = None) -> Tensor:
+    """dX [rows, F] of :func:`segment_aggr_h16`, in the dtype of ``x``: half ``g_out``, ``x`` and ``out`` in, one launch."""
+    dev = N.require_device(g_out, x, out, batch, mask)
+    g_out = g_out.to(x.dtype).contiguous()
+    rows, F = x.shape
+    dx = torch.empty(rows, F, dtype=x.dtype, device=dev)
+    _checked(N.lib().tgp_segment_aggr_bwd_h16, N.H16_CODES[x.dtype], N.ptr(g_out), N.ptr(x), rows, F, _half_ld(x),
+             N.ptr(batch), dense_nodes, N.ptr(mask), N.ptr(out), N.ptr(ties), N.ptr(count), num_groups, ops_mask,
+             N.ptr(dx), N.stream_ptr(dev))
     return dx
 
 

@@ -87,15 +87,21 @@ class BaseLift(Lift):
 
     def forward(self, x_pool: Tensor, so: SelectOutput = None, batch: Optional[Tensor] = None,
                 batch_pooled: Optional[Tensor] = None, **kwargs) -> Tensor:
+        m = None
+        if K.is_half_rows(x_pool) and so is not None:
+            # bf16 / fp16 rows through a sparse lift matrix: the 16-bit storage kernel (the bytes of the upcast route)
+            m = self._get_lift_matrix(so)
+            if m.is_sparse and m.dtype != torch.float64:
+                return self._lift_sparse(m, x_pool, so)
         # fp32 arithmetic; the result carries the dtype of x_pool like the reference's ATen ops would
-        out = self._forward_f32(as_compute_dtype(x_pool), so, batch, batch_pooled)
+        out = self._forward_f32(as_compute_dtype(x_pool), so, batch, batch_pooled, m)
         return like_input_dtype(out, x_pool)
 
     def _forward_f32(self, x_pool: Tensor, so: SelectOutput, batch: Optional[Tensor],
-                     batch_pooled: Optional[Tensor]) -> Tensor:
+                     batch_pooled: Optional[Tensor], m: Optional[Tensor] = None) -> Tensor:
         if batch is None and so.batch is not None:
             batch = so.batch
-        m = self._get_lift_matrix(so)
+        m = self._get_lift_matrix(so) if m is None else m
         if m.is_sparse:
             return self._lift_sparse(m, x_pool, so)
         m = as_compute_dtype(m)

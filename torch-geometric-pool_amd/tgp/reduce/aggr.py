@@ -75,6 +75,16 @@ def native_readout(x: Tensor, ops: Sequence[str], num_groups: int, max_len: int,
     """The kernel route: ``x`` [rows, F] on the device, fp32 arithmetic; the result has the dtype of ``x`` or, with
     assignment weights, the dtype the product ``x * weight`` promotes to."""
     computed = [op for op in K.SEGMENT_OPS if op in ops]
+    # min / max over segments past the chunk length (the split route) were measured slower in 16-bit storage than on the
+    # upcast route (profiles/half_forward.txt: 0.87x at N = 1M, 0.96x on the masked dense batch): they stay on it
+    slow = any(op in ("min", "max") for op in ops) and max_len > K.segment_aggr_chunk_rows()
+    if (K.is_half_rows(x) and not slow and len(set(ops)) == len(ops) and (weight is None or weight.dtype == x.dtype)
+            and not (src[0] == "so" and (x.requires_grad or (weight is not None and weight.requires_grad)))):
+        # bf16 / fp16 rows: the 16-bit storage kernel reads x and writes the result where they lie (the bytes of the
+        # upcast route below); the gathered source's composed backward stays on that route
+        w = None if weight is None else weight.float()
+        return _columns(Fn.segment_aggr(x, K.segment_ops_mask(ops), num_groups, max_len, src, weight=w), computed,
+                        list(ops))
     w = None if weight is None else weight.float()
     out = Fn.segment_aggr(as_compute_dtype(x), K.segment_ops_mask(ops), num_groups, max_len, src, weight=w)
     out = _columns(out, computed, list(ops))

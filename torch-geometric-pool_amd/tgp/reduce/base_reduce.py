@@ -56,6 +56,14 @@ class BaseReduce(Reduce):
             if batch is None and so.batch is not None:
                 batch = so.batch
             return _SparseReduceFn.apply(x, so.weight, so), self.reduce_batch(so, batch)
+        if so.s.is_sparse and K.is_half_rows(x) and so.s.dtype != torch.float64:
+            # bf16 / fp16 rows: the 16-bit storage kernels read x and write x_pool where they lie (fp32 arithmetic in
+            # the fp32 kernel's order, one rounding at the store: the bytes of the upcast route below)
+            if return_batched:
+                raise ValueError("return_batched=True is only supported for dense assignment matrices.")
+            if batch is None and so.batch is not None:
+                batch = so.batch
+            return _SparseReduceFn.apply(x, as_compute_dtype(so.weight), so), self.reduce_batch(so, batch)
         # fp32 arithmetic (the GEMM paths; sparse fp32 / half inputs); the result carries the dtype of x like the
         # reference's ATen ops would
         x_pool, batch_pool = self._forward_f32(as_compute_dtype(x), so, batch=batch, return_batched=return_batched)
@@ -99,9 +107,9 @@ class _SparseReduceFn(torch.autograd.Function):
             out = computed[0]
         else:
             # a clustering whose S has row index 0..N-1 and unit values (GraclusSelect; a cluster vector): known, not probed
-            out = K.reduce_sparse(x, so.node_index, weight, so.assign_index(),
-                                  identity_source=bool(so.__dict__.get("_identity_nodes", False)),
-                                  unit_weight=bool(so.__dict__.get("_unit_values", False)))
+            out = K.reduce_rows(x, so.node_index, weight, so.assign_index(),
+                                identity_source=bool(so.__dict__.get("_identity_nodes", False)),
+                                unit_weight=bool(so.__dict__.get("_unit_values", False)))
         ctx.so = so
         ctx.save_for_backward(x, weight)
         return out
@@ -114,9 +122,11 @@ class _SparseReduceFn(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         if ctx.needs_input_grad[0]:
             from ..lift import lift_index_of
-            gx = K.reduce_sparse(grad_out, so.cluster_index, weight, lift_index_of(so))
+            gx = K.reduce_rows(grad_out, so.cluster_index, weight, lift_index_of(so))  # (half rows: the half Lift)
         if ctx.needs_input_grad[1]:
-            if x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and grad_out.dtype == torch.float32:
+            if K.is_half_rows(x) and K.is_half_rows(grad_out):  # pair_dot has no 16-bit form: widened, as before
+                gw = K.pair_dot(x.float(), so.node_index, grad_out.float(), so.cluster_index)
+            elif x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and grad_out.dtype == torch.float32:
                 gw = K.pair_dot(x, so.node_index, grad_out, so.cluster_index)
             else:
                 gw = (x[so.node_index] * grad_out[so.cluster_index]).reshape(so.node_index.numel(), -1).sum(-1)
